@@ -10,9 +10,12 @@ Workload (BASELINE.json configs[3], the configuration the metric is quoted on; i
   `python -m torch.distributed.run` (RANK set) it is one of the ranks.
 Weights are seeded random-init (no checkpoints exist offline); data is synthetic (rendered text + noise).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including
-  "roofline":     the dominant kernel family (conv_mfma implicit-GEMM): algorithmic FLOPs / HIP-event time
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the
+line ("roofline": null); `--full` adds the measurements beyond the headline figure, each outside the timed region:
+  "value_with_deskew" / "value_with_h2d" / "value_with_decode": second timed loops over the same pages and steps
+  "roofline":     the dominant kernel family (conv_mfma implicit-GEMM): algorithmic FLOPs / HIP-event time of one extra step
   "cpu_baseline": the oracle port of the same path timed on the host cores over a bounded sample.
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (output_arrays).
 """
 import argparse
 import json
@@ -30,6 +33,8 @@ A4_H, A4_W = 2339, 1654
 MFMA_BF16_DENSE_PEAK_TFLOPS = 2500.0   # /opt/skills/guides/MI355X_MICROARCH.md, chip-level parameters (bf16 and fp16 dense alike)
 HBM_PEAK_GBS = 8000.0                  # same guide: HBM3E spec peak
 PMC_FILE = "r03_pmc_hbm.json"          # {"source_sha16": {file: sha}, "kernels": {name: {"hbm_bytes_per_launch": ...}}} (tools/pmc_to_json.py)
+DUMP_SAMPLE = 1 << 20                  # bytes of the processed pages --dump-outputs keeps (fixed seed): 4 MB of float32
+DUMP_LIMIT = 64 << 20                  # all --dump-outputs files together
 
 
 def make_pages(torch, n, seed, device):
@@ -45,6 +50,40 @@ def make_pages(torch, n, seed, device):
         noisy = base_d[i % 8].float() + torch.randn((A4_H, A4_W, 3), generator=g, device=device) * 3.0
         pages[i] = noisy.round().clamp_(0, 255).to(torch.uint8)
     return pages
+
+
+def output_arrays(dets, processed=None):
+    """--dump-outputs: the last step's results as the caller of the timed path receives them (per-page detections, global page
+    order when gathered), flattened over pages into float32 arrays, exact for every value here (box corners, code points and
+    byte values are below 2**24).  The processed pages (uint8, 540 MB per 64-page step) enter as a fixed seeded sample."""
+    import numpy as np
+    pages = dets.pages() if hasattr(dets, "pages") else [dict(quads=d.quads, texts=d.texts, scores=d.scores, det_scores=d.det_scores) for d in dets]
+    texts = [t for p in pages for t in p["texts"]]
+    cps = np.full((len(texts), max([len(t) for t in texts] + [1])), -1, np.float32)
+    for i, t in enumerate(texts):
+        cps[i, :len(t)] = [ord(c) for c in t]
+    out = {"lines_per_page": np.array([len(p["texts"]) for p in pages], np.float32),
+           "quads": np.concatenate([np.asarray(p["quads"], np.float32).reshape(-1, 8) for p in pages]),
+           "scores": np.concatenate([np.asarray(p["scores"], np.float32) for p in pages]),
+           "det_scores": np.concatenate([np.asarray(p["det_scores"], np.float32) for p in pages]),
+           "text_codepoints": cps}
+    if processed is not None:
+        import torch
+        flat = processed.reshape(-1)
+        idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), min(DUMP_SAMPLE, flat.numel())))
+        out["processed_sample"] = flat.index_select(0, torch.from_numpy(idx).to(flat.device)).float().cpu().numpy()
+    return out
+
+
+def dump_outputs(dump_dir, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError("--dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_LIMIT))
+    d = Path(dump_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(d / (name + ".npy"), a)
 
 
 def cpu_baseline(det_w, rec_w, charset, n_pages=6):
@@ -268,13 +307,17 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--pages", type=int, default=PAGES_PER_RANK, help="pages per rank per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU port")
     ap.add_argument("--det-sub-batch", type=int, default=64, help="pages per detector launch group (64: the whole step; +2 %% over 16)")
-    ap.add_argument("--deskew", action="store_true", help="run the reference's default-on de-skew step inside the MAIN timed loop too (by default it is measured by a second loop and reported as value_with_deskew)")
+    ap.add_argument("--deskew", action="store_true", help="run the reference's default-on de-skew step inside the MAIN timed loop too (otherwise --full measures it by a second loop and reports it as value_with_deskew)")
     ap.add_argument("--config", type=int, default=4, choices=[2, 3, 4, 5],
                     help="BASELINE.json configs[n-1]: 4 = end-to-end det+rec on A4 pages (the metric; default), 2 = DBNet-R18 detection only, batch 32 of "
                          "1024x1024 pages, 3 = CRNN-MV3 + CTC greedy on 512 line crops, 5 = SVTR-Base fp16 + Hindi dictionary on 512 crops")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary timed loops of config 4 (value_with_deskew, value_with_h2d)")
+    ap.add_argument("--full", action="store_true", help="config 4: also the secondary timed loops (value_with_deskew, value_with_h2d, value_with_decode), "
+                    "the roofline step and the CPU port; a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="config 4: after the timed steps, write what the last step returned (boxes, scores, "
+                    "strings as code points, a seeded sample of the processed pages) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary timed loops of config 4 (value_with_deskew, value_with_h2d)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo: CPU rehearsal, only with --dry-engine")
     ap.add_argument("--dry-engine", action="store_true", help="no GPU, fake recogniser outputs: rehearses launcher + gather on CPU")
     ap.add_argument("--seed-rank", type=int, default=-1, help="(tests) generate the pages of THIS rank (page seed = 2024 + 1000 * rank) whatever RANK says")
@@ -290,6 +333,8 @@ def main():
     # N > 1 without a launcher: become the launcher (before anything touches the GPU)
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(args))
+    if args.dump_outputs and (args.dry_engine or args.config != 4):
+        ap.error("--dump-outputs writes what the real engine computed on the end-to-end workload (config 4, no --dry-engine)")
     if args.config != 4:
         if args.dry_engine or args.share_device:
             ap.error("--config 2 / 3 / 5 are single-stage measurements on the real engine")
@@ -340,10 +385,10 @@ def main():
     def run_steps(k):
         """k steps through run_many: step i's host-side string decode (multi-GPU: its result gather, on a side stream) overlaps
         the device work of step i+1; every step's work, including the last decode / gather, is finished when this returns."""
-        dets = None
-        for d, _ in (pipe.run_many((pages for _ in range(k)), deskew=args.deskew) if not dry else pipe.run_many(pages for _ in range(k))):
-            dets = d
-        return dets
+        last = (None, None)
+        for last in (pipe.run_many((pages for _ in range(k)), deskew=args.deskew) if not dry else pipe.run_many(pages for _ in range(k))):
+            pass
+        return last
 
     def fence():
         if not dry:
@@ -353,10 +398,10 @@ def main():
         if not dry:
             torch.cuda.synchronize()
 
-    dets = run_steps(args.warmup)
+    run_steps(args.warmup)
     fence()
     t0 = time.perf_counter()
-    dets = run_steps(args.steps)
+    dets, processed = run_steps(args.steps)
     fence()
     elapsed = time.perf_counter() - t0
     if distributed:
@@ -371,10 +416,13 @@ def main():
         import zlib
         per_page = [pg["texts"] for pg in dets.pages()] if hasattr(dets, "pages") else [list(d.texts) for d in dets]
         digests = ["%08x" % zlib.crc32("\n".join(t).encode("utf-8")) for t in per_page]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, output_arrays(dets, processed))
+    del processed
 
     # ---- secondary figures of the same run (the exclusions of the headline, measured instead of described) ----
     secondary = {}
-    if not dry and not args.no_secondary:
+    if args.full and not dry and not args.no_secondary:
         def timed(fn):
             """One secondary loop.  Every rank runs the same collectives whatever happens inside fn (fn None / raising = this rank failed):
             a failure yields None on all ranks instead of a rank stuck in a barrier."""
@@ -452,7 +500,7 @@ def main():
         del dec_bufs
 
     roofline = None
-    if not dry:
+    if args.full and not dry:
         roofline = measure_roofline(eng, pipe, pages)
 
     if rank == 0:
@@ -491,7 +539,7 @@ def main():
         if dry:
             out["data"] = "DRY ENGINE (CPU rehearsal of the launcher and the gather; not a measurement)"
             out["value"] = None
-        if not args.no_cpu_baseline and world == 1 and not dry:   # the CPU port is timed at N = 1 only (13 s of host work)
+        if args.full and not args.no_cpu_baseline and world == 1 and not dry:   # the CPU port is timed at N = 1 only (13 s of host work)
             try:
                 out["cpu_baseline"] = cpu_baseline(det_w, rec_w, charset)
             except Exception as e:  # the baseline is informational; never hide the GPU number

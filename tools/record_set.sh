@@ -7,8 +7,8 @@ cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -- python3 $R/tools/pmc_target.py 64 > $O/fetch.log 2>&1 &&
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -- python3 $R/tools/pmc_target.py 64 > $O/write.log 2>&1 &&
 cd $R && python tools/pmc_to_json.py $O/pmc_hbm.json $O/fetch $O/write > $O/pmc.txt 2>&1 && cp $O/pmc_hbm.json profiles/r03_pmc_hbm.json &&
-timeout -k 10 500 python bench.py > $O/bench.log 2>&1 && tail -1 $O/bench.log > $O/bench_line.json &&
-cd /tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -- python3 $R/bench.py --no-cpu-baseline --no-secondary > $O/ks.log 2>&1 &&
+timeout -k 10 500 python bench.py --full > $O/bench.log 2>&1 && tail -1 $O/bench.log > $O/bench_line.json &&
+cd /tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -- python3 $R/bench.py --full --no-cpu-baseline --no-secondary > $O/ks.log 2>&1 &&
 cd $R && timeout -k 10 120 python tools/perf_probe.py 16 2000 1414 16 > $O/per_layer.txt 2>/dev/null &&
 for c in 2 3 5; do
   timeout -k 10 200 python bench.py --config $c > $O/c$c.log 2>&1 && tail -1 $O/c$c.log > $O/config${c}_line.json &&
