@@ -113,6 +113,85 @@ def compose_fpn_p2(wd: Dict[str, np.ndarray]):
     return np.concatenate([wc, wd["fpn.p2.w"].astype(np.float32)], axis=3)
 
 
+# Per-layer entry points: each takes the NCHW float32 input the engine's previous tap holds (nhwc_to_nchw) and returns the next
+# tensor in the same storage mode, so a single layer can be graded on the engine's own input (teacher forcing, tests/
+# test_gpu_layer_parity.py).  det_forward / rec_backbone / rec_head / svtr_backbone below are compositions of these.
+
+
+def nhwc_to_nchw(a) -> torch.Tensor:
+    """A tap (NHWC numpy, as read_tap / the taps dict hold it) -> NCHW float32 torch."""
+    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).permute(0, 3, 1, 2).contiguous()
+
+
+def det_stem_conv1(wd, x, mode="bf16"):
+    return conv_bn_act(x, wd, "stem.conv1", 2, "relu", mode=mode)
+
+
+def det_stem_conv2(wd, x, mode="bf16"):
+    return conv_bn_act(x, wd, "stem.conv2", 1, "relu", mode=mode)
+
+
+def det_stem_conv3(wd, x, mode="bf16"):
+    return conv_bn_act(x, wd, "stem.conv3", 1, "relu", mode=mode)
+
+
+def det_stem_pool(x):
+    return F.max_pool2d(x, 3, 2, 1)
+
+
+def det_block(wd, x, i: int, j: int, mode="bf16"):
+    """Basic block s{i}.b{j}: conv0 (3x3, stride 2 at the entry of stages 1-3), shortcut, conv1 + residual + relu."""
+    p = f"s{i}.b{j}"
+    stride = 2 if (i > 0 and j == 0) else 1
+    y = conv_bn_act(x, wd, p + ".conv0", stride, "relu", mode=mode)
+    if j == 0:
+        if i == 0:
+            sc = conv_bn_act(x, wd, p + ".short", 1, "none", mode=mode)
+        else:  # vd shortcut: avg-pool 2x2/s2 + 1x1, fused as a 2x2/s2 conv (taps = w/4)
+            sc = conv_bn_act(x, wd, p + ".short", 2, "none", mode=mode, pad=0)
+    else:
+        sc = x
+    return conv_bn_act(y, wd, p + ".conv1", 1, "relu", residual=sc, mode=mode)
+
+
+def det_fpn(wd, c2, c3, c4, c5, mode="bf16", compose=True):
+    """c2 .. c5 -> (p5, p4, p3, p2), each at its own resolution (64 channels)."""
+    in5 = conv_bn_act(c5, wd, "fpn.in5", 1, "none", mode=mode)
+    out4 = conv_bn_act(c4, wd, "fpn.in4", 1, "none", residual=F.interpolate(in5, scale_factor=2, mode="nearest"), mode=mode)
+    out3 = conv_bn_act(c3, wd, "fpn.in3", 1, "none", residual=F.interpolate(out4, scale_factor=2, mode="nearest"), mode=mode)
+    p5 = conv_bn_act(in5, wd, "fpn.p5", 1, "none", mode=mode)
+    p4 = conv_bn_act(out4, wd, "fpn.p4", 1, "none", mode=mode)
+    p3 = conv_bn_act(out3, wd, "fpn.p3", 1, "none", mode=mode)
+    wc = compose_fpn_p2(wd) if compose else None
+    if wc is not None:     # ONE 3x3 conv over [c2 | up2(out3)] (320 channels), fp32 accumulate, one rounding
+        cat = torch.cat([c2, F.interpolate(out3, scale_factor=2, mode="nearest")], dim=1)
+        p2 = conv_bn_act(cat, {"fpn.p2c.w": wc, "fpn.p2c.b": wd["fpn.p2.b"]}, "fpn.p2c", 1, "none", mode=mode)
+    else:
+        out2 = conv_bn_act(c2, wd, "fpn.in2", 1, "none", residual=F.interpolate(out3, scale_factor=2, mode="nearest"), mode=mode)
+        p2 = conv_bn_act(out2, wd, "fpn.p2", 1, "none", mode=mode)
+    return p5, p4, p3, p2
+
+
+def det_fuse(p5, p4, p3, p2):
+    """The 1/4-resolution concat [up8(p5), up4(p4), up2(p3), p2] (exact: nearest upsampling + concat)."""
+    return torch.cat([F.interpolate(p5, scale_factor=8, mode="nearest"),
+                      F.interpolate(p4, scale_factor=4, mode="nearest"),
+                      F.interpolate(p3, scale_factor=2, mode="nearest"), p2], dim=1)
+
+
+def det_head_conv1(wd, fuse, mode="bf16"):
+    return conv_bn_act(fuse, wd, "head.conv1", 1, "relu", mode=mode)
+
+
+def det_head_convt2(wd, y, mode="bf16"):
+    return _convt2x2(y, wd, "head.convt2", "relu", mode)
+
+
+def det_head_convt3(wd, y, mode="bf16"):
+    """-> probability map [B,1,hp,wp]."""
+    return _convt2x2(y, wd, "head.convt3", "sigmoid", mode)
+
+
 def det_forward(wd: Dict[str, np.ndarray], pages_u8: np.ndarray, hp: Optional[int] = None,
                 wp: Optional[int] = None, mode: str = "bf16", taps: Optional[dict] = None, compose: bool = True) -> np.ndarray:
     """pages [B,H,W,3] u8 -> probability map [B,hp,wp] float32 (bf16-exact in mode bf16).
@@ -128,48 +207,21 @@ def det_forward(wd: Dict[str, np.ndarray], pages_u8: np.ndarray, hp: Optional[in
             taps[name] = t.permute(0, 2, 3, 1).contiguous().numpy()  # NHWC
 
     with torch.no_grad():
-        x = conv_bn_act(x, wd, "stem.conv1", 2, "relu", mode=mode); tap("stem.conv1", x)
-        x = conv_bn_act(x, wd, "stem.conv2", 1, "relu", mode=mode); tap("stem.conv2", x)
-        x = conv_bn_act(x, wd, "stem.conv3", 1, "relu", mode=mode); tap("stem.conv3", x)
-        x = F.max_pool2d(x, 3, 2, 1); tap("stem.pool", x)
+        x = det_stem_conv1(wd, x, mode); tap("stem.conv1", x)
+        x = det_stem_conv2(wd, x, mode); tap("stem.conv2", x)
+        x = det_stem_conv3(wd, x, mode); tap("stem.conv3", x)
+        x = det_stem_pool(x); tap("stem.pool", x)
         feats = []
         for i in range(4):
             for j in range(2):
-                p = f"s{i}.b{j}"
-                stride = 2 if (i > 0 and j == 0) else 1
-                y = conv_bn_act(x, wd, p + ".conv0", stride, "relu", mode=mode)
-                if j == 0:
-                    if i == 0:
-                        sc = conv_bn_act(x, wd, p + ".short", 1, "none", mode=mode)
-                    else:  # vd shortcut: avg-pool 2x2/s2 + 1x1, fused as a 2x2/s2 conv (taps = w/4)
-                        sc = conv_bn_act(x, wd, p + ".short", 2, "none", mode=mode, pad=0)
-                else:
-                    sc = x
-                x = conv_bn_act(y, wd, p + ".conv1", 1, "relu", residual=sc, mode=mode)
-                tap(p, x)
+                x = det_block(wd, x, i, j, mode); tap(f"s{i}.b{j}", x)
             feats.append(x)
-        c2, c3, c4, c5 = feats
-        in5 = conv_bn_act(c5, wd, "fpn.in5", 1, "none", mode=mode)
-        out4 = conv_bn_act(c4, wd, "fpn.in4", 1, "none", residual=F.interpolate(in5, scale_factor=2, mode="nearest"), mode=mode)
-        out3 = conv_bn_act(c3, wd, "fpn.in3", 1, "none", residual=F.interpolate(out4, scale_factor=2, mode="nearest"), mode=mode)
-        p5 = conv_bn_act(in5, wd, "fpn.p5", 1, "none", mode=mode); tap("fpn.p5", p5)
-        p4 = conv_bn_act(out4, wd, "fpn.p4", 1, "none", mode=mode); tap("fpn.p4", p4)
-        p3 = conv_bn_act(out3, wd, "fpn.p3", 1, "none", mode=mode); tap("fpn.p3", p3)
-        wc = compose_fpn_p2(wd) if compose else None
-        if wc is not None:     # ONE 3x3 conv over [c2 | up2(out3)] (320 channels), fp32 accumulate, one rounding
-            cat = torch.cat([c2, F.interpolate(out3, scale_factor=2, mode="nearest")], dim=1)
-            p2 = conv_bn_act(cat, {"fpn.p2c.w": wc, "fpn.p2c.b": wd["fpn.p2.b"]}, "fpn.p2c", 1, "none", mode=mode)
-        else:
-            out2 = conv_bn_act(c2, wd, "fpn.in2", 1, "none", residual=F.interpolate(out3, scale_factor=2, mode="nearest"), mode=mode)
-            p2 = conv_bn_act(out2, wd, "fpn.p2", 1, "none", mode=mode)
-        tap("fpn.p2", p2)
-        fuse = torch.cat([F.interpolate(p5, scale_factor=8, mode="nearest"),
-                          F.interpolate(p4, scale_factor=4, mode="nearest"),
-                          F.interpolate(p3, scale_factor=2, mode="nearest"), p2], dim=1)
-        tap("fpn.fuse", fuse)
-        y = conv_bn_act(fuse, wd, "head.conv1", 1, "relu", mode=mode); tap("head.conv1", y)
-        y = _convt2x2(y, wd, "head.convt2", "relu", mode); tap("head.convt2", y)
-        y = _convt2x2(y, wd, "head.convt3", "sigmoid", mode)
+        p5, p4, p3, p2 = det_fpn(wd, *feats, mode=mode, compose=compose)
+        tap("fpn.p5", p5); tap("fpn.p4", p4); tap("fpn.p3", p3); tap("fpn.p2", p2)
+        fuse = det_fuse(p5, p4, p3, p2); tap("fpn.fuse", fuse)
+        y = det_head_conv1(wd, fuse, mode); tap("head.conv1", y)
+        y = det_head_convt2(wd, y, mode); tap("head.convt2", y)
+        y = det_head_convt3(wd, y, mode)
     return y[:, 0].contiguous().numpy()
 
 
@@ -197,26 +249,44 @@ def rec_normalize(crops_u8: np.ndarray, mode="bf16") -> torch.Tensor:
     return _rb(torch.from_numpy(x).permute(0, 3, 1, 2).contiguous(), mode)
 
 
+def rec_conv1(wd, x, mode="bf16"):
+    """Normalised crops (columns past a crop's width already 0) -> stem [N,8,16,160]."""
+    return conv_bn_act(x, wd, "rec.conv1", 2, "hswish", mode=mode)
+
+
+def rec_block(wd, x, i: int, mode="bf16"):
+    """MobileNetV3 block rec.b{i}: expand (1x1), depthwise (stride (s,1)), squeeze-excite, project (+ residual)."""
+    b = arch.rec_block_table()[i]
+    p = f"rec.b{b['idx']}"
+    y = conv_bn_act(x, wd, p + ".expand", 1, b["act"], mode=mode)
+    y = conv_bn_act(y, wd, p + ".dw", (b["stride_h"], 1), b["act"], mode=mode, groups=b["exp"])
+    if b["se"]:
+        s = _rb(y.mean(dim=(2, 3), keepdim=True), mode)
+        s = conv_bn_act(s, wd, p + ".se1", 1, "relu", mode=mode)
+        s = conv_bn_act(s, wd, p + ".se2", 1, "hsigmoid", mode=mode)
+        y = _rb(y * s, mode)
+    return conv_bn_act(y, wd, p + ".project", 1, "none", residual=x if b["res"] else None, mode=mode)
+
+
+def rec_conv2(wd, x, mode="bf16"):
+    return conv_bn_act(x, wd, "rec.conv2", 1, "hswish", mode=mode)
+
+
+def rec_pool(x):
+    """rec.conv2 [N,288,2,160] -> the LSTM input [N,288,1,80] (2x2 max pool; tap "rec.feat" is its [N,80,288] sequence view)."""
+    return F.max_pool2d(x, 2, 2)
+
+
 def rec_backbone(wd, x: torch.Tensor, mode="bf16", taps=None) -> torch.Tensor:
     def tap(name, t):
         if taps is not None:
             taps[name] = t.permute(0, 2, 3, 1).contiguous().numpy()
 
-    x = conv_bn_act(x, wd, "rec.conv1", 2, "hswish", mode=mode); tap("rec.conv1", x)
+    x = rec_conv1(wd, x, mode); tap("rec.conv1", x)
     for b in arch.rec_block_table():
-        p = f"rec.b{b['idx']}"
-        y = conv_bn_act(x, wd, p + ".expand", 1, b["act"], mode=mode)
-        y = conv_bn_act(y, wd, p + ".dw", (b["stride_h"], 1), b["act"], mode=mode, groups=b["exp"])
-        if b["se"]:
-            s = _rb(y.mean(dim=(2, 3), keepdim=True), mode)
-            s = conv_bn_act(s, wd, p + ".se1", 1, "relu", mode=mode)
-            s = conv_bn_act(s, wd, p + ".se2", 1, "hsigmoid", mode=mode)
-            y = _rb(y * s, mode)
-        x = conv_bn_act(y, wd, p + ".project", 1, "none", residual=x if b["res"] else None, mode=mode)
-        tap(p, x)
-    x = conv_bn_act(x, wd, "rec.conv2", 1, "hswish", mode=mode); tap("rec.conv2", x)
-    x = F.max_pool2d(x, 2, 2)
-    return x  # [N, 288, 1, 80]
+        x = rec_block(wd, x, b["idx"], mode); tap(f"rec.b{b['idx']}", x)
+    x = rec_conv2(wd, x, mode); tap("rec.conv2", x)
+    return rec_pool(x)  # [N, 288, 1, 80]
 
 
 def lstm_dir(xs: torch.Tensor, w_ih, w_hh, b, reverse: bool, mode="bf16") -> torch.Tensor:
@@ -237,16 +307,21 @@ def lstm_dir(xs: torch.Tensor, w_ih, w_hh, b, reverse: bool, mode="bf16") -> tor
     return hs
 
 
+def lstm_layer(wd, seq: torch.Tensor, layer: int, mode="bf16") -> torch.Tensor:
+    """One bidirectional LSTM layer: seq [N,T,D] -> [N,T,2H] = [forward | backward] (taps "lstm.l0" / "lstm.l1")."""
+    outs = []
+    for d, rev in (("fw", False), ("bw", True)):
+        p = f"lstm.l{layer}.{d}"
+        outs.append(lstm_dir(seq, torch.from_numpy(wd[p + ".w_ih"]), torch.from_numpy(wd[p + ".w_hh"]),
+                             torch.from_numpy(wd[p + ".b"]), rev, mode))
+    return torch.cat(outs, dim=2)
+
+
 def rec_head(wd, feat: torch.Tensor, mode="bf16"):
     """feat [N,288,1,80] -> (argmax idx [N,T] int64, max prob [N,T] f32, logits [N,T,C] f32)."""
     seq = feat.squeeze(2).permute(0, 2, 1).contiguous()  # [N,T,288]
     for layer in (0, 1):
-        outs = []
-        for d, rev in (("fw", False), ("bw", True)):
-            p = f"lstm.l{layer}.{d}"
-            outs.append(lstm_dir(seq, torch.from_numpy(wd[p + ".w_ih"]), torch.from_numpy(wd[p + ".w_hh"]),
-                                 torch.from_numpy(wd[p + ".b"]), rev, mode))
-        seq = torch.cat(outs, dim=2)
+        seq = lstm_layer(wd, seq, layer, mode)
     logits = seq @ torch.from_numpy(wd["ctc.fc.w"]).t() + torch.from_numpy(wd["ctc.fc.b"])
     mx, idx = logits.max(dim=2)
     prob = 1.0 / torch.exp(logits - mx.unsqueeze(2)).sum(dim=2)
@@ -289,6 +364,47 @@ def _svtr_mask(h, w):
     return ((ys[:, None] - ys[None, :]).abs() <= arch.SVTR_WINDOW[0] // 2) & ((xs[:, None] - xs[None, :]).abs() <= arch.SVTR_WINDOW[1] // 2)
 
 
+def svtr_embed(wd, x, mode="bf16"):
+    """Normalised crops [N,3,32,320] -> tokens [N,640,D0]: patch embedding (two 3x3/s2 convs, GELU) + positional embedding."""
+    x = conv_bn_act(x, wd, "svtr.pe1", 2, "gelu", mode=mode)
+    x = conv_bn_act(x, wd, "svtr.pe2", 2, "gelu", mode=mode)                 # [N,D0,8,80]
+    n, c, h, w = x.shape
+    t = x.permute(0, 2, 3, 1).reshape(n, h * w, c)
+    return _rb(t + _rb(torch.from_numpy(wd["svtr.pos.w"]), mode), mode)
+
+
+def svtr_merge(wd, t, stage: int, h: int, w: int, mode="bf16"):
+    """Height merging after stage `stage`: tokens [N,h*w,C] -> conv 3x3 stride (2,1) + LayerNorm -> [N,(h/2)*w,C']."""
+    n, _, c = t.shape
+    img = t.reshape(n, h, w, c).permute(0, 3, 1, 2)
+    img = conv_bn_act(img, wd, f"svtr.sub{stage}", (2, 1), "none", mode=mode)
+    n, c, h, w = img.shape
+    return _layernorm(img.permute(0, 2, 3, 1).reshape(n, h * w, c), wd, f"svtr.sub{stage}.ln", mode)
+
+
+def svtr_block(wd, t, idx: int, mode="bf16"):
+    """Mixing block svtr.b{idx} on tokens [N,h*w,C] (grid, heads, local / global from arch.svtr_block_table of the weights)."""
+    b = arch.svtr_block_table(arch.svtr_config(wd))[idx]
+    n, h, w, c = t.shape[0], b["h"], b["w"], t.shape[2]
+    p, heads = f"svtr.b{idx}", b["heads"]
+    hd = c // heads
+    qkv = _linear(t, wd, p + ".qkv", mode=mode).reshape(n, h * w, 3, heads, hd).permute(2, 0, 3, 1, 4)   # [3,N,heads,T,hd]
+    sc = (qkv[0] @ qkv[1].transpose(-1, -2)) * np.float32(hd ** -0.5)
+    if b["local"]:
+        sc = sc.masked_fill(~_svtr_mask(h, w), float("-inf"))
+    att = _rb((torch.softmax(sc, dim=-1) @ qkv[2]).permute(0, 2, 1, 3).reshape(n, h * w, c), mode)
+    t = _layernorm(_linear(att, wd, p + ".proj", residual=t, mode=mode), wd, p + ".ln1", mode)
+    m = _linear(t, wd, p + ".fc1", act="gelu", mode=mode)
+    return _layernorm(_linear(m, wd, p + ".fc2", residual=t, mode=mode), wd, p + ".ln2", mode)
+
+
+def svtr_last(wd, t, h: int, w: int, mode="bf16"):
+    """Tokens [N,h*w,C2] -> sequence [N,w,192]: mean over the h remaining rows (rounded), 1x1 conv + hswish."""
+    n, _, c = t.shape
+    pooled = _rb(t.reshape(n, h, w, c).mean(dim=1), mode)                     # [N,80,C2]
+    return _linear(pooled, wd, "svtr.last", act="hswish", mode=mode)
+
+
 def svtr_backbone(wd, x, mode="bf16", taps=None):
     """x [N,3,32,320] normalised -> sequence [N,80,192].  Variant (Tiny / Base) = wd["svtr.config"] (arch.svtr_config)."""
     def tap(name, t):
@@ -296,31 +412,16 @@ def svtr_backbone(wd, x, mode="bf16", taps=None):
             taps[name] = t.contiguous().numpy()
 
     cfg = arch.svtr_config(wd)
-    x = conv_bn_act(x, wd, "svtr.pe1", 2, "gelu", mode=mode)
-    x = conv_bn_act(x, wd, "svtr.pe2", 2, "gelu", mode=mode)                 # [N,D0,8,80]
-    n, c, h, w = x.shape
-    t = x.permute(0, 2, 3, 1).reshape(n, h * w, c)
-    t = _rb(t + _rb(torch.from_numpy(wd["svtr.pos.w"]), mode), mode); tap("svtr.embed", t)
+    t = svtr_embed(wd, x, mode); tap("svtr.embed", t)
+    h, w = arch.REC_H // 4, arch.REC_W // 4
     stage = 0
     for b in arch.svtr_block_table(cfg):
-        if b["stage"] != stage:                                               # height merging: conv 3x3 stride (2,1) + LayerNorm
-            img = t.reshape(n, h, w, c).permute(0, 3, 1, 2)
-            img = conv_bn_act(img, wd, f"svtr.sub{stage}", (2, 1), "none", mode=mode)
-            n, c, h, w = img.shape
-            t = _layernorm(img.permute(0, 2, 3, 1).reshape(n, h * w, c), wd, f"svtr.sub{stage}.ln", mode); tap(f"svtr.sub{stage}", t)
+        if b["stage"] != stage:
+            t = svtr_merge(wd, t, stage, h, w, mode); tap(f"svtr.sub{stage}", t)
+            h //= 2
             stage = b["stage"]
-        p, heads = f"svtr.b{b['idx']}", b["heads"]
-        hd = c // heads
-        qkv = _linear(t, wd, p + ".qkv", mode=mode).reshape(n, h * w, 3, heads, hd).permute(2, 0, 3, 1, 4)   # [3,N,heads,T,hd]
-        sc = (qkv[0] @ qkv[1].transpose(-1, -2)) * np.float32(hd ** -0.5)
-        if b["local"]:
-            sc = sc.masked_fill(~_svtr_mask(h, w), float("-inf"))
-        att = _rb((torch.softmax(sc, dim=-1) @ qkv[2]).permute(0, 2, 1, 3).reshape(n, h * w, c), mode)
-        t = _layernorm(_linear(att, wd, p + ".proj", residual=t, mode=mode), wd, p + ".ln1", mode)
-        m = _linear(t, wd, p + ".fc1", act="gelu", mode=mode)
-        t = _layernorm(_linear(m, wd, p + ".fc2", residual=t, mode=mode), wd, p + ".ln2", mode); tap(p, t)
-    pooled = _rb(t.reshape(n, h, w, c).mean(dim=1), mode)                     # [N,80,C2]: mean over the 2 remaining rows
-    seq = _linear(pooled, wd, "svtr.last", act="hswish", mode=mode); tap("svtr.seq", seq)
+        t = svtr_block(wd, t, b["idx"], mode); tap(f"svtr.b{b['idx']}", t)
+    seq = svtr_last(wd, t, h, w, mode); tap("svtr.seq", seq)
     return seq
 
 
