@@ -42,6 +42,21 @@ struct DeviceGuard {
     DeviceGuard _device_guard((h)->device);                                                                  \
     if (_device_guard.err != hipSuccess) return locr_fail((h), "hipSetDevice", hipGetErrorString(_device_guard.err))
 
+// an entry's last step: 0, or the HIP error recorded in the handle
+static int hip_rc(lumina_ocr* h, const char* what, hipError_t e) { return e == hipSuccess ? 0 : locr_fail(h, what, hipGetErrorString(e)); }
+
+// waits for the device, then hands every timed launch and its milliseconds to f and drops the records (and their events)
+template <class F> static int drain_launches(lumina_ocr* h, const char* what, F&& f) {
+    if (hipDeviceSynchronize() != hipSuccess) return locr_fail(h, what, "sync failed");
+    for (const LaunchRecord& r : h->launches) {
+        float t = 0.f;
+        if (hipEventElapsedTime(&t, r.e0.get(), r.e1.get()) != hipSuccess) t = 0.f;
+        f(r, t);
+    }
+    h->launches.clear();
+    return 0;
+}
+
 extern "C" {
 
 const char* lumina_ocr_version(void) { return "lumina-ocr-mi355x 0.1 (gfx950)"; }
@@ -69,12 +84,7 @@ int lumina_ocr_create(int device, lumina_ocr_t** out) {
 void lumina_ocr_destroy(lumina_ocr_t* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    for (void* p : h->owned) (void)hipFree(p);
-    if (h->ws) (void)hipFree(h->ws);
-    if (h->aux) (void)hipFree(h->aux);
-    for (int k = 0; k < 2; ++k) { if (h->jd_stage[k]) (void)hipHostFree(h->jd_stage[k]); if (h->jd_stage_ev[k]) (void)hipEventDestroy(h->jd_stage_ev[k]); }
-    for (auto& ev : h->conv_events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-    delete h;
+    delete h;   // (its device memory, pinned buffers and events are released by their owners)
 }
 
 const char* lumina_ocr_last_error(const lumina_ocr_t* h) { return h ? h->err.c_str() : "null handle"; }
@@ -120,8 +130,7 @@ int lumina_ocr_normalize(lumina_ocr_t* h, const uint8_t* img_dev, int n, int hei
                          const float shift[3], int layout_nchw, uint16_t* out_dev, void* stream) {
     if (!h || !img_dev || !out_dev || hp < height || wp < width) return locr_fail(h, "normalize", "bad arguments");
     BIND(h);
-    hipError_t e = normalize_launch(img_dev, out_dev, n, height, width, hp, wp, height, width, scale, shift, layout_nchw, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : locr_fail(h, "normalize", hipGetErrorString(e));
+    return hip_rc(h, "normalize", normalize_launch(img_dev, out_dev, n, height, width, hp, wp, height, width, scale, shift, layout_nchw, (hipStream_t)stream));
 }
 
 int lumina_ocr_det_forward(lumina_ocr_t* h, const uint8_t* pages_dev, int batch, int height, int width, int hp, int wp, uint16_t* prob_dev,
@@ -143,14 +152,12 @@ int lumina_ocr_det_postprocess(lumina_ocr_t* h, const uint16_t* prob_dev, int ba
     const int group = h->post_group;
     for (int b0 = 0; b0 < batch; b0 += group) {
         const int nb = batch - b0 < group ? batch - b0 : group;
-        const size_t need = dbpost_workspace_bytes(nb, hp, wp, max_boxes);
-        if (eng_ws_reserve(h, need)) return 1;
+        if (eng_ws_reserve(h, dbpost_workspace_bytes(nb, hp, wp, max_boxes))) return 1;
         DbPostParams p{};
         p.prob = prob_dev + (size_t)b0 * hp * wp; p.B = nb; p.Hp = hp; p.Wp = wp; p.valid_h = valid_h; p.valid_w = valid_w;
         p.thresh = thresh; p.box_thresh = box_thresh; p.unclip_ratio = unclip_ratio; p.min_size = min_size; p.max_boxes = max_boxes;
         p.boxes = boxes_dev + (size_t)b0 * max_boxes * 8; p.scores = scores_dev + (size_t)b0 * max_boxes; p.counts = counts_dev + b0;
-        hipError_t e = dbpost_launch(p, h->ws, (hipStream_t)stream);
-        if (e != hipSuccess) return locr_fail(h, "det_postprocess", hipGetErrorString(e));
+        if (hip_rc(h, "det_postprocess", dbpost_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream))) return 1;
     }
     return 0;
     API_CATCH(h)
@@ -161,8 +168,7 @@ int lumina_ocr_rec_crop(lumina_ocr_t* h, const uint8_t* pages_dev, int batch, in
     if (!h || !pages_dev || !quads_dev || !page_idx_dev || !crops_dev || !widths_dev) return locr_fail(h, "rec_crop", "null argument");
     BIND(h);
     (void)batch;
-    hipError_t e = rec_crop_launch(pages_dev, height, width, quads_dev, page_idx_dev, n_crops, crops_dev, widths_dev, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : locr_fail(h, "rec_crop", hipGetErrorString(e));
+    return hip_rc(h, "rec_crop", rec_crop_launch(pages_dev, height, width, quads_dev, page_idx_dev, n_crops, crops_dev, widths_dev, (hipStream_t)stream));
 }
 
 int lumina_ocr_rec_forward(lumina_ocr_t* h, const uint8_t* crops_dev, const int32_t* widths_dev, int n_crops, int32_t* idx_dev, float* prob_dev,
@@ -190,8 +196,7 @@ int lumina_ocr_ctc_decode(lumina_ocr_t* h, const int32_t* idx_dev, const float* 
     if (!h || !idx_dev || !prob_dev || !text_dev || !len_dev || !score_dev) return locr_fail(h, "ctc_decode", "null argument");
     BIND(h);
     if (n <= 0) return 0;
-    hipError_t e = ctc_collapse_launch(idx_dev, prob_dev, text_dev, len_dev, score_dev, n, LUMINA_REC_T, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : locr_fail(h, "ctc_decode", hipGetErrorString(e));
+    return hip_rc(h, "ctc_decode", ctc_collapse_launch(idx_dev, prob_dev, text_dev, len_dev, score_dev, n, LUMINA_REC_T, (hipStream_t)stream));
 }
 
 int lumina_ocr_conv2d(lumina_ocr_t* h, const uint16_t* x_dev, int n, int height, int width, int cin, const uint16_t* w_host,
@@ -209,23 +214,24 @@ int lumina_ocr_conv2d(lumina_ocr_t* h, const uint16_t* x_dev, int n, int height,
     const int ntiles = (cout + L.cfg.bn - 1) / L.cfg.bn;
     std::vector<float> bias((size_t)ntiles * L.cfg.bn, 0.f);
     memcpy(bias.data(), bias_host, sizeof(float) * cout);
-    void *dw = nullptr, *db = nullptr;
-    if (hipMalloc(&dw, packed.size() * 2) != hipSuccess || hipMalloc(&db, bias.size() * 4) != hipSuccess) return locr_fail(h, "conv2d", "hipMalloc");
-    (void)hipMemcpy(dw, packed.data(), packed.size() * 2, hipMemcpyHostToDevice);
-    (void)hipMemcpy(db, bias.data(), bias.size() * 4, hipMemcpyHostToDevice);
-    L.wpk = static_cast<bf16_t*>(dw); L.bias = static_cast<float*>(db);
     // option conv2d_variant (parity tests): 1 = the LDS-DMA 16x32-tile kernel, 2 = the persistent ring kernel, for the layers
     // those kernels serve in the detector (3x3 / stride 1, >= 32 input channels in chunks of 16, output channels in tiles of 64)
-    void* dw2 = nullptr;
     const bool big_ok = ks == 3 && stride == 1 && cin >= 32 && cin % 16 == 0 && cout % 64 == 0 && L.cfg.bn == 64;
-    if (h->conv2d_variant > 0 && !big_ok) { (void)hipFree(dw); (void)hipFree(db); return locr_fail(h, "conv2d", "conv2d_variant 1/2 needs ks 3, stride 1, cin % 16 == 0, cin >= 32, cout % 64 == 0"); }
+    if (h->conv2d_variant > 0 && !big_ok) return locr_fail(h, "conv2d", "conv2d_variant 1/2 needs ks 3, stride 1, cin % 16 == 0, cin >= 32, cout % 64 == 0");
+    // the layer's weights live for this call only
+    DeviceMem dw, db, dw2;
+    auto upload = [](DeviceMem* d, const void* host, size_t bytes) {
+        hipError_t e = mem_alloc(d, bytes);
+        return e == hipSuccess ? hipMemcpy(d->get(), host, bytes, hipMemcpyHostToDevice) : e;
+    };
+    if (upload(&dw, packed.data(), packed.size() * 2) != hipSuccess || upload(&db, bias.data(), bias.size() * 4) != hipSuccess) return locr_fail(h, "conv2d", "weight upload");
+    L.wpk = static_cast<bf16_t*>(dw.get()); L.bias = static_cast<float*>(db.get());
     if (h->conv2d_variant > 0) {
         L.cfg_big = L.cfg; L.cfg_big.nw = 6; L.cfg_big.ck = 16;
         std::vector<bf16_t> packed2(conv_packed_weight_elems(cout, ks, cin, 64));
         pack_conv_weights(w_host, cout, ks, cin, 64, 16, packed2.data(), 1);
-        if (hipMalloc(&dw2, packed2.size() * 2) != hipSuccess) { (void)hipFree(dw); (void)hipFree(db); return locr_fail(h, "conv2d", "hipMalloc"); }
-        (void)hipMemcpy(dw2, packed2.data(), packed2.size() * 2, hipMemcpyHostToDevice);
-        L.wpk_big = static_cast<bf16_t*>(dw2);
+        if (upload(&dw2, packed2.data(), packed2.size() * 2) != hipSuccess) return locr_fail(h, "conv2d", "weight upload");
+        L.wpk_big = static_cast<bf16_t*>(dw2.get());
         L.force_big = true;
     }
     const bool keep_ring = h->conv_ring;
@@ -239,10 +245,8 @@ int lumina_ocr_conv2d(lumina_ocr_t* h, const uint16_t* x_dev, int n, int height,
     int rc = eng_run_conv(eng, L, x, &y, res_dev ? &r : nullptr, 0, OUT_NORMAL, 0, 0, 0, false, (hipStream_t)stream);
     hipError_t e = hipStreamSynchronize((hipStream_t)stream);
     h->conv_ring = keep_ring;
-    (void)hipFree(dw); (void)hipFree(db);
-    if (dw2) (void)hipFree(dw2);
     if (rc) return rc;
-    return e == hipSuccess ? 0 : locr_fail(h, "conv2d sync", hipGetErrorString(e));
+    return hip_rc(h, "conv2d sync", e);
     API_CATCH(h)
 }
 
@@ -256,23 +260,16 @@ int lumina_ocr_read_tap(lumina_ocr_t* h, const char* name, uint16_t* out_host, s
     if (!out_host) return 0;
     if (capacity_elems < t.elems()) return locr_fail(h, "read_tap", "buffer too small");
     if (hipDeviceSynchronize() != hipSuccess) return locr_fail(h, "read_tap", "sync failed");
-    hipError_t e = hipMemcpy(out_host, t.p, t.elems() * sizeof(bf16_t), hipMemcpyDeviceToHost);
-    return e == hipSuccess ? 0 : locr_fail(h, "read_tap", hipGetErrorString(e));
+    return hip_rc(h, "read_tap", hipMemcpy(out_host, t.p, t.elems() * sizeof(bf16_t), hipMemcpyDeviceToHost));
 }
 
 int lumina_ocr_conv_timing(lumina_ocr_t* h, double* total_ms, double* total_flops, int* launches) {
     if (!h || !total_ms || !total_flops || !launches) return 1;
     BIND(h);
-    if (hipDeviceSynchronize() != hipSuccess) return locr_fail(h, "conv_timing", "sync failed");
     double ms = 0, fl = 0;
-    for (size_t i = 0; i < h->conv_events.size(); ++i) {
-        float t = 0.f;
-        if (hipEventElapsedTime(&t, h->conv_events[i].first, h->conv_events[i].second) == hipSuccess) ms += t;
-        fl += h->conv_flops[i];
-        (void)hipEventDestroy(h->conv_events[i].first); (void)hipEventDestroy(h->conv_events[i].second);
-    }
-    *total_ms = ms; *total_flops = fl; *launches = (int)h->conv_events.size();
-    h->conv_events.clear(); h->conv_flops.clear(); h->conv_bytes.clear(); h->conv_names.clear(); h->conv_kernels.clear();
+    int count = 0;
+    if (drain_launches(h, "conv_timing", [&](const LaunchRecord& r, float t) { ms += t; fl += r.flop; ++count; })) return 1;
+    *total_ms = ms; *total_flops = fl; *launches = count;
     return 0;
 }
 
@@ -284,12 +281,9 @@ static int get_coeffs(lumina_ocr* h, int in_size, int out_size, lumina_ocr::Coef
         lumina_ocr::Coeffs c;
         lanczos_coeffs(in_size, out_size, &c.ksize, &bounds, &kk);
         c.bounds_host = std::make_shared<std::vector<int>>(bounds);
-        if (hipMalloc(reinterpret_cast<void**>(&c.bounds), bounds.size() * 4) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&c.kk), kk.size() * 4) != hipSuccess)
-            return locr_fail(h, "resize", "hipMalloc coefficient tables");
-        (void)hipMemcpy(c.bounds, bounds.data(), bounds.size() * 4, hipMemcpyHostToDevice);
-        (void)hipMemcpy(c.kk, kk.data(), kk.size() * 4, hipMemcpyHostToDevice);
-        h->owned.push_back(c.bounds); h->owned.push_back(c.kk);
+        c.bounds = static_cast<int*>(eng_upload(h, bounds.data(), bounds.size() * 4));
+        c.kk = static_cast<int*>(eng_upload(h, kk.data(), kk.size() * 4));
+        if (!c.bounds || !c.kk) return locr_fail(h, "resize", "coefficient table upload");
         it = h->coeff_cache.emplace(key, c).first;
     }
     *out = it->second;
@@ -308,34 +302,23 @@ int lumina_ocr_resize_lanczos(lumina_ocr_t* h, const uint8_t* in_dev, int n, int
     int cur_w = width;
     const bool need_h = out_w != width, need_v = out_h != height;
     if (!need_h && !need_v) {
-        hipError_t e = hipMemcpyAsync(out_dev, in_dev, (size_t)n * height * width * channels, hipMemcpyDeviceToDevice, st);
-        return e == hipSuccess ? 0 : locr_fail(h, "resize_lanczos", hipGetErrorString(e));
+        return hip_rc(h, "resize_lanczos", hipMemcpyAsync(out_dev, in_dev, (size_t)n * height * width * channels, hipMemcpyDeviceToDevice, st));
     }
     if (need_h) {
         lumina_ocr::Coeffs c;
         if (get_coeffs(h, width, out_w, &c)) return 1;
         uint8_t* dst = out_dev;
         if (need_v) {
-            const size_t need = (size_t)n * height * out_w * channels;
-            if (need > h->aux_cap) {
-                if (hipDeviceSynchronize() != hipSuccess) return locr_fail(h, "resize_lanczos", "sync");
-                if (h->aux) (void)hipFree(h->aux);
-    for (int k = 0; k < 2; ++k) { if (h->jd_stage[k]) (void)hipHostFree(h->jd_stage[k]); if (h->jd_stage_ev[k]) (void)hipEventDestroy(h->jd_stage_ev[k]); }
-                h->aux = nullptr; h->aux_cap = 0;
-                if (hipMalloc(reinterpret_cast<void**>(&h->aux), need) != hipSuccess) return locr_fail(h, "resize_lanczos", "hipMalloc");
-                h->aux_cap = need;
-            }
-            dst = h->aux;
+            if (hip_rc(h, "resize_lanczos", h->aux.reserve((size_t)n * height * out_w * channels))) return 1;
+            dst = h->aux.get();
         }
-        hipError_t e = resample_launch(src, dst, c.bounds, c.kk, c.ksize, n, height, width, channels, out_w, 0, c.bounds_host->data(), st);
-        if (e != hipSuccess) return locr_fail(h, "resize_lanczos", hipGetErrorString(e));
+        if (hip_rc(h, "resize_lanczos", resample_launch(src, dst, c.bounds, c.kk, c.ksize, n, height, width, channels, out_w, 0, c.bounds_host->data(), st))) return 1;
         src = dst; cur_w = out_w;
     }
     if (need_v) {
         lumina_ocr::Coeffs c;
         if (get_coeffs(h, height, out_h, &c)) return 1;
-        hipError_t e = resample_launch(src, out_dev, c.bounds, c.kk, c.ksize, n, height, cur_w, channels, out_h, 1, c.bounds_host->data(), st);
-        if (e != hipSuccess) return locr_fail(h, "resize_lanczos", hipGetErrorString(e));
+        if (hip_rc(h, "resize_lanczos", resample_launch(src, out_dev, c.bounds, c.kk, c.ksize, n, height, cur_w, channels, out_h, 1, c.bounds_host->data(), st))) return 1;
     }
     return 0;
     API_CATCH(h)
@@ -346,43 +329,34 @@ int lumina_ocr_enhance(lumina_ocr_t* h, const uint8_t* img_dev, int n, int heigh
                        uint8_t* tmp_dev, uint8_t* out_dev, void* stream) {
     if (!h || !img_dev || !tmp_dev || !out_dev || n <= 0) return locr_fail(h, "enhance", "bad arguments");
     BIND(h);
-    if (n > h->sums_cap) {
-        unsigned long long* s = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&s), sizeof(unsigned long long) * (size_t)n) != hipSuccess) return locr_fail(h, "enhance", "hipMalloc");
-        h->owned.push_back(s);
-        h->sums = s; h->sums_cap = n;
-    }
-    hipError_t e = enhance_launch(img_dev, tmp_dev, out_dev, h->sums, n, height, width, contrast, sharpness, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : locr_fail(h, "enhance", hipGetErrorString(e));
+    if (hip_rc(h, "enhance", h->sums.reserve(sizeof(unsigned long long) * (size_t)n))) return 1;
+    unsigned long long* sums = reinterpret_cast<unsigned long long*>(h->sums.get());
+    return hip_rc(h, "enhance", enhance_launch(img_dev, tmp_dev, out_dev, sums, n, height, width, contrast, sharpness, (hipStream_t)stream));
 }
 
 int lumina_ocr_binarize(lumina_ocr_t* h, const uint8_t* img_dev, int n, int height, int width, int adaptive, int threshold, uint8_t* out_dev, void* stream) {
     if (!h || !img_dev || !out_dev || n <= 0 || height <= 0 || width <= 0) return locr_fail(h, "binarize", "bad arguments");
     BIND(h);
-    hipError_t e = binarize_launch(img_dev, out_dev, n, height, width, adaptive != 0, threshold, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : locr_fail(h, "binarize", hipGetErrorString(e));
+    return hip_rc(h, "binarize", binarize_launch(img_dev, out_dev, n, height, width, adaptive != 0, threshold, (hipStream_t)stream));
 }
 
 int lumina_ocr_exif_transpose(lumina_ocr_t* h, const uint8_t* img_dev, int n, int height, int width, int orientation, uint8_t* out_dev, void* stream) {
     if (!h || !img_dev || !out_dev || n <= 0 || height <= 0 || width <= 0 || orientation < 1 || orientation > 8 || img_dev == out_dev)
         return locr_fail(h, "exif_transpose", "bad arguments (orientation 1..8, not in place)");
     BIND(h);
-    hipError_t e = exif_transpose_launch(img_dev, out_dev, n, height, width, orientation, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : locr_fail(h, "exif_transpose", hipGetErrorString(e));
+    return hip_rc(h, "exif_transpose", exif_transpose_launch(img_dev, out_dev, n, height, width, orientation, (hipStream_t)stream));
 }
 
 int lumina_ocr_grayscale(lumina_ocr_t* h, const uint8_t* img_dev, int n, int height, int width, uint8_t* out_dev, void* stream) {
     if (!h || !img_dev || !out_dev || n <= 0 || height <= 0 || width <= 0) return locr_fail(h, "grayscale", "bad arguments");
     BIND(h);
-    hipError_t e = grayscale_launch(img_dev, out_dev, n, height, width, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : locr_fail(h, "grayscale", hipGetErrorString(e));
+    return hip_rc(h, "grayscale", grayscale_launch(img_dev, out_dev, n, height, width, (hipStream_t)stream));
 }
 
 int lumina_ocr_denoise(lumina_ocr_t* h, const uint8_t* img_dev, int n, int height, int width, uint8_t* out_dev, void* stream) {
     if (!h || !img_dev || !out_dev || n <= 0 || height <= 0 || width <= 0 || img_dev == out_dev) return locr_fail(h, "denoise", "bad arguments (not in place)");
     BIND(h);
-    hipError_t e = median3_launch(img_dev, out_dev, n, height, width, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : locr_fail(h, "denoise", hipGetErrorString(e));
+    return hip_rc(h, "denoise", median3_launch(img_dev, out_dev, n, height, width, (hipStream_t)stream));
 }
 
 int lumina_ocr_jpeg_encode(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int quality, int optimize,
@@ -393,8 +367,7 @@ int lumina_ocr_jpeg_encode(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int
     if (eng_ws_reserve(h, jpeg_workspace_bytes(n, height, width))) return 1;
     JpegParams p{};
     p.rgb = pages_dev; p.n = n; p.height = height; p.width = width; p.quality = quality; p.optimize = optimize != 0; p.out = out_dev; p.out_stride = out_stride; p.sizes = sizes_dev;
-    hipError_t e = jpeg_encode_launch(p, h->ws, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : locr_fail(h, "jpeg_encode", hipGetErrorString(e));
+    return hip_rc(h, "jpeg_encode", jpeg_encode_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
     API_CATCH(h)
 }
 
@@ -430,8 +403,7 @@ int lumina_ocr_jpeg_coefficients(lumina_ocr_t* h, const uint8_t* pages_dev, int 
                                  void* stream) {
     if (!h || !pages_dev || !coefs_dev || n <= 0 || height <= 0 || width <= 0) return locr_fail(h, "jpeg_coefficients", "bad arguments");
     BIND(h);
-    hipError_t e = jpeg_coefficients_launch(pages_dev, n, height, width, quality, coefs_dev, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : locr_fail(h, "jpeg_coefficients", hipGetErrorString(e));
+    return hip_rc(h, "jpeg_coefficients", jpeg_coefficients_launch(pages_dev, n, height, width, quality, coefs_dev, (hipStream_t)stream));
 }
 
 static int deskew_tables(lumina_ocr* h) {
@@ -440,13 +412,9 @@ static int deskew_tables(lumina_ocr* h) {
     std::vector<short> wtab(32 * 32 * 16);
     deskew_trig_table(trig);
     deskew_weight_table(wtab.data());
-    void *a = nullptr, *b = nullptr;
-    if (hipMalloc(&a, sizeof(trig)) != hipSuccess || hipMalloc(&b, wtab.size() * 2) != hipSuccess) return locr_fail(h, "deskew", "hipMalloc tables");
-    (void)hipMemcpy(a, trig, sizeof(trig), hipMemcpyHostToDevice);
-    (void)hipMemcpy(b, wtab.data(), wtab.size() * 2, hipMemcpyHostToDevice);
-    h->owned.push_back(a); h->owned.push_back(b);
-    h->dk_trig = static_cast<float*>(a); h->dk_wtab = static_cast<short*>(b);
-    return 0;
+    h->dk_trig = static_cast<float*>(eng_upload(h, trig, sizeof(trig)));
+    h->dk_wtab = static_cast<short*>(eng_upload(h, wtab.data(), wtab.size() * 2));
+    return h->dk_trig && h->dk_wtab ? 0 : locr_fail(h, "deskew", "table upload");
 }
 
 int lumina_ocr_deskew(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, uint8_t* out_dev, double* rot_dev, int32_t* info_dev,
@@ -469,8 +437,7 @@ int lumina_ocr_deskew(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int heig
         p.edges_out = edges_dev ? edges_dev + (size_t)b0 * px : nullptr;
         p.segs_out = segs_dev ? segs_dev + (size_t)b0 * DESKEW_MAX_PEAKS * DESKEW_SEG_PER_PEAK * 4 : nullptr;
         p.nsegs_out = nsegs_dev ? nsegs_dev + (size_t)b0 * DESKEW_MAX_PEAKS : nullptr;
-        hipError_t e = deskew_launch(p, h->ws, (hipStream_t)stream);
-        if (e != hipSuccess) return locr_fail(h, "deskew", hipGetErrorString(e));
+        if (hip_rc(h, "deskew", deskew_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream))) return 1;
     }
     return 0;
     API_CATCH(h)
@@ -481,8 +448,7 @@ int lumina_ocr_deskew_warp(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int
     BIND(h);
     API_TRY
     if (deskew_tables(h)) return 1;
-    hipError_t e = deskew_warp_launch(pages_dev, out_dev, rot_dev, h->dk_wtab, n, height, width, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : locr_fail(h, "deskew_warp", hipGetErrorString(e));
+    return hip_rc(h, "deskew_warp", deskew_warp_launch(pages_dev, out_dev, rot_dev, h->dk_wtab, n, height, width, (hipStream_t)stream));
     API_CATCH(h)
 }
 
@@ -492,17 +458,13 @@ int lumina_ocr_svtr_dtype(const lumina_ocr_t* h) { return h ? h->svtr.dtype : 0;
 int lumina_ocr_conv_timing_detail(lumina_ocr_t* h, char* buf, size_t cap) {
     if (!h || !buf || cap == 0) return 1;
     BIND(h);
-    if (hipDeviceSynchronize() != hipSuccess) return locr_fail(h, "conv_timing_detail", "sync failed");
     std::string out;
-    for (size_t i = 0; i < h->conv_events.size(); ++i) {
-        float t = 0.f;
-        (void)hipEventElapsedTime(&t, h->conv_events[i].first, h->conv_events[i].second);
-        char line[256];
-        snprintf(line, sizeof(line), "%s %s %.4f %.4f %.4f\n", h->conv_names[i].c_str(), h->conv_kernels[i].c_str(), t, h->conv_flops[i] * 1e-9, h->conv_bytes[i] * 1e-6);
-        out += line;
-        (void)hipEventDestroy(h->conv_events[i].first); (void)hipEventDestroy(h->conv_events[i].second);
-    }
-    h->conv_events.clear(); h->conv_flops.clear(); h->conv_bytes.clear(); h->conv_names.clear(); h->conv_kernels.clear();
+    if (drain_launches(h, "conv_timing_detail", [&](const LaunchRecord& r, float t) {
+            char line[256];
+            snprintf(line, sizeof(line), "%s %s %.4f %.4f %.4f\n", r.layer.c_str(), r.kernel.c_str(), t, r.flop * 1e-9, r.bytes * 1e-6);
+            out += line;
+        }))
+        return 1;
     snprintf(buf, cap, "%s", out.c_str());
     return 0;
 }

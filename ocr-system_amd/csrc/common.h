@@ -66,8 +66,28 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
-#define LOCR_CHECK(expr)                                                        \
-    do {                                                                        \
-        hipError_t _e = (expr);                                                 \
+// every host entry's HIP error check: record the failing call in the handle (locr_fail, engine.h) and return 1.  Needs `eng` in scope.
+#define LOCR_CHECK(expr)                                                           \
+    do {                                                                           \
+        hipError_t _e = (expr);                                                    \
         if (_e != hipSuccess) return locr_fail(eng, #expr, hipGetErrorString(_e)); \
     } while (0)
+
+// Host-only bump allocator over one workspace: regions start on 256-byte boundaries.  With a null base it only counts (a layout run
+// this way gives the workspace size); with a base it hands out pointers, and a region past `cap` sets `overflow` and comes back null.
+// Each workspace has one layout function that takes its regions from an Arena, used both to size and to carve.
+struct Arena {
+    uint8_t* base = nullptr;
+    size_t cap = 0, off = 0;
+    bool overflow = false;
+    Arena() = default;
+    Arena(void* b, size_t c) : base(static_cast<uint8_t*>(b)), cap(c) {}
+    bool counting() const { return base == nullptr; }
+    template <class T> T* take(size_t count) {
+        const size_t a = (off + 255) & ~(size_t)255;
+        off = a + count * sizeof(T);
+        if (base == nullptr) return nullptr;
+        if (off > cap) { overflow = true; return nullptr; }
+        return reinterpret_cast<T*>(base + a);
+    }
+};

@@ -12,6 +12,6 @@ struct DbPostParams {
 };
 
 size_t dbpost_workspace_bytes(int B, int Hp, int Wp, int max_boxes);
-hipError_t dbpost_launch(const DbPostParams& p, void* workspace, hipStream_t st);
+hipError_t dbpost_launch(const DbPostParams& p, void* workspace, size_t ws_bytes, hipStream_t st);
 hipError_t rec_crop_launch(const uint8_t* pages, int H, int W, const int* quads, const int* page_idx, int n, uint8_t* crops, int* widths,
                            hipStream_t st);

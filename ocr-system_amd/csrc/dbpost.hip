@@ -532,67 +532,60 @@ __global__ __launch_bounds__(256) void rec_crop_kernel(const uint8_t* pages, int
 
 // worst case of a row: every other pixel starts a run
 static size_t dbpost_runcap(int Hp, int Wp) { return (size_t)Hp * ((Wp + 1) / 2); }
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-size_t dbpost_workspace_bytes(int B, int Hp, int Wp, int maxc) {
+// the workspace's regions: one layout sizes it (dbpost_workspace_bytes) and carves it (dbpost_launch)
+struct DbWorkspace {
+    unsigned long long* mask; int *runoff, *rootoff, *nruns, *ncomp; unsigned short *rxs, *rxe;
+    int *parent, *cidr, *ymin, *ymax, *segoff, *rowmin, *rowmax; int2* hull; int* box_tmp; float* score_tmp; int* valid_tmp;
+};
+static DbWorkspace dbpost_layout(Arena& a, int B, int Hp, int Wp, int maxc) {
     const size_t seg_cap = (size_t)maxc * Hp;  // worst case: every candidate spans the page height
     const size_t runcap = dbpost_runcap(Hp, Wp), nseg = (Wp + 63) / 64;
-    size_t n = 0;
-    n += al256((size_t)B * Hp * nseg * 8);             // masks
-    n += 2 * al256((size_t)B * (Hp + 1) * 4);          // run / root counts -> offsets
-    n += 2 * al256((size_t)B * 4);                     // nruns, ncomp
-    n += 2 * al256((size_t)B * runcap * 2);            // run xs, xe
-    n += 2 * al256((size_t)B * runcap * 4);            // parent, component id of root runs
-    n += 2 * al256((size_t)B * maxc * 4);              // ymin, ymax
-    n += al256((size_t)B * (maxc + 1) * 4);            // segoff
-    n += 2 * al256((size_t)B * seg_cap * 4);           // rowmin, rowmax
-    n += al256((size_t)B * seg_cap * 2 * 8);           // hull
-    n += al256((size_t)B * maxc * 8 * 4) + 2 * al256((size_t)B * maxc * 4);
-    return n + 4096;
+    DbWorkspace w;
+    w.mask = a.take<unsigned long long>((size_t)B * Hp * nseg);
+    w.runoff = a.take<int>((size_t)B * (Hp + 1)); w.rootoff = a.take<int>((size_t)B * (Hp + 1));   // run / root counts -> offsets
+    w.nruns = a.take<int>(B); w.ncomp = a.take<int>(B);
+    w.rxs = a.take<unsigned short>((size_t)B * runcap); w.rxe = a.take<unsigned short>((size_t)B * runcap);
+    w.parent = a.take<int>((size_t)B * runcap); w.cidr = a.take<int>((size_t)B * runcap);   // (component id of root runs)
+    w.ymin = a.take<int>((size_t)B * maxc); w.ymax = a.take<int>((size_t)B * maxc);
+    w.segoff = a.take<int>((size_t)B * (maxc + 1));
+    w.rowmin = a.take<int>((size_t)B * seg_cap); w.rowmax = a.take<int>((size_t)B * seg_cap);
+    w.hull = a.take<int2>((size_t)B * seg_cap * 2);
+    w.box_tmp = a.take<int>((size_t)B * maxc * 8); w.score_tmp = a.take<float>((size_t)B * maxc); w.valid_tmp = a.take<int>((size_t)B * maxc);
+    return w;
 }
 
-hipError_t dbpost_launch(const DbPostParams& p, void* workspace, hipStream_t st) {
+size_t dbpost_workspace_bytes(int B, int Hp, int Wp, int maxc) {
+    Arena a;
+    dbpost_layout(a, B, Hp, Wp, maxc);
+    return a.off;
+}
+
+hipError_t dbpost_launch(const DbPostParams& p, void* workspace, size_t ws_bytes, hipStream_t st) {
     const int B = p.B, Hp = p.Hp, Wp = p.Wp, maxc = p.max_boxes;
     if (B <= 0 || Hp <= 0 || Wp <= 0 || Wp > 65535 || maxc <= 0 || (size_t)B * Hp >= (1ull << 31) || dbpost_runcap(Hp, Wp) >= (1ull << 31)) return hipErrorInvalidValue;
     const size_t seg_cap = (size_t)maxc * Hp, runcap = dbpost_runcap(Hp, Wp);
     const int nseg = (Wp + 63) / 64;
-    uint8_t* w = static_cast<uint8_t*>(workspace);
-    auto take = [&](size_t bytes) { void* r = w; w += al256(bytes); return r; };
-    unsigned long long* mask = static_cast<unsigned long long*>(take((size_t)B * Hp * nseg * 8));
-    int* runoff = static_cast<int*>(take((size_t)B * (Hp + 1) * 4));
-    int* rootoff = static_cast<int*>(take((size_t)B * (Hp + 1) * 4));
-    int* nruns = static_cast<int*>(take((size_t)B * 4));
-    int* ncomp = static_cast<int*>(take((size_t)B * 4));
-    unsigned short* rxs = static_cast<unsigned short*>(take((size_t)B * runcap * 2));
-    unsigned short* rxe = static_cast<unsigned short*>(take((size_t)B * runcap * 2));
-    int* parent = static_cast<int*>(take((size_t)B * runcap * 4));
-    int* cidr = static_cast<int*>(take((size_t)B * runcap * 4));
-    int* ymin = static_cast<int*>(take((size_t)B * maxc * 4));
-    int* ymax = static_cast<int*>(take((size_t)B * maxc * 4));
-    int* segoff = static_cast<int*>(take((size_t)B * (maxc + 1) * 4));
-    int* rowmin = static_cast<int*>(take((size_t)B * seg_cap * 4));
-    int* rowmax = static_cast<int*>(take((size_t)B * seg_cap * 4));
-    int2* hull = static_cast<int2*>(take((size_t)B * seg_cap * 2 * 8));
-    int* box_tmp = static_cast<int*>(take((size_t)B * maxc * 8 * 4));
-    float* score_tmp = static_cast<float*>(take((size_t)B * maxc * 4));
-    int* valid_tmp = static_cast<int*>(take((size_t)B * maxc * 4));
+    Arena a(workspace, ws_bytes);
+    const DbWorkspace w = dbpost_layout(a, B, Hp, Wp, maxc);
+    if (a.overflow) return hipErrorOutOfMemory;
 
     const int rows = B * Hp;
     const dim3 grows((unsigned)((rows + 3) / 4));
-    hipLaunchKernelGGL(rl_mask_kernel, grows, dim3(256), 0, st, p.prob, mask, runoff, Hp, Wp, nseg, p.valid_h, p.valid_w, p.thresh, rows);
-    hipLaunchKernelGGL(row_scan_kernel, dim3(B), dim3(64), 0, st, runoff, nruns, Hp);
-    hipLaunchKernelGGL(rl_fill_kernel, grows, dim3(256), 0, st, mask, runoff, rxs, rxe, parent, Hp, nseg, runcap, rows);
-    hipLaunchKernelGGL(rl_merge_kernel, grows, dim3(256), 0, st, runoff, rxs, rxe, parent, Hp, runcap, rows);
-    hipLaunchKernelGGL(rl_roots_kernel, grows, dim3(256), 0, st, runoff, parent, rootoff, Hp, runcap, rows);
-    hipLaunchKernelGGL(row_scan_kernel, dim3(B), dim3(64), 0, st, rootoff, ncomp, Hp);
-    hipLaunchKernelGGL(rl_assign_kernel, grows, dim3(256), 0, st, runoff, rootoff, parent, cidr, ymin, ymax, Hp, runcap, maxc, rows);
-    hipLaunchKernelGGL(rl_extent_kernel, grows, dim3(256), 0, st, runoff, parent, cidr, ymax, Hp, runcap, maxc, rows);
-    hipLaunchKernelGGL(seg_scan_kernel, dim3(B), dim3(64), 0, st, ncomp, ymin, ymax, segoff, maxc);
-    hipLaunchKernelGGL(seg_init_kernel, dim3(64, B), dim3(256), 0, st, ncomp, segoff, rowmin, rowmax, maxc, seg_cap);
-    hipLaunchKernelGGL(rl_extremes_kernel, grows, dim3(256), 0, st, runoff, rxs, rxe, parent, cidr, ymin, segoff, rowmin, rowmax, Hp, runcap, maxc, seg_cap, rows);
-    hipLaunchKernelGGL(comp_box_kernel, dim3(B * maxc), dim3(256), 0, st, p.prob, ncomp, ymin, ymax, segoff, rowmin, rowmax, hull, box_tmp,
-                       score_tmp, valid_tmp, Hp, Wp, p.valid_h, p.valid_w, maxc, seg_cap, p.box_thresh, p.unclip_ratio, p.min_size);
-    hipLaunchKernelGGL(compact_kernel, dim3(B), dim3(64), 0, st, box_tmp, score_tmp, valid_tmp, p.boxes, p.scores, p.counts, maxc);
+    hipLaunchKernelGGL(rl_mask_kernel, grows, dim3(256), 0, st, p.prob, w.mask, w.runoff, Hp, Wp, nseg, p.valid_h, p.valid_w, p.thresh, rows);
+    hipLaunchKernelGGL(row_scan_kernel, dim3(B), dim3(64), 0, st, w.runoff, w.nruns, Hp);
+    hipLaunchKernelGGL(rl_fill_kernel, grows, dim3(256), 0, st, w.mask, w.runoff, w.rxs, w.rxe, w.parent, Hp, nseg, runcap, rows);
+    hipLaunchKernelGGL(rl_merge_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, Hp, runcap, rows);
+    hipLaunchKernelGGL(rl_roots_kernel, grows, dim3(256), 0, st, w.runoff, w.parent, w.rootoff, Hp, runcap, rows);
+    hipLaunchKernelGGL(row_scan_kernel, dim3(B), dim3(64), 0, st, w.rootoff, w.ncomp, Hp);
+    hipLaunchKernelGGL(rl_assign_kernel, grows, dim3(256), 0, st, w.runoff, w.rootoff, w.parent, w.cidr, w.ymin, w.ymax, Hp, runcap, maxc, rows);
+    hipLaunchKernelGGL(rl_extent_kernel, grows, dim3(256), 0, st, w.runoff, w.parent, w.cidr, w.ymax, Hp, runcap, maxc, rows);
+    hipLaunchKernelGGL(seg_scan_kernel, dim3(B), dim3(64), 0, st, w.ncomp, w.ymin, w.ymax, w.segoff, maxc);
+    hipLaunchKernelGGL(seg_init_kernel, dim3(64, B), dim3(256), 0, st, w.ncomp, w.segoff, w.rowmin, w.rowmax, maxc, seg_cap);
+    hipLaunchKernelGGL(rl_extremes_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.cidr, w.ymin, w.segoff, w.rowmin, w.rowmax, Hp, runcap, maxc, seg_cap, rows);
+    hipLaunchKernelGGL(comp_box_kernel, dim3(B * maxc), dim3(256), 0, st, p.prob, w.ncomp, w.ymin, w.ymax, w.segoff, w.rowmin, w.rowmax, w.hull, w.box_tmp,
+                       w.score_tmp, w.valid_tmp, Hp, Wp, p.valid_h, p.valid_w, maxc, seg_cap, p.box_thresh, p.unclip_ratio, p.min_size);
+    hipLaunchKernelGGL(compact_kernel, dim3(B), dim3(64), 0, st, w.box_tmp, w.score_tmp, w.valid_tmp, p.boxes, p.scores, p.counts, maxc);
     return hipGetLastError();
 }
 

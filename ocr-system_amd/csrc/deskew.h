@@ -19,5 +19,5 @@ constexpr int DESKEW_MAX_PEAKS = 512, DESKEW_SEG_PER_PEAK = 8;
 void deskew_trig_table(float* tab /* [360] */);
 void deskew_weight_table(short* wtab /* [32 * 32 * 16] */);
 size_t deskew_workspace_bytes(int B, int H, int W);
-hipError_t deskew_launch(const DeskewParams& p, void* workspace, hipStream_t st);
+hipError_t deskew_launch(const DeskewParams& p, void* workspace, size_t ws_bytes, hipStream_t st);
 hipError_t deskew_warp_launch(const uint8_t* rgb, uint8_t* out, const double* rot, const short* wtab, int B, int H, int W, hipStream_t st);

@@ -616,16 +616,32 @@ void deskew_weight_table(short* wtab) {
         }
 }
 
-static size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-
-size_t deskew_workspace_bytes(int B, int H, int W) {
+// the workspace's regions: one layout sizes it (deskew_workspace_bytes) and carves it (deskew_launch)
+struct DeskewWorkspace {
+    uint8_t *map, *edges, *mark;   // (edges: unused when the caller asks for the edge map)
+    int *label, *list, *accum, *hist, *peaks, *segs, *nsegs, *count, *npeaks, *vcut;
+};
+static DeskewWorkspace deskew_layout(Arena& a, int B, int H, int W) {
     const size_t px = (size_t)B * H * W, numrho = 2 * ((size_t)W + H) + 1;
-    return al(px) /*map*/ + al(px) /*edges*/ + al(px) /*mark*/ + 2 * al(px * 4) /*label, list*/ + al((size_t)B * DK_NANGLE * numrho * 4) /*accum*/ +
-           al((size_t)B * DK_MAX_VOTES * 4) + al((size_t)B * DK_MAX_PEAKS * 4) + al((size_t)B * DK_MAX_PEAKS * DK_SEG_PER_PEAK * 16) +
-           al((size_t)B * DK_MAX_PEAKS * 4) + 4 * al((size_t)B * 16);
+    DeskewWorkspace w;
+    w.map = a.take<uint8_t>(px); w.edges = a.take<uint8_t>(px); w.mark = a.take<uint8_t>(px);
+    w.label = a.take<int>(px); w.list = a.take<int>(px);
+    w.accum = a.take<int>((size_t)B * DK_NANGLE * numrho);
+    w.hist = a.take<int>((size_t)B * DK_MAX_VOTES);
+    w.peaks = a.take<int>((size_t)B * DK_MAX_PEAKS);
+    w.segs = a.take<int>((size_t)B * DK_MAX_PEAKS * DK_SEG_PER_PEAK * 4);
+    w.nsegs = a.take<int>((size_t)B * DK_MAX_PEAKS);
+    w.count = a.take<int>((size_t)B * 4); w.npeaks = a.take<int>((size_t)B * 4); w.vcut = a.take<int>((size_t)B * 4);
+    return w;
 }
 
-hipError_t deskew_launch(const DeskewParams& p, void* workspace, hipStream_t st) {
+size_t deskew_workspace_bytes(int B, int H, int W) {
+    Arena a;
+    deskew_layout(a, B, H, W);
+    return a.off;
+}
+
+hipError_t deskew_launch(const DeskewParams& p, void* workspace, size_t ws_bytes, hipStream_t st) {
     const int B = p.B, H = p.H, W = p.W;
     if (B <= 0 || H <= 0 || W <= 0 || H >= 32768 || W >= 32768) return hipErrorInvalidValue;
     const size_t per = (size_t)H * W, px = (size_t)B * per;
@@ -635,44 +651,32 @@ hipError_t deskew_launch(const DeskewParams& p, void* workspace, hipStream_t st)
     const int rmax = (int)std::sqrt((double)W * W + (double)H * H) + 2;
     const size_t hough_lds = (size_t)2 * (2 * rmax + 1) * 4;
     if (hough_lds > 150 * 1024) return hipErrorInvalidValue;   // the two-angle LDS histograms (page diagonals up to ~9500 px)
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    auto take = [&](size_t bytes) { unsigned char* q = ws; ws += al(bytes); return q; };
-    uint8_t* map = take(px);
-    uint8_t* edges = p.edges_out ? p.edges_out : take(px);
-    if (p.edges_out) take(px);
-    uint8_t* mark = take(px);
-    int* label = reinterpret_cast<int*>(take(px * 4));
-    int* list = reinterpret_cast<int*>(take(px * 4));
-    int* accum = reinterpret_cast<int*>(take((size_t)B * DK_NANGLE * numrho * 4));
-    int* hist = reinterpret_cast<int*>(take((size_t)B * DK_MAX_VOTES * 4));
-    int* peaks = reinterpret_cast<int*>(take((size_t)B * DK_MAX_PEAKS * 4));
-    int* segs = reinterpret_cast<int*>(take((size_t)B * DK_MAX_PEAKS * DK_SEG_PER_PEAK * 16));
-    int* nsegs = reinterpret_cast<int*>(take((size_t)B * DK_MAX_PEAKS * 4));
-    int* count = reinterpret_cast<int*>(take((size_t)B * 16));
-    int* npeaks = reinterpret_cast<int*>(take((size_t)B * 16));
-    int* vcut = reinterpret_cast<int*>(take((size_t)B * 16));
+    Arena a(workspace, ws_bytes);
+    const DeskewWorkspace w = deskew_layout(a, B, H, W);
+    if (a.overflow) return hipErrorOutOfMemory;
+    uint8_t* edges = p.edges_out ? p.edges_out : w.edges;
     hipError_t e;
-    if ((e = hipMemsetAsync(count, 0, (size_t)B * 4, st)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(npeaks, 0, (size_t)B * 4, st)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(hist, 0, (size_t)B * DK_MAX_VOTES * 4, st)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(mark, 0, px, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.count, 0, (size_t)B * 4, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.npeaks, 0, (size_t)B * 4, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.hist, 0, (size_t)B * DK_MAX_VOTES * 4, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.mark, 0, px, st)) != hipSuccess) return e;
     const int tx = ceil_div(W, CT_W), ty = ceil_div(H, CT_H);
-    hipLaunchKernelGGL(canny_map_kernel, dim3((unsigned)(B * tx * ty)), dim3(256), 0, st, p.rgb, map, label, mark, H, W, tx, ty);
+    hipLaunchKernelGGL(canny_map_kernel, dim3((unsigned)(B * tx * ty)), dim3(256), 0, st, p.rgb, w.map, w.label, w.mark, H, W, tx, ty);
     const int bpp = (int)((per + CE_BLOCK - 1) / CE_BLOCK);
-    hipLaunchKernelGGL(cc_border_kernel, dim3((unsigned)(B * tx * ty)), dim3(128), 0, st, map, label, H, W, tx, ty);
-    hipLaunchKernelGGL(cc_mark_kernel, dim3((unsigned)(B * bpp)), dim3(256), 0, st, label, mark, bpp, per);
-    hipLaunchKernelGGL(cc_edges_kernel, dim3((unsigned)(B * bpp)), dim3(256), 0, st, map, label, mark, edges, list, count, W, bpp, per);
+    hipLaunchKernelGGL(cc_border_kernel, dim3((unsigned)(B * tx * ty)), dim3(128), 0, st, w.map, w.label, H, W, tx, ty);
+    hipLaunchKernelGGL(cc_mark_kernel, dim3((unsigned)(B * bpp)), dim3(256), 0, st, w.label, w.mark, bpp, per);
+    hipLaunchKernelGGL(cc_edges_kernel, dim3((unsigned)(B * bpp)), dim3(256), 0, st, w.map, w.label, w.mark, edges, w.list, w.count, W, bpp, per);
     { hipError_t e2 = locr_dyn_lds(reinterpret_cast<const void*>(hough_kernel), 150 * 1024); if (e2 != hipSuccess) return e2; }
-    hipLaunchKernelGGL(hough_kernel, dim3(DK_NANGLE / 2, B), dim3(256), hough_lds, st, list, count, p.trig, accum, numrho, rmax, per);
-    hipLaunchKernelGGL(peak_hist_kernel, dim3(DK_NANGLE, B), dim3(256), 0, st, accum, hist, numrho);
-    hipLaunchKernelGGL(peak_cut_kernel, dim3(B), dim3(256), 0, st, hist, vcut);
-    hipLaunchKernelGGL(peak_list_kernel, dim3(DK_NANGLE, B), dim3(256), 0, st, accum, vcut, peaks, npeaks, numrho);
-    hipLaunchKernelGGL(segments_kernel, dim3(DK_MAX_PEAKS, B), dim3(64), 0, st, edges, peaks, npeaks, p.trig, segs, nsegs, H, W, numrho);
+    hipLaunchKernelGGL(hough_kernel, dim3(DK_NANGLE / 2, B), dim3(256), hough_lds, st, w.list, w.count, p.trig, w.accum, numrho, rmax, per);
+    hipLaunchKernelGGL(peak_hist_kernel, dim3(DK_NANGLE, B), dim3(256), 0, st, w.accum, w.hist, numrho);
+    hipLaunchKernelGGL(peak_cut_kernel, dim3(B), dim3(256), 0, st, w.hist, w.vcut);
+    hipLaunchKernelGGL(peak_list_kernel, dim3(DK_NANGLE, B), dim3(256), 0, st, w.accum, w.vcut, w.peaks, w.npeaks, numrho);
+    hipLaunchKernelGGL(segments_kernel, dim3(DK_MAX_PEAKS, B), dim3(64), 0, st, edges, w.peaks, w.npeaks, p.trig, w.segs, w.nsegs, H, W, numrho);
     { hipError_t e2 = locr_dyn_lds(reinterpret_cast<const void*>(angle_kernel), AG_MAX * 16); if (e2 != hipSuccess) return e2; }
-    hipLaunchKernelGGL(angle_kernel, dim3(B), dim3(256), AG_MAX * 16, st, segs, nsegs, npeaks, p.rot, p.info);
+    hipLaunchKernelGGL(angle_kernel, dim3(B), dim3(256), AG_MAX * 16, st, w.segs, w.nsegs, w.npeaks, p.rot, p.info);
     if (p.segs_out) {
-        if ((e = hipMemcpyAsync(p.segs_out, segs, (size_t)B * DK_MAX_PEAKS * DK_SEG_PER_PEAK * 16, hipMemcpyDeviceToDevice, st)) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(p.nsegs_out, nsegs, (size_t)B * DK_MAX_PEAKS * 4, hipMemcpyDeviceToDevice, st)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(p.segs_out, w.segs, (size_t)B * DK_MAX_PEAKS * DK_SEG_PER_PEAK * 16, hipMemcpyDeviceToDevice, st)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(p.nsegs_out, w.nsegs, (size_t)B * DK_MAX_PEAKS * 4, hipMemcpyDeviceToDevice, st)) != hipSuccess) return e;
     }
     if (p.out) hipLaunchKernelGGL(warp_kernel, dim3(ceil_div(W, WP_T), ceil_div(H, WP_T), B), dim3(256), 0, st, p.rgb, p.out, p.rot, p.wtab, H, W);
     return hipGetLastError();

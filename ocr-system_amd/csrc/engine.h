@@ -3,6 +3,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -74,6 +75,36 @@ struct SvtrModel {
     bf16_t* ctc_wpk = nullptr; float* ctc_bias = nullptr;
 };
 
+// Owning handles (move-only, released by the destructor): the only places device memory, pinned host memory and events are freed
+struct DeviceFree { void operator()(void* p) const { (void)hipFree(p); } };
+struct PinnedFree { void operator()(void* p) const { (void)hipHostFree(p); } };
+struct EventDestroy { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
+using DeviceMem = std::unique_ptr<void, DeviceFree>;
+using PinnedMem = std::unique_ptr<void, PinnedFree>;
+using Event = std::unique_ptr<std::remove_pointer<hipEvent_t>::type, EventDestroy>;
+inline hipError_t mem_alloc(DeviceMem* m, size_t bytes) { void* p = nullptr; hipError_t e = hipMalloc(&p, bytes); m->reset(p); return e; }
+inline hipError_t mem_alloc(PinnedMem* m, size_t bytes) { void* p = nullptr; hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault); m->reset(p); return e; }
+
+// A buffer that grows on demand and never shrinks (contents are not kept).  The old buffer is freed only once the GPU is done with it:
+// after `in_use` (the work that reads it), or, without one, after the whole device has drained.
+template <class Mem> struct Growable {
+    Mem mem;
+    size_t cap = 0;
+    uint8_t* get() const { return static_cast<uint8_t*>(mem.get()); }
+    hipError_t reserve(size_t bytes, hipEvent_t in_use = nullptr) {
+        if (bytes <= cap) return hipSuccess;
+        hipError_t e = in_use ? hipEventSynchronize(in_use) : hipDeviceSynchronize();
+        if (e != hipSuccess) return e;
+        mem.reset(); cap = 0;
+        if ((e = mem_alloc(&mem, bytes)) != hipSuccess) return e;
+        cap = bytes;
+        return hipSuccess;
+    }
+};
+
+// one timed launch (option time_convs): HIP events around it on its stream, its algorithmic work, and what ran
+struct LaunchRecord { Event e0, e1; double flop, bytes; std::string layer, kernel; };
+
 struct HostBlobTensor { int dtype; std::vector<int> dims; const uint8_t* data; size_t nbytes; };
 
 struct lumina_ocr {
@@ -93,9 +124,10 @@ struct lumina_ocr {
     bf16_t* ctc_wpk = nullptr; float* ctc_bias = nullptr;
     SvtrModel svtr;
     // ---- workspace ----
-    uint8_t* ws = nullptr; size_t ws_cap = 0, ws_off = 0;
-    std::vector<void*> owned;  // device allocations freed at destroy
-    bf16_t* zero_block = nullptr;  // 256 B of zeros (out-of-image halo source of the LDS-DMA conv)
+    Growable<DeviceMem> ws;
+    Arena arena;  // carves ws for the forward in progress (null base: its dry run, which sizes ws)
+    std::vector<DeviceMem> owned;  // weights and tables, freed at destroy
+    bf16_t* zeros = nullptr;  // 256 B of zeros (out-of-image halo source of the LDS-DMA conv); zero_block() uploads it at first use
     int det_sub_batch = 16, rec_sub_batch = 4096, post_group = 64;
     int tail_group = 16;   // pages per pass of the detector's 1/4-resolution tail (lateral in2 -> p2 -> head) inside one det forward
     std::map<std::string, Tensor4> taps;  // last forward's intermediates (debug / parity tests)
@@ -113,18 +145,19 @@ struct lumina_ocr {
     bool fpn_multi = true;  // head.conv1 reads p5 / p4 / p3 / p2 at their own resolution (ring kernel): the FPN concat is never written
     bool fuse_stem = true;  // stem.conv1 + stem.conv2 in one kernel (the first 32-channel tensor stays in LDS)
     bool fuse_mb = true;    // recogniser blocks: expand + depthwise in one kernel (the expanded tensor stays in LDS)
-    // per-kernel event timing (bench roofline): accumulated conv-kernel time of the last det forward
+    // per-kernel event timing (bench roofline): the launches of the last det forward
     bool time_convs = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> conv_events;
-    std::vector<double> conv_flops, conv_bytes;
-    std::vector<std::string> conv_names, conv_kernels;
+    std::vector<LaunchRecord> launches;
     // ---- pre-processing (resize / enhance) ----
     struct Coeffs { int ksize = 0; int* bounds = nullptr; int* kk = nullptr; std::shared_ptr<std::vector<int>> bounds_host; };
     std::map<std::pair<int, int>, Coeffs> coeff_cache;  // (in, out) -> device tables
-    uint8_t* aux = nullptr; size_t aux_cap = 0;         // resize intermediate
-    unsigned long long* sums = nullptr; int sums_cap = 0;
+    Growable<DeviceMem> aux;   // resize intermediate
+    Growable<DeviceMem> sums;  // enhance: per-page grey sums
     int jd_last_passes = 0;   // synchronisation passes the last JPEG decode needed (incl. the one that found nothing to change)
-    uint8_t* jd_stage[2] = {nullptr, nullptr}; size_t jd_stage_cap[2] = {0, 0}; hipEvent_t jd_stage_ev[2] = {nullptr, nullptr}; int jd_stage_next = 0;   // pinned staging buffers of the JPEG decoder (jpegdec.hip)
+    // pinned staging buffers of the JPEG decoder (jpegdec.hip), used in turn; `uploaded` is recorded after the uploads that read one
+    struct Staging { Growable<PinnedMem> buf; Event uploaded; };
+    Staging jd_stage[2];
+    int jd_stage_next = 0;
     float* dk_trig = nullptr; short* dk_wtab = nullptr;   // de-skew tables (deskew.h), uploaded at first use
 };
 
@@ -138,7 +171,8 @@ int eng_rec_forward(lumina_ocr* eng, const uint8_t* crops, const int* widths, in
 int eng_load_svtr(lumina_ocr* eng, const void* blob, size_t n);
 int eng_svtr_forward(lumina_ocr* eng, const uint8_t* crops, const int* widths, int N, int* idx, float* prob, hipStream_t st);
 int eng_ws_reserve(lumina_ocr* eng, size_t bytes);
-void* eng_ws_alloc(lumina_ocr* eng, size_t bytes);
+// a device copy of host data, owned by the engine until destroy (nullptr if the allocation or the copy fails)
+void* eng_upload(lumina_ocr* eng, const void* host, size_t bytes);
 // short_l / short_y: the block's shortcut layer and its output, computed by the same launch (ConvParams::wpk2)
 int eng_run_conv(lumina_ocr* eng, const ConvLayer& L, const Tensor4& x, Tensor4* y, const Tensor4* res, int res_shift, int out_mode,
                  int up_shift, int y_cstride, int y_coff, bool flat, hipStream_t st, const bf16_t* gate = nullptr,

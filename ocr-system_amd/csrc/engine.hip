@@ -13,12 +13,6 @@ int locr_fail(lumina_ocr* eng, const char* what, const char* detail) {
     return 1;
 }
 
-#define HIPCHK(expr)                                                                  \
-    do {                                                                              \
-        hipError_t _e = (expr);                                                       \
-        if (_e != hipSuccess) return locr_fail(eng, #expr, hipGetErrorString(_e));    \
-    } while (0)
-
 // hipFuncAttributeMaxDynamicSharedMemorySize is per device: remember (device, kernel) pairs, not kernels
 #include <mutex>
 #include <set>
@@ -69,35 +63,38 @@ bool parse_blob(lumina_ocr* eng, const void* blob, size_t n, std::map<std::strin
 }
 
 // ------------------------------------------------------------------------------ memory
-static void* dev_upload(lumina_ocr* eng, const void* host, size_t bytes) {
-    void* d = nullptr;
-    if (hipMalloc(&d, bytes ? bytes : 16) != hipSuccess) return nullptr;
-    if (bytes && hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
-    eng->owned.push_back(d);
-    return d;
+void* eng_upload(lumina_ocr* eng, const void* host, size_t bytes) {
+    DeviceMem d;
+    if (mem_alloc(&d, bytes ? bytes : 16) != hipSuccess) return nullptr;
+    if (bytes && hipMemcpy(d.get(), host, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    eng->owned.push_back(std::move(d));
+    return eng->owned.back().get();
 }
 
 int eng_ws_reserve(lumina_ocr* eng, size_t bytes) {
-    if (bytes <= eng->ws_cap) return 0;
-    HIPCHK(hipDeviceSynchronize());
-    if (eng->ws) HIPCHK(hipFree(eng->ws));
-    eng->ws = nullptr; eng->ws_cap = 0;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&eng->ws), bytes));
-    eng->ws_cap = bytes;
+    LOCR_CHECK(eng->ws.reserve(bytes));
     return 0;
 }
 
-void* eng_ws_alloc(lumina_ocr* eng, size_t bytes) {
-    const size_t a = (eng->ws_off + 255) & ~(size_t)255;
-    eng->ws_off = a + bytes;
-    if (eng->ws == nullptr || eng->ws_off > eng->ws_cap) return nullptr;  // dry run or overflow
-    return eng->ws + a;
-}
-
+// the forward in progress takes its tensors from eng->arena: null pointers in its dry run (and past the reservation: see ws_null)
 static Tensor4 ws_tensor(lumina_ocr* eng, int n, int h, int w, int c) {
     Tensor4 t; t.n = n; t.h = h; t.w = w; t.c = c;
-    t.p = static_cast<bf16_t*>(eng_ws_alloc(eng, t.elems() * sizeof(bf16_t)));
+    t.p = eng->arena.take<bf16_t>(t.elems());
     return t;
+}
+
+// a launch site found a null workspace pointer: the dry run (0), or a carve past the reservation, which is an error and never a dry run
+static int ws_null(lumina_ocr* eng, const char* what) {
+    return eng->arena.overflow ? locr_fail(eng, what, "workspace layout exceeds the reservation") : 0;
+}
+
+// 256 B of zeros, uploaded at first use (nullptr if that fails)
+static const bf16_t* zero_block(lumina_ocr* eng) {
+    if (eng->zeros == nullptr) {
+        const uint32_t z[64] = {0};
+        eng->zeros = static_cast<bf16_t*>(eng_upload(eng, z, sizeof(z)));
+    }
+    return eng->zeros;
 }
 
 static inline int rup(int v, int m) { return (v + m - 1) / m * m; }
@@ -134,7 +131,7 @@ static bool make_conv(lumina_ocr* eng, const std::map<std::string, HostBlobTenso
             memcpy(&padded[((size_t)co * taps + t) * cin_p], &src[((size_t)co * taps + t) * cin_r], sizeof(bf16_t) * cin_r);
     std::vector<bf16_t> packed(conv_packed_weight_elems(cout_p, ks, cin_p, L->cfg.bn));
     pack_conv_weights(padded.data(), cout_p, ks, cin_p, L->cfg.bn, L->cfg.ck, packed.data());
-    L->wpk = static_cast<bf16_t*>(dev_upload(eng, packed.data(), packed.size() * sizeof(bf16_t)));
+    L->wpk = static_cast<bf16_t*>(eng_upload(eng, packed.data(), packed.size() * sizeof(bf16_t)));
     // 16x32-tile kernel: operands by LDS-DMA into a 2-deep ring (nw == 6, default: +3..5 % on the 128..256-channel layers) or
     // through registers (nw == 5, LUMINA_CONV_DMA=0)
     static const int dma = getenv("LUMINA_CONV_DMA") != nullptr ? atoi(getenv("LUMINA_CONV_DMA")) : 1;
@@ -142,14 +139,14 @@ static bool make_conv(lumina_ocr* eng, const std::map<std::string, HostBlobTenso
         L->cfg_big = L->cfg; L->cfg_big.nw = dma ? 6 : 5; L->cfg_big.ck = 16;
         std::vector<bf16_t> packed2(conv_packed_weight_elems(cout_p, ks, cin_p, 64));
         pack_conv_weights(padded.data(), cout_p, ks, cin_p, 64, 16, packed2.data(), dma ? 1 : 0);
-        L->wpk_big = static_cast<bf16_t*>(dev_upload(eng, packed2.data(), packed2.size() * sizeof(bf16_t)));
+        L->wpk_big = static_cast<bf16_t*>(eng_upload(eng, packed2.data(), packed2.size() * sizeof(bf16_t)));
     }
     const int ntiles = (cout_p + L->cfg.bn - 1) / L->cfg.bn;
     std::vector<float> bias((size_t)ntiles * L->cfg.bn, 0.f);
     const float* bs = reinterpret_cast<const float*>(b->data);
     const int bn_r = b->dims[0];
     for (int i = 0; i < cout_r; ++i) bias[i] = bs[i % bn_r];
-    L->bias = static_cast<float*>(dev_upload(eng, bias.data(), bias.size() * sizeof(float)));
+    L->bias = static_cast<float*>(eng_upload(eng, bias.data(), bias.size() * sizeof(float)));
     if (!L->wpk || !L->bias) { locr_fail(eng, "device upload failed", name.c_str()); return false; }
     return true;
 }
@@ -202,7 +199,7 @@ static int compose_fpn_p2(lumina_ocr* eng, const std::map<std::string, HostBlobT
 int eng_load_det(lumina_ocr* eng, const void* blob, size_t n) {
     std::map<std::string, HostBlobTensor> m;
     if (!parse_blob(eng, blob, n, &m)) return 1;
-    HIPCHK(hipSetDevice(eng->device));
+    LOCR_CHECK(hipSetDevice(eng->device));
     eng->det.clear();
     // stem.conv1 (Cin = 3): dedicated kernel
     {
@@ -211,8 +208,8 @@ int eng_load_det(lumina_ocr* eng, const void* blob, size_t n) {
         if (w->dims.size() != 4 || w->dims[0] != 32 || w->dims[1] != 3 || w->dims[3] != 3) return locr_fail(eng, "stem.conv1", "shape");
         bf16_t packed[2 * 2 * 32 * 8];
         pack_stem_weights(reinterpret_cast<const bf16_t*>(w->data), 32, packed);
-        eng->stem_wpk = static_cast<bf16_t*>(dev_upload(eng, packed, sizeof(packed)));
-        eng->stem_bias = static_cast<float*>(dev_upload(eng, b->data, 32 * sizeof(float)));
+        eng->stem_wpk = static_cast<bf16_t*>(eng_upload(eng, packed, sizeof(packed)));
+        eng->stem_bias = static_cast<float*>(eng_upload(eng, b->data, 32 * sizeof(float)));
     }
     auto add = [&](const std::string& name, int ks, int stride, int cin, int cout, int act) -> bool {
         return make_conv(eng, m, name, ks, stride, cin, cout, cin, cout, act, &eng->det[name]);
@@ -259,7 +256,7 @@ int eng_load_det(lumina_ocr* eng, const void* blob, size_t n) {
                 for (int hh = 0; hh < 2; ++hh)
                     for (int row = 0; row < 4; ++row)
                         for (int j = 0; j < 8; ++j) img[((ks * 2 + hh) * 32 + row) * 8 + j] = w3s[row * 64 + ks * 16 + hh * 8 + j];
-            Lf.fuse_w = static_cast<bf16_t*>(dev_upload(eng, img.data(), img.size() * sizeof(bf16_t)));
+            Lf.fuse_w = static_cast<bf16_t*>(eng_upload(eng, img.data(), img.size() * sizeof(bf16_t)));
         }
         Lf.fuse_b = reinterpret_cast<const float*>(b3->data)[0];
         if (!Lf.fuse_w) return locr_fail(eng, "upload", "head.convt3 fused weights");
@@ -279,6 +276,25 @@ static bool conv_takes_big(const lumina_ocr* eng, const ConvLayer& L, int n, int
     const long long big_min = big_min_env >= 0 ? big_min_env : eng->conv_big_min;
     return (L.force_big && L.wpk_big != nullptr) || (!no_big && !flat && !L.small_only && L.wpk_big != nullptr && big_blocks >= big_min);
 }
+
+// option time_convs: HIP events on the launch stream around ONE launch (the detector's convolutions, and the recogniser paths' launches
+// too: bench.py --config 3 / 5); flop / bytes are the launch's algorithmic work (operands and results once).  The events of a launch
+// that fails go with the timer.
+struct LaunchTimer {
+    lumina_ocr* eng; hipStream_t st; Event e0, e1;
+    LaunchTimer(lumina_ocr* e, hipStream_t s, bool enabled = true) : eng(e), st(s) {
+        if (!enabled || !e->time_convs) return;
+        hipEvent_t a = nullptr, b = nullptr;
+        if (hipEventCreate(&a) == hipSuccess) e0.reset(a);
+        if (hipEventCreate(&b) == hipSuccess) e1.reset(b);
+        if (!e0 || !e1 || hipEventRecord(e0.get(), st) != hipSuccess) { e0.reset(); e1.reset(); }
+    }
+    bool on() const { return e1 != nullptr; }
+    void done(std::string layer, std::string kernel, double flop, double bytes) {
+        if (!on() || hipEventRecord(e1.get(), st) != hipSuccess) return;
+        eng->launches.push_back(LaunchRecord{std::move(e0), std::move(e1), flop, bytes, std::move(layer), std::move(kernel)});
+    }
+};
 
 int eng_run_conv(lumina_ocr* eng, const ConvLayer& L, const Tensor4& x, Tensor4* y, const Tensor4* res, int res_shift, int out_mode,
                  int up_shift, int y_cstride, int y_coff, bool flat, hipStream_t st, const bf16_t* gate, const ConvLayer* short_l, Tensor4* short_y) {
@@ -301,12 +317,8 @@ int eng_run_conv(lumina_ocr* eng, const ConvLayer& L, const Tensor4& x, Tensor4*
         return 0;
     }
     ConvParams p{};
-    if (eng->zero_block == nullptr) {
-        const uint32_t z[64] = {0};
-        eng->zero_block = static_cast<bf16_t*>(dev_upload(eng, z, sizeof(z)));
-        if (!eng->zero_block) return locr_fail(eng, "conv", "zero block upload failed");
-    }
-    p.zeros = eng->zero_block;
+    p.zeros = zero_block(eng);
+    if (!p.zeros) return locr_fail(eng, "conv", "zero block upload failed");
     p.gate = gate; p.gate_hw = x.h * x.w;
     p.x = x.p; p.wpk = L.wpk; p.bias = L.bias; p.res = res ? res->p : nullptr; p.y = y->p;
     p.Cin = L.cin; p.Cout = L.cout; p.act = L.act;
@@ -340,12 +352,8 @@ int eng_run_conv(lumina_ocr* eng, const ConvLayer& L, const Tensor4& x, Tensor4*
         p.wpk2 = short_l->wpk; p.bias2 = short_l->bias; p.y2 = short_y->p; p.y2_cstride = short_y->c;
     }
     if (x.c != L.cin) return locr_fail(eng, "conv input channels mismatch", L.name.c_str());
-    if (x.p == nullptr || y->p == nullptr) return 0;  // dry run (workspace sizing)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (eng->time_convs) {
-        HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-        HIPCHK(hipEventRecord(e0, st));
-    }
+    if (x.p == nullptr || y->p == nullptr) return ws_null(eng, L.name.c_str());  // dry run (workspace sizing)
+    LaunchTimer tm(eng, st);
     if (out_mode == OUT_POOL && (L.wpk_big == nullptr || L.cfg_big.nw != 6)) return locr_fail(eng, "fused max pool needs the LDS-DMA conv kernel", L.name.c_str());
     // 16x32 tiles (less LDS and L2 traffic per MFMA) once they still give >= 2 workgroups per CU on all 256 CUs twice over
     const bool use_big = out_mode == OUT_POOL || p.n_src > 1 || conv_takes_big(eng, L, p.N, p.Ho, p.Wo, flat);   // (a multi-source input is the ring kernel's)
@@ -359,50 +367,31 @@ int eng_run_conv(lumina_ocr* eng, const ConvLayer& L, const Tensor4& x, Tensor4*
     if (!use_ring && (p.x_blk || p.y_blk || p.res_blk)) return locr_fail(eng, "a channel-blocked tensor reached a kernel that cannot address it", L.name.c_str());
     hipError_t e = use_ring ? conv_ring_launch(p, eng->ring_orient, st) : (use_pw ? conv_pw_launch(p, st) : conv_launch(cfg, p, st));
     if (e != hipSuccess) return locr_fail(eng, L.name.c_str(), hipGetErrorString(e));
-    if (eng->time_convs) {
-        HIPCHK(hipEventRecord(e1, st));
-        eng->conv_events.push_back({e0, e1});
+    if (tm.on()) {
         const double px = flat ? (double)p.pix_limit : (double)p.N * p.Ho * p.Wo;
-        eng->conv_flops.push_back((L.alg_flop_per_px > 0 ? px * L.alg_flop_per_px : 2.0 * px * L.ks * L.ks * L.cin * L.cout) +
-                                  (short_l ? 2.0 * px * 4 * short_l->cin * short_l->cout : 0.0));
+        const double flop = (L.alg_flop_per_px > 0 ? px * L.alg_flop_per_px : 2.0 * px * L.ks * L.ks * L.cin * L.cout) +
+                            (short_l ? 2.0 * px * 4 * short_l->cin * short_l->cout : 0.0);
         // algorithmic HBM bytes: input once + output once (+ residual) + weights once
         double in_elems = (double)x.elems();
         if (x.n_src > 1) { in_elems = 0; for (int k = 0; k < x.n_src; ++k) in_elems += (double)x.n * (x.h >> x.xs_shift[k]) * (x.w >> x.xs_shift[k]) * x.src_c(k); }
-        eng->conv_bytes.push_back(2.0 * (in_elems + px * (out_mode == OUT_CONVT && p.fuse_w ? 4.0 : (double)L.cout) * (out_mode == OUT_UPSAMPLE ? (double)(1 << (2 * up_shift)) : (out_mode == OUT_POOL ? 0.25 : 1.0)) + (res ? px * (double)L.cout / (double)(1 << (2 * res_shift)) : 0.0) + (double)L.ks * L.ks * L.cin * L.cout +
-                                         (short_l ? px * (double)short_l->cout + 4.0 * short_l->cin * short_l->cout : 0.0)));
-        eng->conv_names.push_back(short_l ? L.name + "+short" : L.name);
+        const double bytes = 2.0 * (in_elems + px * (out_mode == OUT_CONVT && p.fuse_w ? 4.0 : (double)L.cout) * (out_mode == OUT_UPSAMPLE ? (double)(1 << (2 * up_shift)) : (out_mode == OUT_POOL ? 0.25 : 1.0)) + (res ? px * (double)L.cout / (double)(1 << (2 * res_shift)) : 0.0) + (double)L.ks * L.ks * L.cin * L.cout +
+                                    (short_l ? px * (double)short_l->cout + 4.0 * short_l->cin * short_l->cout : 0.0));
         std::string kname = use_pw ? (L.cin == 64 ? "conv_pw_kernel<64>" : "conv_pw_kernel<128>") : conv_kernel_name(cfg);
         if (use_ring) kname = conv_ring_kernel_name(p, eng->ring_orient);
         if (short_l) { const size_t pos = kname.rfind(",0,2>"); if (pos != std::string::npos) kname.replace(pos, 5, ",5,2>"); }   // the fused-shortcut instantiation
         if (out_mode == OUT_POOL && !use_ring) { const size_t pos = kname.rfind(",3,4>"); if (pos != std::string::npos) kname.replace(pos, 5, ",4,4>"); }  // the fused-pool instantiation
-        eng->conv_kernels.push_back(kname);
+        tm.done(short_l ? L.name + "+short" : L.name, kname, flop, bytes);
     }
     return 0;
 }
 
 #define RUN(expr) do { if ((expr) != 0) return 1; } while (0)
 
-// option time_convs: HIP events on the launch stream around ONE launch of the recogniser paths too (bench.py --config 3 / 5);
-// flop / bytes are the launch's algorithmic work (operands and results once)
-struct LaunchTimer {
-    lumina_ocr* eng; hipStream_t st; hipEvent_t e0 = nullptr, e1 = nullptr; bool on;
-    LaunchTimer(lumina_ocr* e, hipStream_t s, bool enabled) : eng(e), st(s), on(enabled && e->time_convs) {
-        if (on) { on = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess && hipEventRecord(e0, st) == hipSuccess; }
-    }
-    void done(const std::string& layer, const std::string& kernel, double flop, double bytes) {
-        if (!on || hipEventRecord(e1, st) != hipSuccess) return;
-        eng->conv_events.push_back({e0, e1});
-        eng->conv_flops.push_back(flop); eng->conv_bytes.push_back(bytes);
-        eng->conv_names.push_back(layer); eng->conv_kernels.push_back(kernel);
-    }
-};
-
 static void tap(lumina_ocr* eng, const char* name, const Tensor4& t) { if (eng->keep_taps && t.p) eng->taps[name] = t; }
 
 // ------------------------------------------------------------------------------ det forward
 static int det_forward_sub(lumina_ocr* eng, const uint8_t* pages, int B, int H, int W, int Hp, int Wp, bf16_t* prob, hipStream_t st) {
-    eng->ws_off = 0;
-    const bool dry = (eng->ws == nullptr) || pages == nullptr;
+    const bool dry = eng->arena.counting();
     auto& D = eng->det;
     // stem.conv1 + stem.conv2 fused (the first half-resolution tensor stays in LDS) unless it is wanted as a tap
     ConvLayer& c2 = D["stem.conv2"];
@@ -557,24 +546,28 @@ static int det_forward_sub(lumina_ocr* eng, const uint8_t* pages, int B, int H, 
     return head_tail(h1, prob, B);
 }
 
+// A forward over n images in sub-batches of sb: run(b0, nb) -> 0 / 1 runs images b0 .. b0 + nb - 1, taking its tensors from eng->arena.
+// A dry run of one full sub-batch on a counting arena (run(0, sb): no launch) sizes the workspace; every sub-batch then carves it afresh.
+template <class Run> static int forward_sub_batched(lumina_ocr* eng, int n, int sb, Run&& run) {
+    eng->arena = Arena();
+    RUN(run(0, sb));
+    RUN(eng_ws_reserve(eng, eng->arena.off + 4096));
+    eng->taps.clear();
+    for (int b0 = 0; b0 < n; b0 += sb) {
+        eng->arena = Arena(eng->ws.get(), eng->ws.cap);
+        RUN(run(b0, n - b0 < sb ? n - b0 : sb));
+        if (eng->arena.overflow) return ws_null(eng, "forward");
+    }
+    return 0;
+}
+
 int eng_det_forward(lumina_ocr* eng, const uint8_t* pages, int B, int H, int W, int Hp, int Wp, bf16_t* prob, hipStream_t st) {
     if (!eng->det_loaded) return locr_fail(eng, "det_forward", "det weights not loaded");
     if (Hp % 32 || Wp % 32 || Hp < H || Wp < W || B <= 0) return locr_fail(eng, "det_forward", "Hp/Wp must be multiples of 32 and >= H/W");
-    HIPCHK(hipSetDevice(eng->device));
-    const int sb = eng->det_sub_batch < B ? eng->det_sub_batch : B;
-    // size the workspace with a dry run
-    uint8_t* keep = eng->ws; eng->ws = nullptr;
-    int rc = det_forward_sub(eng, nullptr, sb, H, W, Hp, Wp, nullptr, st);
-    const size_t need = eng->ws_off + 4096;
-    eng->ws = keep;
-    if (rc) return rc;
-    RUN(eng_ws_reserve(eng, need));
-    eng->taps.clear();
-    for (int b0 = 0; b0 < B; b0 += sb) {
-        const int nb = (B - b0) < sb ? (B - b0) : sb;
-        RUN(det_forward_sub(eng, pages + (size_t)b0 * H * W * 3, nb, H, W, Hp, Wp, prob + (size_t)b0 * Hp * Wp, st));
-    }
-    return 0;
+    LOCR_CHECK(hipSetDevice(eng->device));
+    return forward_sub_batched(eng, B, eng->det_sub_batch < B ? eng->det_sub_batch : B, [&](int b0, int nb) {
+        return det_forward_sub(eng, pages + (size_t)b0 * H * W * 3, nb, H, W, Hp, Wp, prob + (size_t)b0 * Hp * Wp, st);
+    });
 }
 
 // ------------------------------------------------------------------------------ rec
@@ -597,8 +590,8 @@ static bool make_dw(lumina_ocr* eng, const std::map<std::string, HostBlobTensor>
     std::vector<float> bias(c_p, 0.f);
     memcpy(bias.data(), b->data, sizeof(float) * c_r);
     L->k = k; L->c = c_p;
-    L->w = static_cast<bf16_t*>(dev_upload(eng, wt.data(), wt.size() * sizeof(bf16_t)));
-    L->bias = static_cast<float*>(dev_upload(eng, bias.data(), bias.size() * sizeof(float)));
+    L->w = static_cast<bf16_t*>(eng_upload(eng, wt.data(), wt.size() * sizeof(bf16_t)));
+    L->bias = static_cast<float*>(eng_upload(eng, bias.data(), bias.size() * sizeof(float)));
     return L->w && L->bias;
 }
 
@@ -614,17 +607,17 @@ static bool make_se(lumina_ocr* eng, const std::map<std::string, HostBlobTensor>
     std::vector<float> bb2(c_p, 0.f);
     memcpy(bb2.data(), b2->data, sizeof(float) * c_r);
     L->c = c_p; L->mid = mid;
-    L->w1 = static_cast<bf16_t*>(dev_upload(eng, a.data(), a.size() * sizeof(bf16_t)));
-    L->w2 = static_cast<bf16_t*>(dev_upload(eng, bmat.data(), bmat.size() * sizeof(bf16_t)));
-    L->b1 = static_cast<float*>(dev_upload(eng, b1->data, sizeof(float) * mid));
-    L->b2 = static_cast<float*>(dev_upload(eng, bb2.data(), bb2.size() * sizeof(float)));
+    L->w1 = static_cast<bf16_t*>(eng_upload(eng, a.data(), a.size() * sizeof(bf16_t)));
+    L->w2 = static_cast<bf16_t*>(eng_upload(eng, bmat.data(), bmat.size() * sizeof(bf16_t)));
+    L->b1 = static_cast<float*>(eng_upload(eng, b1->data, sizeof(float) * mid));
+    L->b2 = static_cast<float*>(eng_upload(eng, bb2.data(), bb2.size() * sizeof(float)));
     return L->w1 && L->w2 && L->b1 && L->b2;
 }
 
 int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n) {
     std::map<std::string, HostBlobTensor> m;
     if (!parse_blob(eng, blob, n, &m)) return 1;
-    HIPCHK(hipSetDevice(eng->device));
+    LOCR_CHECK(hipSetDevice(eng->device));
     const double scale = 0.5;
     const int c0 = make_div(16 * scale);
     {
@@ -635,8 +628,8 @@ int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n) {
         pack_stem_weights(reinterpret_cast<const bf16_t*>(w->data), c0, packed);
         float bias[32] = {0};
         memcpy(bias, b->data, sizeof(float) * c0);
-        eng->rstem_wpk = static_cast<bf16_t*>(dev_upload(eng, packed, sizeof(packed)));
-        eng->rstem_bias = static_cast<float*>(dev_upload(eng, bias, sizeof(bias)));
+        eng->rstem_wpk = static_cast<bf16_t*>(eng_upload(eng, packed, sizeof(packed)));
+        eng->rstem_bias = static_cast<float*>(eng_upload(eng, bias, sizeof(bias)));
     }
     struct Row { int k, exp, c; bool se; int act, sh; };
     const Row rows[11] = {{3, 16, 16, true, ACT_RELU, 1},    {3, 72, 24, false, ACT_RELU, 2},   {3, 88, 24, false, ACT_RELU, 1},
@@ -664,8 +657,8 @@ int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n) {
             mbconv_pack_expand(padded.data(), ec, cc, packed.data());
             std::vector<float> bias((size_t)((ec + 31) / 32) * 32, 0.f);
             memcpy(bias.data(), b->data, sizeof(float) * B.exp);
-            B.we_pk = static_cast<bf16_t*>(dev_upload(eng, packed.data(), packed.size() * sizeof(bf16_t)));
-            B.be_pk = static_cast<float*>(dev_upload(eng, bias.data(), bias.size() * sizeof(float)));
+            B.we_pk = static_cast<bf16_t*>(eng_upload(eng, packed.data(), packed.size() * sizeof(bf16_t)));
+            B.be_pk = static_cast<float*>(eng_upload(eng, bias.data(), bias.size() * sizeof(float)));
             if (!B.we_pk || !B.be_pk) return locr_fail(eng, "upload", (p + ".expand (fused)").c_str());
         }
         if (B.se && !make_se(eng, m, p, B.exp, cp16(B.exp), B.se_mid, &B.sel)) return 1;
@@ -694,7 +687,7 @@ int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n) {
         eng->xproj[l].name = "lstm.l" + std::to_string(l) + ".xproj";
         std::vector<uint8_t> hcat(hf->second.nbytes + hb->second.nbytes);
         memcpy(hcat.data(), hf->second.data, hf->second.nbytes); memcpy(hcat.data() + hf->second.nbytes, hb->second.data, hb->second.nbytes);
-        eng->whh[l] = static_cast<bf16_t*>(dev_upload(eng, hcat.data(), hcat.size()));
+        eng->whh[l] = static_cast<bf16_t*>(eng_upload(eng, hcat.data(), hcat.size()));
         if (!eng->whh[l]) return locr_fail(eng, "upload", "whh");
     }
     {
@@ -706,22 +699,24 @@ int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n) {
         pack_ctc_weights(reinterpret_cast<const bf16_t*>(w->second.data), C, 2 * Hh, packed.data());
         std::vector<float> bias((size_t)eng->ctc_ntiles * 64, -1.0e30f);
         memcpy(bias.data(), b->second.data, sizeof(float) * C);
-        eng->ctc_wpk = static_cast<bf16_t*>(dev_upload(eng, packed.data(), packed.size() * sizeof(bf16_t)));
-        eng->ctc_bias = static_cast<float*>(dev_upload(eng, bias.data(), bias.size() * sizeof(float)));
+        eng->ctc_wpk = static_cast<bf16_t*>(eng_upload(eng, packed.data(), packed.size() * sizeof(bf16_t)));
+        eng->ctc_bias = static_cast<float*>(eng_upload(eng, bias.data(), bias.size() * sizeof(float)));
         if (!eng->ctc_wpk || !eng->ctc_bias) return locr_fail(eng, "upload", "ctc");
     }
     eng->rec_loaded = true;
     return 0;
 }
 
-#define LAUNCH(name, expr)                                                                  \
-    do {                                                                                    \
-        if (!dry) { hipError_t _e = (expr); if (_e != hipSuccess) return locr_fail(eng, name, hipGetErrorString(_e)); } \
+#define LAUNCH(name, expr)                                                                                        \
+    do {                                                                                                          \
+        if (!dry) {                                                                                               \
+            if (eng->arena.overflow) return ws_null(eng, name);                                                   \
+            hipError_t _e = (expr); if (_e != hipSuccess) return locr_fail(eng, name, hipGetErrorString(_e));     \
+        }                                                                                                         \
     } while (0)
 
 static int rec_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* widths, int N, int* idx, float* prob, hipStream_t st) {
-    eng->ws_off = 0;
-    const bool dry = (eng->ws == nullptr) || crops == nullptr;
+    const bool dry = eng->arena.counting();
     const int T = 80;
     Tensor4 x = ws_tensor(eng, N, 16, 160, 16);
     if (!dry && x.p) {
@@ -744,11 +739,11 @@ static int rec_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* wid
         Tensor4 e1{};
         if (!fused_mb || dry) e1 = ws_tensor(eng, N, x.h, x.w, cp16(B.exp));   // (dry run sizes the arena for the unfused path too)
         Tensor4 d = ws_tensor(eng, N, ho, x.w, cp16(B.exp));
-        float* pool = B.se ? static_cast<float*>(eng_ws_alloc(eng, (size_t)N * mb_strips(x.w) * d.c * sizeof(float))) : nullptr;
+        float* pool = B.se ? eng->arena.take<float>((size_t)N * mb_strips(x.w) * d.c) : nullptr;
         if (fused_mb) {
             mp.x = x.p; mp.d = d.p; mp.pool = pool;   // squeeze-excite blocks: the pooled sums leave with the tile (the tensor is not read again for them)
             if (!dry && x.p && d.p) {
-                LaunchTimer tm(eng, st, true);
+                LaunchTimer tm(eng, st);
                 LAUNCH("mbconv", mbconv_launch(mp, B.k, B.stride_h, st));
                 const double opx = (double)N * ho * x.w, ipx = (double)N * x.h * x.w;
                 tm.done("rec.b" + std::to_string(bi) + ".expand+dw", "mbconv_kernel<" + std::to_string(B.k) + "," + std::to_string(B.stride_h) + "," + std::to_string(B.act) + ">",
@@ -761,7 +756,7 @@ static int rec_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* wid
         }
         const bf16_t* se_gate_ptr = nullptr;
         if (B.se) {
-            bf16_t* gate = static_cast<bf16_t*>(eng_ws_alloc(eng, (size_t)N * d.c * sizeof(bf16_t)));
+            bf16_t* gate = eng->arena.take<bf16_t>((size_t)N * d.c);
             LAUNCH("se_fc", se_fc_launch(pool, mb_strips(d.w), B.sel.w1, B.sel.b1, B.sel.w2, B.sel.b2, gate, N, d.h * d.w, d.c, B.sel.mid, st));
             se_gate_ptr = gate;   // the scaling itself is fused into the project conv's operand staging
         }
@@ -791,9 +786,8 @@ static int rec_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* wid
         CtcFcParams cp{};
         cp.seq = seq.p; cp.wpk = eng->ctc_wpk; cp.bias = eng->ctc_bias; cp.out_idx = idx; cp.out_prob = prob;
         cp.M = N * T; cp.K = 192; cp.C = eng->num_classes; cp.ntiles = eng->ctc_ntiles;
-        LaunchTimer tm(eng, st, true);
-        hipError_t e = ctc_fc_argmax_launch(cp, st);
-        if (e != hipSuccess) return locr_fail(eng, "ctc_fc_argmax", hipGetErrorString(e));
+        LaunchTimer tm(eng, st);
+        LAUNCH("ctc_fc_argmax", ctc_fc_argmax_launch(cp, st));
         tm.done("ctc.fc+argmax", "ctc_fc_argmax_kernel<0>", 2.0 * cp.M * cp.K * cp.C, 2.0 * cp.M * cp.K + 8.0 * cp.M + 2.0 * cp.K * cp.C);
     }
     return 0;
@@ -802,27 +796,17 @@ static int rec_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* wid
 int eng_rec_forward(lumina_ocr* eng, const uint8_t* crops, const int* widths, int N, int* idx, float* prob, hipStream_t st) {
     if (!eng->rec_loaded) return locr_fail(eng, "rec_forward", "rec weights not loaded");
     if (N <= 0) return 0;
-    HIPCHK(hipSetDevice(eng->device));
-    const int sb = eng->rec_sub_batch < N ? eng->rec_sub_batch : N;
-    uint8_t* keep = eng->ws; eng->ws = nullptr;
-    int rc = rec_forward_sub(eng, nullptr, nullptr, sb, nullptr, nullptr, st);
-    const size_t need = eng->ws_off + 4096;
-    eng->ws = keep;
-    if (rc) return rc;
-    RUN(eng_ws_reserve(eng, need));
-    eng->taps.clear();
-    for (int b0 = 0; b0 < N; b0 += sb) {
-        const int nb = (N - b0) < sb ? (N - b0) : sb;
-        RUN(rec_forward_sub(eng, crops + (size_t)b0 * 32 * 320 * 3, widths ? widths + b0 : nullptr, nb, idx + (size_t)b0 * 80, prob + (size_t)b0 * 80, st));
-    }
-    return 0;
+    LOCR_CHECK(hipSetDevice(eng->device));
+    return forward_sub_batched(eng, N, eng->rec_sub_batch < N ? eng->rec_sub_batch : N, [&](int b0, int nb) {
+        return rec_forward_sub(eng, crops + (size_t)b0 * 32 * 320 * 3, widths ? widths + b0 : nullptr, nb, idx + (size_t)b0 * 80, prob + (size_t)b0 * 80, st);
+    });
 }
 
 // ------------------------------------------------------------------------------ SVTR recogniser (Tiny / Base, bf16 / fp16)
 static float* upload_f32(lumina_ocr* eng, const std::map<std::string, HostBlobTensor>& m, const std::string& name, int n) {
     auto it = m.find(name);
     if (it == m.end() || it->second.dtype != 0 || (int)it->second.dims[0] != n) { locr_fail(eng, "missing/ill-shaped f32 tensor", name.c_str()); return nullptr; }
-    return static_cast<float*>(dev_upload(eng, it->second.data, sizeof(float) * n));
+    return static_cast<float*>(eng_upload(eng, it->second.data, sizeof(float) * n));
 }
 
 static inline uint16_t bf16_bits_to(uint16_t b, int dtype) {   // bf16 bits -> the model's storage type (fp16: exact for |w| >= 2^-14)
@@ -853,8 +837,8 @@ static bool make_linear(lumina_ocr* eng, const std::map<std::string, HostBlobTen
             for (int c = 0; c < cin; ++c)
                 packed[(size_t)n * K + (flat_k ? t * cin + c : t * cin_pad + c)] = bf16_bits_to(src[((size_t)n * taps + t) * cin + c], dtype);
     L->K = K; L->N = N; L->taps = flat_k ? 1 : taps; L->cin = flat_k ? cin_pad : cin_pad; L->act = act;
-    L->w = static_cast<uint16_t*>(dev_upload(eng, packed.data(), packed.size() * 2));
-    L->bias = static_cast<float*>(dev_upload(eng, b->data, sizeof(float) * N));
+    L->w = static_cast<uint16_t*>(eng_upload(eng, packed.data(), packed.size() * 2));
+    L->bias = static_cast<float*>(eng_upload(eng, b->data, sizeof(float) * N));
     if (!ln.empty()) {
         L->gamma = upload_f32(eng, m, ln + ".g", N); L->beta = upload_f32(eng, m, ln + ".b", N);
         if (!L->gamma || !L->beta) return false;
@@ -866,7 +850,7 @@ static bool make_linear(lumina_ocr* eng, const std::map<std::string, HostBlobTen
 int eng_load_svtr(lumina_ocr* eng, const void* blob, size_t n) {
     std::map<std::string, HostBlobTensor> m;
     if (!parse_blob(eng, blob, n, &m)) return 1;
-    HIPCHK(hipSetDevice(eng->device));
+    LOCR_CHECK(hipSetDevice(eng->device));
     SvtrModel& M = eng->svtr;
     M = SvtrModel();
     {   // variant + storage type
@@ -895,7 +879,7 @@ int eng_load_svtr(lumina_ocr* eng, const void* blob, size_t n) {
         const bf16_t* src = reinterpret_cast<const bf16_t*>(it->second.data);
         std::vector<uint16_t> pos((size_t)640 * d0);
         for (size_t i = 0; i < pos.size(); ++i) pos[i] = bf16_bits_to(src[i], dt);
-        M.pos = static_cast<uint16_t*>(dev_upload(eng, pos.data(), pos.size() * 2));
+        M.pos = static_cast<uint16_t*>(eng_upload(eng, pos.data(), pos.size() * 2));
         if (!M.pos) return locr_fail(eng, "upload", "svtr.pos");
     }
     int idx = 0, gh = 8;
@@ -931,8 +915,8 @@ int eng_load_svtr(lumina_ocr* eng, const void* blob, size_t n) {
         pack_ctc_weights(conv.data(), C, M.out_ch, packed.data());
         std::vector<float> bias((size_t)M.ctc_ntiles * 64, -1.0e30f);
         memcpy(bias.data(), b->second.data, sizeof(float) * C);
-        M.ctc_wpk = static_cast<bf16_t*>(dev_upload(eng, packed.data(), packed.size() * sizeof(bf16_t)));
-        M.ctc_bias = static_cast<float*>(dev_upload(eng, bias.data(), bias.size() * sizeof(float)));
+        M.ctc_wpk = static_cast<bf16_t*>(eng_upload(eng, packed.data(), packed.size() * sizeof(bf16_t)));
+        M.ctc_bias = static_cast<float*>(eng_upload(eng, bias.data(), bias.size() * sizeof(float)));
         if (!M.ctc_wpk || !M.ctc_bias) return locr_fail(eng, "upload", "svtr ctc");
     }
     M.loaded = true;
@@ -941,19 +925,15 @@ int eng_load_svtr(lumina_ocr* eng, const void* blob, size_t n) {
 
 // one svtr_gemm launch: y = epi(gather(x) w^T + b)
 static int run_linear(lumina_ocr* eng, const SvtrLinear& L, const Tensor4& x, Tensor4* y, const bf16_t* res, int res_mod, int res_post, int hin, int win,
-                      int hout, int wout, int sh, int sw, bool dry, hipStream_t st) {
-    if (dry) return 0;
-    if (eng->zero_block == nullptr) {
-        const uint32_t z[64] = {0};
-        eng->zero_block = static_cast<bf16_t*>(dev_upload(eng, z, sizeof(z)));
-        if (!eng->zero_block) return locr_fail(eng, "svtr", "zero block upload failed");
-    }
+                      int hout, int wout, int sh, int sw, hipStream_t st) {
+    if (x.p == nullptr || y->p == nullptr) return ws_null(eng, "svtr linear");  // dry run (workspace sizing)
     SvtrGemmParams p{};
     p.x = x.p; p.w = L.w; p.bias = L.bias; p.res = res; p.res_mod = res_mod; p.res_post = res_post; p.gamma = L.gamma; p.beta = L.beta; p.y = y->p;
-    p.zeros = eng->zero_block; p.M = (int)(y->elems() / L.N); p.K = L.K; p.N = L.N; p.act = L.act; p.eps = 1e-6f;
+    p.zeros = zero_block(eng); p.M = (int)(y->elems() / L.N); p.K = L.K; p.N = L.N; p.act = L.act; p.eps = 1e-6f;
     p.taps = L.taps; p.Cin = L.cin; p.Hin = hin; p.Win = win; p.Tout = hout * wout; p.Wout = wout; p.sh = sh; p.sw = sw;
+    if (!p.zeros) return locr_fail(eng, "svtr", "zero block upload failed");
     if (x.c != L.cin || y->c != L.N) return locr_fail(eng, "svtr linear: channel mismatch", "");
-    LaunchTimer tm(eng, st, true);
+    LaunchTimer tm(eng, st);
     hipError_t e = svtr_gemm_launch(p, eng->svtr.dtype, st);
     if (e != hipSuccess) return locr_fail(eng, "svtr_gemm", hipGetErrorString(e));
     // algorithmic bytes: the input tensor, the weights, the result and the residual once (a 9-tap gather re-reads its input from cache)
@@ -963,16 +943,15 @@ static int run_linear(lumina_ocr* eng, const SvtrLinear& L, const Tensor4& x, Te
 }
 
 static int svtr_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* widths, int N, int* idx, float* prob, hipStream_t st) {
-    eng->ws_off = 0;
-    const bool dry = (eng->ws == nullptr) || crops == nullptr;
+    const bool dry = eng->arena.counting();
     SvtrModel& M = eng->svtr;
     const int T = 80, dt = M.dtype, d0 = M.dims[0];
     Tensor4 patches = ws_tensor(eng, N, 16, 160, 32);
     LAUNCH("svtr.im2col", svtr_im2col_launch(crops, widths, patches.p, N, dt, st));
     Tensor4 e1 = ws_tensor(eng, N, 16, 160, d0 / 2);
-    RUN(run_linear(eng, M.pe1, patches, &e1, nullptr, 0, 0, 1, 1, 1, 1, 1, 1, dry, st));
+    RUN(run_linear(eng, M.pe1, patches, &e1, nullptr, 0, 0, 1, 1, 1, 1, 1, 1, st));
     Tensor4 x = ws_tensor(eng, N, 8, 80, d0);   // patch embedding 2 (3x3 / s2, GELU, rounded) + positional embedding (rounded again)
-    RUN(run_linear(eng, M.pe2, e1, &x, M.pos, 640, 1, 16, 160, 8, 80, 2, 2, dry, st));
+    RUN(run_linear(eng, M.pe2, e1, &x, M.pos, 640, 1, 16, 160, 8, 80, 2, 2, st));
     tap(eng, "svtr.embed", x);
     int stage = 0;
     for (size_t bi = 0; bi < M.blocks.size(); ++bi) {
@@ -981,13 +960,13 @@ static int svtr_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* wi
         if (want_stage != stage) {
             // height merging: 3x3 conv, stride (2, 1), + LayerNorm (fused epilogue)
             Tensor4 y = ws_tensor(eng, N, x.h / 2, x.w, M.dims[stage + 1]);
-            RUN(run_linear(eng, M.sub[stage], x, &y, nullptr, 0, 0, x.h, x.w, x.h / 2, x.w, 2, 1, dry, st));
+            RUN(run_linear(eng, M.sub[stage], x, &y, nullptr, 0, 0, x.h, x.w, x.h / 2, x.w, 2, 1, st));
             tap(eng, stage == 0 ? "svtr.sub0" : "svtr.sub1", y);
             x = y; ++stage;
         }
         const int Tk = x.h * x.w, c = B.dim;
         Tensor4 qkv = ws_tensor(eng, N, x.h, x.w, 3 * c);
-        RUN(run_linear(eng, B.qkv, x, &qkv, nullptr, 0, 0, 1, 1, 1, 1, 1, 1, dry, st));
+        RUN(run_linear(eng, B.qkv, x, &qkv, nullptr, 0, 0, 1, 1, 1, 1, 1, 1, st));
         Tensor4 att = ws_tensor(eng, N, x.h, x.w, c);
         {
             LaunchTimer tm(eng, st, !dry);
@@ -996,26 +975,25 @@ static int svtr_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* wi
             tm.done("svtr.attn", std::string("svtr_attn_kernel<") + (dt ? "1>" : "0>"), 4.0 * N * Tk * keys * c, 2.0 * N * Tk * 4.0 * c);
         }
         Tensor4 x1 = ws_tensor(eng, N, x.h, x.w, c);
-        RUN(run_linear(eng, B.proj, att, &x1, x.p, 0, 0, 1, 1, 1, 1, 1, 1, dry, st));        // + residual, LayerNorm 1
+        RUN(run_linear(eng, B.proj, att, &x1, x.p, 0, 0, 1, 1, 1, 1, 1, 1, st));        // + residual, LayerNorm 1
         Tensor4 f1 = ws_tensor(eng, N, x.h, x.w, 4 * c);
-        RUN(run_linear(eng, B.fc1, x1, &f1, nullptr, 0, 0, 1, 1, 1, 1, 1, 1, dry, st));
+        RUN(run_linear(eng, B.fc1, x1, &f1, nullptr, 0, 0, 1, 1, 1, 1, 1, 1, st));
         Tensor4 x2 = ws_tensor(eng, N, x.h, x.w, c);
-        RUN(run_linear(eng, B.fc2, f1, &x2, x1.p, 0, 0, 1, 1, 1, 1, 1, 1, dry, st));         // + residual, LayerNorm 2
+        RUN(run_linear(eng, B.fc2, f1, &x2, x1.p, 0, 0, 1, 1, 1, 1, 1, 1, st));         // + residual, LayerNorm 2
         tap(eng, ("svtr.b" + std::to_string(bi)).c_str(), x2);
         x = x2;
     }
     Tensor4 pooled = ws_tensor(eng, N, 1, T, M.dims[2]);
     LAUNCH("svtr.pool", svtr_rowmean_launch(x.p, pooled.p, N, x.h, x.w, M.dims[2], dt, st));
     Tensor4 seq = ws_tensor(eng, N, 1, T, M.out_ch);
-    RUN(run_linear(eng, M.last, pooled, &seq, nullptr, 0, 0, 1, 1, 1, 1, 1, 1, dry, st));
+    RUN(run_linear(eng, M.last, pooled, &seq, nullptr, 0, 0, 1, 1, 1, 1, 1, 1, st));
     tap(eng, "svtr.seq", seq);
     if (!dry) {
         CtcFcParams cp{};
         cp.seq = seq.p; cp.wpk = M.ctc_wpk; cp.bias = M.ctc_bias; cp.out_idx = idx; cp.out_prob = prob;
         cp.M = N * T; cp.K = M.out_ch; cp.C = M.num_classes; cp.ntiles = M.ctc_ntiles; cp.f16 = dt;
-        LaunchTimer tm(eng, st, true);
-        hipError_t e = ctc_fc_argmax_launch(cp, st);
-        if (e != hipSuccess) return locr_fail(eng, "svtr ctc_fc_argmax", hipGetErrorString(e));
+        LaunchTimer tm(eng, st);
+        LAUNCH("svtr ctc_fc_argmax", ctc_fc_argmax_launch(cp, st));
         tm.done("svtr.ctc.fc+argmax", std::string("ctc_fc_argmax_kernel<") + (dt ? "1>" : "0>"), 2.0 * cp.M * cp.K * cp.C, 2.0 * cp.M * cp.K + 8.0 * cp.M + 2.0 * cp.K * cp.C);
     }
     return 0;
@@ -1024,20 +1002,11 @@ static int svtr_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* wi
 int eng_svtr_forward(lumina_ocr* eng, const uint8_t* crops, const int* widths, int N, int* idx, float* prob, hipStream_t st) {
     if (!eng->svtr.loaded) return locr_fail(eng, "svtr_forward", "SVTR weights not loaded");
     if (N <= 0) return 0;
-    HIPCHK(hipSetDevice(eng->device));
+    LOCR_CHECK(hipSetDevice(eng->device));
     int sb = eng->rec_sub_batch / (eng->svtr.dims[2] > 256 ? 4 : 2);   // ~3 MB (Tiny) / ~7 MB (Base) of activations per crop
     if (sb < 1) sb = 1;
     if (sb > N) sb = N;
-    uint8_t* keep = eng->ws; eng->ws = nullptr;
-    int rc = svtr_forward_sub(eng, nullptr, nullptr, sb, nullptr, nullptr, st);
-    const size_t need = eng->ws_off + 4096;
-    eng->ws = keep;
-    if (rc) return rc;
-    RUN(eng_ws_reserve(eng, need));
-    eng->taps.clear();
-    for (int b0 = 0; b0 < N; b0 += sb) {
-        const int nb = (N - b0) < sb ? (N - b0) : sb;
-        RUN(svtr_forward_sub(eng, crops + (size_t)b0 * 32 * 320 * 3, widths ? widths + b0 : nullptr, nb, idx + (size_t)b0 * 80, prob + (size_t)b0 * 80, st));
-    }
-    return 0;
+    return forward_sub_batched(eng, N, sb, [&](int b0, int nb) {
+        return svtr_forward_sub(eng, crops + (size_t)b0 * 32 * 320 * 3, widths ? widths + b0 : nullptr, nb, idx + (size_t)b0 * 80, prob + (size_t)b0 * 80, st);
+    });
 }

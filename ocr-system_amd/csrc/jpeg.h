@@ -18,6 +18,6 @@ struct JpegParams {
 size_t jpeg_workspace_bytes(int n, int height, int width);
 // Enqueue the whole encoder (colour transform + DCT + quantisation, symbol statistics, optimal Huffman tables, entropy coding,
 // byte stuffing, header assembly) on `st`; nothing is synchronised.
-hipError_t jpeg_encode_launch(const JpegParams& p, void* workspace, hipStream_t st);
+hipError_t jpeg_encode_launch(const JpegParams& p, void* workspace, size_t ws_bytes, hipStream_t st);
 // Test hook: quantised coefficients only -> coefs [n][mcus][6][64] int16 in zig-zag order (dummy blocks resolved).
 hipError_t jpeg_coefficients_launch(const uint8_t* rgb, int n, int height, int width, int quality, int16_t* coefs, hipStream_t st);

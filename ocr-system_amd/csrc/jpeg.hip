@@ -616,17 +616,31 @@ QTab make_qtab(int quality) {
     }
     return q;
 }
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
-// workspace: coefs | hist | tables | blkbits | totalbits | raw
+// the workspace's regions: one layout sizes it (jpeg_workspace_bytes) and carves it (jpeg_encode_launch)
+struct JpegWorkspace {
+    int16_t* coefs; uint32_t* hist; DevHT* tabs; uint32_t* blkbits; unsigned long long* totalbits;
+    uint32_t* raw; size_t raw_words;   // the entropy-coded stream before stuffing
+    uint32_t* ffcnt; int pieces;       // 0xFF bytes per FIN_PIECE piece of it
+    int* hdrlen;
+};
+static JpegWorkspace jpeg_layout(Arena& a, int n, const Geo& g) {
+    JpegWorkspace w;
+    w.coefs = a.take<int16_t>((size_t)n * g.nblk * 64); w.hist = a.take<uint32_t>((size_t)n * 1024); w.tabs = a.take<DevHT>((size_t)n * 4);
+    w.blkbits = a.take<uint32_t>((size_t)n * g.nblk); w.totalbits = a.take<unsigned long long>(n);
+    w.raw_words = ((size_t)g.nblk * 128 + 64) / 4;
+    w.raw = a.take<uint32_t>((size_t)n * w.raw_words);
+    w.pieces = (int)((w.raw_words * 4 + FIN_PIECE - 1) / FIN_PIECE);
+    w.ffcnt = a.take<uint32_t>((size_t)n * w.pieces); w.hdrlen = a.take<int>(n);
+    return w;
+}
+
 size_t jpeg_workspace_bytes(int n, int height, int width) {
-    const Geo g = make_geo(height, width);
-    const size_t coef = al256((size_t)n * g.nblk * 64 * 2), hist = al256((size_t)n * 1024 * 4), tabs = al256((size_t)n * 4 * sizeof(DevHT));
-    const size_t bb = al256((size_t)n * g.nblk * 4), tbits = al256((size_t)n * 8), raw = al256((size_t)n * ((size_t)g.nblk * 128 + 64));
-    const size_t pieces = ((size_t)g.nblk * 128 + 64 + FIN_PIECE - 1) / FIN_PIECE;
-    return coef + hist + tabs + bb + tbits + raw + al256((size_t)n * pieces * 4) + al256((size_t)n * 4);
+    Arena a;
+    jpeg_layout(a, n, make_geo(height, width));
+    return a.off;
 }
 
 hipError_t jpeg_coefficients_launch(const uint8_t* rgb, int n, int height, int width, int quality, int16_t* coefs, hipStream_t st) {
@@ -637,39 +651,32 @@ hipError_t jpeg_coefficients_launch(const uint8_t* rgb, int n, int height, int w
     return hipGetLastError();
 }
 
-hipError_t jpeg_encode_launch(const JpegParams& p, void* workspace, hipStream_t st) {
+hipError_t jpeg_encode_launch(const JpegParams& p, void* workspace, size_t ws_bytes, hipStream_t st) {
     if (p.n <= 0 || p.height <= 0 || p.width <= 0 || p.height > 65535 || p.width > 65535) return hipErrorInvalidValue;
     const Geo g = make_geo(p.height, p.width);
     const QTab q = make_qtab(p.quality);
-    uint8_t* w = static_cast<uint8_t*>(workspace);
-    auto take = [&](size_t bytes) { void* r = w; w += al256(bytes); return r; };
-    int16_t* coefs = static_cast<int16_t*>(take((size_t)p.n * g.nblk * 64 * 2));
-    uint32_t* hist = static_cast<uint32_t*>(take((size_t)p.n * 1024 * 4));
-    DevHT* tabs = static_cast<DevHT*>(take((size_t)p.n * 4 * sizeof(DevHT)));
-    uint32_t* blkbits = static_cast<uint32_t*>(take((size_t)p.n * g.nblk * 4));
-    unsigned long long* totalbits = static_cast<unsigned long long*>(take((size_t)p.n * 8));
-    const size_t raw_words = ((size_t)g.nblk * 128 + 64) / 4;
-    uint32_t* raw = static_cast<uint32_t*>(take((size_t)p.n * raw_words * 4));
-    const int pieces = (int)((raw_words * 4 + FIN_PIECE - 1) / FIN_PIECE);
-    uint32_t* ffcnt = static_cast<uint32_t*>(take((size_t)p.n * pieces * 4));
-    int* hdrlen = static_cast<int*>(take((size_t)p.n * 4));
-    hipError_t e = hipMemsetAsync(hist, 0, (size_t)p.n * 1024 * 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync(raw, 0, (size_t)p.n * raw_words * 4, st);
+    Arena a(workspace, ws_bytes);
+    const JpegWorkspace w = jpeg_layout(a, p.n, g);
+    if (a.overflow) return hipErrorOutOfMemory;
+    const size_t raw_words = w.raw_words;
+    const int pieces = w.pieces;
+    hipError_t e = hipMemsetAsync(w.hist, 0, (size_t)p.n * 1024 * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(w.raw, 0, (size_t)p.n * raw_words * 4, st);
     if (e != hipSuccess) return e;
-    e = jpeg_coefficients_launch(p.rgb, p.n, p.height, p.width, p.quality, coefs, st);
+    e = jpeg_coefficients_launch(p.rgb, p.n, p.height, p.width, p.quality, w.coefs, st);
     if (e != hipSuccess) return e;
     const dim3 gb((g.nblk + 255) / 256, p.n);
     if (p.optimize) {
-        hipLaunchKernelGGL(jpeg_stats_kernel, gb, dim3(256), 0, st, coefs, g, hist);
-        hipLaunchKernelGGL(jpeg_tables_kernel, dim3(p.n * 4), dim3(64), 0, st, hist, tabs);
+        hipLaunchKernelGGL(jpeg_stats_kernel, gb, dim3(256), 0, st, w.coefs, g, w.hist);
+        hipLaunchKernelGGL(jpeg_tables_kernel, dim3(p.n * 4), dim3(64), 0, st, w.hist, w.tabs);
     } else {
-        hipLaunchKernelGGL(jpeg_std_tables_kernel, dim3(p.n * 4), dim3(64), 0, st, tabs);
+        hipLaunchKernelGGL(jpeg_std_tables_kernel, dim3(p.n * 4), dim3(64), 0, st, w.tabs);
     }
-    hipLaunchKernelGGL(jpeg_blockbits_kernel, gb, dim3(256), 0, st, coefs, g, tabs, blkbits);
-    hipLaunchKernelGGL(jpeg_scan_kernel, dim3(p.n), dim3(256), 0, st, blkbits, g, totalbits);
-    hipLaunchKernelGGL(jpeg_emit_kernel, gb, dim3(256), 0, st, coefs, g, tabs, blkbits, raw, raw_words);
-    hipLaunchKernelGGL(jpeg_ffcount_kernel, dim3(pieces, p.n), dim3(256), 0, st, raw, raw_words, totalbits, ffcnt, pieces);
-    hipLaunchKernelGGL(jpeg_head_kernel, dim3(p.n), dim3(64), 0, st, totalbits, raw_words, tabs, g, q, ffcnt, pieces, hdrlen, p.out, p.out_stride, p.sizes);
-    hipLaunchKernelGGL(jpeg_stuff_kernel, dim3(pieces, p.n), dim3(256), 0, st, raw, raw_words, totalbits, ffcnt, pieces, hdrlen, p.out, p.out_stride);
+    hipLaunchKernelGGL(jpeg_blockbits_kernel, gb, dim3(256), 0, st, w.coefs, g, w.tabs, w.blkbits);
+    hipLaunchKernelGGL(jpeg_scan_kernel, dim3(p.n), dim3(256), 0, st, w.blkbits, g, w.totalbits);
+    hipLaunchKernelGGL(jpeg_emit_kernel, gb, dim3(256), 0, st, w.coefs, g, w.tabs, w.blkbits, w.raw, raw_words);
+    hipLaunchKernelGGL(jpeg_ffcount_kernel, dim3(pieces, p.n), dim3(256), 0, st, w.raw, raw_words, w.totalbits, w.ffcnt, pieces);
+    hipLaunchKernelGGL(jpeg_head_kernel, dim3(p.n), dim3(64), 0, st, w.totalbits, raw_words, w.tabs, g, q, w.ffcnt, pieces, w.hdrlen, p.out, p.out_stride, p.sizes);
+    hipLaunchKernelGGL(jpeg_stuff_kernel, dim3(pieces, p.n), dim3(256), 0, st, w.raw, raw_words, w.totalbits, w.ffcnt, pieces, w.hdrlen, p.out, p.out_stride);
     return hipGetLastError();
 }

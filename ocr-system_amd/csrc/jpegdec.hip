@@ -584,20 +584,27 @@ bool build_huff(const unsigned char bits[17], const unsigned char* vals, JdHuff*
     return true;
 }
 
-template <class T> T* carve(uint8_t*& p, size_t count) {
-    uintptr_t a = (reinterpret_cast<uintptr_t>(p) + 255) & ~(uintptr_t)255;
-    T* r = reinterpret_cast<T*>(a);
-    p = reinterpret_cast<uint8_t*>(a + count * sizeof(T));
-    return r;
+// the workspace's regions for a batch with these totals: one layout sizes it and carves it (jpegdec_run)
+struct JdWorkspace {
+    JdFile* F; JdDyn* D; uint8_t *raw, *clean;   // scan bytes as uploaded / un-stuffed (+ 64: the bit reader's look-ahead)
+    int *keep, *rst; unsigned* seg; JdChunks C; short* coef; uint8_t* plane; int *changed, *host_rc, *status;
+};
+JdWorkspace jd_layout(Arena& a, int n, size_t raw_total, size_t ublk_total, size_t seg_total, size_t chunk_total, size_t blk_total, size_t plane_total) {
+    JdWorkspace w;
+    w.F = a.take<JdFile>(n); w.D = a.take<JdDyn>(n);
+    w.raw = a.take<uint8_t>(raw_total); w.clean = a.take<uint8_t>(raw_total + 64);
+    w.keep = a.take<int>(ublk_total + 8); w.rst = a.take<int>(ublk_total + 8);
+    w.seg = a.take<unsigned>(seg_total);
+    w.C.start_pos = a.take<unsigned>(chunk_total + 8); w.C.start_bk = a.take<int>(chunk_total + 8);
+    w.C.end_pos[0] = a.take<unsigned>(chunk_total + 8); w.C.end_pos[1] = a.take<unsigned>(chunk_total + 8);
+    w.C.end_bk[0] = a.take<int>(chunk_total + 8); w.C.end_bk[1] = a.take<int>(chunk_total + 8);
+    w.C.ndc = a.take<int>(chunk_total + 8); w.C.first_blk = a.take<int>(chunk_total + 8);
+    w.coef = a.take<short>(blk_total * 64); w.plane = a.take<uint8_t>(plane_total);
+    w.changed = a.take<int>((size_t)n * (JD_PASSES + 1)); w.host_rc = a.take<int>(n); w.status = a.take<int>(n);
+    return w;
 }
 
 }  // namespace
-
-#define JDCHK(expr)                                                                   \
-    do {                                                                              \
-        hipError_t _e = (expr);                                                       \
-        if (_e != hipSuccess) return locr_fail(eng, #expr, hipGetErrorString(_e));    \
-    } while (0)
 
 int jpegdec_probe(const uint8_t* file, size_t n, JdInfo* info) {
     HostHeader h;
@@ -616,16 +623,15 @@ int jpegdec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* size
     size_t raw_cap = 0;
     for (int i = 0; i < n; ++i) raw_cap += ((sizes[i] + 16 + 255) & ~(size_t)255);
     // two staging buffers in turn: an asynchronous call's upload may still be queued when the next call fills its buffer
-    const int sb = eng->jd_stage_next; eng->jd_stage_next ^= 1;
-    if (eng->jd_stage_ev[sb]) JDCHK(hipEventSynchronize(eng->jd_stage_ev[sb]));
-    else JDCHK(hipEventCreateWithFlags(&eng->jd_stage_ev[sb], hipEventDisableTiming));
-    if (raw_cap > eng->jd_stage_cap[sb]) {
-        if (eng->jd_stage[sb]) (void)hipHostFree(eng->jd_stage[sb]);
-        eng->jd_stage[sb] = nullptr; eng->jd_stage_cap[sb] = 0;
-        JDCHK(hipHostMalloc(reinterpret_cast<void**>(&eng->jd_stage[sb]), raw_cap + 4096, hipHostMallocDefault));
-        eng->jd_stage_cap[sb] = raw_cap;
+    lumina_ocr::Staging& stage = eng->jd_stage[eng->jd_stage_next]; eng->jd_stage_next ^= 1;
+    if (stage.uploaded) LOCR_CHECK(hipEventSynchronize(stage.uploaded.get()));
+    else {
+        hipEvent_t ev = nullptr;
+        LOCR_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        stage.uploaded.reset(ev);
     }
-    uint8_t* raw = eng->jd_stage[sb];
+    LOCR_CHECK(stage.buf.reserve(raw_cap, stage.uploaded.get()));
+    uint8_t* raw = stage.buf.get();
     size_t raw_total = 0, ublk_total = 0, chunk_total = 0, seg_total = 0, blk_total = 0, plane_total = 0;
     unsigned max_ublk = 0, max_chunks = 0;
     int max_blk = 0, any = 0;
@@ -669,32 +675,13 @@ int jpegdec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* size
     }
     if (!any) { if (async_passes > 0) { /* status is already final */ } return 0; }
     // ---- workspace ----
-    size_t need = 4096;
-    auto add = [&](size_t bytes) { need += (bytes + 255) & ~(size_t)255; };
-    add(sizeof(JdFile) * n); add(sizeof(JdDyn) * n); add(raw_total); add(raw_total + 64); add(4 * ublk_total * 2 + 64); add(4 * seg_total);
-    for (int k = 0; k < 8; ++k) add(4 * chunk_total + 64);
-    add(blk_total * 128); add(plane_total); add(4 * (size_t)n * (JD_PASSES + 1)); add(4096); add(8 * (size_t)n + 512);
-    if (eng_ws_reserve(eng, need)) return 1;
-    uint8_t* p = eng->ws;
-    JdFile* dF = carve<JdFile>(p, (size_t)n);
-    JdDyn* dD = carve<JdDyn>(p, (size_t)n);
-    uint8_t* dRaw = carve<uint8_t>(p, raw_total);
-    uint8_t* dClean = carve<uint8_t>(p, raw_total + 64);
-    int* dKeep = carve<int>(p, ublk_total + 8);
-    int* dRst = carve<int>(p, ublk_total + 8);
-    unsigned* dSeg = carve<unsigned>(p, seg_total);
-    JdChunks C;
-    C.start_pos = carve<unsigned>(p, chunk_total + 8); C.start_bk = carve<int>(p, chunk_total + 8);
-    C.end_pos[0] = carve<unsigned>(p, chunk_total + 8); C.end_pos[1] = carve<unsigned>(p, chunk_total + 8);
-    C.end_bk[0] = carve<int>(p, chunk_total + 8); C.end_bk[1] = carve<int>(p, chunk_total + 8);
-    C.ndc = carve<int>(p, chunk_total + 8); C.first_blk = carve<int>(p, chunk_total + 8);
-    short* dCoef = carve<short>(p, blk_total * 64);
-    uint8_t* dPlane = carve<uint8_t>(p, plane_total);
-    int* dChanged = carve<int>(p, (size_t)n * (JD_PASSES + 1));
-    int* dHostRc = carve<int>(p, (size_t)n);
-    int* dStatus = carve<int>(p, (size_t)n);
-    if ((size_t)(p - eng->ws) > eng->ws_cap) return locr_fail(eng, "jpeg_decode", "workspace layout exceeds the reservation");
-    JDCHK(hipMemcpyAsync(dF, F.data(), sizeof(JdFile) * n, hipMemcpyHostToDevice, st));
+    Arena sizing;
+    jd_layout(sizing, n, raw_total, ublk_total, seg_total, chunk_total, blk_total, plane_total);
+    if (eng_ws_reserve(eng, sizing.off)) return 1;
+    Arena a(eng->ws.get(), eng->ws.cap);
+    const JdWorkspace w = jd_layout(a, n, raw_total, ublk_total, seg_total, chunk_total, blk_total, plane_total);
+    if (a.overflow) return locr_fail(eng, "jpeg_decode", "workspace layout exceeds the reservation");
+    LOCR_CHECK(hipMemcpyAsync(w.F, F.data(), sizeof(JdFile) * n, hipMemcpyHostToDevice, st));
     // scan bytes: host copy into the pinned buffer and the asynchronous upload of the previous files overlap (groups of ~8 MB)
     {
         size_t sent = 0;
@@ -706,47 +693,47 @@ int jpegdec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* size
             memset(raw + f.raw_off + f.raw_len, 0, padded - f.raw_len);
             const size_t end = (size_t)f.raw_off + padded;
             if (end - sent >= (8u << 20) || end == raw_total) {
-                JDCHK(hipMemcpyAsync(dRaw + sent, raw + sent, end - sent, hipMemcpyHostToDevice, st));
+                LOCR_CHECK(hipMemcpyAsync(w.raw + sent, raw + sent, end - sent, hipMemcpyHostToDevice, st));
                 sent = end;
             }
         }
-        if (sent < raw_total) JDCHK(hipMemcpyAsync(dRaw + sent, raw + sent, raw_total - sent, hipMemcpyHostToDevice, st));
+        if (sent < raw_total) LOCR_CHECK(hipMemcpyAsync(w.raw + sent, raw + sent, raw_total - sent, hipMemcpyHostToDevice, st));
     }
-    JDCHK(hipEventRecord(eng->jd_stage_ev[sb], st));   // the staging buffer is free again once the uploads have run
-    JDCHK(hipMemsetAsync(dClean, 0, raw_total + 64, st));
-    JDCHK(hipMemsetAsync(dCoef, 0, blk_total * 128, st));
+    LOCR_CHECK(hipEventRecord(stage.uploaded.get(), st));   // the staging buffer is free again once the uploads have run
+    LOCR_CHECK(hipMemsetAsync(w.clean, 0, raw_total + 64, st));
+    LOCR_CHECK(hipMemsetAsync(w.coef, 0, blk_total * 128, st));
     // ---- 1. un-stuff ----
-    hipLaunchKernelGGL(jd_mark_kernel, dim3(max_ublk, n), dim3(256), 0, st, dF, dRaw, dKeep, dRst);
-    hipLaunchKernelGGL(jd_scan_kernel, dim3(n), dim3(256), 0, st, dF, dKeep, dRst, dD);
-    hipLaunchKernelGGL(jd_compact_kernel, dim3(max_ublk, n), dim3(256), 0, st, dF, dRaw, dKeep, dRst, dD, dClean, dSeg);
+    hipLaunchKernelGGL(jd_mark_kernel, dim3(max_ublk, n), dim3(256), 0, st, w.F, w.raw, w.keep, w.rst);
+    hipLaunchKernelGGL(jd_scan_kernel, dim3(n), dim3(256), 0, st, w.F, w.keep, w.rst, w.D);
+    hipLaunchKernelGGL(jd_compact_kernel, dim3(max_ublk, n), dim3(256), 0, st, w.F, w.raw, w.keep, w.rst, w.D, w.clean, w.seg);
     // ---- 2. synchronise the chunk decoders (Jacobi passes until nothing changes) ----
     std::vector<int> changed((size_t)n * (JD_PASSES + 1));
     const dim3 cgrid((max_chunks + 63) / 64, n);
     int pass = 0;
     if (async_passes > 0) {
         // host parse codes travel with the call (the descriptor upload above was from pageable memory: already consumed)
-        JDCHK(hipMemcpyAsync(dHostRc, status, sizeof(int) * n, hipMemcpyHostToDevice, st));
-        JDCHK(hipMemsetAsync(dChanged, 0, sizeof(int) * (size_t)n * (JD_PASSES + 1), st));
+        LOCR_CHECK(hipMemcpyAsync(w.host_rc, status, sizeof(int) * n, hipMemcpyHostToDevice, st));
+        LOCR_CHECK(hipMemsetAsync(w.changed, 0, sizeof(int) * (size_t)n * (JD_PASSES + 1), st));
         for (; pass < async_passes; ++pass) {
-            if (pass == async_passes - 1) JDCHK(hipMemsetAsync(dChanged, 0, sizeof(int) * n, st));
-            hipLaunchKernelGGL(jd_sync_kernel, cgrid, dim3(64), 0, st, dF, dD, dClean, dSeg, C, pass, dChanged);
+            if (pass == async_passes - 1) LOCR_CHECK(hipMemsetAsync(w.changed, 0, sizeof(int) * n, st));
+            hipLaunchKernelGGL(jd_sync_kernel, cgrid, dim3(64), 0, st, w.F, w.D, w.clean, w.seg, w.C, pass, w.changed);
         }
         eng->jd_last_passes = pass;
-        hipLaunchKernelGGL(jd_blkscan_kernel, dim3(n), dim3(256), 0, st, dF, dD, C);
-        hipLaunchKernelGGL(jd_write_kernel, cgrid, dim3(64), 0, st, dF, dD, dClean, dSeg, C, dCoef);
-        hipLaunchKernelGGL(jd_dc_kernel, dim3(3, n), dim3(256), 0, st, dF, dD, dCoef);
-        hipLaunchKernelGGL(jd_idct_kernel, dim3((max_blk + 31) / 32, n), dim3(256), 0, st, dF, dD, dCoef, dPlane);
-        hipLaunchKernelGGL(jd_color_kernel, dim3((width + 63) / 64, (height + 3) / 4, n), dim3(256), 0, st, dF, dD, dPlane, out_dev, height, width);
-        hipLaunchKernelGGL(jd_status_kernel, dim3((n + 63) / 64), dim3(64), 0, st, dF, dD, dHostRc, dChanged, dStatus, n);
-        JDCHK(hipMemcpyAsync(status, dStatus, sizeof(int) * n, hipMemcpyDeviceToHost, st));
-        JDCHK(hipGetLastError());
+        hipLaunchKernelGGL(jd_blkscan_kernel, dim3(n), dim3(256), 0, st, w.F, w.D, w.C);
+        hipLaunchKernelGGL(jd_write_kernel, cgrid, dim3(64), 0, st, w.F, w.D, w.clean, w.seg, w.C, w.coef);
+        hipLaunchKernelGGL(jd_dc_kernel, dim3(3, n), dim3(256), 0, st, w.F, w.D, w.coef);
+        hipLaunchKernelGGL(jd_idct_kernel, dim3((max_blk + 31) / 32, n), dim3(256), 0, st, w.F, w.D, w.coef, w.plane);
+        hipLaunchKernelGGL(jd_color_kernel, dim3((width + 63) / 64, (height + 3) / 4, n), dim3(256), 0, st, w.F, w.D, w.plane, out_dev, height, width);
+        hipLaunchKernelGGL(jd_status_kernel, dim3((n + 63) / 64), dim3(64), 0, st, w.F, w.D, w.host_rc, w.changed, w.status, n);
+        LOCR_CHECK(hipMemcpyAsync(status, w.status, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+        LOCR_CHECK(hipGetLastError());
         return 0;
     }
     for (;;) {
-        JDCHK(hipMemsetAsync(dChanged, 0, sizeof(int) * changed.size(), st));
-        for (int k = 0; k < JD_PASSES; ++k, ++pass) hipLaunchKernelGGL(jd_sync_kernel, cgrid, dim3(64), 0, st, dF, dD, dClean, dSeg, C, pass, dChanged + (size_t)k * n);
-        JDCHK(hipMemcpyAsync(changed.data(), dChanged, sizeof(int) * changed.size(), hipMemcpyDeviceToHost, st));
-        JDCHK(hipStreamSynchronize(st));
+        LOCR_CHECK(hipMemsetAsync(w.changed, 0, sizeof(int) * changed.size(), st));
+        for (int k = 0; k < JD_PASSES; ++k, ++pass) hipLaunchKernelGGL(jd_sync_kernel, cgrid, dim3(64), 0, st, w.F, w.D, w.clean, w.seg, w.C, pass, w.changed + (size_t)k * n);
+        LOCR_CHECK(hipMemcpyAsync(changed.data(), w.changed, sizeof(int) * changed.size(), hipMemcpyDeviceToHost, st));
+        LOCR_CHECK(hipStreamSynchronize(st));
         bool again = false;
         for (int i = 0; i < n; ++i) again = again || changed[(size_t)(JD_PASSES - 1) * n + i] != 0;
         if (!again) break;
@@ -754,15 +741,15 @@ int jpegdec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* size
     }
     eng->jd_last_passes = pass;
     // ---- 3. coefficients, DC, IDCT, colour ----
-    hipLaunchKernelGGL(jd_blkscan_kernel, dim3(n), dim3(256), 0, st, dF, dD, C);
-    hipLaunchKernelGGL(jd_write_kernel, cgrid, dim3(64), 0, st, dF, dD, dClean, dSeg, C, dCoef);
-    hipLaunchKernelGGL(jd_dc_kernel, dim3(3, n), dim3(256), 0, st, dF, dD, dCoef);
-    hipLaunchKernelGGL(jd_idct_kernel, dim3((max_blk + 31) / 32, n), dim3(256), 0, st, dF, dD, dCoef, dPlane);
-    hipLaunchKernelGGL(jd_color_kernel, dim3((width + 63) / 64, (height + 3) / 4, n), dim3(256), 0, st, dF, dD, dPlane, out_dev, height, width);
+    hipLaunchKernelGGL(jd_blkscan_kernel, dim3(n), dim3(256), 0, st, w.F, w.D, w.C);
+    hipLaunchKernelGGL(jd_write_kernel, cgrid, dim3(64), 0, st, w.F, w.D, w.clean, w.seg, w.C, w.coef);
+    hipLaunchKernelGGL(jd_dc_kernel, dim3(3, n), dim3(256), 0, st, w.F, w.D, w.coef);
+    hipLaunchKernelGGL(jd_idct_kernel, dim3((max_blk + 31) / 32, n), dim3(256), 0, st, w.F, w.D, w.coef, w.plane);
+    hipLaunchKernelGGL(jd_color_kernel, dim3((width + 63) / 64, (height + 3) / 4, n), dim3(256), 0, st, w.F, w.D, w.plane, out_dev, height, width);
     std::vector<JdDyn> dyn((size_t)n);
-    JDCHK(hipMemcpyAsync(dyn.data(), dD, sizeof(JdDyn) * n, hipMemcpyDeviceToHost, st));
-    JDCHK(hipStreamSynchronize(st));
-    JDCHK(hipGetLastError());
+    LOCR_CHECK(hipMemcpyAsync(dyn.data(), w.D, sizeof(JdDyn) * n, hipMemcpyDeviceToHost, st));
+    LOCR_CHECK(hipStreamSynchronize(st));
+    LOCR_CHECK(hipGetLastError());
     for (int i = 0; i < n; ++i)
         if (F[(size_t)i].valid && (dyn[(size_t)i].err || dyn[(size_t)i].nseg < 0)) status[i] = -1;
     return 0;

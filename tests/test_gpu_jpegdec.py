@@ -104,3 +104,33 @@ def test_async_decode_equals_the_synchronous_one_and_reports_too_few_passes(engi
     few, st_few = engine.jpeg_decode_async(files, 480, 640, passes=2)
     torch.cuda.synchronize()
     assert st_few.tolist()[3] == -2 and -5 in st_few.tolist()[:3]             # ~100 KB of noise per file: two passes cannot synchronise ~100 chunks
+
+
+def test_decodes_around_a_resize_that_grows_its_buffer_then_close():
+    """The JPEG decoder's two pinned staging buffers and the resize's device intermediate belong to the engine: growing the one must
+    leave the others alone.  Decode, resize a batch that grows the intermediate, decode twice more (both staging buffers), close."""
+    eng = Engine(0)
+    rng = np.random.default_rng(23)
+    w, h = 320, 240
+    files = []
+    for k in range(3):
+        buf = io.BytesIO()
+        Image.fromarray(rng.integers(0, 256, (h, w, 3), dtype=np.uint8)).save(buf, format="JPEG", quality=90 - 10 * k)
+        files.append(buf.getvalue())
+    want = [pil_decode(f) for f in files]
+
+    def decode_and_check():
+        out, status = eng.jpeg_decode(files, h, w)
+        torch.cuda.synchronize()
+        assert status == [0, 0, 0]
+        for k in range(3):
+            assert np.array_equal(out[k].cpu().numpy(), want[k]), k
+
+    decode_and_check()
+    pages = torch.from_numpy(rng.integers(0, 256, (4, 600, 800, 3), dtype=np.uint8)).cuda()
+    resized = eng.resize_lanczos(pages, 300, 700)       # both passes: the horizontal one writes the intermediate (4 x 600 x 700 x 3)
+    torch.cuda.synchronize()
+    assert resized.shape == (4, 300, 700, 3)
+    decode_and_check()
+    decode_and_check()
+    eng.close()
