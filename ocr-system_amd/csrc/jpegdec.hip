@@ -114,14 +114,15 @@ __global__ __launch_bounds__(256) void jd_scan_kernel(const JdFile* files, int* 
     jd_block_scan(r, n);
     if (threadIdx.x == 0) {
         dyn[blockIdx.x].clean_len = (unsigned)total_k;
-        dyn[blockIdx.x].nseg = total_r > (int)F.seg_cap ? -1 : total_r;   // more markers than the header's restart interval allows: corrupt
+        // exactly one marker between two restart intervals: a missing, extra or empty segment is corrupt
+        dyn[blockIdx.x].nseg = total_r != (F.seg_cap ? (int)F.seg_cap - 1 : 0) ? -1 : total_r;
         dyn[blockIdx.x].err = 0;
         dyn[blockIdx.x].total_dc = 0;
     }
 }
 
 __global__ __launch_bounds__(256) void jd_compact_kernel(const JdFile* files, const unsigned char* rawbuf, const int* blk_keep, const int* blk_rst,
-                                                         const JdDyn* dyn, unsigned char* cleanbuf, unsigned* seg_start) {
+                                                         JdDyn* dyn, unsigned char* cleanbuf, unsigned* seg_start) {
     const JdFile& F = files[blockIdx.y];
     if (!F.valid || blockIdx.x >= F.nublk) return;
     __shared__ int wk[4], wr[4];
@@ -152,6 +153,7 @@ __global__ __launch_bounds__(256) void jd_compact_kernel(const JdFile* files, co
     for (int e = 0; e < 4; ++e) {
         const unsigned j = blockIdx.x * JD_UB + threadIdx.x * 4 + e;
         if (mark[e] && nseg >= 0 && pr < (int)F.seg_cap) seg_start[F.seg_off + pr] = (unsigned)pk;   // the segment after this marker starts at the next kept byte
+        if (mark[e] && raw[j + 1] != 0xD0 + (pr & 7)) dyn[blockIdx.y].err = 1;                        // RSTn out of sequence
         pr += mark[e];
         if (keep[e]) clean[pk] = raw[j];
         pk += keep[e];
@@ -198,6 +200,10 @@ __device__ void jd_span(const JdFile& F, const unsigned* clean_w, unsigned total
     int s = 0;
     { int lo = 0, hi = nseg; while (lo < hi) { const int mid = (lo + hi) >> 1; if (seg[mid] * 8u <= pos) lo = mid + 1; else hi = mid; } s = lo; }
     unsigned seg_end = s < nseg ? seg[s] * 8u : total_bits;
+    // WRITE: every segment holds exactly `restart` MCUs (the last one the rest) and its data ends with them — the next block at a
+    // segment start is s * restart MCUs in, at block 0 of an MCU, and no symbol is cut short by the end of the data
+    const int seg_blks = F.restart * F.bpm;
+    if (WRITE && s > 0 && pos == seg[s - 1] * 8u && (b != 0 || k != 0 || blk != s * seg_blks)) *err = 1;
     int ndc = 0;
     int cur = k > 0 ? blk - 1 : blk;   // block whose AC coefficients are being written
     if (!WRITE) (void)cur;
@@ -207,6 +213,7 @@ __device__ void jd_span(const JdFile& F, const unsigned* clean_w, unsigned total
             bool pad = rem == 0u;
             if (!pad) pad = jd_peek(r, (int)rem) == ((1u << rem) - 1u);
             if (pad) {
+                if (WRITE && (b != 0 || k != 0 || (seg_end < total_bits && blk + ndc != (s + 1) * seg_blks))) *err = 1;
                 if (seg_end >= total_bits) { r.pos = total_bits; b = 0; k = 0; break; }
                 r.pos = seg_end; r.have = 0; b = 0; k = 0;
                 ++s; seg_end = s < nseg ? seg[s] * 8u : total_bits;
@@ -216,7 +223,7 @@ __device__ void jd_span(const JdFile& F, const unsigned* clean_w, unsigned total
         const int comp = F.comp_of_blk[b];
         if (k == 0) {
             int sym = jd_sym(r, F.dc[F.td[comp]]);
-            if (sym < 0 || sym > 15) { if (WRITE) *err = 1; sym = 0; }
+            if (sym < 0 || sym > 11) { if (WRITE) *err = 1; sym = 0; }
             int diff = 0;
             if (sym) { diff = jd_extend((int)jd_peek(r, sym), sym); jd_skip(r, sym); }
             if (WRITE) { cur = blk + ndc; if (cur < F.nblk) coef[(size_t)cur * 64] = (short)diff; else *err = 1; }
@@ -250,6 +257,7 @@ __device__ void jd_span(const JdFile& F, const unsigned* clean_w, unsigned total
             ++s; seg_end = s < nseg ? seg[s] * 8u : total_bits;
         }
     }
+    if (WRITE && r.pos >= total_bits && (b != 0 || k != 0)) *err = 1;   // the data ran out inside a block
     *out_pos = r.pos; *out_bk = (b << 8) | k; *out_ndc = ndc;
 }
 
@@ -375,14 +383,21 @@ __device__ __forceinline__ void jd_idct8(const int in[8], int out[8]) {
     out[2] = tmp12 + tmp1; out[5] = tmp12 - tmp1; out[3] = tmp13 + tmp0; out[4] = tmp13 - tmp0;
 }
 
+// The range where libjpeg-turbo's C islow IDCT and its SIMD versions (16-bit lanes, saturating packs) give the same samples: every
+// de-quantised input and pass-1 output in [-16384, 16383], every output sample before the +128 in [-512, 511] (range_limit wraps
+// beyond it, the SIMD code saturates).  Outside it Pillow's answer depends on the host CPU, so the file is refused (err).
+__device__ __forceinline__ bool jd_out16k(int v) { return (unsigned)(v + 16384) > 32767u; }
+__device__ __forceinline__ bool jd_out512(int v) { return (unsigned)(v + 512) > 1023u; }
+
 // 8 lanes per block: lane l does column l (pass 1, into LDS), then row l (pass 2, one 8-byte store into the component plane)
-__global__ __launch_bounds__(256) void jd_idct_kernel(const JdFile* files, const JdDyn* dyn, const short* coefbuf, unsigned char* planebuf) {
+__global__ __launch_bounds__(256) void jd_idct_kernel(const JdFile* files, JdDyn* dyn, const short* coefbuf, unsigned char* planebuf) {
     const JdFile& F = files[blockIdx.y];
     __shared__ int ws[32][64];
     const int lb = threadIdx.x >> 3, l = threadIdx.x & 7;
     const int B = blockIdx.x * 32 + lb;
     const bool on = F.valid && dyn[blockIdx.y].nseg >= 0 && !dyn[blockIdx.y].err && B < F.nblk;
     int comp = 0, sub = 0, m = 0;
+    bool bad = false;
     if (on) {
         m = B / F.bpm;
         const int i = B - m * F.bpm;
@@ -391,10 +406,10 @@ __global__ __launch_bounds__(256) void jd_idct_kernel(const JdFile* files, const
         const unsigned short* q = F.q[comp];
         int in[8], o[8];
 #pragma unroll
-        for (int r = 0; r < 8; ++r) in[r] = (int)c[8 * r + l] * (int)q[8 * r + l];
+        for (int r = 0; r < 8; ++r) { in[r] = (int)c[8 * r + l] * (int)q[8 * r + l]; bad |= jd_out16k(in[r]); }
         jd_idct8(in, o);
 #pragma unroll
-        for (int r = 0; r < 8; ++r) ws[lb][8 * r + l] = JD_DESCALE(o[r], 11);
+        for (int r = 0; r < 8; ++r) { const int v = JD_DESCALE(o[r], 11); bad |= jd_out16k(v); ws[lb][8 * r + l] = v; }
     }
     __syncthreads();
     if (on) {
@@ -407,8 +422,14 @@ __global__ __launch_bounds__(256) void jd_idct_kernel(const JdFile* files, const
         unsigned char* dst = planebuf + F.plane_off[comp] + (size_t)((my * vsc + by) * 8 + l) * F.pw[comp] + (mx * hsc + bx) * 8;
         unsigned lo = 0, hi = 0;
 #pragma unroll
-        for (int cc = 0; cc < 4; ++cc) { lo |= (unsigned)jd_limit(JD_DESCALE(o[cc], 18)) << (8 * cc); hi |= (unsigned)jd_limit(JD_DESCALE(o[4 + cc], 18)) << (8 * cc); }
+        for (int cc = 0; cc < 4; ++cc) {
+            const int x0 = JD_DESCALE(o[cc], 18), x1 = JD_DESCALE(o[4 + cc], 18);
+            bad |= jd_out512(x0);
+            bad |= jd_out512(x1);
+            lo |= (unsigned)jd_limit(x0) << (8 * cc); hi |= (unsigned)jd_limit(x1) << (8 * cc);
+        }
         *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
+        if (bad) dyn[blockIdx.y].err = 1;   // (read by jd_color_kernel, jd_status_kernel and the synchronous path: that page is not written)
     }
 }
 
@@ -471,10 +492,27 @@ struct HostHeader {
     size_t scan_off = 0, scan_end = 0;
 };
 
+// libjpeg's table check (jdhuff.c jpeg_make_d_derived_tbl): at every length the codes must fit WITHOUT the all-ones code, i.e. the
+// code space is never full, let alone oversubscribed; a DC table holds categories 0 .. 15 only
+bool huff_counts_ok(const unsigned char bits[17], const unsigned char* vals, bool dc) {
+    int code = 0, cnt = 0;
+    for (int l = 1; l <= 16; ++l) {
+        code += bits[l]; cnt += bits[l];
+        if (code >= (1 << l)) return false;
+        code <<= 1;
+    }
+    if (dc)
+        for (int i = 0; i < cnt; ++i)
+            if (vals[i] > 15) return false;
+    return true;
+}
+
+// The same rules as the oracle's parse_header (oracle/csrc/jpegdec_oracle.c): a file one of them accepts, the other accepts too.
 int parse_header(const uint8_t* f, size_t n, HostHeader* h) {
     if (n < 4 || f[0] != 0xFF || f[1] != 0xD8) return -1;
     size_t p = 2;
     bool sof = false;
+    int adobe = -1;   // the APP14 transform flag, -1 = no Adobe marker
     for (;;) {
         if (p + 4 > n || f[p] != 0xFF) return -1;
         while (p < n && f[p] == 0xFF) ++p;
@@ -508,6 +546,7 @@ int parse_header(const uint8_t* f, size_t n, HostHeader* h) {
                 if (cnt > 256 || i + cnt > sl) return -1;
                 memset(h->vals[tc][t], 0, 256);
                 memcpy(h->vals[tc][t], s + i, (size_t)cnt);
+                if (!huff_counts_ok(h->bits[tc][t], h->vals[tc][t], tc == 0)) return -1;
                 i += cnt;
                 h->have_h[tc][t] = true;
             }
@@ -516,7 +555,7 @@ int parse_header(const uint8_t* f, size_t n, HostHeader* h) {
             if (s[0] != 8) return -2;
             h->height = (s[1] << 8) | s[2]; h->width = (s[3] << 8) | s[4]; h->ncomp = s[5];
             if (h->height == 0 || h->width == 0 || (h->ncomp != 1 && h->ncomp != 3)) return -2;
-            if (sl < (size_t)(6 + 3 * h->ncomp)) return -1;
+            if (sl != (size_t)(6 + 3 * h->ncomp)) return -1;   // libjpeg: JERR_BAD_LENGTH
             for (int c = 0; c < h->ncomp; ++c) {
                 if (s[6 + 3 * c] != c + 1) return -2;
                 h->hs[c] = s[7 + 3 * c] >> 4; h->vs[c] = s[7 + 3 * c] & 15; h->tq[c] = s[8 + 3 * c];
@@ -526,10 +565,10 @@ int parse_header(const uint8_t* f, size_t n, HostHeader* h) {
         } else if (m >= 0xC2 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
             return -2;
         } else if (m == 0xDD) {
-            if (sl < 2) return -1;
+            if (sl != 2) return -1;
             h->restart = (s[0] << 8) | s[1];
-        } else if (m == 0xEE) {
-            if (sl >= 12 && memcmp(s, "Adobe", 5) == 0 && s[11] != 1 && h->ncomp != 1) return -2;
+        } else if (m == 0xEE) {   // Adobe: the transform flag is judged after SOF (APP14 usually precedes it)
+            if (sl >= 12 && memcmp(s, "Adobe", 5) == 0) adobe = s[11];
         } else if (m == 0xDA) {
             if (!sof) return -1;
             if (sl < 1 || s[0] != h->ncomp || sl < (size_t)(1 + 2 * h->ncomp + 3)) return -2;
@@ -548,17 +587,21 @@ int parse_header(const uint8_t* f, size_t n, HostHeader* h) {
         if (h->hs[1] != 1 || h->vs[1] != 1 || h->hs[2] != 1 || h->vs[2] != 1) return -2;
         if (!((h->hs[0] == 1 && h->vs[0] == 1) || (h->hs[0] == 2 && h->vs[0] == 1) || (h->hs[0] == 2 && h->vs[0] == 2))) return -2;
     }
+    if (h->ncomp == 3 && adobe >= 0 && adobe != 1) return -2;   // a colour transform other than YCbCr changes the colour model
     // the entropy-coded segment ends at the last EOI (trailing bytes after it are ignored, as libjpeg does)
     size_t e = n;
     while (e >= h->scan_off + 2 && !(f[e - 2] == 0xFF && f[e - 1] == 0xD9)) --e;
     if (e < h->scan_off + 2) return -1;
     h->scan_end = e - 2;
-    // any marker other than RSTn inside the scan (DNL, a second SOS ...) is outside the subset
-    for (const uint8_t* q = f + h->scan_off; q + 1 < f + h->scan_end;) {   // (memchr: the scan is megabytes, 0xFF bytes are rare)
-        q = static_cast<const uint8_t*>(memchr(q, 0xFF, (size_t)(f + h->scan_end - 1 - q)));
+    if (h->scan_end - h->scan_off >= ((size_t)1 << 29)) return -2;   // bit positions on the device are 32-bit
+    // inside the scan 0xFF starts a stuffed zero or an RSTn marker; fill bytes (FF FF) or a last byte 0xFF are corrupt, any other
+    // marker (DNL, a second SOS ...) is outside the subset
+    for (const uint8_t* q = f + h->scan_off; q < f + h->scan_end;) {   // (memchr: the scan is megabytes, 0xFF bytes are rare)
+        q = static_cast<const uint8_t*>(memchr(q, 0xFF, (size_t)(f + h->scan_end - q)));
         if (q == nullptr) break;
-        if (q[1] != 0x00 && (q[1] & 0xF8) != 0xD0 && q[1] != 0xFF) return -2;
-        ++q;
+        if (q + 1 >= f + h->scan_end || q[1] == 0xFF) return -1;
+        if (q[1] != 0x00 && (q[1] & 0xF8) != 0xD0) return -2;
+        q += 2;
     }
     return 0;
 }
@@ -566,6 +609,7 @@ int parse_header(const uint8_t* f, size_t n, HostHeader* h) {
 bool build_huff(const unsigned char bits[17], const unsigned char* vals, JdHuff* t) {
     int code = 0, k = 0;
     memset(t, 0, sizeof(*t));
+    if (!huff_counts_ok(bits, vals, false)) return false;   // (checked before fast[] is filled: an oversubscribed table would write past it)
     memcpy(t->vals, vals, 256);
     for (int l = 1; l <= 16; ++l) {
         t->valptr[l] = k - code;
@@ -576,7 +620,6 @@ bool build_huff(const unsigned char bits[17], const unsigned char* vals, JdHuff*
                     for (int f = 0; f < (1 << (8 - l)); ++f) t->fast[(c << (8 - l)) | f] = (unsigned short)((l << 8) | vals[k + i]);
                 }
             k += bits[l]; code += bits[l];
-            if (code > (1 << l) || k > 256) return false;
             t->maxcode[l] = code - 1;
         } else t->maxcode[l] = -1;
         code <<= 1;

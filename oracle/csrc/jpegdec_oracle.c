@@ -29,15 +29,30 @@ typedef struct {
     uint16_t q[4][64];                       /* natural order */
     uint8_t bits[2][4][17], vals[2][4][256]; /* [dc/ac][table] */
     int have_q[4], have_h[2][4];
-    size_t scan_off;                         /* first byte of the entropy-coded segment */
+    size_t scan_off, scan_end;               /* the entropy-coded segment: [scan_off, scan_end), scan_end = the last EOI */
 } JpegHeader;
+
+/* libjpeg's table check (jdhuff.c jpeg_make_d_derived_tbl): at every length the codes must fit WITHOUT the all-ones code, i.e. the
+ * code space is never full, let alone oversubscribed; a DC table holds categories 0 .. 15 only.  0 = usable. */
+static int huff_counts_ok(const uint8_t bits[17], const uint8_t* vals, int dc) {
+    int code = 0, cnt = 0;
+    for (int l = 1; l <= 16; ++l) {
+        code += bits[l]; cnt += bits[l];
+        if (code >= (1 << l)) return -1;
+        code <<= 1;
+    }
+    if (dc)
+        for (int i = 0; i < cnt; ++i)
+            if (vals[i] > 15) return -1;
+    return 0;
+}
 
 /* Parses the markers up to SOS.  0 = a file this decoder handles, -1 = not a JPEG / truncated, -2 = valid but unsupported. */
 static int parse_header(const uint8_t* f, size_t n, JpegHeader* h) {
     memset(h, 0, sizeof(*h));
     if (n < 4 || f[0] != 0xFF || f[1] != 0xD8) return -1;
     size_t p = 2;
-    int seen_sof = 0;
+    int seen_sof = 0, adobe = -1;                      /* adobe: the APP14 transform flag, -1 = no Adobe marker */
     for (;;) {
         if (p + 4 > n) return -1;
         if (f[p] != 0xFF) return -1;
@@ -74,7 +89,9 @@ static int parse_header(const uint8_t* f, size_t n, JpegHeader* h) {
                 for (int k = 1; k <= 16; ++k) { h->bits[tc][t][k] = s[i + k - 1]; cnt += s[i + k - 1]; }
                 i += 16;
                 if (cnt > 256 || i + cnt > sl) return -1;
+                memset(h->vals[tc][t], 0, 256);
                 memcpy(h->vals[tc][t], s + i, (size_t)cnt);
+                if (huff_counts_ok(h->bits[tc][t], h->vals[tc][t], tc == 0)) return -1;
                 i += cnt;
                 h->have_h[tc][t] = 1;
             }
@@ -84,7 +101,7 @@ static int parse_header(const uint8_t* f, size_t n, JpegHeader* h) {
             h->height = (s[1] << 8) | s[2]; h->width = (s[3] << 8) | s[4]; h->ncomp = s[5];
             if (h->height == 0 || h->width == 0) return -2;
             if (h->ncomp != 1 && h->ncomp != 3) return -2;
-            if (sl < (size_t)(6 + 3 * h->ncomp)) return -1;
+            if (sl != (size_t)(6 + 3 * h->ncomp)) return -1;   /* libjpeg: JERR_BAD_LENGTH */
             for (int c = 0; c < h->ncomp; ++c) {
                 if (s[6 + 3 * c] != c + 1) return -2;  /* JFIF component ids 1, 2, 3 = Y, Cb, Cr (anything else: let Pillow decide) */
                 h->hs[c] = s[7 + 3 * c] >> 4; h->vs[c] = s[7 + 3 * c] & 15; h->tq[c] = s[8 + 3 * c];
@@ -94,10 +111,10 @@ static int parse_header(const uint8_t* f, size_t n, JpegHeader* h) {
         } else if ((m >= 0xC2 && m <= 0xCF) && m != 0xC4 && m != 0xC8 && m != 0xCC) {
             return -2;                                 /* progressive, lossless, arithmetic ... */
         } else if (m == 0xDD) {                        /* DRI */
-            if (sl < 2) return -1;
+            if (sl != 2) return -1;
             h->restart = (s[0] << 8) | s[1];
-        } else if (m == 0xEE) {                        /* Adobe: a transform flag other than YCbCr changes the colour model */
-            if (sl >= 12 && memcmp(s, "Adobe", 5) == 0 && s[11] != 1 && h->ncomp != 1) return -2;
+        } else if (m == 0xEE) {                        /* Adobe: the transform flag is judged after SOF (APP14 usually precedes it) */
+            if (sl >= 12 && memcmp(s, "Adobe", 5) == 0) adobe = s[11];
         } else if (m == 0xDA) {                        /* SOS */
             if (!seen_sof || sl < 1 || s[0] != h->ncomp || sl < (size_t)(1 + 2 * h->ncomp + 3)) return seen_sof ? -2 : -1;
             for (int c = 0; c < h->ncomp; ++c) {
@@ -114,6 +131,21 @@ static int parse_header(const uint8_t* f, size_t n, JpegHeader* h) {
     else {
         if (h->hs[1] != 1 || h->vs[1] != 1 || h->hs[2] != 1 || h->vs[2] != 1) return -2;
         if (!((h->hs[0] == 1 && h->vs[0] == 1) || (h->hs[0] == 2 && h->vs[0] == 1) || (h->hs[0] == 2 && h->vs[0] == 2))) return -2;
+    }
+    if (h->ncomp == 3 && adobe >= 0 && adobe != 1) return -2;   /* a colour transform other than YCbCr changes the colour model */
+    /* the entropy-coded segment ends at the last EOI (trailing bytes after it are ignored, as libjpeg does) */
+    size_t e = n;
+    while (e >= h->scan_off + 2 && !(f[e - 2] == 0xFF && f[e - 1] == 0xD9)) --e;
+    if (e < h->scan_off + 2) return -1;
+    h->scan_end = e - 2;
+    if (h->scan_end - h->scan_off >= ((size_t)1 << 29)) return -2;   /* the device's bit positions are 32-bit */
+    /* inside the scan 0xFF starts a stuffed zero or an RSTn marker; fill bytes (FF FF) or a last byte 0xFF are corrupt, any other
+     * marker (DNL, a second SOS ...) is outside the subset */
+    for (size_t i = h->scan_off; i < h->scan_end; ++i) {
+        if (f[i] != 0xFF) continue;
+        if (i + 1 >= h->scan_end || f[i + 1] == 0xFF) return -1;
+        if (f[i + 1] != 0x00 && (f[i + 1] & 0xF8) != 0xD0) return -2;
+        ++i;
     }
     h->hmax = h->hs[0]; h->vmax = h->vs[0];
     h->mcux = (h->width + 8 * h->hmax - 1) / (8 * h->hmax);
@@ -139,36 +171,25 @@ static int build_huff(const uint8_t bits[17], const uint8_t* vals, Huff* t) {
     return 0;
 }
 
-typedef struct { const uint8_t* p; const uint8_t* end; uint32_t acc; int cnt; int marker; } Bits;
-static void fill(Bits* b) {
-    while (b->cnt <= 24) {
-        int v = 0;
-        if (!b->marker && b->p < b->end) {
-            v = *b->p;
-            if (v == 0xFF) {
-                if (b->p + 1 < b->end && b->p[1] == 0) b->p += 2;      /* stuffed zero */
-                else { b->marker = 1; v = 0; }                          /* a marker: feed zeros until the caller deals with it */
-            } else b->p += 1;
-        }
-        b->acc |= (uint32_t)v << (24 - b->cnt);
-        b->cnt += 8;
-    }
+/* Bit reader over ONE restart segment of the un-stuffed scan.  Past its end it reads zeros, as libjpeg does after it hits a marker;
+ * a decode that needed those bits ran out of data (libjpeg's "insufficient data": it leaves the rest of the segment's blocks at
+ * zero, and that recovery is left to Pillow). */
+typedef struct { const uint8_t* d; size_t pos, end; } Bits;   /* bit positions inside the segment */
+static int getbit(Bits* b) {
+    const int v = b->pos < b->end ? (b->d[b->pos >> 3] >> (7 - (b->pos & 7))) & 1 : 0;
+    ++b->pos;
+    return v;
 }
 static int getbits(Bits* b, int n) {
-    if (n == 0) return 0;
-    fill(b);
-    const int v = (int)(b->acc >> (32 - n));
-    b->acc <<= n; b->cnt -= n;
+    int v = 0;
+    for (int i = 0; i < n; ++i) v = (v << 1) | getbit(b);
     return v;
 }
 static int decode_sym(Bits* b, const Huff* t) {
-    fill(b);
     int code = 0;
     for (int l = 1; l <= 16; ++l) {
-        code = (code << 1) | (int)(b->acc >> 31);
-        b->acc <<= 1; b->cnt -= 1;
+        code = (code << 1) | getbit(b);
         if (code <= t->maxcode[l] && t->maxcode[l] >= 0) return t->vals[(t->valptr[l] + code) & 255];
-        if (b->cnt == 0) fill(b);
     }
     return -1;
 }
@@ -182,8 +203,16 @@ static uint8_t idct_limit(int32_t x) {   /* range_limit[(x) & RANGE_MASK] of the
     const int i = (int)(x & 1023);
     return (uint8_t)(i < 128 ? i + 128 : (i < 512 ? 255 : (i < 896 ? 0 : i - 896)));
 }
-static void idct_islow(const int16_t* c, const uint16_t* q, uint8_t* out, int stride) {
+/* The range where libjpeg-turbo's C islow IDCT and its SIMD versions (16-bit lanes, saturating packs) give the same samples:
+ * every de-quantised input and every pass-1 output in [-16384, 16383] (sums of two still fit 16 bits, nothing overflows 32 bits),
+ * every output sample before the +128 in [-512, 511] (range_limit[x & 1023] saturates there, beyond it wraps: 0 <-> 255).
+ * Outside it Pillow's answer depends on the host CPU: the block is reported (returns 1) and the file refused. */
+#define IN16K(v) ((uint32_t)((v) + 16384) < 32768u)
+#define OUT512(v) ((uint32_t)((v) + 512) < 1024u)
+static int idct_islow(const int16_t* c, const uint16_t* q, uint8_t* out, int stride) {
     int32_t ws[64];
+    int ok = 1;
+    for (int i = 0; i < 64; ++i) ok &= IN16K((int32_t)c[i] * (int32_t)q[i]);
     for (int col = 0; col < 8; ++col) {
 #define D(r) ((int32_t)c[8 * (r) + col] * (int32_t)q[8 * (r) + col])
         int32_t z2 = D(2), z3 = D(6);
@@ -206,6 +235,7 @@ static void idct_islow(const int16_t* c, const uint16_t* q, uint8_t* out, int st
         ws[24 + col] = DESCALE(tmp13 + tmp0, CB - P1); ws[32 + col] = DESCALE(tmp13 - tmp0, CB - P1);
 #undef D
     }
+    for (int i = 0; i < 64; ++i) ok &= IN16K(ws[i]);
     for (int row = 0; row < 8; ++row) {
         const int32_t* w = ws + 8 * row;
         int32_t z2 = w[2], z3 = w[6];
@@ -221,12 +251,13 @@ static void idct_islow(const int16_t* c, const uint16_t* q, uint8_t* out, int st
         z1 *= -7373; z2 *= -20995; z3 *= -16069; z4 *= -3196;
         z3 += z5; z4 += z5;
         tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
+        const int32_t x[8] = {DESCALE(tmp10 + tmp3, CB + P1 + 3), DESCALE(tmp11 + tmp2, CB + P1 + 3), DESCALE(tmp12 + tmp1, CB + P1 + 3),
+                              DESCALE(tmp13 + tmp0, CB + P1 + 3), DESCALE(tmp13 - tmp0, CB + P1 + 3), DESCALE(tmp12 - tmp1, CB + P1 + 3),
+                              DESCALE(tmp11 - tmp2, CB + P1 + 3), DESCALE(tmp10 - tmp3, CB + P1 + 3)};
         uint8_t* o = out + row * stride;
-        o[0] = idct_limit(DESCALE(tmp10 + tmp3, CB + P1 + 3)); o[7] = idct_limit(DESCALE(tmp10 - tmp3, CB + P1 + 3));
-        o[1] = idct_limit(DESCALE(tmp11 + tmp2, CB + P1 + 3)); o[6] = idct_limit(DESCALE(tmp11 - tmp2, CB + P1 + 3));
-        o[2] = idct_limit(DESCALE(tmp12 + tmp1, CB + P1 + 3)); o[5] = idct_limit(DESCALE(tmp12 - tmp1, CB + P1 + 3));
-        o[3] = idct_limit(DESCALE(tmp13 + tmp0, CB + P1 + 3)); o[4] = idct_limit(DESCALE(tmp13 - tmp0, CB + P1 + 3));
+        for (int i = 0; i < 8; ++i) { ok &= OUT512(x[i]); o[i] = idct_limit(x[i]); }
     }
+    return !ok;
 }
 
 static uint8_t clamp8(int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
@@ -282,51 +313,62 @@ static long decode_coefficients(const uint8_t* file, size_t n, const JpegHeader*
         if (h->have_h[0][t] && build_huff(h->bits[0][t], h->vals[0][t], &dc[t])) return -1;
         if (h->have_h[1][t] && build_huff(h->bits[1][t], h->vals[1][t], &ac[t])) return -1;
     }
-    Bits b = {file + h->scan_off, file + n, 0, 0, 0};
-    int pred[3] = {0, 0, 0};
-    const long mcus = (long)h->mcux * h->mcuy;
-    int bpm = 0;
-    for (int c = 0; c < h->ncomp; ++c) bpm += h->hs[c] * h->vs[c];
-    long blk = 0;
-    int rst_left = h->restart, next_rst = 0;
-    for (long m = 0; m < mcus; ++m) {
-        if (h->restart && rst_left == 0) {                 /* byte-align, expect RSTn, reset the predictions */
-            b.acc = 0; b.cnt = 0;
-            if (!b.marker) {                                /* the bit reader has not run into the marker yet: it must be next */
-                while (b.p < b.end && !(b.p[0] == 0xFF && b.p + 1 < b.end && b.p[1] != 0 && b.p[1] != 0xFF)) ++b.p;
-            }
-            if (b.p + 1 >= b.end || b.p[0] != 0xFF || b.p[1] != 0xD0 + next_rst) return -1;
-            b.p += 2; b.marker = 0;
-            next_rst = (next_rst + 1) & 7;
-            pred[0] = pred[1] = pred[2] = 0;
-            rst_left = h->restart;
-        }
-        for (int c = 0; c < h->ncomp; ++c)
-            for (int i = 0; i < h->hs[c] * h->vs[c]; ++i) {
-                int16_t* blkp = coef + 64 * blk++;
-                memset(blkp, 0, 64 * sizeof(int16_t));
-                int s = decode_sym(&b, &dc[h->td[c]]);
-                if (s < 0 || s > 11) return -1;
-                pred[c] += extend(getbits(&b, s), s);
-                blkp[0] = (int16_t)pred[c];
-                for (int k = 1; k < 64;) {
-                    const int rs = decode_sym(&b, &ac[h->ta[c]]);
-                    if (rs < 0) return -1;
-                    const int r = rs >> 4;
-                    s = rs & 15;
-                    if (s == 0) {
-                        if (r == 15) { k += 16; continue; }
-                        break;                               /* EOB */
-                    }
-                    k += r;
-                    if (k > 63) return -1;
-                    blkp[DZZ[k]] = (int16_t)extend(getbits(&b, s), s);
-                    ++k;
-                }
-            }
-        if (h->restart) --rst_left;
+    /* un-stuff the scan and cut it at the RSTn markers (parse_header let only FF 00 and FF D0..D7 through) */
+    const size_t sn = h->scan_end - h->scan_off;
+    uint8_t* d = (uint8_t*)malloc(sn + 1);
+    size_t* seg = (size_t*)malloc((sn / 2 + 2) * sizeof(size_t));   /* seg[s] = first byte of segment s; seg[nseg] = end */
+    if (!d || !seg) { free(d); free(seg); return -1; }
+    size_t dn = 0;
+    int nseg = 1;
+    long rc = 0;
+    seg[0] = 0;
+    for (size_t i = h->scan_off; i < h->scan_end; ++i) {
+        const uint8_t c = file[i];
+        if (c != 0xFF) { d[dn++] = c; continue; }
+        if (file[i + 1] == 0x00) { d[dn++] = 0xFF; ++i; continue; }
+        if (file[i + 1] != 0xD0 + ((nseg - 1) & 7)) rc = -1;          /* RSTn out of sequence */
+        seg[nseg++] = dn; ++i;
     }
-    return blk;
+    seg[nseg] = dn;
+    const long mcus = (long)h->mcux * h->mcuy;
+    if (nseg != (h->restart ? (mcus + h->restart - 1) / h->restart : 1)) rc = -1;   /* one segment per restart interval, no more, no fewer */
+    long blk = 0, m = 0;
+    for (int sg = 0; sg < nseg && rc == 0; ++sg) {
+        Bits b = {d + seg[sg], 0, (seg[sg + 1] - seg[sg]) * 8};
+        int pred[3] = {0, 0, 0};
+        const long m_end = h->restart && m + h->restart < mcus ? m + h->restart : mcus;
+        for (; m < m_end && rc == 0; ++m)
+            for (int c = 0; c < h->ncomp && rc == 0; ++c)
+                for (int i = 0; i < h->hs[c] * h->vs[c] && rc == 0; ++i) {
+                    int16_t* blkp = coef + 64 * blk++;
+                    memset(blkp, 0, 64 * sizeof(int16_t));
+                    int s = decode_sym(&b, &dc[h->td[c]]);
+                    if (s < 0 || s > 11) { rc = -1; break; }
+                    pred[c] += extend(getbits(&b, s), s);
+                    blkp[0] = (int16_t)pred[c];
+                    for (int k = 1; k < 64;) {
+                        const int rs = decode_sym(&b, &ac[h->ta[c]]);
+                        if (rs < 0) { rc = -1; break; }
+                        const int r = rs >> 4;
+                        s = rs & 15;
+                        if (s == 0) {
+                            if (r == 15) { k += 16; if (k > 64) rc = -1; continue; }   /* a zero run past the block's end */
+                            break;                               /* EOB */
+                        }
+                        k += r;
+                        if (k > 63) { rc = -1; break; }
+                        blkp[DZZ[k]] = (int16_t)extend(getbits(&b, s), s);
+                        ++k;
+                    }
+                }
+        /* the segment's data must end exactly: no bit read past it, fewer than 8 bits left and all of them 1 (the padding) */
+        if (rc == 0) {
+            const int rem = b.pos > b.end ? -1 : (int)(b.end - b.pos < 8 ? b.end - b.pos : 8);
+            if (rem < 0 || rem == 8 || getbits(&b, rem) != (1 << rem) - 1) rc = -1;
+        }
+    }
+    free(d); free(seg);
+    return rc ? rc : blk;
 }
 
 long oracle_jpeg_decode_coefficients(const uint8_t* file, size_t n, int16_t* coef, long cap_blocks) {
@@ -358,13 +400,15 @@ int oracle_jpeg_decode_rgb(const uint8_t* file, size_t n, uint8_t* out, int cap_
         plane[c] = (uint8_t*)malloc((size_t)pw[c] * ph[c]);
     }
     long blk = 0;
+    int range_err = 0;
     for (int my = 0; my < h.mcuy; ++my)
         for (int mx = 0; mx < h.mcux; ++mx)
             for (int c = 0; c < h.ncomp; ++c)
                 for (int by = 0; by < h.vs[c]; ++by)
                     for (int bx = 0; bx < h.hs[c]; ++bx)
-                        idct_islow(coef + 64 * blk++, h.q[h.tq[c]], plane[c] + (size_t)((my * h.vs[c] + by) * 8) * pw[c] + (mx * h.hs[c] + bx) * 8, pw[c]);
+                        range_err |= idct_islow(coef + 64 * blk++, h.q[h.tq[c]], plane[c] + (size_t)((my * h.vs[c] + by) * 8) * pw[c] + (mx * h.hs[c] + bx) * 8, pw[c]);
     free(coef);
+    if (range_err) { for (int c = 0; c < h.ncomp; ++c) free(plane[c]); return -1; }
     if (ncomp_out) *ncomp_out = h.ncomp;
     if (h.ncomp == 1) {
         for (int y = 0; y < h.height; ++y)
