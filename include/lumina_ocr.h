@@ -44,7 +44,8 @@ const char* lumina_ocr_version(void);
 /* options: "det_sub_batch", "rec_sub_batch", "post_group", "tail_group", "keep_taps", "time_convs"; developer A/B switches (results are
  * bit-identical either way): "fuse_head", "fuse_pool", "fuse_stem", "fuse_mb", "fpn_multi", "conv_ring", "ring_orient", "conv_big_min",
  * "blocked_layout" (experiment: fails loudly when a blocked tensor would reach a kernel other than the ring kernel);
- * "svtr_f16" (storage type of the next SVTR load), "conv2d_variant" (kernel choice of lumina_ocr_conv2d, parity tests) */
+ * "svtr_f16" (storage type of the next SVTR load), "conv2d_variant" (kernel choice of lumina_ocr_conv2d, parity tests);
+ * "png_sub_batch_mb" (lumina_ocr_png_decode: MB of inflated scanlines per sub-batch, default 768 — bounds the workspace a PNG batch reserves) */
 int lumina_ocr_set_option(lumina_ocr_t* h, const char* key, int value);
 
 /* weights: "LOCW" container (ocr-system_amd/lumina_ocr/arch.py write_blob), host memory.
@@ -173,6 +174,23 @@ int lumina_ocr_jpeg_decode_async(lumina_ocr_t* h, const uint8_t* const* files, c
                                  int* status_pinned, int passes, void* stream);
 /* synchronisation passes over the chunk decoders the last lumina_ocr_jpeg_decode call needed (diagnostic) */
 int lumina_ocr_jpeg_last_passes(const lumina_ocr_t* h);
+
+/* PNG decode on the device — the pixel work of the reference's Image.open(...) + convert('RGB') for .png inputs and for the PNG pages
+ * pdf2image returns (image_preprocessing.py:57-75).  The contract is the JPEG pair's: status 0 => byte-identical to Pillow's
+ * Image.open(f).convert('RGB'); any other status => the file is left to Pillow (the device accepts a file only where every conformant
+ * decoder agrees: see the acceptance rule in DESIGN.md).
+ * lumina_ocr_png_probe (host only, no handle): a walk over the chunks before the first IDAT (no pixel data is read); info = {width,
+ * height, colour type, bit depth, interlace, palette entries, EXIF orientation of an eXIf chunk before IDAT (0: none), 0}; returns 0 for
+ * a file the device decodes (non-interlaced grey 1/2/4/8 bit, RGB 8, palette 1/2/4/8, grey+alpha 8, RGBA 8), -1 corrupt / not a PNG,
+ * -2 valid but outside that subset (Adam7, 16 bit, compressed metadata, animation, chunks after the image data): decode those with
+ * Pillow, as the reference does.
+ * lumina_ocr_png_decode: files / sizes are HOST arrays of n file images, all height x width; out_dev uint8 [n][height][width][3] (a grey
+ * file: its value on all three channels; alpha dropped; palette looked up); status HOST int [n]: 0 ok; -1 corrupt (chunk structure, zlib
+ * header, DEFLATE stream, inflated size, Adler-32, filter byte or palette index); -2 outside the subset; -4 another size.  A page with a
+ * non-zero status is not written.  Synchronises `stream`. */
+int lumina_ocr_png_probe(const uint8_t* file, size_t size, int info[8]);
+int lumina_ocr_png_decode(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev,
+                          int* status, void* stream);
 
 int lumina_ocr_jpeg_coefficients(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int quality, int16_t* coefs_dev,
                                  void* stream);

@@ -11,6 +11,7 @@
 #include "resize.h"
 #include "jpeg.h"
 #include "jpegdec.h"
+#include "pngdec.h"
 #include "stem_conv.h"
 
 #define API_TRY try {
@@ -109,6 +110,7 @@ int lumina_ocr_set_option(lumina_ocr_t* h, const char* key, int value) {
     else if (!strcmp(key, "post_group")) h->post_group = value > 0 ? value : 1;
     else if (!strcmp(key, "tail_group")) h->tail_group = value > 0 ? value : 0;
     else if (!strcmp(key, "svtr_f16")) h->svtr_f16 = value < 0 ? -1 : (value != 0);
+    else if (!strcmp(key, "png_sub_batch_mb")) h->pd_sub_batch_mb = value > 0 ? value : 1;
     else if (!strcmp(key, "conv2d_variant")) h->conv2d_variant = value < 0 || value > 2 ? 0 : value;
     else return locr_fail(h, "set_option: unknown key", key);
     return 0;
@@ -398,6 +400,24 @@ int lumina_ocr_jpeg_decode_async(lumina_ocr_t* h, const uint8_t* const* files, c
 }
 
 int lumina_ocr_jpeg_last_passes(const lumina_ocr_t* h) { return h ? h->jd_last_passes : 0; }
+
+int lumina_ocr_png_probe(const uint8_t* file, size_t size, int info[8]) {
+    if (!file || !info) return -1;
+    PdInfo i{};
+    const int rc = pngdec_probe(file, size, &i);
+    info[0] = i.width; info[1] = i.height; info[2] = i.color_type; info[3] = i.bit_depth; info[4] = i.interlace; info[5] = i.palette_size;
+    info[6] = i.orientation; info[7] = 0;
+    return rc;
+}
+
+int lumina_ocr_png_decode(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev, int* status,
+                          void* stream) {
+    if (!h || !files || !sizes || !out_dev || !status || n <= 0 || height <= 0 || width <= 0) return locr_fail(h, "png_decode", "bad arguments");
+    BIND(h);
+    API_TRY
+    return pngdec_run(h, files, sizes, n, height, width, out_dev, status, (hipStream_t)stream);
+    API_CATCH(h)
+}
 
 int lumina_ocr_jpeg_coefficients(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int quality, int16_t* coefs_dev,
                                  void* stream) {

@@ -158,6 +158,8 @@ struct lumina_ocr {
     struct Staging { Growable<PinnedMem> buf; Event uploaded; };
     Staging jd_stage[2];
     int jd_stage_next = 0;
+    Staging pd_stage;   // pinned staging of the PNG decoder's gathered IDAT payloads (pngdec.hip)
+    int pd_sub_batch_mb = 768;   // PNG decoder: filtered-scanline MB per sub-batch (64 A4 RGB pages at 300 dpi are 1.7 GB); sizes its workspace
     float* dk_trig = nullptr; short* dk_wtab = nullptr;   // de-skew tables (deskew.h), uploaded at first use
 };
 

@@ -1,0 +1,25 @@
+// Baseline PNG decoder on the device: the pixel work behind the reference's
+//   Image.open(path) / Image.open(io.BytesIO(bytes)) + convert('RGB')   (ImagePreprocessor.load_image / load_image_bytes,
+//   image_preprocessing.py:57-75; .png inputs, and the PNG pages pdf2image returns for PDFs)
+// byte-identical to Pillow.  The contract is the JPEG decoder's: status 0 => the same bytes as Pillow's decode, any other status =>
+// the file is left to Pillow.  The device accepts a file only where every conformant decoder agrees.
+#pragma once
+#include <cstddef>
+
+#include "common.h"
+
+struct PdInfo { int width, height, color_type, bit_depth, interlace, palette_size, orientation; };
+// Host only, a walk over the chunks before the first IDAT (no pixel data is read): 0 = a file the device decodes (non-interlaced;
+// grey 1/2/4/8 bit, RGB 8, palette 1/2/4/8, grey+alpha 8, RGBA 8), -1 = not a PNG / corrupt header chunks, -2 = valid but outside that
+// subset.  orientation: the EXIF Orientation of an eXIf chunk before IDAT (0 without one).
+int pngdec_probe(const uint8_t* file, size_t n, PdInfo* info);
+
+// bytes of workspace a batch of n files with these totals needs (the layout pngdec_run carves)
+size_t pngdec_workspace_bytes(int n, size_t z_total, size_t filt_total, size_t adler_blocks);
+
+struct lumina_ocr;
+// files: HOST pointers; all n files must be height x width.  out: device RGB u8 [n][height][width][3] (grey files: the grey value on
+// all three channels).  status: HOST int [n], 0 ok / -1 corrupt / -2 unsupported / -4 size mismatch (such a page's pixels are not
+// written).  Synchronous: synchronises the stream once per sub-batch.
+int pngdec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev, int* status,
+               hipStream_t st);

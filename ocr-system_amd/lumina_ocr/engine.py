@@ -71,6 +71,8 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_jpeg_decode_async": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp]),
         "lumina_ocr_jpeg_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_jpeg_coefficients": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
+        "lumina_ocr_png_probe": (i32, [vp, sz, vp]),
+        "lumina_ocr_png_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_load_svtr_weights": (i32, [vp, vp, sz]),
         "lumina_ocr_svtr_forward": (i32, [vp, vp, vp, i32, vp, vp, vp]),
         "lumina_ocr_svtr_num_classes": (i32, [vp]),
@@ -102,6 +104,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_det_forward", "lumina_ocr_det_postprocess", "lumina_ocr_rec_crop", "lumina_ocr_rec_forward",
     "lumina_ocr_ctc_decode", "lumina_ocr_conv2d", "lumina_ocr_read_tap", "lumina_ocr_conv_timing", "lumina_ocr_conv_timing_detail",
     "lumina_ocr_resize_lanczos", "lumina_ocr_enhance", "lumina_ocr_jpeg_encode", "lumina_ocr_jpeg_coefficients", "lumina_ocr_jpeg_probe", "lumina_ocr_jpeg_decode", "lumina_ocr_jpeg_decode_async", "lumina_ocr_jpeg_last_passes",
+    "lumina_ocr_png_probe", "lumina_ocr_png_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
 ]
 
@@ -203,6 +206,31 @@ class Engine:
         sizes = (ctypes.c_size_t * n)(*[len(f) for f in files])
         self._chk(self.lib.lumina_ocr_jpeg_decode_async(self._h, ptrs, sizes, n, int(height), int(width), _ptr(out), status.data_ptr(), int(passes), self._stream()))
         return out, status
+
+    @staticmethod
+    def png_probe(data: bytes):
+        """Host only, the chunks before the first IDAT. -> (rc, dict(width, height, color_type, bit_depth, interlace, palette_size,
+        orientation)); rc 0: the device decodes this file, -2: valid PNG outside the subset (Adam7, 16 bit ...: decode with Pillow as the
+        reference does), -1: corrupt / not a PNG.  orientation: EXIF Orientation of an eXIf chunk before IDAT, 0 without one."""
+        lib = load_library()
+        info = (ctypes.c_int * 8)()
+        rc = lib.lumina_ocr_png_probe(ctypes.c_char_p(data), len(data), info)
+        return rc, dict(width=info[0], height=info[1], color_type=info[2], bit_depth=info[3], interlace=info[4], palette_size=info[5],
+                        orientation=info[6])
+
+    def png_decode(self, files, height: int, width: int, out=None):
+        """PNG file images (a sequence of bytes objects, all height x width) -> (uint8 [n,H,W,3] device, status list): the pixels of the
+        reference's Image.open(...).convert('RGB') for .png inputs (image_preprocessing.py:57-75), byte-identical to Pillow.  status[i] != 0:
+        page i was not decoded (-1 corrupt, -2 outside the device subset, -4 another size) and is left to Pillow."""
+        torch = _torch()
+        n = len(files)
+        if out is None:
+            out = torch.empty((n, height, width, 3), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        ptrs = (ctypes.c_char_p * n)(*files)
+        sizes = (ctypes.c_size_t * n)(*[len(f) for f in files])
+        status = (ctypes.c_int * n)()
+        self._chk(self.lib.lumina_ocr_png_decode(self._h, ptrs, sizes, n, int(height), int(width), _ptr(out), status, self._stream()))
+        return out, list(status)
 
     @property
     def jpeg_last_passes(self) -> int:

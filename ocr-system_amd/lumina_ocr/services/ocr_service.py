@@ -34,6 +34,7 @@ from ..utils.image_preprocessing import ImagePreprocessor, get_optimal_size
 logger = logging.getLogger(__name__)
 
 SUPPORTED_IMAGE_TYPES = ("png", "jpg", "jpeg", "webp", "bmp", "tiff")
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 
 
 @dataclass
@@ -107,6 +108,9 @@ class OCRService:
         # "simple" = the L > 128 threshold the reference falls back to without OpenCV (image_preprocessing.py:473-475)
         b = os.environ.get("PREPROCESSING_APPLY_BINARIZE", "false").lower()
         self.device_jpeg = os.environ.get("LUMINA_OCR_DEVICE_JPEG", "1").lower() not in ("0", "false", "no")   # baseline JPEG inputs are decoded on the device
+        # LUMINA_OCR_DEVICE_PNG=1: non-interlaced PNG inputs of 8 bits or less and lazily opened PNG pages (pdf2image) are decoded on the
+        # device.  Off by default: measured slower than Pillow for single pages and for 300 dpi batches
+        self.device_png = os.environ.get("LUMINA_OCR_DEVICE_PNG", "0").lower() not in ("0", "false", "no")
         self.apply_binarize = "adaptive" if b in ("1", "true", "yes", "adaptive") else ("simple" if b == "simple" else None)
         self._device = int(os.environ.get("LUMINA_OCR_DEVICE", os.environ.get("LOCAL_RANK", 0)))
         self._det_weights = os.environ.get("LUMINA_OCR_DET_WEIGHTS", "")
@@ -305,8 +309,66 @@ class OCRService:
             logger.warning("device JPEG decode not used: %s", e)
             return None
 
+    @staticmethod
+    def _png_orientation(image: Image.Image) -> Optional[int]:
+        """The EXIF orientation auto_orient would apply, read without decoding, or None: leave the file to the host path.  Pillow's PNG
+        getexif() loads the pixels when the eXIf chunk was not among the chunks read at open (a file with chunks after IDAT is refused by
+        the device decoder anyway), and Pillow also takes the orientation from a "Raw profile type exif" text chunk or an XMP
+        tiff:Orientation ("XML:com.adobe.xmp"): files carrying either are left to the host path, so that no orientation source is missed."""
+        if "Raw profile type exif" in image.info or "XML:com.adobe.xmp" in image.info:
+            return None
+        return image.getexif().get(0x0112, 1) if "exif" in image.info else 1
+
+    def _decode_png_on_device(self, data: bytes, image: Image.Image):
+        """The reference decodes every input with Image.open + convert('RGB') (image_preprocessing.py:57-75).  For a PNG in the device
+        subset the pixels are produced on the device instead (lumina_ocr_png_decode: byte-identical to Pillow); `image` must be the
+        lazily opened file (nothing decoded yet).  -> device tensor [1,H,W,3] with the EXIF orientation applied, or None: Pillow decodes."""
+        if not self.device_png or image.format != "PNG" or data[:8] != PNG_SIGNATURE:
+            return None
+        try:
+            orientation = self._png_orientation(image)
+            if orientation is None or orientation not in range(0, 9):
+                return None
+            # the engine first: it brings up torch's HIP runtime before the probe loads the engine library (loaded the other way round,
+            # the library's own runtime was the first in the process and torch's saw no device)
+            self._ensure_engine()
+            from ..engine import Engine
+            rc, info = Engine.png_probe(data)
+            if rc != 0 or (info["width"], info["height"]) != image.size:
+                return None
+            with self._device_ctx():
+                out, status = self._engine.png_decode([data], info["height"], info["width"])
+                if status != [0]:
+                    return None
+                return self._engine.exif_transpose(out, orientation)
+        except Exception as e:       # any doubt: the reference's own path
+            logger.warning("device PNG decode not used: %s", e)
+            return None
+
+    def _process_png_on_device(self, image_source: Union[str, Path, bytes], page_number: int) -> Optional[OCROutput]:
+        """A PNG path / bytes whose pixels the device decodes -> its result; None: today's path (load_image converts P / RGBA / LA / 1
+        files at once, so the lazily opened file is looked at before that)."""
+        try:
+            data = image_source if isinstance(image_source, bytes) else Path(image_source).read_bytes()
+        except OSError:
+            return None
+        if data[:8] != PNG_SIGNATURE:
+            return None
+        try:
+            image = Image.open(io.BytesIO(data))
+        except Exception:
+            return None
+        decoded = self._decode_png_on_device(data, image)
+        if decoded is None:
+            return None
+        return self._process_single_image_sync(image, page_number, decoded=decoded)
+
     def process_image_sync(self, image_source: Union[str, Path, Image.Image, bytes], page_number: int = 1) -> OCROutput:
         data = None
+        if self.device_png and isinstance(image_source, (bytes, str, Path)):
+            r = self._process_png_on_device(image_source, page_number)
+            if r is not None:
+                return r
         if isinstance(image_source, bytes):
             data = image_source
             image = self._pre.load_image_bytes(image_source)
@@ -325,13 +387,69 @@ class OCRService:
         return self._process_single_image_sync(image, page_number, decoded=decoded)
 
     # ---- page batches: the data-parallel unit (reference loops pages serially, :620-627) ----
+    @staticmethod
+    def _lazy_png_bytes(im: Image.Image) -> Optional[bytes]:
+        """The file bytes of a PNG page Pillow has not decoded yet (pdf2image's pages: Image.open over a BytesIO, or a file), else None."""
+        if getattr(im, "format", None) != "PNG" or getattr(im, "_im", 0) is not None:   # (Pillow 12: _im is None until load())
+            return None
+        try:
+            fp = getattr(im, "fp", None)
+            if isinstance(fp, io.BytesIO):
+                data = fp.getvalue()
+            elif getattr(im, "filename", None):
+                data = Path(im.filename).read_bytes()
+            else:
+                return None
+        except (OSError, ValueError):
+            return None
+        return data if data[:8] == PNG_SIGNATURE else None
+
+    def _decode_png_pages(self, images: List[Image.Image]) -> Dict[int, Any]:
+        """Lazily opened PNG pages -> {page index: device tensor [1,H,W,3], EXIF orientation applied}, one png_decode per size group.
+        Pages the decoder refuses, and everything else, are absent: they take the host path."""
+        try:
+            if not any(self._lazy_png_bytes(im) is not None for im in images):
+                return {}
+            self._ensure_engine()   # (before the probe loads the engine library: see _decode_png_on_device)
+            from ..engine import Engine
+            cand: Dict[Any, list] = {}
+            for i, im in enumerate(images):
+                data = self._lazy_png_bytes(im)
+                if data is None:
+                    continue
+                rc, info = Engine.png_probe(data)
+                if rc != 0 or (info["width"], info["height"]) != im.size:
+                    continue
+                # (only now: getexif() caches on the image, and a refused page keeps its host path exactly as it was)
+                orientation = self._png_orientation(im)
+                if orientation is None or orientation not in range(0, 9):
+                    continue
+                cand.setdefault(im.size, []).append((i, data, orientation))
+            if not cand:
+                return {}
+            res: Dict[int, Any] = {}
+            with self._device_ctx():
+                for (w, h), items in cand.items():
+                    out, status = self._engine.png_decode([d for _, d, _ in items], h, w)
+                    for k, (i, _, orientation) in enumerate(items):
+                        if status[k] == 0:
+                            res[i] = self._engine.exif_transpose(out[k:k + 1], orientation)
+            return res
+        except Exception as e:       # any doubt: the reference's own path for every page
+            logger.warning("device PNG decode not used: %s", e)
+            return {}
+
     def process_pages_sync(self, images: List[Image.Image], first_page_number: int = 1) -> List[OCROutput]:
         """Same-size pages go through the engine as one batch; results are identical to the per-page path."""
         out: List[Optional[OCROutput]] = [None] * len(images)
         with self._semaphore:
             groups: Dict[Any, List[int]] = {}
             prepared: List[Optional[Image.Image]] = [None] * len(images)
+            on_device = self._decode_png_pages(images) if self.device_png else {}
             for i, im in enumerate(images):
+                if i in on_device:   # decoded (and oriented) on the device: grouped by its oriented size, apart from host pages
+                    groups.setdefault(("device", on_device[i].shape[2], on_device[i].shape[1]), []).append(i)
+                    continue
                 try:
                     prepared[i] = self._prepare(im)   # (EXIF orientation may swap width and height: group by the prepared size)
                     groups.setdefault(prepared[i].size, []).append(i)
@@ -342,9 +460,12 @@ class OCRService:
                 try:
                     import torch
                     self._ensure_engine()
-                    batch = [prepared[i] for i in idxs]
                     with self._device_ctx():
-                        dets, processed = self._pipeline.run(self._upload(self._stage_pages(batch)), deskew=self.apply_deskew)
+                        if size[0] == "device":
+                            pages = torch.cat([on_device[i] for i in idxs]) if len(idxs) > 1 else on_device[idxs[0]]
+                        else:
+                            pages = self._upload(self._stage_pages([prepared[i] for i in idxs]))
+                        dets, processed = self._pipeline.run(pages, deskew=self.apply_deskew)
                         jpegs = self._pre.compress_for_azure_device(processed)
                     for j, i in enumerate(idxs):
                         out[i] = self._finish_page(dets[j], jpegs[j], tuple(processed.shape[1:3]), first_page_number + i, images[i].size, t0)
