@@ -41,7 +41,7 @@ int lumina_ocr_create(int device, lumina_ocr_t** out);
 void lumina_ocr_destroy(lumina_ocr_t* h);
 const char* lumina_ocr_last_error(const lumina_ocr_t* h);
 const char* lumina_ocr_version(void);
-/* options: "det_sub_batch", "rec_sub_batch", "post_group", "tail_group", "keep_taps", "time_convs"; developer A/B switches (results are
+/* options: "det_sub_batch", "rec_sub_batch", "cls_sub_batch", "post_group", "tail_group", "keep_taps", "time_convs"; developer A/B switches (results are
  * bit-identical either way): "fuse_head", "fuse_pool", "fuse_stem", "fuse_mb", "fpn_multi", "conv_ring", "ring_orient", "conv_big_min",
  * "blocked_layout" (experiment: fails loudly when a blocked tensor would reach a kernel other than the ring kernel);
  * "svtr_f16" (storage type of the next SVTR load), "conv2d_variant" (kernel choice of lumina_ocr_conv2d, parity tests);
@@ -76,6 +76,32 @@ int lumina_ocr_det_postprocess(lumina_ocr_t* h, const uint16_t* prob_dev, int ba
  * crops_dev uint8 [n][32][320][3]; widths_dev int32 [n] receives the valid width. */
 int lumina_ocr_rec_crop(lumina_ocr_t* h, const uint8_t* pages_dev, int batch, int height, int width, const int32_t* quads_dev,
                         const int32_t* page_idx_dev, int n_crops, uint8_t* crops_dev, int32_t* widths_dev, void* stream);
+
+/* lumina_ocr_rec_crop with a per-crop flag flip_dev int32 [n] (lumina_ocr_cls_forward's: the lines PaddleOCR's use_angle_cls reads as
+ * upside down): a flagged crop is the 180-degree turn of the crop lumina_ocr_rec_crop makes, within its valid width —
+ * out[i][j] = crop[31-i][wc-1-j] for j < wc; padding and widths are unchanged, an unflagged crop is byte-identical.
+ * n_crops == 0 is a no-op (no pointer is read). */
+int lumina_ocr_rec_crop_oriented(lumina_ocr_t* h, const uint8_t* pages_dev, int batch, int height, int width, const int32_t* quads_dev,
+                                 const int32_t* page_idx_dev, int n_crops, const int32_t* flip_dev, uint8_t* crops_dev, int32_t* widths_dev,
+                                 void* stream);
+
+/* Text-line orientation classifier (PP-OCR `cls`, ch_ppocr_mobile_v2.0_cls; PaddleOCR's use_angle_cls): MobileNetV3-small x0.35 on
+ * 48 x 192 crops -> conv 1x1 (200) -> 2x2 max pool -> mean -> FC(2) -> soft-max.  Blob: LOCW with the cls.* tensors of
+ * lumina_ocr/arch.py make_cls_weights; every shape is checked as lumina_ocr_load_rec_weights checks its own. */
+int lumina_ocr_load_cls_weights(lumina_ocr_t* h, const void* blob, size_t nbytes);
+
+/* Orientation-classifier crops (PP-OCR `cls` input): the sampling of lumina_ocr_rec_crop, 48 rows, into crops_dev
+ * uint8 [n][48][192][3]; widths_dev int32 [n] receives the valid width min(192, ceil(48 * ratio)), columns past it are 0.
+ * n_crops == 0 is a no-op. */
+int lumina_ocr_cls_crop(lumina_ocr_t* h, const uint8_t* pages_dev, int batch, int height, int width, const int32_t* quads_dev,
+                        const int32_t* page_idx_dev, int n_crops, uint8_t* crops_dev, int32_t* widths_dev, void* stream);
+
+/* Orientation classifier: crops uint8 [n][48][192][3] (+ optional valid widths, as lumina_ocr_cls_crop writes them) ->
+ * label_dev int32 [n] (0 = "0", 1 = "180"), score_dev float [n] (soft-max probability of the label), flip_dev int32 [n] =
+ * label == 1 && score > thresh (PaddleOCR's cls_thresh, 0.9), the flags lumina_ocr_rec_crop_oriented takes.  Runs in sub-batches of
+ * option "cls_sub_batch" crops (default 4096); no host synchronisation.  n_crops == 0 is a no-op. */
+int lumina_ocr_cls_forward(lumina_ocr_t* h, const uint8_t* crops_dev, const int32_t* widths_dev, int n_crops, float thresh, int32_t* label_dev,
+                           float* score_dev, int32_t* flip_dev, void* stream);
 
 /* CRNN (MobileNetV3-small x0.5 + 2xBiLSTM(96) + FC) with the CTC FC, arg-max and soft-max fused:
  * crops uint8 [n][32][320][3] (+ optional valid widths) -> idx int32 [n][80], prob float [n][80]. */

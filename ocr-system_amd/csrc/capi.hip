@@ -94,6 +94,7 @@ int lumina_ocr_set_option(lumina_ocr_t* h, const char* key, int value) {
     if (!h || !key) return 1;
     if (!strcmp(key, "det_sub_batch")) h->det_sub_batch = value > 0 ? value : 1;
     else if (!strcmp(key, "rec_sub_batch")) h->rec_sub_batch = value > 0 ? value : 1;
+    else if (!strcmp(key, "cls_sub_batch")) h->cls_sub_batch = value > 0 ? value : 1;
     else if (!strcmp(key, "keep_taps")) h->keep_taps = value < 0 || value > 2 ? 0 : value;
     else if (!strcmp(key, "time_convs")) h->time_convs = value != 0;
     else if (!strcmp(key, "fuse_head")) h->fuse_head = value != 0;
@@ -171,6 +172,43 @@ int lumina_ocr_rec_crop(lumina_ocr_t* h, const uint8_t* pages_dev, int batch, in
     BIND(h);
     (void)batch;
     return hip_rc(h, "rec_crop", rec_crop_launch(pages_dev, height, width, quads_dev, page_idx_dev, n_crops, crops_dev, widths_dev, (hipStream_t)stream));
+}
+
+int lumina_ocr_load_cls_weights(lumina_ocr_t* h, const void* blob, size_t nbytes) {
+    if (!h || !blob) return locr_fail(h, "load_cls_weights", "null argument");
+    BIND(h);
+    API_TRY return eng_load_cls(h, blob, nbytes); API_CATCH(h)
+}
+
+int lumina_ocr_cls_forward(lumina_ocr_t* h, const uint8_t* crops_dev, const int32_t* widths_dev, int n_crops, float thresh, int32_t* label_dev,
+                           float* score_dev, int32_t* flip_dev, void* stream) {
+    if (!h) return 1;
+    if (n_crops <= 0) return 0;
+    if (!crops_dev || !label_dev || !score_dev || !flip_dev) return locr_fail(h, "cls_forward", "null argument");
+    BIND(h);
+    API_TRY return eng_cls_forward(h, crops_dev, widths_dev, n_crops, thresh, label_dev, score_dev, flip_dev, (hipStream_t)stream); API_CATCH(h)
+}
+
+int lumina_ocr_rec_crop_oriented(lumina_ocr_t* h, const uint8_t* pages_dev, int batch, int height, int width, const int32_t* quads_dev,
+                                 const int32_t* page_idx_dev, int n_crops, const int32_t* flip_dev, uint8_t* crops_dev, int32_t* widths_dev,
+                                 void* stream) {
+    if (!h) return 1;
+    if (n_crops <= 0) return 0;
+    if (!pages_dev || !quads_dev || !page_idx_dev || !flip_dev || !crops_dev || !widths_dev) return locr_fail(h, "rec_crop_oriented", "null argument");
+    BIND(h);
+    (void)batch;
+    return hip_rc(h, "rec_crop_oriented", rec_crop_launch(pages_dev, height, width, quads_dev, page_idx_dev, n_crops, crops_dev, widths_dev,
+                                                         (hipStream_t)stream, flip_dev));
+}
+
+int lumina_ocr_cls_crop(lumina_ocr_t* h, const uint8_t* pages_dev, int batch, int height, int width, const int32_t* quads_dev,
+                        const int32_t* page_idx_dev, int n_crops, uint8_t* crops_dev, int32_t* widths_dev, void* stream) {
+    if (!h) return 1;
+    if (n_crops <= 0) return 0;
+    if (!pages_dev || !quads_dev || !page_idx_dev || !crops_dev || !widths_dev) return locr_fail(h, "cls_crop", "null argument");
+    BIND(h);
+    (void)batch;
+    return hip_rc(h, "cls_crop", cls_crop_launch(pages_dev, height, width, quads_dev, page_idx_dev, n_crops, crops_dev, widths_dev, (hipStream_t)stream));
 }
 
 int lumina_ocr_rec_forward(lumina_ocr_t* h, const uint8_t* crops_dev, const int32_t* widths_dev, int n_crops, int32_t* idx_dev, float* prob_dev,

@@ -472,9 +472,12 @@ __global__ __launch_bounds__(64) void compact_kernel(const int* box_tmp, const f
     if (lane == 0) counts[pg] = run;
 }
 
-// ---- recognition crop: one block per crop, threads over (row, col) ----
-__global__ __launch_bounds__(256) void rec_crop_kernel(const uint8_t* pages, int H, int W, const int* quads, const int* page_idx, uint8_t* crops,
-                                                       int* widths) {
+// ---- crops: one block per crop, threads over (row, col).  CH x CW = 32 x 320 (recogniser) or 48 x 192 (orientation classifier).
+// flip (optional): a crop whose flag is set is the 180-degree turn of the unflagged crop within its valid width — output (i, j) samples
+// the source position of (CH-1-i, wc-1-j) with the same operations, so it equals the turned crop byte for byte ----
+template <int CH, int CW>
+__global__ __launch_bounds__(256) void crop_kernel(const uint8_t* pages, int H, int W, const int* quads, const int* page_idx, const int* flip,
+                                                   uint8_t* crops, int* widths) {
     const int ci = blockIdx.x, tid = threadIdx.x;
     long long p[4][2];
 #pragma unroll
@@ -489,23 +492,25 @@ __global__ __launch_bounds__(256) void rec_crop_kernel(const uint8_t* pages, int
         p[2][0] = p[3][0]; p[2][1] = p[3][1]; p[3][0] = t0; p[3][1] = t1;
         const long long t = cw2; cw2 = ch2; ch2 = t;
     }
-    uint8_t* out = crops + (size_t)ci * 32 * 320 * 3;
+    uint8_t* out = crops + (size_t)ci * CH * CW * 3;
     int wc = 0;
     if (ch2 != 0 && cw2 != 0) {
         const double ratio = sqrt(__ddiv_rn((double)cw2, (double)ch2));
-        wc = (int)ceil(__dmul_rn(32.0, ratio));
-        wc = wc < 1 ? 1 : (wc > 320 ? 320 : wc);
+        wc = (int)ceil(__dmul_rn((double)CH, ratio));
+        wc = wc < 1 ? 1 : (wc > CW ? CW : wc);
     }
     if (tid == 0) widths[ci] = wc;
+    const bool turn = flip != nullptr && flip[ci] != 0;
     const uint8_t* page = pages + (size_t)page_idx[ci] * H * W * 3;
     const float tlx = (float)p[0][0], tly = (float)p[0][1];
     const float ex = (float)(p[1][0] - p[0][0]), ey = (float)(p[1][1] - p[0][1]);
     const float fx = (float)(p[3][0] - p[0][0]), fy = (float)(p[3][1] - p[0][1]);
-    for (int t = tid; t < 32 * 320; t += 256) {
-        const int i = t / 320, j = t - i * 320;
+    for (int t = tid; t < CH * CW; t += 256) {
+        const int i = t / CW, j = t - i * CW;
         uint8_t r3[3] = {0, 0, 0};
         if (j < wc) {
-            const float u = __fdiv_rn((float)j + 0.5f, (float)wc), v = __fdiv_rn((float)i + 0.5f, 32.0f);
+            const int si = turn ? CH - 1 - i : i, sj = turn ? wc - 1 - j : j;
+            const float u = __fdiv_rn((float)sj + 0.5f, (float)wc), v = __fdiv_rn((float)si + 0.5f, (float)CH);
             const float t1 = __fmul_rn(u, ex), t2 = __fmul_rn(v, fx), t3 = __fmul_rn(u, ey), t4 = __fmul_rn(v, fy);
             const float sx = __fadd_rn(__fadd_rn(tlx, t1), t2), sy = __fadd_rn(__fadd_rn(tly, t3), t4);
             const float x0f = floorf(sx), y0f = floorf(sy);
@@ -590,8 +595,15 @@ hipError_t dbpost_launch(const DbPostParams& p, void* workspace, size_t ws_bytes
 }
 
 hipError_t rec_crop_launch(const uint8_t* pages, int H, int W, const int* quads, const int* page_idx, int n, uint8_t* crops, int* widths,
+                           hipStream_t st, const int* flip) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL((crop_kernel<32, 320>), dim3(n), dim3(256), 0, st, pages, H, W, quads, page_idx, flip, crops, widths);
+    return hipGetLastError();
+}
+
+hipError_t cls_crop_launch(const uint8_t* pages, int H, int W, const int* quads, const int* page_idx, int n, uint8_t* crops, int* widths,
                            hipStream_t st) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(rec_crop_kernel, dim3(n), dim3(256), 0, st, pages, H, W, quads, page_idx, crops, widths);
+    hipLaunchKernelGGL((crop_kernel<48, 192>), dim3(n), dim3(256), 0, st, pages, H, W, quads, page_idx, nullptr, crops, widths);
     return hipGetLastError();
 }

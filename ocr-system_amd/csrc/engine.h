@@ -123,12 +123,18 @@ struct lumina_ocr {
     bf16_t* whh[2] = {nullptr, nullptr};
     bf16_t* ctc_wpk = nullptr; float* ctc_bias = nullptr;
     SvtrModel svtr;
+    // ---- orientation classifier (PP-OCR cls: MobileNetV3-small x0.35 on 48 x 192 crops, FC 200 -> 2) ----
+    bool cls_loaded = false;
+    bf16_t* cstem_wpk = nullptr; float* cstem_bias = nullptr;
+    std::vector<RecBlock> cblocks;
+    ConvLayer cconv2;
+    float *cls_fc_w = nullptr, *cls_fc_b = nullptr;   // fp32 [2][200], [2]
     // ---- workspace ----
     Growable<DeviceMem> ws;
     Arena arena;  // carves ws for the forward in progress (null base: its dry run, which sizes ws)
     std::vector<DeviceMem> owned;  // weights and tables, freed at destroy
     bf16_t* zeros = nullptr;  // 256 B of zeros (out-of-image halo source of the LDS-DMA conv); zero_block() uploads it at first use
-    int det_sub_batch = 16, rec_sub_batch = 4096, post_group = 64;
+    int det_sub_batch = 16, rec_sub_batch = 4096, cls_sub_batch = 4096, post_group = 64;
     int tail_group = 16;   // pages per pass of the detector's 1/4-resolution tail (lateral in2 -> p2 -> head) inside one det forward
     std::map<std::string, Tensor4> taps;  // last forward's intermediates (debug / parity tests)
     int keep_taps = 0;   // 1: every intermediate (switches the fusions that would skip one off); 2: fusions stay on, tap what still exists
@@ -171,6 +177,8 @@ int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n);
 int eng_det_forward(lumina_ocr* eng, const uint8_t* pages, int B, int H, int W, int Hp, int Wp, bf16_t* prob, hipStream_t st);
 int eng_rec_forward(lumina_ocr* eng, const uint8_t* crops, const int* widths, int N, int* idx, float* prob, hipStream_t st);
 int eng_load_svtr(lumina_ocr* eng, const void* blob, size_t n);
+int eng_load_cls(lumina_ocr* eng, const void* blob, size_t n);
+int eng_cls_forward(lumina_ocr* eng, const uint8_t* crops, const int* widths, int N, float thresh, int* label, float* score, int* flip, hipStream_t st);
 int eng_svtr_forward(lumina_ocr* eng, const uint8_t* crops, const int* widths, int N, int* idx, float* prob, hipStream_t st);
 int eng_ws_reserve(lumina_ocr* eng, size_t bytes);
 // a device copy of host data, owned by the engine until destroy (nullptr if the allocation or the copy fails)

@@ -98,6 +98,7 @@ static const bf16_t* zero_block(lumina_ocr* eng) {
 }
 
 static inline int rup(int v, int m) { return (v + m - 1) / m * m; }
+constexpr int CLS_H = 48, CLS_W = 192, CLS_FEAT = 200;   // classifier crop, conv2 channels (arch.CLS_*)
 
 // ------------------------------------------------------------------------------ layer construction
 static bool get_wb(lumina_ocr* eng, const std::map<std::string, HostBlobTensor>& m, const std::string& name,
@@ -614,37 +615,23 @@ static bool make_se(lumina_ocr* eng, const std::map<std::string, HostBlobTensor>
     return L->w1 && L->w2 && L->b1 && L->b2;
 }
 
-int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n) {
-    std::map<std::string, HostBlobTensor> m;
-    if (!parse_blob(eng, blob, n, &m)) return 1;
-    LOCR_CHECK(hipSetDevice(eng->device));
-    const double scale = 0.5;
-    const int c0 = make_div(16 * scale);
-    {
-        const HostBlobTensor *w, *b;
-        if (!get_wb(eng, m, "rec.conv1", &w, &b)) return 1;
-        if (w->dims[0] != c0 || w->dims[1] != 3 || w->dims[3] != 3) return locr_fail(eng, "rec.conv1", "shape");
-        bf16_t packed[2 * 2 * 32 * 8];
-        pack_stem_weights(reinterpret_cast<const bf16_t*>(w->data), c0, packed);
-        float bias[32] = {0};
-        memcpy(bias, b->data, sizeof(float) * c0);
-        eng->rstem_wpk = static_cast<bf16_t*>(eng_upload(eng, packed, sizeof(packed)));
-        eng->rstem_bias = static_cast<float*>(eng_upload(eng, bias, sizeof(bias)));
-    }
-    struct Row { int k, exp, c; bool se; int act, sh; };
-    const Row rows[11] = {{3, 16, 16, true, ACT_RELU, 1},    {3, 72, 24, false, ACT_RELU, 2},   {3, 88, 24, false, ACT_RELU, 1},
-                          {5, 96, 40, true, ACT_HSWISH, 2},  {5, 240, 40, true, ACT_HSWISH, 1}, {5, 240, 40, true, ACT_HSWISH, 1},
-                          {5, 120, 48, true, ACT_HSWISH, 1}, {5, 144, 48, true, ACT_HSWISH, 1}, {5, 288, 96, true, ACT_HSWISH, 2},
-                          {5, 576, 96, true, ACT_HSWISH, 1}, {5, 576, 96, true, ACT_HSWISH, 1}};
-    eng->rblocks.clear();
-    eng->rblocks.resize(11);
-    int cin = c0;
+// the 11 MobileNetV3-small blocks (arch._MV3_SMALL) of the recogniser ("rec") or the orientation classifier ("cls"): channel counts at
+// `scale`, vertical strides sh[11], input channels cin
+static int load_mv3_blocks(lumina_ocr* eng, const std::map<std::string, HostBlobTensor>& m, const std::string& prefix, double scale, const int* sh,
+                           int cin, std::vector<RecBlock>* blocks) {
+    struct Row { int k, exp, c; bool se; int act; };
+    static const Row rows[11] = {{3, 16, 16, true, ACT_RELU},    {3, 72, 24, false, ACT_RELU},   {3, 88, 24, false, ACT_RELU},
+                                 {5, 96, 40, true, ACT_HSWISH},  {5, 240, 40, true, ACT_HSWISH}, {5, 240, 40, true, ACT_HSWISH},
+                                 {5, 120, 48, true, ACT_HSWISH}, {5, 144, 48, true, ACT_HSWISH}, {5, 288, 96, true, ACT_HSWISH},
+                                 {5, 576, 96, true, ACT_HSWISH}, {5, 576, 96, true, ACT_HSWISH}};
+    blocks->clear();
+    blocks->resize(11);
     for (int i = 0; i < 11; ++i) {
-        RecBlock& B = eng->rblocks[i];
+        RecBlock& B = (*blocks)[i];
         B.k = rows[i].k; B.cin = cin; B.exp = make_div(rows[i].exp * scale); B.cout = make_div(rows[i].c * scale);
-        B.se = rows[i].se; B.se_mid = B.exp / 4; B.stride_h = rows[i].sh; B.act = rows[i].act;
+        B.se = rows[i].se; B.se_mid = B.exp / 4; B.stride_h = sh[i]; B.act = rows[i].act;
         B.res = (B.stride_h == 1 && B.cin == B.cout);
-        const std::string p = "rec.b" + std::to_string(i);
+        const std::string p = prefix + ".b" + std::to_string(i);
         if (!make_conv(eng, m, p + ".expand", 1, 1, B.cin, B.exp, cp16(B.cin), cp16(B.exp), B.act, &B.expand)) return 1;
         if (!make_dw(eng, m, p + ".dw", B.k, B.exp, cp16(B.exp), &B.dw)) return locr_fail(eng, "dw", p.c_str());
         {   // the same expand weights once more, in the fused kernel's fragment order
@@ -665,6 +652,29 @@ int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n) {
         if (!make_conv(eng, m, p + ".project", 1, 1, B.exp, B.cout, cp16(B.exp), cp16(B.cout), ACT_NONE, &B.project)) return 1;
         cin = B.cout;
     }
+    return 0;
+}
+
+int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n) {
+    std::map<std::string, HostBlobTensor> m;
+    if (!parse_blob(eng, blob, n, &m)) return 1;
+    LOCR_CHECK(hipSetDevice(eng->device));
+    const double scale = 0.5;
+    const int c0 = make_div(16 * scale);
+    {
+        const HostBlobTensor *w, *b;
+        if (!get_wb(eng, m, "rec.conv1", &w, &b)) return 1;
+        if (w->dims[0] != c0 || w->dims[1] != 3 || w->dims[3] != 3) return locr_fail(eng, "rec.conv1", "shape");
+        bf16_t packed[2 * 2 * 32 * 8];
+        pack_stem_weights(reinterpret_cast<const bf16_t*>(w->data), c0, packed);
+        float bias[32] = {0};
+        memcpy(bias, b->data, sizeof(float) * c0);
+        eng->rstem_wpk = static_cast<bf16_t*>(eng_upload(eng, packed, sizeof(packed)));
+        eng->rstem_bias = static_cast<float*>(eng_upload(eng, bias, sizeof(bias)));
+    }
+    static const int sh[11] = {1, 2, 1, 2, 1, 1, 1, 1, 2, 1, 1};
+    if (load_mv3_blocks(eng, m, "rec", scale, sh, c0, &eng->rblocks)) return 1;
+    const int cin = eng->rblocks.back().cout;
     if (!make_conv(eng, m, "rec.conv2", 1, 1, cin, 288, cp16(cin), 288, ACT_HSWISH, &eng->rconv2)) return 1;
     // LSTM: x-projection of both directions as one GEMM; recurrent weights [2][4H][H]
     const int Hh = 96;
@@ -715,6 +725,47 @@ int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n) {
         }                                                                                                         \
     } while (0)
 
+// one MobileNetV3 block (expand -> depthwise -> [squeeze-excite] -> project [+ residual]) of the recogniser or the classifier on *x, which
+// becomes the block's output (tap `name`)
+static int run_mv3_block(lumina_ocr* eng, const RecBlock& B, const std::string& name, Tensor4* x, hipStream_t st) {
+    const bool dry = eng->arena.counting();
+    const int N = x->n;
+    const int ho = (x->h + 2 * (B.k / 2) - B.k) / B.stride_h + 1;
+    MbParams mp{};
+    mp.we = B.we_pk; mp.be = B.be_pk; mp.wd = B.dw.w; mp.bd = B.dw.bias;
+    mp.N = N; mp.H = x->h; mp.W = x->w; mp.cin = x->c; mp.expc = cp16(B.exp); mp.Ho = ho; mp.act = B.act;
+    const bool fused_mb = eng->fuse_mb && mbconv_supported(mp, B.k, B.stride_h);
+    Tensor4 e1{};
+    if (!fused_mb || dry) e1 = ws_tensor(eng, N, x->h, x->w, cp16(B.exp));   // (dry run sizes the arena for the unfused path too)
+    Tensor4 d = ws_tensor(eng, N, ho, x->w, cp16(B.exp));
+    float* pool = B.se ? eng->arena.take<float>((size_t)N * mb_strips(x->w) * d.c) : nullptr;
+    if (fused_mb) {
+        mp.x = x->p; mp.d = d.p; mp.pool = pool;   // squeeze-excite blocks: the pooled sums leave with the tile (the tensor is not read again for them)
+        if (!dry && x->p && d.p) {
+            LaunchTimer tm(eng, st);
+            LAUNCH("mbconv", mbconv_launch(mp, B.k, B.stride_h, st));
+            const double opx = (double)N * ho * x->w, ipx = (double)N * x->h * x->w;
+            tm.done(name + ".expand+dw", "mbconv_kernel<" + std::to_string(B.k) + "," + std::to_string(B.stride_h) + "," + std::to_string(B.act) + ">",
+                    2.0 * ipx * x->c * mp.expc + 2.0 * opx * B.k * B.k * mp.expc, 2.0 * (ipx * x->c + opx * mp.expc));
+        }
+    } else {
+        RUN(eng_run_conv(eng, B.expand, *x, &e1, nullptr, 0, OUT_NORMAL, 0, 0, 0, true, st));
+        LAUNCH("dwconv", dwconv_launch(e1.p, B.dw.w, B.dw.bias, d.p, N, e1.h, e1.w, e1.c, B.k, B.stride_h, B.act, st));
+        if (B.se) LAUNCH("se_pool", se_pool_launch(d.p, pool, N, d.h, d.w, d.c, st));   // the same sums in the same order
+    }
+    const bf16_t* se_gate_ptr = nullptr;
+    if (B.se) {
+        bf16_t* gate = eng->arena.take<bf16_t>((size_t)N * d.c);
+        LAUNCH("se_fc", se_fc_launch(pool, mb_strips(d.w), B.sel.w1, B.sel.b1, B.sel.w2, B.sel.b2, gate, N, d.h * d.w, d.c, B.sel.mid, st));
+        se_gate_ptr = gate;   // the scaling itself is fused into the project conv's operand staging
+    }
+    Tensor4 o = ws_tensor(eng, N, d.h, d.w, cp16(B.cout));
+    RUN(eng_run_conv(eng, B.project, d, &o, B.res ? x : nullptr, 0, OUT_NORMAL, 0, 0, 0, true, st, se_gate_ptr));
+    tap(eng, name.c_str(), o);
+    *x = o;
+    return 0;
+}
+
 static int rec_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* widths, int N, int* idx, float* prob, hipStream_t st) {
     const bool dry = eng->arena.counting();
     const int T = 80;
@@ -729,42 +780,7 @@ static int rec_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* wid
         if (e != hipSuccess) return locr_fail(eng, "rec.conv1", hipGetErrorString(e));
     }
     tap(eng, "rec.conv1", x);
-    for (size_t bi = 0; bi < eng->rblocks.size(); ++bi) {
-        RecBlock& B = eng->rblocks[bi];
-        const int ho = (x.h + 2 * (B.k / 2) - B.k) / B.stride_h + 1;
-        MbParams mp{};
-        mp.we = B.we_pk; mp.be = B.be_pk; mp.wd = B.dw.w; mp.bd = B.dw.bias;
-        mp.N = N; mp.H = x.h; mp.W = x.w; mp.cin = x.c; mp.expc = cp16(B.exp); mp.Ho = ho; mp.act = B.act;
-        const bool fused_mb = eng->fuse_mb && mbconv_supported(mp, B.k, B.stride_h);
-        Tensor4 e1{};
-        if (!fused_mb || dry) e1 = ws_tensor(eng, N, x.h, x.w, cp16(B.exp));   // (dry run sizes the arena for the unfused path too)
-        Tensor4 d = ws_tensor(eng, N, ho, x.w, cp16(B.exp));
-        float* pool = B.se ? eng->arena.take<float>((size_t)N * mb_strips(x.w) * d.c) : nullptr;
-        if (fused_mb) {
-            mp.x = x.p; mp.d = d.p; mp.pool = pool;   // squeeze-excite blocks: the pooled sums leave with the tile (the tensor is not read again for them)
-            if (!dry && x.p && d.p) {
-                LaunchTimer tm(eng, st);
-                LAUNCH("mbconv", mbconv_launch(mp, B.k, B.stride_h, st));
-                const double opx = (double)N * ho * x.w, ipx = (double)N * x.h * x.w;
-                tm.done("rec.b" + std::to_string(bi) + ".expand+dw", "mbconv_kernel<" + std::to_string(B.k) + "," + std::to_string(B.stride_h) + "," + std::to_string(B.act) + ">",
-                        2.0 * ipx * x.c * mp.expc + 2.0 * opx * B.k * B.k * mp.expc, 2.0 * (ipx * x.c + opx * mp.expc));
-            }
-        } else {
-            RUN(eng_run_conv(eng, B.expand, x, &e1, nullptr, 0, OUT_NORMAL, 0, 0, 0, true, st));
-            LAUNCH("dwconv", dwconv_launch(e1.p, B.dw.w, B.dw.bias, d.p, N, e1.h, e1.w, e1.c, B.k, B.stride_h, B.act, st));
-            if (B.se) LAUNCH("se_pool", se_pool_launch(d.p, pool, N, d.h, d.w, d.c, st));   // the same sums in the same order
-        }
-        const bf16_t* se_gate_ptr = nullptr;
-        if (B.se) {
-            bf16_t* gate = eng->arena.take<bf16_t>((size_t)N * d.c);
-            LAUNCH("se_fc", se_fc_launch(pool, mb_strips(d.w), B.sel.w1, B.sel.b1, B.sel.w2, B.sel.b2, gate, N, d.h * d.w, d.c, B.sel.mid, st));
-            se_gate_ptr = gate;   // the scaling itself is fused into the project conv's operand staging
-        }
-        Tensor4 o = ws_tensor(eng, N, d.h, d.w, cp16(B.cout));
-        RUN(eng_run_conv(eng, B.project, d, &o, B.res ? &x : nullptr, 0, OUT_NORMAL, 0, 0, 0, true, st, se_gate_ptr));
-        tap(eng, ("rec.b" + std::to_string(bi)).c_str(), o);
-        x = o;
-    }
+    for (size_t bi = 0; bi < eng->rblocks.size(); ++bi) RUN(run_mv3_block(eng, eng->rblocks[bi], "rec.b" + std::to_string(bi), &x, st));
     Tensor4 f = ws_tensor(eng, N, x.h, x.w, 288);
     RUN(eng_run_conv(eng, eng->rconv2, x, &f, nullptr, 0, OUT_NORMAL, 0, 0, 0, true, st)); tap(eng, "rec.conv2", f);
     Tensor4 seq = ws_tensor(eng, N, 1, T, 288);
@@ -799,6 +815,90 @@ int eng_rec_forward(lumina_ocr* eng, const uint8_t* crops, const int* widths, in
     LOCR_CHECK(hipSetDevice(eng->device));
     return forward_sub_batched(eng, N, eng->rec_sub_batch < N ? eng->rec_sub_batch : N, [&](int b0, int nb) {
         return rec_forward_sub(eng, crops + (size_t)b0 * 32 * 320 * 3, widths ? widths + b0 : nullptr, nb, idx + (size_t)b0 * 80, prob + (size_t)b0 * 80, st);
+    });
+}
+
+// ------------------------------------------------------------------------------ orientation classifier (PP-OCR cls)
+// MobileNetV3-small x0.35 (arch.cls_block_table: the recogniser's blocks, vertical strides 2 on blocks 0, 1, 3, 8) on 48 x 192 crops:
+// 24 x 96 after the stem, 2 x 96 after block 10 -> conv2 (1x1, 200, hswish) -> 2x2 max pool -> 48 positions -> cls_head_kernel
+int eng_load_cls(lumina_ocr* eng, const void* blob, size_t n) {
+    std::map<std::string, HostBlobTensor> m;
+    if (!parse_blob(eng, blob, n, &m)) return 1;
+    LOCR_CHECK(hipSetDevice(eng->device));
+    eng->cls_loaded = false;
+    const double scale = 0.35;
+    const int c0 = make_div(16 * scale);
+    {
+        const HostBlobTensor *w, *b;
+        if (!get_wb(eng, m, "cls.conv1", &w, &b)) return 1;
+        if (w->dims.size() != 4 || w->dims[0] != c0 || w->dims[1] != 3 || w->dims[2] != 3 || w->dims[3] != 3 || b->dims[0] != c0)
+            return locr_fail(eng, "cls.conv1", "shape");
+        bf16_t packed[2 * 2 * 32 * 8];
+        pack_stem_weights(reinterpret_cast<const bf16_t*>(w->data), c0, packed);
+        float bias[32] = {0};
+        memcpy(bias, b->data, sizeof(float) * c0);
+        eng->cstem_wpk = static_cast<bf16_t*>(eng_upload(eng, packed, sizeof(packed)));
+        eng->cstem_bias = static_cast<float*>(eng_upload(eng, bias, sizeof(bias)));
+        if (!eng->cstem_wpk || !eng->cstem_bias) return locr_fail(eng, "upload", "cls.conv1");
+    }
+    static const int sh[11] = {2, 2, 1, 2, 1, 1, 1, 1, 2, 1, 1};
+    if (load_mv3_blocks(eng, m, "cls", scale, sh, c0, &eng->cblocks)) return 1;
+    const int cin = eng->cblocks.back().cout;
+    if (!make_conv(eng, m, "cls.conv2", 1, 1, cin, CLS_FEAT, cp16(cin), cp16(CLS_FEAT), ACT_HSWISH, &eng->cconv2)) return 1;
+    {
+        auto w = m.find("cls.fc.w"), b = m.find("cls.fc.b");
+        if (w == m.end() || b == m.end() || w->second.dtype != 1 || b->second.dtype != 0 || w->second.dims.size() != 2 || w->second.dims[0] != 2 ||
+            w->second.dims[1] != CLS_FEAT || b->second.dims.size() != 1 || b->second.dims[0] != 2)
+            return locr_fail(eng, "cls.fc", "missing/shape (w bf16 [2][200], b f32 [2])");
+        std::vector<float> fw(2 * CLS_FEAT);
+        const bf16_t* src = reinterpret_cast<const bf16_t*>(w->second.data);
+        for (int i = 0; i < 2 * CLS_FEAT; ++i) fw[i] = host_bf16_to_f32(src[i]);
+        eng->cls_fc_w = static_cast<float*>(eng_upload(eng, fw.data(), fw.size() * sizeof(float)));
+        eng->cls_fc_b = static_cast<float*>(eng_upload(eng, b->second.data, 2 * sizeof(float)));
+        if (!eng->cls_fc_w || !eng->cls_fc_b) return locr_fail(eng, "upload", "cls.fc");
+    }
+    eng->cls_loaded = true;
+    return 0;
+}
+
+static int cls_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* widths, int N, float thresh, int* label, float* score, int* flip,
+                           hipStream_t st) {
+    const bool dry = eng->arena.counting();
+    Tensor4 x = ws_tensor(eng, N, CLS_H / 2, CLS_W / 2, 16);
+    if (!dry && x.p) {
+        StemParams sp{};
+        sp.x = crops; sp.wpk = eng->cstem_wpk; sp.bias = eng->cstem_bias; sp.y = x.p; sp.valid_w_per_img = widths;
+        sp.N = N; sp.H = CLS_H; sp.W = CLS_W; sp.valid_h = CLS_H; sp.valid_w = CLS_W; sp.Ho = x.h; sp.Wo = x.w; sp.Cout_store = 16;
+        sp.act = ACT_HSWISH;
+        for (int c = 0; c < 3; ++c) { sp.scale[c] = 2.0f / 255.0f; sp.shift[c] = -1.0f; }
+        hipError_t e = stem_conv_launch(sp, st);
+        if (e != hipSuccess) return locr_fail(eng, "cls.conv1", hipGetErrorString(e));
+    }
+    tap(eng, "cls.conv1", x);
+    for (size_t bi = 0; bi < eng->cblocks.size(); ++bi) RUN(run_mv3_block(eng, eng->cblocks[bi], "cls.b" + std::to_string(bi), &x, st));
+    Tensor4 f = ws_tensor(eng, N, x.h, x.w, eng->cconv2.cout);
+    RUN(eng_run_conv(eng, eng->cconv2, x, &f, nullptr, 0, OUT_NORMAL, 0, 0, 0, true, st)); tap(eng, "cls.conv2", f);
+    if (f.h != 2 || f.w % 2) return locr_fail(eng, "cls_forward", "unexpected feature map");
+    Tensor4 feat = ws_tensor(eng, N, 1, f.w / 2, f.c);
+    LAUNCH("cls.pool", maxpool_launch(f.p, feat.p, N, f.h, f.w, f.c, 2, 2, 0, 1, feat.w, st));
+    tap(eng, "cls.feat", feat);
+    Tensor4 logits = ws_tensor(eng, N, 1, 1, 2);
+    {
+        LaunchTimer tm(eng, st, !dry);
+        LAUNCH("cls.head", cls_head_launch(feat.p, eng->cls_fc_w, eng->cls_fc_b, N, feat.w, CLS_FEAT, feat.c, thresh, label, score, flip, logits.p, st));
+        tm.done("cls.head", "cls_head_kernel", (double)N * (feat.w * CLS_FEAT + 4.0 * CLS_FEAT), 2.0 * N * feat.w * feat.c);
+    }
+    tap(eng, "cls.logits", logits);
+    return 0;
+}
+
+int eng_cls_forward(lumina_ocr* eng, const uint8_t* crops, const int* widths, int N, float thresh, int* label, float* score, int* flip, hipStream_t st) {
+    if (!eng->cls_loaded) return locr_fail(eng, "cls_forward", "cls weights not loaded");
+    if (N <= 0) return 0;
+    LOCR_CHECK(hipSetDevice(eng->device));
+    return forward_sub_batched(eng, N, eng->cls_sub_batch < N ? eng->cls_sub_batch : N, [&](int b0, int nb) {
+        return cls_forward_sub(eng, crops + (size_t)b0 * CLS_H * CLS_W * 3, widths ? widths + b0 : nullptr, nb, thresh, label + b0, score + b0,
+                               flip + b0, st);
     });
 }
 

@@ -36,5 +36,11 @@ size_t ctc_packed_weight_elems(int C, int K);
 void pack_ctc_weights(const bf16_t* w /*[C][K]*/, int C, int K, bf16_t* out);
 hipError_t ctc_fc_argmax_launch(const CtcFcParams& p, hipStream_t st);
 
+// Orientation-classifier head (PP-OCR ClsHead + the cls_thresh decision), one wave per crop: feat [N][P][Cs] bf16 (C <= 256 real channels)
+// -> mean over the P positions (summed in position order, then / P) -> logits = FC (w [2][C] f32, summed in channel order, + b) ->
+// label = argmax (ties: 0), score = 1 / (1 + exp(-|l1 - l0|)), flip = label == 1 && score > thresh; logits_bf16 [N][2] (tap).
+hipError_t cls_head_launch(const bf16_t* feat, const float* w, const float* b, int N, int P, int C, int Cs, float thresh, int* label, float* score,
+                           int* flip, bf16_t* logits_bf16, hipStream_t st);
+
 // CTC greedy collapse: idx/prob [N][T] -> text [N][T] (class indices, -1 padded), len [N], score [N]
 hipError_t ctc_collapse_launch(const int* idx, const float* prob, int* text, int* len, float* score, int N, int T, hipStream_t st);

@@ -400,6 +400,34 @@ int grid_for(size_t total) {
     return (int)(g > 256 * 64 ? 256 * 64 : (g ? g : 1));
 }
 
+// ---- orientation-classifier head: one wave per crop ----
+__global__ __launch_bounds__(64) void cls_head_kernel(const bf16_t* __restrict__ feat, const float* __restrict__ w, const float* __restrict__ b, int P,
+                                                      int C, int Cs, float thresh, int* label, float* score, int* flip, bf16_t* logits_bf16) {
+    __shared__ float mean[256];
+    __shared__ float lg[2];
+    const int n = blockIdx.x, lane = threadIdx.x;
+    const bf16_t* f = feat + (size_t)n * P * Cs;
+    for (int c = lane; c < C; c += 64) {
+        float s = 0.f;
+        for (int q = 0; q < P; ++q) s = __fadd_rn(s, bf16_to_f32(f[(size_t)q * Cs + c]));
+        mean[c] = __fdiv_rn(s, (float)P);
+    }
+    __syncthreads();
+    if (lane < 2) {
+        float acc = 0.f;
+        for (int c = 0; c < C; ++c) acc = __fadd_rn(acc, __fmul_rn(w[lane * C + c], mean[c]));
+        lg[lane] = __fadd_rn(acc, b[lane]);
+    }
+    __syncthreads();
+    if (lane == 0) {
+        const int lab = lg[1] > lg[0] ? 1 : 0;
+        const float d = fabsf(__fsub_rn(lg[1], lg[0]));
+        const float sc = __fdiv_rn(1.f, __fadd_rn(1.f, expf(-d)));
+        label[n] = lab; score[n] = sc; flip[n] = (lab == 1 && sc > thresh) ? 1 : 0;
+        logits_bf16[2 * n] = f32_to_bf16(lg[0]); logits_bf16[2 * n + 1] = f32_to_bf16(lg[1]);
+    }
+}
+
 }  // namespace
 
 hipError_t maxpool_launch(const bf16_t* x, bf16_t* y, int N, int H, int W, int C, int k, int s, int pad, int Ho, int Wo, hipStream_t st) {
@@ -474,5 +502,13 @@ hipError_t ctc_fc_argmax_launch(const CtcFcParams& p, hipStream_t st) {
 hipError_t ctc_collapse_launch(const int* idx, const float* prob, int* text, int* len, float* score, int N, int T, hipStream_t st) {
     if (T > 128) return hipErrorInvalidValue;
     hipLaunchKernelGGL(ctc_collapse_kernel, dim3(N), dim3(64), 0, st, idx, prob, text, len, score, T);
+    return hipGetLastError();
+}
+
+hipError_t cls_head_launch(const bf16_t* feat, const float* w, const float* b, int N, int P, int C, int Cs, float thresh, int* label, float* score,
+                           int* flip, bf16_t* logits_bf16, hipStream_t st) {
+    if (N <= 0) return hipSuccess;
+    if (C <= 0 || C > 256 || Cs < C || P <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cls_head_kernel, dim3(N), dim3(64), 0, st, feat, w, b, P, C, Cs, thresh, label, score, flip, logits_bf16);
     return hipGetLastError();
 }

@@ -15,7 +15,7 @@ engine (which hard-codes the same layer names) and the test oracle:
 from __future__ import annotations
 
 import struct
-from typing import Dict, List, Tuple
+from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 
@@ -152,10 +152,13 @@ _MV3_SMALL = [
 ]
 
 
-def rec_block_table(scale: float = 0.5) -> List[dict]:
+def rec_block_table(scale: float = 0.5, strides: Sequence[int] = None) -> List[dict]:
+    """strides: vertical stride per block (default: the CRNN's, the last field of _MV3_SMALL)."""
     blocks = []
     cin = _make_div(16 * scale)
     for i, (k, exp, c, se, act, sh) in enumerate(_MV3_SMALL):
+        if strides is not None:
+            sh = strides[i]
         e, co = _make_div(exp * scale), _make_div(c * scale)
         blocks.append(dict(idx=i, k=k, cin=cin, exp=e, cout=co, se=se, act=act, stride_h=sh,
                            res=(sh == 1 and cin == co), se_mid=e // 4))
@@ -429,6 +432,121 @@ def make_rec_weights(seed: int = 4321, num_classes: int = 6625, scale: float = 0
     w["ctc.fc.b"] = (rng.standard_normal(num_classes, dtype=np.float32) * np.float32(0.1)).astype(np.float32)
     if code_path:
         _install_code_path(w, num_classes, scale)
+    return w
+
+
+# --------------------------------------------------------------------------------------
+# Text-line orientation classifier (PP-OCR `cls`, ch_ppocr_mobile_v2.0_cls): the recogniser's MobileNetV3-small backbone at
+# scale 0.35 on 48 x 192 crops with small_stride [2, 2, 2, 2] (block 0 halves the height too) -> conv2 (1x1, 200, hswish) ->
+# 2x2 max pool -> mean over the 48 positions -> FC(2) -> soft-max.  Label 0 = "0", 1 = "180"; a crop is turned when
+# label == 1 and its probability > CLS_THRESH (PaddleOCR's cls_thresh).
+# --------------------------------------------------------------------------------------
+CLS_H, CLS_W = 48, 192
+CLS_SCALE = 0.35
+CLS_STRIDES = (2, 2, 1, 2, 1, 1, 1, 1, 2, 1, 1)
+CLS_FEAT = 200
+CLS_THRESH = 0.9
+
+
+def cls_block_table() -> List[dict]:
+    """rec_block_table at scale 0.35 with the classifier's strides; `h` = the block's output height on a 48-row crop."""
+    blocks = rec_block_table(CLS_SCALE, CLS_STRIDES)
+    h = CLS_H // 2
+    for b in blocks:
+        h = (h + 2 * (b["k"] // 2) - b["k"]) // b["stride_h"] + 1
+        b["h"] = h
+    return blocks
+
+
+# Hand-set "orientation path" of the classifier (the counterpart of the text path and the code path; make_cls_weights(orientation_path=True)).
+# What it reads: a SOLID horizontal ink band, such as the rule under each line of synth.synth_page(..., ruled=True) (a filled-in
+# form); a glyph stroke is rarely 3 px wide and 2 rows high at once.  Channel 0 of every tensor up to block 7 carries it; block 8 splits
+# it into T (channel 0, crop rows 0..15) and B (channel 1, crop rows 32..47):
+#   cls.conv1 ch 0  : hswish(-(sum of the G channel over crop rows 2r, 2r + 1 x 3 columns) - 3.5): > 0 only where all six pixels are
+#                     dark (the ink shades of synth pages, 0..40, give 0.62..2.5); relu in b0 drops the rest
+#   b0, b1, b3      : expand 1.0, depthwise with TWO unit taps (rows 2o, 2o + 1), project 1.0: each stride-2 stage sums a pair of
+#                     rows, so b3's output row 0 holds crop rows 0..15 and its row 2 crop rows 32..47
+#   residual blocks : carried by the shortcut (project row = 0); squeeze-excite gates of the path channels pinned to 1
+#   b8 (k 5, s 2)   : T = one tap kh = 0 (output row 0 reads the zero padding, row 1 = b3's row 0), B = one tap kh = 4 (row 0 = b3's
+#                     row 2, row 1 reads the padding); conv2 and the max pool carry both (unit weights, the padding row gives 0)
+#   cls.fc          : logit0 = CLS_GAIN * mean(B), logit1 = CLS_GAIN * mean(T) + the FC's dense columns scaled by 2^-6
+# Exactness: the stem's six G values are bf16 in [-1, 1] (multiples of 2^-15), so its sum is exact in any order; every later value on
+# the path is a bf16 number >= 2^-16 or 0 and <= 2^7, and sums of a few such values are exact in fp32 in any order.  The head sums
+# positions and channels in a fixed order.  Engine and restatement agree on the path bit for bit.
+# Decision rule: a line is read upside down when its top band holds more solid ink than its bottom band.  The detector's boxes
+# reach further below the ink than above it, so an upright line's rule falls in the bottom band only when it is thick: the ruled
+# pages draw it size // 3 px thick, 2 px under the text.  Measured with the restatement (seeds 3 / 7 / 21, detector text path):
+# every line of every page labelled right, upright and turned; on pages 480 and 640 rows high (fonts 16-25 px) |logit1 - logit0|
+# >= 9.7 on every line (score > 0.9999); on 320-row pages (10-15 px fonts) the thinnest rules miss the bottom band of some upright
+# lines, whose label stays 0 with a margin down to 0.85.
+# All other rows of every layer stay seeded and dense.
+CLS_GAIN = 16.0
+CLS_DENSE_SCALE = 2.0 ** -6     # the FC's dense columns, scaled (exactly) so that the seeded part cannot outvote the path
+CLS_MARGIN = 8.0                # |logit1 - logit0| the tests require on every line of ruled pages >= 480 rows high
+
+
+def _install_orientation_path(w: Dict[str, np.ndarray]) -> None:
+    def zero_rows(name, rows):
+        for r in rows:
+            w[name + ".w"][r] = 0.0
+            w[name + ".b"][r] = 0.0
+
+    zero_rows("cls.conv1", [0])
+    w["cls.conv1.w"][0, 1:3, :, 1] = -1.0
+    w["cls.conv1.b"][0] = -3.5
+    for b in cls_block_table():
+        p, c = f"cls.b{b['idx']}", b["k"] // 2
+        if b["res"]:
+            zero_rows(p + ".project", [0, 1] if b["idx"] > 8 else [0])
+            continue
+        rows = [0, 1] if b["idx"] == 8 else [0]
+        zero_rows(p + ".expand", rows); zero_rows(p + ".dw", rows); zero_rows(p + ".project", rows)
+        for r in rows:
+            w[p + ".expand.w"][r, 0, 0, 0] = 1.0
+            w[p + ".project.w"][r, 0, 0, r] = 1.0
+        if b["idx"] == 8:
+            w[p + ".dw.w"][0, 0, c, 0] = 1.0          # T: the top band
+            w[p + ".dw.w"][1, 4, c, 0] = 1.0          # B: the bottom band
+        else:
+            w[p + ".dw.w"][0, c, c, 0] = 1.0          # rows 2o, 2o + 1
+            w[p + ".dw.w"][0, c + 1, c, 0] = 1.0
+        if b["se"]:
+            zero_rows(p + ".se2", rows)
+            w[p + ".se2.b"][rows] = 4.0               # hard-sigmoid(4) = 1
+    zero_rows("cls.conv2", [0, 1])
+    w["cls.conv2.w"][0, 0, 0, 0] = 1.0
+    w["cls.conv2.w"][1, 0, 0, 1] = 1.0
+    w["cls.fc.w"][:, 2:] *= CLS_DENSE_SCALE
+    w["cls.fc.w"][:, :2] = 0.0
+    w["cls.fc.w"][0, 1] = CLS_GAIN
+    w["cls.fc.w"][1, 0] = CLS_GAIN
+    w["cls.fc.b"][:] = 0.0
+
+
+def make_cls_weights(seed: int = 2718, orientation_path: bool = False) -> Dict[str, np.ndarray]:
+    """Seeded classifier weights in the LOCW naming (cls.*), every row dense; orientation_path: install the hand-set exact path above."""
+    rng = np.random.default_rng(seed)
+    w: Dict[str, np.ndarray] = {}
+
+    def conv(name, cout, k, cin, gain=1.0, depthwise=False):
+        w[name + ".w"] = _he(rng, cout, k, 1 if depthwise else cin, gain, depthwise)
+        w[name + ".b"] = (rng.standard_normal(cout, dtype=np.float32) * np.float32(0.05)).astype(np.float32)
+
+    conv("cls.conv1", rec_stem_ch(CLS_SCALE), 3, 3)
+    for b in cls_block_table():
+        p = f"cls.b{b['idx']}"
+        hs = b["act"] == "hswish"
+        conv(p + ".expand", b["exp"], 1, b["cin"], gain=1.25 if hs else 1.0)
+        conv(p + ".dw", b["exp"], b["k"], b["exp"], gain=1.25 if hs else 1.0, depthwise=True)
+        if b["se"]:
+            conv(p + ".se1", b["se_mid"], 1, b["exp"])
+            conv(p + ".se2", b["exp"], 1, b["se_mid"], gain=0.7071)
+        conv(p + ".project", b["cout"], 1, b["exp"], gain=(0.5 if b["res"] else 1.4) * (1.4 if b["se"] else 1.0))
+    conv("cls.conv2", CLS_FEAT, 1, cls_block_table()[-1]["cout"])
+    w["cls.fc.w"] = bf16_round(rng.standard_normal((2, CLS_FEAT), dtype=np.float32) * np.float32(1.0 / np.sqrt(CLS_FEAT)))
+    w["cls.fc.b"] = (rng.standard_normal(2, dtype=np.float32) * np.float32(0.05)).astype(np.float32)
+    if orientation_path:
+        _install_orientation_path(w)
     return w
 
 

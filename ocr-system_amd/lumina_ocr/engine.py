@@ -57,6 +57,10 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_det_forward": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp]),
         "lumina_ocr_det_postprocess": (i32, [vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, i32, i32, vp, vp, vp, vp]),
         "lumina_ocr_rec_crop": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp]),
+        "lumina_ocr_rec_crop_oriented": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp]),
+        "lumina_ocr_cls_crop": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, vp]),
+        "lumina_ocr_load_cls_weights": (i32, [vp, vp, sz]),
+        "lumina_ocr_cls_forward": (i32, [vp, vp, vp, i32, f32, vp, vp, vp, vp]),
         "lumina_ocr_rec_forward": (i32, [vp, vp, vp, i32, vp, vp, vp]),
         "lumina_ocr_ctc_decode": (i32, [vp, vp, vp, i32, vp, vp, vp, vp]),
         "lumina_ocr_conv2d": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
@@ -101,7 +105,8 @@ def load_library() -> ctypes.CDLL:
 EXPORTED_SYMBOLS = [
     "lumina_ocr_create", "lumina_ocr_destroy", "lumina_ocr_last_error", "lumina_ocr_version", "lumina_ocr_set_option",
     "lumina_ocr_load_det_weights", "lumina_ocr_load_rec_weights", "lumina_ocr_num_classes", "lumina_ocr_normalize",
-    "lumina_ocr_det_forward", "lumina_ocr_det_postprocess", "lumina_ocr_rec_crop", "lumina_ocr_rec_forward",
+    "lumina_ocr_det_forward", "lumina_ocr_det_postprocess", "lumina_ocr_rec_crop", "lumina_ocr_rec_crop_oriented", "lumina_ocr_cls_crop",
+    "lumina_ocr_load_cls_weights", "lumina_ocr_cls_forward", "lumina_ocr_rec_forward",
     "lumina_ocr_ctc_decode", "lumina_ocr_conv2d", "lumina_ocr_read_tap", "lumina_ocr_conv_timing", "lumina_ocr_conv_timing_detail",
     "lumina_ocr_resize_lanczos", "lumina_ocr_enhance", "lumina_ocr_jpeg_encode", "lumina_ocr_jpeg_coefficients", "lumina_ocr_jpeg_probe", "lumina_ocr_jpeg_decode", "lumina_ocr_jpeg_decode_async", "lumina_ocr_jpeg_last_passes",
     "lumina_ocr_png_probe", "lumina_ocr_png_decode",
@@ -135,7 +140,7 @@ class Engine:
             msg = self.lib.lumina_ocr_last_error(h).decode() if h else "create failed"
             raise EngineUnavailable(msg)
         self.num_classes = self.svtr_num_classes = 0
-        self.det_loaded = self.rec_loaded = self.svtr_loaded = False
+        self.det_loaded = self.rec_loaded = self.svtr_loaded = self.cls_loaded = False
 
     # -- plumbing -------------------------------------------------------------------------
     def close(self):
@@ -264,6 +269,13 @@ class Engine:
         self.num_classes = self.lib.lumina_ocr_num_classes(self._h)
         self.rec_loaded = True
 
+    def load_cls(self, weights):
+        """Orientation-classifier weights (arch.make_cls_weights or a LOCW blob with the cls.* tensors)."""
+        blob = weights if isinstance(weights, (bytes, bytearray)) else arch.write_blob(weights)
+        buf = ctypes.create_string_buffer(bytes(blob), len(blob))
+        self._chk(self.lib.lumina_ocr_load_cls_weights(self._h, ctypes.cast(buf, ctypes.c_void_p), len(blob)))
+        self.cls_loaded = True
+
     def load_svtr(self, weights, f16=None):
         """SVTR recogniser weights (arch.make_svtr_weights or a LOCW blob with the svtr.* tensors): Tiny or Base, bf16 or fp16 as the
         blob's svtr.config says; f16 = True / False overrides the storage / MFMA type."""
@@ -309,16 +321,50 @@ class Engine:
                                                       self._stream()))
         return boxes, scores, counts
 
-    def rec_crop(self, pages, quads, page_idx):
+    def rec_crop(self, pages, quads, page_idx, flip=None):
+        """flip: None, or int32 [n] device flags (cls_forward's): a flagged crop is turned by 180 degrees within its valid width."""
         torch = _torch()
         b, h, w, _ = pages.shape
         n = quads.shape[0]
         crops = torch.empty((n, REC_H, REC_W, 3), dtype=torch.uint8, device=pages.device)
         widths = torch.empty((n,), dtype=torch.int32, device=pages.device)
-        if n:
+        if n and flip is None:
             self._chk(self.lib.lumina_ocr_rec_crop(self._h, _ptr(pages), b, h, w, _ptr(quads), _ptr(page_idx), n, _ptr(crops),
                                                    _ptr(widths), self._stream()))
+        elif n:
+            if flip.dtype != torch.int32 or flip.device != pages.device or tuple(flip.shape) != (n,):
+                raise ValueError("flip must be int32 [%d] on %s" % (n, pages.device))
+            flip = flip.contiguous()
+            self._chk(self.lib.lumina_ocr_rec_crop_oriented(self._h, _ptr(pages), b, h, w, _ptr(quads), _ptr(page_idx), n, _ptr(flip),
+                                                            _ptr(crops), _ptr(widths), self._stream()))
         return crops, widths
+
+    def cls_crop(self, pages, quads, page_idx):
+        """The orientation classifier's crops: uint8 [n, 48, 192, 3] device + valid widths int32 [n] (min(192, ceil(48 * ratio)))."""
+        torch = _torch()
+        b, h, w, _ = pages.shape
+        n = quads.shape[0]
+        crops = torch.empty((n, arch.CLS_H, arch.CLS_W, 3), dtype=torch.uint8, device=pages.device)
+        widths = torch.empty((n,), dtype=torch.int32, device=pages.device)
+        if n:
+            self._chk(self.lib.lumina_ocr_cls_crop(self._h, _ptr(pages), b, h, w, _ptr(quads), _ptr(page_idx), n, _ptr(crops),
+                                                   _ptr(widths), self._stream()))
+        return crops, widths
+
+    def cls_forward(self, crops, widths=None, thresh: float = arch.CLS_THRESH):
+        """cls_crop's crops uint8 [n, 48, 192, 3] device -> (label int32 [n]: 0 = "0", 1 = "180"; score float32 [n]: probability of the
+        label; flip int32 [n]: label == 1 and score > thresh, rec_crop's flip argument).  Asynchronous."""
+        torch = _torch()
+        n = crops.shape[0]
+        label = torch.empty((n,), dtype=torch.int32, device=crops.device)
+        score = torch.empty((n,), dtype=torch.float32, device=crops.device)
+        flip = torch.empty((n,), dtype=torch.int32, device=crops.device)
+        if n:
+            if crops.dtype != torch.uint8 or tuple(crops.shape[1:]) != (arch.CLS_H, arch.CLS_W, 3) or not crops.is_contiguous():
+                raise ValueError("crops must be contiguous uint8 [n, %d, %d, 3]" % (arch.CLS_H, arch.CLS_W))
+            self._chk(self.lib.lumina_ocr_cls_forward(self._h, _ptr(crops), _ptr(widths), n, float(thresh), _ptr(label), _ptr(score), _ptr(flip),
+                                                      self._stream()))
+        return label, score, flip
 
     def rec_forward(self, crops, widths=None):
         torch = _torch()

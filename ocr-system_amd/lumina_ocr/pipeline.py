@@ -27,6 +27,8 @@ class PageDetections:
     height: int = 0
     text_ids: Optional[np.ndarray] = None   # int32 [n, 80] class ids (-1 padded): what travels in the multi-GPU gather
     lens: Optional[np.ndarray] = None       # int32 [n]
+    cls_labels: Optional[np.ndarray] = None   # int32 [n] 0 / 1 (= "0" / "180"): OcrPipeline(angle_cls=True) only
+    cls_scores: Optional[np.ndarray] = None   # float32 [n] probability of the label
 
     def triples(self) -> List[Tuple[Sequence[int], str, float]]:
         return [(self.quads[i].tolist(), self.texts[i], float(self.scores[i])) for i in range(len(self.texts))]
@@ -48,8 +50,11 @@ class _Pending:
 
 class OcrPipeline:
     def __init__(self, engine: Engine, charset: Optional[List[str]] = None, max_dimension: int = 2000, post: Optional[dict] = None,
-                 recognizer: str = "crnn", gather=None):
+                 recognizer: str = "crnn", gather=None, angle_cls: bool = False, cls_thresh: float = arch.CLS_THRESH):
         """recognizer: "crnn" (CRNN-MobileNetV3 + BiLSTM, engine.load_rec) or "svtr" (SVTR, engine.load_svtr).
+        angle_cls: PaddleOCR's use_angle_cls — every line is classified 0 / 180 degrees (engine.load_cls) before recognition, and a line
+        read as 180 with probability > cls_thresh is recognised turned; boxes and reading order are unchanged.  Per-line labels are
+        not part of the multi-GPU gather.
         gather: a dist.PageGather — multi-GPU runs: every batch's results are all-gathered from the device tensors and
         finish() returns a GatheredPages over the pages of ALL ranks instead of this rank's PageDetections."""
         assert recognizer in ("crnn", "svtr")
@@ -61,6 +66,9 @@ class OcrPipeline:
         self._decoder = arch.TextDecoder(self.charset)   # class ids -> strings (vectorised for single-code-point dictionaries)
         self.max_dimension = max_dimension
         self.post = dict(arch.DEFAULT_POST if post is None else post)
+        self.angle_cls, self.cls_thresh = bool(angle_cls), float(cls_thresh)
+        if self.angle_cls and not engine.cls_loaded:
+            raise ValueError("angle_cls needs the orientation classifier's weights (Engine.load_cls)")
 
     # ---- stages -------------------------------------------------------------------------
     def preprocess(self, pages, enhance: bool = True, deskew: bool = False):
@@ -112,13 +120,18 @@ class OcrPipeline:
         quads = boxes.view(-1, 8).index_select(0, flat)
         det_sc = scores.view(-1).index_select(0, flat)
         page_idx = torch.from_numpy(page_h.astype(np.int32)).to(boxes.device, non_blocking=True)
-        crops, widths = self.eng.rec_crop(processed, quads, page_idx)
+        cls = None
+        if self.angle_cls:   # classifier crops -> labels and flip flags -> turned recognition crops, all on the device
+            ccrops, cwidths = self.eng.cls_crop(processed, quads, page_idx)
+            cls = self.eng.cls_forward(ccrops, cwidths, self.cls_thresh)
+        crops, widths = self.eng.rec_crop(processed, quads, page_idx, flip=None if cls is None else cls[2])
         idx, prob = (self.eng.svtr_forward if self.recognizer == "svtr" else self.eng.rec_forward)(crops, widths)
         text, length, score = self.eng.ctc_decode(idx, prob)
         if self.gather is not None:
             pend.gathered = self.gather.submit(counts_h, quads, det_sc, text, length, score)
             return pend
-        pend.host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in (text, length, score, quads, det_sc)]
+        outs = (text, length, score, quads, det_sc) + (() if cls is None else cls[:2])
+        pend.host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in outs]
         pend.event = torch.cuda.Event()
         pend.event.record(torch.cuda.current_stream(processed.device))
         return pend
@@ -131,14 +144,15 @@ class OcrPipeline:
         if pend.n == 0:
             return [PageDetections(np.zeros((0, 8), np.int32), [], np.zeros(0, np.float32), np.zeros(0, np.float32), w, h) for _ in range(b)], pend.processed
         pend.event.synchronize()
-        text_h, len_h, score_h, quads_h, det_h = (t.numpy() for t in pend.host)
+        text_h, len_h, score_h, quads_h, det_h, *cls_h = (t.numpy() for t in pend.host)
         all_texts = self._decoder.decode(text_h, len_h)
         out, off = [], 0
         for p in range(b):
             c = int(pend.counts_h[p])
             texts = all_texts[off:off + c]
             out.append(PageDetections(quads_h[off:off + c], texts, score_h[off:off + c], det_h[off:off + c], w, h,
-                                      text_h[off:off + c], len_h[off:off + c]))
+                                      text_h[off:off + c], len_h[off:off + c],
+                                      *((cls_h[0][off:off + c], cls_h[1][off:off + c]) if cls_h else ())))
             off += c
         return out, pend.processed
 

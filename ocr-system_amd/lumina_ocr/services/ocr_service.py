@@ -119,6 +119,10 @@ class OCRService:
         self._svtr_weights = os.environ.get("LUMINA_OCR_SVTR_WEIGHTS", "")
         self._rec_dict = os.environ.get("LUMINA_OCR_REC_DICT", "")               # dictionary file: one symbol per line (PP-OCR key-file format)
         self._allow_synthetic = os.environ.get("LUMINA_OCR_ALLOW_SYNTHETIC", "") == "1"
+        # PaddleOCR's use_angle_cls: lines read upside down (0/180-degree classifier, LOCW blob with the cls.* tensors) are recognised
+        # turned.  Off by default: every code path is then the one without the classifier.
+        self._use_angle_cls = os.environ.get("LUMINA_OCR_USE_ANGLE_CLS", "0").lower() not in ("", "0", "false", "no")
+        self._cls_weights = os.environ.get("LUMINA_OCR_CLS_WEIGHTS", "")
         self._weights_kind = "unloaded"
         self._pre = ImagePreprocessor(self.max_dimension)
         self._initialized = True
@@ -143,6 +147,9 @@ class OCRService:
                                           ("LUMINA_OCR_SVTR_WEIGHTS" if svtr else "LUMINA_OCR_REC_WEIGHTS", self._svtr_weights if svtr else self._rec_weights)) if not v]
                 raise RuntimeError("OCR weights not configured: set %s (LOCW blobs) and LUMINA_OCR_REC_DICT, or LUMINA_OCR_ALLOW_SYNTHETIC=1 "
                                    "for seeded synthetic networks" % " and ".join(missing))
+            if self._use_angle_cls and not self._cls_weights and not self._allow_synthetic:
+                raise RuntimeError("orientation classifier weights not configured: set LUMINA_OCR_CLS_WEIGHTS (LOCW blob) with "
+                                   "LUMINA_OCR_USE_ANGLE_CLS=1, or LUMINA_OCR_ALLOW_SYNTHETIC=1 for a seeded synthetic classifier")
             if have_files and not self._rec_dict:
                 raise RuntimeError("LUMINA_OCR_REC_DICT (the dictionary file the recogniser was trained with) is required with weight files")
             eng = Engine(self._device)  # raises EngineUnavailable without the HIP library / a GPU
@@ -165,11 +172,18 @@ class OCRService:
                         else:
                             eng.load_rec(arch.make_rec_weights(num_classes=len(charset), code_path=True))
                         kind, post = "seeded-synthetic", arch.TEXT_PATH_POST
+                    if self._use_angle_cls:
+                        if self._cls_weights:
+                            eng.load_cls(Path(self._cls_weights).read_bytes())
+                        else:
+                            logger.warning("OCR provider is running a SEEDED SYNTHETIC orientation classifier (LUMINA_OCR_ALLOW_SYNTHETIC=1)")
+                            eng.load_cls(arch.make_cls_weights(orientation_path=True))
                     n_cls = eng.svtr_num_classes if svtr else eng.num_classes
                     if len(charset) != n_cls:
                         raise RuntimeError("dictionary has %d classes (blank + symbols + space) but the %s head has %d"
                                            % (len(charset), "SVTR" if svtr else "CRNN", n_cls))
-                    pipeline = OcrPipeline(eng, charset=charset, max_dimension=self.max_dimension, post=post, recognizer=self._recognizer)
+                    pipeline = OcrPipeline(eng, charset=charset, max_dimension=self.max_dimension, post=post, recognizer=self._recognizer,
+                                           angle_cls=self._use_angle_cls)
             except Exception:
                 eng.close()
                 raise

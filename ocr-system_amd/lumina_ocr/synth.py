@@ -26,8 +26,9 @@ def random_text(rng: np.random.Generator, lo: int = 4, hi: int = 24) -> str:
     return s or "A"
 
 
-def synth_page(h: int, w: int, seed: int, n_lines: int = 60, noise: float = 3.0) -> Tuple[np.ndarray, List[dict]]:
+def synth_page(h: int, w: int, seed: int, n_lines: int = 60, noise: float = 3.0, ruled: bool = False) -> Tuple[np.ndarray, List[dict]]:
     """White page with rendered text lines (10-14 pt at 200 DPI ~ 28-39 px) + Gaussian noise.
+    ruled: every line is underlined by a rule size // 3 px thick, 2 px under its text, as on a filled-in form (same text otherwise).
     -> (uint8 [h,w,3], [{'text', 'box': (x0,y0,x1,y1)}])"""
     rng = np.random.default_rng(seed)
     img = Image.new("RGB", (w, h), (255, 255, 255))
@@ -53,6 +54,9 @@ def synth_page(h: int, w: int, seed: int, n_lines: int = 60, noise: float = 3.0)
         shade = int(rng.integers(0, 41))
         d.text((x, y), txt, fill=(shade, shade, shade), font=_font(size))
         bb = d.textbbox((x, y), txt, font=_font(size))
+        if ruled:
+            d.rectangle((bb[0], bb[3] + 2, bb[2], bb[3] + 1 + size // 3), fill=(shade, shade, shade))
+            bb = (bb[0], bb[1], bb[2], bb[3] + 1 + size // 3)
         gt.append(dict(text=txt, box=bb))
         y += max(pitch, size + 6)
     arr = np.asarray(img, np.float32)
