@@ -154,6 +154,20 @@ int lumina_ocr_deskew(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int heig
 int lumina_ocr_deskew_warp(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, const double* rot_dev, uint8_t* out_dev,
                            void* stream);
 
+/* Rules of ruled ("lattice") tables: the long thin ink lines of each page, the device half of the `table` / `table_cell` entries of
+ * the reference's result (ocr_service.py:324-352; the host half is lumina_ocr/utils/tables.py).  ink = L < threshold with L = PIL
+ * convert('L'); in every row the ink runs at most `gap` non-ink pixels apart merge and those at least min_len long are kept; kept
+ * runs of adjacent rows whose x-intervals overlap form components; a component with bounding box x0, y0, x1, y1 and area (the sum
+ * of its run lengths) is a horizontal rule when x1 - x0 + 1 >= min_len and area <= max_thick * (x1 - x0 + 1).  Vertical rules:
+ * the same with x and y exchanged.  pages_dev uint8 [n,H,W,3]; hrules_dev / vrules_dev int32 [n][max_rules][5] = x0, y0, x1, y1,
+ * area, sorted by (y0, x0, y1, x1) / (x0, y0, x1, y1), rows past the count untouched; counts_dev int32 [n][2] = the true numbers of
+ * horizontal and vertical rules (a list whose count exceeds max_rules is not written).  hmask_dev: optional parity hook (NULL to
+ * skip), the ink mask uint64 [n][H][ceil(W / 64)], bit x % 64 of word x / 64, bits past W zero.  max_rules <= 2048.  Integer
+ * arithmetic throughout: the result is defined bit for bit (tests/table_reference.py).  Asynchronous; n == 0 is a no-op. */
+int lumina_ocr_table_rules(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int gap, int min_len,
+                           int max_thick, int max_rules, int32_t* hrules_dev, int32_t* vrules_dev, int32_t* counts_dev, uint64_t* hmask_dev,
+                           void* stream);
+
 /* Second recogniser family (BASELINE configs[4]: "SVTR-base multilingual (Hindi dict), fp16 MFMA"): same slot and the same outputs as
  * lumina_ocr_load_rec_weights / lumina_ocr_rec_forward (the `rec` model of the engine call, ocr_service_paddleocr_backup.py:232-238,
  * :285), with an SVTR backbone (patch embedding, local / global mixing blocks, CTC head) instead of CRNN.  Blob: LOCW with the

@@ -13,6 +13,7 @@
 #include "jpegdec.h"
 #include "pngdec.h"
 #include "stem_conv.h"
+#include "tables.h"
 
 #define API_TRY try {
 #define API_CATCH(h)                                                             \
@@ -507,6 +508,34 @@ int lumina_ocr_deskew_warp(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int
     API_TRY
     if (deskew_tables(h)) return 1;
     return hip_rc(h, "deskew_warp", deskew_warp_launch(pages_dev, out_dev, rot_dev, h->dk_wtab, n, height, width, (hipStream_t)stream));
+    API_CATCH(h)
+}
+
+int lumina_ocr_table_rules(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int gap, int min_len, int max_thick,
+                           int max_rules, int32_t* hrules_dev, int32_t* vrules_dev, int32_t* counts_dev, uint64_t* hmask_dev, void* stream) {
+    if (!h) return 1;
+    if (n == 0) return 0;
+    if (!pages_dev || !hrules_dev || !vrules_dev || !counts_dev || n < 0) return locr_fail(h, "table_rules", "bad arguments");
+    if (table_workspace_bytes(1, height, width, gap, min_len, max_rules) == 0)
+        return locr_fail(h, "table_rules", "bad dimensions or parameters (sides 1..65535, gap >= 0, min_len >= 1, max_rules 1..2048)");
+    if (max_thick < 0) return locr_fail(h, "table_rules", "max_thick must be >= 0");
+    BIND(h);
+    API_TRY
+    // pages are processed in groups that bound the workspace (the run slots: ~40 bytes per (min_len + gap + 1) pixels, both directions)
+    int group = h->post_group < n ? h->post_group : n;
+    while (group > 1 && table_workspace_bytes(group, height, width, gap, min_len, max_rules) > ((size_t)1 << 30)) group = (group + 1) / 2;
+    const size_t nw = ((size_t)width + 63) / 64;
+    for (int b0 = 0; b0 < n; b0 += group) {
+        const int nb = n - b0 < group ? n - b0 : group;
+        if (eng_ws_reserve(h, table_workspace_bytes(nb, height, width, gap, min_len, max_rules))) return 1;
+        TableParams p{};
+        p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.H = height; p.W = width;
+        p.threshold = threshold; p.gap = gap; p.min_len = min_len; p.max_thick = max_thick; p.max_rules = max_rules;
+        p.hrules = hrules_dev + (size_t)b0 * max_rules * 5; p.vrules = vrules_dev + (size_t)b0 * max_rules * 5; p.counts = counts_dev + (size_t)b0 * 2;
+        p.hmask_out = hmask_dev ? reinterpret_cast<unsigned long long*>(hmask_dev) + (size_t)b0 * height * nw : nullptr;
+        if (hip_rc(h, "table_rules", table_rules_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream))) return 1;
+    }
+    return 0;
     API_CATCH(h)
 }
 

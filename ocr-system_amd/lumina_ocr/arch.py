@@ -447,6 +447,11 @@ CLS_STRIDES = (2, 2, 1, 2, 1, 1, 1, 1, 2, 1, 1)
 CLS_FEAT = 200
 CLS_THRESH = 0.9
 
+# Ruled tables (lumina_ocr_table_rules + utils/tables.py): ink = L < threshold; runs of a row / column at most `gap` apart merge and
+# count from min_len pixels on; a component of such runs is a rule when its area <= max_thick x its length; max_rules = capacity of a
+# page's list per direction; snap = the distance (pixels) within which rule ends, centre-lines and grid lines count as meeting.
+TABLE_PARAMS = dict(threshold=128, gap=2, min_len=64, max_thick=12, max_rules=512, snap=8)
+
 
 def cls_block_table() -> List[dict]:
     """rec_block_table at scale 0.35 with the classifier's strides; `h` = the block's output height on a 48-row crop."""

@@ -87,6 +87,7 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_denoise": (i32, [vp, vp, i32, i32, i32, vp, vp]),
         "lumina_ocr_deskew": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
         "lumina_ocr_deskew_warp": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+        "lumina_ocr_table_rules": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     }
     missing = []
     for name, (res, args) in sig.items():
@@ -111,6 +112,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_resize_lanczos", "lumina_ocr_enhance", "lumina_ocr_jpeg_encode", "lumina_ocr_jpeg_coefficients", "lumina_ocr_jpeg_probe", "lumina_ocr_jpeg_decode", "lumina_ocr_jpeg_decode_async", "lumina_ocr_jpeg_last_passes",
     "lumina_ocr_png_probe", "lumina_ocr_png_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
+    "lumina_ocr_table_rules",
 ]
 
 
@@ -470,6 +472,26 @@ class Engine:
         out = torch.empty_like(pages)
         self._chk(self.lib.lumina_ocr_deskew_warp(self._h, _ptr(pages), n, h, w, _ptr(rot), _ptr(out), self._stream()))
         return out
+
+    # -- ruled tables (the device half of the reference's `table` / `table_cell` entries, ocr_service.py:324-352) ----------------
+    def table_rules(self, pages, threshold=None, gap=None, min_len=None, max_thick=None, max_rules=None, debug: bool = False):
+        """uint8 [n,H,W,3] device -> (hrules int32 [n,max_rules,5], vrules int32 [n,max_rules,5], counts int32 [n,2]) on the device:
+        the long thin ink lines of each page as x0, y0, x1, y1, area, horizontal ones sorted by (y0, x0, y1, x1), vertical ones by
+        (x0, y0, x1, y1); counts = the true numbers (a list whose count exceeds max_rules is not written).  Parameters default to
+        arch.TABLE_PARAMS.  Asynchronous.  debug=True also returns the ink mask as int64 [n,H,ceil(W/64)] (the uint64 words' bits)."""
+        torch = _torch()
+        n, h, w, c = pages.shape
+        assert c == 3 and pages.dtype == torch.uint8 and pages.is_contiguous()
+        tp = arch.TABLE_PARAMS
+        threshold, gap, min_len = (tp[k] if v is None else int(v) for k, v in (("threshold", threshold), ("gap", gap), ("min_len", min_len)))
+        max_thick, max_rules = (tp[k] if v is None else int(v) for k, v in (("max_thick", max_thick), ("max_rules", max_rules)))
+        hrules = torch.zeros((n, max_rules, 5), dtype=torch.int32, device=pages.device)
+        vrules = torch.zeros((n, max_rules, 5), dtype=torch.int32, device=pages.device)
+        counts = torch.zeros((n, 2), dtype=torch.int32, device=pages.device)
+        mask = torch.zeros((n, h, (w + 63) // 64), dtype=torch.int64, device=pages.device) if debug else None
+        self._chk(self.lib.lumina_ocr_table_rules(self._h, _ptr(pages), n, h, w, threshold, gap, min_len, max_thick, max_rules, _ptr(hrules),
+                                                  _ptr(vrules), _ptr(counts), _ptr(mask), self._stream()))
+        return (hrules, vrules, counts, mask) if debug else (hrules, vrules, counts)
 
     @staticmethod
     def skew_degrees(rot) -> list:

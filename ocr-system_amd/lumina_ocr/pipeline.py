@@ -7,6 +7,7 @@ index-gather ops between stages; one host sync (box counts) separates det from r
 """
 from __future__ import annotations
 
+import logging
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
 
@@ -15,6 +16,8 @@ import numpy as np
 from . import arch
 from .engine import MAX_BOXES, Engine
 from .utils.image_preprocessing import get_optimal_size
+
+logger = logging.getLogger(__name__)
 
 
 @dataclass
@@ -29,6 +32,8 @@ class PageDetections:
     lens: Optional[np.ndarray] = None       # int32 [n]
     cls_labels: Optional[np.ndarray] = None   # int32 [n] 0 / 1 (= "0" / "180"): OcrPipeline(angle_cls=True) only
     cls_scores: Optional[np.ndarray] = None   # float32 [n] probability of the label
+    hrules: Optional[np.ndarray] = None       # int32 [nh, 5] x0, y0, x1, y1, area of the page's horizontal rules: OcrPipeline(tables=True) only
+    vrules: Optional[np.ndarray] = None       # int32 [nv, 5] vertical rules (both empty when a list overflowed its capacity)
 
     def triples(self) -> List[Tuple[Sequence[int], str, float]]:
         return [(self.quads[i].tolist(), self.texts[i], float(self.scores[i])) for i in range(len(self.texts))]
@@ -46,15 +51,19 @@ class _Pending:
     host: Optional[list] = None
     event: Optional[object] = None
     gathered: Optional[object] = None   # multi-GPU: handle of dist.PageGather.submit (the batch's results of ALL ranks)
+    rules_host: Optional[list] = None   # tables: pinned copies of hrules, vrules, counts
 
 
 class OcrPipeline:
     def __init__(self, engine: Engine, charset: Optional[List[str]] = None, max_dimension: int = 2000, post: Optional[dict] = None,
-                 recognizer: str = "crnn", gather=None, angle_cls: bool = False, cls_thresh: float = arch.CLS_THRESH):
+                 recognizer: str = "crnn", gather=None, angle_cls: bool = False, cls_thresh: float = arch.CLS_THRESH,
+                 tables: bool = False, table_params: Optional[dict] = None):
         """recognizer: "crnn" (CRNN-MobileNetV3 + BiLSTM, engine.load_rec) or "svtr" (SVTR, engine.load_svtr).
         angle_cls: PaddleOCR's use_angle_cls — every line is classified 0 / 180 degrees (engine.load_cls) before recognition, and a line
         read as 180 with probability > cls_thresh is recognised turned; boxes and reading order are unchanged.  Per-line labels are
         not part of the multi-GPU gather.
+        tables: the rules of ruled tables are extracted from the processed pages (engine.table_rules, parameters arch.TABLE_PARAMS or
+        table_params) and come back as PageDetections.hrules / vrules; like the per-line labels they stay on their rank.
         gather: a dist.PageGather — multi-GPU runs: every batch's results are all-gathered from the device tensors and
         finish() returns a GatheredPages over the pages of ALL ranks instead of this rank's PageDetections."""
         assert recognizer in ("crnn", "svtr")
@@ -67,6 +76,8 @@ class OcrPipeline:
         self.max_dimension = max_dimension
         self.post = dict(arch.DEFAULT_POST if post is None else post)
         self.angle_cls, self.cls_thresh = bool(angle_cls), float(cls_thresh)
+        self.tables = bool(tables)
+        self.table_params = dict(arch.TABLE_PARAMS if table_params is None else table_params)
         if self.angle_cls and not engine.cls_loaded:
             raise ValueError("angle_cls needs the orientation classifier's weights (Engine.load_cls)")
 
@@ -101,15 +112,24 @@ class OcrPipeline:
         """One host sync (box counts), then crop + CRNN + CTC and the device->pinned-host copies are enqueued. -> pending."""
         import torch
         b, h, w, _ = processed.shape
+        rules = None
+        if self.tables and self.gather is None:   # enqueued before the sync below: it runs while the host waits for the box counts
+            tp = self.table_params
+            rules = self.eng.table_rules(processed, tp["threshold"], tp["gap"], tp["min_len"], tp["max_thick"], tp["max_rules"])
         counts_h = counts.cpu().numpy()  # the one host sync of the pipeline
         n = int(counts_h.sum())
         pend = _Pending(b=b, w=w, h=h, counts_h=counts_h, n=n, processed=processed)
+        if rules is not None:
+            pend.rules_host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in rules]
         if self.gather is not None:
             self.gather.begin(counts_h)          # capacity all-reduce runs beside the recogniser
         if n == 0:
             if self.gather is not None:          # every rank takes part in the collective, with or without lines
                 e = lambda *shape, dt=torch.int32: torch.empty(shape, dtype=dt, device=boxes.device)
                 pend.gathered = self.gather.submit(counts_h, e(0, 8), e(0, dt=torch.float32), e(0, 80), e(0), e(0, dt=torch.float32))
+            elif pend.rules_host is not None:
+                pend.event = torch.cuda.Event()
+                pend.event.record(torch.cuda.current_stream(processed.device))
             return pend
         # the valid (page, slot) pairs are known on the host (counts): one small index upload + three gathers, instead of boolean-mask
         # indexing (each of those runs a nonzero kernel and synchronises to learn its output size)
@@ -141,9 +161,12 @@ class OcrPipeline:
         b, w, h = pend.b, pend.w, pend.h
         if pend.gathered is not None:
             return self.gather.finish(pend.gathered), pend.processed
+        if pend.event is not None:
+            pend.event.synchronize()
+        rules = self._page_rules(pend)
         if pend.n == 0:
-            return [PageDetections(np.zeros((0, 8), np.int32), [], np.zeros(0, np.float32), np.zeros(0, np.float32), w, h) for _ in range(b)], pend.processed
-        pend.event.synchronize()
+            return [PageDetections(np.zeros((0, 8), np.int32), [], np.zeros(0, np.float32), np.zeros(0, np.float32), w, h,
+                                   hrules=rules[p][0], vrules=rules[p][1]) for p in range(b)], pend.processed
         text_h, len_h, score_h, quads_h, det_h, *cls_h = (t.numpy() for t in pend.host)
         all_texts = self._decoder.decode(text_h, len_h)
         out, off = [], 0
@@ -152,9 +175,26 @@ class OcrPipeline:
             texts = all_texts[off:off + c]
             out.append(PageDetections(quads_h[off:off + c], texts, score_h[off:off + c], det_h[off:off + c], w, h,
                                       text_h[off:off + c], len_h[off:off + c],
-                                      *((cls_h[0][off:off + c], cls_h[1][off:off + c]) if cls_h else ())))
+                                      *((cls_h[0][off:off + c], cls_h[1][off:off + c]) if cls_h else ()),
+                                      hrules=rules[p][0], vrules=rules[p][1]))
             off += c
         return out, pend.processed
+
+    def _page_rules(self, pend: "_Pending"):
+        """-> per page (hrules [nh,5], vrules [nv,5]) from the pending batch's host copies, or (None, None) without tables.  A page whose
+        true count exceeds the capacity of a list has no guaranteed rules: it is treated as having none."""
+        if pend.rules_host is None:
+            return [(None, None)] * pend.b
+        hr, vr, cnt = (t.numpy() for t in pend.rules_host)
+        cap = hr.shape[1]
+        out = []
+        for p in range(pend.b):
+            nh, nv = int(cnt[p, 0]), int(cnt[p, 1])
+            if nh > cap or nv > cap:
+                logger.warning("page %d of the batch has %d horizontal / %d vertical rules, more than max_rules = %d: no tables are built for it", p, nh, nv, cap)
+                nh = nv = 0
+            out.append((hr[p, :nh].copy(), vr[p, :nv].copy()))
+        return out
 
     def run_many(self, batches, enhance: bool = True, deskew: bool = False):
         """Generator over batches: yields (detections, processed) per batch, in order, with batch k's host decode running

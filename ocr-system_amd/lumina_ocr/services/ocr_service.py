@@ -29,6 +29,7 @@ from PIL import Image
 
 from .. import arch
 from ..utils import layout
+from ..utils import tables as table_layout
 from ..utils.image_preprocessing import ImagePreprocessor, get_optimal_size
 
 logger = logging.getLogger(__name__)
@@ -123,6 +124,9 @@ class OCRService:
         # turned.  Off by default: every code path is then the one without the classifier.
         self._use_angle_cls = os.environ.get("LUMINA_OCR_USE_ANGLE_CLS", "0").lower() not in ("", "0", "false", "no")
         self._cls_weights = os.environ.get("LUMINA_OCR_CLS_WEIGHTS", "")
+        # LUMINA_OCR_TABLES=1: ruled tables become `table` / `table_cell` entries and <table> blocks of the Markdown (the reference gets them
+        # from Azure's layout model, :324-352).  Off by default: every output is then the one without them and tables_count stays 0.
+        self._use_tables = os.environ.get("LUMINA_OCR_TABLES", "0").lower() not in ("", "0", "false", "no")
         self._weights_kind = "unloaded"
         self._pre = ImagePreprocessor(self.max_dimension)
         self._initialized = True
@@ -183,7 +187,7 @@ class OCRService:
                         raise RuntimeError("dictionary has %d classes (blank + symbols + space) but the %s head has %d"
                                            % (len(charset), "SVTR" if svtr else "CRNN", n_cls))
                     pipeline = OcrPipeline(eng, charset=charset, max_dimension=self.max_dimension, post=post, recognizer=self._recognizer,
-                                           angle_cls=self._use_angle_cls)
+                                           angle_cls=self._use_angle_cls, tables=self._use_tables)
             except Exception:
                 eng.close()
                 raise
@@ -262,13 +266,18 @@ class OCRService:
 
     def _finish_page(self, det, jpeg: bytes, processed_hw, page_number: int, original_size, t0: float) -> OCROutput:
         merged, ordered = layout.reading_order(det.triples())
-        md = layout.page_markdown(merged)
+        tabs = []
+        if det.hrules is not None:   # LUMINA_OCR_TABLES=1; table_index counts from 0 here, _number_tables makes it run over a document
+            tabs = table_layout.find_tables(det.hrules, det.vrules, arch.TABLE_PARAMS["snap"])
+            table_layout.fill_cells(tabs, ordered)
+        md = layout.page_markdown(merged, tabs) if tabs else layout.page_markdown(merged)
         paragraphs = layout.build_paragraph_boxes(merged, page_number)
-        boxes = layout.build_layout_boxes(ordered, page_number) + paragraphs     # words, lines, ..., paragraphs: the order of ocr_service.py:285-367
+        # words, lines, tables with their cells, paragraphs: the order of ocr_service.py:285-367
+        boxes = layout.build_layout_boxes(ordered, page_number) + layout.build_table_boxes(tabs, page_number) + paragraphs
         ph, pw = processed_hw
         return OCROutput(markdown=md, html=layout.html_from_markdown(md),
                          json_output={"page_count": 1, "words_count": sum(1 for b in boxes if b["type"] == "word"),
-                                      "lines_count": len(ordered), "tables_count": 0, "paragraphs_count": len(paragraphs)},
+                                      "lines_count": len(ordered), "tables_count": len(tabs), "paragraphs_count": len(paragraphs)},
                          processing_time_ms=_ms_since(t0), success=True, page_number=page_number, image_width=original_size[0],
                          image_height=original_size[1], layout_boxes=boxes, processed_image_bytes=jpeg,
                          page_width_inches=float(pw), page_height_inches=float(ph))
@@ -487,7 +496,20 @@ class OCRService:
                     for i in idxs:
                         out[i] = OCROutput(success=False, error=str(e), processing_time_ms=_ms_since(t0),
                                            page_number=first_page_number + i, image_width=images[i].size[0], image_height=images[i].size[1])
+        self._number_tables(out)
         return out  # type: ignore[return-value]
+
+    @staticmethod
+    def _number_tables(pages) -> None:
+        """table_index runs over the document's tables in page order, as the index of Azure's result.tables does (:326)."""
+        seen = 0
+        for p in pages:
+            if p is None or not p.success:
+                continue
+            for b in p.layout_boxes:
+                if b["type"] == "table":
+                    b["table_index"] += seen
+            seen += int((p.json_output or {}).get("tables_count", 0))
 
     def _document_from_pages(self, pages: List[OCROutput], t0: float) -> DocumentOCRResult:
         ok = all(p.success for p in pages)

@@ -102,3 +102,76 @@ def synth_form_page(seed: int = 0, w: int = 2000, h: int = 1090) -> Tuple[np.nda
         put(620, y, v, 32)
         y += 88
     return np.asarray(img, np.uint8).copy(), gt
+
+
+def synth_table_page(seed: int, h: int = 1100, w: int = 1500, n_tables: int = 1, thickness: int = 0, inset: int = 14, spans: bool = False,
+                     noise: float = 0.0, rows: int = 0, cols: int = 0, size: int = 0) -> Tuple[np.ndarray, List[dict]]:
+    """White page with n_tables ruled tables under a title line, one text per cell.
+    thickness: rule thickness in pixels (0: drawn from the seed, 2-5); inset: clear distance between a rule and the text box of its
+    cell; spans: the first row is one header cell across all columns and, with three or more rows, the first column's cells of rows 1
+    and 2 are one cell; rows / cols / size: grid and font size (0: from the seed, 2-5 x 2-4, 26-34 px scaled like synth_page).
+    -> (uint8 [h,w,3], [dict(xs, ys, thickness, row_count, column_count, cells=[dict(row_index, column_index, row_span, column_span,
+    text, box)])]): xs / ys are the centre-lines of the drawn rules, (first + last pixel) // 2; cells in row-major order."""
+    rng = np.random.default_rng(seed)
+    img = Image.new("RGB", (w, h), (255, 255, 255))
+    d = ImageDraw.Draw(img)
+    scale = min(1.0, h / 2339.0 * 1.6 + 0.2)
+    margin = max(8, int(0.06 * w))
+    y = max(8, int(0.04 * h))
+    tsize = max(10, int(30 * scale))
+    d.text((margin, y), "Table %d" % seed, fill=(20, 20, 20), font=_font(tsize))
+    y += tsize + 3 * inset
+    gt = []
+    for _ in range(n_tables):
+        t = int(thickness) if thickness else int(rng.integers(2, 6))
+        nr = int(rows) if rows else int(rng.integers(2, 6))
+        nc = int(cols) if cols else int(rng.integers(2, 5))
+        fs = int(size) if size else max(10, int(rng.integers(26, 35) * scale))
+        row_h = max(72, fs + 2 * inset + t + 10)
+        left = margin + int(rng.integers(0, max(1, w // 12)))
+        right = w - margin - int(rng.integers(0, max(1, w // 12)))
+        col_w = (right - left - t) // nc
+        if y + nr * row_h + t >= h - 4 or col_w < 2 * inset + t + 3 * fs:
+            break
+        x0 = [left + c * col_w for c in range(nc + 1)]       # first pixel of every vertical rule
+        y0 = [y + r * row_h for r in range(nr + 1)]          # first pixel of every horizontal rule
+        group = {(r, c): (r, c) for r in range(nr) for c in range(nc)}   # cell -> top-left cell of its group
+        span = {(r, c): (1, 1) for r in range(nr) for c in range(nc)}
+        if spans:
+            for c in range(nc):
+                group[(0, c)] = (0, 0)
+            span[(0, 0)] = (1, nc)
+            if nr >= 3:
+                group[(2, 0)] = (1, 0)
+                span[(1, 0)] = (2, 1)
+        shade = int(rng.integers(0, 41))
+        ink = (shade, shade, shade)
+        for k in range(nr + 1):
+            for c in range(nc):
+                if k in (0, nr) or group[(k - 1, c)] != group[(k, c)]:
+                    d.rectangle((x0[c], y0[k], x0[c + 1] + t - 1, y0[k] + t - 1), fill=ink)
+        for k in range(nc + 1):
+            for r in range(nr):
+                if k in (0, nc) or group[(r, k - 1)] != group[(r, k)]:
+                    d.rectangle((x0[k], y0[r], x0[k] + t - 1, y0[r + 1] + t - 1), fill=ink)
+        cells = []
+        for r in range(nr):
+            for c in range(nc):
+                if group[(r, c)] != (r, c):
+                    continue
+                rs, cs = span[(r, c)]
+                tx, ty = x0[c] + t + inset, y0[r] + t + inset
+                room = x0[c + cs] - inset - tx
+                txt = random_text(rng, 4, 9).replace(" ", "x")
+                while len(txt) > 1 and d.textbbox((tx, ty), txt, font=_font(fs))[2] - tx > room:
+                    txt = txt[:-1]
+                tshade = int(rng.integers(0, 41))
+                d.text((tx, ty), txt, fill=(tshade, tshade, tshade), font=_font(fs))
+                cells.append(dict(row_index=r, column_index=c, row_span=rs, column_span=cs, text=txt, box=d.textbbox((tx, ty), txt, font=_font(fs))))
+        gt.append(dict(xs=[(2 * v + t - 1) // 2 for v in x0], ys=[(2 * v + t - 1) // 2 for v in y0], thickness=t, row_count=nr, column_count=nc,
+                       cells=cells))
+        y = y0[-1] + t + 4 * inset + tsize
+    arr = np.asarray(img, np.float32)
+    if noise > 0:
+        arr = arr + rng.normal(0.0, noise, arr.shape).astype(np.float32)
+    return np.clip(np.rint(arr), 0, 255).astype(np.uint8), gt

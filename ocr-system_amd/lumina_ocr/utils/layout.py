@@ -10,8 +10,10 @@ A det+rec engine yields line quads; `line` entries are mandatory for matching
 """
 from __future__ import annotations
 
-from typing import Any, Dict, List, Sequence, Tuple
+import html
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
+from . import tables as _tables
 from .ocr_postprocessor import MergedLine, TextBlock, group_into_lines, sort_and_merge_lines
 
 
@@ -95,10 +97,74 @@ def reading_order(dets: Sequence[Tuple[Sequence[int], str, float]]) -> Tuple[Lis
     return merged, ordered
 
 
-def page_markdown(merged: Sequence[MergedLine]) -> str:
+def build_table_boxes(tables: Sequence[Dict[str, Any]], page_number: int = 1, first_table_index: int = 0) -> List[Dict[str, Any]]:
+    """`table` and `table_cell` entries with the reference's keys (backend/services/ocr_service.py:324-352): every table
+    (utils/tables.find_tables, cells filled by fill_cells) is followed by its cells in row-major order.  table_index counts from
+    first_table_index (the document's tables so far: Azure's index runs over result.tables).  row_span / column_span are Azure's
+    DocumentTableCell fields; they are added only when they exceed 1."""
+    out: List[Dict[str, Any]] = []
+    for k, t in enumerate(tables):
+        out.append({"type": "table", "table_index": first_table_index + k, "row_count": int(t["row_count"]),
+                    "column_count": int(t["column_count"]), "polygon": [float(v) for v in t["polygon"]], "page_number": page_number})
+        for c in t["cells"]:
+            cell = {"type": "table_cell", "content": c["content"], "row_index": int(c["row_index"]), "column_index": int(c["column_index"]),
+                    "polygon": [float(v) for v in c["polygon"]], "page_number": page_number}
+            if c.get("row_span", 1) > 1:
+                cell["row_span"] = int(c["row_span"])
+            if c.get("column_span", 1) > 1:
+                cell["column_span"] = int(c["column_span"])
+            out.append(cell)
+    return out
+
+
+def table_markdown(table: Dict[str, Any]) -> str:
+    """A table the way Azure's Markdown content carries one: a <table> block, one <tr> per line, rowspan / colspan where they exceed 1,
+    text HTML-escaped."""
+    rows = ["<table>"]
+    for r in range(table["row_count"]):
+        tds = []
+        for c in sorted((c for c in table["cells"] if c["row_index"] == r), key=lambda c: c["column_index"]):
+            attr = (' rowspan="%d"' % c["row_span"] if c.get("row_span", 1) > 1 else "") + \
+                   (' colspan="%d"' % c["column_span"] if c.get("column_span", 1) > 1 else "")
+            tds.append("<td%s>%s</td>" % (attr, html.escape(c["content"], quote=False)))
+        rows.append("<tr>%s</tr>" % "".join(tds))
+    rows.append("</table>")
+    return "\n".join(rows)
+
+
+def page_markdown(merged: Sequence[MergedLine], tables: Optional[Sequence[Dict[str, Any]]] = None) -> str:
     """combined_markdown is fed verbatim to the LLM step and must be non-blank for a non-empty page
-    (/root/reference/backend/services/extraction_service.py:290-295, :658-662): one reading-order line per row."""
-    return "\n".join(m.text for m in merged if m.text)
+    (/root/reference/backend/services/extraction_service.py:290-295, :658-662): one reading-order line per row.
+    tables (utils/tables.find_tables + fill_cells): every table is written as its <table> block at the position of its first contained
+    line, and the lines inside it (quad centre in a cell) leave the plain flow; what is left of a row that crosses a table stays a row
+    of its own.  Lines outside tables are unchanged."""
+    if not tables:
+        return "\n".join(m.text for m in merged if m.text)
+    rows: List[str] = []
+    written = set()
+    for m in merged:
+        plain: List[str] = []
+        inside = False
+        for b in m.blocks:
+            x, y = _tables.quad_centre([v for pt in b.box for v in pt])
+            ti = next((i for i, t in enumerate(tables) if _tables.cell_at(t, x, y) is not None), -1)
+            if ti < 0:
+                plain.append(b.text)
+                continue
+            inside = True
+            if ti not in written:
+                if plain:
+                    rows.append(" ".join(plain))
+                    plain = []
+                written.add(ti)
+                rows.append(table_markdown(tables[ti]))
+        if not inside:
+            if m.text:
+                rows.append(m.text)
+        elif plain:
+            rows.append(" ".join(plain))
+    rows.extend(table_markdown(t) for i, t in enumerate(tables) if i not in written)   # a table without a line: after the text
+    return "\n".join(rows)
 
 
 def html_from_markdown(markdown_text: str) -> str:
@@ -135,6 +201,19 @@ def validate_layout_boxes(boxes: Sequence[Dict[str, Any]]) -> List[str]:
             problems.append(f"{i}: content must be str")
         if b.get("type") == "word" and not isinstance(b.get("confidence"), float):
             problems.append(f"{i}: word confidence must be float")
+        if b.get("type") == "table":
+            for k in ("table_index", "row_count", "column_count"):
+                if not isinstance(b.get(k), int) or isinstance(b.get(k), bool) or b[k] < (0 if k == "table_index" else 1):
+                    problems.append(f"{i}: table {k} must be int >= {0 if k == 'table_index' else 1}")
+        if b.get("type") == "table_cell":
+            if not isinstance(b.get("content"), str):
+                problems.append(f"{i}: table_cell content must be str")
+            for k in ("row_index", "column_index"):
+                if not isinstance(b.get(k), int) or isinstance(b.get(k), bool) or b[k] < 0:
+                    problems.append(f"{i}: table_cell {k} must be int >= 0")
+            for k in ("row_span", "column_span"):
+                if k in b and (not isinstance(b[k], int) or isinstance(b[k], bool) or b[k] < 2):
+                    problems.append(f"{i}: table_cell {k}, when present, must be int >= 2")
         if b.get("type") == "paragraph" and not (isinstance(b.get("content"), str) and len(b["content"]) <= 103 and isinstance(b.get("role"), str)):
             problems.append(f"{i}: paragraph needs content (<= 100 characters + '...') and role")
     return problems

@@ -3,7 +3,8 @@
 (/root/reference/debug_azure_output.py:93-111 -> azure_debug_output.json): success, total_pages, combined_layout_boxes_count,
 combined_layout_boxes_sample[:10], pages[{page_number, layout_boxes_count, has_processed_image, page_width_inches,
 page_height_inches}].  Usage: python tools/dump_ocr.py path/to/page.png [out.json]   (needs the GPU; without trained weights
-set LUMINA_OCR_ALLOW_SYNTHETIC=1)."""
+set LUMINA_OCR_ALLOW_SYNTHETIC=1; LUMINA_OCR_TABLES=1 adds the `table` / `table_cell` entries of ruled tables, which the layout box counts
+then include)."""
 import asyncio
 import json
 import sys
@@ -38,7 +39,8 @@ async def main(path: str, out: str) -> int:
         print("OCR failed: %s" % result.error, file=sys.stderr)
         return 1
     Path(out).write_text(json.dumps(dump_dict(result), indent=2, ensure_ascii=False))
-    print("pages %d, layout boxes %d, %d ms -> %s" % (result.total_pages, len(result.combined_layout_boxes), result.total_processing_time_ms, out))
+    tables = sum(1 for b in result.combined_layout_boxes if b.get("type") == "table")
+    print("pages %d, layout boxes %d (tables %d), %d ms -> %s" % (result.total_pages, len(result.combined_layout_boxes), tables, result.total_processing_time_ms, out))
     return 0
 
 
