@@ -168,6 +168,28 @@ int lumina_ocr_table_rules(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int
                            int max_thick, int max_rules, int32_t* hrules_dev, int32_t* vrules_dev, int32_t* counts_dev, uint64_t* hmask_dev,
                            void* stream);
 
+/* Selection marks (checkboxes): the device half of the `selection_mark` entries of the reference's result (ocr_service.py:313-322;
+ * the host half is lumina_ocr/utils/marks.py).  ink as in lumina_ocr_table_rules.  The 8-connected components of the ink with a
+ * bounding box x0, y0, x1, y1 (inclusive; w, h its sides) are candidates when min_side <= w, h <= max_side and
+ * 4 |w - h| <= min(w, h).  Frame test on the page's ink inside the box, t = 1 + min(w, h) / 8: top / bottom = the columns of the box
+ * with ink in its first / last t rows, left / right = the rows with ink in its first / last t columns; a mark has top, bottom >=
+ * w - w / 8 and left, right >= h - h / 8.  ink_in = the ink pixels of columns x0 + w / 4 .. x1 - w / 4, rows y0 + h / 4 .. y1 - h / 4,
+ * area_in = the size of that interior, state = 1 (selected) when 16 ink_in >= area_in.  pages_dev uint8 [n,H,W,3]; marks_dev int32
+ * [n][max_marks][8] = x0, y0, x1, y1, top + bottom + left + right, ink_in, area_in, state, sorted by (y0, x0, y1, x1, first run of the
+ * component in raster order), rows past the count untouched; counts_dev int32 [n] = the true number of marks (a list whose count
+ * exceeds max_marks is not written).  mask_dev: optional parity hook (NULL to skip), the ink mask as hmask_dev of
+ * lumina_ocr_table_rules.  4 <= min_side <= max_side <= 64 (a box's window is one 64-bit word per row), max_marks <= 2048, sides
+ * 1..65535.  Integer arithmetic throughout: the result is defined bit for bit (tests/mark_reference.py).  Asynchronous; n == 0 is a
+ * no-op; bad arguments return a status before anything is written. */
+int lumina_ocr_selection_marks(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_side,
+                               int max_side, int max_marks, int32_t* marks_dev, int32_t* counts_dev, uint64_t* mask_dev, void* stream);
+
+/* lumina_ocr_table_rules and lumina_ocr_selection_marks on the same pages with one threshold: the ink mask is computed once and both
+ * read it.  Every output equals that of the two calls made one after the other. */
+int lumina_ocr_rules_and_marks(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int gap, int min_len,
+                               int max_thick, int max_rules, int32_t* hrules_dev, int32_t* vrules_dev, int32_t* rule_counts_dev, int min_side,
+                               int max_side, int max_marks, int32_t* marks_dev, int32_t* mark_counts_dev, void* stream);
+
 /* Second recogniser family (BASELINE configs[4]: "SVTR-base multilingual (Hindi dict), fp16 MFMA"): same slot and the same outputs as
  * lumina_ocr_load_rec_weights / lumina_ocr_rec_forward (the `rec` model of the engine call, ocr_service_paddleocr_backup.py:232-238,
  * :285), with an SVTR backbone (patch embedding, local / global mixing blocks, CTC head) instead of CRNN.  Blob: LOCW with the

@@ -7,6 +7,7 @@
 #include "dbpost.h"
 #include "deskew.h"
 #include "engine.h"
+#include "marks.h"
 #include "ops.h"
 #include "resize.h"
 #include "jpeg.h"
@@ -534,6 +535,87 @@ int lumina_ocr_table_rules(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int
         p.hrules = hrules_dev + (size_t)b0 * max_rules * 5; p.vrules = vrules_dev + (size_t)b0 * max_rules * 5; p.counts = counts_dev + (size_t)b0 * 2;
         p.hmask_out = hmask_dev ? reinterpret_cast<unsigned long long*>(hmask_dev) + (size_t)b0 * height * nw : nullptr;
         if (hip_rc(h, "table_rules", table_rules_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream))) return 1;
+    }
+    return 0;
+    API_CATCH(h)
+}
+
+// what is wrong with a selection_marks argument set, or null
+static const char* marks_bad_args(int height, int width, int min_side, int max_side, int max_marks) {
+    if (min_side < MARK_MIN_SIDE || max_side > MARK_MAX_SIDE || max_side < min_side) return "sides must satisfy 4 <= min_side <= max_side <= 64";
+    if (marks_workspace_bytes(1, height, width, max_marks) == 0) return "bad dimensions or parameters (sides 1..65535, max_marks 1..2048)";
+    return nullptr;
+}
+// pages per launch: the run list is sized for its worst case (24 bytes per two pixels), so the group is halved until it fits 1 GiB
+static int marks_group(const lumina_ocr* h, int n, int height, int width, int max_marks) {
+    int group = h->post_group < n ? h->post_group : n;
+    while (group > 1 && marks_workspace_bytes(group, height, width, max_marks) > ((size_t)1 << 30)) group = (group + 1) / 2;
+    return group;
+}
+
+int lumina_ocr_selection_marks(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_side, int max_side,
+                               int max_marks, int32_t* marks_dev, int32_t* counts_dev, uint64_t* mask_dev, void* stream) {
+    if (!h) return 1;
+    if (n == 0) return 0;
+    if (!pages_dev || !marks_dev || !counts_dev || n < 0) return locr_fail(h, "selection_marks", "bad arguments");
+    if (const char* why = marks_bad_args(height, width, min_side, max_side, max_marks)) return locr_fail(h, "selection_marks", why);
+    BIND(h);
+    API_TRY
+    const int group = marks_group(h, n, height, width, max_marks);
+    const size_t nw = ((size_t)width + 63) / 64;
+    for (int b0 = 0; b0 < n; b0 += group) {
+        const int nb = n - b0 < group ? n - b0 : group;
+        if (eng_ws_reserve(h, marks_workspace_bytes(nb, height, width, max_marks))) return 1;
+        MarkParams p{};
+        p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.H = height; p.W = width;
+        p.threshold = threshold; p.min_side = min_side; p.max_side = max_side; p.max_marks = max_marks;
+        p.marks = marks_dev + (size_t)b0 * max_marks * 8; p.counts = counts_dev + b0;
+        p.mask_out = mask_dev ? reinterpret_cast<unsigned long long*>(mask_dev) + (size_t)b0 * height * nw : nullptr;
+        if (hip_rc(h, "selection_marks", marks_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream))) return 1;
+    }
+    return 0;
+    API_CATCH(h)
+}
+
+int lumina_ocr_rules_and_marks(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int gap, int min_len,
+                               int max_thick, int max_rules, int32_t* hrules_dev, int32_t* vrules_dev, int32_t* rule_counts_dev, int min_side,
+                               int max_side, int max_marks, int32_t* marks_dev, int32_t* mark_counts_dev, void* stream) {
+    if (!h) return 1;
+    if (n == 0) return 0;
+    if (!pages_dev || !hrules_dev || !vrules_dev || !rule_counts_dev || !marks_dev || !mark_counts_dev || n < 0) return locr_fail(h, "rules_and_marks", "bad arguments");
+    if (table_workspace_bytes(1, height, width, gap, min_len, max_rules) == 0 || max_thick < 0)
+        return locr_fail(h, "rules_and_marks", "bad dimensions or table parameters (sides 1..65535, gap >= 0, min_len >= 1, max_thick >= 0, max_rules 1..2048)");
+    if (const char* why = marks_bad_args(height, width, min_side, max_side, max_marks)) return locr_fail(h, "rules_and_marks", why);
+    BIND(h);
+    API_TRY
+    // one group size for both; the workspace is the group's mask, then room for the larger of the two passes (they run one after the
+    // other on the stream)
+    int group = marks_group(h, n, height, width, max_marks);
+    while (group > 1 && table_workspace_bytes(group, height, width, gap, min_len, max_rules) > ((size_t)1 << 30)) group = (group + 1) / 2;
+    const size_t nw = ((size_t)width + 63) / 64;
+    hipStream_t st = (hipStream_t)stream;
+    for (int b0 = 0; b0 < n; b0 += group) {
+        const int nb = n - b0 < group ? n - b0 : group;
+        const size_t wt = table_workspace_bytes(nb, height, width, gap, min_len, max_rules), wm = marks_workspace_bytes(nb, height, width, max_marks);
+        Arena sizes;
+        sizes.take<unsigned long long>((size_t)nb * height * nw);
+        sizes.take<uint8_t>(wt > wm ? wt : wm);
+        if (eng_ws_reserve(h, sizes.off)) return 1;
+        Arena a(h->ws.get(), h->ws.cap);
+        unsigned long long* mask = a.take<unsigned long long>((size_t)nb * height * nw);
+        uint8_t* rest = a.take<uint8_t>(wt > wm ? wt : wm);
+        if (a.overflow) return locr_fail(h, "rules_and_marks", "workspace");
+        const uint8_t* rgb = pages_dev + (size_t)b0 * height * width * 3;
+        if (hip_rc(h, "rules_and_marks", table_mask_launch(rgb, mask, nb, height, width, threshold, st))) return 1;
+        TableParams t{};
+        t.rgb = rgb; t.B = nb; t.H = height; t.W = width; t.threshold = threshold; t.gap = gap; t.min_len = min_len; t.max_thick = max_thick;
+        t.max_rules = max_rules; t.hrules = hrules_dev + (size_t)b0 * max_rules * 5; t.vrules = vrules_dev + (size_t)b0 * max_rules * 5;
+        t.counts = rule_counts_dev + (size_t)b0 * 2; t.hmask_in = mask;
+        if (hip_rc(h, "rules_and_marks", table_rules_launch(t, rest, wt > wm ? wt : wm, st))) return 1;
+        MarkParams p{};
+        p.rgb = rgb; p.B = nb; p.H = height; p.W = width; p.threshold = threshold; p.min_side = min_side; p.max_side = max_side; p.max_marks = max_marks;
+        p.marks = marks_dev + (size_t)b0 * max_marks * 8; p.counts = mark_counts_dev + b0; p.mask_in = mask;
+        if (hip_rc(h, "rules_and_marks", marks_launch(p, rest, wt > wm ? wt : wm, st))) return 1;
     }
     return 0;
     API_CATCH(h)

@@ -1,0 +1,23 @@
+#pragma once
+#include "common.h"
+
+// Selection marks (checkboxes) of a batch of pages, on the device (marks.hip; definition restated in tests/mark_reference.py).
+// Integer arithmetic throughout: the result does not depend on the order anything runs in.
+struct MarkParams {
+    const uint8_t* rgb;   // [B][H][W][3]
+    int B, H, W;
+    int threshold;        // ink = L < threshold, L = Pillow's convert('L')
+    int min_side;         // a candidate's bounding box has min_side <= w, h <= max_side (and 4 |w - h| <= min(w, h))
+    int max_side;         // <= MARK_MAX_SIDE: a candidate's window is one 64-bit word per row, one lane per row
+    int max_marks;        // capacity of a page's list (<= MARK_MAX_MARKS)
+    int* marks;           // device, [B][max_marks][8] = x0, y0, x1, y1, edge, ink_in, area_in, state; sorted by (y0, x0, y1, x1, root)
+    int* counts;          // device, [B]: true number of marks (a list is not written when it overflows)
+    unsigned long long* mask_out;        // optional parity hook: ink mask [B][H][ceil(W / 64)], bit x % 64 of word x / 64
+    const unsigned long long* mask_in;   // optional: the ink mask of these pages at this threshold, already computed (table_mask_launch)
+};
+constexpr int MARK_MAX_SIDE = 64;
+constexpr int MARK_MIN_SIDE = 4;
+constexpr int MARK_MAX_MARKS = 2048;
+
+size_t marks_workspace_bytes(int B, int H, int W, int max_marks);
+hipError_t marks_launch(const MarkParams& p, void* workspace, size_t ws_bytes, hipStream_t st);

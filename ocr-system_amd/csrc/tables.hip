@@ -267,6 +267,13 @@ size_t table_workspace_bytes(int B, int H, int W, int gap, int min_len, int max_
     return a.off;
 }
 
+hipError_t table_mask_launch(const uint8_t* rgb, unsigned long long* mask, int B, int H, int W, int threshold, hipStream_t st) {
+    if (!rgb || !mask || B <= 0 || H <= 0 || W <= 0 || (size_t)B * H >= (1ull << 31)) return hipErrorInvalidValue;
+    const long long rows = (long long)B * H;
+    hipLaunchKernelGGL(tb_mask_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, rgb, mask, W, (W + 63) / 64, threshold, rows);
+    return hipGetLastError();
+}
+
 hipError_t table_rules_launch(const TableParams& p, void* workspace, size_t ws_bytes, hipStream_t st) {
     const int B = p.B, H = p.H, W = p.W;
     if (!table_args_ok(B, H, W, p.gap, p.min_len, p.max_rules) || p.max_thick < 0 || !p.rgb || !p.hrules || !p.vrules || !p.counts) return hipErrorInvalidValue;
@@ -274,12 +281,15 @@ hipError_t table_rules_launch(const TableParams& p, void* workspace, size_t ws_b
     const TableWorkspace w = table_layout(a, B, H, W, p.gap, p.min_len, p.max_rules);
     if (a.overflow) return hipErrorOutOfMemory;
     const int nw = (W + 63) / 64, nhw = (H + 63) / 64;
-    unsigned long long* hmask = p.hmask_out ? p.hmask_out : w.hmask;
+    // the mask: given (hmask_in; copied to the parity hook when that is asked for too), or computed here
+    const unsigned long long* hmask = p.hmask_in ? p.hmask_in : (p.hmask_out ? p.hmask_out : w.hmask);
 
     hipError_t e = hipMemsetAsync(p.counts, 0, sizeof(int) * 2 * (size_t)B, st);
     if (e != hipSuccess) return e;
-    const long long rows = (long long)B * H, blocks = (long long)B * nw * nhw;
-    hipLaunchKernelGGL(tb_mask_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, p.rgb, hmask, W, nw, p.threshold, rows);
+    const long long blocks = (long long)B * nw * nhw;
+    if (!p.hmask_in) e = table_mask_launch(p.rgb, p.hmask_out ? p.hmask_out : w.hmask, B, H, W, p.threshold, st);
+    else if (p.hmask_out) e = hipMemcpyAsync(p.hmask_out, p.hmask_in, sizeof(unsigned long long) * (size_t)B * H * nw, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(tb_transpose_kernel, dim3((unsigned)((blocks + 3) / 4)), dim3(256), 0, st, hmask, w.vmask, H, W, nw, nhw, blocks);
     TDirs D;
     D.B = B;

@@ -452,6 +452,12 @@ CLS_THRESH = 0.9
 # page's list per direction; snap = the distance (pixels) within which rule ends, centre-lines and grid lines count as meeting.
 TABLE_PARAMS = dict(threshold=128, gap=2, min_len=64, max_thick=12, max_rules=512, snap=8)
 
+# Selection marks (lumina_ocr_selection_marks + utils/marks.py): ink as above; a connected component of the ink is a candidate when its
+# bounding box has min_side <= w, h <= max_side and is nearly square; a candidate whose box carries ink along all four sides is a mark,
+# selected when a sixteenth of its interior is ink.  max_side <= 64 is part of the contract (one 64-bit word and one wave64 lane per
+# row of a box); max_marks = capacity of a page's list.
+MARK_PARAMS = dict(threshold=128, min_side=12, max_side=64, max_marks=256)
+
 
 def cls_block_table() -> List[dict]:
     """rec_block_table at scale 0.35 with the classifier's strides; `h` = the block's output height on a 48-row crop."""

@@ -88,6 +88,8 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_deskew": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
         "lumina_ocr_deskew_warp": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_table_rules": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+        "lumina_ocr_selection_marks": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+        "lumina_ocr_rules_and_marks": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     }
     missing = []
     for name, (res, args) in sig.items():
@@ -112,7 +114,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_resize_lanczos", "lumina_ocr_enhance", "lumina_ocr_jpeg_encode", "lumina_ocr_jpeg_coefficients", "lumina_ocr_jpeg_probe", "lumina_ocr_jpeg_decode", "lumina_ocr_jpeg_decode_async", "lumina_ocr_jpeg_last_passes",
     "lumina_ocr_png_probe", "lumina_ocr_png_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
-    "lumina_ocr_table_rules",
+    "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks",
 ]
 
 
@@ -492,6 +494,50 @@ class Engine:
         self._chk(self.lib.lumina_ocr_table_rules(self._h, _ptr(pages), n, h, w, threshold, gap, min_len, max_thick, max_rules, _ptr(hrules),
                                                   _ptr(vrules), _ptr(counts), _ptr(mask), self._stream()))
         return (hrules, vrules, counts, mask) if debug else (hrules, vrules, counts)
+
+    # -- selection marks (the device half of the reference's `selection_mark` entries, ocr_service.py:313-322) -------------------
+    @staticmethod
+    def _mark_params(min_side, max_side, max_marks):
+        mp = arch.MARK_PARAMS
+        return tuple(mp[k] if v is None else int(v) for k, v in (("min_side", min_side), ("max_side", max_side), ("max_marks", max_marks)))
+
+    def selection_marks(self, pages, threshold=None, min_side=None, max_side=None, max_marks=None, debug: bool = False):
+        """uint8 [n,H,W,3] device -> (marks int32 [n,max_marks,8], counts int32 [n]) on the device: the checkboxes of each page as
+        x0, y0, x1, y1, edge, ink_in, area_in, state (1 = selected), sorted by (y0, x0, y1, x1); counts = the true numbers (a list
+        whose count exceeds max_marks is not written).  Parameters default to arch.MARK_PARAMS.  Asynchronous.  debug=True also
+        returns the ink mask as int64 [n,H,ceil(W/64)] (the uint64 words' bits)."""
+        torch = _torch()
+        n, h, w, c = pages.shape
+        assert c == 3 and pages.dtype == torch.uint8 and pages.is_contiguous()
+        threshold = arch.MARK_PARAMS["threshold"] if threshold is None else int(threshold)
+        min_side, max_side, max_marks = self._mark_params(min_side, max_side, max_marks)
+        marks = torch.zeros((n, max(max_marks, 0), 8), dtype=torch.int32, device=pages.device)
+        counts = torch.zeros((n,), dtype=torch.int32, device=pages.device)
+        mask = torch.zeros((n, h, (w + 63) // 64), dtype=torch.int64, device=pages.device) if debug else None
+        self._chk(self.lib.lumina_ocr_selection_marks(self._h, _ptr(pages), n, h, w, threshold, min_side, max_side, max_marks, _ptr(marks),
+                                                      _ptr(counts), _ptr(mask), self._stream()))
+        return (marks, counts, mask) if debug else (marks, counts)
+
+    def rules_and_marks(self, pages, threshold=None, gap=None, min_len=None, max_thick=None, max_rules=None, min_side=None, max_side=None,
+                        max_marks=None):
+        """table_rules and selection_marks of the same pages at one threshold, the ink mask computed once.
+        -> (hrules, vrules, rule counts, marks, mark counts), each as the two calls return it."""
+        torch = _torch()
+        n, h, w, c = pages.shape
+        assert c == 3 and pages.dtype == torch.uint8 and pages.is_contiguous()
+        tp = arch.TABLE_PARAMS
+        threshold, gap, min_len = (tp[k] if v is None else int(v) for k, v in (("threshold", threshold), ("gap", gap), ("min_len", min_len)))
+        max_thick, max_rules = (tp[k] if v is None else int(v) for k, v in (("max_thick", max_thick), ("max_rules", max_rules)))
+        min_side, max_side, max_marks = self._mark_params(min_side, max_side, max_marks)
+        hrules = torch.zeros((n, max_rules, 5), dtype=torch.int32, device=pages.device)
+        vrules = torch.zeros((n, max_rules, 5), dtype=torch.int32, device=pages.device)
+        rcounts = torch.zeros((n, 2), dtype=torch.int32, device=pages.device)
+        marks = torch.zeros((n, max_marks, 8), dtype=torch.int32, device=pages.device)
+        mcounts = torch.zeros((n,), dtype=torch.int32, device=pages.device)
+        self._chk(self.lib.lumina_ocr_rules_and_marks(self._h, _ptr(pages), n, h, w, threshold, gap, min_len, max_thick, max_rules, _ptr(hrules),
+                                                      _ptr(vrules), _ptr(rcounts), min_side, max_side, max_marks, _ptr(marks), _ptr(mcounts),
+                                                      self._stream()))
+        return hrules, vrules, rcounts, marks, mcounts
 
     @staticmethod
     def skew_degrees(rot) -> list:

@@ -34,6 +34,8 @@ class PageDetections:
     cls_scores: Optional[np.ndarray] = None   # float32 [n] probability of the label
     hrules: Optional[np.ndarray] = None       # int32 [nh, 5] x0, y0, x1, y1, area of the page's horizontal rules: OcrPipeline(tables=True) only
     vrules: Optional[np.ndarray] = None       # int32 [nv, 5] vertical rules (both empty when a list overflowed its capacity)
+    marks: Optional[np.ndarray] = None        # int32 [m, 8] x0, y0, x1, y1, edge, ink_in, area_in, state of the page's checkboxes:
+                                              # OcrPipeline(marks=True) only (empty when the list overflowed its capacity)
 
     def triples(self) -> List[Tuple[Sequence[int], str, float]]:
         return [(self.quads[i].tolist(), self.texts[i], float(self.scores[i])) for i in range(len(self.texts))]
@@ -52,18 +54,22 @@ class _Pending:
     event: Optional[object] = None
     gathered: Optional[object] = None   # multi-GPU: handle of dist.PageGather.submit (the batch's results of ALL ranks)
     rules_host: Optional[list] = None   # tables: pinned copies of hrules, vrules, counts
+    marks_host: Optional[list] = None   # marks: pinned copies of marks, counts
 
 
 class OcrPipeline:
     def __init__(self, engine: Engine, charset: Optional[List[str]] = None, max_dimension: int = 2000, post: Optional[dict] = None,
                  recognizer: str = "crnn", gather=None, angle_cls: bool = False, cls_thresh: float = arch.CLS_THRESH,
-                 tables: bool = False, table_params: Optional[dict] = None):
+                 tables: bool = False, table_params: Optional[dict] = None, marks: bool = False, mark_params: Optional[dict] = None):
         """recognizer: "crnn" (CRNN-MobileNetV3 + BiLSTM, engine.load_rec) or "svtr" (SVTR, engine.load_svtr).
         angle_cls: PaddleOCR's use_angle_cls — every line is classified 0 / 180 degrees (engine.load_cls) before recognition, and a line
         read as 180 with probability > cls_thresh is recognised turned; boxes and reading order are unchanged.  Per-line labels are
         not part of the multi-GPU gather.
         tables: the rules of ruled tables are extracted from the processed pages (engine.table_rules, parameters arch.TABLE_PARAMS or
         table_params) and come back as PageDetections.hrules / vrules; like the per-line labels they stay on their rank.
+        marks: the checkboxes of the processed pages (engine.selection_marks, parameters arch.MARK_PARAMS or mark_params) come back as
+        PageDetections.marks; they stay on their rank too.  With tables on as well and one threshold for both, the ink mask is
+        computed once (engine.rules_and_marks).
         gather: a dist.PageGather — multi-GPU runs: every batch's results are all-gathered from the device tensors and
         finish() returns a GatheredPages over the pages of ALL ranks instead of this rank's PageDetections."""
         assert recognizer in ("crnn", "svtr")
@@ -78,6 +84,8 @@ class OcrPipeline:
         self.angle_cls, self.cls_thresh = bool(angle_cls), float(cls_thresh)
         self.tables = bool(tables)
         self.table_params = dict(arch.TABLE_PARAMS if table_params is None else table_params)
+        self.marks = bool(marks)
+        self.mark_params = dict(arch.MARK_PARAMS if mark_params is None else mark_params)
         if self.angle_cls and not engine.cls_loaded:
             raise ValueError("angle_cls needs the orientation classifier's weights (Engine.load_cls)")
 
@@ -112,22 +120,32 @@ class OcrPipeline:
         """One host sync (box counts), then crop + CRNN + CTC and the device->pinned-host copies are enqueued. -> pending."""
         import torch
         b, h, w, _ = processed.shape
-        rules = None
-        if self.tables and self.gather is None:   # enqueued before the sync below: it runs while the host waits for the box counts
-            tp = self.table_params
-            rules = self.eng.table_rules(processed, tp["threshold"], tp["gap"], tp["min_len"], tp["max_thick"], tp["max_rules"])
+        rules = marks = None
+        if self.gather is None and (self.tables or self.marks):   # enqueued before the sync below: it runs while the host waits for the box counts
+            tp, mp = self.table_params, self.mark_params
+            if self.tables and self.marks and tp["threshold"] == mp["threshold"]:
+                both = self.eng.rules_and_marks(processed, tp["threshold"], tp["gap"], tp["min_len"], tp["max_thick"], tp["max_rules"],
+                                                mp["min_side"], mp["max_side"], mp["max_marks"])
+                rules, marks = both[:3], both[3:]
+            else:
+                if self.tables:
+                    rules = self.eng.table_rules(processed, tp["threshold"], tp["gap"], tp["min_len"], tp["max_thick"], tp["max_rules"])
+                if self.marks:
+                    marks = self.eng.selection_marks(processed, mp["threshold"], mp["min_side"], mp["max_side"], mp["max_marks"])
         counts_h = counts.cpu().numpy()  # the one host sync of the pipeline
         n = int(counts_h.sum())
         pend = _Pending(b=b, w=w, h=h, counts_h=counts_h, n=n, processed=processed)
         if rules is not None:
             pend.rules_host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in rules]
+        if marks is not None:
+            pend.marks_host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in marks]
         if self.gather is not None:
             self.gather.begin(counts_h)          # capacity all-reduce runs beside the recogniser
         if n == 0:
             if self.gather is not None:          # every rank takes part in the collective, with or without lines
                 e = lambda *shape, dt=torch.int32: torch.empty(shape, dtype=dt, device=boxes.device)
                 pend.gathered = self.gather.submit(counts_h, e(0, 8), e(0, dt=torch.float32), e(0, 80), e(0), e(0, dt=torch.float32))
-            elif pend.rules_host is not None:
+            elif pend.rules_host is not None or pend.marks_host is not None:
                 pend.event = torch.cuda.Event()
                 pend.event.record(torch.cuda.current_stream(processed.device))
             return pend
@@ -164,9 +182,10 @@ class OcrPipeline:
         if pend.event is not None:
             pend.event.synchronize()
         rules = self._page_rules(pend)
+        marks = self._page_marks(pend)
         if pend.n == 0:
             return [PageDetections(np.zeros((0, 8), np.int32), [], np.zeros(0, np.float32), np.zeros(0, np.float32), w, h,
-                                   hrules=rules[p][0], vrules=rules[p][1]) for p in range(b)], pend.processed
+                                   hrules=rules[p][0], vrules=rules[p][1], marks=marks[p]) for p in range(b)], pend.processed
         text_h, len_h, score_h, quads_h, det_h, *cls_h = (t.numpy() for t in pend.host)
         all_texts = self._decoder.decode(text_h, len_h)
         out, off = [], 0
@@ -176,7 +195,7 @@ class OcrPipeline:
             out.append(PageDetections(quads_h[off:off + c], texts, score_h[off:off + c], det_h[off:off + c], w, h,
                                       text_h[off:off + c], len_h[off:off + c],
                                       *((cls_h[0][off:off + c], cls_h[1][off:off + c]) if cls_h else ()),
-                                      hrules=rules[p][0], vrules=rules[p][1]))
+                                      hrules=rules[p][0], vrules=rules[p][1], marks=marks[p]))
             off += c
         return out, pend.processed
 
@@ -194,6 +213,22 @@ class OcrPipeline:
                 logger.warning("page %d of the batch has %d horizontal / %d vertical rules, more than max_rules = %d: no tables are built for it", p, nh, nv, cap)
                 nh = nv = 0
             out.append((hr[p, :nh].copy(), vr[p, :nv].copy()))
+        return out
+
+    def _page_marks(self, pend: "_Pending"):
+        """-> per page marks [m,8] from the pending batch's host copies, or None without marks.  A page whose true count exceeds the
+        capacity has no rows: it is treated as having no marks."""
+        if pend.marks_host is None:
+            return [None] * pend.b
+        rows, cnt = (t.numpy() for t in pend.marks_host)
+        cap = rows.shape[1]
+        out = []
+        for p in range(pend.b):
+            m = int(cnt[p])
+            if m > cap:
+                logger.warning("page %d of the batch has %d selection marks, more than max_marks = %d: none are reported for it", p, m, cap)
+                m = 0
+            out.append(rows[p, :m].copy())
         return out
 
     def run_many(self, batches, enhance: bool = True, deskew: bool = False):

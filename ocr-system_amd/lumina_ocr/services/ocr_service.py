@@ -29,6 +29,7 @@ from PIL import Image
 
 from .. import arch
 from ..utils import layout
+from ..utils import marks as mark_layout
 from ..utils import tables as table_layout
 from ..utils.image_preprocessing import ImagePreprocessor, get_optimal_size
 
@@ -127,6 +128,9 @@ class OCRService:
         # LUMINA_OCR_TABLES=1: ruled tables become `table` / `table_cell` entries and <table> blocks of the Markdown (the reference gets them
         # from Azure's layout model, :324-352).  Off by default: every output is then the one without them and tables_count stays 0.
         self._use_tables = os.environ.get("LUMINA_OCR_TABLES", "0").lower() not in ("", "0", "false", "no")
+        # LUMINA_OCR_SELECTION_MARKS=1: checkboxes become `selection_mark` entries and :selected: / :unselected: tokens of the Markdown (the
+        # reference gets them from Azure's layout model, :313-322).  Off by default: every output is then the one without them.
+        self._use_marks = os.environ.get("LUMINA_OCR_SELECTION_MARKS", "0").lower() not in ("", "0", "false", "no")
         self._weights_kind = "unloaded"
         self._pre = ImagePreprocessor(self.max_dimension)
         self._initialized = True
@@ -187,7 +191,7 @@ class OCRService:
                         raise RuntimeError("dictionary has %d classes (blank + symbols + space) but the %s head has %d"
                                            % (len(charset), "SVTR" if svtr else "CRNN", n_cls))
                     pipeline = OcrPipeline(eng, charset=charset, max_dimension=self.max_dimension, post=post, recognizer=self._recognizer,
-                                           angle_cls=self._use_angle_cls, tables=self._use_tables)
+                                           angle_cls=self._use_angle_cls, tables=self._use_tables, marks=self._use_marks)
             except Exception:
                 eng.close()
                 raise
@@ -270,14 +274,22 @@ class OCRService:
         if det.hrules is not None:   # LUMINA_OCR_TABLES=1; table_index counts from 0 here, _number_tables makes it run over a document
             tabs = table_layout.find_tables(det.hrules, det.vrules, arch.TABLE_PARAMS["snap"])
             table_layout.fill_cells(tabs, ordered)
-        md = layout.page_markdown(merged, tabs) if tabs else layout.page_markdown(merged)
+        found = mark_layout.select_marks(det.marks) if getattr(det, "marks", None) is not None else None   # LUMINA_OCR_SELECTION_MARKS=1
+        if found:
+            md = layout.page_markdown(merged, tabs, marks=found)
+        else:
+            md = layout.page_markdown(merged, tabs) if tabs else layout.page_markdown(merged)
         paragraphs = layout.build_paragraph_boxes(merged, page_number)
-        # words, lines, tables with their cells, paragraphs: the order of ocr_service.py:285-367
-        boxes = layout.build_layout_boxes(ordered, page_number) + layout.build_table_boxes(tabs, page_number) + paragraphs
+        # words, lines, selection marks, tables with their cells, paragraphs: the order of ocr_service.py:285-367
+        boxes = (layout.build_layout_boxes(ordered, page_number) + layout.build_mark_boxes(found or [], page_number)
+                 + layout.build_table_boxes(tabs, page_number) + paragraphs)
+        counts = {"page_count": 1, "words_count": sum(1 for b in boxes if b["type"] == "word"), "lines_count": len(ordered),
+                  "tables_count": len(tabs), "paragraphs_count": len(paragraphs)}
+        if found is not None:
+            counts["selection_marks_count"] = len(found)
         ph, pw = processed_hw
         return OCROutput(markdown=md, html=layout.html_from_markdown(md),
-                         json_output={"page_count": 1, "words_count": sum(1 for b in boxes if b["type"] == "word"),
-                                      "lines_count": len(ordered), "tables_count": len(tabs), "paragraphs_count": len(paragraphs)},
+                         json_output=counts,
                          processing_time_ms=_ms_since(t0), success=True, page_number=page_number, image_width=original_size[0],
                          image_height=original_size[1], layout_boxes=boxes, processed_image_bytes=jpeg,
                          page_width_inches=float(pw), page_height_inches=float(ph))

@@ -175,3 +175,93 @@ def synth_table_page(seed: int, h: int = 1100, w: int = 1500, n_tables: int = 1,
     if noise > 0:
         arr = arr + rng.normal(0.0, noise, arr.shape).astype(np.float32)
     return np.clip(np.rint(arr), 0, 255).astype(np.uint8), gt
+
+
+MARK_KINDS = ("empty", "cross", "tick", "filled", "block")   # the first is unselected, the others selected
+
+
+def _draw_mark(d: ImageDraw.ImageDraw, x0: int, y0: int, side: int, stroke: int, kind: str, ink) -> None:
+    """A square frame of `stroke` pixels with its first pixel at (x0, y0), and what is in it: nothing, a cross, a tick, all of it
+    filled, or a filled block 2 pixels clear of the frame.  Nothing leaves the square."""
+    x1, y1 = x0 + side - 1, y0 + side - 1
+    for k in range(stroke):
+        d.rectangle((x0 + k, y0 + k, x1 - k, y1 - k), outline=ink)
+    pen = max(stroke, 1 + side // 12)          # the pen that ticks a box is not thinner than a twelfth of it
+    a = stroke + 1 + pen // 2                  # first and last pixel of the pen's centre-line, relative to the corner
+    b = side - 1 - a
+    if kind == "cross":
+        d.line((x0 + a, y0 + a, x0 + b, y0 + b), fill=ink, width=pen)
+        d.line((x0 + a, y0 + b, x0 + b, y0 + a), fill=ink, width=pen)
+    elif kind == "tick":
+        d.line((x0 + a, y0 + side // 2, x0 + side // 2, y0 + b), fill=ink, width=pen)
+        d.line((x0 + side // 2, y0 + b, x0 + b, y0 + a), fill=ink, width=pen)
+    elif kind == "filled":
+        d.rectangle((x0, y0, x1, y1), fill=ink)
+    elif kind == "block":
+        d.rectangle((x0 + stroke + 2, y0 + stroke + 2, x1 - stroke - 2, y1 - stroke - 2), fill=ink)
+
+
+def synth_marks_page(seed: int, h: int = 1100, w: int = 1500, n_marks: int = 12, stroke: int = 0, side: int = 0, noise: float = 0.0,
+                     table: bool = True, min_side: int = 12, max_side: int = 64) -> Tuple[np.ndarray, List[dict]]:
+    """White form page with checkboxes: a title line, n_marks boxes in two columns, each with a label to its right, and (table) a ruled
+    2 x 2 table whose cells hold a box and a label, clear of the rules.
+    side: the box side in pixels (0: drawn from the seed per box, min_side .. max_side); stroke: the frame's thickness (0: from the
+    seed, 1-4), never more than side // 4, so that the frame stays out of the interior the state is read from; kind per box from the
+    seed (MARK_KINDS).  -> (uint8 [h,w,3], [dict(box=(x0, y0, x1, y1) inclusive, state='selected' | 'unselected', kind, stroke,
+    label, label_box, in_table)]) in drawing order: top to bottom, the left column before the right one in a row."""
+    rng = np.random.default_rng(seed)
+    img = Image.new("RGB", (w, h), (255, 255, 255))
+    d = ImageDraw.Draw(img)
+    scale = min(1.0, h / 2339.0 * 1.6 + 0.2)
+    margin = max(8, int(0.06 * w))
+    y = max(8, int(0.04 * h))
+    tsize = max(10, int(30 * scale))
+    fs = max(10, int(28 * scale))
+    d.text((margin, y), "Form %d" % seed, fill=(20, 20, 20), font=_font(tsize))
+    y += tsize + 40
+    gt: List[dict] = []
+
+    def put(x: int, yy: int, room: int, in_table: bool) -> int:
+        """box with its corner at (x, yy) + label; -> the box side"""
+        s = int(side) if side else int(rng.integers(min_side, max_side + 1))
+        t = max(1, min(int(stroke) if stroke else int(rng.integers(1, 5)), s // 4))
+        kind = MARK_KINDS[int(rng.integers(0, len(MARK_KINDS)))]
+        shade = int(rng.integers(0, 41))
+        _draw_mark(d, x, yy, s, t, kind, (shade, shade, shade))
+        tx, ty = x + s + s // 2 + 8, yy + max(0, (s - fs) // 2)
+        txt = random_text(rng, 4, 10).replace(" ", "x")
+        while len(txt) > 1 and d.textbbox((tx, ty), txt, font=_font(fs))[2] > x + room:
+            txt = txt[:-1]
+        d.text((tx, ty), txt, fill=(shade, shade, shade), font=_font(fs))
+        gt.append(dict(box=(x, yy, x + s - 1, yy + s - 1), state="unselected" if kind == "empty" else "selected", kind=kind, stroke=t,
+                       label=txt, label_box=d.textbbox((tx, ty), txt, font=_font(fs)), in_table=in_table))
+        return s
+
+    col_w = (w - 2 * margin) // 2
+    k = 0
+    while k < n_marks:
+        row_side = 0
+        for c in range(2):
+            if k < n_marks and y + max_side + 8 < h:
+                row_side = max(row_side, put(margin + c * col_w + int(rng.integers(0, 24)), y, col_w - 30, False))
+                k += 1
+        if row_side == 0:
+            break
+        y += max(row_side, fs) + 26
+    if table:
+        t, row_h = 3, max_side + 2 * 20 + 3
+        y += 20
+        if y + 2 * row_h + t < h - 4:
+            xs = [margin, margin + col_w, margin + 2 * col_w]
+            ys = [y, y + row_h, y + 2 * row_h]
+            for yy in ys:
+                d.rectangle((xs[0], yy, xs[-1] + t - 1, yy + t - 1), fill=(10, 10, 10))
+            for xx in xs:
+                d.rectangle((xx, ys[0], xx + t - 1, ys[-1] + t - 1), fill=(10, 10, 10))
+            for r in range(2):
+                for c in range(2):
+                    put(xs[c] + t + 20, ys[r] + t + 20, col_w - 40, True)
+    arr = np.asarray(img, np.float32)
+    if noise > 0:
+        arr = arr + rng.normal(0.0, noise, arr.shape).astype(np.float32)
+    return np.clip(np.rint(arr), 0, 255).astype(np.uint8), gt

@@ -132,12 +132,89 @@ def table_markdown(table: Dict[str, Any]) -> str:
     return "\n".join(rows)
 
 
-def page_markdown(merged: Sequence[MergedLine], tables: Optional[Sequence[Dict[str, Any]]] = None) -> str:
+def build_mark_boxes(marks: Sequence[Dict[str, Any]], page_number: int = 1) -> List[Dict[str, Any]]:
+    """`selection_mark` entries with the reference's keys (backend/services/ocr_service.py:313-322): type, state ("selected" /
+    "unselected"), confidence, polygon, page_number; marks as utils/marks.select_marks gives them, in their order."""
+    return [{"type": "selection_mark", "state": str(m["state"]), "confidence": float(m["confidence"]),
+             "polygon": [float(v) for v in m["polygon"]], "page_number": page_number} for m in marks]
+
+
+def _block_extent(b: TextBlock) -> Tuple[float, float, float]:
+    """-> (left, top, bottom) of a detection's quad"""
+    return min(pt[0] for pt in b.box), min(pt[1] for pt in b.box), max(pt[1] for pt in b.box)
+
+
+def _markdown_with_marks(merged: Sequence[MergedLine], tables: Sequence[Dict[str, Any]], marks: Sequence[Dict[str, Any]]) -> str:
+    """page_markdown for a page with selection marks.  A mark is Azure's Markdown token :selected: / :unselected: in front of the text
+    of the detection that starts nearest to the right of the mark's centre and whose vertical extent holds that centre.  A mark without
+    such a detection: inside a table cell it is appended to the cell, elsewhere it is a row of its own after the text, in mark order."""
+    blocks = [b for m in merged for b in m.blocks]
+    tokens: Dict[int, List[str]] = {}
+    loose: List[Tuple[str, float, float]] = []
+    for mk in marks:
+        x0, y0, x1, y1 = mk["box"]
+        cx, cy = (x0 + x1) / 2.0, (y0 + y1) / 2.0
+        token = ":%s:" % mk["state"]
+        best = None
+        for b in blocks:
+            left, top, bottom = _block_extent(b)
+            if left >= cx and top <= cy <= bottom and (best is None or left < best[0]):
+                best = (left, b)
+        if best is None:
+            loose.append((token, cx, cy))
+        else:
+            tokens.setdefault(id(best[1]), []).append(token)
+
+    def text_of(b: TextBlock) -> str:
+        return " ".join(tokens.get(id(b), []) + ([b.text] if b.text else []))
+
+    # the tables' cells as the Markdown shows them: their detections again, in reading order, now with the tokens
+    shown = [dict(t, cells=[dict(c, parts=[]) for c in t["cells"]]) for t in tables]
+    rows: List[str] = []
+    written = set()
+    for m in merged:
+        plain: List[str] = []
+        for b in m.blocks:
+            x, y = _tables.quad_centre([v for pt in b.box for v in pt])
+            hit = next(((i, c) for i, t in enumerate(shown) for c in [_tables.cell_at(t, x, y)] if c is not None), None)
+            if hit is None:
+                if text_of(b):
+                    plain.append(text_of(b))
+                continue
+            hit[1]["parts"].append(text_of(b))
+            if hit[0] not in written:
+                if plain:
+                    rows.append(" ".join(plain))
+                    plain = []
+                written.add(hit[0])
+                rows.append(hit[0])          # the table's place in the flow; its block is written once every cell is known
+        if plain:
+            rows.append(" ".join(plain))
+    orphans = []
+    for token, cx, cy in loose:
+        cell = next((c for t in shown for c in [_tables.cell_at(t, cx, cy)] if c is not None), None)
+        if cell is None:
+            orphans.append(token)
+        else:
+            cell["parts"].append(token)
+    for t in shown:
+        for c in t["cells"]:
+            c["content"] = " ".join(p for p in c["parts"] if p)
+    rows = [table_markdown(shown[r]) if isinstance(r, int) else r for r in rows]
+    rows.extend(table_markdown(t) for i, t in enumerate(shown) if i not in written)
+    return "\n".join(rows + orphans)
+
+
+def page_markdown(merged: Sequence[MergedLine], tables: Optional[Sequence[Dict[str, Any]]] = None,
+                  marks: Optional[Sequence[Dict[str, Any]]] = None) -> str:
     """combined_markdown is fed verbatim to the LLM step and must be non-blank for a non-empty page
     (/root/reference/backend/services/extraction_service.py:290-295, :658-662): one reading-order line per row.
     tables (utils/tables.find_tables + fill_cells): every table is written as its <table> block at the position of its first contained
     line, and the lines inside it (quad centre in a cell) leave the plain flow; what is left of a row that crosses a table stays a row
-    of its own.  Lines outside tables are unchanged."""
+    of its own.  Lines outside tables are unchanged.
+    marks (utils/marks.select_marks): see _markdown_with_marks; without marks the result is the one without the argument."""
+    if marks:
+        return _markdown_with_marks(merged, tables or [], marks)
     if not tables:
         return "\n".join(m.text for m in merged if m.text)
     rows: List[str] = []
