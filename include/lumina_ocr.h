@@ -190,6 +190,33 @@ int lumina_ocr_rules_and_marks(lumina_ocr_t* h, const uint8_t* pages_dev, int n,
                                int max_thick, int max_rules, int32_t* hrules_dev, int32_t* vrules_dev, int32_t* rule_counts_dev, int min_side,
                                int max_side, int max_marks, int32_t* marks_dev, int32_t* mark_counts_dev, void* stream);
 
+/* ---- page orientation (optional; DESIGN.md: "Page orientation") ----
+ * A page is upright after `turn` quarter turns: upright = np.rot90(page, turn) (counter-clockwise).  The three entries below are the
+ * device half; which pages get which turn is decided on the host (lumina_ocr/utils/page_orient.py, OcrPipeline.run_oriented).
+ *
+ * lumina_ocr_page_quarter: is a page sideways?  ink as in lumina_ocr_table_rules (L < threshold, Pillow's luma); r[y] / c[x] = the ink
+ * pixels of row y / column x; E_r = sum over y of (r[y+1] - r[y])^2, E_c likewise over x, in 64-bit integers: text lines make the
+ * profile across them jagged and the one along them flat.  energies_dev int64 [n][2] = E_r, E_c; sideways_dev int32 [n] = 1 when
+ * E_c > ratio * E_r (a blank page: 0).  pages_dev uint8 [n,H,W,3], sides 1..65535, ratio 1..1024.  A heuristic, not a model: a page
+ * whose ink is mostly long vertical rules is misjudged.  Integer arithmetic throughout: defined bit for bit
+ * (tests/page_orient_reference.py).  Asynchronous; n == 0 is a no-op; bad arguments return a status before anything is written.
+ * lumina_ocr_page_quarter_workspace_bytes: the workspace n pages of that size need in one launch (0: bad dimensions); the entry itself
+ * works in groups of pages bounded by 1 GiB.
+ *
+ * lumina_ocr_page_turn: out_dev uint8 [m][H'][W'][3], page j = np.rot90(pages[index[j]], turn) byte for byte; (H', W') = (W, H) for
+ * turn 1 and 3.  index_dev int32 [m] on the device, entries in 0..n-1, in any order, with repeats (an entry outside the range leaves
+ * its page unwritten).  Not in place.  Asynchronous; m == 0 is a no-op.
+ *
+ * lumina_ocr_page_vote: counts_dev int32 [pages][2] = the lines of each page and those among them whose flip flag is set, from
+ * lumina_ocr_cls_forward's flip_dev int32 [n] and the lines' page_idx_dev int32 [n] (entries outside 0..pages-1 are not counted).
+ * Asynchronous; n == 0 writes zeros. */
+size_t lumina_ocr_page_quarter_workspace_bytes(int n, int height, int width);
+int lumina_ocr_page_quarter(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int ratio,
+                            int64_t* energies_dev, int32_t* sideways_dev, void* stream);
+int lumina_ocr_page_turn(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, const int32_t* index_dev, int m, int turn,
+                         uint8_t* out_dev, void* stream);
+int lumina_ocr_page_vote(lumina_ocr_t* h, const int32_t* flip_dev, const int32_t* page_idx_dev, int n, int pages, int32_t* counts_dev, void* stream);
+
 /* Second recogniser family (BASELINE configs[4]: "SVTR-base multilingual (Hindi dict), fp16 MFMA"): same slot and the same outputs as
  * lumina_ocr_load_rec_weights / lumina_ocr_rec_forward (the `rec` model of the engine call, ocr_service_paddleocr_backup.py:232-238,
  * :285), with an SVTR backbone (patch embedding, local / global mixing blocks, CTC head) instead of CRNN.  Blob: LOCW with the

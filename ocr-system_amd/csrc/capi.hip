@@ -9,6 +9,7 @@
 #include "engine.h"
 #include "marks.h"
 #include "ops.h"
+#include "orient.h"
 #include "resize.h"
 #include "jpeg.h"
 #include "jpegdec.h"
@@ -619,6 +620,62 @@ int lumina_ocr_rules_and_marks(lumina_ocr_t* h, const uint8_t* pages_dev, int n,
     }
     return 0;
     API_CATCH(h)
+}
+
+// pages per quarter_launch: two masks and the profiles (~1/12 of the page bytes), halved until they fit 1 GiB
+static int quarter_group(const lumina_ocr* h, int n, int height, int width) {
+    int group = h->post_group < n ? h->post_group : n;
+    while (group > 1 && quarter_workspace_bytes(group, height, width) > ((size_t)1 << 30)) group = (group + 1) / 2;
+    return group;
+}
+
+size_t lumina_ocr_page_quarter_workspace_bytes(int n, int height, int width) { return n > 0 ? quarter_workspace_bytes(n, height, width) : 0; }
+
+int lumina_ocr_page_quarter(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int ratio, int64_t* energies_dev,
+                            int32_t* sideways_dev, void* stream) {
+    if (!h) return 1;
+    if (n == 0) return 0;
+    if (!pages_dev || !energies_dev || !sideways_dev || n < 0) return locr_fail(h, "page_quarter", "bad arguments");
+    if (quarter_workspace_bytes(1, height, width) == 0) return locr_fail(h, "page_quarter", "bad dimensions (sides 1..65535)");
+    if (ratio < 1 || ratio > QUARTER_MAX_RATIO) return locr_fail(h, "page_quarter", "ratio must be 1..1024");
+    BIND(h);
+    API_TRY
+    const int group = quarter_group(h, n, height, width);
+    for (int b0 = 0; b0 < n; b0 += group) {
+        const int nb = n - b0 < group ? n - b0 : group;
+        if (eng_ws_reserve(h, quarter_workspace_bytes(nb, height, width))) return 1;
+        QuarterParams p{};
+        p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.H = height; p.W = width; p.threshold = threshold; p.ratio = ratio;
+        p.energies = reinterpret_cast<long long*>(energies_dev) + (size_t)b0 * 2; p.sideways = sideways_dev + b0;
+        if (hip_rc(h, "page_quarter", quarter_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream))) return 1;
+    }
+    return 0;
+    API_CATCH(h)
+}
+
+int lumina_ocr_page_turn(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, const int32_t* index_dev, int m, int turn,
+                         uint8_t* out_dev, void* stream) {
+    if (!h) return 1;
+    if (m == 0) return 0;
+    if (!pages_dev || !index_dev || !out_dev || n <= 0 || m < 0 || height <= 0 || width <= 0 || height > 65535 || width > 65535 || turn < 0 || turn > 3 ||
+        pages_dev == out_dev)
+        return locr_fail(h, "page_turn", "bad arguments (sides 1..65535, turn 0..3, not in place)");
+    BIND(h);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t page = (size_t)height * width * 3;
+    for (int j0 = 0; j0 < m; j0 += 32768) {   // (the page index is a grid dimension)
+        const int mj = m - j0 < 32768 ? m - j0 : 32768;
+        if (hip_rc(h, "page_turn", page_turn_launch(pages_dev, n, height, width, index_dev + j0, mj, turn, out_dev + (size_t)j0 * page, st))) return 1;
+    }
+    return 0;
+}
+
+int lumina_ocr_page_vote(lumina_ocr_t* h, const int32_t* flip_dev, const int32_t* page_idx_dev, int n, int pages, int32_t* counts_dev, void* stream) {
+    if (!h) return 1;
+    if (pages == 0) return 0;
+    if (!counts_dev || pages < 0 || n < 0 || (n > 0 && (!flip_dev || !page_idx_dev))) return locr_fail(h, "page_vote", "bad arguments");
+    BIND(h);
+    return hip_rc(h, "page_vote", page_vote_launch(flip_dev, page_idx_dev, n, pages, counts_dev, (hipStream_t)stream));
 }
 
 int lumina_ocr_svtr_num_classes(const lumina_ocr_t* h) { return h ? h->svtr.num_classes : 0; }

@@ -22,4 +22,6 @@ constexpr int TABLE_MAX_RULES = 2048;
 size_t table_workspace_bytes(int B, int H, int W, int gap, int min_len, int max_rules);
 // the ink mask alone, [B][H][ceil(W / 64)] (tb_mask): shared with the selection marks (marks.hip)
 hipError_t table_mask_launch(const uint8_t* rgb, unsigned long long* mask, int B, int H, int W, int threshold, hipStream_t st);
+// the mask with x and y exchanged, [B][W][ceil(H / 64)] (tb_transpose): shared with the page orientation (orient.hip)
+hipError_t table_transpose_launch(const unsigned long long* hmask, unsigned long long* vmask, int B, int H, int W, hipStream_t st);
 hipError_t table_rules_launch(const TableParams& p, void* workspace, size_t ws_bytes, hipStream_t st);

@@ -274,6 +274,15 @@ hipError_t table_mask_launch(const uint8_t* rgb, unsigned long long* mask, int B
     return hipGetLastError();
 }
 
+hipError_t table_transpose_launch(const unsigned long long* hmask, unsigned long long* vmask, int B, int H, int W, hipStream_t st) {
+    if (!hmask || !vmask || B <= 0 || H <= 0 || W <= 0) return hipErrorInvalidValue;
+    const int nw = (W + 63) / 64, nhw = (H + 63) / 64;
+    const long long blocks = (long long)B * nw * nhw;
+    if (blocks >= (1ll << 33)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tb_transpose_kernel, dim3((unsigned)((blocks + 3) / 4)), dim3(256), 0, st, hmask, vmask, H, W, nw, nhw, blocks);
+    return hipGetLastError();
+}
+
 hipError_t table_rules_launch(const TableParams& p, void* workspace, size_t ws_bytes, hipStream_t st) {
     const int B = p.B, H = p.H, W = p.W;
     if (!table_args_ok(B, H, W, p.gap, p.min_len, p.max_rules) || p.max_thick < 0 || !p.rgb || !p.hrules || !p.vrules || !p.counts) return hipErrorInvalidValue;
@@ -286,11 +295,10 @@ hipError_t table_rules_launch(const TableParams& p, void* workspace, size_t ws_b
 
     hipError_t e = hipMemsetAsync(p.counts, 0, sizeof(int) * 2 * (size_t)B, st);
     if (e != hipSuccess) return e;
-    const long long blocks = (long long)B * nw * nhw;
     if (!p.hmask_in) e = table_mask_launch(p.rgb, p.hmask_out ? p.hmask_out : w.hmask, B, H, W, p.threshold, st);
     else if (p.hmask_out) e = hipMemcpyAsync(p.hmask_out, p.hmask_in, sizeof(unsigned long long) * (size_t)B * H * nw, hipMemcpyDeviceToDevice, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(tb_transpose_kernel, dim3((unsigned)((blocks + 3) / 4)), dim3(256), 0, st, hmask, w.vmask, H, W, nw, nhw, blocks);
+    if ((e = table_transpose_launch(hmask, w.vmask, B, H, W, st)) != hipSuccess) return e;
     TDirs D;
     D.B = B;
     for (int k = 0; k < 2; ++k) {

@@ -458,6 +458,11 @@ TABLE_PARAMS = dict(threshold=128, gap=2, min_len=64, max_thick=12, max_rules=51
 # row of a box); max_marks = capacity of a page's list.
 MARK_PARAMS = dict(threshold=128, min_side=12, max_side=64, max_marks=256)
 
+# Page orientation (lumina_ocr_page_quarter / _page_turn / _page_vote + utils/page_orient.py): ink as above; a page is sideways when the
+# energy of its column profile exceeds `ratio` times that of its row profile (text lines make the profile across them jagged), and an
+# upright-or-upside-down page is upside-down when it has at least min_lines lines and the classifier flips more than half of them.
+PAGE_ORIENT_PARAMS = dict(threshold=TABLE_PARAMS["threshold"], ratio=2, min_lines=3)
+
 
 def cls_block_table() -> List[dict]:
     """rec_block_table at scale 0.35 with the classifier's strides; `h` = the block's output height on a 48-row crop."""

@@ -90,6 +90,10 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_table_rules": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
         "lumina_ocr_selection_marks": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
         "lumina_ocr_rules_and_marks": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+        "lumina_ocr_page_quarter_workspace_bytes": (sz, [i32, i32, i32]),
+        "lumina_ocr_page_quarter": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+        "lumina_ocr_page_turn": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp]),
+        "lumina_ocr_page_vote": (i32, [vp, vp, vp, i32, i32, vp, vp]),
     }
     missing = []
     for name, (res, args) in sig.items():
@@ -115,6 +119,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_png_probe", "lumina_ocr_png_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
     "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks",
+    "lumina_ocr_page_quarter_workspace_bytes", "lumina_ocr_page_quarter", "lumina_ocr_page_turn", "lumina_ocr_page_vote",
 ]
 
 
@@ -538,6 +543,47 @@ class Engine:
                                                       _ptr(vrules), _ptr(rcounts), min_side, max_side, max_marks, _ptr(marks), _ptr(mcounts),
                                                       self._stream()))
         return hrules, vrules, rcounts, marks, mcounts
+
+    # -- page orientation (utils/page_orient.py, OcrPipeline.run_oriented) ---------------------------------------------------------
+    def page_quarter(self, pages, threshold=None, ratio=None):
+        """uint8 [n,H,W,3] device -> (energies int64 [n,2] = E_r, E_c: the summed squared differences of neighbouring row / column ink
+        counts; sideways int32 [n]: E_c > ratio * E_r) on the device.  Parameters default to arch.PAGE_ORIENT_PARAMS.  Asynchronous."""
+        torch = _torch()
+        n, h, w, c = pages.shape
+        assert c == 3 and pages.dtype == torch.uint8 and pages.is_contiguous()
+        pp = arch.PAGE_ORIENT_PARAMS
+        threshold, ratio = (pp[k] if v is None else int(v) for k, v in (("threshold", threshold), ("ratio", ratio)))
+        energies = torch.zeros((n, 2), dtype=torch.int64, device=pages.device)
+        sideways = torch.zeros((n,), dtype=torch.int32, device=pages.device)
+        self._chk(self.lib.lumina_ocr_page_quarter(self._h, _ptr(pages), n, h, w, threshold, ratio, _ptr(energies), _ptr(sideways), self._stream()))
+        return energies, sideways
+
+    def page_turn(self, pages, index, turn: int):
+        """uint8 [n,H,W,3] device, index int32 [m] device (entries 0..n-1, any order, repeats allowed), turn 0..3 -> uint8 [m,H',W',3]:
+        page j = np.rot90(pages[index[j]], turn) byte for byte; (H', W') = (W, H) for turn 1 and 3.  Asynchronous."""
+        torch = _torch()
+        n, h, w, c = pages.shape
+        assert c == 3 and pages.dtype == torch.uint8 and pages.is_contiguous()
+        if index.dtype != torch.int32 or index.device != pages.device or index.dim() != 1:
+            raise ValueError("index must be int32 [m] on %s" % pages.device)
+        if turn not in (0, 1, 2, 3):
+            raise ValueError("turn must be 0..3")
+        index = index.contiguous()
+        m = index.shape[0]
+        out = torch.empty((m, w, h, 3) if turn & 1 else (m, h, w, 3), dtype=torch.uint8, device=pages.device)
+        self._chk(self.lib.lumina_ocr_page_turn(self._h, _ptr(pages), n, h, w, _ptr(index), m, int(turn), _ptr(out), self._stream()))
+        return out
+
+    def page_vote(self, flip, page_idx, pages: int):
+        """cls_forward's flip flags int32 [n] + the lines' page indices int32 [n] (device) -> int32 [pages, 2] device: lines of each
+        page, lines among them whose flag is set.  Asynchronous."""
+        torch = _torch()
+        n = flip.shape[0]
+        if flip.dtype != torch.int32 or page_idx.dtype != torch.int32 or tuple(page_idx.shape) != (n,) or flip.dim() != 1:
+            raise ValueError("flip and page_idx must be int32 [n]")
+        counts = torch.zeros((pages, 2), dtype=torch.int32, device=flip.device)
+        self._chk(self.lib.lumina_ocr_page_vote(self._h, _ptr(flip.contiguous()), _ptr(page_idx.contiguous()), n, int(pages), _ptr(counts), self._stream()))
+        return counts
 
     @staticmethod
     def skew_degrees(rot) -> list:

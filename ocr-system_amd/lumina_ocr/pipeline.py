@@ -15,6 +15,7 @@ import numpy as np
 
 from . import arch
 from .engine import MAX_BOXES, Engine
+from .utils import page_orient
 from .utils.image_preprocessing import get_optimal_size
 
 logger = logging.getLogger(__name__)
@@ -36,6 +37,8 @@ class PageDetections:
     vrules: Optional[np.ndarray] = None       # int32 [nv, 5] vertical rules (both empty when a list overflowed its capacity)
     marks: Optional[np.ndarray] = None        # int32 [m, 8] x0, y0, x1, y1, edge, ink_in, area_in, state of the page's checkboxes:
                                               # OcrPipeline(marks=True) only (empty when the list overflowed its capacity)
+    turn: Optional[int] = None                # quarter turns that made the page upright, upright = np.rot90(input, turn); everything above
+                                              # refers to the upright page: OcrPipeline(page_orient=True).run_oriented only
 
     def triples(self) -> List[Tuple[Sequence[int], str, float]]:
         return [(self.quads[i].tolist(), self.texts[i], float(self.scores[i])) for i in range(len(self.texts))]
@@ -60,7 +63,8 @@ class _Pending:
 class OcrPipeline:
     def __init__(self, engine: Engine, charset: Optional[List[str]] = None, max_dimension: int = 2000, post: Optional[dict] = None,
                  recognizer: str = "crnn", gather=None, angle_cls: bool = False, cls_thresh: float = arch.CLS_THRESH,
-                 tables: bool = False, table_params: Optional[dict] = None, marks: bool = False, mark_params: Optional[dict] = None):
+                 tables: bool = False, table_params: Optional[dict] = None, marks: bool = False, mark_params: Optional[dict] = None,
+                 page_orient: bool = False, page_orient_params: Optional[dict] = None):
         """recognizer: "crnn" (CRNN-MobileNetV3 + BiLSTM, engine.load_rec) or "svtr" (SVTR, engine.load_svtr).
         angle_cls: PaddleOCR's use_angle_cls — every line is classified 0 / 180 degrees (engine.load_cls) before recognition, and a line
         read as 180 with probability > cls_thresh is recognised turned; boxes and reading order are unchanged.  Per-line labels are
@@ -70,6 +74,10 @@ class OcrPipeline:
         marks: the checkboxes of the processed pages (engine.selection_marks, parameters arch.MARK_PARAMS or mark_params) come back as
         PageDetections.marks; they stay on their rank too.  With tables on as well and one threshold for both, the ink mask is
         computed once (engine.rules_and_marks).
+        page_orient: run_oriented() finds for every page the quarter turns that make it upright (ink profiles for sideways pages,
+        parameters arch.PAGE_ORIENT_PARAMS or page_orient_params; the line classifier's majority for upside-down ones, so it needs
+        engine.load_cls like angle_cls), turns the raw page on the device and runs the stages below on the upright page.  run /
+        run_many / submit_* are the same with it on or off.  Not with a gather.
         gather: a dist.PageGather — multi-GPU runs: every batch's results are all-gathered from the device tensors and
         finish() returns a GatheredPages over the pages of ALL ranks instead of this rank's PageDetections."""
         assert recognizer in ("crnn", "svtr")
@@ -86,8 +94,14 @@ class OcrPipeline:
         self.table_params = dict(arch.TABLE_PARAMS if table_params is None else table_params)
         self.marks = bool(marks)
         self.mark_params = dict(arch.MARK_PARAMS if mark_params is None else mark_params)
+        self.page_orient = bool(page_orient)
+        self.page_orient_params = dict(arch.PAGE_ORIENT_PARAMS if page_orient_params is None else page_orient_params)
         if self.angle_cls and not engine.cls_loaded:
             raise ValueError("angle_cls needs the orientation classifier's weights (Engine.load_cls)")
+        if self.page_orient and not engine.cls_loaded:
+            raise ValueError("page_orient needs the orientation classifier's weights (Engine.load_cls)")
+        if self.page_orient and gather is not None:
+            raise ValueError("page_orient does not run with a gather: a page's turn and its processed size stay on their rank")
 
     # ---- stages -------------------------------------------------------------------------
     def preprocess(self, pages, enhance: bool = True, deskew: bool = False):
@@ -118,10 +132,14 @@ class OcrPipeline:
 
     def submit_recognize(self, processed, boxes, scores, counts) -> "_Pending":
         """One host sync (box counts), then crop + CRNN + CTC and the device->pinned-host copies are enqueued. -> pending."""
-        import torch
-        b, h, w, _ = processed.shape
+        rules, marks = self._submit_rules_marks(processed)   # enqueued before the sync below: it runs while the host waits for the box counts
+        counts_h = counts.cpu().numpy()  # the one host sync of the pipeline
+        return self._submit_lines(processed, boxes, scores, counts_h, rules, marks)
+
+    def _submit_rules_marks(self, processed):
+        """Enqueue the table rules and / or selection marks of the processed pages -> (rules, marks) device tensors, or None each."""
         rules = marks = None
-        if self.gather is None and (self.tables or self.marks):   # enqueued before the sync below: it runs while the host waits for the box counts
+        if self.gather is None and (self.tables or self.marks):
             tp, mp = self.table_params, self.mark_params
             if self.tables and self.marks and tp["threshold"] == mp["threshold"]:
                 both = self.eng.rules_and_marks(processed, tp["threshold"], tp["gap"], tp["min_len"], tp["max_thick"], tp["max_rules"],
@@ -132,7 +150,28 @@ class OcrPipeline:
                     rules = self.eng.table_rules(processed, tp["threshold"], tp["gap"], tp["min_len"], tp["max_thick"], tp["max_rules"])
                 if self.marks:
                     marks = self.eng.selection_marks(processed, mp["threshold"], mp["min_side"], mp["max_side"], mp["max_marks"])
-        counts_h = counts.cpu().numpy()  # the one host sync of the pipeline
+        return rules, marks
+
+    @staticmethod
+    def _select_lines(boxes, scores, counts_h, b: int):
+        """The valid (page, slot) pairs are known on the host (counts): one small index upload + two gathers, instead of boolean-mask
+        indexing (each of those runs a nonzero kernel and synchronises to learn its output size). -> quads, det scores, page index"""
+        import torch
+        n = int(counts_h.sum())
+        cap = boxes.shape[1]
+        page_h = np.repeat(np.arange(b, dtype=np.int64), counts_h)
+        slot_h = np.arange(n, dtype=np.int64) - np.repeat(np.cumsum(counts_h) - counts_h, counts_h)
+        flat = torch.from_numpy(page_h * cap + slot_h).to(boxes.device, non_blocking=True)
+        quads = boxes.view(-1, 8).index_select(0, flat)
+        det_sc = scores.view(-1).index_select(0, flat)
+        page_idx = torch.from_numpy(page_h.astype(np.int32)).to(boxes.device, non_blocking=True)
+        return quads, det_sc, page_idx
+
+    def _submit_lines(self, processed, boxes, scores, counts_h, rules, marks, lines=None) -> "_Pending":
+        """submit_recognize after its sync.  lines: (quads, det scores, page index, cls_forward's outputs or None) of the counted lines when
+        the caller has them already (run_oriented: the vote needed them), else they are selected and classified here."""
+        import torch
+        b, h, w, _ = processed.shape
         n = int(counts_h.sum())
         pend = _Pending(b=b, w=w, h=h, counts_h=counts_h, n=n, processed=processed)
         if rules is not None:
@@ -149,19 +188,14 @@ class OcrPipeline:
                 pend.event = torch.cuda.Event()
                 pend.event.record(torch.cuda.current_stream(processed.device))
             return pend
-        # the valid (page, slot) pairs are known on the host (counts): one small index upload + three gathers, instead of boolean-mask
-        # indexing (each of those runs a nonzero kernel and synchronises to learn its output size)
-        cap = boxes.shape[1]
-        page_h = np.repeat(np.arange(b, dtype=np.int64), counts_h)
-        slot_h = np.arange(n, dtype=np.int64) - np.repeat(np.cumsum(counts_h) - counts_h, counts_h)
-        flat = torch.from_numpy(page_h * cap + slot_h).to(boxes.device, non_blocking=True)
-        quads = boxes.view(-1, 8).index_select(0, flat)
-        det_sc = scores.view(-1).index_select(0, flat)
-        page_idx = torch.from_numpy(page_h.astype(np.int32)).to(boxes.device, non_blocking=True)
-        cls = None
-        if self.angle_cls:   # classifier crops -> labels and flip flags -> turned recognition crops, all on the device
-            ccrops, cwidths = self.eng.cls_crop(processed, quads, page_idx)
-            cls = self.eng.cls_forward(ccrops, cwidths, self.cls_thresh)
+        if lines is None:
+            quads, det_sc, page_idx = self._select_lines(boxes, scores, counts_h, b)
+            cls = None
+            if self.angle_cls:   # classifier crops -> labels and flip flags -> turned recognition crops, all on the device
+                ccrops, cwidths = self.eng.cls_crop(processed, quads, page_idx)
+                cls = self.eng.cls_forward(ccrops, cwidths, self.cls_thresh)
+        else:
+            quads, det_sc, page_idx, cls = lines
         crops, widths = self.eng.rec_crop(processed, quads, page_idx, flip=None if cls is None else cls[2])
         idx, prob = (self.eng.svtr_forward if self.recognizer == "svtr" else self.eng.rec_forward)(crops, widths)
         text, length, score = self.eng.ctc_decode(idx, prob)
@@ -246,3 +280,77 @@ class OcrPipeline:
     def run(self, pages, enhance: bool = True, deskew: bool = False) -> Tuple[List[PageDetections], "object"]:
         """-> (per-page detections, processed pages on device)."""
         return self.finish(self.submit_recognize(*self.submit_detect(pages, enhance, deskew)))
+
+    # ---- page orientation -----------------------------------------------------------------------------------------------
+    def _submit_first_pass(self, pages, enhance: bool, deskew: bool):
+        """The stages up to the classifier on pages that are upright or upside-down, the vote, then recognition of the pages voted
+        upright from the detections they have. -> (pending, bool [b]: voted upside-down; those pages have no lines in the pending)"""
+        import torch
+        processed, boxes, scores, counts = self.submit_detect(pages, enhance, deskew)
+        b = processed.shape[0]
+        rules, marks = self._submit_rules_marks(processed)
+        counts_h = counts.cpu().numpy()
+        if int(counts_h.sum()) == 0:
+            return self._submit_lines(processed, boxes, scores, counts_h, rules, marks), np.zeros(b, bool)
+        quads, det_sc, page_idx = self._select_lines(boxes, scores, counts_h, b)
+        ccrops, cwidths = self.eng.cls_crop(processed, quads, page_idx)
+        cls = self.eng.cls_forward(ccrops, cwidths, self.cls_thresh)
+        votes = self.eng.page_vote(cls[2], page_idx, b).cpu().numpy()   # the second small read: b x 2 integers
+        flipped = page_orient.upside_down(votes, self.page_orient_params["min_lines"])
+        if flipped.any():   # their lines leave the first pass: the second one reads the turned raw page
+            keep_h = np.nonzero(~flipped[np.repeat(np.arange(b), counts_h)])[0]
+            keep = torch.from_numpy(keep_h).to(boxes.device, non_blocking=True)
+            quads, det_sc, page_idx = (t.index_select(0, keep) for t in (quads, det_sc, page_idx))
+            cls = tuple(t.index_select(0, keep) for t in cls)
+            counts_h = np.where(flipped, 0, counts_h).astype(counts_h.dtype)
+        lines = (quads, det_sc, page_idx, cls if self.angle_cls else None)
+        return self._submit_lines(processed, boxes, scores, counts_h, rules, marks, lines=lines), flipped
+
+    def run_oriented_groups(self, pages, enhance: bool = True, deskew: bool = False):
+        """run_oriented's work, as the passes made it: -> [(input indices, detections, processed pages [m,H',W',3] on the device)], every
+        input page in exactly one entry; detections carry `turn`."""
+        import torch
+        if not self.page_orient:
+            raise ValueError("run_oriented needs OcrPipeline(page_orient=True)")
+        pp = self.page_orient_params
+        dev = pages.device
+        n = pages.shape[0]
+        _, sideways = self.eng.page_quarter(pages, pp["threshold"], pp["ratio"])
+        sideways_h = sideways.cpu().numpy()   # the first small read: which pages make the W x H group
+        index = lambda idxs: torch.tensor(idxs, dtype=torch.int32, device=dev)
+        first = []
+        for quarter, idxs in page_orient.first_pass_groups(sideways_h):
+            sub = pages if quarter == 0 and len(idxs) == n else self.eng.page_turn(pages, index(idxs), quarter)
+            first.append((quarter, idxs) + self._submit_first_pass(sub, enhance, deskew))
+        second = []
+        for quarter, idxs, _, flipped in first:
+            turn, again, _ = page_orient.second_pass(quarter, idxs, flipped)
+            if again:
+                turned = self.eng.page_turn(pages, index(again), turn)
+                second.append((turn, again, self.submit_recognize(*self.submit_detect(turned, enhance, deskew))))
+        out = []
+        for quarter, idxs, pend, flipped in first:
+            dets, processed = self.finish(pend)
+            keep = np.nonzero(~flipped)[0].tolist()
+            if not keep:
+                continue
+            for k in keep:
+                dets[k].turn = quarter
+            whole = len(keep) == len(idxs)
+            out.append(([idxs[k] for k in keep], dets if whole else [dets[k] for k in keep],
+                        processed if whole else processed.index_select(0, torch.tensor(keep, dtype=torch.int64, device=dev))))
+        for turn, idxs, pend in second:
+            dets, processed = self.finish(pend)
+            for d in dets:
+                d.turn = turn
+            out.append((idxs, dets, processed))
+        return out
+
+    def run_oriented(self, pages, enhance: bool = True, deskew: bool = False) -> Tuple[List[PageDetections], list]:
+        """pages uint8 [B,H,W,3] on the device, each lying any of the four ways -> (per-page detections in input order, each of the upright
+        page and with its `turn`; per-page processed page uint8 [H',W',3] on the device, upright).  Two small host reads more than run()
+        (the sideways flags, the votes), and a second pass over the pages found upside-down."""
+        groups = self.run_oriented_groups(pages, enhance, deskew)
+        dets = page_orient.reassemble(pages.shape[0], [(idxs, d) for idxs, d, _ in groups])
+        processed = page_orient.reassemble(pages.shape[0], [(idxs, list(p.unbind(0))) for idxs, _, p in groups])
+        return dets, processed

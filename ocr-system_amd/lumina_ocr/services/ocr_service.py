@@ -30,6 +30,7 @@ from PIL import Image
 from .. import arch
 from ..utils import layout
 from ..utils import marks as mark_layout
+from ..utils import page_orient
 from ..utils import tables as table_layout
 from ..utils.image_preprocessing import ImagePreprocessor, get_optimal_size
 
@@ -131,6 +132,10 @@ class OCRService:
         # LUMINA_OCR_SELECTION_MARKS=1: checkboxes become `selection_mark` entries and :selected: / :unselected: tokens of the Markdown (the
         # reference gets them from Azure's layout model, :313-322).  Off by default: every output is then the one without them.
         self._use_marks = os.environ.get("LUMINA_OCR_SELECTION_MARKS", "0").lower() not in ("", "0", "false", "no")
+        # LUMINA_OCR_PAGE_ORIENTATION=1: pages lying sideways or upside-down are turned upright on the device before anything else reads
+        # them (after decode and EXIF orientation, before the resize), and json_output reports page_rotation.  It uses the classifier
+        # (LUMINA_OCR_CLS_WEIGHTS) whether or not LUMINA_OCR_USE_ANGLE_CLS is set.  Off by default: every output is then the one without it.
+        self._use_page_orient = os.environ.get("LUMINA_OCR_PAGE_ORIENTATION", "0").lower() not in ("", "0", "false", "no")
         self._weights_kind = "unloaded"
         self._pre = ImagePreprocessor(self.max_dimension)
         self._initialized = True
@@ -155,9 +160,11 @@ class OCRService:
                                           ("LUMINA_OCR_SVTR_WEIGHTS" if svtr else "LUMINA_OCR_REC_WEIGHTS", self._svtr_weights if svtr else self._rec_weights)) if not v]
                 raise RuntimeError("OCR weights not configured: set %s (LOCW blobs) and LUMINA_OCR_REC_DICT, or LUMINA_OCR_ALLOW_SYNTHETIC=1 "
                                    "for seeded synthetic networks" % " and ".join(missing))
-            if self._use_angle_cls and not self._cls_weights and not self._allow_synthetic:
+            use_cls = self._use_angle_cls or self._use_page_orient
+            if use_cls and not self._cls_weights and not self._allow_synthetic:
                 raise RuntimeError("orientation classifier weights not configured: set LUMINA_OCR_CLS_WEIGHTS (LOCW blob) with "
-                                   "LUMINA_OCR_USE_ANGLE_CLS=1, or LUMINA_OCR_ALLOW_SYNTHETIC=1 for a seeded synthetic classifier")
+                                   "%s=1, or LUMINA_OCR_ALLOW_SYNTHETIC=1 for a seeded synthetic classifier"
+                                   % ("LUMINA_OCR_USE_ANGLE_CLS" if self._use_angle_cls else "LUMINA_OCR_PAGE_ORIENTATION"))
             if have_files and not self._rec_dict:
                 raise RuntimeError("LUMINA_OCR_REC_DICT (the dictionary file the recogniser was trained with) is required with weight files")
             eng = Engine(self._device)  # raises EngineUnavailable without the HIP library / a GPU
@@ -180,7 +187,7 @@ class OCRService:
                         else:
                             eng.load_rec(arch.make_rec_weights(num_classes=len(charset), code_path=True))
                         kind, post = "seeded-synthetic", arch.TEXT_PATH_POST
-                    if self._use_angle_cls:
+                    if use_cls:
                         if self._cls_weights:
                             eng.load_cls(Path(self._cls_weights).read_bytes())
                         else:
@@ -191,7 +198,8 @@ class OCRService:
                         raise RuntimeError("dictionary has %d classes (blank + symbols + space) but the %s head has %d"
                                            % (len(charset), "SVTR" if svtr else "CRNN", n_cls))
                     pipeline = OcrPipeline(eng, charset=charset, max_dimension=self.max_dimension, post=post, recognizer=self._recognizer,
-                                           angle_cls=self._use_angle_cls, tables=self._use_tables, marks=self._use_marks)
+                                           angle_cls=self._use_angle_cls, tables=self._use_tables, marks=self._use_marks,
+                                           page_orient=self._use_page_orient)
             except Exception:
                 eng.close()
                 raise
@@ -287,12 +295,29 @@ class OCRService:
                   "tables_count": len(tabs), "paragraphs_count": len(paragraphs)}
         if found is not None:
             counts["selection_marks_count"] = len(found)
+        if getattr(det, "turn", None) is not None:   # LUMINA_OCR_PAGE_ORIENTATION=1
+            counts["page_rotation"] = page_orient.page_rotation(det.turn)
         ph, pw = processed_hw
         return OCROutput(markdown=md, html=layout.html_from_markdown(md),
                          json_output=counts,
                          processing_time_ms=_ms_since(t0), success=True, page_number=page_number, image_width=original_size[0],
                          image_height=original_size[1], layout_boxes=boxes, processed_image_bytes=jpeg,
                          page_width_inches=float(pw), page_height_inches=float(ph))
+
+    def _run_pages(self, pages):
+        """Same-size pages on the device -> per page (detections, processed_image_bytes, processed (height, width)), in order.  With
+        LUMINA_OCR_PAGE_ORIENTATION=1 the pages come back upright: a batch may leave in several groups of two sizes."""
+        if not self._use_page_orient:
+            dets, processed = self._pipeline.run(pages, deskew=self.apply_deskew)
+            jpegs = self._pre.compress_for_azure_device(processed)   # processed_image_bytes: encoded on the device
+            hw = tuple(processed.shape[1:3])
+            return [(d, j, hw) for d, j in zip(dets, jpegs)]
+        parts = []
+        for idxs, dets, processed in self._pipeline.run_oriented_groups(pages, deskew=self.apply_deskew):
+            jpegs = self._pre.compress_for_azure_device(processed)
+            hw = tuple(processed.shape[1:3])
+            parts.append((idxs, [(d, j, hw) for d, j in zip(dets, jpegs)]))
+        return page_orient.reassemble(pages.shape[0], parts)
 
     def _process_single_image_sync(self, image: Image.Image, page_number: int = 1, decoded=None) -> OCROutput:
         """decoded: the page already on the device (uint8 [1,H,W,3], from the device JPEG decoder) — `image` is then only consulted
@@ -311,9 +336,8 @@ class OCRService:
                         nw, nh = get_optimal_size(w, h, self.max_dimension)
                         if nw <= 0 or nh <= 0:
                             raise ValueError("height and width must be > 0")
-                    dets, processed = self._pipeline.run(decoded, deskew=self.apply_deskew)
-                    jpeg = self._pre.compress_for_azure_device(processed)[0]   # processed_image_bytes: encoded on the device
-                return self._finish_page(dets[0], jpeg, tuple(processed.shape[1:3]), page_number, original_size, t0)
+                    det, jpeg, processed_hw = self._run_pages(decoded)[0]
+                return self._finish_page(det, jpeg, processed_hw, page_number, original_size, t0)
             except Exception as e:  # errors are data (:464-475)
                 logger.error("OCR failed: %s", e)
                 return OCROutput(success=False, error=str(e), processing_time_ms=_ms_since(t0), page_number=page_number,
@@ -500,10 +524,9 @@ class OCRService:
                             pages = torch.cat([on_device[i] for i in idxs]) if len(idxs) > 1 else on_device[idxs[0]]
                         else:
                             pages = self._upload(self._stage_pages([prepared[i] for i in idxs]))
-                        dets, processed = self._pipeline.run(pages, deskew=self.apply_deskew)
-                        jpegs = self._pre.compress_for_azure_device(processed)
-                    for j, i in enumerate(idxs):
-                        out[i] = self._finish_page(dets[j], jpegs[j], tuple(processed.shape[1:3]), first_page_number + i, images[i].size, t0)
+                        results = self._run_pages(pages)
+                    for (det, jpeg, processed_hw), i in zip(results, idxs):
+                        out[i] = self._finish_page(det, jpeg, processed_hw, first_page_number + i, images[i].size, t0)
                 except Exception as e:
                     for i in idxs:
                         out[i] = OCROutput(success=False, error=str(e), processing_time_ms=_ms_since(t0),
