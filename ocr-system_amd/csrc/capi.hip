@@ -11,6 +11,7 @@
 #include "ops.h"
 #include "orient.h"
 #include "resize.h"
+#include "runs.h"
 #include "jpeg.h"
 #include "jpegdec.h"
 #include "pngdec.h"
@@ -58,6 +59,22 @@ template <class F> static int drain_launches(lumina_ocr* h, const char* what, F&
         f(r, t);
     }
     h->launches.clear();
+    return 0;
+}
+
+// Pages are processed in groups that bound the workspace, whose size for a group of nb pages is ws(nb).  for_page_groups reserves it
+// and runs body(b0, nb) for every group of n pages (body returns 0, or 1 after locr_fail).  A group is the handle's post_group;
+// passes whose worst case is large (run lists, run slots, masks) take fit_group of it: at most n, and halved until it fits 1 GiB.
+template <class WS> static int fit_group(int group, int n, WS&& ws) {
+    if (group > n) group = n;
+    while (group > 1 && ws(group) > ((size_t)1 << 30)) group = (group + 1) / 2;
+    return group;
+}
+template <class WS, class Body> static int for_page_groups(lumina_ocr* h, int n, int group, WS&& ws, Body&& body) {
+    for (int b0 = 0; b0 < n; b0 += group) {
+        const int nb = n - b0 < group ? n - b0 : group;
+        if (eng_ws_reserve(h, ws(nb)) || body(b0, nb)) return 1;
+    }
     return 0;
 }
 
@@ -153,19 +170,14 @@ int lumina_ocr_det_postprocess(lumina_ocr_t* h, const uint16_t* prob_dev, int ba
     if (batch <= 0 || max_boxes <= 0 || valid_h > hp || valid_w > wp) return locr_fail(h, "det_postprocess", "bad dimensions");
     BIND(h);
     API_TRY
-    // pages are processed in groups that bound the workspace (~66 MB per A4 page: worst-case run list + row-extreme segments and hull scratch
-    // of max_boxes page-high candidates)
-    const int group = h->post_group;
-    for (int b0 = 0; b0 < batch; b0 += group) {
-        const int nb = batch - b0 < group ? batch - b0 : group;
-        if (eng_ws_reserve(h, dbpost_workspace_bytes(nb, hp, wp, max_boxes))) return 1;
+    // ~66 MB per A4 page: worst-case run list + row-extreme segments and hull scratch of max_boxes page-high candidates
+    return for_page_groups(h, batch, h->post_group, [&](int nb) { return dbpost_workspace_bytes(nb, hp, wp, max_boxes); }, [&](int b0, int nb) {
         DbPostParams p{};
         p.prob = prob_dev + (size_t)b0 * hp * wp; p.B = nb; p.Hp = hp; p.Wp = wp; p.valid_h = valid_h; p.valid_w = valid_w;
         p.thresh = thresh; p.box_thresh = box_thresh; p.unclip_ratio = unclip_ratio; p.min_size = min_size; p.max_boxes = max_boxes;
         p.boxes = boxes_dev + (size_t)b0 * max_boxes * 8; p.scores = scores_dev + (size_t)b0 * max_boxes; p.counts = counts_dev + b0;
-        if (hip_rc(h, "det_postprocess", dbpost_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream))) return 1;
-    }
-    return 0;
+        return hip_rc(h, "det_postprocess", dbpost_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
+    });
     API_CATCH(h)
 }
 
@@ -485,11 +497,8 @@ int lumina_ocr_deskew(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int heig
     BIND(h);
     API_TRY
     if (deskew_tables(h)) return 1;
-    // pages are processed in groups that bound the workspace (~16 bytes per pixel + the accumulators)
-    const int group = h->post_group;
-    for (int b0 = 0; b0 < n; b0 += group) {
-        const int nb = n - b0 < group ? n - b0 : group;
-        if (eng_ws_reserve(h, deskew_workspace_bytes(nb, height, width))) return 1;
+    // ~16 bytes per pixel + the accumulators
+    return for_page_groups(h, n, h->post_group, [&](int nb) { return deskew_workspace_bytes(nb, height, width); }, [&](int b0, int nb) {
         const size_t px = (size_t)height * width;
         DeskewParams p{};
         p.rgb = pages_dev + (size_t)b0 * px * 3; p.out = out_dev ? out_dev + (size_t)b0 * px * 3 : nullptr;
@@ -498,9 +507,8 @@ int lumina_ocr_deskew(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int heig
         p.edges_out = edges_dev ? edges_dev + (size_t)b0 * px : nullptr;
         p.segs_out = segs_dev ? segs_dev + (size_t)b0 * DESKEW_MAX_PEAKS * DESKEW_SEG_PER_PEAK * 4 : nullptr;
         p.nsegs_out = nsegs_dev ? nsegs_dev + (size_t)b0 * DESKEW_MAX_PEAKS : nullptr;
-        if (hip_rc(h, "deskew", deskew_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream))) return 1;
-    }
-    return 0;
+        return hip_rc(h, "deskew", deskew_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
+    });
     API_CATCH(h)
 }
 
@@ -513,45 +521,41 @@ int lumina_ocr_deskew_warp(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int
     API_CATCH(h)
 }
 
-int lumina_ocr_table_rules(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int gap, int min_len, int max_thick,
-                           int max_rules, int32_t* hrules_dev, int32_t* vrules_dev, int32_t* counts_dev, uint64_t* hmask_dev, void* stream) {
-    if (!h) return 1;
-    if (n == 0) return 0;
-    if (!pages_dev || !hrules_dev || !vrules_dev || !counts_dev || n < 0) return locr_fail(h, "table_rules", "bad arguments");
-    if (table_workspace_bytes(1, height, width, gap, min_len, max_rules) == 0)
-        return locr_fail(h, "table_rules", "bad dimensions or parameters (sides 1..65535, gap >= 0, min_len >= 1, max_rules 1..2048)");
-    if (max_thick < 0) return locr_fail(h, "table_rules", "max_thick must be >= 0");
-    BIND(h);
-    API_TRY
-    // pages are processed in groups that bound the workspace (the run slots: ~40 bytes per (min_len + gap + 1) pixels, both directions)
-    int group = h->post_group < n ? h->post_group : n;
-    while (group > 1 && table_workspace_bytes(group, height, width, gap, min_len, max_rules) > ((size_t)1 << 30)) group = (group + 1) / 2;
-    const size_t nw = ((size_t)width + 63) / 64;
-    for (int b0 = 0; b0 < n; b0 += group) {
-        const int nb = n - b0 < group ? n - b0 : group;
-        if (eng_ws_reserve(h, table_workspace_bytes(nb, height, width, gap, min_len, max_rules))) return 1;
-        TableParams p{};
-        p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.H = height; p.W = width;
-        p.threshold = threshold; p.gap = gap; p.min_len = min_len; p.max_thick = max_thick; p.max_rules = max_rules;
-        p.hrules = hrules_dev + (size_t)b0 * max_rules * 5; p.vrules = vrules_dev + (size_t)b0 * max_rules * 5; p.counts = counts_dev + (size_t)b0 * 2;
-        p.hmask_out = hmask_dev ? reinterpret_cast<unsigned long long*>(hmask_dev) + (size_t)b0 * height * nw : nullptr;
-        if (hip_rc(h, "table_rules", table_rules_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream))) return 1;
-    }
-    return 0;
-    API_CATCH(h)
+// what is wrong with a table_rules / selection_marks argument set, or null.  rules_and_marks, which takes both sets, reports the table
+// parameters in one text of its own (both_sets)
+static const char* tables_bad_args(int height, int width, int gap, int min_len, int max_thick, int max_rules, bool both_sets) {
+    const bool dims = table_workspace_bytes(1, height, width, gap, min_len, max_rules) == 0;
+    if (both_sets)
+        return dims || max_thick < 0 ? "bad dimensions or table parameters (sides 1..65535, gap >= 0, min_len >= 1, max_thick >= 0, max_rules 1..2048)" : nullptr;
+    if (dims) return "bad dimensions or parameters (sides 1..65535, gap >= 0, min_len >= 1, max_rules 1..2048)";
+    return max_thick < 0 ? "max_thick must be >= 0" : nullptr;
 }
-
-// what is wrong with a selection_marks argument set, or null
 static const char* marks_bad_args(int height, int width, int min_side, int max_side, int max_marks) {
     if (min_side < MARK_MIN_SIDE || max_side > MARK_MAX_SIDE || max_side < min_side) return "sides must satisfy 4 <= min_side <= max_side <= 64";
     if (marks_workspace_bytes(1, height, width, max_marks) == 0) return "bad dimensions or parameters (sides 1..65535, max_marks 1..2048)";
     return nullptr;
 }
-// pages per launch: the run list is sized for its worst case (24 bytes per two pixels), so the group is halved until it fits 1 GiB
-static int marks_group(const lumina_ocr* h, int n, int height, int width, int max_marks) {
-    int group = h->post_group < n ? h->post_group : n;
-    while (group > 1 && marks_workspace_bytes(group, height, width, max_marks) > ((size_t)1 << 30)) group = (group + 1) / 2;
-    return group;
+
+int lumina_ocr_table_rules(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int gap, int min_len, int max_thick,
+                           int max_rules, int32_t* hrules_dev, int32_t* vrules_dev, int32_t* counts_dev, uint64_t* hmask_dev, void* stream) {
+    if (!h) return 1;
+    if (n == 0) return 0;
+    if (!pages_dev || !hrules_dev || !vrules_dev || !counts_dev || n < 0) return locr_fail(h, "table_rules", "bad arguments");
+    if (const char* why = tables_bad_args(height, width, gap, min_len, max_thick, max_rules, false)) return locr_fail(h, "table_rules", why);
+    BIND(h);
+    API_TRY
+    // the run slots: ~40 bytes per (min_len + gap + 1) pixels, both directions
+    const auto ws = [&](int nb) { return table_workspace_bytes(nb, height, width, gap, min_len, max_rules); };
+    const size_t nw = ((size_t)width + 63) / 64;
+    return for_page_groups(h, n, fit_group(h->post_group, n, ws), ws, [&](int b0, int nb) {
+        TableParams p{};
+        p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.H = height; p.W = width;
+        p.threshold = threshold; p.gap = gap; p.min_len = min_len; p.max_thick = max_thick; p.max_rules = max_rules;
+        p.hrules = hrules_dev + (size_t)b0 * max_rules * 5; p.vrules = vrules_dev + (size_t)b0 * max_rules * 5; p.counts = counts_dev + (size_t)b0 * 2;
+        p.hmask_out = hmask_dev ? reinterpret_cast<unsigned long long*>(hmask_dev) + (size_t)b0 * height * nw : nullptr;
+        return hip_rc(h, "table_rules", table_rules_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
+    });
+    API_CATCH(h)
 }
 
 int lumina_ocr_selection_marks(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_side, int max_side,
@@ -562,19 +566,17 @@ int lumina_ocr_selection_marks(lumina_ocr_t* h, const uint8_t* pages_dev, int n,
     if (const char* why = marks_bad_args(height, width, min_side, max_side, max_marks)) return locr_fail(h, "selection_marks", why);
     BIND(h);
     API_TRY
-    const int group = marks_group(h, n, height, width, max_marks);
+    // the run list is sized for its worst case (24 bytes per two pixels)
+    const auto ws = [&](int nb) { return marks_workspace_bytes(nb, height, width, max_marks); };
     const size_t nw = ((size_t)width + 63) / 64;
-    for (int b0 = 0; b0 < n; b0 += group) {
-        const int nb = n - b0 < group ? n - b0 : group;
-        if (eng_ws_reserve(h, marks_workspace_bytes(nb, height, width, max_marks))) return 1;
+    return for_page_groups(h, n, fit_group(h->post_group, n, ws), ws, [&](int b0, int nb) {
         MarkParams p{};
         p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.H = height; p.W = width;
         p.threshold = threshold; p.min_side = min_side; p.max_side = max_side; p.max_marks = max_marks;
         p.marks = marks_dev + (size_t)b0 * max_marks * 8; p.counts = counts_dev + b0;
         p.mask_out = mask_dev ? reinterpret_cast<unsigned long long*>(mask_dev) + (size_t)b0 * height * nw : nullptr;
-        if (hip_rc(h, "selection_marks", marks_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream))) return 1;
-    }
-    return 0;
+        return hip_rc(h, "selection_marks", marks_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
+    });
     API_CATCH(h)
 }
 
@@ -584,49 +586,42 @@ int lumina_ocr_rules_and_marks(lumina_ocr_t* h, const uint8_t* pages_dev, int n,
     if (!h) return 1;
     if (n == 0) return 0;
     if (!pages_dev || !hrules_dev || !vrules_dev || !rule_counts_dev || !marks_dev || !mark_counts_dev || n < 0) return locr_fail(h, "rules_and_marks", "bad arguments");
-    if (table_workspace_bytes(1, height, width, gap, min_len, max_rules) == 0 || max_thick < 0)
-        return locr_fail(h, "rules_and_marks", "bad dimensions or table parameters (sides 1..65535, gap >= 0, min_len >= 1, max_thick >= 0, max_rules 1..2048)");
+    if (const char* why = tables_bad_args(height, width, gap, min_len, max_thick, max_rules, true)) return locr_fail(h, "rules_and_marks", why);
     if (const char* why = marks_bad_args(height, width, min_side, max_side, max_marks)) return locr_fail(h, "rules_and_marks", why);
     BIND(h);
     API_TRY
-    // one group size for both; the workspace is the group's mask, then room for the larger of the two passes (they run one after the
-    // other on the stream)
-    int group = marks_group(h, n, height, width, max_marks);
-    while (group > 1 && table_workspace_bytes(group, height, width, gap, min_len, max_rules) > ((size_t)1 << 30)) group = (group + 1) / 2;
+    // one group size for both (the marks limit, then the tables limit); the workspace is the group's mask, then room for the larger of
+    // the two passes (they run one after the other on the stream)
+    const auto wt = [&](int nb) { return table_workspace_bytes(nb, height, width, gap, min_len, max_rules); };
+    const auto wm = [&](int nb) { return marks_workspace_bytes(nb, height, width, max_marks); };
     const size_t nw = ((size_t)width + 63) / 64;
-    hipStream_t st = (hipStream_t)stream;
-    for (int b0 = 0; b0 < n; b0 += group) {
-        const int nb = n - b0 < group ? n - b0 : group;
-        const size_t wt = table_workspace_bytes(nb, height, width, gap, min_len, max_rules), wm = marks_workspace_bytes(nb, height, width, max_marks);
+    const auto rest_bytes = [&](int nb) { return wt(nb) > wm(nb) ? wt(nb) : wm(nb); };
+    const auto ws = [&](int nb) {
         Arena sizes;
         sizes.take<unsigned long long>((size_t)nb * height * nw);
-        sizes.take<uint8_t>(wt > wm ? wt : wm);
-        if (eng_ws_reserve(h, sizes.off)) return 1;
+        sizes.take<uint8_t>(rest_bytes(nb));
+        return sizes.off;
+    };
+    hipStream_t st = (hipStream_t)stream;
+    return for_page_groups(h, n, fit_group(fit_group(h->post_group, n, wm), n, wt), ws, [&](int b0, int nb) {
+        const size_t bytes = rest_bytes(nb);
         Arena a(h->ws.get(), h->ws.cap);
         unsigned long long* mask = a.take<unsigned long long>((size_t)nb * height * nw);
-        uint8_t* rest = a.take<uint8_t>(wt > wm ? wt : wm);
+        uint8_t* rest = a.take<uint8_t>(bytes);
         if (a.overflow) return locr_fail(h, "rules_and_marks", "workspace");
         const uint8_t* rgb = pages_dev + (size_t)b0 * height * width * 3;
-        if (hip_rc(h, "rules_and_marks", table_mask_launch(rgb, mask, nb, height, width, threshold, st))) return 1;
+        if (hip_rc(h, "rules_and_marks", ink_mask_launch(rgb, mask, nb, height, width, threshold, st))) return 1;
         TableParams t{};
         t.rgb = rgb; t.B = nb; t.H = height; t.W = width; t.threshold = threshold; t.gap = gap; t.min_len = min_len; t.max_thick = max_thick;
         t.max_rules = max_rules; t.hrules = hrules_dev + (size_t)b0 * max_rules * 5; t.vrules = vrules_dev + (size_t)b0 * max_rules * 5;
         t.counts = rule_counts_dev + (size_t)b0 * 2; t.hmask_in = mask;
-        if (hip_rc(h, "rules_and_marks", table_rules_launch(t, rest, wt > wm ? wt : wm, st))) return 1;
+        if (hip_rc(h, "rules_and_marks", table_rules_launch(t, rest, bytes, st))) return 1;
         MarkParams p{};
         p.rgb = rgb; p.B = nb; p.H = height; p.W = width; p.threshold = threshold; p.min_side = min_side; p.max_side = max_side; p.max_marks = max_marks;
         p.marks = marks_dev + (size_t)b0 * max_marks * 8; p.counts = mark_counts_dev + b0; p.mask_in = mask;
-        if (hip_rc(h, "rules_and_marks", marks_launch(p, rest, wt > wm ? wt : wm, st))) return 1;
-    }
-    return 0;
+        return hip_rc(h, "rules_and_marks", marks_launch(p, rest, bytes, st));
+    });
     API_CATCH(h)
-}
-
-// pages per quarter_launch: two masks and the profiles (~1/12 of the page bytes), halved until they fit 1 GiB
-static int quarter_group(const lumina_ocr* h, int n, int height, int width) {
-    int group = h->post_group < n ? h->post_group : n;
-    while (group > 1 && quarter_workspace_bytes(group, height, width) > ((size_t)1 << 30)) group = (group + 1) / 2;
-    return group;
 }
 
 size_t lumina_ocr_page_quarter_workspace_bytes(int n, int height, int width) { return n > 0 ? quarter_workspace_bytes(n, height, width) : 0; }
@@ -640,16 +635,14 @@ int lumina_ocr_page_quarter(lumina_ocr_t* h, const uint8_t* pages_dev, int n, in
     if (ratio < 1 || ratio > QUARTER_MAX_RATIO) return locr_fail(h, "page_quarter", "ratio must be 1..1024");
     BIND(h);
     API_TRY
-    const int group = quarter_group(h, n, height, width);
-    for (int b0 = 0; b0 < n; b0 += group) {
-        const int nb = n - b0 < group ? n - b0 : group;
-        if (eng_ws_reserve(h, quarter_workspace_bytes(nb, height, width))) return 1;
+    // two masks and the profiles (~1/12 of the page bytes)
+    const auto ws = [&](int nb) { return quarter_workspace_bytes(nb, height, width); };
+    return for_page_groups(h, n, fit_group(h->post_group, n, ws), ws, [&](int b0, int nb) {
         QuarterParams p{};
         p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.H = height; p.W = width; p.threshold = threshold; p.ratio = ratio;
         p.energies = reinterpret_cast<long long*>(energies_dev) + (size_t)b0 * 2; p.sideways = sideways_dev + b0;
-        if (hip_rc(h, "page_quarter", quarter_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream))) return 1;
-    }
-    return 0;
+        return hip_rc(h, "page_quarter", quarter_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
+    });
     API_CATCH(h)
 }
 

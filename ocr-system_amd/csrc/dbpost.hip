@@ -6,8 +6,8 @@
 // /root/reference/backend/utils/ocr_postprocessor.py:24 / flat polygon of ocr_service.py:295-301.
 //
 // Pipeline (all stream-ordered kernels, no host round trip).  Steps 1-7 work on the RUNS of the binarised map, one wave per page row:
-//   1 rl_mask / row_scan / rl_fill   threshold -> 64-bit masks per row segment -> run list [xs, xe] of the page in raster order
-//   2 rl_merge      union-find (atomicMin) over run ids: a run joins the runs of the row above it touches (8-connectivity)
+//   1 rl_mask / row_scan / run_fill   threshold -> 64-bit masks per row segment -> run list [xs, xe] of the page in raster order
+//   2 run_merge     union-find (atomicMin) over run ids: a run joins the runs of the row above it touches (8-connectivity)
 //   3 rl_roots      parent = root = the component's first run (starts at its smallest linear pixel index: canonical); roots per row
 //   4 row_scan / rl_assign : roots in raster order -> component id k < max_boxes, top row
 //   5 rl_extent     atomicMax of the component's bottom row
@@ -15,38 +15,22 @@
 //   8 comp_box      one work-group per component: hull (monotone chains), rotating calipers over hull
 //                   edges (lanes = edges), fixed-point score (lanes = pixels), unclip, corner order
 //   9 compact       valid boxes in component order -> boxes / scores / count
+// row_scan, run_fill and run_merge are the run-list kernels of runs.hip, shared with the selection marks.
 #include "dbpost.h"
+#include "runs.h"
 
 namespace {
 
-__device__ __forceinline__ int uf_find(const int* L, int i) {
-    int p = L[i];
-    while (p != i) { i = p; p = L[i]; }
-    return i;
-}
-__device__ __forceinline__ void uf_union(int* L, int a, int b) {
-    bool done = false;
-    while (!done) {
-        a = uf_find(L, a); b = uf_find(L, b);
-        if (a < b) { const int old = atomicMin(&L[b], a); done = (old == b); b = old; }
-        else if (b < a) { const int old = atomicMin(&L[a], b); done = (old == a); a = old; }
-        else done = true;
-    }
-}
-
 // ---- 1-7: connected components over RUNS.  A row of the binarised map is a short list of runs (a text page: ~10 per row, 2 %
 // of what a per-pixel label image holds), in raster order; everything between the threshold and the per-component row extremes
-// works on that list.  All kernels are one wave per (page, row), four rows per work-group.
-#define ROW_WAVE_DECODE                                                        \
-    const int wrow = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63; \
-    if (wrow >= rows_total) return;                                            \
-    const int row = wrow % Hp, pg = wrow / Hp;
+// works on that list.  All kernels are one wave per (page, row), four rows per work-group (row_wave).
 
 // 1a: threshold -> one 64-bit mask per 64-pixel segment of the row + the number of runs in the row; the row's probabilities are
 // requested 8 segments at a time
 __global__ __launch_bounds__(256) void rl_mask_kernel(const bf16_t* prob, unsigned long long* mask, int* runcnt, int Hp, int Wp, int nseg, int vh, int vw,
                                                       float thresh, int rows_total) {
-    ROW_WAVE_DECODE
+    int pg, row, lane;
+    if (!row_wave(Hp, rows_total, pg, row, lane)) return;
     const size_t base = ((size_t)pg * Hp + row) * Wp;
     unsigned long long* mrow = mask + ((size_t)pg * Hp + row) * nseg;
     int cnt = 0;
@@ -64,81 +48,16 @@ __global__ __launch_bounds__(256) void rl_mask_kernel(const bf16_t* prob, unsign
             if (x0 >= Wp) break;
             const unsigned long long m = __ballot(x < vw && row < vh && pv[u] > thresh);
             if (lane == 0) mrow[x0 >> 6] = m;
-            cnt += __popcll(m & ~((m << 1) | carry));
+            cnt += __popcll(run_starts(m, carry));
             carry = m >> 63;
         }
     }
     if (lane == 0) runcnt[(size_t)pg * (Hp + 1) + row] = cnt;
 }
-// exclusive scan of a page's Hp row counts (one wave, chunked): cnt[r] -> offset of row r, cnt[Hp] = total (also -> total_out)
-__global__ __launch_bounds__(64) void row_scan_kernel(int* cnt, int* total_out, int Hp) {
-    const int pg = blockIdx.x, lane = threadIdx.x;
-    int* rc = cnt + (size_t)pg * (Hp + 1);
-    int run = 0;
-    for (int r0 = 0; r0 < Hp; r0 += 64) {
-        const int r = r0 + lane;
-        const int v = r < Hp ? rc[r] : 0;
-        int inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(inc, d); if (lane >= d) inc += t; }
-        if (r < Hp) rc[r] = run + inc - v;
-        run += __shfl(inc, 63);
-    }
-    if (lane == 0) { rc[Hp] = run; if (total_out) total_out[pg] = run; }
-}
-// 1b: masks -> runs [xs, xe] of the row at its offset in the page's run list; a run is its own union-find parent.  Lanes = segments:
-// the j-th run start of the row pairs with the j-th run end (a run may span segments), so starts and ends are ranked separately.
-__global__ __launch_bounds__(256) void rl_fill_kernel(const unsigned long long* mask, const int* runoff, unsigned short* rxs, unsigned short* rxe, int* parent,
-                                                      int Hp, int nseg, size_t runcap, int rows_total) {
-    ROW_WAVE_DECODE
-    const unsigned long long* mrow = mask + ((size_t)pg * Hp + row) * nseg;
-    const size_t rb = (size_t)pg * runcap;
-    int sbase = runoff[(size_t)pg * (Hp + 1) + row], ebase = sbase;
-    unsigned long long carry = 0;
-    for (int s0 = 0; s0 < nseg; s0 += 64) {
-        const int sg = s0 + lane;
-        const unsigned long long m = sg < nseg ? mrow[sg] : 0ull;
-        unsigned long long prev = (unsigned long long)__shfl_up((int)(m >> 63), 1);          // bit 63 of the segment to the left
-        if (lane == 0) prev = carry;
-        unsigned long long next = (unsigned long long)(__shfl_down((int)(m & 1ull), 1) & 1);  // bit 0 of the segment to the right
-        if (lane == 63) next = s0 + 64 < nseg ? (mrow[s0 + 64] & 1ull) : 0ull;
-        unsigned long long st = m & ~((m << 1) | prev), en = m & ~((m >> 1) | (next << 63));
-        int si = __popcll(st), ei = __popcll(en);
-        const int ns = si, ne = ei;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int a = __shfl_up(si, d), b = __shfl_up(ei, d);
-            if (lane >= d) { si += a; ei += b; }
-        }
-        int sp = sbase + si - ns, ep = ebase + ei - ne;   // exclusive ranks
-        while (st) { const int bit = __ffsll((long long)st) - 1; st &= st - 1; rxs[rb + sp] = (unsigned short)(sg * 64 + bit); parent[rb + sp] = sp; ++sp; }
-        while (en) { const int bit = __ffsll((long long)en) - 1; en &= en - 1; rxe[rb + ep] = (unsigned short)(sg * 64 + bit); ++ep; }
-        sbase += __shfl(si, 63); ebase += __shfl(ei, 63);
-        carry = (unsigned long long)__shfl((int)(m >> 63), 63);
-    }
-}
-// 2: a run joins every run of the row above that it touches (8-connectivity: [xs - 1, xe + 1] overlaps [xs', xe']).  Run ids grow in
-// raster order and the union keeps the smaller root, so a component's root is its first run — the one that starts at the
-// component's smallest linear pixel index, the canonical root of the per-pixel definition.
-__global__ __launch_bounds__(256) void rl_merge_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* parent, int Hp,
-                                                       size_t runcap, int rows_total) {
-    ROW_WAVE_DECODE
-    if (row == 0) return;
-    const int* ro = runoff + (size_t)pg * (Hp + 1);
-    const int u0 = ro[row - 1], r0 = ro[row], r1 = ro[row + 1];
-    if (u0 == r0) return;
-    const size_t rb = (size_t)pg * runcap;
-    int* P = parent + rb;
-    for (int id = r0 + lane; id < r1; id += 64) {
-        const int xs = rxs[rb + id], xe = rxe[rb + id];
-        int lo = u0, hi = r0;   // first run of the row above with xe' + 1 >= xs
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if ((int)rxe[rb + mid] + 1 < xs) lo = mid + 1; else hi = mid; }
-        for (int t = lo; t < r0 && (int)rxs[rb + t] <= xe + 1; ++t) uf_union(P, id, t);
-    }
-}
 // 3 + 4a: every run learns its root; roots per row are counted
 __global__ __launch_bounds__(256) void rl_roots_kernel(const int* runoff, int* parent, int* rootcnt, int Hp, size_t runcap, int rows_total) {
-    ROW_WAVE_DECODE
+    int pg, row, lane;
+    if (!row_wave(Hp, rows_total, pg, row, lane)) return;
     const int* ro = runoff + (size_t)pg * (Hp + 1);
     const int r0 = ro[row], r1 = ro[row + 1];
     int* P = parent + (size_t)pg * runcap;
@@ -158,7 +77,8 @@ __global__ __launch_bounds__(256) void rl_roots_kernel(const int* runoff, int* p
 // 4c: roots in raster order -> component id k (or -1 beyond the cap); the root's row IS the component's top row
 __global__ __launch_bounds__(256) void rl_assign_kernel(const int* runoff, const int* rootoff, const int* parent, int* cidr, int* ymin, int* ymax, int Hp,
                                                         size_t runcap, int maxc, int rows_total) {
-    ROW_WAVE_DECODE
+    int pg, row, lane;
+    if (!row_wave(Hp, rows_total, pg, row, lane)) return;
     const int* ro = runoff + (size_t)pg * (Hp + 1);
     const int r0 = ro[row], r1 = ro[row + 1];
     const size_t rb = (size_t)pg * runcap;
@@ -178,7 +98,8 @@ __global__ __launch_bounds__(256) void rl_assign_kernel(const int* runoff, const
 // 5: bottom row of every component
 __global__ __launch_bounds__(256) void rl_extent_kernel(const int* runoff, const int* parent, const int* cidr, int* ymax, int Hp, size_t runcap, int maxc,
                                                         int rows_total) {
-    ROW_WAVE_DECODE
+    int pg, row, lane;
+    if (!row_wave(Hp, rows_total, pg, row, lane)) return;
     const int* ro = runoff + (size_t)pg * (Hp + 1);
     const size_t rb = (size_t)pg * runcap;
     for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
@@ -212,7 +133,8 @@ __global__ __launch_bounds__(256) void seg_init_kernel(const int* ncomp, const i
 __global__ __launch_bounds__(256) void rl_extremes_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, const int* parent,
                                                           const int* cidr, const int* ymin, const int* segoff, int* rowmin, int* rowmax, int Hp,
                                                           size_t runcap, int maxc, size_t seg_cap, int rows_total) {
-    ROW_WAVE_DECODE
+    int pg, row, lane;
+    if (!row_wave(Hp, rows_total, pg, row, lane)) return;
     const int* ro = runoff + (size_t)pg * (Hp + 1);
     const size_t rb = (size_t)pg * runcap;
     for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
@@ -535,9 +457,6 @@ __global__ __launch_bounds__(256) void crop_kernel(const uint8_t* pages, int H, 
 
 }  // namespace
 
-// worst case of a row: every other pixel starts a run
-static size_t dbpost_runcap(int Hp, int Wp) { return (size_t)Hp * ((Wp + 1) / 2); }
-
 // the workspace's regions: one layout sizes it (dbpost_workspace_bytes) and carves it (dbpost_launch)
 struct DbWorkspace {
     unsigned long long* mask; int *runoff, *rootoff, *nruns, *ncomp; unsigned short *rxs, *rxe;
@@ -545,7 +464,7 @@ struct DbWorkspace {
 };
 static DbWorkspace dbpost_layout(Arena& a, int B, int Hp, int Wp, int maxc) {
     const size_t seg_cap = (size_t)maxc * Hp;  // worst case: every candidate spans the page height
-    const size_t runcap = dbpost_runcap(Hp, Wp), nseg = (Wp + 63) / 64;
+    const size_t runcap = run_cap(Hp, Wp), nseg = (Wp + 63) / 64;
     DbWorkspace w;
     w.mask = a.take<unsigned long long>((size_t)B * Hp * nseg);
     w.runoff = a.take<int>((size_t)B * (Hp + 1)); w.rootoff = a.take<int>((size_t)B * (Hp + 1));   // run / root counts -> offsets
@@ -568,21 +487,21 @@ size_t dbpost_workspace_bytes(int B, int Hp, int Wp, int maxc) {
 
 hipError_t dbpost_launch(const DbPostParams& p, void* workspace, size_t ws_bytes, hipStream_t st) {
     const int B = p.B, Hp = p.Hp, Wp = p.Wp, maxc = p.max_boxes;
-    if (B <= 0 || Hp <= 0 || Wp <= 0 || Wp > 65535 || maxc <= 0 || (size_t)B * Hp >= (1ull << 31) || dbpost_runcap(Hp, Wp) >= (1ull << 31)) return hipErrorInvalidValue;
-    const size_t seg_cap = (size_t)maxc * Hp, runcap = dbpost_runcap(Hp, Wp);
+    if (B <= 0 || Hp <= 0 || Wp <= 0 || Wp > 65535 || maxc <= 0 || (size_t)B * Hp >= (1ull << 31) || run_cap(Hp, Wp) >= (1ull << 31)) return hipErrorInvalidValue;
+    const size_t seg_cap = (size_t)maxc * Hp, runcap = run_cap(Hp, Wp);
     const int nseg = (Wp + 63) / 64;
     Arena a(workspace, ws_bytes);
     const DbWorkspace w = dbpost_layout(a, B, Hp, Wp, maxc);
     if (a.overflow) return hipErrorOutOfMemory;
 
     const int rows = B * Hp;
-    const dim3 grows((unsigned)((rows + 3) / 4));
+    const dim3 grows = row_wave_grid(rows);
     hipLaunchKernelGGL(rl_mask_kernel, grows, dim3(256), 0, st, p.prob, w.mask, w.runoff, Hp, Wp, nseg, p.valid_h, p.valid_w, p.thresh, rows);
-    hipLaunchKernelGGL(row_scan_kernel, dim3(B), dim3(64), 0, st, w.runoff, w.nruns, Hp);
-    hipLaunchKernelGGL(rl_fill_kernel, grows, dim3(256), 0, st, w.mask, w.runoff, w.rxs, w.rxe, w.parent, Hp, nseg, runcap, rows);
-    hipLaunchKernelGGL(rl_merge_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, Hp, runcap, rows);
+    row_scan_launch(w.runoff, w.nruns, B, Hp, st);
+    run_fill_launch(w.mask, w.runoff, w.rxs, w.rxe, w.parent, nullptr, B, Hp, nseg, runcap, st);
+    run_merge_launch(w.runoff, w.rxs, w.rxe, w.parent, B, Hp, runcap, st);
     hipLaunchKernelGGL(rl_roots_kernel, grows, dim3(256), 0, st, w.runoff, w.parent, w.rootoff, Hp, runcap, rows);
-    hipLaunchKernelGGL(row_scan_kernel, dim3(B), dim3(64), 0, st, w.rootoff, w.ncomp, Hp);
+    row_scan_launch(w.rootoff, w.ncomp, B, Hp, st);
     hipLaunchKernelGGL(rl_assign_kernel, grows, dim3(256), 0, st, w.runoff, w.rootoff, w.parent, w.cidr, w.ymin, w.ymax, Hp, runcap, maxc, rows);
     hipLaunchKernelGGL(rl_extent_kernel, grows, dim3(256), 0, st, w.runoff, w.parent, w.cidr, w.ymax, Hp, runcap, maxc, rows);
     hipLaunchKernelGGL(seg_scan_kernel, dim3(B), dim3(64), 0, st, w.ncomp, w.ymin, w.ymax, w.segoff, maxc);

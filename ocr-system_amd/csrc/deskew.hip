@@ -21,6 +21,7 @@
 //                  (sin, cos, flag) in fp64
 //   warp           fixed-point bicubic gather (32x32 phases, 15-bit weights), or a plain copy when the page is not rotated
 #include "deskew.h"
+#include "runs.h"
 
 #include <cmath>
 #include <cstring>
@@ -32,22 +33,6 @@ constexpr int DK_MAX_PEAKS = 512, DK_MAX_VOTES = 8192, DK_SEG_PER_PEAK = 8;
 constexpr double DK_SIN_HALF_DEG = 0.008726535498373935;
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// min-label union-find (parents only ever decrease: the root of a set is its smallest index); used on LDS tiles and on pages
-__device__ __forceinline__ int uf_find(const int* L, int i) {
-    int p = L[i];
-    while (p != i) { i = p; p = L[i]; }
-    return i;
-}
-__device__ __forceinline__ void uf_union(int* L, int a, int b) {
-    bool done = false;
-    while (!done) {
-        a = uf_find(L, a); b = uf_find(L, b);
-        if (a < b) { const int old = atomicMin(&L[b], a); done = (old == b); b = old; }
-        else if (b < a) { const int old = atomicMin(&L[a], b); done = (old == a); a = old; }
-        else done = true;
-    }
-}
 
 // ---------------------------------------------------------------------------------------------- 1 + 2a: map
 constexpr int CT_H = 16, CT_W = 64;

@@ -13,7 +13,7 @@ struct MarkParams {
     int* marks;           // device, [B][max_marks][8] = x0, y0, x1, y1, edge, ink_in, area_in, state; sorted by (y0, x0, y1, x1, root)
     int* counts;          // device, [B]: true number of marks (a list is not written when it overflows)
     unsigned long long* mask_out;        // optional parity hook: ink mask [B][H][ceil(W / 64)], bit x % 64 of word x / 64
-    const unsigned long long* mask_in;   // optional: the ink mask of these pages at this threshold, already computed (table_mask_launch)
+    const unsigned long long* mask_in;   // optional: the ink mask of these pages at this threshold, already computed (ink_mask_launch, runs.h)
 };
 constexpr int MARK_MAX_SIDE = 64;
 constexpr int MARK_MIN_SIDE = 4;

@@ -4,12 +4,12 @@
 //
 // A box side (14-60 pixels at 200 dpi) is shorter than any rule, so the fixed run slots of tables.hip do not apply: marks need the
 // connected components of ALL ink.  A row of a page is a list of runs (a text page: ~100 per row), in raster order, and everything
-// up to the candidates works on that list, as dbpost.hip does for the probability map.
+// up to the candidates works on that list, as dbpost.hip does for the probability map: steps 1-3 are the shared kernels of runs.hip.
 //
 // All stream-ordered kernels, no host round trip; kernels 2-5 are one wave per (page, row), four rows per work-group:
-//   1 tb_mask (tables.hip)   ink = L < threshold packed into 64-bit words along x — or the mask the caller already has
-//   2 mk_count / mk_scan / mk_fill   mask words -> run list [xs, xe] of the page in raster order; a run is its own parent and box
-//   3 mk_merge    union-find (atomicMin) over run ids: a run joins the runs of the row above it touches (8-connectivity); the root
+//   1 ink_mask    ink = L < threshold packed into 64-bit words along x — or the mask the caller already has
+//   2 run_count / row_scan / run_fill   mask words -> run list [xs, xe] of the page in raster order; a run is its own parent and box
+//   3 run_merge   union-find (atomicMin) over run ids: a run joins the runs of the row above it touches (8-connectivity); the root
 //                 of a component is its first run in raster order
 //   4 mk_accum    every run learns its root; bounding box of every component accumulated at the root (atomicMin / atomicMax,
 //                 issued only when the value read would change)
@@ -18,26 +18,11 @@
 //                 interior ink are wave-wide OR / popcount / add reductions (no LDS, no per-pixel loop) -> counted, gathered
 //   6 mk_sort     one work-group per page: rank sort by (y0, x0, y1, x1, root) -> the output
 #include "marks.h"
-#include "tables.h"
+#include "runs.h"
 
 namespace {
 
 typedef unsigned long long u64;
-
-__device__ __forceinline__ int uf_find(const int* L, int i) {
-    int p = L[i];
-    while (p != i) { i = p; p = L[i]; }
-    return i;
-}
-__device__ __forceinline__ void uf_union(int* L, int a, int b) {
-    bool done = false;
-    while (!done) {
-        a = uf_find(L, a); b = uf_find(L, b);
-        if (a < b) { const int old = atomicMin(&L[b], a); done = (old == b); b = old; }
-        else if (b < a) { const int old = atomicMin(&L[a], b); done = (old == a); a = old; }
-        else done = true;
-    }
-}
 
 __device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
@@ -51,112 +36,12 @@ __device__ __forceinline__ u64 wave_or(u64 v) {
     return ((u64)hi << 32) | lo;
 }
 
-#define ROW_WAVE_DECODE                                                                          \
-    const long long wrow = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);                       \
-    const int lane = threadIdx.x & 63;                                                           \
-    if (wrow >= rows_total) return;                                                              \
-    const int row = (int)(wrow % H), pg = (int)(wrow / H);
-
-// 2a: number of runs in the row (a run starts at an ink bit whose left neighbour, the previous word's bit 63 included, is not ink)
-__global__ __launch_bounds__(256) void mk_count_kernel(const u64* mask, int* runcnt, int H, int nw, long long rows_total) {
-    ROW_WAVE_DECODE
-    const u64* mrow = mask + (size_t)wrow * nw;
-    int cnt = 0;
-    u64 carry = 0;
-    for (int s0 = 0; s0 < nw; s0 += 64) {
-        const int sg = s0 + lane;
-        const u64 m = sg < nw ? mrow[sg] : 0ull;
-        u64 prev = (u64)(unsigned)__shfl_up((int)(m >> 63), 1);
-        if (lane == 0) prev = carry;
-        cnt += __popcll(m & ~((m << 1) | prev));
-        carry = (u64)(unsigned)__shfl((int)(m >> 63), 63);
-    }
-    cnt = wave_sum(cnt);
-    if (lane == 0) runcnt[(size_t)pg * (H + 1) + row] = cnt;
-}
-// 2b: exclusive scan of a page's H row counts (one wave, chunked): cnt[r] -> offset of row r, cnt[H] = total
-__global__ __launch_bounds__(64) void mk_scan_kernel(int* cnt, int H) {
-    const int pg = blockIdx.x, lane = threadIdx.x;
-    int* rc = cnt + (size_t)pg * (H + 1);
-    int run = 0;
-    for (int r0 = 0; r0 < H; r0 += 64) {
-        const int r = r0 + lane;
-        const int v = r < H ? rc[r] : 0;
-        int inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(inc, d); if (lane >= d) inc += t; }
-        if (r < H) rc[r] = run + inc - v;
-        run += __shfl(inc, 63);
-    }
-    if (lane == 0) rc[H] = run;
-}
-// 2c: mask words -> runs [xs, xe] of the row at its offset in the page's run list.  Lanes = words: the j-th run start of the row
-// pairs with the j-th run end (a run may span words), so starts and ends are ranked separately.  box = x0, x1, y0, y1 of the run.
-__global__ __launch_bounds__(256) void mk_fill_kernel(const u64* mask, const int* runoff, unsigned short* rxs, unsigned short* rxe, int* parent, int4* box,
-                                                      int H, int nw, size_t runcap, long long rows_total) {
-    ROW_WAVE_DECODE
-    const u64* mrow = mask + (size_t)wrow * nw;
-    const size_t rb = (size_t)pg * runcap;
-    int sbase = runoff[(size_t)pg * (H + 1) + row], ebase = sbase;
-    u64 carry = 0;
-    for (int s0 = 0; s0 < nw; s0 += 64) {
-        const int sg = s0 + lane;
-        const u64 m = sg < nw ? mrow[sg] : 0ull;
-        u64 prev = (u64)(unsigned)__shfl_up((int)(m >> 63), 1);             // bit 63 of the word to the left
-        if (lane == 0) prev = carry;
-        u64 next = (u64)(unsigned)(__shfl_down((int)(m & 1ull), 1) & 1);    // bit 0 of the word to the right
-        if (lane == 63) next = s0 + 64 < nw ? (mrow[s0 + 64] & 1ull) : 0ull;
-        u64 st = m & ~((m << 1) | prev), en = m & ~((m >> 1) | (next << 63));
-        int si = __popcll(st), ei = __popcll(en);
-        const int ns = si, ne = ei;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int a = __shfl_up(si, d), b = __shfl_up(ei, d);
-            if (lane >= d) { si += a; ei += b; }
-        }
-        int sp = sbase + si - ns, ep = ebase + ei - ne;   // exclusive ranks
-        while (st) {
-            const int x = sg * 64 + __ffsll((long long)st) - 1;
-            st &= st - 1;
-            rxs[rb + sp] = (unsigned short)x; parent[rb + sp] = sp;
-            int* b = reinterpret_cast<int*>(box + rb + sp);
-            b[0] = x; b[2] = row; b[3] = row;
-            ++sp;
-        }
-        while (en) {
-            const int x = sg * 64 + __ffsll((long long)en) - 1;
-            en &= en - 1;
-            rxe[rb + ep] = (unsigned short)x;
-            reinterpret_cast<int*>(box + rb + ep)[1] = x;
-            ++ep;
-        }
-        sbase += __shfl(si, 63); ebase += __shfl(ei, 63);
-        carry = (u64)(unsigned)__shfl((int)(m >> 63), 63);
-    }
-}
-// 3: a run joins every run of the row above that it touches ([xs - 1, xe + 1] overlaps [xs', xe']).  Run ids grow in raster order and
-// the union keeps the smaller root, so a component's root is its first run
-__global__ __launch_bounds__(256) void mk_merge_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* parent, int H,
-                                                       size_t runcap, long long rows_total) {
-    ROW_WAVE_DECODE
-    if (row == 0) return;
-    const int* ro = runoff + (size_t)pg * (H + 1);
-    const int u0 = ro[row - 1], r0 = ro[row], r1 = ro[row + 1];
-    if (u0 == r0) return;
-    const size_t rb = (size_t)pg * runcap;
-    int* P = parent + rb;
-    for (int id = r0 + lane; id < r1; id += 64) {
-        const int xs = rxs[rb + id], xe = rxe[rb + id];
-        int lo = u0, hi = r0;   // first run of the row above with xe' + 1 >= xs
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if ((int)rxe[rb + mid] + 1 < xs) lo = mid + 1; else hi = mid; }
-        for (int t = lo; t < r0 && (int)rxs[rb + t] <= xe + 1; ++t) uf_union(P, id, t);
-    }
-}
 // 4: parent = root; the root's box grows to the component's.  The box only ever moves one way, so a value read before the atomic
 // that already covers this run makes the atomic unnecessary (most runs of a component lie inside what earlier ones reported)
 __global__ __launch_bounds__(256) void mk_accum_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* parent, int4* box, int H,
-                                                       size_t runcap, long long rows_total) {
-    ROW_WAVE_DECODE
+                                                       size_t runcap, int rows_total) {
+    int pg, row, lane;
+    if (!row_wave(H, rows_total, pg, row, lane)) return;
     const int* ro = runoff + (size_t)pg * (H + 1);
     const size_t rb = (size_t)pg * runcap;
     int* P = parent + rb;
@@ -175,8 +60,9 @@ __global__ __launch_bounds__(256) void mk_accum_kernel(const int* runoff, const 
 
 // 5: tmp [B][max_marks][9] = y0, x0, y1, x1, root, edge, ink_in, area_in, state
 __global__ __launch_bounds__(256) void mk_marks_kernel(const u64* mask, const int* runoff, const int* parent, const int4* box, int H, int nw, size_t runcap,
-                                                       int min_side, int max_side, int max_marks, int* counts, int* tmp, long long rows_total) {
-    ROW_WAVE_DECODE
+                                                       int min_side, int max_side, int max_marks, int* counts, int* tmp, int rows_total) {
+    int pg, row, lane;
+    if (!row_wave(H, rows_total, pg, row, lane)) return;
     const int* ro = runoff + (size_t)pg * (H + 1);
     const int r0 = ro[row], r1 = ro[row + 1];
     const size_t rb = (size_t)pg * runcap;
@@ -228,44 +114,26 @@ __global__ __launch_bounds__(256) void mk_marks_kernel(const u64* mask, const in
 // 6: the five key columns in LDS; roots are distinct, so ranks are
 __global__ __launch_bounds__(256) void mk_sort_kernel(const int* counts, const int* tmp, int* marks, int max_marks) {
     __shared__ int s_key[MARK_MAX_MARKS * 5];
-    const int pg = blockIdx.x, tid = threadIdx.x;
+    const int pg = blockIdx.x;
     const int n = counts[pg];
     if (n > max_marks) return;   // overflow: the count is all that is reported
     const int* t = tmp + (size_t)pg * max_marks * 9;
-    for (int i = tid; i < n * 5; i += 256) s_key[i] = t[(i / 5) * 9 + i % 5];
-    __syncthreads();
     int* out = marks + (size_t)pg * max_marks * 8;
-    for (int i = tid; i < n; i += 256) {
-        int k[5];
-#pragma unroll
-        for (int c = 0; c < 5; ++c) k[c] = s_key[i * 5 + c];
-        int rank = 0;
-        for (int j = 0; j < n; ++j) {
-            bool less = false, decided = false;
-#pragma unroll
-            for (int c = 0; c < 5; ++c) {
-                const int v = s_key[j * 5 + c];
-                if (!decided && v != k[c]) { less = v < k[c]; decided = true; }
-            }
-            rank += less ? 1 : 0;
-        }
+    rank_sort<5>(s_key, t, 9, n, [=](int i, int rank, const int (&k)[5]) {
         int* o = out + (size_t)rank * 8;
         o[0] = k[1]; o[1] = k[0]; o[2] = k[3]; o[3] = k[2];
         o[4] = t[i * 9 + 5]; o[5] = t[i * 9 + 6]; o[6] = t[i * 9 + 7]; o[7] = t[i * 9 + 8];
-    }
+    });
 }
 
 }  // namespace
-
-// worst case of a row: every other pixel starts a run
-static size_t marks_runcap(int H, int W) { return (size_t)H * ((W + 1) / 2); }
 
 // the workspace's regions: one layout sizes it (marks_workspace_bytes) and carves it (marks_launch)
 struct MarkWorkspace {
     unsigned long long* mask; int* runoff; unsigned short *rxs, *rxe; int* parent; int4* box; int* tmp;
 };
 static MarkWorkspace marks_layout(Arena& a, int B, int H, int W, int max_marks) {
-    const size_t runcap = marks_runcap(H, W), nw = (W + 63) / 64;
+    const size_t runcap = run_cap(H, W), nw = (W + 63) / 64;
     MarkWorkspace w;
     w.mask = a.take<unsigned long long>((size_t)B * H * nw);
     w.runoff = a.take<int>((size_t)B * (H + 1));   // run counts -> offsets
@@ -278,7 +146,7 @@ static MarkWorkspace marks_layout(Arena& a, int B, int H, int W, int max_marks) 
 
 static bool marks_args_ok(int B, int H, int W, int max_marks) {
     if (B <= 0 || H <= 0 || W <= 0 || H > 65535 || W > 65535 || max_marks < 1 || max_marks > MARK_MAX_MARKS) return false;
-    return (size_t)B * H < (1ull << 31) && marks_runcap(H, W) < (1ull << 31);
+    return (size_t)B * H < (1ull << 31) && run_cap(H, W) < (1ull << 31);
 }
 
 size_t marks_workspace_bytes(int B, int H, int W, int max_marks) {
@@ -296,21 +164,17 @@ hipError_t marks_launch(const MarkParams& p, void* workspace, size_t ws_bytes, h
     const MarkWorkspace w = marks_layout(a, B, H, W, p.max_marks);
     if (a.overflow) return hipErrorOutOfMemory;
     const int nw = (W + 63) / 64;
-    const size_t runcap = marks_runcap(H, W);
-    // the mask: given (mask_in; copied to the parity hook when that is asked for too), or computed here
-    const unsigned long long* mask = p.mask_in ? p.mask_in : (p.mask_out ? p.mask_out : w.mask);
-
+    const size_t runcap = run_cap(H, W);
+    const unsigned long long* mask;
     hipError_t e = hipMemsetAsync(p.counts, 0, sizeof(int) * (size_t)B, st);
     if (e != hipSuccess) return e;
-    if (!p.mask_in) e = table_mask_launch(p.rgb, p.mask_out ? p.mask_out : w.mask, B, H, W, p.threshold, st);
-    else if (p.mask_out) e = hipMemcpyAsync(p.mask_out, p.mask_in, sizeof(unsigned long long) * (size_t)B * H * nw, hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) return e;
-    const long long rows = (long long)B * H;
-    const dim3 grows((unsigned)((rows + 3) / 4));
-    hipLaunchKernelGGL(mk_count_kernel, grows, dim3(256), 0, st, mask, w.runoff, H, nw, rows);
-    hipLaunchKernelGGL(mk_scan_kernel, dim3(B), dim3(64), 0, st, w.runoff, H);
-    hipLaunchKernelGGL(mk_fill_kernel, grows, dim3(256), 0, st, mask, w.runoff, w.rxs, w.rxe, w.parent, w.box, H, nw, runcap, rows);
-    hipLaunchKernelGGL(mk_merge_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, H, runcap, rows);
+    if ((e = ink_mask_resolve(p.rgb, p.mask_in, p.mask_out, w.mask, B, H, W, p.threshold, st, &mask)) != hipSuccess) return e;
+    const int rows = B * H;
+    const dim3 grows = row_wave_grid(rows);
+    run_count_launch(mask, w.runoff, B, H, nw, st);
+    row_scan_launch(w.runoff, nullptr, B, H, st);
+    run_fill_launch(mask, w.runoff, w.rxs, w.rxe, w.parent, w.box, B, H, nw, runcap, st);
+    run_merge_launch(w.runoff, w.rxs, w.rxe, w.parent, B, H, runcap, st);
     hipLaunchKernelGGL(mk_accum_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.box, H, runcap, rows);
     hipLaunchKernelGGL(mk_marks_kernel, grows, dim3(256), 0, st, mask, w.runoff, w.parent, w.box, H, nw, runcap, p.min_side, p.max_side, p.max_marks,
                        p.counts, w.tmp, rows);

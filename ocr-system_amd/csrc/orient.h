@@ -7,7 +7,7 @@
 struct QuarterParams {
     const uint8_t* rgb;       // [B][H][W][3]
     int B, H, W;
-    int threshold;            // ink = L < threshold, L = Pillow's convert('L') (tb_mask)
+    int threshold;            // ink = L < threshold, L = Pillow's convert('L') (ink_mask, runs.hip)
     int ratio;                // sideways iff E_c > ratio * E_r
     long long* energies;      // device, [B][2] = E_r, E_c: sums of the squared differences of neighbouring row / column ink counts
     int* sideways;            // device, [B]: 0 / 1

@@ -3,7 +3,7 @@
 // tests/page_orient_reference.py.
 //
 // Sideways or not (quarter_launch), all stream-ordered, no host round trip:
-//   1 tb_mask / tb_transpose (tables.hip)   ink = L < threshold packed along x, and the same mask with x and y exchanged: the page
+//   1 ink_mask / ink_transpose (runs.hip)   ink = L < threshold packed along x, and the same mask with x and y exchanged: the page
 //                    bytes are read once, everything after works on 1/24 of them
 //   2 or_profile     ink count of every row (mask) and every column (transposed mask): 16 lanes per line, popcounts of its words
 //   3 or_energy      E = sum of (p[i + 1] - p[i])^2 per (page, direction) in 64 bits: wave sums, one atomic per wave
@@ -11,7 +11,7 @@
 // Turning (page_turn_launch): t = 0 / 2 keep the lines of a page, one thread per pixel; t = 1 / 3 exchange x and y: a 64 x 64 pixel
 // tile goes through LDS so that the reads and the writes are both whole 192-byte pieces of a line.
 #include "orient.h"
-#include "tables.h"
+#include "runs.h"
 
 namespace {
 
@@ -147,8 +147,8 @@ hipError_t quarter_launch(const QuarterParams& p, void* workspace, size_t ws_byt
     u64* energies = reinterpret_cast<u64*>(p.energies);
     hipError_t e = hipMemsetAsync(p.energies, 0, sizeof(long long) * 2 * (size_t)B, st);
     if (e != hipSuccess) return e;
-    if ((e = table_mask_launch(p.rgb, w.hmask, B, H, W, p.threshold, st)) != hipSuccess) return e;
-    if ((e = table_transpose_launch(w.hmask, w.vmask, B, H, W, st)) != hipSuccess) return e;
+    if ((e = ink_mask_launch(p.rgb, w.hmask, B, H, W, p.threshold, st)) != hipSuccess) return e;
+    if ((e = ink_transpose_launch(w.hmask, w.vmask, B, H, W, st)) != hipSuccess) return e;
     const long long lines = (long long)B * ((long long)H + W);
     hipLaunchKernelGGL(or_profile_kernel, dim3((unsigned)((lines + 15) / 16)), dim3(256), 0, st, w.hmask, w.vmask, w.prof, B, H, W, nw, nhw);
     const int longest = H > W ? H : W;

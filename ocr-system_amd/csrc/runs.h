@@ -1,0 +1,87 @@
+#pragma once
+#include "common.h"
+
+// What the page-analysis passes share (DB post-process, de-skew, tables, selection marks, page orientation): the lock-free
+// union-find, the ink mask of a page and its bit transpose, the run list of a batch of row masks with its 8-connected merge, and a
+// rank sort of a few integer key columns in LDS.  Device helpers are defined here; the kernels live in runs.hip behind the host
+// launchers below (every kernel of the library sits in the anonymous namespace of its own file).
+
+// ---- min-label union-find (parents only ever decrease: the root of a set is its smallest index); on LDS tiles and on pages ----
+__device__ __forceinline__ int uf_find(const int* L, int i) {
+    int p = L[i];
+    while (p != i) { i = p; p = L[i]; }
+    return i;
+}
+__device__ __forceinline__ void uf_union(int* L, int a, int b) {
+    bool done = false;
+    while (!done) {
+        a = uf_find(L, a); b = uf_find(L, b);
+        if (a < b) { const int old = atomicMin(&L[b], a); done = (old == b); b = old; }
+        else if (b < a) { const int old = atomicMin(&L[a], b); done = (old == a); a = old; }
+        else done = true;
+    }
+}
+
+// ---- one wave per (page, row), four rows per work-group (256 threads): false when the wave has no row ----
+__device__ __forceinline__ bool row_wave(int H, int rows_total, int& pg, int& row, int& lane) {
+    const int wrow = blockIdx.x * 4 + (threadIdx.x >> 6);
+    lane = threadIdx.x & 63;
+    if (wrow >= rows_total) return false;
+    row = wrow % H; pg = wrow / H;
+    return true;
+}
+inline dim3 row_wave_grid(int rows_total) { return dim3(((unsigned)rows_total + 3u) / 4u); }
+
+// bits of mask word m that start a run: ink whose left neighbour (prev = bit 63 of the word to the left) is not ink
+__device__ __forceinline__ unsigned long long run_starts(unsigned long long m, unsigned long long prev) { return m & ~((m << 1) | prev); }
+
+// ---- rank sort of n <= cap rows of NC integer key columns, by one 256-thread work-group: the keys (the first NC of every `stride`
+// ints of t) go to LDS (s_key, NC * cap ints), every row is ranked lexicographically against all others, and emit(i, rank, key)
+// writes it out.  Rows are distinct (the last column is an id), so ranks are. ----
+template <int NC, class Emit>
+__device__ __forceinline__ void rank_sort(int* s_key, const int* t, int stride, int n, Emit emit) {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < n * NC; i += 256) s_key[i] = t[(i / NC) * stride + i % NC];
+    __syncthreads();
+    for (int i = tid; i < n; i += 256) {
+        int k[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) k[c] = s_key[i * NC + c];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) {
+            bool less = false, decided = false;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const int v = s_key[j * NC + c];
+                if (!decided && v != k[c]) { less = v < k[c]; decided = true; }
+            }
+            rank += less ? 1 : 0;
+        }
+        emit(i, rank, k);
+    }
+}
+
+// ---- ink mask ----
+// ink = L < threshold (L = Pillow's convert('L')) packed into 64-bit words along x: [B][H][ceil(W / 64)], bit x % 64 of word x / 64
+hipError_t ink_mask_launch(const uint8_t* rgb, unsigned long long* mask, int B, int H, int W, int threshold, hipStream_t st);
+// the mask with x and y exchanged, [B][W][ceil(H / 64)]
+hipError_t ink_transpose_launch(const unsigned long long* hmask, unsigned long long* vmask, int B, int H, int W, hipStream_t st);
+// the mask a pass works on, returned in *mask: mask_in when given (copied to the parity hook mask_out when that is asked for too),
+// otherwise computed here into mask_out or, without a hook, into scratch
+hipError_t ink_mask_resolve(const uint8_t* rgb, const unsigned long long* mask_in, unsigned long long* mask_out, unsigned long long* scratch,
+                            int B, int H, int W, int threshold, hipStream_t st, const unsigned long long** mask);
+
+// ---- run list of a batch of row masks ([B][H][nw] words), page by page in raster order.  B * H < 2^31 and run_cap < 2^31 are the
+// caller's to check; runoff is [B][H + 1], rxs / rxe / parent / box are [B][runcap]. ----
+// worst case of a page: every other pixel of every row starts a run
+inline size_t run_cap(int H, int W) { return (size_t)H * ((W + 1) / 2); }
+// runs per row -> runcnt[pg][row] (for a mask that is already there; the DB post-process counts while it thresholds)
+void run_count_launch(const unsigned long long* mask, int* runcnt, int B, int H, int nw, hipStream_t st);
+// exclusive scan of every page's H row counts: cnt[pg][r] -> offset of row r, cnt[pg][H] = total (also -> total_out[pg] when given)
+void row_scan_launch(int* cnt, int* total_out, int B, int H, hipStream_t st);
+// masks -> runs [xs, xe] at the row's offset; a run is its own union-find parent and, when box is given, its own box (x0, x1, y0, y1)
+void run_fill_launch(const unsigned long long* mask, const int* runoff, unsigned short* rxs, unsigned short* rxe, int* parent, int4* box, int B,
+                     int H, int nw, size_t runcap, hipStream_t st);
+// union-find over run ids: a run joins every run of the row above that it touches (8-connectivity)
+void run_merge_launch(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* parent, int B, int H, size_t runcap,
+                      hipStream_t st);

@@ -15,13 +15,9 @@ struct TableParams {
     int* vrules;          // device, [B][max_rules][5], sorted by (x0, y0, x1, y1)
     int* counts;          // device, [B][2]: true number of horizontal / vertical rules (a list is not written when it overflows)
     unsigned long long* hmask_out;   // optional parity hook: ink mask [B][H][ceil(W / 64)], bit x % 64 of word x / 64
-    const unsigned long long* hmask_in;   // optional: the ink mask of these pages at this threshold, already computed (table_mask_launch)
+    const unsigned long long* hmask_in;   // optional: the ink mask of these pages at this threshold, already computed (ink_mask_launch, runs.h)
 };
 constexpr int TABLE_MAX_RULES = 2048;
 
 size_t table_workspace_bytes(int B, int H, int W, int gap, int min_len, int max_rules);
-// the ink mask alone, [B][H][ceil(W / 64)] (tb_mask): shared with the selection marks (marks.hip)
-hipError_t table_mask_launch(const uint8_t* rgb, unsigned long long* mask, int B, int H, int W, int threshold, hipStream_t st);
-// the mask with x and y exchanged, [B][W][ceil(H / 64)] (tb_transpose): shared with the page orientation (orient.hip)
-hipError_t table_transpose_launch(const unsigned long long* hmask, unsigned long long* vmask, int B, int H, int W, hipStream_t st);
 hipError_t table_rules_launch(const TableParams& p, void* workspace, size_t ws_bytes, hipStream_t st);

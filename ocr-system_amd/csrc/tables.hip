@@ -3,8 +3,8 @@
 // lists equal the sequential definition restated in tests/table_reference.py.
 //
 // All stream-ordered kernels, no host round trip:
-//   1 tb_mask        ink = L < threshold packed into 64-bit words along x, one wave ballot per 64 pixels (the page is read once)
-//   2 tb_transpose   the same mask with x and y exchanged (64 x 64 bit blocks, 64 ballots each): the vertical pass below is the
+//   1 ink_mask       (runs.hip) ink = L < threshold packed into 64-bit words along x, one wave ballot per 64 pixels (the page is read once)
+//   2 ink_transpose  (runs.hip) the same mask with x and y exchanged (64 x 64 bit blocks, 64 ballots each): the vertical pass below is the
 //                    horizontal pass on it.  From here on a "line" is a row (horizontal) or a column (vertical) and a "position"
 //                    runs along it; kernels 3-6 take both directions in one launch, one thread per line (a line holds few runs)
 //   3 tb_fill        maximal ink runs of the line, merged across gaps <= gap, kept when >= min_len long -> the line's slots.
@@ -16,25 +16,11 @@
 //   6 tb_select      roots that are rules (length >= min_len, area <= max_thick * length) -> counted, gathered in arrival order
 //   7 tb_sort        one work-group per (page, direction): rank sort by (line0, pos0, line1, pos1, area, slot) -> the output
 #include "tables.h"
+#include "runs.h"
 
 namespace {
 
 typedef unsigned long long u64;
-
-__device__ __forceinline__ int uf_find(const int* L, int i) {
-    int p = L[i];
-    while (p != i) { i = p; p = L[i]; }
-    return i;
-}
-__device__ __forceinline__ void uf_union(int* L, int a, int b) {
-    bool done = false;
-    while (!done) {
-        a = uf_find(L, a); b = uf_find(L, b);
-        if (a < b) { const int old = atomicMin(&L[b], a); done = (old == b); b = old; }
-        else if (b < a) { const int old = atomicMin(&L[a], b); done = (old == a); a = old; }
-        else done = true;
-    }
-}
 
 // one direction of the pass: R lines of C positions per page
 struct TDir {
@@ -57,49 +43,6 @@ struct TDirs { TDir d[2]; int B; };
     const long long lg = dir ? gid - nh : gid;                                \
     const int pg = (int)(lg / d.R), line = (int)(lg % d.R);                   \
     const size_t lb = (size_t)pg * d.R + line, sb = lb * d.cap, pb = (size_t)pg * d.R * d.cap;
-
-// 1: one wave per page row, four rows per work-group; four 64-pixel segments are requested at a time
-__global__ __launch_bounds__(256) void tb_mask_kernel(const uint8_t* rgb, u64* mask, int W, int nw, int threshold, long long rows_total) {
-    const long long wrow = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (wrow >= rows_total) return;
-    const uint8_t* rp = rgb + (size_t)wrow * W * 3;
-    u64* mrow = mask + (size_t)wrow * nw;
-    for (int s0 = 0; s0 < nw; s0 += 4) {
-        int l[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int x = (s0 + u) * 64 + lane;
-            const uint8_t* s = rp + (size_t)(x < W ? x : W - 1) * 3;
-            l[u] = (int)((19595u * s[0] + 38470u * s[1] + 7471u * s[2] + 0x8000u) >> 16);
-        }
-        u64 mine = 0;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const u64 m = __ballot((s0 + u) * 64 + lane < W && l[u] < threshold);
-            if (lane == u) mine = m;
-        }
-        if (lane < 4 && s0 + lane < nw) mrow[s0 + lane] = mine;
-    }
-}
-
-// 2: one wave per 64 x 64 bit block: lane r holds row r's word, ballot c is column c's word
-__global__ __launch_bounds__(256) void tb_transpose_kernel(const u64* hmask, u64* vmask, int H, int W, int nw, int nhw, long long blocks_total) {
-    const long long wb = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (wb >= blocks_total) return;
-    const int cb = (int)(wb % nw), rb = (int)((wb / nw) % nhw), pg = (int)(wb / ((long long)nw * nhw));
-    const int row = rb * 64 + lane;
-    const u64 w = row < H ? hmask[((size_t)pg * H + row) * nw + cb] : 0ull;
-    u64 mine = 0;
-#pragma unroll 8
-    for (int c = 0; c < 64; ++c) {
-        const u64 v = __ballot((w >> c) & 1ull);
-        if (lane == c) mine = v;
-    }
-    const int col = cb * 64 + lane;
-    if (col < W) vmask[((size_t)pg * W + col) * nhw + rb] = mine;
-}
 
 // 3
 struct RunAcc { int cs, ce, k; };
@@ -197,32 +140,16 @@ __global__ __launch_bounds__(256) void tb_select_kernel(TDirs D, int min_len, in
 // 7
 __global__ __launch_bounds__(256) void tb_sort_kernel(const int* counts, const int* tmp, int* hrules, int* vrules, int max_rules) {
     __shared__ int s_key[TABLE_MAX_RULES * 6];
-    const int pg = blockIdx.x >> 1, dir = blockIdx.x & 1, tid = threadIdx.x;
+    const int pg = blockIdx.x >> 1, dir = blockIdx.x & 1;
     const int n = counts[pg * 2 + dir];
     if (n > max_rules) return;   // overflow: the count is all that is reported
-    const int* t = tmp + ((size_t)pg * 2 + dir) * max_rules * 6;
-    for (int i = tid; i < n * 6; i += 256) s_key[i] = t[i];
-    __syncthreads();
     int* out = (dir ? vrules : hrules) + (size_t)pg * max_rules * 5;
-    for (int i = tid; i < n; i += 256) {
-        int k[6];
-#pragma unroll
-        for (int c = 0; c < 6; ++c) k[c] = s_key[i * 6 + c];
-        int rank = 0;
-        for (int j = 0; j < n; ++j) {
-            bool less = false, decided = false;
-#pragma unroll
-            for (int c = 0; c < 6; ++c) {
-                const int v = s_key[j * 6 + c];
-                if (!decided && v != k[c]) { less = v < k[c]; decided = true; }
-            }
-            rank += less ? 1 : 0;
-        }
+    rank_sort<6>(s_key, tmp + ((size_t)pg * 2 + dir) * max_rules * 6, 6, n, [=](int, int rank, const int (&k)[6]) {
         int* o = out + (size_t)rank * 5;
         if (dir == 0) { o[0] = k[1]; o[1] = k[0]; o[2] = k[3]; o[3] = k[2]; }   // line = y, position = x
         else          { o[0] = k[0]; o[1] = k[1]; o[2] = k[2]; o[3] = k[3]; }   // line = x, position = y
         o[4] = k[4];
-    }
+    });
 }
 
 }  // namespace
@@ -267,22 +194,6 @@ size_t table_workspace_bytes(int B, int H, int W, int gap, int min_len, int max_
     return a.off;
 }
 
-hipError_t table_mask_launch(const uint8_t* rgb, unsigned long long* mask, int B, int H, int W, int threshold, hipStream_t st) {
-    if (!rgb || !mask || B <= 0 || H <= 0 || W <= 0 || (size_t)B * H >= (1ull << 31)) return hipErrorInvalidValue;
-    const long long rows = (long long)B * H;
-    hipLaunchKernelGGL(tb_mask_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, rgb, mask, W, (W + 63) / 64, threshold, rows);
-    return hipGetLastError();
-}
-
-hipError_t table_transpose_launch(const unsigned long long* hmask, unsigned long long* vmask, int B, int H, int W, hipStream_t st) {
-    if (!hmask || !vmask || B <= 0 || H <= 0 || W <= 0) return hipErrorInvalidValue;
-    const int nw = (W + 63) / 64, nhw = (H + 63) / 64;
-    const long long blocks = (long long)B * nw * nhw;
-    if (blocks >= (1ll << 33)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(tb_transpose_kernel, dim3((unsigned)((blocks + 3) / 4)), dim3(256), 0, st, hmask, vmask, H, W, nw, nhw, blocks);
-    return hipGetLastError();
-}
-
 hipError_t table_rules_launch(const TableParams& p, void* workspace, size_t ws_bytes, hipStream_t st) {
     const int B = p.B, H = p.H, W = p.W;
     if (!table_args_ok(B, H, W, p.gap, p.min_len, p.max_rules) || p.max_thick < 0 || !p.rgb || !p.hrules || !p.vrules || !p.counts) return hipErrorInvalidValue;
@@ -290,15 +201,11 @@ hipError_t table_rules_launch(const TableParams& p, void* workspace, size_t ws_b
     const TableWorkspace w = table_layout(a, B, H, W, p.gap, p.min_len, p.max_rules);
     if (a.overflow) return hipErrorOutOfMemory;
     const int nw = (W + 63) / 64, nhw = (H + 63) / 64;
-    // the mask: given (hmask_in; copied to the parity hook when that is asked for too), or computed here
-    const unsigned long long* hmask = p.hmask_in ? p.hmask_in : (p.hmask_out ? p.hmask_out : w.hmask);
-
+    const unsigned long long* hmask;
     hipError_t e = hipMemsetAsync(p.counts, 0, sizeof(int) * 2 * (size_t)B, st);
     if (e != hipSuccess) return e;
-    if (!p.hmask_in) e = table_mask_launch(p.rgb, p.hmask_out ? p.hmask_out : w.hmask, B, H, W, p.threshold, st);
-    else if (p.hmask_out) e = hipMemcpyAsync(p.hmask_out, p.hmask_in, sizeof(unsigned long long) * (size_t)B * H * nw, hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) return e;
-    if ((e = table_transpose_launch(hmask, w.vmask, B, H, W, st)) != hipSuccess) return e;
+    if ((e = ink_mask_resolve(p.rgb, p.hmask_in, p.hmask_out, w.hmask, B, H, W, p.threshold, st, &hmask)) != hipSuccess) return e;
+    if ((e = ink_transpose_launch(hmask, w.vmask, B, H, W, st)) != hipSuccess) return e;
     TDirs D;
     D.B = B;
     for (int k = 0; k < 2; ++k) {
