@@ -34,6 +34,7 @@ typedef struct lumina_ocr lumina_ocr_t;
 #define LUMINA_REC_H 32
 #define LUMINA_REC_W 320
 #define LUMINA_REC_T 80
+#define LUMINA_MAX_WORDS 40 /* words of one line: 80 steps hold at most 40 characters with a space between each two */
 #define LUMINA_MAX_BOXES 1000 /* DB max_candidates; box buffers are [B][LUMINA_MAX_BOXES][8] */
 
 /* lifecycle — replaces OCRService._ensure_client_initialized (ocr_service.py:166-207) */
@@ -113,6 +114,30 @@ int lumina_ocr_rec_forward(lumina_ocr_t* h, const uint8_t* crops_dev, const int3
  * ocr_postprocessor.py:73-93 and the "confidence" key of ocr_service.py:298. */
 int lumina_ocr_ctc_decode(lumina_ocr_t* h, const int32_t* idx_dev, const float* prob_dev, int n, int32_t* text_dev, int32_t* len_dev,
                           float* score_dev, void* stream);
+
+/* lumina_ocr_ctc_decode + the words of every line, from the same pass over the CTC alignment (PaddleOCR's return_word_box; Azure's
+ * `word` entries with their own polygon and confidence, ocr_service.py:293-311).  text / len / score are bit-identical to
+ * lumina_ocr_ctc_decode.  Step t of the recogniser covers columns [4t, 4t + 4) of the line's crop.
+ *   kept character: a step t with idx[t] != 0 && idx[t] != idx[t-1]; its run ends at the last consecutive step with the same class.
+ *   word: a maximal run of kept characters whose class is not space_id — the non-empty pieces of text.split(" "), in text order;
+ *     space_id < 0: the whole line is one word (none when it is empty).  At most LUMINA_MAX_WORDS per line.
+ *   columns: c0 = min(4 * t_first, wc), c1 = max(min(4 * (run end of the last character + 1), wc), c0), wc = widths_dev[i], the crop's
+ *     valid width (lumina_ocr_rec_crop).  flip_dev (optional, the flags lumina_ocr_rec_crop_oriented took): a set flag means the crop
+ *     was turned, so the word covers the source columns [wc - c1, wc - c0).  A line with wc <= 0 has no words.
+ *   quad: the corners P0..P3 of quads_dev[i] in the order the crop used them (lumina_ocr_rec_crop rotates the corners by one when
+ *     4 * height^2 >= 9 * width^2 of the quad's longer sides: a vertical line); a column c maps to P0 + R((P1 - P0) * c / wc) on the
+ *     top edge and P3 + R((P2 - P3) * c / wc) on the bottom edge, per coordinate, in 64-bit integers, R = round half away from zero.
+ *     The four points are written in the line quad's own corner order: point k lies on the side of corner k of the line (TL, TR,
+ *     BR, BL for an unrotated line).
+ *   score: the fp32 sum, in time order, of the kept probabilities of the word's characters, divided by their count (the rule of
+ *     `score`).
+ * word_quads_dev int32 [n][LUMINA_MAX_WORDS][8]; word_span_dev int32 [n][LUMINA_MAX_WORDS][2] = index of the word's first character
+ * in text, character count; word_score_dev float [n][LUMINA_MAX_WORDS]; word_count_dev int32 [n]; rows past the count are left
+ * untouched.  No workspace.  Defined bit for bit (tests/word_reference.py).  Asynchronous; n == 0 is a no-op. */
+int lumina_ocr_ctc_decode_words(lumina_ocr_t* h, const int32_t* idx_dev, const float* prob_dev, int n, const int32_t* quads_dev,
+                                const int32_t* widths_dev, const int32_t* flip_dev /* may be NULL */, int space_id, int32_t* text_dev,
+                                int32_t* len_dev, float* score_dev, int32_t* word_quads_dev, int32_t* word_span_dev, float* word_score_dev,
+                                int32_t* word_count_dev, void* stream);
 
 /* Reference pre-processing on the device, byte-exact with the reference's PIL path:
  * resize_if_needed (image_preprocessing.py:81-110): 8-bit two-pass LANCZOS to (out_h, out_w); any channel count. */

@@ -254,6 +254,21 @@ int lumina_ocr_ctc_decode(lumina_ocr_t* h, const int32_t* idx_dev, const float* 
     return hip_rc(h, "ctc_decode", ctc_collapse_launch(idx_dev, prob_dev, text_dev, len_dev, score_dev, n, LUMINA_REC_T, (hipStream_t)stream));
 }
 
+int lumina_ocr_ctc_decode_words(lumina_ocr_t* h, const int32_t* idx_dev, const float* prob_dev, int n, const int32_t* quads_dev,
+                                const int32_t* widths_dev, const int32_t* flip_dev, int space_id, int32_t* text_dev, int32_t* len_dev,
+                                float* score_dev, int32_t* word_quads_dev, int32_t* word_span_dev, float* word_score_dev, int32_t* word_count_dev,
+                                void* stream) {
+    if (!h) return 1;
+    if (n <= 0) return 0;
+    if (!idx_dev || !prob_dev || !quads_dev || !widths_dev || !text_dev || !len_dev || !score_dev || !word_quads_dev || !word_span_dev ||
+        !word_score_dev || !word_count_dev)
+        return locr_fail(h, "ctc_decode_words", "null argument");
+    BIND(h);
+    return hip_rc(h, "ctc_decode_words", ctc_words_launch(idx_dev, prob_dev, quads_dev, widths_dev, flip_dev, space_id, text_dev, len_dev, score_dev,
+                                                          word_quads_dev, word_span_dev, word_score_dev, word_count_dev, n, LUMINA_REC_T,
+                                                          (hipStream_t)stream));
+}
+
 int lumina_ocr_conv2d(lumina_ocr_t* h, const uint16_t* x_dev, int n, int height, int width, int cin, const uint16_t* w_host,
                       const float* bias_host, int cout, int ks, int stride, int act, const uint16_t* res_dev, uint16_t* y_dev, void* stream) {
     if (!h || !x_dev || !w_host || !bias_host || !y_dev) return locr_fail(h, "conv2d", "null argument");

@@ -44,3 +44,9 @@ hipError_t cls_head_launch(const bf16_t* feat, const float* w, const float* b, i
 
 // CTC greedy collapse: idx/prob [N][T] -> text [N][T] (class indices, -1 padded), len [N], score [N]
 hipError_t ctc_collapse_launch(const int* idx, const float* prob, int* text, int* len, float* score, int N, int T, hipStream_t st);
+// The same collapse (text, len, score bit-identical) + the words of every line (include/lumina_ocr.h, lumina_ocr_ctc_decode_words):
+// quads int [N][8], widths int [N] (the crops' valid widths), flip int [N] or nullptr; word_quads int [N][LUMINA_MAX_WORDS][8],
+// word_span int [N][LUMINA_MAX_WORDS][2], word_score float [N][LUMINA_MAX_WORDS], word_count int [N]
+hipError_t ctc_words_launch(const int* idx, const float* prob, const int* quads, const int* widths, const int* flip, int space_id, int* text,
+                            int* len, float* score, int* word_quads, int* word_span, float* word_score, int* word_count, int N, int T,
+                            hipStream_t st);

@@ -1,6 +1,7 @@
 // Bandwidth-bound helper kernels (NHWC bf16), the LSTM recurrence and the CTC tail for gfx950.
 // No reference counterpart exists; semantics are defined by oracle/nets.py.
 #include "ops.h"
+#include "../../include/lumina_ocr.h"   // LUMINA_MAX_WORDS
 
 #include <type_traits>
 
@@ -370,9 +371,9 @@ __global__ __launch_bounds__(256, 2) void ctc_fc_argmax_kernel(const CtcFcParams
 }
 
 // ------------------------------------------------------------------ CTC greedy collapse (one wave per sequence)
-__global__ __launch_bounds__(64) void ctc_collapse_kernel(const int* idx, const float* prob, int* text, int* len, float* score, int T) {
-    __shared__ float kept_p[128];
-    const int n = blockIdx.x, lane = threadIdx.x;
+// The collapse of one row by one wave: kept classes -> text (-1 padded), kept probabilities -> kept_p (LDS, 128 floats), -> their count.
+// kept_t (LDS, optional): the step of every kept character.  Both kernels below run exactly this.
+__device__ __forceinline__ int ctc_collapse_row(const int* idx, const float* prob, int* text, float* kept_p, int* kept_t, int n, int T, int lane) {
     int base = 0;
     for (int t0 = 0; t0 < T; t0 += 64) {
         const int t = t0 + lane;
@@ -382,10 +383,20 @@ __global__ __launch_bounds__(64) void ctc_collapse_kernel(const int* idx, const 
         const bool keep = t < T && cur != 0 && cur != prev;
         const unsigned long long mask = __ballot(keep);
         const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
-        if (keep) { text[(size_t)n * T + pos] = cur; kept_p[pos] = prob[(size_t)n * T + t]; }
+        if (keep) {
+            text[(size_t)n * T + pos] = cur; kept_p[pos] = prob[(size_t)n * T + t];
+            if (kept_t) kept_t[pos] = t;
+        }
         base += __popcll(mask);
     }
     for (int t = base + lane; t < T; t += 64) text[(size_t)n * T + t] = -1;
+    return base;
+}
+
+__global__ __launch_bounds__(64) void ctc_collapse_kernel(const int* idx, const float* prob, int* text, int* len, float* score, int T) {
+    __shared__ float kept_p[128];
+    const int n = blockIdx.x, lane = threadIdx.x;
+    const int base = ctc_collapse_row(idx, prob, text, kept_p, nullptr, n, T, lane);
     __syncthreads();
     if (lane == 0) {
         float s = 0.f;
@@ -393,6 +404,75 @@ __global__ __launch_bounds__(64) void ctc_collapse_kernel(const int* idx, const 
         len[n] = base;
         score[n] = base ? s / (float)base : 0.f;
     }
+}
+
+// round-half-away-from-zero of a * c / wc (wc > 0, c >= 0): the one rounding rule of the word quads (include/lumina_ocr.h)
+__device__ __forceinline__ long long word_round_div(long long a, long long c, long long wc) {
+    const long long num = a * c, mag = ((num < 0 ? -num : num) * 2 + wc) / (2 * wc);
+    return num < 0 ? -mag : mag;
+}
+
+// ---- CTC collapse + the line's words (lumina_ocr_ctc_decode_words): one wave per line.  text / len / score as ctc_collapse_kernel;
+// a lane that holds the first character of a word walks the word: its end, its fp32 score in time order, its columns, its quad ----
+__global__ __launch_bounds__(64) void ctc_words_kernel(const int* idx, const float* prob, const int* quads, const int* widths, const int* flip,
+                                                       int space_id, int* text, int* len, float* score, int* word_quads, int* word_span,
+                                                       float* word_score, int* word_count, int T) {
+    __shared__ float kept_p[128];
+    __shared__ int kept_t[128];
+    const int n = blockIdx.x, lane = threadIdx.x;
+    const int base = ctc_collapse_row(idx, prob, text, kept_p, kept_t, n, T, lane);
+    __syncthreads();
+    if (lane == 0) {
+        float s = 0.f;
+        for (int k = 0; k < base; ++k) s = s + kept_p[k];
+        len[n] = base;
+        score[n] = base ? s / (float)base : 0.f;
+    }
+    const int* row = idx + (size_t)n * T;
+    const int wc = widths[n];
+    // the line quad's corners in the order the crop used them (crop_kernel, dbpost.hip: same test, same 64-bit integers)
+    long long p[4][2];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) { p[t][0] = quads[(size_t)n * 8 + 2 * t]; p[t][1] = quads[(size_t)n * 8 + 2 * t + 1]; }
+#define D2(a, b) ((p[a][0] - p[b][0]) * (p[a][0] - p[b][0]) + (p[a][1] - p[b][1]) * (p[a][1] - p[b][1]))
+    const long long cw2 = D2(1, 0) > D2(2, 3) ? D2(1, 0) : D2(2, 3);
+    const long long ch2 = D2(3, 0) > D2(2, 1) ? D2(3, 0) : D2(2, 1);
+#undef D2
+    const int rot = 4 * ch2 >= 9 * cw2 ? 1 : 0;   // crop corner k is line corner (k + rot) & 3
+    const bool turn = flip != nullptr && flip[n] != 0;
+    int nwords = 0;
+    for (int k0 = 0; k0 < base; k0 += 64) {
+        const int k = k0 + lane;
+        const bool inw = k < base && (space_id < 0 || row[kept_t[k]] != space_id);
+        const bool start = inw && (k == 0 || (space_id >= 0 && row[kept_t[k - 1]] == space_id));
+        const unsigned long long mask = __ballot(start);
+        const int w = nwords + __popcll(mask & ((1ull << lane) - 1ull));
+        nwords += __popcll(mask);
+        if (!start || w >= LUMINA_MAX_WORDS || wc <= 0) continue;   // (uniform trip count: the lanes meet again at the next ballot)
+        int e = k;   // last character of the word
+        float s = 0.f + kept_p[k];
+        while (e + 1 < base && (space_id < 0 || row[kept_t[e + 1]] != space_id)) { ++e; s = s + kept_p[e]; }
+        int te = kept_t[e];   // last step of the last character's run
+        const int cls = row[te];
+        while (te + 1 < T && row[te + 1] == cls) ++te;
+        int c0 = 4 * kept_t[k], c1 = 4 * (te + 1);
+        c0 = c0 < wc ? c0 : wc; c1 = c1 < wc ? c1 : wc; c1 = c1 > c0 ? c1 : c0;
+        const int s0 = turn ? wc - c1 : c0, s1 = turn ? wc - c0 : c1;
+        const int cs[4] = {s0, s1, s1, s0};   // crop corner k of the word: top edge P0 -> P1 at s0, s1; bottom edge P3 -> P2 at s1, s0
+        int* q = word_quads + ((size_t)n * LUMINA_MAX_WORDS + w) * 8;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int a = (c < 2 ? 0 : 3), b = (c < 2 ? 1 : 2);   // edge a -> b in crop corners
+            const long long ax = p[(a + rot) & 3][0], ay = p[(a + rot) & 3][1], bx = p[(b + rot) & 3][0], by = p[(b + rot) & 3][1];
+            const int j = (c + rot) & 3;   // the line's own corner on whose side this point lies
+            q[2 * j] = (int)(ax + word_round_div(bx - ax, cs[c], wc));
+            q[2 * j + 1] = (int)(ay + word_round_div(by - ay, cs[c], wc));
+        }
+        word_span[((size_t)n * LUMINA_MAX_WORDS + w) * 2] = k;
+        word_span[((size_t)n * LUMINA_MAX_WORDS + w) * 2 + 1] = e - k + 1;
+        word_score[(size_t)n * LUMINA_MAX_WORDS + w] = __fdiv_rn(s, (float)(e - k + 1));
+    }
+    if (lane == 0) word_count[n] = wc <= 0 ? 0 : (nwords < LUMINA_MAX_WORDS ? nwords : LUMINA_MAX_WORDS);
 }
 
 int grid_for(size_t total) {
@@ -502,6 +582,15 @@ hipError_t ctc_fc_argmax_launch(const CtcFcParams& p, hipStream_t st) {
 hipError_t ctc_collapse_launch(const int* idx, const float* prob, int* text, int* len, float* score, int N, int T, hipStream_t st) {
     if (T > 128) return hipErrorInvalidValue;
     hipLaunchKernelGGL(ctc_collapse_kernel, dim3(N), dim3(64), 0, st, idx, prob, text, len, score, T);
+    return hipGetLastError();
+}
+
+hipError_t ctc_words_launch(const int* idx, const float* prob, const int* quads, const int* widths, const int* flip, int space_id, int* text,
+                            int* len, float* score, int* word_quads, int* word_span, float* word_score, int* word_count, int N, int T,
+                            hipStream_t st) {
+    if (T > 128) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ctc_words_kernel, dim3(N), dim3(64), 0, st, idx, prob, quads, widths, flip, space_id, text, len, score, word_quads,
+                       word_span, word_score, word_count, T);
     return hipGetLastError();
 }
 

@@ -19,6 +19,7 @@ from . import arch
 _LIB_PATH = Path(__file__).resolve().parent.parent / "lib" / "liblumina_ocr.so"
 
 REC_H, REC_W, REC_T = 32, 320, 80
+MAX_WORDS = 40
 MAX_BOXES = 1000
 
 
@@ -63,6 +64,7 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_cls_forward": (i32, [vp, vp, vp, i32, f32, vp, vp, vp, vp]),
         "lumina_ocr_rec_forward": (i32, [vp, vp, vp, i32, vp, vp, vp]),
         "lumina_ocr_ctc_decode": (i32, [vp, vp, vp, i32, vp, vp, vp, vp]),
+        "lumina_ocr_ctc_decode_words": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "lumina_ocr_conv2d": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_read_tap": (i32, [vp, c.c_char_p, vp, sz, c.POINTER(i32)]),
         "lumina_ocr_conv_timing": (i32, [vp, c.POINTER(c.c_double), c.POINTER(c.c_double), c.POINTER(i32)]),
@@ -114,7 +116,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_load_det_weights", "lumina_ocr_load_rec_weights", "lumina_ocr_num_classes", "lumina_ocr_normalize",
     "lumina_ocr_det_forward", "lumina_ocr_det_postprocess", "lumina_ocr_rec_crop", "lumina_ocr_rec_crop_oriented", "lumina_ocr_cls_crop",
     "lumina_ocr_load_cls_weights", "lumina_ocr_cls_forward", "lumina_ocr_rec_forward",
-    "lumina_ocr_ctc_decode", "lumina_ocr_conv2d", "lumina_ocr_read_tap", "lumina_ocr_conv_timing", "lumina_ocr_conv_timing_detail",
+    "lumina_ocr_ctc_decode", "lumina_ocr_ctc_decode_words", "lumina_ocr_conv2d", "lumina_ocr_read_tap", "lumina_ocr_conv_timing", "lumina_ocr_conv_timing_detail",
     "lumina_ocr_resize_lanczos", "lumina_ocr_enhance", "lumina_ocr_jpeg_encode", "lumina_ocr_jpeg_coefficients", "lumina_ocr_jpeg_probe", "lumina_ocr_jpeg_decode", "lumina_ocr_jpeg_decode_async", "lumina_ocr_jpeg_last_passes",
     "lumina_ocr_png_probe", "lumina_ocr_png_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
@@ -404,6 +406,33 @@ class Engine:
             self._chk(self.lib.lumina_ocr_ctc_decode(self._h, _ptr(idx), _ptr(prob), n, _ptr(text), _ptr(length), _ptr(score),
                                                      self._stream()))
         return text, length, score
+
+    def ctc_decode_words(self, idx, prob, quads, widths, flip=None, space_id: int = -1):
+        """ctc_decode + the words of every line from the CTC alignment (lumina_ocr_ctc_decode_words; the definition is in the header).
+        quads int32 [n, 8] and widths int32 [n] are rec_crop's input and output, flip the flags it was given (or None), space_id the
+        class of " " (-1: none, every line is one word).  -> (text, length, score) exactly as ctc_decode, then word_quads int32
+        [n, 40, 8], word_spans int32 [n, 40, 2] (first character in text, count), word_scores float32 [n, 40], word_counts int32 [n];
+        rows past a line's count are zero.  Asynchronous."""
+        torch = _torch()
+        n = idx.shape[0]
+        dev = idx.device
+        for name, t, shape in (("quads", quads, (n, 8)), ("widths", widths, (n,))) + ((("flip", flip, (n,)),) if flip is not None else ()):
+            if t.dtype != torch.int32 or t.device != dev or tuple(t.shape) != shape:
+                raise ValueError("%s must be int32 %s on %s" % (name, list(shape), dev))
+        text = torch.empty((n, REC_T), dtype=torch.int32, device=dev)
+        length = torch.empty((n,), dtype=torch.int32, device=dev)
+        score = torch.empty((n,), dtype=torch.float32, device=dev)
+        wquads = torch.zeros((n, MAX_WORDS, 8), dtype=torch.int32, device=dev)
+        wspans = torch.zeros((n, MAX_WORDS, 2), dtype=torch.int32, device=dev)
+        wscores = torch.zeros((n, MAX_WORDS), dtype=torch.float32, device=dev)
+        wcounts = torch.zeros((n,), dtype=torch.int32, device=dev)
+        if n:
+            quads, widths = quads.contiguous(), widths.contiguous()
+            flip = None if flip is None else flip.contiguous()
+            self._chk(self.lib.lumina_ocr_ctc_decode_words(self._h, _ptr(idx), _ptr(prob), n, _ptr(quads), _ptr(widths), _ptr(flip), int(space_id),
+                                                           _ptr(text), _ptr(length), _ptr(score), _ptr(wquads), _ptr(wspans), _ptr(wscores),
+                                                           _ptr(wcounts), self._stream()))
+        return text, length, score, wquads, wspans, wscores, wcounts
 
     # -- kernel-level ---------------------------------------------------------------------
     def conv2d(self, x, w_ohwi_f32: np.ndarray, bias: np.ndarray, ks: int, stride: int, act: int = 0, res=None):

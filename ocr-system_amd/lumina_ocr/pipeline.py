@@ -37,11 +37,24 @@ class PageDetections:
     vrules: Optional[np.ndarray] = None       # int32 [nv, 5] vertical rules (both empty when a list overflowed its capacity)
     marks: Optional[np.ndarray] = None        # int32 [m, 8] x0, y0, x1, y1, edge, ink_in, area_in, state of the page's checkboxes:
                                               # OcrPipeline(marks=True) only (empty when the list overflowed its capacity)
+    word_quads: Optional[np.ndarray] = None   # int32 [n, 40, 8] the words of every line from the CTC alignment, each in its line's corner
+                                              # order: OcrPipeline(word_boxes=True) only, like the three below
+    word_spans: Optional[np.ndarray] = None   # int32 [n, 40, 2] first character in texts[i], character count
+    word_scores: Optional[np.ndarray] = None  # float32 [n, 40] mean max-prob of the word's characters
+    word_counts: Optional[np.ndarray] = None  # int32 [n] words of line i: the rows before it are valid
     turn: Optional[int] = None                # quarter turns that made the page upright, upright = np.rot90(input, turn); everything above
                                               # refers to the upright page: OcrPipeline(page_orient=True).run_oriented only
 
     def triples(self) -> List[Tuple[Sequence[int], str, float]]:
         return [(self.quads[i].tolist(), self.texts[i], float(self.scores[i])) for i in range(len(self.texts))]
+
+    def line_words(self) -> Optional[List[List[Tuple[int, int, List[int], float]]]]:
+        """Per line its words as (first character, count, quad 8 ints, score) in text order — utils/layout.build_layout_boxes' `words`;
+        None without OcrPipeline(word_boxes=True)."""
+        if self.word_counts is None:
+            return None
+        return [[(int(self.word_spans[i, k, 0]), int(self.word_spans[i, k, 1]), self.word_quads[i, k].tolist(), float(self.word_scores[i, k]))
+                 for k in range(int(self.word_counts[i]))] for i in range(len(self.texts))]
 
 
 @dataclass
@@ -58,13 +71,14 @@ class _Pending:
     gathered: Optional[object] = None   # multi-GPU: handle of dist.PageGather.submit (the batch's results of ALL ranks)
     rules_host: Optional[list] = None   # tables: pinned copies of hrules, vrules, counts
     marks_host: Optional[list] = None   # marks: pinned copies of marks, counts
+    words_host: Optional[list] = None   # word_boxes: pinned copies of word quads, spans, scores, counts
 
 
 class OcrPipeline:
     def __init__(self, engine: Engine, charset: Optional[List[str]] = None, max_dimension: int = 2000, post: Optional[dict] = None,
                  recognizer: str = "crnn", gather=None, angle_cls: bool = False, cls_thresh: float = arch.CLS_THRESH,
                  tables: bool = False, table_params: Optional[dict] = None, marks: bool = False, mark_params: Optional[dict] = None,
-                 page_orient: bool = False, page_orient_params: Optional[dict] = None):
+                 page_orient: bool = False, page_orient_params: Optional[dict] = None, word_boxes: bool = False):
         """recognizer: "crnn" (CRNN-MobileNetV3 + BiLSTM, engine.load_rec) or "svtr" (SVTR, engine.load_svtr).
         angle_cls: PaddleOCR's use_angle_cls — every line is classified 0 / 180 degrees (engine.load_cls) before recognition, and a line
         read as 180 with probability > cls_thresh is recognised turned; boxes and reading order are unchanged.  Per-line labels are
@@ -78,6 +92,10 @@ class OcrPipeline:
         parameters arch.PAGE_ORIENT_PARAMS or page_orient_params; the line classifier's majority for upside-down ones, so it needs
         engine.load_cls like angle_cls), turns the raw page on the device and runs the stages below on the upright page.  run /
         run_many / submit_* are the same with it on or off.  Not with a gather.
+        word_boxes: the words of every line come from the recogniser's CTC alignment (engine.ctc_decode_words instead of ctc_decode: same
+        texts and scores, plus PageDetections.word_quads / word_spans / word_scores / word_counts); it works with both recognisers, with
+        angle_cls and inside run_oriented, and adds no host synchronisation.  With a gather the words are not computed: like the table
+        rules they are not part of what travels between the ranks.
         gather: a dist.PageGather — multi-GPU runs: every batch's results are all-gathered from the device tensors and
         finish() returns a GatheredPages over the pages of ALL ranks instead of this rank's PageDetections."""
         assert recognizer in ("crnn", "svtr")
@@ -95,6 +113,8 @@ class OcrPipeline:
         self.marks = bool(marks)
         self.mark_params = dict(arch.MARK_PARAMS if mark_params is None else mark_params)
         self.page_orient = bool(page_orient)
+        self.word_boxes = bool(word_boxes)
+        self.space_id = self.charset.index(" ") if " " in self.charset else -1   # the class words split on (-1: a line is one word)
         self.page_orient_params = dict(arch.PAGE_ORIENT_PARAMS if page_orient_params is None else page_orient_params)
         if self.angle_cls and not engine.cls_loaded:
             raise ValueError("angle_cls needs the orientation classifier's weights (Engine.load_cls)")
@@ -198,12 +218,18 @@ class OcrPipeline:
             quads, det_sc, page_idx, cls = lines
         crops, widths = self.eng.rec_crop(processed, quads, page_idx, flip=None if cls is None else cls[2])
         idx, prob = (self.eng.svtr_forward if self.recognizer == "svtr" else self.eng.rec_forward)(crops, widths)
-        text, length, score = self.eng.ctc_decode(idx, prob)
+        words = None
+        if self.word_boxes and self.gather is None:
+            text, length, score, *words = self.eng.ctc_decode_words(idx, prob, quads, widths, None if cls is None else cls[2], self.space_id)
+        else:
+            text, length, score = self.eng.ctc_decode(idx, prob)
         if self.gather is not None:
             pend.gathered = self.gather.submit(counts_h, quads, det_sc, text, length, score)
             return pend
         outs = (text, length, score, quads, det_sc) + (() if cls is None else cls[:2])
         pend.host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in outs]
+        if words is not None:
+            pend.words_host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in words]
         pend.event = torch.cuda.Event()
         pend.event.record(torch.cuda.current_stream(processed.device))
         return pend
@@ -218,10 +244,15 @@ class OcrPipeline:
         rules = self._page_rules(pend)
         marks = self._page_marks(pend)
         if pend.n == 0:
+            nw = self._empty_words() if self.word_boxes else {}
             return [PageDetections(np.zeros((0, 8), np.int32), [], np.zeros(0, np.float32), np.zeros(0, np.float32), w, h,
-                                   hrules=rules[p][0], vrules=rules[p][1], marks=marks[p]) for p in range(b)], pend.processed
+                                   hrules=rules[p][0], vrules=rules[p][1], marks=marks[p], **nw) for p in range(b)], pend.processed
         text_h, len_h, score_h, quads_h, det_h, *cls_h = (t.numpy() for t in pend.host)
         all_texts = self._decoder.decode(text_h, len_h)
+        words_h = None
+        if pend.words_host is not None:
+            words_h = [t.numpy() for t in pend.words_host]
+            words_h[1] = self._string_spans(words_h[1], words_h[3], text_h)
         out, off = [], 0
         for p in range(b):
             c = int(pend.counts_h[p])
@@ -229,9 +260,32 @@ class OcrPipeline:
             out.append(PageDetections(quads_h[off:off + c], texts, score_h[off:off + c], det_h[off:off + c], w, h,
                                       text_h[off:off + c], len_h[off:off + c],
                                       *((cls_h[0][off:off + c], cls_h[1][off:off + c]) if cls_h else ()),
-                                      hrules=rules[p][0], vrules=rules[p][1], marks=marks[p]))
+                                      hrules=rules[p][0], vrules=rules[p][1], marks=marks[p],
+                                      **({} if words_h is None else dict(zip(self._WORD_FIELDS, (t[off:off + c] for t in words_h))))))
             off += c
         return out, pend.processed
+
+    _WORD_FIELDS = ("word_quads", "word_spans", "word_scores", "word_counts")
+
+    @staticmethod
+    def _empty_words() -> dict:
+        from .engine import MAX_WORDS
+        return dict(word_quads=np.zeros((0, MAX_WORDS, 8), np.int32), word_spans=np.zeros((0, MAX_WORDS, 2), np.int32),
+                    word_scores=np.zeros((0, MAX_WORDS), np.float32), word_counts=np.zeros(0, np.int32))
+
+    def _string_spans(self, spans: np.ndarray, counts: np.ndarray, text_ids: np.ndarray) -> np.ndarray:
+        """The device counts a word's span in classes; texts[i] is indexed in code points.  They are the same for a dictionary of single
+        code points (every PP-OCR key file); otherwise the spans are moved to code points here."""
+        if self._decoder.single:
+            return spans
+        width = np.array([len(c) for c in self.charset], np.int64)
+        out = spans.copy()
+        for i in np.nonzero(counts)[0]:
+            cum = np.concatenate([[0], np.cumsum(width[np.maximum(text_ids[i], 0)])])
+            for k in range(int(counts[i])):
+                a, n = int(spans[i, k, 0]), int(spans[i, k, 1])
+                out[i, k] = (cum[a], cum[a + n] - cum[a])
+        return out
 
     def _page_rules(self, pend: "_Pending"):
         """-> per page (hrules [nh,5], vrules [nv,5]) from the pending batch's host copies, or (None, None) without tables.  A page whose

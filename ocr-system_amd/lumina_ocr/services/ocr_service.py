@@ -136,6 +136,10 @@ class OCRService:
         # them (after decode and EXIF orientation, before the resize), and json_output reports page_rotation.  It uses the classifier
         # (LUMINA_OCR_CLS_WEIGHTS) whether or not LUMINA_OCR_USE_ANGLE_CLS is set.  Off by default: every output is then the one without it.
         self._use_page_orient = os.environ.get("LUMINA_OCR_PAGE_ORIENTATION", "0").lower() not in ("", "0", "false", "no")
+        # LUMINA_OCR_WORD_BOXES=1: every `word` entry takes its polygon and confidence from the recogniser's CTC alignment
+        # (lumina_ocr_ctc_decode_words) instead of a proportional split of its line and the line's score.  Contents, order and every other
+        # entry are the same.  Off by default: every output is then the one without it.
+        self._use_word_boxes = os.environ.get("LUMINA_OCR_WORD_BOXES", "0").lower() not in ("", "0", "false", "no")
         self._weights_kind = "unloaded"
         self._pre = ImagePreprocessor(self.max_dimension)
         self._initialized = True
@@ -199,7 +203,7 @@ class OCRService:
                                            % (len(charset), "SVTR" if svtr else "CRNN", n_cls))
                     pipeline = OcrPipeline(eng, charset=charset, max_dimension=self.max_dimension, post=post, recognizer=self._recognizer,
                                            angle_cls=self._use_angle_cls, tables=self._use_tables, marks=self._use_marks,
-                                           page_orient=self._use_page_orient)
+                                           page_orient=self._use_page_orient, word_boxes=self._use_word_boxes)
             except Exception:
                 eng.close()
                 raise
@@ -277,7 +281,13 @@ class OCRService:
         return out
 
     def _finish_page(self, det, jpeg: bytes, processed_hw, page_number: int, original_size, t0: float) -> OCROutput:
-        merged, ordered = layout.reading_order(det.triples())
+        triples = det.triples()
+        merged, ordered = layout.reading_order(triples)
+        words = None
+        line_words = det.line_words() if getattr(det, "word_counts", None) is not None else None   # LUMINA_OCR_WORD_BOXES=1
+        if line_words is not None:   # reading_order hands the same tuples back in another order: the words follow their lines
+            at = {id(t): i for i, t in enumerate(triples)}
+            words = [line_words[at[id(t)]] for t in ordered]
         tabs = []
         if det.hrules is not None:   # LUMINA_OCR_TABLES=1; table_index counts from 0 here, _number_tables makes it run over a document
             tabs = table_layout.find_tables(det.hrules, det.vrules, arch.TABLE_PARAMS["snap"])
@@ -289,7 +299,8 @@ class OCRService:
             md = layout.page_markdown(merged, tabs) if tabs else layout.page_markdown(merged)
         paragraphs = layout.build_paragraph_boxes(merged, page_number)
         # words, lines, selection marks, tables with their cells, paragraphs: the order of ocr_service.py:285-367
-        boxes = (layout.build_layout_boxes(ordered, page_number) + layout.build_mark_boxes(found or [], page_number)
+        boxes = ((layout.build_layout_boxes(ordered, page_number) if words is None else layout.build_layout_boxes(ordered, page_number, words=words))
+                 + layout.build_mark_boxes(found or [], page_number)
                  + layout.build_table_boxes(tabs, page_number) + paragraphs)
         counts = {"page_count": 1, "words_count": sum(1 for b in boxes if b["type"] == "word"), "lines_count": len(ordered),
                   "tables_count": len(tabs), "paragraphs_count": len(paragraphs)}
@@ -600,7 +611,7 @@ class OCRService:
     # ---- status (:759-795) ----
     def get_status(self) -> Dict[str, Any]:
         st = {"client_initialized": self._pipeline is not None, "model_id": "dbnet-r18vd+crnn-mv3", "max_dimension": self.max_dimension,
-              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
+              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
         if self._engine is not None:
             st["engine_version"] = self._engine.version()
             st["num_classes"] = self._engine.num_classes

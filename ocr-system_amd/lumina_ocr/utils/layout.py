@@ -6,7 +6,8 @@ Schema (stored verbatim in extractions.layout_data and consumed by BoundingBoxMa
   Units: pixels of the processed image (fixture page 2000.0 x 1090.0, :172-173), origin top-left, TL,TR,BR,BL.
 A det+rec engine yields line quads; `line` entries are mandatory for matching
 (/root/reference/backend/utils/bbox_matcher.py:47, :103-144) and `word` entries feed the union fallback
-(:48, :155-208), so words are synthesised by splitting the line text on spaces and interpolating along the quad.
+(:48, :155-208), so words are synthesised by splitting the line text on spaces and interpolating along the quad — or, with the
+provider's LUMINA_OCR_WORD_BOXES=1, taken from the recogniser's CTC alignment (build_layout_boxes(words=...)).
 """
 from __future__ import annotations
 
@@ -39,16 +40,28 @@ def split_words(quad: Sequence[float], text: str) -> List[Tuple[str, List[float]
     return out
 
 
-def build_layout_boxes(lines: Sequence[Tuple[Sequence[int], str, float]], page_number: int = 1) -> List[Dict[str, Any]]:
-    """lines: (quad 8 ints, text, score) in reading order -> words first, then lines (the order of ocr_service.py:285-311)."""
-    words: List[Dict[str, Any]] = []
+def build_layout_boxes(lines: Sequence[Tuple[Sequence[int], str, float]], page_number: int = 1,
+                       words: Optional[Sequence[Sequence[Tuple[int, int, Sequence[int], float]]]] = None) -> List[Dict[str, Any]]:
+    """lines: (quad 8 ints, text, score) in reading order -> words first, then lines (the order of ocr_service.py:285-311).
+    words: None, or for every entry of `lines` its words as the device found them in the CTC alignment (PageDetections.line_words):
+    (first character in the text, character count, quad 8 ints, confidence) in text order.  A line's `word` entries then take their
+    polygon and confidence from those rows and their content from that span of the text, instead of split_words' proportional guess
+    and the line's score.  Without `words` the result is the one without the argument."""
+    if words is not None and len(words) != len(lines):
+        raise ValueError("words must hold one list per line (%d lines, %d lists)" % (len(lines), len(words)))
+    word_boxes: List[Dict[str, Any]] = []
     line_boxes: List[Dict[str, Any]] = []
-    for quad, text, score in lines:
+    for i, (quad, text, score) in enumerate(lines):
         q = [float(v) for v in quad]
-        for w, wq in split_words(q, text):
-            words.append({"type": "word", "content": w, "confidence": float(score), "polygon": wq, "page_number": page_number})
+        if words is None:
+            for w, wq in split_words(q, text):
+                word_boxes.append({"type": "word", "content": w, "confidence": float(score), "polygon": wq, "page_number": page_number})
+        else:
+            for first, count, wq, conf in words[i]:
+                word_boxes.append({"type": "word", "content": text[int(first):int(first) + int(count)], "confidence": float(conf),
+                                   "polygon": [float(v) for v in wq], "page_number": page_number})
         line_boxes.append({"type": "line", "content": text, "polygon": q, "page_number": page_number})
-    return words + line_boxes
+    return word_boxes + line_boxes
 
 
 def build_paragraph_boxes(merged: Sequence[MergedLine], page_number: int = 1, gap_ratio: float = 0.7) -> List[Dict[str, Any]]:
