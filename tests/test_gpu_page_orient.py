@@ -1,9 +1,6 @@
 """GPU: the page orientation's device half (lumina_ocr_page_quarter / _page_turn / _page_vote) against tests/page_orient_reference.py and
 numpy, and OcrPipeline(page_orient=True).run_oriented on ruled synthetic pages with the hand-set text, code and orientation paths: the
-result of a page does not depend on which of the four ways it lies.
-
-Not yet run on a GPU: no MI355X could be had while this file was written (the restatement side of every precondition used here —
-line counts, votes and sideways flags of the pages — was checked on the CPU)."""
+result of a page does not depend on which of the four ways it lies."""
 import numpy as np
 import pytest
 import torch

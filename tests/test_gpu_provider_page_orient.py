@@ -1,9 +1,6 @@
 """GPU: page orientation through the provider (LUMINA_OCR_PAGE_ORIENTATION=1): a page gives the same boxes, Markdown and processed bytes
 whichever of the four ways it lies; sizes and page_rotation; tables and marks on turned pages; a document of mixed orientations; files
-decoded on the device; the option off.
-
-Not yet run on a GPU: no MI355X could be had while this file was written (the restatement side of every precondition used here —
-line counts, votes and sideways flags of the pages — was checked on the CPU)."""
+decoded on the device; the option off."""
 import io
 
 import numpy as np
