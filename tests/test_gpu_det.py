@@ -354,21 +354,127 @@ def test_db_postprocess_structured_maps(engine):
     assert total > 5
 
 
-def _post_vs_oracle(engine, prob, vh, vw):
+def _post_vs_oracle(engine, prob, vh, vw, counts_out=None, **params):
+    """params: det_postprocess's keywords (thresh, box_thresh, unclip_ratio, min_size, max_boxes), forwarded to the device and — max_boxes
+    as max_candidates — to the oracle.  -> total boxes; counts_out (a list) receives the oracle's count per page."""
     from oracle import dbpost
     bits = arch.f32_to_bf16_bits(prob)
     pd = torch.from_numpy(bits.view(np.int16)).cuda().view(torch.bfloat16)
-    boxes, scores, counts = engine.det_postprocess(pd, vh, vw)
+    boxes, scores, counts = engine.det_postprocess(pd, vh, vw, **params)
     torch.cuda.synchronize()
+    boxes, scores, counts = boxes.cpu().numpy(), scores.cpu().numpy(), counts.cpu().numpy()
+    oparams = {("max_candidates" if k == "max_boxes" else k): v for k, v in params.items()}
     total = 0
     for i in range(prob.shape[0]):
-        rb, rs, ncomp = dbpost.db_postprocess(bits[i], vh, vw)
+        rb, rs, ncomp = dbpost.db_postprocess(bits[i], vh, vw, **oparams)
         n = int(counts[i])
-        assert n == len(rb), (i, n, len(rb), ncomp)
-        assert np.array_equal(boxes[i, :n].cpu().numpy(), rb), i
-        assert np.array_equal(scores[i, :n].cpu().numpy(), rs), i
+        assert n == len(rb), (i, n, len(rb), ncomp, params)
+        assert np.array_equal(boxes[i, :n], rb), (i, params)
+        assert np.array_equal(scores[i, :n], rs), (i, params)
+        assert not boxes[i, n:].any() and not scores[i, n:].any(), (i, params)      # rows past the count are zero
+        if counts_out is not None:
+            counts_out.append(n)
         total += n
     return total
+
+
+def _bar(p, y0, rows, x0, width, value, slant=0.0):
+    """rows x width pixels of `value` from row y0, the left edge moving right by `slant` pixels per row"""
+    for r in range(rows):
+        x = x0 + int(r * slant)
+        p[y0 + r, x:x + width] = value
+
+
+def _tall_maps():
+    """[2, 2112, 96]: page 0 an upright bar of 2100 rows (global hull path), a slanted one of 2079 (global, hull edges that are not axis-
+    aligned) and an upright one of exactly 2048 (the last LDS case); page 1 a bar of 2049 rows (the first global case) next to short blobs"""
+    p = np.zeros((2, 2112, 96), np.float32)
+    _bar(p[0], 4, 2100, 4, 6, 0.9)
+    _bar(p[0], 10, 2079, 20, 5, 0.8, slant=30.0 / 2079)
+    _bar(p[0], 30, 2048, 70, 7, 0.95)
+    for k in range(6):
+        p[1, 40 + 300 * k:52 + 300 * k, 6:36] = 0.7 + 0.04 * k
+    _bar(p[1], 20, 2049, 50, 6, 0.85)
+    p[1, 2080:2100, 70:90] = 0.9
+    return p
+
+
+@pytest.mark.parametrize("post", ["default", "text_path"])
+def test_db_postprocess_tall_components(engine, post):
+    """Components taller than HULL_LDS / 2 = 2048 rows: comp_box_kernel builds their hull in the global scratch (at the page's offset) and
+    reads the row extremes from global memory; 2048 rows is the last height that stays in LDS.  Both paths and a second page in one launch."""
+    hp, wp = 2112, 96
+    params = {} if post == "default" else dict(arch.TEXT_PATH_POST)
+    per_page = []
+    total = _post_vs_oracle(engine, _tall_maps(), hp, wp, counts_out=per_page, **params)
+    assert per_page == [3, 8] and total == 11, per_page
+
+
+def _parameter_maps(seed=17):
+    """[2, 256, 320] built like test_db_postprocess_structured_maps: noise floor below 0.25, rotated bars with values drawn from 0.5 .. 1.0;
+    shorter and thinner bars (down to 3 pixels across, which only survive with an unclip margin), and more of them"""
+    rng = np.random.default_rng(seed)
+    hp, wp = 256, 320
+    yy, xx = np.mgrid[0:hp, 0:wp]
+    maps = []
+    for k in range(2):
+        p = rng.random((hp, wp), dtype=np.float32) * 0.25
+        for _ in range(24):
+            cx, cy = rng.uniform(0, wp), rng.uniform(0, hp)
+            ang = rng.uniform(-1.5, 1.5)
+            hl, hw = rng.uniform(8, 50), rng.uniform(1.5, 9)
+            u = (xx - cx) * np.cos(ang) + (yy - cy) * np.sin(ang)
+            v = -(xx - cx) * np.sin(ang) + (yy - cy) * np.cos(ang)
+            p[(np.abs(u) < hl) & (np.abs(v) < hw)] = rng.uniform(0.5, 1.0)
+        maps.append(p)
+    return np.stack(maps)
+
+
+PARAMETER_VALUES = dict(thresh=[0.1, 0.55, 0.85], box_thresh=[0.0, 0.75, 0.99], unclip_ratio=[0.0, 0.35, 4.0], min_size=[1, 8, 13],
+                        max_boxes=[1, 2, 7, 64])
+
+
+def test_db_postprocess_parameters(engine):
+    """Every parameter of det_postprocess away from its default, one at a time, on maps whose bars carry values between 0.5 and 1.0 (so
+    the thresholds bite) and reach past the valid region 250 x 310 of the 256 x 320 map (so unclip_ratio 4.0 meets the clamp to the
+    valid size and the components are cut at the valid border).  Each parameter must be seen to act: for at least one of its values
+    the oracle's box count differs from the count under the defaults."""
+    prob = _parameter_maps()
+    vh, vw = 250, 310
+    assert (prob[:, vh:, :] > 0.5).any() and (prob[:, :, vw:] > 0.5).any()          # ink beyond the valid border: the cut is in play
+    base = []
+    _post_vs_oracle(engine, prob, vh, vw, counts_out=base)
+    assert min(base) > 7, base                                                      # more candidates than the caps 1, 2 and 7
+    for name, values in PARAMETER_VALUES.items():
+        acted = False
+        for v in values:
+            got = []
+            _post_vs_oracle(engine, prob, vh, vw, counts_out=got, **{name: v})
+            acted = acted or got != base
+            if name == "max_boxes":
+                assert all(n <= v for n in got), (v, got)
+        assert acted, (name, base)
+    # unclip_ratio 4.0: some corner really sits on the clamp
+    from oracle import dbpost
+    rb, _, _ = dbpost.db_postprocess(arch.f32_to_bf16_bits(prob)[0], vh, vw, unclip_ratio=4.0)
+    assert ((rb[:, 0::2] == vw) | (rb[:, 1::2] == vh)).any() and (rb == 0).any()
+
+
+@pytest.mark.parametrize("value", [0.75, 0.5])
+def test_db_postprocess_score_at_the_threshold(engine, value):
+    """Axis-aligned blobs whose pixels all hold one value that is exact in bf16: the fixed-point mean is exactly that value.  comp_box_kernel
+    drops a box when score < box_thresh, so box_thresh == value keeps the blobs and the next float32 above it drops them."""
+    hp, wp = 64, 96
+    p = np.zeros((1, hp, wp), np.float32)
+    p[0, 8:20, 10:50] = value
+    p[0, 30:50, 60:90] = value
+    p[0, 40:52, 5:30] = 0.875                     # (a blob well above either threshold: the result is never empty)
+    assert np.array_equal(arch.bf16_bits_to_f32(arch.f32_to_bf16_bits(p)), p)
+    above = float(np.nextafter(np.float32(value), np.float32(1.0)))
+    kept, dropped = [], []
+    _post_vs_oracle(engine, p, hp, wp, counts_out=kept, thresh=0.3, box_thresh=value)
+    _post_vs_oracle(engine, p, hp, wp, counts_out=dropped, thresh=0.3, box_thresh=above)
+    assert kept == [3] and dropped == [1], (kept, dropped)
 
 
 def test_db_postprocess_run_list_edge_cases(engine):
