@@ -215,6 +215,31 @@ int lumina_ocr_rules_and_marks(lumina_ocr_t* h, const uint8_t* pages_dev, int n,
                                int max_thick, int max_rules, int32_t* hrules_dev, int32_t* vrules_dev, int32_t* rule_counts_dev, int min_side,
                                int max_side, int max_marks, int32_t* marks_dev, int32_t* mark_counts_dev, void* stream);
 
+/* lumina_ocr_selection_marks plus the ROUND selection marks (radio buttons) of the same pages, in a second list of the same format,
+ * order and capacity (round_dev int32 [n][max_marks][8], round_counts_dev int32 [n]; the host half is lumina_ocr/utils/marks.py).  The
+ * checkbox outputs are those of lumina_ocr_selection_marks, bit for bit.  A candidate (as above) that passes the frame test is a
+ * checkbox and never a round mark: the lists are disjoint.  Any other candidate is read in doubled coordinates about the centre of its
+ * box: u = 2 x - (x0 + x1), v = 2 y - (y0 + y1), q = u^2 + v^2, D = max(w, h), T = 1 + D / ring_div.  Zones: outside q > (D + 1)^2; core
+ * q <= D^2 / 4; ring zone inner < q <= (D + 1)^2 with inner = max((max(D - 2 T, 0))^2, D^2 / 4); moat = what lies between core and ring
+ * zone.  It is a round mark when at most out_max ink pixels of the box lie outside; the ink of the ring zone covers top, bottom >=
+ * w - w / 8 columns in the rows with v <= 0 / v >= 0 and left, right >= h - h / 8 rows in the columns with u <= 0 / u >= 0; the moat
+ * holds no ink; and the band of band_min + min(w, h) / band_div pixels around the box, clipped to the page, holds no ink (what keeps
+ * letters out: a glyph inside a word has a neighbour nearer than that).  Row: x0, y0, x1, y1, top + bottom + left + right, ink_in (the
+ * ink of the core), area_in (the pixels of the core), state = 1 when 16 ink_in >= area_in.  out_max >= 0, ring_div >= 1, band_div >= 4,
+ * 0 <= band_min <= 16 (the band is at most 32 pixels); defaults in lumina_ocr/arch.py ROUND_MARK_PARAMS.  Integer arithmetic
+ * throughout (tests/radio_reference.py).  Asynchronous; n == 0 is a no-op; bad arguments return a status before anything is written. */
+int lumina_ocr_selection_marks_round(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_side,
+                                     int max_side, int max_marks, int32_t* marks_dev, int32_t* counts_dev, uint64_t* mask_dev, int out_max,
+                                     int ring_div, int band_div, int band_min, int32_t* round_dev, int32_t* round_counts_dev, void* stream);
+
+/* lumina_ocr_rules_and_marks with the round marks as well: one ink mask for the rules, the checkboxes and the round marks.  Every
+ * output equals that of lumina_ocr_table_rules and lumina_ocr_selection_marks_round made one after the other. */
+int lumina_ocr_rules_and_marks_round(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int gap,
+                                     int min_len, int max_thick, int max_rules, int32_t* hrules_dev, int32_t* vrules_dev,
+                                     int32_t* rule_counts_dev, int min_side, int max_side, int max_marks, int32_t* marks_dev,
+                                     int32_t* mark_counts_dev, int out_max, int ring_div, int band_div, int band_min, int32_t* round_dev,
+                                     int32_t* round_counts_dev, void* stream);
+
 /* ---- page orientation (optional; DESIGN.md: "Page orientation") ----
  * A page is upright after `turn` quarter turns: upright = np.rot90(page, turn) (counter-clockwise).  The three entries below are the
  * device half; which pages get which turn is decided on the host (lumina_ocr/utils/page_orient.py, OcrPipeline.run_oriented).

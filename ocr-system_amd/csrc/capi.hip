@@ -573,42 +573,54 @@ int lumina_ocr_table_rules(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int
     API_CATCH(h)
 }
 
-int lumina_ocr_selection_marks(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_side, int max_side,
-                               int max_marks, int32_t* marks_dev, int32_t* counts_dev, uint64_t* mask_dev, void* stream) {
+// the round marks' parameters (marks.h: the band is at most 32 pixels, one lane per band row)
+static const char* const ROUND_BAD_ARGS = "round parameters must satisfy out_max >= 0, ring_div >= 1, band_div >= 4, 0 <= band_min <= 16";
+
+// selection_marks, and with round_dev / round_counts_dev the round marks (radio buttons) of the same components in a second list.
+// Without them the pass, its workspace and its rows are the checkboxes' alone
+static int selection_marks_impl(lumina_ocr_t* h, const char* what, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_side, int max_side,
+                               int max_marks, int32_t* marks_dev, int32_t* counts_dev, uint64_t* mask_dev, int out_max, int ring_div, int band_div,
+                                     int band_min, int32_t* round_dev, int32_t* round_counts_dev, void* stream) {
     if (!h) return 1;
     if (n == 0) return 0;
-    if (!pages_dev || !marks_dev || !counts_dev || n < 0) return locr_fail(h, "selection_marks", "bad arguments");
-    if (const char* why = marks_bad_args(height, width, min_side, max_side, max_marks)) return locr_fail(h, "selection_marks", why);
+    if (!pages_dev || !marks_dev || !counts_dev || (round_dev == nullptr) != (round_counts_dev == nullptr) || n < 0) return locr_fail(h, what, "bad arguments");
+    if (const char* why = marks_bad_args(height, width, min_side, max_side, max_marks)) return locr_fail(h, what, why);
+    if (round_dev && !round_params_ok(out_max, ring_div, band_div, band_min)) return locr_fail(h, what, ROUND_BAD_ARGS);
     BIND(h);
     API_TRY
     // the run list is sized for its worst case (24 bytes per two pixels)
-    const auto ws = [&](int nb) { return marks_workspace_bytes(nb, height, width, max_marks); };
+    const auto ws = [&](int nb) { return marks_workspace_bytes(nb, height, width, max_marks, round_dev != nullptr); };
     const size_t nw = ((size_t)width + 63) / 64;
     return for_page_groups(h, n, fit_group(h->post_group, n, ws), ws, [&](int b0, int nb) {
         MarkParams p{};
         p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.H = height; p.W = width;
         p.threshold = threshold; p.min_side = min_side; p.max_side = max_side; p.max_marks = max_marks;
         p.marks = marks_dev + (size_t)b0 * max_marks * 8; p.counts = counts_dev + b0;
+        if (round_dev) { p.rounds = round_dev + (size_t)b0 * max_marks * 8; p.round_counts = round_counts_dev + b0; }
+        p.out_max = out_max; p.ring_div = ring_div; p.band_div = band_div; p.band_min = band_min;
         p.mask_out = mask_dev ? reinterpret_cast<unsigned long long*>(mask_dev) + (size_t)b0 * height * nw : nullptr;
-        return hip_rc(h, "selection_marks", marks_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
+        return hip_rc(h, what, marks_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
     });
     API_CATCH(h)
 }
 
-int lumina_ocr_rules_and_marks(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int gap, int min_len,
+// rules_and_marks, with or without the round marks: one ink mask for all of them
+static int rules_and_marks_impl(lumina_ocr_t* h, const char* what, const uint8_t* pages_dev, int n, int height, int width, int threshold, int gap, int min_len,
                                int max_thick, int max_rules, int32_t* hrules_dev, int32_t* vrules_dev, int32_t* rule_counts_dev, int min_side,
-                               int max_side, int max_marks, int32_t* marks_dev, int32_t* mark_counts_dev, void* stream) {
+                               int max_side, int max_marks, int32_t* marks_dev, int32_t* mark_counts_dev, int out_max, int ring_div, int band_div,
+                                     int band_min, int32_t* round_dev, int32_t* round_counts_dev, void* stream) {
     if (!h) return 1;
     if (n == 0) return 0;
-    if (!pages_dev || !hrules_dev || !vrules_dev || !rule_counts_dev || !marks_dev || !mark_counts_dev || n < 0) return locr_fail(h, "rules_and_marks", "bad arguments");
-    if (const char* why = tables_bad_args(height, width, gap, min_len, max_thick, max_rules, true)) return locr_fail(h, "rules_and_marks", why);
-    if (const char* why = marks_bad_args(height, width, min_side, max_side, max_marks)) return locr_fail(h, "rules_and_marks", why);
+    if (!pages_dev || !hrules_dev || !vrules_dev || !rule_counts_dev || !marks_dev || !mark_counts_dev || (round_dev == nullptr) != (round_counts_dev == nullptr) || n < 0) return locr_fail(h, what, "bad arguments");
+    if (const char* why = tables_bad_args(height, width, gap, min_len, max_thick, max_rules, true)) return locr_fail(h, what, why);
+    if (const char* why = marks_bad_args(height, width, min_side, max_side, max_marks)) return locr_fail(h, what, why);
+    if (round_dev && !round_params_ok(out_max, ring_div, band_div, band_min)) return locr_fail(h, what, ROUND_BAD_ARGS);
     BIND(h);
     API_TRY
     // one group size for both (the marks limit, then the tables limit); the workspace is the group's mask, then room for the larger of
     // the two passes (they run one after the other on the stream)
     const auto wt = [&](int nb) { return table_workspace_bytes(nb, height, width, gap, min_len, max_rules); };
-    const auto wm = [&](int nb) { return marks_workspace_bytes(nb, height, width, max_marks); };
+    const auto wm = [&](int nb) { return marks_workspace_bytes(nb, height, width, max_marks, round_dev != nullptr); };
     const size_t nw = ((size_t)width + 63) / 64;
     const auto rest_bytes = [&](int nb) { return wt(nb) > wm(nb) ? wt(nb) : wm(nb); };
     const auto ws = [&](int nb) {
@@ -623,20 +635,53 @@ int lumina_ocr_rules_and_marks(lumina_ocr_t* h, const uint8_t* pages_dev, int n,
         Arena a(h->ws.get(), h->ws.cap);
         unsigned long long* mask = a.take<unsigned long long>((size_t)nb * height * nw);
         uint8_t* rest = a.take<uint8_t>(bytes);
-        if (a.overflow) return locr_fail(h, "rules_and_marks", "workspace");
+        if (a.overflow) return locr_fail(h, what, "workspace");
         const uint8_t* rgb = pages_dev + (size_t)b0 * height * width * 3;
-        if (hip_rc(h, "rules_and_marks", ink_mask_launch(rgb, mask, nb, height, width, threshold, st))) return 1;
+        if (hip_rc(h, what, ink_mask_launch(rgb, mask, nb, height, width, threshold, st))) return 1;
         TableParams t{};
         t.rgb = rgb; t.B = nb; t.H = height; t.W = width; t.threshold = threshold; t.gap = gap; t.min_len = min_len; t.max_thick = max_thick;
         t.max_rules = max_rules; t.hrules = hrules_dev + (size_t)b0 * max_rules * 5; t.vrules = vrules_dev + (size_t)b0 * max_rules * 5;
         t.counts = rule_counts_dev + (size_t)b0 * 2; t.hmask_in = mask;
-        if (hip_rc(h, "rules_and_marks", table_rules_launch(t, rest, bytes, st))) return 1;
+        if (hip_rc(h, what, table_rules_launch(t, rest, bytes, st))) return 1;
         MarkParams p{};
         p.rgb = rgb; p.B = nb; p.H = height; p.W = width; p.threshold = threshold; p.min_side = min_side; p.max_side = max_side; p.max_marks = max_marks;
         p.marks = marks_dev + (size_t)b0 * max_marks * 8; p.counts = mark_counts_dev + b0; p.mask_in = mask;
-        return hip_rc(h, "rules_and_marks", marks_launch(p, rest, bytes, st));
+        if (round_dev) { p.rounds = round_dev + (size_t)b0 * max_marks * 8; p.round_counts = round_counts_dev + b0; }
+        p.out_max = out_max; p.ring_div = ring_div; p.band_div = band_div; p.band_min = band_min;
+        return hip_rc(h, what, marks_launch(p, rest, bytes, st));
     });
     API_CATCH(h)
+}
+
+int lumina_ocr_selection_marks(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_side, int max_side,
+                               int max_marks, int32_t* marks_dev, int32_t* counts_dev, uint64_t* mask_dev, void* stream) {
+    return selection_marks_impl(h, "selection_marks", pages_dev, n, height, width, threshold, min_side, max_side, max_marks, marks_dev, counts_dev, mask_dev,
+                                0, 0, 0, 0, nullptr, nullptr, stream);
+}
+
+int lumina_ocr_selection_marks_round(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_side, int max_side,
+                                     int max_marks, int32_t* marks_dev, int32_t* counts_dev, uint64_t* mask_dev, int out_max, int ring_div, int band_div,
+                                     int band_min, int32_t* round_dev, int32_t* round_counts_dev, void* stream) {
+    if (h && n != 0 && (!round_dev || !round_counts_dev)) return locr_fail(h, "selection_marks_round", "bad arguments");
+    return selection_marks_impl(h, "selection_marks_round", pages_dev, n, height, width, threshold, min_side, max_side, max_marks, marks_dev, counts_dev,
+                                mask_dev, out_max, ring_div, band_div, band_min, round_dev, round_counts_dev, stream);
+}
+
+int lumina_ocr_rules_and_marks(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int gap, int min_len,
+                               int max_thick, int max_rules, int32_t* hrules_dev, int32_t* vrules_dev, int32_t* rule_counts_dev, int min_side,
+                               int max_side, int max_marks, int32_t* marks_dev, int32_t* mark_counts_dev, void* stream) {
+    return rules_and_marks_impl(h, "rules_and_marks", pages_dev, n, height, width, threshold, gap, min_len, max_thick, max_rules, hrules_dev, vrules_dev,
+                                rule_counts_dev, min_side, max_side, max_marks, marks_dev, mark_counts_dev, 0, 0, 0, 0, nullptr, nullptr, stream);
+}
+
+int lumina_ocr_rules_and_marks_round(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int gap, int min_len,
+                                     int max_thick, int max_rules, int32_t* hrules_dev, int32_t* vrules_dev, int32_t* rule_counts_dev, int min_side,
+                                     int max_side, int max_marks, int32_t* marks_dev, int32_t* mark_counts_dev, int out_max, int ring_div, int band_div,
+                                     int band_min, int32_t* round_dev, int32_t* round_counts_dev, void* stream) {
+    if (h && n != 0 && (!round_dev || !round_counts_dev)) return locr_fail(h, "rules_and_marks_round", "bad arguments");
+    return rules_and_marks_impl(h, "rules_and_marks_round", pages_dev, n, height, width, threshold, gap, min_len, max_thick, max_rules, hrules_dev,
+                                vrules_dev, rule_counts_dev, min_side, max_side, max_marks, marks_dev, mark_counts_dev, out_max, ring_div, band_div, band_min,
+                                round_dev, round_counts_dev, stream);
 }
 
 size_t lumina_ocr_page_quarter_workspace_bytes(int n, int height, int width) { return n > 0 ? quarter_workspace_bytes(n, height, width) : 0; }

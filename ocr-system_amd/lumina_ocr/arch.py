@@ -458,6 +458,14 @@ TABLE_PARAMS = dict(threshold=128, gap=2, min_len=64, max_thick=12, max_rules=51
 # row of a box); max_marks = capacity of a page's list.
 MARK_PARAMS = dict(threshold=128, min_side=12, max_side=64, max_marks=256)
 
+# Round selection marks (radio buttons; lumina_ocr_selection_marks_round, definition restated in tests/radio_reference.py): a candidate
+# of the checkboxes that is no frame, read in doubled coordinates about the centre of its box (u = 2x - (x0 + x1), v = 2y - (y0 + y1),
+# q = u^2 + v^2, D = max(w, h)).  At most out_max ink pixels lie beyond the outer circle q <= (D + 1)^2; the ring zone
+# (D - 2T)^2 < q <= (D + 1)^2, T = 1 + D / ring_div, carries ink over all but an eighth of the columns of the top and of the bottom half
+# and of the rows of the left and of the right half; the moat between the ring zone and the core q <= D^2 / 4 is empty; a band of
+# band_min + min(w, h) / band_div pixels around the box, clipped to the page, is empty.  State from the core as for the checkboxes.
+ROUND_MARK_PARAMS = dict(out_max=0, ring_div=12, band_div=4, band_min=4)
+
 # Page orientation (lumina_ocr_page_quarter / _page_turn / _page_vote + utils/page_orient.py): ink as above; a page is sideways when the
 # energy of its column profile exceeds `ratio` times that of its row profile (text lines make the profile across them jagged), and an
 # upright-or-upside-down page is upside-down when it has at least min_lines lines and the classifier flips more than half of them.

@@ -92,6 +92,9 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_table_rules": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
         "lumina_ocr_selection_marks": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
         "lumina_ocr_rules_and_marks": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+        "lumina_ocr_selection_marks_round": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+        "lumina_ocr_rules_and_marks_round": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp,
+                                                   i32, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_page_quarter_workspace_bytes": (sz, [i32, i32, i32]),
         "lumina_ocr_page_quarter": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_page_turn": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp]),
@@ -120,7 +123,8 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_resize_lanczos", "lumina_ocr_enhance", "lumina_ocr_jpeg_encode", "lumina_ocr_jpeg_coefficients", "lumina_ocr_jpeg_probe", "lumina_ocr_jpeg_decode", "lumina_ocr_jpeg_decode_async", "lumina_ocr_jpeg_last_passes",
     "lumina_ocr_png_probe", "lumina_ocr_png_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
-    "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks",
+    "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks", "lumina_ocr_selection_marks_round",
+    "lumina_ocr_rules_and_marks_round",
     "lumina_ocr_page_quarter_workspace_bytes", "lumina_ocr_page_quarter", "lumina_ocr_page_turn", "lumina_ocr_page_vote",
 ]
 
@@ -572,6 +576,48 @@ class Engine:
                                                       _ptr(vrules), _ptr(rcounts), min_side, max_side, max_marks, _ptr(marks), _ptr(mcounts),
                                                       self._stream()))
         return hrules, vrules, rcounts, marks, mcounts
+
+    @staticmethod
+    def _round_params(round_params):
+        rp = dict(arch.ROUND_MARK_PARAMS if round_params is None else round_params)
+        return tuple(int(rp[k]) for k in ("out_max", "ring_div", "band_div", "band_min"))
+
+    def selection_marks_round(self, pages, threshold=None, min_side=None, max_side=None, max_marks=None, round_params=None, debug: bool = False):
+        """selection_marks plus the round marks (radio buttons) of the same pages -> (marks, counts, round marks int32 [n,max_marks,8],
+        round counts int32 [n]) on the device: the first two are selection_marks' outputs, the round list has the same row format, order
+        and capacity.  round_params defaults to arch.ROUND_MARK_PARAMS.  Asynchronous.  debug=True also returns the ink mask."""
+        torch = _torch()
+        n, h, w, c = pages.shape
+        assert c == 3 and pages.dtype == torch.uint8 and pages.is_contiguous()
+        threshold = arch.MARK_PARAMS["threshold"] if threshold is None else int(threshold)
+        min_side, max_side, max_marks = self._mark_params(min_side, max_side, max_marks)
+        marks, rounds = (torch.zeros((n, max(max_marks, 0), 8), dtype=torch.int32, device=pages.device) for _ in range(2))
+        counts, rcounts = (torch.zeros((n,), dtype=torch.int32, device=pages.device) for _ in range(2))
+        mask = torch.zeros((n, h, (w + 63) // 64), dtype=torch.int64, device=pages.device) if debug else None
+        self._chk(self.lib.lumina_ocr_selection_marks_round(self._h, _ptr(pages), n, h, w, threshold, min_side, max_side, max_marks, _ptr(marks),
+                                                            _ptr(counts), _ptr(mask), *self._round_params(round_params), _ptr(rounds),
+                                                            _ptr(rcounts), self._stream()))
+        return (marks, counts, rounds, rcounts) + ((mask,) if debug else ())
+
+    def rules_and_marks_round(self, pages, threshold=None, gap=None, min_len=None, max_thick=None, max_rules=None, min_side=None, max_side=None,
+                              max_marks=None, round_params=None):
+        """table_rules and selection_marks_round of the same pages at one threshold, the ink mask computed once.
+        -> (hrules, vrules, rule counts, marks, mark counts, round marks, round counts), each as the two calls return it."""
+        torch = _torch()
+        n, h, w, c = pages.shape
+        assert c == 3 and pages.dtype == torch.uint8 and pages.is_contiguous()
+        tp = arch.TABLE_PARAMS
+        threshold, gap, min_len = (tp[k] if v is None else int(v) for k, v in (("threshold", threshold), ("gap", gap), ("min_len", min_len)))
+        max_thick, max_rules = (tp[k] if v is None else int(v) for k, v in (("max_thick", max_thick), ("max_rules", max_rules)))
+        min_side, max_side, max_marks = self._mark_params(min_side, max_side, max_marks)
+        hrules, vrules = (torch.zeros((n, max_rules, 5), dtype=torch.int32, device=pages.device) for _ in range(2))
+        rcounts = torch.zeros((n, 2), dtype=torch.int32, device=pages.device)
+        marks, rounds = (torch.zeros((n, max_marks, 8), dtype=torch.int32, device=pages.device) for _ in range(2))
+        mcounts, ocounts = (torch.zeros((n,), dtype=torch.int32, device=pages.device) for _ in range(2))
+        self._chk(self.lib.lumina_ocr_rules_and_marks_round(self._h, _ptr(pages), n, h, w, threshold, gap, min_len, max_thick, max_rules, _ptr(hrules),
+                                                            _ptr(vrules), _ptr(rcounts), min_side, max_side, max_marks, _ptr(marks), _ptr(mcounts),
+                                                            *self._round_params(round_params), _ptr(rounds), _ptr(ocounts), self._stream()))
+        return hrules, vrules, rcounts, marks, mcounts, rounds, ocounts
 
     # -- page orientation (utils/page_orient.py, OcrPipeline.run_oriented) ---------------------------------------------------------
     def page_quarter(self, pages, threshold=None, ratio=None):

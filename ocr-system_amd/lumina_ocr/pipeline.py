@@ -37,6 +37,7 @@ class PageDetections:
     vrules: Optional[np.ndarray] = None       # int32 [nv, 5] vertical rules (both empty when a list overflowed its capacity)
     marks: Optional[np.ndarray] = None        # int32 [m, 8] x0, y0, x1, y1, edge, ink_in, area_in, state of the page's checkboxes:
                                               # OcrPipeline(marks=True) only (empty when the list overflowed its capacity)
+    round_marks: Optional[np.ndarray] = None  # int32 [m, 8] the same of the page's radio buttons: OcrPipeline(marks=True, round_marks=True) only
     word_quads: Optional[np.ndarray] = None   # int32 [n, 40, 8] the words of every line from the CTC alignment, each in its line's corner
                                               # order: OcrPipeline(word_boxes=True) only, like the three below
     word_spans: Optional[np.ndarray] = None   # int32 [n, 40, 2] first character in texts[i], character count
@@ -70,7 +71,7 @@ class _Pending:
     event: Optional[object] = None
     gathered: Optional[object] = None   # multi-GPU: handle of dist.PageGather.submit (the batch's results of ALL ranks)
     rules_host: Optional[list] = None   # tables: pinned copies of hrules, vrules, counts
-    marks_host: Optional[list] = None   # marks: pinned copies of marks, counts
+    marks_host: Optional[list] = None   # marks: pinned copies of marks, counts (round_marks: and of round marks, round counts)
     words_host: Optional[list] = None   # word_boxes: pinned copies of word quads, spans, scores, counts
 
 
@@ -78,7 +79,8 @@ class OcrPipeline:
     def __init__(self, engine: Engine, charset: Optional[List[str]] = None, max_dimension: int = 2000, post: Optional[dict] = None,
                  recognizer: str = "crnn", gather=None, angle_cls: bool = False, cls_thresh: float = arch.CLS_THRESH,
                  tables: bool = False, table_params: Optional[dict] = None, marks: bool = False, mark_params: Optional[dict] = None,
-                 page_orient: bool = False, page_orient_params: Optional[dict] = None, word_boxes: bool = False):
+                 page_orient: bool = False, page_orient_params: Optional[dict] = None, word_boxes: bool = False, round_marks: bool = False,
+                 round_mark_params: Optional[dict] = None):
         """recognizer: "crnn" (CRNN-MobileNetV3 + BiLSTM, engine.load_rec) or "svtr" (SVTR, engine.load_svtr).
         angle_cls: PaddleOCR's use_angle_cls — every line is classified 0 / 180 degrees (engine.load_cls) before recognition, and a line
         read as 180 with probability > cls_thresh is recognised turned; boxes and reading order are unchanged.  Per-line labels are
@@ -88,6 +90,9 @@ class OcrPipeline:
         marks: the checkboxes of the processed pages (engine.selection_marks, parameters arch.MARK_PARAMS or mark_params) come back as
         PageDetections.marks; they stay on their rank too.  With tables on as well and one threshold for both, the ink mask is
         computed once (engine.rules_and_marks).
+        round_marks: with marks, the radio buttons as well (engine.selection_marks_round / rules_and_marks_round, parameters
+        arch.ROUND_MARK_PARAMS or round_mark_params) as PageDetections.round_marks; the checkbox rows are the ones without it.  Without
+        marks it is a ValueError.
         page_orient: run_oriented() finds for every page the quarter turns that make it upright (ink profiles for sideways pages,
         parameters arch.PAGE_ORIENT_PARAMS or page_orient_params; the line classifier's majority for upside-down ones, so it needs
         engine.load_cls like angle_cls), turns the raw page on the device and runs the stages below on the upright page.  run /
@@ -112,6 +117,10 @@ class OcrPipeline:
         self.table_params = dict(arch.TABLE_PARAMS if table_params is None else table_params)
         self.marks = bool(marks)
         self.mark_params = dict(arch.MARK_PARAMS if mark_params is None else mark_params)
+        self.round_marks = bool(round_marks)
+        self.round_mark_params = dict(arch.ROUND_MARK_PARAMS if round_mark_params is None else round_mark_params)
+        if self.round_marks and not self.marks:
+            raise ValueError("round_marks needs marks=True: the radio buttons are found in the checkboxes' pass")
         self.page_orient = bool(page_orient)
         self.word_boxes = bool(word_boxes)
         self.space_id = self.charset.index(" ") if " " in self.charset else -1   # the class words split on (-1: a line is one word)
@@ -157,18 +166,26 @@ class OcrPipeline:
         return self._submit_lines(processed, boxes, scores, counts_h, rules, marks)
 
     def _submit_rules_marks(self, processed):
-        """Enqueue the table rules and / or selection marks of the processed pages -> (rules, marks) device tensors, or None each."""
+        """Enqueue the table rules and / or selection marks of the processed pages -> (rules, marks) device tensors, or None each; with
+        round_marks the marks are four tensors: marks, counts, round marks, round counts."""
         rules = marks = None
         if self.gather is None and (self.tables or self.marks):
             tp, mp = self.table_params, self.mark_params
             if self.tables and self.marks and tp["threshold"] == mp["threshold"]:
-                both = self.eng.rules_and_marks(processed, tp["threshold"], tp["gap"], tp["min_len"], tp["max_thick"], tp["max_rules"],
-                                                mp["min_side"], mp["max_side"], mp["max_marks"])
+                if self.round_marks:
+                    both = self.eng.rules_and_marks_round(processed, tp["threshold"], tp["gap"], tp["min_len"], tp["max_thick"], tp["max_rules"],
+                                                          mp["min_side"], mp["max_side"], mp["max_marks"], self.round_mark_params)
+                else:
+                    both = self.eng.rules_and_marks(processed, tp["threshold"], tp["gap"], tp["min_len"], tp["max_thick"], tp["max_rules"],
+                                                    mp["min_side"], mp["max_side"], mp["max_marks"])
                 rules, marks = both[:3], both[3:]
             else:
                 if self.tables:
                     rules = self.eng.table_rules(processed, tp["threshold"], tp["gap"], tp["min_len"], tp["max_thick"], tp["max_rules"])
-                if self.marks:
+                if self.marks and self.round_marks:
+                    marks = self.eng.selection_marks_round(processed, mp["threshold"], mp["min_side"], mp["max_side"], mp["max_marks"],
+                                                           self.round_mark_params)
+                elif self.marks:
                     marks = self.eng.selection_marks(processed, mp["threshold"], mp["min_side"], mp["max_side"], mp["max_marks"])
         return rules, marks
 
@@ -243,10 +260,11 @@ class OcrPipeline:
             pend.event.synchronize()
         rules = self._page_rules(pend)
         marks = self._page_marks(pend)
+        rounds = self._page_marks(pend, 2)
         if pend.n == 0:
             nw = self._empty_words() if self.word_boxes else {}
             return [PageDetections(np.zeros((0, 8), np.int32), [], np.zeros(0, np.float32), np.zeros(0, np.float32), w, h,
-                                   hrules=rules[p][0], vrules=rules[p][1], marks=marks[p], **nw) for p in range(b)], pend.processed
+                                   hrules=rules[p][0], vrules=rules[p][1], marks=marks[p], round_marks=rounds[p], **nw) for p in range(b)], pend.processed
         text_h, len_h, score_h, quads_h, det_h, *cls_h = (t.numpy() for t in pend.host)
         all_texts = self._decoder.decode(text_h, len_h)
         words_h = None
@@ -260,7 +278,7 @@ class OcrPipeline:
             out.append(PageDetections(quads_h[off:off + c], texts, score_h[off:off + c], det_h[off:off + c], w, h,
                                       text_h[off:off + c], len_h[off:off + c],
                                       *((cls_h[0][off:off + c], cls_h[1][off:off + c]) if cls_h else ()),
-                                      hrules=rules[p][0], vrules=rules[p][1], marks=marks[p],
+                                      hrules=rules[p][0], vrules=rules[p][1], marks=marks[p], round_marks=rounds[p],
                                       **({} if words_h is None else dict(zip(self._WORD_FIELDS, (t[off:off + c] for t in words_h))))))
             off += c
         return out, pend.processed
@@ -303,18 +321,18 @@ class OcrPipeline:
             out.append((hr[p, :nh].copy(), vr[p, :nv].copy()))
         return out
 
-    def _page_marks(self, pend: "_Pending"):
+    def _page_marks(self, pend: "_Pending", first: int = 0):
         """-> per page marks [m,8] from the pending batch's host copies, or None without marks.  A page whose true count exceeds the
-        capacity has no rows: it is treated as having no marks."""
-        if pend.marks_host is None:
+        capacity has no rows: it is treated as having no marks.  first = 2: the same for the round marks."""
+        if pend.marks_host is None or len(pend.marks_host) < first + 2:
             return [None] * pend.b
-        rows, cnt = (t.numpy() for t in pend.marks_host)
+        rows, cnt = (t.numpy() for t in pend.marks_host[first:first + 2])
         cap = rows.shape[1]
         out = []
         for p in range(pend.b):
             m = int(cnt[p])
             if m > cap:
-                logger.warning("page %d of the batch has %d selection marks, more than max_marks = %d: none are reported for it", p, m, cap)
+                logger.warning("page %d of the batch has %d %sselection marks, more than max_marks = %d: none are reported for it", p, m, "round " if first else "", cap)
                 m = 0
             out.append(rows[p, :m].copy())
         return out

@@ -132,6 +132,9 @@ class OCRService:
         # LUMINA_OCR_SELECTION_MARKS=1: checkboxes become `selection_mark` entries and :selected: / :unselected: tokens of the Markdown (the
         # reference gets them from Azure's layout model, :313-322).  Off by default: every output is then the one without them.
         self._use_marks = os.environ.get("LUMINA_OCR_SELECTION_MARKS", "0").lower() not in ("", "0", "false", "no")
+        # LUMINA_OCR_RADIO_BUTTONS=1 (with LUMINA_OCR_SELECTION_MARKS=1; alone it is an error): radio buttons become `selection_mark` entries
+        # and tokens exactly as checkboxes do (Azure's selection marks cover both).  Off by default: every output is then the one without it.
+        self._use_round_marks = os.environ.get("LUMINA_OCR_RADIO_BUTTONS", "0").lower() not in ("", "0", "false", "no")
         # LUMINA_OCR_PAGE_ORIENTATION=1: pages lying sideways or upside-down are turned upright on the device before anything else reads
         # them (after decode and EXIF orientation, before the resize), and json_output reports page_rotation.  It uses the classifier
         # (LUMINA_OCR_CLS_WEIGHTS) whether or not LUMINA_OCR_USE_ANGLE_CLS is set.  Off by default: every output is then the one without it.
@@ -169,6 +172,8 @@ class OCRService:
                 raise RuntimeError("orientation classifier weights not configured: set LUMINA_OCR_CLS_WEIGHTS (LOCW blob) with "
                                    "%s=1, or LUMINA_OCR_ALLOW_SYNTHETIC=1 for a seeded synthetic classifier"
                                    % ("LUMINA_OCR_USE_ANGLE_CLS" if self._use_angle_cls else "LUMINA_OCR_PAGE_ORIENTATION"))
+            if self._use_round_marks and not self._use_marks:
+                raise RuntimeError("LUMINA_OCR_RADIO_BUTTONS=1 needs LUMINA_OCR_SELECTION_MARKS=1: radio buttons are found in the checkboxes' pass")
             if have_files and not self._rec_dict:
                 raise RuntimeError("LUMINA_OCR_REC_DICT (the dictionary file the recogniser was trained with) is required with weight files")
             eng = Engine(self._device)  # raises EngineUnavailable without the HIP library / a GPU
@@ -203,7 +208,7 @@ class OCRService:
                                            % (len(charset), "SVTR" if svtr else "CRNN", n_cls))
                     pipeline = OcrPipeline(eng, charset=charset, max_dimension=self.max_dimension, post=post, recognizer=self._recognizer,
                                            angle_cls=self._use_angle_cls, tables=self._use_tables, marks=self._use_marks,
-                                           page_orient=self._use_page_orient, word_boxes=self._use_word_boxes)
+                                           page_orient=self._use_page_orient, word_boxes=self._use_word_boxes, round_marks=self._use_round_marks)
             except Exception:
                 eng.close()
                 raise
@@ -292,7 +297,10 @@ class OCRService:
         if det.hrules is not None:   # LUMINA_OCR_TABLES=1; table_index counts from 0 here, _number_tables makes it run over a document
             tabs = table_layout.find_tables(det.hrules, det.vrules, arch.TABLE_PARAMS["snap"])
             table_layout.fill_cells(tabs, ordered)
-        found = mark_layout.select_marks(det.marks) if getattr(det, "marks", None) is not None else None   # LUMINA_OCR_SELECTION_MARKS=1
+        found = None
+        if getattr(det, "marks", None) is not None:   # LUMINA_OCR_SELECTION_MARKS=1 [+ LUMINA_OCR_RADIO_BUTTONS=1]
+            rounds = getattr(det, "round_marks", None)
+            found = mark_layout.select_marks(det.marks) if rounds is None else mark_layout.select_marks(det.marks, rounds)
         if found:
             md = layout.page_markdown(merged, tabs, marks=found)
         else:

@@ -265,3 +265,150 @@ def synth_marks_page(seed: int, h: int = 1100, w: int = 1500, n_marks: int = 12,
     if noise > 0:
         arr = arr + rng.normal(0.0, noise, arr.shape).astype(np.float32)
     return np.clip(np.rint(arr), 0, 255).astype(np.uint8), gt
+
+
+def _draw_radio(d: ImageDraw.ImageDraw, x0: int, y0: int, diameter: int, stroke: int, dot: bool, ink) -> None:
+    """A ring of `stroke` pixels whose bounding box has its first pixel at (x0, y0) and `diameter` pixels a side, and (dot) a filled
+    disc in its centre of under half the diameter, clear of the ring."""
+    d.ellipse((x0, y0, x0 + diameter - 1, y0 + diameter - 1), outline=ink, width=stroke)
+    if dot:
+        dd = max(2, diameter // 2 - 2)
+        a = (diameter - dd) // 2
+        d.ellipse((x0 + a, y0 + a, x0 + a + dd - 1, y0 + a + dd - 1), fill=ink)
+
+
+RADIO_MAX_STROKE = 4
+
+
+def synth_radio_page(seed: int, h: int = 1100, w: int = 1500, n_marks: int = 12, stroke: int = 0, diameter: int = 0, noise: float = 0.0,
+                     table: bool = True, min_side: int = 12, max_side: int = 64) -> Tuple[np.ndarray, List[dict]]:
+    """White form page with radio buttons, laid out as synth_marks_page lays out its boxes: a title line, n_marks marks in two columns,
+    each with a label to its right at the same distance, every fourth of them a checkbox (_draw_mark) instead of a radio button, and
+    (table) a ruled 2 x 2 table whose cells hold a group of four radio buttons with labels, clear of the rules.
+    diameter: of the radio buttons (and side of the checkboxes) in pixels (0: from the seed per mark, min_side .. max_side); stroke: the
+    ring's thickness (0: from the seed, 1 .. RADIO_MAX_STROKE), never more than diameter // 12: a radio ring is thin; a radio button is
+    empty or has a centre dot, from the seed.  -> (uint8 [h,w,3], [dict(box, state, kind, stroke, label, label_box, in_table,
+    shape='round' | 'square')]) in drawing order."""
+    rng = np.random.default_rng(seed)
+    img = Image.new("RGB", (w, h), (255, 255, 255))
+    d = ImageDraw.Draw(img)
+    scale = min(1.0, h / 2339.0 * 1.6 + 0.2)
+    margin = max(8, int(0.06 * w))
+    y = max(8, int(0.04 * h))
+    tsize = max(10, int(30 * scale))
+    fs = max(10, int(28 * scale))
+    d.text((margin, y), "Choice %d" % seed, fill=(20, 20, 20), font=_font(tsize))
+    y += tsize + 40
+    gt: List[dict] = []
+
+    def put(x: int, yy: int, room: int, in_table: bool, square: bool) -> int:
+        s = int(diameter) if diameter else int(rng.integers(min_side, max_side + 1))
+        want = int(stroke) if stroke else int(rng.integers(1, RADIO_MAX_STROKE + 1))
+        shade = int(rng.integers(0, 41))
+        if square:
+            t = max(1, min(want, s // 4))
+            kind = MARK_KINDS[int(rng.integers(0, len(MARK_KINDS)))]
+            _draw_mark(d, x, yy, s, t, kind, (shade, shade, shade))
+            state = "unselected" if kind == "empty" else "selected"
+        else:
+            t = max(1, min(want, s // 12))
+            dot = bool(rng.integers(0, 2))
+            _draw_radio(d, x, yy, s, t, dot, (shade, shade, shade))
+            kind, state = ("dot", "selected") if dot else ("empty", "unselected")
+        tx, ty = x + s + s // 2 + 8, yy + max(0, (s - fs) // 2)
+        txt = random_text(rng, 4, 10).replace(" ", "x")
+        while len(txt) > 1 and d.textbbox((tx, ty), txt, font=_font(fs))[2] > x + room:
+            txt = txt[:-1]
+        d.text((tx, ty), txt, fill=(shade, shade, shade), font=_font(fs))
+        gt.append(dict(box=(x, yy, x + s - 1, yy + s - 1), state=state, kind=kind, stroke=t, label=txt,
+                       label_box=d.textbbox((tx, ty), txt, font=_font(fs)), in_table=in_table, shape="square" if square else "round"))
+        return s
+
+    col_w = (w - 2 * margin) // 2
+    k = 0
+    while k < n_marks:
+        row_side = 0
+        for c in range(2):
+            if k < n_marks and y + max_side + 8 < h:
+                row_side = max(row_side, put(margin + c * col_w + int(rng.integers(0, 24)), y, col_w - 30, False, k % 4 == 3))
+                k += 1
+        if row_side == 0:
+            break
+        y += max(row_side, fs) + 26
+    if table:
+        t, row_h = 3, max_side + 2 * 20 + 3
+        y += 20
+        if y + 2 * row_h + t < h - 4:
+            xs = [margin, margin + col_w, margin + 2 * col_w]
+            ys = [y, y + row_h, y + 2 * row_h]
+            for yy in ys:
+                d.rectangle((xs[0], yy, xs[-1] + t - 1, yy + t - 1), fill=(10, 10, 10))
+            for xx in xs:
+                d.rectangle((xx, ys[0], xx + t - 1, ys[-1] + t - 1), fill=(10, 10, 10))
+            for r in range(2):
+                for c in range(2):
+                    put(xs[c] + t + 20, ys[r] + t + 20, col_w - 40, True, False)
+    arr = np.asarray(img, np.float32)
+    if noise > 0:
+        arr = arr + rng.normal(0.0, noise, arr.shape).astype(np.float32)
+    return np.clip(np.rint(arr), 0, 255).astype(np.uint8), gt
+
+
+ROUND_DECOY_SIZES = (16, 20, 24, 28, 34, 40, 48, 56, 64, 70)
+ROUND_DECOY_WORDS = ("Of", "OK", "On", "OQDCG0oe@", "GOOD", "DOG", "Oo0", "CoCo", "e@o", "QUOTE", "O0O", "oOo")
+
+
+def synth_round_decoys(seed: int, h: int = 1100, w: int = 1500, noise: float = 0.0) -> Tuple[np.ndarray, List[dict]]:
+    """White page of what is round and no radio button.  One line of words per font size of ROUND_DECOY_SIZES (16-70 px), the words
+    drawn from ROUND_DECOY_WORDS and from random_text with an O in front, in seeded order; and, on a free strip to the right, a solid
+    filled disc, a circle touching a rule, a circle with a letter in it, and two concentric rings, at seeded diameters.
+    -> (uint8 [h,w,3], [dict(kind, box)]) of the four shapes."""
+    rng = np.random.default_rng(seed)
+    img = Image.new("RGB", (w, h), (255, 255, 255))
+    d = ImageDraw.Draw(img)
+    margin = max(8, int(0.06 * w))
+    strip = w - margin - 220                      # the shapes' strip starts here
+    y = max(8, int(0.03 * h))
+    for size in ROUND_DECOY_SIZES:
+        if y + size + 8 >= h:
+            break
+        x = margin + int(rng.integers(0, 30))
+        order = rng.permutation(len(ROUND_DECOY_WORDS))
+        for i in order:
+            word = ROUND_DECOY_WORDS[int(i)] if rng.integers(0, 3) else "O" + random_text(rng, 2, 5).replace(" ", "o")
+            bb = d.textbbox((x, y), word, font=_font(size))
+            if bb[2] >= strip - 20:
+                break
+            shade = int(rng.integers(0, 41))
+            d.text((x, y), word, fill=(shade, shade, shade), font=_font(size))
+            x = bb[2] + max(6, size // 3)
+        y += size + max(10, size // 2)
+    gt = []
+    ink = (10, 10, 10)
+    x, y = strip, max(8, int(0.04 * h))
+    s = int(rng.integers(14, 61))
+    d.ellipse((x, y, x + s - 1, y + s - 1), fill=ink)                                  # a solid disc
+    gt.append(dict(kind="disc", box=(x, y, x + s - 1, y + s - 1)))
+    y += s + 60
+    s = int(rng.integers(20, 61))
+    d.ellipse((x, y, x + s - 1, y + s - 1), outline=ink, width=max(1, s // 16))         # a circle standing on a rule
+    d.rectangle((x - 40, y + s - 1, x + s + 80, y + s + 1), fill=ink)
+    gt.append(dict(kind="on_rule", box=(x, y, x + s - 1, y + s - 1)))
+    y += s + 60
+    s = int(rng.integers(36, 65))
+    d.ellipse((x, y, x + s - 1, y + s - 1), outline=ink, width=max(1, s // 16))         # a circle with a letter in it
+    fs = (3 * s) // 4
+    letter = "CRPM"[int(rng.integers(0, 4))]
+    bb = d.textbbox((0, 0), letter, font=_font(fs))
+    d.text((x + (s - (bb[2] + bb[0])) // 2, y + (s - (bb[3] + bb[1])) // 2), letter, fill=ink, font=_font(fs))
+    gt.append(dict(kind="lettered", box=(x, y, x + s - 1, y + s - 1)))
+    y += s + 60
+    s = int(rng.integers(32, 65))
+    d.ellipse((x, y, x + s - 1, y + s - 1), outline=ink, width=max(1, s // 20))         # two concentric rings
+    a = max(3, s // 8)
+    d.ellipse((x + a, y + a, x + s - 1 - a, y + s - 1 - a), outline=ink, width=max(1, s // 20))
+    gt.append(dict(kind="concentric", box=(x, y, x + s - 1, y + s - 1)))
+    arr = np.asarray(img, np.float32)
+    if noise > 0:
+        arr = arr + rng.normal(0.0, noise, arr.shape).astype(np.float32)
+    return np.clip(np.rint(arr), 0, 255).astype(np.uint8), gt
