@@ -10,7 +10,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from lumina_ocr import arch
+from lumina_ocr import arch, synth
 from oracle import dbpost, nets, preprocess
 from oracle.nets import _rb, conv_bn_act
 
@@ -98,6 +98,47 @@ def cls_block(wd, x, b: dict, mode: str = "bf16"):
         s = conv_bn_act(s, wd, p + ".se2", 1, "hsigmoid", mode=mode)
         y = _rb(y * s, mode)
     return conv_bn_act(y, wd, p + ".project", 1, "none", residual=x if b["res"] else None, mode=mode)
+
+
+def cls_conv1(wd, x, mode: str = "bf16"):
+    """Normalised crops [N,3,48,192] (columns past a crop's width already 0) -> the stem [N,8,24,96]."""
+    return conv_bn_act(x, wd, "cls.conv1", 2, "hswish", mode=mode)
+
+
+def cls_conv2(wd, x, mode: str = "bf16"):
+    """cls.b10 [N,32,2,96] -> [N,200,2,96]: 1x1, hswish."""
+    return conv_bn_act(x, wd, "cls.conv2", 1, "hswish", mode=mode)
+
+
+def cls_pool(x):
+    """cls.conv2 [N,200,2,96] -> tap "cls.feat" [N,200,1,48]: the 2x2 max pool."""
+    return F.max_pool2d(x, 2, 2)
+
+
+# The inputs of the per-layer grading (tests/test_gpu_layer_parity.py): valid widths the stem masks by (1 and 191 / 192 are the mask's
+# edges), cycled over the crops, and 48 x 192 crops with real structure.
+LAYER_WIDTHS = [1, 8, 31, 77, 150, 191, 192]
+
+
+def layer_crops(n: int, seed: int = 31):
+    """-> (crops uint8 [n,48,192,3], widths int32 [n]).  Crop 0 is uniform noise (every tap of every depthwise window matters); the
+    others are crop() of the rendered lines' boxes of synthetic pages (no detector needed), with a margin that varies per line.  The
+    widths are LAYER_WIDTHS cycled from 191 on (the noise crop keeps nearly all its columns), not the crops' own: the pixels past a
+    width stay in the crop and the stem must zero them."""
+    rng = np.random.default_rng(seed)
+    crops = [rng.integers(0, 256, (arch.CLS_H, arch.CLS_W, 3), dtype=np.uint8)]
+    page_seed = seed
+    while len(crops) < n:
+        page, lines = synth.synth_page(480, 640, page_seed, n_lines=8)
+        page_seed += 1
+        for g in lines:
+            x0, y0, x1, y1 = g["box"]
+            m = 1 + len(crops) % 4
+            c, wc = crop(page, [x0 - m, y0 - m, x1 + m, y0 - m, x1 + m, y1 + m, x0 - m, y1 + m])
+            if wc > 0 and len(crops) < n:
+                crops.append(c)
+    widths = np.array([LAYER_WIDTHS[(i + 5) % len(LAYER_WIDTHS)] for i in range(n)], np.int32)
+    return np.stack(crops), widths
 
 
 def backbone(wd, x: torch.Tensor, mode: str = "bf16", taps=None) -> np.ndarray:

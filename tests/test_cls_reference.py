@@ -104,6 +104,50 @@ def test_orientation_path_keeps_dense_rows():
     assert path["cls.fc.w"][0, 1] == arch.CLS_GAIN and path["cls.fc.w"][1, 0] == arch.CLS_GAIN
 
 
+def test_per_layer_wrappers_chain_to_the_backbone():
+    """cls_conv1 -> cls_block x 11 -> cls_conv2 -> cls_pool, each on the previous result, IS backbone(): every tap bit for bit."""
+    import torch
+    from oracle import nets
+    w = arch.make_cls_weights(2718)
+    crops, widths = cr.layer_crops(3)
+    x = cr.normalize(crops, widths)
+    taps = {}
+    feat = cr.backbone(w, x, "bf16", taps)
+    nhwc = lambda t: t.permute(0, 2, 3, 1).contiguous().numpy()           # noqa: E731
+    with torch.no_grad():
+        y = cr.cls_conv1(w, x)
+        assert np.array_equal(nhwc(y), taps["cls.conv1"]) and y.shape == (3, 8, 24, 96)
+        for b in arch.cls_block_table():
+            y = cr.cls_block(w, nets.nhwc_to_nchw(nhwc(y)), b)              # through the NHWC form the GPU test hands over
+            assert np.array_equal(nhwc(y), taps["cls.b%d" % b["idx"]]), b["idx"]
+            assert y.shape[1:3] == (b["cout"], b["h"])
+        y = cr.cls_conv2(w, y)
+        assert np.array_equal(nhwc(y), taps["cls.conv2"]) and y.shape == (3, arch.CLS_FEAT, 2, 96)
+        y = cr.cls_pool(y)
+        assert np.array_equal(nhwc(y), taps["cls.feat"]) and y.shape == (3, arch.CLS_FEAT, 1, 48)
+    assert np.array_equal(y[:, :, 0, :].permute(0, 2, 1).numpy(), feat)
+
+
+def test_layer_crops_and_width_mask():
+    """The per-layer grading's inputs: a noise crop first, text crops after it, the widths cycling through every edge of the mask; the
+    normalised input really is zero from each width on and is not before it."""
+    crops, widths = cr.layer_crops(33)
+    assert crops.shape == (33, 48, 192, 3) and crops.dtype == np.uint8
+    assert set(widths.tolist()) == set(cr.LAYER_WIDTHS) and widths[0] == 191 and widths[1] == 192 and widths[2] == 1
+    assert len(np.unique(crops[0])) == 256                                   # uniform noise
+    for c in crops[1:]:
+        assert c.min() < 100 and c.max() > 200 and c[:, :, 0].std() > 10     # ink and paper: a rendered line
+    assert len({c.tobytes() for c in crops}) == 33
+    a, wa = cr.layer_crops(7)
+    assert np.array_equal(a, crops[:7]) and np.array_equal(wa, widths[:7])  # the smaller sets are prefixes
+    x = cr.normalize(crops, widths).numpy()
+    plain = cr.normalize(crops, np.full(33, 192)).numpy()
+    for i, wv in enumerate(widths):
+        assert not x[i, :, :, wv:].any() and np.array_equal(x[i, :, :, :wv], plain[i, :, :, :wv])
+        assert wv == 192 or plain[i, :, :, wv:].any()                        # the mask removes real pixels
+    assert x[2, :, :, 0].any() and not x[2, :, :, 1:].any()                  # width 1: one column survives
+
+
 def _service(monkeypatch, **attrs):
     from lumina_ocr.services import ocr_service as svc
     s = svc.OCRService()

@@ -1,4 +1,4 @@
-"""GPU: every layer of the det, CRNN and SVTR nets graded on its OWN input (teacher forcing).
+"""GPU: every layer of the det, CRNN, orientation-classifier and SVTR nets graded on its OWN input (teacher forcing).
 
 The engine keeps its layer boundaries readable (option keep_taps); each tap is bf16- (or, for an fp16 SVTR model, fp16-) exact.
 For every tap the oracle layer (oracle/nets.py det_* / rec_* / lstm_layer / svtr_*) is run on the engine's own input tap, in the
@@ -11,14 +11,17 @@ Tolerance classes (bounds in BOUNDS below, with the measured figures behind ever
   EXACT (np.array_equal)
     det   stem.pool (from stem.conv3, keep_taps=1); fpn.fuse (nearest upsampling + concat of its own p5 .. p2 slices)
     CRNN  rec.feat (2x2 max pool of rec.conv2)
-    all   the padded channels of every CRNN tap (rec.conv1 8 -> 16, rec.b3 20 -> 32 ...) are exactly 0.  Invariant: the loader
-          zero-pads weights and biases, relu / hswish map 0 to 0, and the SE gate hsigmoid(0) = 0.5 only ever multiplies the zero
-          padded channels of the depthwise output.  (det and SVTR tensors have no padded channels.)
+    cls   cls.feat (2x2 max pool of cls.conv2)
+    all   the padded channels of every CRNN and classifier tap (rec.conv1 8 -> 16, rec.b3 20 -> 32, cls.conv2 200 -> 208 ...) are
+          exactly 0.  Invariant: the loader zero-pads weights and biases, relu / hswish map 0 to 0, and the SE gate
+          hsigmoid(0) = 0.5 only ever multiplies the zero padded channels of the depthwise output.  (det and SVTR tensors have
+          no padded channels.)
   STEM1  det stem.conv1 from the u8 page: every value within 1 ulp (as end to end today), not array_equal — the 27-term fp32 sum is
          ordered differently from torch's, and 1 of 1.2 M values measured lands on the other side of a rounding boundary
   ONE    one rounding between the taps: within1 > 0.999 and within4 == 1.0 (as test_gpu_conv.py), max 2 ulps
     det   stem.conv2, stem.conv3, head.conv1, head.convt2 (keep_taps=1)
     CRNN  rec.conv1 (from the u8 crop, width-masked), rec.conv2
+    cls   cls.conv1 (from the u8 crop, width-masked), cls.conv2
     LSTM  the first 8 steps of each layer's forward direction and the last 8 of its backward direction (gate order, gate arithmetic)
   PROB   det probability map from head.convt2 (keep_taps=1): one rounding after the device's fast_sigmoidf
   SVTR_SEQ  svtr.seq (row mean + linear + hswish): one-rounding tightness
@@ -29,6 +32,8 @@ Tolerance classes (bounds in BOUNDS below, with the measured figures behind ever
     HEAD_TAIL   prob from head.conv1 with keep_taps=2 (fused DBHead tail incl. fast_sigmoidf)
     MBCONV      rec.b{i} (expand, depthwise, SE pool / FC / gate, project + residual: mbconv_kernel or conv + dwconv_kernel +
                 se_pool_kernel, se_fc_kernel, the project conv applying the gate in its operand staging)
+                cls.b{i}: the same code at scale 0.35, 24-row maps, 96 columns (3 squeeze-excite strips) and block 0 as a
+                stride-2 block WITH squeeze-excite
     SVTR_EMBED  svtr.embed (im2col, two patch-embedding GEMMs with GELU, positional embedding)
     SVTR_MERGE  svtr.sub{s} (3x3 / (2,1) conv + LayerNorm epilogue); also graded with a small-variance input (LayerNorm eps)
     SVTR_BLOCK  svtr.b{i}, local (7x11 window) and global blocks alike
@@ -73,6 +78,7 @@ def _dump_stats():
 # value over all cases and taps of the class; "w1" = share within 1 ulp, "w4" within 4, "max" = largest error in ulps):
 BOUNDS = {
     "ONE": (0.999, 1.0, 2.0),           # measured: w1 1.0, max 1.0 ulp (stem.conv2/3, head.conv1/convt2, rec.conv1/conv2, LSTM 8-step windows)
+                                        #   classifier: cls.conv1 w1 1.0, max 0.96 ulp; cls.conv2 w1 1.0, max 0.85 ulp
     "STEM1": (0.99999, 1.0, 1.0),       # stem.conv1 from the page: w1 1.0, max 0.06 ulp; bit-equal on all but 1 of 1.2 M values
     "PROB": (0.999, 1.0, 2.0),          # prob from head.convt2: w1 1.0, max 0.8 ulp; vs the oracle with fast_sigmoidf emulated: the same
                                         #   figures — the approximation's share of the error is below one bf16 rounding
@@ -81,6 +87,10 @@ BOUNDS = {
     "FPN": (None, 0.999, 32.0),         # fpn.p5 .. p2 from c2 .. c5: w4 0.99985, max 13.9 ulp (end to end today: w4 > 0.85)
     "HEAD_TAIL": (None, 0.9999, 4.0),   # prob from head.conv1 (fused DBHead tail): w4 1.0, max 1.1 ulp; fast_sigmoidf share: none measurable
     "MBCONV": (None, 0.9999, 8.0),      # rec.b{i}: w1 1.0, w4 1.0, max 2.5 ulp (end to end today: w4 > 0.90)
+                                        #   cls.b{i}: w1 0.999995, w4 1.0, max 2.1 ulp (cls.b9, N = 33); b0 .. b3 and b6 bit-equal to the
+                                        #   oracle in all four cases, fused and unfused alike.  For scale: one depthwise tap dropped in the
+                                        #   stride-2 blocks gives cls.b0 w4 0.04, max 7400 ulp; 2 of the 3 squeeze-excite strips summed gives
+                                        #   cls.b0 w4 0.61, max 510 ulp
     "LSTM": (None, 0.999, 8.0),         # whole layer, teacher-forced: w4 1.0, max 1.7 ulp (end to end today: lstm.l1 w4 > 0.6)
     "SVTR_EMBED": (None, 0.999, 32.0),  # svtr.embed: bf16 max 0.9 ulp; f16 w4 0.99994, max 16 ulp (fast_erf emulated: max 7.1 ulp —
                                         #   half of the fp16 error is the GELU approximation's; in bf16 it does not show)
@@ -90,6 +100,8 @@ BOUNDS = {
                                         #   kernel rounds the un-normalised soft-max weights exp(s - m) to the storage type for the P.V
                                         #   MFMA; the definition keeps them fp32.  fast_erf emulated: the same figures (GELU is not it)
 }
+
+
 def _stats(got, ref, dtype="bf16"):
     got = np.asarray(got, np.float32)
     ref = np.asarray(ref, np.float32)
@@ -330,6 +342,95 @@ def test_rec_layers_teacher_forced(request, engine, rec_weights, n, fuse_mb):
         l1 = nets.lstm_layer(wd, torch.from_numpy(got["lstm.l0"].reshape(n, 80, 192).copy()), 1).numpy()
         _lstm_grade(g, "lstm.l1", got["lstm.l1"].reshape(n, 80, 192), l1)
     g.done()
+
+
+# -------------------------------------------------------------------------------------------------- orientation classifier
+CLS_TAPS = ["cls.conv1"] + ["cls.b%d" % i for i in range(11)] + ["cls.conv2", "cls.feat"]
+
+
+def _cls_real_channels():
+    chans = {"cls.conv1": arch.rec_stem_ch(arch.CLS_SCALE), "cls.conv2": arch.CLS_FEAT, "cls.feat": arch.CLS_FEAT}
+    for b in arch.cls_block_table():
+        chans["cls.b%d" % b["idx"]] = b["cout"]
+    return chans
+
+
+@pytest.fixture(scope="module")
+def cls_weights():
+    return arch.make_cls_weights(2718)
+
+
+@pytest.mark.parametrize("n,fuse_mb", [(33, 1), (33, 0), (1, 1), (7, 1)], ids=lambda v: str(v))
+def test_cls_layers_teacher_forced(request, engine, cls_weights, n, fuse_mb):
+    """The shared MobileNetV3 code at the classifier's shapes: scale 0.35 (other padded channel counts), strides (2,2,1,2,1,1,1,1,2,1,1)
+    (block 0 is stride 2 WITH squeeze-excite), 24-row maps, 96 columns (3 squeeze-excite strips), the 2 x 2 pool down to one row.
+    N = 33 leaves a group of one wherever the code groups by 32; crop 0 is uniform noise, the others rendered text lines; the valid
+    widths cycle through every edge of the stem's mask (1, 191, 192)."""
+    import cls_reference as cr
+    wd = cls_weights
+    crops, widths = cr.layer_crops(n)
+    engine.load_cls(wd)
+    engine.set_option("keep_taps", 1)
+    engine.set_option("fuse_mb", fuse_mb)
+    try:
+        engine.cls_forward(torch.from_numpy(crops).cuda(), torch.from_numpy(widths).cuda())
+        torch.cuda.synchronize()
+        got = {k: engine.read_tap(k) for k in CLS_TAPS}
+    finally:
+        engine.set_option("keep_taps", 0)
+        engine.set_option("fuse_mb", 1)
+    g = Grader(request.node.name)
+    chans = _cls_real_channels()
+    table = arch.cls_block_table()
+    assert got["cls.conv1"].shape[:3] == (n, 24, 96) and got["cls.feat"].shape[:3] == (n, 1, 48)
+    assert [got["cls.b%d" % b["idx"]].shape[1] for b in table] == [b["h"] for b in table]
+    with torch.no_grad():
+        for name, c in chans.items():                      # padded channels: exactly zero
+            assert got[name].shape[-1] >= c, (name, got[name].shape)
+            if got[name].shape[-1] > c:
+                g.exact(name + ".pad", got[name][..., c:], np.zeros_like(got[name][..., c:]))
+        real = {k: got[k][..., :c] for k, c in chans.items()}
+        g.grade("cls.conv1", real["cls.conv1"], _nhwc(cr.cls_conv1(wd, cr.normalize(crops, widths))), "ONE")
+        prev = "cls.conv1"
+        for b in table:
+            name = "cls.b%d" % b["idx"]
+            g.grade(name, real[name], _nhwc(cr.cls_block(wd, _T(real[prev]), b)), "MBCONV", stride_h=b["stride_h"], se=bool(b["se"]))
+            prev = name
+        g.grade("cls.conv2", real["cls.conv2"], _nhwc(cr.cls_conv2(wd, _T(real["cls.b10"]))), "ONE")
+        g.exact("cls.feat", real["cls.feat"], _nhwc(cr.cls_pool(_T(real["cls.conv2"]))))
+    g.done()
+
+
+def test_cls_fused_expand_depthwise_is_bit_identical(engine, cls_weights):
+    """The classifier with fuse_mb 1 and 0 on the same 9 crops (ragged widths): every block output, the pooled features, the logits and
+    label / score / flip are bit-identical, and the launch records show that the two runs really differ in kernels — mbconv_kernel<...>
+    is listed with fuse_mb = 1 and absent with 0."""
+    import cls_reference as cr
+    crops, widths = cr.layer_crops(9, seed=77)
+    names = ["cls.b%d" % i for i in range(11)] + ["cls.feat", "cls.logits"]
+    engine.load_cls(cls_weights)
+    engine.conv_timing_detail()                     # drop earlier records
+    engine.set_option("keep_taps", 1)
+    engine.set_option("time_convs", 1)
+    outs, kernels = [], []
+    try:
+        for fuse in (1, 0):
+            engine.set_option("fuse_mb", fuse)
+            res = engine.cls_forward(torch.from_numpy(crops).cuda(), torch.from_numpy(widths).cuda())
+            torch.cuda.synchronize()
+            kernels.append([k for _, k, *_ in engine.conv_timing_detail()])
+            outs.append(([engine.read_tap(k).copy() for k in names], [r.cpu().numpy() for r in res]))
+    finally:
+        engine.set_option("fuse_mb", 1)
+        engine.set_option("keep_taps", 0)
+        engine.set_option("time_convs", 0)
+    fused = [k for k in kernels[0] if k.startswith("mbconv_kernel<")]
+    assert fused and any(k.startswith("mbconv_kernel<3,2,") for k in fused), kernels[0]      # incl. a stride-2 block
+    assert not any(k.startswith("mbconv_kernel<") for k in kernels[1]), kernels[1]
+    for name, a, b in zip(names, outs[0][0], outs[1][0]):
+        assert np.array_equal(a, b), name
+    for name, a, b in zip(("label", "score", "flip"), outs[0][1], outs[1][1]):
+        assert np.array_equal(a, b), name
 
 
 # -------------------------------------------------------------------------------------------------------------------------- SVTR
