@@ -275,7 +275,6 @@ int lumina_ocr_conv2d(lumina_ocr_t* h, const uint16_t* x_dev, int n, int height,
     if (cout % 8 != 0) return locr_fail(h, "conv2d", "cout must be a multiple of 8");
     BIND(h);
     API_TRY
-    lumina_ocr* eng = h;
     ConvLayer L;
     L.name = "conv2d"; L.ks = ks; L.stride = stride; L.cin = cin; L.cout = cout; L.act = act;
     if (!conv_pick_cfg(ks, stride, cin, cout, &L.cfg)) return locr_fail(h, "conv2d", "unsupported ks/stride/cin");
@@ -302,19 +301,16 @@ int lumina_ocr_conv2d(lumina_ocr_t* h, const uint16_t* x_dev, int n, int height,
         pack_conv_weights(w_host, cout, ks, cin, 64, 16, packed2.data(), 1);
         if (upload(&dw2, packed2.data(), packed2.size() * 2) != hipSuccess) return locr_fail(h, "conv2d", "weight upload");
         L.wpk_big = static_cast<bf16_t*>(dw2.get());
-        L.force_big = true;
     }
-    const bool keep_ring = h->conv_ring;
-    if (h->conv2d_variant == 1) h->conv_ring = false;
-    if (h->conv2d_variant == 2) h->conv_ring = true;
     Tensor4 x; x.p = const_cast<bf16_t*>(x_dev); x.n = n; x.h = height; x.w = width; x.c = cin;
     Tensor4 y; y.p = y_dev; y.n = n; y.c = cout;
     y.h = (ks == 3) ? (height - 1) / stride + 1 : height / stride;
     y.w = (ks == 3) ? (width - 1) / stride + 1 : width / stride;
     Tensor4 r; r.p = const_cast<bf16_t*>(res_dev); r.n = n; r.h = y.h; r.w = y.w; r.c = cout;
-    int rc = eng_run_conv(eng, L, x, &y, res_dev ? &r : nullptr, 0, OUT_NORMAL, 0, 0, 0, false, (hipStream_t)stream);
+    ConvCall call;
+    call.res = res_dev ? &r : nullptr; call.variant = h->conv2d_variant;
+    int rc = eng_run_conv(h, L, x, &y, (hipStream_t)stream, call);
     hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-    h->conv_ring = keep_ring;
     if (rc) return rc;
     return hip_rc(h, "conv2d sync", e);
     API_CATCH(h)

@@ -35,9 +35,6 @@ struct ConvLayer {
     // second packing for the 16x32-tile / 4x2-register-tile kernel (3x3, stride 1, >= 64 input channels): picked per launch
     // when the grid is large enough to fill the chip with the bigger tiles
     ConvKernelCfg cfg_big{}; bf16_t* wpk_big = nullptr;
-    bool force_big = false;   // conv2d test hook: take the 16x32-tile kernel whatever the grid size / channel count
-    int launch_group = 0;     // > 0: images per launch (measured: the 256-channel 1/4-resolution layers run 7 % faster in launches of 16 pages than of 64)
-    bool small_only = false;  // never switch to the 16x32-tile kernel (layers whose maps are only 4-8 rows high)
     bf16_t* fuse_w = nullptr; float fuse_b = 0.f;  // optional fused DBHead tail (see ConvParams)
     double alg_flop_per_px = 0;   // > 0: algorithmic FLOP per output pixel of the architecture's layers this launch replaces (a composed layer executes more)
     float* bias = nullptr;  // device, n_tiles*BN
@@ -144,7 +141,7 @@ struct lumina_ocr {
     bool blocked_layout = true;   // stage-0 activations between ring-kernel layers in channel-blocked layout (bit-identical)
     bool conv_ring = true;  // persistent ring kernel for the 3x3 / stride-1 layers (conv_ring.hip)
     int svtr_f16 = -1;      // storage type of the next SVTR load: -1 = what the blob's svtr.config says, 0 bf16, 1 fp16
-    int conv2d_variant = 0; // lumina_ocr_conv2d: 0 = the layer's default kernel, 1 = LDS-DMA 16x32 tile, 2 = ring kernel (tests)
+    int conv2d_variant = 0; // lumina_ocr_conv2d passes it as ConvCall::variant (tests)
     int ring_orient = -1;   // its tile orientation: -1 auto, 0 / 1 forced (tests)
     bool fuse_short = true;   // stages 1-3: the block entry's 2x2 / stride-2 shortcut conv computed by its 3x3 / stride-2 conv0 kernel (one read of the input)
     bool fpn_compose = true;  // the lateral fpn.in2 composed into fpn.p2 (the 256-channel 1/4-resolution lateral is never computed); needs fpn_multi
@@ -183,7 +180,21 @@ int eng_svtr_forward(lumina_ocr* eng, const uint8_t* crops, const int* widths, i
 int eng_ws_reserve(lumina_ocr* eng, size_t bytes);
 // a device copy of host data, owned by the engine until destroy (nullptr if the allocation or the copy fails)
 void* eng_upload(lumina_ocr* eng, const void* host, size_t bytes);
-// short_l / short_y: the block's shortcut layer and its output, computed by the same launch (ConvParams::wpk2)
-int eng_run_conv(lumina_ocr* eng, const ConvLayer& L, const Tensor4& x, Tensor4* y, const Tensor4* res, int res_shift, int out_mode,
-                 int up_shift, int y_cstride, int y_coff, bool flat, hipStream_t st, const bf16_t* gate = nullptr,
-                 const ConvLayer* short_l = nullptr, Tensor4* short_y = nullptr);
+// What an eng_run_conv call asks for beyond y = act(conv(L, x) + bias); a call site names only what differs from the defaults.
+struct ConvCall {
+    const Tensor4* res = nullptr; int res_shift = 0;   // residual / top-down tensor, read at (oy >> res_shift, ox >> res_shift)
+    int out_mode = OUT_NORMAL, up_shift = 0;           // ConvOutMode; OUT_UPSAMPLE replicates every pixel (1 << up_shift)^2 times
+    int y_cstride = 0, y_coff = 0;                     // y is the channel slice [y_coff, y_coff + cout) of pixels y_cstride wide (0: y->c)
+    bool flat = false;                                 // 1x1 conv as one GEMM over all pixels of the batch
+    const bf16_t* gate = nullptr;                      // squeeze-excite gate [n][cin] multiplied into the input (ConvParams::gate)
+    const ConvLayer* short_l = nullptr; Tensor4* short_y = nullptr;   // the block's shortcut layer and its output, computed by the same launch (ConvParams::wpk2)
+    int variant = 0;   // lumina_ocr_conv2d: 0 = the layer's own choice, 1 = LDS-DMA 16x32 tile and never the ring, 2 = ring kernel or an error
+    ConvCall& residual(const Tensor4* r, int shift = 0) { res = r; res_shift = shift; return *this; }
+    ConvCall& mode(int m) { out_mode = m; return *this; }
+    ConvCall& upsample(int shift) { out_mode = OUT_UPSAMPLE; up_shift = shift; return *this; }
+    ConvCall& channel_slice(int cstride, int coff) { y_cstride = cstride; y_coff = coff; return *this; }
+    ConvCall& flat_gemm(bool on = true) { flat = on; return *this; }
+    ConvCall& gated(const bf16_t* g) { gate = g; return *this; }
+    ConvCall& shortcut(const ConvLayer* l, Tensor4* y) { short_l = l; short_y = y; return *this; }
+};
+int eng_run_conv(lumina_ocr* eng, const ConvLayer& L, const Tensor4& x, Tensor4* y, hipStream_t st, const ConvCall& c = {});

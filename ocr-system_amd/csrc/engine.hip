@@ -13,6 +13,8 @@ int locr_fail(lumina_ocr* eng, const char* what, const char* detail) {
     return 1;
 }
 
+#define RUN(expr) do { if ((expr) != 0) return 1; } while (0)
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is per device: remember (device, kernel) pairs, not kernels
 #include <mutex>
 #include <set>
@@ -158,6 +160,51 @@ static inline bf16_t host_f32_to_bf16(float f) {   // round to nearest even (fin
     return (bf16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
 
+static inline uint16_t bf16_bits_to(uint16_t b, int dtype) {   // bf16 bits -> the model's storage type (fp16: exact for |w| >= 2^-14)
+    if (!dtype) return b;
+    uint32_t u = (uint32_t)b << 16;
+    float f; memcpy(&f, &u, 4);
+    const _Float16 hv = (_Float16)f;
+    uint16_t o; memcpy(&o, &hv, 2);
+    return o;
+}
+
+// The 3-channel stem conv name.w [cout][3][3][3] / name.b [cout] (cout <= 32) of the detector, the recogniser or the classifier, in the
+// dedicated kernel's layout (stem_conv.h)
+static int load_stem(lumina_ocr* eng, const std::map<std::string, HostBlobTensor>& m, const char* name, int cout, bf16_t** wpk, float** bias) {
+    const HostBlobTensor *w, *b;
+    if (!get_wb(eng, m, name, &w, &b)) return 1;
+    if (w->dims.size() != 4 || w->dims[0] != cout || w->dims[1] != 3 || w->dims[2] != 3 || w->dims[3] != 3 || b->dims[0] != cout)
+        return locr_fail(eng, name, "shape");
+    bf16_t packed[2 * 2 * 32 * 8];
+    pack_stem_weights(reinterpret_cast<const bf16_t*>(w->data), cout, packed);
+    float padded[32] = {0};
+    memcpy(padded, b->data, sizeof(float) * cout);
+    *wpk = static_cast<bf16_t*>(eng_upload(eng, packed, sizeof(packed)));
+    *bias = static_cast<float*>(eng_upload(eng, padded, sizeof(padded)));
+    return *wpk && *bias ? 0 : locr_fail(eng, "upload", name);
+}
+
+// The CTC head name.w [classes][K] (bf16, stored as `dtype`) / name.b [classes] of the CRNN or of SVTR, in ctc_fc_argmax's layout; the
+// bias of the padding classes is -1e30
+static int load_ctc_head(lumina_ocr* eng, const std::map<std::string, HostBlobTensor>& m, const char* name, int K, int dtype, int* num_classes,
+                         int* ntiles, bf16_t** wpk, float** bias) {
+    auto w = m.find(std::string(name) + ".w"), b = m.find(std::string(name) + ".b");
+    if (w == m.end() || b == m.end() || w->second.dims.size() != 2 || w->second.dims[1] != K || b->second.dims[0] != w->second.dims[0])
+        return locr_fail(eng, name, "missing/shape");
+    const int C = w->second.dims[0];
+    *num_classes = C; *ntiles = (C + 63) / 64;
+    std::vector<bf16_t> conv((size_t)C * K), packed(ctc_packed_weight_elems(C, K));
+    const bf16_t* src = reinterpret_cast<const bf16_t*>(w->second.data);
+    for (size_t i = 0; i < conv.size(); ++i) conv[i] = bf16_bits_to(src[i], dtype);
+    pack_ctc_weights(conv.data(), C, K, packed.data());
+    std::vector<float> padded((size_t)*ntiles * 64, -1.0e30f);
+    memcpy(padded.data(), b->second.data, sizeof(float) * C);
+    *wpk = static_cast<bf16_t*>(eng_upload(eng, packed.data(), packed.size() * sizeof(bf16_t)));
+    *bias = static_cast<float*>(eng_upload(eng, padded.data(), padded.size() * sizeof(float)));
+    return *wpk && *bias ? 0 : locr_fail(eng, "upload", name);
+}
+
 // The lateral fpn.in2 (1x1, 64 -> 256, no bias in DBFPN) composed into the smoothing conv fpn.p2 (3x3, 256 -> 64):
 //     p2 = conv3x3(W_p2, W_in2 c2 + up2(out3)) = conv3x3(W_c, c2) + conv3x3(W_p2, up2(out3)),   W_c[co][tap][ci] = sum_m W_p2[co][tap][m] W_in2[m][ci]
 // -> layer "fpn.p2c": ONE 3x3 conv over the 320 channels [c2 (64, full resolution) | out3 (256, half resolution, read nearest-upsampled)];
@@ -202,16 +249,7 @@ int eng_load_det(lumina_ocr* eng, const void* blob, size_t n) {
     if (!parse_blob(eng, blob, n, &m)) return 1;
     LOCR_CHECK(hipSetDevice(eng->device));
     eng->det.clear();
-    // stem.conv1 (Cin = 3): dedicated kernel
-    {
-        const HostBlobTensor *w, *b;
-        if (!get_wb(eng, m, "stem.conv1", &w, &b)) return 1;
-        if (w->dims.size() != 4 || w->dims[0] != 32 || w->dims[1] != 3 || w->dims[3] != 3) return locr_fail(eng, "stem.conv1", "shape");
-        bf16_t packed[2 * 2 * 32 * 8];
-        pack_stem_weights(reinterpret_cast<const bf16_t*>(w->data), 32, packed);
-        eng->stem_wpk = static_cast<bf16_t*>(eng_upload(eng, packed, sizeof(packed)));
-        eng->stem_bias = static_cast<float*>(eng_upload(eng, b->data, 32 * sizeof(float)));
-    }
+    RUN(load_stem(eng, m, "stem.conv1", 32, &eng->stem_wpk, &eng->stem_bias));   // (Cin = 3: dedicated kernel)
     auto add = [&](const std::string& name, int ks, int stride, int cin, int cout, int act) -> bool {
         return make_conv(eng, m, name, ks, stride, cin, cout, cin, cout, act, &eng->det[name]);
     };
@@ -275,7 +313,7 @@ static bool conv_takes_big(const lumina_ocr* eng, const ConvLayer& L, int n, int
     const long long nb_eff = n > eng->det_sub_batch ? n : eng->det_sub_batch;
     const long long big_blocks = nb_eff * ((ho + 15) / 16) * ((wo + 31) / 32) * ((L.cout + L.cfg.bn - 1) / L.cfg.bn);
     const long long big_min = big_min_env >= 0 ? big_min_env : eng->conv_big_min;
-    return (L.force_big && L.wpk_big != nullptr) || (!no_big && !flat && !L.small_only && L.wpk_big != nullptr && big_blocks >= big_min);
+    return !no_big && !flat && L.wpk_big != nullptr && big_blocks >= big_min;
 }
 
 // option time_convs: HIP events on the launch stream around ONE launch (the detector's convolutions, and the recogniser paths' launches
@@ -297,35 +335,17 @@ struct LaunchTimer {
     }
 };
 
-int eng_run_conv(lumina_ocr* eng, const ConvLayer& L, const Tensor4& x, Tensor4* y, const Tensor4* res, int res_shift, int out_mode,
-                 int up_shift, int y_cstride, int y_coff, bool flat, hipStream_t st, const bf16_t* gate, const ConvLayer* short_l, Tensor4* short_y) {
-    if (short_l != nullptr && L.launch_group > 0) return locr_fail(eng, "fused shortcut", "not available with launch groups");
-    if (L.launch_group > 0 && x.n > L.launch_group && !flat && gate == nullptr && x.p != nullptr && y->p != nullptr &&
-        (out_mode == OUT_NORMAL) && !x.blk && !y->blk && (!res || !res->blk)) {
-        // the same layer in launches of launch_group images (slices of the NHWC tensors; results are per image, hence identical)
-        ConvLayer one = L;
-        one.launch_group = 0;
-        const size_t ystride = (size_t)y->h * y->w * (y_cstride ? y_cstride : y->c);
-        for (int b0 = 0; b0 < x.n; b0 += L.launch_group) {
-            const int nb = x.n - b0 < L.launch_group ? x.n - b0 : L.launch_group;
-            Tensor4 xs = x, ys = *y, rs;
-            xs.n = nb; xs.p = x.p + (size_t)b0 * x.h * x.w * (x.n_src > 1 ? x.src_cs(x.n_src - 1) : x.c);   // (multi-source: p is the last source)
-            for (int k = 0; k < x.n_src; ++k) xs.xs[k] = x.xs[k] + (size_t)b0 * (x.h >> x.xs_shift[k]) * (x.w >> x.xs_shift[k]) * x.src_cs(k);
-            ys.n = nb; ys.p = y->p + (size_t)b0 * ystride;
-            if (res) { rs = *res; rs.n = nb; rs.p = res->p + (size_t)b0 * res->h * res->w * res->c; }
-            if (eng_run_conv(eng, one, xs, &ys, res ? &rs : nullptr, res_shift, out_mode, up_shift, y_cstride, y_coff, flat, st, gate)) return 1;
-        }
-        return 0;
-    }
+// the call's geometry as the kernels want it (the weight image is the kernel choice's: conv_choose)
+static int conv_params(lumina_ocr* eng, const ConvLayer& L, const Tensor4& x, const Tensor4& y, const ConvCall& c, ConvParams* out) {
     ConvParams p{};
     p.zeros = zero_block(eng);
     if (!p.zeros) return locr_fail(eng, "conv", "zero block upload failed");
-    p.gate = gate; p.gate_hw = x.h * x.w;
-    p.x = x.p; p.wpk = L.wpk; p.bias = L.bias; p.res = res ? res->p : nullptr; p.y = y->p;
+    p.gate = c.gate; p.gate_hw = x.h * x.w;
+    p.x = x.p; p.wpk = L.wpk; p.bias = L.bias; p.res = c.res ? c.res->p : nullptr; p.y = y.p;
     p.Cin = L.cin; p.Cout = L.cout; p.act = L.act;
-    p.out_mode = out_mode; p.up_shift = up_shift; p.convt_c = L.convt_c;
-    p.fuse_w = (out_mode == OUT_CONVT) ? L.fuse_w : nullptr; p.fuse_b = L.fuse_b;
-    if (flat) {  // 1x1 conv == GEMM over all pixels: re-tile as rows of 32 so every 8x32 tile is full
+    p.out_mode = c.out_mode; p.up_shift = c.up_shift; p.convt_c = L.convt_c;
+    p.fuse_w = (c.out_mode == OUT_CONVT) ? L.fuse_w : nullptr; p.fuse_b = L.fuse_b;
+    if (c.flat) {  // 1x1 conv == GEMM over all pixels: re-tile as rows of 32 so every 8x32 tile is full
         const long long m = (long long)x.n * x.h * x.w;
         p.N = 1; p.W = 32; p.H = (int)((m + 31) / 32); p.pix_limit = (int)m;
         p.Ho = p.H; p.Wo = 32;
@@ -334,61 +354,102 @@ int eng_run_conv(lumina_ocr* eng, const ConvLayer& L, const Tensor4& x, Tensor4*
         p.N = x.n; p.H = x.h; p.W = x.w; p.pix_limit = 0;
         p.Ho = (L.ks == 3) ? (x.h - 1) / L.stride + 1 : x.h / L.stride;
         p.Wo = (L.ks == 3) ? (x.w - 1) / L.stride + 1 : x.w / L.stride;
-        if (res) { p.res_h = res->h; p.res_w = res->w; }
+        if (c.res) { p.res_h = c.res->h; p.res_w = c.res->w; }
     }
-    p.res_shift = res_shift;
-    p.x_blk = x.blk; p.y_blk = y->blk; p.res_blk = res ? res->blk : 0;
+    p.res_shift = c.res_shift;
+    p.x_blk = x.blk; p.y_blk = y.blk; p.res_blk = c.res ? c.res->blk : 0;
     p.n_src = x.n_src;
     for (int k = 0; k < 4; ++k) {
         p.xs[k] = x.xs[k]; p.xs_shift[k] = x.xs_shift[k];
         p.xs_nchunk[k] = k < x.n_src ? x.src_c(k) / 16 : 0; p.xs_cstride[k] = k < x.n_src ? x.src_cs(k) : 0;
     }
-    p.res_cstride = res ? res->c : 0;
-    p.y_cstride = y_cstride ? y_cstride : y->c;
-    p.y_coff = y_coff;
-    if (short_l != nullptr) {
-        if (short_y == nullptr || short_l->cin != L.cin || short_l->cout != L.cout || short_l->cfg.bn != L.cfg.bn || short_l->cfg.ck != L.cfg.ck ||
-            short_l->ks != 2 || short_l->stride != 2 || short_y->c != L.cout || short_y->h != y->h || short_y->w != y->w)
+    p.res_cstride = c.res ? c.res->c : 0;
+    p.y_cstride = c.y_cstride ? c.y_cstride : y.c;
+    p.y_coff = c.y_coff;
+    if (const ConvLayer* s = c.short_l) {
+        const Tensor4* sy = c.short_y;
+        if (sy == nullptr || s->cin != L.cin || s->cout != L.cout || s->cfg.bn != L.cfg.bn || s->cfg.ck != L.cfg.ck || s->ks != 2 || s->stride != 2 ||
+            sy->c != L.cout || sy->h != y.h || sy->w != y.w)
             return locr_fail(eng, "fused shortcut: layer mismatch", L.name.c_str());
-        p.wpk2 = short_l->wpk; p.bias2 = short_l->bias; p.y2 = short_y->p; p.y2_cstride = short_y->c;
+        p.wpk2 = s->wpk; p.bias2 = s->bias; p.y2 = sy->p; p.y2_cstride = sy->c;
     }
     if (x.c != L.cin) return locr_fail(eng, "conv input channels mismatch", L.name.c_str());
-    if (x.p == nullptr || y->p == nullptr) return ws_null(eng, L.name.c_str());  // dry run (workspace sizing)
-    LaunchTimer tm(eng, st);
-    if (out_mode == OUT_POOL && (L.wpk_big == nullptr || L.cfg_big.nw != 6)) return locr_fail(eng, "fused max pool needs the LDS-DMA conv kernel", L.name.c_str());
-    // 16x32 tiles (less LDS and L2 traffic per MFMA) once they still give >= 2 workgroups per CU on all 256 CUs twice over
-    const bool use_big = out_mode == OUT_POOL || p.n_src > 1 || conv_takes_big(eng, L, p.N, p.Ho, p.Wo, flat);   // (a multi-source input is the ring kernel's)
-    if (L.force_big && eng->conv2d_variant == 2 && !conv_ring_supported(L.cfg_big, p)) return locr_fail(eng, "conv2d_variant 2: the ring kernel does not take this layer", L.name.c_str());
-    ConvKernelCfg cfg = L.cfg;
-    if (use_big) { cfg = L.cfg_big; p.wpk = L.wpk_big; }
-    static const bool no_pw = getenv("LUMINA_CONV_NO_PW") != nullptr;
-    const bool use_pw = !no_pw && !use_big && conv_pw_supported(cfg, p);
-    const bool use_ring = eng->conv_ring && use_big && !use_pw && conv_ring_supported(cfg, p);
-    if (p.n_src > 1 && !use_ring) return locr_fail(eng, "a multi-source input reached a kernel other than the ring kernel", L.name.c_str());
-    if (!use_ring && (p.x_blk || p.y_blk || p.res_blk)) return locr_fail(eng, "a channel-blocked tensor reached a kernel that cannot address it", L.name.c_str());
-    hipError_t e = use_ring ? conv_ring_launch(p, eng->ring_orient, st) : (use_pw ? conv_pw_launch(p, st) : conv_launch(cfg, p, st));
-    if (e != hipSuccess) return locr_fail(eng, L.name.c_str(), hipGetErrorString(e));
-    if (tm.on()) {
-        const double px = flat ? (double)p.pix_limit : (double)p.N * p.Ho * p.Wo;
-        const double flop = (L.alg_flop_per_px > 0 ? px * L.alg_flop_per_px : 2.0 * px * L.ks * L.ks * L.cin * L.cout) +
-                            (short_l ? 2.0 * px * 4 * short_l->cin * short_l->cout : 0.0);
-        // algorithmic HBM bytes: input once + output once (+ residual) + weights once
-        double in_elems = (double)x.elems();
-        if (x.n_src > 1) { in_elems = 0; for (int k = 0; k < x.n_src; ++k) in_elems += (double)x.n * (x.h >> x.xs_shift[k]) * (x.w >> x.xs_shift[k]) * x.src_c(k); }
-        const double bytes = 2.0 * (in_elems + px * (out_mode == OUT_CONVT && p.fuse_w ? 4.0 : (double)L.cout) * (out_mode == OUT_UPSAMPLE ? (double)(1 << (2 * up_shift)) : (out_mode == OUT_POOL ? 0.25 : 1.0)) + (res ? px * (double)L.cout / (double)(1 << (2 * res_shift)) : 0.0) + (double)L.ks * L.ks * L.cin * L.cout +
-                                    (short_l ? px * (double)short_l->cout + 4.0 * short_l->cin * short_l->cout : 0.0));
-        std::string kname = use_pw ? (L.cin == 64 ? "conv_pw_kernel<64>" : "conv_pw_kernel<128>") : conv_kernel_name(cfg);
-        if (use_ring) kname = conv_ring_kernel_name(p, eng->ring_orient);
-        if (short_l) { const size_t pos = kname.rfind(",0,2>"); if (pos != std::string::npos) kname.replace(pos, 5, ",5,2>"); }   // the fused-shortcut instantiation
-        if (out_mode == OUT_POOL && !use_ring) { const size_t pos = kname.rfind(",3,4>"); if (pos != std::string::npos) kname.replace(pos, 5, ",4,4>"); }  // the fused-pool instantiation
-        tm.done(short_l ? L.name + "+short" : L.name, kname, flop, bytes);
-    }
+    *out = p;
     return 0;
 }
 
-#define RUN(expr) do { if ((expr) != 0) return 1; } while (0)
+// which kernel runs the call, with which configuration and weight image
+enum ConvKernel { CONV_TILE_8X32, CONV_TILE_16X32, CONV_POINTWISE, CONV_RING };
+struct ConvChoice { ConvKernel kernel; ConvKernelCfg cfg; const bf16_t* wpk; };
+
+static int conv_choose(lumina_ocr* eng, const ConvLayer& L, const ConvParams& p, const ConvCall& c, ConvChoice* out) {
+    if (p.out_mode == OUT_POOL && (L.wpk_big == nullptr || L.cfg_big.nw != 6)) return locr_fail(eng, "fused max pool needs the LDS-DMA conv kernel", L.name.c_str());
+    const bool forced = c.variant != 0 && L.wpk_big != nullptr;   // (the conv2d hook)
+    // 16x32 tiles (less LDS and L2 traffic per MFMA) once they still give >= 2 workgroups per CU on all 256 CUs twice over
+    const bool big = forced || p.out_mode == OUT_POOL || p.n_src > 1 || conv_takes_big(eng, L, p.N, p.Ho, p.Wo, c.flat);   // (a multi-source input is the ring kernel's)
+    if (forced && c.variant == 2 && !conv_ring_supported(L.cfg_big, p)) return locr_fail(eng, "conv2d_variant 2: the ring kernel does not take this layer", L.name.c_str());
+    *out = big ? ConvChoice{CONV_TILE_16X32, L.cfg_big, L.wpk_big} : ConvChoice{CONV_TILE_8X32, L.cfg, L.wpk};
+    static const bool no_pw = getenv("LUMINA_CONV_NO_PW") != nullptr;
+    const bool ring_on = c.variant == 0 ? eng->conv_ring : c.variant == 2;
+    if (!no_pw && !big && conv_pw_supported(out->cfg, p)) out->kernel = CONV_POINTWISE;
+    else if (ring_on && big && conv_ring_supported(out->cfg, p)) out->kernel = CONV_RING;
+    if (p.n_src > 1 && out->kernel != CONV_RING) return locr_fail(eng, "a multi-source input reached a kernel other than the ring kernel", L.name.c_str());
+    if (out->kernel != CONV_RING && (p.x_blk || p.y_blk || p.res_blk)) return locr_fail(eng, "a channel-blocked tensor reached a kernel that cannot address it", L.name.c_str());
+    return 0;
+}
+
+static hipError_t conv_dispatch(const lumina_ocr* eng, const ConvChoice& k, const ConvParams& p, hipStream_t st) {
+    if (k.kernel == CONV_RING) return conv_ring_launch(p, eng->ring_orient, st);
+    return k.kernel == CONV_POINTWISE ? conv_pw_launch(p, st) : conv_launch(k.cfg, p, st);
+}
+
+// the launch's algorithmic work and the name of the instantiation that ran, for option time_convs
+static void conv_account(const lumina_ocr* eng, const ConvLayer& L, const Tensor4& x, const ConvCall& c, const ConvParams& p, const ConvChoice& k, LaunchTimer* tm) {
+    const ConvLayer* s = c.short_l;
+    const double px = c.flat ? (double)p.pix_limit : (double)p.N * p.Ho * p.Wo;
+    const double flop = (L.alg_flop_per_px > 0 ? px * L.alg_flop_per_px : 2.0 * px * L.ks * L.ks * L.cin * L.cout) + (s ? 2.0 * px * 4 * s->cin * s->cout : 0.0);
+    // algorithmic HBM bytes: input once + output once (+ residual) + weights once
+    double in_elems = (double)x.elems();
+    if (x.n_src > 1) { in_elems = 0; for (int i = 0; i < x.n_src; ++i) in_elems += (double)x.n * (x.h >> x.xs_shift[i]) * (x.w >> x.xs_shift[i]) * x.src_c(i); }
+    const double bytes = 2.0 * (in_elems + px * (c.out_mode == OUT_CONVT && p.fuse_w ? 4.0 : (double)L.cout) * (c.out_mode == OUT_UPSAMPLE ? (double)(1 << (2 * c.up_shift)) : (c.out_mode == OUT_POOL ? 0.25 : 1.0)) + (c.res ? px * (double)L.cout / (double)(1 << (2 * c.res_shift)) : 0.0) + (double)L.ks * L.ks * L.cin * L.cout +
+                                (s ? px * (double)s->cout + 4.0 * s->cin * s->cout : 0.0));
+    std::string kname = k.kernel == CONV_POINTWISE ? (L.cin == 64 ? "conv_pw_kernel<64>" : "conv_pw_kernel<128>") : conv_kernel_name(k.cfg);
+    if (k.kernel == CONV_RING) kname = conv_ring_kernel_name(p, eng->ring_orient);
+    if (s) { const size_t pos = kname.rfind(",0,2>"); if (pos != std::string::npos) kname.replace(pos, 5, ",5,2>"); }   // the fused-shortcut instantiation
+    if (c.out_mode == OUT_POOL && k.kernel != CONV_RING) { const size_t pos = kname.rfind(",3,4>"); if (pos != std::string::npos) kname.replace(pos, 5, ",4,4>"); }  // the fused-pool instantiation
+    tm->done(s ? L.name + "+short" : L.name, kname, flop, bytes);
+}
+
+int eng_run_conv(lumina_ocr* eng, const ConvLayer& L, const Tensor4& x, Tensor4* y, hipStream_t st, const ConvCall& c) {
+    ConvParams p;
+    RUN(conv_params(eng, L, x, *y, c, &p));
+    if (x.p == nullptr || y->p == nullptr) return ws_null(eng, L.name.c_str());  // dry run (workspace sizing)
+    LaunchTimer tm(eng, st);
+    ConvChoice k;
+    RUN(conv_choose(eng, L, p, c, &k));
+    p.wpk = k.wpk;
+    hipError_t e = conv_dispatch(eng, k, p, st);
+    if (e != hipSuccess) return locr_fail(eng, L.name.c_str(), hipGetErrorString(e));
+    if (tm.on()) conv_account(eng, L, x, c, p, k, &tm);
+    return 0;
+}
 
 static void tap(lumina_ocr* eng, const char* name, const Tensor4& t) { if (eng->keep_taps && t.p) eng->taps[name] = t; }
+
+// The 3-channel stem conv (load_stem) of N H x W uint8 images -> y: pixel * scale[c] + shift[c], 3x3 / stride 2, act; widths: valid
+// width per image (the rest reads as zero) or null.  conv2 (detector): that 3x3 / stride-1 layer computed by the same kernel.
+static int run_stem(lumina_ocr* eng, const char* name, const uint8_t* x, const int* widths, int N, int H, int W, const bf16_t* wpk, const float* bias,
+                    int act, const float scale[3], const float shift[3], const Tensor4& y, hipStream_t st, const ConvLayer* conv2 = nullptr) {
+    if (eng->arena.counting() || y.p == nullptr) return 0;
+    StemParams sp{};
+    sp.x = x; sp.wpk = wpk; sp.bias = bias; sp.y = y.p; sp.valid_w_per_img = widths;
+    sp.N = N; sp.H = H; sp.W = W; sp.valid_h = H; sp.valid_w = W; sp.Ho = y.h; sp.Wo = y.w; sp.Cout_store = y.c;
+    sp.act = act;
+    for (int c = 0; c < 3; ++c) { sp.scale[c] = scale[c]; sp.shift[c] = shift[c]; }
+    hipError_t e = conv2 ? stem12_launch(sp, conv2->wpk, conv2->bias, st) : stem_conv_launch(sp, st);
+    return e == hipSuccess ? 0 : locr_fail(eng, name, hipGetErrorString(e));
+}
+static const float STEM_SCALE_PM1[3] = {2.0f / 255.0f, 2.0f / 255.0f, 2.0f / 255.0f}, STEM_SHIFT_PM1[3] = {-1.0f, -1.0f, -1.0f};   // pixels to [-1, 1] (rec, cls)
 
 // ------------------------------------------------------------------------------ det forward
 static int det_forward_sub(lumina_ocr* eng, const uint8_t* pages, int B, int H, int W, int Hp, int Wp, bf16_t* prob, hipStream_t st) {
@@ -400,19 +461,15 @@ static int det_forward_sub(lumina_ocr* eng, const uint8_t* pages, int B, int H, 
     Tensor4 t1{};
     if (!fuse_stem || dry) t1 = ws_tensor(eng, B, Hp / 2, Wp / 2, 32);
     Tensor4 t2 = ws_tensor(eng, B, Hp / 2, Wp / 2, 32);
-    if (!dry && t2.p && (fuse_stem || t1.p)) {
-        StemParams sp{};
-        sp.x = pages; sp.wpk = eng->stem_wpk; sp.bias = eng->stem_bias; sp.y = fuse_stem ? t2.p : t1.p; sp.valid_w_per_img = nullptr;
-        sp.N = B; sp.H = H; sp.W = W; sp.valid_h = H; sp.valid_w = W; sp.Ho = Hp / 2; sp.Wo = Wp / 2; sp.Cout_store = 32;
-        sp.act = ACT_RELU;
-        const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-        for (int c = 0; c < 3; ++c) { sp.scale[c] = 1.0f / (255.0f * stdv[c]); sp.shift[c] = -mean[c] / stdv[c]; }
-        hipError_t e = fuse_stem ? stem12_launch(sp, c2.wpk, c2.bias, st) : stem_conv_launch(sp, st);
-        if (e != hipSuccess) return locr_fail(eng, "stem.conv1", hipGetErrorString(e));
+    {
+        const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};   // ImageNet
+        float scale[3], shift[3];
+        for (int c = 0; c < 3; ++c) { scale[c] = 1.0f / (255.0f * stdv[c]); shift[c] = -mean[c] / stdv[c]; }
+        RUN(run_stem(eng, "stem.conv1", pages, nullptr, B, H, W, eng->stem_wpk, eng->stem_bias, ACT_RELU, scale, shift, fuse_stem ? t2 : t1, st, fuse_stem ? &c2 : nullptr));
     }
     if (!fuse_stem) {
         tap(eng, "stem.conv1", t1);
-        RUN(eng_run_conv(eng, c2, t1, &t2, nullptr, 0, OUT_NORMAL, 0, 0, 0, false, st)); tap(eng, "stem.conv2", t2);
+        RUN(eng_run_conv(eng, c2, t1, &t2, st)); tap(eng, "stem.conv2", t2);
     }
     // stem.conv3 + 3x3/s2 max pool: fused (the 64-channel half-resolution tensor, 93 MB per page, is never written) unless the
     // intermediate is wanted as a tap
@@ -421,9 +478,9 @@ static int det_forward_sub(lumina_ocr* eng, const uint8_t* pages, int B, int H, 
     if (!fuse_pool || dry) t3 = ws_tensor(eng, B, Hp / 2, Wp / 2, 64);
     Tensor4 x = ws_tensor(eng, B, Hp / 4, Wp / 4, 64);
     if (fuse_pool) {
-        RUN(eng_run_conv(eng, D["stem.conv3"], t2, &x, nullptr, 0, OUT_POOL, 0, 0, 0, false, st));
+        RUN(eng_run_conv(eng, D["stem.conv3"], t2, &x, st, ConvCall().mode(OUT_POOL)));
     } else {
-        RUN(eng_run_conv(eng, D["stem.conv3"], t2, &t3, nullptr, 0, OUT_NORMAL, 0, 0, 0, false, st)); tap(eng, "stem.conv3", t3);
+        RUN(eng_run_conv(eng, D["stem.conv3"], t2, &t3, st)); tap(eng, "stem.conv3", t3);
         if (!dry && x.p) {
             hipError_t e = maxpool_launch(t3.p, x.p, B, t3.h, t3.w, 64, 3, 2, 1, x.h, x.w, st);
             if (e != hipSuccess) return locr_fail(eng, "stem.pool", hipGetErrorString(e));
@@ -449,14 +506,14 @@ static int det_forward_sub(lumina_ocr* eng, const uint8_t* pages, int B, int H, 
             Tensor4 sc = x;
             if (j == 0) sc = ws_tensor(eng, B, y.h, y.w, chs[i]);
             if (fuse_sc) {
-                RUN(eng_run_conv(eng, c0, x, &y, nullptr, 0, OUT_NORMAL, 0, 0, 0, false, st, nullptr, &D[p + ".short"], &sc));
+                RUN(eng_run_conv(eng, c0, x, &y, st, ConvCall().shortcut(&D[p + ".short"], &sc)));
             } else {
-                RUN(eng_run_conv(eng, c0, x, &y, nullptr, 0, OUT_NORMAL, 0, 0, 0, false, st));
-                if (j == 0) RUN(eng_run_conv(eng, D[p + ".short"], x, &sc, nullptr, 0, OUT_NORMAL, 0, 0, 0, i == 0, st));
+                RUN(eng_run_conv(eng, c0, x, &y, st));
+                if (j == 0) RUN(eng_run_conv(eng, D[p + ".short"], x, &sc, st, ConvCall().flat_gemm(i == 0)));
             }
             Tensor4 o = ws_tensor(eng, B, y.h, y.w, chs[i]);
             o.blk = blk && j == 0;
-            RUN(eng_run_conv(eng, D[p + ".conv1"], y, &o, &sc, 0, OUT_NORMAL, 0, 0, 0, false, st));
+            RUN(eng_run_conv(eng, D[p + ".conv1"], y, &o, st, ConvCall().residual(&sc)));
             tap(eng, p.c_str(), o);
             x = o;
         }
@@ -464,11 +521,11 @@ static int det_forward_sub(lumina_ocr* eng, const uint8_t* pages, int B, int H, 
     }
     // FPN: laterals with fused top-down nearest-upsample add
     Tensor4 in5 = ws_tensor(eng, B, feats[3].h, feats[3].w, 256);
-    RUN(eng_run_conv(eng, D["fpn.in5"], feats[3], &in5, nullptr, 0, OUT_NORMAL, 0, 0, 0, false, st));
+    RUN(eng_run_conv(eng, D["fpn.in5"], feats[3], &in5, st));
     Tensor4 out4 = ws_tensor(eng, B, feats[2].h, feats[2].w, 256);
-    RUN(eng_run_conv(eng, D["fpn.in4"], feats[2], &out4, &in5, 1, OUT_NORMAL, 0, 0, 0, false, st));
+    RUN(eng_run_conv(eng, D["fpn.in4"], feats[2], &out4, st, ConvCall().residual(&in5, 1)));
     Tensor4 out3 = ws_tensor(eng, B, feats[1].h, feats[1].w, 256);
-    RUN(eng_run_conv(eng, D["fpn.in3"], feats[1], &out3, &out4, 1, OUT_NORMAL, 0, 0, 0, false, st));
+    RUN(eng_run_conv(eng, D["fpn.in3"], feats[1], &out3, st, ConvCall().residual(&out4, 1)));
     // DBHead's first conv runs over the concat [up8(p5), up4(p4), up2(p3), p2].  Default: the smoothing convs write p5 .. p2 at their
     // own resolution and head.conv1 (ring kernel) reads them nearest-upsampled through its halo addressing — the 1/4-resolution
     // 256-channel concat (1.5 GB per 16 A4 pages, written 4 / 16 / 64-fold replicated) never exists.  Same products, same order.
@@ -492,24 +549,24 @@ static int det_forward_sub(lumina_ocr* eng, const uint8_t* pages, int B, int H, 
             in.c = 320; in.n_src = 2;
             in.xs[0] = c2.p; in.xs[1] = o3.p; in.p = o3.p;
             in.xs_shift[0] = 0; in.xs_shift[1] = 1; in.xs_c[0] = 64; in.xs_c[1] = 256;
-            return eng_run_conv(eng, D["fpn.p2c"], in, dst, nullptr, 0, OUT_NORMAL, 0, y_cstride, y_coff, false, st);
+            return eng_run_conv(eng, D["fpn.p2c"], in, dst, st, ConvCall().channel_slice(y_cstride, y_coff));
         }
-        RUN(eng_run_conv(eng, D["fpn.in2"], c2, lateral, &o3, 1, OUT_NORMAL, 0, 0, 0, false, st));
-        return eng_run_conv(eng, D["fpn.p2"], *lateral, dst, nullptr, 0, OUT_NORMAL, 0, y_cstride, y_coff, false, st);
+        RUN(eng_run_conv(eng, D["fpn.in2"], c2, lateral, st, ConvCall().residual(&o3, 1)));
+        return eng_run_conv(eng, D["fpn.p2"], *lateral, dst, st, ConvCall().channel_slice(y_cstride, y_coff));
     };
     auto head_tail = [&](const Tensor4& h1, bf16_t* prob_g, int nb) -> int {
         Tensor4 pm; pm.p = dry ? nullptr : prob_g; pm.n = nb; pm.h = Hp; pm.w = Wp; pm.c = 1;
         if (eng->fuse_head && eng->keep_taps != 1)   // DBHead tail in one launch: the 64-channel 1/2-resolution tensor never exists
-            return eng_run_conv(eng, D["head.convt2.fused"], h1, &pm, nullptr, 0, OUT_CONVT, 0, 1, 0, false, st);
+            return eng_run_conv(eng, D["head.convt2.fused"], h1, &pm, st, ConvCall().mode(OUT_CONVT));
         Tensor4 h2 = ws_tensor(eng, nb, Hp / 2, Wp / 2, 64);
-        RUN(eng_run_conv(eng, D["head.convt2"], h1, &h2, nullptr, 0, OUT_CONVT, 0, 0, 0, false, st)); tap(eng, "head.convt2", h2);
-        return eng_run_conv(eng, D["head.convt3"], h2, &pm, nullptr, 0, OUT_CONVT1, 0, 1, 0, false, st);
+        RUN(eng_run_conv(eng, D["head.convt2"], h1, &h2, st, ConvCall().mode(OUT_CONVT))); tap(eng, "head.convt2", h2);
+        return eng_run_conv(eng, D["head.convt3"], h2, &pm, st, ConvCall().mode(OUT_CONVT1));
     };
     if (multi) {
         Tensor4 p5 = ws_tensor(eng, B, in5.h, in5.w, 64), p4 = ws_tensor(eng, B, out4.h, out4.w, 64), p3 = ws_tensor(eng, B, out3.h, out3.w, 64);
-        RUN(eng_run_conv(eng, D["fpn.p5"], in5, &p5, nullptr, 0, OUT_NORMAL, 0, 0, 0, false, st)); tap(eng, "fpn.p5", p5);
-        RUN(eng_run_conv(eng, D["fpn.p4"], out4, &p4, nullptr, 0, OUT_NORMAL, 0, 0, 0, false, st)); tap(eng, "fpn.p4", p4);
-        RUN(eng_run_conv(eng, D["fpn.p3"], out3, &p3, nullptr, 0, OUT_NORMAL, 0, 0, 0, false, st)); tap(eng, "fpn.p3", p3);
+        RUN(eng_run_conv(eng, D["fpn.p5"], in5, &p5, st)); tap(eng, "fpn.p5", p5);
+        RUN(eng_run_conv(eng, D["fpn.p4"], out4, &p4, st)); tap(eng, "fpn.p4", p4);
+        RUN(eng_run_conv(eng, D["fpn.p3"], out3, &p3, st)); tap(eng, "fpn.p3", p3);
         // The 1/4-resolution tail — lateral in2 (1.5 GB per 16 pages), p2, head.conv1, DBHead tail — runs in groups of tail_group
         // pages: each consumer then finds part of its producer's output still in the 256 MB Infinity Cache (A/B on one device,
         // 64 A4 pages in one forward: p2 3.68 -> 3.47 ms, head.conv1 3.32 -> 3.12 ms), and the 256-channel lateral only ever exists for
@@ -528,7 +585,7 @@ static int det_forward_sub(lumina_ocr* eng, const uint8_t* pages, int B, int H, 
             cat.c = 256; cat.n_src = 4;
             cat.xs[0] = slice(p5, g0, nb).p; cat.xs[1] = slice(p4, g0, nb).p; cat.xs[2] = slice(p3, g0, nb).p; cat.xs[3] = p2g.p;
             cat.xs_shift[0] = 3; cat.xs_shift[1] = 2; cat.xs_shift[2] = 1; cat.xs_shift[3] = 0;
-            RUN(eng_run_conv(eng, hc1, cat, &h1g, nullptr, 0, OUT_NORMAL, 0, 0, 0, false, st)); tap(eng, "head.conv1", h1g);
+            RUN(eng_run_conv(eng, hc1, cat, &h1g, st)); tap(eng, "head.conv1", h1g);
             RUN(head_tail(h1g, prob ? prob + (size_t)g0 * Hp * Wp : nullptr, nb));
         }
         return 0;
@@ -537,13 +594,13 @@ static int det_forward_sub(lumina_ocr* eng, const uint8_t* pages, int B, int H, 
     if (!compose) out2 = ws_tensor(eng, B, feats[0].h, feats[0].w, 256);
     // smooth convs write straight into the channel slices of the 1/4-resolution concat (replicated)
     Tensor4 fuse = ws_tensor(eng, B, Hp / 4, Wp / 4, 256);
-    RUN(eng_run_conv(eng, D["fpn.p5"], in5, &fuse, nullptr, 0, OUT_UPSAMPLE, 3, 256, 0, false, st));
-    RUN(eng_run_conv(eng, D["fpn.p4"], out4, &fuse, nullptr, 0, OUT_UPSAMPLE, 2, 256, 64, false, st));
-    RUN(eng_run_conv(eng, D["fpn.p3"], out3, &fuse, nullptr, 0, OUT_UPSAMPLE, 1, 256, 128, false, st));
+    RUN(eng_run_conv(eng, D["fpn.p5"], in5, &fuse, st, ConvCall().upsample(3).channel_slice(256, 0)));
+    RUN(eng_run_conv(eng, D["fpn.p4"], out4, &fuse, st, ConvCall().upsample(2).channel_slice(256, 64)));
+    RUN(eng_run_conv(eng, D["fpn.p3"], out3, &fuse, st, ConvCall().upsample(1).channel_slice(256, 128)));
     RUN(run_p2(feats[0], out3, &out2, &fuse, 256, 192));
     tap(eng, "fpn.fuse", fuse);
     Tensor4 h1 = ws_tensor(eng, B, Hp / 4, Wp / 4, 64);
-    RUN(eng_run_conv(eng, hc1, fuse, &h1, nullptr, 0, OUT_NORMAL, 0, 0, 0, false, st)); tap(eng, "head.conv1", h1);
+    RUN(eng_run_conv(eng, hc1, fuse, &h1, st)); tap(eng, "head.conv1", h1);
     return head_tail(h1, prob, B);
 }
 
@@ -661,17 +718,7 @@ int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n) {
     LOCR_CHECK(hipSetDevice(eng->device));
     const double scale = 0.5;
     const int c0 = make_div(16 * scale);
-    {
-        const HostBlobTensor *w, *b;
-        if (!get_wb(eng, m, "rec.conv1", &w, &b)) return 1;
-        if (w->dims[0] != c0 || w->dims[1] != 3 || w->dims[3] != 3) return locr_fail(eng, "rec.conv1", "shape");
-        bf16_t packed[2 * 2 * 32 * 8];
-        pack_stem_weights(reinterpret_cast<const bf16_t*>(w->data), c0, packed);
-        float bias[32] = {0};
-        memcpy(bias, b->data, sizeof(float) * c0);
-        eng->rstem_wpk = static_cast<bf16_t*>(eng_upload(eng, packed, sizeof(packed)));
-        eng->rstem_bias = static_cast<float*>(eng_upload(eng, bias, sizeof(bias)));
-    }
+    RUN(load_stem(eng, m, "rec.conv1", c0, &eng->rstem_wpk, &eng->rstem_bias));
     static const int sh[11] = {1, 2, 1, 2, 1, 1, 1, 1, 2, 1, 1};
     if (load_mv3_blocks(eng, m, "rec", scale, sh, c0, &eng->rblocks)) return 1;
     const int cin = eng->rblocks.back().cout;
@@ -700,19 +747,7 @@ int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n) {
         eng->whh[l] = static_cast<bf16_t*>(eng_upload(eng, hcat.data(), hcat.size()));
         if (!eng->whh[l]) return locr_fail(eng, "upload", "whh");
     }
-    {
-        auto w = m.find("ctc.fc.w"), b = m.find("ctc.fc.b");
-        if (w == m.end() || b == m.end() || w->second.dims[1] != 2 * Hh) return locr_fail(eng, "ctc.fc", "missing/shape");
-        const int C = w->second.dims[0];
-        eng->num_classes = C; eng->ctc_ntiles = (C + 63) / 64;
-        std::vector<bf16_t> packed(ctc_packed_weight_elems(C, 2 * Hh));
-        pack_ctc_weights(reinterpret_cast<const bf16_t*>(w->second.data), C, 2 * Hh, packed.data());
-        std::vector<float> bias((size_t)eng->ctc_ntiles * 64, -1.0e30f);
-        memcpy(bias.data(), b->second.data, sizeof(float) * C);
-        eng->ctc_wpk = static_cast<bf16_t*>(eng_upload(eng, packed.data(), packed.size() * sizeof(bf16_t)));
-        eng->ctc_bias = static_cast<float*>(eng_upload(eng, bias.data(), bias.size() * sizeof(float)));
-        if (!eng->ctc_wpk || !eng->ctc_bias) return locr_fail(eng, "upload", "ctc");
-    }
+    RUN(load_ctc_head(eng, m, "ctc.fc", 2 * Hh, 0, &eng->num_classes, &eng->ctc_ntiles, &eng->ctc_wpk, &eng->ctc_bias));
     eng->rec_loaded = true;
     return 0;
 }
@@ -749,7 +784,7 @@ static int run_mv3_block(lumina_ocr* eng, const RecBlock& B, const std::string& 
                     2.0 * ipx * x->c * mp.expc + 2.0 * opx * B.k * B.k * mp.expc, 2.0 * (ipx * x->c + opx * mp.expc));
         }
     } else {
-        RUN(eng_run_conv(eng, B.expand, *x, &e1, nullptr, 0, OUT_NORMAL, 0, 0, 0, true, st));
+        RUN(eng_run_conv(eng, B.expand, *x, &e1, st, ConvCall().flat_gemm()));
         LAUNCH("dwconv", dwconv_launch(e1.p, B.dw.w, B.dw.bias, d.p, N, e1.h, e1.w, e1.c, B.k, B.stride_h, B.act, st));
         if (B.se) LAUNCH("se_pool", se_pool_launch(d.p, pool, N, d.h, d.w, d.c, st));   // the same sums in the same order
     }
@@ -760,7 +795,7 @@ static int run_mv3_block(lumina_ocr* eng, const RecBlock& B, const std::string& 
         se_gate_ptr = gate;   // the scaling itself is fused into the project conv's operand staging
     }
     Tensor4 o = ws_tensor(eng, N, d.h, d.w, cp16(B.cout));
-    RUN(eng_run_conv(eng, B.project, d, &o, B.res ? x : nullptr, 0, OUT_NORMAL, 0, 0, 0, true, st, se_gate_ptr));
+    RUN(eng_run_conv(eng, B.project, d, &o, st, ConvCall().flat_gemm().residual(B.res ? x : nullptr).gated(se_gate_ptr)));
     tap(eng, name.c_str(), o);
     *x = o;
     return 0;
@@ -770,25 +805,17 @@ static int rec_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* wid
     const bool dry = eng->arena.counting();
     const int T = 80;
     Tensor4 x = ws_tensor(eng, N, 16, 160, 16);
-    if (!dry && x.p) {
-        StemParams sp{};
-        sp.x = crops; sp.wpk = eng->rstem_wpk; sp.bias = eng->rstem_bias; sp.y = x.p; sp.valid_w_per_img = widths;
-        sp.N = N; sp.H = 32; sp.W = 320; sp.valid_h = 32; sp.valid_w = 320; sp.Ho = 16; sp.Wo = 160; sp.Cout_store = 16;
-        sp.act = ACT_HSWISH;
-        for (int c = 0; c < 3; ++c) { sp.scale[c] = 2.0f / 255.0f; sp.shift[c] = -1.0f; }
-        hipError_t e = stem_conv_launch(sp, st);
-        if (e != hipSuccess) return locr_fail(eng, "rec.conv1", hipGetErrorString(e));
-    }
+    RUN(run_stem(eng, "rec.conv1", crops, widths, N, 32, 320, eng->rstem_wpk, eng->rstem_bias, ACT_HSWISH, STEM_SCALE_PM1, STEM_SHIFT_PM1, x, st));
     tap(eng, "rec.conv1", x);
     for (size_t bi = 0; bi < eng->rblocks.size(); ++bi) RUN(run_mv3_block(eng, eng->rblocks[bi], "rec.b" + std::to_string(bi), &x, st));
     Tensor4 f = ws_tensor(eng, N, x.h, x.w, 288);
-    RUN(eng_run_conv(eng, eng->rconv2, x, &f, nullptr, 0, OUT_NORMAL, 0, 0, 0, true, st)); tap(eng, "rec.conv2", f);
+    RUN(eng_run_conv(eng, eng->rconv2, x, &f, st, ConvCall().flat_gemm())); tap(eng, "rec.conv2", f);
     Tensor4 seq = ws_tensor(eng, N, 1, T, 288);
     LAUNCH("rec.pool", maxpool_launch(f.p, seq.p, N, f.h, f.w, 288, 2, 2, 0, 1, T, st));
     tap(eng, "rec.feat", seq);
     for (int l = 0; l < 2; ++l) {
         Tensor4 xp = ws_tensor(eng, N, 1, T, 8 * 96);
-        RUN(eng_run_conv(eng, eng->xproj[l], seq, &xp, nullptr, 0, OUT_NORMAL, 0, 0, 0, true, st));
+        RUN(eng_run_conv(eng, eng->xproj[l], seq, &xp, st, ConvCall().flat_gemm()));
         Tensor4 hs = ws_tensor(eng, N, 1, T, 2 * 96);
         {
             LaunchTimer tm(eng, st, !dry);
@@ -828,19 +855,7 @@ int eng_load_cls(lumina_ocr* eng, const void* blob, size_t n) {
     eng->cls_loaded = false;
     const double scale = 0.35;
     const int c0 = make_div(16 * scale);
-    {
-        const HostBlobTensor *w, *b;
-        if (!get_wb(eng, m, "cls.conv1", &w, &b)) return 1;
-        if (w->dims.size() != 4 || w->dims[0] != c0 || w->dims[1] != 3 || w->dims[2] != 3 || w->dims[3] != 3 || b->dims[0] != c0)
-            return locr_fail(eng, "cls.conv1", "shape");
-        bf16_t packed[2 * 2 * 32 * 8];
-        pack_stem_weights(reinterpret_cast<const bf16_t*>(w->data), c0, packed);
-        float bias[32] = {0};
-        memcpy(bias, b->data, sizeof(float) * c0);
-        eng->cstem_wpk = static_cast<bf16_t*>(eng_upload(eng, packed, sizeof(packed)));
-        eng->cstem_bias = static_cast<float*>(eng_upload(eng, bias, sizeof(bias)));
-        if (!eng->cstem_wpk || !eng->cstem_bias) return locr_fail(eng, "upload", "cls.conv1");
-    }
+    RUN(load_stem(eng, m, "cls.conv1", c0, &eng->cstem_wpk, &eng->cstem_bias));
     static const int sh[11] = {2, 2, 1, 2, 1, 1, 1, 1, 2, 1, 1};
     if (load_mv3_blocks(eng, m, "cls", scale, sh, c0, &eng->cblocks)) return 1;
     const int cin = eng->cblocks.back().cout;
@@ -865,19 +880,11 @@ static int cls_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* wid
                            hipStream_t st) {
     const bool dry = eng->arena.counting();
     Tensor4 x = ws_tensor(eng, N, CLS_H / 2, CLS_W / 2, 16);
-    if (!dry && x.p) {
-        StemParams sp{};
-        sp.x = crops; sp.wpk = eng->cstem_wpk; sp.bias = eng->cstem_bias; sp.y = x.p; sp.valid_w_per_img = widths;
-        sp.N = N; sp.H = CLS_H; sp.W = CLS_W; sp.valid_h = CLS_H; sp.valid_w = CLS_W; sp.Ho = x.h; sp.Wo = x.w; sp.Cout_store = 16;
-        sp.act = ACT_HSWISH;
-        for (int c = 0; c < 3; ++c) { sp.scale[c] = 2.0f / 255.0f; sp.shift[c] = -1.0f; }
-        hipError_t e = stem_conv_launch(sp, st);
-        if (e != hipSuccess) return locr_fail(eng, "cls.conv1", hipGetErrorString(e));
-    }
+    RUN(run_stem(eng, "cls.conv1", crops, widths, N, CLS_H, CLS_W, eng->cstem_wpk, eng->cstem_bias, ACT_HSWISH, STEM_SCALE_PM1, STEM_SHIFT_PM1, x, st));
     tap(eng, "cls.conv1", x);
     for (size_t bi = 0; bi < eng->cblocks.size(); ++bi) RUN(run_mv3_block(eng, eng->cblocks[bi], "cls.b" + std::to_string(bi), &x, st));
     Tensor4 f = ws_tensor(eng, N, x.h, x.w, eng->cconv2.cout);
-    RUN(eng_run_conv(eng, eng->cconv2, x, &f, nullptr, 0, OUT_NORMAL, 0, 0, 0, true, st)); tap(eng, "cls.conv2", f);
+    RUN(eng_run_conv(eng, eng->cconv2, x, &f, st, ConvCall().flat_gemm())); tap(eng, "cls.conv2", f);
     if (f.h != 2 || f.w % 2) return locr_fail(eng, "cls_forward", "unexpected feature map");
     Tensor4 feat = ws_tensor(eng, N, 1, f.w / 2, f.c);
     LAUNCH("cls.pool", maxpool_launch(f.p, feat.p, N, f.h, f.w, f.c, 2, 2, 0, 1, feat.w, st));
@@ -909,15 +916,6 @@ static float* upload_f32(lumina_ocr* eng, const std::map<std::string, HostBlobTe
     return static_cast<float*>(eng_upload(eng, it->second.data, sizeof(float) * n));
 }
 
-static inline uint16_t bf16_bits_to(uint16_t b, int dtype) {   // bf16 bits -> the model's storage type (fp16: exact for |w| >= 2^-14)
-    if (!dtype) return b;
-    uint32_t u = (uint32_t)b << 16;
-    float f; memcpy(&f, &u, 4);
-    const _Float16 hv = (_Float16)f;
-    uint16_t o; memcpy(&o, &hv, 2);
-    return o;
-}
-
 // name.w [N][ks][ks][cin] bf16 (+ name.b) -> SvtrLinear with w [N][taps * cin_pad] in the storage type; ln != "" fuses that LayerNorm
 static bool make_linear(lumina_ocr* eng, const std::map<std::string, HostBlobTensor>& m, const std::string& name, int ks, int cin, int cin_pad, int N, int act,
                         const std::string& ln, int dtype, bool flat_k, SvtrLinear* L) {
@@ -936,7 +934,7 @@ static bool make_linear(lumina_ocr* eng, const std::map<std::string, HostBlobTen
         for (int t = 0; t < taps; ++t)
             for (int c = 0; c < cin; ++c)
                 packed[(size_t)n * K + (flat_k ? t * cin + c : t * cin_pad + c)] = bf16_bits_to(src[((size_t)n * taps + t) * cin + c], dtype);
-    L->K = K; L->N = N; L->taps = flat_k ? 1 : taps; L->cin = flat_k ? cin_pad : cin_pad; L->act = act;
+    L->K = K; L->N = N; L->taps = flat_k ? 1 : taps; L->cin = cin_pad; L->act = act;
     L->w = static_cast<uint16_t*>(eng_upload(eng, packed.data(), packed.size() * 2));
     L->bias = static_cast<float*>(eng_upload(eng, b->data, sizeof(float) * N));
     if (!ln.empty()) {
@@ -1003,34 +1001,27 @@ int eng_load_svtr(lumina_ocr* eng, const void* blob, size_t n) {
         }
     }
     if (!make_linear(eng, m, "svtr.last", 1, M.dims[2], M.dims[2], M.out_ch, ACT_HSWISH, "", dt, false, &M.last)) return 1;
-    {
-        auto w = m.find("svtr.ctc.fc.w"), b = m.find("svtr.ctc.fc.b");
-        if (w == m.end() || b == m.end() || w->second.dims.size() != 2 || w->second.dims[1] != M.out_ch) return locr_fail(eng, "svtr.ctc.fc", "missing/shape");
-        const int C = w->second.dims[0];
-        M.num_classes = C; M.ctc_ntiles = (C + 63) / 64;
-        std::vector<bf16_t> conv((size_t)C * M.out_ch);
-        const bf16_t* src = reinterpret_cast<const bf16_t*>(w->second.data);
-        for (size_t i = 0; i < conv.size(); ++i) conv[i] = bf16_bits_to(src[i], dt);
-        std::vector<bf16_t> packed(ctc_packed_weight_elems(C, M.out_ch));
-        pack_ctc_weights(conv.data(), C, M.out_ch, packed.data());
-        std::vector<float> bias((size_t)M.ctc_ntiles * 64, -1.0e30f);
-        memcpy(bias.data(), b->second.data, sizeof(float) * C);
-        M.ctc_wpk = static_cast<bf16_t*>(eng_upload(eng, packed.data(), packed.size() * sizeof(bf16_t)));
-        M.ctc_bias = static_cast<float*>(eng_upload(eng, bias.data(), bias.size() * sizeof(float)));
-        if (!M.ctc_wpk || !M.ctc_bias) return locr_fail(eng, "upload", "svtr ctc");
-    }
+    RUN(load_ctc_head(eng, m, "svtr.ctc.fc", M.out_ch, dt, &M.num_classes, &M.ctc_ntiles, &M.ctc_wpk, &M.ctc_bias));
     M.loaded = true;
     return 0;
 }
 
+// What a run_linear call asks for beyond a plain linear layer without residual.
+struct LinearCall {
+    const bf16_t* res = nullptr; int res_mod = 0, res_post = 0;   // SvtrGemmParams: residual [M][N], or a table of res_mod rows added after the activation
+    int hin = 1, win = 1, hout = 1, wout = 1, sh = 1, sw = 1;     // gather geometry of a 3x3 conv (1x1: none)
+    LinearCall& residual(const bf16_t* r) { res = r; return *this; }
+    LinearCall& add_table_after_act(const bf16_t* table, int rows) { res = table; res_mod = rows; res_post = 1; return *this; }
+    LinearCall& conv3x3(const Tensor4& in, const Tensor4& out) { hin = in.h; win = in.w; hout = out.h; wout = out.w; sh = in.h / out.h; sw = in.w / out.w; return *this; }
+};
+
 // one svtr_gemm launch: y = epi(gather(x) w^T + b)
-static int run_linear(lumina_ocr* eng, const SvtrLinear& L, const Tensor4& x, Tensor4* y, const bf16_t* res, int res_mod, int res_post, int hin, int win,
-                      int hout, int wout, int sh, int sw, hipStream_t st) {
+static int run_linear(lumina_ocr* eng, const SvtrLinear& L, const Tensor4& x, Tensor4* y, hipStream_t st, const LinearCall& c = {}) {
     if (x.p == nullptr || y->p == nullptr) return ws_null(eng, "svtr linear");  // dry run (workspace sizing)
     SvtrGemmParams p{};
-    p.x = x.p; p.w = L.w; p.bias = L.bias; p.res = res; p.res_mod = res_mod; p.res_post = res_post; p.gamma = L.gamma; p.beta = L.beta; p.y = y->p;
+    p.x = x.p; p.w = L.w; p.bias = L.bias; p.res = c.res; p.res_mod = c.res_mod; p.res_post = c.res_post; p.gamma = L.gamma; p.beta = L.beta; p.y = y->p;
     p.zeros = zero_block(eng); p.M = (int)(y->elems() / L.N); p.K = L.K; p.N = L.N; p.act = L.act; p.eps = 1e-6f;
-    p.taps = L.taps; p.Cin = L.cin; p.Hin = hin; p.Win = win; p.Tout = hout * wout; p.Wout = wout; p.sh = sh; p.sw = sw;
+    p.taps = L.taps; p.Cin = L.cin; p.Hin = c.hin; p.Win = c.win; p.Tout = c.hout * c.wout; p.Wout = c.wout; p.sh = c.sh; p.sw = c.sw;
     if (!p.zeros) return locr_fail(eng, "svtr", "zero block upload failed");
     if (x.c != L.cin || y->c != L.N) return locr_fail(eng, "svtr linear: channel mismatch", "");
     LaunchTimer tm(eng, st);
@@ -1038,7 +1029,7 @@ static int run_linear(lumina_ocr* eng, const SvtrLinear& L, const Tensor4& x, Te
     if (e != hipSuccess) return locr_fail(eng, "svtr_gemm", hipGetErrorString(e));
     // algorithmic bytes: the input tensor, the weights, the result and the residual once (a 9-tap gather re-reads its input from cache)
     tm.done("svtr.linear", svtr_gemm_kernel_name(p, eng->svtr.dtype), 2.0 * p.M * p.K * p.N,
-            2.0 * ((double)x.elems() + (double)p.N * p.K + (double)p.M * p.N + (res && res_mod == 0 ? (double)p.M * p.N : 0.0)));
+            2.0 * ((double)x.elems() + (double)p.N * p.K + (double)p.M * p.N + (c.res && c.res_mod == 0 ? (double)p.M * p.N : 0.0)));
     return 0;
 }
 
@@ -1049,9 +1040,9 @@ static int svtr_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* wi
     Tensor4 patches = ws_tensor(eng, N, 16, 160, 32);
     LAUNCH("svtr.im2col", svtr_im2col_launch(crops, widths, patches.p, N, dt, st));
     Tensor4 e1 = ws_tensor(eng, N, 16, 160, d0 / 2);
-    RUN(run_linear(eng, M.pe1, patches, &e1, nullptr, 0, 0, 1, 1, 1, 1, 1, 1, st));
+    RUN(run_linear(eng, M.pe1, patches, &e1, st));
     Tensor4 x = ws_tensor(eng, N, 8, 80, d0);   // patch embedding 2 (3x3 / s2, GELU, rounded) + positional embedding (rounded again)
-    RUN(run_linear(eng, M.pe2, e1, &x, M.pos, 640, 1, 16, 160, 8, 80, 2, 2, st));
+    RUN(run_linear(eng, M.pe2, e1, &x, st, LinearCall().conv3x3(e1, x).add_table_after_act(M.pos, 640)));
     tap(eng, "svtr.embed", x);
     int stage = 0;
     for (size_t bi = 0; bi < M.blocks.size(); ++bi) {
@@ -1060,13 +1051,13 @@ static int svtr_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* wi
         if (want_stage != stage) {
             // height merging: 3x3 conv, stride (2, 1), + LayerNorm (fused epilogue)
             Tensor4 y = ws_tensor(eng, N, x.h / 2, x.w, M.dims[stage + 1]);
-            RUN(run_linear(eng, M.sub[stage], x, &y, nullptr, 0, 0, x.h, x.w, x.h / 2, x.w, 2, 1, st));
+            RUN(run_linear(eng, M.sub[stage], x, &y, st, LinearCall().conv3x3(x, y)));
             tap(eng, stage == 0 ? "svtr.sub0" : "svtr.sub1", y);
             x = y; ++stage;
         }
         const int Tk = x.h * x.w, c = B.dim;
         Tensor4 qkv = ws_tensor(eng, N, x.h, x.w, 3 * c);
-        RUN(run_linear(eng, B.qkv, x, &qkv, nullptr, 0, 0, 1, 1, 1, 1, 1, 1, st));
+        RUN(run_linear(eng, B.qkv, x, &qkv, st));
         Tensor4 att = ws_tensor(eng, N, x.h, x.w, c);
         {
             LaunchTimer tm(eng, st, !dry);
@@ -1075,18 +1066,18 @@ static int svtr_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* wi
             tm.done("svtr.attn", std::string("svtr_attn_kernel<") + (dt ? "1>" : "0>"), 4.0 * N * Tk * keys * c, 2.0 * N * Tk * 4.0 * c);
         }
         Tensor4 x1 = ws_tensor(eng, N, x.h, x.w, c);
-        RUN(run_linear(eng, B.proj, att, &x1, x.p, 0, 0, 1, 1, 1, 1, 1, 1, st));        // + residual, LayerNorm 1
+        RUN(run_linear(eng, B.proj, att, &x1, st, LinearCall().residual(x.p)));   // + residual, LayerNorm 1
         Tensor4 f1 = ws_tensor(eng, N, x.h, x.w, 4 * c);
-        RUN(run_linear(eng, B.fc1, x1, &f1, nullptr, 0, 0, 1, 1, 1, 1, 1, 1, st));
+        RUN(run_linear(eng, B.fc1, x1, &f1, st));
         Tensor4 x2 = ws_tensor(eng, N, x.h, x.w, c);
-        RUN(run_linear(eng, B.fc2, f1, &x2, x1.p, 0, 0, 1, 1, 1, 1, 1, 1, st));         // + residual, LayerNorm 2
+        RUN(run_linear(eng, B.fc2, f1, &x2, st, LinearCall().residual(x1.p)));   // + residual, LayerNorm 2
         tap(eng, ("svtr.b" + std::to_string(bi)).c_str(), x2);
         x = x2;
     }
     Tensor4 pooled = ws_tensor(eng, N, 1, T, M.dims[2]);
     LAUNCH("svtr.pool", svtr_rowmean_launch(x.p, pooled.p, N, x.h, x.w, M.dims[2], dt, st));
     Tensor4 seq = ws_tensor(eng, N, 1, T, M.out_ch);
-    RUN(run_linear(eng, M.last, pooled, &seq, nullptr, 0, 0, 1, 1, 1, 1, 1, 1, st));
+    RUN(run_linear(eng, M.last, pooled, &seq, st));
     tap(eng, "svtr.seq", seq);
     if (!dry) {
         CtcFcParams cp{};
