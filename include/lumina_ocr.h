@@ -240,6 +240,31 @@ int lumina_ocr_rules_and_marks_round(lumina_ocr_t* h, const uint8_t* pages_dev, 
                                      int32_t* mark_counts_dev, int out_max, int ring_div, int band_div, int band_min, int32_t* round_dev,
                                      int32_t* round_counts_dev, void* stream);
 
+/* Barcodes: Code 128 and Code 39 strips of the pages, read on the device (the host half is lumina_ocr/utils/barcodes.py).  ink as in
+ * lumina_ocr_table_rules.  A row of the ink is a list of runs; its elements are the run widths (bars) and the gaps between them.
+ * Read from a bar to the right, or to the left (a strip printed upside down: flags bit 0), symbol k of a Code 128 is elements
+ * 6 k .. 6 k + 5 (11 modules), of a Code 39 elements 10 k .. 10 k + 8 (15 modules, wide = 3) with element 10 k + 9 the gap between
+ * characters.  A symbol of S pixels is matched against every pattern p of its table by d = sum |w_i M - p_i S|: the lowest d wins,
+ * ties go to the lowest value, d > max_dist S M / 256 rejects.  A Code 128 reads when symbol 0 is a start (103-105), the first stop
+ * (106: its first six elements, then a bar of 1.5 .. 2.5 modules) is symbol k >= 2, the symbols between are <= 102 and the mod-103
+ * checksum holds; a Code 39 when symbol 0 is `*` (43), the first later `*` ends it, and every gap between characters is at most two
+ * modules.  2..64 symbols; the gap before the start is at least `quiet` module widths of the start symbol (the page edge is quiet).
+ * Scanning a row bar by bar to the right a read claims its bars, the same to the left; a read to the left that shares a bar with one
+ * to the right is dropped, and the four leftmost reads are the row's.  Columns are read the same way on the transposed mask (flags
+ * bit 1: top to bottom, or reversed).  Reads of one direction join when kind, reversal and symbols are equal, their ranges along the
+ * code overlap and their rows are at most row_gap apart; a group of at least min_rows reads is a barcode, its box the hull.
+ * codes_dev int32 [n][max_codes][8] = x0, y0, x1, y1 (inclusive), kind (0 Code 128, 1 Code 39), nsym, rows (the reads of the group),
+ * flags, sorted by (y0, x0, y1, x1, first read in row-then-column raster order), rows past the count untouched; syms_dev int32
+ * [n][max_codes][64] = the symbol values in reading order (Code 128: start, data, check, stop; Code 39: character indices with both
+ * `*`), zero behind nsym; counts_dev int32 [n] = the true number (a list whose count exceeds max_codes is not written).  mask_in_dev:
+ * optional, the ink mask of these pages at this threshold (as hmask_dev of lumina_ocr_table_rules), computed already; mask_out_dev:
+ * optional parity hook, receives the mask.  0 <= quiet <= 64, 0 <= max_dist <= 256, min_rows >= 1, 1 <= row_gap <= 16, max_codes
+ * 1..256, sides 1..65535; defaults in lumina_ocr/arch.py BARCODE_PARAMS.  Integer arithmetic throughout: the result is defined bit for
+ * bit (tests/barcode_reference.py).  Asynchronous; n == 0 is a no-op; bad arguments return a status before anything is written. */
+int lumina_ocr_barcodes(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int quiet, int max_dist,
+                        int min_rows, int row_gap, int max_codes, int32_t* codes_dev, int32_t* syms_dev, int32_t* counts_dev,
+                        const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream);
+
 /* ---- page orientation (optional; DESIGN.md: "Page orientation") ----
  * A page is upright after `turn` quarter turns: upright = np.rot90(page, turn) (counter-clockwise).  The three entries below are the
  * device half; which pages get which turn is decided on the host (lumina_ocr/utils/page_orient.py, OcrPipeline.run_oriented).

@@ -8,6 +8,7 @@
 #include "deskew.h"
 #include "engine.h"
 #include "marks.h"
+#include "barcodes.h"
 #include "ops.h"
 #include "orient.h"
 #include "resize.h"
@@ -678,6 +679,32 @@ int lumina_ocr_rules_and_marks_round(lumina_ocr_t* h, const uint8_t* pages_dev, 
     return rules_and_marks_impl(h, "rules_and_marks_round", pages_dev, n, height, width, threshold, gap, min_len, max_thick, max_rules, hrules_dev,
                                 vrules_dev, rule_counts_dev, min_side, max_side, max_marks, marks_dev, mark_counts_dev, out_max, ring_div, band_div, band_min,
                                 round_dev, round_counts_dev, stream);
+}
+
+int lumina_ocr_barcodes(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int quiet, int max_dist, int min_rows,
+                        int row_gap, int max_codes, int32_t* codes_dev, int32_t* syms_dev, int32_t* counts_dev, const uint64_t* mask_in_dev,
+                        uint64_t* mask_out_dev, void* stream) {
+    if (!h) return 1;
+    if (n == 0) return 0;
+    if (!pages_dev || !codes_dev || !syms_dev || !counts_dev || n < 0) return locr_fail(h, "barcodes", "bad arguments");
+    if (!barcode_params_ok(quiet, max_dist, min_rows, row_gap, max_codes))
+        return locr_fail(h, "barcodes", "parameters must satisfy 0 <= quiet <= 64, 0 <= max_dist <= 256, min_rows >= 1, 1 <= row_gap <= 16, max_codes 1..256");
+    if (barcodes_workspace_bytes(1, height, width, max_codes) == 0) return locr_fail(h, "barcodes", "bad dimensions (sides 1..65535)");
+    BIND(h);
+    API_TRY
+    // the run list is sized for its worst case (8 bytes per two pixels); four read slots a row and a column
+    const auto ws = [&](int nb) { return barcodes_workspace_bytes(nb, height, width, max_codes); };
+    const size_t nw = ((size_t)width + 63) / 64;
+    return for_page_groups(h, n, fit_group(h->post_group, n, ws), ws, [&](int b0, int nb) {
+        BarcodeParams p{};
+        p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.H = height; p.W = width;
+        p.threshold = threshold; p.quiet = quiet; p.max_dist = max_dist; p.min_rows = min_rows; p.row_gap = row_gap; p.max_codes = max_codes;
+        p.codes = codes_dev + (size_t)b0 * max_codes * 8; p.syms = syms_dev + (size_t)b0 * max_codes * BARCODE_MAX_SYMS; p.counts = counts_dev + b0;
+        p.mask_in = mask_in_dev ? reinterpret_cast<const unsigned long long*>(mask_in_dev) + (size_t)b0 * height * nw : nullptr;
+        p.mask_out = mask_out_dev ? reinterpret_cast<unsigned long long*>(mask_out_dev) + (size_t)b0 * height * nw : nullptr;
+        return hip_rc(h, "barcodes", barcodes_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
+    });
+    API_CATCH(h)
 }
 
 size_t lumina_ocr_page_quarter_workspace_bytes(int n, int height, int width) { return n > 0 ? quarter_workspace_bytes(n, height, width) : 0; }

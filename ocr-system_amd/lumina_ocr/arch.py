@@ -466,6 +466,17 @@ MARK_PARAMS = dict(threshold=128, min_side=12, max_side=64, max_marks=256)
 # band_min + min(w, h) / band_div pixels around the box, clipped to the page, is empty.  State from the core as for the checkboxes.
 ROUND_MARK_PARAMS = dict(out_max=0, ring_div=12, band_div=4, band_min=4)
 
+# Barcodes (lumina_ocr_barcodes + utils/barcodes.py, definition restated in tests/barcode_reference.py): ink as above.  A row reads a
+# Code 128 or a Code 39 when every symbol from a start to a stop matches its table within max_dist / 256 of the symbol's width (summed
+# over its elements, in modules), the gap before the start is `quiet` modules wide and, for Code 128, the checksum holds; equal reads
+# at most row_gap rows apart join, and min_rows of them make a barcode.  The issue's proposed values are kept but for max_dist, which
+# the synthetic set moved from 64 to 24: a Code 128 symbol with one element a module too wide (13 px over 12 modules of m px) lies at
+# least 14 m from every pattern and 64 accepts up to 16.5 m, so the widened-bar decoy read whenever its checksum happened to hold; 24
+# accepts 12.4 m and never takes a module's error, while an edge off by one pixel inside a symbol (22 at most) still passes from
+# m = 2 px on.  The nearest pattern wins anyway; the checksum, the stop and min_rows equal reads carry the rest of the rejection.
+# quiet = 5 is half the standard's ten modules: forms crowd their codes.  max_codes = capacity of a page's list (<= 256).
+BARCODE_PARAMS = dict(threshold=MARK_PARAMS["threshold"], quiet=5, max_dist=24, min_rows=8, row_gap=2, max_codes=64)
+
 # Page orientation (lumina_ocr_page_quarter / _page_turn / _page_vote + utils/page_orient.py): ink as above; a page is sideways when the
 # energy of its column profile exceeds `ratio` times that of its row profile (text lines make the profile across them jagged), and an
 # upright-or-upside-down page is upside-down when it has at least min_lines lines and the classifier flips more than half of them.

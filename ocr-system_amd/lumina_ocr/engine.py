@@ -91,6 +91,7 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_deskew_warp": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_table_rules": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
         "lumina_ocr_selection_marks": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+        "lumina_ocr_barcodes": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
         "lumina_ocr_rules_and_marks": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_selection_marks_round": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_rules_and_marks_round": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp,
@@ -124,7 +125,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_png_probe", "lumina_ocr_png_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
     "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks", "lumina_ocr_selection_marks_round",
-    "lumina_ocr_rules_and_marks_round",
+    "lumina_ocr_rules_and_marks_round", "lumina_ocr_barcodes",
     "lumina_ocr_page_quarter_workspace_bytes", "lumina_ocr_page_quarter", "lumina_ocr_page_turn", "lumina_ocr_page_vote",
 ]
 
@@ -555,6 +556,30 @@ class Engine:
         self._chk(self.lib.lumina_ocr_selection_marks(self._h, _ptr(pages), n, h, w, threshold, min_side, max_side, max_marks, _ptr(marks),
                                                       _ptr(counts), _ptr(mask), self._stream()))
         return (marks, counts, mask) if debug else (marks, counts)
+
+    # -- barcodes (Code 128 and Code 39; the host half is utils/barcodes.py) ------------------------------------------------------
+    def barcodes(self, pages, threshold=None, quiet=None, max_dist=None, min_rows=None, row_gap=None, max_codes=None, mask_in=None,
+                 debug: bool = False):
+        """uint8 [n,H,W,3] device -> (codes int32 [n,max_codes,8], syms int32 [n,max_codes,64], counts int32 [n]) on the device: the
+        barcodes of each page as x0, y0, x1, y1, kind (0 Code 128, 1 Code 39), nsym, rows, flags (bit 0 reversed, bit 1 vertical),
+        sorted by (y0, x0, y1, x1), with their symbol values; counts = the true numbers (a list whose count exceeds max_codes is not
+        written).  Parameters default to arch.BARCODE_PARAMS.  mask_in: the ink mask of the pages at this threshold, int64
+        [n,H,ceil(W/64)], when it is there already.  Asynchronous.  debug=True also returns the ink mask the pass worked on."""
+        torch = _torch()
+        n, h, w, c = pages.shape
+        assert c == 3 and pages.dtype == torch.uint8 and pages.is_contiguous()
+        bp = arch.BARCODE_PARAMS
+        threshold, quiet, max_dist, min_rows, row_gap, max_codes = (bp[k] if v is None else int(v) for k, v in (
+            ("threshold", threshold), ("quiet", quiet), ("max_dist", max_dist), ("min_rows", min_rows), ("row_gap", row_gap), ("max_codes", max_codes)))
+        if mask_in is not None:
+            assert mask_in.dtype == torch.int64 and mask_in.is_contiguous() and tuple(mask_in.shape) == (n, h, (w + 63) // 64)
+        codes = torch.zeros((n, max(max_codes, 0), 8), dtype=torch.int32, device=pages.device)
+        syms = torch.zeros((n, max(max_codes, 0), 64), dtype=torch.int32, device=pages.device)
+        counts = torch.zeros((n,), dtype=torch.int32, device=pages.device)
+        mask = torch.zeros((n, h, (w + 63) // 64), dtype=torch.int64, device=pages.device) if debug else None
+        self._chk(self.lib.lumina_ocr_barcodes(self._h, _ptr(pages), n, h, w, threshold, quiet, max_dist, min_rows, row_gap, max_codes, _ptr(codes),
+                                               _ptr(syms), _ptr(counts), _ptr(mask_in), _ptr(mask), self._stream()))
+        return (codes, syms, counts, mask) if debug else (codes, syms, counts)
 
     def rules_and_marks(self, pages, threshold=None, gap=None, min_len=None, max_thick=None, max_rules=None, min_side=None, max_side=None,
                         max_marks=None):

@@ -29,6 +29,7 @@ from PIL import Image
 
 from .. import arch
 from ..utils import layout
+from ..utils import barcodes as barcode_layout
 from ..utils import marks as mark_layout
 from ..utils import page_orient
 from ..utils import tables as table_layout
@@ -135,6 +136,9 @@ class OCRService:
         # LUMINA_OCR_RADIO_BUTTONS=1 (with LUMINA_OCR_SELECTION_MARKS=1; alone it is an error): radio buttons become `selection_mark` entries
         # and tokens exactly as checkboxes do (Azure's selection marks cover both).  Off by default: every output is then the one without it.
         self._use_round_marks = os.environ.get("LUMINA_OCR_RADIO_BUTTONS", "0").lower() not in ("", "0", "false", "no")
+        # LUMINA_OCR_BARCODES=1: Code 128 and Code 39 strips become `barcode` entries with their decoded content and a `:barcode: <content>`
+        # line of the Markdown; the text lines the detector found on a strip are dropped.  Off by default: every output is then the one without it.
+        self._use_barcodes = os.environ.get("LUMINA_OCR_BARCODES", "0").lower() not in ("", "0", "false", "no")
         # LUMINA_OCR_PAGE_ORIENTATION=1: pages lying sideways or upside-down are turned upright on the device before anything else reads
         # them (after decode and EXIF orientation, before the resize), and json_output reports page_rotation.  It uses the classifier
         # (LUMINA_OCR_CLS_WEIGHTS) whether or not LUMINA_OCR_USE_ANGLE_CLS is set.  Off by default: every output is then the one without it.
@@ -208,7 +212,8 @@ class OCRService:
                                            % (len(charset), "SVTR" if svtr else "CRNN", n_cls))
                     pipeline = OcrPipeline(eng, charset=charset, max_dimension=self.max_dimension, post=post, recognizer=self._recognizer,
                                            angle_cls=self._use_angle_cls, tables=self._use_tables, marks=self._use_marks,
-                                           page_orient=self._use_page_orient, word_boxes=self._use_word_boxes, round_marks=self._use_round_marks)
+                                           page_orient=self._use_page_orient, word_boxes=self._use_word_boxes, round_marks=self._use_round_marks,
+                                           barcodes=self._use_barcodes)
             except Exception:
                 eng.close()
                 raise
@@ -287,9 +292,16 @@ class OCRService:
 
     def _finish_page(self, det, jpeg: bytes, processed_hw, page_number: int, original_size, t0: float) -> OCROutput:
         triples = det.triples()
+        line_words = det.line_words() if getattr(det, "word_counts", None) is not None else None   # LUMINA_OCR_WORD_BOXES=1
+        codes = None
+        if getattr(det, "barcodes", None) is not None:   # LUMINA_OCR_BARCODES=1: what the recogniser made of the bars is no text
+            codes = barcode_layout.read_barcodes(det.barcodes, det.barcode_syms)
+            keep = [i for i, t in enumerate(triples) if not barcode_layout.inside_any(t[0], codes)]
+            if len(keep) < len(triples):
+                triples = [triples[i] for i in keep]
+                line_words = None if line_words is None else [line_words[i] for i in keep]
         merged, ordered = layout.reading_order(triples)
         words = None
-        line_words = det.line_words() if getattr(det, "word_counts", None) is not None else None   # LUMINA_OCR_WORD_BOXES=1
         if line_words is not None:   # reading_order hands the same tuples back in another order: the words follow their lines
             at = {id(t): i for i, t in enumerate(triples)}
             words = [line_words[at[id(t)]] for t in ordered]
@@ -301,19 +313,23 @@ class OCRService:
         if getattr(det, "marks", None) is not None:   # LUMINA_OCR_SELECTION_MARKS=1 [+ LUMINA_OCR_RADIO_BUTTONS=1]
             rounds = getattr(det, "round_marks", None)
             found = mark_layout.select_marks(det.marks) if rounds is None else mark_layout.select_marks(det.marks, rounds)
-        if found:
+        if codes:
+            md = layout.page_markdown(merged, tabs, marks=found or None, barcodes=codes)
+        elif found:
             md = layout.page_markdown(merged, tabs, marks=found)
         else:
             md = layout.page_markdown(merged, tabs) if tabs else layout.page_markdown(merged)
         paragraphs = layout.build_paragraph_boxes(merged, page_number)
         # words, lines, selection marks, tables with their cells, paragraphs: the order of ocr_service.py:285-367
         boxes = ((layout.build_layout_boxes(ordered, page_number) if words is None else layout.build_layout_boxes(ordered, page_number, words=words))
-                 + layout.build_mark_boxes(found or [], page_number)
+                 + layout.build_mark_boxes(found or [], page_number) + layout.build_barcode_boxes(codes or [], page_number)
                  + layout.build_table_boxes(tabs, page_number) + paragraphs)
         counts = {"page_count": 1, "words_count": sum(1 for b in boxes if b["type"] == "word"), "lines_count": len(ordered),
                   "tables_count": len(tabs), "paragraphs_count": len(paragraphs)}
         if found is not None:
             counts["selection_marks_count"] = len(found)
+        if codes is not None:
+            counts["barcodes_count"] = len(codes)
         if getattr(det, "turn", None) is not None:   # LUMINA_OCR_PAGE_ORIENTATION=1
             counts["page_rotation"] = page_orient.page_rotation(det.turn)
         ph, pw = processed_hw
@@ -619,7 +635,7 @@ class OCRService:
     # ---- status (:759-795) ----
     def get_status(self) -> Dict[str, Any]:
         st = {"client_initialized": self._pipeline is not None, "model_id": "dbnet-r18vd+crnn-mv3", "max_dimension": self.max_dimension,
-              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
+              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
         if self._engine is not None:
             st["engine_version"] = self._engine.version()
             st["num_classes"] = self._engine.num_classes

@@ -412,3 +412,192 @@ def synth_round_decoys(seed: int, h: int = 1100, w: int = 1500, noise: float = 0
     if noise > 0:
         arr = arr + rng.normal(0.0, noise, arr.shape).astype(np.float32)
     return np.clip(np.rint(arr), 0, 255).astype(np.uint8), gt
+
+
+# ---- barcodes (Code 128, Code 39): an encoder of our own (no barcode library exists offline); tables in utils/barcodes.py ----
+def code128_symbols(text: str) -> List[int]:
+    """ASCII text -> the symbol values start, data ..., check, stop with an automatic choice of code sets: runs of four or more digits
+    (an even count of them) go to set C, control characters need set A, lower case needs set B; a single character of the other set
+    among characters of the current one takes a SHIFT, more of them a code switch."""
+    from .utils import barcodes as bc
+    if not text or any(ord(c) > 127 for c in text):
+        raise ValueError("Code 128 text must be non-empty ASCII")
+
+    def digits_at(i):
+        j = i
+        while j < len(text) and text[j].isdigit():
+            j += 1
+        return j - i
+
+    def need(c):   # the set a character needs, or None when both A and B hold it
+        return "A" if ord(c) < 32 else "B" if ord(c) >= 96 else None
+
+    def first_need(i):
+        for c in text[i:]:
+            if need(c):
+                return need(c)
+        return "B"
+
+    n0 = digits_at(0)
+    cur = "C" if n0 >= 4 or (n0 == len(text) and n0 % 2 == 0) else first_need(0)
+    vals = [{"A": bc.C128_START_A, "B": bc.C128_START_B, "C": bc.C128_START_C}[cur]]
+    i = 0
+    while i < len(text):
+        nd = digits_at(i)
+        if cur == "C":
+            if nd >= 2:
+                vals.append(int(text[i:i + 2]))
+                i += 2
+                continue
+            cur = first_need(i)
+            vals.append(101 if cur == "A" else 100)
+            continue
+        if nd >= 4 and (nd % 2 == 0 or nd >= 5):
+            if nd % 2:                 # an odd run: its first digit stays in the current set
+                vals.append(ord(text[i]) - 32)
+                i += 1
+            vals.append(99)
+            cur = "C"
+            continue
+        c = text[i]
+        want = need(c)
+        if want and want != cur:
+            nxt = need(text[i + 1]) if i + 1 < len(text) else None
+            if nxt != want and (i + 1 < len(text)):
+                vals.append(98)        # SHIFT: this character alone
+                vals.append(ord(c) - 32 if want == "B" else ord(c) + 64)
+                i += 1
+                continue
+            vals.append(101 if want == "A" else 100)
+            cur = want
+        vals.append(ord(c) + 64 if ord(c) < 32 else ord(c) - 32)
+        i += 1
+    check = (vals[0] + sum(k * v for k, v in enumerate(vals[1:], 1))) % 103
+    return vals + [check, bc.C128_STOP]
+
+
+def code39_symbols(text: str) -> List[int]:
+    """Text over Code 39's 43 characters -> the character indices * text *."""
+    from .utils import barcodes as bc
+    if any(c == "*" or c not in bc.CODE39_CHARS for c in text):
+        raise ValueError("not a Code 39 text: %r" % text)
+    return [bc.C39_STAR] + [bc.CODE39_CHARS.index(c) for c in text] + [bc.C39_STAR]
+
+
+def barcode_modules(symbols, kind: str) -> List[int]:
+    """Symbol values -> the element widths in modules, bar first, bars and spaces alternating."""
+    from .utils import barcodes as bc
+    el: List[int] = []
+    if kind == "Code128":
+        for v in symbols:
+            el += [int(c) for c in (bc.CODE128_STOP if v == bc.C128_STOP else bc.CODE128_PATTERNS[v])]
+    elif kind == "Code39":
+        for k, v in enumerate(symbols):
+            el += ([1] if k else []) + [int(c) for c in bc.CODE39_PATTERNS[v]]
+    else:
+        raise ValueError(kind)
+    return el
+
+
+def barcode_length(symbols, kind: str, module_px: int) -> int:
+    return module_px * sum(barcode_modules(symbols, kind))
+
+
+def render_barcode(page: np.ndarray, x: int, y: int, symbols, kind: str, module_px: int, height: int, reversed: bool = False,
+                   vertical: bool = False, ink: int = 0) -> Tuple[int, int, int, int]:
+    """Draw exact module-wide bars into page (uint8 [H,W,3], in place) from (x, y): along x and `height` rows tall, or with vertical
+    along y and `height` columns wide; reversed draws the elements from the far end (a strip printed upside down).
+    -> the box (x0, y0, x1, y1), inclusive."""
+    el = barcode_modules(symbols, kind)
+    if reversed:
+        el = el[::-1]
+    length = module_px * sum(el)
+    if x < 0 or y < 0 or (y + length > page.shape[0] or x + height > page.shape[1] if vertical else x + length > page.shape[1] or y + height > page.shape[0]):
+        raise ValueError("the barcode does not fit the page")
+    pos = 0
+    for i, m in enumerate(el):
+        if i % 2 == 0:
+            a, b = pos, pos + m * module_px
+            if vertical:
+                page[y + a:y + b, x:x + height] = ink
+            else:
+                page[y:y + height, x + a:x + b] = ink
+        pos += m * module_px
+    return (x, y, x + height - 1, y + length - 1) if vertical else (x, y, x + length - 1, y + height - 1)
+
+
+def synth_barcode_page(seed: int, h: int = 700, w: int = 1000, n_codes: int = 3, text_lines: int = 6, module_px: int = 0,
+                       allow_vertical: bool = True) -> Tuple[np.ndarray, List[dict]]:
+    """White page with text lines in its upper part and n_codes barcodes below them, each in a cell of its own with a clear margin:
+    seeded kinds, texts, module widths (2-4 px unless given), heights, reversed and vertical ones.
+    -> (uint8 [h,w,3], [dict(kind, text, symbols, box, reversed, vertical)])"""
+    rng = np.random.default_rng(seed)
+    top = h // 3 if text_lines else 0
+    page = np.full((h, w, 3), 255, np.uint8)
+    if text_lines:
+        page[:top] = synth_page(top, w, seed + 1000, n_lines=text_lines, noise=0.0)[0]
+    gt = []
+    cell_w = w // max(n_codes, 1)
+    for i in range(n_codes):
+        mp = module_px or int(rng.integers(2, 5))
+        kind = "Code39" if rng.integers(0, 3) == 0 else "Code128"
+        vertical = bool(allow_vertical and rng.integers(0, 4) == 0)
+        along = (h - top - 40) if vertical else cell_w - 20 - 12 * mp
+        for n_chars in range(12, 0, -1):
+            if kind == "Code39":
+                text = "".join("ABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789-. $/+%"[int(k)] for k in rng.integers(0, 43, n_chars))
+                syms = code39_symbols(text)
+            else:
+                text = "".join(chr(int(k)) for k in rng.integers(32, 127, n_chars)) if rng.integers(0, 2) else "".join(
+                    "0123456789"[int(k)] for k in rng.integers(0, 10, 2 * n_chars))
+                syms = code128_symbols(text)
+            if barcode_length(syms, kind, mp) <= along:
+                break
+        else:
+            continue
+        rev = bool(rng.integers(0, 4) == 0)
+        height = min(int(rng.integers(24, 60)), cell_w - 40 if vertical else h - top - 40)
+        x = i * cell_w + 10 + 6 * mp
+        y = top + 10 + int(rng.integers(0, 20))
+        box = render_barcode(page, x, y, syms, kind, mp, height, reversed=rev, vertical=vertical)
+        gt.append(dict(kind=kind, text=text, symbols=syms, box=box, reversed=rev, vertical=vertical))
+    return page, gt
+
+
+def synth_barcode_decoys(h: int = 420, w: int = 900, min_rows: int = 8) -> Tuple[np.ndarray, List[dict]]:
+    """White page of what looks like a barcode and is none: an evenly ruled grid of 24 vertical rules, a comb, a paragraph of |l1I
+    text, a Code 128 with one bar widened by a module (the checksum breaks), a good code of fewer than min_rows rows, and a good code
+    whose left quiet zone is filled with ink.  -> (uint8 [h,w,3], [dict(kind, box)])"""
+    page = np.full((h, w, 3), 255, np.uint8)
+    gt = []
+    for k in range(24):                                           # ruled grid
+        page[20:100, 20 + 9 * k:22 + 9 * k] = 0
+    gt.append(dict(kind="grid", box=(20, 20, 20 + 9 * 23 + 1, 99)))
+    page[20:26, 300:500] = 0                                      # comb: a spine with teeth
+    for k in range(34):
+        page[26:90, 300 + 6 * k:303 + 6 * k] = 0
+    gt.append(dict(kind="comb", box=(300, 20, 499, 89)))
+    img = Image.fromarray(page)
+    d = ImageDraw.Draw(img)
+    for r, line in enumerate(("|l1I|Il1|lI1|1lI|l1I|Il1|lI1", "Il1|lI1|1lI|l1I|Il1|lI1|1lI|", "1lI|l1I|Il1|lI1|1lI|l1I|Il1")):
+        d.text((540, 20 + 30 * r), line, fill=(0, 0, 0), font=_font(26))
+    page = np.array(img)
+    gt.append(dict(kind="text", box=(540, 20, w - 1, 110)))
+    syms = code128_symbols("DECOY-128")
+    el = barcode_modules(syms, "Code128")
+    el[8] += 1                                                    # one bar of the second symbol, a module wider
+    x = 30
+    for i, m in enumerate(el):
+        if i % 2 == 0:
+            page[150:200, x:x + 2 * m] = 0
+        x += 2 * m
+    gt.append(dict(kind="bad_check", box=(30, 150, x - 1, 199)))
+    box = render_barcode(page, 400, 150, code128_symbols("SHORT"), "Code128", 2, min_rows - 1)
+    gt.append(dict(kind="short", box=box))
+    box = render_barcode(page, 60, 260, code128_symbols("NOQUIET"), "Code128", 2, 50)
+    page[260:310, 20:58] = 0                                      # ink up to two pixels before the start
+    gt.append(dict(kind="no_quiet", box=box))
+    box = render_barcode(page, 460, 260, code39_symbols("NOQUIET"), "Code39", 2, 50)
+    page[260:310, 420:458] = 0
+    gt.append(dict(kind="no_quiet39", box=box))
+    return page, gt

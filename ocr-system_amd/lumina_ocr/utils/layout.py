@@ -152,6 +152,27 @@ def build_mark_boxes(marks: Sequence[Dict[str, Any]], page_number: int = 1) -> L
              "polygon": [float(v) for v in m["polygon"]], "page_number": page_number} for m in marks]
 
 
+def build_barcode_boxes(found: Sequence[Dict[str, Any]], page_number: int = 1) -> List[Dict[str, Any]]:
+    """`barcode` entries: type, kind ("Code128" / "Code39"), content (the decoded text), confidence, polygon, page_number; barcodes as
+    utils/barcodes.read_barcodes gives them, in their order."""
+    return [{"type": "barcode", "kind": str(b["kind"]), "content": str(b["content"]), "confidence": float(b["confidence"]),
+             "polygon": [float(v) for v in b["polygon"]], "page_number": page_number} for b in found]
+
+
+def _with_barcode_lines(merged: Sequence[MergedLine], barcodes: Sequence[Dict[str, Any]]) -> List[MergedLine]:
+    """The reading-order lines with a line `:barcode: <content>` for every barcode, each in front of the first line that lies below
+    the barcode's centre (barcodes at one place keep their order)."""
+    out = list(merged)
+    for b in barcodes:
+        x0, y0, x1, y1 = b["box"]
+        cy = (y0 + y1 + 1) / 2.0
+        text = ":barcode: %s" % b["content"]
+        block = TextBlock(text, float(b["confidence"]), [[float(x0), float(y0)], [float(x1 + 1), float(y0)], [float(x1 + 1), float(y1 + 1)], [float(x0), float(y1 + 1)]])
+        at = next((i for i, m in enumerate(out) if m.y_position > cy), len(out))
+        out.insert(at, MergedLine(text, float(b["confidence"]), cy, [block]))
+    return out
+
+
 def _block_extent(b: TextBlock) -> Tuple[float, float, float]:
     """-> (left, top, bottom) of a detection's quad"""
     return min(pt[0] for pt in b.box), min(pt[1] for pt in b.box), max(pt[1] for pt in b.box)
@@ -219,13 +240,17 @@ def _markdown_with_marks(merged: Sequence[MergedLine], tables: Sequence[Dict[str
 
 
 def page_markdown(merged: Sequence[MergedLine], tables: Optional[Sequence[Dict[str, Any]]] = None,
-                  marks: Optional[Sequence[Dict[str, Any]]] = None) -> str:
+                  marks: Optional[Sequence[Dict[str, Any]]] = None, barcodes: Optional[Sequence[Dict[str, Any]]] = None) -> str:
     """combined_markdown is fed verbatim to the LLM step and must be non-blank for a non-empty page
     (/root/reference/backend/services/extraction_service.py:290-295, :658-662): one reading-order line per row.
     tables (utils/tables.find_tables + fill_cells): every table is written as its <table> block at the position of its first contained
     line, and the lines inside it (quad centre in a cell) leave the plain flow; what is left of a row that crosses a table stays a row
     of its own.  Lines outside tables are unchanged.
-    marks (utils/marks.select_marks): see _markdown_with_marks; without marks the result is the one without the argument."""
+    marks (utils/marks.select_marks): see _markdown_with_marks; without marks the result is the one without the argument.
+    barcodes (utils/barcodes.read_barcodes): every barcode is a line `:barcode: <content>` of its own at its place in the reading order
+    (_with_barcode_lines); without barcodes the result is the one without the argument."""
+    if barcodes:
+        merged = _with_barcode_lines(merged, barcodes)
     if marks:
         return _markdown_with_marks(merged, tables or [], marks)
     if not tables:
@@ -280,7 +305,7 @@ def validate_layout_boxes(boxes: Sequence[Dict[str, Any]]) -> List[str]:
     """Schema check against the reference fixture's shape; returns a list of problems (empty == valid)."""
     problems = []
     for i, b in enumerate(boxes):
-        if b.get("type") not in ("word", "line", "selection_mark", "table", "table_cell", "paragraph"):
+        if b.get("type") not in ("word", "line", "selection_mark", "table", "table_cell", "paragraph", "barcode"):
             problems.append(f"{i}: bad type {b.get('type')!r}")
         poly = b.get("polygon")
         if not isinstance(poly, list) or len(poly) != 8 or not all(isinstance(v, float) for v in poly):
@@ -291,6 +316,13 @@ def validate_layout_boxes(boxes: Sequence[Dict[str, Any]]) -> List[str]:
             problems.append(f"{i}: content must be str")
         if b.get("type") == "word" and not isinstance(b.get("confidence"), float):
             problems.append(f"{i}: word confidence must be float")
+        if b.get("type") == "barcode":
+            if b.get("kind") not in ("Code128", "Code39"):
+                problems.append(f"{i}: barcode kind must be Code128 or Code39")
+            if not isinstance(b.get("content"), str):
+                problems.append(f"{i}: barcode content must be str")
+            if not isinstance(b.get("confidence"), float) or not 0.0 <= b["confidence"] <= 1.0:
+                problems.append(f"{i}: barcode confidence must be a float in 0..1")
         if b.get("type") == "table":
             for k in ("table_index", "row_count", "column_count"):
                 if not isinstance(b.get(k), int) or isinstance(b.get(k), bool) or b[k] < (0 if k == "table_index" else 1):
