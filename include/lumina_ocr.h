@@ -356,6 +356,27 @@ int lumina_ocr_png_probe(const uint8_t* file, size_t size, int info[8]);
 int lumina_ocr_png_decode(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev,
                           int* status, void* stream);
 
+/* Scanned PDF pages — the images of a PDF whose pages are one image each (utils/pdf_pages.py finds them), decoded at their own sample
+ * grid instead of the rasterisation pdf2image / poppler does for the reference (ocr_service.py:508-660).  /DCTDecode streams are JPEG
+ * files: lumina_ocr_jpeg_decode.  The two entries below take the other two filters; the batch contract is lumina_ocr_png_decode's:
+ * HOST pointers to n same-size streams, out_dev uint8 [n][height][width][3], a HOST status per page (0: exact pixels, -1 corrupt,
+ * -2 unsupported; the pixels of a page with a non-zero status are undefined), `stream` synchronised.
+ * lumina_ocr_flate_image_decode: /FlateDecode image streams (plain zlib).  params int32 [n][5] = {Predictor (1 packed rows, 2 TIFF
+ * horizontal differencing with 8-bit samples, 10..15 PNG row filters), components (1 | 3), bits per component (8; 1 / 2 / 4 with one
+ * component), indexed (0 | 1), invert (/Decode [1 0]: one non-indexed component)}; palettes: per indexed stream 768 bytes of RGB (the
+ * /Indexed lookup expanded to RGB, entries past hival filled by the caller), null entries elsewhere; may be null without indexed streams.
+ * Grey samples map as v * 255 / (2^bits - 1).  -1: zlib header, DEFLATE stream, Adler-32, a PNG filter byte past 4, bytes after the
+ * Adler-32, or an inflated length other than rows x row bytes.
+ * lumina_ocr_ccitt_decode: /CCITTFaxDecode with K < 0 (ITU-T T.6, Group 4).  params int32 [n][4] = {K, EncodedByteAlign, BlackIs1,
+ * invert}; -2 for K >= 0, EncodedByteAlign or columns > 8192 (CC_MAX_COLS, ccitt.h).  Decoding stops after `rows` lines or at
+ * EOFB, whichever comes first; bytes after that are ignored.  A coded-white run is sample 1 unless BlackIs1; sample 1 is white (255)
+ * unless invert.  -1: an unused code, a line whose a0 does not advance or passes `columns`, more than columns + 1 changing elements on a
+ * line, bits past the stream's end, or fewer than `rows` lines. */
+int lumina_ocr_flate_image_decode(lumina_ocr_t* h, const uint8_t* const* streams, const size_t* sizes, int n, int height, int width,
+                                  const int32_t* params, const uint8_t* const* palettes, uint8_t* out_dev, int* status, void* stream);
+int lumina_ocr_ccitt_decode(lumina_ocr_t* h, const uint8_t* const* streams, const size_t* sizes, int n, int rows, int columns,
+                            const int32_t* params, uint8_t* out_dev, int* status, void* stream);
+
 int lumina_ocr_jpeg_coefficients(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int quality, int16_t* coefs_dev,
                                  void* stream);
 

@@ -16,6 +16,7 @@
 #include "jpeg.h"
 #include "jpegdec.h"
 #include "pngdec.h"
+#include "ccitt.h"
 #include "stem_conv.h"
 #include "tables.h"
 
@@ -481,6 +482,24 @@ int lumina_ocr_png_decode(lumina_ocr_t* h, const uint8_t* const* files, const si
     BIND(h);
     API_TRY
     return pngdec_run(h, files, sizes, n, height, width, out_dev, status, (hipStream_t)stream);
+    API_CATCH(h)
+}
+
+int lumina_ocr_flate_image_decode(lumina_ocr_t* h, const uint8_t* const* streams, const size_t* sizes, int n, int height, int width,
+                                  const int32_t* params, const uint8_t* const* palettes, uint8_t* out_dev, int* status, void* stream) {
+    if (!h || !streams || !sizes || !params || !out_dev || !status || n <= 0 || height <= 0 || width <= 0) return locr_fail(h, "flate_image_decode", "bad arguments");
+    BIND(h);
+    API_TRY
+    return flate_image_run(h, streams, sizes, n, height, width, params, palettes, out_dev, status, (hipStream_t)stream);
+    API_CATCH(h)
+}
+
+int lumina_ocr_ccitt_decode(lumina_ocr_t* h, const uint8_t* const* streams, const size_t* sizes, int n, int rows, int columns,
+                            const int32_t* params, uint8_t* out_dev, int* status, void* stream) {
+    if (!h || !streams || !sizes || !params || !out_dev || !status || n <= 0 || rows <= 0 || columns <= 0) return locr_fail(h, "ccitt_decode", "bad arguments");
+    BIND(h);
+    API_TRY
+    return ccitt_run(h, streams, sizes, n, rows, columns, params, out_dev, status, (hipStream_t)stream);
     API_CATCH(h)
 }
 

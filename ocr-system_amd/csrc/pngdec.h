@@ -23,3 +23,13 @@ struct lumina_ocr;
 // written).  Synchronous: synchronises the stream once per sub-batch.
 int pngdec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev, int* status,
                hipStream_t st);
+
+// The image streams of PDF's /FlateDecode: plain zlib streams of height rows (a scanned page is one such image).  The batch contract
+// is pngdec_run's and so are the inflate and Adler-32 stages; the row stage depends on /Predictor.  params: HOST int [n][5] =
+// {Predictor (1: packed rows; 2: TIFF horizontal differencing, 8-bit samples; 10..15: PNG row filters), components (1 | 3), bits per
+// component (8; 1 / 2 / 4 with one component), indexed (0 | 1: the sample is an index into palettes[i]), invert (/Decode [1 0], one
+// non-indexed component)}.  palettes: HOST, 768 bytes of RGB per indexed stream (entries past /hival filled by the caller; may be null
+// when no stream is indexed).  status: 0 exact pixels / -1 corrupt (zlib header, DEFLATE stream, Adler-32, a PNG filter byte past 4, or
+// an inflated length other than rows x row bytes) / -2 a combination outside this list.
+int flate_image_run(lumina_ocr* eng, const uint8_t* const* streams, const size_t* sizes, int n, int height, int width, const int* params,
+                    const uint8_t* const* palettes, uint8_t* out_dev, int* status, hipStream_t st);

@@ -15,6 +15,11 @@
 //      behind lane i-1, so the up / up-left bytes Up, Avg and Paeth need come from lane i-1 by a cross-lane move and the left byte from
 //      the lane's own last steps; row 63 of a band is handed to the next band through LDS.  Palette indices are checked here;
 //   4. pd_expand: unfiltered rows -> RGB u8 as Pillow's convert('RGB') maps them; pd_status: error words + host results -> status.
+//
+// The image streams of PDF's /FlateDecode (flate_image_run: the pages of scanned PDFs) are plain zlib streams of the same rows and take
+// the same stages; only the row stage differs with /Predictor: PNG row filters (10..15) are stage 3; TIFF horizontal differencing (2)
+// is pd_tiff_predict, a prefix sum mod 256 per row and component across lanes; packed rows (1) have no filter byte and no row stage.
+// pd_expand applies /Decode [1 0] and looks /Indexed samples up in the palette the host built.
 #include "pngdec.h"
 
 #include <algorithm>
@@ -36,8 +41,9 @@ enum : int { PD_E_STREAM = 1, PD_E_PALETTE = 2, PD_E_ADLER = 4, PD_E_FILTER = 8 
 
 struct PdFile {
     unsigned long long zoff, foff;   // byte offsets of the zlib stream / the filtered scanlines in the sub-batch's buffers
-    unsigned zlen, rb, total;        // stream bytes; bytes per row (filter byte excluded); inflated bytes = height * (rb + 1)
+    unsigned zlen, rb, total;        // stream bytes; bytes per row (filter byte excluded); inflated bytes = height * (rb + fb)
     int width, height, ct, depth, bpp, npal, wsize, valid, out_index, ablk_off;
+    int fb, tiff, invert;            // filter bytes per row (1: PNG rows; 0: packed rows of a PDF Flate image); /Predictor 2 rows; /Decode [1 0]
     uint8_t pal[768];
 };
 
@@ -338,7 +344,8 @@ __global__ __launch_bounds__(256) void pd_adler_fin(const PdFile* __restrict__ F
         bsum += p.y + (unsigned long long)p.x * ((f.total - end) % 65521u);
     }
     bool badf = false;
-    for (int r = t; r < f.height; r += 256) badf |= filt[f.foff + (size_t)r * (f.rb + 1)] > 4;
+    if (f.fb)
+        for (int r = t; r < f.height; r += 256) badf |= filt[f.foff + (size_t)r * (f.rb + 1)] > 4;
     __shared__ unsigned long long ra[256], rbs[256];
     __shared__ int rf[256];
     ra[t] = a % 65521u; rbs[t] = bsum % 65521u; rf[t] = badf;
@@ -426,7 +433,7 @@ __device__ void pd_unfilter_file(const PdFile& f, uint8_t* __restrict__ fb, uint
 __global__ __launch_bounds__(64) void pd_unfilter(const PdFile* __restrict__ F, uint8_t* __restrict__ filt, int* __restrict__ err) {
     __shared__ uint8_t prevrow[PD_MAX_ROW];
     const PdFile& f = F[blockIdx.x];
-    if (!f.valid || err[blockIdx.x]) return;
+    if (!f.valid || err[blockIdx.x] || !f.fb) return;
     const int lane = threadIdx.x;
     bool pal_bad = false;
     uint8_t* fb = filt + f.foff;
@@ -439,6 +446,37 @@ __global__ __launch_bounds__(64) void pd_unfilter(const PdFile* __restrict__ F, 
     if (__ballot(pal_bad) && lane == 0) err[blockIdx.x] |= PD_E_PALETTE;
 }
 
+// /Predictor 2 of a PDF Flate image (TIFF horizontal differencing, 8-bit components): every byte is the difference to the same component
+// of the pixel on its left, so a row is an inclusive prefix sum mod 256 per component.  One wave per row: lanes over 64 consecutive
+// pixels, a six-step shuffle scan, the chunk's last sums carried into the next chunk.
+__global__ __launch_bounds__(64) void pd_tiff_predict(const PdFile* __restrict__ F, uint8_t* __restrict__ filt, const int* __restrict__ err) {
+    const PdFile& f = F[blockIdx.y];
+    if (!f.valid || err[blockIdx.y] || !f.tiff) return;
+    const int lane = threadIdx.x, C = f.bpp;
+    for (int r = blockIdx.x; r < f.height; r += gridDim.x) {
+        uint8_t* row = filt + f.foff + (size_t)r * f.rb;
+        int carry0 = 0, carry1 = 0, carry2 = 0;
+        for (int x0 = 0; x0 < f.width; x0 += 64) {
+            const int x = x0 + lane;
+            const bool act = x < f.width;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (c >= C) break;
+                int v = act ? row[(size_t)x * C + c] : 0;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const int u = __shfl_up(v, d, 64);
+                    if (lane >= d) v += u;
+                }
+                v += c == 0 ? carry0 : c == 1 ? carry1 : carry2;
+                if (act) row[(size_t)x * C + c] = (uint8_t)v;
+                const int last = __shfl(v, 63, 64) & 255;
+                if (c == 0) carry0 = last; else if (c == 1) carry1 = last; else carry2 = last;
+            }
+        }
+    }
+}
+
 // unfiltered rows -> RGB u8, as Pillow's convert('RGB') maps them: grey 1 bit -> 0 / 255, 2 bit -> v * 85, 4 bit -> v * 17; palette
 // looked up; alpha dropped; grey replicated
 __global__ __launch_bounds__(256) void pd_expand(const PdFile* __restrict__ F, const uint8_t* __restrict__ filt, const int* __restrict__ err,
@@ -448,16 +486,16 @@ __global__ __launch_bounds__(256) void pd_expand(const PdFile* __restrict__ F, c
     const size_t npx = (size_t)f.width * f.height;
     for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < npx; p += (size_t)gridDim.x * 256) {
         const int y = (int)(p / f.width), x = (int)(p - (size_t)y * f.width);
-        const uint8_t* row = filt + f.foff + (size_t)y * (f.rb + 1) + 1;
+        const uint8_t* row = filt + f.foff + (size_t)y * (f.rb + f.fb) + f.fb;
         int r, g, b;
         if (f.depth < 8) {
             const int d = f.depth, bit = x * d;
             const int v = (row[bit >> 3] >> (8 - d - (bit & 7))) & ((1 << d) - 1);
             if (f.ct == 3) { r = f.pal[3 * v]; g = f.pal[3 * v + 1]; b = f.pal[3 * v + 2]; }
-            else { r = g = b = d == 1 ? v * 255 : d == 2 ? v * 85 : v * 17; }
+            else { r = g = b = d == 1 ? v * 255 : d == 2 ? v * 85 : v * 17; if (f.invert) r = g = b = 255 - r; }
         } else {
             switch (f.ct) {
-                case 0: r = g = b = row[x]; break;
+                case 0: r = g = b = f.invert ? 255 - row[x] : row[x]; break;
                 case 2: r = row[3 * x]; g = row[3 * x + 1]; b = row[3 * x + 2]; break;
                 case 3: { const int v = row[x]; r = f.pal[3 * v]; g = f.pal[3 * v + 1]; b = f.pal[3 * v + 2]; } break;
                 case 4: r = g = b = row[2 * x]; break;
@@ -519,6 +557,7 @@ struct Walk {
     uint8_t pal[768];
     std::vector<std::pair<size_t, size_t>> idat;   // (offset, length) of every IDAT payload
     size_t zlen = 0;
+    int fb = 1, tiff = 0, invert = 0;   // PdFile's row-stage fields (a PNG file: filter bytes, nothing else)
 };
 
 // header = true: stop at the first IDAT (the probe).  Returns 0 / -1 / -2 as pngdec_probe.
@@ -603,35 +642,23 @@ PdWorkspace pd_layout(Arena& a, int n, size_t z_total, size_t filt_total, size_t
     return w;
 }
 
-}  // namespace
 
-size_t pngdec_workspace_bytes(int n, size_t z_total, size_t filt_total, size_t adler_blocks) {
-    Arena a;
-    pd_layout(a, n, z_total, filt_total, adler_blocks);
-    return a.off;
-}
-
-int pngdec_probe(const uint8_t* file, size_t n, PdInfo* info) {
-    Walk w;
-    const int rc = walk(file, n, &w, true);
-    if (info) *info = w.info;
-    return rc;
-}
-
-int pngdec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev, int* status,
-               hipStream_t st) {
-    std::vector<Walk> W((size_t)n);
+// the device half of both entries: W[i] describes stream i (the pieces of files[i] that make up its zlib stream, its sample layout and
+// row stage) where status[i] == 0
+int pd_run_walked(lumina_ocr* eng, const std::vector<Walk>& W, const uint8_t* const* files, int n, int height, int width, uint8_t* out_dev,
+                  int* status, hipStream_t st, const char* what) {
     std::vector<size_t> fbytes((size_t)n, 0);
+    bool any_fb = false, any_tiff = false;
     for (int i = 0; i < n; ++i) {
-        Walk& w = W[(size_t)i];
-        int rc = walk(files[i], sizes[i], &w, false);
-        if (rc == 0 && (w.info.width != width || w.info.height != height)) rc = -4;
+        const Walk& w = W[(size_t)i];
+        int rc = status[i];
         if (rc == 0) {
             const int ch = w.info.color_type == 2 ? 3 : w.info.color_type == 4 ? 2 : w.info.color_type == 6 ? 4 : 1;
             const size_t rb = ((size_t)width * ch * w.info.bit_depth + 7) / 8;
-            const size_t total = (size_t)height * (rb + 1);
+            const size_t total = (size_t)height * (rb + (size_t)w.fb);
             if (rb > (size_t)PD_MAX_ROW || total >= ((size_t)1 << 31) || w.zlen >= ((size_t)1 << 29) - 4096) rc = -2;   // (32-bit byte offsets; bit positions, with the reader's look-ahead)
             fbytes[(size_t)i] = total;
+            if (rc == 0) { any_fb |= w.fb != 0; any_tiff |= w.tiff != 0; }
         }
         status[i] = rc;
     }
@@ -665,6 +692,7 @@ int pngdec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes
             f.rb = (unsigned)(((size_t)width * ch * f.depth + 7) / 8);
             f.total = (unsigned)fbytes[(size_t)i];
             f.npal = w.info.palette_size;
+            f.fb = w.fb; f.tiff = w.tiff; f.invert = w.invert;
             if (f.ct == 3) memcpy(f.pal, w.pal, (size_t)f.npal * 3);
             f.zlen = (unsigned)w.zlen;
             f.zoff = z_total; z_total += ((w.zlen + 255) & ~(size_t)255) + PD_Z_PAD;
@@ -698,7 +726,7 @@ int pngdec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes
             if (eng_ws_reserve(eng, sizing.off)) return 1;
             Arena a(eng->ws.get(), eng->ws.cap);
             const PdWorkspace w = pd_layout(a, nb, z_total, filt_total, ablk_total);
-            if (a.overflow) return locr_fail(eng, "png_decode", "workspace layout exceeds the reservation");
+            if (a.overflow) return locr_fail(eng, what, "workspace layout exceeds the reservation");
             LOCR_CHECK(hipMemcpyAsync(w.F, F.data(), sizeof(PdFile) * nb, hipMemcpyHostToDevice, st));
             LOCR_CHECK(hipMemcpyAsync(w.z, stage.buf.get(), z_total, hipMemcpyHostToDevice, st));
             LOCR_CHECK(hipEventRecord(stage.uploaded.get(), st));
@@ -706,7 +734,8 @@ int pngdec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes
             hipLaunchKernelGGL(pd_inflate, dim3(nb), dim3(64), 0, st, w.F, w.z, w.filt, w.err, w.adler_want);
             hipLaunchKernelGGL(pd_adler_part, dim3((unsigned)max_ablk, nb), dim3(256), 0, st, w.F, w.filt, w.err, w.part);
             hipLaunchKernelGGL(pd_adler_fin, dim3(nb), dim3(256), 0, st, w.F, w.filt, w.part, w.adler_want, w.err);
-            hipLaunchKernelGGL(pd_unfilter, dim3(nb), dim3(64), 0, st, w.F, w.filt, w.err);
+            if (any_fb) hipLaunchKernelGGL(pd_unfilter, dim3(nb), dim3(64), 0, st, w.F, w.filt, w.err);
+            if (any_tiff) hipLaunchKernelGGL(pd_tiff_predict, dim3((unsigned)std::min(height, 1024), nb), dim3(64), 0, st, w.F, w.filt, w.err);
             const size_t npx = (size_t)width * height;
             hipLaunchKernelGGL(pd_expand, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 4096), nb), dim3(256), 0, st, w.F, w.filt, w.err, out_dev);
             hipLaunchKernelGGL(pd_status, dim3((nb + 63) / 64), dim3(64), 0, st, w.F, w.err, w.status, nb);
@@ -720,4 +749,57 @@ int pngdec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes
         i0 = i1;
     }
     return 0;
+}
+
+}  // namespace
+
+size_t pngdec_workspace_bytes(int n, size_t z_total, size_t filt_total, size_t adler_blocks) {
+    Arena a;
+    pd_layout(a, n, z_total, filt_total, adler_blocks);
+    return a.off;
+}
+
+int pngdec_probe(const uint8_t* file, size_t n, PdInfo* info) {
+    Walk w;
+    const int rc = walk(file, n, &w, true);
+    if (info) *info = w.info;
+    return rc;
+}
+
+int pngdec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev, int* status,
+               hipStream_t st) {
+    std::vector<Walk> W((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        Walk& w = W[(size_t)i];
+        int rc = walk(files[i], sizes[i], &w, false);
+        if (rc == 0 && (w.info.width != width || w.info.height != height)) rc = -4;
+        status[i] = rc;
+    }
+    return pd_run_walked(eng, W, files, n, height, width, out_dev, status, st, "png_decode");
+}
+
+int flate_image_run(lumina_ocr* eng, const uint8_t* const* streams, const size_t* sizes, int n, int height, int width, const int* params,
+                    const uint8_t* const* palettes, uint8_t* out_dev, int* status, hipStream_t st) {
+    std::vector<Walk> W((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        Walk& w = W[(size_t)i];
+        const int* q = params + 5 * (size_t)i;
+        const int predictor = q[0], comps = q[1], depth = q[2], indexed = q[3], invert = q[4];
+        memset(&w.info, 0, sizeof(w.info));
+        bool ok = (predictor == 1 || predictor == 2 || (predictor >= 10 && predictor <= 15)) && (comps == 1 || comps == 3) &&
+                  (depth == 8 || (comps == 1 && (depth == 1 || depth == 2 || depth == 4)));
+        if (predictor == 2 && depth != 8) ok = false;           // (TIFF differencing of packed samples: not taken)
+        if (indexed && (comps != 1 || invert || !palettes || !palettes[i])) ok = false;
+        if (invert && comps != 1) ok = false;
+        if (!ok) { status[i] = -2; continue; }
+        if (!streams[i] || sizes[i] == 0) { status[i] = -1; continue; }
+        w.info.width = width; w.info.height = height; w.info.bit_depth = depth;
+        w.info.color_type = indexed ? 3 : comps == 3 ? 2 : 0;
+        if (indexed) { w.info.palette_size = 256; memcpy(w.pal, palettes[i], 768); }
+        w.idat.emplace_back((size_t)0, sizes[i]);
+        w.zlen = sizes[i];
+        w.fb = predictor >= 10; w.tiff = predictor == 2; w.invert = invert != 0;
+        status[i] = 0;
+    }
+    return pd_run_walked(eng, W, streams, n, height, width, out_dev, status, st, "flate_image_decode");
 }

@@ -79,6 +79,8 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_jpeg_coefficients": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
         "lumina_ocr_png_probe": (i32, [vp, sz, vp]),
         "lumina_ocr_png_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+        "lumina_ocr_flate_image_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+        "lumina_ocr_ccitt_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
         "lumina_ocr_load_svtr_weights": (i32, [vp, vp, sz]),
         "lumina_ocr_svtr_forward": (i32, [vp, vp, vp, i32, vp, vp, vp]),
         "lumina_ocr_svtr_num_classes": (i32, [vp]),
@@ -122,7 +124,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_load_cls_weights", "lumina_ocr_cls_forward", "lumina_ocr_rec_forward",
     "lumina_ocr_ctc_decode", "lumina_ocr_ctc_decode_words", "lumina_ocr_conv2d", "lumina_ocr_read_tap", "lumina_ocr_conv_timing", "lumina_ocr_conv_timing_detail",
     "lumina_ocr_resize_lanczos", "lumina_ocr_enhance", "lumina_ocr_jpeg_encode", "lumina_ocr_jpeg_coefficients", "lumina_ocr_jpeg_probe", "lumina_ocr_jpeg_decode", "lumina_ocr_jpeg_decode_async", "lumina_ocr_jpeg_last_passes",
-    "lumina_ocr_png_probe", "lumina_ocr_png_decode",
+    "lumina_ocr_png_probe", "lumina_ocr_png_decode", "lumina_ocr_flate_image_decode", "lumina_ocr_ccitt_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
     "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks", "lumina_ocr_selection_marks_round",
     "lumina_ocr_rules_and_marks_round", "lumina_ocr_barcodes",
@@ -251,6 +253,39 @@ class Engine:
         sizes = (ctypes.c_size_t * n)(*[len(f) for f in files])
         status = (ctypes.c_int * n)()
         self._chk(self.lib.lumina_ocr_png_decode(self._h, ptrs, sizes, n, int(height), int(width), _ptr(out), status, self._stream()))
+        return out, list(status)
+
+    def _stream_batch(self, streams, height: int, width: int, out):
+        torch = _torch()
+        n = len(streams)
+        if out is None:
+            out = torch.empty((n, height, width, 3), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        streams = [s if isinstance(s, bytes) else bytes(s) for s in streams]   # (the records of utils/pdf_pages.py carry memoryviews)
+        ptrs = (ctypes.c_char_p * n)(*streams)
+        sizes = (ctypes.c_size_t * n)(*[len(s) for s in streams])
+        return n, out, streams, ptrs, sizes, (ctypes.c_int * n)()
+
+    def flate_image_decode(self, streams, height: int, width: int, params, palettes=None, out=None):
+        """The /FlateDecode image streams of scanned PDF pages (all height x width) -> (uint8 [n,H,W,3] device, status list).  params: per
+        stream (predictor, components, bits, indexed, invert); palettes: per stream None or 768 bytes of RGB (see lumina_ocr.h).
+        status 0: exact pixels, -1 corrupt, -2 outside the supported combinations."""
+        n, out, streams, ptrs, sizes, status = self._stream_batch(streams, height, width, out)
+        flat = (ctypes.c_int32 * (5 * n))(*[int(v) for p in params for v in p])
+        pals = None
+        if palettes is not None and any(p is not None for p in palettes):
+            keep = [None if p is None else bytes(p) for p in palettes]
+            assert all(p is None or len(p) == 768 for p in keep)
+            pals = (ctypes.c_char_p * n)(*keep)
+        self._chk(self.lib.lumina_ocr_flate_image_decode(self._h, ptrs, sizes, n, int(height), int(width), flat, pals, _ptr(out), status, self._stream()))
+        return out, list(status)
+
+    def ccitt_decode(self, streams, rows: int, columns: int, params, out=None):
+        """The /CCITTFaxDecode (Group 4, K < 0) streams of scanned PDF pages (all rows x columns) -> (uint8 [n,rows,columns,3] device,
+        status list).  params: per stream (K, EncodedByteAlign, BlackIs1, invert).  status 0: exact pixels, -1 corrupt, -2 unsupported
+        (K >= 0, EncodedByteAlign, columns > 8192)."""
+        n, out, streams, ptrs, sizes, status = self._stream_batch(streams, rows, columns, out)
+        flat = (ctypes.c_int32 * (4 * n))(*[int(v) for p in params for v in p])
+        self._chk(self.lib.lumina_ocr_ccitt_decode(self._h, ptrs, sizes, n, int(rows), int(columns), flat, _ptr(out), status, self._stream()))
         return out, list(status)
 
     @property

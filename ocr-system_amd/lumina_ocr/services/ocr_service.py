@@ -32,6 +32,7 @@ from ..utils import layout
 from ..utils import barcodes as barcode_layout
 from ..utils import marks as mark_layout
 from ..utils import page_orient
+from ..utils import pdf_pages
 from ..utils import tables as table_layout
 from ..utils.image_preprocessing import ImagePreprocessor, get_optimal_size
 
@@ -115,6 +116,10 @@ class OCRService:
         # LUMINA_OCR_DEVICE_PNG=1: non-interlaced PNG inputs of 8 bits or less and lazily opened PNG pages (pdf2image) are decoded on the
         # device.  Off by default: measured slower than Pillow for single pages and for 300 dpi batches
         self.device_png = os.environ.get("LUMINA_OCR_DEVICE_PNG", "0").lower() not in ("0", "false", "no")
+        # LUMINA_OCR_PDF_SCANS=1: a PDF page that is one image over the whole MediaBox (a scan: DCT, Flate or CCITT Group 4) is decoded
+        # on the device from its embedded stream, at the image's own sample grid, instead of being rasterised by pdf2image / poppler; other
+        # pages still go to pdf_to_images.  Off by default: process_pdf_sync is then the rasterise-and-batch path alone.
+        self.device_pdf = os.environ.get("LUMINA_OCR_PDF_SCANS", "0").lower() not in ("", "0", "false", "no")
         self.apply_binarize = "adaptive" if b in ("1", "true", "yes", "adaptive") else ("simple" if b == "simple" else None)
         self._device = int(os.environ.get("LUMINA_OCR_DEVICE", os.environ.get("LOCAL_RANK", 0)))
         self._det_weights = os.environ.get("LUMINA_OCR_DET_WEIGHTS", "")
@@ -549,25 +554,31 @@ class OCRService:
                     groups.setdefault(prepared[i].size, []).append(i)
                 except Exception as e:
                     out[i] = OCROutput(success=False, error=str(e), page_number=first_page_number + i, image_width=im.size[0], image_height=im.size[1])
+            sizes = [im.size for im in images]
             for size, idxs in groups.items():
-                t0 = time.time()
-                try:
-                    import torch
-                    self._ensure_engine()
-                    with self._device_ctx():
-                        if size[0] == "device":
-                            pages = torch.cat([on_device[i] for i in idxs]) if len(idxs) > 1 else on_device[idxs[0]]
-                        else:
-                            pages = self._upload(self._stage_pages([prepared[i] for i in idxs]))
-                        results = self._run_pages(pages)
-                    for (det, jpeg, processed_hw), i in zip(results, idxs):
-                        out[i] = self._finish_page(det, jpeg, processed_hw, first_page_number + i, images[i].size, t0)
-                except Exception as e:
-                    for i in idxs:
-                        out[i] = OCROutput(success=False, error=str(e), processing_time_ms=_ms_since(t0),
-                                           page_number=first_page_number + i, image_width=images[i].size[0], image_height=images[i].size[1])
+                self._run_group(idxs, on_device if size[0] == "device" else None, prepared, sizes, first_page_number, out)
         self._number_tables(out)
         return out  # type: ignore[return-value]
+
+    def _run_group(self, idxs: List[int], on_device, prepared, sizes, first_page_number: int, out: List[Optional[OCROutput]]) -> None:
+        """One same-size group of a page batch through the engine (the caller holds the semaphore): pages idxs, either already on the
+        device (on_device[i]: uint8 [1,H,W,3]) or prepared PIL images; sizes[i]: the page's own (width, height).  Fills out[i]."""
+        t0 = time.time()
+        try:
+            import torch
+            self._ensure_engine()
+            with self._device_ctx():
+                if on_device is not None:
+                    pages = torch.cat([on_device[i] for i in idxs]) if len(idxs) > 1 else on_device[idxs[0]]
+                else:
+                    pages = self._upload(self._stage_pages([prepared[i] for i in idxs]))
+                results = self._run_pages(pages)
+            for (det, jpeg, processed_hw), i in zip(results, idxs):
+                out[i] = self._finish_page(det, jpeg, processed_hw, first_page_number + i, sizes[i], t0)
+        except Exception as e:
+            for i in idxs:
+                out[i] = OCROutput(success=False, error=str(e), processing_time_ms=_ms_since(t0),
+                                   page_number=first_page_number + i, image_width=sizes[i][0], image_height=sizes[i][1])
 
     @staticmethod
     def _number_tables(pages) -> None:
@@ -604,7 +615,102 @@ class OCRService:
     def process_pdf_sync(self, pdf_path: Union[str, Path]) -> DocumentOCRResult:
         if not Path(pdf_path).exists():
             return DocumentOCRResult(success=False, error=f"File not found: {Path(pdf_path)}")
+        if self.device_pdf:
+            return self._process_pdf_scans_sync(pdf_path)
         return self.process_pdf_as_images_sync(pdf_path)
+
+    # ---- scanned PDFs (LUMINA_OCR_PDF_SCANS=1): the pages' embedded images, decoded on the device ----
+    ROTATE_TO_EXIF = {0: 1, 90: 6, 180: 3, 270: 8}   # /Rotate turns the page clockwise, as these EXIF orientations do
+
+    def _decode_pdf_pages(self, entries, reasons: Dict[int, str]) -> Dict[int, Any]:
+        """The accepted pages of pdf_pages.read_pages -> {page index: device tensor [1,H,W,3], /Rotate applied}: grouped by filter and
+        size, one decoder call per group.  A page a decoder refuses gets its reason in `reasons` (it goes to the rasteriser); a DCT page
+        the device JPEG decoder does not take is decoded by Pillow, as JPEG files are."""
+        groups: Dict[Any, List[int]] = {}
+        for i, e in enumerate(entries):
+            if isinstance(e, pdf_pages.PageImage):
+                groups.setdefault((e.filter, e.width, e.height), []).append(i)
+        res: Dict[int, Any] = {}
+        self._ensure_engine()
+        eng = self._engine
+        with self._device_ctx():
+            for (filt, w, h), idxs in groups.items():
+                recs = [entries[i] for i in idxs]
+                streams = [bytes(r.stream) for r in recs]
+                try:
+                    if filt == "DCTDecode":
+                        out, status = eng.jpeg_decode(streams, h, w) if self.device_jpeg else (None, [-2] * len(idxs))
+                    elif filt == "FlateDecode":
+                        params = [(r.params["predictor"], r.params["components"], r.params["bits"], int(r.params["indexed"]), int(r.params["invert"]))
+                                  for r in recs]
+                        out, status = eng.flate_image_decode(streams, h, w, params, [r.params["palette"] for r in recs])
+                    else:
+                        params = [(r.params["K"], int(r.params["EncodedByteAlign"]), int(r.params["BlackIs1"]), int(r.params["invert"])) for r in recs]
+                        out, status = eng.ccitt_decode(streams, h, w, params)
+                except Exception as e:   # the engine's own failure: these pages go to the rasteriser
+                    for i in idxs:
+                        reasons[i] = "%s decode failed: %s" % (filt, e)
+                    continue
+                for k, i in enumerate(idxs):
+                    page = None
+                    if status[k] == 0:
+                        page = out[k:k + 1]
+                    elif filt == "DCTDecode":   # progressive, CMYK, Adobe transforms ...: the fallback JPEG files have
+                        try:
+                            im = Image.open(io.BytesIO(streams[k])).convert("RGB")
+                            if im.size == (w, h):
+                                page = self._upload(self._stage_pages([im]))
+                        except Exception as e:
+                            reasons[i] = "embedded JPEG not decodable: %s" % e
+                            continue
+                    if page is None:
+                        reasons[i] = "%s stream %s (status %d)" % (filt, "corrupt" if status[k] == -1 else "outside the device subset", status[k])
+                        continue
+                    res[i] = eng.exif_transpose(page, self.ROTATE_TO_EXIF[recs[k].rotate])
+        return res
+
+    def _process_pdf_scans_sync(self, pdf_path: Union[str, Path]) -> DocumentOCRResult:
+        t0 = time.time()
+        try:
+            data = Path(pdf_path).read_bytes()
+            try:
+                entries = pdf_pages.read_pages(data)
+            except pdf_pages.PdfRefused as e:   # not a file the reader takes: the rasterise-and-batch path, whole
+                r = self.process_pdf_as_images_sync(pdf_path)
+                if not r.success and r.error and not r.pages:
+                    r.error = "%s (scanned-page reader: %s)" % (r.error, e.reason)
+                return r
+            n = len(entries)
+            reasons: Dict[int, str] = {i: e.reason for i, e in enumerate(entries) if isinstance(e, pdf_pages.PdfRefused)}
+            out: List[Optional[OCROutput]] = [None] * n
+            with self._semaphore:
+                try:
+                    on_device = self._decode_pdf_pages(entries, reasons)
+                except Exception as e:   # no engine: errors are data
+                    return DocumentOCRResult(success=False, error=str(e), total_processing_time_ms=_ms_since(t0))
+                groups: Dict[Any, List[int]] = {}
+                sizes: List[Any] = [None] * n
+                for i, page in on_device.items():
+                    sizes[i] = (int(page.shape[2]), int(page.shape[1]))   # the size the page has after /Rotate
+                    groups.setdefault(sizes[i], []).append(i)
+                for idxs in groups.values():
+                    self._run_group(sorted(idxs), on_device, None, sizes, 1, out)
+            for i in range(n):
+                if out[i] is not None:
+                    continue
+                why = reasons.get(i, "not decoded")
+                try:   # a page that is no scan: rasterised, as every page is with the option off
+                    images = self._pre.pdf_to_images(pdf_path, first_page=i + 1, last_page=i + 1)
+                    if not images:
+                        raise ValueError("the rasteriser returned no page")
+                    out[i] = self.process_pages_sync(images[:1], first_page_number=i + 1)[0]
+                except Exception as e:
+                    out[i] = OCROutput(success=False, error="page %d is not a scanned page the device decodes (%s) and could not be rasterised: %s"
+                                       % (i + 1, why, e), page_number=i + 1)
+            self._number_tables(out)
+            return self._document_from_pages(out, t0)  # type: ignore[arg-type]
+        except Exception as e:
+            return DocumentOCRResult(success=False, error=str(e), total_processing_time_ms=_ms_since(t0))
 
     # ---- async wrappers (:666-731) ----
     async def process_image(self, image_source, page_number: int = 1, timeout: float = 120.0) -> OCROutput:
@@ -635,7 +741,7 @@ class OCRService:
     # ---- status (:759-795) ----
     def get_status(self) -> Dict[str, Any]:
         st = {"client_initialized": self._pipeline is not None, "model_id": "dbnet-r18vd+crnn-mv3", "max_dimension": self.max_dimension,
-              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
+              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "device_pdf": self.device_pdf, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
         if self._engine is not None:
             st["engine_version"] = self._engine.version()
             st["num_classes"] = self._engine.num_classes

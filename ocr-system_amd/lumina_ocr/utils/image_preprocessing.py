@@ -160,8 +160,10 @@ class ImagePreprocessor:
             result[i] = files[0, :sz].cpu().numpy().tobytes()
         return result  # type: ignore[return-value]
 
-    def pdf_to_images(self, pdf_path: Union[str, Path], dpi: Optional[int] = None) -> List[Image.Image]:
-        """:248-295 — needs pdf2image + poppler exactly like the reference; absent here -> ImportError as data upstream."""
+    def pdf_to_images(self, pdf_path: Union[str, Path], dpi: Optional[int] = None, first_page: Optional[int] = None,
+                      last_page: Optional[int] = None) -> List[Image.Image]:
+        """:248-295 — needs pdf2image + poppler exactly like the reference; absent here -> ImportError as data upstream.
+        first_page / last_page (1-based, as pdf2image counts): only those pages (the scanned-PDF path rasterises the pages it refuses)."""
         try:
             from pdf2image import convert_from_path
         except ImportError:
@@ -169,7 +171,8 @@ class ImagePreprocessor:
         path = Path(pdf_path)
         if not path.exists():
             raise FileNotFoundError(f"PDF not found: {path}")
-        return list(convert_from_path(str(path), dpi=dpi or self.target_dpi, fmt="png"))
+        span = {k: v for k, v in (("first_page", first_page), ("last_page", last_page)) if v is not None}
+        return list(convert_from_path(str(path), dpi=dpi or self.target_dpi, fmt="png", **span))
 
 
 image_preprocessor = ImagePreprocessor()
