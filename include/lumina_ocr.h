@@ -377,6 +377,26 @@ int lumina_ocr_flate_image_decode(lumina_ocr_t* h, const uint8_t* const* streams
 int lumina_ocr_ccitt_decode(lumina_ocr_t* h, const uint8_t* const* streams, const size_t* sizes, int n, int rows, int columns,
                             const int32_t* params, uint8_t* out_dev, int* status, void* stream);
 
+/* Strip-coded page images — the strips of a scanned TIFF page (utils/tiff_pages.py finds them) and PDF's /LZWDecode and
+ * /RunLengthDecode image streams (one strip a page).  The batch contract is lumina_ocr_flate_image_decode's: HOST pointers, n pages of
+ * one size, out_dev uint8 [n][height][width][3], a HOST status per page (0: exact pixels, the bytes of Pillow's
+ * Image.open(f).convert('RGB'); any other status: the page is left to Pillow, its pixels are undefined), `stream` synchronised.
+ * strips / sizes: m strips, those of page 0 first, each page's consecutive and in row order; strip k of a page covers rows
+ * [k * rows_per_strip, min(height, (k + 1) * rows_per_strip)) as whole packed rows.  strip_counts int32 [n] must each equal
+ * ceil(height / rows_per_strip) (else that page is -2) and add up to m (else the call fails).  params int32 [n][7] = {codec (1 none,
+ * 5 LZW: MSB-first codes of 9..12 bits with early change, 256 Clear, 257 EOI; 32773 PackBits), predictor (1; 2: horizontal differencing,
+ * 8-bit samples), components (1 | 3), bits per component (8; 1 / 2 / 4 with one component), indexed (0 | 1), invert (0 | 1: MinIsWhite
+ * or /Decode [1 0], one non-indexed component), rle_eod (0 | 1: a PackBits header byte of 128 ends the data as in /RunLengthDecode;
+ * 0 skips it as TIFF does)}; palettes as for lumina_ocr_flate_image_decode.  A page's status is the lowest of its strips':
+ * 0 exactly when the strip produced its rows x row bytes (codes or bytes after that are ignored, no EOI is needed);
+ * -1: an LZW code above the next free entry, a code >= 258 right after Clear, a full table followed by anything but Clear, EOI or the end
+ * of the data before the strip is full, a PackBits literal or repeat that runs past the input, fewer raw bytes than the strip's rows;
+ * -2: a combination outside this list, or an LZW strip whose first code is not Clear (old-style LSB-first LZW among them).
+ * Output is clipped at the strip's end; a hostile stream ends in -1 after at most one step per 9 bits (LZW) or per byte (PackBits). */
+int lumina_ocr_strip_image_decode(lumina_ocr_t* h, const uint8_t* const* strips, const size_t* sizes, int m, const int32_t* strip_counts, int n,
+                                  int height, int width, int rows_per_strip, const int32_t* params, const uint8_t* const* palettes,
+                                  uint8_t* out_dev, int* status, void* stream);
+
 int lumina_ocr_jpeg_coefficients(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int quality, int16_t* coefs_dev,
                                  void* stream);
 

@@ -15,6 +15,7 @@
 #include "runs.h"
 #include "jpeg.h"
 #include "jpegdec.h"
+#include "lzw.h"
 #include "pngdec.h"
 #include "ccitt.h"
 #include "stem_conv.h"
@@ -491,6 +492,17 @@ int lumina_ocr_flate_image_decode(lumina_ocr_t* h, const uint8_t* const* streams
     BIND(h);
     API_TRY
     return flate_image_run(h, streams, sizes, n, height, width, params, palettes, out_dev, status, (hipStream_t)stream);
+    API_CATCH(h)
+}
+
+int lumina_ocr_strip_image_decode(lumina_ocr_t* h, const uint8_t* const* strips, const size_t* sizes, int m, const int32_t* strip_counts, int n,
+                                  int height, int width, int rows_per_strip, const int32_t* params, const uint8_t* const* palettes,
+                                  uint8_t* out_dev, int* status, void* stream) {
+    if (!h || !strips || !sizes || !strip_counts || !params || !out_dev || !status || m < 0 || n <= 0 || height <= 0 || width <= 0 || rows_per_strip <= 0)
+        return locr_fail(h, "strip_image_decode", "bad arguments");
+    BIND(h);
+    API_TRY
+    return strip_image_run(h, strips, sizes, m, strip_counts, n, height, width, rows_per_strip, params, palettes, out_dev, status, (hipStream_t)stream);
     API_CATCH(h)
 }
 

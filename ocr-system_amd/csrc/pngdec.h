@@ -33,3 +33,17 @@ int pngdec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes
 // an inflated length other than rows x row bytes) / -2 a combination outside this list.
 int flate_image_run(lumina_ocr* eng, const uint8_t* const* streams, const size_t* sizes, int n, int height, int width, const int* params,
                     const uint8_t* const* palettes, uint8_t* out_dev, int* status, hipStream_t st);
+
+// One image of a sub-batch as the device stages see it.  The row stage below reads width .. out_index, fb .. pal and foff.
+struct PdFile {
+    unsigned long long zoff, foff;   // byte offsets of the zlib stream / the filtered scanlines in the sub-batch's buffers
+    unsigned zlen, rb, total;        // stream bytes; bytes per row (filter byte excluded); inflated bytes = height * (rb + fb)
+    int width, height, ct, depth, bpp, npal, wsize, valid, out_index, ablk_off;
+    int fb, tiff, invert;            // filter bytes per row (1: PNG rows; 0: packed rows of a PDF Flate image); /Predictor 2 rows; /Decode [1 0]
+    uint8_t pal[768];
+};
+
+// The row stage both flate_image_run and strip_image_run (lzw.h) end with: rows at rows + F[k].foff (F[k].rb + F[k].fb bytes each) ->
+// out_dev[F[k].out_index] as RGB; pd_tiff_predict first where any_tiff (the F[k].tiff images).  F, rows, err: device; images with
+// err[k] != 0 or !valid are skipped.  Launches only.
+void pd_rows_to_rgb(const PdFile* F, uint8_t* rows, const int* err, int nb, int height, int width, bool any_tiff, uint8_t* out_dev, hipStream_t st);

@@ -39,14 +39,6 @@ constexpr size_t PD_Z_PAD = 512;        // zero tail per file: the bit reader's 
 
 enum : int { PD_E_STREAM = 1, PD_E_PALETTE = 2, PD_E_ADLER = 4, PD_E_FILTER = 8 };
 
-struct PdFile {
-    unsigned long long zoff, foff;   // byte offsets of the zlib stream / the filtered scanlines in the sub-batch's buffers
-    unsigned zlen, rb, total;        // stream bytes; bytes per row (filter byte excluded); inflated bytes = height * (rb + fb)
-    int width, height, ct, depth, bpp, npal, wsize, valid, out_index, ablk_off;
-    int fb, tiff, invert;            // filter bytes per row (1: PNG rows; 0: packed rows of a PDF Flate image); /Predictor 2 rows; /Decode [1 0]
-    uint8_t pal[768];
-};
-
 __constant__ unsigned short pd_len_base[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
 __constant__ unsigned char pd_len_extra[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
 __constant__ unsigned short pd_dist_base[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
@@ -735,9 +727,7 @@ int pd_run_walked(lumina_ocr* eng, const std::vector<Walk>& W, const uint8_t* co
             hipLaunchKernelGGL(pd_adler_part, dim3((unsigned)max_ablk, nb), dim3(256), 0, st, w.F, w.filt, w.err, w.part);
             hipLaunchKernelGGL(pd_adler_fin, dim3(nb), dim3(256), 0, st, w.F, w.filt, w.part, w.adler_want, w.err);
             if (any_fb) hipLaunchKernelGGL(pd_unfilter, dim3(nb), dim3(64), 0, st, w.F, w.filt, w.err);
-            if (any_tiff) hipLaunchKernelGGL(pd_tiff_predict, dim3((unsigned)std::min(height, 1024), nb), dim3(64), 0, st, w.F, w.filt, w.err);
-            const size_t npx = (size_t)width * height;
-            hipLaunchKernelGGL(pd_expand, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 4096), nb), dim3(256), 0, st, w.F, w.filt, w.err, out_dev);
+            pd_rows_to_rgb(w.F, w.filt, w.err, nb, height, width, any_tiff, out_dev, st);
             hipLaunchKernelGGL(pd_status, dim3((nb + 63) / 64), dim3(64), 0, st, w.F, w.err, w.status, nb);
             std::vector<int> dev_status((size_t)nb);
             LOCR_CHECK(hipMemcpyAsync(dev_status.data(), w.status, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
@@ -752,6 +742,12 @@ int pd_run_walked(lumina_ocr* eng, const std::vector<Walk>& W, const uint8_t* co
 }
 
 }  // namespace
+
+void pd_rows_to_rgb(const PdFile* F, uint8_t* rows, const int* err, int nb, int height, int width, bool any_tiff, uint8_t* out_dev, hipStream_t st) {
+    if (any_tiff) hipLaunchKernelGGL(pd_tiff_predict, dim3((unsigned)std::min(height, 1024), nb), dim3(64), 0, st, F, rows, err);
+    const size_t npx = (size_t)width * height;
+    hipLaunchKernelGGL(pd_expand, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 4096), nb), dim3(256), 0, st, F, rows, err, out_dev);
+}
 
 size_t pngdec_workspace_bytes(int n, size_t z_total, size_t filt_total, size_t adler_blocks) {
     Arena a;

@@ -81,6 +81,7 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_png_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_flate_image_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
         "lumina_ocr_ccitt_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "lumina_ocr_strip_image_decode": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
         "lumina_ocr_load_svtr_weights": (i32, [vp, vp, sz]),
         "lumina_ocr_svtr_forward": (i32, [vp, vp, vp, i32, vp, vp, vp]),
         "lumina_ocr_svtr_num_classes": (i32, [vp]),
@@ -124,7 +125,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_load_cls_weights", "lumina_ocr_cls_forward", "lumina_ocr_rec_forward",
     "lumina_ocr_ctc_decode", "lumina_ocr_ctc_decode_words", "lumina_ocr_conv2d", "lumina_ocr_read_tap", "lumina_ocr_conv_timing", "lumina_ocr_conv_timing_detail",
     "lumina_ocr_resize_lanczos", "lumina_ocr_enhance", "lumina_ocr_jpeg_encode", "lumina_ocr_jpeg_coefficients", "lumina_ocr_jpeg_probe", "lumina_ocr_jpeg_decode", "lumina_ocr_jpeg_decode_async", "lumina_ocr_jpeg_last_passes",
-    "lumina_ocr_png_probe", "lumina_ocr_png_decode", "lumina_ocr_flate_image_decode", "lumina_ocr_ccitt_decode",
+    "lumina_ocr_png_probe", "lumina_ocr_png_decode", "lumina_ocr_flate_image_decode", "lumina_ocr_ccitt_decode", "lumina_ocr_strip_image_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
     "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks", "lumina_ocr_selection_marks_round",
     "lumina_ocr_rules_and_marks_round", "lumina_ocr_barcodes",
@@ -286,6 +287,33 @@ class Engine:
         n, out, streams, ptrs, sizes, status = self._stream_batch(streams, rows, columns, out)
         flat = (ctypes.c_int32 * (4 * n))(*[int(v) for p in params for v in p])
         self._chk(self.lib.lumina_ocr_ccitt_decode(self._h, ptrs, sizes, n, int(rows), int(columns), flat, _ptr(out), status, self._stream()))
+        return out, list(status)
+
+    def strip_image_decode(self, pages, height: int, width: int, rows_per_strip: int, params, palettes=None, out=None):
+        """Strip-coded page images (the strips of scanned TIFF pages; PDF /LZWDecode and /RunLengthDecode streams as one-strip pages), all
+        height x width with rows_per_strip rows a strip -> (uint8 [n,H,W,3] device, status list).  pages: per page the sequence of its
+        strips (bytes or memoryviews) in row order; params: per page (codec 1 none | 5 LZW | 32773 PackBits, predictor, components, bits,
+        indexed, invert, rle_eod); palettes: per page None or 768 bytes of RGB (see lumina_ocr.h).  status 0: exact pixels, -1 corrupt,
+        -2 outside the supported combinations (a strip count other than ceil(height / rows_per_strip) among them)."""
+        torch = _torch()
+        n = len(pages)
+        if out is None:
+            out = torch.empty((n, height, width, 3), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        strips = [s if isinstance(s, bytes) else bytes(s) for p in pages for s in p]
+        m = len(strips)
+        ptrs = (ctypes.c_char_p * max(m, 1))(*strips)
+        sizes = (ctypes.c_size_t * max(m, 1))(*[len(s) for s in strips])
+        counts = (ctypes.c_int32 * n)(*[len(p) for p in pages])
+        flat = (ctypes.c_int32 * (7 * n))(*[int(v) for p in params for v in p])
+        assert len(flat) == 7 * n
+        pals = None
+        if palettes is not None and any(p is not None for p in palettes):
+            keep = [None if p is None else bytes(p) for p in palettes]
+            assert all(p is None or len(p) == 768 for p in keep)
+            pals = (ctypes.c_char_p * n)(*keep)
+        status = (ctypes.c_int * n)()
+        self._chk(self.lib.lumina_ocr_strip_image_decode(self._h, ptrs, sizes, m, counts, n, int(height), int(width), int(rows_per_strip), flat, pals,
+                                                         _ptr(out), status, self._stream()))
         return out, list(status)
 
     @property

@@ -32,7 +32,7 @@ from ..utils import layout
 from ..utils import barcodes as barcode_layout
 from ..utils import marks as mark_layout
 from ..utils import page_orient
-from ..utils import pdf_pages
+from ..utils import pdf_pages, tiff_pages
 from ..utils import tables as table_layout
 from ..utils.image_preprocessing import ImagePreprocessor, get_optimal_size
 
@@ -120,6 +120,10 @@ class OCRService:
         # on the device from its embedded stream, at the image's own sample grid, instead of being rasterised by pdf2image / poppler; other
         # pages still go to pdf_to_images.  Off by default: process_pdf_sync is then the rasterise-and-batch path alone.
         self.device_pdf = os.environ.get("LUMINA_OCR_PDF_SCANS", "0").lower() not in ("", "0", "false", "no")
+        # LUMINA_OCR_DEVICE_TIFF=1: stripped TIFF inputs (LZW, PackBits, Deflate, Group 4, uncompressed; utils/tiff_pages.py) are decoded on
+        # the device, process_tiff_sync reads every page of a multi-page TIFF, and process_document sends "tiff" and "tif" there.  Off by
+        # default: a TIFF is then decoded by Pillow, first frame only, and every output is exactly the one without the option.
+        self.device_tiff = os.environ.get("LUMINA_OCR_DEVICE_TIFF", "0").lower() not in ("", "0", "false", "no")
         self.apply_binarize = "adaptive" if b in ("1", "true", "yes", "adaptive") else ("simple" if b == "simple" else None)
         self._device = int(os.environ.get("LUMINA_OCR_DEVICE", os.environ.get("LOCAL_RANK", 0)))
         self._det_weights = os.environ.get("LUMINA_OCR_DET_WEIGHTS", "")
@@ -464,6 +468,10 @@ class OCRService:
 
     def process_image_sync(self, image_source: Union[str, Path, Image.Image, bytes], page_number: int = 1) -> OCROutput:
         data = None
+        if self.device_tiff and isinstance(image_source, (bytes, str, Path)):
+            r = self._process_tiff_on_device(image_source, page_number)
+            if r is not None:
+                return r
         if self.device_png and isinstance(image_source, (bytes, str, Path)):
             r = self._process_png_on_device(image_source, page_number)
             if r is not None:
@@ -640,6 +648,11 @@ class OCRService:
                 try:
                     if filt == "DCTDecode":
                         out, status = eng.jpeg_decode(streams, h, w) if self.device_jpeg else (None, [-2] * len(idxs))
+                    elif filt in ("LZWDecode", "RunLengthDecode"):   # one-strip pages of the strip decoders
+                        codec = 5 if filt == "LZWDecode" else 32773
+                        params = [(codec, r.params["predictor"], r.params["components"], r.params["bits"], int(r.params["indexed"]),
+                                   int(r.params["invert"]), int(filt == "RunLengthDecode")) for r in recs]
+                        out, status = eng.strip_image_decode([[s] for s in streams], h, w, h, params, [r.params["palette"] for r in recs])
                     elif filt == "FlateDecode":
                         params = [(r.params["predictor"], r.params["components"], r.params["bits"], int(r.params["indexed"]), int(r.params["invert"]))
                                   for r in recs]
@@ -674,7 +687,7 @@ class OCRService:
         try:
             data = Path(pdf_path).read_bytes()
             try:
-                entries = pdf_pages.read_pages(data)
+                entries = pdf_pages.read_pages(data, strip_filters=self.device_tiff)
             except pdf_pages.PdfRefused as e:   # not a file the reader takes: the rasterise-and-batch path, whole
                 r = self.process_pdf_as_images_sync(pdf_path)
                 if not r.success and r.error and not r.pages:
@@ -712,6 +725,154 @@ class OCRService:
         except Exception as e:
             return DocumentOCRResult(success=False, error=str(e), total_processing_time_ms=_ms_since(t0))
 
+    # ---- scanned TIFFs (LUMINA_OCR_DEVICE_TIFF=1): the pages' strips, decoded on the device ----
+    def _decode_tiff_strips_in_place(self, eng, recs, w: int, h: int, rps: int, group4: bool):
+        """Group 4 and Deflate pages of one shape through the existing one-image decoders: a strip is an image of rps rows, and the strips
+        of a page are contiguous rows of its output.  The full strips of all pages decode in one call (in place as a [n * k, rps, W, 3] view
+        when the height is a multiple of rps, else into a temporary that is copied); the shorter last strips of all pages go in one more.  -> (pages uint8 [n,H,W,3], status per page = the lowest of its strips')."""
+        import torch
+        n = len(recs)
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=torch.device("cuda", self._device))
+        full, rem = h // rps, h % rps
+        status = [0] * n
+
+        def run(strips, owners, rows, view):
+            if group4:
+                _, st = eng.ccitt_decode(strips, rows, w, [recs[o].ccitt_params() for o in owners], out=view)
+            else:
+                _, st = eng.flate_image_decode(strips, rows, w, [recs[o].flate_params() for o in owners], [recs[o].palette for o in owners], out=view)
+            for o, v in zip(owners, st):
+                status[o] = min(status[o], v)
+
+        if full and rem == 0:     # the pages follow each other without a gap: every strip of the group in one call, in place
+            run([s for r in recs for s in r.strips], [k for k in range(n) for _ in range(full)], rps, out.view(n * full, rps, w, 3))
+        elif full:                # a shorter last strip separates the pages: all full strips in one call into a temporary, then copied
+            body = torch.empty((n * full, rps, w, 3), dtype=torch.uint8, device=out.device)
+            run([s for r in recs for s in r.strips[:full]], [k for k in range(n) for _ in range(full)], rps, body)
+            out[:, :full * rps] = body.view(n, full * rps, w, 3)
+        if rem:
+            last = torch.empty((n, rem, w, 3), dtype=torch.uint8, device=out.device)
+            run([r.strips[full] for r in recs], list(range(n)), rem, last)
+            out[:, full * rps:] = last
+        return out, status
+
+    def _decode_tiff_pages(self, entries, reasons: Dict[int, str]) -> Dict[int, Any]:
+        """The accepted pages of tiff_pages.read_pages -> {page index: device tensor [1,H,W,3], Orientation applied}: grouped by codec
+        and shape, one decoder call per group (Group 4 and Deflate: see _decode_tiff_strips_in_place).  A page a decoder refuses gets its
+        reason in `reasons` (it goes to Pillow)."""
+        groups: Dict[Any, List[int]] = {}
+        for i, e in enumerate(entries):
+            if isinstance(e, tiff_pages.PageImage):
+                kind = e.codec if e.codec in ("group4", "deflate") else "strips"
+                groups.setdefault((kind, e.width, e.height, e.rows_per_strip), []).append(i)
+        res: Dict[int, Any] = {}
+        if not groups:
+            return res
+        self._ensure_engine()
+        eng = self._engine
+        with self._device_ctx():
+            for (kind, w, h, rps), idxs in groups.items():
+                recs = [entries[i] for i in idxs]
+                try:
+                    if kind == "strips":
+                        out, status = eng.strip_image_decode([r.strips for r in recs], h, w, rps, [r.strip_params() for r in recs],
+                                                             [r.palette for r in recs])
+                    else:
+                        out, status = self._decode_tiff_strips_in_place(eng, recs, w, h, rps, kind == "group4")
+                except Exception as e:   # the engine's own failure: these pages go to Pillow
+                    for i in idxs:
+                        reasons[i] = "%s decode failed: %s" % (kind, e)
+                    continue
+                for k, i in enumerate(idxs):
+                    if status[k] != 0:
+                        reasons[i] = "%s strips %s (status %d)" % (recs[k].codec, "corrupt" if status[k] == -1 else "outside the device subset", status[k])
+                        continue
+                    res[i] = eng.exif_transpose(out[k:k + 1], recs[k].orientation)
+        return res
+
+    def _process_tiff_on_device(self, image_source: Union[str, Path, bytes], page_number: int) -> Optional[OCROutput]:
+        """A TIFF path / bytes whose first page the device decodes -> its result; None: today's path."""
+        try:
+            if isinstance(image_source, bytes):
+                data = image_source
+            else:
+                with open(image_source, "rb") as f:
+                    if not tiff_pages.is_tiff(f.read(4)):
+                        return None
+                data = Path(image_source).read_bytes()
+        except OSError:
+            return None
+        if not tiff_pages.is_tiff(data[:4]):
+            return None
+        try:
+            first = tiff_pages.read_pages(data, max_pages=1)[0]
+            if not isinstance(first, tiff_pages.PageImage):
+                return None
+            image = Image.open(io.BytesIO(data))      # lazily opened: consulted for its size only
+            reasons: Dict[int, str] = {}
+            decoded = self._decode_tiff_pages([first], reasons).get(0)
+            if decoded is None or (int(decoded.shape[2]), int(decoded.shape[1])) != image.size:
+                return None
+        except Exception as e:       # any doubt: the reference's own path
+            logger.warning("device TIFF decode not used: %s", e)
+            return None
+        return self._process_single_image_sync(image, page_number, decoded=decoded)
+
+    def process_tiff_sync(self, tiff_path: Union[str, Path]) -> DocumentOCRResult:
+        """Every page (IFD) of a TIFF: decoded on the device where the reader and the decoders take it, by Pillow (Image.open; seek(k))
+        where they do not; same-size pages run through the engine as one batch; tables are numbered over the document."""
+        t0 = time.time()
+        path = Path(tiff_path)
+        if not path.exists():
+            return DocumentOCRResult(success=False, error=f"File not found: {path}")
+        try:
+            data = path.read_bytes()
+            entries = tiff_pages.read_pages(data)
+            reasons: Dict[int, str] = {}
+            if isinstance(entries[0], tiff_pages.TiffRefused) and entries[0].whole_file:
+                # not a file the reader takes: every frame Pillow finds is Pillow's
+                try:
+                    with Image.open(io.BytesIO(data)) as probe:
+                        n = int(getattr(probe, "n_frames", 1))
+                except Exception as e:
+                    return DocumentOCRResult(success=False, error="%s (TIFF reader: %s)" % (e, entries[0].reason), total_processing_time_ms=_ms_since(t0))
+                reasons = {i: entries[0].reason for i in range(n)}
+                entries = [entries[0]] * n
+            n = len(entries)
+            for i, e in enumerate(entries):
+                if isinstance(e, tiff_pages.TiffRefused):
+                    reasons.setdefault(i, e.reason)
+            out: List[Optional[OCROutput]] = [None] * n
+            with self._semaphore:
+                try:
+                    on_device = self._decode_tiff_pages(entries, reasons)
+                except Exception as e:   # no engine: errors are data
+                    return DocumentOCRResult(success=False, error=str(e), total_processing_time_ms=_ms_since(t0))
+                for i in range(n):
+                    if i in on_device:
+                        continue
+                    why = reasons.get(i, "not decoded")
+                    try:   # Pillow's frame, as every TIFF is read with the option off; it joins the group of its size
+                        im = Image.open(io.BytesIO(data))
+                        im.seek(i)
+                        prepared = self._prepare(self._pre._normalise_mode(im))
+                        with self._device_ctx():
+                            on_device[i] = self._upload(self._stage_pages([prepared]))
+                    except Exception as e:
+                        out[i] = OCROutput(success=False, error="page %d is not a page the device decodes (%s) and Pillow could not decode it: %s"
+                                           % (i + 1, why, e), page_number=i + 1)
+                groups: Dict[Any, List[int]] = {}
+                sizes: List[Any] = [None] * n
+                for i, page in on_device.items():
+                    sizes[i] = (int(page.shape[2]), int(page.shape[1]))   # the size the page has after Orientation
+                    groups.setdefault(sizes[i], []).append(i)
+                for idxs in groups.values():
+                    self._run_group(sorted(idxs), on_device, None, sizes, 1, out)
+            self._number_tables(out)
+            return self._document_from_pages(out, t0)  # type: ignore[arg-type]
+        except Exception as e:
+            return DocumentOCRResult(success=False, error=str(e), total_processing_time_ms=_ms_since(t0))
+
     # ---- async wrappers (:666-731) ----
     async def process_image(self, image_source, page_number: int = 1, timeout: float = 120.0) -> OCROutput:
         try:
@@ -732,6 +893,11 @@ class OCRService:
             return DocumentOCRResult(success=False, error=f"File not found: {path}")
         if file_type == "pdf":
             return await self.process_pdf(path)
+        if self.device_tiff and file_type in ("tiff", "tif"):
+            try:
+                return await asyncio.wait_for(asyncio.to_thread(self.process_tiff_sync, path), timeout=600.0)
+            except asyncio.TimeoutError:
+                return DocumentOCRResult(success=False, error="Timed out after 600.0s")
         if file_type in SUPPORTED_IMAGE_TYPES:
             r = await self.process_image(path)
             return DocumentOCRResult(pages=[r], total_pages=1, total_processing_time_ms=r.processing_time_ms, success=r.success,
@@ -741,7 +907,7 @@ class OCRService:
     # ---- status (:759-795) ----
     def get_status(self) -> Dict[str, Any]:
         st = {"client_initialized": self._pipeline is not None, "model_id": "dbnet-r18vd+crnn-mv3", "max_dimension": self.max_dimension,
-              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "device_pdf": self.device_pdf, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
+              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "device_pdf": self.device_pdf, "device_tiff": self.device_tiff, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
         if self._engine is not None:
             st["engine_version"] = self._engine.version()
             st["num_classes"] = self._engine.num_classes

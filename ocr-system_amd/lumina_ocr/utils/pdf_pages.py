@@ -18,8 +18,9 @@ Supported page: content streams holding nothing but q, Q, cm and exactly one Do 
 onto the MediaBox: axis-aligned, positive scales, each edge within 1 % of the box side.
 Supported image: /BitsPerComponent 1 or 8 (2 and 4 for grey / indexed Flate images); /ColorSpace DeviceGray, DeviceRGB, ICCBased with
 N = 1 or 3 (READ AS ITS DEVICE ALTERNATE: the profile is not applied, as Pillow does not apply it to a JPEG or PNG file either), or
-Indexed over those with hival <= 255; one /Filter (a name or a one-element array) of DCTDecode, FlateDecode, CCITTFaxDecode; /Decode the
-default, or [1 0] on one-component Flate / CCITT images; no /ImageMask, /SMask or /Mask.
+Indexed over those with hival <= 255; one /Filter (a name or a one-element array) of DCTDecode, FlateDecode, CCITTFaxDecode (and, with
+strip_filters, LZWDecode and RunLengthDecode under the Flate rules); /Decode the default, or [1 0] on one-component Flate / CCITT
+images; no /ImageMask, /SMask or /Mask.
 
 The reader ends on any input: every loop advances through the file or a decoded stream, /Prev chains, page-tree nodes and indirect
 references are followed through visited-sets, every offset and /Length is checked against the file size, and the number of objects, the
@@ -37,6 +38,7 @@ MAX_PAGES = 20000
 MAX_META_BYTES = 32 << 20    # inflated size of one metadata stream
 EDGE_TOLERANCE = 0.01        # each image edge within this fraction of the MediaBox side
 FILTERS = ("DCTDecode", "FlateDecode", "CCITTFaxDecode")
+STRIP_FILTERS = ("LZWDecode", "RunLengthDecode")   # taken only when read_pages is asked to (strip_filters=True)
 
 _WS = b"\x00\t\n\x0c\r "
 _DELIM = b"()<>[]{}/%"
@@ -68,9 +70,10 @@ class Stream(dict):
 
 @dataclass
 class PageImage:
-    filter: str                     # "DCTDecode" | "FlateDecode" | "CCITTFaxDecode"
+    filter: str                     # "DCTDecode" | "FlateDecode" | "CCITTFaxDecode" | "LZWDecode" | "RunLengthDecode"
     stream: memoryview              # the image's raw stream, a view into the file
-    params: Dict[str, Any]          # FlateDecode: predictor, components, bits, indexed, invert, palette (768 bytes RGB or None)
+    params: Dict[str, Any]          # FlateDecode, LZWDecode, RunLengthDecode: predictor, components, bits, indexed, invert, palette
+    #                                 (768 bytes RGB or None); predictor is 1 | 2 for LZWDecode and 1 for RunLengthDecode
     #                                 CCITTFaxDecode: K, EncodedByteAlign, BlackIs1, invert;  DCTDecode: components
     width: int
     height: int
@@ -681,7 +684,7 @@ def _colour_space(doc: _Document, cs):
     return _components(doc, cs), None
 
 
-def _page_image(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any]) -> PageImage:
+def _page_image(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], strip_filters: bool = False) -> PageImage:
     box = doc.resolve(attrs.get("MediaBox"))
     if not isinstance(box, list) or len(box) != 4:
         raise PdfRefused("no MediaBox")
@@ -732,7 +735,7 @@ def _page_image(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any]) -> 
     if not all(isinstance(v, int) and 0 < v <= 65535 for v in (width, height)):
         raise PdfRefused("malformed image size")
     filt, parms = doc.single_filter(img)
-    if filt not in FILTERS:
+    if filt not in FILTERS and not (strip_filters and filt in STRIP_FILTERS):
         raise PdfRefused("image filter %s" % filt)
     bits = doc.resolve(img.get("BitsPerComponent", 1 if filt == "CCITTFaxDecode" else None))
     comps, palette = _colour_space(doc, img.get("ColorSpace"))
@@ -759,12 +762,17 @@ def _page_image(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any]) -> 
             raise PdfRefused("CCITT /Columns or /Rows differ from the image size")
         params = {"K": k, "EncodedByteAlign": parms.get("EncodedByteAlign", False) is True, "BlackIs1": parms.get("BlackIs1", False) is True,
                   "invert": invert}
-    else:
+    else:   # FlateDecode, LZWDecode, RunLengthDecode: the same rows, the same rules for bits, colour space and /Decode
+        kind = {"FlateDecode": "Flate", "LZWDecode": "LZW", "RunLengthDecode": "RunLength"}[filt]
         if bits not in ((1, 2, 4, 8) if comps == 1 else (8,)):
-            raise PdfRefused("Flate image with %r bits per component" % (bits,))
+            raise PdfRefused("%s image with %r bits per component" % (kind, bits))
+        if filt == "RunLengthDecode":
+            parms = {}                                   # (the filter has no parameters)
+        if filt == "LZWDecode" and parms.get("EarlyChange", 1) != 1:
+            raise PdfRefused("LZW /EarlyChange %r" % (parms.get("EarlyChange"),))
         pred = parms.get("Predictor", 1)
-        if pred not in (1, 2, 10, 11, 12, 13, 14, 15):
-            raise PdfRefused("Flate /Predictor %r" % (pred,))
+        if pred not in ((1, 2, 10, 11, 12, 13, 14, 15) if filt == "FlateDecode" else (1, 2)):
+            raise PdfRefused("%s /Predictor %r" % (kind, pred))
         if pred != 1 and (parms.get("Colors", 1), parms.get("BitsPerComponent", 8), parms.get("Columns", 1)) != (comps, bits, width):
             raise PdfRefused("predictor parameters differ from the image")
         if pred == 2 and bits != 8:
@@ -773,15 +781,18 @@ def _page_image(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any]) -> 
     return PageImage(filter=filt, stream=img.raw, params=params, width=width, height=height, rotate=rotate, media_box=(x0, y0, x1, y1))
 
 
-def read_pages(data) -> List[Union[PageImage, PdfRefused]]:
+def read_pages(data, strip_filters: bool = False) -> List[Union[PageImage, PdfRefused]]:
     """One entry per page of the PDF in `data` (bytes, or anything with the buffer protocol: the records' streams are views into it):
-    the page's image record, or the PdfRefused that says why the page is not a scanned page.  Raises PdfRefused for the whole file."""
+    the page's image record, or the PdfRefused that says why the page is not a scanned page.  Raises PdfRefused for the whole file.
+    strip_filters: also take /LZWDecode (/EarlyChange 1 or absent, /Predictor 1 or 2) and /RunLengthDecode images, which
+    lumina_ocr_strip_image_decode decodes as one-strip pages (the provider asks for them with LUMINA_OCR_DEVICE_TIFF=1); without it
+    they are refused as any other filter is."""
     try:
         doc = _Document(data)
         out: List[Union[PageImage, PdfRefused]] = []
         for page, attrs in doc.pages():
             try:
-                out.append(_page_image(doc, page, attrs))
+                out.append(_page_image(doc, page, attrs, strip_filters))
             except PdfRefused as e:
                 out.append(e)
         return out
