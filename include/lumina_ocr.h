@@ -265,6 +265,33 @@ int lumina_ocr_barcodes(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int he
                         int min_rows, int row_gap, int max_codes, int32_t* codes_dev, int32_t* syms_dev, int32_t* counts_dev,
                         const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream);
 
+/* QR codes: QR Code Model 2 symbols (ISO/IEC 18004) of versions 1-10 on the pages, located, sampled and error-corrected on the device
+ * (the host half is lumina_ocr/utils/qrcodes.py).  ink as in lumina_ocr_table_rules.  Of the 8-connected components of the ink a CORE
+ * is a solid square (sides 3 min_module .. 3 max_module, 4 |w - h| <= min(w, h), 4 area >= 3 w h) whose centre row has, before and
+ * after the core's run, two runs of one other component, the RING, concentric within centre_tol / 16 of a module and 7/3 of the
+ * core's size within ring_tol / 16 of a module (the ring's w + h stands for 14 modules): a finder, its centre the ring's in doubled
+ * pixel coordinates.  A finder A is a symbol's corner with the partners B (+x) and C (+y) when |AB|^2 and |AC|^2 agree within a
+ * quarter, |cos| <= 1/8, cross(AB, AC) > 0 in image coordinates (all four rotations, no mirror images), the module estimates agree
+ * within a quarter and a version lies within three modules of |AB|; the valid pairs are tried in the order of |AB|^2 + |AC|^2
+ * (then the partners' roots), eight at most, and the first that decodes is the corner's symbol.  Module (col i, row j) is the ink
+ * at A + ((i - 3) AB + (j - 3) AC) / (D - 7), rounded down to a pixel, clear off the page.  Of the versions in reach the one with the fewest timing-pattern mismatches is read (at most timing_max); the
+ * `quiet` rings of modules round the symbol must be clear; the format information is the nearer of the 32 words within distance 3,
+ * the first copy preferred; the codewords are unmasked, read in placement order, de-interleaved and corrected block by block over
+ * GF(256) (0x11D, roots alpha^0 ..), and the syndromes of the corrected block must vanish.
+ * codes_dev int32 [n][max_codes][12] = x0, y0, x1, y1 (the hull of the symbol's corners, inclusive), version, level (0..3 = L, M, Q,
+ * H), mask, ndata, corrected errors, rotation (quarter turns clockwise), format distance (+ 16 when the second copy was read), timing
+ * mismatches; sorted by (y0, x0, y1, x1, root of the corner finder's core), rows past the count untouched; data_dev int32
+ * [n][max_codes][288] = the corrected data codewords, zero behind ndata; counts_dev int32 [n] = the true number (a list whose count
+ * exceeds max_codes is not written); finder_counts_dev: optional, int32 [n] = the finders of each page (a page with more than
+ * max_finders is not read: its count is 0).  mask_in_dev / mask_out_dev as in lumina_ocr_barcodes.  1 <= min_module <= max_module <= 64,
+ * 0 <= quiet <= 4, 0 <= centre_tol, ring_tol <= 64, 0 <= timing_max <= 128, max_finders 1..64, max_codes 1..64, sides 1..65535;
+ * defaults in lumina_ocr/arch.py QR_PARAMS.  Integer arithmetic throughout: the result is defined bit for bit
+ * (tests/qr_reference.py).  Asynchronous; n == 0 is a no-op; bad arguments return a status before anything is written. */
+int lumina_ocr_qrcodes(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module, int max_module,
+                       int quiet, int centre_tol, int ring_tol, int timing_max, int max_finders, int max_codes, int32_t* codes_dev,
+                       int32_t* data_dev, int32_t* counts_dev, int32_t* finder_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev,
+                       void* stream);
+
 /* ---- page orientation (optional; DESIGN.md: "Page orientation") ----
  * A page is upright after `turn` quarter turns: upright = np.rot90(page, turn) (counter-clockwise).  The three entries below are the
  * device half; which pages get which turn is decided on the host (lumina_ocr/utils/page_orient.py, OcrPipeline.run_oriented).

@@ -1,0 +1,36 @@
+#pragma once
+#include "common.h"
+
+// QR codes (Model 2, versions 1-10) of a batch of pages, on the device (qrcodes.hip; definition restated in tests/qr_reference.py).
+// Integer arithmetic throughout: the result does not depend on the order anything runs in.
+struct QrParams {
+    const uint8_t* rgb;   // [B][H][W][3]
+    int B, H, W;
+    int threshold;        // ink = L < threshold, L = Pillow's convert('L')
+    int min_module, max_module;   // a finder's core (3 x 3 modules) has sides 3 min_module .. 3 max_module
+    int quiet;            // rings of clear modules round the symbol (0 .. QR_MAX_QUIET; pixels off the page are clear)
+    int centre_tol;       // core and ring centres agree within centre_tol / 16 of a module
+    int ring_tol;         // the ring's sides are 7/3 of the core's within ring_tol / 16 of a module
+    int timing_max;       // mismatches allowed in the two timing patterns
+    int max_finders;      // capacity of a page's finder list (<= QR_MAX_FINDERS); a page with more finders is not read
+    int max_codes;        // capacity of a page's list (<= QR_MAX_CODES)
+    int* codes;           // device, [B][max_codes][12] = x0, y0, x1, y1 (the symbol's hull), version, level (0..3 = L, M, Q, H), mask, ndata,
+                          // corrected errors, rotation (quarter turns clockwise), format distance (+ 16: second copy), timing mismatches;
+                          // sorted by (y0, x0, y1, x1, corner finder's root)
+    int* data;            // device, [B][max_codes][QR_MAX_DATA]: the corrected data codewords, zero behind ndata
+    int* counts;          // device, [B]: true number of symbols (a list is not written when it overflows)
+    int* finder_counts;   // optional, device, [B]: true number of finder patterns
+    unsigned long long* mask_out;        // optional parity hook: ink mask [B][H][ceil(W / 64)], bit x % 64 of word x / 64
+    const unsigned long long* mask_in;   // optional: the ink mask of these pages at this threshold, already computed
+};
+constexpr int QR_MAX_DATA = 288;       // >= 274, the data codewords of 10-L
+constexpr int QR_MAX_FINDERS = 64;     // one wave64 lane per finder
+constexpr int QR_MAX_CODES = 64;
+constexpr int QR_MAX_MODULE = 64;
+constexpr int QR_MAX_QUIET = 4;
+constexpr int QR_MAX_TOL = 64;
+constexpr int QR_MAX_TIMING = 128;
+
+bool qr_params_ok(int min_module, int max_module, int quiet, int centre_tol, int ring_tol, int timing_max, int max_finders, int max_codes);
+size_t qrcodes_workspace_bytes(int B, int H, int W, int max_finders, int max_codes);
+hipError_t qrcodes_launch(const QrParams& p, void* workspace, size_t ws_bytes, hipStream_t st);

@@ -1,0 +1,543 @@
+// QR codes (Model 2, versions 1-10) on the GPU (gfx950): the symbols of a page as (x0, y0, x1, y1, version, level, mask, ndata, errors,
+// rotation, format distance, timing mismatches) with their corrected data codewords, in a canonical order.  Everything is integer and
+// every reduction is order-free (min / max / add / xor, ballots), so the lists equal the sequential definition restated in
+// tests/qr_reference.py.
+//
+// All stream-ordered kernels, no host round trip:
+//   1 ink_mask                          the mask (or the one the caller already has)
+//   2 run_count / row_scan / run_fill / run_merge   mask words -> run list and its 8-connected components (the shared kernels of runs.hip)
+//   3 qr_area, qr_accum   a run's length is its area; every run learns its root, box and area are accumulated at the root
+//   4 qr_finders  one wave per row, lanes over the row's roots: a solid square core whose centre row has, before and after the core's run,
+//                 two runs of one other component, the ring, concentric and 7/3 of its size -> counted, gathered per page
+//   5 qr_decode   one wave per (page, finder A): lanes over B, a loop over C pick A's partners (64-bit products, no division, no root),
+//                 the nearest valid pairs in turn until one decodes;
+//                 per version in reach lane r samples module row r on the affine grid as one 64-bit word and the timing patterns are
+//                 counted; quiet rings; both format copies against the 32 words (popcount, wave min); unmask; lanes gather the codewords
+//                 through the placement table from the rows in LDS; per block syndromes (lanes over positions, wave xor),
+//                 Berlekamp-Massey by one lane in LDS, Chien and Forney with lanes over positions, syndromes again.  Every loop has a
+//                 constant bound, every table and LDS index is clamped, and no wave waits for another (a work-group is one wave)
+//   6 qr_output   one work-group per page: valid candidates counted, gathered, rank-sorted by (y0, x0, y1, x1, corner root)
+#include "qrcodes.h"
+#include "qr_tables.h"
+#include "runs.h"
+
+namespace {
+
+typedef unsigned long long u64;
+typedef long long i64;
+
+constexpr int QR_SPAN = 8192;          // |B - A|, |C - A| per axis in doubled pixels: keeps every product inside 64 bits
+constexpr int RES_INTS = 16;           // a candidate's result: y0, x0, y1, x1, root, version, level, mask, ndata, errors, rotation, fdist, timing, valid
+constexpr int QR_MAX_TOTAL = 346, QR_MAX_BLOCK = 146, QR_MAX_EC = 30, QR_MAX_NB = 8;
+constexpr int BIG = 0x7fffffff;
+constexpr int QR_PAIR_TRIES = 8;      // of a corner's valid partner pairs, the nearest ones are tried in turn
+
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { const int o = __shfl_xor(v, d); v = o < v ? o : v; }
+    return v;
+}
+__device__ __forceinline__ int wave_xor(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v ^= __shfl_xor(v, d);
+    return v;
+}
+__device__ __forceinline__ int iabs(int v) { return v < 0 ? -v : v; }
+__device__ __forceinline__ i64 labs64(i64 v) { return v < 0 ? -v : v; }
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ __forceinline__ i64 floor_div(i64 a, i64 b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }   // b > 0
+
+// 3a: a run's own length is the start of its component's area
+__global__ __launch_bounds__(256) void qr_area_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* area, int H, size_t runcap,
+                                                      int rows_total) {
+    int pg, row, lane;
+    if (!row_wave(H, rows_total, pg, row, lane)) return;
+    const int* ro = runoff + (size_t)pg * (H + 1);
+    const size_t rb = (size_t)pg * runcap;
+    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) area[rb + id] = (int)rxe[rb + id] - (int)rxs[rb + id] + 1;
+}
+
+// 3b: parent = root; the root's box grows to the component's (as mk_accum of marks.hip) and its area by every other run's length
+__global__ __launch_bounds__(256) void qr_accum_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* parent, int4* box, int* area,
+                                                       int H, size_t runcap, int rows_total) {
+    int pg, row, lane;
+    if (!row_wave(H, rows_total, pg, row, lane)) return;
+    const int* ro = runoff + (size_t)pg * (H + 1);
+    const size_t rb = (size_t)pg * runcap;
+    int* P = parent + rb;
+    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
+        const int p = P[id];
+        if (p == id) continue;
+        const int root = uf_find(P, p);
+        if (root != p) P[id] = root;   // concurrent compressions only ever replace a parent by an ancestor
+        const int xs = rxs[rb + id], xe = rxe[rb + id];
+        int* b = reinterpret_cast<int*>(box + rb + root);
+        if (xs < __atomic_load_n(b + 0, __ATOMIC_RELAXED)) atomicMin(b + 0, xs);
+        if (xe > __atomic_load_n(b + 1, __ATOMIC_RELAXED)) atomicMax(b + 1, xe);
+        if (row > __atomic_load_n(b + 3, __ATOMIC_RELAXED)) atomicMax(b + 3, row);
+        atomicAdd(area + rb + root, xe - xs + 1);
+    }
+}
+
+// 4: finders [B][max_finders] = cx2, cy2, me, root
+__global__ __launch_bounds__(256) void qr_finders_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, const int* parent,
+                                                         const int4* box, const int* area, int H, size_t runcap, int min_module, int max_module, int centre_tol,
+                                                         int ring_tol, int max_finders, int* nfind, int4* finders, int rows_total) {
+    int pg, row, lane;
+    if (!row_wave(H, rows_total, pg, row, lane)) return;
+    const int* ro = runoff + (size_t)pg * (H + 1);
+    const size_t rb = (size_t)pg * runcap;
+    const int* P = parent + rb;
+    const unsigned short* xs = rxs + rb;
+    const unsigned short* xe = rxe + rb;
+    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
+        if (P[id] != id) continue;
+        const int4 bx = box[rb + id];   // x0, x1, y0, y1
+        const int w = bx.y - bx.x + 1, h = bx.w - bx.z + 1, mn = w < h ? w : h;
+        if (w < 3 * min_module || h < 3 * min_module || w > 3 * max_module || h > 3 * max_module || 4 * iabs(w - h) > mn) continue;
+        if (4 * (i64)area[rb + id] < 3 * (i64)w * h) continue;
+        const int yc = clampi((bx.z + bx.w) >> 1, 0, H - 1), xc = (bx.x + bx.y) >> 1;
+        const int r0 = ro[yc], r1 = ro[yc + 1];
+        int lo = r0, hi = r1;   // the first run of the row that ends at or behind xc
+        for (int it = 0; it < 17; ++it) {
+            if (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if ((int)xe[mid] < xc) lo = mid + 1; else hi = mid;
+            }
+        }
+        const int j = lo;
+        if (j <= r0 || j + 1 >= r1 || (int)xs[j] > xc || P[j] != id) continue;
+        const int q = P[j - 1];
+        if (q != P[j + 1] || q == id) continue;
+        const int4 rx = box[rb + q];
+        const int rw = rx.y - rx.x + 1, rh = rx.w - rx.z + 1, me = rw + rh;
+        if (112 * (i64)iabs((rx.x + rx.y) - (bx.x + bx.y)) > (i64)centre_tol * me || 112 * (i64)iabs((rx.z + rx.w) - (bx.z + bx.w)) > (i64)centre_tol * me) continue;
+        if (224 * (i64)iabs(3 * rw - 7 * w) > 3 * (i64)ring_tol * me || 224 * (i64)iabs(3 * rh - 7 * h) > 3 * (i64)ring_tol * me) continue;
+        const int idx = atomicAdd(&nfind[pg], 1);
+        if (idx < max_finders) finders[(size_t)pg * max_finders + idx] = make_int4(rx.x + rx.y + 1, rx.z + rx.w + 1, me, id);
+    }
+}
+
+// the versions (bit v) whose n = 10 + 4 v modules between finder centres lie within three modules of what l2 = |AB|^2 + |AC|^2 (doubled
+// pixels) and m = meA + meB + meC say
+__device__ __forceinline__ unsigned reach_mask(i64 l2, i64 m) {
+    unsigned out = 0;
+    const i64 t = 882 * l2;
+#pragma unroll
+    for (int v = 1; v <= QR_VERSIONS; ++v) {
+        const i64 lo = 2 * (7 + 4 * v) * m, hi = 2 * (13 + 4 * v) * m;
+        if (lo * lo <= t && t <= hi * hi) out |= 1u << v;
+    }
+    return out;
+}
+
+struct QrGrid { int ax, ay, abx, aby, acx, acy, n; };
+
+// module (col i, row j) of the grid: the ink at pixel (nx / 2n, ny / 2n); off the page reads clear
+__device__ __forceinline__ int qr_sample(const u64* mpage, int H, int W, int nw, const QrGrid& g, int i, int j) {
+    const int nx = g.ax * g.n + (i - 3) * g.abx + (j - 3) * g.acx, ny = g.ay * g.n + (i - 3) * g.aby + (j - 3) * g.acy;
+    if (nx < 0 || ny < 0) return 0;
+    const int px = nx / (2 * g.n), py = ny / (2 * g.n);
+    if (px >= W || py >= H) return 0;
+    return (int)((mpage[(size_t)py * nw + (px >> 6)] >> (px & 63)) & 1ull);
+}
+
+__device__ __forceinline__ bool qr_mask_bit(int mask, int y, int x) {
+    switch (mask) {
+        case 0: return (x + y) % 2 == 0;
+        case 1: return y % 2 == 0;
+        case 2: return x % 3 == 0;
+        case 3: return (x + y) % 3 == 0;
+        case 4: return (x / 3 + y / 2) % 2 == 0;
+        case 5: return x * y % 2 + x * y % 3 == 0;
+        case 6: return (x * y % 2 + x * y % 3) % 2 == 0;
+        default: return ((x + y) % 2 + x * y % 3) % 2 == 0;
+    }
+}
+
+struct QrLds {
+    u64 rows[64];
+    unsigned char exp[512], log[256], raw[384], blk[192];
+    int S[32], C[32], Bp[32], T[32], O[16];
+    int L;
+};
+
+__device__ __forceinline__ int gmul(const QrLds& s, int a, int b) { return a && b ? s.exp[s.log[a & 255] + s.log[b & 255]] : 0; }
+// a * alpha^e, 0 <= e <= 255 (log a + e <= 509, inside the doubled table)
+__device__ __forceinline__ int gmul_exp(const QrLds& s, int a, int e) { return a ? s.exp[s.log[a & 255] + e] : 0; }
+
+// the ec syndromes of s.blk[0 .. len) -> s.S; true when one is not zero.  (barriers inside: the whole wave calls it)
+__device__ __forceinline__ bool qr_syndromes(QrLds& s, int len, int ec, int lane) {
+    int nz = 0;
+    for (int k = 0; k < QR_MAX_EC; ++k) {
+        if (k >= ec) break;
+        int acc = 0;
+#pragma unroll
+        for (int p0 = 0; p0 < 192; p0 += 64) {
+            const int p = p0 + lane;
+            if (p < len) acc ^= gmul_exp(s, s.blk[p], (k * (len - 1 - p)) % 255);
+        }
+        acc = wave_xor(acc);
+        if (lane == 0) s.S[k] = acc;
+        nz |= acc;
+    }
+    __syncthreads();
+    return nz != 0;
+}
+
+// Berlekamp-Massey over s.S[0 .. ec) by one lane -> s.C (the locator), s.O (the evaluator's first L coefficients), s.L
+__device__ __forceinline__ void qr_locator(QrLds& s, int ec) {
+    for (int i = 0; i < 32; ++i) { s.C[i] = 0; s.Bp[i] = 0; }
+    s.C[0] = 1; s.Bp[0] = 1;
+    int L = 0, m = 1, b = 1;
+    for (int k = 0; k < QR_MAX_EC; ++k) {
+        if (k >= ec) break;
+        int d = s.S[k];
+        for (int i = 1; i <= QR_MAX_EC; ++i)
+            if (i <= L && i <= k) d ^= gmul(s, s.C[i], s.S[k - i]);
+        if (d == 0) { ++m; continue; }
+        for (int i = 0; i < 32; ++i) s.T[i] = s.C[i];
+        const int f = gmul_exp(s, d, 255 - s.log[b & 255]);
+        for (int i = 0; i <= QR_MAX_EC; ++i)
+            if (i + m <= ec) s.C[i + m] ^= gmul(s, f, s.Bp[i]);
+        if (2 * L <= k) {
+            L = k + 1 - L; b = d; m = 1;
+            for (int i = 0; i < 32; ++i) s.Bp[i] = s.T[i];
+        } else ++m;
+    }
+    for (int i = 0; i < 16; ++i) {
+        int o = 0;
+        if (i < L)
+            for (int j = 0; j <= 15; ++j)
+                if (j <= i) o ^= gmul(s, s.S[i - j], s.C[j]);
+        s.O[i] = o;
+    }
+    s.L = L;
+}
+
+// a candidate (the corner A of g with its partners) through the whole decode -> true with the result in o / od, false when it is none.
+// The whole wave calls it (barriers inside) and returns one answer.
+__device__ __forceinline__ bool qr_try(QrLds& s, const u64* mpage, int H, int W, int nw, QrGrid g, unsigned reach, int quiet, int timing_max, int ida, int lane,
+                                       int* o, unsigned char* od) {
+    // the version: fewest timing mismatches, the smaller on a tie
+    int timing = BIG, version = 0;
+    u64 row = 0;
+    for (int v = 1; v <= QR_VERSIONS; ++v) {
+        if (!((reach >> v) & 1u)) continue;
+        const int D = 17 + 4 * v;
+        g.n = D - 7;
+        u64 r = 0;
+        if (lane < D)
+            for (int i = 0; i < 57; ++i)
+                if (i < D) r |= (u64)qr_sample(mpage, H, W, nw, g, i, lane) << i;
+        __syncthreads();
+        s.rows[lane] = r;
+        __syncthreads();
+        const u64 span = ((1ull << (D - 16)) - 1ull) << 8;   // columns 8 .. D - 9
+        const int t = __popcll((s.rows[6] ^ 0x5555555555555555ull) & span) +
+                      __popcll(__ballot(lane >= 8 && lane <= D - 9 && (int)((r >> 6) & 1ull) != ((lane & 1) ^ 1)));
+        if (t < timing) { timing = t; version = v; row = r; }
+    }
+    if (version == 0 || timing > timing_max) return false;
+    const int D = 17 + 4 * version;
+    g.n = D - 7;
+    __syncthreads();
+    s.rows[lane] = row;
+    // the quiet rings
+    bool dirty = false;
+    for (int k = 1; k <= QR_MAX_QUIET; ++k) {
+        if (k > quiet) break;
+#pragma unroll
+        for (int t0 = 0; t0 < 128; t0 += 64) {
+            const int t = t0 + lane - k;
+            if (t < D + k)
+                dirty = dirty || qr_sample(mpage, H, W, nw, g, t, -k) || qr_sample(mpage, H, W, nw, g, t, D - 1 + k) || qr_sample(mpage, H, W, nw, g, -k, t) ||
+                        qr_sample(mpage, H, W, nw, g, D - 1 + k, t);
+        }
+    }
+    __syncthreads();
+    if (__ballot(dirty)) return false;
+    // format information: lane i < 15 reads bit i of both copies, lanes < 32 measure a word each
+    int b1 = 0, b2 = 0;
+    if (lane < 15) {
+        const int r1 = lane < 6 ? lane : (lane == 6 ? 7 : 8), c1 = lane < 8 ? 8 : (lane == 8 ? 7 : 14 - lane);
+        const int r2 = lane < 8 ? 8 : D - 15 + lane, c2 = lane < 8 ? D - 1 - lane : 8;
+        b1 = (int)((s.rows[r1 & 63] >> (c1 & 63)) & 1ull);
+        b2 = (int)((s.rows[r2 & 63] >> (c2 & 63)) & 1ull);
+    }
+    const int f1 = (int)(__ballot(b1) & 0x7fffull), f2 = (int)(__ballot(b2) & 0x7fffull);
+    const int fw = QR_FORMAT[lane & 31];
+    const int k1 = wave_min(lane < 32 ? (__popc(f1 ^ fw) << 5) | lane : BIG), k2 = wave_min(lane < 32 ? (__popc(f2 ^ fw) << 5) | lane : BIG);
+    int word, fdist;
+    if ((k1 >> 5) <= 3) { word = k1 & 31; fdist = k1 >> 5; }
+    else if ((k2 >> 5) <= 3) { word = k2 & 31; fdist = (k2 >> 5) + 16; }
+    else return false;
+    const int level = (word >> 3) ^ 1, mpat = word & 7;
+    // unmask the data modules
+    if (lane < D) {
+        u64 m = 0;
+        for (int x = 0; x < 57; ++x)
+            if (x < D && qr_mask_bit(mpat, lane, x)) m |= 1ull << x;
+        s.rows[lane] = row ^ (m & ~QR_FUNC[(version - 1) * 64 + lane]);
+    }
+    __syncthreads();
+    // codewords in placement order
+    const int total = QR_TOTAL[version - 1], poff = QR_PLACE_OFF[version - 1];
+#pragma unroll 1
+    for (int k = lane; k < 384; k += 64) {
+        int val = 0;
+        if (k < total) {
+            for (int bit = 0; bit < 8; ++bit) {
+                const int at = poff + 8 * k + bit;
+                const unsigned p = QR_PLACE[at < QR_PLACE_N ? at : QR_PLACE_N - 1];
+                val = (val << 1) | (int)((s.rows[(p >> 6) & 63] >> (p & 63)) & 1ull);
+            }
+        }
+        s.raw[k] = (unsigned char)val;
+    }
+    __syncthreads();
+    const unsigned char* bs = QR_BLOCKS + ((version - 1) * 4 + level) * 4;
+    const int nb = clampi(bs[0], 1, QR_MAX_NB), nshort = clampi(bs[1], 1, nb), dlen = bs[2], ec = clampi(bs[3], 2, QR_MAX_EC);
+    const int ndata = nb * dlen + (nb - nshort);
+    if (dlen + (nshort < nb ? 1 : 0) + ec > QR_MAX_BLOCK || ndata > QR_MAX_DATA || ndata + nb * ec > QR_MAX_TOTAL) return false;   // (the tables never say so)
+    int errors = 0, dpos = 0;
+    for (int blk = 0; blk < QR_MAX_NB; ++blk) {
+        if (blk >= nb) break;
+        const int nd = dlen + (blk >= nshort ? 1 : 0), len = nd + ec;
+#pragma unroll
+        for (int p0 = 0; p0 < 192; p0 += 64) {
+            const int p = p0 + lane;
+            if (p < len) {
+                const int src = p < dlen ? p * nb + blk : (p < nd ? dlen * nb + blk - nshort : ndata + (p - nd) * nb + blk);
+                s.blk[p] = s.raw[clampi(src, 0, 383)];
+            }
+        }
+        __syncthreads();
+        if (qr_syndromes(s, len, ec, lane)) {
+            if (lane == 0) qr_locator(s, ec);
+            __syncthreads();
+            const int L = s.L;
+            if (L > ec / 2 || L > 15) return false;
+            int roots = 0;
+            bool bad = false;
+#pragma unroll
+            for (int p0 = 0; p0 < 192; p0 += 64) {
+                const int p = p0 + lane, e = (len - 1 - p) % 255, xi = (255 - e) % 255;   // X = alpha^e, xi = log of X^-1
+                int val = 1, den = 0, num = 0;
+                if (p < len) {
+                    val = 0;
+                    for (int i = 0; i <= 15; ++i) {
+                        if (i > L) break;
+                        val ^= gmul_exp(s, s.C[i], (xi * i) % 255);
+                        if (i & 1) den ^= gmul_exp(s, s.C[i], (xi * (i - 1)) % 255);
+                        if (i < L) num ^= gmul_exp(s, s.O[i], (xi * i) % 255);
+                    }
+                }
+                const bool root = val == 0;
+                if (root) {
+                    if (den == 0) bad = true;
+                    else s.blk[p] ^= (unsigned char)gmul_exp(s, gmul_exp(s, num, 255 - s.log[den & 255]), e);
+                }
+                roots += __popcll(__ballot(root));
+            }
+            __syncthreads();
+            if (__ballot(bad) || roots != L) return false;
+            if (qr_syndromes(s, len, ec, lane)) return false;
+            errors += L;
+        }
+#pragma unroll
+        for (int p0 = 0; p0 < 192; p0 += 64) {
+            const int p = p0 + lane;
+            if (p < nd && dpos + p < QR_MAX_DATA) od[dpos + p] = s.blk[p];
+        }
+        dpos += nd;
+        __syncthreads();
+    }
+    if (lane == 0) {
+        // the hull: the four outer module corners, (u, v) = 2 (i, j) - 6 in {-7, 2 n + 7}
+        const int n = g.n;
+        i64 x0 = 0, x1 = 0, y0 = 0, y1 = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int u = (k & 1) ? 2 * n + 7 : -7, v = (k & 2) ? 2 * n + 7 : -7;
+            const i64 qx = floor_div((i64)g.ax * 2 * n + (i64)u * g.abx + (i64)v * g.acx, 4 * n);
+            const i64 qy = floor_div((i64)g.ay * 2 * n + (i64)u * g.aby + (i64)v * g.acy, 4 * n);
+            x0 = k == 0 || qx < x0 ? qx : x0; x1 = k == 0 || qx > x1 ? qx : x1;
+            y0 = k == 0 || qy < y0 ? qy : y0; y1 = k == 0 || qy > y1 ? qy : y1;
+        }
+        const auto cl = [](i64 v, int hi) { return (int)(v < 0 ? 0 : (v > hi ? hi : v)); };
+        o[0] = cl(y0, H - 1); o[1] = cl(x0, W - 1); o[2] = cl(y1 - 1, H - 1); o[3] = cl(x1 - 1, W - 1); o[4] = ida;
+        o[5] = version; o[6] = level; o[7] = mpat; o[8] = ndata; o[9] = errors;
+        o[10] = iabs(g.abx) >= iabs(g.aby) ? (g.abx > 0 ? 0 : 2) : (g.aby > 0 ? 1 : 3);
+        o[11] = fdist; o[12] = timing; o[13] = 1;
+    }
+    return true;
+}
+
+// 5: one wave per (page, finder): res [B][max_finders][RES_INTS], resdata [B][max_finders][QR_MAX_DATA]
+__global__ __launch_bounds__(64) void qr_decode_kernel(const u64* mask, const int4* finders, const int* nfind, int H, int W, int nw, int max_finders, int quiet,
+                                                       int timing_max, int* res, unsigned char* resdata) {
+    __shared__ QrLds s;
+    const int pg = blockIdx.y, a = blockIdx.x, lane = threadIdx.x;
+    const int nf = nfind[pg];
+    if (nf > max_finders || a >= nf || nf > QR_MAX_FINDERS) return;
+    const u64* mpage = mask + (size_t)pg * H * nw;
+    const int4 f = lane < nf ? finders[(size_t)pg * max_finders + lane] : make_int4(0, 0, 0, 0);
+    const int ax = __shfl(f.x, a), ay = __shfl(f.y, a), ma = __shfl(f.z, a), ida = __shfl(f.w, a);
+    for (int i = lane; i < 512; i += 64) s.exp[i] = QR_EXP[i];
+    for (int i = lane; i < 256; i += 64) s.log[i] = QR_LOG[i];
+    // A's partners: lane = B, loop over C; the valid pairs in the order of (|AB|^2 + |AC|^2, root of B, root of C), the first that decodes
+    const bool b_ok = lane < nf && lane != a && iabs(f.x - ax) <= QR_SPAN && iabs(f.y - ay) <= QR_SPAN && 4 * iabs(ma - f.z) <= (ma < f.z ? ma : f.z);
+    const int abx = b_ok ? f.x - ax : 0, aby = b_ok ? f.y - ay : 0;   // (zero where the products below could leave 64 bits)
+    const i64 lab = (i64)abx * abx + (i64)aby * aby;
+    int pl = -1, pb = -1, pc = -1;   // the key tried last
+#pragma unroll 1
+    for (int attempt = 0; attempt < QR_PAIR_TRIES; ++attempt) {
+        int best_l = BIG, best_idc = BIG, best_c = 0;
+#pragma unroll 1
+        for (int c = 0; c < QR_MAX_FINDERS; ++c) {
+            if (c >= nf) break;
+            const int cx = __shfl(f.x, c), cy = __shfl(f.y, c), mc = __shfl(f.z, c), idc = __shfl(f.w, c);
+            bool ok = b_ok && c != a && c != lane && iabs(cx - ax) <= QR_SPAN && iabs(cy - ay) <= QR_SPAN && 4 * iabs(ma - mc) <= (ma < mc ? ma : mc);
+            const int acx = ok ? cx - ax : 0, acy = ok ? cy - ay : 0;
+            const i64 lac = (i64)acx * acx + (i64)acy * acy, dot = (i64)abx * acx + (i64)aby * acy, cross = (i64)abx * acy - (i64)aby * acx;
+            ok = ok && 4 * labs64(lab - lac) <= (lab < lac ? lab : lac) && 64 * dot * dot <= lab * lac && cross > 0;
+            ok = ok && reach_mask(lab + lac, (i64)ma + f.z + mc) != 0u;
+            const int l = ok ? (int)(lab + lac) : BIG;   // (< 2^29)
+            ok = ok && (l > pl || (l == pl && (f.w > pb || (f.w == pb && idc > pc))));   // behind the key tried last
+            if (ok && (l < best_l || (l == best_l && idc < best_idc))) { best_l = l; best_idc = idc; best_c = c; }
+        }
+        const int min_l = wave_min(best_l);
+        if (min_l == BIG) return;
+        const int min_b = wave_min(best_l == min_l ? f.w : BIG);
+        const u64 win = __ballot(best_l == min_l && f.w == min_b);   // roots are distinct: one lane
+        if (!win) return;
+        const int b = __ffsll((long long)win) - 1, c = __shfl(best_c, b) & 63;
+        pl = min_l; pb = min_b; pc = __shfl(best_idc, b);
+        QrGrid g;
+        g.ax = ax; g.ay = ay; g.n = 14;
+        g.abx = __shfl(f.x, b) - ax; g.aby = __shfl(f.y, b) - ay; g.acx = __shfl(f.x, c) - ax; g.acy = __shfl(f.y, c) - ay;
+        const unsigned reach = reach_mask((i64)min_l, (i64)ma + __shfl(f.z, b) + __shfl(f.z, c));
+        if (qr_try(s, mpage, H, W, nw, g, reach, quiet, timing_max, ida, lane, res + ((size_t)pg * max_finders + a) * RES_INTS,
+                   resdata + ((size_t)pg * max_finders + a) * QR_MAX_DATA))
+            return;
+        __syncthreads();
+    }
+}
+
+// 6: tmp [B][max_codes][6] = y0, x0, y1, x1, root, slot
+__global__ __launch_bounds__(256) void qr_output_kernel(const int* res_all, const unsigned char* resdata_all, const int* nfind, int max_finders, int max_codes,
+                                                        int* tmp_all, int* counts, int* codes, int* data, int* finder_counts) {
+    __shared__ int s_key[QR_MAX_CODES * 5];
+    __shared__ int s_n;
+    const int pg = blockIdx.x;
+    const int nf = nfind[pg];
+    const int* res = res_all + (size_t)pg * max_finders * RES_INTS;
+    int* tmp = tmp_all + (size_t)pg * max_codes * 6;
+    if (threadIdx.x == 0) {
+        s_n = 0;
+        if (finder_counts) finder_counts[pg] = nf;
+    }
+    __syncthreads();
+    const int lim = nf > max_finders ? 0 : nf;   // a page with too many finders is not read
+    for (int a = threadIdx.x; a < lim; a += 256) {
+        const int* r = res + a * RES_INTS;
+        if (r[13] != 1) continue;
+        const int idx = atomicAdd(&s_n, 1);
+        if (idx >= max_codes) continue;
+        int* o = tmp + idx * 6;
+        o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3]; o[4] = r[4]; o[5] = a;
+    }
+    __syncthreads();
+    const int n = s_n;
+    if (threadIdx.x == 0) counts[pg] = n;
+    if (n > max_codes) return;   // overflow: the count is all that is reported
+    int* out = codes + (size_t)pg * max_codes * 12;
+    int* odat = data + (size_t)pg * max_codes * QR_MAX_DATA;
+    const unsigned char* rd = resdata_all + (size_t)pg * max_finders * QR_MAX_DATA;
+    rank_sort<5>(s_key, tmp, 6, n, [=](int i, int rank, const int (&k)[5]) {
+        const int slot = clampi(tmp[i * 6 + 5], 0, max_finders - 1);
+        const int* r = res + slot * RES_INTS;
+        int* o = out + (size_t)rank * 12;
+        o[0] = k[1]; o[1] = k[0]; o[2] = k[3]; o[3] = k[2];
+        for (int j = 0; j < 8; ++j) o[4 + j] = r[5 + j];
+        const int nd = r[8];
+        for (int j = 0; j < QR_MAX_DATA; ++j) odat[(size_t)rank * QR_MAX_DATA + j] = j < nd ? rd[(size_t)slot * QR_MAX_DATA + j] : 0;
+    });
+}
+
+}  // namespace
+
+// the workspace's regions: one layout sizes it (qrcodes_workspace_bytes) and carves it (qrcodes_launch)
+struct QrWorkspace {
+    unsigned long long* mask; int* runoff; unsigned short *rxs, *rxe; int* parent; int4* box; int* area;
+    int* nfind; int4* finders; int* res; unsigned char* resdata; int* tmp;
+};
+static QrWorkspace qrcodes_layout(Arena& a, int B, int H, int W, int max_finders, int max_codes) {
+    const size_t runcap = run_cap(H, W), nw = (W + 63) / 64;
+    QrWorkspace w;
+    w.mask = a.take<unsigned long long>((size_t)B * H * nw);
+    w.runoff = a.take<int>((size_t)B * (H + 1));   // run counts -> offsets
+    w.rxs = a.take<unsigned short>((size_t)B * runcap); w.rxe = a.take<unsigned short>((size_t)B * runcap);
+    w.parent = a.take<int>((size_t)B * runcap);
+    w.box = a.take<int4>((size_t)B * runcap);      // at a root: x0, x1, y0, y1 of its component
+    w.area = a.take<int>((size_t)B * runcap);      // at a root: its component's ink
+    w.nfind = a.take<int>((size_t)B);
+    w.finders = a.take<int4>((size_t)B * max_finders);
+    w.res = a.take<int>((size_t)B * max_finders * RES_INTS);
+    w.resdata = a.take<unsigned char>((size_t)B * max_finders * QR_MAX_DATA);
+    w.tmp = a.take<int>((size_t)B * max_codes * 6);
+    return w;
+}
+
+static bool qrcodes_args_ok(int B, int H, int W, int max_finders, int max_codes) {
+    if (B <= 0 || H <= 0 || W <= 0 || H > 65535 || W > 65535 || max_codes < 1 || max_codes > QR_MAX_CODES || max_finders < 1 || max_finders > QR_MAX_FINDERS)
+        return false;
+    return (size_t)B * H < (1ull << 31) && run_cap(H, W) < (1ull << 31);
+}
+
+bool qr_params_ok(int min_module, int max_module, int quiet, int centre_tol, int ring_tol, int timing_max, int max_finders, int max_codes) {
+    return min_module >= 1 && max_module >= min_module && max_module <= QR_MAX_MODULE && quiet >= 0 && quiet <= QR_MAX_QUIET && centre_tol >= 0 &&
+           centre_tol <= QR_MAX_TOL && ring_tol >= 0 && ring_tol <= QR_MAX_TOL && timing_max >= 0 && timing_max <= QR_MAX_TIMING && max_finders >= 1 &&
+           max_finders <= QR_MAX_FINDERS && max_codes >= 1 && max_codes <= QR_MAX_CODES;
+}
+
+size_t qrcodes_workspace_bytes(int B, int H, int W, int max_finders, int max_codes) {
+    if (!qrcodes_args_ok(B, H, W, max_finders, max_codes)) return 0;
+    Arena a;
+    qrcodes_layout(a, B, H, W, max_finders, max_codes);
+    return a.off;
+}
+
+hipError_t qrcodes_launch(const QrParams& p, void* workspace, size_t ws_bytes, hipStream_t st) {
+    const int B = p.B, H = p.H, W = p.W;
+    if (!qrcodes_args_ok(B, H, W, p.max_finders, p.max_codes) ||
+        !qr_params_ok(p.min_module, p.max_module, p.quiet, p.centre_tol, p.ring_tol, p.timing_max, p.max_finders, p.max_codes))
+        return hipErrorInvalidValue;
+    if (!p.rgb || !p.codes || !p.data || !p.counts) return hipErrorInvalidValue;
+    Arena a(workspace, ws_bytes);
+    const QrWorkspace w = qrcodes_layout(a, B, H, W, p.max_finders, p.max_codes);
+    if (a.overflow) return hipErrorOutOfMemory;
+    const int nw = (W + 63) / 64;
+    const size_t runcap = run_cap(H, W);
+    const unsigned long long* mask;
+    hipError_t e;
+    if ((e = hipMemsetAsync(w.nfind, 0, sizeof(int) * (size_t)B, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.res, 0, sizeof(int) * (size_t)B * p.max_finders * RES_INTS, st)) != hipSuccess) return e;
+    if ((e = ink_mask_resolve(p.rgb, p.mask_in, p.mask_out, w.mask, B, H, W, p.threshold, st, &mask)) != hipSuccess) return e;
+    const int rows = B * H;
+    const dim3 grows = row_wave_grid(rows);
+    run_count_launch(mask, w.runoff, B, H, nw, st);
+    row_scan_launch(w.runoff, nullptr, B, H, st);
+    run_fill_launch(mask, w.runoff, w.rxs, w.rxe, w.parent, w.box, B, H, nw, runcap, st);
+    run_merge_launch(w.runoff, w.rxs, w.rxe, w.parent, B, H, runcap, st);
+    hipLaunchKernelGGL(qr_area_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.area, H, runcap, rows);
+    hipLaunchKernelGGL(qr_accum_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.box, w.area, H, runcap, rows);
+    hipLaunchKernelGGL(qr_finders_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.box, w.area, H, runcap, p.min_module, p.max_module,
+                       p.centre_tol, p.ring_tol, p.max_finders, w.nfind, w.finders, rows);
+    hipLaunchKernelGGL(qr_decode_kernel, dim3(p.max_finders, B), dim3(64), 0, st, mask, w.finders, w.nfind, H, W, nw, p.max_finders, p.quiet, p.timing_max, w.res,
+                       w.resdata);
+    hipLaunchKernelGGL(qr_output_kernel, dim3(B), dim3(256), 0, st, w.res, w.resdata, w.nfind, p.max_finders, p.max_codes, w.tmp, p.counts, p.codes, p.data,
+                       p.finder_counts);
+    return hipGetLastError();
+}

@@ -477,6 +477,25 @@ ROUND_MARK_PARAMS = dict(out_max=0, ring_div=12, band_div=4, band_min=4)
 # quiet = 5 is half the standard's ten modules: forms crowd their codes.  max_codes = capacity of a page's list (<= 256).
 BARCODE_PARAMS = dict(threshold=MARK_PARAMS["threshold"], quiet=5, max_dist=24, min_rows=8, row_gap=2, max_codes=64)
 
+# QR codes (lumina_ocr_qrcodes + utils/qrcodes.py, definition restated in tests/qr_reference.py): ink as above, at the barcodes'
+# threshold so that one mask serves both.  min_module = 3 px is the issue's floor; max_module = 24 px lets a version 10 symbol span 1368 of the 2000 processed pixels.  centre_tol and ring_tol
+# are sixteenths of a module (the ring's w + h stands for 14 modules): 8 = half a module between the centres of core and ring, 12 =
+# three quarters of a module on the ring's side against 7/3 of the core's, which is one pixel at each edge of a 3 px module and a
+# little ink spread.  quiet = 2 modules, half the standard's four, as the 1-D codes halve theirs: forms crowd their codes; the rings
+# of modules round the symbol are sampled on the decode grid and must be clear.  timing_max = 3 mismatches in the two timing
+# patterns: a clean symbol has none, a wrong version about half of its 10..82 timing modules, and Reed-Solomon carries the rest of
+# the rejection.  Changed against the issue's outline, the restatement being the definition: a core is solid when 4 area >= 3 w h, not
+# 8 area >= 7 w h: half a degree of tilt puts a one-pixel stair on every edge, a 12 px core then has a 13 x 13 box and 146 of its 169
+# pixels (0.86), and a 9 px core 81 of 100; three quarters keeps both and still refuses rings, frames and text; grouping is the decode wave's first step,
+# not a kernel of its own (the finders of a page are one int4 a lane); a corner finder tries its valid pairs in the order of
+# |AB|^2 + |AC|^2 (ties by the partners' roots), eight at most, until one decodes: on a page of several symbols a neighbour's finder
+# can lie nearer than the corner's own partners, and the nearest pair alone lost one of 64 symbols of the probe's pages; a page has
+# at most one symbol per finder and the decode kernel's grid is max_finders waves a page; the version's reach is three modules either side of n = 10 + 4 v (neighbouring
+# versions lie four apart, so at most two are tried); the reported format distance has 16 added when the second copy was read.
+# max_finders <= 64 (one wave sorts them), max_codes <= 64.
+QR_PARAMS = dict(threshold=BARCODE_PARAMS["threshold"], min_module=3, max_module=24, quiet=2, centre_tol=8, ring_tol=12, timing_max=3,
+                 max_finders=64, max_codes=16)
+
 # Page orientation (lumina_ocr_page_quarter / _page_turn / _page_vote + utils/page_orient.py): ink as above; a page is sideways when the
 # energy of its column profile exceeds `ratio` times that of its row profile (text lines make the profile across them jagged), and an
 # upright-or-upside-down page is upside-down when it has at least min_lines lines and the classifier flips more than half of them.

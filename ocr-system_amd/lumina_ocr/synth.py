@@ -601,3 +601,193 @@ def synth_barcode_decoys(h: int = 420, w: int = 900, min_rows: int = 8) -> Tuple
     page[260:310, 420:458] = 0
     gt.append(dict(kind="no_quiet39", box=box))
     return page, gt
+
+
+# ---- QR codes (versions 1-10; the tables are utils/qrcodes.py's, everything else is the encoder's own) ----
+def qr_segment_bits(data, version: int) -> List[int]:
+    """One segment a call: str of digits -> numeric, str of the 45 alphanumeric characters -> alphanumeric, other str (as UTF-8) or
+    bytes -> byte; a list of those -> the segments in turn; a tuple ("bits", value, width) puts raw bits (mode indicators the host
+    does not read, ECI headers).  -> the bit list without terminator or padding."""
+    from .utils import qrcodes as qr
+    if isinstance(data, list):
+        return [b for part in data for b in qr_segment_bits(part, version)]
+    put = lambda v, k: [(v >> (k - 1 - i)) & 1 for i in range(k)]
+    if isinstance(data, tuple):
+        return put(int(data[1]), int(data[2]))
+    if isinstance(data, str) and data and all(c in "0123456789" for c in data):
+        bits = put(qr.MODE_NUMERIC, 4) + put(len(data), qr.count_bits(qr.MODE_NUMERIC, version))
+        for k in range(0, len(data), 3):
+            g = data[k:k + 3]
+            bits += put(int(g), (0, 4, 7, 10)[len(g)])
+        return bits
+    if isinstance(data, str) and data and all(c in qr.ALNUM for c in data):
+        bits = put(qr.MODE_ALNUM, 4) + put(len(data), qr.count_bits(qr.MODE_ALNUM, version))
+        for k in range(0, len(data) - 1, 2):
+            bits += put(45 * qr.ALNUM.index(data[k]) + qr.ALNUM.index(data[k + 1]), 11)
+        if len(data) % 2:
+            bits += put(qr.ALNUM.index(data[-1]), 6)
+        return bits
+    raw = data.encode("utf-8") if isinstance(data, str) else bytes(data)
+    bits = put(qr.MODE_BYTE, 4) + put(len(raw), qr.count_bits(qr.MODE_BYTE, version))
+    for v in raw:
+        bits += put(v, 8)
+    return bits
+
+
+def qr_data_codewords(data, version: int, level: int) -> List[int]:
+    """Segments -> the data codewords of (version, level index 0..3 = L, M, Q, H): terminator (up to four zero bits), zero bits to
+    the byte boundary, then 236 / 17 alternately."""
+    from .utils import qrcodes as qr
+    bits, cap = qr_segment_bits(data, version), 8 * qr.data_codewords(version, level)
+    if len(bits) > cap:
+        raise ValueError("%d bits do not fit version %d-%s (%d)" % (len(bits), version, qr.LEVELS[level], cap))
+    bits += [0] * min(4, cap - len(bits))
+    bits += [0] * (-len(bits) % 8)
+    cw = [int("".join(map(str, bits[i:i + 8])), 2) for i in range(0, len(bits), 8)]
+    pad = (236, 17)
+    return cw + [pad[i % 2] for i in range(cap // 8 - len(cw))]
+
+
+def qr_rs_remainder(data: List[int], ec: int) -> List[int]:
+    """The ec Reed-Solomon check codewords of a block over GF(256) / 0x11D, generator (x - a^0) ... (x - a^(ec-1))."""
+    from .utils import qrcodes as qr
+    gen = [1]                                   # descending powers, the leading 1 first
+    for i in range(ec):
+        gen = [a ^ qr.gf_mul(b, qr.GF_EXP[i]) for a, b in zip(gen + [0], [0] + gen)]
+    rem = [0] * ec
+    for d in data:
+        f = d ^ rem[0]
+        rem = rem[1:] + [0]
+        for k in range(ec):
+            rem[k] ^= qr.gf_mul(gen[k + 1], f)
+    return rem
+
+
+def qr_interleave(cw: List[int], version: int, level: int) -> List[int]:
+    """Data codewords -> all codewords of the symbol in placement order: the blocks' data column by column, then their check
+    codewords the same way."""
+    from .utils import qrcodes as qr
+    nb, short, dlen, ec = qr.block_structure(version, level)
+    blocks, at = [], 0
+    for b in range(nb):
+        n = dlen + (b >= short)
+        blocks.append(cw[at:at + n])
+        at += n
+    checks = [qr_rs_remainder(b, ec) for b in blocks]
+    out = [b[i] for i in range(dlen + 1) for b in blocks if i < len(b)]
+    return out + [c[i] for i in range(ec) for c in checks]
+
+
+def qr_matrix(codewords: List[int], version: int, level: int, mask: int) -> np.ndarray:
+    """All codewords of a symbol -> bool [D,D] (True = dark): function patterns, the codewords in placement order, the mask, the
+    format information and, from version 7, the version information."""
+    from .utils import qrcodes as qr
+    d = qr.dimension(version)
+    m = np.zeros((d, d), bool)
+    for (r, c), dark in qr.function_modules(version).items():
+        m[r, c] = dark
+    place = qr.placement_of(version)
+    for i, (r, c) in enumerate(place):
+        bit = (codewords[i >> 3] >> (7 - (i & 7))) & 1 if i < 8 * len(codewords) else 0
+        m[r, c] = bool(bit) ^ qr.mask_bit(mask, r, c)
+    word = qr.format_word(level, mask)
+    for pos in qr.format_positions(version):
+        for i, (r, c) in enumerate(pos):
+            m[r, c] = bool((word >> i) & 1)
+    if version >= 7:
+        word = qr.version_word(version)
+        for i, (a, b) in enumerate(qr.version_positions(version)):
+            m[a] = m[b] = bool((word >> i) & 1)
+    return m
+
+
+def qr_encode(data, version: int, level: int = 1, mask: int = 0) -> np.ndarray:
+    """data (see qr_segment_bits) -> the symbol's modules, bool [D,D] indexed [row, col], True = dark.  The mask is the caller's:
+    no penalty rule is applied."""
+    return qr_matrix(qr_interleave(qr_data_codewords(data, version, level), version, level), version, level, mask)
+
+
+def draw_qr(page: np.ndarray, x: int, y: int, modules: np.ndarray, module: int, rotation: int = 0, ink: int = 0) -> Tuple[int, int, int, int]:
+    """Draw a symbol into page (uint8 [H,W,3], in place) with its top-left pixel at (x, y), `module` pixels a module, turned clockwise by
+    rotation quarter turns; only dark modules are drawn.  -> the box (x0, y0, x1, y1), inclusive."""
+    m = np.rot90(np.asarray(modules, bool), -int(rotation) % 4)
+    side = m.shape[0] * module
+    if x < 0 or y < 0 or x + side > page.shape[1] or y + side > page.shape[0]:
+        raise ValueError("the symbol does not fit the page")
+    big = np.kron(m, np.ones((module, module), bool))
+    page[y:y + side, x:x + side][big] = ink
+    return x, y, x + side - 1, y + side - 1
+
+
+def qr_finder(page: np.ndarray, x: int, y: int, module: int, ink: int = 0) -> None:
+    """A lone finder pattern (7 x 7 modules) at (x, y)."""
+    f = np.array([[max(abs(r - 3), abs(c - 3)) != 2 for c in range(7)] for r in range(7)])
+    draw_qr(page, x, y, f, module, ink=ink)
+
+
+def synth_qr_page(seed: int, h: int = 700, w: int = 1000, n_codes: int = 3, text_lines: int = 6, module_px: int = 0) -> Tuple[np.ndarray, List[dict]]:
+    """White page with text lines in its upper part and n_codes QR symbols below them, each in a cell of its own: seeded versions,
+    levels, masks, rotations, module sizes (3-6 px unless given) and contents (digits, alphanumeric or UTF-8 text).
+    -> (uint8 [h,w,3], [dict(text, version, level, mask, rotation, module, box)])"""
+    from .utils import qrcodes as qr
+    rng = np.random.default_rng(seed)
+    top = h // 3 if text_lines else 0
+    page = np.full((h, w, 3), 255, np.uint8)
+    if text_lines:
+        page[:top] = synth_page(top, w, seed + 2000, n_lines=text_lines, noise=0.0)[0]
+    gt = []
+    cell_w = w // max(n_codes, 1)
+    for i in range(n_codes):
+        mp = module_px or int(rng.integers(3, 7))
+        room = min(cell_w, h - top) - 8 * mp - 24
+        vmax = min(qr.MAX_VERSION, (room // mp - 17) // 4)
+        if vmax < 1:
+            continue
+        version, level, mask, rot = int(rng.integers(1, vmax + 1)), int(rng.integers(0, 4)), int(rng.integers(0, 8)), int(rng.integers(0, 4))
+        cap = qr.data_codewords(version, level) - 3
+        kind = int(rng.integers(0, 3))
+        if kind == 0:
+            text = "".join("0123456789"[int(k)] for k in rng.integers(0, 10, max(1, min(2 * cap, 40))))
+        elif kind == 1:
+            text = "".join(qr.ALNUM[int(k)] for k in rng.integers(0, 45, max(1, min(cap, 30))))
+        else:
+            text = ("https://lumina.example/p?id=%d&k=éü" % int(rng.integers(0, 10 ** 6)))[:max(1, cap - 4)]
+        x = i * cell_w + 12 + 4 * mp
+        y = top + 12 + 4 * mp + int(rng.integers(0, 8))
+        box = draw_qr(page, x, y, qr_encode(text, version, level, mask), mp, rot)
+        gt.append(dict(text=text, version=version, level=level, mask=mask, rotation=rot, module=mp, box=box))
+    return page, gt
+
+
+def synth_qr_decoys(h: int = 330, w: int = 520) -> Tuple[np.ndarray, List[dict]]:
+    """White page of what looks like a QR symbol and is none: lone finder patterns, three finders at a symbol's corners with white
+    between them, a mirrored symbol, an inverted one (light on dark) and a halftone block.  -> (uint8 [h,w,3], [dict(kind, box)])"""
+    page = np.full((h, w, 3), 255, np.uint8)
+    gt = []
+    for k, (x, y, m) in enumerate(((10, 10, 3), (60, 14, 4), (20, 60, 5))):           # lone finders of three sizes
+        qr_finder(page, x, y, m)
+        gt.append(dict(kind="finder", box=(x, y, x + 7 * m - 1, y + 7 * m - 1)))
+    x, y, m, d = 130, 10, 4, 25                                                       # a version 2 symbol's three finders, nothing else
+    for fx, fy in ((0, 0), (d - 7, 0), (0, d - 7)):
+        qr_finder(page, x + fx * m, y + fy * m, m)
+    gt.append(dict(kind="three_finders", box=(x, y, x + d * m - 1, y + d * m - 1)))
+    sym = qr_encode("MIRRORED 123", 2, 1, 3)
+    gt.append(dict(kind="mirrored", box=draw_qr(page, 260, 10, sym[:, ::-1], 4)))
+    sym = qr_encode("INVERTED", 1, 0, 2)
+    page[140:140 + 29 * 4, 20:20 + 29 * 4] = 0                                        # dark field, the symbol light on it
+    draw_qr(page, 20 + 4 * 4, 140 + 4 * 4, sym, 4, ink=255)
+    gt.append(dict(kind="inverted", box=(20, 140, 20 + 29 * 4 - 1, 140 + 29 * 4 - 1)))
+    yy, xx = np.mgrid[0:120, 0:160]
+    page[150:270, 200:360][((xx % 6 < 3) & (yy % 6 < 3)) | ((xx % 6 >= 3) & (yy % 6 >= 3) & ((xx // 6 + yy // 6) % 3 == 0))] = 0   # halftone block
+    gt.append(dict(kind="halftone", box=(200, 150, 359, 269)))
+    return page, gt
+
+
+def synth_qr_crowded_page() -> Tuple[np.ndarray, dict]:
+    """A 6-M symbol turned by 90 degrees (its corner finder is the top right one) and, to its right at the distance of its own finder
+    spacing, a second symbol of the same module size: the corner's nearest valid partner pair takes the neighbour's finder for its +x
+    partner and does not decode.  -> (uint8 [150,331,3], {box: text})"""
+    page = np.full((150, 331, 3), 255, np.uint8)
+    a = draw_qr(page, 10, 12, qr_encode("CROWDED CORNER 6-M", 6, 1, 4), 3, 1)
+    b = draw_qr(page, 211, 12, qr_encode("NEIGHBOUR", 2, 1, 0), 3)
+    return page, {a: "CROWDED CORNER 6-M", b: "NEIGHBOUR"}
