@@ -397,8 +397,8 @@ int lumina_ocr_png_decode(lumina_ocr_t* h, const uint8_t* const* files, const si
  * lumina_ocr_ccitt_decode: /CCITTFaxDecode with K < 0 (ITU-T T.6, Group 4).  params int32 [n][4] = {K, EncodedByteAlign, BlackIs1,
  * invert}; -2 for K >= 0, EncodedByteAlign or columns > 8192 (CC_MAX_COLS, ccitt.h).  Decoding stops after `rows` lines or at
  * EOFB, whichever comes first; bytes after that are ignored.  A coded-white run is sample 1 unless BlackIs1; sample 1 is white (255)
- * unless invert.  -1: an unused code, a line whose a0 does not advance or passes `columns`, more than columns + 1 changing elements on a
- * line, bits past the stream's end, or fewer than `rows` lines. */
+ * unless invert.  -1: an unused code, a line whose a0 does not advance or passes `columns`, a pass code whose b2 is the line's end,
+ * more than columns + 1 changing elements on a line, bits past the stream's end, or fewer than `rows` lines. */
 int lumina_ocr_flate_image_decode(lumina_ocr_t* h, const uint8_t* const* streams, const size_t* sizes, int n, int height, int width,
                                   const int32_t* params, const uint8_t* const* palettes, uint8_t* out_dev, int* status, void* stream);
 int lumina_ocr_ccitt_decode(lumina_ocr_t* h, const uint8_t* const* streams, const size_t* sizes, int n, int rows, int columns,

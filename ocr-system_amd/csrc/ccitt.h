@@ -12,7 +12,7 @@ struct lumina_ocr;
 // streams: HOST pointers to n T.6 streams, all rows x columns.  params: HOST int [n][4] = {K, EncodedByteAlign, BlackIs1, invert}
 // (invert: /Decode [1 0]).  out: device RGB u8 [n][rows][columns][3], PDF's convention: a coded-white run is sample 1 unless BlackIs1,
 // sample 1 is white (255) unless invert.  status: HOST int [n], 0 ok / -1 corrupt (an unused code, a0 that does not advance, a run past
-// the line's end, more than columns + 1 changing elements on a line, bits past the stream's end, fewer than `rows` lines) /
+// the line's end, a pass code whose b2 is the line's end, more than columns + 1 changing elements on a line, bits past the stream's end, fewer than `rows` lines) /
 // -2 unsupported (K >= 0, EncodedByteAlign, columns > CC_MAX_COLS).  Decoding stops after `rows` lines or at EOFB; bytes after that are
 // ignored.  The pixels of a page with a non-zero status are undefined.  Synchronises the stream.
 int ccitt_run(lumina_ocr* eng, const uint8_t* const* streams, const size_t* sizes, int n, int rows, int columns, const int* params,

@@ -9,8 +9,10 @@
 // colour at the word's start, then the elements inside it), then lanes over the RGB bytes of the output row with coalesced stores.
 //
 // Hostile streams: every table index is a bit field of the table's width; an unused pattern has entry 0 and ends the page; a0 must
-// advance on every code and never passes `columns`; a line holds at most columns + 1 changing elements (the arrays have room for
-// them and three sentinels); the bit position is checked against the stream length after every code.  Each of these is status -1.
+// advance on every code and never passes `columns`; a pass code whose b2 is the line's end is refused (T.6 allows pass mode only when
+// b2 lies left of a1, and a1 <= columns; libtiff reads such a code differently, and the host path is libtiff); a line holds at most
+// columns + 1 changing elements (the arrays have room for them and three sentinels); the bit position is checked against the stream
+// length after every code.  Each of these is status -1.
 #include "ccitt.h"
 
 #include <cstring>
@@ -117,8 +119,11 @@ __global__ __launch_bounds__(64) void cc_decode(const CcPage* __restrict__ P, co
             b.pos += e >> 12;
             if (b.pos > limit) { bad = true; break; }
             const int mode = (int)(e & 4095);
-            if (mode == CC_M_PASS) { a0 = b2; continue; }   // (b2 >= b1 > a0)
-            if (n + (mode == CC_M_HORIZ ? 2 : 1) > W + 1) { bad = true; break; }
+            if (mode == CC_M_PASS) {
+                if (b2 >= W) { bad = true; break; }   // T.6, pass mode: "identified when the position of b2 lies to the left of a1", and a1 <= columns
+                a0 = b2;   // (b2 > b1 > a0)
+                continue;
+            }
             if (mode == CC_M_HORIZ) {
                 const int start = a0 < 0 ? 0 : a0;
                 const int r1 = cc_run(L, b, white, W - start, limit, lane);
@@ -127,7 +132,8 @@ __global__ __launch_bounds__(64) void cc_decode(const CcPage* __restrict__ P, co
                 if (r2 < 0) { bad = true; break; }
                 const int t1 = start + r1, t2 = t1 + r2;
                 if (t2 <= a0) { bad = true; break; }
-                // (a change at the line's end is the sentinel's)
+                // (a change at the line's end is the sentinel's and takes no room: a line of `columns` elements may end with such a pair)
+                if (n + (t1 < W) + (t2 < W) > W + 1) { bad = true; break; }
                 if (lane == 0) {
                     if (t1 < W) cur[n] = (unsigned short)t1;
                     if (t2 < W) cur[n + (t1 < W)] = (unsigned short)t2;
@@ -137,7 +143,7 @@ __global__ __launch_bounds__(64) void cc_decode(const CcPage* __restrict__ P, co
             } else {
                 const int d = mode <= CC_M_VR3 ? mode - CC_M_V0 : CC_M_VR3 - mode;
                 const int a1 = b1 + d;
-                if (a1 <= a0 || a1 > W) { bad = true; break; }
+                if (a1 <= a0 || a1 > W || (a1 < W && n + 1 > W + 1)) { bad = true; break; }
                 if (a1 < W) {
                     if (lane == 0) cur[n] = (unsigned short)a1;
                     ++n;

@@ -6,8 +6,8 @@ and 3, T.6 table 1); the tests grade it against source bitmaps encoded by libtif
 
 bits: uint8 [rows][columns] of 0 / 1 in PDF's convention (a coded-white run gives 1 when BlackIs1 is false, 0 when it is true; in DeviceGray
 with the default /Decode 0 is black and 1 is white).  status 0 ok; -1 corrupt: an unused code, a0 that does not advance, a run past the
-line's end, more transitions than columns + 1, bits read past the stream's end, or fewer lines than `rows` before EOFB / the end of the
-stream.  Decoding stops after `rows` lines or at EOFB, whichever comes first; whatever follows is ignored.
+line's end, a pass code whose b2 is the line's end, more transitions than columns + 1, bits read past the stream's end, or fewer lines
+than `rows` before EOFB / the end of the stream.  Decoding stops after `rows` lines or at EOFB, whichever comes first; whatever follows is ignored.
 """
 import numpy as np
 
@@ -126,10 +126,10 @@ def decode_ex(stream, columns: int, rows: int, black_is_1: bool = False):
                 return -1, out, b.pos
             mode = e & 4095
             if mode == M_PASS:
+                if b2 >= W:   # T.6, pass mode: "identified when the position of b2 lies to the left of a1", and a1 <= columns
+                    return -1, out, b.pos
                 a0 = b2
                 continue
-            if len(cur) + (2 if mode == M_HORIZ else 1) > W + 1:
-                return -1, out, b.pos
             if mode == M_HORIZ:
                 start = max(a0, 0)
                 r1 = _run(b, white, W - start)
@@ -140,13 +140,18 @@ def decode_ex(stream, columns: int, rows: int, black_is_1: bool = False):
                     return -1, out, b.pos
                 if start + r1 + r2 <= a0:
                     return -1, out, b.pos
-                cur += [t for t in (start + r1, start + r1 + r2) if t < W]   # (a change at the line's end is the sentinel's)
+                new = [t for t in (start + r1, start + r1 + r2) if t < W]   # (a change at the line's end is the sentinel's)
+                if len(cur) + len(new) > W + 1:
+                    return -1, out, b.pos
+                cur += new
                 a0 = start + r1 + r2
                 continue
             a1 = b1 + V_DELTA[mode]
             if a1 <= a0 or a1 > W:
                 return -1, out, b.pos
             if a1 < W:
+                if len(cur) + 1 > W + 1:
+                    return -1, out, b.pos
                 cur.append(a1)
             a0 = a1
             white = not white

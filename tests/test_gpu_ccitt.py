@@ -93,3 +93,60 @@ def test_truncated_and_random_streams_are_minus_one_neighbours_intact(engine):
     assert status == [0, -1, -1, 0]
     want = cr.to_rgb(cr.decode(stream, w, h)[1])
     assert np.array_equal(got[0], want) and np.array_equal(got[3], want)
+
+
+# ---- damaged streams: device == restatement on every page (the restatement's accepted streams are held to libtiff on the CPU) ----
+@pytest.mark.parametrize("name", ["begins_black_65x12", "rand_65x40", pytest.param("rand_7x9", marks=needs_libtiff)])
+def test_damage_sweep_equals_restatement_neighbours_intact(engine, name):
+    """one call per file: every stream of cc.damage_sweep (single-bit flips and cuts at every byte length), the intact stream at every
+    64th position.  Status equal to the restatement's on every page, pixels on every status-0 page, every intact page untouched."""
+    stream, w, h, damaged = cc.damage_sweep(name)
+    ref = cc.sweep_restatement(name)
+    pages, owner = [], []   # owner: the damaged stream's index, -1 for the intact one
+    for k, (_, d) in enumerate(damaged):
+        if len(pages) % 64 == 0:
+            pages.append(stream)
+            owner.append(-1)
+        pages.append(d)
+        owner.append(k)
+    pages.append(stream)
+    owner.append(-1)
+    assert all(o == -1 for o in owner[::64]) and sorted(o for o in owner if o >= 0) == list(range(len(damaged)))
+    got, status = _decode(engine, pages, h, w, [(-1, 0, 0, 0)] * len(pages))
+    want_status = [0 if o < 0 else ref[o][0] for o in owner]
+    wrong = [(damaged[o][0] if o >= 0 else "intact", s, t) for o, s, t in zip(owner, status, want_status) if s != t]
+    assert wrong == [], wrong[:10]
+    intact = cr.to_rgb(cr.decode(stream, w, h)[1])
+    accepted = 0
+    for i, o in enumerate(owner):
+        if o < 0:
+            assert np.array_equal(got[i], intact), ("intact page", i)
+        elif ref[o][0] == 0:
+            accepted += 1
+            assert np.array_equal(got[i], cr.to_rgb(ref[o][1])), damaged[o][0]
+    assert accepted >= 20, accepted
+    if name == "rand_65x40":   # a pass code whose b2 is the line's end (T.6: pass mode only when b2 lies left of a1): libtiff reads these two differently
+        labels = [l for l, _ in damaged]
+        assert [status[owner.index(labels.index("bit %d" % b))] for b in (5230, 5309)] == [-1, -1]
+
+
+# ---- legal streams that libtiff never writes (cc.g4_encode_policy, pinned against libtiff's decoder on the CPU) ----
+@pytest.mark.parametrize("p_horiz", [0.0, 0.3, 1.0])
+def test_policy_encoder_streams_equal_source(engine, p_horiz):
+    """vertical pairs recoded in horizontal mode with probability p_horiz, runs from 2560 up as repeated make-ups, with and without
+    EOFB; widths around the 32-pixel words of the line stage; a line of 8192 changing elements in horizontal mode alone; a stream that
+    ends on the last bit of its last byte.  Status 0 and the pixels of the source bitmap, both BlackIs1 values."""
+    cases = dict(cc.policy_bitmaps())
+    cases["exact_fit"], exact = cc.exact_fit_stream(p_horiz)
+    for name, bm in cases.items():
+        h, w = bm.shape
+        with_eofb, without = (cc.g4_encode_policy(bm, np.random.default_rng(5), p_horiz, e) for e in (True, False))
+        if name == "exact_fit":
+            without = exact
+            assert cr.decode_ex(exact, w, h)[2] == 8 * len(exact)
+        streams = [with_eofb, without, without]
+        params = [(-1, 0, 0, 0), (-1, 0, 0, 0), (-1, 0, 1, 0)]
+        got, status = _decode(engine, streams, h, w, params)
+        assert status == [0] * 3, (name, status)
+        for k, (_, _, b1, _) in enumerate(params):
+            assert np.array_equal(got[k], cr.to_rgb(cc.expected_bits(bm, bool(b1)))), (name, k)

@@ -1,6 +1,6 @@
 """GPU: PDF /FlateDecode image streams (csrc/pngdec.hip, through lumina_ocr_flate_image_decode) against the source arrays: predictors 1,
-2 and 10..15 with all five row filters mixed, grey at 1 and 8 bits, RGB, indexed colour at 4 and 8 bits, /Decode [1 0], stored / fixed /
-dynamic deflate blocks, and corrupt streams.  One mixed batch per size."""
+2 and 10..15 with all five row filters mixed, grey at 1, 2, 4 and 8 bits, RGB, indexed colour at 1, 2, 4 and 8 bits, /Decode [1 0], stored /
+fixed / dynamic deflate blocks, and corrupt streams.  One mixed batch per size; width 3 makes a packed row a part of one byte."""
 import zlib
 
 import numpy as np
@@ -11,7 +11,7 @@ import pdf_cases as pc
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [(61, 37), (128, 64)]   # (width, height)
+SIZES = [(61, 37), (128, 64), (3, 37)]   # (width, height)
 
 
 def _rgb_of_grey(g):
@@ -29,6 +29,8 @@ def _cases(w, h):
     bw = rng.integers(0, 2, (h, w), dtype=np.uint8)
     i4, i8 = rng.integers(0, 16, (h, w)), rng.integers(0, 200, (h, w))
     lut4, lut8 = rng.integers(0, 256, (16, 3), dtype=np.uint8), rng.integers(0, 256, (200, 3), dtype=np.uint8)
+    g2, g4, i1, i2 = rng.integers(0, 4, (h, w)), rng.integers(0, 16, (h, w)), rng.integers(0, 2, (h, w)), rng.integers(0, 4, (h, w))
+    lut1, lut2 = rng.integers(0, 256, (2, 3), dtype=np.uint8), rng.integers(0, 256, (4, 3), dtype=np.uint8)
 
     def pal(lut):
         return np.concatenate([lut, np.repeat(lut[-1:], 256 - len(lut), axis=0)]).tobytes()
@@ -51,6 +53,15 @@ def _cases(w, h):
     add("grey1_p1", bits1.tobytes(), (1, 1, 1, 0, 0), None, _rgb_of_grey(bw * 255))
     add("grey1_invert", bits1.tobytes(), (1, 1, 1, 0, 1), None, _rgb_of_grey(255 - bw * 255))
     add("grey1_p12", pc.png_filter_rows(bits1, 1, mixed), (12, 1, 1, 0, 0), None, _rgb_of_grey(bw * 255))
+    # grey at 2 and 4 bits maps as v * 85 and v * 17 (v * 255 / (2^bits - 1)); indexed colour below 4 bits
+    for bits, v, scale in ((2, g2, 85), (4, g4, 17)):
+        packed = pc.pack_bits(v, bits)
+        add("grey%d_p1" % bits, packed.tobytes(), (1, 1, bits, 0, 0), None, _rgb_of_grey(v * scale), "stored")
+        add("grey%d_invert" % bits, packed.tobytes(), (1, 1, bits, 0, 1), None, _rgb_of_grey(255 - v * scale))
+        add("grey%d_p13" % bits, pc.png_filter_rows(packed, 1, mixed), (13, 1, bits, 0, 0), None, _rgb_of_grey(v * scale))
+    add("indexed1", pc.pack_bits(i1, 1).tobytes(), (1, 1, 1, 1, 0), pal(lut1), lut1[i1])
+    add("indexed2", pc.pack_bits(i2, 2).tobytes(), (1, 1, 2, 1, 0), pal(lut2), lut2[i2])
+    add("indexed2_p11", pc.png_filter_rows(pc.pack_bits(i2, 2), 1, mixed), (11, 1, 2, 1, 0), pal(lut2), lut2[i2], "fixed")
     add("indexed4", bits4.tobytes(), (1, 1, 4, 1, 0), pal(lut4), lut4[i4])
     add("indexed4_p15", pc.png_filter_rows(bits4, 1, mixed), (15, 1, 4, 1, 0), pal(lut4), lut4[i4])
     add("indexed8", i8.astype(np.uint8).tobytes(), (1, 1, 8, 1, 0), pal(lut8), lut8[i8])
@@ -92,3 +103,19 @@ def test_single_stream_without_palettes_argument(engine):
     assert status == [0] and np.array_equal(out[0].cpu().numpy(), _rgb_of_grey(g))
     # an indexed stream without its palette is outside the subset, not a fault
     assert engine.flate_image_decode([zlib.compress(g.tobytes())], h, w, [(1, 1, 8, 1, 0)])[1] == [-2]
+
+
+def test_predictor_2_rows_beyond_the_grid(engine):
+    """pd_tiff_predict runs min(height, 1024) work-groups a stream and takes the rows beyond them by a grid stride: 65 x 1030 grey and
+    RGB (width 65: one full chunk of 64 pixels and a carry into a chunk of one), stored blocks, every row different"""
+    w, h = 65, 1030
+    rng = np.random.default_rng(1030)
+    g, rgb = rng.integers(0, 256, (h, w), dtype=np.uint8), rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    streams = [pc.deflate(pc.tiff_predict_rows(g, 1), "stored"), pc.deflate(pc.tiff_predict_rows(rgb.reshape(h, -1), 3), "stored")]
+    out, status = engine.flate_image_decode(streams, h, w, [(2, 1, 8, 0, 0), (2, 3, 8, 0, 0)])
+    torch.cuda.synchronize()
+    got = out.cpu().numpy()
+    assert status == [0, 0]
+    for k, want in enumerate((_rgb_of_grey(g), rgb)):
+        rows = np.flatnonzero((got[k] != want).any(axis=(1, 2)))
+        assert rows.size == 0, (k, rows[:8])

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 from PIL import Image, features
 
+import ccitt_cases as cc
 import tiff_cases as tc
 from lumina_ocr import synth
 
@@ -141,6 +142,38 @@ def test_in_place_strip_decode_pixels_equal_pillow(service, height):
     out, status = s._decode_tiff_strips_in_place(s._engine, bad, w, height, 16, False)
     assert status == [0, -1, 0]
     assert np.array_equal(out[0].cpu().numpy(), tc.pillow_rgb(data, 3)) and np.array_equal(out[2].cpu().numpy(), tc.pillow_rgb(data, 5))
+
+
+def test_pass_code_at_the_line_end_goes_to_pillow(service):
+    """rand_65x40 with bit 5309 flipped: its last line ends with a pass code whose b2 is the line's end.  T.6 does not allow the
+    code there, libtiff reads the line's last two pixels as white, and a decoder that takes the code paints them black.  The device
+    refuses the strip (-1), so the page is Pillow's with the option on as with it off; the intact stream is still the device's."""
+    s = service
+    stream, w, h, _ = cc.fixtures()["rand_65x40"]
+    file = lambda strip: tc.tiff_file([dict(strips=[strip], tags=tc.base_tags(w, h, tc.G4, 0, 1, 1, h))])
+    def on_and_off(data):
+        s.device_tiff = False
+        off = s.process_image_sync(data)
+        s.device_tiff = True
+        seen = []
+        inner = s._decode_tiff_pages
+
+        def spy(entries, reasons):
+            res = inner(entries, reasons)
+            seen.append((sorted(res), dict(reasons)))
+            return res
+        s._decode_tiff_pages = spy
+        try:
+            on = s.process_image_sync(data)
+        finally:
+            del s._decode_tiff_pages
+        assert off.success and (off.image_width, off.image_height) == (w, h), off.error
+        return on, off, seen
+
+    on, off, seen = on_and_off(file(stream))
+    assert seen == [([0], {})] and _same(on, off)
+    on, off, seen = on_and_off(file(cc.flip_bit(stream, 5309)))
+    assert seen == [([], {0: "group4 strips corrupt (status -1)"})] and _same(on, off)
 
 
 def _three(pages, second):

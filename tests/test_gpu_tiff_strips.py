@@ -120,3 +120,41 @@ def test_damage_sweep(engine, which):
     for k, f in enumerate(files):
         if status[k] == 0:
             assert np.array_equal(got[k], tc.pillow_rgb(f)), (name, k)
+
+
+def test_rows_of_part_of_a_byte(engine):
+    """width 3: a packed row is 3, 6 or 12 bits.  Grey at 1, 2 and 4 bits with and without MinIsWhite and indexed colour at 1, 2 and 4
+    bits, uncompressed, against the source arrays (v * 255, v * 85, v * 17; the palette's high bytes).  The same sample formats at
+    width 331, against Pillow, are test_case_equals_pillow_and_restatement's lzw_1bit_*, lzw_grey2_331, lzw_grey4_331,
+    lzw_miniswhite_1bit / _2bit / _4bit, raw_pal1, raw_pal2 and lzw_pal4_331: they are not repeated here."""
+    w, h = 3, 37
+    rng = np.random.default_rng(337)
+    pal = np.array([[v // 256 for v in rgb] for rgb in tc.PALETTE16], np.uint8)
+    cases, want = [], []
+    for bits, scale in ((1, 255), (2, 85), (4, 17)):
+        v = rng.integers(0, 1 << bits, (h, w))
+        for photo in (1, 0, 3):
+            cases.append(tc.make_case("w3_%d_%d" % (bits, photo), tc.pack_bits(v, bits), w, tc.NONE, photo=photo, bits=bits, rps=16))
+            grey = (v * scale if photo == 1 else 255 - v * scale).astype(np.uint8)
+            want.append(pal[v] if photo == 3 else np.repeat(grey[:, :, None], 3, axis=2))
+    got, status = _decode(engine, [c["strips"] for c in cases], h, w, 16, [c["params"] for c in cases], [c["palette"] for c in cases])
+    assert status == [0] * len(cases)
+    for k, c in enumerate(cases):
+        assert np.array_equal(got[k], want[k]), c["name"]
+        assert np.array_equal(want[k], tc.pillow_rgb(c["file"])), c["name"]   # (the source mapping is Pillow's)
+
+
+def test_predictor_2_rows_beyond_the_grid(engine):
+    """pd_tiff_predict (the row stage shared with the Flate images) runs min(height, 1024) work-groups a page and takes the rows beyond
+    them by a grid stride; no other predictor-2 case has more than 300 rows.  65 x 1030 grey and RGB, uncompressed in one strip, against
+    the source arrays (Pillow is no reference here: libtiff ignores Predictor outside LZW and Deflate)."""
+    w, h = 65, 1030
+    rng = np.random.default_rng(1031)
+    g, rgb = rng.integers(0, 256, (h, w), dtype=np.uint8), rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    cases = [tc.make_case("p2_grey", g, w, tc.NONE, predictor=2), tc.make_case("p2_rgb", rgb.reshape(h, -1), w, tc.NONE, photo=2, spp=3, predictor=2)]
+    assert all(len(c["strips"]) == 1 and c["rps"] == h for c in cases)
+    for c, want in zip(cases, (np.repeat(g[:, :, None], 3, axis=2), rgb)):     # (one component and three: a call has one shape of page, not one of sample)
+        got, status = _decode(engine, [c["strips"]], h, w, h, [c["params"]])
+        assert status == [0]
+        rows = np.flatnonzero((got[0] != want).any(axis=(1, 2)))
+        assert rows.size == 0, (c["name"], rows[:8])
