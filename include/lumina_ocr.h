@@ -398,11 +398,25 @@ int lumina_ocr_png_decode(lumina_ocr_t* h, const uint8_t* const* files, const si
  * invert}; -2 for K >= 0, EncodedByteAlign or columns > 8192 (CC_MAX_COLS, ccitt.h).  Decoding stops after `rows` lines or at
  * EOFB, whichever comes first; bytes after that are ignored.  A coded-white run is sample 1 unless BlackIs1; sample 1 is white (255)
  * unless invert.  -1: an unused code, a line whose a0 does not advance or passes `columns`, a pass code whose b2 is the line's end,
- * more than columns + 1 changing elements on a line, bits past the stream's end, or fewer than `rows` lines. */
+ * more than columns + 1 changing elements on a line, bits past the stream's end, or fewer than `rows` lines.
+ * lumina_ocr_fax_decode: the same arguments with params int32 [n][5] = {K, EncodedByteAlign, BlackIs1, invert, path}: every
+ * /CCITTFaxDecode coding, and the strips of TIFF Compression 2 (CCITT RLE), 3 (Group 3, TIFF-F) and 4.  K < 0 is decoded exactly as
+ * by lumina_ocr_ccitt_decode.  K = 0: ITU-T T.4 one-dimensional lines; K > 0: the bit after each EOL says whether the line is one- or
+ * two-dimensional.  EOLs are found, not announced: at each line's start zero bits are skipped (fill of any length), and 11 or more of
+ * them followed by a 1 are an EOL; a stream has one in front of every line or of none (its first line decides).  EncodedByteAlign: in
+ * a stream without EOLs every line begins on a byte boundary (Compression 2).  Decoding stops after `rows` lines; an RTC or anything
+ * else behind them is ignored.  path: 0 automatic, 1 the serial walk; 2 is reserved for a line-parallel decode and answers -2.
+ * -1 (the host's libtiff is lenient, this decoder is not): an unused code, a line whose runs do not add up to `columns` exactly, a run
+ * of length 0 other than a line's first, the two-dimensional violations listed above, an EOL in front of some lines only, two EOLs
+ * in a row before `rows` lines, bits other than 0 between a line's end and the next EOL, bits past the stream's end.  -2: K > 0 in a
+ * stream without EOLs (PDF allows it; libtiff cannot express it, so nothing can serve as its oracle), EncodedByteAlign in a stream
+ * with EOLs (the same), a path other than 0 / 1, columns > 8192.  T.4's uncompressed mode is not decoded. */
 int lumina_ocr_flate_image_decode(lumina_ocr_t* h, const uint8_t* const* streams, const size_t* sizes, int n, int height, int width,
                                   const int32_t* params, const uint8_t* const* palettes, uint8_t* out_dev, int* status, void* stream);
 int lumina_ocr_ccitt_decode(lumina_ocr_t* h, const uint8_t* const* streams, const size_t* sizes, int n, int rows, int columns,
                             const int32_t* params, uint8_t* out_dev, int* status, void* stream);
+int lumina_ocr_fax_decode(lumina_ocr_t* h, const uint8_t* const* streams, const size_t* sizes, int n, int rows, int columns,
+                          const int32_t* params, uint8_t* out_dev, int* status, void* stream);
 
 /* Strip-coded page images — the strips of a scanned TIFF page (utils/tiff_pages.py finds them) and PDF's /LZWDecode and
  * /RunLengthDecode image streams (one strip a page).  The batch contract is lumina_ocr_flate_image_decode's: HOST pointers, n pages of

@@ -516,6 +516,15 @@ int lumina_ocr_ccitt_decode(lumina_ocr_t* h, const uint8_t* const* streams, cons
     API_CATCH(h)
 }
 
+int lumina_ocr_fax_decode(lumina_ocr_t* h, const uint8_t* const* streams, const size_t* sizes, int n, int rows, int columns,
+                          const int32_t* params, uint8_t* out_dev, int* status, void* stream) {
+    if (!h || !streams || !sizes || !params || !out_dev || !status || n <= 0 || rows <= 0 || columns <= 0) return locr_fail(h, "fax_decode", "bad arguments");
+    BIND(h);
+    API_TRY
+    return fax_run(h, streams, sizes, n, rows, columns, params, out_dev, status, (hipStream_t)stream);
+    API_CATCH(h)
+}
+
 int lumina_ocr_jpeg_coefficients(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int quality, int16_t* coefs_dev,
                                  void* stream) {
     if (!h || !pages_dev || !coefs_dev || n <= 0 || height <= 0 || width <= 0) return locr_fail(h, "jpeg_coefficients", "bad arguments");

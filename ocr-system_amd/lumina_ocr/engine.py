@@ -81,6 +81,7 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_png_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_flate_image_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
         "lumina_ocr_ccitt_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "lumina_ocr_fax_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
         "lumina_ocr_strip_image_decode": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
         "lumina_ocr_load_svtr_weights": (i32, [vp, vp, sz]),
         "lumina_ocr_svtr_forward": (i32, [vp, vp, vp, i32, vp, vp, vp]),
@@ -126,7 +127,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_load_cls_weights", "lumina_ocr_cls_forward", "lumina_ocr_rec_forward",
     "lumina_ocr_ctc_decode", "lumina_ocr_ctc_decode_words", "lumina_ocr_conv2d", "lumina_ocr_read_tap", "lumina_ocr_conv_timing", "lumina_ocr_conv_timing_detail",
     "lumina_ocr_resize_lanczos", "lumina_ocr_enhance", "lumina_ocr_jpeg_encode", "lumina_ocr_jpeg_coefficients", "lumina_ocr_jpeg_probe", "lumina_ocr_jpeg_decode", "lumina_ocr_jpeg_decode_async", "lumina_ocr_jpeg_last_passes",
-    "lumina_ocr_png_probe", "lumina_ocr_png_decode", "lumina_ocr_flate_image_decode", "lumina_ocr_ccitt_decode", "lumina_ocr_strip_image_decode",
+    "lumina_ocr_png_probe", "lumina_ocr_png_decode", "lumina_ocr_flate_image_decode", "lumina_ocr_ccitt_decode", "lumina_ocr_fax_decode", "lumina_ocr_strip_image_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
     "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks", "lumina_ocr_selection_marks_round",
     "lumina_ocr_rules_and_marks_round", "lumina_ocr_barcodes", "lumina_ocr_qrcodes",
@@ -288,6 +289,18 @@ class Engine:
         n, out, streams, ptrs, sizes, status = self._stream_batch(streams, rows, columns, out)
         flat = (ctypes.c_int32 * (4 * n))(*[int(v) for p in params for v in p])
         self._chk(self.lib.lumina_ocr_ccitt_decode(self._h, ptrs, sizes, n, int(rows), int(columns), flat, _ptr(out), status, self._stream()))
+        return out, list(status)
+
+    def fax_decode(self, streams, rows: int, columns: int, params, out=None):
+        """Fax-coded streams (all rows x columns): /CCITTFaxDecode of any K, and the strips of TIFF Compression 2 / 3 / 4 -> (uint8
+        [n,rows,columns,3] device, status list).  params: per stream (K, EncodedByteAlign, BlackIs1, invert, path); K < 0 is
+        ccitt_decode's Group 4, K = 0 one-dimensional T.4, K > 0 two-dimensional T.4; path 0 automatic, 1 the serial walk.  status 0:
+        exact pixels, -1 anything irregular (see lumina_ocr.h), -2 unsupported (K > 0 without EOLs, EncodedByteAlign with EOLs, path 2,
+        columns > 8192)."""
+        n, out, streams, ptrs, sizes, status = self._stream_batch(streams, rows, columns, out)
+        flat = (ctypes.c_int32 * (5 * n))(*[int(v) for p in params for v in p])
+        assert len(flat) == 5 * n
+        self._chk(self.lib.lumina_ocr_fax_decode(self._h, ptrs, sizes, n, int(rows), int(columns), flat, _ptr(out), status, self._stream()))
         return out, list(status)
 
     def strip_image_decode(self, pages, height: int, width: int, rows_per_strip: int, params, palettes=None, out=None):

@@ -117,11 +117,11 @@ class OCRService:
         # LUMINA_OCR_DEVICE_PNG=1: non-interlaced PNG inputs of 8 bits or less and lazily opened PNG pages (pdf2image) are decoded on the
         # device.  Off by default: measured slower than Pillow for single pages and for 300 dpi batches
         self.device_png = os.environ.get("LUMINA_OCR_DEVICE_PNG", "0").lower() not in ("0", "false", "no")
-        # LUMINA_OCR_PDF_SCANS=1: a PDF page that is one image over the whole MediaBox (a scan: DCT, Flate or CCITT Group 4) is decoded
+        # LUMINA_OCR_PDF_SCANS=1: a PDF page that is one image over the whole MediaBox (a scan: DCT, Flate or CCITT of any /K) is decoded
         # on the device from its embedded stream, at the image's own sample grid, instead of being rasterised by pdf2image / poppler; other
         # pages still go to pdf_to_images.  Off by default: process_pdf_sync is then the rasterise-and-batch path alone.
         self.device_pdf = os.environ.get("LUMINA_OCR_PDF_SCANS", "0").lower() not in ("", "0", "false", "no")
-        # LUMINA_OCR_DEVICE_TIFF=1: stripped TIFF inputs (LZW, PackBits, Deflate, Group 4, uncompressed; utils/tiff_pages.py) are decoded on
+        # LUMINA_OCR_DEVICE_TIFF=1: stripped TIFF inputs (LZW, PackBits, Deflate, Group 4, Group 3, CCITT RLE, uncompressed; utils/tiff_pages.py) are decoded on
         # the device, process_tiff_sync reads every page of a multi-page TIFF, and process_document sends "tiff" and "tif" there.  Off by
         # default: a TIFF is then decoded by Pillow, first frame only, and every output is exactly the one without the option.
         self.device_tiff = os.environ.get("LUMINA_OCR_DEVICE_TIFF", "0").lower() not in ("", "0", "false", "no")
@@ -670,7 +670,7 @@ class OCRService:
                         out, status = eng.flate_image_decode(streams, h, w, params, [r.params["palette"] for r in recs])
                     else:
                         params = [(r.params["K"], int(r.params["EncodedByteAlign"]), int(r.params["BlackIs1"]), int(r.params["invert"])) for r in recs]
-                        out, status = eng.ccitt_decode(streams, h, w, params)
+                        out, status = eng.fax_decode(streams, h, w, [q + (0,) for q in params])
                 except Exception as e:   # the engine's own failure: these pages go to the rasteriser
                     for i in idxs:
                         reasons[i] = "%s decode failed: %s" % (filt, e)
@@ -737,8 +737,8 @@ class OCRService:
             return DocumentOCRResult(success=False, error=str(e), total_processing_time_ms=_ms_since(t0))
 
     # ---- scanned TIFFs (LUMINA_OCR_DEVICE_TIFF=1): the pages' strips, decoded on the device ----
-    def _decode_tiff_strips_in_place(self, eng, recs, w: int, h: int, rps: int, group4: bool):
-        """Group 4 and Deflate pages of one shape through the existing one-image decoders: a strip is an image of rps rows, and the strips
+    def _decode_tiff_strips_in_place(self, eng, recs, w: int, h: int, rps: int, fax: bool):
+        """Fax-coded (Group 4, Group 3, CCITT RLE: every strip restarts the coder) and Deflate pages of one shape through the existing one-image decoders: a strip is an image of rps rows, and the strips
         of a page are contiguous rows of its output.  The full strips of all pages decode in one call (in place as a [n * k, rps, W, 3] view
         when the height is a multiple of rps, else into a temporary that is copied); the shorter last strips of all pages go in one more.  -> (pages uint8 [n,H,W,3], status per page = the lowest of its strips')."""
         import torch
@@ -748,8 +748,8 @@ class OCRService:
         status = [0] * n
 
         def run(strips, owners, rows, view):
-            if group4:
-                _, st = eng.ccitt_decode(strips, rows, w, [recs[o].ccitt_params() for o in owners], out=view)
+            if fax:
+                _, st = eng.fax_decode(strips, rows, w, [recs[o].ccitt_params() + (0,) for o in owners], out=view)
             else:
                 _, st = eng.flate_image_decode(strips, rows, w, [recs[o].flate_params() for o in owners], [recs[o].palette for o in owners], out=view)
             for o, v in zip(owners, st):
@@ -769,12 +769,12 @@ class OCRService:
 
     def _decode_tiff_pages(self, entries, reasons: Dict[int, str]) -> Dict[int, Any]:
         """The accepted pages of tiff_pages.read_pages -> {page index: device tensor [1,H,W,3], Orientation applied}: grouped by codec
-        and shape, one decoder call per group (Group 4 and Deflate: see _decode_tiff_strips_in_place).  A page a decoder refuses gets its
+        and shape, one decoder call per group (the fax codings and Deflate: see _decode_tiff_strips_in_place).  A page a decoder refuses gets its
         reason in `reasons` (it goes to Pillow)."""
         groups: Dict[Any, List[int]] = {}
         for i, e in enumerate(entries):
             if isinstance(e, tiff_pages.PageImage):
-                kind = e.codec if e.codec in ("group4", "deflate") else "strips"
+                kind = "fax" if e.codec in tiff_pages.FAX_CODECS else e.codec if e.codec == "deflate" else "strips"
                 groups.setdefault((kind, e.width, e.height, e.rows_per_strip), []).append(i)
         res: Dict[int, Any] = {}
         if not groups:
@@ -789,7 +789,7 @@ class OCRService:
                         out, status = eng.strip_image_decode([r.strips for r in recs], h, w, rps, [r.strip_params() for r in recs],
                                                              [r.palette for r in recs])
                     else:
-                        out, status = self._decode_tiff_strips_in_place(eng, recs, w, h, rps, kind == "group4")
+                        out, status = self._decode_tiff_strips_in_place(eng, recs, w, h, rps, kind == "fax")
                 except Exception as e:   # the engine's own failure: these pages go to Pillow
                     for i in idxs:
                         reasons[i] = "%s decode failed: %s" % (kind, e)

@@ -4,15 +4,15 @@
 
 A TIFF from a scanner or a fax gateway is a chain of IFDs, each one page stored as strips of whole rows.  This module finds the strips
 and says how they are coded; the device decoders make the pixels (lumina_ocr_strip_image_decode for LZW, PackBits and raw strips,
-lumina_ocr_ccitt_decode for Group 4, lumina_ocr_flate_image_decode for Deflate), under the contract of the other device decoders:
+lumina_ocr_fax_decode for Group 4, Group 3 and CCITT RLE, lumina_ocr_flate_image_decode for Deflate), under the contract of the other device decoders:
 status 0 => byte-identical to Pillow's Image.open(f) (frame k) .convert('RGB'), anything else => the page is left to Pillow.
 
 The acceptance rule: a combination of tags is accepted only if tests/tiff_cases.py holds a file of that combination and
 the device decodes it equal to Pillow.  Accepted: classic TIFF (II and MM), stripped layout (no RowsPerStrip: one strip),
-PlanarConfiguration 1, Compression 1 / 4 (Group 4) / 5 (LZW) / 8 and 32946 (Deflate) / 32773 (PackBits); Photometric 0 and 1 with one
+PlanarConfiguration 1, Compression 1 / 2 (CCITT RLE) / 3 (Group 3: T4Options 0, 1, 4, 5) / 4 (Group 4) / 5 (LZW) / 8 and 32946 (Deflate) / 32773 (PackBits); Photometric 0 and 1 with one
 sample of 1 / 2 / 4 / 8 bits (Pillow opens 2- and 4-bit MinIsWhite files too), Photometric 2 with three 8-bit samples, Photometric 3
 with 1 / 2 / 4 / 8-bit indices (a palette entry is ColorMap value // 256, as in Pillow); Predictor 1, or 2 with 8-bit samples under LZW or Deflate (libtiff ignores the tag elsewhere); FillOrder 2
-only with Group 4 (the bits of each byte are reversed here); Orientation 1..8 from tag 274 (an XMP packet without that tag is refused:
+only with the three fax codings (the bits of each byte are reversed here); Orientation 1..8 from tag 274 (an XMP packet without that tag is refused:
 Pillow would read tiff:Orientation from it); no tag twice in an IFD.  Everything else is refused with a reason and nothing is
 raised past read_pages: a problem of one IFD's tags refuses that page, a problem of the chain (or any exception of this reader's own)
 refuses the whole file, which is then one TiffRefused with .whole_file set."""
@@ -23,8 +23,9 @@ from typing import Any, Dict, List, Optional, Tuple, Union
 MAX_PAGES = 20000            # IFDs in one chain
 MAX_STRIPS = 1 << 20         # strips of one page
 MAX_SIDE = 65535
-CC_MAX_COLS = 8192           # the Group 4 decoder's widest line (csrc/ccitt.h)
-COMPRESSIONS = {1: "none", 4: "group4", 5: "lzw", 8: "deflate", 32946: "deflate", 32773: "packbits"}
+CC_MAX_COLS = 8192           # the fax decoders' widest line (csrc/ccitt.h)
+COMPRESSIONS = {1: "none", 2: "rle", 3: "group3", 4: "group4", 5: "lzw", 8: "deflate", 32946: "deflate", 32773: "packbits"}
+FAX_CODECS = ("group4", "group3", "rle")
 CODEC_ID = {"none": 1, "lzw": 5, "packbits": 32773}   # the codec numbers of lumina_ocr_strip_image_decode
 
 _TYPE_SIZE = {1: 1, 2: 1, 3: 2, 4: 4, 5: 8, 6: 1, 7: 1, 8: 2, 9: 4, 10: 8, 11: 4, 12: 8, 13: 4}
@@ -43,7 +44,7 @@ class TiffRefused(Exception):
 class PageImage:
     width: int
     height: int
-    codec: str                      # "none" | "lzw" | "packbits" | "group4" | "deflate"
+    codec: str                      # "none" | "lzw" | "packbits" | "group4" | "group3" | "rle" | "deflate"
     rows_per_strip: int
     strips: List[Any]               # memoryviews into the file (bytes for FillOrder 2: the bits already reversed), in row order
     predictor: int                  # 1 | 2
@@ -54,6 +55,7 @@ class PageImage:
     invert: bool                    # MinIsWhite: sample 0 is white
     fill_order: int                 # as stored (1 | 2)
     orientation: int                # 1..8, to be applied after the decode
+    two_d: bool = False             # Group 3: T4Options bit 0 (lines may be coded two-dimensionally)
 
     def strip_rows(self, k: int) -> int:
         return min(self.height, (k + 1) * self.rows_per_strip) - k * self.rows_per_strip
@@ -66,8 +68,10 @@ class PageImage:
         return (self.predictor, self.components, self.bits, int(self.indexed), int(self.invert))
 
     def ccitt_params(self) -> Tuple[int, ...]:
-        """(K, EncodedByteAlign, BlackIs1, invert): a coded-white run is sample 0 in a TIFF, which is white under MinIsWhite"""
-        return (-1, 0, 0, int(not self.invert))
+        """(K, EncodedByteAlign, BlackIs1, invert): a coded-white run is sample 0 in a TIFF, which is white under MinIsWhite.  Group 4:
+        K -1; Group 3: K 0, or 1 with two-dimensional lines (fill bits need no flag); CCITT RLE: K 0 with byte-aligned lines."""
+        k, align = {"group4": (-1, 0), "group3": (int(self.two_d), 0), "rle": (0, 1)}[self.codec]
+        return (k, align, 0, int(not self.invert))
 
 
 class _Ifd:
@@ -148,8 +152,6 @@ def _page(ifd: _Ifd) -> PageImage:
     comp = ifd.one(259, 1)
     if comp in (6, 7):
         raise TiffRefused("JPEG-in-TIFF (Compression %d)" % comp)
-    if comp in (2, 3):
-        raise TiffRefused("Group 3 / CCITT RLE (Compression %d)" % comp)
     if comp not in COMPRESSIONS:
         raise TiffRefused("Compression %d" % comp)
     codec = COMPRESSIONS[comp]
@@ -177,7 +179,7 @@ def _page(ifd: _Ifd) -> PageImage:
     if predictor == 2 and codec not in ("lzw", "deflate"):
         raise TiffRefused("Predictor 2 with compression %s" % codec)   # (libtiff applies it with LZW and Deflate only; elsewhere the tag is ignored)
     fill = ifd.one(266, 1)
-    if fill not in (1, 2) or (fill == 2 and codec != "group4"):
+    if fill not in (1, 2) or (fill == 2 and codec not in FAX_CODECS):
         raise TiffRefused("FillOrder %d with compression %s" % (fill, codec))
     if 700 in ifd.tags and 274 not in ifd.tags:
         raise TiffRefused("XMP packet without an Orientation tag")   # (Pillow then takes tiff:Orientation from the XMP)
@@ -191,6 +193,18 @@ def _page(ifd: _Ifd) -> PageImage:
             raise TiffRefused("T6Options: uncompressed mode")
         if width > CC_MAX_COLS:
             raise TiffRefused("Group 4 wider than %d" % CC_MAX_COLS)
+    two_d = False
+    if codec in ("group3", "rle"):
+        if bits != 1 or photo not in (0, 1) or predictor != 1:
+            raise TiffRefused("Group 3 / CCITT RLE that is not one bit of grey")
+        t4 = ifd.one(292, 0) if codec == "group3" else 0   # (bit 2, fill bits before EOLs, needs nothing: the decoder skips fill anyway)
+        if t4 & 2:
+            raise TiffRefused("T4Options: uncompressed mode")
+        if t4 & ~5:
+            raise TiffRefused("T4Options %d" % t4)
+        if width > CC_MAX_COLS:
+            raise TiffRefused("Group 3 / CCITT RLE wider than %d" % CC_MAX_COLS)
+        two_d = bool(t4 & 1)
     rps = ifd.one(278, height)
     if rps == 0:
         raise TiffRefused("RowsPerStrip 0")
@@ -209,7 +223,7 @@ def _page(ifd: _Ifd) -> PageImage:
             raise TiffRefused("strip outside the file")
         strips.append(bytes(data[o:o + c]).translate(_REVERSE) if fill == 2 else data[o:o + c])
     return PageImage(width=width, height=height, codec=codec, rows_per_strip=rps, strips=strips, predictor=predictor, components=comps,
-                     bits=bits, indexed=photo == 3, palette=palette, invert=photo == 0, fill_order=fill, orientation=orientation)
+                     bits=bits, indexed=photo == 3, palette=palette, invert=photo == 0, fill_order=fill, orientation=orientation, two_d=two_d)
 
 
 def is_tiff(head: bytes) -> bool:

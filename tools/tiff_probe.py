@@ -1,7 +1,7 @@
 """Times the scanned-TIFF decoders: 64 A4@200DPI pages (1654 x 2339; --distinct different synth pages, repeated) per codec, as the
 provider's LUMINA_OCR_DEVICE_TIFF path hands them over: the strips utils/tiff_pages.py finds in files Pillow / libtiff wrote (64 KB
 strips, Pillow's default) go to lumina_ocr_strip_image_decode (LZW grey, LZW RGB with and without predictor 2, PackBits), to
-lumina_ocr_ccitt_decode (Group 4 bilevel) or to lumina_ocr_flate_image_decode (Deflate), the last two strip by strip in place.  Beside
+lumina_ocr_fax_decode (Group 4 bilevel; the fax codings have tools/fax_probe.py) or to lumina_ocr_flate_image_decode (Deflate), the last two strip by strip in place.  Beside
 each, the same files decoded by Pillow / libtiff on one host thread.  lzw_rgb_one_strip is the LZW RGB page stored as ONE strip (every
 /LZWDecode PDF page, some writers' TIFFs): it decodes on a single wave and is recorded apart.  Wall-clock per call (the calls
 synchronise), median of --reps with the spread.  Each codec runs in a child process of its own under a time limit, and the first one that
