@@ -114,6 +114,21 @@ def test_70_roots_in_one_row(engine):
     assert int((ink[10, 1:] & ~ink[10, :-1]).sum()) + int(ink[10, 0]) >= 70
 
 
+@pytest.mark.parametrize("w", [4160, 8191])
+def test_long_sides(engine, w):
+    """a side past 4096 pixels (a row of more than 64 mask words): rings of diameter 30 whose window starts at 4096 - k, one page a k,
+    the one at k = 15 with a dot, and a ring of min_side whose last column is the page's; then with x and y exchanged"""
+    offsets = (0, 1, 15, 31, 63)
+    pages = np.stack([rings_page(40, w, [(4096 - k, 5, 30, 2, k == 15), (w - 12, 14, 12, 1)]) for k in offsets])
+    assert P["min_side"] == 12 and w > 4096 + 30
+    res = check(engine, pages)
+    for k, (sq, rd) in zip(offsets, res):
+        assert [r[:4] + r[7:] for r in rd.tolist()] == [[4096 - k, 5, 4096 - k + 29, 34, int(k == 15)], [w - 12, 14, w - 1, 25, 0]] and len(sq) == 0
+    turned = check(engine, np.ascontiguousarray(pages.transpose(0, 2, 1, 3)))
+    for (_, rd), (_, td) in zip(res, turned):
+        assert td[:, [1, 0, 3, 2, 7]].tolist() == rd[:, [0, 1, 2, 3, 7]].tolist()
+
+
 def test_overflow_reports_the_true_count_and_writes_no_row(engine):
     page = synth.synth_radio_page(5)[0]
     ((sq, rd),) = check(engine, page[None], max_marks=4)
