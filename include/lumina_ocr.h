@@ -265,6 +265,32 @@ int lumina_ocr_barcodes(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int he
                         int min_rows, int row_gap, int max_codes, int32_t* codes_dev, int32_t* syms_dev, int32_t* counts_dev,
                         const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream);
 
+/* lumina_ocr_barcodes with the kinds to read: `kinds` is a bit mask, bit k = kind k, of 0 Code 128, 1 Code 39, 2 EAN-13 (UPC-A is an
+ * EAN-13 whose first digit is 0), 3 EAN-8, 4 UPC-E, 5 ITF (Interleaved 2 of 5); 1 <= kinds <= 63, and kinds = 3 is lumina_ocr_barcodes
+ * bit for bit.  At a bar the kinds of the set are tried in that order and the first that reads claims its bars; scan, directions,
+ * slots, merge and outputs are lumina_ocr_barcodes'.  A GUARD of n elements beside a digit of S pixels holds when its elements match
+ * n single modules by the measure (M = n) and its G pixels are n of the digit's seven modules within a quarter (4 |7 G - n S| <= n S).
+ * EAN-13 (30 bars), EAN-8 (22), UPC-E (17): start guard = elements 0-2 beside digit 0; digit k = four elements (7 modules) from
+ * element 3 + 4 k, behind the centre guard from 8 + 4 k; centre guard = five elements behind the left half (EAN-13: 6 digits, EAN-8: 4),
+ * beside the digit before it; end guard = three elements (UPC-E: six) behind the last digit, beside it.  The gap before the first bar
+ * is at least `quiet` modules of digit 0 and the gap behind the last bar the same of the last digit (the page edge is quiet).  A
+ * left-half digit is matched against sets L and G, a right-half digit against set R.  EAN-13: the L / G pattern is the first digit
+ * and the 13 digits pass the mod-10 check (nsym 13).  EAN-8: the left half is all L and the 8 digits pass mod 10 (nsym 8).  UPC-E: the
+ * pattern gives number system and check digit, which is the mod-10 check digit of the UPC-A the six digits abbreviate; symbols =
+ * number system, six digits, check digit (nsym 8).  ITF: start = elements 0-3, four single modules by the measure with a gap of
+ * `quiet` of them before it; pair k = elements 4 + 10 k .. 13 + 10 k, its five bars one digit and its five spaces the next (two wide
+ * of five, weights 1, 2, 4, 7, 0, digit 0 = 4 + 7), each matched on its own sum at M half-modules (narrow 2, wide (M - 6) / 2); M is
+ * the one of 14, 16, 18 (wide : narrow = 2, 2.5, 3) whose best pattern for pair 0's bars has the lowest d * (1008 / M), ties to the
+ * lower, and the start is 8 half-modules of that quintuple within a quarter; the stop behind pair k = its next three elements matched
+ * against wide, narrow, narrow, M / 2 + 1 half-modules of the pair's bars within a quarter, with a gap of `quiet` modules (or the page
+ * edge) behind it; the code ends at the first pair k >= 2 with a stop and every pair up to it matched: 6..64 digits, an even count
+ * (nsym = the digits).  ITF has no check symbol; 14 digits that pass mod 10 set flags bit 2 (ITF-14).  The symbol values of kinds 2-5
+ * are the digits.  Everything else as lumina_ocr_barcodes; kinds of 0 or with unknown bits is a bad-argument status before anything is
+ * written.  Integer arithmetic throughout: the result is defined bit for bit (tests/linear_reference.py). */
+int lumina_ocr_barcodes_kinds(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int quiet, int max_dist,
+                              int min_rows, int row_gap, int max_codes, int32_t* codes_dev, int32_t* syms_dev, int32_t* counts_dev,
+                              const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream, int kinds);
+
 /* QR codes: QR Code Model 2 symbols (ISO/IEC 18004) of versions 1-10 on the pages, located, sampled and error-corrected on the device
  * (the host half is lumina_ocr/utils/qrcodes.py).  ink as in lumina_ocr_table_rules.  Of the 8-connected components of the ink a CORE
  * is a solid square (sides 3 min_module .. 3 max_module, 4 |w - h| <= min(w, h), 4 area >= 3 w h) whose centre row has, before and

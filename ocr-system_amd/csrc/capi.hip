@@ -722,15 +722,16 @@ int lumina_ocr_rules_and_marks_round(lumina_ocr_t* h, const uint8_t* pages_dev, 
                                 round_dev, round_counts_dev, stream);
 }
 
-int lumina_ocr_barcodes(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int quiet, int max_dist, int min_rows,
-                        int row_gap, int max_codes, int32_t* codes_dev, int32_t* syms_dev, int32_t* counts_dev, const uint64_t* mask_in_dev,
-                        uint64_t* mask_out_dev, void* stream) {
+static int barcodes_impl(lumina_ocr_t* h, const char* what, const uint8_t* pages_dev, int n, int height, int width, int threshold, int quiet, int max_dist,
+                         int min_rows, int row_gap, int max_codes, int kinds, int32_t* codes_dev, int32_t* syms_dev, int32_t* counts_dev,
+                         const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream) {
     if (!h) return 1;
     if (n == 0) return 0;
-    if (!pages_dev || !codes_dev || !syms_dev || !counts_dev || n < 0) return locr_fail(h, "barcodes", "bad arguments");
+    if (!pages_dev || !codes_dev || !syms_dev || !counts_dev || n < 0) return locr_fail(h, what, "bad arguments");
+    if (!barcode_kinds_ok(kinds)) return locr_fail(h, what, "kinds must be a non-empty set of the bits 0..5 (1..63)");
     if (!barcode_params_ok(quiet, max_dist, min_rows, row_gap, max_codes))
-        return locr_fail(h, "barcodes", "parameters must satisfy 0 <= quiet <= 64, 0 <= max_dist <= 256, min_rows >= 1, 1 <= row_gap <= 16, max_codes 1..256");
-    if (barcodes_workspace_bytes(1, height, width, max_codes) == 0) return locr_fail(h, "barcodes", "bad dimensions (sides 1..65535)");
+        return locr_fail(h, what, "parameters must satisfy 0 <= quiet <= 64, 0 <= max_dist <= 256, min_rows >= 1, 1 <= row_gap <= 16, max_codes 1..256");
+    if (barcodes_workspace_bytes(1, height, width, max_codes) == 0) return locr_fail(h, what, "bad dimensions (sides 1..65535)");
     BIND(h);
     API_TRY
     // the run list is sized for its worst case (8 bytes per two pixels); four read slots a row and a column
@@ -740,12 +741,27 @@ int lumina_ocr_barcodes(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int he
         BarcodeParams p{};
         p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.H = height; p.W = width;
         p.threshold = threshold; p.quiet = quiet; p.max_dist = max_dist; p.min_rows = min_rows; p.row_gap = row_gap; p.max_codes = max_codes;
+        p.kinds = kinds;
         p.codes = codes_dev + (size_t)b0 * max_codes * 8; p.syms = syms_dev + (size_t)b0 * max_codes * BARCODE_MAX_SYMS; p.counts = counts_dev + b0;
         p.mask_in = mask_in_dev ? reinterpret_cast<const unsigned long long*>(mask_in_dev) + (size_t)b0 * height * nw : nullptr;
         p.mask_out = mask_out_dev ? reinterpret_cast<unsigned long long*>(mask_out_dev) + (size_t)b0 * height * nw : nullptr;
-        return hip_rc(h, "barcodes", barcodes_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
+        return hip_rc(h, what, barcodes_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
     });
     API_CATCH(h)
+}
+
+int lumina_ocr_barcodes(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int quiet, int max_dist, int min_rows,
+                        int row_gap, int max_codes, int32_t* codes_dev, int32_t* syms_dev, int32_t* counts_dev, const uint64_t* mask_in_dev,
+                        uint64_t* mask_out_dev, void* stream) {
+    return barcodes_impl(h, "barcodes", pages_dev, n, height, width, threshold, quiet, max_dist, min_rows, row_gap, max_codes, BARCODE_KINDS_DEFAULT, codes_dev,
+                         syms_dev, counts_dev, mask_in_dev, mask_out_dev, stream);
+}
+
+int lumina_ocr_barcodes_kinds(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int quiet, int max_dist, int min_rows,
+                              int row_gap, int max_codes, int32_t* codes_dev, int32_t* syms_dev, int32_t* counts_dev, const uint64_t* mask_in_dev,
+                              uint64_t* mask_out_dev, void* stream, int kinds) {
+    return barcodes_impl(h, "barcodes_kinds", pages_dev, n, height, width, threshold, quiet, max_dist, min_rows, row_gap, max_codes, kinds, codes_dev, syms_dev,
+                         counts_dev, mask_in_dev, mask_out_dev, stream);
 }
 
 int lumina_ocr_qrcodes(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module, int max_module, int quiet,

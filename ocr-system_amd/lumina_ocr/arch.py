@@ -476,6 +476,29 @@ ROUND_MARK_PARAMS = dict(out_max=0, ring_div=12, band_div=4, band_min=4)
 # m = 2 px on.  The nearest pattern wins anyway; the checksum, the stop and min_rows equal reads carry the rest of the rejection.
 # quiet = 5 is half the standard's ten modules: forms crowd their codes.  max_codes = capacity of a page's list (<= 256).
 BARCODE_PARAMS = dict(threshold=MARK_PARAMS["threshold"], quiet=5, max_dist=24, min_rows=8, row_gap=2, max_codes=64)
+# The kinds lumina_ocr_barcodes_kinds reads, name -> bit of its mask (definition restated in tests/linear_reference.py).  "ean13" reads
+# UPC-A as well (an EAN-13 whose first digit is 0).  The same parameters serve every kind: the guards of EAN / UPC and the start and stop
+# of ITF are matched by the same measure, both of their ends need the quiet gap, and ITF reads from 6 digits on.
+BARCODE_KINDS = dict(code128=1, code39=2, ean13=4, ean8=8, upce=16, itf=32)
+BARCODE_KINDS_DEFAULT = ("code128", "code39")
+
+
+def barcode_kinds_mask(names) -> int:
+    """Names of BARCODE_KINDS (a sequence, or a comma list; "all" is every kind) -> the bit mask; an unknown name or an empty set is a
+    ValueError."""
+    if isinstance(names, str):
+        names = [n.strip().lower() for n in names.split(",") if n.strip()]
+    mask = 0
+    for n in names:
+        if n == "all":
+            mask |= sum(BARCODE_KINDS.values())
+        elif n in BARCODE_KINDS:
+            mask |= BARCODE_KINDS[n]
+        else:
+            raise ValueError("unknown barcode kind %r: one of %s, or all" % (n, ", ".join(BARCODE_KINDS)))
+    if not mask:
+        raise ValueError("no barcode kind given: some of %s, or all" % ", ".join(BARCODE_KINDS))
+    return mask
 
 # QR codes (lumina_ocr_qrcodes + utils/qrcodes.py, definition restated in tests/qr_reference.py): ink as above, at the barcodes'
 # threshold so that one mask serves both.  min_module = 3 px is the issue's floor; max_module = 24 px lets a version 10 symbol span 1368 of the 2000 processed pixels.  centre_tol and ring_tol

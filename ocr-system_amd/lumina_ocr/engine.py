@@ -96,6 +96,7 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_table_rules": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
         "lumina_ocr_selection_marks": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
         "lumina_ocr_barcodes": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+        "lumina_ocr_barcodes_kinds": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32]),
         "lumina_ocr_qrcodes": (i32, [vp, vp, i32, i32, i32] + [i32] * 9 + [vp] * 7),
         "lumina_ocr_rules_and_marks": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_selection_marks_round": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
@@ -130,7 +131,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_png_probe", "lumina_ocr_png_decode", "lumina_ocr_flate_image_decode", "lumina_ocr_ccitt_decode", "lumina_ocr_fax_decode", "lumina_ocr_strip_image_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
     "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks", "lumina_ocr_selection_marks_round",
-    "lumina_ocr_rules_and_marks_round", "lumina_ocr_barcodes", "lumina_ocr_qrcodes",
+    "lumina_ocr_rules_and_marks_round", "lumina_ocr_barcodes", "lumina_ocr_barcodes_kinds", "lumina_ocr_qrcodes",
     "lumina_ocr_page_quarter_workspace_bytes", "lumina_ocr_page_quarter", "lumina_ocr_page_turn", "lumina_ocr_page_vote",
 ]
 
@@ -634,13 +635,15 @@ class Engine:
                                                       _ptr(counts), _ptr(mask), self._stream()))
         return (marks, counts, mask) if debug else (marks, counts)
 
-    # -- barcodes (Code 128 and Code 39; the host half is utils/barcodes.py) ------------------------------------------------------
+    # -- barcodes (Code 128, Code 39, EAN / UPC, ITF; the host half is utils/barcodes.py) ------------------------------------------
     def barcodes(self, pages, threshold=None, quiet=None, max_dist=None, min_rows=None, row_gap=None, max_codes=None, mask_in=None,
-                 debug: bool = False):
+                 debug: bool = False, kinds=None):
         """uint8 [n,H,W,3] device -> (codes int32 [n,max_codes,8], syms int32 [n,max_codes,64], counts int32 [n]) on the device: the
-        barcodes of each page as x0, y0, x1, y1, kind (0 Code 128, 1 Code 39), nsym, rows, flags (bit 0 reversed, bit 1 vertical),
-        sorted by (y0, x0, y1, x1), with their symbol values; counts = the true numbers (a list whose count exceeds max_codes is not
-        written).  Parameters default to arch.BARCODE_PARAMS.  mask_in: the ink mask of the pages at this threshold, int64
+        barcodes of each page as x0, y0, x1, y1, kind (0 Code 128, 1 Code 39, 2 EAN-13, 3 EAN-8, 4 UPC-E, 5 ITF), nsym, rows, flags (bit 0
+        reversed, bit 1 vertical, bit 2 ITF-14), sorted by (y0, x0, y1, x1), with their symbol values; counts = the true numbers (a list
+        whose count exceeds max_codes is not written).  kinds: None reads Code 128 and Code 39 (lumina_ocr_barcodes); otherwise the set
+        to read (lumina_ocr_barcodes_kinds) as a bit mask, bit k = kind k, or as names of arch.BARCODE_KINDS.  Parameters default to
+        arch.BARCODE_PARAMS.  mask_in: the ink mask of the pages at this threshold, int64
         [n,H,ceil(W/64)], when it is there already.  Asynchronous.  debug=True also returns the ink mask the pass worked on."""
         torch = _torch()
         n, h, w, c = pages.shape
@@ -654,8 +657,12 @@ class Engine:
         syms = torch.zeros((n, max(max_codes, 0), 64), dtype=torch.int32, device=pages.device)
         counts = torch.zeros((n,), dtype=torch.int32, device=pages.device)
         mask = torch.zeros((n, h, (w + 63) // 64), dtype=torch.int64, device=pages.device) if debug else None
-        self._chk(self.lib.lumina_ocr_barcodes(self._h, _ptr(pages), n, h, w, threshold, quiet, max_dist, min_rows, row_gap, max_codes, _ptr(codes),
-                                               _ptr(syms), _ptr(counts), _ptr(mask_in), _ptr(mask), self._stream()))
+        args = (self._h, _ptr(pages), n, h, w, threshold, quiet, max_dist, min_rows, row_gap, max_codes, _ptr(codes), _ptr(syms), _ptr(counts),
+                _ptr(mask_in), _ptr(mask), self._stream())
+        if kinds is None:
+            self._chk(self.lib.lumina_ocr_barcodes(*args))
+        else:
+            self._chk(self.lib.lumina_ocr_barcodes_kinds(*args, kinds if isinstance(kinds, int) else arch.barcode_kinds_mask(kinds)))
         return (codes, syms, counts, mask) if debug else (codes, syms, counts)
 
     # -- QR codes (Model 2, versions 1-10; the host half is utils/qrcodes.py) --------------------------------------------------------

@@ -38,7 +38,7 @@ class PageDetections:
     marks: Optional[np.ndarray] = None        # int32 [m, 8] x0, y0, x1, y1, edge, ink_in, area_in, state of the page's checkboxes:
                                               # OcrPipeline(marks=True) only (empty when the list overflowed its capacity)
     round_marks: Optional[np.ndarray] = None  # int32 [m, 8] the same of the page's radio buttons: OcrPipeline(marks=True, round_marks=True) only
-    barcodes: Optional[np.ndarray] = None     # int32 [m, 8] x0, y0, x1, y1, kind, nsym, rows, flags of the page's Code 128 / Code 39 strips:
+    barcodes: Optional[np.ndarray] = None     # int32 [m, 8] x0, y0, x1, y1, kind, nsym, rows, flags of the page's barcode strips:
                                               # OcrPipeline(barcodes=True) only (empty when the list overflowed its capacity)
     barcode_syms: Optional[np.ndarray] = None  # int32 [m, 64] their symbol values (utils/barcodes.py turns them into text)
     qrcodes: Optional[np.ndarray] = None      # int32 [m, 12] x0, y0, x1, y1, version, level, mask, ndata, errors, rotation, format distance,
@@ -89,7 +89,7 @@ class OcrPipeline:
                  tables: bool = False, table_params: Optional[dict] = None, marks: bool = False, mark_params: Optional[dict] = None,
                  page_orient: bool = False, page_orient_params: Optional[dict] = None, word_boxes: bool = False, round_marks: bool = False,
                  round_mark_params: Optional[dict] = None, barcodes: bool = False, barcode_params: Optional[dict] = None,
-                 qrcodes: bool = False, qr_params: Optional[dict] = None):
+                 qrcodes: bool = False, qr_params: Optional[dict] = None, barcode_kinds=arch.BARCODE_KINDS_DEFAULT):
         """recognizer: "crnn" (CRNN-MobileNetV3 + BiLSTM, engine.load_rec) or "svtr" (SVTR, engine.load_svtr).
         angle_cls: PaddleOCR's use_angle_cls — every line is classified 0 / 180 degrees (engine.load_cls) before recognition, and a line
         read as 180 with probability > cls_thresh is recognised turned; boxes and reading order are unchanged.  Per-line labels are
@@ -104,7 +104,8 @@ class OcrPipeline:
         marks it is a ValueError.
         barcodes: the Code 128 and Code 39 strips of the processed pages (engine.barcodes, parameters arch.BARCODE_PARAMS or
         barcode_params) come back as PageDetections.barcodes / barcode_syms; like the marks they stay on their rank, and with a gather
-        the pass is not run.
+        the pass is not run.  barcode_kinds: the kinds to read instead, names of arch.BARCODE_KINDS ("ean13", "ean8", "upce", "itf"
+        beside the two) or "all"; an unknown name is a ValueError.
         qrcodes: the QR symbols (Model 2, versions 1-10) of the processed pages (engine.qrcodes, parameters arch.QR_PARAMS or qr_params)
         come back as PageDetections.qrcodes / qr_data; they stay on their rank too, and with a gather the pass is not run.
         page_orient: run_oriented() finds for every page the quarter turns that make it upright (ink profiles for sideways pages,
@@ -137,6 +138,9 @@ class OcrPipeline:
             raise ValueError("round_marks needs marks=True: the radio buttons are found in the checkboxes' pass")
         self.barcodes = bool(barcodes)
         self.barcode_params = dict(arch.BARCODE_PARAMS if barcode_params is None else barcode_params)
+        self.barcode_kinds = arch.barcode_kinds_mask(barcode_kinds)
+        # the default kinds go through lumina_ocr_barcodes, as before there were others
+        self._barcode_kinds_arg = None if self.barcode_kinds == arch.barcode_kinds_mask(arch.BARCODE_KINDS_DEFAULT) else self.barcode_kinds
         self.qrcodes = bool(qrcodes)
         self.qr_params = dict(arch.QR_PARAMS if qr_params is None else qr_params)
         self.page_orient = bool(page_orient)
@@ -209,7 +213,7 @@ class OcrPipeline:
             return None
         bp = self.barcode_params
         return self.eng.barcodes(processed, bp["threshold"], bp["quiet"], bp["max_dist"], bp["min_rows"], bp["row_gap"], bp["max_codes"],
-                                 mask_in=mask_in, debug=mask_out)
+                                 mask_in=mask_in, debug=mask_out, kinds=self._barcode_kinds_arg)
 
     def _submit_rules_marks(self, processed, mask_at: Optional[int] = None):
         """Enqueue the table rules and / or selection marks of the processed pages -> (rules, marks, mask): device tensors, or None each; with

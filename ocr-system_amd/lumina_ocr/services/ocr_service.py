@@ -149,6 +149,10 @@ class OCRService:
         # LUMINA_OCR_BARCODES=1: Code 128 and Code 39 strips become `barcode` entries with their decoded content and a `:barcode: <content>`
         # line of the Markdown; the text lines the detector found on a strip are dropped.  Off by default: every output is then the one without it.
         self._use_barcodes = os.environ.get("LUMINA_OCR_BARCODES", "0").lower() not in ("", "0", "false", "no")
+        # LUMINA_OCR_BARCODE_KINDS (with LUMINA_OCR_BARCODES=1; alone it has no effect): the kinds to read, a comma list of code128, code39,
+        # ean13 (UPC-A with it), ean8, upce, itf, or all.  Default code128,code39: every output is then the one without the variable.  An
+        # unknown name is an error result.
+        self._barcode_kinds = os.environ.get("LUMINA_OCR_BARCODE_KINDS", "") or ",".join(arch.BARCODE_KINDS_DEFAULT)
         # LUMINA_OCR_QRCODES=1: QR symbols (Model 2, versions 1-10) become `barcode` entries of kind "QRCode" with their decoded content and a
         # `:barcode: <content>` line of the Markdown, behind the 1-D codes of the page when LUMINA_OCR_BARCODES is on as well; the text lines the
         # detector found inside a symbol are dropped.  Off by default: every output is then the one without it.
@@ -192,6 +196,11 @@ class OCRService:
                                    % ("LUMINA_OCR_USE_ANGLE_CLS" if self._use_angle_cls else "LUMINA_OCR_PAGE_ORIENTATION"))
             if self._use_round_marks and not self._use_marks:
                 raise RuntimeError("LUMINA_OCR_RADIO_BUTTONS=1 needs LUMINA_OCR_SELECTION_MARKS=1: radio buttons are found in the checkboxes' pass")
+            if self._use_barcodes:
+                try:
+                    arch.barcode_kinds_mask(self._barcode_kinds)
+                except ValueError as e:
+                    raise RuntimeError("LUMINA_OCR_BARCODE_KINDS: %s" % e)
             if have_files and not self._rec_dict:
                 raise RuntimeError("LUMINA_OCR_REC_DICT (the dictionary file the recogniser was trained with) is required with weight files")
             eng = Engine(self._device)  # raises EngineUnavailable without the HIP library / a GPU
@@ -227,7 +236,8 @@ class OCRService:
                     pipeline = OcrPipeline(eng, charset=charset, max_dimension=self.max_dimension, post=post, recognizer=self._recognizer,
                                            angle_cls=self._use_angle_cls, tables=self._use_tables, marks=self._use_marks,
                                            page_orient=self._use_page_orient, word_boxes=self._use_word_boxes, round_marks=self._use_round_marks,
-                                           barcodes=self._use_barcodes, qrcodes=self._use_qrcodes)
+                                           barcodes=self._use_barcodes, qrcodes=self._use_qrcodes,
+                                           barcode_kinds=self._barcode_kinds if self._use_barcodes else arch.BARCODE_KINDS_DEFAULT)
             except Exception:
                 eng.close()
                 raise
@@ -236,6 +246,16 @@ class OCRService:
             self._pre._engine = eng
             pipeline.binarize = self.apply_binarize
             self._pipeline = pipeline
+
+    def _barcode_kinds_names(self):
+        """The kinds the provider reads, by name ([] with barcodes off; the variable's text when it names an unknown kind)."""
+        if not self._use_barcodes:
+            return []
+        try:
+            mask = arch.barcode_kinds_mask(self._barcode_kinds)
+        except ValueError:
+            return [self._barcode_kinds]
+        return [k for k, bit in arch.BARCODE_KINDS.items() if mask & bit]
 
     def _device_ctx(self):
         """Binds the calling thread (possibly an asyncio.to_thread worker, which starts on device 0) to the engine's GPU."""
@@ -918,7 +938,7 @@ class OCRService:
     # ---- status (:759-795) ----
     def get_status(self) -> Dict[str, Any]:
         st = {"client_initialized": self._pipeline is not None, "model_id": "dbnet-r18vd+crnn-mv3", "max_dimension": self.max_dimension,
-              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "qrcodes": self._use_qrcodes, "device_pdf": self.device_pdf, "device_tiff": self.device_tiff, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
+              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "device_pdf": self.device_pdf, "device_tiff": self.device_tiff, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
         if self._engine is not None:
             st["engine_version"] = self._engine.version()
             st["num_classes"] = self._engine.num_classes

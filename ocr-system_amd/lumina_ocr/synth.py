@@ -508,22 +508,74 @@ def render_barcode(page: np.ndarray, x: int, y: int, symbols, kind: str, module_
     """Draw exact module-wide bars into page (uint8 [H,W,3], in place) from (x, y): along x and `height` rows tall, or with vertical
     along y and `height` columns wide; reversed draws the elements from the far end (a strip printed upside down).
     -> the box (x0, y0, x1, y1), inclusive."""
-    el = barcode_modules(symbols, kind)
-    if reversed:
-        el = el[::-1]
-    length = module_px * sum(el)
+    return render_elements(page, x, y, [module_px * m for m in barcode_modules(symbols, kind)], height, reversed, vertical, ink)
+
+
+def render_elements(page: np.ndarray, x: int, y: int, el_px, height: int, reversed: bool = False, vertical: bool = False,
+                    ink: int = 0) -> Tuple[int, int, int, int]:
+    """render_barcode for element widths in pixels (bar first)."""
+    el = list(el_px)[::-1] if reversed else list(el_px)
+    length = sum(el)
     if x < 0 or y < 0 or (y + length > page.shape[0] or x + height > page.shape[1] if vertical else x + length > page.shape[1] or y + height > page.shape[0]):
         raise ValueError("the barcode does not fit the page")
     pos = 0
     for i, m in enumerate(el):
         if i % 2 == 0:
-            a, b = pos, pos + m * module_px
+            a, b = pos, pos + m
             if vertical:
                 page[y + a:y + b, x:x + height] = ink
             else:
                 page[y:y + height, x + a:x + b] = ink
-        pos += m * module_px
+        pos += m
     return (x, y, x + height - 1, y + length - 1) if vertical else (x, y, x + length - 1, y + height - 1)
+
+
+# ---- EAN-13 / UPC-A, EAN-8, UPC-E and ITF: encoders from digit strings, written from the tables of utils/barcodes.py ----
+def check_digit(body: str) -> int:
+    """The GS1 mod-10 check digit of a digit string without it: from the right the weights are 3, 1, 3 ..."""
+    return -sum(int(c) * (1 if i % 2 else 3) for i, c in enumerate(body[::-1])) % 10
+
+
+def linear_elements(kind: str, digits: str, module_px: int = 2, ratio: float = 2.0) -> List[int]:
+    """The digits of an "EAN13" (13; a UPC-A is 0 + its 12), "EAN8" (8), "UPCE" (8: number system, six digits, check) or "ITF" (an even
+    count) -> the element widths in pixels, bar first, as they are printed; no digit is checked.  ITF's wide elements are
+    round(ratio * module_px) pixels."""
+    from .utils import barcodes as bc
+    d = [int(c) for c in digits]
+    el: List[int] = []
+    if kind == "ITF":
+        if len(d) % 2:
+            raise ValueError("ITF takes an even number of digits")
+        wide = int(ratio * module_px + 0.5)
+        px = lambda v: [wide if c == "w" else module_px for c in bc.ITF_PATTERNS[v]]
+        el += [module_px] * 4
+        for a, b in zip(d[0::2], d[1::2]):
+            el += [w for pair in zip(px(a), px(b)) for w in pair]
+        return el + [wide, module_px, module_px]
+    sets = {"L": bc.EAN_L, "G": bc.EAN_G, "R": bc.EAN_R, "O": bc.EAN_L, "E": bc.EAN_G}
+    if kind == "EAN13" and len(d) == 13:
+        left, right, parity, end = d[1:7], d[7:], bc.EAN13_PARITY[d[0]], 3
+    elif kind == "EAN8" and len(d) == 8:
+        left, right, parity, end = d[:4], d[4:], "LLLL", 3
+    elif kind == "UPCE" and len(d) == 8 and d[0] in (0, 1):
+        left, right, parity, end = d[1:7], [], bc.UPCE_PARITY[10 * d[0] + d[7]], 6
+    else:
+        raise ValueError("%s of %d digits" % (kind, len(d)))
+    el += [1, 1, 1]
+    for v, s in zip(left, parity):
+        el += [int(c) for c in sets[s][v]]
+    if right:
+        el += [1] * 5
+        for v in right:
+            el += [int(c) for c in bc.EAN_R[v]]
+    el += [1] * end
+    return [module_px * m for m in el]
+
+
+def render_linear(page: np.ndarray, x: int, y: int, kind: str, digits: str, module_px: int = 2, height: int = 24, ratio: float = 2.0,
+                  reversed: bool = False, vertical: bool = False, ink: int = 0) -> Tuple[int, int, int, int]:
+    """render_barcode for the digit-only kinds of linear_elements; the quiet zones are the caller's (what lies round (x, y))."""
+    return render_elements(page, x, y, linear_elements(kind, digits, module_px, ratio), height, reversed, vertical, ink)
 
 
 def synth_barcode_page(seed: int, h: int = 700, w: int = 1000, n_codes: int = 3, text_lines: int = 6, module_px: int = 0,

@@ -1,16 +1,19 @@
-"""Barcodes, host half (pure Python): the symbol tables of Code 128 and Code 39, the symbol values of a device row
-(lumina_ocr_barcodes: x0, y0, x1, y1, kind, nsym, rows, flags + the symbol values) -> text, and the entries the provider reports.
+"""Barcodes, host half (pure Python): the symbol tables of Code 128, Code 39, EAN / UPC and ITF, the symbol values of a device row
+(lumina_ocr_barcodes / lumina_ocr_barcodes_kinds: x0, y0, x1, y1, kind, nsym, rows, flags + the symbol values) -> text, and the
+entries the provider reports.
 
-The tables are our reading of the public standards (ISO/IEC 15417 and 16388).  Code 39 is built from its rule; Code 128 is typed
-and pinned structurally (tests/test_barcode_tables.py).  csrc/barcode_tables.h holds the same tables for the device (device_header()
-writes it; the test compares)."""
+The tables are our reading of the public standards (ISO/IEC 15417, 16388, 15420 and 16390).  Code 39 and ITF are built from their
+rule; Code 128 and EAN's set L and parity rows are typed and pinned structurally (tests/test_barcode_tables.py,
+tests/test_linear_tables.py).  csrc/barcode_tables.h holds Code 128 and Code 39 for the device (device_header() writes it),
+csrc/linear_tables.h the EAN / UPC / ITF tables (linear_device_header()); the tests compare."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence
 
 MAX_SYMS = 64
-KINDS = ("Code128", "Code39")
-FLAG_REVERSED, FLAG_VERTICAL = 1, 2
+KINDS = ("Code128", "Code39", "EAN13", "EAN8", "UPCE", "ITF")      # by device kind; an EAN13 with first digit 0 is reported as "UPCA"
+KIND_CODE128, KIND_CODE39, KIND_EAN13, KIND_EAN8, KIND_UPCE, KIND_ITF = range(6)
+FLAG_REVERSED, FLAG_VERTICAL, FLAG_ITF14 = 1, 2, 4
 
 # ---- Code 128: values 0..105 are six elements (bar, space, bar, space, bar, space) of 1..4 modules, 11 modules in all; the stop
 # (106) is seven elements, 13 modules: its first six are matched like any symbol and a two-module bar ends it ----
@@ -73,6 +76,86 @@ def _code39_table() -> List[str]:
 CODE39_PATTERNS = tuple(_code39_table())
 
 
+# ---- EAN / UPC: a digit is four elements of 1..4 modules, 7 modules in all.  Set L (left half, odd parity) is typed, space first;
+# set R (right half) has the same widths bar first; set G (left half, even parity) is L's widths reversed, space first ----
+EAN_L = "3211 2221 2122 1411 1132 1231 1114 1312 1213 3112".split()
+EAN_R = tuple(EAN_L)
+EAN_G = tuple(p[::-1] for p in EAN_L)
+EAN_MATCH = tuple(EAN_L) + EAN_G        # what the device matches a left-half digit against: L 0-9 are values 0..9, G 0-9 values 10..19
+EAN_MODULES = 7
+EAN13_PARITY = "LLLLLL LLGLGG LLGGLG LLGGGL LGLLGG LGGLLG LGGGLL LGLGLG LGLGGL LGGLGL".split()     # by the first digit
+UPCE_PARITY_0 = "EEEOOO EEOEOO EEOOEO EEOOOE EOEEOO EOOEEO EOOOEE EOEOEO EOEOOE EOOEOE".split()    # number system 0, by the check digit
+UPCE_PARITY = tuple(UPCE_PARITY_0) + tuple(p.translate({69: 79, 79: 69}) for p in UPCE_PARITY_0)   # then number system 1: the complement
+# layout by device kind: digits read, digits of the left half, first element of the centre guard (or None), of the end guard, the end
+# guard's elements, bars
+EAN_LAYOUT = {KIND_EAN13: (12, 6, 27, 56, 3, 30), KIND_EAN8: (8, 4, 19, 40, 3, 22), KIND_UPCE: (6, 6, None, 27, 6, 17)}
+
+# ---- ITF: a quintuple (the five bars of a pair, or its five spaces) is two-of-five with weights 1, 2, 4, 7, 0; the digit 0 is 4 + 7 ----
+ITF_WEIGHTS = (1, 2, 4, 7, 0)
+ITF_RATIOS = (14, 16, 18)               # half-modules of a quintuple at wide : narrow = 2, 2.5 and 3 (narrow 2, wide 4, 5, 6)
+ITF_MIN_DIGITS, ITF_MAX_DIGITS = 6, 64
+
+
+def _itf_table() -> List[str]:
+    """-> for every digit its five elements as 'n' (narrow) and 'w' (wide)"""
+    table = [None] * 10
+    for a in range(5):
+        for b in range(a + 1, 5):
+            v = ITF_WEIGHTS[a] + ITF_WEIGHTS[b]
+            table[0 if v == 11 else v] = "".join("w" if i in (a, b) else "n" for i in range(5))
+    return table
+
+
+ITF_PATTERNS = tuple(_itf_table())
+
+
+def itf_widths(digit: int, modules: int) -> List[int]:
+    """The five elements of a digit in half-modules at a quintuple of `modules` half-modules (ITF_RATIOS)."""
+    return [(modules - 6) // 2 if c == "w" else 2 for c in ITF_PATTERNS[digit]]
+
+
+def mod10_ok(digits: Sequence[int]) -> bool:
+    """The GS1 check of a digit string that ends in its check digit: from the right the weights are 1 (the check), 3, 1, 3 ..."""
+    return sum(int(v) * (3 if i % 2 else 1) for i, v in enumerate(reversed(list(digits)))) % 10 == 0
+
+
+def upce_to_upca(syms: Sequence[int]) -> Optional[List[int]]:
+    """The 8 digits of a UPC-E (number system, six digits a b c d e f, check) -> the 12 digits of the UPC-A it abbreviates, by its last
+    digit f: 0-2 -> manufacturer a b f 0 0, product 0 0 c d e; 3 -> a b c 0 0, 0 0 0 d e; 4 -> a b c d 0, 0 0 0 0 e; 5-9 -> a b c d e,
+    0 0 0 0 f.  The check digit is the UPC-A's."""
+    syms = [int(s) for s in syms]
+    if len(syms) != 8 or syms[0] not in (0, 1) or any(not 0 <= s <= 9 for s in syms):
+        return None
+    a, b, c, d, e, f = syms[1:7]
+    if f <= 2:
+        body = [a, b, f, 0, 0, 0, 0, c, d, e]
+    elif f == 3:
+        body = [a, b, c, 0, 0, 0, 0, 0, d, e]
+    elif f == 4:
+        body = [a, b, c, d, 0, 0, 0, 0, 0, e]
+    else:
+        body = [a, b, c, d, e, 0, 0, 0, 0, f]
+    return [syms[0]] + body + [syms[7]]
+
+
+def linear_device_header() -> str:
+    """The text of csrc/linear_tables.h: the 20 left-half digit patterns as four nibbles (element i in bits 4 i), the parity rows as
+    six bits (bit k set: digit k is of set G / E), ITF's digits as five bits (bit i set: element i is wide)."""
+    ean = [sum(int(c) << (4 * i) for i, c in enumerate(p)) for p in EAN_MATCH]
+    p13 = [sum((c == "G") << i for i, c in enumerate(p)) for p in EAN13_PARITY]
+    pe = [sum((c == "E") << i for i, c in enumerate(p)) for p in UPCE_PARITY]
+    itf = [sum((c == "w") << i for i, c in enumerate(p)) for p in ITF_PATTERNS]
+    rows = lambda v, f: ",\n".join("    " + ", ".join(f % x for x in v[i:i + 10]) for i in range(0, len(v), 10))
+    return ("#pragma once\n// Written by lumina_ocr.utils.barcodes.linear_device_header(); tests/test_linear_tables.py compares.  EAN / UPC: sets L (values\n"
+            "// 0..9) and G (10..19), element i in bits 4 i .. 4 i + 3; set R has L's widths.  Parity rows: bit k set when left digit k is of set G\n"
+            "// (EAN-13, by the first digit) or E (UPC-E, number system 0 by the check digit, then number system 1).  ITF: bit i set when element i\n"
+            "// of the digit's quintuple is wide.\n"
+            "constexpr int BC_NEAN = %d, BC_NUPCE = %d;\n__constant__ const unsigned BC_EAN[BC_NEAN] = {\n%s};\n"
+            "__constant__ const unsigned BC_EAN13_PARITY[10] = {\n%s};\n__constant__ const unsigned BC_UPCE_PARITY[BC_NUPCE] = {\n%s};\n"
+            "__constant__ const unsigned BC_ITF[10] = {\n%s};\n"
+            % (len(ean), len(pe), rows(ean, "0x%04x"), rows(p13, "0x%02x"), rows(pe, "0x%02x"), rows(itf, "0x%02x")))
+
+
 def device_header() -> str:
     """The text of csrc/barcode_tables.h: Code 128 as six nibbles a pattern (element i in bits 4 i), Code 39 as nine bits (bit i set:
     element i is wide)."""
@@ -128,14 +211,35 @@ def code39_text(syms: Sequence[int]) -> Optional[str]:
     return "".join(CODE39_CHARS[s] for s in syms[1:-1])
 
 
+def digits_text(kind: int, syms: Sequence[int]) -> Optional[str]:
+    """The digits of an EAN-13 (13), EAN-8 (8), UPC-E (its 8: number system, six digits, check) or ITF (even, 6..64) -> the string, or
+    None when they are no message of the kind: a wrong count, no digits, a failing mod-10 check (ITF has none)."""
+    syms = [int(s) for s in syms]
+    if any(not 0 <= s <= 9 for s in syms):
+        return None
+    if kind == KIND_ITF:
+        ok = ITF_MIN_DIGITS <= len(syms) <= ITF_MAX_DIGITS and len(syms) % 2 == 0
+    elif kind == KIND_UPCE:
+        full = upce_to_upca(syms)
+        ok = full is not None and mod10_ok(full)
+    else:
+        ok = len(syms) == (13 if kind == KIND_EAN13 else 8) and mod10_ok(syms)
+    return "".join(map(str, syms)) if ok else None
+
+
 def symbols_text(kind: int, syms: Sequence[int]) -> Optional[str]:
-    return code128_text(syms) if kind == 0 else code39_text(syms)
+    if kind == KIND_CODE128:
+        return code128_text(syms)
+    if kind == KIND_CODE39:
+        return code39_text(syms)
+    return digits_text(kind, syms) if kind in (KIND_EAN13, KIND_EAN8, KIND_UPCE, KIND_ITF) else None
 
 
 def read_barcodes(codes, syms) -> List[dict]:
     """Device rows int32 [m,8] + symbol values [m,64] -> one dict a barcode, in the rows' order: kind, content, confidence (the share
     of the box's rows across the bars that read), polygon (TL, TR, BR, BL as 8 floats), box, reversed, vertical.  A row whose symbols
-    are no message of its kind is left out."""
+    are no message of its kind is left out.  An EAN-13 whose first digit is 0 is a UPC-A: kind "UPCA", its 12 digits the content.  An ITF
+    of 14 digits whose mod-10 check holds (flags bit 2) has "itf14": True."""
     out = []
     for c, s in zip(codes, syms):
         x0, y0, x1, y1, kind, nsym, rows, flags = (int(v) for v in c)
@@ -144,9 +248,14 @@ def read_barcodes(codes, syms) -> List[dict]:
             continue
         vertical = bool(flags & FLAG_VERTICAL)
         extent = (x1 - x0 + 1) if vertical else (y1 - y0 + 1)
-        out.append({"kind": KINDS[kind], "content": text, "confidence": min(1.0, rows / float(max(extent, 1))),
+        name = KINDS[kind]
+        if kind == KIND_EAN13 and text[0] == "0":
+            name, text = "UPCA", text[1:]
+        out.append({"kind": name, "content": text, "confidence": min(1.0, rows / float(max(extent, 1))),
                     "polygon": [float(v) for v in (x0, y0, x1 + 1, y0, x1 + 1, y1 + 1, x0, y1 + 1)], "box": (x0, y0, x1, y1),
                     "reversed": bool(flags & FLAG_REVERSED), "vertical": vertical})
+        if kind == KIND_ITF and flags & FLAG_ITF14:
+            out[-1]["itf14"] = True
     return out
 
 

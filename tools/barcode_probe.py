@@ -2,9 +2,11 @@
 synth.synth_barcode_page drawn under their text) -> lumina_ocr_barcodes alone (twice: the spread between the two is the run's own
 noise), in the same run on the same pages lumina_ocr_selection_marks (the yardstick: the same run list, then components), and a whole
 pipeline step with barcodes off and on (twice).  HIP events around each stage, median of --reps, with the spread (min, max) of the
-repeats.  One JSON line; needs an MI355X.
+repeats.  With --kinds (names of arch.BARCODE_KINDS, or all) every page also gets one EAN-13 and one ITF-14 strip in its bottom margin
+and the pass is timed on those pages with the default kinds and with the kinds given, each twice: the difference is what the extra
+start filters and decoders cost, reported per row and column read.  One JSON line; needs an MI355X.
 
-    python tools/barcode_probe.py [--reps 20]"""
+    python tools/barcode_probe.py [--reps 20] [--kinds all]"""
 import argparse
 import json
 import sys
@@ -20,6 +22,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--pages", type=int, default=64)
     ap.add_argument("--code-pages", type=int, default=16)
+    ap.add_argument("--kinds", default="", help="comma list of barcode kinds (or all) to time beside the default ones")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -67,6 +70,23 @@ def main():
                barcodes_over_marks=round(t_codes["median"] / t_marks["median"], 3),
                pipeline_delta_ms=round(min(t_on["median"], t_on2["median"]) - min(t_off["median"], t_off2["median"]), 2),
                off_spread_ms=round(abs(t_off["median"] - t_off2["median"]), 2))
+    if args.kinds:
+        mask = arch.barcode_kinds_mask(args.kinds)
+        more = pages.clone()
+        y = h - 70
+        more[:, y - 20:, :, :] = 255                                      # a clear bottom margin for the two strips
+        strip = np.full((50, w, 3), 255, np.uint8)
+        synth.render_linear(strip, 100, 5, "EAN13", "4006381333931", 3, 40)
+        synth.render_linear(strip, 600, 5, "ITF", "00012345678905", 3, 40, ratio=2.5)
+        more[:, y:y + 50] = torch.from_numpy(strip).cuda()
+        t_def, (_, _, c_def) = stage(lambda: eng.barcodes(more))
+        t_k, (_, _, c_k) = stage(lambda: eng.barcodes(more, kinds=mask))
+        t_def2, _ = stage(lambda: eng.barcodes(more))
+        t_k2, _ = stage(lambda: eng.barcodes(more, kinds=mask))
+        extra = min(t_k["median"], t_k2["median"]) - min(t_def["median"], t_def2["median"])
+        res.update(kinds=args.kinds, kinds_mask=mask, strips_default_ms=t_def, strips_default_again_ms=t_def2, strips_kinds_ms=t_k, strips_kinds_again_ms=t_k2,
+                   strips_codes_default=int(c_def.sum()), strips_codes_kinds=int(c_k.sum()), kinds_extra_ms=round(extra, 3),
+                   kinds_extra_ns_per_row=round(extra * 1e6 / (args.pages * (h + w)), 1))
     print(json.dumps(res))
     eng.close()
 
