@@ -318,6 +318,32 @@ int lumina_ocr_qrcodes(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int hei
                        int32_t* data_dev, int32_t* counts_dev, int32_t* finder_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev,
                        void* stream);
 
+/* Data Matrix: ECC 200 symbols (ISO/IEC 16022) of the 21 sizes whose rows fit one 64-bit word (10 x 10 .. 52 x 52, 8 x 18 .. 16 x 48) on
+ * the pages, located, sampled and error-corrected on the device (the host half is lumina_ocr/utils/datamatrix.py).  ink as in
+ * lumina_ocr_table_rules.  Every 8-connected component of the ink has its box, its area and four diagonal extremes (the pixels that
+ * minimise x + y, maximise x - y, maximise x + y, minimise x - y, ties by the smaller y); it is a CANDIDATE when its box sides lie in
+ * 8 min_module .. 52 max_module and 32 area >= w h.  With nothing touching it, the component of a symbol's L finder has three of
+ * its extremes at the L's outer corners at any residual skew; the fourth corner is completed as a parallelogram.  Every rotation
+ * (quarter turns clockwise, the elbow at one extreme and the arms to its neighbours) and every size whose two module sizes lie in
+ * min_module .. max_module and agree within a quarter is tried: a module is the ink at its centre on the affine grid, clear off the
+ * page; the try with the fewest mismatches in the clock tracks and inner clock bars is read (ties: fewer clear modules in the L and
+ * the inner solid bars, smaller area, smaller rotation), at most timing_max mismatches and solid_max clear modules; the `quiet`
+ * rings of modules round the symbol must be clear; the codewords are read through the placement, de-interleaved (52 x 52) and
+ * corrected block by block over GF(256) (0x12D, roots alpha^1 ..), and the syndromes of the corrected block must vanish.
+ * codes_dev int32 [n][max_codes][12] = x0, y0, x1, y1 (the hull of the symbol's corners, inclusive), rows, cols, ndata, corrected
+ * errors, rotation (quarter turns clockwise), timing mismatches, L misses, 0; sorted by (y0, x0, y1, x1, root of the component), rows
+ * past the count untouched; data_dev int32 [n][max_codes][208] = the corrected data codewords, zero behind ndata; counts_dev int32 [n]
+ * = the true number (a list whose count exceeds max_codes is not written); candidate_counts_dev: optional, int32 [n] = the candidates
+ * of each page (a page with more than max_candidates is not read: its count is 0).  mask_in_dev / mask_out_dev as in
+ * lumina_ocr_barcodes.  1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= timing_max, solid_max <= 128, max_candidates 1..1024,
+ * max_codes 1..64, sides 1..65535; defaults in lumina_ocr/arch.py DM_PARAMS.  Not read: 64 x 64 and larger, ECC 000-140,
+ * light-on-dark and mirrored symbols, perspective, a symbol that other ink touches.  Integer arithmetic throughout: the result is
+ * defined bit for bit (tests/dm_reference.py).  Asynchronous; n == 0 is a no-op; bad arguments return a status before anything is
+ * written. */
+int lumina_ocr_datamatrix(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module, int max_module,
+                          int quiet, int timing_max, int solid_max, int max_candidates, int max_codes, int32_t* codes_dev, int32_t* data_dev,
+                          int32_t* counts_dev, int32_t* candidate_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream);
+
 /* ---- page orientation (optional; DESIGN.md: "Page orientation") ----
  * A page is upright after `turn` quarter turns: upright = np.rot90(page, turn) (counter-clockwise).  The three entries below are the
  * device half; which pages get which turn is decided on the host (lumina_ocr/utils/page_orient.py, OcrPipeline.run_oriented).

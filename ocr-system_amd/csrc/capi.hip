@@ -10,6 +10,7 @@
 #include "marks.h"
 #include "barcodes.h"
 #include "qrcodes.h"
+#include "datamatrix.h"
 #include "ops.h"
 #include "orient.h"
 #include "resize.h"
@@ -789,6 +790,35 @@ int lumina_ocr_qrcodes(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int hei
         p.mask_in = mask_in_dev ? reinterpret_cast<const unsigned long long*>(mask_in_dev) + (size_t)b0 * height * nw : nullptr;
         p.mask_out = mask_out_dev ? reinterpret_cast<unsigned long long*>(mask_out_dev) + (size_t)b0 * height * nw : nullptr;
         return hip_rc(h, "qrcodes", qrcodes_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
+    });
+    API_CATCH(h)
+}
+
+int lumina_ocr_datamatrix(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module, int max_module, int quiet,
+                          int timing_max, int solid_max, int max_candidates, int max_codes, int32_t* codes_dev, int32_t* data_dev, int32_t* counts_dev,
+                          int32_t* candidate_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream) {
+    if (!h) return 1;
+    if (n == 0) return 0;
+    if (!pages_dev || !codes_dev || !data_dev || !counts_dev || n < 0) return locr_fail(h, "datamatrix", "bad arguments");
+    if (!dm_params_ok(min_module, max_module, quiet, timing_max, solid_max, max_candidates, max_codes))
+        return locr_fail(h, "datamatrix", "parameters must satisfy 1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= timing_max, solid_max <= 128, "
+                                          "max_candidates 1..1024, max_codes 1..64");
+    if (datamatrix_workspace_bytes(1, height, width, max_candidates, max_codes) == 0) return locr_fail(h, "datamatrix", "bad dimensions (sides 1..65535)");
+    BIND(h);
+    API_TRY
+    // the run list is sized for its worst case (60 bytes per two pixels)
+    const auto ws = [&](int nb) { return datamatrix_workspace_bytes(nb, height, width, max_candidates, max_codes); };
+    const size_t nw = ((size_t)width + 63) / 64;
+    return for_page_groups(h, n, fit_group(h->post_group, n, ws), ws, [&](int b0, int nb) {
+        DmParams p{};
+        p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.H = height; p.W = width;
+        p.threshold = threshold; p.min_module = min_module; p.max_module = max_module; p.quiet = quiet; p.timing_max = timing_max; p.solid_max = solid_max;
+        p.max_candidates = max_candidates; p.max_codes = max_codes;
+        p.codes = codes_dev + (size_t)b0 * max_codes * 12; p.data = data_dev + (size_t)b0 * max_codes * DM_MAX_DATA; p.counts = counts_dev + b0;
+        p.candidate_counts = candidate_counts_dev ? candidate_counts_dev + b0 : nullptr;
+        p.mask_in = mask_in_dev ? reinterpret_cast<const unsigned long long*>(mask_in_dev) + (size_t)b0 * height * nw : nullptr;
+        p.mask_out = mask_out_dev ? reinterpret_cast<unsigned long long*>(mask_out_dev) + (size_t)b0 * height * nw : nullptr;
+        return hip_rc(h, "datamatrix", datamatrix_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
     });
     API_CATCH(h)
 }

@@ -1,0 +1,384 @@
+// Data Matrix (ECC 200; 10 x 10 .. 52 x 52 and the six rectangles) on the GPU (gfx950): the symbols of a page as (x0, y0, x1, y1, rows,
+// cols, ndata, errors, rotation, timing mismatches, L misses, 0) with their corrected data codewords, in a canonical order.
+// Everything is integer and every reduction is order-free (min / max / add / xor, ballots), so the lists equal the sequential
+// definition restated in tests/dm_reference.py.
+//
+// All stream-ordered kernels, no host round trip:
+//   1 ink_mask                          the mask (or the one the caller already has)
+//   2 run_count / row_scan / run_fill / run_merge   mask words -> run list and its 8-connected components (the shared kernels of runs.hip)
+//   3 dm_init, dm_accum   a run is its own area and its own four diagonal extremes (min x + y, max x - y, max x + y, min x - y, ties by
+//                 the smaller y: one 64-bit word (key, y, x) each, so that one atomic min / max keeps the tie rule exact); every run
+//                 learns its root, and box, area and extremes are accumulated there
+//   4 dm_candidates  one wave per row, lanes over the row's roots: the box and area filter -> counted, gathered per page
+//   5 dm_decode   one wave per (page, candidate): every (size, rotation) try that is in reach (wave-uniform) is scored with lanes
+//                 over the modules of its solid and clock rows and columns; for the kept try lane r samples module row r on the
+//                 affine grid as one 64-bit word; the quiet rings; lanes gather the codewords through the placement table from the
+//                 rows in LDS; per block the decoder of rs_gf256.h.  Every loop has a constant bound, every table, LDS and page index
+//                 is clamped, and no wave waits for another (a work-group is one wave)
+//   6 dm_output   one work-group per page: valid candidates counted, gathered, rank-sorted by (y0, x0, y1, x1, root)
+#include "datamatrix.h"
+#include "dm_tables.h"
+#include "rs_gf256.h"
+#include "runs.h"
+
+namespace {
+
+typedef unsigned long long u64;
+typedef long long i64;
+
+constexpr int RES_INTS = 16;           // a candidate's result: y0, x0, y1, x1, root, rows, cols, ndata, errors, rotation, timing, misses, 0, valid
+constexpr int DM_MAX_TOTAL = 288, DM_MAX_BLOCK = 242, DM_MAX_EC = 68, DM_MAX_NB = 2;
+constexpr int DM_RAW = 320, DM_BLK = 256;   // LDS arrays: the codewords of a symbol, of a block (multiples of 64)
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// the four extremes of one run as packed words: min types hold y, max types 65535 - y below the key, so ties go to the smaller y
+__device__ __forceinline__ void run_extremes(int xs, int xe, int y, u64 (&e)[4]) {
+    e[0] = ((u64)(unsigned)(xs + y) << 32) | ((u64)y << 16) | (u64)xs;
+    e[1] = ((u64)(unsigned)(xe - y + 65536) << 32) | ((u64)(65535 - y) << 16) | (u64)xe;
+    e[2] = ((u64)(unsigned)(xe + y) << 32) | ((u64)(65535 - y) << 16) | (u64)xe;
+    e[3] = ((u64)(unsigned)(xs - y + 65536) << 32) | ((u64)y << 16) | (u64)xs;
+}
+
+// 3a: a run's own length and extremes are the start of its component's
+__global__ __launch_bounds__(256) void dm_init_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* area, u64* ext, int H,
+                                                      size_t runcap, int rows_total) {
+    int pg, row, lane;
+    if (!row_wave(H, rows_total, pg, row, lane)) return;
+    const int* ro = runoff + (size_t)pg * (H + 1);
+    const size_t rb = (size_t)pg * runcap;
+    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
+        const int xs = rxs[rb + id], xe = rxe[rb + id];
+        area[rb + id] = xe - xs + 1;
+        u64 e[4];
+        run_extremes(xs, xe, row, e);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ext[(rb + id) * 4 + j] = e[j];
+    }
+}
+
+// 3b: parent = root; the root's box, area and extremes grow to the component's
+__global__ __launch_bounds__(256) void dm_accum_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* parent, int4* box, int* area,
+                                                       u64* ext, int H, size_t runcap, int rows_total) {
+    int pg, row, lane;
+    if (!row_wave(H, rows_total, pg, row, lane)) return;
+    const int* ro = runoff + (size_t)pg * (H + 1);
+    const size_t rb = (size_t)pg * runcap;
+    int* P = parent + rb;
+    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
+        const int p = P[id];
+        if (p == id) continue;
+        const int root = uf_find(P, p);
+        if (root != p) P[id] = root;   // concurrent compressions only ever replace a parent by an ancestor
+        const int xs = rxs[rb + id], xe = rxe[rb + id];
+        int* b = reinterpret_cast<int*>(box + rb + root);
+        if (xs < __atomic_load_n(b + 0, __ATOMIC_RELAXED)) atomicMin(b + 0, xs);
+        if (xe > __atomic_load_n(b + 1, __ATOMIC_RELAXED)) atomicMax(b + 1, xe);
+        if (row > __atomic_load_n(b + 3, __ATOMIC_RELAXED)) atomicMax(b + 3, row);
+        atomicAdd(area + rb + root, xe - xs + 1);
+        u64 e[4];
+        run_extremes(xs, xe, row, e);
+        u64* x = ext + (rb + root) * 4;
+        if (e[0] < __atomic_load_n(x + 0, __ATOMIC_RELAXED)) atomicMin(x + 0, e[0]);
+        if (e[1] > __atomic_load_n(x + 1, __ATOMIC_RELAXED)) atomicMax(x + 1, e[1]);
+        if (e[2] > __atomic_load_n(x + 2, __ATOMIC_RELAXED)) atomicMax(x + 2, e[2]);
+        if (e[3] < __atomic_load_n(x + 3, __ATOMIC_RELAXED)) atomicMin(x + 3, e[3]);
+    }
+}
+
+// 4: cands [B][max_candidates] = the roots that pass the box and area filter
+__global__ __launch_bounds__(256) void dm_candidates_kernel(const int* runoff, const int* parent, const int4* box, const int* area, int H, size_t runcap,
+                                                            int min_module, int max_module, int max_candidates, int* ncand, int* cands, int rows_total) {
+    int pg, row, lane;
+    if (!row_wave(H, rows_total, pg, row, lane)) return;
+    const int* ro = runoff + (size_t)pg * (H + 1);
+    const size_t rb = (size_t)pg * runcap;
+    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
+        if (parent[rb + id] != id) continue;
+        const int4 bx = box[rb + id];   // x0, x1, y0, y1
+        const int w = bx.y - bx.x + 1, h = bx.w - bx.z + 1;
+        if (w < 8 * min_module || h < 8 * min_module || w > 52 * max_module || h > 52 * max_module) continue;
+        if (32 * (i64)area[rb + id] < (i64)w * h) continue;
+        const int idx = atomicAdd(&ncand[pg], 1);
+        if (idx < max_candidates) cands[(size_t)pg * max_candidates + idx] = id;
+    }
+}
+
+// the affine grid of a try: O the L's elbow, U up its upright (R rows), V along its foot (C columns), doubled pixel coordinates
+struct DmGrid { int ox2, oy2, vxr, vyr, uxc, uyc, R, C; unsigned den; };
+
+// module (row r, col c): the ink at the pixel of its centre; off the page reads clear.  Every term stays below 2^30: the arms of a
+// try in reach are at most 2 * 52 * 64 doubled pixels and the page's sides at most 65535.
+__device__ __forceinline__ int dm_sample(const u64* mpage, int H, int W, int nw, const DmGrid& g, int r, int c) {
+    const int nx = g.ox2 + g.vxr * (2 * c + 1) + g.uxc * (2 * g.R - 2 * r - 1), ny = g.oy2 + g.vyr * (2 * c + 1) + g.uyc * (2 * g.R - 2 * r - 1);
+    if (nx < 0 || ny < 0) return 0;
+    const int px = (int)((unsigned)nx / g.den), py = (int)((unsigned)ny / g.den);
+    if (px >= W || py >= H) return 0;
+    return (int)((mpage[(size_t)py * nw + (px >> 6)] >> (px & 63)) & 1ull);
+}
+
+struct DmLds {
+    u64 rows[64];
+    unsigned char raw[DM_RAW];
+    RsLds<DM_BLK, DM_MAX_EC> rs;
+};
+
+// 5: one wave per (page, candidate): res [B][max_candidates][RES_INTS], resdata [B][max_candidates][DM_MAX_DATA]
+__global__ __launch_bounds__(64) void dm_decode_kernel(const u64* mask, const int* cands, const int* ncand, const u64* ext, int H, int W, int nw, size_t runcap,
+                                                       int max_candidates, int min_module, int max_module, int quiet, int timing_max, int solid_max, int* res,
+                                                       unsigned char* resdata) {
+    __shared__ DmLds s;
+    const int pg = blockIdx.y, a = blockIdx.x, lane = threadIdx.x;
+    const int nc_page = ncand[pg];
+    if (nc_page > max_candidates || a >= nc_page || a >= DM_MAX_CANDIDATES) return;
+    const u64* mpage = mask + (size_t)pg * H * nw;
+    const int root = clampi(cands[(size_t)pg * max_candidates + a], 0, (int)runcap - 1);
+    rs_load_tables(s.rs, DM_EXP, DM_LOG, lane);
+    // the outer corners of the four extremes, doubled
+    int cx[4], cy[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const u64 e = ext[((size_t)pg * runcap + root) * 4 + j];
+        const int x = (int)(e & 0xffffull), yf = (int)((e >> 16) & 0xffffull), y = (j == 0 || j == 3) ? yf : 65535 - yf;
+        cx[j] = 2 * (x + ((j == 1 || j == 2) ? 1 : 0));
+        cy[j] = 2 * (y + (j >= 2 ? 1 : 0));
+    }
+    // every (size, rotation) in reach: the smallest (timing mismatches, L misses, R C, k, size)
+    i64 best = -1;
+    const i64 lo_m = (i64)min_module, hi_m = (i64)max_module;
+#pragma unroll 1
+    for (int sz = 0; sz < DM_NUM_SIZES; ++sz) {
+        const int R = DM_SIZES[sz * 8 + 0], C = DM_SIZES[sz * 8 + 1], nr = clampi(DM_SIZES[sz * 8 + 4], 1, 2), nc = clampi(DM_SIZES[sz * 8 + 5], 1, 2);
+        const int RH = R / nr, RW = C / nc;
+#pragma unroll 1
+        for (int k = 0; k < 4; ++k) {
+            const int ox = cx[(k + 3) & 3], oy = cy[(k + 3) & 3];
+            const int ux = cx[k] - ox, uy = cy[k] - oy, vx = cx[(k + 2) & 3] - ox, vy = cy[(k + 2) & 3] - oy;
+            const i64 lu = (i64)ux * ux + (i64)uy * uy, lv = (i64)vx * vx + (i64)vy * vy;
+            const i64 ulo = 2 * R * lo_m, uhi = 2 * R * hi_m, vlo = 2 * C * lo_m, vhi = 2 * C * hi_m;
+            if (lu < ulo * ulo || lu > uhi * uhi || lv < vlo * vlo || lv > vhi * vhi) continue;
+            const i64 qa = lu * C * C, qb = lv * R * R;
+            if (16 * (qa > qb ? qa : qb) > 25 * (qa < qb ? qa : qb)) continue;
+            DmGrid g;
+            g.R = R; g.C = C; g.den = 4u * R * C;
+            g.ox2 = ox * 2 * R * C; g.oy2 = oy * 2 * R * C; g.vxr = vx * R; g.vyr = vy * R; g.uxc = ux * C; g.uyc = uy * C;
+            int misses = 0, timing = 0;
+            for (int i = 0; i < 4; ++i) {   // the regions' clock rows (even i) and solid rows (odd i)
+                if (i >= 2 * nr) break;
+                const int r = (i >> 1) * RH + ((i & 1) ? RH - 1 : 0);
+                const bool on = lane < C;
+                const int v = on ? dm_sample(mpage, H, W, nw, g, r, lane) : 0;
+                const int lc = lane >= RW ? lane - RW : lane;
+                const bool solid = (i & 1) || lc == 0;
+                misses += __popcll(__ballot(on && solid && !v));
+                timing += __popcll(__ballot(on && !solid && v != ((lane & 1) ^ 1)));
+            }
+            for (int j = 0; j < 4; ++j) {   // the regions' solid columns (even j) and clock columns (odd j), without the rows above
+                if (j >= 2 * nc) break;
+                const int c = (j >> 1) * RW + ((j & 1) ? RW - 1 : 0);
+                const int lr = lane >= RH ? lane - RH : lane;
+                const bool on = lane < R && lr != 0 && lr != RH - 1;
+                const int v = on ? dm_sample(mpage, H, W, nw, g, lane, c) : 0;
+                misses += __popcll(__ballot(on && !(j & 1) && !v));
+                timing += __popcll(__ballot(on && (j & 1) && v != (lane & 1)));
+            }
+            const i64 key = ((i64)timing << 32) | ((i64)misses << 20) | ((i64)(R * C) << 8) | (i64)(k << 5) | (i64)sz;
+            if (best < 0 || key < best) best = key;
+        }
+    }
+    if (best < 0) return;
+    const int timing = (int)(best >> 32), misses = (int)((best >> 20) & 0xfff), k = (int)((best >> 5) & 3), sz = clampi((int)(best & 31), 0, DM_NUM_SIZES - 1);
+    if (timing > timing_max || misses > solid_max) return;
+    const int R = DM_SIZES[sz * 8 + 0], C = DM_SIZES[sz * 8 + 1], ndata = DM_SIZES[sz * 8 + 2], ncheck = DM_SIZES[sz * 8 + 3];
+    const int nb = clampi(DM_SIZES[sz * 8 + 6], 1, DM_MAX_NB), total = ndata + ncheck, ec = ncheck / nb;
+    if (total > DM_MAX_TOTAL || ndata > DM_MAX_DATA || ec < 2 || ec > DM_MAX_EC || (ndata + nb - 1) / nb + ec > DM_MAX_BLOCK) return;   // (the tables never say so)
+    const int ox = cx[(k + 3) & 3], oy = cy[(k + 3) & 3];
+    const int ux = cx[k] - ox, uy = cy[k] - oy, vx = cx[(k + 2) & 3] - ox, vy = cy[(k + 2) & 3] - oy;
+    DmGrid g;
+    g.R = R; g.C = C; g.den = 4u * R * C;
+    g.ox2 = ox * 2 * R * C; g.oy2 = oy * 2 * R * C; g.vxr = vx * R; g.vyr = vy * R; g.uxc = ux * C; g.uyc = uy * C;
+    // the quiet rings
+    bool dirty = false;
+    for (int q = 1; q <= DM_MAX_QUIET; ++q) {
+        if (q > quiet) break;
+        const int t = lane - q;
+        if (t < C + q) dirty = dirty || dm_sample(mpage, H, W, nw, g, -q, t) || dm_sample(mpage, H, W, nw, g, R - 1 + q, t);
+        if (t < R + q) dirty = dirty || dm_sample(mpage, H, W, nw, g, t, -q) || dm_sample(mpage, H, W, nw, g, t, C - 1 + q);
+    }
+    if (__ballot(dirty)) return;
+    // lane r samples module row r
+    u64 row = 0;
+    if (lane < R)
+        for (int c = 0; c < 52; ++c)
+            if (c < C) row |= (u64)dm_sample(mpage, H, W, nw, g, lane, c) << c;
+    s.rows[lane] = row;
+    __syncthreads();
+    // codewords in placement order
+    const int poff = DM_PLACE_OFF[sz];
+#pragma unroll 1
+    for (int i = lane; i < DM_RAW; i += 64) {
+        int val = 0;
+        if (i < total) {
+            for (int bit = 0; bit < 8; ++bit) {
+                const int at = poff + 8 * i + bit;
+                const unsigned p = DM_PLACE[at < DM_PLACE_N ? at : DM_PLACE_N - 1];
+                val = (val << 1) | (int)((s.rows[(p >> 6) & 63] >> (p & 63)) & 1ull);
+            }
+        }
+        s.raw[i] = (unsigned char)val;
+    }
+    __syncthreads();
+    unsigned char* od = resdata + ((size_t)pg * max_candidates + a) * DM_MAX_DATA;
+    int errors = 0;
+    for (int blk = 0; blk < DM_MAX_NB; ++blk) {
+        if (blk >= nb) break;
+        const int nd = (ndata - blk + nb - 1) / nb, len = nd + ec;   // block blk takes every nb-th codeword from blk on
+#pragma unroll
+        for (int p0 = 0; p0 < DM_BLK; p0 += 64) {
+            const int p = p0 + lane;
+            if (p < len) s.rs.blk[p] = s.raw[clampi(p < nd ? p * nb + blk : ndata + (p - nd) * nb + blk, 0, DM_RAW - 1)];
+        }
+        __syncthreads();
+        const int got = rs_correct_block(s.rs, len, ec, 1, lane);
+        if (got < 0) return;
+        errors += got;
+#pragma unroll
+        for (int p0 = 0; p0 < DM_BLK; p0 += 64) {
+            const int p = p0 + lane;
+            if (p < nd && p * nb + blk < DM_MAX_DATA) od[p * nb + blk] = s.rs.blk[p];
+        }
+        __syncthreads();
+    }
+    if (lane == 0) {
+        // the hull: the parallelogram O, O + U, O + V, O + U + V (every coordinate is even)
+        int x0 = 0, x1 = 0, y0 = 0, y1 = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int qx = (ox + ((c & 1) ? ux : 0) + ((c & 2) ? vx : 0)) >> 1, qy = (oy + ((c & 1) ? uy : 0) + ((c & 2) ? vy : 0)) >> 1;
+            x0 = c == 0 || qx < x0 ? qx : x0; x1 = c == 0 || qx > x1 ? qx : x1;
+            y0 = c == 0 || qy < y0 ? qy : y0; y1 = c == 0 || qy > y1 ? qy : y1;
+        }
+        int* o = res + ((size_t)pg * max_candidates + a) * RES_INTS;
+        o[0] = clampi(y0, 0, H - 1); o[1] = clampi(x0, 0, W - 1); o[2] = clampi(y1 - 1, 0, H - 1); o[3] = clampi(x1 - 1, 0, W - 1); o[4] = root;
+        o[5] = R; o[6] = C; o[7] = ndata; o[8] = errors; o[9] = k; o[10] = timing; o[11] = misses; o[12] = 0; o[13] = 1;
+    }
+}
+
+// 6: tmp [B][max_codes][6] = y0, x0, y1, x1, root, slot
+__global__ __launch_bounds__(256) void dm_output_kernel(const int* res_all, const unsigned char* resdata_all, const int* ncand, int max_candidates, int max_codes,
+                                                        int* tmp_all, int* counts, int* codes, int* data, int* candidate_counts) {
+    __shared__ int s_key[DM_MAX_CODES * 5];
+    __shared__ int s_n;
+    const int pg = blockIdx.x;
+    const int nc = ncand[pg];
+    const int* res = res_all + (size_t)pg * max_candidates * RES_INTS;
+    int* tmp = tmp_all + (size_t)pg * max_codes * 6;
+    if (threadIdx.x == 0) {
+        s_n = 0;
+        if (candidate_counts) candidate_counts[pg] = nc;
+    }
+    __syncthreads();
+    const int lim = nc > max_candidates ? 0 : nc;   // a page with too many candidates is not read
+    for (int a = threadIdx.x; a < lim; a += 256) {
+        const int* r = res + a * RES_INTS;
+        if (r[13] != 1) continue;
+        const int idx = atomicAdd(&s_n, 1);
+        if (idx >= max_codes) continue;
+        int* o = tmp + idx * 6;
+        o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3]; o[4] = r[4]; o[5] = a;
+    }
+    __syncthreads();
+    const int n = s_n;
+    if (threadIdx.x == 0) counts[pg] = n;
+    if (n > max_codes) return;   // overflow: the count is all that is reported
+    int* out = codes + (size_t)pg * max_codes * 12;
+    int* odat = data + (size_t)pg * max_codes * DM_MAX_DATA;
+    const unsigned char* rd = resdata_all + (size_t)pg * max_candidates * DM_MAX_DATA;
+    rank_sort<5>(s_key, tmp, 6, n, [=](int i, int rank, const int (&k)[5]) {
+        const int slot = clampi(tmp[i * 6 + 5], 0, max_candidates - 1);
+        const int* r = res + slot * RES_INTS;
+        int* o = out + (size_t)rank * 12;
+        o[0] = k[1]; o[1] = k[0]; o[2] = k[3]; o[3] = k[2];
+        for (int j = 0; j < 8; ++j) o[4 + j] = r[5 + j];
+        const int nd = r[7];
+        for (int j = 0; j < DM_MAX_DATA; ++j) odat[(size_t)rank * DM_MAX_DATA + j] = j < nd ? rd[(size_t)slot * DM_MAX_DATA + j] : 0;
+    });
+}
+
+}  // namespace
+
+// the workspace's regions: one layout sizes it (datamatrix_workspace_bytes) and carves it (datamatrix_launch)
+struct DmWorkspace {
+    unsigned long long* mask; int* runoff; unsigned short *rxs, *rxe; int* parent; int4* box; int* area; unsigned long long* ext;
+    int* ncand; int* cands; int* res; unsigned char* resdata; int* tmp;
+};
+static DmWorkspace datamatrix_layout(Arena& a, int B, int H, int W, int max_candidates, int max_codes) {
+    const size_t runcap = run_cap(H, W), nw = (W + 63) / 64;
+    DmWorkspace w;
+    w.mask = a.take<unsigned long long>((size_t)B * H * nw);
+    w.runoff = a.take<int>((size_t)B * (H + 1));   // run counts -> offsets
+    w.rxs = a.take<unsigned short>((size_t)B * runcap); w.rxe = a.take<unsigned short>((size_t)B * runcap);
+    w.parent = a.take<int>((size_t)B * runcap);
+    w.box = a.take<int4>((size_t)B * runcap);      // at a root: x0, x1, y0, y1 of its component
+    w.area = a.take<int>((size_t)B * runcap);      // at a root: its component's ink
+    w.ext = a.take<unsigned long long>((size_t)B * runcap * 4);   // at a root: its component's four diagonal extremes, packed
+    w.ncand = a.take<int>((size_t)B);
+    w.cands = a.take<int>((size_t)B * max_candidates);
+    w.res = a.take<int>((size_t)B * max_candidates * RES_INTS);
+    w.resdata = a.take<unsigned char>((size_t)B * max_candidates * DM_MAX_DATA);
+    w.tmp = a.take<int>((size_t)B * max_codes * 6);
+    return w;
+}
+
+static bool datamatrix_args_ok(int B, int H, int W, int max_candidates, int max_codes) {
+    if (B <= 0 || H <= 0 || W <= 0 || H > 65535 || W > 65535 || max_codes < 1 || max_codes > DM_MAX_CODES || max_candidates < 1 ||
+        max_candidates > DM_MAX_CANDIDATES)
+        return false;
+    return (size_t)B * H < (1ull << 31) && run_cap(H, W) < (1ull << 31);
+}
+
+bool dm_params_ok(int min_module, int max_module, int quiet, int timing_max, int solid_max, int max_candidates, int max_codes) {
+    return min_module >= 1 && max_module >= min_module && max_module <= DM_MAX_MODULE && quiet >= 0 && quiet <= DM_MAX_QUIET && timing_max >= 0 &&
+           timing_max <= DM_MAX_TIMING && solid_max >= 0 && solid_max <= DM_MAX_TIMING && max_candidates >= 1 && max_candidates <= DM_MAX_CANDIDATES &&
+           max_codes >= 1 && max_codes <= DM_MAX_CODES;
+}
+
+size_t datamatrix_workspace_bytes(int B, int H, int W, int max_candidates, int max_codes) {
+    if (!datamatrix_args_ok(B, H, W, max_candidates, max_codes)) return 0;
+    Arena a;
+    datamatrix_layout(a, B, H, W, max_candidates, max_codes);
+    return a.off;
+}
+
+hipError_t datamatrix_launch(const DmParams& p, void* workspace, size_t ws_bytes, hipStream_t st) {
+    const int B = p.B, H = p.H, W = p.W;
+    if (!datamatrix_args_ok(B, H, W, p.max_candidates, p.max_codes) ||
+        !dm_params_ok(p.min_module, p.max_module, p.quiet, p.timing_max, p.solid_max, p.max_candidates, p.max_codes))
+        return hipErrorInvalidValue;
+    if (!p.rgb || !p.codes || !p.data || !p.counts) return hipErrorInvalidValue;
+    Arena a(workspace, ws_bytes);
+    const DmWorkspace w = datamatrix_layout(a, B, H, W, p.max_candidates, p.max_codes);
+    if (a.overflow) return hipErrorOutOfMemory;
+    const int nw = (W + 63) / 64;
+    const size_t runcap = run_cap(H, W);
+    const unsigned long long* mask;
+    hipError_t e;
+    if ((e = hipMemsetAsync(w.ncand, 0, sizeof(int) * (size_t)B, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.res, 0, sizeof(int) * (size_t)B * p.max_candidates * RES_INTS, st)) != hipSuccess) return e;
+    if ((e = ink_mask_resolve(p.rgb, p.mask_in, p.mask_out, w.mask, B, H, W, p.threshold, st, &mask)) != hipSuccess) return e;
+    const int rows = B * H;
+    const dim3 grows = row_wave_grid(rows);
+    run_count_launch(mask, w.runoff, B, H, nw, st);
+    row_scan_launch(w.runoff, nullptr, B, H, st);
+    run_fill_launch(mask, w.runoff, w.rxs, w.rxe, w.parent, w.box, B, H, nw, runcap, st);
+    run_merge_launch(w.runoff, w.rxs, w.rxe, w.parent, B, H, runcap, st);
+    hipLaunchKernelGGL(dm_init_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.area, w.ext, H, runcap, rows);
+    hipLaunchKernelGGL(dm_accum_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.box, w.area, w.ext, H, runcap, rows);
+    hipLaunchKernelGGL(dm_candidates_kernel, grows, dim3(256), 0, st, w.runoff, w.parent, w.box, w.area, H, runcap, p.min_module, p.max_module,
+                       p.max_candidates, w.ncand, w.cands, rows);
+    hipLaunchKernelGGL(dm_decode_kernel, dim3(p.max_candidates, B), dim3(64), 0, st, mask, w.cands, w.ncand, w.ext, H, W, nw, runcap, p.max_candidates,
+                       p.min_module, p.max_module, p.quiet, p.timing_max, p.solid_max, w.res, w.resdata);
+    hipLaunchKernelGGL(dm_output_kernel, dim3(B), dim3(256), 0, st, w.res, w.resdata, w.ncand, p.max_candidates, p.max_codes, w.tmp, p.counts, p.codes, p.data,
+                       p.candidate_counts);
+    return hipGetLastError();
+}

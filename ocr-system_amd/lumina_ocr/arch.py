@@ -519,6 +519,19 @@ def barcode_kinds_mask(names) -> int:
 QR_PARAMS = dict(threshold=BARCODE_PARAMS["threshold"], min_module=3, max_module=24, quiet=2, centre_tol=8, ring_tol=12, timing_max=3,
                  max_finders=64, max_codes=16)
 
+# Data Matrix (lumina_ocr_datamatrix + utils/datamatrix.py, definition restated in tests/dm_reference.py): ink at the barcodes'
+# threshold so that one mask serves the three passes.  A candidate is a component whose box sides lie in 8 min_module .. 52 max_module
+# with 32 area >= w h (the L alone is 3.8 % of a 52 x 52 symbol).  quiet = 1 module, the standard's own.  timing_max = 3 mismatches in
+# the clock tracks and solid_max = 3 clear modules in the L and the inner solid bars: a clean symbol has none of either, a wrong size
+# or orientation about half of its clock modules, a letter L or a frame all of the dark or all of the light ones (at least 8), and
+# Reed-Solomon carries the rest of the rejection.  Changed against the issue's outline, which capped max_candidates at 64: the box and
+# area filter lets every glyph of 24 px and more through, the benchmark's A4 text pages have 50 candidates on average and up to 98,
+# and a page above the capacity is not read at all; nothing in the pass needs a lane per candidate (the decode kernel's grid is
+# max_candidates waves a page, all but the candidates' exit after one load), so the capacity is max_candidates <= 1024 and 256 by
+# default.  max_codes <= 64.
+DM_PARAMS = dict(threshold=BARCODE_PARAMS["threshold"], min_module=3, max_module=24, quiet=1, timing_max=3, solid_max=3, max_candidates=256,
+                 max_codes=16)
+
 # Page orientation (lumina_ocr_page_quarter / _page_turn / _page_vote + utils/page_orient.py): ink as above; a page is sideways when the
 # energy of its column profile exceeds `ratio` times that of its row profile (text lines make the profile across them jagged), and an
 # upright-or-upside-down page is upside-down when it has at least min_lines lines and the classifier flips more than half of them.

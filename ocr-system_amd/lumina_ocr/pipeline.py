@@ -44,6 +44,9 @@ class PageDetections:
     qrcodes: Optional[np.ndarray] = None      # int32 [m, 12] x0, y0, x1, y1, version, level, mask, ndata, errors, rotation, format distance,
                                               # timing mismatches of the page's QR symbols: OcrPipeline(qrcodes=True) only (empty on overflow)
     qr_data: Optional[np.ndarray] = None      # int32 [m, 288] their corrected data codewords (utils/qrcodes.py turns them into text)
+    datamatrix: Optional[np.ndarray] = None   # int32 [m, 12] x0, y0, x1, y1, rows, cols, ndata, errors, rotation, timing mismatches, L misses, 0
+                                              # of the page's Data Matrix symbols: OcrPipeline(datamatrix=True) only (empty on overflow)
+    dm_data: Optional[np.ndarray] = None      # int32 [m, 208] their corrected data codewords (utils/datamatrix.py turns them into text)
     word_quads: Optional[np.ndarray] = None   # int32 [n, 40, 8] the words of every line from the CTC alignment, each in its line's corner
                                               # order: OcrPipeline(word_boxes=True) only, like the three below
     word_spans: Optional[np.ndarray] = None   # int32 [n, 40, 2] first character in texts[i], character count
@@ -80,6 +83,7 @@ class _Pending:
     marks_host: Optional[list] = None   # marks: pinned copies of marks, counts (round_marks: and of round marks, round counts)
     barcodes_host: Optional[list] = None   # barcodes: pinned copies of codes, symbol values, counts
     qrcodes_host: Optional[list] = None    # qrcodes: pinned copies of codes, data codewords, counts
+    datamatrix_host: Optional[list] = None   # datamatrix: pinned copies of codes, data codewords, counts
     words_host: Optional[list] = None   # word_boxes: pinned copies of word quads, spans, scores, counts
 
 
@@ -89,7 +93,8 @@ class OcrPipeline:
                  tables: bool = False, table_params: Optional[dict] = None, marks: bool = False, mark_params: Optional[dict] = None,
                  page_orient: bool = False, page_orient_params: Optional[dict] = None, word_boxes: bool = False, round_marks: bool = False,
                  round_mark_params: Optional[dict] = None, barcodes: bool = False, barcode_params: Optional[dict] = None,
-                 qrcodes: bool = False, qr_params: Optional[dict] = None, barcode_kinds=arch.BARCODE_KINDS_DEFAULT):
+                 qrcodes: bool = False, qr_params: Optional[dict] = None, barcode_kinds=arch.BARCODE_KINDS_DEFAULT,
+                 datamatrix: bool = False, dm_params: Optional[dict] = None):
         """recognizer: "crnn" (CRNN-MobileNetV3 + BiLSTM, engine.load_rec) or "svtr" (SVTR, engine.load_svtr).
         angle_cls: PaddleOCR's use_angle_cls — every line is classified 0 / 180 degrees (engine.load_cls) before recognition, and a line
         read as 180 with probability > cls_thresh is recognised turned; boxes and reading order are unchanged.  Per-line labels are
@@ -108,6 +113,9 @@ class OcrPipeline:
         beside the two) or "all"; an unknown name is a ValueError.
         qrcodes: the QR symbols (Model 2, versions 1-10) of the processed pages (engine.qrcodes, parameters arch.QR_PARAMS or qr_params)
         come back as PageDetections.qrcodes / qr_data; they stay on their rank too, and with a gather the pass is not run.
+        datamatrix: the Data Matrix symbols (ECC 200, up to 52 x 52) of the processed pages (engine.datamatrix, parameters arch.DM_PARAMS
+        or dm_params) come back as PageDetections.datamatrix / dm_data; the pass runs behind the QR pass and takes the ink mask the
+        earlier passes made at its threshold; with a gather it is not run.
         page_orient: run_oriented() finds for every page the quarter turns that make it upright (ink profiles for sideways pages,
         parameters arch.PAGE_ORIENT_PARAMS or page_orient_params; the line classifier's majority for upside-down ones, so it needs
         engine.load_cls like angle_cls), turns the raw page on the device and runs the stages below on the upright page.  run /
@@ -143,6 +151,8 @@ class OcrPipeline:
         self._barcode_kinds_arg = None if self.barcode_kinds == arch.barcode_kinds_mask(arch.BARCODE_KINDS_DEFAULT) else self.barcode_kinds
         self.qrcodes = bool(qrcodes)
         self.qr_params = dict(arch.QR_PARAMS if qr_params is None else qr_params)
+        self.datamatrix = bool(datamatrix)
+        self.dm_params = dict(arch.DM_PARAMS if dm_params is None else dm_params)
         self.page_orient = bool(page_orient)
         self.word_boxes = bool(word_boxes)
         self.space_id = self.charset.index(" ") if " " in self.charset else -1   # the class words split on (-1: a line is one word)
@@ -183,20 +193,41 @@ class OcrPipeline:
 
     def submit_recognize(self, processed, boxes, scores, counts) -> "_Pending":
         """One host sync (box counts), then crop + CRNN + CTC and the device->pinned-host copies are enqueued. -> pending."""
-        rules, marks, codes, qrs = self._submit_page_analysis(processed)   # enqueued before the sync below: it runs while the host waits for the box counts
+        rules, marks, codes, qrs, dms = self._submit_page_analysis(processed)   # enqueued before the sync below: it runs while the host waits for the box counts
         counts_h = counts.cpu().numpy()  # the one host sync of the pipeline
-        return self._submit_lines(processed, boxes, scores, counts_h, rules, marks, barcodes=codes, qrcodes=qrs)
+        return self._submit_lines(processed, boxes, scores, counts_h, rules, marks, barcodes=codes, qrcodes=qrs, datamatrix=dms)
+
+    def _submit_datamatrix(self, processed, mask, mask_at):
+        """Enqueue the Data Matrix pass -> (codes, data codewords, counts) device tensors; mask: the ink mask an earlier pass made at the
+        threshold mask_at, or None."""
+        dp = self.dm_params
+        return self.eng.datamatrix(processed, mask_in=mask if mask is not None and mask_at == dp["threshold"] else None, **dp)
 
     def _submit_page_analysis(self, processed):
-        """Enqueue the table rules, selection marks, barcodes and QR codes of the processed pages -> (rules, marks, codes, qr codes), None
-        where a pass is off.  The barcode pass takes the ink mask from the marks or the tables call when that call ran on its own at the
-        barcodes' threshold; the joint rules-and-marks call hands no mask out, so behind it the barcode pass computes its own.  The QR
-        pass takes the mask the same way, or from the barcode pass when that one computed it at the QR threshold."""
+        """Enqueue the table rules, selection marks, barcodes, QR codes and Data Matrix symbols of the processed pages -> (rules, marks,
+        codes, qr codes, data matrix symbols), None where a pass is off.  The barcode pass takes the ink mask from the marks or the tables
+        call when that call ran on its own at the barcodes' threshold; the joint rules-and-marks call hands no mask out, so behind it the barcode pass computes its own.  The QR
+        pass takes the mask the same way, or from the barcode pass when that one computed it at the QR threshold.  The Data Matrix pass
+        runs last, on the mask of whichever earlier pass made one at its threshold (the barcode or the QR pass hands its own out)."""
         on = self.gather is None
+        if self.datamatrix and on:   # behind the other passes, with the mask they made when it is the Data Matrix pass's threshold too
+            want = (self.barcode_params["threshold"] if self.barcodes else self.qr_params["threshold"] if self.qrcodes else self.dm_params["threshold"])
+            rules, marks, mask = self._submit_rules_marks(processed, mask_at=want)
+            codes = qrs = None
+            if self.barcodes:
+                codes = self._submit_barcodes(processed, mask, mask_out=mask is None)
+                if mask is None:
+                    codes, mask = codes[:3], codes[3]
+            if self.qrcodes:
+                qmask = mask if self.qr_params["threshold"] == want else None
+                qrs = self.eng.qrcodes(processed, mask_in=qmask, debug=mask is None, **self.qr_params)
+                if mask is None:
+                    qrs, mask, want = qrs[:3], qrs[3], self.qr_params["threshold"]
+            return rules, marks, codes, qrs, self._submit_datamatrix(processed, mask, want)
         want = self.barcode_params["threshold"] if self.barcodes and on else (self.qr_params["threshold"] if self.qrcodes and on else None)
         rules, marks, mask = self._submit_rules_marks(processed, mask_at=want)
         if not (self.qrcodes and on):
-            return rules, marks, self._submit_barcodes(processed, mask), None
+            return rules, marks, self._submit_barcodes(processed, mask), None, None
         if self.barcodes and self.qr_params["threshold"] == want:
             codes = self._submit_barcodes(processed, mask, mask_out=mask is None)
             if mask is None:
@@ -204,7 +235,7 @@ class OcrPipeline:
         else:
             codes = self._submit_barcodes(processed, mask)
             mask = mask if self.qr_params["threshold"] == want else None
-        return rules, marks, codes, self.eng.qrcodes(processed, mask_in=mask, **self.qr_params)
+        return rules, marks, codes, self.eng.qrcodes(processed, mask_in=mask, **self.qr_params), None
 
     def _submit_barcodes(self, processed, mask_in=None, mask_out: bool = False):
         """Enqueue the barcode pass of the processed pages -> (codes, symbol values, counts) device tensors, or None; with mask_out the
@@ -261,7 +292,7 @@ class OcrPipeline:
         page_idx = torch.from_numpy(page_h.astype(np.int32)).to(boxes.device, non_blocking=True)
         return quads, det_sc, page_idx
 
-    def _submit_lines(self, processed, boxes, scores, counts_h, rules, marks, lines=None, barcodes=None, qrcodes=None) -> "_Pending":
+    def _submit_lines(self, processed, boxes, scores, counts_h, rules, marks, lines=None, barcodes=None, qrcodes=None, datamatrix=None) -> "_Pending":
         """submit_recognize after its sync.  lines: (quads, det scores, page index, cls_forward's outputs or None) of the counted lines when
         the caller has them already (run_oriented: the vote needed them), else they are selected and classified here."""
         import torch
@@ -276,13 +307,15 @@ class OcrPipeline:
             pend.barcodes_host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in barcodes]
         if qrcodes is not None:
             pend.qrcodes_host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in qrcodes]
+        if datamatrix is not None:
+            pend.datamatrix_host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in datamatrix]
         if self.gather is not None:
             self.gather.begin(counts_h)          # capacity all-reduce runs beside the recogniser
         if n == 0:
             if self.gather is not None:          # every rank takes part in the collective, with or without lines
                 e = lambda *shape, dt=torch.int32: torch.empty(shape, dtype=dt, device=boxes.device)
                 pend.gathered = self.gather.submit(counts_h, e(0, 8), e(0, dt=torch.float32), e(0, 80), e(0), e(0, dt=torch.float32))
-            elif pend.rules_host is not None or pend.marks_host is not None or pend.barcodes_host is not None or pend.qrcodes_host is not None:
+            elif pend.rules_host is not None or pend.marks_host is not None or pend.barcodes_host is not None or pend.qrcodes_host is not None or pend.datamatrix_host is not None:
                 pend.event = torch.cuda.Event()
                 pend.event.record(torch.cuda.current_stream(processed.device))
             return pend
@@ -324,11 +357,12 @@ class OcrPipeline:
         rounds = self._page_marks(pend, 2)
         codes = self._page_barcodes(pend)
         qrs = self._page_barcodes(pend, qr=True)
+        dms = self._page_barcodes(pend, dm=True)
         if pend.n == 0:
             nw = self._empty_words() if self.word_boxes else {}
             return [PageDetections(np.zeros((0, 8), np.int32), [], np.zeros(0, np.float32), np.zeros(0, np.float32), w, h,
                                    hrules=rules[p][0], vrules=rules[p][1], marks=marks[p], round_marks=rounds[p], barcodes=codes[p][0],
-                                   barcode_syms=codes[p][1], qrcodes=qrs[p][0], qr_data=qrs[p][1], **nw) for p in range(b)], pend.processed
+                                   barcode_syms=codes[p][1], qrcodes=qrs[p][0], qr_data=qrs[p][1], datamatrix=dms[p][0], dm_data=dms[p][1], **nw) for p in range(b)], pend.processed
         text_h, len_h, score_h, quads_h, det_h, *cls_h = (t.numpy() for t in pend.host)
         all_texts = self._decoder.decode(text_h, len_h)
         words_h = None
@@ -344,6 +378,7 @@ class OcrPipeline:
                                       *((cls_h[0][off:off + c], cls_h[1][off:off + c]) if cls_h else ()),
                                       hrules=rules[p][0], vrules=rules[p][1], marks=marks[p], round_marks=rounds[p],
                                       barcodes=codes[p][0], barcode_syms=codes[p][1], qrcodes=qrs[p][0], qr_data=qrs[p][1],
+                                      datamatrix=dms[p][0], dm_data=dms[p][1],
                                       **({} if words_h is None else dict(zip(self._WORD_FIELDS, (t[off:off + c] for t in words_h))))))
             off += c
         return out, pend.processed
@@ -402,11 +437,11 @@ class OcrPipeline:
             out.append(rows[p, :m].copy())
         return out
 
-    def _page_barcodes(self, pend: "_Pending", qr: bool = False):
+    def _page_barcodes(self, pend: "_Pending", qr: bool = False, dm: bool = False):
         """-> per page (codes [m,8], symbol values [m,64]) from the pending batch's host copies, or (None, None) without barcodes.  A
         page whose true count exceeds the capacity has no rows: it is treated as having no barcodes.  qr: the same of the QR pass's
-        copies, (codes [m,12], data codewords [m,288])."""
-        host = pend.qrcodes_host if qr else pend.barcodes_host
+        copies, (codes [m,12], data codewords [m,288]); dm: of the Data Matrix pass's, (codes [m,12], data codewords [m,208])."""
+        host = pend.datamatrix_host if dm else pend.qrcodes_host if qr else pend.barcodes_host
         if host is None:
             return [(None, None)] * pend.b
         rows, syms, cnt = (t.numpy() for t in host)
@@ -415,7 +450,7 @@ class OcrPipeline:
         for p in range(pend.b):
             m = int(cnt[p])
             if m > cap:
-                logger.warning("page %d of the batch has %d %s, more than max_codes = %d: none are reported for it", p, m, "QR codes" if qr else "barcodes", cap)
+                logger.warning("page %d of the batch has %d %s, more than max_codes = %d: none are reported for it", p, m, "Data Matrix symbols" if dm else "QR codes" if qr else "barcodes", cap)
                 m = 0
             out.append((rows[p, :m].copy(), syms[p, :m].copy()))
         return out
@@ -443,10 +478,10 @@ class OcrPipeline:
         import torch
         processed, boxes, scores, counts = self.submit_detect(pages, enhance, deskew)
         b = processed.shape[0]
-        rules, marks, codes, qrs = self._submit_page_analysis(processed)
+        rules, marks, codes, qrs, dms = self._submit_page_analysis(processed)
         counts_h = counts.cpu().numpy()
         if int(counts_h.sum()) == 0:
-            return self._submit_lines(processed, boxes, scores, counts_h, rules, marks, barcodes=codes, qrcodes=qrs), np.zeros(b, bool)
+            return self._submit_lines(processed, boxes, scores, counts_h, rules, marks, barcodes=codes, qrcodes=qrs, datamatrix=dms), np.zeros(b, bool)
         quads, det_sc, page_idx = self._select_lines(boxes, scores, counts_h, b)
         ccrops, cwidths = self.eng.cls_crop(processed, quads, page_idx)
         cls = self.eng.cls_forward(ccrops, cwidths, self.cls_thresh)
@@ -459,7 +494,7 @@ class OcrPipeline:
             cls = tuple(t.index_select(0, keep) for t in cls)
             counts_h = np.where(flipped, 0, counts_h).astype(counts_h.dtype)
         lines = (quads, det_sc, page_idx, cls if self.angle_cls else None)
-        return self._submit_lines(processed, boxes, scores, counts_h, rules, marks, lines=lines, barcodes=codes, qrcodes=qrs), flipped
+        return self._submit_lines(processed, boxes, scores, counts_h, rules, marks, lines=lines, barcodes=codes, qrcodes=qrs, datamatrix=dms), flipped
 
     def run_oriented_groups(self, pages, enhance: bool = True, deskew: bool = False):
         """run_oriented's work, as the passes made it: -> [(input indices, detections, processed pages [m,H',W',3] on the device)], every

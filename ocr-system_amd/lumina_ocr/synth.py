@@ -843,3 +843,245 @@ def synth_qr_crowded_page() -> Tuple[np.ndarray, dict]:
     a = draw_qr(page, 10, 12, qr_encode("CROWDED CORNER 6-M", 6, 1, 4), 3, 1)
     b = draw_qr(page, 211, 12, qr_encode("NEIGHBOUR", 2, 1, 0), 3)
     return page, {a: "CROWDED CORNER 6-M", b: "NEIGHBOUR"}
+
+
+# ---- Data Matrix (ECC 200; the tables are utils/datamatrix.py's, everything else is the encoder's own) ----
+DM_SCHEMES = ("ascii", "c40", "text", "x12", "edifact", "base256")
+
+
+def _dm_ascii(raw: bytes) -> List[int]:
+    out, i = [], 0
+    while i < len(raw):
+        if i + 1 < len(raw) and 48 <= raw[i] <= 57 and 48 <= raw[i + 1] <= 57:
+            out.append(130 + 10 * (raw[i] - 48) + raw[i + 1] - 48)
+            i += 2
+            continue
+        out += [raw[i] + 1] if raw[i] < 128 else [235, raw[i] - 127]
+        i += 1
+    return out
+
+
+def _dm_c40_values(ch: int, scheme: str) -> List[int]:
+    """One byte -> its C40 / Text / X12 values (shifts included)."""
+    from .utils import datamatrix as dm
+    if scheme == "x12":
+        return [dm.X12_SET.index(chr(ch))]                 # (ValueError: not an X12 character)
+    if ch >= 128:
+        return [1, 30] + _dm_c40_values(ch - 128, scheme)
+    basic, c = (dm.C40_BASIC if scheme == "c40" else dm.TEXT_BASIC), chr(ch)
+    if c in basic:
+        return [3 + basic.index(c)]
+    if ch < 32:
+        return [0, ch]
+    if c in dm.SHIFT2:
+        return [1, dm.SHIFT2.index(c)]
+    return [2, ch - 96] if scheme == "c40" else [2, dm.TEXT_SHIFT3.index(c)]
+
+
+def dm_data_codewords(data, size: int, scheme: str = "ascii") -> List[int]:
+    """data -> the data codewords of SIZES[size], padded (129, then its 253-state randomisation).  str (as UTF-8) or bytes are
+    encoded in the one scheme named (DM_SCHEMES; the characters the scheme lacks are a ValueError, except that C40 and Text shift);
+    a list of ints is taken as codewords as they are; a list of such parts is encoded part by part, ("scheme", part) tuples
+    choosing the part's scheme.  C40 / Text / X12 end as the standard says: values that do not fill a triple go to ASCII behind an
+    unlatch, the unlatch is left out when the data ends with the symbol, and one last character in one last codeword is ASCII without
+    an unlatch.  EDIFACT unlatches unless its triples end with the symbol; Base 256 writes its length, or 0 ("to the end of the
+    symbol") when the field fills the symbol."""
+    from .utils import datamatrix as dm
+    cap = dm.SIZES[size][2]
+    if scheme not in DM_SCHEMES:
+        raise ValueError("scheme must be one of %s" % (DM_SCHEMES,))
+
+    def part(p, sch: str, cw: List[int]) -> None:
+        if isinstance(p, tuple):
+            return part(p[1], p[0], cw)
+        if isinstance(p, list):
+            if all(isinstance(v, int) for v in p):
+                cw += p
+            else:
+                for q in p:
+                    part(q, sch, cw)
+            return
+        raw = p.encode("utf-8") if isinstance(p, str) else bytes(p)
+        if sch == "ascii":
+            cw += _dm_ascii(raw)
+        elif sch in ("c40", "text", "x12"):
+            groups, k = [_dm_c40_values(b, sch) for b in raw], 0
+            vals: List[int] = []
+            done = 0                                       # bytes whose values lie in whole triples
+            for i, g in enumerate(groups):
+                vals += g
+                if len(vals) % 3 == 0:
+                    done, k = i + 1, len(vals)
+            cw.append({"c40": dm.LATCH_C40, "text": dm.LATCH_TEXT, "x12": dm.LATCH_X12}[sch])
+            for i in range(0, k, 3):
+                v = 1600 * vals[i] + 40 * vals[i + 1] + vals[i + 2] + 1
+                cw += [v >> 8, v & 255]
+            rest = _dm_ascii(raw[done:])
+            if rest and not (len(cw) + 1 == cap and len(rest) == 1):
+                cw.append(dm.UNLATCH)
+            elif not rest and len(cw) < cap:
+                cw.append(dm.UNLATCH)
+            cw += rest
+        elif sch == "edifact":
+            if any(not 32 <= b <= 94 for b in raw):
+                raise ValueError("not an EDIFACT character")
+            cw.append(dm.LATCH_EDIFACT)
+            vals = [b & 63 for b in raw]
+            if not (len(vals) % 4 == 0 and len(cw) + 3 * len(vals) // 4 == cap):
+                vals.append(0x1F)
+            bits = "".join("{:06b}".format(v) for v in vals)
+            bits += "0" * (-len(bits) % 8)
+            cw += [int(bits[i:i + 8], 2) for i in range(0, len(bits), 8)]
+        else:
+            cw.append(dm.LATCH_BASE256)
+            fills = len(cw) + 1 + len(raw) == cap
+            field = [0] if fills else ([len(raw)] if len(raw) < 250 else [249 + len(raw) // 250, len(raw) % 250])
+            for v in field + list(raw):
+                r = v + (149 * (len(cw) + 1)) % 255 + 1
+                cw.append(r if r <= 255 else r - 256)
+
+    cw: List[int] = []
+    part(data, scheme, cw)
+    if len(cw) > cap:
+        raise ValueError("%d codewords do not fit %d x %d (%d)" % (len(cw), dm.SIZES[size][0], dm.SIZES[size][1], cap))
+    if len(cw) < cap:
+        cw.append(dm.PAD)
+    while len(cw) < cap:
+        cw.append(dm.randomised_pad(len(cw) + 1))
+    return cw
+
+
+def dm_rs_remainder(data: List[int], ec: int) -> List[int]:
+    """The ec Reed-Solomon check codewords of a block over GF(256) / 0x12D, generator (x - a^1) ... (x - a^ec)."""
+    from .utils import datamatrix as dm
+    gen = dm.rs_generator(ec)
+    rem = [0] * ec
+    for d in data:
+        f = d ^ rem[0]
+        rem = rem[1:] + [0]
+        for k in range(ec):
+            rem[k] ^= dm.gf_mul(gen[k + 1], f)
+    return rem
+
+
+def dm_interleave(cw: List[int], size: int) -> List[int]:
+    """Data codewords -> all codewords of the symbol in placement order: the data, then the blocks' check codewords interleaved
+    (block b takes every nb-th data codeword from b on)."""
+    from .utils import datamatrix as dm
+    nb, ec = dm.SIZES[size][6], dm.SIZES[size][3] // dm.SIZES[size][6]
+    checks = [dm_rs_remainder(cw[b::nb], ec) for b in range(nb)]
+    return list(cw) + [checks[b][i] for i in range(ec) for b in range(nb)]
+
+
+def dm_matrix(codewords: List[int], size: int) -> np.ndarray:
+    """All codewords of a symbol -> bool [rows, cols] (True = dark): function modules, the codewords through the placement and the
+    fixed 2 x 2 corner."""
+    from .utils import datamatrix as dm
+    m = np.zeros(dm.SIZES[size][:2], bool)
+    for (r, c), dark in dm.function_modules(size).items():
+        m[r, c] = dark
+    for i, (r, c) in enumerate(dm.placement_of(size)):
+        m[r, c] = bool((codewords[i >> 3] >> (7 - (i & 7))) & 1)
+    for (r, c), dark in dm.fixed_modules(size):
+        m[r, c] = dark
+    return m
+
+
+def dm_encode(data, size: int, scheme: str = "ascii") -> np.ndarray:
+    """data (see dm_data_codewords) -> the symbol's modules, bool [rows, cols] indexed [row, col], True = dark."""
+    return dm_matrix(dm_interleave(dm_data_codewords(data, size, scheme), size), size)
+
+
+def dm_smallest_size(data, scheme: str = "ascii", square: bool = True) -> int:
+    """The first square (or any) size of the table that holds data."""
+    from .utils import datamatrix as dm
+    for s in sorted(range(dm.NUM_SIZES), key=lambda s: dm.SIZES[s][2]):
+        if square and dm.SIZES[s][0] != dm.SIZES[s][1]:
+            continue
+        try:
+            dm_data_codewords(data, s, scheme)
+            return s
+        except ValueError as e:
+            if "do not fit" not in str(e):
+                raise
+    raise ValueError("the data fits no size")
+
+
+def draw_dm(page: np.ndarray, x: int, y: int, modules: np.ndarray, module: int, rotation: int = 0, ink: int = 0) -> Tuple[int, int, int, int]:
+    """draw_qr for a matrix that need not be square: top-left pixel at (x, y), `module` pixels a module, turned clockwise by rotation
+    quarter turns; only dark modules are drawn.  -> the box (x0, y0, x1, y1), inclusive."""
+    m = np.rot90(np.asarray(modules, bool), -int(rotation) % 4)
+    hh, ww = m.shape[0] * module, m.shape[1] * module
+    if x < 0 or y < 0 or x + ww > page.shape[1] or y + hh > page.shape[0]:
+        raise ValueError("the symbol does not fit the page")
+    page[y:y + hh, x:x + ww][np.kron(m, np.ones((module, module), bool))] = ink
+    return x, y, x + ww - 1, y + hh - 1
+
+
+def synth_dm_page(seed: int, h: int = 700, w: int = 1000, n_codes: int = 3, text_lines: int = 6, module_px: int = 0) -> Tuple[np.ndarray, List[dict]]:
+    """White page with text lines in its upper part and n_codes Data Matrix symbols below them, each in a cell of its own: seeded
+    sizes, schemes, rotations, module sizes (3-6 px unless given) and contents.
+    -> (uint8 [h,w,3], [dict(text, size, rows, cols, scheme, rotation, module, box)])"""
+    from .utils import datamatrix as dm
+    rng = np.random.default_rng(seed)
+    top = h // 3 if text_lines else 0
+    page = np.full((h, w, 3), 255, np.uint8)
+    if text_lines:
+        page[:top] = synth_page(top, w, seed + 3000, n_lines=text_lines, noise=0.0)[0]
+    gt = []
+    cell_w = w // max(n_codes, 1)
+    for i in range(n_codes):
+        mp = module_px or int(rng.integers(3, 7))
+        room = min(cell_w, h - top) - 4 * mp - 24
+        fits = [s for s in range(dm.NUM_SIZES) if max(dm.SIZES[s][:2]) * mp <= room]
+        if not fits:
+            continue
+        size, rot = fits[int(rng.integers(0, len(fits)))], int(rng.integers(0, 4))
+        cap = dm.SIZES[size][2]
+        scheme = DM_SCHEMES[int(rng.integers(0, len(DM_SCHEMES)))]
+        if scheme == "ascii":
+            text = ("LOT%d/" % int(rng.integers(0, 10 ** 4)) + "".join("0123456789"[int(k)] for k in rng.integers(0, 10, 2 * cap)))[:max(1, cap - 1)]
+        elif scheme == "base256":
+            text = ("réf %d: " % int(rng.integers(0, 100)) + "données " * 30)[:max(1, (cap - 2) // 2)]
+        elif scheme == "text":
+            text = ("part no %d rev b, " % int(rng.integers(0, 10 ** 5)) * 12)[:max(1, cap - 3)]
+        else:                                              # c40, x12, edifact: capitals, digits and two separators each set has
+            sep = {"c40": (" ", ">"), "x12": ("*", ">"), "edifact": (" ", "-")}[scheme]
+            text = ("INV %d%sPART%s" % (int(rng.integers(0, 10 ** 5)), sep[0], sep[1]) * 12)[:max(1, cap - 3)]
+        x = i * cell_w + 12 + 2 * mp
+        y = top + 12 + 2 * mp + int(rng.integers(0, 8))
+        box = draw_dm(page, x, y, dm_encode(text, size, scheme), mp, rot)
+        gt.append(dict(text=text, size=size, rows=dm.SIZES[size][0], cols=dm.SIZES[size][1], scheme=scheme, rotation=rot, module=mp, box=box))
+    return page, gt
+
+
+def synth_dm_decoys(h: int = 243, w: int = 420) -> Tuple[np.ndarray, List[dict]]:
+    """White page of what looks like a Data Matrix symbol and is none: a ruled table frame, a large letter L, a QR symbol, a solid
+    square, a checkbox, an L whose arm has a gap, a mirrored symbol and an inverted one.  -> (uint8 [h,w,3], [dict(kind, box)])"""
+    page = np.full((h, w, 3), 255, np.uint8)
+    gt = []
+    x0, y0, x1, y1 = 8, 8, 127, 79                                                    # a 3 x 2 table frame, 2 px rules
+    for yy in (y0, (y0 + y1) // 2, y1 - 1):
+        page[yy:yy + 2, x0:x1 + 1] = 0
+    for xx in (x0, x0 + 40, x0 + 80, x1 - 1):
+        page[y0:y1 + 1, xx:xx + 2] = 0
+    gt.append(dict(kind="table", box=(x0, y0, x1, y1)))
+    page[10:70, 140:146] = 0                                                          # a letter L: no clock tracks
+    page[64:70, 140:190] = 0
+    gt.append(dict(kind="letter_l", box=(140, 10, 189, 69)))
+    gt.append(dict(kind="qr", box=draw_qr(page, 200, 8, qr_encode("NOT A DATA MATRIX", 2, 1, 2), 3)))
+    page[10:50, 290:330] = 0
+    gt.append(dict(kind="solid", box=(290, 10, 329, 49)))
+    page[10:46, 340:376] = 0
+    page[13:43, 343:373] = 255
+    gt.append(dict(kind="checkbox", box=(340, 10, 375, 45)))
+    sym = dm_encode("GAP IN THE ARM", 4)
+    sym[6:9, 0] = False                                                               # three modules of the upright are missing
+    gt.append(dict(kind="gap", box=draw_dm(page, 10, 100, sym, 4)))
+    sym = dm_encode("MIRRORED 123", 3)
+    gt.append(dict(kind="mirrored", box=draw_dm(page, 110, 100, sym[:, ::-1], 4)))
+    sym = dm_encode("INVERTED", 2)
+    page[100:100 + 18 * 4, 200:200 + 18 * 4] = 0                                      # dark field, the symbol light on it
+    draw_dm(page, 208, 108, sym, 4, ink=255)
+    gt.append(dict(kind="inverted", box=(200, 100, 271, 171)))
+    return page, gt

@@ -153,12 +153,14 @@ def build_mark_boxes(marks: Sequence[Dict[str, Any]], page_number: int = 1) -> L
 
 
 def build_barcode_boxes(found: Sequence[Dict[str, Any]], page_number: int = 1) -> List[Dict[str, Any]]:
-    """`barcode` entries: type, kind ("Code128" / "Code39" / "EAN13" / "UPCA" / "EAN8" / "UPCE" / "ITF" / "QRCode"), content (the decoded
-    text), confidence, polygon, page_number; barcodes as utils/barcodes.read_barcodes and utils/qrcodes.read_qrcodes give them, in their
-    order.  A QR symbol whose content is out of scope has content "" and the reason under `unsupported`; an ITF-14 has `itf14`: True."""
+    """`barcode` entries: type, kind ("Code128" / "Code39" / "EAN13" / "UPCA" / "EAN8" / "UPCE" / "ITF" / "QRCode" / "DataMatrix"), content
+    (the decoded text), confidence, polygon, page_number; barcodes as utils/barcodes.read_barcodes, utils/qrcodes.read_qrcodes and
+    utils/datamatrix.read_datamatrix give them, in their order.  A QR or Data Matrix symbol whose content is out of scope has content ""
+    and the reason under `unsupported`; an ITF-14 has `itf14`: True; a GS1 Data Matrix has `gs1`: True."""
     return [dict({"type": "barcode", "kind": str(b["kind"]), "content": str(b["content"]), "confidence": float(b["confidence"]),
                   "polygon": [float(v) for v in b["polygon"]], "page_number": page_number},
-                 **({"unsupported": str(b["unsupported"])} if "unsupported" in b else {}), **({"itf14": True} if b.get("itf14") else {})) for b in found]
+                 **({"unsupported": str(b["unsupported"])} if "unsupported" in b else {}), **({"itf14": True} if b.get("itf14") else {}),
+                 **({"gs1": True} if b.get("gs1") else {})) for b in found]
 
 
 def _with_barcode_lines(merged: Sequence[MergedLine], barcodes: Sequence[Dict[str, Any]]) -> List[MergedLine]:
@@ -319,8 +321,8 @@ def validate_layout_boxes(boxes: Sequence[Dict[str, Any]]) -> List[str]:
         if b.get("type") == "word" and not isinstance(b.get("confidence"), float):
             problems.append(f"{i}: word confidence must be float")
         if b.get("type") == "barcode":
-            if b.get("kind") not in ("Code128", "Code39", "EAN13", "UPCA", "EAN8", "UPCE", "ITF", "QRCode"):
-                problems.append(f"{i}: barcode kind must be Code128, Code39, EAN13, UPCA, EAN8, UPCE, ITF or QRCode")
+            if b.get("kind") not in ("Code128", "Code39", "EAN13", "UPCA", "EAN8", "UPCE", "ITF", "QRCode", "DataMatrix"):
+                problems.append(f"{i}: barcode kind must be Code128, Code39, EAN13, UPCA, EAN8, UPCE, ITF, QRCode or DataMatrix")
             if not isinstance(b.get("content"), str):
                 problems.append(f"{i}: barcode content must be str")
             if not isinstance(b.get("confidence"), float) or not 0.0 <= b["confidence"] <= 1.0:

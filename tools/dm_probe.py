@@ -1,0 +1,77 @@
+"""Times the Data Matrix pass on the bench's step: 64 A4@200DPI pages (bench.make_pages, seed 2024; --code-pages of them carry the four
+symbols of synth.synth_dm_page drawn under their text) -> lumina_ocr_datamatrix alone (twice: the spread between the two is the run's
+own noise), in the same run on the same pages lumina_ocr_qrcodes (the yardstick: the same run list and components), and a whole
+pipeline step with Data Matrix off and on (twice).  HIP events around each stage, median of --reps, with the spread (min, max) of the
+repeats.  One JSON line; needs an MI355X.
+
+    python tools/dm_probe.py [--reps 20]"""
+import argparse
+import json
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+for p in (ROOT, ROOT / "ocr-system_amd"):
+    sys.path.insert(0, str(p))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--pages", type=int, default=64)
+    ap.add_argument("--code-pages", type=int, default=16)
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    import bench
+    from lumina_ocr import arch, synth
+    from lumina_ocr.engine import Engine
+    from lumina_ocr.pipeline import OcrPipeline
+
+    eng = Engine(0)
+    eng.load_det(arch.make_det_weights(1234))
+    eng.load_rec(arch.make_rec_weights(4321, code_path=True))
+    pages = bench.make_pages(torch, args.pages, 2024, torch.device("cuda", 0))
+    _, h, w, _ = pages.shape
+    n_code, drawn = min(args.code_pages, args.pages), 0
+    for i in range(n_code):
+        page, gt = synth.synth_dm_page(i, h, w, n_codes=4, text_lines=20)
+        pages[i] = torch.from_numpy(page).cuda()
+        drawn += len(gt)
+
+    def stage(fn):
+        times = []
+        for i in range(args.reps + 3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if i >= 3:
+                times.append(e0.elapsed_time(e1))
+        return dict(median=round(float(np.median(times)), 3), min=round(min(times), 3), max=round(max(times), 3)), out
+
+    res = dict(pages=args.pages, height=h, width=w, code_pages=n_code, codes_drawn=drawn, reps=args.reps)
+    off = OcrPipeline(eng, post=arch.TEXT_PATH_POST)
+    on = OcrPipeline(eng, post=arch.TEXT_PATH_POST, datamatrix=True)
+    t_off, _ = stage(lambda: off.run(pages))
+    t_dm, (_, _, cnt, _, cands) = stage(lambda: eng.datamatrix(pages, debug=True))
+    t_dm, _ = stage(lambda: eng.datamatrix(pages))
+    t_qr, _ = stage(lambda: eng.qrcodes(pages))
+    t_on, _ = stage(lambda: on.run(pages))
+    t_dm2, _ = stage(lambda: eng.datamatrix(pages))
+    t_off2, _ = stage(lambda: off.run(pages))
+    t_on2, _ = stage(lambda: on.run(pages))
+    cnt, cands = cnt.cpu().numpy(), cands.cpu().numpy()
+    res.update(codes_read=int(cnt.sum()), pages_with_codes=int((cnt > 0).sum()), candidates=int(cands.sum()), max_candidates_a_page=int(cands.max()),
+               datamatrix_ms=t_dm, datamatrix_again_ms=t_dm2, qrcodes_ms=t_qr,
+               pipeline_off_ms=t_off, pipeline_off_again_ms=t_off2, pipeline_on_ms=t_on, pipeline_on_again_ms=t_on2,
+               datamatrix_over_qrcodes=round(t_dm["median"] / t_qr["median"], 3),
+               pipeline_delta_ms=round(min(t_on["median"], t_on2["median"]) - min(t_off["median"], t_off2["median"]), 2),
+               off_spread_ms=round(abs(t_off["median"] - t_off2["median"]), 2))
+    print(json.dumps(res))
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
