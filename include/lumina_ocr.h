@@ -318,6 +318,32 @@ int lumina_ocr_qrcodes(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int hei
                        int32_t* data_dev, int32_t* counts_dev, int32_t* finder_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev,
                        void* stream);
 
+/* QR codes of every version: QR Code Model 2 symbols of versions 1 .. max_version (10 <= max_version <= 40) in two stages.  STAGE 1 is
+ * lumina_ocr_qrcodes itself: the same ink, components, finders, pairs and decode of versions 1-10, with the same result bit for bit; at
+ * max_version = 10 nothing else runs.  STAGE 2 runs for every finder A to which stage 1 gave no symbol.  A's pairs (B, C) pass stage 1's
+ * geometric tests; version v in 11 .. max_version, n = 10 + 4 v modules between finder centres, is in reach when
+ * (2 (n - w) M)^2 <= 882 (|AB|^2 + |AC|^2) <= (2 (n + w) M)^2 with w = 3 + n / 16 and M = meA + meB + meC (doubled pixels); the valid
+ * pairs with a version in reach are tried in the order of |AB|^2 + |AC|^2 (then the partners' roots), eight at most, and the first that
+ * decodes is the corner's symbol.  Per pair, for every version in reach only row 6 and column 6 are sampled on that version's grid
+ * (the module formula of lumina_ocr_qrcodes with that n) and the version with the fewest timing mismatches is kept, the smaller on a
+ * tie; more than timing_max * D / 57 mismatches (D = 17 + 4 v, rounded down) drop the candidate.  The version information must agree:
+ * the top-right copy within Hamming distance 3 of the version's 18-bit word (generator 0x1F25), otherwise the bottom-left copy,
+ * otherwise the candidate is dropped.  Then as stage 1: the whole grid is sampled once, the `quiet` rings must be clear, the format
+ * information is read (first copy, then second), the codewords are unmasked, read in placement order (two-column strips from the right
+ * edge, alternately up and down, column 6 skipped, function modules skipped: finders, separators, timing, format, version and
+ * alignment patterns, the dark module), de-interleaved and corrected block by block over GF(256) (0x11D, roots alpha^0 ..), up to 81
+ * blocks of up to 153 codewords, and the syndromes of every corrected block must vanish.  The grid is affine through the three
+ * finders at every version: alignment patterns are function modules only, so a symbol must be flat and nearly upright.
+ * codes_dev int32 [n][max_codes][12]: the twelve fields and the sort key of lumina_ocr_qrcodes, rows past the count untouched;
+ * data_dev uint8 [n][max_codes][2956] = the corrected data codewords as bytes (40-L has 2956), zero behind ndata; counts_dev,
+ * finder_counts_dev, mask_in_dev / mask_out_dev and the parameters' ranges as in lumina_ocr_qrcodes.  Integer arithmetic throughout:
+ * the result is defined bit for bit (tests/qr_versions_reference.py).  Asynchronous; n == 0 is a no-op; bad arguments (max_version
+ * outside 10..40 among them) return a status before anything is written. */
+int lumina_ocr_qrcodes_versions(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module,
+                                int max_module, int quiet, int centre_tol, int ring_tol, int timing_max, int max_finders, int max_codes,
+                                int max_version, int32_t* codes_dev, uint8_t* data_dev, int32_t* counts_dev, int32_t* finder_counts_dev,
+                                const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream);
+
 /* Data Matrix: ECC 200 symbols (ISO/IEC 16022) of the 21 sizes whose rows fit one 64-bit word (10 x 10 .. 52 x 52, 8 x 18 .. 16 x 48) on
  * the pages, located, sampled and error-corrected on the device (the host half is lumina_ocr/utils/datamatrix.py).  ink as in
  * lumina_ocr_table_rules.  Every 8-connected component of the ink has its box, its area and four diagonal extremes (the pixels that

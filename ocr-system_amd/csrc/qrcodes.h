@@ -34,3 +34,24 @@ constexpr int QR_MAX_TIMING = 128;
 bool qr_params_ok(int min_module, int max_module, int quiet, int centre_tol, int ring_tol, int timing_max, int max_finders, int max_codes);
 size_t qrcodes_workspace_bytes(int B, int H, int W, int max_finders, int max_codes);
 hipError_t qrcodes_launch(const QrParams& p, void* workspace, size_t ws_bytes, hipStream_t st);
+
+// QR codes of every version, 1-40 (definition restated in tests/qr_versions_reference.py): stage 1 is the pass above and gives its result
+// bit for bit; stage 2 reads versions 11 .. max_version for the corner finders stage 1 gave no symbol.  Everything but max_version and
+// data means what it means in QrParams.
+struct QrVersionsParams {
+    const uint8_t* rgb;
+    int B, H, W;
+    int threshold, min_module, max_module, quiet, centre_tol, ring_tol, timing_max, max_finders, max_codes;
+    int max_version;      // 10 .. 40; at 10 stage 2 never runs
+    int* codes;           // device, [B][max_codes][12], as QrParams::codes
+    unsigned char* data;  // device, [B][max_codes][QR_VERSIONS_MAX_DATA]: the corrected data codewords as bytes, zero behind ndata
+    int* counts;
+    int* finder_counts;
+    unsigned long long* mask_out;
+    const unsigned long long* mask_in;
+};
+constexpr int QR_VERSIONS_MAX_DATA = 2956;   // the data codewords of 40-L
+
+bool qr_max_version_ok(int max_version);
+size_t qrcodes_versions_workspace_bytes(int B, int H, int W, int max_finders, int max_codes);
+hipError_t qrcodes_versions_launch(const QrVersionsParams& p, void* workspace, size_t ws_bytes, hipStream_t st);

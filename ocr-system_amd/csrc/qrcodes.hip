@@ -541,3 +541,449 @@ hipError_t qrcodes_launch(const QrParams& p, void* workspace, size_t ws_bytes, h
                        p.finder_counts);
     return hipGetLastError();
 }
+
+// ---- every version, 1-40 (lumina_ocr_qrcodes_versions; definition restated in tests/qr_versions_reference.py) ---------------------------------
+// Stage 1 is the pass above, kernel for kernel.  Stage 2 (qr_decode_versions) runs behind it for the finders it gave no symbol: one wave per
+// (page, finder A) again, A's nearest valid pairs with a version 11 .. max_version in reach in turn.  Per pair the versions in reach are
+// scored on their timing patterns alone (lanes over the pattern's modules), the best one's version information must agree, then the grid
+// (up to 177 x 177, three words a row) is sampled with lanes over columns and a loop over rows: the numerators advance by a constant from
+// row to row, so one division at the top and an add-and-carry per row give the floor division exactly, and a ballot is the row's word.
+// The function mask is built in LDS from the alignment centres and the fixed areas (lanes over rows); the codewords are placed without a
+// table: lanes over the two-column strips count their free modules, a wave prefix sum gives each strip its bit offset, and each lane walks
+// its strip and ORs whole and partial bytes into the codewords (LDS atomics).  Blocks are corrected by rs_gf256.h (field 0x11D, first root
+// 0).  Every loop has a constant bound, every table and LDS index is clamped, and no wave waits for another.
+#include "qr_version_tables.h"
+#include "rs_gf256.h"
+
+namespace {
+
+constexpr int QRV_ROWS = 177;                   // modules a side at version 40
+constexpr int QRV_RAW = 3712;                   // >= QRV_MAX_TOTAL, a multiple of 4
+constexpr int QRV_RS_LEN = 192, QRV_RS_EC = 30;
+static_assert(QRV_MAX_BLOCK <= QRV_RS_LEN && QRV_MAX_TOTAL <= QRV_RAW && QRV_VERSIONS == 40, "qr_version_tables.h");
+
+struct QrvLds {
+    u64 grid[QRV_ROWS * 3], func[QRV_ROWS * 3];   // module rows and the function mask: bit col % 64 of word col / 64
+    unsigned raw[QRV_RAW / 4];                    // the codewords in placement order, as bytes
+    RsLds<QRV_RS_LEN, QRV_RS_EC> rs;
+};
+
+// the versions 11 .. max_version (bit v) in reach of l2 = |AB|^2 + |AC|^2 and m = meA + meB + meC: n within 3 + n / 16 modules
+__device__ __forceinline__ u64 reach_mask_versions(i64 l2, i64 m, int max_version) {
+    u64 out = 0;
+    const i64 t = 882 * l2;
+#pragma unroll 1
+    for (int v = 11; v <= QRV_VERSIONS; ++v) {
+        if (v > max_version) break;
+        const int n = 10 + 4 * v, w = 3 + n / 16;
+        const i64 lo = 2 * (n - w) * m, hi = 2 * (n + w) * m;
+        if (lo * lo <= t && t <= hi * hi) out |= 1ull << v;
+    }
+    return out;
+}
+
+__device__ __forceinline__ int floor_div32(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }   // b > 0
+
+// bit (row, col) of a 177 x 3 word array; both clamped
+__device__ __forceinline__ int qrv_bit(const u64* rows, int row, int col) {
+    const int r = clampi(row, 0, QRV_ROWS - 1), c = clampi(col, 0, QRV_ROWS - 1);
+    return (int)((rows[r * 3 + (c >> 6)] >> (c & 63)) & 1ull);
+}
+
+// columns lo .. hi (inclusive, clipped) set in a row of three words
+__device__ __forceinline__ void qrv_set(u64 (&w)[3], int lo, int hi) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int a = lo - 64 * k < 0 ? 0 : lo - 64 * k, b = hi - 64 * k > 63 ? 63 : hi - 64 * k;
+        if (a <= b) w[k] |= (b - a == 63 ? ~0ull : ((1ull << (b - a + 1)) - 1ull)) << a;
+    }
+}
+
+__device__ __forceinline__ int wave_excl_scan(int v, int lane, int& total) {
+    int inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(inc, d);
+        if (lane >= d) inc += o;
+    }
+    total = __shfl(inc, 63);
+    return inc - v;
+}
+
+// strip s of a D-module symbol: its right column, and whether it runs upwards
+__device__ __forceinline__ int qrv_strip_right(int s, int D) {
+    const int wide = (D - 7) / 2;
+    return s < wide ? D - 1 - 2 * s : 5 - 2 * (s - wide);
+}
+
+// a lane's strip walked in placement order from bit offset pos: the unmasked bits ORed into s.raw
+__device__ __forceinline__ void qrv_walk(QrvLds& s, int strip, int D, int mpat, int total, int pos) {
+    const int right = qrv_strip_right(strip, D);
+    const bool up = (strip & 1) == 0;
+    int cur = -1, acc = 0;
+#pragma unroll 1
+    for (int k = 0; k < QRV_ROWS; ++k) {
+        if (k >= D) break;
+        const int row = up ? D - 1 - k : k;
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) {
+            const int col = right - cc;
+            if (qrv_bit(s.func, row, col)) continue;
+            const int byte = pos >> 3;
+            if (byte != cur) {
+                if (cur >= 0 && cur < total && acc) atomicOr(&s.raw[cur >> 2], (unsigned)acc << ((cur & 3) * 8));
+                cur = byte; acc = 0;
+            }
+            acc |= (qrv_bit(s.grid, row, col) ^ (qr_mask_bit(mpat, row, col) ? 1 : 0)) << (7 - (pos & 7));
+            ++pos;
+        }
+    }
+    if (cur >= 0 && cur < total && acc) atomicOr(&s.raw[cur >> 2], (unsigned)acc << ((cur & 3) * 8));
+}
+
+// a candidate through stage 2's decode -> true with the result in o / od.  The whole wave calls it (barriers inside) and returns one answer.
+__device__ __forceinline__ bool qr_try_versions(QrvLds& s, const u64* mpage, int H, int W, int nw, QrGrid g, u64 reach, int quiet, int timing_max, int ida,
+                                                int lane, int* o, unsigned char* od) {
+    // the version: fewest timing mismatches, the smaller on a tie
+    int timing = BIG, version = 0;
+#pragma unroll 1
+    for (int v = 11; v <= QRV_VERSIONS; ++v) {
+        if (!((reach >> v) & 1ull)) continue;
+        const int Dv = 17 + 4 * v;
+        g.n = Dv - 7;
+        int t = 0;
+#pragma unroll 1
+        for (int k0 = 0; k0 < 192; k0 += 64) {
+            const int k = k0 + lane, want = (k & 1) ^ 1;
+            const bool in = k >= 8 && k <= Dv - 9;
+            const bool m1 = in && qr_sample(mpage, H, W, nw, g, k, 6) != want, m2 = in && qr_sample(mpage, H, W, nw, g, 6, k) != want;
+            t += __popcll(__ballot(m1)) + __popcll(__ballot(m2));
+        }
+        if (t < timing) { timing = t; version = v; }
+    }
+    if (version == 0) return false;
+    const int D = 17 + 4 * version;
+    g.n = D - 7;
+    if (timing > timing_max * D / 57) return false;
+    // the version information: the top-right copy, otherwise the bottom-left one, within distance 3
+    {
+        const int a = lane / 3, b = D - 11 + lane % 3;
+        const bool v1 = lane < 18 && qr_sample(mpage, H, W, nw, g, b, a), v2 = lane < 18 && qr_sample(mpage, H, W, nw, g, a, b);
+        const unsigned w1 = (unsigned)(__ballot(v1) & 0x3ffffull), w2 = (unsigned)(__ballot(v2) & 0x3ffffull);
+        const unsigned want = QRV_VERSION_WORD[clampi(version - 7, 0, QRV_VERSIONS - 7)];
+        if (__popc(w1 ^ want) > 3 && __popc(w2 ^ want) > 3) return false;
+    }
+    __syncthreads();
+    // the grid: lane = column (three a lane), a loop over rows; q = floor(numerator / 2n) and the remainder advance by AC's
+    {
+        const int den = 2 * g.n;
+        const int sqx = floor_div32(g.acx, den), srx = g.acx - sqx * den, sqy = floor_div32(g.acy, den), sry = g.acy - sqy * den;
+        int qx[3], rx[3], qy[3], ry[3];
+#pragma unroll
+        for (int w = 0; w < 3; ++w) {
+            const int i = 64 * w + lane;
+            const int nx = g.ax * g.n + (i - 3) * g.abx - 3 * g.acx, ny = g.ay * g.n + (i - 3) * g.aby - 3 * g.acy;
+            qx[w] = floor_div32(nx, den); rx[w] = nx - qx[w] * den;
+            qy[w] = floor_div32(ny, den); ry[w] = ny - qy[w] * den;
+        }
+#pragma unroll 1
+        for (int j = 0; j < QRV_ROWS; ++j) {
+            if (j >= D) break;
+#pragma unroll
+            for (int w = 0; w < 3; ++w) {
+                const int px = qx[w], py = qy[w];
+                bool bit = false;
+                if (64 * w + lane < D && px >= 0 && py >= 0 && px < W && py < H) bit = (mpage[(size_t)py * nw + (px >> 6)] >> (px & 63)) & 1ull;
+                const u64 word = __ballot(bit);
+                if (lane == 0) s.grid[j * 3 + w] = word;
+                qx[w] += sqx; rx[w] += srx;
+                if (rx[w] >= den) { rx[w] -= den; ++qx[w]; }
+                qy[w] += sqy; ry[w] += sry;
+                if (ry[w] >= den) { ry[w] -= den; ++qy[w]; }
+            }
+        }
+    }
+    // the quiet rings
+    bool dirty = false;
+    for (int k = 1; k <= QR_MAX_QUIET; ++k) {
+        if (k > quiet) break;
+#pragma unroll 1
+        for (int t0 = 0; t0 < 192; t0 += 64) {
+            const int t = t0 + lane - k;
+            if (t < D + k)
+                dirty = dirty || qr_sample(mpage, H, W, nw, g, t, -k) || qr_sample(mpage, H, W, nw, g, t, D - 1 + k) || qr_sample(mpage, H, W, nw, g, -k, t) ||
+                        qr_sample(mpage, H, W, nw, g, D - 1 + k, t);
+        }
+    }
+    __syncthreads();
+    if (__ballot(dirty)) return false;
+    // format information: lane i < 15 reads bit i of both copies, lanes < 32 measure a word each
+    int b1 = 0, b2 = 0;
+    if (lane < 15) {
+        const int r1 = lane < 6 ? lane : (lane == 6 ? 7 : 8), c1 = lane < 8 ? 8 : (lane == 8 ? 7 : 14 - lane);
+        const int r2 = lane < 8 ? 8 : D - 15 + lane, c2 = lane < 8 ? D - 1 - lane : 8;
+        b1 = qrv_bit(s.grid, r1, c1);
+        b2 = qrv_bit(s.grid, r2, c2);
+    }
+    const int f1 = (int)(__ballot(b1) & 0x7fffull), f2 = (int)(__ballot(b2) & 0x7fffull);
+    const int fw = QRV_FORMAT[lane & 31];
+    const int k1 = wave_min(lane < 32 ? (__popc(f1 ^ fw) << 5) | lane : BIG), k2 = wave_min(lane < 32 ? (__popc(f2 ^ fw) << 5) | lane : BIG);
+    int word, fdist;
+    if ((k1 >> 5) <= 3) { word = k1 & 31; fdist = k1 >> 5; }
+    else if ((k2 >> 5) <= 3) { word = k2 & 31; fdist = (k2 >> 5) + 16; }
+    else return false;
+    const int level = (word >> 3) ^ 1, mpat = word & 7;
+    // the function mask (lanes over rows) and cleared codewords
+    {
+        const unsigned char* ac = QRV_ALIGN + (version - 1) * QRV_MAX_ALIGN;
+        const int cnt = clampi(version / 7 + 2, 2, QRV_MAX_ALIGN), last = ac[cnt - 1];
+#pragma unroll 1
+        for (int r0 = 0; r0 < 192; r0 += 64) {
+            const int r = r0 + lane;
+            if (r >= D) continue;
+            u64 w[3] = {1ull << 6, 0, 0};                                     // column 6: timing
+            if (r == 6) qrv_set(w, 0, D - 1);                                 // row 6: timing
+            if (r <= 8) { qrv_set(w, 0, 8); qrv_set(w, D - 8, D - 1); }       // the two upper finders, separators, format
+            if (r >= D - 8) qrv_set(w, 0, 8);                                 // the lower finder, format, the dark module
+            if (r <= 5) qrv_set(w, D - 11, D - 9);                            // version information
+            if (r >= D - 11 && r <= D - 9) qrv_set(w, 0, 5);
+            for (int ia = 0; ia < QRV_MAX_ALIGN; ++ia) {
+                if (ia >= cnt) break;
+                const int ar = ac[ia];
+                if (iabs(r - ar) > 2) continue;
+                for (int ib = 0; ib < QRV_MAX_ALIGN; ++ib) {
+                    if (ib >= cnt) break;
+                    const int cc = ac[ib];
+                    if ((ar == 6 && (cc == 6 || cc == last)) || (ar == last && cc == 6)) continue;
+                    qrv_set(w, cc - 2, cc + 2);
+                }
+            }
+            s.func[r * 3] = w[0]; s.func[r * 3 + 1] = w[1]; s.func[r * 3 + 2] = w[2];
+        }
+        for (int i = lane; i < QRV_RAW / 4; i += 64) s.raw[i] = 0u;
+    }
+    __syncthreads();
+    // codewords in placement order: strips 64 r + lane
+    const int total = clampi(QRV_TOTAL[version - 1], 1, QRV_MAX_TOTAL);
+    {
+        const int strips = (D - 7) / 2 + 3;   // <= 88
+        int cnt[2];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int sidx = 64 * r + lane;
+            cnt[r] = 0;
+            if (sidx < strips) {
+                const int right = qrv_strip_right(sidx, D);
+#pragma unroll 1
+                for (int k = 0; k < QRV_ROWS; ++k) {
+                    if (k >= D) break;
+                    cnt[r] += 2 - qrv_bit(s.func, k, right) - qrv_bit(s.func, k, right - 1);
+                }
+            }
+        }
+        int tot0, tot1;
+        const int off0 = wave_excl_scan(cnt[0], lane, tot0), off1 = tot0 + wave_excl_scan(cnt[1], lane, tot1);
+        if (lane < strips) qrv_walk(s, lane, D, mpat, total, off0);
+        if (64 + lane < strips) qrv_walk(s, 64 + lane, D, mpat, total, off1);
+    }
+    __syncthreads();
+    const unsigned char* raw = reinterpret_cast<const unsigned char*>(s.raw);
+    const int bi = (version - 1) * 4 + (level & 3);
+    const int nb = clampi(QRV_NB[bi], 1, QRV_MAX_NB), ec = clampi(QRV_EC[bi], 2, QRV_RS_EC);
+    const int nshort = nb - total % nb, dlen = total / nb - ec, ndata = total - nb * ec;
+    if (dlen < 1 || dlen + 1 + ec > QRV_RS_LEN || ndata < 1 || ndata > QRV_MAX_DATA) return false;   // (the tables never say so)
+    int errors = 0, dpos = 0;
+#pragma unroll 1
+    for (int blk = 0; blk < QRV_MAX_NB; ++blk) {
+        if (blk >= nb) break;
+        const int nd = dlen + (blk >= nshort ? 1 : 0), len = nd + ec;
+#pragma unroll
+        for (int p0 = 0; p0 < QRV_RS_LEN; p0 += 64) {
+            const int p = p0 + lane;
+            if (p < len) {
+                const int src = p < dlen ? p * nb + blk : (p < nd ? dlen * nb + blk - nshort : ndata + (p - nd) * nb + blk);
+                s.rs.blk[p] = raw[clampi(src, 0, QRV_RAW - 1)];
+            }
+        }
+        __syncthreads();
+        const int e = rs_correct_block(s.rs, len, ec, 0, lane);
+        if (e < 0) return false;
+        errors += e;
+#pragma unroll
+        for (int p0 = 0; p0 < QRV_RS_LEN; p0 += 64) {
+            const int p = p0 + lane;
+            if (p < nd && dpos + p < QRV_MAX_DATA) od[dpos + p] = s.rs.blk[p];
+        }
+        dpos += nd;
+        __syncthreads();
+    }
+    if (lane == 0) {
+        const int n = g.n;
+        i64 x0 = 0, x1 = 0, y0 = 0, y1 = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int u = (k & 1) ? 2 * n + 7 : -7, v = (k & 2) ? 2 * n + 7 : -7;
+            const i64 qx = floor_div((i64)g.ax * 2 * n + (i64)u * g.abx + (i64)v * g.acx, 4 * n);
+            const i64 qy = floor_div((i64)g.ay * 2 * n + (i64)u * g.aby + (i64)v * g.acy, 4 * n);
+            x0 = k == 0 || qx < x0 ? qx : x0; x1 = k == 0 || qx > x1 ? qx : x1;
+            y0 = k == 0 || qy < y0 ? qy : y0; y1 = k == 0 || qy > y1 ? qy : y1;
+        }
+        const auto cl = [](i64 v, int hi) { return (int)(v < 0 ? 0 : (v > hi ? hi : v)); };
+        o[0] = cl(y0, H - 1); o[1] = cl(x0, W - 1); o[2] = cl(y1 - 1, H - 1); o[3] = cl(x1 - 1, W - 1); o[4] = ida;
+        o[5] = version; o[6] = level; o[7] = mpat; o[8] = ndata; o[9] = errors;
+        o[10] = iabs(g.abx) >= iabs(g.aby) ? (g.abx > 0 ? 0 : 2) : (g.aby > 0 ? 1 : 3);
+        o[11] = fdist; o[12] = timing; o[13] = 1;
+    }
+    return true;
+}
+
+// stage 2: one wave per (page, finder) that stage 1 left without a symbol; res as stage 1's, resdata [B][max_finders][QRV_MAX_DATA]
+__global__ __launch_bounds__(64) void qr_decode_versions_kernel(const u64* mask, const int4* finders, const int* nfind, int H, int W, int nw, int max_finders,
+                                                                int quiet, int timing_max, int max_version, int* res, unsigned char* resdata) {
+    __shared__ QrvLds s;
+    const int pg = blockIdx.y, a = blockIdx.x, lane = threadIdx.x;
+    const int nf = nfind[pg];
+    if (nf > max_finders || a >= nf || nf > QR_MAX_FINDERS) return;
+    int* o = res + ((size_t)pg * max_finders + a) * RES_INTS;
+    if (o[13] == 1) return;   // stage 1 has A's symbol
+    const u64* mpage = mask + (size_t)pg * H * nw;
+    const int4 f = lane < nf ? finders[(size_t)pg * max_finders + lane] : make_int4(0, 0, 0, 0);
+    const int ax = __shfl(f.x, a), ay = __shfl(f.y, a), ma = __shfl(f.z, a), ida = __shfl(f.w, a);
+    rs_load_tables(s.rs, QR_EXP, QR_LOG, lane);
+    // A's partners as in stage 1 (lane = B, loop over C), with stage 2's reach
+    const bool b_ok = lane < nf && lane != a && iabs(f.x - ax) <= QR_SPAN && iabs(f.y - ay) <= QR_SPAN && 4 * iabs(ma - f.z) <= (ma < f.z ? ma : f.z);
+    const int abx = b_ok ? f.x - ax : 0, aby = b_ok ? f.y - ay : 0;
+    const i64 lab = (i64)abx * abx + (i64)aby * aby;
+    int pl = -1, pb = -1, pc = -1;   // the key tried last
+#pragma unroll 1
+    for (int attempt = 0; attempt < QR_PAIR_TRIES; ++attempt) {
+        int best_l = BIG, best_idc = BIG, best_c = 0;
+#pragma unroll 1
+        for (int c = 0; c < QR_MAX_FINDERS; ++c) {
+            if (c >= nf) break;
+            const int cx = __shfl(f.x, c), cy = __shfl(f.y, c), mc = __shfl(f.z, c), idc = __shfl(f.w, c);
+            bool ok = b_ok && c != a && c != lane && iabs(cx - ax) <= QR_SPAN && iabs(cy - ay) <= QR_SPAN && 4 * iabs(ma - mc) <= (ma < mc ? ma : mc);
+            const int acx = ok ? cx - ax : 0, acy = ok ? cy - ay : 0;
+            const i64 lac = (i64)acx * acx + (i64)acy * acy, dot = (i64)abx * acx + (i64)aby * acy, cross = (i64)abx * acy - (i64)aby * acx;
+            ok = ok && 4 * labs64(lab - lac) <= (lab < lac ? lab : lac) && 64 * dot * dot <= lab * lac && cross > 0;
+            const int l = ok ? (int)(lab + lac) : BIG;   // (< 2^29)
+            ok = ok && (l > pl || (l == pl && (f.w > pb || (f.w == pb && idc > pc))));   // behind the key tried last
+            ok = ok && (l < best_l || (l == best_l && idc < best_idc));
+            if (ok && reach_mask_versions(lab + lac, (i64)ma + f.z + mc, max_version) != 0ull) { best_l = l; best_idc = idc; best_c = c; }
+        }
+        const int min_l = wave_min(best_l);
+        if (min_l == BIG) return;
+        const int min_b = wave_min(best_l == min_l ? f.w : BIG);
+        const u64 win = __ballot(best_l == min_l && f.w == min_b);   // roots are distinct: one lane
+        if (!win) return;
+        const int b = __ffsll((long long)win) - 1, c = __shfl(best_c, b) & 63;
+        pl = min_l; pb = min_b; pc = __shfl(best_idc, b);
+        QrGrid g;
+        g.ax = ax; g.ay = ay; g.n = 54;
+        g.abx = __shfl(f.x, b) - ax; g.aby = __shfl(f.y, b) - ay; g.acx = __shfl(f.x, c) - ax; g.acy = __shfl(f.y, c) - ay;
+        const u64 reach = reach_mask_versions((i64)min_l, (i64)ma + __shfl(f.z, b) + __shfl(f.z, c), max_version);
+        if (qr_try_versions(s, mpage, H, W, nw, g, reach, quiet, timing_max, ida, lane, o, resdata + ((size_t)pg * max_finders + a) * QRV_MAX_DATA)) return;
+        __syncthreads();
+    }
+}
+
+// the output of both stages: as qr_output_kernel with byte rows of QRV_MAX_DATA; a symbol's codewords come from the stage that read it
+__global__ __launch_bounds__(256) void qr_output_versions_kernel(const int* res_all, const unsigned char* resdata1_all, const unsigned char* resdata2_all,
+                                                                 const int* nfind, int max_finders, int max_codes, int* tmp_all, int* counts, int* codes,
+                                                                 unsigned char* data, int* finder_counts) {
+    __shared__ int s_key[QR_MAX_CODES * 5];
+    __shared__ int s_slot[QR_MAX_CODES];
+    __shared__ int s_n;
+    const int pg = blockIdx.x;
+    const int nf = nfind[pg];
+    const int* res = res_all + (size_t)pg * max_finders * RES_INTS;
+    int* tmp = tmp_all + (size_t)pg * max_codes * 6;
+    if (threadIdx.x == 0) {
+        s_n = 0;
+        if (finder_counts) finder_counts[pg] = nf;
+    }
+    __syncthreads();
+    const int lim = nf > max_finders ? 0 : nf;   // a page with too many finders is not read
+    for (int a = threadIdx.x; a < lim; a += 256) {
+        const int* r = res + a * RES_INTS;
+        if (r[13] != 1) continue;
+        const int idx = atomicAdd(&s_n, 1);
+        if (idx >= max_codes) continue;
+        int* o = tmp + idx * 6;
+        o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3]; o[4] = r[4]; o[5] = a;
+    }
+    __syncthreads();
+    const int n = s_n;
+    if (threadIdx.x == 0) counts[pg] = n;
+    if (n > max_codes) return;   // overflow: the count is all that is reported
+    int* out = codes + (size_t)pg * max_codes * 12;
+    rank_sort<5>(s_key, tmp, 6, n, [=](int i, int rank, const int (&k)[5]) {
+        const int slot = clampi(tmp[i * 6 + 5], 0, max_finders - 1);
+        const int* r = res + slot * RES_INTS;
+        int* o = out + (size_t)rank * 12;
+        o[0] = k[1]; o[1] = k[0]; o[2] = k[3]; o[3] = k[2];
+        for (int j = 0; j < 8; ++j) o[4 + j] = r[5 + j];
+        s_slot[clampi(rank, 0, QR_MAX_CODES - 1)] = slot;
+    });
+    __syncthreads();
+    unsigned char* odat = data + (size_t)pg * max_codes * QRV_MAX_DATA;
+    const unsigned char* rd1 = resdata1_all + (size_t)pg * max_finders * QR_MAX_DATA;
+    const unsigned char* rd2 = resdata2_all + (size_t)pg * max_finders * QRV_MAX_DATA;
+    for (int idx = threadIdx.x; idx < n * QRV_MAX_DATA; idx += 256) {
+        const int rank = idx / QRV_MAX_DATA, j = idx - rank * QRV_MAX_DATA, slot = clampi(s_slot[rank & (QR_MAX_CODES - 1)], 0, max_finders - 1);
+        const int* r = res + slot * RES_INTS;
+        const int nd = r[8];
+        unsigned char v = 0;
+        if (j < nd) v = r[5] <= QR_VERSIONS ? (j < QR_MAX_DATA ? rd1[(size_t)slot * QR_MAX_DATA + j] : 0) : rd2[(size_t)slot * QRV_MAX_DATA + j];
+        odat[idx] = v;
+    }
+}
+
+}  // namespace
+
+bool qr_max_version_ok(int max_version) { return max_version >= QR_VERSIONS && max_version <= QRV_VERSIONS; }
+
+size_t qrcodes_versions_workspace_bytes(int B, int H, int W, int max_finders, int max_codes) {
+    if (!qrcodes_args_ok(B, H, W, max_finders, max_codes)) return 0;
+    Arena a;
+    qrcodes_layout(a, B, H, W, max_finders, max_codes);
+    a.take<unsigned char>((size_t)B * max_finders * QRV_MAX_DATA);
+    return a.off;
+}
+
+hipError_t qrcodes_versions_launch(const QrVersionsParams& p, void* workspace, size_t ws_bytes, hipStream_t st) {
+    const int B = p.B, H = p.H, W = p.W;
+    if (!qrcodes_args_ok(B, H, W, p.max_finders, p.max_codes) || !qr_max_version_ok(p.max_version) ||
+        !qr_params_ok(p.min_module, p.max_module, p.quiet, p.centre_tol, p.ring_tol, p.timing_max, p.max_finders, p.max_codes))
+        return hipErrorInvalidValue;
+    if (!p.rgb || !p.codes || !p.data || !p.counts) return hipErrorInvalidValue;
+    Arena a(workspace, ws_bytes);
+    const QrWorkspace w = qrcodes_layout(a, B, H, W, p.max_finders, p.max_codes);
+    unsigned char* resdata2 = a.take<unsigned char>((size_t)B * p.max_finders * QRV_MAX_DATA);
+    if (a.overflow) return hipErrorOutOfMemory;
+    const int nw = (W + 63) / 64;
+    const size_t runcap = run_cap(H, W);
+    const unsigned long long* mask;
+    hipError_t e;
+    if ((e = hipMemsetAsync(w.nfind, 0, sizeof(int) * (size_t)B, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.res, 0, sizeof(int) * (size_t)B * p.max_finders * RES_INTS, st)) != hipSuccess) return e;
+    if ((e = ink_mask_resolve(p.rgb, p.mask_in, p.mask_out, w.mask, B, H, W, p.threshold, st, &mask)) != hipSuccess) return e;
+    const int rows = B * H;
+    const dim3 grows = row_wave_grid(rows);
+    run_count_launch(mask, w.runoff, B, H, nw, st);
+    row_scan_launch(w.runoff, nullptr, B, H, st);
+    run_fill_launch(mask, w.runoff, w.rxs, w.rxe, w.parent, w.box, B, H, nw, runcap, st);
+    run_merge_launch(w.runoff, w.rxs, w.rxe, w.parent, B, H, runcap, st);
+    hipLaunchKernelGGL(qr_area_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.area, H, runcap, rows);
+    hipLaunchKernelGGL(qr_accum_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.box, w.area, H, runcap, rows);
+    hipLaunchKernelGGL(qr_finders_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.box, w.area, H, runcap, p.min_module, p.max_module,
+                       p.centre_tol, p.ring_tol, p.max_finders, w.nfind, w.finders, rows);
+    hipLaunchKernelGGL(qr_decode_kernel, dim3(p.max_finders, B), dim3(64), 0, st, mask, w.finders, w.nfind, H, W, nw, p.max_finders, p.quiet, p.timing_max, w.res,
+                       w.resdata);
+    if (p.max_version > QR_VERSIONS)
+        hipLaunchKernelGGL(qr_decode_versions_kernel, dim3(p.max_finders, B), dim3(64), 0, st, mask, w.finders, w.nfind, H, W, nw, p.max_finders, p.quiet,
+                           p.timing_max, p.max_version, w.res, resdata2);
+    hipLaunchKernelGGL(qr_output_versions_kernel, dim3(B), dim3(256), 0, st, w.res, w.resdata, resdata2, w.nfind, p.max_finders, p.max_codes, w.tmp, p.counts,
+                       p.codes, p.data, p.finder_counts);
+    return hipGetLastError();
+}

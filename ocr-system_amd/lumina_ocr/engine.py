@@ -98,6 +98,7 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_barcodes": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
         "lumina_ocr_barcodes_kinds": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32]),
         "lumina_ocr_qrcodes": (i32, [vp, vp, i32, i32, i32] + [i32] * 9 + [vp] * 7),
+        "lumina_ocr_qrcodes_versions": (i32, [vp, vp, i32, i32, i32] + [i32] * 10 + [vp] * 7),
         "lumina_ocr_datamatrix": (i32, [vp, vp, i32, i32, i32] + [i32] * 8 + [vp] * 7),
         "lumina_ocr_rules_and_marks": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_selection_marks_round": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
@@ -132,7 +133,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_png_probe", "lumina_ocr_png_decode", "lumina_ocr_flate_image_decode", "lumina_ocr_ccitt_decode", "lumina_ocr_fax_decode", "lumina_ocr_strip_image_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
     "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks", "lumina_ocr_selection_marks_round",
-    "lumina_ocr_rules_and_marks_round", "lumina_ocr_barcodes", "lumina_ocr_barcodes_kinds", "lumina_ocr_qrcodes", "lumina_ocr_datamatrix",
+    "lumina_ocr_rules_and_marks_round", "lumina_ocr_barcodes", "lumina_ocr_barcodes_kinds", "lumina_ocr_qrcodes", "lumina_ocr_qrcodes_versions", "lumina_ocr_datamatrix",
     "lumina_ocr_page_quarter_workspace_bytes", "lumina_ocr_page_quarter", "lumina_ocr_page_turn", "lumina_ocr_page_vote",
 ]
 
@@ -666,7 +667,7 @@ class Engine:
             self._chk(self.lib.lumina_ocr_barcodes_kinds(*args, kinds if isinstance(kinds, int) else arch.barcode_kinds_mask(kinds)))
         return (codes, syms, counts, mask) if debug else (codes, syms, counts)
 
-    # -- QR codes (Model 2, versions 1-10; the host half is utils/qrcodes.py) --------------------------------------------------------
+    # -- QR codes (Model 2; qrcodes: versions 1-10, qrcodes_versions: 1-40; the host half is utils/qrcodes.py) --------------------------------------------------------
     _QR_KEYS = ("threshold", "min_module", "max_module", "quiet", "centre_tol", "ring_tol", "timing_max", "max_finders", "max_codes")
 
     def qrcodes(self, pages, mask_in=None, debug: bool = False, **params):
@@ -693,6 +694,30 @@ class Engine:
         finders = torch.zeros((n,), dtype=torch.int32, device=pages.device) if debug else None
         self._chk(self.lib.lumina_ocr_qrcodes(self._h, _ptr(pages), n, h, w, *q, _ptr(codes), _ptr(data), _ptr(counts), _ptr(finders), _ptr(mask_in),
                                               _ptr(mask), self._stream()))
+        return (codes, data, counts, mask, finders) if debug else (codes, data, counts)
+
+    def qrcodes_versions(self, pages, max_version: int, mask_in=None, debug: bool = False, **params):
+        """qrcodes for versions 1 .. max_version (10..40): uint8 [n,H,W,3] device -> (codes int32 [n,max_codes,12], data uint8
+        [n,max_codes,2956], counts int32 [n]).  Versions 1-10 are read as qrcodes reads them, with the same rows; a corner finder that
+        gave no such symbol is tried for versions 11 .. max_version (lumina_ocr_qrcodes_versions).  The data codewords are bytes here.
+        params, mask_in and debug as in qrcodes."""
+        torch = _torch()
+        n, h, w, c = pages.shape
+        assert c == 3 and pages.dtype == torch.uint8 and pages.is_contiguous()
+        unknown = set(params) - set(self._QR_KEYS)
+        if unknown:
+            raise TypeError("qrcodes_versions: unknown parameters %s" % sorted(unknown))
+        q = [int(params[k]) if params.get(k) is not None else arch.QR_PARAMS[k] for k in self._QR_KEYS]
+        max_codes = q[-1]
+        if mask_in is not None:
+            assert mask_in.dtype == torch.int64 and mask_in.is_contiguous() and tuple(mask_in.shape) == (n, h, (w + 63) // 64)
+        codes = torch.zeros((n, max(max_codes, 0), 12), dtype=torch.int32, device=pages.device)
+        data = torch.zeros((n, max(max_codes, 0), 2956), dtype=torch.uint8, device=pages.device)
+        counts = torch.zeros((n,), dtype=torch.int32, device=pages.device)
+        mask = torch.zeros((n, h, (w + 63) // 64), dtype=torch.int64, device=pages.device) if debug else None
+        finders = torch.zeros((n,), dtype=torch.int32, device=pages.device) if debug else None
+        self._chk(self.lib.lumina_ocr_qrcodes_versions(self._h, _ptr(pages), n, h, w, *q, int(max_version), _ptr(codes), _ptr(data), _ptr(counts),
+                                                       _ptr(finders), _ptr(mask_in), _ptr(mask), self._stream()))
         return (codes, data, counts, mask, finders) if debug else (codes, data, counts)
 
     # -- Data Matrix (ECC 200, 10 x 10 .. 52 x 52 and the rectangles; the host half is utils/datamatrix.py) ------------------------------

@@ -43,7 +43,8 @@ class PageDetections:
     barcode_syms: Optional[np.ndarray] = None  # int32 [m, 64] their symbol values (utils/barcodes.py turns them into text)
     qrcodes: Optional[np.ndarray] = None      # int32 [m, 12] x0, y0, x1, y1, version, level, mask, ndata, errors, rotation, format distance,
                                               # timing mismatches of the page's QR symbols: OcrPipeline(qrcodes=True) only (empty on overflow)
-    qr_data: Optional[np.ndarray] = None      # int32 [m, 288] their corrected data codewords (utils/qrcodes.py turns them into text)
+    qr_data: Optional[np.ndarray] = None      # int32 [m, 288] their corrected data codewords (utils/qrcodes.py turns them into text);
+                                              # uint8 [m, 2956] with OcrPipeline(qr_max_version > 10)
     datamatrix: Optional[np.ndarray] = None   # int32 [m, 12] x0, y0, x1, y1, rows, cols, ndata, errors, rotation, timing mismatches, L misses, 0
                                               # of the page's Data Matrix symbols: OcrPipeline(datamatrix=True) only (empty on overflow)
     dm_data: Optional[np.ndarray] = None      # int32 [m, 208] their corrected data codewords (utils/datamatrix.py turns them into text)
@@ -93,7 +94,7 @@ class OcrPipeline:
                  tables: bool = False, table_params: Optional[dict] = None, marks: bool = False, mark_params: Optional[dict] = None,
                  page_orient: bool = False, page_orient_params: Optional[dict] = None, word_boxes: bool = False, round_marks: bool = False,
                  round_mark_params: Optional[dict] = None, barcodes: bool = False, barcode_params: Optional[dict] = None,
-                 qrcodes: bool = False, qr_params: Optional[dict] = None, barcode_kinds=arch.BARCODE_KINDS_DEFAULT,
+                 qrcodes: bool = False, qr_params: Optional[dict] = None, qr_max_version: int = 10, barcode_kinds=arch.BARCODE_KINDS_DEFAULT,
                  datamatrix: bool = False, dm_params: Optional[dict] = None):
         """recognizer: "crnn" (CRNN-MobileNetV3 + BiLSTM, engine.load_rec) or "svtr" (SVTR, engine.load_svtr).
         angle_cls: PaddleOCR's use_angle_cls — every line is classified 0 / 180 degrees (engine.load_cls) before recognition, and a line
@@ -113,6 +114,8 @@ class OcrPipeline:
         beside the two) or "all"; an unknown name is a ValueError.
         qrcodes: the QR symbols (Model 2, versions 1-10) of the processed pages (engine.qrcodes, parameters arch.QR_PARAMS or qr_params)
         come back as PageDetections.qrcodes / qr_data; they stay on their rank too, and with a gather the pass is not run.
+        qr_max_version (10..40): above 10 the pass is engine.qrcodes_versions, which reads versions 11 .. qr_max_version as well;
+        qr_data is then uint8 [m, 2956].
         datamatrix: the Data Matrix symbols (ECC 200, up to 52 x 52) of the processed pages (engine.datamatrix, parameters arch.DM_PARAMS
         or dm_params) come back as PageDetections.datamatrix / dm_data; the pass runs behind the QR pass and takes the ink mask the
         earlier passes made at its threshold; with a gather it is not run.
@@ -151,6 +154,9 @@ class OcrPipeline:
         self._barcode_kinds_arg = None if self.barcode_kinds == arch.barcode_kinds_mask(arch.BARCODE_KINDS_DEFAULT) else self.barcode_kinds
         self.qrcodes = bool(qrcodes)
         self.qr_params = dict(arch.QR_PARAMS if qr_params is None else qr_params)
+        self.qr_max_version = int(qr_max_version)
+        if not 10 <= self.qr_max_version <= 40:
+            raise ValueError("qr_max_version must be 10..40, not %r" % (qr_max_version,))
         self.datamatrix = bool(datamatrix)
         self.dm_params = dict(arch.DM_PARAMS if dm_params is None else dm_params)
         self.page_orient = bool(page_orient)
@@ -220,7 +226,7 @@ class OcrPipeline:
                     codes, mask = codes[:3], codes[3]
             if self.qrcodes:
                 qmask = mask if self.qr_params["threshold"] == want else None
-                qrs = self.eng.qrcodes(processed, mask_in=qmask, debug=mask is None, **self.qr_params)
+                qrs = self._submit_qrcodes(processed, qmask, debug=mask is None)
                 if mask is None:
                     qrs, mask, want = qrs[:3], qrs[3], self.qr_params["threshold"]
             return rules, marks, codes, qrs, self._submit_datamatrix(processed, mask, want)
@@ -235,7 +241,13 @@ class OcrPipeline:
         else:
             codes = self._submit_barcodes(processed, mask)
             mask = mask if self.qr_params["threshold"] == want else None
-        return rules, marks, codes, self.eng.qrcodes(processed, mask_in=mask, **self.qr_params), None
+        return rules, marks, codes, self._submit_qrcodes(processed, mask), None
+
+    def _submit_qrcodes(self, processed, mask_in=None, debug: bool = False):
+        """Enqueue the QR pass: today's call at qr_max_version = 10, the all-versions call (byte data rows of 2956) above it."""
+        if self.qr_max_version == 10:
+            return self.eng.qrcodes(processed, mask_in=mask_in, debug=debug, **self.qr_params)
+        return self.eng.qrcodes_versions(processed, self.qr_max_version, mask_in=mask_in, debug=debug, **self.qr_params)
 
     def _submit_barcodes(self, processed, mask_in=None, mask_out: bool = False):
         """Enqueue the barcode pass of the processed pages -> (codes, symbol values, counts) device tensors, or None; with mask_out the
@@ -440,7 +452,7 @@ class OcrPipeline:
     def _page_barcodes(self, pend: "_Pending", qr: bool = False, dm: bool = False):
         """-> per page (codes [m,8], symbol values [m,64]) from the pending batch's host copies, or (None, None) without barcodes.  A
         page whose true count exceeds the capacity has no rows: it is treated as having no barcodes.  qr: the same of the QR pass's
-        copies, (codes [m,12], data codewords [m,288]); dm: of the Data Matrix pass's, (codes [m,12], data codewords [m,208])."""
+        copies, (codes [m,12], data codewords [m,288], or bytes [m,2956] above qr_max_version 10); dm: of the Data Matrix pass's, (codes [m,12], data codewords [m,208])."""
         host = pend.datamatrix_host if dm else pend.qrcodes_host if qr else pend.barcodes_host
         if host is None:
             return [(None, None)] * pend.b

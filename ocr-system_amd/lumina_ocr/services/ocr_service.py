@@ -158,6 +158,10 @@ class OCRService:
         # `:barcode: <content>` line of the Markdown, behind the 1-D codes of the page when LUMINA_OCR_BARCODES is on as well; the text lines the
         # detector found inside a symbol are dropped.  Off by default: every output is then the one without it.
         self._use_qrcodes = os.environ.get("LUMINA_OCR_QRCODES", "0").lower() not in ("", "0", "false", "no")
+        # LUMINA_OCR_QR_MAX_VERSION (with LUMINA_OCR_QRCODES=1; alone it has no effect): the largest QR version to read, 10..40.  Default 10:
+        # every output is then the one without the variable.  Above 10 the symbols of versions 11 and up (e-invoice, payment and
+        # certificate codes) are read too, on the affine grid through the three finders.  A value outside 10..40 is an error result.
+        self._qr_max_version = os.environ.get("LUMINA_OCR_QR_MAX_VERSION", "") or "10"
         # LUMINA_OCR_DATAMATRIX=1: Data Matrix symbols (ECC 200, 10 x 10 .. 52 x 52 and the six rectangles) become `barcode` entries of kind
         # "DataMatrix" with their decoded content and a `:barcode: <content>` line of the Markdown, behind the 1-D and QR codes of the page;
         # the text lines the detector found inside a symbol are dropped.  Off by default: every output is then the one without it.
@@ -201,6 +205,11 @@ class OCRService:
                                    % ("LUMINA_OCR_USE_ANGLE_CLS" if self._use_angle_cls else "LUMINA_OCR_PAGE_ORIENTATION"))
             if self._use_round_marks and not self._use_marks:
                 raise RuntimeError("LUMINA_OCR_RADIO_BUTTONS=1 needs LUMINA_OCR_SELECTION_MARKS=1: radio buttons are found in the checkboxes' pass")
+            qr_max_version = 10
+            if self._use_qrcodes:
+                if not (self._qr_max_version.strip().isdigit() and 10 <= int(self._qr_max_version) <= 40):
+                    raise RuntimeError("LUMINA_OCR_QR_MAX_VERSION: %r is not a version 10..40" % self._qr_max_version)
+                qr_max_version = int(self._qr_max_version)
             if self._use_barcodes:
                 try:
                     arch.barcode_kinds_mask(self._barcode_kinds)
@@ -241,7 +250,7 @@ class OCRService:
                     pipeline = OcrPipeline(eng, charset=charset, max_dimension=self.max_dimension, post=post, recognizer=self._recognizer,
                                            angle_cls=self._use_angle_cls, tables=self._use_tables, marks=self._use_marks,
                                            page_orient=self._use_page_orient, word_boxes=self._use_word_boxes, round_marks=self._use_round_marks,
-                                           barcodes=self._use_barcodes, qrcodes=self._use_qrcodes, datamatrix=self._use_datamatrix,
+                                           barcodes=self._use_barcodes, qrcodes=self._use_qrcodes, qr_max_version=qr_max_version, datamatrix=self._use_datamatrix,
                                            barcode_kinds=self._barcode_kinds if self._use_barcodes else arch.BARCODE_KINDS_DEFAULT)
             except Exception:
                 eng.close()
@@ -251,6 +260,13 @@ class OCRService:
             self._pre._engine = eng
             pipeline.binarize = self.apply_binarize
             self._pipeline = pipeline
+
+    def _qr_max_version_status(self):
+        """The largest QR version the provider reads (None with QR codes off; the variable's text when it is no version 10..40)."""
+        if not self._use_qrcodes:
+            return None
+        text = self._qr_max_version.strip()
+        return int(text) if text.isdigit() and 10 <= int(text) <= 40 else self._qr_max_version
 
     def _barcode_kinds_names(self):
         """The kinds the provider reads, by name ([] with barcodes off; the variable's text when it names an unknown kind)."""
@@ -947,7 +963,7 @@ class OCRService:
     # ---- status (:759-795) ----
     def get_status(self) -> Dict[str, Any]:
         st = {"client_initialized": self._pipeline is not None, "model_id": "dbnet-r18vd+crnn-mv3", "max_dimension": self.max_dimension,
-              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "datamatrix": self._use_datamatrix, "device_pdf": self.device_pdf, "device_tiff": self.device_tiff, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
+              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "device_pdf": self.device_pdf, "device_tiff": self.device_tiff, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
         if self._engine is not None:
             st["engine_version"] = self._engine.version()
             st["num_classes"] = self._engine.num_classes

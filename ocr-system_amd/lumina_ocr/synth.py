@@ -655,7 +655,7 @@ def synth_barcode_decoys(h: int = 420, w: int = 900, min_rows: int = 8) -> Tuple
     return page, gt
 
 
-# ---- QR codes (versions 1-10; the tables are utils/qrcodes.py's, everything else is the encoder's own) ----
+# ---- QR codes (versions 1-40; the tables are utils/qrcodes.py's, everything else is the encoder's own) ----
 def qr_segment_bits(data, version: int) -> List[int]:
     """One segment a call: str of digits -> numeric, str of the 45 alphanumeric characters -> alphanumeric, other str (as UTF-8) or
     bytes -> byte; a list of those -> the segments in turn; a tuple ("bits", value, width) puts raw bits (mode indicators the host
@@ -809,6 +809,31 @@ def synth_qr_page(seed: int, h: int = 700, w: int = 1000, n_codes: int = 3, text
         box = draw_qr(page, x, y, qr_encode(text, version, level, mask), mp, rot)
         gt.append(dict(text=text, version=version, level=level, mask=mask, rotation=rot, module=mp, box=box))
     return page, gt
+
+
+def synth_qr_large_page(seed: int, h: int = 1100, w: int = 800, versions=(11, 40), module_px: int = 0, text_lines: int = 6) -> Tuple[np.ndarray, List[dict]]:
+    """White page with text lines in its upper part and one large QR symbol below them: a seeded version of `versions` (inclusive, as
+    far as the page has room), level, mask, rotation, module size (3-4 px unless given) and a byte-mode content that fills it.  A
+    page maker of its own: synth_qr_page's draws are not touched.  -> (uint8 [h,w,3], [dict(text, version, level, mask, rotation,
+    module, box)])"""
+    from .utils import qrcodes as qr
+    rng = np.random.default_rng(seed)
+    top = h // 4 if text_lines else 0
+    page = np.full((h, w, 3), 255, np.uint8)
+    if text_lines:
+        page[:top] = synth_page(top, w, seed + 3000, n_lines=text_lines, noise=0.0)[0]
+    mp = module_px or int(rng.integers(3, 5))
+    room = min(w, h - top) - 8 * mp - 24
+    vmax = min(int(versions[1]), (room // mp - 17) // 4)
+    if vmax < int(versions[0]):
+        return page, []
+    version, level, mask, rot = int(rng.integers(int(versions[0]), vmax + 1)), int(rng.integers(0, 4)), int(rng.integers(0, 8)), int(rng.integers(0, 4))
+    n = qr.data_codewords(version, level) - 4
+    body = "https://lumina.example/e-invoice/%d?jwt=" % int(rng.integers(0, 10 ** 6))
+    text = (body + "".join(ALPHABET[int(k)] for k in rng.integers(0, 62, n)))[:n]
+    x, y = 12 + 4 * mp + int(rng.integers(0, 8)), top + 12 + 4 * mp + int(rng.integers(0, 8))
+    box = draw_qr(page, x, y, qr_encode(text, version, level, mask), mp, rot)
+    return page, [dict(text=text, version=version, level=level, mask=mask, rotation=rot, module=mp, box=box)]
 
 
 def synth_qr_decoys(h: int = 330, w: int = 520) -> Tuple[np.ndarray, List[dict]]:

@@ -7,6 +7,10 @@ patterns, the format and version areas and the dark module make the function mas
 gives the placement order; the block structure is typed and pinned by the published totals (tests/test_qr_tables.py).
 csrc/qr_tables.h holds the same tables for the device (device_header() writes it; the test compares).
 
+Versions 11-40 (lumina_ocr_qrcodes_versions, data codewords as bytes) have tables of their own under the *_ALL names, built for all
+40 versions; the ten-version names above them stay what they were.  csrc/qr_version_tables.h is their device copy
+(device_header_versions()): block counts, totals, alignment centres, version and format words, and no placement table.
+
 Coordinates: a module is (row, col), both 0 .. D - 1, D = 17 + 4 version; a row of modules is one 64-bit word, bit col."""
 from __future__ import annotations
 
@@ -34,6 +38,49 @@ NUM_BLOCKS = ((1, 1, 1, 1, 1, 2, 2, 2, 2, 4),
               (1, 1, 2, 4, 4, 4, 5, 6, 8, 8))
 ALIGNMENT_CENTRES = ((), (6, 18), (6, 22), (6, 26), (6, 30), (6, 34), (6, 22, 38), (6, 24, 42), (6, 26, 46), (6, 28, 50))
 
+# ---- all 40 versions (lumina_ocr_qrcodes_versions): the tables above stay as they are, these are what the functions below read ----
+VERSIONS_ALL = 40
+MAX_DATA_ALL = 2956                    # bytes a device data row of the all-versions call holds: the data codewords of 40-L
+MAX_CODEWORDS_ALL = 3706
+MAX_BLOCKS_ALL, MAX_BLOCK_LEN_ALL = 81, 153
+MAX_ALIGNMENT = 7
+# EC codewords per block and number of blocks, [level][version - 1].  Typed from memory of the standard's table; what pins them is in
+# tests/test_qr_version_tables.py (the module count of every version, monotony, the data codewords of nine symbols, the first ten columns)
+EC_PER_BLOCK_ALL = (
+    (7, 10, 15, 20, 26, 18, 20, 24, 30, 18, 20, 24, 26, 30, 22, 24, 28, 30, 28, 28, 28, 28, 30, 30, 26, 28, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30),
+    (10, 16, 26, 18, 24, 16, 18, 22, 22, 26, 30, 22, 22, 24, 24, 28, 28, 26, 26, 26, 26, 28, 28, 28, 28, 28, 28, 28, 28, 28, 28, 28, 28, 28, 28, 28, 28, 28, 28, 28),
+    (13, 22, 18, 26, 18, 24, 18, 22, 20, 24, 28, 26, 24, 20, 30, 24, 28, 28, 26, 30, 28, 30, 30, 30, 30, 28, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30),
+    (17, 28, 22, 16, 22, 28, 26, 26, 24, 28, 24, 28, 22, 24, 24, 30, 28, 28, 26, 28, 30, 24, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30, 30))
+NUM_BLOCKS_ALL = (
+    (1, 1, 1, 1, 1, 2, 2, 2, 2, 4, 4, 4, 4, 4, 6, 6, 6, 6, 7, 8, 8, 9, 9, 10, 12, 12, 12, 13, 14, 15, 16, 17, 18, 19, 19, 20, 21, 22, 24, 25),
+    (1, 1, 1, 2, 2, 4, 4, 4, 5, 5, 5, 8, 9, 9, 10, 10, 11, 13, 14, 16, 17, 17, 18, 20, 21, 23, 25, 26, 28, 29, 31, 33, 35, 37, 38, 40, 43, 45, 47, 49),
+    (1, 1, 2, 2, 4, 4, 6, 6, 8, 8, 8, 10, 12, 16, 12, 17, 16, 18, 21, 20, 23, 23, 25, 27, 29, 34, 34, 35, 38, 40, 43, 45, 48, 51, 53, 56, 59, 62, 65, 68),
+    (1, 1, 2, 4, 4, 4, 5, 6, 8, 8, 11, 11, 16, 16, 18, 16, 19, 21, 25, 25, 25, 34, 30, 32, 35, 37, 40, 42, 45, 48, 51, 54, 57, 60, 63, 66, 70, 74, 77, 81))
+
+
+def alignment_centres(version: int) -> Tuple[int, ...]:
+    """The alignment pattern centres of a version by rule: version // 7 + 2 of them, the first 6, the last 4 version + 10, the others
+    a constant even step back from the last (version 32 steps by 26, where the rule would say 28)."""
+    if version == 1:
+        return ()
+    c, last = version // 7 + 2, 4 * version + 10
+    step = 26 if version == 32 else (4 * version + 2 * c + 1) // (2 * c - 2) * 2
+    return (6,) + tuple(last - step * k for k in range(c - 2, -1, -1))
+
+
+def _data_modules(version: int) -> int:
+    """Modules of a version that are no function module, counted from the patterns' sizes."""
+    d, c = 17 + 4 * version, (0 if version == 1 else version // 7 + 2)
+    n = d * d - 3 * 64 - 2 * (d - 16) - 31            # finders with separators, timing between them, format and the dark module
+    if c:
+        n -= 25 * (c * c - 3) - 2 * 5 * (c - 2)       # alignment patterns; those on a timing pattern share five modules with it
+    return n - (36 if version >= 7 else 0)
+
+
+ALIGNMENT_CENTRES_ALL = tuple(alignment_centres(v) for v in range(1, VERSIONS_ALL + 1))
+TOTAL_CODEWORDS_ALL = tuple(_data_modules(v) // 8 for v in range(1, VERSIONS_ALL + 1))
+REMAINDER_BITS_ALL = tuple(_data_modules(v) % 8 for v in range(1, VERSIONS_ALL + 1))
+
 
 def dimension(version: int) -> int:
     return 17 + 4 * version
@@ -42,12 +89,12 @@ def dimension(version: int) -> int:
 def block_structure(version: int, level: int) -> Tuple[int, int, int, int]:
     """-> (blocks, short blocks, data codewords of a short block, EC codewords of every block); the long blocks, which come last,
     hold one data codeword more."""
-    total, nb, ec = TOTAL_CODEWORDS[version - 1], NUM_BLOCKS[level][version - 1], EC_PER_BLOCK[level][version - 1]
+    total, nb, ec = TOTAL_CODEWORDS_ALL[version - 1], NUM_BLOCKS_ALL[level][version - 1], EC_PER_BLOCK_ALL[level][version - 1]
     return nb, nb - total % nb, total // nb - ec, ec
 
 
 def data_codewords(version: int, level: int) -> int:
-    return TOTAL_CODEWORDS[version - 1] - NUM_BLOCKS[level][version - 1] * EC_PER_BLOCK[level][version - 1]
+    return TOTAL_CODEWORDS_ALL[version - 1] - NUM_BLOCKS_ALL[level][version - 1] * EC_PER_BLOCK_ALL[level][version - 1]
 
 
 # ---- GF(256), polynomial 0x11D: EXP has 512 entries so that EXP[LOG[a] + LOG[b]] needs no reduction ----
@@ -126,7 +173,7 @@ def function_modules(version: int) -> Dict[Tuple[int, int], bool]:
                 r, c = cr + dr, cc + dc
                 if 0 <= r < d and 0 <= c < d:
                     f[(r, c)] = max(abs(dr), abs(dc)) not in (2, 4)
-    cs = ALIGNMENT_CENTRES[version - 1]
+    cs = ALIGNMENT_CENTRES_ALL[version - 1]
     for ar in cs:
         for ac in cs:
             if (ar, ac) in ((6, 6), (6, cs[-1]), (cs[-1], 6)):
@@ -175,12 +222,52 @@ _PLACEMENT = {v: tuple(placement(v)) for v in range(MIN_VERSION, MAX_VERSION + 1
 _FUNCTION = {v: tuple(function_mask(v)) for v in range(MIN_VERSION, MAX_VERSION + 1)}
 
 
+_PLACEMENT_ALL: Dict[int, Tuple[Tuple[int, int], ...]] = {}     # versions 11-40, built when first asked for
+_FUNCTION_ALL: Dict[int, Tuple[int, ...]] = {}
+
+
 def placement_of(version: int) -> Tuple[Tuple[int, int], ...]:
-    return _PLACEMENT[version]
+    if version <= MAX_VERSION:
+        return _PLACEMENT[version]
+    if version not in _PLACEMENT_ALL:
+        _PLACEMENT_ALL[version] = tuple(placement(version))
+    return _PLACEMENT_ALL[version]
 
 
 def function_mask_of(version: int) -> Tuple[int, ...]:
-    return _FUNCTION[version]
+    if version <= MAX_VERSION:
+        return _FUNCTION[version]
+    if version not in _FUNCTION_ALL:
+        _FUNCTION_ALL[version] = tuple(function_mask(version))
+    return _FUNCTION_ALL[version]
+
+
+VERSION_WORDS = tuple(version_word(v) for v in range(7, VERSIONS_ALL + 1))
+
+
+def device_header_versions() -> str:
+    """The text of csrc/qr_version_tables.h: what the all-versions kernel reads.  No placement and no function mask: the kernel
+    builds the mask from the alignment centres and walks the strips itself."""
+    vs = range(1, VERSIONS_ALL + 1)
+    rows = lambda v, f, per: ",\n".join("    " + ", ".join(f % x for x in v[i:i + per]) for i in range(0, len(v), per))
+    nb = [NUM_BLOCKS_ALL[lv][v - 1] for v in vs for lv in range(4)]
+    ec = [EC_PER_BLOCK_ALL[lv][v - 1] for v in vs for lv in range(4)]
+    align = [x for v in vs for x in (list(ALIGNMENT_CENTRES_ALL[v - 1]) + [0] * MAX_ALIGNMENT)[:MAX_ALIGNMENT]]
+    return ("#pragma once\n// Written by lumina_ocr.utils.qrcodes.device_header_versions(); tests/test_qr_version_tables.py compares.  QR Code Model 2,\n"
+            "// versions 1..40.  QRV_NB / QRV_EC: blocks and EC codewords of a block by (version - 1) * 4 + level (L, M, Q, H); a symbol's\n"
+            "// total %% blocks last blocks hold one data codeword more.  QRV_TOTAL: all codewords.  QRV_ALIGN: version / 7 + 2 alignment centres\n"
+            "// (none at version 1), zero padded to 7.  QRV_VERSION_WORD: the 18 drawn bits of versions 7..40.  QRV_FORMAT: the 15 drawn bits by\n"
+            "// (level bits << 3 | mask).\n"
+            "constexpr int QRV_VERSIONS = %d, QRV_MAX_ALIGN = %d, QRV_MAX_TOTAL = %d, QRV_MAX_DATA = %d, QRV_MAX_NB = %d, QRV_MAX_BLOCK = %d;\n"
+            "__device__ const unsigned char QRV_NB[QRV_VERSIONS * 4] = {\n%s};\n"
+            "__device__ const unsigned char QRV_EC[QRV_VERSIONS * 4] = {\n%s};\n"
+            "__device__ const unsigned short QRV_TOTAL[QRV_VERSIONS] = {\n%s};\n"
+            "__device__ const unsigned char QRV_ALIGN[QRV_VERSIONS * QRV_MAX_ALIGN] = {\n%s};\n"
+            "__device__ const unsigned int QRV_VERSION_WORD[QRV_VERSIONS - 6] = {\n%s};\n"
+            "__device__ const unsigned short QRV_FORMAT[32] = {\n%s};\n"
+            % (len(vs), MAX_ALIGNMENT, MAX_CODEWORDS_ALL, MAX_DATA_ALL, MAX_BLOCKS_ALL, MAX_BLOCK_LEN_ALL, rows(nb, "%d", 16), rows(ec, "%d", 16),
+               rows(list(TOTAL_CODEWORDS_ALL), "%d", 10), rows(align, "%d", 14), rows(list(VERSION_WORDS), "0x%05x", 8),
+               rows(list(FORMAT_WORDS), "0x%04x", 8)))
 
 
 def device_header() -> str:
@@ -222,9 +309,9 @@ ECI_UTF8 = 26
 
 
 def count_bits(mode: int, version: int) -> int:
-    """Width of the character count of a segment: versions 1-9 and 10-26 differ."""
-    small = version <= 9
-    return {MODE_NUMERIC: 10 if small else 12, MODE_ALNUM: 9 if small else 11, MODE_BYTE: 8 if small else 16}[mode]
+    """Width of the character count of a segment: versions 1-9, 10-26 and 27-40 differ."""
+    k = 0 if version <= 9 else 1 if version <= 26 else 2
+    return {MODE_NUMERIC: (10, 12, 14), MODE_ALNUM: (9, 11, 13), MODE_BYTE: (8, 16, 16)}[mode][k]
 
 
 class _Bits:
@@ -320,13 +407,14 @@ def confidence(version: int, level: int, errors: int) -> float:
 
 
 def read_qrcodes(codes, data) -> List[dict]:
-    """Device rows int32 [m,12] + data codewords [m,MAX_DATA] -> one dict a symbol, in the rows' order: kind "QRCode", content,
+    """Device rows int32 [m,12] + data codewords [m,MAX_DATA] (int32, lumina_ocr_qrcodes) or [m,MAX_DATA_ALL] (uint8,
+    lumina_ocr_qrcodes_versions, versions up to 40) -> one dict a symbol, in the rows' order: kind "QRCode", content,
     confidence, polygon (the hull's TL, TR, BR, BL as 8 floats), box, version, level, mask, rotation, errors, and `unsupported` with
     the reason where the content is out of scope (content is then "").  A row whose bit stream runs past its codewords is left out."""
     out = []
     for c, d in zip(codes, data):
         x0, y0, x1, y1, version, level, mask, ndata, errors, rotation = (int(v) for v in c[:10])
-        if not (MIN_VERSION <= version <= MAX_VERSION and 0 <= level < 4 and 0 < ndata <= MAX_DATA):
+        if not (MIN_VERSION <= version <= VERSIONS_ALL and 0 <= level < 4 and 0 < ndata <= len(d)):
             continue
         text, reason = codewords_text(version, list(d[:ndata]))
         if text is None:

@@ -2,9 +2,11 @@
 of synth.synth_qr_page drawn under their text) -> lumina_ocr_qrcodes alone (twice: the spread between the two is the run's own noise),
 in the same run on the same pages lumina_ocr_selection_marks and lumina_ocr_barcodes (the yardsticks: the same run list and, for the
 marks, the same components), and a whole pipeline step with QR codes off and on (twice).  HIP events around each stage, median of
---reps, with the spread (min, max) of the repeats.  One JSON line; needs an MI355X.
+--reps, with the spread (min, max) of the repeats.  With --max-version above 10 also lumina_ocr_qrcodes_versions on the same pages (twice:
+what stage 2 costs where it finds nothing) and on the same pages with one 25-M and one 40-H symbol at 3 px drawn on each of the
+--code-pages (twice).  One JSON line; needs an MI355X.
 
-    python tools/qr_probe.py [--reps 20]"""
+    python tools/qr_probe.py [--reps 20] [--max-version 40]"""
 import argparse
 import json
 import sys
@@ -15,11 +17,17 @@ for p in (ROOT, ROOT / "ocr-system_amd"):
     sys.path.insert(0, str(p))
 
 
+def synth_qr_capacity(version: int, level: int) -> int:
+    from lumina_ocr.utils import qrcodes as qr
+    return qr.data_codewords(version, level) - 4
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--pages", type=int, default=64)
     ap.add_argument("--code-pages", type=int, default=16)
+    ap.add_argument("--max-version", type=int, default=10)
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -69,6 +77,23 @@ def main():
                qrcodes_over_marks=round(t_codes["median"] / t_marks["median"], 3),
                pipeline_delta_ms=round(min(t_on["median"], t_on2["median"]) - min(t_off["median"], t_off2["median"]), 2),
                off_spread_ms=round(abs(t_off["median"] - t_off2["median"]), 2))
+    if args.max_version > 10:
+        mv = args.max_version
+        t_v, (_, _, vcnt) = stage(lambda: eng.qrcodes_versions(pages, mv))
+        t_base, _ = stage(lambda: eng.qrcodes(pages))
+        t_v2, _ = stage(lambda: eng.qrcodes_versions(pages, mv))
+        large = pages.clone()
+        for i in range(n_code):
+            page = np.full((h, w, 3), 255, np.uint8)
+            for x, version, level in ((40, 25, 1), (520, 40, 3)):
+                text = ("probe %d v%d " % (i, version) + "e-invoice/" * 300)[:synth_qr_capacity(version, level)]
+                synth.draw_qr(page, x, h - 600, synth.qr_encode(text, version, level, i % 8), 3)
+            large[i, h - 640:] = torch.from_numpy(page[h - 640:]).cuda()
+        t_l, (_, _, lcnt) = stage(lambda: eng.qrcodes_versions(large, mv))
+        t_l2, _ = stage(lambda: eng.qrcodes_versions(large, mv))
+        res.update(max_version=mv, versions_small_ms=t_v, versions_small_again_ms=t_v2, qrcodes_beside_ms=t_base, versions_small_read=int(vcnt.sum().item()),
+                   versions_large_ms=t_l, versions_large_again_ms=t_l2, versions_large_read=int(lcnt.sum().item()), large_drawn=2 * n_code,
+                   stage2_idle_ms=round(min(t_v["median"], t_v2["median"]) - min(t_base["median"], t_codes["median"], t_codes2["median"]), 3))
     print(json.dumps(res))
     eng.close()
 
