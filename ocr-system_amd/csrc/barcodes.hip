@@ -31,12 +31,6 @@ typedef unsigned short u16;
 
 constexpr int C128_M = 11, C128_STOP = 106, C39_M = 15, C39_STAR = 43;
 
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-__device__ __forceinline__ int iabs(int v) { return v < 0 ? -v : v; }
 // the gap between bar a and the bar after it in direction d (b)
 __device__ __forceinline__ int gap_of(int sa, int ea, int sb, int eb, int d) { return d > 0 ? sb - ea - 1 : sa - eb - 1; }
 

@@ -765,13 +765,23 @@ int lumina_ocr_barcodes_kinds(lumina_ocr_t* h, const uint8_t* pages_dev, int n, 
                          counts_dev, mask_in_dev, mask_out_dev, stream);
 }
 
+// the scalar parameters both QR calls take
+static QrCommon qr_common(int height, int width, int threshold, int min_module, int max_module, int quiet, int centre_tol, int ring_tol, int timing_max,
+                          int max_finders, int max_codes) {
+    QrCommon c{};
+    c.H = height; c.W = width; c.threshold = threshold; c.min_module = min_module; c.max_module = max_module; c.quiet = quiet; c.centre_tol = centre_tol;
+    c.ring_tol = ring_tol; c.timing_max = timing_max; c.max_finders = max_finders; c.max_codes = max_codes;
+    return c;
+}
+
 int lumina_ocr_qrcodes(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module, int max_module, int quiet,
                        int centre_tol, int ring_tol, int timing_max, int max_finders, int max_codes, int32_t* codes_dev, int32_t* data_dev, int32_t* counts_dev,
                        int32_t* finder_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream) {
     if (!h) return 1;
     if (n == 0) return 0;
     if (!pages_dev || !codes_dev || !data_dev || !counts_dev || n < 0) return locr_fail(h, "qrcodes", "bad arguments");
-    if (!qr_params_ok(min_module, max_module, quiet, centre_tol, ring_tol, timing_max, max_finders, max_codes))
+    const QrCommon c = qr_common(height, width, threshold, min_module, max_module, quiet, centre_tol, ring_tol, timing_max, max_finders, max_codes);
+    if (!qr_params_ok(c))
         return locr_fail(h, "qrcodes", "parameters must satisfy 1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= centre_tol, ring_tol <= 64, "
                                        "0 <= timing_max <= 128, max_finders 1..64, max_codes 1..64");
     if (qrcodes_workspace_bytes(1, height, width, max_finders, max_codes) == 0) return locr_fail(h, "qrcodes", "bad dimensions (sides 1..65535)");
@@ -782,9 +792,8 @@ int lumina_ocr_qrcodes(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int hei
     const size_t nw = ((size_t)width + 63) / 64;
     return for_page_groups(h, n, fit_group(h->post_group, n, ws), ws, [&](int b0, int nb) {
         QrParams p{};
-        p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.H = height; p.W = width;
-        p.threshold = threshold; p.min_module = min_module; p.max_module = max_module; p.quiet = quiet; p.centre_tol = centre_tol; p.ring_tol = ring_tol;
-        p.timing_max = timing_max; p.max_finders = max_finders; p.max_codes = max_codes;
+        static_cast<QrCommon&>(p) = c;
+        p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb;
         p.codes = codes_dev + (size_t)b0 * max_codes * 12; p.data = data_dev + (size_t)b0 * max_codes * QR_MAX_DATA; p.counts = counts_dev + b0;
         p.finder_counts = finder_counts_dev ? finder_counts_dev + b0 : nullptr;
         p.mask_in = mask_in_dev ? reinterpret_cast<const unsigned long long*>(mask_in_dev) + (size_t)b0 * height * nw : nullptr;
@@ -801,7 +810,8 @@ int lumina_ocr_qrcodes_versions(lumina_ocr_t* h, const uint8_t* pages_dev, int n
     if (!h) return 1;
     if (n == 0) return 0;
     if (!pages_dev || !codes_dev || !data_dev || !counts_dev || n < 0) return locr_fail(h, "qrcodes_versions", "bad arguments");
-    if (!qr_params_ok(min_module, max_module, quiet, centre_tol, ring_tol, timing_max, max_finders, max_codes) || !qr_max_version_ok(max_version))
+    const QrCommon c = qr_common(height, width, threshold, min_module, max_module, quiet, centre_tol, ring_tol, timing_max, max_finders, max_codes);
+    if (!qr_params_ok(c) || !qr_max_version_ok(max_version))
         return locr_fail(h, "qrcodes_versions", "parameters must satisfy 1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= centre_tol, ring_tol <= 64, "
                                                 "0 <= timing_max <= 128, max_finders 1..64, max_codes 1..64, max_version 10..40");
     if (qrcodes_versions_workspace_bytes(1, height, width, max_finders, max_codes) == 0)
@@ -812,9 +822,8 @@ int lumina_ocr_qrcodes_versions(lumina_ocr_t* h, const uint8_t* pages_dev, int n
     const size_t nw = ((size_t)width + 63) / 64;
     return for_page_groups(h, n, fit_group(h->post_group, n, ws), ws, [&](int b0, int nb) {
         QrVersionsParams p{};
-        p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.H = height; p.W = width;
-        p.threshold = threshold; p.min_module = min_module; p.max_module = max_module; p.quiet = quiet; p.centre_tol = centre_tol; p.ring_tol = ring_tol;
-        p.timing_max = timing_max; p.max_finders = max_finders; p.max_codes = max_codes; p.max_version = max_version;
+        static_cast<QrCommon&>(p) = c;
+        p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.max_version = max_version;
         p.codes = codes_dev + (size_t)b0 * max_codes * 12; p.data = data_dev + (size_t)b0 * max_codes * QR_VERSIONS_MAX_DATA; p.counts = counts_dev + b0;
         p.finder_counts = finder_counts_dev ? finder_counts_dev + b0 : nullptr;
         p.mask_in = mask_in_dev ? reinterpret_cast<const unsigned long long*>(mask_in_dev) + (size_t)b0 * height * nw : nullptr;

@@ -55,6 +55,25 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// small integer helpers and the order-free reductions of one wave64 (every lane gets the result)
+__device__ __forceinline__ int iabs(int v) { return v < 0 ? -v : v; }
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { const int o = __shfl_xor(v, d); v = o < v ? o : v; }
+    return v;
+}
+__device__ __forceinline__ int wave_xor(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v ^= __shfl_xor(v, d);
+    return v;
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device setting: applied once per (current device, kernel), so that a
 // second handle on another GPU of the same process gets it too (engine.hip)
 hipError_t locr_dyn_lds(const void* kernel, int bytes);

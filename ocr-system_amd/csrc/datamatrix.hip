@@ -30,8 +30,6 @@ constexpr int RES_INTS = 16;           // a candidate's result: y0, x0, y1, x1, 
 constexpr int DM_MAX_TOTAL = 288, DM_MAX_BLOCK = 242, DM_MAX_EC = 68, DM_MAX_NB = 2;
 constexpr int DM_RAW = 320, DM_BLK = 256;   // LDS arrays: the codewords of a symbol, of a block (multiples of 64)
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // the four extremes of one run as packed words: min types hold y, max types 65535 - y below the key, so ties go to the smaller y
 __device__ __forceinline__ void run_extremes(int xs, int xe, int y, u64 (&e)[4]) {
     e[0] = ((u64)(unsigned)(xs + y) << 32) | ((u64)y << 16) | (u64)xs;
@@ -64,17 +62,10 @@ __global__ __launch_bounds__(256) void dm_accum_kernel(const int* runoff, const 
     if (!row_wave(H, rows_total, pg, row, lane)) return;
     const int* ro = runoff + (size_t)pg * (H + 1);
     const size_t rb = (size_t)pg * runcap;
-    int* P = parent + rb;
     for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
-        const int p = P[id];
-        if (p == id) continue;
-        const int root = uf_find(P, p);
-        if (root != p) P[id] = root;   // concurrent compressions only ever replace a parent by an ancestor
-        const int xs = rxs[rb + id], xe = rxe[rb + id];
-        int* b = reinterpret_cast<int*>(box + rb + root);
-        if (xs < __atomic_load_n(b + 0, __ATOMIC_RELAXED)) atomicMin(b + 0, xs);
-        if (xe > __atomic_load_n(b + 1, __ATOMIC_RELAXED)) atomicMax(b + 1, xe);
-        if (row > __atomic_load_n(b + 3, __ATOMIC_RELAXED)) atomicMax(b + 3, row);
+        int xs, xe;
+        const int root = run_join_root(parent + rb, rxs + rb, rxe + rb, box + rb, id, row, xs, xe);
+        if (root < 0) continue;
         atomicAdd(area + rb + root, xe - xs + 1);
         u64 e[4];
         run_extremes(xs, xe, row, e);

@@ -32,8 +32,6 @@ constexpr int DK_LOW = 50, DK_HIGH = 150, DK_TG22 = 13573, DK_NANGLE = 180, DK_T
 constexpr int DK_MAX_PEAKS = 512, DK_MAX_VOTES = 8192, DK_SEG_PER_PEAK = 8;
 constexpr double DK_SIN_HALF_DEG = 0.008726535498373935;
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // ---------------------------------------------------------------------------------------------- 1 + 2a: map
 constexpr int CT_H = 16, CT_W = 64;
 __global__ __launch_bounds__(256) void canny_map_kernel(const uint8_t* rgb, uint8_t* map, int* label, uint8_t* mark, int H, int W, int tiles_x, int tiles_y) {

@@ -30,11 +30,6 @@ namespace {
 
 typedef unsigned long long u64;
 
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
 __device__ __forceinline__ u64 wave_or(u64 v) {
     unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
 #pragma unroll
@@ -42,25 +37,16 @@ __device__ __forceinline__ u64 wave_or(u64 v) {
     return ((u64)hi << 32) | lo;
 }
 
-// 4: parent = root; the root's box grows to the component's.  The box only ever moves one way, so a value read before the atomic
-// that already covers this run makes the atomic unnecessary (most runs of a component lie inside what earlier ones reported)
+// 4: parent = root; the root's box grows to the component's (run_join_root of runs.h)
 __global__ __launch_bounds__(256) void mk_accum_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* parent, int4* box, int H,
                                                        size_t runcap, int rows_total) {
     int pg, row, lane;
     if (!row_wave(H, rows_total, pg, row, lane)) return;
     const int* ro = runoff + (size_t)pg * (H + 1);
     const size_t rb = (size_t)pg * runcap;
-    int* P = parent + rb;
     for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
-        const int p = P[id];
-        if (p == id) continue;
-        const int root = uf_find(P, p);
-        if (root != p) P[id] = root;   // concurrent compressions only ever replace a parent by an ancestor
-        const int xs = rxs[rb + id], xe = rxe[rb + id];
-        int* b = reinterpret_cast<int*>(box + rb + root);
-        if (xs < __atomic_load_n(b + 0, __ATOMIC_RELAXED)) atomicMin(b + 0, xs);
-        if (xe > __atomic_load_n(b + 1, __ATOMIC_RELAXED)) atomicMax(b + 1, xe);
-        if (row > __atomic_load_n(b + 3, __ATOMIC_RELAXED)) atomicMax(b + 3, row);
+        int xs, xe;
+        run_join_root(parent + rb, rxs + rb, rxe + rb, box + rb, id, row, xs, xe);
     }
 }
 

@@ -1,24 +1,35 @@
-// QR codes (Model 2, versions 1-10) on the GPU (gfx950): the symbols of a page as (x0, y0, x1, y1, version, level, mask, ndata, errors,
-// rotation, format distance, timing mismatches) with their corrected data codewords, in a canonical order.  Everything is integer and
-// every reduction is order-free (min / max / add / xor, ballots), so the lists equal the sequential definition restated in
-// tests/qr_reference.py.
+// QR codes (Model 2) on the GPU (gfx950): the symbols of a page as (x0, y0, x1, y1, version, level, mask, ndata, errors, rotation, format
+// distance, timing mismatches) with their corrected data codewords, in a canonical order.  Everything is integer and every reduction is
+// order-free (min / max / add / xor, ballots), so the lists equal the sequential definitions restated in tests/qr_reference.py (versions
+// 1-10, lumina_ocr_qrcodes) and tests/qr_versions_reference.py (versions 1-40, lumina_ocr_qrcodes_versions).
 //
-// All stream-ordered kernels, no host round trip:
+// All stream-ordered kernels, no host round trip; both calls enqueue 1-5 through one front end:
 //   1 ink_mask                          the mask (or the one the caller already has)
 //   2 run_count / row_scan / run_fill / run_merge   mask words -> run list and its 8-connected components (the shared kernels of runs.hip)
 //   3 qr_area, qr_accum   a run's length is its area; every run learns its root, box and area are accumulated at the root
 //   4 qr_finders  one wave per row, lanes over the row's roots: a solid square core whose centre row has, before and after the core's run,
 //                 two runs of one other component, the ring, concentric and 7/3 of its size -> counted, gathered per page
-//   5 qr_decode   one wave per (page, finder A): lanes over B, a loop over C pick A's partners (64-bit products, no division, no root),
-//                 the nearest valid pairs in turn until one decodes;
-//                 per version in reach lane r samples module row r on the affine grid as one 64-bit word and the timing patterns are
-//                 counted; quiet rings; both format copies against the 32 words (popcount, wave min); unmask; lanes gather the codewords
-//                 through the placement table from the rows in LDS; per block syndromes (lanes over positions, wave xor),
-//                 Berlekamp-Massey by one lane in LDS, Chien and Forney with lanes over positions, syndromes again.  Every loop has a
-//                 constant bound, every table and LDS index is clamped, and no wave waits for another (a work-group is one wave)
-//   6 qr_output   one work-group per page: valid candidates counted, gathered, rank-sorted by (y0, x0, y1, x1, corner root)
+//   5 qr_decode   stage 1, versions 1-10.  One wave per (page, finder A): lanes over B, a loop over C pick A's partners (64-bit products, no
+//                 division, no root), the nearest valid pairs in turn until one decodes.  Per version in reach lane r samples module row r
+//                 on the affine grid as one 64-bit word and the timing patterns are counted; the codewords are gathered through the
+//                 placement table from the rows in LDS
+//  5b qr_decode_versions   stage 2, versions 11 .. max_version (the all-versions call only), for the finders stage 1 gave no symbol.  The
+//                 versions in reach are scored on their timing patterns alone (lanes over the pattern's modules), the best one's version
+//                 information must agree, then the grid (up to 177 x 177, three words a row) is sampled with lanes over columns and a loop
+//                 over rows: the numerators advance by a constant from row to row, so one division at the top and an add-and-carry per
+//                 row give the floor division exactly, and a ballot is the row's word.  The function mask is built in LDS from the
+//                 alignment centres and the fixed areas (lanes over rows); the codewords are placed without a table: lanes over the
+//                 two-column strips count their free modules, a wave prefix sum gives each strip its bit offset, and each lane walks its
+//                 strip and ORs whole and partial bytes into the codewords (LDS atomics)
+//   6 qr_output   one work-group per page: valid candidates counted, gathered, rank-sorted by (y0, x0, y1, x1, corner root); int rows of
+//                 stage 1's codewords, or (the all-versions call) byte rows from the stage that read the symbol
+// The stages differ in how a version is scored, how the grid is sampled and how the codewords are placed; the pair search, the quiet
+// rings, the format information, the block loop (rs_gf256.h: field 0x11D, first root 0) and the result are one piece of code each.  Every
+// loop has a constant bound, every table and LDS index is clamped, and no wave waits for another (a work-group is one wave).
 #include "qrcodes.h"
 #include "qr_tables.h"
+#include "qr_version_tables.h"
+#include "rs_gf256.h"
 #include "runs.h"
 
 namespace {
@@ -28,24 +39,17 @@ typedef long long i64;
 
 constexpr int QR_SPAN = 8192;          // |B - A|, |C - A| per axis in doubled pixels: keeps every product inside 64 bits
 constexpr int RES_INTS = 16;           // a candidate's result: y0, x0, y1, x1, root, version, level, mask, ndata, errors, rotation, fdist, timing, valid
-constexpr int QR_MAX_TOTAL = 346, QR_MAX_BLOCK = 146, QR_MAX_EC = 30, QR_MAX_NB = 8;
+constexpr int QR_MAX_TOTAL = 346, QR_MAX_NB = 8, QR_RAW = 384;   // stage 1: the codewords and blocks of version 10, its LDS array
+constexpr int QRV_ROWS = 177;          // stage 2: modules a side at version 40
+constexpr int QRV_RAW = 3712;          // >= QRV_MAX_TOTAL, a multiple of 4
+constexpr int QR_RS_LEN = 192, QR_RS_EC = 30;   // both stages: the longest block (153 at version 40, 146 up to version 10) and its EC codewords
 constexpr int BIG = 0x7fffffff;
 constexpr int QR_PAIR_TRIES = 8;      // of a corner's valid partner pairs, the nearest ones are tried in turn
+static_assert(QRV_MAX_BLOCK <= QR_RS_LEN && QRV_MAX_TOTAL <= QRV_RAW && QRV_VERSIONS == 40 && QR_MAX_TOTAL <= QR_RAW, "qr_version_tables.h");
 
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const int o = __shfl_xor(v, d); v = o < v ? o : v; }
-    return v;
-}
-__device__ __forceinline__ int wave_xor(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v ^= __shfl_xor(v, d);
-    return v;
-}
-__device__ __forceinline__ int iabs(int v) { return v < 0 ? -v : v; }
 __device__ __forceinline__ i64 labs64(i64 v) { return v < 0 ? -v : v; }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ i64 floor_div(i64 a, i64 b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }   // b > 0
+__device__ __forceinline__ int floor_div32(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }   // b > 0
 
 // 3a: a run's own length is the start of its component's area
 __global__ __launch_bounds__(256) void qr_area_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* area, int H, size_t runcap,
@@ -57,25 +61,17 @@ __global__ __launch_bounds__(256) void qr_area_kernel(const int* runoff, const u
     for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) area[rb + id] = (int)rxe[rb + id] - (int)rxs[rb + id] + 1;
 }
 
-// 3b: parent = root; the root's box grows to the component's (as mk_accum of marks.hip) and its area by every other run's length
+// 3b: parent = root; the root's box grows to the component's and its area by every other run's length
 __global__ __launch_bounds__(256) void qr_accum_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* parent, int4* box, int* area,
                                                        int H, size_t runcap, int rows_total) {
     int pg, row, lane;
     if (!row_wave(H, rows_total, pg, row, lane)) return;
     const int* ro = runoff + (size_t)pg * (H + 1);
     const size_t rb = (size_t)pg * runcap;
-    int* P = parent + rb;
     for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
-        const int p = P[id];
-        if (p == id) continue;
-        const int root = uf_find(P, p);
-        if (root != p) P[id] = root;   // concurrent compressions only ever replace a parent by an ancestor
-        const int xs = rxs[rb + id], xe = rxe[rb + id];
-        int* b = reinterpret_cast<int*>(box + rb + root);
-        if (xs < __atomic_load_n(b + 0, __ATOMIC_RELAXED)) atomicMin(b + 0, xs);
-        if (xe > __atomic_load_n(b + 1, __ATOMIC_RELAXED)) atomicMax(b + 1, xe);
-        if (row > __atomic_load_n(b + 3, __ATOMIC_RELAXED)) atomicMax(b + 3, row);
-        atomicAdd(area + rb + root, xe - xs + 1);
+        int xs, xe;
+        const int root = run_join_root(parent + rb, rxs + rb, rxe + rb, box + rb, id, row, xs, xe);
+        if (root >= 0) atomicAdd(area + rb + root, xe - xs + 1);
     }
 }
 
@@ -118,18 +114,7 @@ __global__ __launch_bounds__(256) void qr_finders_kernel(const int* runoff, cons
     }
 }
 
-// the versions (bit v) whose n = 10 + 4 v modules between finder centres lie within three modules of what l2 = |AB|^2 + |AC|^2 (doubled
-// pixels) and m = meA + meB + meC say
-__device__ __forceinline__ unsigned reach_mask(i64 l2, i64 m) {
-    unsigned out = 0;
-    const i64 t = 882 * l2;
-#pragma unroll
-    for (int v = 1; v <= QR_VERSIONS; ++v) {
-        const i64 lo = 2 * (7 + 4 * v) * m, hi = 2 * (13 + 4 * v) * m;
-        if (lo * lo <= t && t <= hi * hi) out |= 1u << v;
-    }
-    return out;
-}
+// ---- what both stages share ------------------------------------------------------------------------------------------------------------------
 
 struct QrGrid { int ax, ay, abx, aby, acx, acy, n; };
 
@@ -155,75 +140,177 @@ __device__ __forceinline__ bool qr_mask_bit(int mask, int y, int x) {
     }
 }
 
-struct QrLds {
-    u64 rows[64];
-    unsigned char exp[512], log[256], raw[384], blk[192];
-    int S[32], C[32], Bp[32], T[32], O[16];
-    int L;
-};
-
-__device__ __forceinline__ int gmul(const QrLds& s, int a, int b) { return a && b ? s.exp[s.log[a & 255] + s.log[b & 255]] : 0; }
-// a * alpha^e, 0 <= e <= 255 (log a + e <= 509, inside the doubled table)
-__device__ __forceinline__ int gmul_exp(const QrLds& s, int a, int e) { return a ? s.exp[s.log[a & 255] + e] : 0; }
-
-// the ec syndromes of s.blk[0 .. len) -> s.S; true when one is not zero.  (barriers inside: the whole wave calls it)
-__device__ __forceinline__ bool qr_syndromes(QrLds& s, int len, int ec, int lane) {
-    int nz = 0;
-    for (int k = 0; k < QR_MAX_EC; ++k) {
-        if (k >= ec) break;
-        int acc = 0;
-#pragma unroll
-        for (int p0 = 0; p0 < 192; p0 += 64) {
-            const int p = p0 + lane;
-            if (p < len) acc ^= gmul_exp(s, s.blk[p], (k * (len - 1 - p)) % 255);
+// the partners of corner A = finder a of the nf in lanes (f = cx2, cy2, me, root): lane = B, a loop over C; the valid pairs with a version in
+// reach, in the order of (|AB|^2 + |AC|^2, root of B, root of C), are handed to attempt(grid, versions in reach) in turn, the nearest
+// QR_PAIR_TRIES of them, until one returns true.  reach(l2, m) -> the versions (bit v) that l2 = |AB|^2 + |AC|^2 (doubled pixels) and
+// m = meA + meB + meC allow.  The whole wave calls it (attempt holds barriers).
+template <class Reach, class Attempt>
+__device__ __forceinline__ void qr_pairs(const int4 f, int nf, int a, int lane, Reach reach, Attempt attempt) {
+    const int ax = __shfl(f.x, a), ay = __shfl(f.y, a), ma = __shfl(f.z, a);
+    const bool b_ok = lane < nf && lane != a && iabs(f.x - ax) <= QR_SPAN && iabs(f.y - ay) <= QR_SPAN && 4 * iabs(ma - f.z) <= (ma < f.z ? ma : f.z);
+    const int abx = b_ok ? f.x - ax : 0, aby = b_ok ? f.y - ay : 0;   // (zero where the products below could leave 64 bits)
+    const i64 lab = (i64)abx * abx + (i64)aby * aby;
+    int pl = -1, pb = -1, pc = -1;   // the key tried last
+#pragma unroll 1
+    for (int tries = 0; tries < QR_PAIR_TRIES; ++tries) {
+        int best_l = BIG, best_idc = BIG, best_c = 0;
+#pragma unroll 1
+        for (int c = 0; c < QR_MAX_FINDERS; ++c) {
+            if (c >= nf) break;
+            const int cx = __shfl(f.x, c), cy = __shfl(f.y, c), mc = __shfl(f.z, c), idc = __shfl(f.w, c);
+            bool ok = b_ok && c != a && c != lane && iabs(cx - ax) <= QR_SPAN && iabs(cy - ay) <= QR_SPAN && 4 * iabs(ma - mc) <= (ma < mc ? ma : mc);
+            const int acx = ok ? cx - ax : 0, acy = ok ? cy - ay : 0;
+            const i64 lac = (i64)acx * acx + (i64)acy * acy, dot = (i64)abx * acx + (i64)aby * acy, cross = (i64)abx * acy - (i64)aby * acx;
+            ok = ok && 4 * labs64(lab - lac) <= (lab < lac ? lab : lac) && 64 * dot * dot <= lab * lac && cross > 0;
+            const int l = ok ? (int)(lab + lac) : BIG;   // (< 2^29)
+            ok = ok && (l > pl || (l == pl && (f.w > pb || (f.w == pb && idc > pc))));   // behind the key tried last
+            ok = ok && (l < best_l || (l == best_l && idc < best_idc));
+            if (ok && reach(lab + lac, (i64)ma + f.z + mc) != 0ull) { best_l = l; best_idc = idc; best_c = c; }
         }
-        acc = wave_xor(acc);
-        if (lane == 0) s.S[k] = acc;
-        nz |= acc;
+        const int min_l = wave_min(best_l);
+        if (min_l == BIG) return;
+        const int min_b = wave_min(best_l == min_l ? f.w : BIG);
+        const u64 win = __ballot(best_l == min_l && f.w == min_b);   // roots are distinct: one lane
+        if (!win) return;
+        const int b = __ffsll((long long)win) - 1, c = __shfl(best_c, b) & 63;
+        pl = min_l; pb = min_b; pc = __shfl(best_idc, b);
+        QrGrid g;
+        g.ax = ax; g.ay = ay; g.n = 1;   // (n: the modules between finder centres, set per version)
+        g.abx = __shfl(f.x, b) - ax; g.aby = __shfl(f.y, b) - ay; g.acx = __shfl(f.x, c) - ax; g.acy = __shfl(f.y, c) - ay;
+        if (attempt(g, reach((i64)min_l, (i64)ma + __shfl(f.z, b) + __shfl(f.z, c)))) return;
+        __syncthreads();
     }
-    __syncthreads();
-    return nz != 0;
 }
 
-// Berlekamp-Massey over s.S[0 .. ec) by one lane -> s.C (the locator), s.O (the evaluator's first L coefficients), s.L
-__device__ __forceinline__ void qr_locator(QrLds& s, int ec) {
-    for (int i = 0; i < 32; ++i) { s.C[i] = 0; s.Bp[i] = 0; }
-    s.C[0] = 1; s.Bp[0] = 1;
-    int L = 0, m = 1, b = 1;
-    for (int k = 0; k < QR_MAX_EC; ++k) {
-        if (k >= ec) break;
-        int d = s.S[k];
-        for (int i = 1; i <= QR_MAX_EC; ++i)
-            if (i <= L && i <= k) d ^= gmul(s, s.C[i], s.S[k - i]);
-        if (d == 0) { ++m; continue; }
-        for (int i = 0; i < 32; ++i) s.T[i] = s.C[i];
-        const int f = gmul_exp(s, d, 255 - s.log[b & 255]);
-        for (int i = 0; i <= QR_MAX_EC; ++i)
-            if (i + m <= ec) s.C[i + m] ^= gmul(s, f, s.Bp[i]);
-        if (2 * L <= k) {
-            L = k + 1 - L; b = d; m = 1;
-            for (int i = 0; i < 32; ++i) s.Bp[i] = s.T[i];
-        } else ++m;
+// the quiet rings of a D-module symbol, lanes over the SPAN >= D + 2 QR_MAX_QUIET positions of a side -> true when one holds ink
+template <int SPAN>
+__device__ __forceinline__ bool qr_quiet_dirty(const u64* mpage, int H, int W, int nw, const QrGrid& g, int D, int quiet, int lane) {
+    bool dirty = false;
+    for (int k = 1; k <= QR_MAX_QUIET; ++k) {
+        if (k > quiet) break;
+#pragma unroll 1
+        for (int t0 = 0; t0 < SPAN; t0 += 64) {
+            const int t = t0 + lane - k;
+            if (t < D + k)
+                dirty = dirty || qr_sample(mpage, H, W, nw, g, t, -k) || qr_sample(mpage, H, W, nw, g, t, D - 1 + k) || qr_sample(mpage, H, W, nw, g, -k, t) ||
+                        qr_sample(mpage, H, W, nw, g, D - 1 + k, t);
+        }
     }
-    for (int i = 0; i < 16; ++i) {
-        int o = 0;
-        if (i < L)
-            for (int j = 0; j <= 15; ++j)
-                if (j <= i) o ^= gmul(s, s.S[i - j], s.C[j]);
-        s.O[i] = o;
-    }
-    s.L = L;
+    return __ballot(dirty) != 0ull;
 }
+
+// format information through bit(row, col): lane i < 15 reads bit i of both copies, lanes < 32 measure a word each -> false when neither
+// copy is within distance 3 of a word
+template <class Bit>
+__device__ __forceinline__ bool qr_format(Bit bit, int D, int lane, int& level, int& mpat, int& fdist) {
+    int b1 = 0, b2 = 0;
+    if (lane < 15) {
+        const int r1 = lane < 6 ? lane : (lane == 6 ? 7 : 8), c1 = lane < 8 ? 8 : (lane == 8 ? 7 : 14 - lane);
+        const int r2 = lane < 8 ? 8 : D - 15 + lane, c2 = lane < 8 ? D - 1 - lane : 8;
+        b1 = bit(r1, c1);
+        b2 = bit(r2, c2);
+    }
+    const int f1 = (int)(__ballot(b1) & 0x7fffull), f2 = (int)(__ballot(b2) & 0x7fffull);
+    const int fw = QRV_FORMAT[lane & 31];
+    const int k1 = wave_min(lane < 32 ? (__popc(f1 ^ fw) << 5) | lane : BIG), k2 = wave_min(lane < 32 ? (__popc(f2 ^ fw) << 5) | lane : BIG);
+    int word;
+    if ((k1 >> 5) <= 3) { word = k1 & 31; fdist = k1 >> 5; }
+    else if ((k2 >> 5) <= 3) { word = k2 & 31; fdist = (k2 >> 5) + 16; }
+    else return false;
+    level = (word >> 3) ^ 1; mpat = word & 7;
+    return true;
+}
+
+// the blocks of a symbol: its `total` codewords in placement order (raw, RAW_CAP of them) de-interleaved block by block into rs.blk,
+// corrected there, the data codewords written to od (DATA_CAP of them) -> false when a block has more errors than it can correct.  A
+// symbol's total % blocks last blocks hold one data codeword more.  The whole wave calls it (barriers inside).
+template <int MAX_NB, int RAW_CAP, int DATA_CAP, int MAX_LEN, int MAX_EC>
+__device__ __forceinline__ bool qr_blocks(RsLds<MAX_LEN, MAX_EC>& rs, const unsigned char* raw, int total, int version, int level, int lane, unsigned char* od,
+                                          int& ndata, int& errors) {
+    const int bi = (version - 1) * 4 + (level & 3);
+    const int nb = clampi(QRV_NB[bi], 1, MAX_NB), ec = clampi(QRV_EC[bi], 2, MAX_EC);
+    const int nshort = nb - total % nb, dlen = total / nb - ec;
+    ndata = total - nb * ec;
+    errors = 0;
+    if (dlen < 1 || dlen + 1 + ec > MAX_LEN || ndata < 1 || ndata > DATA_CAP || total > RAW_CAP) return false;   // (the tables never say so)
+    int dpos = 0;
+#pragma unroll 1
+    for (int blk = 0; blk < MAX_NB; ++blk) {
+        if (blk >= nb) break;
+        const int nd = dlen + (blk >= nshort ? 1 : 0), len = nd + ec;
+#pragma unroll
+        for (int p0 = 0; p0 < MAX_LEN; p0 += 64) {
+            const int p = p0 + lane;
+            if (p < len) {
+                const int src = p < dlen ? p * nb + blk : (p < nd ? dlen * nb + blk - nshort : ndata + (p - nd) * nb + blk);
+                rs.blk[p] = raw[clampi(src, 0, RAW_CAP - 1)];
+            }
+        }
+        __syncthreads();
+        const int e = rs_correct_block(rs, len, ec, 0, lane);
+        if (e < 0) return false;
+        errors += e;
+#pragma unroll
+        for (int p0 = 0; p0 < MAX_LEN; p0 += 64) {
+            const int p = p0 + lane;
+            if (p < nd && dpos + p < DATA_CAP) od[dpos + p] = rs.blk[p];
+        }
+        dpos += nd;
+        __syncthreads();
+    }
+    return true;
+}
+
+// a decoded symbol's result (one lane): the hull, which is the four outer module corners, (u, v) = 2 (i, j) - 6 in {-7, 2 n + 7}, and the
+// 14 ints behind it
+__device__ __forceinline__ void qr_write_result(int* o, const QrGrid& g, int H, int W, int ida, int version, int level, int mpat, int ndata, int errors, int fdist,
+                                                int timing) {
+    const int n = g.n;
+    i64 x0 = 0, x1 = 0, y0 = 0, y1 = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int u = (k & 1) ? 2 * n + 7 : -7, v = (k & 2) ? 2 * n + 7 : -7;
+        const i64 qx = floor_div((i64)g.ax * 2 * n + (i64)u * g.abx + (i64)v * g.acx, 4 * n);
+        const i64 qy = floor_div((i64)g.ay * 2 * n + (i64)u * g.aby + (i64)v * g.acy, 4 * n);
+        x0 = k == 0 || qx < x0 ? qx : x0; x1 = k == 0 || qx > x1 ? qx : x1;
+        y0 = k == 0 || qy < y0 ? qy : y0; y1 = k == 0 || qy > y1 ? qy : y1;
+    }
+    const auto cl = [](i64 v, int hi) { return (int)(v < 0 ? 0 : (v > hi ? hi : v)); };
+    o[0] = cl(y0, H - 1); o[1] = cl(x0, W - 1); o[2] = cl(y1 - 1, H - 1); o[3] = cl(x1 - 1, W - 1); o[4] = ida;
+    o[5] = version; o[6] = level; o[7] = mpat; o[8] = ndata; o[9] = errors;
+    o[10] = iabs(g.abx) >= iabs(g.aby) ? (g.abx > 0 ? 0 : 2) : (g.aby > 0 ? 1 : 3);
+    o[11] = fdist; o[12] = timing; o[13] = 1;
+}
+
+// ---- stage 1: versions 1-10 ----------------------------------------------------------------------------------------------------------------
+
+// the versions (bit v) whose n = 10 + 4 v modules between finder centres lie within three modules of what l2 and m say
+__device__ __forceinline__ u64 reach_mask(i64 l2, i64 m) {
+    unsigned out = 0;
+    const i64 t = 882 * l2;
+#pragma unroll
+    for (int v = 1; v <= QR_VERSIONS; ++v) {
+        const i64 lo = 2 * (7 + 4 * v) * m, hi = 2 * (13 + 4 * v) * m;
+        if (lo * lo <= t && t <= hi * hi) out |= 1u << v;
+    }
+    return out;
+}
+
+struct QrLds {
+    u64 rows[64];              // module rows: bit col
+    unsigned char raw[QR_RAW];   // the codewords in placement order
+    RsLds<QR_RS_LEN, QR_RS_EC> rs;
+};
 
 // a candidate (the corner A of g with its partners) through the whole decode -> true with the result in o / od, false when it is none.
 // The whole wave calls it (barriers inside) and returns one answer.
-__device__ __forceinline__ bool qr_try(QrLds& s, const u64* mpage, int H, int W, int nw, QrGrid g, unsigned reach, int quiet, int timing_max, int ida, int lane,
+__device__ __forceinline__ bool qr_try(QrLds& s, const u64* mpage, int H, int W, int nw, QrGrid g, u64 reach, int quiet, int timing_max, int ida, int lane,
                                        int* o, unsigned char* od) {
     // the version: fewest timing mismatches, the smaller on a tie
     int timing = BIG, version = 0;
     u64 row = 0;
     for (int v = 1; v <= QR_VERSIONS; ++v) {
-        if (!((reach >> v) & 1u)) continue;
+        if (!((reach >> v) & 1ull)) continue;
         const int D = 17 + 4 * v;
         g.n = D - 7;
         u64 r = 0;
@@ -243,36 +330,11 @@ __device__ __forceinline__ bool qr_try(QrLds& s, const u64* mpage, int H, int W,
     g.n = D - 7;
     __syncthreads();
     s.rows[lane] = row;
-    // the quiet rings
-    bool dirty = false;
-    for (int k = 1; k <= QR_MAX_QUIET; ++k) {
-        if (k > quiet) break;
-#pragma unroll
-        for (int t0 = 0; t0 < 128; t0 += 64) {
-            const int t = t0 + lane - k;
-            if (t < D + k)
-                dirty = dirty || qr_sample(mpage, H, W, nw, g, t, -k) || qr_sample(mpage, H, W, nw, g, t, D - 1 + k) || qr_sample(mpage, H, W, nw, g, -k, t) ||
-                        qr_sample(mpage, H, W, nw, g, D - 1 + k, t);
-        }
-    }
+    const bool dirty = qr_quiet_dirty<128>(mpage, H, W, nw, g, D, quiet, lane);
     __syncthreads();
-    if (__ballot(dirty)) return false;
-    // format information: lane i < 15 reads bit i of both copies, lanes < 32 measure a word each
-    int b1 = 0, b2 = 0;
-    if (lane < 15) {
-        const int r1 = lane < 6 ? lane : (lane == 6 ? 7 : 8), c1 = lane < 8 ? 8 : (lane == 8 ? 7 : 14 - lane);
-        const int r2 = lane < 8 ? 8 : D - 15 + lane, c2 = lane < 8 ? D - 1 - lane : 8;
-        b1 = (int)((s.rows[r1 & 63] >> (c1 & 63)) & 1ull);
-        b2 = (int)((s.rows[r2 & 63] >> (c2 & 63)) & 1ull);
-    }
-    const int f1 = (int)(__ballot(b1) & 0x7fffull), f2 = (int)(__ballot(b2) & 0x7fffull);
-    const int fw = QR_FORMAT[lane & 31];
-    const int k1 = wave_min(lane < 32 ? (__popc(f1 ^ fw) << 5) | lane : BIG), k2 = wave_min(lane < 32 ? (__popc(f2 ^ fw) << 5) | lane : BIG);
-    int word, fdist;
-    if ((k1 >> 5) <= 3) { word = k1 & 31; fdist = k1 >> 5; }
-    else if ((k2 >> 5) <= 3) { word = k2 & 31; fdist = (k2 >> 5) + 16; }
-    else return false;
-    const int level = (word >> 3) ^ 1, mpat = word & 7;
+    if (dirty) return false;
+    int level, mpat, fdist;
+    if (!qr_format([&](int r, int c) { return (int)((s.rows[r & 63] >> (c & 63)) & 1ull); }, D, lane, level, mpat, fdist)) return false;
     // unmask the data modules
     if (lane < D) {
         u64 m = 0;
@@ -282,9 +344,9 @@ __device__ __forceinline__ bool qr_try(QrLds& s, const u64* mpage, int H, int W,
     }
     __syncthreads();
     // codewords in placement order
-    const int total = QR_TOTAL[version - 1], poff = QR_PLACE_OFF[version - 1];
+    const int total = clampi(QRV_TOTAL[version - 1], 1, QR_MAX_TOTAL), poff = QR_PLACE_OFF[version - 1];
 #pragma unroll 1
-    for (int k = lane; k < 384; k += 64) {
+    for (int k = lane; k < QR_RAW; k += 64) {
         int val = 0;
         if (k < total) {
             for (int bit = 0; bit < 8; ++bit) {
@@ -296,81 +358,9 @@ __device__ __forceinline__ bool qr_try(QrLds& s, const u64* mpage, int H, int W,
         s.raw[k] = (unsigned char)val;
     }
     __syncthreads();
-    const unsigned char* bs = QR_BLOCKS + ((version - 1) * 4 + level) * 4;
-    const int nb = clampi(bs[0], 1, QR_MAX_NB), nshort = clampi(bs[1], 1, nb), dlen = bs[2], ec = clampi(bs[3], 2, QR_MAX_EC);
-    const int ndata = nb * dlen + (nb - nshort);
-    if (dlen + (nshort < nb ? 1 : 0) + ec > QR_MAX_BLOCK || ndata > QR_MAX_DATA || ndata + nb * ec > QR_MAX_TOTAL) return false;   // (the tables never say so)
-    int errors = 0, dpos = 0;
-    for (int blk = 0; blk < QR_MAX_NB; ++blk) {
-        if (blk >= nb) break;
-        const int nd = dlen + (blk >= nshort ? 1 : 0), len = nd + ec;
-#pragma unroll
-        for (int p0 = 0; p0 < 192; p0 += 64) {
-            const int p = p0 + lane;
-            if (p < len) {
-                const int src = p < dlen ? p * nb + blk : (p < nd ? dlen * nb + blk - nshort : ndata + (p - nd) * nb + blk);
-                s.blk[p] = s.raw[clampi(src, 0, 383)];
-            }
-        }
-        __syncthreads();
-        if (qr_syndromes(s, len, ec, lane)) {
-            if (lane == 0) qr_locator(s, ec);
-            __syncthreads();
-            const int L = s.L;
-            if (L > ec / 2 || L > 15) return false;
-            int roots = 0;
-            bool bad = false;
-#pragma unroll
-            for (int p0 = 0; p0 < 192; p0 += 64) {
-                const int p = p0 + lane, e = (len - 1 - p) % 255, xi = (255 - e) % 255;   // X = alpha^e, xi = log of X^-1
-                int val = 1, den = 0, num = 0;
-                if (p < len) {
-                    val = 0;
-                    for (int i = 0; i <= 15; ++i) {
-                        if (i > L) break;
-                        val ^= gmul_exp(s, s.C[i], (xi * i) % 255);
-                        if (i & 1) den ^= gmul_exp(s, s.C[i], (xi * (i - 1)) % 255);
-                        if (i < L) num ^= gmul_exp(s, s.O[i], (xi * i) % 255);
-                    }
-                }
-                const bool root = val == 0;
-                if (root) {
-                    if (den == 0) bad = true;
-                    else s.blk[p] ^= (unsigned char)gmul_exp(s, gmul_exp(s, num, 255 - s.log[den & 255]), e);
-                }
-                roots += __popcll(__ballot(root));
-            }
-            __syncthreads();
-            if (__ballot(bad) || roots != L) return false;
-            if (qr_syndromes(s, len, ec, lane)) return false;
-            errors += L;
-        }
-#pragma unroll
-        for (int p0 = 0; p0 < 192; p0 += 64) {
-            const int p = p0 + lane;
-            if (p < nd && dpos + p < QR_MAX_DATA) od[dpos + p] = s.blk[p];
-        }
-        dpos += nd;
-        __syncthreads();
-    }
-    if (lane == 0) {
-        // the hull: the four outer module corners, (u, v) = 2 (i, j) - 6 in {-7, 2 n + 7}
-        const int n = g.n;
-        i64 x0 = 0, x1 = 0, y0 = 0, y1 = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int u = (k & 1) ? 2 * n + 7 : -7, v = (k & 2) ? 2 * n + 7 : -7;
-            const i64 qx = floor_div((i64)g.ax * 2 * n + (i64)u * g.abx + (i64)v * g.acx, 4 * n);
-            const i64 qy = floor_div((i64)g.ay * 2 * n + (i64)u * g.aby + (i64)v * g.acy, 4 * n);
-            x0 = k == 0 || qx < x0 ? qx : x0; x1 = k == 0 || qx > x1 ? qx : x1;
-            y0 = k == 0 || qy < y0 ? qy : y0; y1 = k == 0 || qy > y1 ? qy : y1;
-        }
-        const auto cl = [](i64 v, int hi) { return (int)(v < 0 ? 0 : (v > hi ? hi : v)); };
-        o[0] = cl(y0, H - 1); o[1] = cl(x0, W - 1); o[2] = cl(y1 - 1, H - 1); o[3] = cl(x1 - 1, W - 1); o[4] = ida;
-        o[5] = version; o[6] = level; o[7] = mpat; o[8] = ndata; o[9] = errors;
-        o[10] = iabs(g.abx) >= iabs(g.aby) ? (g.abx > 0 ? 0 : 2) : (g.aby > 0 ? 1 : 3);
-        o[11] = fdist; o[12] = timing; o[13] = 1;
-    }
+    int ndata, errors;
+    if (!qr_blocks<QR_MAX_NB, QR_RAW, QR_MAX_DATA>(s.rs, s.raw, total, version, level, lane, od, ndata, errors)) return false;
+    if (lane == 0) qr_write_result(o, g, H, W, ida, version, level, mpat, ndata, errors, fdist, timing);
     return true;
 }
 
@@ -383,189 +373,19 @@ __global__ __launch_bounds__(64) void qr_decode_kernel(const u64* mask, const in
     if (nf > max_finders || a >= nf || nf > QR_MAX_FINDERS) return;
     const u64* mpage = mask + (size_t)pg * H * nw;
     const int4 f = lane < nf ? finders[(size_t)pg * max_finders + lane] : make_int4(0, 0, 0, 0);
-    const int ax = __shfl(f.x, a), ay = __shfl(f.y, a), ma = __shfl(f.z, a), ida = __shfl(f.w, a);
-    for (int i = lane; i < 512; i += 64) s.exp[i] = QR_EXP[i];
-    for (int i = lane; i < 256; i += 64) s.log[i] = QR_LOG[i];
-    // A's partners: lane = B, loop over C; the valid pairs in the order of (|AB|^2 + |AC|^2, root of B, root of C), the first that decodes
-    const bool b_ok = lane < nf && lane != a && iabs(f.x - ax) <= QR_SPAN && iabs(f.y - ay) <= QR_SPAN && 4 * iabs(ma - f.z) <= (ma < f.z ? ma : f.z);
-    const int abx = b_ok ? f.x - ax : 0, aby = b_ok ? f.y - ay : 0;   // (zero where the products below could leave 64 bits)
-    const i64 lab = (i64)abx * abx + (i64)aby * aby;
-    int pl = -1, pb = -1, pc = -1;   // the key tried last
-#pragma unroll 1
-    for (int attempt = 0; attempt < QR_PAIR_TRIES; ++attempt) {
-        int best_l = BIG, best_idc = BIG, best_c = 0;
-#pragma unroll 1
-        for (int c = 0; c < QR_MAX_FINDERS; ++c) {
-            if (c >= nf) break;
-            const int cx = __shfl(f.x, c), cy = __shfl(f.y, c), mc = __shfl(f.z, c), idc = __shfl(f.w, c);
-            bool ok = b_ok && c != a && c != lane && iabs(cx - ax) <= QR_SPAN && iabs(cy - ay) <= QR_SPAN && 4 * iabs(ma - mc) <= (ma < mc ? ma : mc);
-            const int acx = ok ? cx - ax : 0, acy = ok ? cy - ay : 0;
-            const i64 lac = (i64)acx * acx + (i64)acy * acy, dot = (i64)abx * acx + (i64)aby * acy, cross = (i64)abx * acy - (i64)aby * acx;
-            ok = ok && 4 * labs64(lab - lac) <= (lab < lac ? lab : lac) && 64 * dot * dot <= lab * lac && cross > 0;
-            ok = ok && reach_mask(lab + lac, (i64)ma + f.z + mc) != 0u;
-            const int l = ok ? (int)(lab + lac) : BIG;   // (< 2^29)
-            ok = ok && (l > pl || (l == pl && (f.w > pb || (f.w == pb && idc > pc))));   // behind the key tried last
-            if (ok && (l < best_l || (l == best_l && idc < best_idc))) { best_l = l; best_idc = idc; best_c = c; }
-        }
-        const int min_l = wave_min(best_l);
-        if (min_l == BIG) return;
-        const int min_b = wave_min(best_l == min_l ? f.w : BIG);
-        const u64 win = __ballot(best_l == min_l && f.w == min_b);   // roots are distinct: one lane
-        if (!win) return;
-        const int b = __ffsll((long long)win) - 1, c = __shfl(best_c, b) & 63;
-        pl = min_l; pb = min_b; pc = __shfl(best_idc, b);
-        QrGrid g;
-        g.ax = ax; g.ay = ay; g.n = 14;
-        g.abx = __shfl(f.x, b) - ax; g.aby = __shfl(f.y, b) - ay; g.acx = __shfl(f.x, c) - ax; g.acy = __shfl(f.y, c) - ay;
-        const unsigned reach = reach_mask((i64)min_l, (i64)ma + __shfl(f.z, b) + __shfl(f.z, c));
-        if (qr_try(s, mpage, H, W, nw, g, reach, quiet, timing_max, ida, lane, res + ((size_t)pg * max_finders + a) * RES_INTS,
-                   resdata + ((size_t)pg * max_finders + a) * QR_MAX_DATA))
-            return;
-        __syncthreads();
-    }
+    const int ida = __shfl(f.w, a);
+    int* o = res + ((size_t)pg * max_finders + a) * RES_INTS;
+    unsigned char* od = resdata + ((size_t)pg * max_finders + a) * QR_MAX_DATA;
+    rs_load_tables(s.rs, QR_EXP, QR_LOG, lane);
+    qr_pairs(f, nf, a, lane, [](i64 l2, i64 m) { return reach_mask(l2, m); }, [&](const QrGrid& g, u64 reach) { return qr_try(s, mpage, H, W, nw, g, reach, quiet, timing_max, ida, lane, o, od); });
 }
 
-// 6: tmp [B][max_codes][6] = y0, x0, y1, x1, root, slot
-__global__ __launch_bounds__(256) void qr_output_kernel(const int* res_all, const unsigned char* resdata_all, const int* nfind, int max_finders, int max_codes,
-                                                        int* tmp_all, int* counts, int* codes, int* data, int* finder_counts) {
-    __shared__ int s_key[QR_MAX_CODES * 5];
-    __shared__ int s_n;
-    const int pg = blockIdx.x;
-    const int nf = nfind[pg];
-    const int* res = res_all + (size_t)pg * max_finders * RES_INTS;
-    int* tmp = tmp_all + (size_t)pg * max_codes * 6;
-    if (threadIdx.x == 0) {
-        s_n = 0;
-        if (finder_counts) finder_counts[pg] = nf;
-    }
-    __syncthreads();
-    const int lim = nf > max_finders ? 0 : nf;   // a page with too many finders is not read
-    for (int a = threadIdx.x; a < lim; a += 256) {
-        const int* r = res + a * RES_INTS;
-        if (r[13] != 1) continue;
-        const int idx = atomicAdd(&s_n, 1);
-        if (idx >= max_codes) continue;
-        int* o = tmp + idx * 6;
-        o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3]; o[4] = r[4]; o[5] = a;
-    }
-    __syncthreads();
-    const int n = s_n;
-    if (threadIdx.x == 0) counts[pg] = n;
-    if (n > max_codes) return;   // overflow: the count is all that is reported
-    int* out = codes + (size_t)pg * max_codes * 12;
-    int* odat = data + (size_t)pg * max_codes * QR_MAX_DATA;
-    const unsigned char* rd = resdata_all + (size_t)pg * max_finders * QR_MAX_DATA;
-    rank_sort<5>(s_key, tmp, 6, n, [=](int i, int rank, const int (&k)[5]) {
-        const int slot = clampi(tmp[i * 6 + 5], 0, max_finders - 1);
-        const int* r = res + slot * RES_INTS;
-        int* o = out + (size_t)rank * 12;
-        o[0] = k[1]; o[1] = k[0]; o[2] = k[3]; o[3] = k[2];
-        for (int j = 0; j < 8; ++j) o[4 + j] = r[5 + j];
-        const int nd = r[8];
-        for (int j = 0; j < QR_MAX_DATA; ++j) odat[(size_t)rank * QR_MAX_DATA + j] = j < nd ? rd[(size_t)slot * QR_MAX_DATA + j] : 0;
-    });
-}
-
-}  // namespace
-
-// the workspace's regions: one layout sizes it (qrcodes_workspace_bytes) and carves it (qrcodes_launch)
-struct QrWorkspace {
-    unsigned long long* mask; int* runoff; unsigned short *rxs, *rxe; int* parent; int4* box; int* area;
-    int* nfind; int4* finders; int* res; unsigned char* resdata; int* tmp;
-};
-static QrWorkspace qrcodes_layout(Arena& a, int B, int H, int W, int max_finders, int max_codes) {
-    const size_t runcap = run_cap(H, W), nw = (W + 63) / 64;
-    QrWorkspace w;
-    w.mask = a.take<unsigned long long>((size_t)B * H * nw);
-    w.runoff = a.take<int>((size_t)B * (H + 1));   // run counts -> offsets
-    w.rxs = a.take<unsigned short>((size_t)B * runcap); w.rxe = a.take<unsigned short>((size_t)B * runcap);
-    w.parent = a.take<int>((size_t)B * runcap);
-    w.box = a.take<int4>((size_t)B * runcap);      // at a root: x0, x1, y0, y1 of its component
-    w.area = a.take<int>((size_t)B * runcap);      // at a root: its component's ink
-    w.nfind = a.take<int>((size_t)B);
-    w.finders = a.take<int4>((size_t)B * max_finders);
-    w.res = a.take<int>((size_t)B * max_finders * RES_INTS);
-    w.resdata = a.take<unsigned char>((size_t)B * max_finders * QR_MAX_DATA);
-    w.tmp = a.take<int>((size_t)B * max_codes * 6);
-    return w;
-}
-
-static bool qrcodes_args_ok(int B, int H, int W, int max_finders, int max_codes) {
-    if (B <= 0 || H <= 0 || W <= 0 || H > 65535 || W > 65535 || max_codes < 1 || max_codes > QR_MAX_CODES || max_finders < 1 || max_finders > QR_MAX_FINDERS)
-        return false;
-    return (size_t)B * H < (1ull << 31) && run_cap(H, W) < (1ull << 31);
-}
-
-bool qr_params_ok(int min_module, int max_module, int quiet, int centre_tol, int ring_tol, int timing_max, int max_finders, int max_codes) {
-    return min_module >= 1 && max_module >= min_module && max_module <= QR_MAX_MODULE && quiet >= 0 && quiet <= QR_MAX_QUIET && centre_tol >= 0 &&
-           centre_tol <= QR_MAX_TOL && ring_tol >= 0 && ring_tol <= QR_MAX_TOL && timing_max >= 0 && timing_max <= QR_MAX_TIMING && max_finders >= 1 &&
-           max_finders <= QR_MAX_FINDERS && max_codes >= 1 && max_codes <= QR_MAX_CODES;
-}
-
-size_t qrcodes_workspace_bytes(int B, int H, int W, int max_finders, int max_codes) {
-    if (!qrcodes_args_ok(B, H, W, max_finders, max_codes)) return 0;
-    Arena a;
-    qrcodes_layout(a, B, H, W, max_finders, max_codes);
-    return a.off;
-}
-
-hipError_t qrcodes_launch(const QrParams& p, void* workspace, size_t ws_bytes, hipStream_t st) {
-    const int B = p.B, H = p.H, W = p.W;
-    if (!qrcodes_args_ok(B, H, W, p.max_finders, p.max_codes) ||
-        !qr_params_ok(p.min_module, p.max_module, p.quiet, p.centre_tol, p.ring_tol, p.timing_max, p.max_finders, p.max_codes))
-        return hipErrorInvalidValue;
-    if (!p.rgb || !p.codes || !p.data || !p.counts) return hipErrorInvalidValue;
-    Arena a(workspace, ws_bytes);
-    const QrWorkspace w = qrcodes_layout(a, B, H, W, p.max_finders, p.max_codes);
-    if (a.overflow) return hipErrorOutOfMemory;
-    const int nw = (W + 63) / 64;
-    const size_t runcap = run_cap(H, W);
-    const unsigned long long* mask;
-    hipError_t e;
-    if ((e = hipMemsetAsync(w.nfind, 0, sizeof(int) * (size_t)B, st)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(w.res, 0, sizeof(int) * (size_t)B * p.max_finders * RES_INTS, st)) != hipSuccess) return e;
-    if ((e = ink_mask_resolve(p.rgb, p.mask_in, p.mask_out, w.mask, B, H, W, p.threshold, st, &mask)) != hipSuccess) return e;
-    const int rows = B * H;
-    const dim3 grows = row_wave_grid(rows);
-    run_count_launch(mask, w.runoff, B, H, nw, st);
-    row_scan_launch(w.runoff, nullptr, B, H, st);
-    run_fill_launch(mask, w.runoff, w.rxs, w.rxe, w.parent, w.box, B, H, nw, runcap, st);
-    run_merge_launch(w.runoff, w.rxs, w.rxe, w.parent, B, H, runcap, st);
-    hipLaunchKernelGGL(qr_area_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.area, H, runcap, rows);
-    hipLaunchKernelGGL(qr_accum_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.box, w.area, H, runcap, rows);
-    hipLaunchKernelGGL(qr_finders_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.box, w.area, H, runcap, p.min_module, p.max_module,
-                       p.centre_tol, p.ring_tol, p.max_finders, w.nfind, w.finders, rows);
-    hipLaunchKernelGGL(qr_decode_kernel, dim3(p.max_finders, B), dim3(64), 0, st, mask, w.finders, w.nfind, H, W, nw, p.max_finders, p.quiet, p.timing_max, w.res,
-                       w.resdata);
-    hipLaunchKernelGGL(qr_output_kernel, dim3(B), dim3(256), 0, st, w.res, w.resdata, w.nfind, p.max_finders, p.max_codes, w.tmp, p.counts, p.codes, p.data,
-                       p.finder_counts);
-    return hipGetLastError();
-}
-
-// ---- every version, 1-40 (lumina_ocr_qrcodes_versions; definition restated in tests/qr_versions_reference.py) ---------------------------------
-// Stage 1 is the pass above, kernel for kernel.  Stage 2 (qr_decode_versions) runs behind it for the finders it gave no symbol: one wave per
-// (page, finder A) again, A's nearest valid pairs with a version 11 .. max_version in reach in turn.  Per pair the versions in reach are
-// scored on their timing patterns alone (lanes over the pattern's modules), the best one's version information must agree, then the grid
-// (up to 177 x 177, three words a row) is sampled with lanes over columns and a loop over rows: the numerators advance by a constant from
-// row to row, so one division at the top and an add-and-carry per row give the floor division exactly, and a ballot is the row's word.
-// The function mask is built in LDS from the alignment centres and the fixed areas (lanes over rows); the codewords are placed without a
-// table: lanes over the two-column strips count their free modules, a wave prefix sum gives each strip its bit offset, and each lane walks
-// its strip and ORs whole and partial bytes into the codewords (LDS atomics).  Blocks are corrected by rs_gf256.h (field 0x11D, first root
-// 0).  Every loop has a constant bound, every table and LDS index is clamped, and no wave waits for another.
-#include "qr_version_tables.h"
-#include "rs_gf256.h"
-
-namespace {
-
-constexpr int QRV_ROWS = 177;                   // modules a side at version 40
-constexpr int QRV_RAW = 3712;                   // >= QRV_MAX_TOTAL, a multiple of 4
-constexpr int QRV_RS_LEN = 192, QRV_RS_EC = 30;
-static_assert(QRV_MAX_BLOCK <= QRV_RS_LEN && QRV_MAX_TOTAL <= QRV_RAW && QRV_VERSIONS == 40, "qr_version_tables.h");
+// ---- stage 2: versions 11-40 ---------------------------------------------------------------------------------------------------------------
 
 struct QrvLds {
     u64 grid[QRV_ROWS * 3], func[QRV_ROWS * 3];   // module rows and the function mask: bit col % 64 of word col / 64
     unsigned raw[QRV_RAW / 4];                    // the codewords in placement order, as bytes
-    RsLds<QRV_RS_LEN, QRV_RS_EC> rs;
+    RsLds<QR_RS_LEN, QR_RS_EC> rs;
 };
 
 // the versions 11 .. max_version (bit v) in reach of l2 = |AB|^2 + |AC|^2 and m = meA + meB + meC: n within 3 + n / 16 modules
@@ -581,8 +401,6 @@ __device__ __forceinline__ u64 reach_mask_versions(i64 l2, i64 m, int max_versio
     }
     return out;
 }
-
-__device__ __forceinline__ int floor_div32(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }   // b > 0
 
 // bit (row, col) of a 177 x 3 word array; both clamped
 __device__ __forceinline__ int qrv_bit(const u64* rows, int row, int col) {
@@ -703,36 +521,11 @@ __device__ __forceinline__ bool qr_try_versions(QrvLds& s, const u64* mpage, int
             }
         }
     }
-    // the quiet rings
-    bool dirty = false;
-    for (int k = 1; k <= QR_MAX_QUIET; ++k) {
-        if (k > quiet) break;
-#pragma unroll 1
-        for (int t0 = 0; t0 < 192; t0 += 64) {
-            const int t = t0 + lane - k;
-            if (t < D + k)
-                dirty = dirty || qr_sample(mpage, H, W, nw, g, t, -k) || qr_sample(mpage, H, W, nw, g, t, D - 1 + k) || qr_sample(mpage, H, W, nw, g, -k, t) ||
-                        qr_sample(mpage, H, W, nw, g, D - 1 + k, t);
-        }
-    }
+    const bool dirty = qr_quiet_dirty<192>(mpage, H, W, nw, g, D, quiet, lane);
     __syncthreads();
-    if (__ballot(dirty)) return false;
-    // format information: lane i < 15 reads bit i of both copies, lanes < 32 measure a word each
-    int b1 = 0, b2 = 0;
-    if (lane < 15) {
-        const int r1 = lane < 6 ? lane : (lane == 6 ? 7 : 8), c1 = lane < 8 ? 8 : (lane == 8 ? 7 : 14 - lane);
-        const int r2 = lane < 8 ? 8 : D - 15 + lane, c2 = lane < 8 ? D - 1 - lane : 8;
-        b1 = qrv_bit(s.grid, r1, c1);
-        b2 = qrv_bit(s.grid, r2, c2);
-    }
-    const int f1 = (int)(__ballot(b1) & 0x7fffull), f2 = (int)(__ballot(b2) & 0x7fffull);
-    const int fw = QRV_FORMAT[lane & 31];
-    const int k1 = wave_min(lane < 32 ? (__popc(f1 ^ fw) << 5) | lane : BIG), k2 = wave_min(lane < 32 ? (__popc(f2 ^ fw) << 5) | lane : BIG);
-    int word, fdist;
-    if ((k1 >> 5) <= 3) { word = k1 & 31; fdist = k1 >> 5; }
-    else if ((k2 >> 5) <= 3) { word = k2 & 31; fdist = (k2 >> 5) + 16; }
-    else return false;
-    const int level = (word >> 3) ^ 1, mpat = word & 7;
+    if (dirty) return false;
+    int level, mpat, fdist;
+    if (!qr_format([&](int r, int c) { return qrv_bit(s.grid, r, c); }, D, lane, level, mpat, fdist)) return false;
     // the function mask (lanes over rows) and cleared codewords
     {
         const unsigned char* ac = QRV_ALIGN + (version - 1) * QRV_MAX_ALIGN;
@@ -787,57 +580,14 @@ __device__ __forceinline__ bool qr_try_versions(QrvLds& s, const u64* mpage, int
         if (64 + lane < strips) qrv_walk(s, 64 + lane, D, mpat, total, off1);
     }
     __syncthreads();
-    const unsigned char* raw = reinterpret_cast<const unsigned char*>(s.raw);
-    const int bi = (version - 1) * 4 + (level & 3);
-    const int nb = clampi(QRV_NB[bi], 1, QRV_MAX_NB), ec = clampi(QRV_EC[bi], 2, QRV_RS_EC);
-    const int nshort = nb - total % nb, dlen = total / nb - ec, ndata = total - nb * ec;
-    if (dlen < 1 || dlen + 1 + ec > QRV_RS_LEN || ndata < 1 || ndata > QRV_MAX_DATA) return false;   // (the tables never say so)
-    int errors = 0, dpos = 0;
-#pragma unroll 1
-    for (int blk = 0; blk < QRV_MAX_NB; ++blk) {
-        if (blk >= nb) break;
-        const int nd = dlen + (blk >= nshort ? 1 : 0), len = nd + ec;
-#pragma unroll
-        for (int p0 = 0; p0 < QRV_RS_LEN; p0 += 64) {
-            const int p = p0 + lane;
-            if (p < len) {
-                const int src = p < dlen ? p * nb + blk : (p < nd ? dlen * nb + blk - nshort : ndata + (p - nd) * nb + blk);
-                s.rs.blk[p] = raw[clampi(src, 0, QRV_RAW - 1)];
-            }
-        }
-        __syncthreads();
-        const int e = rs_correct_block(s.rs, len, ec, 0, lane);
-        if (e < 0) return false;
-        errors += e;
-#pragma unroll
-        for (int p0 = 0; p0 < QRV_RS_LEN; p0 += 64) {
-            const int p = p0 + lane;
-            if (p < nd && dpos + p < QRV_MAX_DATA) od[dpos + p] = s.rs.blk[p];
-        }
-        dpos += nd;
-        __syncthreads();
-    }
-    if (lane == 0) {
-        const int n = g.n;
-        i64 x0 = 0, x1 = 0, y0 = 0, y1 = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int u = (k & 1) ? 2 * n + 7 : -7, v = (k & 2) ? 2 * n + 7 : -7;
-            const i64 qx = floor_div((i64)g.ax * 2 * n + (i64)u * g.abx + (i64)v * g.acx, 4 * n);
-            const i64 qy = floor_div((i64)g.ay * 2 * n + (i64)u * g.aby + (i64)v * g.acy, 4 * n);
-            x0 = k == 0 || qx < x0 ? qx : x0; x1 = k == 0 || qx > x1 ? qx : x1;
-            y0 = k == 0 || qy < y0 ? qy : y0; y1 = k == 0 || qy > y1 ? qy : y1;
-        }
-        const auto cl = [](i64 v, int hi) { return (int)(v < 0 ? 0 : (v > hi ? hi : v)); };
-        o[0] = cl(y0, H - 1); o[1] = cl(x0, W - 1); o[2] = cl(y1 - 1, H - 1); o[3] = cl(x1 - 1, W - 1); o[4] = ida;
-        o[5] = version; o[6] = level; o[7] = mpat; o[8] = ndata; o[9] = errors;
-        o[10] = iabs(g.abx) >= iabs(g.aby) ? (g.abx > 0 ? 0 : 2) : (g.aby > 0 ? 1 : 3);
-        o[11] = fdist; o[12] = timing; o[13] = 1;
-    }
+    int ndata, errors;
+    if (!qr_blocks<QRV_MAX_NB, QRV_RAW, QRV_MAX_DATA>(s.rs, reinterpret_cast<const unsigned char*>(s.raw), total, version, level, lane, od, ndata, errors))
+        return false;
+    if (lane == 0) qr_write_result(o, g, H, W, ida, version, level, mpat, ndata, errors, fdist, timing);
     return true;
 }
 
-// stage 2: one wave per (page, finder) that stage 1 left without a symbol; res as stage 1's, resdata [B][max_finders][QRV_MAX_DATA]
+// 5b: one wave per (page, finder) that stage 1 left without a symbol; res as stage 1's, resdata [B][max_finders][QRV_MAX_DATA]
 __global__ __launch_bounds__(64) void qr_decode_versions_kernel(const u64* mask, const int4* finders, const int* nfind, int H, int W, int nw, int max_finders,
                                                                 int quiet, int timing_max, int max_version, int* res, unsigned char* resdata) {
     __shared__ QrvLds s;
@@ -848,122 +598,123 @@ __global__ __launch_bounds__(64) void qr_decode_versions_kernel(const u64* mask,
     if (o[13] == 1) return;   // stage 1 has A's symbol
     const u64* mpage = mask + (size_t)pg * H * nw;
     const int4 f = lane < nf ? finders[(size_t)pg * max_finders + lane] : make_int4(0, 0, 0, 0);
-    const int ax = __shfl(f.x, a), ay = __shfl(f.y, a), ma = __shfl(f.z, a), ida = __shfl(f.w, a);
+    const int ida = __shfl(f.w, a);
+    unsigned char* od = resdata + ((size_t)pg * max_finders + a) * QRV_MAX_DATA;
     rs_load_tables(s.rs, QR_EXP, QR_LOG, lane);
-    // A's partners as in stage 1 (lane = B, loop over C), with stage 2's reach
-    const bool b_ok = lane < nf && lane != a && iabs(f.x - ax) <= QR_SPAN && iabs(f.y - ay) <= QR_SPAN && 4 * iabs(ma - f.z) <= (ma < f.z ? ma : f.z);
-    const int abx = b_ok ? f.x - ax : 0, aby = b_ok ? f.y - ay : 0;
-    const i64 lab = (i64)abx * abx + (i64)aby * aby;
-    int pl = -1, pb = -1, pc = -1;   // the key tried last
-#pragma unroll 1
-    for (int attempt = 0; attempt < QR_PAIR_TRIES; ++attempt) {
-        int best_l = BIG, best_idc = BIG, best_c = 0;
-#pragma unroll 1
-        for (int c = 0; c < QR_MAX_FINDERS; ++c) {
-            if (c >= nf) break;
-            const int cx = __shfl(f.x, c), cy = __shfl(f.y, c), mc = __shfl(f.z, c), idc = __shfl(f.w, c);
-            bool ok = b_ok && c != a && c != lane && iabs(cx - ax) <= QR_SPAN && iabs(cy - ay) <= QR_SPAN && 4 * iabs(ma - mc) <= (ma < mc ? ma : mc);
-            const int acx = ok ? cx - ax : 0, acy = ok ? cy - ay : 0;
-            const i64 lac = (i64)acx * acx + (i64)acy * acy, dot = (i64)abx * acx + (i64)aby * acy, cross = (i64)abx * acy - (i64)aby * acx;
-            ok = ok && 4 * labs64(lab - lac) <= (lab < lac ? lab : lac) && 64 * dot * dot <= lab * lac && cross > 0;
-            const int l = ok ? (int)(lab + lac) : BIG;   // (< 2^29)
-            ok = ok && (l > pl || (l == pl && (f.w > pb || (f.w == pb && idc > pc))));   // behind the key tried last
-            ok = ok && (l < best_l || (l == best_l && idc < best_idc));
-            if (ok && reach_mask_versions(lab + lac, (i64)ma + f.z + mc, max_version) != 0ull) { best_l = l; best_idc = idc; best_c = c; }
-        }
-        const int min_l = wave_min(best_l);
-        if (min_l == BIG) return;
-        const int min_b = wave_min(best_l == min_l ? f.w : BIG);
-        const u64 win = __ballot(best_l == min_l && f.w == min_b);   // roots are distinct: one lane
-        if (!win) return;
-        const int b = __ffsll((long long)win) - 1, c = __shfl(best_c, b) & 63;
-        pl = min_l; pb = min_b; pc = __shfl(best_idc, b);
-        QrGrid g;
-        g.ax = ax; g.ay = ay; g.n = 54;
-        g.abx = __shfl(f.x, b) - ax; g.aby = __shfl(f.y, b) - ay; g.acx = __shfl(f.x, c) - ax; g.acy = __shfl(f.y, c) - ay;
-        const u64 reach = reach_mask_versions((i64)min_l, (i64)ma + __shfl(f.z, b) + __shfl(f.z, c), max_version);
-        if (qr_try_versions(s, mpage, H, W, nw, g, reach, quiet, timing_max, ida, lane, o, resdata + ((size_t)pg * max_finders + a) * QRV_MAX_DATA)) return;
-        __syncthreads();
-    }
+    qr_pairs(f, nf, a, lane, [=](i64 l2, i64 m) { return reach_mask_versions(l2, m, max_version); },
+             [&](const QrGrid& g, u64 reach) { return qr_try_versions(s, mpage, H, W, nw, g, reach, quiet, timing_max, ida, lane, o, od); });
 }
 
-// the output of both stages: as qr_output_kernel with byte rows of QRV_MAX_DATA; a symbol's codewords come from the stage that read it
-__global__ __launch_bounds__(256) void qr_output_versions_kernel(const int* res_all, const unsigned char* resdata1_all, const unsigned char* resdata2_all,
-                                                                 const int* nfind, int max_finders, int max_codes, int* tmp_all, int* counts, int* codes,
-                                                                 unsigned char* data, int* finder_counts) {
-    __shared__ int s_key[QR_MAX_CODES * 5];
-    __shared__ int s_slot[QR_MAX_CODES];
-    __shared__ int s_n;
-    const int pg = blockIdx.x;
-    const int nf = nfind[pg];
-    const int* res = res_all + (size_t)pg * max_finders * RES_INTS;
-    int* tmp = tmp_all + (size_t)pg * max_codes * 6;
-    if (threadIdx.x == 0) {
-        s_n = 0;
-        if (finder_counts) finder_counts[pg] = nf;
-    }
+// ---- 6: the output ----------------------------------------------------------------------------------------------------------------------------
+
+struct QrOutLds { int key[QR_MAX_CODES * 5], slot[QR_MAX_CODES], n; };
+
+// a page's valid results (one work-group): counted, gathered into tmp [max_codes][6] = y0, x0, y1, x1, root, slot, rank-sorted, the 12-int
+// rows written -> the number of rows, s.slot[rank] the finder slot of row rank.  An overflowing list has no rows: its count is all that
+// is reported.
+__device__ __forceinline__ int qr_output_rows(QrOutLds& s, const int* res, int nf, int max_finders, int max_codes, int* tmp, int* out) {
+    if (threadIdx.x == 0) s.n = 0;
     __syncthreads();
     const int lim = nf > max_finders ? 0 : nf;   // a page with too many finders is not read
     for (int a = threadIdx.x; a < lim; a += 256) {
         const int* r = res + a * RES_INTS;
         if (r[13] != 1) continue;
-        const int idx = atomicAdd(&s_n, 1);
+        const int idx = atomicAdd(&s.n, 1);
         if (idx >= max_codes) continue;
         int* o = tmp + idx * 6;
         o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3]; o[4] = r[4]; o[5] = a;
     }
     __syncthreads();
-    const int n = s_n;
-    if (threadIdx.x == 0) counts[pg] = n;
-    if (n > max_codes) return;   // overflow: the count is all that is reported
-    int* out = codes + (size_t)pg * max_codes * 12;
-    rank_sort<5>(s_key, tmp, 6, n, [=](int i, int rank, const int (&k)[5]) {
+    const int n = s.n;
+    if (n > max_codes) return n;
+    int* slots = s.slot;
+    rank_sort<5>(s.key, tmp, 6, n, [=](int i, int rank, const int (&k)[5]) {
         const int slot = clampi(tmp[i * 6 + 5], 0, max_finders - 1);
         const int* r = res + slot * RES_INTS;
         int* o = out + (size_t)rank * 12;
         o[0] = k[1]; o[1] = k[0]; o[2] = k[3]; o[3] = k[2];
         for (int j = 0; j < 8; ++j) o[4 + j] = r[5 + j];
-        s_slot[clampi(rank, 0, QR_MAX_CODES - 1)] = slot;
+        slots[clampi(rank, 0, QR_MAX_CODES - 1)] = slot;
     });
     __syncthreads();
-    unsigned char* odat = data + (size_t)pg * max_codes * QRV_MAX_DATA;
+    return n;
+}
+
+// the output kernel of either call: DataOut is int (stage 1's codewords alone, rows of QR_MAX_DATA) or unsigned char (rows of QRV_MAX_DATA,
+// a symbol's codewords from the stage that read it)
+template <class DataOut, int ROW>
+__global__ __launch_bounds__(256) void qr_output_kernel(const int* res_all, const unsigned char* resdata1_all, const unsigned char* resdata2_all, const int* nfind,
+                                                        int max_finders, int max_codes, int* tmp_all, int* counts, int* codes, DataOut* data, int* finder_counts) {
+    __shared__ QrOutLds s;
+    const int pg = blockIdx.x;
+    const int nf = nfind[pg];
+    const int* res = res_all + (size_t)pg * max_finders * RES_INTS;
+    const int n = qr_output_rows(s, res, nf, max_finders, max_codes, tmp_all + (size_t)pg * max_codes * 6, codes + (size_t)pg * max_codes * 12);
+    if (threadIdx.x == 0) {
+        counts[pg] = n;
+        if (finder_counts) finder_counts[pg] = nf;
+    }
+    if (n > max_codes) return;
+    DataOut* odat = data + (size_t)pg * max_codes * ROW;
     const unsigned char* rd1 = resdata1_all + (size_t)pg * max_finders * QR_MAX_DATA;
-    const unsigned char* rd2 = resdata2_all + (size_t)pg * max_finders * QRV_MAX_DATA;
-    for (int idx = threadIdx.x; idx < n * QRV_MAX_DATA; idx += 256) {
-        const int rank = idx / QRV_MAX_DATA, j = idx - rank * QRV_MAX_DATA, slot = clampi(s_slot[rank & (QR_MAX_CODES - 1)], 0, max_finders - 1);
+    const unsigned char* rd2 = resdata2_all ? resdata2_all + (size_t)pg * max_finders * QRV_MAX_DATA : nullptr;
+    for (int idx = threadIdx.x; idx < n * ROW; idx += 256) {
+        const int rank = idx / ROW, j = idx - rank * ROW, slot = clampi(s.slot[rank & (QR_MAX_CODES - 1)], 0, max_finders - 1);
         const int* r = res + slot * RES_INTS;
-        const int nd = r[8];
         unsigned char v = 0;
-        if (j < nd) v = r[5] <= QR_VERSIONS ? (j < QR_MAX_DATA ? rd1[(size_t)slot * QR_MAX_DATA + j] : 0) : rd2[(size_t)slot * QRV_MAX_DATA + j];
+        if (j < r[8]) v = r[5] <= QR_VERSIONS || !rd2 ? (j < QR_MAX_DATA ? rd1[(size_t)slot * QR_MAX_DATA + j] : 0) : rd2[(size_t)slot * QRV_MAX_DATA + j];
         odat[idx] = v;
     }
 }
 
-}  // namespace
+// ---- host ----------------------------------------------------------------------------------------------------------------------------------------
 
-bool qr_max_version_ok(int max_version) { return max_version >= QR_VERSIONS && max_version <= QRV_VERSIONS; }
+// the workspace's regions: one layout sizes it (the *_workspace_bytes) and carves it (qr_front_end); resdata2 is the all-versions call's
+struct QrWorkspace {
+    u64* mask; int* runoff; unsigned short *rxs, *rxe; int* parent; int4* box; int* area;
+    int* nfind; int4* finders; int* res; unsigned char *resdata, *resdata2; int* tmp;
+};
+QrWorkspace qrcodes_layout(Arena& a, int B, int H, int W, int max_finders, int max_codes, bool versions) {
+    const size_t runcap = run_cap(H, W), nw = (W + 63) / 64;
+    QrWorkspace w;
+    w.mask = a.take<u64>((size_t)B * H * nw);
+    w.runoff = a.take<int>((size_t)B * (H + 1));   // run counts -> offsets
+    w.rxs = a.take<unsigned short>((size_t)B * runcap); w.rxe = a.take<unsigned short>((size_t)B * runcap);
+    w.parent = a.take<int>((size_t)B * runcap);
+    w.box = a.take<int4>((size_t)B * runcap);      // at a root: x0, x1, y0, y1 of its component
+    w.area = a.take<int>((size_t)B * runcap);      // at a root: its component's ink
+    w.nfind = a.take<int>((size_t)B);
+    w.finders = a.take<int4>((size_t)B * max_finders);
+    w.res = a.take<int>((size_t)B * max_finders * RES_INTS);
+    w.resdata = a.take<unsigned char>((size_t)B * max_finders * QR_MAX_DATA);
+    w.tmp = a.take<int>((size_t)B * max_codes * 6);
+    w.resdata2 = versions ? a.take<unsigned char>((size_t)B * max_finders * QRV_MAX_DATA) : nullptr;
+    return w;
+}
 
-size_t qrcodes_versions_workspace_bytes(int B, int H, int W, int max_finders, int max_codes) {
+bool qrcodes_args_ok(int B, int H, int W, int max_finders, int max_codes) {
+    if (B <= 0 || H <= 0 || W <= 0 || H > 65535 || W > 65535 || max_codes < 1 || max_codes > QR_MAX_CODES || max_finders < 1 || max_finders > QR_MAX_FINDERS)
+        return false;
+    return (size_t)B * H < (1ull << 31) && run_cap(H, W) < (1ull << 31);
+}
+
+size_t qr_workspace_bytes(int B, int H, int W, int max_finders, int max_codes, bool versions) {
     if (!qrcodes_args_ok(B, H, W, max_finders, max_codes)) return 0;
     Arena a;
-    qrcodes_layout(a, B, H, W, max_finders, max_codes);
-    a.take<unsigned char>((size_t)B * max_finders * QRV_MAX_DATA);
+    qrcodes_layout(a, B, H, W, max_finders, max_codes, versions);
     return a.off;
 }
 
-hipError_t qrcodes_versions_launch(const QrVersionsParams& p, void* workspace, size_t ws_bytes, hipStream_t st) {
+// what both calls do first: the arguments checked, the workspace carved, everything up to stage 1's decode enqueued
+hipError_t qr_front_end(const QrCommon& p, const void* data, bool versions, void* workspace, size_t ws_bytes, hipStream_t st, QrWorkspace& w, const u64*& mask) {
     const int B = p.B, H = p.H, W = p.W;
-    if (!qrcodes_args_ok(B, H, W, p.max_finders, p.max_codes) || !qr_max_version_ok(p.max_version) ||
-        !qr_params_ok(p.min_module, p.max_module, p.quiet, p.centre_tol, p.ring_tol, p.timing_max, p.max_finders, p.max_codes))
-        return hipErrorInvalidValue;
-    if (!p.rgb || !p.codes || !p.data || !p.counts) return hipErrorInvalidValue;
+    if (!qrcodes_args_ok(B, H, W, p.max_finders, p.max_codes) || !qr_params_ok(p)) return hipErrorInvalidValue;
+    if (!p.rgb || !p.codes || !data || !p.counts) return hipErrorInvalidValue;
     Arena a(workspace, ws_bytes);
-    const QrWorkspace w = qrcodes_layout(a, B, H, W, p.max_finders, p.max_codes);
-    unsigned char* resdata2 = a.take<unsigned char>((size_t)B * p.max_finders * QRV_MAX_DATA);
+    w = qrcodes_layout(a, B, H, W, p.max_finders, p.max_codes, versions);
     if (a.overflow) return hipErrorOutOfMemory;
     const int nw = (W + 63) / 64;
     const size_t runcap = run_cap(H, W);
-    const unsigned long long* mask;
     hipError_t e;
     if ((e = hipMemsetAsync(w.nfind, 0, sizeof(int) * (size_t)B, st)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(w.res, 0, sizeof(int) * (size_t)B * p.max_finders * RES_INTS, st)) != hipSuccess) return e;
@@ -980,10 +731,41 @@ hipError_t qrcodes_versions_launch(const QrVersionsParams& p, void* workspace, s
                        p.centre_tol, p.ring_tol, p.max_finders, w.nfind, w.finders, rows);
     hipLaunchKernelGGL(qr_decode_kernel, dim3(p.max_finders, B), dim3(64), 0, st, mask, w.finders, w.nfind, H, W, nw, p.max_finders, p.quiet, p.timing_max, w.res,
                        w.resdata);
+    return hipSuccess;
+}
+
+}  // namespace
+
+bool qr_params_ok(const QrCommon& p) {
+    return p.min_module >= 1 && p.max_module >= p.min_module && p.max_module <= QR_MAX_MODULE && p.quiet >= 0 && p.quiet <= QR_MAX_QUIET && p.centre_tol >= 0 &&
+           p.centre_tol <= QR_MAX_TOL && p.ring_tol >= 0 && p.ring_tol <= QR_MAX_TOL && p.timing_max >= 0 && p.timing_max <= QR_MAX_TIMING &&
+           p.max_finders >= 1 && p.max_finders <= QR_MAX_FINDERS && p.max_codes >= 1 && p.max_codes <= QR_MAX_CODES;
+}
+bool qr_max_version_ok(int max_version) { return max_version >= QR_VERSIONS && max_version <= QRV_VERSIONS; }
+
+size_t qrcodes_workspace_bytes(int B, int H, int W, int max_finders, int max_codes) { return qr_workspace_bytes(B, H, W, max_finders, max_codes, false); }
+size_t qrcodes_versions_workspace_bytes(int B, int H, int W, int max_finders, int max_codes) { return qr_workspace_bytes(B, H, W, max_finders, max_codes, true); }
+
+hipError_t qrcodes_launch(const QrParams& p, void* workspace, size_t ws_bytes, hipStream_t st) {
+    QrWorkspace w;
+    const u64* mask;
+    const hipError_t e = qr_front_end(p, p.data, false, workspace, ws_bytes, st, w, mask);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((qr_output_kernel<int, QR_MAX_DATA>), dim3(p.B), dim3(256), 0, st, w.res, w.resdata, nullptr, w.nfind, p.max_finders, p.max_codes, w.tmp,
+                       p.counts, p.codes, p.data, p.finder_counts);
+    return hipGetLastError();
+}
+
+hipError_t qrcodes_versions_launch(const QrVersionsParams& p, void* workspace, size_t ws_bytes, hipStream_t st) {
+    if (!qr_max_version_ok(p.max_version)) return hipErrorInvalidValue;
+    QrWorkspace w;
+    const u64* mask;
+    const hipError_t e = qr_front_end(p, p.data, true, workspace, ws_bytes, st, w, mask);
+    if (e != hipSuccess) return e;
     if (p.max_version > QR_VERSIONS)
-        hipLaunchKernelGGL(qr_decode_versions_kernel, dim3(p.max_finders, B), dim3(64), 0, st, mask, w.finders, w.nfind, H, W, nw, p.max_finders, p.quiet,
-                           p.timing_max, p.max_version, w.res, resdata2);
-    hipLaunchKernelGGL(qr_output_versions_kernel, dim3(B), dim3(256), 0, st, w.res, w.resdata, resdata2, w.nfind, p.max_finders, p.max_codes, w.tmp, p.counts,
-                       p.codes, p.data, p.finder_counts);
+        hipLaunchKernelGGL(qr_decode_versions_kernel, dim3(p.max_finders, p.B), dim3(64), 0, st, mask, w.finders, w.nfind, p.H, p.W, (p.W + 63) / 64, p.max_finders,
+                           p.quiet, p.timing_max, p.max_version, w.res, w.resdata2);
+    hipLaunchKernelGGL((qr_output_kernel<unsigned char, QRV_MAX_DATA>), dim3(p.B), dim3(256), 0, st, w.res, w.resdata, w.resdata2, w.nfind, p.max_finders,
+                       p.max_codes, w.tmp, p.counts, p.codes, p.data, p.finder_counts);
     return hipGetLastError();
 }

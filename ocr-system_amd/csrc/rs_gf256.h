@@ -14,12 +14,6 @@ struct RsLds {
     int L;
 };
 
-__device__ __forceinline__ int rs_wave_xor(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v ^= __shfl_xor(v, d);
-    return v;
-}
-
 template <class S>
 __device__ __forceinline__ void rs_load_tables(S& s, const unsigned char* exp, const unsigned char* log, int lane) {
     for (int i = lane; i < 512; i += 64) s.exp[i] = exp[i];
@@ -44,7 +38,7 @@ __device__ __forceinline__ bool rs_syndromes(RsLds<MAX_LEN, MAX_EC>& s, int len,
             const int p = p0 + lane;
             if (p < len) acc ^= rs_mul_exp(s, s.blk[p], ((k + first_root) * (len - 1 - p)) % 255);
         }
-        acc = rs_wave_xor(acc);
+        acc = wave_xor(acc);
         if (lane == 0) s.S[k] = acc;
         nz |= acc;
     }

@@ -35,6 +35,23 @@ inline dim3 row_wave_grid(int rows_total) { return dim3(((unsigned)rows_total + 
 // bits of mask word m that start a run: ink whose left neighbour (prev = bit 63 of the word to the left) is not ink
 __device__ __forceinline__ unsigned long long run_starts(unsigned long long m, unsigned long long prev) { return m & ~((m << 1) | prev); }
 
+// ---- after run_merge: run id (of `row`, [xs, xe] read here) learns its root -> the root, or -1 when the run is a root itself.  Its parent
+// is compressed to the root (concurrent compressions only ever replace a parent by an ancestor) and the root's box (x0, x1, y0, y1)
+// grows over the run.  The box only ever moves one way, so a value read before the atomic that already covers this run makes the atomic
+// unnecessary (most runs of a component lie inside what earlier ones reported).  P, rxs, rxe, box are the page's. ----
+__device__ __forceinline__ int run_join_root(int* P, const unsigned short* rxs, const unsigned short* rxe, int4* box, int id, int row, int& xs, int& xe) {
+    const int p = P[id];
+    if (p == id) return -1;
+    const int root = uf_find(P, p);
+    if (root != p) P[id] = root;
+    xs = rxs[id]; xe = rxe[id];
+    int* b = reinterpret_cast<int*>(box + root);
+    if (xs < __atomic_load_n(b + 0, __ATOMIC_RELAXED)) atomicMin(b + 0, xs);
+    if (xe > __atomic_load_n(b + 1, __ATOMIC_RELAXED)) atomicMax(b + 1, xe);
+    if (row > __atomic_load_n(b + 3, __ATOMIC_RELAXED)) atomicMax(b + 3, row);
+    return root;
+}
+
 // ---- rank sort of n <= cap rows of NC integer key columns, by one 256-thread work-group: the keys (the first NC of every `stride`
 // ints of t) go to LDS (s_key, NC * cap ints), every row is ranked lexicographically against all others, and emit(i, rank, key)
 // writes it out.  Rows are distinct (the last column is an id), so ranks are. ----

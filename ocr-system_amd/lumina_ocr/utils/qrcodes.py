@@ -5,11 +5,11 @@ codewords) -> text, and the entries the provider reports.
 The tables are our reading of the public standard (ISO/IEC 18004), built from its rules: finder, separator, timing and alignment
 patterns, the format and version areas and the dark module make the function mask; the two-column zigzag from the bottom right
 gives the placement order; the block structure is typed and pinned by the published totals (tests/test_qr_tables.py).
-csrc/qr_tables.h holds the same tables for the device (device_header() writes it; the test compares).
-
-Versions 11-40 (lumina_ocr_qrcodes_versions, data codewords as bytes) have tables of their own under the *_ALL names, built for all
-40 versions; the ten-version names above them stay what they were.  csrc/qr_version_tables.h is their device copy
-(device_header_versions()): block counts, totals, alignment centres, version and format words, and no placement table.
+The tables are built for all 40 versions under the *_ALL names (lumina_ocr_qrcodes_versions reads versions 11-40, data codewords as
+bytes); the ten-version names are their first ten columns.  csrc/qr_version_tables.h is the device's copy of the *_ALL tables
+(device_header_versions()): block counts, totals, alignment centres, version and format words; both decode stages read it.
+csrc/qr_tables.h (device_header()) holds what only the ten-version stage reads: function masks, the placement table, GF(256).
+The tests compare both files with what these functions write.
 
 Coordinates: a module is (row, col), both 0 .. D - 1, D = 17 + 4 version; a row of modules is one 64-bit word, bit col."""
 from __future__ import annotations
@@ -25,20 +25,8 @@ MAX_BLOCKS, MAX_BLOCK_LEN, MAX_EC = 8, 146, 30
 FORMAT_XOR = 0b101010000010010
 SECOND_COPY = 16                       # added to the reported format distance when the second copy was the one read
 
-TOTAL_CODEWORDS = (26, 44, 70, 100, 134, 172, 196, 242, 292, 346)
-REMAINDER_BITS = (0, 7, 7, 7, 7, 7, 0, 0, 0, 0)
-# EC codewords per block and number of blocks, [level][version - 1]
-EC_PER_BLOCK = ((7, 10, 15, 20, 26, 18, 20, 24, 30, 18),
-                (10, 16, 26, 18, 24, 16, 18, 22, 22, 26),
-                (13, 22, 18, 26, 18, 24, 18, 22, 20, 24),
-                (17, 28, 22, 16, 22, 28, 26, 26, 24, 28))
-NUM_BLOCKS = ((1, 1, 1, 1, 1, 2, 2, 2, 2, 4),
-              (1, 1, 1, 2, 2, 4, 4, 4, 5, 5),
-              (1, 1, 2, 2, 4, 4, 6, 6, 8, 8),
-              (1, 1, 2, 4, 4, 4, 5, 6, 8, 8))
-ALIGNMENT_CENTRES = ((), (6, 18), (6, 22), (6, 26), (6, 30), (6, 34), (6, 22, 38), (6, 24, 42), (6, 26, 46), (6, 28, 50))
 
-# ---- all 40 versions (lumina_ocr_qrcodes_versions): the tables above stay as they are, these are what the functions below read ----
+# ---- the tables, all 40 versions: what the functions below read ----
 VERSIONS_ALL = 40
 MAX_DATA_ALL = 2956                    # bytes a device data row of the all-versions call holds: the data codewords of 40-L
 MAX_CODEWORDS_ALL = 3706
@@ -80,6 +68,12 @@ def _data_modules(version: int) -> int:
 ALIGNMENT_CENTRES_ALL = tuple(alignment_centres(v) for v in range(1, VERSIONS_ALL + 1))
 TOTAL_CODEWORDS_ALL = tuple(_data_modules(v) // 8 for v in range(1, VERSIONS_ALL + 1))
 REMAINDER_BITS_ALL = tuple(_data_modules(v) % 8 for v in range(1, VERSIONS_ALL + 1))
+
+# versions 1-10 under their own names: the first ten columns (tests/test_qr_tables.py pins their values)
+TOTAL_CODEWORDS, REMAINDER_BITS = TOTAL_CODEWORDS_ALL[:MAX_VERSION], REMAINDER_BITS_ALL[:MAX_VERSION]
+EC_PER_BLOCK = tuple(row[:MAX_VERSION] for row in EC_PER_BLOCK_ALL)
+NUM_BLOCKS = tuple(row[:MAX_VERSION] for row in NUM_BLOCKS_ALL)
+ALIGNMENT_CENTRES = ALIGNMENT_CENTRES_ALL[:MAX_VERSION]
 
 
 def dimension(version: int) -> int:
@@ -279,26 +273,17 @@ def device_header() -> str:
     for v in vs:
         place += [(r << 6) | c for r, c in _PLACEMENT[v]]
         off.append(len(place))
-    blocks = [x for v in vs for lv in range(4) for x in block_structure(v, lv)]
-    align = [x for v in vs for x in (list(ALIGNMENT_CENTRES[v - 1]) + [0, 0, 0])[:3]]
     return ("#pragma once\n// Written by lumina_ocr.utils.qrcodes.device_header(); tests/test_qr_tables.py compares.  QR Code Model 2, versions 1..10.\n"
             "// QR_FUNC: 64 row words a version, bit col set where (row, col) is a function module.  QR_PLACE: (row << 6 | col) of every data\n"
-            "// module in placement order, version v at QR_PLACE_OFF[v - 1] .. QR_PLACE_OFF[v].  QR_BLOCKS: blocks, short blocks, data codewords\n"
-            "// of a short block, EC codewords of a block, by (version - 1) * 4 + level (L, M, Q, H).  QR_ALIGN: alignment centres, zero padded (for\n"
-            "// reference only: no kernel reads it, the alignment patterns are part of QR_FUNC).\n"
-            "// QR_FORMAT: the 15 drawn bits by (level bits << 3 | mask).  QR_EXP / QR_LOG: GF(256), polynomial 0x11D, EXP doubled.\n"
+            "// module in placement order, version v at QR_PLACE_OFF[v - 1] .. QR_PLACE_OFF[v].  QR_EXP / QR_LOG: GF(256), polynomial 0x11D, EXP\n"
+            "// doubled.  Totals, block structure and format words: qr_version_tables.h.\n"
             "constexpr int QR_VERSIONS = %d, QR_PLACE_N = %d;\n"
             "__device__ const unsigned long long QR_FUNC[QR_VERSIONS * 64] = {\n%s};\n"
             "__device__ const unsigned short QR_PLACE[QR_PLACE_N] = {\n%s};\n"
             "__device__ const int QR_PLACE_OFF[QR_VERSIONS + 1] = {\n%s};\n"
-            "__device__ const unsigned short QR_TOTAL[QR_VERSIONS] = {\n%s};\n"
-            "__device__ const unsigned char QR_BLOCKS[QR_VERSIONS * 4 * 4] = {\n%s};\n"
-            "__device__ const unsigned char QR_ALIGN[QR_VERSIONS * 3] = {\n%s};\n"
-            "__device__ const unsigned short QR_FORMAT[32] = {\n%s};\n"
             "__device__ const unsigned char QR_EXP[512] = {\n%s};\n"
             "__device__ const unsigned char QR_LOG[256] = {\n%s};\n"
-            % (len(vs), len(place), rows(func, "0x%016xull", 4), rows(place, "0x%03x", 16), rows(off, "%d", 11), rows(list(TOTAL_CODEWORDS), "%d", 10),
-               rows(blocks, "%d", 16), rows(align, "%d", 15), rows(list(FORMAT_WORDS), "0x%04x", 8), rows(list(GF_EXP), "%d", 32),
+            % (len(vs), len(place), rows(func, "0x%016xull", 4), rows(place, "0x%03x", 16), rows(off, "%d", 11), rows(list(GF_EXP), "%d", 32),
                rows(list(GF_LOG), "%d", 32)))
 
 

@@ -1,7 +1,7 @@
 """GPU: lumina_ocr_qrcodes through the C ABI against the restatement (tests/qr_reference.py): the ink mask (parity hook), the rows, the
 data codewords, the counts and the finder counts are EQUAL — the definition is integer arithmetic with a canonical order, so there is
 no tolerance — and the decoded strings are what was rendered.  Pages are about 260 x 330: the smallest that hold a version 10 symbol
-at 3 px a module with its quiet zone; W is no multiple of 64."""
+at 3 px a module with its quiet zone; W is no multiple of 64.  (The longest-block case uses the 560 x 587 pages of the all-versions tests.)"""
 import numpy as np
 import pytest
 import torch
@@ -100,6 +100,25 @@ def test_corrected_errors_second_format_copy_word_boundary_and_page_edges(engine
     by_box = {tuple(int(v) for v in c[:4]): c for c in res[1][0]}
     assert int(by_box[box5][8]) == t5 == 9 and int(by_box[box2][10]) == qr.SECOND_COPY and int(by_box[box5][10]) == 0
     assert found(*res[2][:2]) == {boxa: "TOP LEFT", boxb: "bottom right"}
+
+
+def longest_block_pages():
+    """9-L at 3 px on two 560 x 587 pages: ec = 30 and two blocks of 146 codewords, the longest block and the largest locator (L = 15)
+    versions 1-10 ever build.  Page 0 has ec // 2 = 15 errors in the last block, page 1 one more -> pages, the symbol's box, its text"""
+    nb, _, _, ec = qr.block_structure(9, 0)
+    assert (nb, ec) == (2, 30)
+    text = ("9-L " + "the longest block / " * 16)[:qr.data_codewords(9, 0) - 3]
+    pages = np.stack([blank(587, 560), blank(587, 560)])
+    box = put(pages[0], 90, 120, "", 9, module=3, sym=corrupted(text, 9, 0, 5, nb - 1, ec // 2))
+    put(pages[1], 90, 120, "", 9, module=3, sym=corrupted(text, 9, 0, 5, nb - 1, ec // 2 + 1))
+    return pages, box, text
+
+
+def test_the_longest_block_reads_at_its_capacity_and_not_one_error_past_it(engine):
+    pages, box, text = longest_block_pages()
+    res = check(engine, pages)
+    assert found(*res[0][:2]) == {box: text} and int(res[0][0][0][8]) == 15
+    assert len(res[1][0]) == 0 and res[1][2] == 3                                  # three finders and no symbol
 
 
 def test_every_version_and_level_reads(engine):
