@@ -370,6 +370,37 @@ int lumina_ocr_datamatrix(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int 
                           int quiet, int timing_max, int solid_max, int max_candidates, int max_codes, int32_t* codes_dev, int32_t* data_dev,
                           int32_t* counts_dev, int32_t* candidate_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream);
 
+/* Aztec codes (ISO/IEC 24778, written from recollection of the public symbology): compact symbols of 1-4 layers and full-range
+ * symbols of 1-11 layers (15 .. 61 modules: the symbols whose rows fit one 64-bit word) on the pages, located, sampled and
+ * error-corrected on the device (the host half is lumina_ocr/utils/aztec.py).  ink as in lumina_ocr_table_rules.  The FINDER is the
+ * bullseye's core: a component whose box sides lie in min_module .. max_module, square within a quarter and at least three quarters
+ * ink, whose neighbours on its centre row both belong to one other component, the 5-module ring: sides five of the core's within
+ * ring_tol / 16 of a module, concentric within centre_tol / 16, 12/25 .. 20/25 of its box ink.  A page with more than max_finders
+ * finders is not read.  A FRAME is the ring's centre, a slope t / 128 and a pitch (the ring's box sides are ten modules) scaled by
+ * (256 + 2 k) / 256; a point of it is a pixel by integer multiplications and shifts, clear off the page.  For either kind the frame
+ * (k even in -12 .. 12, t in -4, 0, 4) with the fewest mismatches in the bullseye is taken, the rotation is the one with the fewest
+ * mismatches in the mode ring's twelve corner modules, and the mode message is corrected over GF(16); the kind with the fewest
+ * mismatches (at most mark_max) that corrects and is in scope is read (ties: fewer mode errors, compact).  The size known, the frame
+ * (k in -12 .. 12, t in -6 .. 6) with no ink a quarter module outside the symbol's outline, the fewest mismatches on the centre
+ * reference lines and the most ink a quarter module inside the outline is taken; the `quiet` rings of modules must be clear; the
+ * codewords are read through the layer spiral and corrected as one block over GF(64) / GF(256) / GF(1024), and the syndromes of the
+ * corrected block must vanish.
+ * codes_dev int32 [n][max_codes][12] = x0, y0, x1, y1 (the hull of the symbol's corners, inclusive), layers, compact (0 / 1), codeword
+ * width, ndata, corrected errors, rotation (quarter turns clockwise), mode-message errors, bullseye + corner + reference-line
+ * mismatches; sorted by (y0, x0, y1, x1, root of the core), rows past the count untouched; data_dev int32 [n][max_codes][320] = the
+ * corrected data codewords, still bit-stuffed, zero behind ndata; counts_dev int32 [n] = the true number (a list whose count exceeds
+ * max_codes is not written); finder_counts_dev: optional, int32 [n] = the finders of each page.  mask_in_dev / mask_out_dev as in
+ * lumina_ocr_barcodes.  1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= centre_tol <= 64, 0 <= ring_tol <= 15,
+ * 0 <= mark_max <= 64, max_finders 1..64, max_codes 1..64, sides 1..65535; defaults in lumina_ocr/arch.py AZTEC_PARAMS.  Not read:
+ * full-range symbols of 12-32 layers, runes, light-on-dark and mirrored symbols, perspective, a bullseye that other ink touches.
+ * Integer arithmetic throughout: the result is defined bit for bit (tests/aztec_reference.py).  Asynchronous; n == 0 is a no-op; bad
+ * arguments return a status before anything is written.  lumina_ocr_aztec_workspace_bytes: the workspace n pages of that size need
+ * in one launch (0: bad arguments); the entry itself splits n into groups that fit the handle's workspace. */
+size_t lumina_ocr_aztec_workspace_bytes(int n, int height, int width, int max_finders, int max_codes);
+int lumina_ocr_aztec(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module, int max_module,
+                     int quiet, int centre_tol, int ring_tol, int mark_max, int max_finders, int max_codes, int32_t* codes_dev, int32_t* data_dev,
+                     int32_t* counts_dev, int32_t* finder_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream);
+
 /* ---- page orientation (optional; DESIGN.md: "Page orientation") ----
  * A page is upright after `turn` quarter turns: upright = np.rot90(page, turn) (counter-clockwise).  The three entries below are the
  * device half; which pages get which turn is decided on the host (lumina_ocr/utils/page_orient.py, OcrPipeline.run_oriented).

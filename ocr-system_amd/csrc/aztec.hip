@@ -1,0 +1,465 @@
+// Aztec codes (compact 1-4 layers, full-range 1-11 layers) on the GPU (gfx950): the symbols of a page as (x0, y0, x1, y1, layers,
+// compact, codeword width, ndata, errors, rotation, mode-message errors, mismatches) with their corrected data codewords, in a
+// canonical order.  Everything is integer and every reduction is order-free (min / max / add / xor, ballots), so the lists equal the
+// sequential definition restated in tests/aztec_reference.py.
+//
+// All stream-ordered kernels, no host round trip:
+//   1 ink_mask                          the mask (or the one the caller already has)
+//   2 run_count / row_scan / run_fill / run_merge   mask words -> run list and its 8-connected components (the shared kernels of runs.hip)
+//   3 az_init, az_accum   a run is its own area; every run learns its root, and box and area are accumulated there
+//   4 az_finders  one wave per row, lanes over the row's roots: a solid square core whose neighbours on its centre row both belong to
+//                 one concentric component of five times its side -> counted, gathered per page
+//   5 az_decode   one wave per (page, finder).  A frame is the ring's centre, a slope and a pitch; a point of it is a pixel by
+//                 64-bit multiplications and shifts.  Frames are scored with lanes over modules: first on the bullseye for either
+//                 kind, whose corner marks give the rotation and whose mode message (GF(16)) gives layers and data words; then,
+//                 the size known, on the symbol's outline (ink just inside it, none just outside) and the centre reference lines.
+//                 Lane r samples module row r as one 64-bit word; lanes gather the codewords through the layer spiral from the
+//                 rows in LDS; the one block goes through rs_gf2m.h.  Every loop has a constant bound, every LDS and page index is
+//                 clamped, and no wave waits for another (a work-group is one wave)
+//   6 az_output   one work-group per page: valid finders counted, gathered, rank-sorted by (y0, x0, y1, x1, root)
+#include "aztec.h"
+#include "aztec_tables.h"
+#include "rs_gf2m.h"
+#include "runs.h"
+
+namespace {
+
+typedef unsigned long long u64;
+typedef long long i64;
+
+constexpr int RES_INTS = 16;   // a finder's result: y0, x0, y1, x1, root, layers, compact, width, ndata, errors, rotation, mode errors, mismatches, valid
+constexpr int AZ_MAX_WORDS = 320, AZ_MAX_EC = 318, AZ_MAX_M = 10, AZ_MAX_LAYERS = 11, AZ_MAX_SIDE = 61;
+
+// 3a: a run's own length is the start of its component's area
+__global__ __launch_bounds__(256) void az_init_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* area, int H, size_t runcap,
+                                                      int rows_total) {
+    int pg, row, lane;
+    if (!row_wave(H, rows_total, pg, row, lane)) return;
+    const int* ro = runoff + (size_t)pg * (H + 1);
+    const size_t rb = (size_t)pg * runcap;
+    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) area[rb + id] = rxe[rb + id] - rxs[rb + id] + 1;
+}
+
+// 3b: parent = root; the root's box and area grow to the component's
+__global__ __launch_bounds__(256) void az_accum_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* parent, int4* box, int* area,
+                                                       int H, size_t runcap, int rows_total) {
+    int pg, row, lane;
+    if (!row_wave(H, rows_total, pg, row, lane)) return;
+    const int* ro = runoff + (size_t)pg * (H + 1);
+    const size_t rb = (size_t)pg * runcap;
+    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
+        int xs, xe;
+        const int root = run_join_root(parent + rb, rxs + rb, rxe + rb, box + rb, id, row, xs, xe);
+        if (root >= 0) atomicAdd(area + rb + root, xe - xs + 1);
+    }
+}
+
+__device__ __forceinline__ int iabs(int v) { return v < 0 ? -v : v; }
+
+// 4: finders [B][max_finders][2] = the core's root, the ring's root
+__global__ __launch_bounds__(256) void az_finders_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, const int* parent, const int4* box,
+                                                         const int* area, int H, size_t runcap, int min_module, int max_module, int centre_tol, int ring_tol,
+                                                         int max_finders, int* nfind, int* finders, int rows_total) {
+    int pg, row, lane;
+    if (!row_wave(H, rows_total, pg, row, lane)) return;
+    const int* ro = runoff + (size_t)pg * (H + 1);
+    const size_t rb = (size_t)pg * runcap;
+    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
+        if (parent[rb + id] != id) continue;
+        const int4 bx = box[rb + id];   // x0, x1, y0, y1
+        const int w = bx.y - bx.x + 1, h = bx.w - bx.z + 1;
+        if (w < min_module || h < min_module || w > max_module || h > max_module) continue;
+        if (4 * iabs(w - h) > (w > h ? w : h) || 4 * area[rb + id] < 3 * w * h) continue;
+        const int cy = clampi((bx.z + bx.w) >> 1, 0, H - 1), cx = (bx.x + bx.y) >> 1;
+        const int lo = ro[cy], hi = ro[cy + 1];
+        // the last run of the centre row that starts at or before cx
+        int a = lo, b = hi;   // the answer is in [a, b) when there is one
+        for (int it = 0; it < 17; ++it) {
+            if (b - a <= 1) break;
+            const int mid = (a + b) >> 1;
+            if (rxs[rb + mid] <= cx) a = mid; else b = mid;
+        }
+        if (a >= hi || a - 1 < lo || a + 1 >= hi) continue;
+        if (rxs[rb + a] > cx || rxe[rb + a] < cx || uf_find(parent + rb, a) != id) continue;
+        const int g = uf_find(parent + rb, a - 1);
+        if (g == id || uf_find(parent + rb, a + 1) != g) continue;
+        const int4 gx = box[rb + g];
+        const int w5 = gx.y - gx.x + 1, h5 = gx.w - gx.z + 1;
+        if (16 * iabs(5 * w - w5) > ring_tol * w5 || 16 * iabs(5 * h - h5) > ring_tol * h5) continue;
+        if (80 * iabs(gx.x + gx.y - bx.x - bx.y) > 2 * centre_tol * w5 || 80 * iabs(gx.z + gx.w - bx.z - bx.w) > 2 * centre_tol * h5) continue;
+        const i64 wh = (i64)w5 * h5, a25 = 25 * (i64)area[rb + g];
+        if (12 * wh > a25 || a25 > 20 * wh) continue;
+        const int idx = atomicAdd(&nfind[pg], 1);
+        if (idx < max_finders) {
+            finders[((size_t)pg * max_finders + idx) * 2 + 0] = id;
+            finders[((size_t)pg * max_finders + idx) * 2 + 1] = g;
+        }
+    }
+}
+
+// a frame: the ring's centre (doubled pixels << 30), slope t / 128, pitch step k; a point (u, v) in quarter modules from the centre
+struct AzFrame { i64 cx, cy, q; int t; };
+
+__device__ __forceinline__ AzFrame az_frame(int cx2, int cy2, int s10, int t, int k) {
+    AzFrame f;
+    f.cx = (i64)cx2 << 30; f.cy = (i64)cy2 << 30; f.t = t;
+    f.q = (((i64)s10 << 20) / (5 * (128 + iabs(t)))) * (256 + 2 * k);
+    return f;
+}
+__device__ __forceinline__ void az_pixel(const AzFrame& f, int u, int v, i64& px, i64& py) {
+    px = (f.cx + f.q * (i64)(128 * u - f.t * v)) >> 31;
+    py = (f.cy + f.q * (i64)(f.t * u + 128 * v)) >> 31;
+}
+// the ink at a point; off the page reads clear
+__device__ __forceinline__ int az_at(const u64* mpage, int H, int W, int nw, const AzFrame& f, int u, int v) {
+    i64 px, py;
+    az_pixel(f, u, v, px, py);
+    if (px < 0 || py < 0 || px >= W || py >= H) return 0;
+    return (int)((mpage[(size_t)py * nw + (size_t)(px >> 6)] >> (px & 63)) & 1ull);
+}
+// a symbol offset turned clockwise by r quarter turns
+__device__ __forceinline__ void az_turn(int x, int y, int r, int& tx, int& ty) {
+    tx = r == 0 ? x : r == 1 ? -y : r == 2 ? -x : y;
+    ty = r == 0 ? y : r == 1 ? x : r == 2 ? -y : -x;
+}
+
+__device__ __forceinline__ int az_width(int layers) { return layers <= 2 ? 6 : layers <= 8 ? 8 : 10; }
+__device__ __forceinline__ int az_total_bits(bool compact, int layers) { return ((compact ? 88 : 112) + 16 * layers) * layers; }
+__device__ __forceinline__ int az_modules(bool compact, int layers) {
+    const int base = (compact ? 11 : 14) + 4 * layers;
+    return compact ? base : base + 1 + 2 * ((base / 2 - 1) / 15);
+}
+// index of the matrix without the reference grid's lines -> the symbol's coordinate
+__device__ __forceinline__ int az_grid(bool compact, int layers, int i) {
+    if (compact) return i;
+    const int half = 7 + 2 * layers, c = az_modules(false, layers) / 2;
+    if (i >= half) { const int j = i - half; return c + j + j / 15 + 1; }
+    const int j = half - 1 - i;
+    return c - j - j / 15 - 1;
+}
+// bit b of the symbol's stream -> its module: layer 0 outermost, the left side going down, the bottom going right, the right side
+// going up, the top going left; bit 2 j + k of a side is domino j, k modules inwards
+__device__ __forceinline__ void az_bit_pos(bool compact, int layers, int b, int& x, int& y) {
+    int i = 0, row = 0;
+    for (i = 0; i < AZ_MAX_LAYERS; ++i) {
+        row = 4 * (layers - i) + (compact ? 9 : 12);
+        if (b < 8 * row || i >= layers - 1) break;
+        b -= 8 * row;
+    }
+    b = clampi(b, 0, 8 * row - 1);
+    const int side = b / (2 * row), r = b % (2 * row), j = r >> 1, k = r & 1;
+    const int low = 2 * i, high = (compact ? 11 : 14) + 4 * layers - 1 - 2 * i;
+    const int mx = side == 0 ? low + k : side == 1 ? low + j : side == 2 ? high - k : high - j;
+    const int my = side == 0 ? low + j : side == 1 ? high - k : side == 2 ? high - j : low + k;
+    x = clampi(az_grid(compact, layers, mx), 0, 63);
+    y = clampi(az_grid(compact, layers, my), 0, 63);
+}
+
+struct AzLds {
+    u64 rows[64];
+    Rs2mLds<AZ_MAX_WORDS, AZ_MAX_EC, AZ_MAX_M> rs;
+};
+
+// ink on the square at d quarter modules, points every `step` quarter modules, corners included on all four sides (d / step * 2 + 1 <= 128 points a side)
+__device__ __forceinline__ int az_square(const u64* mpage, int H, int W, int nw, const AzFrame& f, int d, int step, int lane) {
+    int n = 0;
+    const int cnt = 2 * d / step + 1;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int idx = lane + 64 * j, a = -d + step * idx;
+        const bool on = idx < cnt;
+        n += __popcll(__ballot(on && az_at(mpage, H, W, nw, f, a, -d))) + __popcll(__ballot(on && az_at(mpage, H, W, nw, f, a, d))) +
+             __popcll(__ballot(on && az_at(mpage, H, W, nw, f, -d, a))) + __popcll(__ballot(on && az_at(mpage, H, W, nw, f, d, a)));
+    }
+    return n;
+}
+
+// 5: one wave per (page, finder): res [B][max_finders][RES_INTS], resdata [B][max_finders][AZ_MAX_DATA]
+__global__ __launch_bounds__(64) void az_decode_kernel(const u64* mask, const int* finders, const int* nfind, const int4* box, int H, int W, int nw, size_t runcap,
+                                                       int max_finders, int quiet, int mark_max, int* res, unsigned short* resdata) {
+    __shared__ AzLds s;
+    const int pg = blockIdx.y, a = blockIdx.x, lane = threadIdx.x;
+    const int nf_page = nfind[pg];
+    if (nf_page > max_finders || a >= nf_page || a >= AZ_MAX_FINDERS) return;
+    const u64* mpage = mask + (size_t)pg * H * nw;
+    const int root = clampi(finders[((size_t)pg * max_finders + a) * 2 + 0], 0, (int)runcap - 1);
+    const int ring = clampi(finders[((size_t)pg * max_finders + a) * 2 + 1], 0, (int)runcap - 1);
+    const int4 gx = box[(size_t)pg * runcap + ring];   // x0, x1, y0, y1
+    const int cx2 = gx.x + gx.y + 1, cy2 = gx.z + gx.w + 1, s10 = (gx.y - gx.x + 1) + (gx.w - gx.z + 1);
+    rs2m_load_tables(s.rs, AZ_EXP + AZ_EXP_OFF[0], AZ_LOG + AZ_LOG_OFF[0], 4, lane);
+    // either kind: the bullseye's best frame, the rotation, the mode message
+    i64 kind_best = -1;
+#pragma unroll 1
+    for (int full = 0; full < 2; ++full) {
+        const int sd = full ? 7 : 5, side = 2 * sd - 1;
+        int best = -1;
+#pragma unroll 1
+        for (int k = -12; k <= 12; k += 2) {
+#pragma unroll 1
+            for (int t = -4; t <= 4; t += 4) {
+                const AzFrame f = az_frame(cx2, cy2, s10, t, k);
+                int mism = 0;
+                for (int j = 0; j < 3; ++j) {
+                    const int idx = lane + 64 * j, dx = idx % side - (sd - 1), dy = idx / side - (sd - 1);
+                    const bool on = idx < side * side;
+                    const int want = ((iabs(dx) > iabs(dy) ? iabs(dx) : iabs(dy)) & 1) ^ 1;
+                    mism += __popcll(__ballot(on && az_at(mpage, H, W, nw, f, 4 * dx, 4 * dy) != want));
+                }
+                const int key = (mism << 16) | (iabs(k) << 12) | (iabs(t) << 9) | ((k + 12) << 4) | (t + 6);
+                if (best < 0 || key < best) best = key;
+            }
+        }
+        const int bull = best >> 16;
+        const AzFrame f = az_frame(cx2, cy2, s10, (best & 15) - 6, ((best >> 4) & 31) - 12);
+        // the twelve corner modules of the mode ring
+        const int corner = (lane >> 2) & 3, which = lane & 3;   // lanes 0 .. 15, `which` 3 unused
+        const int sx = (corner == 1 || corner == 2) ? 1 : -1, sy = corner >= 2 ? 1 : -1;
+        const int mx = sx * (which == 1 ? sd - 1 : sd), my = sy * (which == 2 ? sd - 1 : sd);
+        const int dark = corner == 0 || (corner == 1 && which != 1) || (corner == 2 && which == 2);
+        int rot = 0, mm = 99;
+        for (int r = 0; r < 4; ++r) {
+            int tx, ty;
+            az_turn(mx, my, r, tx, ty);
+            const int got = __popcll(__ballot(lane < 16 && which < 3 && az_at(mpage, H, W, nw, f, 4 * tx, 4 * ty) != dark));
+            if (got < mm) { mm = got; rot = r; }
+        }
+        if (bull + mm > mark_max) continue;
+        // the mode message, clockwise from the top side's left end
+        const int n = full ? 10 : 7, nwords = n, ecw = full ? 6 : 5;
+        int bit = 0;
+        if (lane < 4 * n) {
+            const int sde = lane / n, jj = lane % n, i = sde < 2 ? jj : n - 1 - jj;
+            const int o = full ? -5 + i + i / 5 : -3 + i;
+            const int px = sde == 0 ? o : sde == 1 ? sd : sde == 2 ? o : -sd, py = sde == 0 ? -sd : sde == 1 ? o : sde == 2 ? sd : o;
+            int tx, ty;
+            az_turn(px, py, rot, tx, ty);
+            bit = az_at(mpage, H, W, nw, f, 4 * tx, 4 * ty);
+        }
+        const u64 ball = __ballot(bit);
+        __syncthreads();
+        if (lane < nwords) {
+            const int v = (int)((ball >> (4 * lane)) & 15ull);
+            s.rs.blk[lane] = (unsigned short)(((v & 1) << 3) | ((v & 2) << 1) | ((v & 4) >> 1) | ((v & 8) >> 3));
+        }
+        __syncthreads();
+        const int merr = rs2m_correct_block(s.rs, nwords, ecw, lane);
+        if (merr < 0) continue;
+        int layers, ndata;
+        if (!full) {
+            const int v = (s.rs.blk[0] << 4) | s.rs.blk[1];
+            layers = (v >> 6) + 1; ndata = (v & 63) + 1;
+        } else {
+            const int v = (s.rs.blk[0] << 12) | (s.rs.blk[1] << 8) | (s.rs.blk[2] << 4) | s.rs.blk[3];
+            layers = (v >> 11) + 1; ndata = (v & 2047) + 1;
+            if (layers > AZ_MAX_LAYERS) continue;
+        }
+        if (az_total_bits(!full, layers) / az_width(layers) - ndata < 2) continue;
+        // (mismatches, mode errors, full) | rotation, layers, ndata
+        const i64 key = ((i64)(bull + mm) << 40) | ((i64)merr << 32) | ((i64)full << 31) | ((i64)rot << 20) | ((i64)layers << 12) | (i64)ndata;
+        if (kind_best < 0 || key < kind_best) kind_best = key;
+    }
+    if (kind_best < 0) return;
+    const int mism = (int)(kind_best >> 40), merr = (int)((kind_best >> 32) & 255), rot = (int)((kind_best >> 20) & 3);
+    const bool compact = !((kind_best >> 31) & 1);
+    const int layers = clampi((int)((kind_best >> 12) & 255), 1, compact ? 4 : AZ_MAX_LAYERS), ndata = (int)(kind_best & 4095);
+    const int n = az_modules(compact, layers), h = n / 2, width = az_width(layers);
+    const int total = az_total_bits(compact, layers) / width, pad = az_total_bits(compact, layers) % width, ec = total - ndata;
+    if (n > AZ_MAX_SIDE || total > AZ_MAX_WORDS || ndata < 1 || ndata > AZ_MAX_DATA || ec < 2 || ec > AZ_MAX_EC) return;   // (the formulas never say so)
+    // the frame of the whole symbol: nothing just outside its outline, the most ink just inside it, the centre lines alternating
+    i64 best = -1;
+#pragma unroll 1
+    for (int k = -12; k <= 12; ++k) {
+#pragma unroll 1
+        for (int t = -6; t <= 6; ++t) {
+            const AzFrame f = az_frame(cx2, cy2, s10, t, k);
+            if (az_square(mpage, H, W, nw, f, 4 * h + 3, 2, lane)) continue;
+            const int in = az_square(mpage, H, W, nw, f, 4 * h + 1, 2, lane);
+            int ref = 0;
+            if (!compact) {
+                const int span = h - 7;   // distances 8 .. h
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int idx = lane + 64 * j, d = 8 + idx % span, dir = idx / span;
+                    const int u = dir == 0 ? d : dir == 1 ? -d : 0, v = dir == 2 ? d : dir == 3 ? -d : 0;
+                    ref += __popcll(__ballot(idx < 4 * span && az_at(mpage, H, W, nw, f, 4 * u, 4 * v) != ((d & 1) ^ 1)));
+                }
+            }
+            const i64 key = ((i64)ref << 26) | ((i64)(1023 - in) << 16) | (iabs(k) << 12) | (iabs(t) << 9) | ((k + 12) << 4) | (t + 6);
+            if (best < 0 || key < best) best = key;
+        }
+    }
+    if (best < 0) return;
+    const int ref = (int)(best >> 26);
+    const AzFrame f = az_frame(cx2, cy2, s10, (int)(best & 15) - 6, (int)((best >> 4) & 31) - 12);
+    // the quiet rings, at the modules' centres
+    bool dirty = false;
+    for (int q = 1; q <= AZ_MAX_QUIET; ++q) {
+        if (q > quiet) break;
+        if (az_square(mpage, H, W, nw, f, 4 * (h + q), 4, lane)) dirty = true;
+    }
+    if (dirty) return;
+    // lane y samples module row y
+    u64 row = 0;
+    if (lane < n)
+        for (int x = 0; x < AZ_MAX_SIDE; ++x) {
+            if (x >= n) break;
+            int tx, ty;
+            az_turn(x - h, lane - h, rot, tx, ty);
+            row |= (u64)az_at(mpage, H, W, nw, f, 4 * tx, 4 * ty) << x;
+        }
+    __syncthreads();
+    s.rows[lane] = row;
+    rs2m_load_tables(s.rs, AZ_EXP + AZ_EXP_OFF[(width - 4) >> 1], AZ_LOG + AZ_LOG_OFF[(width - 4) >> 1], width, lane);
+    // codewords through the layer spiral, the pad bits first
+#pragma unroll 1
+    for (int j = lane; j < AZ_MAX_WORDS; j += 64) {
+        int val = 0;
+        if (j < total)
+            for (int b = 0; b < AZ_MAX_M; ++b) {
+                if (b >= width) break;
+                int x, y;
+                az_bit_pos(compact, layers, pad + j * width + b, x, y);
+                val = (val << 1) | (int)((s.rows[y] >> x) & 1ull);
+            }
+        s.rs.blk[j] = (unsigned short)val;
+    }
+    __syncthreads();
+    const int errors = rs2m_correct_block(s.rs, total, ec, lane);
+    if (errors < 0) return;
+    unsigned short* od = resdata + ((size_t)pg * max_finders + a) * AZ_MAX_DATA;
+    for (int p = lane; p < AZ_MAX_DATA; p += 64)
+        if (p < ndata) od[p] = s.rs.blk[p];
+    if (lane == 0) {
+        // the hull: the box of the outline's four corners
+        i64 x0 = 0, x1 = 0, y0 = 0, y1 = 0;
+        const int e = 4 * h + 2;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            i64 qx, qy;
+            az_pixel(f, (c & 1) ? e : -e, (c & 2) ? e : -e, qx, qy);
+            x0 = c == 0 || qx < x0 ? qx : x0; x1 = c == 0 || qx > x1 ? qx : x1;
+            y0 = c == 0 || qy < y0 ? qy : y0; y1 = c == 0 || qy > y1 ? qy : y1;
+        }
+        const auto cl = [](i64 v, int hi) { return (int)(v < 0 ? 0 : v > hi ? hi : v); };
+        int* o = res + ((size_t)pg * max_finders + a) * RES_INTS;
+        o[0] = cl(y0, H - 1); o[1] = cl(x0, W - 1); o[2] = cl(y1 - 1, H - 1); o[3] = cl(x1 - 1, W - 1); o[4] = root;
+        o[5] = layers; o[6] = compact ? 1 : 0; o[7] = width; o[8] = ndata; o[9] = errors; o[10] = rot; o[11] = merr; o[12] = mism + ref; o[13] = 1;
+    }
+}
+
+// 6: tmp [B][max_codes][6] = y0, x0, y1, x1, root, slot
+__global__ __launch_bounds__(256) void az_output_kernel(const int* res_all, const unsigned short* resdata_all, const int* nfind, int max_finders, int max_codes,
+                                                        int* tmp_all, int* counts, int* codes, int* data, int* finder_counts) {
+    __shared__ int s_key[AZ_MAX_CODES * 5];
+    __shared__ int s_n;
+    const int pg = blockIdx.x;
+    const int nf = nfind[pg];
+    const int* res = res_all + (size_t)pg * max_finders * RES_INTS;
+    int* tmp = tmp_all + (size_t)pg * max_codes * 6;
+    if (threadIdx.x == 0) {
+        s_n = 0;
+        if (finder_counts) finder_counts[pg] = nf;
+    }
+    __syncthreads();
+    const int lim = nf > max_finders ? 0 : nf;   // a page with too many finders is not read
+    for (int a = threadIdx.x; a < lim; a += 256) {
+        const int* r = res + a * RES_INTS;
+        if (r[13] != 1) continue;
+        const int idx = atomicAdd(&s_n, 1);
+        if (idx >= max_codes) continue;
+        int* o = tmp + idx * 6;
+        o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3]; o[4] = r[4]; o[5] = a;
+    }
+    __syncthreads();
+    const int n = s_n;
+    if (threadIdx.x == 0) counts[pg] = n;
+    if (n > max_codes) return;   // overflow: the count is all that is reported
+    int* out = codes + (size_t)pg * max_codes * 12;
+    int* odat = data + (size_t)pg * max_codes * AZ_MAX_DATA;
+    const unsigned short* rd = resdata_all + (size_t)pg * max_finders * AZ_MAX_DATA;
+    rank_sort<5>(s_key, tmp, 6, n, [=](int i, int rank, const int (&k)[5]) {
+        const int slot = clampi(tmp[i * 6 + 5], 0, max_finders - 1);
+        const int* r = res + slot * RES_INTS;
+        int* o = out + (size_t)rank * 12;
+        o[0] = k[1]; o[1] = k[0]; o[2] = k[3]; o[3] = k[2];
+        for (int j = 0; j < 8; ++j) o[4 + j] = r[5 + j];
+        const int nd = r[8];
+        for (int j = 0; j < AZ_MAX_DATA; ++j) odat[(size_t)rank * AZ_MAX_DATA + j] = j < nd ? rd[(size_t)slot * AZ_MAX_DATA + j] : 0;
+    });
+}
+
+}  // namespace
+
+// the workspace's regions: one layout sizes it (aztec_workspace_bytes) and carves it (aztec_launch)
+struct AzWorkspace {
+    unsigned long long* mask; int* runoff; unsigned short *rxs, *rxe; int* parent; int4* box; int* area;
+    int* nfind; int* finders; int* res; unsigned short* resdata; int* tmp;
+};
+static AzWorkspace aztec_layout(Arena& a, int B, int H, int W, int max_finders, int max_codes) {
+    const size_t runcap = run_cap(H, W), nw = (W + 63) / 64;
+    AzWorkspace w;
+    w.mask = a.take<unsigned long long>((size_t)B * H * nw);
+    w.runoff = a.take<int>((size_t)B * (H + 1));   // run counts -> offsets
+    w.rxs = a.take<unsigned short>((size_t)B * runcap); w.rxe = a.take<unsigned short>((size_t)B * runcap);
+    w.parent = a.take<int>((size_t)B * runcap);
+    w.box = a.take<int4>((size_t)B * runcap);      // at a root: x0, x1, y0, y1 of its component
+    w.area = a.take<int>((size_t)B * runcap);      // at a root: its component's ink
+    w.nfind = a.take<int>((size_t)B);
+    w.finders = a.take<int>((size_t)B * max_finders * 2);
+    w.res = a.take<int>((size_t)B * max_finders * RES_INTS);
+    w.resdata = a.take<unsigned short>((size_t)B * max_finders * AZ_MAX_DATA);
+    w.tmp = a.take<int>((size_t)B * max_codes * 6);
+    return w;
+}
+
+static bool aztec_args_ok(int B, int H, int W, int max_finders, int max_codes) {
+    if (B <= 0 || H <= 0 || W <= 0 || H > 65535 || W > 65535 || max_codes < 1 || max_codes > AZ_MAX_CODES || max_finders < 1 || max_finders > AZ_MAX_FINDERS)
+        return false;
+    return (size_t)B * H < (1ull << 31) && run_cap(H, W) < (1ull << 31);
+}
+
+bool aztec_params_ok(int min_module, int max_module, int quiet, int centre_tol, int ring_tol, int mark_max, int max_finders, int max_codes) {
+    return min_module >= 1 && max_module >= min_module && max_module <= AZ_MAX_MODULE && quiet >= 0 && quiet <= AZ_MAX_QUIET && centre_tol >= 0 &&
+           centre_tol <= 64 && ring_tol >= 0 && ring_tol <= AZ_MAX_TOL && mark_max >= 0 && mark_max <= AZ_MAX_MARKS && max_finders >= 1 &&
+           max_finders <= AZ_MAX_FINDERS && max_codes >= 1 && max_codes <= AZ_MAX_CODES;
+}
+
+size_t aztec_workspace_bytes(int B, int H, int W, int max_finders, int max_codes) {
+    if (!aztec_args_ok(B, H, W, max_finders, max_codes)) return 0;
+    Arena a;
+    aztec_layout(a, B, H, W, max_finders, max_codes);
+    return a.off;
+}
+
+hipError_t aztec_launch(const AztecParams& p, void* workspace, size_t ws_bytes, hipStream_t st) {
+    const int B = p.B, H = p.H, W = p.W;
+    if (!aztec_args_ok(B, H, W, p.max_finders, p.max_codes) ||
+        !aztec_params_ok(p.min_module, p.max_module, p.quiet, p.centre_tol, p.ring_tol, p.mark_max, p.max_finders, p.max_codes))
+        return hipErrorInvalidValue;
+    if (!p.rgb || !p.codes || !p.data || !p.counts) return hipErrorInvalidValue;
+    Arena a(workspace, ws_bytes);
+    const AzWorkspace w = aztec_layout(a, B, H, W, p.max_finders, p.max_codes);
+    if (a.overflow) return hipErrorOutOfMemory;
+    const int nw = (W + 63) / 64;
+    const size_t runcap = run_cap(H, W);
+    const unsigned long long* mask;
+    hipError_t e;
+    if ((e = hipMemsetAsync(w.nfind, 0, sizeof(int) * (size_t)B, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.res, 0, sizeof(int) * (size_t)B * p.max_finders * RES_INTS, st)) != hipSuccess) return e;
+    if ((e = ink_mask_resolve(p.rgb, p.mask_in, p.mask_out, w.mask, B, H, W, p.threshold, st, &mask)) != hipSuccess) return e;
+    const int rows = B * H;
+    const dim3 grows = row_wave_grid(rows);
+    run_count_launch(mask, w.runoff, B, H, nw, st);
+    row_scan_launch(w.runoff, nullptr, B, H, st);
+    run_fill_launch(mask, w.runoff, w.rxs, w.rxe, w.parent, w.box, B, H, nw, runcap, st);
+    run_merge_launch(w.runoff, w.rxs, w.rxe, w.parent, B, H, runcap, st);
+    hipLaunchKernelGGL(az_init_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.area, H, runcap, rows);
+    hipLaunchKernelGGL(az_accum_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.box, w.area, H, runcap, rows);
+    hipLaunchKernelGGL(az_finders_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.box, w.area, H, runcap, p.min_module, p.max_module,
+                       p.centre_tol, p.ring_tol, p.max_finders, w.nfind, w.finders, rows);
+    hipLaunchKernelGGL(az_decode_kernel, dim3(p.max_finders, B), dim3(64), 0, st, mask, w.finders, w.nfind, w.box, H, W, nw, runcap, p.max_finders, p.quiet,
+                       p.mark_max, w.res, w.resdata);
+    hipLaunchKernelGGL(az_output_kernel, dim3(B), dim3(256), 0, st, w.res, w.resdata, w.nfind, p.max_finders, p.max_codes, w.tmp, p.counts, p.codes, p.data,
+                       p.finder_counts);
+    return hipGetLastError();
+}

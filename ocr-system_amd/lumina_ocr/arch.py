@@ -532,6 +532,14 @@ QR_PARAMS = dict(threshold=BARCODE_PARAMS["threshold"], min_module=3, max_module
 DM_PARAMS = dict(threshold=BARCODE_PARAMS["threshold"], min_module=3, max_module=24, quiet=1, timing_max=3, solid_max=3, max_candidates=256,
                  max_codes=16)
 
+# Aztec (lumina_ocr_aztec + utils/aztec.py, definition restated in tests/aztec_reference.py): ink at the barcodes' threshold so that
+# one mask serves the four passes.  The finder is the bullseye's core, a solid square of one module, inside the component of its
+# 5-module ring: the ring's sides are 5 cores within ring_tol / 16 of a module and the two are concentric within centre_tol / 16.
+# quiet = 1 module.  mark_max = 4 mismatches in the bullseye's modules and the twelve corner modules of the mode ring together: a
+# clean symbol has none, the wrong kind (compact read as full or the reverse) at least six.  max_finders <= 64, max_codes <= 64.
+AZTEC_PARAMS = dict(threshold=BARCODE_PARAMS["threshold"], min_module=3, max_module=24, quiet=1, centre_tol=8, ring_tol=8, mark_max=4,
+                    max_finders=64, max_codes=16)
+
 # Page orientation (lumina_ocr_page_quarter / _page_turn / _page_vote + utils/page_orient.py): ink as above; a page is sideways when the
 # energy of its column profile exceeds `ratio` times that of its row profile (text lines make the profile across them jagged), and an
 # upright-or-upside-down page is upside-down when it has at least min_lines lines and the classifier flips more than half of them.

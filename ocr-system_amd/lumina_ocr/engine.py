@@ -100,11 +100,13 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_qrcodes": (i32, [vp, vp, i32, i32, i32] + [i32] * 9 + [vp] * 7),
         "lumina_ocr_qrcodes_versions": (i32, [vp, vp, i32, i32, i32] + [i32] * 10 + [vp] * 7),
         "lumina_ocr_datamatrix": (i32, [vp, vp, i32, i32, i32] + [i32] * 8 + [vp] * 7),
+        "lumina_ocr_aztec": (i32, [vp, vp, i32, i32, i32] + [i32] * 9 + [vp] * 7),
         "lumina_ocr_rules_and_marks": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_selection_marks_round": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_rules_and_marks_round": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp,
                                                    i32, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_page_quarter_workspace_bytes": (sz, [i32, i32, i32]),
+        "lumina_ocr_aztec_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
         "lumina_ocr_page_quarter": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_page_turn": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp]),
         "lumina_ocr_page_vote": (i32, [vp, vp, vp, i32, i32, vp, vp]),
@@ -133,7 +135,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_png_probe", "lumina_ocr_png_decode", "lumina_ocr_flate_image_decode", "lumina_ocr_ccitt_decode", "lumina_ocr_fax_decode", "lumina_ocr_strip_image_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
     "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks", "lumina_ocr_selection_marks_round",
-    "lumina_ocr_rules_and_marks_round", "lumina_ocr_barcodes", "lumina_ocr_barcodes_kinds", "lumina_ocr_qrcodes", "lumina_ocr_qrcodes_versions", "lumina_ocr_datamatrix",
+    "lumina_ocr_rules_and_marks_round", "lumina_ocr_barcodes", "lumina_ocr_barcodes_kinds", "lumina_ocr_qrcodes", "lumina_ocr_qrcodes_versions", "lumina_ocr_datamatrix", "lumina_ocr_aztec", "lumina_ocr_aztec_workspace_bytes",
     "lumina_ocr_page_quarter_workspace_bytes", "lumina_ocr_page_quarter", "lumina_ocr_page_turn", "lumina_ocr_page_vote",
 ]
 
@@ -748,6 +750,35 @@ class Engine:
         self._chk(self.lib.lumina_ocr_datamatrix(self._h, _ptr(pages), n, h, w, *q, _ptr(codes), _ptr(data), _ptr(counts), _ptr(cands), _ptr(mask_in),
                                                  _ptr(mask), self._stream()))
         return (codes, data, counts, mask, cands) if debug else (codes, data, counts)
+
+    # -- Aztec (compact 1-4 layers, full-range 1-11 layers; the host half is utils/aztec.py) ----------------------------------------------
+    _AZTEC_KEYS = ("threshold", "min_module", "max_module", "quiet", "centre_tol", "ring_tol", "mark_max", "max_finders", "max_codes")
+
+    def aztec(self, pages, mask_in=None, debug: bool = False, **params):
+        """uint8 [n,H,W,3] device -> (codes int32 [n,max_codes,12], data int32 [n,max_codes,320], counts int32 [n]) on the device: the
+        Aztec symbols of each page as x0, y0, x1, y1, layers, compact, codeword width, ndata, corrected errors, rotation, mode-message
+        errors, mismatches, sorted by (y0, x0, y1, x1), with their corrected data codewords (still bit-stuffed); counts = the true
+        numbers (a list whose count exceeds max_codes is not written).  params: any of arch.AZTEC_PARAMS' keys, defaulting to them.
+        mask_in: the ink mask of the pages at this threshold, int64 [n,H,ceil(W/64)], when it is there already.  Asynchronous.
+        debug=True also returns the ink mask the pass worked on and the finder count of every page."""
+        torch = _torch()
+        n, h, w, c = pages.shape
+        assert c == 3 and pages.dtype == torch.uint8 and pages.is_contiguous()
+        unknown = set(params) - set(self._AZTEC_KEYS)
+        if unknown:
+            raise TypeError("aztec: unknown parameters %s" % sorted(unknown))
+        q = [int(params[k]) if params.get(k) is not None else arch.AZTEC_PARAMS[k] for k in self._AZTEC_KEYS]
+        max_codes = q[-1]
+        if mask_in is not None:
+            assert mask_in.dtype == torch.int64 and mask_in.is_contiguous() and tuple(mask_in.shape) == (n, h, (w + 63) // 64)
+        codes = torch.zeros((n, max(max_codes, 0), 12), dtype=torch.int32, device=pages.device)
+        data = torch.zeros((n, max(max_codes, 0), 320), dtype=torch.int32, device=pages.device)
+        counts = torch.zeros((n,), dtype=torch.int32, device=pages.device)
+        mask = torch.zeros((n, h, (w + 63) // 64), dtype=torch.int64, device=pages.device) if debug else None
+        finders = torch.zeros((n,), dtype=torch.int32, device=pages.device) if debug else None
+        self._chk(self.lib.lumina_ocr_aztec(self._h, _ptr(pages), n, h, w, *q, _ptr(codes), _ptr(data), _ptr(counts), _ptr(finders), _ptr(mask_in),
+                                            _ptr(mask), self._stream()))
+        return (codes, data, counts, mask, finders) if debug else (codes, data, counts)
 
     def rules_and_marks(self, pages, threshold=None, gap=None, min_len=None, max_thick=None, max_rules=None, min_side=None, max_side=None,
                         max_marks=None):

@@ -48,6 +48,9 @@ class PageDetections:
     datamatrix: Optional[np.ndarray] = None   # int32 [m, 12] x0, y0, x1, y1, rows, cols, ndata, errors, rotation, timing mismatches, L misses, 0
                                               # of the page's Data Matrix symbols: OcrPipeline(datamatrix=True) only (empty on overflow)
     dm_data: Optional[np.ndarray] = None      # int32 [m, 208] their corrected data codewords (utils/datamatrix.py turns them into text)
+    aztec: Optional[np.ndarray] = None        # int32 [m, 12] x0, y0, x1, y1, layers, compact, codeword width, ndata, errors, rotation, mode errors,
+                                              # mismatches of the page's Aztec symbols: OcrPipeline(aztec=True) only (empty on overflow)
+    az_data: Optional[np.ndarray] = None      # int32 [m, 320] their corrected data codewords (utils/aztec.py turns them into text)
     word_quads: Optional[np.ndarray] = None   # int32 [n, 40, 8] the words of every line from the CTC alignment, each in its line's corner
                                               # order: OcrPipeline(word_boxes=True) only, like the three below
     word_spans: Optional[np.ndarray] = None   # int32 [n, 40, 2] first character in texts[i], character count
@@ -85,6 +88,7 @@ class _Pending:
     barcodes_host: Optional[list] = None   # barcodes: pinned copies of codes, symbol values, counts
     qrcodes_host: Optional[list] = None    # qrcodes: pinned copies of codes, data codewords, counts
     datamatrix_host: Optional[list] = None   # datamatrix: pinned copies of codes, data codewords, counts
+    aztec_host: Optional[list] = None        # aztec: pinned copies of codes, data codewords, counts
     words_host: Optional[list] = None   # word_boxes: pinned copies of word quads, spans, scores, counts
 
 
@@ -95,7 +99,7 @@ class OcrPipeline:
                  page_orient: bool = False, page_orient_params: Optional[dict] = None, word_boxes: bool = False, round_marks: bool = False,
                  round_mark_params: Optional[dict] = None, barcodes: bool = False, barcode_params: Optional[dict] = None,
                  qrcodes: bool = False, qr_params: Optional[dict] = None, qr_max_version: int = 10, barcode_kinds=arch.BARCODE_KINDS_DEFAULT,
-                 datamatrix: bool = False, dm_params: Optional[dict] = None):
+                 datamatrix: bool = False, dm_params: Optional[dict] = None, aztec: bool = False, aztec_params: Optional[dict] = None):
         """recognizer: "crnn" (CRNN-MobileNetV3 + BiLSTM, engine.load_rec) or "svtr" (SVTR, engine.load_svtr).
         angle_cls: PaddleOCR's use_angle_cls — every line is classified 0 / 180 degrees (engine.load_cls) before recognition, and a line
         read as 180 with probability > cls_thresh is recognised turned; boxes and reading order are unchanged.  Per-line labels are
@@ -119,6 +123,9 @@ class OcrPipeline:
         datamatrix: the Data Matrix symbols (ECC 200, up to 52 x 52) of the processed pages (engine.datamatrix, parameters arch.DM_PARAMS
         or dm_params) come back as PageDetections.datamatrix / dm_data; the pass runs behind the QR pass and takes the ink mask the
         earlier passes made at its threshold; with a gather it is not run.
+        aztec: the Aztec symbols (compact 1-4 layers, full-range 1-11 layers) of the processed pages (engine.aztec, parameters
+        arch.AZTEC_PARAMS or aztec_params; an unknown key is a ValueError) come back as PageDetections.aztec / az_data; the pass runs behind
+        the Data Matrix pass and takes the ink mask an earlier pass made at its threshold; with a gather it is not run.
         page_orient: run_oriented() finds for every page the quarter turns that make it upright (ink profiles for sideways pages,
         parameters arch.PAGE_ORIENT_PARAMS or page_orient_params; the line classifier's majority for upside-down ones, so it needs
         engine.load_cls like angle_cls), turns the raw page on the device and runs the stages below on the upright page.  run /
@@ -159,6 +166,10 @@ class OcrPipeline:
             raise ValueError("qr_max_version must be 10..40, not %r" % (qr_max_version,))
         self.datamatrix = bool(datamatrix)
         self.dm_params = dict(arch.DM_PARAMS if dm_params is None else dm_params)
+        self.aztec = bool(aztec)
+        self.aztec_params = dict(arch.AZTEC_PARAMS if aztec_params is None else aztec_params)
+        if set(self.aztec_params) - set(arch.AZTEC_PARAMS):
+            raise ValueError("aztec_params: unknown keys %s" % sorted(set(self.aztec_params) - set(arch.AZTEC_PARAMS)))
         self.page_orient = bool(page_orient)
         self.word_boxes = bool(word_boxes)
         self.space_id = self.charset.index(" ") if " " in self.charset else -1   # the class words split on (-1: a line is one word)
@@ -199,9 +210,9 @@ class OcrPipeline:
 
     def submit_recognize(self, processed, boxes, scores, counts) -> "_Pending":
         """One host sync (box counts), then crop + CRNN + CTC and the device->pinned-host copies are enqueued. -> pending."""
-        rules, marks, codes, qrs, dms = self._submit_page_analysis(processed)   # enqueued before the sync below: it runs while the host waits for the box counts
+        rules, marks, codes, qrs, dms, azs = self._submit_page_analysis(processed)   # enqueued before the sync below: it runs while the host waits for the box counts
         counts_h = counts.cpu().numpy()  # the one host sync of the pipeline
-        return self._submit_lines(processed, boxes, scores, counts_h, rules, marks, barcodes=codes, qrcodes=qrs, datamatrix=dms)
+        return self._submit_lines(processed, boxes, scores, counts_h, rules, marks, barcodes=codes, qrcodes=qrs, datamatrix=dms, aztec=azs)
 
     def _submit_datamatrix(self, processed, mask, mask_at):
         """Enqueue the Data Matrix pass -> (codes, data codewords, counts) device tensors; mask: the ink mask an earlier pass made at the
@@ -210,14 +221,28 @@ class OcrPipeline:
         return self.eng.datamatrix(processed, mask_in=mask if mask is not None and mask_at == dp["threshold"] else None, **dp)
 
     def _submit_page_analysis(self, processed):
+        """_submit_passes, then the Aztec pass behind them -> (rules, marks, codes, qr codes, data matrix symbols, aztec symbols), None
+        where a pass is off.  With the Aztec pass off this is _submit_passes as it ever was."""
+        if not (self.aztec and self.gather is None):
+            return self._submit_passes(processed) + (None,)
+        ap = self.aztec_params
+        handed = []
+        out = self._submit_passes(processed, handed)
+        mask = handed[0][0] if handed and handed[0][1] == ap["threshold"] else None
+        return out + (self.eng.aztec(processed, mask_in=mask, **ap),)
+
+    def _submit_passes(self, processed, handed: Optional[list] = None):
         """Enqueue the table rules, selection marks, barcodes, QR codes and Data Matrix symbols of the processed pages -> (rules, marks,
         codes, qr codes, data matrix symbols), None where a pass is off.  The barcode pass takes the ink mask from the marks or the tables
         call when that call ran on its own at the barcodes' threshold; the joint rules-and-marks call hands no mask out, so behind it the barcode pass computes its own.  The QR
         pass takes the mask the same way, or from the barcode pass when that one computed it at the QR threshold.  The Data Matrix pass
-        runs last, on the mask of whichever earlier pass made one at its threshold (the barcode or the QR pass hands its own out)."""
+        runs last, on the mask of whichever earlier pass made one at its threshold (the barcode or the QR pass hands its own out).
+        handed: a list that receives (mask, threshold) when an earlier pass made a mask (the Aztec pass asks, and the passes then hand
+        their mask on as they do for the Data Matrix pass); without it nothing runs differently."""
         on = self.gather is None
-        if self.datamatrix and on:   # behind the other passes, with the mask they made when it is the Data Matrix pass's threshold too
-            want = (self.barcode_params["threshold"] if self.barcodes else self.qr_params["threshold"] if self.qrcodes else self.dm_params["threshold"])
+        if (self.datamatrix or handed is not None) and on:   # behind the other passes, with the mask they made when it is the last pass's threshold too
+            last = self.dm_params if self.datamatrix else self.aztec_params
+            want = (self.barcode_params["threshold"] if self.barcodes else self.qr_params["threshold"] if self.qrcodes else last["threshold"])
             rules, marks, mask = self._submit_rules_marks(processed, mask_at=want)
             codes = qrs = None
             if self.barcodes:
@@ -229,7 +254,9 @@ class OcrPipeline:
                 qrs = self._submit_qrcodes(processed, qmask, debug=mask is None)
                 if mask is None:
                     qrs, mask, want = qrs[:3], qrs[3], self.qr_params["threshold"]
-            return rules, marks, codes, qrs, self._submit_datamatrix(processed, mask, want)
+            if handed is not None and mask is not None:
+                handed.append((mask, want))
+            return rules, marks, codes, qrs, self._submit_datamatrix(processed, mask, want) if self.datamatrix else None
         want = self.barcode_params["threshold"] if self.barcodes and on else (self.qr_params["threshold"] if self.qrcodes and on else None)
         rules, marks, mask = self._submit_rules_marks(processed, mask_at=want)
         if not (self.qrcodes and on):
@@ -304,7 +331,7 @@ class OcrPipeline:
         page_idx = torch.from_numpy(page_h.astype(np.int32)).to(boxes.device, non_blocking=True)
         return quads, det_sc, page_idx
 
-    def _submit_lines(self, processed, boxes, scores, counts_h, rules, marks, lines=None, barcodes=None, qrcodes=None, datamatrix=None) -> "_Pending":
+    def _submit_lines(self, processed, boxes, scores, counts_h, rules, marks, lines=None, barcodes=None, qrcodes=None, datamatrix=None, aztec=None) -> "_Pending":
         """submit_recognize after its sync.  lines: (quads, det scores, page index, cls_forward's outputs or None) of the counted lines when
         the caller has them already (run_oriented: the vote needed them), else they are selected and classified here."""
         import torch
@@ -321,13 +348,15 @@ class OcrPipeline:
             pend.qrcodes_host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in qrcodes]
         if datamatrix is not None:
             pend.datamatrix_host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in datamatrix]
+        if aztec is not None:
+            pend.aztec_host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in aztec]
         if self.gather is not None:
             self.gather.begin(counts_h)          # capacity all-reduce runs beside the recogniser
         if n == 0:
             if self.gather is not None:          # every rank takes part in the collective, with or without lines
                 e = lambda *shape, dt=torch.int32: torch.empty(shape, dtype=dt, device=boxes.device)
                 pend.gathered = self.gather.submit(counts_h, e(0, 8), e(0, dt=torch.float32), e(0, 80), e(0), e(0, dt=torch.float32))
-            elif pend.rules_host is not None or pend.marks_host is not None or pend.barcodes_host is not None or pend.qrcodes_host is not None or pend.datamatrix_host is not None:
+            elif pend.rules_host is not None or pend.marks_host is not None or pend.barcodes_host is not None or pend.qrcodes_host is not None or pend.datamatrix_host is not None or pend.aztec_host is not None:
                 pend.event = torch.cuda.Event()
                 pend.event.record(torch.cuda.current_stream(processed.device))
             return pend
@@ -370,11 +399,12 @@ class OcrPipeline:
         codes = self._page_barcodes(pend)
         qrs = self._page_barcodes(pend, qr=True)
         dms = self._page_barcodes(pend, dm=True)
+        azs = self._page_barcodes(pend, az=True)
         if pend.n == 0:
             nw = self._empty_words() if self.word_boxes else {}
             return [PageDetections(np.zeros((0, 8), np.int32), [], np.zeros(0, np.float32), np.zeros(0, np.float32), w, h,
                                    hrules=rules[p][0], vrules=rules[p][1], marks=marks[p], round_marks=rounds[p], barcodes=codes[p][0],
-                                   barcode_syms=codes[p][1], qrcodes=qrs[p][0], qr_data=qrs[p][1], datamatrix=dms[p][0], dm_data=dms[p][1], **nw) for p in range(b)], pend.processed
+                                   barcode_syms=codes[p][1], qrcodes=qrs[p][0], qr_data=qrs[p][1], datamatrix=dms[p][0], dm_data=dms[p][1], aztec=azs[p][0], az_data=azs[p][1], **nw) for p in range(b)], pend.processed
         text_h, len_h, score_h, quads_h, det_h, *cls_h = (t.numpy() for t in pend.host)
         all_texts = self._decoder.decode(text_h, len_h)
         words_h = None
@@ -390,7 +420,7 @@ class OcrPipeline:
                                       *((cls_h[0][off:off + c], cls_h[1][off:off + c]) if cls_h else ()),
                                       hrules=rules[p][0], vrules=rules[p][1], marks=marks[p], round_marks=rounds[p],
                                       barcodes=codes[p][0], barcode_syms=codes[p][1], qrcodes=qrs[p][0], qr_data=qrs[p][1],
-                                      datamatrix=dms[p][0], dm_data=dms[p][1],
+                                      datamatrix=dms[p][0], dm_data=dms[p][1], aztec=azs[p][0], az_data=azs[p][1],
                                       **({} if words_h is None else dict(zip(self._WORD_FIELDS, (t[off:off + c] for t in words_h))))))
             off += c
         return out, pend.processed
@@ -449,11 +479,11 @@ class OcrPipeline:
             out.append(rows[p, :m].copy())
         return out
 
-    def _page_barcodes(self, pend: "_Pending", qr: bool = False, dm: bool = False):
+    def _page_barcodes(self, pend: "_Pending", qr: bool = False, dm: bool = False, az: bool = False):
         """-> per page (codes [m,8], symbol values [m,64]) from the pending batch's host copies, or (None, None) without barcodes.  A
         page whose true count exceeds the capacity has no rows: it is treated as having no barcodes.  qr: the same of the QR pass's
-        copies, (codes [m,12], data codewords [m,288], or bytes [m,2956] above qr_max_version 10); dm: of the Data Matrix pass's, (codes [m,12], data codewords [m,208])."""
-        host = pend.datamatrix_host if dm else pend.qrcodes_host if qr else pend.barcodes_host
+        copies, (codes [m,12], data codewords [m,288], or bytes [m,2956] above qr_max_version 10); dm: of the Data Matrix pass's, (codes [m,12], data codewords [m,208]); az: of the Aztec pass's, (codes [m,12], data codewords [m,320])."""
+        host = pend.aztec_host if az else pend.datamatrix_host if dm else pend.qrcodes_host if qr else pend.barcodes_host
         if host is None:
             return [(None, None)] * pend.b
         rows, syms, cnt = (t.numpy() for t in host)
@@ -462,7 +492,7 @@ class OcrPipeline:
         for p in range(pend.b):
             m = int(cnt[p])
             if m > cap:
-                logger.warning("page %d of the batch has %d %s, more than max_codes = %d: none are reported for it", p, m, "Data Matrix symbols" if dm else "QR codes" if qr else "barcodes", cap)
+                logger.warning("page %d of the batch has %d %s, more than max_codes = %d: none are reported for it", p, m, "Aztec symbols" if az else "Data Matrix symbols" if dm else "QR codes" if qr else "barcodes", cap)
                 m = 0
             out.append((rows[p, :m].copy(), syms[p, :m].copy()))
         return out
@@ -490,10 +520,10 @@ class OcrPipeline:
         import torch
         processed, boxes, scores, counts = self.submit_detect(pages, enhance, deskew)
         b = processed.shape[0]
-        rules, marks, codes, qrs, dms = self._submit_page_analysis(processed)
+        rules, marks, codes, qrs, dms, azs = self._submit_page_analysis(processed)
         counts_h = counts.cpu().numpy()
         if int(counts_h.sum()) == 0:
-            return self._submit_lines(processed, boxes, scores, counts_h, rules, marks, barcodes=codes, qrcodes=qrs, datamatrix=dms), np.zeros(b, bool)
+            return self._submit_lines(processed, boxes, scores, counts_h, rules, marks, barcodes=codes, qrcodes=qrs, datamatrix=dms, aztec=azs), np.zeros(b, bool)
         quads, det_sc, page_idx = self._select_lines(boxes, scores, counts_h, b)
         ccrops, cwidths = self.eng.cls_crop(processed, quads, page_idx)
         cls = self.eng.cls_forward(ccrops, cwidths, self.cls_thresh)
@@ -506,7 +536,7 @@ class OcrPipeline:
             cls = tuple(t.index_select(0, keep) for t in cls)
             counts_h = np.where(flipped, 0, counts_h).astype(counts_h.dtype)
         lines = (quads, det_sc, page_idx, cls if self.angle_cls else None)
-        return self._submit_lines(processed, boxes, scores, counts_h, rules, marks, lines=lines, barcodes=codes, qrcodes=qrs, datamatrix=dms), flipped
+        return self._submit_lines(processed, boxes, scores, counts_h, rules, marks, lines=lines, barcodes=codes, qrcodes=qrs, datamatrix=dms, aztec=azs), flipped
 
     def run_oriented_groups(self, pages, enhance: bool = True, deskew: bool = False):
         """run_oriented's work, as the passes made it: -> [(input indices, detections, processed pages [m,H',W',3] on the device)], every

@@ -34,6 +34,7 @@ from ..utils import marks as mark_layout
 from ..utils import page_orient
 from ..utils import qrcodes as qr_layout
 from ..utils import datamatrix as dm_layout
+from ..utils import aztec as aztec_layout
 from ..utils import pdf_pages, tiff_pages
 from ..utils import tables as table_layout
 from ..utils.image_preprocessing import ImagePreprocessor, get_optimal_size
@@ -166,6 +167,10 @@ class OCRService:
         # "DataMatrix" with their decoded content and a `:barcode: <content>` line of the Markdown, behind the 1-D and QR codes of the page;
         # the text lines the detector found inside a symbol are dropped.  Off by default: every output is then the one without it.
         self._use_datamatrix = os.environ.get("LUMINA_OCR_DATAMATRIX", "0").lower() not in ("", "0", "false", "no")
+        # LUMINA_OCR_AZTEC=1: Aztec symbols (compact 1-4 layers, full-range 1-11 layers) become `barcode` entries of kind "Aztec" with their
+        # decoded content and a `:barcode: <content>` line of the Markdown, behind the 1-D, QR and Data Matrix codes of the page; the text
+        # lines the detector found inside a symbol are dropped.  Off by default: every output is then the one without it.
+        self._use_aztec = os.environ.get("LUMINA_OCR_AZTEC", "0").lower() not in ("", "0", "false", "no")
         # LUMINA_OCR_PAGE_ORIENTATION=1: pages lying sideways or upside-down are turned upright on the device before anything else reads
         # them (after decode and EXIF orientation, before the resize), and json_output reports page_rotation.  It uses the classifier
         # (LUMINA_OCR_CLS_WEIGHTS) whether or not LUMINA_OCR_USE_ANGLE_CLS is set.  Off by default: every output is then the one without it.
@@ -250,7 +255,7 @@ class OCRService:
                     pipeline = OcrPipeline(eng, charset=charset, max_dimension=self.max_dimension, post=post, recognizer=self._recognizer,
                                            angle_cls=self._use_angle_cls, tables=self._use_tables, marks=self._use_marks,
                                            page_orient=self._use_page_orient, word_boxes=self._use_word_boxes, round_marks=self._use_round_marks,
-                                           barcodes=self._use_barcodes, qrcodes=self._use_qrcodes, qr_max_version=qr_max_version, datamatrix=self._use_datamatrix,
+                                           barcodes=self._use_barcodes, qrcodes=self._use_qrcodes, qr_max_version=qr_max_version, datamatrix=self._use_datamatrix, aztec=self._use_aztec,
                                            barcode_kinds=self._barcode_kinds if self._use_barcodes else arch.BARCODE_KINDS_DEFAULT)
             except Exception:
                 eng.close()
@@ -348,15 +353,17 @@ class OCRService:
     def _finish_page(self, det, jpeg: bytes, processed_hw, page_number: int, original_size, t0: float) -> OCROutput:
         triples = det.triples()
         line_words = det.line_words() if getattr(det, "word_counts", None) is not None else None   # LUMINA_OCR_WORD_BOXES=1
-        codes = strips = squares = matrices = None
+        codes = strips = squares = matrices = aztecs = None
         if getattr(det, "barcodes", None) is not None:   # LUMINA_OCR_BARCODES=1: what the recogniser made of the bars is no text
             strips = barcode_layout.read_barcodes(det.barcodes, det.barcode_syms)
         if getattr(det, "qrcodes", None) is not None:    # LUMINA_OCR_QRCODES=1: the same for the modules of a QR symbol
             squares = qr_layout.read_qrcodes(det.qrcodes, det.qr_data)
         if getattr(det, "datamatrix", None) is not None:   # LUMINA_OCR_DATAMATRIX=1: and of a Data Matrix symbol
             matrices = dm_layout.read_datamatrix(det.datamatrix, det.dm_data)
-        if strips is not None or squares is not None or matrices is not None:
-            codes = (strips or []) + (squares or []) + (matrices or [])
+        if getattr(det, "aztec", None) is not None:   # LUMINA_OCR_AZTEC=1: and of an Aztec symbol
+            aztecs = aztec_layout.read_aztec(det.aztec, det.az_data)
+        if strips is not None or squares is not None or matrices is not None or aztecs is not None:
+            codes = (strips or []) + (squares or []) + (matrices or []) + (aztecs or [])
             keep = [i for i, t in enumerate(triples) if not barcode_layout.inside_any(t[0], codes)]
             if len(keep) < len(triples):
                 triples = [triples[i] for i in keep]
@@ -395,6 +402,8 @@ class OCRService:
             counts["qrcodes_count"] = len(squares)
         if matrices is not None:
             counts["datamatrix_count"] = len(matrices)
+        if aztecs is not None:
+            counts["aztec_count"] = len(aztecs)
         if getattr(det, "turn", None) is not None:   # LUMINA_OCR_PAGE_ORIENTATION=1
             counts["page_rotation"] = page_orient.page_rotation(det.turn)
         ph, pw = processed_hw
@@ -963,7 +972,7 @@ class OCRService:
     # ---- status (:759-795) ----
     def get_status(self) -> Dict[str, Any]:
         st = {"client_initialized": self._pipeline is not None, "model_id": "dbnet-r18vd+crnn-mv3", "max_dimension": self.max_dimension,
-              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "device_pdf": self.device_pdf, "device_tiff": self.device_tiff, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
+              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "aztec": self._use_aztec, "device_pdf": self.device_pdf, "device_tiff": self.device_tiff, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
         if self._engine is not None:
             st["engine_version"] = self._engine.version()
             st["num_classes"] = self._engine.num_classes

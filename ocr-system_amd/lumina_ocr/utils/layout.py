@@ -153,7 +153,7 @@ def build_mark_boxes(marks: Sequence[Dict[str, Any]], page_number: int = 1) -> L
 
 
 def build_barcode_boxes(found: Sequence[Dict[str, Any]], page_number: int = 1) -> List[Dict[str, Any]]:
-    """`barcode` entries: type, kind ("Code128" / "Code39" / "EAN13" / "UPCA" / "EAN8" / "UPCE" / "ITF" / "QRCode" / "DataMatrix"), content
+    """`barcode` entries: type, kind ("Code128" / "Code39" / "EAN13" / "UPCA" / "EAN8" / "UPCE" / "ITF" / "QRCode" / "DataMatrix" / "Aztec"), content
     (the decoded text), confidence, polygon, page_number; barcodes as utils/barcodes.read_barcodes, utils/qrcodes.read_qrcodes and
     utils/datamatrix.read_datamatrix give them, in their order.  A QR or Data Matrix symbol whose content is out of scope has content ""
     and the reason under `unsupported`; an ITF-14 has `itf14`: True; a GS1 Data Matrix has `gs1`: True."""
@@ -321,8 +321,8 @@ def validate_layout_boxes(boxes: Sequence[Dict[str, Any]]) -> List[str]:
         if b.get("type") == "word" and not isinstance(b.get("confidence"), float):
             problems.append(f"{i}: word confidence must be float")
         if b.get("type") == "barcode":
-            if b.get("kind") not in ("Code128", "Code39", "EAN13", "UPCA", "EAN8", "UPCE", "ITF", "QRCode", "DataMatrix"):
-                problems.append(f"{i}: barcode kind must be Code128, Code39, EAN13, UPCA, EAN8, UPCE, ITF, QRCode or DataMatrix")
+            if b.get("kind") not in ("Code128", "Code39", "EAN13", "UPCA", "EAN8", "UPCE", "ITF", "QRCode", "DataMatrix", "Aztec"):
+                problems.append(f"{i}: barcode kind must be Code128, Code39, EAN13, UPCA, EAN8, UPCE, ITF, QRCode, DataMatrix or Aztec")
             if not isinstance(b.get("content"), str):
                 problems.append(f"{i}: barcode content must be str")
             if not isinstance(b.get("confidence"), float) or not 0.0 <= b["confidence"] <= 1.0:
