@@ -24,7 +24,7 @@ hipError_t lstm_recurrent_launch(const bf16_t* xproj, const bf16_t* whh, bf16_t*
 // CTC head: logits = seq[M][K] * W^T[K][C] + b, never materialised; per row -> argmax index + softmax max-prob.
 // wpk: weights packed [ntile of 64 classes][plane][64 rows][8] (pack_ctc_weights).
 struct CtcFcParams {
-    const bf16_t* seq;  // [M][K], K % 32 == 0
+    const bf16_t* seq;  // [M][K], K == 192; the launcher refuses any other K, and M < 1 or ntiles < 1 (hipErrorInvalidValue)
     const bf16_t* wpk;
     const float* bias;  // [ntiles*64], padded entries = -1e30 (never win)
     float* part_max; int* part_idx; float* part_sum;  // [M][ntiles]

@@ -252,121 +252,173 @@ __global__ __launch_bounds__(192) void lstm_kernel(const bf16_t* xproj, const bf
 }
 
 // ------------------------------------------------------------------ CTC head: fused FC + argmax + softmax-max
-// A-stationary MFMA GEMM: the block keeps its 128 sequence rows (K <= 192) in LDS and streams all
-// 64-class weight tiles through a second LDS region; running (max, argmax, sum-exp) stay in registers,
-// the [M, C] logits never exist in memory.
-constexpr int CT_MT = 1, CT_NT = 2;  // per wave: CT_MT x 32 rows, CT_NT x 32 classes per weight tile (2 workgroups per CU)
-constexpr int CT_ROWS = 4 * 32 * CT_MT, CT_BN = 32 * CT_NT, CT_KMAX = 192, CT_WIT = CT_BN * (CT_KMAX / 8) / 256;
-constexpr int CT_PLANE_A = CT_ROWS + 4;  // entries, == 4 (mod 16)
+// A-stationary MFMA GEMM for K = 192 (both recognisers).  A wave keeps its 32 sequence rows in registers (12 fragments) for the whole
+// launch; the 64-class weight tiles stream through two LDS buffers (LDS-DMA), their 64 biases through a ring of four slots, both one
+// tile ahead, so one barrier per tile is enough.  Two accumulator sets: while the MFMAs of tile t fill one, the soft-max
+// and arg-max work of tile t - 1 reads the other (the vector instructions issue in the MFMAs' shadow).  The running (max, argmax,
+// sum-exp) stay in registers, the [M, C] logits never exist in memory.
+// What defines the bits: logit = K sum + bias in fp32; exp2((v - tm) * log2e) as a subtraction, then a multiplication; the tile's sum
+// over (nt, j) ascending, then the partner half-wave's; the two rescale forms of the running sum.  The maximum is exact in any order,
+// so it is taken with max3 and the class index is derived only when a tile's maximum beats the running one.
+constexpr int CT_NT = 2;                                   // per wave: 32 rows x CT_NT x 32 classes per weight tile
+constexpr int CT_ROWS = 4 * 32, CT_BN = 32 * CT_NT, CT_K = 192, CT_KSTEPS = CT_K / 16;
+constexpr int CT_W_ITEMS = CT_BN * (CT_K / 8);             // 16-byte items of a weight tile: 1536 = 6 per thread, no remainder
+constexpr int CT_WIT = CT_W_ITEMS / 256, CT_WBYTES = CT_W_ITEMS * 16;
+constexpr int CT_BIAS_SLOTS = 4;                           // tile t + 1 is written while t - 1 (epilogue) and t are still read
+constexpr size_t CT_LDS = 2 * (size_t)CT_WBYTES;          // dynamic; + 1 KB of bias slots (static) = 50 176 B: two work-groups per CU
+static_assert(CT_W_ITEMS % 256 == 0 && CT_BN * sizeof(float) / 16 <= 64, "the staging below has no remainder loop");
 
 typedef _Float16 ctc_f16x8_t __attribute__((ext_vector_type(8)));
 template <int DT>   // storage type of the sequence and the weights: 0 bf16, 1 fp16 (SVTR fp16 mode)
 __global__ __launch_bounds__(256, 2) void ctc_fc_argmax_kernel(const CtcFcParams p) {
+    typedef typename std::conditional<DT == 1, ctc_f16x8_t, bf16x8_t>::type frag_t;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int npl = p.K >> 3;
-    unsigned char* sA = smem;
-    unsigned char* sW = smem + (size_t)npl * CT_PLANE_A * 16;
+    // the bias ring is an LDS object of its own: the compiler then knows that the weight DMA cannot write what the epilogue reads
+    __shared__ __attribute__((aligned(16))) float sB[CT_BIAS_SLOTS * CT_BN];
+    unsigned char* sW = smem;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int row0 = blockIdx.x * CT_ROWS;
+    const int last = p.ntiles - 1;
+    constexpr float LOG2E = 1.4426950408889634f;
 
-    for (int i = tid; i < CT_ROWS * npl; i += 256) {
-        const int row = i / npl, c = i - row * npl;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (row0 + row < p.M) v = *reinterpret_cast<const uint4*>(p.seq + (size_t)(row0 + row) * p.K + c * 8);
-        *reinterpret_cast<uint4*>(sA + ((size_t)c * CT_PLANE_A + row) * 16) = v;
-    }
-    const int w_items = CT_BN * npl;           // 16-byte items per weight tile (<= 3072)
-    const int wit = (w_items + 255) / 256;     // <= CT_WIT
-    uint4 wreg[CT_WIT];
-#define CTC_LOAD_W(tile_)                                                                              \
-    {                                                                                                  \
-        const uint4* src = reinterpret_cast<const uint4*>(p.wpk + (size_t)(tile_) * w_items * 8);      \
-        _Pragma("unroll") for (int it = 0; it < CT_WIT; ++it) {                                            \
-            const int i = tid + 256 * it;                                                              \
-            uint4 t_ = make_uint4(0, 0, 0, 0);                                                         \
-            if (it < wit && i < w_items) t_ = src[i];                                                  \
-            wreg[it] = t_;                                                                             \
-        }                                                                                              \
-    }
-    float run_m[CT_MT], run_s[CT_MT];
-    int run_i[CT_MT];
+    // this lane's part of its row: the B operand of every K step (rows past M are zero and are not written at the end)
+    frag_t arow[CT_KSTEPS];
+    {
+        const int row = row0 + wave * 32 + r;
+        const frag_t* src = reinterpret_cast<const frag_t*>(p.seq + (size_t)row * CT_K) + h;
 #pragma unroll
-    for (int mt = 0; mt < CT_MT; ++mt) { run_m[mt] = -3.0e38f; run_s[mt] = 0.f; run_i[mt] = 0; }
+        for (int kc = 0; kc < CT_KSTEPS; ++kc) {
+            frag_t v = {};
+            if (row < p.M) v = src[2 * kc];
+            arow[kc] = v;
+        }
+    }
 
-    CTC_LOAD_W(0);
-    const int ksteps = p.K >> 4;
-    for (int tile = 0; tile < p.ntiles; ++tile) {
+    // weight tile `tile` -> LDS buffer slot & 1 by LDS-DMA (no register round trip): six 1 KB pieces per wave, lane-linear, which is
+    // the packed tile's own order.  Its 64 biases travel through a register of 16 lanes into bias slot slot & 3 (landed): a DMA
+    // into a slot the compiler cannot tell from the one the epilogue reads would put a vmcnt(0) in front of that read.  No guards:
+    // 1536 items are 6 x 256, and a request past the last tile repeats the last tile into a buffer nobody reads any more.
+    uint4 breg = make_uint4(0, 0, 0, 0);
+    auto stage = [&](int tile, int slot) {
+        const uint4* src = reinterpret_cast<const uint4*>(p.wpk) + (size_t)tile * CT_W_ITEMS + tid;
+        unsigned char* dst = sW + (slot & 1) * CT_WBYTES + (tid - lane) * 16;
+#pragma unroll
+        for (int it = 0; it < CT_WIT; ++it)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 256 * it),
+                                             (__attribute__((address_space(3))) void*)(dst + 256 * it * 16), 16, 0, 0);
+        if (tid < CT_BN / 4) breg = reinterpret_cast<const uint4*>(p.bias + (size_t)tile * CT_BN)[tid];
+    };
+    // the requests of this wave have landed; the barrier then makes every wave's part visible
+    auto landed = [&](int slot) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (tid < CT_BN / 4) reinterpret_cast<uint4*>(sB + (slot & (CT_BIAS_SLOTS - 1)) * CT_BN)[tid] = breg;
         __syncthreads();
+    };
+
+    float run_m = -3.0e38f, run_s = 0.f;
+    int run_i = 0;
+
+    // tile t: request tile t + 1 into the other buffer, 24 MFMAs from buffer t & 1 (the fragments of K step k + 1 are requested
+    // before the MFMAs of step k; the first step's C operand is zero)
+    auto mma = [&](f32x16_t (&acc)[CT_NT], int t) {
+        stage(min(t + 1, last), t + 1);
+        const unsigned char* w = sW + (t & 1) * CT_WBYTES + (h * CT_BN + r) * 16;
+        frag_t wf[2][CT_NT];
 #pragma unroll
-        for (int it = 0; it < CT_WIT; ++it) {
-            const int i = tid + 256 * it;
-            if (it < wit && i < w_items) *reinterpret_cast<uint4*>(sW + (size_t)i * 16) = wreg[it];
-        }
-        __syncthreads();
-        if (tile + 1 < p.ntiles) CTC_LOAD_W(tile + 1);
-        f32x16_t acc[CT_MT][CT_NT];
+        for (int nt = 0; nt < CT_NT; ++nt) wf[0][nt] = *reinterpret_cast<const frag_t*>(w + nt * 32 * 16);
 #pragma unroll
-        for (int mt = 0; mt < CT_MT; ++mt)
+        for (int kc = 0; kc < CT_KSTEPS; ++kc) {
+            if (kc + 1 < CT_KSTEPS) {
 #pragma unroll
-            for (int nt = 0; nt < CT_NT; ++nt)
+                for (int nt = 0; nt < CT_NT; ++nt)
+                    wf[(kc + 1) & 1][nt] = *reinterpret_cast<const frag_t*>(w + (2 * (kc + 1) * CT_BN + nt * 32) * 16);
+            }
 #pragma unroll
-                for (int j = 0; j < 16; ++j) acc[mt][nt][j] = 0.f;
-        for (int kc = 0; kc < ksteps; ++kc) {
-            typedef typename std::conditional<DT == 1, ctc_f16x8_t, bf16x8_t>::type frag_t;
-            frag_t bfr[CT_MT], afr[CT_NT];
-#pragma unroll
-            for (int mt = 0; mt < CT_MT; ++mt)
-                bfr[mt] = *reinterpret_cast<const frag_t*>(sA + ((size_t)(2 * kc + h) * CT_PLANE_A + wave * (32 * CT_MT) + mt * 32 + r) * 16);
-#pragma unroll
-            for (int nt = 0; nt < CT_NT; ++nt)
-                afr[nt] = *reinterpret_cast<const frag_t*>(sW + ((size_t)(2 * kc + h) * CT_BN + nt * 32 + r) * 16);
-#pragma unroll
-            for (int mt = 0; mt < CT_MT; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < CT_NT; ++nt) {
-                    if constexpr (DT == 1) acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(afr[nt], bfr[mt], acc[mt][nt], 0, 0, 0);
-                    else acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[nt], bfr[mt], acc[mt][nt], 0, 0, 0);
-                }
-        }
-        // per-tile reduction over this lane's 64 classes, then the partner half-wave, then the running state
-        const float* bt = p.bias + tile * CT_BN;
-#pragma unroll
-        for (int mt = 0; mt < CT_MT; ++mt) {
-            float tm = -3.0e38f;
-            int ti = 0;
-#pragma unroll
-            for (int nt = 0; nt < CT_NT; ++nt)
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const int cls = nt * 32 + (j & 3) + 8 * (j >> 2) + 4 * h;
-                    const float v = acc[mt][nt][j] + bt[cls];
-                    acc[mt][nt][j] = v;
-                    if (v > tm) { tm = v; ti = cls; }
-                }
-            const float om = __shfl_xor(tm, 32);
-            const int oi = __shfl_xor(ti, 32);
-            if (om > tm || (om == tm && oi < ti)) { tm = om; ti = oi; }
-            float ts = 0.f;
-#pragma unroll
-            for (int nt = 0; nt < CT_NT; ++nt)
-#pragma unroll
-                for (int j = 0; j < 16; ++j) ts += __builtin_amdgcn_exp2f((acc[mt][nt][j] - tm) * 1.4426950408889634f);
-            ts += __shfl_xor(ts, 32);
-            if (tm > run_m[mt]) {
-                run_s[mt] = run_s[mt] * __builtin_amdgcn_exp2f((run_m[mt] - tm) * 1.4426950408889634f) + ts;
-                run_m[mt] = tm;
-                run_i[mt] = tile * CT_BN + ti;
-            } else {
-                run_s[mt] += ts * __builtin_amdgcn_exp2f((tm - run_m[mt]) * 1.4426950408889634f);
+            for (int nt = 0; nt < CT_NT; ++nt) {
+                const f32x16_t c = kc == 0 ? f32x16_t{} : acc[nt];
+                if constexpr (DT == 1) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[kc & 1][nt], arow[kc], c, 0, 0, 0);
+                else acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[kc & 1][nt], arow[kc], c, 0, 0, 0);
             }
         }
+    };
+    // tile t's logits (in place), its maximum over this lane's 32 classes and the partner's, its sum of exponentials
+    auto tile_sum = [&](f32x16_t (&acc)[CT_NT], int t, float& tm, float& ts) {
+        const float* bt = sB + (t & (CT_BIAS_SLOTS - 1)) * CT_BN + 4 * h;
+#pragma unroll
+        for (int nt = 0; nt < CT_NT; ++nt)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {   // classes nt * 32 + 8 * q + 4 * h + (0 .. 3) are accumulator entries 4 * q + (0 .. 3)
+                // (read as a fragment and re-typed: hipcc puts s_waitcnt vmcnt(0), a wait for the weight tile just requested, in front
+                // of a float4 read of LDS while an LDS-DMA is pending, and none in front of the fragment reads; check the ISA after edits)
+                typedef float ctc_f32x4_t __attribute__((ext_vector_type(4)));
+                const ctc_f32x4_t b = __builtin_bit_cast(ctc_f32x4_t, *reinterpret_cast<const frag_t*>(bt + nt * 32 + 8 * q));
+                acc[nt][4 * q + 0] = acc[nt][4 * q + 0] + b[0]; acc[nt][4 * q + 1] = acc[nt][4 * q + 1] + b[1];
+                acc[nt][4 * q + 2] = acc[nt][4 * q + 2] + b[2]; acc[nt][4 * q + 3] = acc[nt][4 * q + 3] + b[3];
+            }
+        float m = -3.0e38f;
+#pragma unroll
+        for (int nt = 0; nt < CT_NT; ++nt)
+#pragma unroll
+            for (int j = 0; j < 16; j += 2) m = __builtin_fmaxf(__builtin_fmaxf(m, acc[nt][j]), acc[nt][j + 1]);
+        tm = __builtin_fmaxf(m, __shfl_xor(m, 32));
+        float s = 0.f;
+#pragma unroll
+        for (int nt = 0; nt < CT_NT; ++nt)
+#pragma unroll
+            for (int j = 0; j < 16; ++j) s += __builtin_amdgcn_exp2f((acc[nt][j] - tm) * LOG2E);
+        ts = s + __shfl_xor(s, 32);
+    };
+    // the running state.  Only a tile whose maximum is strictly above the running one changes the class (an equal one loses to the
+    // earlier tile): then the index is the lowest class that holds the maximum, in this lane or its partner (both take this branch
+    // together: they hold the same row)
+    auto update = [&](const f32x16_t (&acc)[CT_NT], int t, float tm, float ts) {
+        if (tm > run_m) {
+            int ti = CT_BN;
+#pragma unroll
+            for (int nt = CT_NT - 1; nt >= 0; --nt)
+#pragma unroll
+                for (int j = 15; j >= 0; --j)
+                    if (acc[nt][j] == tm) ti = nt * 32 + (j & 3) + 8 * (j >> 2) + 4 * h;
+            ti = min(ti, __shfl_xor(ti, 32));
+            run_s = run_s * __builtin_amdgcn_exp2f((run_m - tm) * LOG2E) + ts;
+            run_m = tm;
+            run_i = t * CT_BN + ti;
+        } else {
+            run_s += ts * __builtin_amdgcn_exp2f((tm - run_m) * LOG2E);
+        }
+    };
+    // MFMAs of tile t into accc, beside them the vector work of tile t - 1 on acce; one barrier: after it buffer (t + 1) & 1 and
+    // bias slot (t + 1) & 3 are complete, and buffer t & 1 and slot (t - 1) & 3 are free for the requests of step t + 1
+    auto step = [&](f32x16_t (&accc)[CT_NT], f32x16_t (&acce)[CT_NT], int t) {
+        float tm, ts;
+        mma(accc, t);
+        tile_sum(acce, t - 1, tm, ts);
+        update(acce, t - 1, tm, ts);
+        landed(t + 1);
+    };
+
+    stage(0, 0);
+    landed(0);
+    f32x16_t acc0[CT_NT], acc1[CT_NT];
+    mma(acc0, 0);            // prologue: tile 0 has no epilogue beside it
+    landed(1);
+    int t = 1;
+    for (; t + 1 < p.ntiles; t += 2) {
+        step(acc1, acc0, t);
+        step(acc0, acc1, t + 1);
+    }
+    float tm, ts;
+    if (t < p.ntiles) {      // an even number of tiles: one more step, then drain acc1
+        step(acc1, acc0, t);
+        tile_sum(acc1, t, tm, ts);
+        update(acc1, t, tm, ts);
+    } else {                 // drain acc0
+        tile_sum(acc0, last, tm, ts);
+        update(acc0, last, tm, ts);
     }
     if (h == 0) {
-#pragma unroll
-        for (int mt = 0; mt < CT_MT; ++mt) {
-            const int row = row0 + wave * (32 * CT_MT) + mt * 32 + r;
-            if (row < p.M) { p.out_idx[row] = run_i[mt]; p.out_prob[row] = 1.f / run_s[mt]; }
-        }
+        const int row = row0 + wave * 32 + r;
+        if (row < p.M) { p.out_idx[row] = run_i; p.out_prob[row] = 1.f / run_s; }
     }
 }
 
@@ -567,13 +619,13 @@ void pack_ctc_weights(const bf16_t* w, int C, int K, bf16_t* out) {
 }
 
 hipError_t ctc_fc_argmax_launch(const CtcFcParams& p, hipStream_t st) {
-    if (p.K % 16 != 0 || p.K > CT_KMAX) return hipErrorInvalidValue;
-    const size_t lds = (size_t)(p.K / 8) * (CT_PLANE_A + CT_BN) * 16;
+    if (p.K != CT_K || p.ntiles < 1 || p.M < 1) return hipErrorInvalidValue;   // the kernel is built for the recognisers' K = 192
+    const size_t lds = CT_LDS;
     if (p.f16) {
-        { hipError_t e = locr_dyn_lds(reinterpret_cast<const void*>(ctc_fc_argmax_kernel<1>), 160 * 1024); if (e != hipSuccess) return e; }
+        { hipError_t e = locr_dyn_lds(reinterpret_cast<const void*>(ctc_fc_argmax_kernel<1>), (int)CT_LDS); if (e != hipSuccess) return e; }
         hipLaunchKernelGGL(ctc_fc_argmax_kernel<1>, dim3((p.M + CT_ROWS - 1) / CT_ROWS), dim3(256), lds, st, p);
     } else {
-        { hipError_t e = locr_dyn_lds(reinterpret_cast<const void*>(ctc_fc_argmax_kernel<0>), 160 * 1024); if (e != hipSuccess) return e; }
+        { hipError_t e = locr_dyn_lds(reinterpret_cast<const void*>(ctc_fc_argmax_kernel<0>), (int)CT_LDS); if (e != hipSuccess) return e; }
         hipLaunchKernelGGL(ctc_fc_argmax_kernel<0>, dim3((p.M + CT_ROWS - 1) / CT_ROWS), dim3(256), lds, st, p);
     }
     return hipGetLastError();
