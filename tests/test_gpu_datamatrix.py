@@ -12,17 +12,13 @@ from lumina_ocr.utils import datamatrix as dm
 
 import dm_reference as R
 import table_reference as tr
+from dm_pages import H, W, blank, corrupted, payload, put
 
 pytestmark = pytest.mark.gpu
 
 P = arch.DM_PARAMS
-H, W = 200, 243
 KEYS = ("min_module", "max_module", "quiet", "timing_max", "solid_max", "max_candidates")
 ORDER = ("threshold", "min_module", "max_module", "quiet", "timing_max", "solid_max", "max_candidates", "max_codes")
-
-
-def blank(h: int = H, w: int = W) -> np.ndarray:
-    return np.full((h, w, 3), 255, np.uint8)
 
 
 def check(engine, pages: np.ndarray, **params):
@@ -49,25 +45,6 @@ def check(engine, pages: np.ndarray, **params):
 def found(rc, rd):
     """-> {(x0, y0, x1, y1): text}"""
     return {tuple(int(v) for v in c[:4]): t for c, t in zip(rc, R.texts(rc, rd))}
-
-
-def put(page, x, y, text, size, module=3, rotation=0, scheme="ascii", sym=None):
-    return synth.draw_dm(page, x, y, synth.dm_encode(text, size, scheme) if sym is None else sym, module, rotation)
-
-
-def payload(size: int, tag: str = "") -> str:
-    """A text that fills most of the size in ASCII (digits pair up, so the tail is letters)."""
-    return (tag + "S%d " % size + "data matrix / " * 20)[:max(1, dm.SIZES[size][2] - 1)]
-
-
-def corrupted(text, size, wrong):
-    """The symbol with `wrong` codewords of every block destroyed."""
-    cw = synth.dm_interleave(synth.dm_data_codewords(text, size), size)
-    nb = dm.SIZES[size][6]
-    for b in range(nb):
-        for i in range(wrong):
-            cw[(2 * i + 1) * nb + b] ^= (0xFF, 0x5A, 0x01, 0x80)[i % 4]
-    return synth.dm_matrix(cw, size)
 
 
 def test_empty_page_and_every_size_reads(engine):
