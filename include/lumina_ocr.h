@@ -392,7 +392,8 @@ int lumina_ocr_datamatrix(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int 
  * max_codes is not written); finder_counts_dev: optional, int32 [n] = the finders of each page.  mask_in_dev / mask_out_dev as in
  * lumina_ocr_barcodes.  1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= centre_tol <= 64, 0 <= ring_tol <= 15,
  * 0 <= mark_max <= 64, max_finders 1..64, max_codes 1..64, sides 1..65535; defaults in lumina_ocr/arch.py AZTEC_PARAMS.  Not read:
- * full-range symbols of 12-32 layers, runes, light-on-dark and mirrored symbols, perspective, a bullseye that other ink touches.
+ * full-range symbols of 12-32 layers (lumina_ocr_aztec_layers below reads them), runes, light-on-dark and mirrored symbols,
+ * perspective, a bullseye that other ink touches.
  * Integer arithmetic throughout: the result is defined bit for bit (tests/aztec_reference.py).  Asynchronous; n == 0 is a no-op; bad
  * arguments return a status before anything is written.  lumina_ocr_aztec_workspace_bytes: the workspace n pages of that size need
  * in one launch (0: bad arguments); the entry itself splits n into groups that fit the handle's workspace. */
@@ -400,6 +401,29 @@ size_t lumina_ocr_aztec_workspace_bytes(int n, int height, int width, int max_fi
 int lumina_ocr_aztec(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module, int max_module,
                      int quiet, int centre_tol, int ring_tol, int mark_max, int max_finders, int max_codes, int32_t* codes_dev, int32_t* data_dev,
                      int32_t* counts_dev, int32_t* finder_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream);
+
+/* lumina_ocr_aztec_layers: lumina_ocr_aztec for full-range symbols of every size, up to max_layers (11 .. 32) layers and 151 modules a
+ * side.  Stage 1 is lumina_ocr_aztec itself: every symbol it reads is in this list with the same 12 ints and the same data codewords
+ * (max_layers = 11 gives exactly its list).  A full-range finder whose mode message says 12 .. max_layers layers, and that stage 1
+ * gave no row for, goes to stage 2, one wave per finder.  Its frame is finer: the ring's centre, a slope t / 1024 and a pitch of
+ * (1024 + k) / 1024 of the ring's tenth.  From the bullseye's frame it is refined outwards along the centre reference lines, at the
+ * radii 16, 32, 64 modules and the symbol's half side with steps of 8, 4, 2, 1: of the 9 x 9 neighbouring frames the middle of those
+ * with the fewest mismatches a quarter module round the lines' module centres is kept.  It is finished on the outline: of the 9 x 9
+ * nearest frames with no ink a quarter module outside it and some ink a quarter module inside it, the one with the fewest mismatches
+ * on the centre lines, then the nearest.  The `quiet` rings must be clear; module rows are three 64-bit words; the codewords are 10
+ * bits over GF(1024) up to 22 layers and 12 bits over GF(4096) / 0x1069 from 23 layers; the hull is the box of the outline's corners,
+ * each at its nearest pixel.
+ * codes_dev and counts_dev as lumina_ocr_aztec, both stages' rows sorted together; data_dev uint16 [n][max_codes][1664], zero behind
+ * ndata.  The parameters' ranges as lumina_ocr_aztec, and 11 <= max_layers <= 32; a finder whose mode message says more layers than
+ * max_layers is dropped.  Not read: runes, light-on-dark and mirrored symbols, perspective, a bullseye that other ink touches.
+ * Integer arithmetic throughout: the result is defined bit for bit (tests/aztec_layers_reference.py).  Asynchronous; n == 0 is a
+ * no-op; bad arguments return a status before anything is written.  lumina_ocr_aztec_layers_workspace_bytes as
+ * lumina_ocr_aztec_workspace_bytes. */
+size_t lumina_ocr_aztec_layers_workspace_bytes(int n, int height, int width, int max_finders, int max_codes);
+int lumina_ocr_aztec_layers(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module, int max_module,
+                            int quiet, int centre_tol, int ring_tol, int mark_max, int max_finders, int max_codes, int max_layers, int32_t* codes_dev,
+                            uint16_t* data_dev, int32_t* counts_dev, int32_t* finder_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev,
+                            void* stream);
 
 /* ---- page orientation (optional; DESIGN.md: "Page orientation") ----
  * A page is upright after `turn` quarter turns: upright = np.rot90(page, turn) (counter-clockwise).  The three entries below are the

@@ -25,6 +25,7 @@ struct AztecParams {
     const unsigned long long* mask_in;   // optional: the ink mask of these pages at this threshold, already computed
 };
 constexpr int AZ_MAX_DATA = 320;      // >= 316, the codewords of 11 layers
+constexpr int AZ_MAX_DATA_ALL = 1664;  // the codewords of 32 layers (lumina_ocr_aztec_layers)
 constexpr int AZ_MAX_FINDERS = 64;
 constexpr int AZ_MAX_CODES = 64;
 constexpr int AZ_MAX_MODULE = 64;
@@ -35,3 +36,14 @@ constexpr int AZ_MAX_MARKS = 64;
 bool aztec_params_ok(int min_module, int max_module, int quiet, int centre_tol, int ring_tol, int mark_max, int max_finders, int max_codes);
 size_t aztec_workspace_bytes(int B, int H, int W, int max_finders, int max_codes);
 hipError_t aztec_launch(const AztecParams& p, void* workspace, size_t ws_bytes, hipStream_t st);
+
+// full-range symbols of every size, 1-32 layers (definition restated in tests/aztec_layers_reference.py): stage 1 is the pass above and
+// gives its rows bit for bit; a full-range finder whose mode message says 12 .. max_layers layers and that gave no row is read by a
+// second stage with a finer frame and three-word module rows.  p.data is not used: the data rows are data_all.
+struct AztecLayersParams : AztecParams {
+    int max_layers;             // 11 .. 32; 11 is stage 1 alone
+    unsigned short* data_all;   // device, [B][max_codes][AZ_MAX_DATA_ALL]: the corrected data codewords, zero behind ndata
+};
+bool aztec_max_layers_ok(int max_layers);
+size_t aztec_layers_workspace_bytes(int B, int H, int W, int max_finders, int max_codes);
+hipError_t aztec_layers_launch(const AztecLayersParams& p, void* workspace, size_t ws_bytes, hipStream_t st);

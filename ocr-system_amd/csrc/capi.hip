@@ -896,6 +896,38 @@ int lumina_ocr_aztec(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int heigh
     API_CATCH(h)
 }
 
+size_t lumina_ocr_aztec_layers_workspace_bytes(int n, int height, int width, int max_finders, int max_codes) {
+    return n > 0 ? aztec_layers_workspace_bytes(n, height, width, max_finders, max_codes) : 0;
+}
+
+int lumina_ocr_aztec_layers(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module, int max_module, int quiet,
+                            int centre_tol, int ring_tol, int mark_max, int max_finders, int max_codes, int max_layers, int32_t* codes_dev, uint16_t* data_dev,
+                            int32_t* counts_dev, int32_t* finder_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream) {
+    if (!h) return 1;
+    if (n == 0) return 0;
+    if (!pages_dev || !codes_dev || !data_dev || !counts_dev || n < 0) return locr_fail(h, "aztec_layers", "bad arguments");
+    if (!aztec_params_ok(min_module, max_module, quiet, centre_tol, ring_tol, mark_max, max_finders, max_codes) || !aztec_max_layers_ok(max_layers))
+        return locr_fail(h, "aztec_layers", "parameters must satisfy 1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= centre_tol <= 64, "
+                                            "0 <= ring_tol <= 15, 0 <= mark_max <= 64, max_finders 1..64, max_codes 1..64, max_layers 11..32");
+    if (aztec_layers_workspace_bytes(1, height, width, max_finders, max_codes) == 0) return locr_fail(h, "aztec_layers", "bad dimensions (sides 1..65535)");
+    BIND(h);
+    API_TRY
+    const auto ws = [&](int nb) { return aztec_layers_workspace_bytes(nb, height, width, max_finders, max_codes); };
+    const size_t nw = ((size_t)width + 63) / 64;
+    return for_page_groups(h, n, fit_group(h->post_group, n, ws), ws, [&](int b0, int nb) {
+        AztecLayersParams p{};
+        p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.H = height; p.W = width;
+        p.threshold = threshold; p.min_module = min_module; p.max_module = max_module; p.quiet = quiet; p.centre_tol = centre_tol; p.ring_tol = ring_tol;
+        p.mark_max = mark_max; p.max_finders = max_finders; p.max_codes = max_codes; p.max_layers = max_layers;
+        p.codes = codes_dev + (size_t)b0 * max_codes * 12; p.data_all = data_dev + (size_t)b0 * max_codes * AZ_MAX_DATA_ALL; p.counts = counts_dev + b0;
+        p.finder_counts = finder_counts_dev ? finder_counts_dev + b0 : nullptr;
+        p.mask_in = mask_in_dev ? reinterpret_cast<const unsigned long long*>(mask_in_dev) + (size_t)b0 * height * nw : nullptr;
+        p.mask_out = mask_out_dev ? reinterpret_cast<unsigned long long*>(mask_out_dev) + (size_t)b0 * height * nw : nullptr;
+        return hip_rc(h, "aztec_layers", aztec_layers_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
+    });
+    API_CATCH(h)
+}
+
 size_t lumina_ocr_page_quarter_workspace_bytes(int n, int height, int width) { return n > 0 ? quarter_workspace_bytes(n, height, width) : 0; }
 
 int lumina_ocr_page_quarter(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int ratio, int64_t* energies_dev,

@@ -101,12 +101,14 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_qrcodes_versions": (i32, [vp, vp, i32, i32, i32] + [i32] * 10 + [vp] * 7),
         "lumina_ocr_datamatrix": (i32, [vp, vp, i32, i32, i32] + [i32] * 8 + [vp] * 7),
         "lumina_ocr_aztec": (i32, [vp, vp, i32, i32, i32] + [i32] * 9 + [vp] * 7),
+        "lumina_ocr_aztec_layers": (i32, [vp, vp, i32, i32, i32] + [i32] * 10 + [vp] * 7),
         "lumina_ocr_rules_and_marks": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_selection_marks_round": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_rules_and_marks_round": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp,
                                                    i32, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_page_quarter_workspace_bytes": (sz, [i32, i32, i32]),
         "lumina_ocr_aztec_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+        "lumina_ocr_aztec_layers_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
         "lumina_ocr_page_quarter": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_page_turn": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp]),
         "lumina_ocr_page_vote": (i32, [vp, vp, vp, i32, i32, vp, vp]),
@@ -135,7 +137,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_png_probe", "lumina_ocr_png_decode", "lumina_ocr_flate_image_decode", "lumina_ocr_ccitt_decode", "lumina_ocr_fax_decode", "lumina_ocr_strip_image_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
     "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks", "lumina_ocr_selection_marks_round",
-    "lumina_ocr_rules_and_marks_round", "lumina_ocr_barcodes", "lumina_ocr_barcodes_kinds", "lumina_ocr_qrcodes", "lumina_ocr_qrcodes_versions", "lumina_ocr_datamatrix", "lumina_ocr_aztec", "lumina_ocr_aztec_workspace_bytes",
+    "lumina_ocr_rules_and_marks_round", "lumina_ocr_barcodes", "lumina_ocr_barcodes_kinds", "lumina_ocr_qrcodes", "lumina_ocr_qrcodes_versions", "lumina_ocr_datamatrix", "lumina_ocr_aztec", "lumina_ocr_aztec_workspace_bytes", "lumina_ocr_aztec_layers", "lumina_ocr_aztec_layers_workspace_bytes",
     "lumina_ocr_page_quarter_workspace_bytes", "lumina_ocr_page_quarter", "lumina_ocr_page_turn", "lumina_ocr_page_vote",
 ]
 
@@ -751,7 +753,7 @@ class Engine:
                                                  _ptr(mask), self._stream()))
         return (codes, data, counts, mask, cands) if debug else (codes, data, counts)
 
-    # -- Aztec (compact 1-4 layers, full-range 1-11 layers; the host half is utils/aztec.py) ----------------------------------------------
+    # -- Aztec (aztec: compact 1-4 layers, full-range 1-11 layers; aztec_layers: full-range up to 32; the host half is utils/aztec.py) ----------------------------------------------
     _AZTEC_KEYS = ("threshold", "min_module", "max_module", "quiet", "centre_tol", "ring_tol", "mark_max", "max_finders", "max_codes")
 
     def aztec(self, pages, mask_in=None, debug: bool = False, **params):
@@ -778,6 +780,30 @@ class Engine:
         finders = torch.zeros((n,), dtype=torch.int32, device=pages.device) if debug else None
         self._chk(self.lib.lumina_ocr_aztec(self._h, _ptr(pages), n, h, w, *q, _ptr(codes), _ptr(data), _ptr(counts), _ptr(finders), _ptr(mask_in),
                                             _ptr(mask), self._stream()))
+        return (codes, data, counts, mask, finders) if debug else (codes, data, counts)
+
+    def aztec_layers(self, pages, max_layers: int, mask_in=None, debug: bool = False, **params):
+        """aztec for full-range symbols of up to max_layers (11..32) layers: uint8 [n,H,W,3] device -> (codes int32 [n,max_codes,12], data
+        uint16 [n,max_codes,1664], counts int32 [n]).  Every symbol aztec reads comes with the same row and codewords; a full-range finder
+        of 12 .. max_layers layers that gave no such row goes through the second stage (lumina_ocr_aztec_layers).  params, mask_in and
+        debug as in aztec."""
+        torch = _torch()
+        n, h, w, c = pages.shape
+        assert c == 3 and pages.dtype == torch.uint8 and pages.is_contiguous()
+        unknown = set(params) - set(self._AZTEC_KEYS)
+        if unknown:
+            raise TypeError("aztec_layers: unknown parameters %s" % sorted(unknown))
+        q = [int(params[k]) if params.get(k) is not None else arch.AZTEC_PARAMS[k] for k in self._AZTEC_KEYS]
+        max_codes = q[-1]
+        if mask_in is not None:
+            assert mask_in.dtype == torch.int64 and mask_in.is_contiguous() and tuple(mask_in.shape) == (n, h, (w + 63) // 64)
+        codes = torch.zeros((n, max(max_codes, 0), 12), dtype=torch.int32, device=pages.device)
+        data = torch.zeros((n, max(max_codes, 0), 1664), dtype=torch.int16, device=pages.device).view(torch.uint16)
+        counts = torch.zeros((n,), dtype=torch.int32, device=pages.device)
+        mask = torch.zeros((n, h, (w + 63) // 64), dtype=torch.int64, device=pages.device) if debug else None
+        finders = torch.zeros((n,), dtype=torch.int32, device=pages.device) if debug else None
+        self._chk(self.lib.lumina_ocr_aztec_layers(self._h, _ptr(pages), n, h, w, *q, int(max_layers), _ptr(codes), _ptr(data), _ptr(counts),
+                                                   _ptr(finders), _ptr(mask_in), _ptr(mask), self._stream()))
         return (codes, data, counts, mask, finders) if debug else (codes, data, counts)
 
     def rules_and_marks(self, pages, threshold=None, gap=None, min_len=None, max_thick=None, max_rules=None, min_side=None, max_side=None,

@@ -50,7 +50,8 @@ class PageDetections:
     dm_data: Optional[np.ndarray] = None      # int32 [m, 208] their corrected data codewords (utils/datamatrix.py turns them into text)
     aztec: Optional[np.ndarray] = None        # int32 [m, 12] x0, y0, x1, y1, layers, compact, codeword width, ndata, errors, rotation, mode errors,
                                               # mismatches of the page's Aztec symbols: OcrPipeline(aztec=True) only (empty on overflow)
-    az_data: Optional[np.ndarray] = None      # int32 [m, 320] their corrected data codewords (utils/aztec.py turns them into text)
+    az_data: Optional[np.ndarray] = None      # int32 [m, 320] their corrected data codewords (utils/aztec.py turns them into text);
+                                              # uint16 [m, 1664] with OcrPipeline(aztec_max_layers > 11)
     word_quads: Optional[np.ndarray] = None   # int32 [n, 40, 8] the words of every line from the CTC alignment, each in its line's corner
                                               # order: OcrPipeline(word_boxes=True) only, like the three below
     word_spans: Optional[np.ndarray] = None   # int32 [n, 40, 2] first character in texts[i], character count
@@ -99,7 +100,8 @@ class OcrPipeline:
                  page_orient: bool = False, page_orient_params: Optional[dict] = None, word_boxes: bool = False, round_marks: bool = False,
                  round_mark_params: Optional[dict] = None, barcodes: bool = False, barcode_params: Optional[dict] = None,
                  qrcodes: bool = False, qr_params: Optional[dict] = None, qr_max_version: int = 10, barcode_kinds=arch.BARCODE_KINDS_DEFAULT,
-                 datamatrix: bool = False, dm_params: Optional[dict] = None, aztec: bool = False, aztec_params: Optional[dict] = None):
+                 datamatrix: bool = False, dm_params: Optional[dict] = None, aztec: bool = False, aztec_params: Optional[dict] = None,
+                 aztec_max_layers: int = 11):
         """recognizer: "crnn" (CRNN-MobileNetV3 + BiLSTM, engine.load_rec) or "svtr" (SVTR, engine.load_svtr).
         angle_cls: PaddleOCR's use_angle_cls — every line is classified 0 / 180 degrees (engine.load_cls) before recognition, and a line
         read as 180 with probability > cls_thresh is recognised turned; boxes and reading order are unchanged.  Per-line labels are
@@ -126,6 +128,8 @@ class OcrPipeline:
         aztec: the Aztec symbols (compact 1-4 layers, full-range 1-11 layers) of the processed pages (engine.aztec, parameters
         arch.AZTEC_PARAMS or aztec_params; an unknown key is a ValueError) come back as PageDetections.aztec / az_data; the pass runs behind
         the Data Matrix pass and takes the ink mask an earlier pass made at its threshold; with a gather it is not run.
+        aztec_max_layers (11..32): above 11 the pass is engine.aztec_layers, which reads full-range symbols of 12 .. aztec_max_layers
+        layers as well; az_data is then uint16 [m, 1664].
         page_orient: run_oriented() finds for every page the quarter turns that make it upright (ink profiles for sideways pages,
         parameters arch.PAGE_ORIENT_PARAMS or page_orient_params; the line classifier's majority for upside-down ones, so it needs
         engine.load_cls like angle_cls), turns the raw page on the device and runs the stages below on the upright page.  run /
@@ -170,6 +174,9 @@ class OcrPipeline:
         self.aztec_params = dict(arch.AZTEC_PARAMS if aztec_params is None else aztec_params)
         if set(self.aztec_params) - set(arch.AZTEC_PARAMS):
             raise ValueError("aztec_params: unknown keys %s" % sorted(set(self.aztec_params) - set(arch.AZTEC_PARAMS)))
+        self.aztec_max_layers = int(aztec_max_layers)
+        if not 11 <= self.aztec_max_layers <= 32:
+            raise ValueError("aztec_max_layers must be 11..32, not %r" % (aztec_max_layers,))
         self.page_orient = bool(page_orient)
         self.word_boxes = bool(word_boxes)
         self.space_id = self.charset.index(" ") if " " in self.charset else -1   # the class words split on (-1: a line is one word)
@@ -229,7 +236,9 @@ class OcrPipeline:
         handed = []
         out = self._submit_passes(processed, handed)
         mask = handed[0][0] if handed and handed[0][1] == ap["threshold"] else None
-        return out + (self.eng.aztec(processed, mask_in=mask, **ap),)
+        if self.aztec_max_layers == 11:
+            return out + (self.eng.aztec(processed, mask_in=mask, **ap),)
+        return out + (self.eng.aztec_layers(processed, self.aztec_max_layers, mask_in=mask, **ap),)
 
     def _submit_passes(self, processed, handed: Optional[list] = None):
         """Enqueue the table rules, selection marks, barcodes, QR codes and Data Matrix symbols of the processed pages -> (rules, marks,
@@ -482,7 +491,7 @@ class OcrPipeline:
     def _page_barcodes(self, pend: "_Pending", qr: bool = False, dm: bool = False, az: bool = False):
         """-> per page (codes [m,8], symbol values [m,64]) from the pending batch's host copies, or (None, None) without barcodes.  A
         page whose true count exceeds the capacity has no rows: it is treated as having no barcodes.  qr: the same of the QR pass's
-        copies, (codes [m,12], data codewords [m,288], or bytes [m,2956] above qr_max_version 10); dm: of the Data Matrix pass's, (codes [m,12], data codewords [m,208]); az: of the Aztec pass's, (codes [m,12], data codewords [m,320])."""
+        copies, (codes [m,12], data codewords [m,288], or bytes [m,2956] above qr_max_version 10); dm: of the Data Matrix pass's, (codes [m,12], data codewords [m,208]); az: of the Aztec pass's, (codes [m,12], data codewords [m,320], or uint16 [m,1664] above aztec_max_layers 11)."""
         host = pend.aztec_host if az else pend.datamatrix_host if dm else pend.qrcodes_host if qr else pend.barcodes_host
         if host is None:
             return [(None, None)] * pend.b

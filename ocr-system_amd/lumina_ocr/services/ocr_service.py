@@ -171,6 +171,9 @@ class OCRService:
         # decoded content and a `:barcode: <content>` line of the Markdown, behind the 1-D, QR and Data Matrix codes of the page; the text
         # lines the detector found inside a symbol are dropped.  Off by default: every output is then the one without it.
         self._use_aztec = os.environ.get("LUMINA_OCR_AZTEC", "0").lower() not in ("", "0", "false", "no")
+        # LUMINA_OCR_AZTEC_MAX_LAYERS=11..32 (with LUMINA_OCR_AZTEC=1; default 11: the pass above and nothing else): full-range symbols of up
+        # to that many layers are read as well (lumina_ocr_aztec_layers).  Checked when the engine starts: another value is an error result.
+        self._aztec_max_layers = os.environ.get("LUMINA_OCR_AZTEC_MAX_LAYERS", "") or "11"
         # LUMINA_OCR_PAGE_ORIENTATION=1: pages lying sideways or upside-down are turned upright on the device before anything else reads
         # them (after decode and EXIF orientation, before the resize), and json_output reports page_rotation.  It uses the classifier
         # (LUMINA_OCR_CLS_WEIGHTS) whether or not LUMINA_OCR_USE_ANGLE_CLS is set.  Off by default: every output is then the one without it.
@@ -215,6 +218,11 @@ class OCRService:
                 if not (self._qr_max_version.strip().isdigit() and 10 <= int(self._qr_max_version) <= 40):
                     raise RuntimeError("LUMINA_OCR_QR_MAX_VERSION: %r is not a version 10..40" % self._qr_max_version)
                 qr_max_version = int(self._qr_max_version)
+            aztec_max_layers = 11
+            if self._use_aztec:
+                if not (self._aztec_max_layers.strip().isdigit() and 11 <= int(self._aztec_max_layers) <= 32):
+                    raise RuntimeError("LUMINA_OCR_AZTEC_MAX_LAYERS: %r is not a number of layers 11..32" % self._aztec_max_layers)
+                aztec_max_layers = int(self._aztec_max_layers)
             if self._use_barcodes:
                 try:
                     arch.barcode_kinds_mask(self._barcode_kinds)
@@ -256,7 +264,7 @@ class OCRService:
                                            angle_cls=self._use_angle_cls, tables=self._use_tables, marks=self._use_marks,
                                            page_orient=self._use_page_orient, word_boxes=self._use_word_boxes, round_marks=self._use_round_marks,
                                            barcodes=self._use_barcodes, qrcodes=self._use_qrcodes, qr_max_version=qr_max_version, datamatrix=self._use_datamatrix, aztec=self._use_aztec,
-                                           barcode_kinds=self._barcode_kinds if self._use_barcodes else arch.BARCODE_KINDS_DEFAULT)
+                                           aztec_max_layers=aztec_max_layers, barcode_kinds=self._barcode_kinds if self._use_barcodes else arch.BARCODE_KINDS_DEFAULT)
             except Exception:
                 eng.close()
                 raise
@@ -272,6 +280,13 @@ class OCRService:
             return None
         text = self._qr_max_version.strip()
         return int(text) if text.isdigit() and 10 <= int(text) <= 40 else self._qr_max_version
+
+    def _aztec_max_layers_status(self):
+        """The most layers of a full-range Aztec symbol the provider reads (None with Aztec off; the variable's text when it is no number 11..32)."""
+        if not self._use_aztec:
+            return None
+        text = self._aztec_max_layers.strip()
+        return int(text) if text.isdigit() and 11 <= int(text) <= 32 else self._aztec_max_layers
 
     def _barcode_kinds_names(self):
         """The kinds the provider reads, by name ([] with barcodes off; the variable's text when it names an unknown kind)."""
@@ -361,7 +376,7 @@ class OCRService:
         if getattr(det, "datamatrix", None) is not None:   # LUMINA_OCR_DATAMATRIX=1: and of a Data Matrix symbol
             matrices = dm_layout.read_datamatrix(det.datamatrix, det.dm_data)
         if getattr(det, "aztec", None) is not None:   # LUMINA_OCR_AZTEC=1: and of an Aztec symbol
-            aztecs = aztec_layout.read_aztec(det.aztec, det.az_data)
+            aztecs = aztec_layout.read_aztec(det.aztec, det.az_data, max_layers=self._pipeline.aztec_max_layers if self._pipeline is not None else 11)
         if strips is not None or squares is not None or matrices is not None or aztecs is not None:
             codes = (strips or []) + (squares or []) + (matrices or []) + (aztecs or [])
             keep = [i for i, t in enumerate(triples) if not barcode_layout.inside_any(t[0], codes)]
@@ -972,7 +987,7 @@ class OCRService:
     # ---- status (:759-795) ----
     def get_status(self) -> Dict[str, Any]:
         st = {"client_initialized": self._pipeline is not None, "model_id": "dbnet-r18vd+crnn-mv3", "max_dimension": self.max_dimension,
-              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "aztec": self._use_aztec, "device_pdf": self.device_pdf, "device_tiff": self.device_tiff, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
+              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "aztec": self._use_aztec, "aztec_max_layers": self._aztec_max_layers_status(), "device_pdf": self.device_pdf, "device_tiff": self.device_tiff, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
         if self._engine is not None:
             st["engine_version"] = self._engine.version()
             st["num_classes"] = self._engine.num_classes

@@ -8,8 +8,13 @@ was at hand.  What can be pinned structurally is pinned by tests/test_aztec_tabl
 and capacity formulas tabulate, the placement visits every data module exactly once and no function module, the mode bits are
 distinct and on their ring.  csrc/aztec_tables.h holds the fields for the device (device_header() writes it; the test compares).
 
+Full-range symbols of 12 .. 32 layers (ALL_SYMBOLS, MAX_DATA_ALL; lumina_ocr_aztec_layers reads them, read_aztec takes their rows with
+max_layers above 11) go through the same formulas.  From recollection as well, and pinned only structurally by
+tests/test_aztec_layers_tables.py: the polynomial 0x1069 of GF(4096), the 12-bit codewords from 23 layers on, and the reference grid's
+lines every 16 modules from the centre.  csrc/aztec_tables12.h holds GF(4096) for the device (device_header12()).
+
 Coordinates: a module is (x, y), x to the right, y down, in the upright symbol; the centre module is (c, c), c = size // 2.  A row of
-modules is one 64-bit word, bit x."""
+modules is one 64-bit word, bit x, up to 11 layers and three words above."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
@@ -34,7 +39,8 @@ def gf_tables(m: int) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
     return tuple(exp), tuple(log)
 
 
-_TABLES = {m: gf_tables(m) for m in (4, 6, 8, 10)}
+_TABLES = {m: gf_tables(m) for m in (4, 6, 8, 10, 12)}
+_NP_TABLES = {m: (np.array(e, np.int64), np.array(l, np.int64)) for m, (e, l) in _TABLES.items()}
 
 
 def gf_mul(m: int, a: int, b: int) -> int:
@@ -44,21 +50,29 @@ def gf_mul(m: int, a: int, b: int) -> int:
 
 def rs_check_words(data: Sequence[int], ec: int, m: int) -> List[int]:
     """The ec check words of data over GF(2^m), generator (x - a^1) ... (x - a^ec), the first word the highest power."""
-    exp, _ = _TABLES[m]
-    gen = [1]
+    exp, log = _NP_TABLES[m]
+    gen = np.zeros(ec + 1, np.int64)    # gen[j]: the coefficient j places below the leading one, which is gen[0] = 1
+    gen[0] = 1
     for i in range(1, ec + 1):
-        gen = [a ^ gf_mul(m, b, exp[i]) for a, b in zip(gen + [0], [0] + gen)]
-    rem = [0] * ec
+        low = gen[:i]
+        gen[1:i + 1] ^= np.where(low != 0, exp[log[low] + i], 0)
+    tail, tail_log = gen[1:], log[gen[1:]]
+    rem = np.zeros(ec + 1, np.int64)    # (one spare word behind, always zero)
     for d in data:
-        f = d ^ rem[0]
-        rem = [r ^ gf_mul(m, f, g) for r, g in zip(rem[1:] + [0], gen[1:])]
-    return rem
+        f = int(d) ^ int(rem[0])
+        rem[:ec] = rem[1:]
+        if f:
+            rem[:ec] ^= np.where(tail != 0, exp[tail_log + int(log[f])], 0)
+    return [int(v) for v in rem[:ec]]
 
 
 # ---- sizes ----
 MAX_COMPACT_LAYERS, MAX_FULL_LAYERS = 4, 11     # in scope: rows of at most 61 modules
 SYMBOLS = tuple((True, L) for L in range(1, 5)) + tuple((False, L) for L in range(1, 12))
 MAX_DATA = 320                                  # ints a device data row holds (>= 316, the codewords of 11 layers)
+MAX_LAYERS_ALL = 32                             # lumina_ocr_aztec_layers: full-range symbols of every size, rows of up to 151 modules
+ALL_SYMBOLS = SYMBOLS + tuple((False, L) for L in range(12, 33))
+MAX_DATA_ALL = 1664                             # uint16 words a device data row of lumina_ocr_aztec_layers holds: the codewords of 32 layers
 
 
 def word_width(layers: int) -> int:
@@ -451,15 +465,16 @@ def confidence(ec: int, errors: int) -> float:
     return max(0.0, 1.0 - errors / float(max(1, ec // 2)))
 
 
-def read_aztec(codes, data) -> List[dict]:
-    """Device rows int32 [m,12] + data codewords [m,MAX_DATA] -> one dict a symbol, in the rows' order: kind "Aztec", content, confidence,
+def read_aztec(codes, data, max_layers: int = MAX_FULL_LAYERS) -> List[dict]:
+    """Device rows int32 [m,12] + data codewords [m,MAX_DATA] ([m,MAX_DATA_ALL] from lumina_ocr_aztec_layers, whose max_layers the caller
+    passes on: full-range rows above it are left out) -> one dict a symbol, in the rows' order: kind "Aztec", content, confidence,
     polygon (the hull's TL, TR, BR, BL as 8 floats), box, layers, compact, rotation, errors, `gs1`: True for a GS1 symbol, and
     `unsupported` with the reason where the content is out of scope (content is then "").  A row whose codewords are no valid
     message (a stuffed word of 0 or 2^w - 1) is left out."""
     out = []
     for c, d in zip(codes, data):
         x0, y0, x1, y1, layers, compact, w, ndata, errors, rotation = (int(v) for v in c[:10])
-        if not (1 <= layers <= (MAX_COMPACT_LAYERS if compact else MAX_FULL_LAYERS)) or w != word_width(layers):
+        if not (1 <= layers <= (MAX_COMPACT_LAYERS if compact else max(MAX_FULL_LAYERS, min(int(max_layers), MAX_LAYERS_ALL)))) or w != word_width(layers):
             continue
         total = total_words(bool(compact), layers)
         if not 1 <= ndata < total:
@@ -497,3 +512,14 @@ def device_header() -> str:
             "__device__ const unsigned short AZ_EXP[AZ_EXP_N] = {\n%s};\n"
             "__device__ const unsigned short AZ_LOG[AZ_LOG_N] = {\n%s};\n"
             % (len(exp), len(log), ", ".join(map(str, off_e)), ", ".join(map(str, off_l)), rows(exp, 24), rows(log, 24)))
+
+
+def device_header12() -> str:
+    """The text of csrc/aztec_tables12.h: the field of the 12-bit codewords (23 .. 32 layers)."""
+    rows = lambda v, per: ",\n".join("    " + ", ".join("%d" % x for x in v[i:i + per]) for i in range(0, len(v), per))
+    exp, log = _TABLES[12]
+    return ("#pragma once\n// Written by lumina_ocr.utils.aztec.device_header12(); tests/test_aztec_layers_tables.py compares.  The field of the Aztec\n"
+            "// symbols of 23 .. 32 layers: GF(4096) / 0x1069 as exp (doubled: 2 * 2^12 entries) and log tables.\n"
+            "constexpr int AZ12_EXP_N = %d, AZ12_LOG_N = %d;\n"
+            "__device__ const unsigned short AZ12_EXP[AZ12_EXP_N] = {\n%s};\n"
+            "__device__ const unsigned short AZ12_LOG[AZ12_LOG_N] = {\n%s};\n" % (len(exp), len(log), rows(exp, 24), rows(log, 24)))
