@@ -5,7 +5,13 @@
 //   enhance_sharpness :146-158 (blend with the 3x3 SMOOTH-filtered image, factor 1.1)
 // Coefficient tables are computed on the host in double precision with libm sin(), exactly like Pillow's
 // precompute_coeffs / normalize_coeffs_8bpc, and cached on the device per (in, out) size.
-// HBM-bound: 3 B/px read + 3 B/px written per pass.
+// Each pass reads 3 B/px and writes 3 B/px, but none of the tiled kernels was bound by those bytes (counters over 64 A4 pages,
+// profiles/preprocess_before_* / preprocess_after_*): the horizontal pass waited on LDS 36 % of its wave cycles (tap reads wider
+// than a word off their natural alignment are replayed), the vertical pass and enhance were bound by vector issue (177 and 311
+// vector instructions per output word, about a third of them fill_rows() addressing; a global load per output row in the vertical
+// loop), the gray sum by the latency of byte loads.  As they stand: the gray sum streams at 4.8 TB/s; the other three move
+// 2.5 - 3.1 TB/s and are bound by vector issue again, now mostly by the multiplies and float operations Pillow's arithmetic needs
+// (2 instructions per tap and byte in the resamplers; about 115 per output word in enhance).
 #include "resize.h"
 #include "lds_rows.h"
 
@@ -104,21 +110,61 @@ __global__ __launch_bounds__(256) void resample_v_kernel(const uint8_t* in, uint
     }
 }
 
+// fill_rows() for the tiles of this file.  A tile that lies wholly inside the tensor (all but the first and last few of a launch)
+// takes the lean loop: the row loop is workgroup-uniform and thread t owns words t, t + 256, ... of every row, so a word costs one
+// load and one ds_write at immediate offsets — no per-word division, range test or 64-bit address (those cost fill_rows() about 30
+// vector instructions a word, as much as the filters the tiles feed).  A tile that touches the tensor's first or last word goes
+// through fill_rows(), which patches partial words bytewise.  Rows outside [rlo, rhi) are left unwritten, as there.  BATCH loads
+// are in flight per thread before the first LDS write: a tile of BATCH rows is filled in one memory round trip.
+template <int BATCH, typename F>
+__device__ __forceinline__ void fill_tile(uint32_t* lds, int pitch, int nw, const uint8_t* img, long long g0, int row_stride, int nrows,
+                                          int rlo, int rhi, long long total, F f) {
+    if (rhi <= rlo) return;
+    const int m0 = (int)((reinterpret_cast<uintptr_t>(img) + (unsigned long long)g0) & 3);
+    const long long gal = g0 - m0;   // img + gal is 4-byte aligned
+    const long long first = gal + (((long long)m0 + (long long)rlo * row_stride) & ~3ll);
+    const long long last = gal + (((long long)m0 + (long long)(rhi - 1) * row_stride) & ~3ll) + 4ll * nw;
+    if (first < 0 || last > total) {
+        fill_rows(lds, pitch, nw, img, g0, row_stride, nrows, rlo, rhi, total, f);
+        return;
+    }
+    const uint8_t* pal = img + gal;
+    for (int k = (int)threadIdx.x; k < nw; k += (int)blockDim.x) {
+        for (int r0 = rlo; r0 < rhi; r0 += BATCH) {
+            uint32_t w[BATCH];
+#pragma unroll
+            for (int u = 0; u < BATCH; ++u) {   // all loads of a batch before the first LDS write; rows past rhi re-read the last row
+                const int r = min(r0 + u, rhi - 1);
+                w[u] = *reinterpret_cast<const uint32_t*>(pal + (((m0 + r * row_stride) & ~3) + 4 * k));
+            }
+#pragma unroll
+            for (int u = 0; u < BATCH; ++u)
+                if (r0 + u < rhi) lds[(r0 + u) * pitch + k] = f(w[u]);
+        }
+    }
+}
+
 // Horizontal pass, RGB fast path (<= HK <= HKMAX taps, segment <= HPXMAX input pixels): one workgroup = HR rows x HX output pixels, one
 // output pixel (of all HR rows) per thread.  The thread's tap coefficients are fetched up front into registers, the HR input
-// row segments go to LDS by fill_rows(), results are staged in LDS and leave as aligned 4-byte stores.
+// row segments go to LDS by fill_tile().  A pixel's 3 * HK tap bytes are contiguous in the staged row: they are read as ALIGNED
+// words (an LDS access wider than a word that is off its natural alignment is replayed at 64 clocks per wave instruction, which
+// is what bounded this kernel while it read the taps at their byte address) and shifted into place with v_alignbyte; the
+// multiplies select their byte in the instruction.  The four pixels of a lane quad are packed into three words with one DPP move
+// (one ds_write_b32 per quad lane instead of three byte writes), and the staged rows leave as aligned 4-byte stores.
 constexpr int HR = 8, HX = 256, HKMAX = 12, HPXMAX = 400;
 constexpr int HP_IN = (HPXMAX * 3 + 3) / 4 + 2 + HKMAX;   // LDS pitch (words) of an input row segment (+ slack for zero taps)
-constexpr int HP_OUT = (HX * 3 + 3) / 4 + 2;           // LDS pitch (words) of an output row segment
+constexpr int HP_OUT = HX * 3 / 4 + 4;                 // LDS pitch (words) of an output row segment: one word in front, slack behind
 template <int HK>
-__global__ __launch_bounds__(256) void resample_h_rgb_kernel(const uint8_t* in, uint8_t* out, const int* bounds, const int* kk, int ksize, int rows,
-                                                             int W, int Wo, long long total_in) {
+__global__ __launch_bounds__(256) void resample_h_rgb_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, const int* __restrict__ bounds,
+                                                             const int* __restrict__ kk, int ksize, int rows, int W, int Wo, long long total_in) {
+    constexpr int NA = (3 * HK + 3) / 4;   // aligned words that hold the 3 * HK tap bytes once shifted; NA + 1 are read
+    static_assert(3 + 3 * (HPXMAX - 1) + 4 * (NA + 1) <= 4 * HP_IN, "the tap window of the last pixel stays inside its LDS row");
     __shared__ uint32_t lin[HR * HP_IN];
     __shared__ uint32_t lout[HR * HP_OUT];
     const int tid = threadIdx.x;
     const int xo0 = blockIdx.x * HX, row0 = blockIdx.y * HR;
     const int nx = min(HX, Wo - xo0), nrows = min(HR, rows - row0);
-    const int xo = xo0 + min(tid, nx - 1);
+    const int xo = xo0 + min(tid, nx - 1);   // threads past the segment repeat its last pixel: every lane stays active for the DPP move
     const int lo = bounds[2 * xo];
     int kreg[HK];
 #pragma unroll
@@ -128,58 +174,72 @@ __global__ __launch_bounds__(256) void resample_h_rgb_kernel(const uint8_t* in, 
     const int rowb = W * 3;
     const long long g0 = (long long)row0 * rowb + (long long)in_lo * 3;
     const int nw = ((in_hi - in_lo) * 3 + 3 + 3) / 4;
-    fill_rows(lin, HP_IN, nw, in, g0, rowb, nrows, 0, nrows, total_in, WordIdentity());
+    fill_tile<HR>(lin, HP_IN, nw, in, g0, rowb, nrows, 0, nrows, total_in, WordIdentity());
     __syncthreads();
     const uintptr_t ibase = reinterpret_cast<uintptr_t>(in), obase = reinterpret_cast<uintptr_t>(out);
-    const uint8_t* lb = reinterpret_cast<const uint8_t*>(lin);
-    uint8_t* ob = reinterpret_cast<uint8_t*>(lout);
-    if (tid < nx) {
+    const int pb = (lo - in_lo) * 3;                          // segment byte of the pixel's first tap
+    const int q3 = tid & 3, wout = 3 * (tid >> 2) + q3 + 1;   // quad lane, and the staged output word lanes 0..2 of a quad write
 #pragma unroll
-        for (int r = 0; r < HR; ++r) {
-            if (r >= nrows) break;
-            const int m = (int)((ibase + (unsigned long long)(g0 + (long long)r * rowb)) & 3);
-            const uint8_t* p = lb + r * HP_IN * 4 + m + (lo - in_lo) * 3;
-            int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
+    for (int r = 0; r < HR; ++r) {
+        if (r >= nrows) break;
+        const int off = (int)((ibase + (unsigned long long)(g0 + (long long)r * rowb)) & 3) + pb;
+        const uint32_t* lr = lin + r * HP_IN + (off >> 2);
+        const uint32_t sh = (uint32_t)(off & 3);
+        uint32_t wd[NA + 1], a[NA];
 #pragma unroll
-            for (int j = 0; j < HK; ++j) {  // straight-line: taps beyond the pixel's count have coefficient 0 (reads stay inside the LDS slack)
-                s0 += __mul24((int)p[3 * j], kreg[j]); s1 += __mul24((int)p[3 * j + 1], kreg[j]); s2 += __mul24((int)p[3 * j + 2], kreg[j]);   // |coefficient| < 2^23: v_mad_i32_i24 (v_mul_lo_u32 is quarter rate)
-            }
-            s0 >>= PRECISION_BITS; s1 >>= PRECISION_BITS; s2 >>= PRECISION_BITS;
-            const long long go = ((long long)(row0 + r) * Wo + xo0) * 3;
-            const int mo = (int)((obase + (unsigned long long)go) & 3);
-            uint8_t* o = ob + r * HP_OUT * 4 + mo + tid * 3;
-            o[0] = (uint8_t)(s0 < 0 ? 0 : (s0 > 255 ? 255 : s0));
-            o[1] = (uint8_t)(s1 < 0 ? 0 : (s1 > 255 ? 255 : s1));
-            o[2] = (uint8_t)(s2 < 0 ? 0 : (s2 > 255 ? 255 : s2));
+        for (int i = 0; i <= NA; ++i) wd[i] = lr[i];
+#pragma unroll
+        for (int i = 0; i < NA; ++i) a[i] = __builtin_amdgcn_alignbyte(wd[i + 1], wd[i], sh);
+        int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
+#define HB(p_) ((int)((a[(p_) >> 2] >> (8 * ((p_) & 3))) & 0xffu))
+#pragma unroll
+        for (int j = 0; j < HK; ++j) {  // straight-line: taps beyond the pixel's count have coefficient 0 (reads stay inside the LDS slack)
+            s0 += __mul24(HB(3 * j), kreg[j]); s1 += __mul24(HB(3 * j + 1), kreg[j]); s2 += __mul24(HB(3 * j + 2), kreg[j]);   // |coefficient| < 2^23: 24-bit multiplies (v_mul_lo_u32 is quarter rate)
         }
+#undef HB
+        s0 >>= PRECISION_BITS; s1 >>= PRECISION_BITS; s2 >>= PRECISION_BITS;
+        const uint32_t px = (uint32_t)(s0 < 0 ? 0 : (s0 > 255 ? 255 : s0)) | ((uint32_t)(s1 < 0 ? 0 : (s1 > 255 ? 255 : s1)) << 8) |
+                            ((uint32_t)(s2 < 0 ? 0 : (s2 > 255 ? 255 : s2)) << 16);
+        // the quad's 12 bytes as three words: lane q of a quad forms bytes [4q, 4q + 4) from its own pixel and its right neighbour's
+        const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)px, 0xF9 /* quad_perm:[1,2,3,3] */, 0xf, 0xf, false);
+        const uint32_t word = __builtin_amdgcn_alignbyte(nb >> 8, px | (nb << 24), (uint32_t)q3);
+        if (q3 < 3) lout[r * HP_OUT + wout] = word;
     }
     __syncthreads();
+    // staged word i + 1 of a row holds segment bytes [4i, 4i + 4); global word k of the row holds segment bytes [4k - mo, 4k - mo + 4)
     const int segb = nx * 3;
-    for (int i = tid; i < nrows * HP_OUT; i += 256) {
-        const int r = i / HP_OUT, k = i - r * HP_OUT;
+    for (int r = 0; r < nrows; ++r) {
         const long long go = ((long long)(row0 + r) * Wo + xo0) * 3;
         const int mo = (int)((obase + (unsigned long long)go) & 3);
-        const int b0 = 4 * k - mo;  // segment byte index of this word's byte 0
-        if (b0 >= segb || b0 + 3 < 0) continue;
-        const uint32_t w = lout[r * HP_OUT + k];
-        uint8_t* dst = out + go + b0;
-        if (b0 >= 0 && b0 + 4 <= segb) *reinterpret_cast<uint32_t*>(dst) = w;
-        else
-            for (int b = 0; b < 4; ++b)
-                if (b0 + b >= 0 && b0 + b < segb) dst[b] = (uint8_t)(w >> (8 * b));
+        const uint32_t* ls = lout + r * HP_OUT + (mo == 0 ? 1 : 0);
+        const uint32_t sh = (uint32_t)((4 - mo) & 3);
+        for (int k = tid; 4 * k - mo < segb; k += 256) {
+            const int b0 = 4 * k - mo;  // segment byte index of this word's byte 0
+            const uint32_t w = __builtin_amdgcn_alignbyte(ls[k + 1], ls[k], sh);
+            uint8_t* dst = out + go + b0;
+            if (b0 >= 0 && b0 + 4 <= segb) *reinterpret_cast<uint32_t*>(dst) = w;
+            else
+                for (int b = 0; b < 4; ++b)
+                    if (b0 + b >= 0 && b0 + b < segb) dst[b] = (uint8_t)(w >> (8 * b));
+        }
     }
 }
 
 // Vertical pass, tiled (<= VK <= VKMAX taps): one workgroup = VT_R output rows x VT_XB row bytes.  The input rows those outputs
-// touch are staged in LDS by fill_rows() (lds_rows rows are allocated: the largest span of any row group + VK of slack, so the
+// touch are staged in LDS by fill_tile() (lds_rows rows are allocated: the largest span of any row group + VK of slack, so the
 // straight-line tap loop may read rows past the span with zero coefficients), the VT_R coefficient rows are staged too; every
 // thread owns one ALIGNED 4-byte word of each output row and, per tap, reads the 4 input bytes above it as two LDS words +
-// v_alignbyte.
-constexpr int VT_XB = 1024, VT_R = 8, VKMAX = 16, VT_PAD = 4;
-constexpr int VT_NW = (VT_XB + 2 * VT_PAD) / 4 + 1, VT_PITCH = VT_NW + 2;
+// v_alignbyte.  Nothing in the row loop waits on global memory: lane rr of every wave keeps output row rr's first input row
+// (v_readlane), the coefficients come from LDS, and the word offset and shift
+// of a tap — which depend on the tap only through (row * rowbytes) & 3, period 4 — are formed once per output row.
+// VT_R = 16 keeps four workgroups on a CU (about 37 KB each at the A4 ratio); 32 rows would stage each input row 1.4 times instead
+// of 1.7 but leave two workgroups per CU to hide the fill behind the sums.
+constexpr int VT_XB = 1008, VT_R = 16, VKMAX = 16, VT_PAD = 4;
+constexpr int VT_NW = (VT_XB + 2 * VT_PAD) / 4 + 1, VT_PITCH = VT_NW + 1;   // 255 words a row: one fill_tile() sweep of 256 threads
+static_assert(VT_R <= 64, "one lane per output row of a group");
 template <int VK>
-__global__ __launch_bounds__(256) void resample_v_tile_kernel(const uint8_t* in, uint8_t* out, const int* bounds, const int* kk, int ksize, int H,
-                                                              int rowbytes, int Ho, long long total_in) {
+__global__ __launch_bounds__(256) void resample_v_tile_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, const int* __restrict__ bounds,
+                                                              const int* __restrict__ kk, int ksize, int H, int rowbytes, int Ho, long long total_in) {
     extern __shared__ uint32_t lds[];   // [lds_rows][VT_PITCH]
     __shared__ int kl[VT_R * VK];
     const int tid = threadIdx.x;
@@ -189,49 +249,73 @@ __global__ __launch_bounds__(256) void resample_v_tile_kernel(const uint8_t* in,
         const int rr = i / VK, j = i - rr * VK;
         kl[i] = (rr < nyo && j < ksize) ? kk[(size_t)(yo0 + rr) * ksize + j] : 0;
     }
+    const int lo_lane = bounds[2 * (yo0 + min(tid & 63, nyo - 1))];   // lane rr: first input row of output row yo0 + rr
     const int in_lo = bounds[2 * yo0];
     const int in_hi = bounds[2 * (yo0 + nyo - 1)] + bounds[2 * (yo0 + nyo - 1) + 1];  // exclusive
     const uintptr_t ibase = reinterpret_cast<uintptr_t>(in), obase = reinterpret_cast<uintptr_t>(out);
     const long long g0 = ((long long)n * H + in_lo) * rowbytes + x0 - VT_PAD;
-    fill_rows(lds, VT_PITCH, VT_NW, in, g0, rowbytes, in_hi - in_lo, 0, in_hi - in_lo, total_in, WordIdentity());
+    fill_tile<16>(lds, VT_PITCH, VT_NW, in, g0, rowbytes, in_hi - in_lo, 0, in_hi - in_lo, total_in, WordIdentity());
     __syncthreads();
     const int m0 = (int)((ibase + (unsigned long long)g0) & 3), dm = rowbytes & 3;
+    const uint32_t* lt = lds + tid;
     for (int rr = 0; rr < nyo; ++rr) {
         const int yo = yo0 + rr;
-        const int lo = bounds[2 * yo] - in_lo;
+        const int lo = __builtin_amdgcn_readlane(lo_lane, rr) - in_lo;
         const long long go = ((long long)n * Ho + yo) * rowbytes + x0;
         const int mo = (int)((obase + (unsigned long long)go) & 3);
         const int ew = x0 - mo + 4 * tid;
-        if (ew >= rowbytes || ew + 3 < 0) continue;
-        int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0, s3 = s0;
+        if (tid < VT_XB / 4 && ew < rowbytes && ew + 3 >= 0) {
+            // tap j reads LDS row lo + j at byte u + 4 * tid, u = ((m0 + (lo + j) * dm) & 3) - mo + VT_PAD in [1, 7]: four cases of j & 3
+            const uint32_t* lb[4];
+            uint32_t sh[4];
 #pragma unroll
-        for (int j = 0; j < VK; ++j) {  // straight-line: taps beyond the row's count have coefficient 0
-            const int r = lo + j;
-            const int off = ((m0 + r * dm) & 3) - mo + 4 * tid + VT_PAD;
-            const uint32_t* lr = lds + r * VT_PITCH + (off >> 2);
-            const uint32_t w = __builtin_amdgcn_alignbyte(lr[1], lr[0], (uint32_t)(off & 3));
-            const int kj = kl[rr * VK + j];
-            s0 += __mul24((int)(w & 0xff), kj); s1 += __mul24((int)((w >> 8) & 0xff), kj); s2 += __mul24((int)((w >> 16) & 0xff), kj); s3 += __mul24((int)(w >> 24), kj);
+            for (int c = 0; c < 4; ++c) {
+                const int u = ((m0 + (lo + c) * dm) & 3) - mo + VT_PAD;
+                lb[c] = lt + lo * VT_PITCH + (u >> 2);
+                sh[c] = (uint32_t)(u & 3);
+            }
+            int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0, s3 = s0;
+#pragma unroll
+            for (int j = 0; j < VK; ++j) {  // straight-line: taps beyond the row's count have coefficient 0
+                const uint32_t* lr = lb[j & 3] + j * VT_PITCH;
+                const uint32_t w = __builtin_amdgcn_alignbyte(lr[1], lr[0], sh[j & 3]);
+                const int kj = kl[rr * VK + j];
+                s0 += __mul24((int)(w & 0xff), kj); s1 += __mul24((int)((w >> 8) & 0xff), kj); s2 += __mul24((int)((w >> 16) & 0xff), kj); s3 += __mul24((int)(w >> 24), kj);
+            }
+            s0 >>= PRECISION_BITS; s1 >>= PRECISION_BITS; s2 >>= PRECISION_BITS; s3 >>= PRECISION_BITS;
+            const uint32_t res = (uint32_t)(s0 < 0 ? 0 : (s0 > 255 ? 255 : s0)) | ((uint32_t)(s1 < 0 ? 0 : (s1 > 255 ? 255 : s1)) << 8) |
+                                 ((uint32_t)(s2 < 0 ? 0 : (s2 > 255 ? 255 : s2)) << 16) | ((uint32_t)(s3 < 0 ? 0 : (s3 > 255 ? 255 : s3)) << 24);
+            uint8_t* dst = out + go - mo + 4 * tid;
+            if (ew >= 0 && ew + 4 <= rowbytes) *reinterpret_cast<uint32_t*>(dst) = res;
+            else
+                for (int j = 0; j < 4; ++j)
+                    if (ew + j >= 0 && ew + j < rowbytes) dst[j] = (uint8_t)(res >> (8 * j));
         }
-        s0 >>= PRECISION_BITS; s1 >>= PRECISION_BITS; s2 >>= PRECISION_BITS; s3 >>= PRECISION_BITS;
-        const uint32_t res = (uint32_t)(s0 < 0 ? 0 : (s0 > 255 ? 255 : s0)) | ((uint32_t)(s1 < 0 ? 0 : (s1 > 255 ? 255 : s1)) << 8) |
-                             ((uint32_t)(s2 < 0 ? 0 : (s2 > 255 ? 255 : s2)) << 16) | ((uint32_t)(s3 < 0 ? 0 : (s3 > 255 ? 255 : s3)) << 24);
-        uint8_t* dst = out + go - mo + 4 * tid;
-        if (ew >= 0 && ew + 4 <= rowbytes) *reinterpret_cast<uint32_t*>(dst) = res;
-        else
-            for (int j = 0; j < 4; ++j)
-                if (ew + j >= 0 && ew + j < rowbytes) dst[j] = (uint8_t)(res >> (8 * j));
     }
 }
 
-__global__ __launch_bounds__(256) void gray_sum_kernel(const uint8_t* img, unsigned long long* sums, int HW) {
+__device__ __forceinline__ unsigned lum_u(unsigned r, unsigned g, unsigned b) { return (r * 19595u + g * 38470u + b * 7471u + 0x8000u) >> 16; }
+
+// Sum of PIL's L over an image.  Four pixels (12 bytes) per thread and step as three aligned words: pixel i of the image starts on a
+// word boundary when i = (image address) mod 4, so up to three head pixels and three tail pixels are summed bytewise.  The 64-bit
+// integer sum does not depend on the order.
+__global__ __launch_bounds__(256) void gray_sum_kernel(const uint8_t* __restrict__ img, unsigned long long* sums, int HW) {
     __shared__ unsigned long long part[4];
     const int n = blockIdx.y;
     const uint8_t* p = img + (size_t)n * HW * 3;
+    const int head = min(HW, (int)(reinterpret_cast<uintptr_t>(p) & 3));
+    const int ngroups = (HW - head) >> 2;
+    const uint32_t* wp = reinterpret_cast<const uint32_t*>(p + 3 * head);
     unsigned long long s = 0;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += gridDim.x * blockDim.x) {
-        const unsigned r = p[(size_t)i * 3], g = p[(size_t)i * 3 + 1], b = p[(size_t)i * 3 + 2];
-        s += (r * 19595u + g * 38470u + b * 7471u + 0x8000u) >> 16;
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += gridDim.x * blockDim.x) {
+        const uint32_t w0 = wp[3 * (size_t)g], w1 = wp[3 * (size_t)g + 1], w2 = wp[3 * (size_t)g + 2];
+        s += lum_u(w0 & 0xff, (w0 >> 8) & 0xff, (w0 >> 16) & 0xff) + lum_u(w0 >> 24, w1 & 0xff, (w1 >> 8) & 0xff) +
+             lum_u((w1 >> 16) & 0xff, w1 >> 24, w2 & 0xff) + lum_u((w2 >> 8) & 0xff, (w2 >> 16) & 0xff, w2 >> 24);
+    }
+    const int rest = HW - 4 * ngroups;   // head + tail pixels, at most 6
+    if (blockIdx.x == 0 && (int)threadIdx.x < rest) {
+        const size_t i = (int)threadIdx.x < head ? threadIdx.x : (size_t)threadIdx.x + 4 * (size_t)ngroups;
+        s += lum_u(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
     }
     for (int m = 32; m >= 1; m >>= 1) {
         const unsigned lo = __shfl_xor((unsigned)(s & 0xffffffffull), m), hi = __shfl_xor((unsigned)(s >> 32), m);
@@ -242,37 +326,44 @@ __global__ __launch_bounds__(256) void gray_sum_kernel(const uint8_t* img, unsig
     if (threadIdx.x == 0) atomicAdd(&sums[n], part[0] + part[1] + part[2] + part[3]);  // one atomic per workgroup
 }
 
-__device__ __forceinline__ uint8_t blend_u8(int deg, int v, float alpha) {
-    const float t = __fadd_rn((float)deg, __fmul_rn(alpha, (float)(v - deg)));
-    // PIL clips only when alpha is outside [0, 1]; inside, t already lies between the two byte values, so one unconditional
-    // clamp (v_med3_f32) is the same function without a per-byte branch
-    return (uint8_t)fminf(fmaxf(t, 0.f), 255.f);
+// ImageEnhance's blend of a byte v with a degenerate value deg, both given as floats: deg + alpha * (v - deg) in float32, then PIL's
+// clip and truncation.  v - deg is formed in float: both are integers below 2^24, so it equals PIL's (float)(v - deg) exactly.
+// PIL clips only when alpha is outside [0, 1]; inside, t already lies between the two byte values, so one unconditional clamp
+// (v_med3_f32) is the same function without a per-byte branch.
+__device__ __forceinline__ uint32_t blend_f(float deg, float v, float alpha) {
+    const float t = __fadd_rn(deg, __fmul_rn(alpha, __fadd_rn(v, -deg)));
+    return (uint32_t)fminf(fmaxf(t, 0.f), 255.f);
 }
-
-// Fused contrast + sharpness.  One workgroup = EN_R rows x EN_XB row bytes.  The contrast-blended bytes of the EN_R + 2 rows
-// (8 bytes of apron left and right) are built ONCE in LDS from aligned 4-byte global loads — every LDS row keeps its global
-// word alignment, so the fill is load -> 4 blends -> ds_write_b32 — and the 3x3 SMOOTH blend then reads 12-byte windows at
-// arbitrary byte offsets (4 aligned LDS words + v_alignbyte).  Each thread owns one ALIGNED 4-byte word of the output row
-// (rows of W*3 bytes are not word aligned in general: the strip of a row is shifted left by the row's misalignment), so
-// the result is stored with one dword store; the first / last word of a row is stored bytewise.
-// Arithmetic order is Pillow's (ImageFilter.SMOOTH: row y+1, y, y-1, left to right, + 0.5 offset, float32), see
-// /root/reference/backend/utils/image_preprocessing.py:132-158.
-constexpr int EN_XB = 1024, EN_R = 8, EN_PAD = 8;
-constexpr int EN_NW = (EN_XB + 2 * EN_PAD) / 4 + 1;  // words per LDS row (misalignment <= 3 bytes)
-constexpr int EN_PITCH = EN_NW + 3;
-
-__device__ __forceinline__ uint32_t blend_u8x4(int deg, uint32_t w, float alpha) {
-    return (uint32_t)blend_u8(deg, (int)(w & 0xff), alpha) | ((uint32_t)blend_u8(deg, (int)((w >> 8) & 0xff), alpha) << 8) |
-           ((uint32_t)blend_u8(deg, (int)((w >> 16) & 0xff), alpha) << 16) | ((uint32_t)blend_u8(deg, (int)(w >> 24), alpha) << 24);
-}
+__device__ __forceinline__ float byte_f(uint32_t w, int b) { return (float)((w >> (8 * b)) & 0xffu); }   // v_cvt_f32_ubyte<b>
 
 struct ContrastWord {
-    int mean; float alpha;
-    __device__ __forceinline__ uint32_t operator()(uint32_t w) const { return blend_u8x4(mean, w, alpha); }
+    float mean, alpha;
+    __device__ __forceinline__ uint32_t operator()(uint32_t w) const {
+        return blend_f(mean, byte_f(w, 0), alpha) | (blend_f(mean, byte_f(w, 1), alpha) << 8) | (blend_f(mean, byte_f(w, 2), alpha) << 16) |
+               (blend_f(mean, byte_f(w, 3), alpha) << 24);
+    }
 };
 
-__global__ __launch_bounds__(256) void enhance_kernel(const uint8_t* img, uint8_t* out, const unsigned long long* sums, int H, int W,
-                                                      float alpha_c, float alpha_s, long long total_bytes) {
+// Fused contrast + sharpness.  One workgroup = EN_R rows x EN_XB row bytes.  The contrast-blended bytes of the EN_R + 2 rows
+// (8 bytes of apron on the left, 4 on the right) are built ONCE in LDS from aligned 4-byte global loads — every LDS row keeps its
+// global word alignment, so the fill is load -> 4 blends -> ds_write_b32.
+// The 3x3 SMOOTH blend walks DOWN the tile with a thread per 4-byte column that is fixed relative to the row (bytes e0 - 4 + 4c ..
+// + 3 of every row, c = 63 * wave + lane), so that what a row contributes is computed once: its 12-byte window (4 aligned LDS words
+// + v_alignbyte by the row's misalignment, which is uniform), the 10 byte -> float conversions, and the two horizontal sums of
+// Pillow's kernel — (a + b) + c with weights 1,1,1 (used by the output rows above and below) and 1,5,1 (the row itself).  An
+// output row then costs three adds and the sharpness blend per byte.  Rows of W*3 bytes are not word aligned in general, so the
+// ALIGNED output word that starts mo bytes before the thread's column is put together from the thread's result and its right
+// neighbour's (one wave shuffle; lane 63 of a wave only feeds lane 62, which is why a wave stores 63 words and a workgroup
+// 4 * 63 * 4 = EN_XB bytes); the first / last word of a row is stored bytewise.
+// Arithmetic order is Pillow's (ImageFilter.SMOOTH: row y+1, y, y-1, left to right, + 0.5 offset, float32), see
+// /root/reference/backend/utils/image_preprocessing.py:132-158.
+constexpr int EN_XB = 1008, EN_R = 16, EN_PAD = 8;
+constexpr int EN_NW = (EN_PAD + EN_XB + 4 + 3 + 3) / 4;  // words per LDS row: apron + strip + the last column's window, misalignment <= 3 bytes
+constexpr int EN_PITCH = EN_NW;
+static_assert(EN_XB == 4 * 63 * 4 && EN_NW <= 256 && 63 * 3 + 63 + 3 < EN_NW, "column c reads words c .. c + 3 of a row");
+
+__global__ __launch_bounds__(256) void enhance_kernel(const uint8_t* __restrict__ img, uint8_t* __restrict__ out, const unsigned long long* sums, int H,
+                                                      int W, float alpha_c, float alpha_s, long long total_bytes) {
     __shared__ uint32_t lds[(EN_R + 2) * EN_PITCH];
     const int tid = threadIdx.x;
     const int n = blockIdx.z, yb = blockIdx.y * EN_R, e0 = blockIdx.x * EN_XB;
@@ -281,65 +372,68 @@ __global__ __launch_bounds__(256) void enhance_kernel(const uint8_t* img, uint8_
     const uintptr_t ibase = reinterpret_cast<uintptr_t>(img), obase = reinterpret_cast<uintptr_t>(out);
     const long long g0 = ((long long)n * H + yb - 1) * rowb + e0 - EN_PAD;  // flat byte index of LDS row 0's byte 0 (image row yb - 1)
     const int rlo = yb == 0 ? 1 : 0, rhi = min(EN_R + 2, H - yb + 1);       // LDS rows whose image row exists
-    fill_rows(lds, EN_PITCH, EN_NW, img, g0, rowb, EN_R + 2, rlo, rhi, total_bytes, ContrastWord{mean, alpha_c});
+    fill_tile<EN_R + 2>(lds, EN_PITCH, EN_NW, img, g0, rowb, EN_R + 2, rlo, rhi, total_bytes, ContrastWord{(float)mean, alpha_c});
     __syncthreads();
 
-    for (int rr = 0; rr < EN_R; ++rr) {
-        const int y = yb + rr;
-        if (y >= H) break;
-        const long long go = ((long long)n * H + y) * rowb + e0;
-        const int mo = (int)((obase + (unsigned long long)go) & 3);
-        const int ew = e0 - mo + 4 * tid;  // row-relative byte index of this thread's aligned output word
-        if (ew >= rowb || ew + 3 < 0) continue;
-        uint32_t win[3][3];  // [row y-1, y, y+1][12 bytes starting at row byte ew - 3]
+    const int lane = tid & 63, c = 63 * (tid >> 6) + lane;
+    const int ec = e0 - 4 + 4 * c;            // row-relative byte index of the column's byte 0
+    const uint32_t* lc = lds + c;
+    const float k1 = 1.0f / 13.0f, k5 = 5.0f / 13.0f;
+    float up[4], mid1[4], mid5[4], vmid[4];   // 1,1,1 sums of rows y - 1 and y, 1,5,1 sums and centre bytes of row y
 #pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const int yy = y - 1 + d;
-            const long long g = ((long long)n * H + yy) * rowb + e0 - EN_PAD;
-            const int m = (int)((ibase + (unsigned long long)g) & 3);
-            const int off = m - mo + 4 * tid + (EN_PAD - 3);
-            const int q = off >> 2;
-            const uint32_t sh = (uint32_t)(off & 3);
-            const uint32_t* lr = lds + (rr + d) * EN_PITCH + q;
-            const uint32_t w0 = lr[0], w1 = lr[1], w2 = lr[2], w3 = lr[3];
-            win[d][0] = __builtin_amdgcn_alignbyte(w1, w0, sh);
-            win[d][1] = __builtin_amdgcn_alignbyte(w2, w1, sh);
-            win[d][2] = __builtin_amdgcn_alignbyte(w3, w2, sh);
-        }
-        const bool yin = y > 0 && y < H - 1;
-        uint32_t res = 0;
-#define WB(d_, p_) ((float)((win[d_][(p_) >> 2] >> (8 * ((p_) & 3))) & 0xffu))
+    for (int j = 0; j < 4; ++j) up[j] = mid1[j] = mid5[j] = vmid[j] = 0.f;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int e = ew + j;
-            const int v = (int)((win[1][(j + 3) >> 2] >> (8 * ((j + 3) & 3))) & 0xffu);
-            // straight-line: the smoothed value is computed for every byte and selected for interior pixels only
-            const float k1 = 1.0f / 13.0f, k5 = 5.0f / 13.0f;
-            float ss = 0.5f;
-            float a = __fmul_rn(WB(2, j), k1);
-            a = __fadd_rn(a, __fmul_rn(WB(2, j + 3), k1));
-            a = __fadd_rn(a, __fmul_rn(WB(2, j + 6), k1));
-            ss = __fadd_rn(ss, a);
-            a = __fmul_rn(WB(1, j), k1);
-            a = __fadd_rn(a, __fmul_rn(WB(1, j + 3), k5));
-            a = __fadd_rn(a, __fmul_rn(WB(1, j + 6), k1));
-            ss = __fadd_rn(ss, a);
-            a = __fmul_rn(WB(0, j), k1);
-            a = __fadd_rn(a, __fmul_rn(WB(0, j + 3), k1));
-            a = __fadd_rn(a, __fmul_rn(WB(0, j + 6), k1));
-            ss = __fadd_rn(ss, a);
-            const int sm = (int)fminf(fmaxf(ss, 0.f), 255.f);
-            const int deg = (yin && e >= 3 && e < rowb - 3) ? sm : v;
-            res |= (uint32_t)blend_u8(deg, v, alpha_s) << (8 * j);
+    for (int r = 0; r < EN_R + 2; ++r) {      // LDS row r = image row yb - 1 + r; it completes output row y = yb + r - 2
+        if (r >= 2 && yb + r - 2 >= H) break;
+        const uint32_t sh = (uint32_t)((ibase + (unsigned long long)(g0 + (long long)r * rowb)) & 3);
+        const uint32_t* lr = lc + r * EN_PITCH;
+        const uint32_t q0 = lr[0], q1 = lr[1], q2 = lr[2], q3 = lr[3];
+        const uint32_t win[3] = {__builtin_amdgcn_alignbyte(q1, q0, sh), __builtin_amdgcn_alignbyte(q2, q1, sh),
+                                 __builtin_amdgcn_alignbyte(q3, q2, sh)};   // row bytes ec - 4 .. ec + 7
+        float f[12];
+#pragma unroll
+        for (int i = 1; i <= 10; ++i) f[i] = byte_f(win[i >> 2], i & 3);
+        float dn1[4], dn5[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {         // byte ec + j: its left neighbour is window byte 1 + j, itself 4 + j, its right neighbour 7 + j
+            dn1[j] = __fadd_rn(__fadd_rn(__fmul_rn(f[1 + j], k1), __fmul_rn(f[4 + j], k1)), __fmul_rn(f[7 + j], k1));
+            dn5[j] = __fadd_rn(__fadd_rn(__fmul_rn(f[1 + j], k1), __fmul_rn(f[4 + j], k5)), __fmul_rn(f[7 + j], k1));
         }
-#undef WB
-        uint8_t* dst = out + go - mo + 4 * tid;
-        if (ew >= 0 && ew + 4 <= rowb) *reinterpret_cast<uint32_t*>(dst) = res;
-        else
-            for (int j = 0; j < 4; ++j)
-                if (ew + j >= 0 && ew + j < rowb) dst[j] = (uint8_t)(res >> (8 * j));
+        if (r >= 2) {
+            const int y = yb + r - 2;
+            const bool yin = y > 0 && y < H - 1;
+            uint32_t res = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int e = ec + j;
+                // straight-line: the smoothed value is computed for every byte and selected for interior pixels only
+                float ss = 0.5f;
+                ss = __fadd_rn(ss, dn1[j]);
+                ss = __fadd_rn(ss, mid5[j]);
+                ss = __fadd_rn(ss, up[j]);
+                const float sm = truncf(fminf(fmaxf(ss, 0.f), 255.f));
+                const float deg = (yin && e >= 3 && e < rowb - 3) ? sm : vmid[j];
+                res |= blend_f(deg, vmid[j], alpha_s) << (8 * j);
+            }
+            // global word a = ec + 4 - mo of row y: bytes 4 - mo .. of this column, the rest from the column to the right
+            const long long go = ((long long)n * H + y) * rowb;
+            const int mo = (int)((obase + (unsigned long long)go) & 3);
+            const uint32_t nxt = (uint32_t)__shfl_down((int)res, 1);
+            const uint32_t word = mo == 0 ? nxt : __builtin_amdgcn_alignbyte(nxt, res, (uint32_t)(4 - mo));
+            const int ew = ec + 4 - mo;
+            if (lane < 63 && ew < rowb && ew + 3 >= 0) {
+                uint8_t* dst = out + go + ew;
+                if (ew >= 0 && ew + 4 <= rowb) *reinterpret_cast<uint32_t*>(dst) = word;
+                else
+                    for (int j = 0; j < 4; ++j)
+                        if (ew + j >= 0 && ew + j < rowb) dst[j] = (uint8_t)(word >> (8 * j));
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { up[j] = mid1[j]; mid1[j] = dn1[j]; mid5[j] = dn5[j]; vmid[j] = f[4 + j]; }
     }
 }
+
 
 inline int grid_for(size_t total) {
     size_t g = (total + 255) / 256;
