@@ -5,9 +5,8 @@
 // (tests/aztec_layers_reference.py for the second stage).
 //
 // All stream-ordered kernels, no host round trip:
-//   1 ink_mask                          the mask (or the one the caller already has)
-//   2 run_count / row_scan / run_fill / run_merge   mask words -> run list and its 8-connected components (the shared kernels of runs.hip)
-//   3 az_init, az_accum   a run is its own area; every run learns its root, and box and area are accumulated there
+//   1-3 components_launch (runs.h)      the mask (or the one the caller already has), its run list, the 8-connected components; a run is
+//                 its own area; every run learns its root, and box and area are accumulated there
 //   4 az_finders  one wave per row, lanes over the row's roots: a solid square core whose neighbours on its centre row both belong to
 //                 one concentric component of five times its side -> counted, gathered per page
 //   5 az_decode   one wave per (page, finder).  A frame is the ring's centre, a slope and a pitch; a point of it is a pixel by
@@ -15,17 +14,18 @@
 //                 kind, whose corner marks give the rotation and whose mode message (GF(16)) gives layers and data words; then,
 //                 the size known, on the symbol's outline (ink just inside it, none just outside) and the centre reference lines.
 //                 Lane r samples module row r as one 64-bit word; lanes gather the codewords through the layer spiral from the
-//                 rows in LDS; the one block goes through rs_gf2m.h.  Every loop has a constant bound, every LDS and page index is
+//                 rows in LDS; the one block goes through rs.h.  Every loop has a constant bound, every LDS and page index is
 //                 clamped, and no wave waits for another (a work-group is one wave)
 //   5b az_layers  (lumina_ocr_aztec_layers alone) one wave per (page, finder): a full-range finder of 12 .. max_layers layers that
 //                 az_decode left pending gets a finer frame (slope and pitch in 1024ths), refined outwards along the centre reference
 //                 lines and finished on the outline; lane r samples rows r, r + 64, r + 128 as three words each; GF(1024) up to 22
 //                 layers, GF(4096) above.  The same rules: constant loop bounds, clamped indices, no wave waits for another
-//   6 az_output   one work-group per page: valid finders counted, gathered, rank-sorted by (y0, x0, y1, x1, root)
+//   6 az_output   one work-group per page (code_output.h): valid finders counted, gathered, rank-sorted by (y0, x0, y1, x1, root)
 #include "aztec.h"
+#include "code_output.h"
 #include "aztec_tables.h"
 #include "aztec_tables12.h"
-#include "rs_gf2m.h"
+#include "rs.h"
 #include "runs.h"
 
 namespace {
@@ -33,36 +33,10 @@ namespace {
 typedef unsigned long long u64;
 typedef long long i64;
 
-constexpr int RES_INTS = 16;   // a finder's result: y0, x0, y1, x1, root, layers, compact, width, ndata, errors, rotation, mode errors, mismatches, valid
-                               // (1: a row; 2: pending for az_layers, which then finds the bullseye's frame t0, k0 in the last two)
+// a finder's result (code_output.h): y0, x0, y1, x1, root, layers, compact, width, ndata, errors, rotation, mode errors, mismatches, state
+// (CODE_PENDING: for az_layers, which then finds the bullseye's frame t0, k0 in the last two)
 constexpr int AZ_MAX_WORDS = 320, AZ_MAX_EC = 318, AZ_MAX_M = 10, AZ_MAX_LAYERS = 11, AZ_MAX_SIDE = 61;
 constexpr int AZL_MAX_WORDS = 1664, AZL_MAX_EC = 1662, AZL_MAX_M = 12, AZL_MAX_LAYERS = 32, AZL_MAX_SIDE = 151, AZL_SPAN = 4, AZL_FRAMES = 81;
-
-// 3a: a run's own length is the start of its component's area
-__global__ __launch_bounds__(256) void az_init_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* area, int H, size_t runcap,
-                                                      int rows_total) {
-    int pg, row, lane;
-    if (!row_wave(H, rows_total, pg, row, lane)) return;
-    const int* ro = runoff + (size_t)pg * (H + 1);
-    const size_t rb = (size_t)pg * runcap;
-    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) area[rb + id] = rxe[rb + id] - rxs[rb + id] + 1;
-}
-
-// 3b: parent = root; the root's box and area grow to the component's
-__global__ __launch_bounds__(256) void az_accum_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* parent, int4* box, int* area,
-                                                       int H, size_t runcap, int rows_total) {
-    int pg, row, lane;
-    if (!row_wave(H, rows_total, pg, row, lane)) return;
-    const int* ro = runoff + (size_t)pg * (H + 1);
-    const size_t rb = (size_t)pg * runcap;
-    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
-        int xs, xe;
-        const int root = run_join_root(parent + rb, rxs + rb, rxe + rb, box + rb, id, row, xs, xe);
-        if (root >= 0) atomicAdd(area + rb + root, xe - xs + 1);
-    }
-}
-
-__device__ __forceinline__ int iabs(int v) { return v < 0 ? -v : v; }
 
 // 4: finders [B][max_finders][2] = the core's root, the ring's root
 __global__ __launch_bounds__(256) void az_finders_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, const int* parent, const int4* box,
@@ -166,7 +140,7 @@ __device__ __forceinline__ void az_bit_pos(bool compact, int layers, int b, int&
 
 struct AzLds {
     u64 rows[64];
-    Rs2mLds<AZ_MAX_WORDS, AZ_MAX_EC, AZ_MAX_M> rs;
+    RsLds<unsigned short, AZ_MAX_WORDS, AZ_MAX_EC, AZ_MAX_M> rs;
 };
 
 // ink on the square at d quarter modules, points every `step` quarter modules, corners included on all four sides (d / step * 2 + 1 <= 128 points a side)
@@ -183,7 +157,7 @@ __device__ __forceinline__ int az_square(const u64* mpage, int H, int W, int nw,
     return n;
 }
 
-// 5: one wave per (page, finder): res [B][max_finders][RES_INTS], resdata [B][max_finders][data_stride].  A full-range finder of
+// 5: one wave per (page, finder): res [B][max_finders][CODE_RES_INTS], resdata [B][max_finders][data_stride].  A full-range finder of
 // AZ_MAX_LAYERS < layers <= max_layers that ends without a row is left pending
 __global__ __launch_bounds__(64) void az_decode_kernel(const u64* mask, const int* finders, const int* nfind, const int4* box, int H, int W, int nw, size_t runcap,
                                                        int max_finders, int quiet, int mark_max, int max_layers, int data_stride, int* res,
@@ -197,7 +171,7 @@ __global__ __launch_bounds__(64) void az_decode_kernel(const u64* mask, const in
     const int ring = clampi(finders[((size_t)pg * max_finders + a) * 2 + 1], 0, (int)runcap - 1);
     const int4 gx = box[(size_t)pg * runcap + ring];   // x0, x1, y0, y1
     const int cx2 = gx.x + gx.y + 1, cy2 = gx.z + gx.w + 1, s10 = (gx.y - gx.x + 1) + (gx.w - gx.z + 1);
-    rs2m_load_tables(s.rs, AZ_EXP + AZ_EXP_OFF[0], AZ_LOG + AZ_LOG_OFF[0], 4, lane);
+    rs_load_tables(s.rs, AZ_EXP + AZ_EXP_OFF[0], AZ_LOG + AZ_LOG_OFF[0], 4, lane);
     // either kind: the bullseye's best frame, the rotation, the mode message
     i64 kind_best = -1;
     int pend_layers = 0, pend_ndata = 0, pend_rot = 0, pend_merr = 0, pend_mism = 0, pend_t = 0, pend_k = 0;
@@ -254,7 +228,7 @@ __global__ __launch_bounds__(64) void az_decode_kernel(const u64* mask, const in
             s.rs.blk[lane] = (unsigned short)(((v & 1) << 3) | ((v & 2) << 1) | ((v & 4) >> 1) | ((v & 8) >> 3));
         }
         __syncthreads();
-        const int merr = rs2m_correct_block(s.rs, nwords, ecw, lane);
+        const int merr = rs_correct_block(s.rs, nwords, ecw, 1, lane);
         if (merr < 0) continue;
         int layers, ndata;
         if (!full) {
@@ -277,8 +251,8 @@ __global__ __launch_bounds__(64) void az_decode_kernel(const u64* mask, const in
         if (kind_best < 0 || key < kind_best) kind_best = key;
     }
     if (pend_layers && lane == 0) {   // (a row of this finder overwrites it)
-        int* o = res + ((size_t)pg * max_finders + a) * RES_INTS;
-        o[5] = pend_layers; o[8] = pend_ndata; o[10] = pend_rot; o[11] = pend_merr; o[12] = pend_mism; o[13] = 2; o[14] = pend_t; o[15] = pend_k;
+        int* o = res + ((size_t)pg * max_finders + a) * CODE_RES_INTS;
+        o[5] = pend_layers; o[8] = pend_ndata; o[10] = pend_rot; o[11] = pend_merr; o[12] = pend_mism; o[CODE_RES_STATE] = CODE_PENDING; o[14] = pend_t; o[15] = pend_k;
     }
     if (kind_best < 0) return;
     const int mism = (int)(kind_best >> 40), merr = (int)((kind_best >> 32) & 255), rot = (int)((kind_best >> 20) & 3);
@@ -331,7 +305,7 @@ __global__ __launch_bounds__(64) void az_decode_kernel(const u64* mask, const in
         }
     __syncthreads();
     s.rows[lane] = row;
-    rs2m_load_tables(s.rs, AZ_EXP + AZ_EXP_OFF[(width - 4) >> 1], AZ_LOG + AZ_LOG_OFF[(width - 4) >> 1], width, lane);
+    rs_load_tables(s.rs, AZ_EXP + AZ_EXP_OFF[(width - 4) >> 1], AZ_LOG + AZ_LOG_OFF[(width - 4) >> 1], width, lane);
     // codewords through the layer spiral, the pad bits first
 #pragma unroll 1
     for (int j = lane; j < AZ_MAX_WORDS; j += 64) {
@@ -346,7 +320,7 @@ __global__ __launch_bounds__(64) void az_decode_kernel(const u64* mask, const in
         s.rs.blk[j] = (unsigned short)val;
     }
     __syncthreads();
-    const int errors = rs2m_correct_block(s.rs, total, ec, lane);
+    const int errors = rs_correct_block(s.rs, total, ec, 1, lane);
     if (errors < 0) return;
     unsigned short* od = resdata + ((size_t)pg * max_finders + a) * data_stride;
     for (int p = lane; p < AZ_MAX_DATA; p += 64)
@@ -363,9 +337,9 @@ __global__ __launch_bounds__(64) void az_decode_kernel(const u64* mask, const in
             y0 = c == 0 || qy < y0 ? qy : y0; y1 = c == 0 || qy > y1 ? qy : y1;
         }
         const auto cl = [](i64 v, int hi) { return (int)(v < 0 ? 0 : v > hi ? hi : v); };
-        int* o = res + ((size_t)pg * max_finders + a) * RES_INTS;
+        int* o = res + ((size_t)pg * max_finders + a) * CODE_RES_INTS;
         o[0] = cl(y0, H - 1); o[1] = cl(x0, W - 1); o[2] = cl(y1 - 1, H - 1); o[3] = cl(x1 - 1, W - 1); o[4] = root;
-        o[5] = layers; o[6] = compact ? 1 : 0; o[7] = width; o[8] = ndata; o[9] = errors; o[10] = rot; o[11] = merr; o[12] = mism + ref; o[13] = 1;
+        o[5] = layers; o[6] = compact ? 1 : 0; o[7] = width; o[8] = ndata; o[9] = errors; o[10] = rot; o[11] = merr; o[12] = mism + ref; o[CODE_RES_STATE] = CODE_ROW;
     }
 }
 
@@ -431,7 +405,7 @@ __device__ __forceinline__ int az_arms2(const u64* mpage, int H, int W, int nw, 
 struct AzLds2 {
     u64 rows[192][3];          // module row y: bit x of the 151
     int score[AZL_FRAMES];
-    Rs2mLds<AZL_MAX_WORDS, AZL_MAX_EC, AZL_MAX_M> rs;
+    RsLds<unsigned short, AZL_MAX_WORDS, AZL_MAX_EC, AZL_MAX_M> rs;
 };
 
 // 5b: one wave per (page, finder); a finder that stage 1 did not leave pending ends at once
@@ -441,8 +415,8 @@ __global__ __launch_bounds__(64) void az_layers_kernel(const u64* mask, const in
     const int pg = blockIdx.y, a = blockIdx.x, lane = threadIdx.x;
     const int nf_page = nfind[pg];
     if (nf_page > max_finders || a >= nf_page || a >= AZ_MAX_FINDERS) return;
-    int* o = res + ((size_t)pg * max_finders + a) * RES_INTS;
-    if (o[13] != 2) return;
+    int* o = res + ((size_t)pg * max_finders + a) * CODE_RES_INTS;
+    if (o[CODE_RES_STATE] != CODE_PENDING) return;
     const int layers = clampi(o[5], AZ_MAX_LAYERS + 1, AZL_MAX_LAYERS), ndata = o[8], rot = o[10] & 3, merr = o[11], mism = o[12];
     const int t0 = clampi(o[14], -4, 4), k0 = clampi(o[15], -12, 12);
     __syncthreads();   // (every lane has read the row that lane 0 will write)
@@ -522,8 +496,8 @@ __global__ __launch_bounds__(64) void az_layers_kernel(const u64* mask, const in
             }
         s.rows[y][0] = w0; s.rows[y][1] = w1; s.rows[y][2] = w2;
     }
-    if (width == 12) rs2m_load_tables(s.rs, AZ12_EXP, AZ12_LOG, 12, lane);
-    else rs2m_load_tables(s.rs, AZ_EXP + AZ_EXP_OFF[3], AZ_LOG + AZ_LOG_OFF[3], 10, lane);
+    if (width == 12) rs_load_tables(s.rs, AZ12_EXP, AZ12_LOG, 12, lane);
+    else rs_load_tables(s.rs, AZ_EXP + AZ_EXP_OFF[3], AZ_LOG + AZ_LOG_OFF[3], 10, lane);
     // codewords through the layer spiral, the pad bits first
 #pragma unroll 1
     for (int j = lane; j < AZL_MAX_WORDS; j += 64) {
@@ -538,7 +512,7 @@ __global__ __launch_bounds__(64) void az_layers_kernel(const u64* mask, const in
         s.rs.blk[j] = (unsigned short)val;
     }
     __syncthreads();
-    const int errors = rs2m_correct_block(s.rs, total, ec, lane);
+    const int errors = rs_correct_block(s.rs, total, ec, 1, lane);
     if (errors < 0) return;
     unsigned short* od = resdata + ((size_t)pg * max_finders + a) * AZ_MAX_DATA_ALL;
     for (int p = lane; p < AZ_MAX_DATA_ALL; p += 64)
@@ -556,7 +530,7 @@ __global__ __launch_bounds__(64) void az_layers_kernel(const u64* mask, const in
         }
         const auto cl = [](i64 v, int hi) { return (int)(v < 0 ? 0 : v > hi ? hi : v); };
         o[0] = cl(y0, H - 1); o[1] = cl(x0, W - 1); o[2] = cl(y1 - 1, H - 1); o[3] = cl(x1 - 1, W - 1); o[4] = root;
-        o[5] = layers; o[6] = 0; o[7] = width; o[8] = ndata; o[9] = errors; o[10] = rot; o[11] = merr; o[12] = mism + ref; o[13] = 1;
+        o[5] = layers; o[6] = 0; o[7] = width; o[8] = ndata; o[9] = errors; o[10] = rot; o[11] = merr; o[12] = mism + ref; o[CODE_RES_STATE] = CODE_ROW;
     }
 }
 
@@ -564,81 +538,37 @@ __global__ __launch_bounds__(64) void az_layers_kernel(const u64* mask, const in
 template <class T, int ND>
 __global__ __launch_bounds__(256) void az_output_kernel(const int* res_all, const unsigned short* resdata_all, const int* nfind, int max_finders, int max_codes,
                                                         int* tmp_all, int* counts, int* codes, T* data, int* finder_counts) {
-    __shared__ int s_key[AZ_MAX_CODES * 5];
-    __shared__ int s_slot[AZ_MAX_CODES];
-    __shared__ int s_n;
+    __shared__ CodeOutLds<AZ_MAX_CODES> s;
     const int pg = blockIdx.x;
-    const int nf = nfind[pg];
-    const int* res = res_all + (size_t)pg * max_finders * RES_INTS;
-    int* tmp = tmp_all + (size_t)pg * max_codes * 6;
-    if (threadIdx.x == 0) {
-        s_n = 0;
-        if (finder_counts) finder_counts[pg] = nf;
-    }
-    __syncthreads();
-    const int lim = nf > max_finders ? 0 : nf;   // a page with too many finders is not read
-    for (int a = threadIdx.x; a < lim; a += 256) {
-        const int* r = res + a * RES_INTS;
-        if (r[13] != 1) continue;
-        const int idx = atomicAdd(&s_n, 1);
-        if (idx >= max_codes) continue;
-        int* o = tmp + idx * 6;
-        o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3]; o[4] = r[4]; o[5] = a;
-    }
-    __syncthreads();
-    const int n = s_n;
-    if (threadIdx.x == 0) counts[pg] = n;
-    if (n > max_codes) return;   // overflow: the count is all that is reported
-    int* out = codes + (size_t)pg * max_codes * 12;
-    T* odat = data + (size_t)pg * max_codes * ND;
+    const int* res = res_all + (size_t)pg * max_finders * CODE_RES_INTS;
+    const int n = code_output_rows(s, res, nfind[pg], max_finders, max_codes, tmp_all + (size_t)pg * max_codes * 6, codes + (size_t)pg * max_codes * 12,
+                                   counts + pg, finder_counts ? finder_counts + pg : nullptr);
+    if (n > max_codes) return;
     const unsigned short* rd = resdata_all + (size_t)pg * max_finders * ND;
-    rank_sort<5>(s_key, tmp, 6, n, [=](int i, int rank, const int (&k)[5]) {
-        const int slot = clampi(tmp[i * 6 + 5], 0, max_finders - 1);
-        const int* r = res + slot * RES_INTS;
-        int* o = out + (size_t)rank * 12;
-        o[0] = k[1]; o[1] = k[0]; o[2] = k[3]; o[3] = k[2];
-        for (int j = 0; j < 8; ++j) o[4 + j] = r[5 + j];
-        const int nd = r[8];
-        if (ND > AZ_MAX_DATA) { s_slot[rank] = slot; return; }   // the wide rows are copied by the whole work-group below
-        for (int j = 0; j < ND; ++j) odat[(size_t)rank * ND + j] = j < nd ? (T)rd[(size_t)slot * ND + j] : (T)0;
-    });
-    if (ND <= AZ_MAX_DATA) return;
-    __syncthreads();
-    for (int rank = 0; rank < AZ_MAX_CODES; ++rank) {
-        if (rank >= n) break;
-        const int slot = clampi(s_slot[rank], 0, max_finders - 1), nd = res[slot * RES_INTS + 8];
-        for (int j = threadIdx.x; j < ND; j += 256) odat[(size_t)rank * ND + j] = j < nd ? (T)rd[(size_t)slot * ND + j] : (T)0;
-    }
+    code_output_data(s, n, max_finders, ND, data + (size_t)pg * max_codes * ND,
+                     [=](int slot, int j) -> T { return j < res[slot * CODE_RES_INTS + 8] ? (T)rd[(size_t)slot * ND + j] : (T)0; });
 }
 
 }  // namespace
 
 // the workspace's regions: one layout sizes it (aztec_workspace_bytes) and carves it (aztec_launch)
 struct AzWorkspace {
-    unsigned long long* mask; int* runoff; unsigned short *rxs, *rxe; int* parent; int4* box; int* area;
+    Components c;
     int* nfind; int* finders; int* res; unsigned short* resdata; int* tmp;
 };
 static AzWorkspace aztec_layout(Arena& a, int B, int H, int W, int max_finders, int max_codes, int data_stride = AZ_MAX_DATA) {
-    const size_t runcap = run_cap(H, W), nw = (W + 63) / 64;
     AzWorkspace w;
-    w.mask = a.take<unsigned long long>((size_t)B * H * nw);
-    w.runoff = a.take<int>((size_t)B * (H + 1));   // run counts -> offsets
-    w.rxs = a.take<unsigned short>((size_t)B * runcap); w.rxe = a.take<unsigned short>((size_t)B * runcap);
-    w.parent = a.take<int>((size_t)B * runcap);
-    w.box = a.take<int4>((size_t)B * runcap);      // at a root: x0, x1, y0, y1 of its component
-    w.area = a.take<int>((size_t)B * runcap);      // at a root: its component's ink
+    w.c = components_layout(a, B, H, W, true);
     w.nfind = a.take<int>((size_t)B);
     w.finders = a.take<int>((size_t)B * max_finders * 2);
-    w.res = a.take<int>((size_t)B * max_finders * RES_INTS);
+    w.res = a.take<int>((size_t)B * max_finders * CODE_RES_INTS);
     w.resdata = a.take<unsigned short>((size_t)B * max_finders * data_stride);
     w.tmp = a.take<int>((size_t)B * max_codes * 6);
     return w;
 }
 
 static bool aztec_args_ok(int B, int H, int W, int max_finders, int max_codes) {
-    if (B <= 0 || H <= 0 || W <= 0 || H > 65535 || W > 65535 || max_codes < 1 || max_codes > AZ_MAX_CODES || max_finders < 1 || max_finders > AZ_MAX_FINDERS)
-        return false;
-    return (size_t)B * H < (1ull << 31) && run_cap(H, W) < (1ull << 31);
+    return page_args_ok(B, H, W) && max_codes >= 1 && max_codes <= AZ_MAX_CODES && max_finders >= 1 && max_finders <= AZ_MAX_FINDERS;
 }
 
 bool aztec_params_ok(int min_module, int max_module, int quiet, int centre_tol, int ring_tol, int mark_max, int max_finders, int max_codes) {
@@ -673,26 +603,19 @@ static hipError_t aztec_run(const AztecParams& p, int max_layers, unsigned short
     if (!p.rgb || !p.codes || !(data_all ? (const void*)data_all : (const void*)p.data) || !p.counts) return hipErrorInvalidValue;
     const int stride = data_all ? AZ_MAX_DATA_ALL : AZ_MAX_DATA;
     Arena a(workspace, ws_bytes);
-    const AzWorkspace w = aztec_layout(a, B, H, W, p.max_finders, p.max_codes, stride);
+    AzWorkspace w = aztec_layout(a, B, H, W, p.max_finders, p.max_codes, stride);
     if (a.overflow) return hipErrorOutOfMemory;
     const int nw = (W + 63) / 64;
     const size_t runcap = run_cap(H, W);
-    const unsigned long long* mask;
     hipError_t e;
     if ((e = hipMemsetAsync(w.nfind, 0, sizeof(int) * (size_t)B, st)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(w.res, 0, sizeof(int) * (size_t)B * p.max_finders * RES_INTS, st)) != hipSuccess) return e;
-    if ((e = ink_mask_resolve(p.rgb, p.mask_in, p.mask_out, w.mask, B, H, W, p.threshold, st, &mask)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.res, 0, sizeof(int) * (size_t)B * p.max_finders * CODE_RES_INTS, st)) != hipSuccess) return e;
+    if ((e = components_launch(w.c, p.rgb, p.mask_in, p.mask_out, B, H, W, p.threshold, st)) != hipSuccess) return e;
+    const unsigned long long* mask = w.c.mask;
     const int rows = B * H;
-    const dim3 grows = row_wave_grid(rows);
-    run_count_launch(mask, w.runoff, B, H, nw, st);
-    row_scan_launch(w.runoff, nullptr, B, H, st);
-    run_fill_launch(mask, w.runoff, w.rxs, w.rxe, w.parent, w.box, B, H, nw, runcap, st);
-    run_merge_launch(w.runoff, w.rxs, w.rxe, w.parent, B, H, runcap, st);
-    hipLaunchKernelGGL(az_init_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.area, H, runcap, rows);
-    hipLaunchKernelGGL(az_accum_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.box, w.area, H, runcap, rows);
-    hipLaunchKernelGGL(az_finders_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.box, w.area, H, runcap, p.min_module, p.max_module,
-                       p.centre_tol, p.ring_tol, p.max_finders, w.nfind, w.finders, rows);
-    hipLaunchKernelGGL(az_decode_kernel, dim3(p.max_finders, B), dim3(64), 0, st, mask, w.finders, w.nfind, w.box, H, W, nw, runcap, p.max_finders, p.quiet,
+    hipLaunchKernelGGL(az_finders_kernel, row_wave_grid(rows), dim3(256), 0, st, w.c.runoff, w.c.rxs, w.c.rxe, w.c.parent, w.c.box, w.c.area, H, runcap,
+                       p.min_module, p.max_module, p.centre_tol, p.ring_tol, p.max_finders, w.nfind, w.finders, rows);
+    hipLaunchKernelGGL(az_decode_kernel, dim3(p.max_finders, B), dim3(64), 0, st, mask, w.finders, w.nfind, w.c.box, H, W, nw, runcap, p.max_finders, p.quiet,
                        p.mark_max, max_layers, stride, w.res, w.resdata);
     if (!data_all) {
         hipLaunchKernelGGL((az_output_kernel<int, AZ_MAX_DATA>), dim3(B), dim3(256), 0, st, w.res, w.resdata, w.nfind, p.max_finders, p.max_codes, w.tmp, p.counts,
@@ -700,7 +623,7 @@ static hipError_t aztec_run(const AztecParams& p, int max_layers, unsigned short
         return hipGetLastError();
     }
     if (max_layers > AZ_MAX_LAYERS)
-        hipLaunchKernelGGL(az_layers_kernel, dim3(p.max_finders, B), dim3(64), 0, st, mask, w.finders, w.nfind, w.box, H, W, nw, runcap, p.max_finders, p.quiet,
+        hipLaunchKernelGGL(az_layers_kernel, dim3(p.max_finders, B), dim3(64), 0, st, mask, w.finders, w.nfind, w.c.box, H, W, nw, runcap, p.max_finders, p.quiet,
                            max_layers, w.res, w.resdata);
     hipLaunchKernelGGL((az_output_kernel<unsigned short, AZ_MAX_DATA_ALL>), dim3(B), dim3(256), 0, st, w.res, w.resdata, w.nfind, p.max_finders, p.max_codes, w.tmp,
                        p.counts, p.codes, data_all, p.finder_counts);

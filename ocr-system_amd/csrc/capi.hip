@@ -84,6 +84,40 @@ template <class WS, class Body> static int for_page_groups(lumina_ocr* h, int n,
     return 0;
 }
 
+// What the five matrix-code entries share.  A page group's base pointers: rows of 12 ints, data rows of row_len elements of T, one count
+// and (optionally) one finder or candidate count a page, the masks [H][ceil(W / 64)] a page.
+template <class T> struct CodeGroup {
+    const uint8_t* rgb; int nb; int32_t* codes; T* data; int32_t* counts; int32_t* slot_counts; const unsigned long long* mask_in; unsigned long long* mask_out;
+    // the fields every reader's Params names alike
+    template <class P> void bind(P& p) const { p.rgb = rgb; p.B = nb; p.codes = codes; p.counts = counts; p.mask_in = mask_in; p.mask_out = mask_out; }
+};
+// The checks in their order (handle, no pages, pointers, the caller's parameter message: nullptr when they are fine, the sides), the
+// device, the page groups (ws(nb): the workspace of nb pages; the run list is sized for its worst case, 28 to 60 bytes per two pixels),
+// and per group launch(group, workspace, its capacity).
+template <class T, class WS, class Launch>
+static int matrix_codes(lumina_ocr_t* h, const char* what, const char* bad_params, const uint8_t* pages_dev, int n, int height, int width, int max_codes,
+                        int row_len, int32_t* codes_dev, T* data_dev, int32_t* counts_dev, int32_t* slot_counts_dev, const uint64_t* mask_in_dev,
+                        uint64_t* mask_out_dev, WS ws, Launch launch) {
+    if (!h) return 1;
+    if (n == 0) return 0;
+    if (!pages_dev || !codes_dev || !data_dev || !counts_dev || n < 0) return locr_fail(h, what, "bad arguments");
+    if (bad_params) return locr_fail(h, what, bad_params);
+    if (ws(1) == 0) return locr_fail(h, what, "bad dimensions (sides 1..65535)");
+    BIND(h);
+    API_TRY
+    const size_t nw = ((size_t)width + 63) / 64;
+    return for_page_groups(h, n, fit_group(h->post_group, n, ws), ws, [&](int b0, int nb) {
+        CodeGroup<T> g{};
+        g.rgb = pages_dev + (size_t)b0 * height * width * 3; g.nb = nb;
+        g.codes = codes_dev + (size_t)b0 * max_codes * 12; g.data = data_dev + (size_t)b0 * max_codes * row_len; g.counts = counts_dev + b0;
+        g.slot_counts = slot_counts_dev ? slot_counts_dev + b0 : nullptr;
+        g.mask_in = mask_in_dev ? reinterpret_cast<const unsigned long long*>(mask_in_dev) + (size_t)b0 * height * nw : nullptr;
+        g.mask_out = mask_out_dev ? reinterpret_cast<unsigned long long*>(mask_out_dev) + (size_t)b0 * height * nw : nullptr;
+        return hip_rc(h, what, launch(g, h->ws.get(), h->ws.cap));
+    });
+    API_CATCH(h)
+}
+
 extern "C" {
 
 const char* lumina_ocr_version(void) { return "lumina-ocr-mi355x 0.1 (gfx950)"; }
@@ -778,122 +812,87 @@ static QrCommon qr_common(int height, int width, int threshold, int min_module, 
 int lumina_ocr_qrcodes(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module, int max_module, int quiet,
                        int centre_tol, int ring_tol, int timing_max, int max_finders, int max_codes, int32_t* codes_dev, int32_t* data_dev, int32_t* counts_dev,
                        int32_t* finder_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream) {
-    if (!h) return 1;
-    if (n == 0) return 0;
-    if (!pages_dev || !codes_dev || !data_dev || !counts_dev || n < 0) return locr_fail(h, "qrcodes", "bad arguments");
     const QrCommon c = qr_common(height, width, threshold, min_module, max_module, quiet, centre_tol, ring_tol, timing_max, max_finders, max_codes);
-    if (!qr_params_ok(c))
-        return locr_fail(h, "qrcodes", "parameters must satisfy 1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= centre_tol, ring_tol <= 64, "
-                                       "0 <= timing_max <= 128, max_finders 1..64, max_codes 1..64");
-    if (qrcodes_workspace_bytes(1, height, width, max_finders, max_codes) == 0) return locr_fail(h, "qrcodes", "bad dimensions (sides 1..65535)");
-    BIND(h);
-    API_TRY
-    // the run list is sized for its worst case (28 bytes per two pixels)
-    const auto ws = [&](int nb) { return qrcodes_workspace_bytes(nb, height, width, max_finders, max_codes); };
-    const size_t nw = ((size_t)width + 63) / 64;
-    return for_page_groups(h, n, fit_group(h->post_group, n, ws), ws, [&](int b0, int nb) {
-        QrParams p{};
-        static_cast<QrCommon&>(p) = c;
-        p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb;
-        p.codes = codes_dev + (size_t)b0 * max_codes * 12; p.data = data_dev + (size_t)b0 * max_codes * QR_MAX_DATA; p.counts = counts_dev + b0;
-        p.finder_counts = finder_counts_dev ? finder_counts_dev + b0 : nullptr;
-        p.mask_in = mask_in_dev ? reinterpret_cast<const unsigned long long*>(mask_in_dev) + (size_t)b0 * height * nw : nullptr;
-        p.mask_out = mask_out_dev ? reinterpret_cast<unsigned long long*>(mask_out_dev) + (size_t)b0 * height * nw : nullptr;
-        return hip_rc(h, "qrcodes", qrcodes_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
-    });
-    API_CATCH(h)
+    const char* bad = qr_params_ok(c) ? nullptr
+                                      : "parameters must satisfy 1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= centre_tol, ring_tol <= 64, "
+                                        "0 <= timing_max <= 128, max_finders 1..64, max_codes 1..64";
+    return matrix_codes(
+        h, "qrcodes", bad, pages_dev, n, height, width, max_codes, QR_MAX_DATA, codes_dev, data_dev, counts_dev, finder_counts_dev, mask_in_dev, mask_out_dev,
+        [&](int nb) { return qrcodes_workspace_bytes(nb, height, width, max_finders, max_codes); },
+        [&](const CodeGroup<int32_t>& g, void* ws, size_t cap) {
+            QrParams p{};
+            static_cast<QrCommon&>(p) = c;
+            g.bind(p); p.data = g.data; p.finder_counts = g.slot_counts;
+            return qrcodes_launch(p, ws, cap, (hipStream_t)stream);
+        });
 }
 
 int lumina_ocr_qrcodes_versions(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module, int max_module,
                                 int quiet, int centre_tol, int ring_tol, int timing_max, int max_finders, int max_codes, int max_version, int32_t* codes_dev,
                                 uint8_t* data_dev, int32_t* counts_dev, int32_t* finder_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev,
                                 void* stream) {
-    if (!h) return 1;
-    if (n == 0) return 0;
-    if (!pages_dev || !codes_dev || !data_dev || !counts_dev || n < 0) return locr_fail(h, "qrcodes_versions", "bad arguments");
     const QrCommon c = qr_common(height, width, threshold, min_module, max_module, quiet, centre_tol, ring_tol, timing_max, max_finders, max_codes);
-    if (!qr_params_ok(c) || !qr_max_version_ok(max_version))
-        return locr_fail(h, "qrcodes_versions", "parameters must satisfy 1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= centre_tol, ring_tol <= 64, "
-                                                "0 <= timing_max <= 128, max_finders 1..64, max_codes 1..64, max_version 10..40");
-    if (qrcodes_versions_workspace_bytes(1, height, width, max_finders, max_codes) == 0)
-        return locr_fail(h, "qrcodes_versions", "bad dimensions (sides 1..65535)");
-    BIND(h);
-    API_TRY
-    const auto ws = [&](int nb) { return qrcodes_versions_workspace_bytes(nb, height, width, max_finders, max_codes); };
-    const size_t nw = ((size_t)width + 63) / 64;
-    return for_page_groups(h, n, fit_group(h->post_group, n, ws), ws, [&](int b0, int nb) {
-        QrVersionsParams p{};
-        static_cast<QrCommon&>(p) = c;
-        p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.max_version = max_version;
-        p.codes = codes_dev + (size_t)b0 * max_codes * 12; p.data = data_dev + (size_t)b0 * max_codes * QR_VERSIONS_MAX_DATA; p.counts = counts_dev + b0;
-        p.finder_counts = finder_counts_dev ? finder_counts_dev + b0 : nullptr;
-        p.mask_in = mask_in_dev ? reinterpret_cast<const unsigned long long*>(mask_in_dev) + (size_t)b0 * height * nw : nullptr;
-        p.mask_out = mask_out_dev ? reinterpret_cast<unsigned long long*>(mask_out_dev) + (size_t)b0 * height * nw : nullptr;
-        return hip_rc(h, "qrcodes_versions", qrcodes_versions_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
-    });
-    API_CATCH(h)
+    const char* bad = qr_params_ok(c) && qr_max_version_ok(max_version)
+                          ? nullptr
+                          : "parameters must satisfy 1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= centre_tol, ring_tol <= 64, "
+                            "0 <= timing_max <= 128, max_finders 1..64, max_codes 1..64, max_version 10..40";
+    return matrix_codes(
+        h, "qrcodes_versions", bad, pages_dev, n, height, width, max_codes, QR_VERSIONS_MAX_DATA, codes_dev, data_dev, counts_dev, finder_counts_dev, mask_in_dev,
+        mask_out_dev, [&](int nb) { return qrcodes_versions_workspace_bytes(nb, height, width, max_finders, max_codes); },
+        [&](const CodeGroup<uint8_t>& g, void* ws, size_t cap) {
+            QrVersionsParams p{};
+            static_cast<QrCommon&>(p) = c;
+            g.bind(p); p.data = g.data; p.finder_counts = g.slot_counts; p.max_version = max_version;
+            return qrcodes_versions_launch(p, ws, cap, (hipStream_t)stream);
+        });
 }
 
 int lumina_ocr_datamatrix(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module, int max_module, int quiet,
                           int timing_max, int solid_max, int max_candidates, int max_codes, int32_t* codes_dev, int32_t* data_dev, int32_t* counts_dev,
                           int32_t* candidate_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream) {
-    if (!h) return 1;
-    if (n == 0) return 0;
-    if (!pages_dev || !codes_dev || !data_dev || !counts_dev || n < 0) return locr_fail(h, "datamatrix", "bad arguments");
-    if (!dm_params_ok(min_module, max_module, quiet, timing_max, solid_max, max_candidates, max_codes))
-        return locr_fail(h, "datamatrix", "parameters must satisfy 1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= timing_max, solid_max <= 128, "
-                                          "max_candidates 1..1024, max_codes 1..64");
-    if (datamatrix_workspace_bytes(1, height, width, max_candidates, max_codes) == 0) return locr_fail(h, "datamatrix", "bad dimensions (sides 1..65535)");
-    BIND(h);
-    API_TRY
-    // the run list is sized for its worst case (60 bytes per two pixels)
-    const auto ws = [&](int nb) { return datamatrix_workspace_bytes(nb, height, width, max_candidates, max_codes); };
-    const size_t nw = ((size_t)width + 63) / 64;
-    return for_page_groups(h, n, fit_group(h->post_group, n, ws), ws, [&](int b0, int nb) {
-        DmParams p{};
-        p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.H = height; p.W = width;
-        p.threshold = threshold; p.min_module = min_module; p.max_module = max_module; p.quiet = quiet; p.timing_max = timing_max; p.solid_max = solid_max;
-        p.max_candidates = max_candidates; p.max_codes = max_codes;
-        p.codes = codes_dev + (size_t)b0 * max_codes * 12; p.data = data_dev + (size_t)b0 * max_codes * DM_MAX_DATA; p.counts = counts_dev + b0;
-        p.candidate_counts = candidate_counts_dev ? candidate_counts_dev + b0 : nullptr;
-        p.mask_in = mask_in_dev ? reinterpret_cast<const unsigned long long*>(mask_in_dev) + (size_t)b0 * height * nw : nullptr;
-        p.mask_out = mask_out_dev ? reinterpret_cast<unsigned long long*>(mask_out_dev) + (size_t)b0 * height * nw : nullptr;
-        return hip_rc(h, "datamatrix", datamatrix_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
-    });
-    API_CATCH(h)
+    const char* bad = dm_params_ok(min_module, max_module, quiet, timing_max, solid_max, max_candidates, max_codes)
+                          ? nullptr
+                          : "parameters must satisfy 1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= timing_max, solid_max <= 128, "
+                            "max_candidates 1..1024, max_codes 1..64";
+    return matrix_codes(
+        h, "datamatrix", bad, pages_dev, n, height, width, max_codes, DM_MAX_DATA, codes_dev, data_dev, counts_dev, candidate_counts_dev, mask_in_dev, mask_out_dev,
+        [&](int nb) { return datamatrix_workspace_bytes(nb, height, width, max_candidates, max_codes); },
+        [&](const CodeGroup<int32_t>& g, void* ws, size_t cap) {
+            DmParams p{};
+            g.bind(p); p.data = g.data; p.candidate_counts = g.slot_counts; p.H = height; p.W = width;
+            p.threshold = threshold; p.min_module = min_module; p.max_module = max_module; p.quiet = quiet; p.timing_max = timing_max; p.solid_max = solid_max;
+            p.max_candidates = max_candidates; p.max_codes = max_codes;
+            return datamatrix_launch(p, ws, cap, (hipStream_t)stream);
+        });
 }
 
 size_t lumina_ocr_aztec_workspace_bytes(int n, int height, int width, int max_finders, int max_codes) {
     return n > 0 ? aztec_workspace_bytes(n, height, width, max_finders, max_codes) : 0;
 }
 
+// the scalar parameters both Aztec calls take
+static void aztec_common(AztecParams& p, int height, int width, int threshold, int min_module, int max_module, int quiet, int centre_tol, int ring_tol,
+                         int mark_max, int max_finders, int max_codes) {
+    p.H = height; p.W = width; p.threshold = threshold; p.min_module = min_module; p.max_module = max_module; p.quiet = quiet; p.centre_tol = centre_tol;
+    p.ring_tol = ring_tol; p.mark_max = mark_max; p.max_finders = max_finders; p.max_codes = max_codes;
+}
+
 int lumina_ocr_aztec(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module, int max_module, int quiet,
                      int centre_tol, int ring_tol, int mark_max, int max_finders, int max_codes, int32_t* codes_dev, int32_t* data_dev, int32_t* counts_dev,
                      int32_t* finder_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream) {
-    if (!h) return 1;
-    if (n == 0) return 0;
-    if (!pages_dev || !codes_dev || !data_dev || !counts_dev || n < 0) return locr_fail(h, "aztec", "bad arguments");
-    if (!aztec_params_ok(min_module, max_module, quiet, centre_tol, ring_tol, mark_max, max_finders, max_codes))
-        return locr_fail(h, "aztec", "parameters must satisfy 1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= centre_tol <= 64, 0 <= ring_tol <= 15, "
-                                     "0 <= mark_max <= 64, max_finders 1..64, max_codes 1..64");
-    if (aztec_workspace_bytes(1, height, width, max_finders, max_codes) == 0) return locr_fail(h, "aztec", "bad dimensions (sides 1..65535)");
-    BIND(h);
-    API_TRY
-    // the run list is sized for its worst case (28 bytes per two pixels)
-    const auto ws = [&](int nb) { return aztec_workspace_bytes(nb, height, width, max_finders, max_codes); };
-    const size_t nw = ((size_t)width + 63) / 64;
-    return for_page_groups(h, n, fit_group(h->post_group, n, ws), ws, [&](int b0, int nb) {
-        AztecParams p{};
-        p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.H = height; p.W = width;
-        p.threshold = threshold; p.min_module = min_module; p.max_module = max_module; p.quiet = quiet; p.centre_tol = centre_tol; p.ring_tol = ring_tol;
-        p.mark_max = mark_max; p.max_finders = max_finders; p.max_codes = max_codes;
-        p.codes = codes_dev + (size_t)b0 * max_codes * 12; p.data = data_dev + (size_t)b0 * max_codes * AZ_MAX_DATA; p.counts = counts_dev + b0;
-        p.finder_counts = finder_counts_dev ? finder_counts_dev + b0 : nullptr;
-        p.mask_in = mask_in_dev ? reinterpret_cast<const unsigned long long*>(mask_in_dev) + (size_t)b0 * height * nw : nullptr;
-        p.mask_out = mask_out_dev ? reinterpret_cast<unsigned long long*>(mask_out_dev) + (size_t)b0 * height * nw : nullptr;
-        return hip_rc(h, "aztec", aztec_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
-    });
-    API_CATCH(h)
+    const char* bad = aztec_params_ok(min_module, max_module, quiet, centre_tol, ring_tol, mark_max, max_finders, max_codes)
+                          ? nullptr
+                          : "parameters must satisfy 1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= centre_tol <= 64, 0 <= ring_tol <= 15, "
+                            "0 <= mark_max <= 64, max_finders 1..64, max_codes 1..64";
+    return matrix_codes(
+        h, "aztec", bad, pages_dev, n, height, width, max_codes, AZ_MAX_DATA, codes_dev, data_dev, counts_dev, finder_counts_dev, mask_in_dev, mask_out_dev,
+        [&](int nb) { return aztec_workspace_bytes(nb, height, width, max_finders, max_codes); },
+        [&](const CodeGroup<int32_t>& g, void* ws, size_t cap) {
+            AztecParams p{};
+            aztec_common(p, height, width, threshold, min_module, max_module, quiet, centre_tol, ring_tol, mark_max, max_finders, max_codes);
+            g.bind(p); p.data = g.data; p.finder_counts = g.slot_counts;
+            return aztec_launch(p, ws, cap, (hipStream_t)stream);
+        });
 }
 
 size_t lumina_ocr_aztec_layers_workspace_bytes(int n, int height, int width, int max_finders, int max_codes) {
@@ -903,29 +902,19 @@ size_t lumina_ocr_aztec_layers_workspace_bytes(int n, int height, int width, int
 int lumina_ocr_aztec_layers(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module, int max_module, int quiet,
                             int centre_tol, int ring_tol, int mark_max, int max_finders, int max_codes, int max_layers, int32_t* codes_dev, uint16_t* data_dev,
                             int32_t* counts_dev, int32_t* finder_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream) {
-    if (!h) return 1;
-    if (n == 0) return 0;
-    if (!pages_dev || !codes_dev || !data_dev || !counts_dev || n < 0) return locr_fail(h, "aztec_layers", "bad arguments");
-    if (!aztec_params_ok(min_module, max_module, quiet, centre_tol, ring_tol, mark_max, max_finders, max_codes) || !aztec_max_layers_ok(max_layers))
-        return locr_fail(h, "aztec_layers", "parameters must satisfy 1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= centre_tol <= 64, "
-                                            "0 <= ring_tol <= 15, 0 <= mark_max <= 64, max_finders 1..64, max_codes 1..64, max_layers 11..32");
-    if (aztec_layers_workspace_bytes(1, height, width, max_finders, max_codes) == 0) return locr_fail(h, "aztec_layers", "bad dimensions (sides 1..65535)");
-    BIND(h);
-    API_TRY
-    const auto ws = [&](int nb) { return aztec_layers_workspace_bytes(nb, height, width, max_finders, max_codes); };
-    const size_t nw = ((size_t)width + 63) / 64;
-    return for_page_groups(h, n, fit_group(h->post_group, n, ws), ws, [&](int b0, int nb) {
-        AztecLayersParams p{};
-        p.rgb = pages_dev + (size_t)b0 * height * width * 3; p.B = nb; p.H = height; p.W = width;
-        p.threshold = threshold; p.min_module = min_module; p.max_module = max_module; p.quiet = quiet; p.centre_tol = centre_tol; p.ring_tol = ring_tol;
-        p.mark_max = mark_max; p.max_finders = max_finders; p.max_codes = max_codes; p.max_layers = max_layers;
-        p.codes = codes_dev + (size_t)b0 * max_codes * 12; p.data_all = data_dev + (size_t)b0 * max_codes * AZ_MAX_DATA_ALL; p.counts = counts_dev + b0;
-        p.finder_counts = finder_counts_dev ? finder_counts_dev + b0 : nullptr;
-        p.mask_in = mask_in_dev ? reinterpret_cast<const unsigned long long*>(mask_in_dev) + (size_t)b0 * height * nw : nullptr;
-        p.mask_out = mask_out_dev ? reinterpret_cast<unsigned long long*>(mask_out_dev) + (size_t)b0 * height * nw : nullptr;
-        return hip_rc(h, "aztec_layers", aztec_layers_launch(p, h->ws.get(), h->ws.cap, (hipStream_t)stream));
-    });
-    API_CATCH(h)
+    const char* bad = aztec_params_ok(min_module, max_module, quiet, centre_tol, ring_tol, mark_max, max_finders, max_codes) && aztec_max_layers_ok(max_layers)
+                          ? nullptr
+                          : "parameters must satisfy 1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= centre_tol <= 64, "
+                            "0 <= ring_tol <= 15, 0 <= mark_max <= 64, max_finders 1..64, max_codes 1..64, max_layers 11..32";
+    return matrix_codes(
+        h, "aztec_layers", bad, pages_dev, n, height, width, max_codes, AZ_MAX_DATA_ALL, codes_dev, data_dev, counts_dev, finder_counts_dev, mask_in_dev,
+        mask_out_dev, [&](int nb) { return aztec_layers_workspace_bytes(nb, height, width, max_finders, max_codes); },
+        [&](const CodeGroup<uint16_t>& g, void* ws, size_t cap) {
+            AztecLayersParams p{};
+            aztec_common(p, height, width, threshold, min_module, max_module, quiet, centre_tol, ring_tol, mark_max, max_finders, max_codes);
+            g.bind(p); p.data_all = g.data; p.finder_counts = g.slot_counts; p.max_layers = max_layers;
+            return aztec_layers_launch(p, ws, cap, (hipStream_t)stream);
+        });
 }
 
 size_t lumina_ocr_page_quarter_workspace_bytes(int n, int height, int width) { return n > 0 ? quarter_workspace_bytes(n, height, width) : 0; }

@@ -4,21 +4,20 @@
 // definition restated in tests/dm_reference.py.
 //
 // All stream-ordered kernels, no host round trip:
-//   1 ink_mask                          the mask (or the one the caller already has)
-//   2 run_count / row_scan / run_fill / run_merge   mask words -> run list and its 8-connected components (the shared kernels of runs.hip)
-//   3 dm_init, dm_accum   a run is its own area and its own four diagonal extremes (min x + y, max x - y, max x + y, min x - y, ties by
-//                 the smaller y: one 64-bit word (key, y, x) each, so that one atomic min / max keeps the tie rule exact); every run
-//                 learns its root, and box, area and extremes are accumulated there
+//   1-3 components_launch (runs.h)      the mask (or the one the caller already has), its run list, the 8-connected components; a run is
+//                 its own area and its own four diagonal extremes (run_extremes); every run learns its root, and box, area and
+//                 extremes are accumulated there
 //   4 dm_candidates  one wave per row, lanes over the row's roots: the box and area filter -> counted, gathered per page
 //   5 dm_decode   one wave per (page, candidate): every (size, rotation) try that is in reach (wave-uniform) is scored with lanes
 //                 over the modules of its solid and clock rows and columns; for the kept try lane r samples module row r on the
 //                 affine grid as one 64-bit word; the quiet rings; lanes gather the codewords through the placement table from the
-//                 rows in LDS; per block the decoder of rs_gf256.h.  Every loop has a constant bound, every table, LDS and page index
+//                 rows in LDS; per block the decoder of rs.h.  Every loop has a constant bound, every table, LDS and page index
 //                 is clamped, and no wave waits for another (a work-group is one wave)
-//   6 dm_output   one work-group per page: valid candidates counted, gathered, rank-sorted by (y0, x0, y1, x1, root)
+//   6 dm_output   one work-group per page (code_output.h): valid candidates counted, gathered, rank-sorted by (y0, x0, y1, x1, root)
 #include "datamatrix.h"
+#include "code_output.h"
 #include "dm_tables.h"
-#include "rs_gf256.h"
+#include "rs.h"
 #include "runs.h"
 
 namespace {
@@ -26,56 +25,9 @@ namespace {
 typedef unsigned long long u64;
 typedef long long i64;
 
-constexpr int RES_INTS = 16;           // a candidate's result: y0, x0, y1, x1, root, rows, cols, ndata, errors, rotation, timing, misses, 0, valid
+// a candidate's result (code_output.h): y0, x0, y1, x1, root, rows, cols, ndata, errors, rotation, timing, misses, 0, state
 constexpr int DM_MAX_TOTAL = 288, DM_MAX_BLOCK = 242, DM_MAX_EC = 68, DM_MAX_NB = 2;
 constexpr int DM_RAW = 320, DM_BLK = 256;   // LDS arrays: the codewords of a symbol, of a block (multiples of 64)
-
-// the four extremes of one run as packed words: min types hold y, max types 65535 - y below the key, so ties go to the smaller y
-__device__ __forceinline__ void run_extremes(int xs, int xe, int y, u64 (&e)[4]) {
-    e[0] = ((u64)(unsigned)(xs + y) << 32) | ((u64)y << 16) | (u64)xs;
-    e[1] = ((u64)(unsigned)(xe - y + 65536) << 32) | ((u64)(65535 - y) << 16) | (u64)xe;
-    e[2] = ((u64)(unsigned)(xe + y) << 32) | ((u64)(65535 - y) << 16) | (u64)xe;
-    e[3] = ((u64)(unsigned)(xs - y + 65536) << 32) | ((u64)y << 16) | (u64)xs;
-}
-
-// 3a: a run's own length and extremes are the start of its component's
-__global__ __launch_bounds__(256) void dm_init_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* area, u64* ext, int H,
-                                                      size_t runcap, int rows_total) {
-    int pg, row, lane;
-    if (!row_wave(H, rows_total, pg, row, lane)) return;
-    const int* ro = runoff + (size_t)pg * (H + 1);
-    const size_t rb = (size_t)pg * runcap;
-    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
-        const int xs = rxs[rb + id], xe = rxe[rb + id];
-        area[rb + id] = xe - xs + 1;
-        u64 e[4];
-        run_extremes(xs, xe, row, e);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ext[(rb + id) * 4 + j] = e[j];
-    }
-}
-
-// 3b: parent = root; the root's box, area and extremes grow to the component's
-__global__ __launch_bounds__(256) void dm_accum_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* parent, int4* box, int* area,
-                                                       u64* ext, int H, size_t runcap, int rows_total) {
-    int pg, row, lane;
-    if (!row_wave(H, rows_total, pg, row, lane)) return;
-    const int* ro = runoff + (size_t)pg * (H + 1);
-    const size_t rb = (size_t)pg * runcap;
-    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
-        int xs, xe;
-        const int root = run_join_root(parent + rb, rxs + rb, rxe + rb, box + rb, id, row, xs, xe);
-        if (root < 0) continue;
-        atomicAdd(area + rb + root, xe - xs + 1);
-        u64 e[4];
-        run_extremes(xs, xe, row, e);
-        u64* x = ext + (rb + root) * 4;
-        if (e[0] < __atomic_load_n(x + 0, __ATOMIC_RELAXED)) atomicMin(x + 0, e[0]);
-        if (e[1] > __atomic_load_n(x + 1, __ATOMIC_RELAXED)) atomicMax(x + 1, e[1]);
-        if (e[2] > __atomic_load_n(x + 2, __ATOMIC_RELAXED)) atomicMax(x + 2, e[2]);
-        if (e[3] < __atomic_load_n(x + 3, __ATOMIC_RELAXED)) atomicMin(x + 3, e[3]);
-    }
-}
 
 // 4: cands [B][max_candidates] = the roots that pass the box and area filter
 __global__ __launch_bounds__(256) void dm_candidates_kernel(const int* runoff, const int* parent, const int4* box, const int* area, int H, size_t runcap,
@@ -111,10 +63,10 @@ __device__ __forceinline__ int dm_sample(const u64* mpage, int H, int W, int nw,
 struct DmLds {
     u64 rows[64];
     unsigned char raw[DM_RAW];
-    RsLds<DM_BLK, DM_MAX_EC> rs;
+    RsLds<unsigned char, DM_BLK, DM_MAX_EC, 8> rs;
 };
 
-// 5: one wave per (page, candidate): res [B][max_candidates][RES_INTS], resdata [B][max_candidates][DM_MAX_DATA]
+// 5: one wave per (page, candidate): res [B][max_candidates][CODE_RES_INTS], resdata [B][max_candidates][DM_MAX_DATA]
 __global__ __launch_bounds__(64) void dm_decode_kernel(const u64* mask, const int* cands, const int* ncand, const u64* ext, int H, int W, int nw, size_t runcap,
                                                        int max_candidates, int min_module, int max_module, int quiet, int timing_max, int solid_max, int* res,
                                                        unsigned char* resdata) {
@@ -124,7 +76,7 @@ __global__ __launch_bounds__(64) void dm_decode_kernel(const u64* mask, const in
     if (nc_page > max_candidates || a >= nc_page || a >= DM_MAX_CANDIDATES) return;
     const u64* mpage = mask + (size_t)pg * H * nw;
     const int root = clampi(cands[(size_t)pg * max_candidates + a], 0, (int)runcap - 1);
-    rs_load_tables(s.rs, DM_EXP, DM_LOG, lane);
+    rs_load_tables(s.rs, DM_EXP, DM_LOG, 8, lane);
     // the outer corners of the four extremes, doubled
     int cx[4], cy[4];
 #pragma unroll
@@ -249,83 +201,47 @@ __global__ __launch_bounds__(64) void dm_decode_kernel(const u64* mask, const in
             x0 = c == 0 || qx < x0 ? qx : x0; x1 = c == 0 || qx > x1 ? qx : x1;
             y0 = c == 0 || qy < y0 ? qy : y0; y1 = c == 0 || qy > y1 ? qy : y1;
         }
-        int* o = res + ((size_t)pg * max_candidates + a) * RES_INTS;
+        int* o = res + ((size_t)pg * max_candidates + a) * CODE_RES_INTS;
         o[0] = clampi(y0, 0, H - 1); o[1] = clampi(x0, 0, W - 1); o[2] = clampi(y1 - 1, 0, H - 1); o[3] = clampi(x1 - 1, 0, W - 1); o[4] = root;
-        o[5] = R; o[6] = C; o[7] = ndata; o[8] = errors; o[9] = k; o[10] = timing; o[11] = misses; o[12] = 0; o[13] = 1;
+        o[5] = R; o[6] = C; o[7] = ndata; o[8] = errors; o[9] = k; o[10] = timing; o[11] = misses; o[12] = 0; o[CODE_RES_STATE] = CODE_ROW;
     }
 }
 
 // 6: tmp [B][max_codes][6] = y0, x0, y1, x1, root, slot
 __global__ __launch_bounds__(256) void dm_output_kernel(const int* res_all, const unsigned char* resdata_all, const int* ncand, int max_candidates, int max_codes,
                                                         int* tmp_all, int* counts, int* codes, int* data, int* candidate_counts) {
-    __shared__ int s_key[DM_MAX_CODES * 5];
-    __shared__ int s_n;
+    __shared__ CodeOutLds<DM_MAX_CODES> s;
     const int pg = blockIdx.x;
-    const int nc = ncand[pg];
-    const int* res = res_all + (size_t)pg * max_candidates * RES_INTS;
-    int* tmp = tmp_all + (size_t)pg * max_codes * 6;
-    if (threadIdx.x == 0) {
-        s_n = 0;
-        if (candidate_counts) candidate_counts[pg] = nc;
-    }
-    __syncthreads();
-    const int lim = nc > max_candidates ? 0 : nc;   // a page with too many candidates is not read
-    for (int a = threadIdx.x; a < lim; a += 256) {
-        const int* r = res + a * RES_INTS;
-        if (r[13] != 1) continue;
-        const int idx = atomicAdd(&s_n, 1);
-        if (idx >= max_codes) continue;
-        int* o = tmp + idx * 6;
-        o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3]; o[4] = r[4]; o[5] = a;
-    }
-    __syncthreads();
-    const int n = s_n;
-    if (threadIdx.x == 0) counts[pg] = n;
-    if (n > max_codes) return;   // overflow: the count is all that is reported
-    int* out = codes + (size_t)pg * max_codes * 12;
-    int* odat = data + (size_t)pg * max_codes * DM_MAX_DATA;
+    const int* res = res_all + (size_t)pg * max_candidates * CODE_RES_INTS;
+    const int n = code_output_rows(s, res, ncand[pg], max_candidates, max_codes, tmp_all + (size_t)pg * max_codes * 6, codes + (size_t)pg * max_codes * 12,
+                                   counts + pg, candidate_counts ? candidate_counts + pg : nullptr);
+    if (n > max_codes) return;
     const unsigned char* rd = resdata_all + (size_t)pg * max_candidates * DM_MAX_DATA;
-    rank_sort<5>(s_key, tmp, 6, n, [=](int i, int rank, const int (&k)[5]) {
-        const int slot = clampi(tmp[i * 6 + 5], 0, max_candidates - 1);
-        const int* r = res + slot * RES_INTS;
-        int* o = out + (size_t)rank * 12;
-        o[0] = k[1]; o[1] = k[0]; o[2] = k[3]; o[3] = k[2];
-        for (int j = 0; j < 8; ++j) o[4 + j] = r[5 + j];
-        const int nd = r[7];
-        for (int j = 0; j < DM_MAX_DATA; ++j) odat[(size_t)rank * DM_MAX_DATA + j] = j < nd ? rd[(size_t)slot * DM_MAX_DATA + j] : 0;
-    });
+    code_output_data(s, n, max_candidates, DM_MAX_DATA, data + (size_t)pg * max_codes * DM_MAX_DATA,
+                     [=](int slot, int j) -> int { return j < res[slot * CODE_RES_INTS + 7] ? rd[(size_t)slot * DM_MAX_DATA + j] : 0; });
 }
 
 }  // namespace
 
 // the workspace's regions: one layout sizes it (datamatrix_workspace_bytes) and carves it (datamatrix_launch)
 struct DmWorkspace {
-    unsigned long long* mask; int* runoff; unsigned short *rxs, *rxe; int* parent; int4* box; int* area; unsigned long long* ext;
+    Components c;   // c.ext: at a root, its component's four diagonal extremes, packed
     int* ncand; int* cands; int* res; unsigned char* resdata; int* tmp;
 };
 static DmWorkspace datamatrix_layout(Arena& a, int B, int H, int W, int max_candidates, int max_codes) {
-    const size_t runcap = run_cap(H, W), nw = (W + 63) / 64;
     DmWorkspace w;
-    w.mask = a.take<unsigned long long>((size_t)B * H * nw);
-    w.runoff = a.take<int>((size_t)B * (H + 1));   // run counts -> offsets
-    w.rxs = a.take<unsigned short>((size_t)B * runcap); w.rxe = a.take<unsigned short>((size_t)B * runcap);
-    w.parent = a.take<int>((size_t)B * runcap);
-    w.box = a.take<int4>((size_t)B * runcap);      // at a root: x0, x1, y0, y1 of its component
-    w.area = a.take<int>((size_t)B * runcap);      // at a root: its component's ink
-    w.ext = a.take<unsigned long long>((size_t)B * runcap * 4);   // at a root: its component's four diagonal extremes, packed
+    w.c = components_layout(a, B, H, W, true);
+    w.c.ext = a.take<unsigned long long>((size_t)B * run_cap(H, W) * 4);
     w.ncand = a.take<int>((size_t)B);
     w.cands = a.take<int>((size_t)B * max_candidates);
-    w.res = a.take<int>((size_t)B * max_candidates * RES_INTS);
+    w.res = a.take<int>((size_t)B * max_candidates * CODE_RES_INTS);
     w.resdata = a.take<unsigned char>((size_t)B * max_candidates * DM_MAX_DATA);
     w.tmp = a.take<int>((size_t)B * max_codes * 6);
     return w;
 }
 
 static bool datamatrix_args_ok(int B, int H, int W, int max_candidates, int max_codes) {
-    if (B <= 0 || H <= 0 || W <= 0 || H > 65535 || W > 65535 || max_codes < 1 || max_codes > DM_MAX_CODES || max_candidates < 1 ||
-        max_candidates > DM_MAX_CANDIDATES)
-        return false;
-    return (size_t)B * H < (1ull << 31) && run_cap(H, W) < (1ull << 31);
+    return page_args_ok(B, H, W) && max_codes >= 1 && max_codes <= DM_MAX_CODES && max_candidates >= 1 && max_candidates <= DM_MAX_CANDIDATES;
 }
 
 bool dm_params_ok(int min_module, int max_module, int quiet, int timing_max, int solid_max, int max_candidates, int max_codes) {
@@ -348,26 +264,18 @@ hipError_t datamatrix_launch(const DmParams& p, void* workspace, size_t ws_bytes
         return hipErrorInvalidValue;
     if (!p.rgb || !p.codes || !p.data || !p.counts) return hipErrorInvalidValue;
     Arena a(workspace, ws_bytes);
-    const DmWorkspace w = datamatrix_layout(a, B, H, W, p.max_candidates, p.max_codes);
+    DmWorkspace w = datamatrix_layout(a, B, H, W, p.max_candidates, p.max_codes);
     if (a.overflow) return hipErrorOutOfMemory;
     const int nw = (W + 63) / 64;
     const size_t runcap = run_cap(H, W);
-    const unsigned long long* mask;
     hipError_t e;
     if ((e = hipMemsetAsync(w.ncand, 0, sizeof(int) * (size_t)B, st)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(w.res, 0, sizeof(int) * (size_t)B * p.max_candidates * RES_INTS, st)) != hipSuccess) return e;
-    if ((e = ink_mask_resolve(p.rgb, p.mask_in, p.mask_out, w.mask, B, H, W, p.threshold, st, &mask)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.res, 0, sizeof(int) * (size_t)B * p.max_candidates * CODE_RES_INTS, st)) != hipSuccess) return e;
+    if ((e = components_launch(w.c, p.rgb, p.mask_in, p.mask_out, B, H, W, p.threshold, st)) != hipSuccess) return e;
     const int rows = B * H;
-    const dim3 grows = row_wave_grid(rows);
-    run_count_launch(mask, w.runoff, B, H, nw, st);
-    row_scan_launch(w.runoff, nullptr, B, H, st);
-    run_fill_launch(mask, w.runoff, w.rxs, w.rxe, w.parent, w.box, B, H, nw, runcap, st);
-    run_merge_launch(w.runoff, w.rxs, w.rxe, w.parent, B, H, runcap, st);
-    hipLaunchKernelGGL(dm_init_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.area, w.ext, H, runcap, rows);
-    hipLaunchKernelGGL(dm_accum_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.box, w.area, w.ext, H, runcap, rows);
-    hipLaunchKernelGGL(dm_candidates_kernel, grows, dim3(256), 0, st, w.runoff, w.parent, w.box, w.area, H, runcap, p.min_module, p.max_module,
+    hipLaunchKernelGGL(dm_candidates_kernel, row_wave_grid(rows), dim3(256), 0, st, w.c.runoff, w.c.parent, w.c.box, w.c.area, H, runcap, p.min_module, p.max_module,
                        p.max_candidates, w.ncand, w.cands, rows);
-    hipLaunchKernelGGL(dm_decode_kernel, dim3(p.max_candidates, B), dim3(64), 0, st, mask, w.cands, w.ncand, w.ext, H, W, nw, runcap, p.max_candidates,
+    hipLaunchKernelGGL(dm_decode_kernel, dim3(p.max_candidates, B), dim3(64), 0, st, w.c.mask, w.cands, w.ncand, w.c.ext, H, W, nw, runcap, p.max_candidates,
                        p.min_module, p.max_module, p.quiet, p.timing_max, p.solid_max, w.res, w.resdata);
     hipLaunchKernelGGL(dm_output_kernel, dim3(B), dim3(256), 0, st, w.res, w.resdata, w.ncand, p.max_candidates, p.max_codes, w.tmp, p.counts, p.codes, p.data,
                        p.candidate_counts);

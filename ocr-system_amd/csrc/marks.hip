@@ -4,14 +4,14 @@
 //
 // A box side (14-60 pixels at 200 dpi) is shorter than any rule, so the fixed run slots of tables.hip do not apply: marks need the
 // connected components of ALL ink.  A row of a page is a list of runs (a text page: ~100 per row), in raster order, and everything
-// up to the candidates works on that list, as dbpost.hip does for the probability map: steps 1-3 are the shared kernels of runs.hip.
+// up to the candidates works on that list, as dbpost.hip does for the probability map: steps 1-4 are components_launch of runs.h.
 //
 // All stream-ordered kernels, no host round trip; kernels 2-5 are one wave per (page, row), four rows per work-group:
 //   1 ink_mask    ink = L < threshold packed into 64-bit words along x — or the mask the caller already has
 //   2 run_count / row_scan / run_fill   mask words -> run list [xs, xe] of the page in raster order; a run is its own parent and box
 //   3 run_merge   union-find (atomicMin) over run ids: a run joins the runs of the row above it touches (8-connectivity); the root
 //                 of a component is its first run in raster order
-//   4 mk_accum    every run learns its root; bounding box of every component accumulated at the root (atomicMin / atomicMax,
+//   4 run_accum   every run learns its root; bounding box of every component accumulated at the root (atomicMin / atomicMax,
 //                 issued only when the value read would change)
 //   5 mk_marks    roots whose box is a candidate (sides in range, nearly square): the row's WAVE takes each one — lane r owns row
 //                 y0 + r and builds its 64-bit window from the one or two mask words the box straddles; the frame counts and the
@@ -35,19 +35,6 @@ __device__ __forceinline__ u64 wave_or(u64 v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) { lo |= (unsigned)__shfl_xor((int)lo, d); hi |= (unsigned)__shfl_xor((int)hi, d); }
     return ((u64)hi << 32) | lo;
-}
-
-// 4: parent = root; the root's box grows to the component's (run_join_root of runs.h)
-__global__ __launch_bounds__(256) void mk_accum_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* parent, int4* box, int H,
-                                                       size_t runcap, int rows_total) {
-    int pg, row, lane;
-    if (!row_wave(H, rows_total, pg, row, lane)) return;
-    const int* ro = runoff + (size_t)pg * (H + 1);
-    const size_t rb = (size_t)pg * runcap;
-    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
-        int xs, xe;
-        run_join_root(parent + rb, rxs + rb, rxe + rb, box + rb, id, row, xs, xe);
-    }
 }
 
 // 5: tmp [B][max_marks][9] = y0, x0, y1, x1, root, edge, ink_in, area_in, state
@@ -227,24 +214,19 @@ __global__ __launch_bounds__(256) void mk_sort_kernel(const int* counts, const i
 
 // the workspace's regions: one layout sizes it (marks_workspace_bytes) and carves it (marks_launch)
 struct MarkWorkspace {
-    unsigned long long* mask; int* runoff; unsigned short *rxs, *rxe; int* parent; int4* box; int* tmp; int* round_tmp;   // round_tmp: only with the round list
+    Components c;   // (no area)
+    int* tmp; int* round_tmp;   // round_tmp: only with the round list
 };
 static MarkWorkspace marks_layout(Arena& a, int B, int H, int W, int max_marks, bool rounds) {
-    const size_t runcap = run_cap(H, W), nw = (W + 63) / 64;
     MarkWorkspace w;
-    w.mask = a.take<unsigned long long>((size_t)B * H * nw);
-    w.runoff = a.take<int>((size_t)B * (H + 1));   // run counts -> offsets
-    w.rxs = a.take<unsigned short>((size_t)B * runcap); w.rxe = a.take<unsigned short>((size_t)B * runcap);
-    w.parent = a.take<int>((size_t)B * runcap);
-    w.box = a.take<int4>((size_t)B * runcap);      // at a root: x0, x1, y0, y1 of its component
+    w.c = components_layout(a, B, H, W, false);
     w.tmp = a.take<int>((size_t)B * max_marks * 9);
     w.round_tmp = rounds ? a.take<int>((size_t)B * max_marks * 9) : nullptr;
     return w;
 }
 
 static bool marks_args_ok(int B, int H, int W, int max_marks) {
-    if (B <= 0 || H <= 0 || W <= 0 || H > 65535 || W > 65535 || max_marks < 1 || max_marks > MARK_MAX_MARKS) return false;
-    return (size_t)B * H < (1ull << 31) && run_cap(H, W) < (1ull << 31);
+    return page_args_ok(B, H, W) && max_marks >= 1 && max_marks <= MARK_MAX_MARKS;
 }
 
 bool round_params_ok(int out_max, int ring_div, int band_div, int band_min) {
@@ -266,27 +248,22 @@ hipError_t marks_launch(const MarkParams& p, void* workspace, size_t ws_bytes, h
     if (rounds != (p.round_counts != nullptr)) return hipErrorInvalidValue;
     if (rounds && !round_params_ok(p.out_max, p.ring_div, p.band_div, p.band_min)) return hipErrorInvalidValue;
     Arena a(workspace, ws_bytes);
-    const MarkWorkspace w = marks_layout(a, B, H, W, p.max_marks, rounds);
+    MarkWorkspace w = marks_layout(a, B, H, W, p.max_marks, rounds);
     if (a.overflow) return hipErrorOutOfMemory;
     const int nw = (W + 63) / 64;
     const size_t runcap = run_cap(H, W);
-    const unsigned long long* mask;
     hipError_t e = hipMemsetAsync(p.counts, 0, sizeof(int) * (size_t)B, st);
     if (e != hipSuccess) return e;
-    if ((e = ink_mask_resolve(p.rgb, p.mask_in, p.mask_out, w.mask, B, H, W, p.threshold, st, &mask)) != hipSuccess) return e;
+    if ((e = components_launch(w.c, p.rgb, p.mask_in, p.mask_out, B, H, W, p.threshold, st)) != hipSuccess) return e;
+    const unsigned long long* mask = w.c.mask;
     const int rows = B * H;
     const dim3 grows = row_wave_grid(rows);
-    run_count_launch(mask, w.runoff, B, H, nw, st);
-    row_scan_launch(w.runoff, nullptr, B, H, st);
-    run_fill_launch(mask, w.runoff, w.rxs, w.rxe, w.parent, w.box, B, H, nw, runcap, st);
-    run_merge_launch(w.runoff, w.rxs, w.rxe, w.parent, B, H, runcap, st);
-    hipLaunchKernelGGL(mk_accum_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.box, H, runcap, rows);
-    hipLaunchKernelGGL(mk_marks_kernel, grows, dim3(256), 0, st, mask, w.runoff, w.parent, w.box, H, nw, runcap, p.min_side, p.max_side, p.max_marks,
+    hipLaunchKernelGGL(mk_marks_kernel, grows, dim3(256), 0, st, mask, w.c.runoff, w.c.parent, w.c.box, H, nw, runcap, p.min_side, p.max_side, p.max_marks,
                        p.counts, w.tmp, rows);
     hipLaunchKernelGGL(mk_sort_kernel, dim3(B), dim3(256), 0, st, p.counts, w.tmp, p.marks, p.max_marks);
     if (rounds) {
         if ((e = hipMemsetAsync(p.round_counts, 0, sizeof(int) * (size_t)B, st)) != hipSuccess) return e;
-        hipLaunchKernelGGL(mk_rounds_kernel, grows, dim3(256), 0, st, mask, w.runoff, w.parent, w.box, H, W, nw, runcap, p.min_side, p.max_side, p.out_max,
+        hipLaunchKernelGGL(mk_rounds_kernel, grows, dim3(256), 0, st, mask, w.c.runoff, w.c.parent, w.c.box, H, W, nw, runcap, p.min_side, p.max_side, p.out_max,
                            p.ring_div, p.band_div, p.band_min, p.max_marks, p.round_counts, w.round_tmp, rows);
         hipLaunchKernelGGL(mk_sort_kernel, dim3(B), dim3(256), 0, st, p.round_counts, w.round_tmp, p.rounds, p.max_marks);
     }

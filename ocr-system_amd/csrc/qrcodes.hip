@@ -4,9 +4,8 @@
 // 1-10, lumina_ocr_qrcodes) and tests/qr_versions_reference.py (versions 1-40, lumina_ocr_qrcodes_versions).
 //
 // All stream-ordered kernels, no host round trip; both calls enqueue 1-5 through one front end:
-//   1 ink_mask                          the mask (or the one the caller already has)
-//   2 run_count / row_scan / run_fill / run_merge   mask words -> run list and its 8-connected components (the shared kernels of runs.hip)
-//   3 qr_area, qr_accum   a run's length is its area; every run learns its root, box and area are accumulated at the root
+//   1-3 components_launch (runs.h)      the mask (or the one the caller already has), its run list, the 8-connected components; every run
+//                 learns its root, box and area are accumulated at the root
 //   4 qr_finders  one wave per row, lanes over the row's roots: a solid square core whose centre row has, before and after the core's run,
 //                 two runs of one other component, the ring, concentric and 7/3 of its size -> counted, gathered per page
 //   5 qr_decode   stage 1, versions 1-10.  One wave per (page, finder A): lanes over B, a loop over C pick A's partners (64-bit products, no
@@ -21,15 +20,16 @@
 //                 alignment centres and the fixed areas (lanes over rows); the codewords are placed without a table: lanes over the
 //                 two-column strips count their free modules, a wave prefix sum gives each strip its bit offset, and each lane walks its
 //                 strip and ORs whole and partial bytes into the codewords (LDS atomics)
-//   6 qr_output   one work-group per page: valid candidates counted, gathered, rank-sorted by (y0, x0, y1, x1, corner root); int rows of
-//                 stage 1's codewords, or (the all-versions call) byte rows from the stage that read the symbol
+//   6 qr_output   one work-group per page (code_output.h): valid candidates counted, gathered, rank-sorted by (y0, x0, y1, x1, corner root);
+//                 int rows of stage 1's codewords, or (the all-versions call) byte rows from the stage that read the symbol
 // The stages differ in how a version is scored, how the grid is sampled and how the codewords are placed; the pair search, the quiet
-// rings, the format information, the block loop (rs_gf256.h: field 0x11D, first root 0) and the result are one piece of code each.  Every
+// rings, the format information, the block loop (rs.h: field 0x11D, first root 0) and the result are one piece of code each.  Every
 // loop has a constant bound, every table and LDS index is clamped, and no wave waits for another (a work-group is one wave).
 #include "qrcodes.h"
+#include "code_output.h"
 #include "qr_tables.h"
 #include "qr_version_tables.h"
-#include "rs_gf256.h"
+#include "rs.h"
 #include "runs.h"
 
 namespace {
@@ -38,7 +38,7 @@ typedef unsigned long long u64;
 typedef long long i64;
 
 constexpr int QR_SPAN = 8192;          // |B - A|, |C - A| per axis in doubled pixels: keeps every product inside 64 bits
-constexpr int RES_INTS = 16;           // a candidate's result: y0, x0, y1, x1, root, version, level, mask, ndata, errors, rotation, fdist, timing, valid
+// a candidate's result (code_output.h): y0, x0, y1, x1, root, version, level, mask, ndata, errors, rotation, fdist, timing, state
 constexpr int QR_MAX_TOTAL = 346, QR_MAX_NB = 8, QR_RAW = 384;   // stage 1: the codewords and blocks of version 10, its LDS array
 constexpr int QRV_ROWS = 177;          // stage 2: modules a side at version 40
 constexpr int QRV_RAW = 3712;          // >= QRV_MAX_TOTAL, a multiple of 4
@@ -50,30 +50,6 @@ static_assert(QRV_MAX_BLOCK <= QR_RS_LEN && QRV_MAX_TOTAL <= QRV_RAW && QRV_VERS
 __device__ __forceinline__ i64 labs64(i64 v) { return v < 0 ? -v : v; }
 __device__ __forceinline__ i64 floor_div(i64 a, i64 b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }   // b > 0
 __device__ __forceinline__ int floor_div32(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }   // b > 0
-
-// 3a: a run's own length is the start of its component's area
-__global__ __launch_bounds__(256) void qr_area_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* area, int H, size_t runcap,
-                                                      int rows_total) {
-    int pg, row, lane;
-    if (!row_wave(H, rows_total, pg, row, lane)) return;
-    const int* ro = runoff + (size_t)pg * (H + 1);
-    const size_t rb = (size_t)pg * runcap;
-    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) area[rb + id] = (int)rxe[rb + id] - (int)rxs[rb + id] + 1;
-}
-
-// 3b: parent = root; the root's box grows to the component's and its area by every other run's length
-__global__ __launch_bounds__(256) void qr_accum_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* parent, int4* box, int* area,
-                                                       int H, size_t runcap, int rows_total) {
-    int pg, row, lane;
-    if (!row_wave(H, rows_total, pg, row, lane)) return;
-    const int* ro = runoff + (size_t)pg * (H + 1);
-    const size_t rb = (size_t)pg * runcap;
-    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
-        int xs, xe;
-        const int root = run_join_root(parent + rb, rxs + rb, rxe + rb, box + rb, id, row, xs, xe);
-        if (root >= 0) atomicAdd(area + rb + root, xe - xs + 1);
-    }
-}
 
 // 4: finders [B][max_finders] = cx2, cy2, me, root
 __global__ __launch_bounds__(256) void qr_finders_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, const int* parent,
@@ -225,8 +201,8 @@ __device__ __forceinline__ bool qr_format(Bit bit, int D, int lane, int& level, 
 // corrected there, the data codewords written to od (DATA_CAP of them) -> false when a block has more errors than it can correct.  A
 // symbol's total % blocks last blocks hold one data codeword more.  The whole wave calls it (barriers inside).
 template <int MAX_NB, int RAW_CAP, int DATA_CAP, int MAX_LEN, int MAX_EC>
-__device__ __forceinline__ bool qr_blocks(RsLds<MAX_LEN, MAX_EC>& rs, const unsigned char* raw, int total, int version, int level, int lane, unsigned char* od,
-                                          int& ndata, int& errors) {
+__device__ __forceinline__ bool qr_blocks(RsLds<unsigned char, MAX_LEN, MAX_EC, 8>& rs, const unsigned char* raw, int total, int version, int level, int lane,
+                                          unsigned char* od, int& ndata, int& errors) {
     const int bi = (version - 1) * 4 + (level & 3);
     const int nb = clampi(QRV_NB[bi], 1, MAX_NB), ec = clampi(QRV_EC[bi], 2, MAX_EC);
     const int nshort = nb - total % nb, dlen = total / nb - ec;
@@ -279,7 +255,7 @@ __device__ __forceinline__ void qr_write_result(int* o, const QrGrid& g, int H, 
     o[0] = cl(y0, H - 1); o[1] = cl(x0, W - 1); o[2] = cl(y1 - 1, H - 1); o[3] = cl(x1 - 1, W - 1); o[4] = ida;
     o[5] = version; o[6] = level; o[7] = mpat; o[8] = ndata; o[9] = errors;
     o[10] = iabs(g.abx) >= iabs(g.aby) ? (g.abx > 0 ? 0 : 2) : (g.aby > 0 ? 1 : 3);
-    o[11] = fdist; o[12] = timing; o[13] = 1;
+    o[11] = fdist; o[12] = timing; o[CODE_RES_STATE] = CODE_ROW;
 }
 
 // ---- stage 1: versions 1-10 ----------------------------------------------------------------------------------------------------------------
@@ -299,7 +275,7 @@ __device__ __forceinline__ u64 reach_mask(i64 l2, i64 m) {
 struct QrLds {
     u64 rows[64];              // module rows: bit col
     unsigned char raw[QR_RAW];   // the codewords in placement order
-    RsLds<QR_RS_LEN, QR_RS_EC> rs;
+    RsLds<unsigned char, QR_RS_LEN, QR_RS_EC, 8> rs;
 };
 
 // a candidate (the corner A of g with its partners) through the whole decode -> true with the result in o / od, false when it is none.
@@ -364,7 +340,7 @@ __device__ __forceinline__ bool qr_try(QrLds& s, const u64* mpage, int H, int W,
     return true;
 }
 
-// 5: one wave per (page, finder): res [B][max_finders][RES_INTS], resdata [B][max_finders][QR_MAX_DATA]
+// 5: one wave per (page, finder): res [B][max_finders][CODE_RES_INTS], resdata [B][max_finders][QR_MAX_DATA]
 __global__ __launch_bounds__(64) void qr_decode_kernel(const u64* mask, const int4* finders, const int* nfind, int H, int W, int nw, int max_finders, int quiet,
                                                        int timing_max, int* res, unsigned char* resdata) {
     __shared__ QrLds s;
@@ -374,9 +350,9 @@ __global__ __launch_bounds__(64) void qr_decode_kernel(const u64* mask, const in
     const u64* mpage = mask + (size_t)pg * H * nw;
     const int4 f = lane < nf ? finders[(size_t)pg * max_finders + lane] : make_int4(0, 0, 0, 0);
     const int ida = __shfl(f.w, a);
-    int* o = res + ((size_t)pg * max_finders + a) * RES_INTS;
+    int* o = res + ((size_t)pg * max_finders + a) * CODE_RES_INTS;
     unsigned char* od = resdata + ((size_t)pg * max_finders + a) * QR_MAX_DATA;
-    rs_load_tables(s.rs, QR_EXP, QR_LOG, lane);
+    rs_load_tables(s.rs, QR_EXP, QR_LOG, 8, lane);
     qr_pairs(f, nf, a, lane, [](i64 l2, i64 m) { return reach_mask(l2, m); }, [&](const QrGrid& g, u64 reach) { return qr_try(s, mpage, H, W, nw, g, reach, quiet, timing_max, ida, lane, o, od); });
 }
 
@@ -385,7 +361,7 @@ __global__ __launch_bounds__(64) void qr_decode_kernel(const u64* mask, const in
 struct QrvLds {
     u64 grid[QRV_ROWS * 3], func[QRV_ROWS * 3];   // module rows and the function mask: bit col % 64 of word col / 64
     unsigned raw[QRV_RAW / 4];                    // the codewords in placement order, as bytes
-    RsLds<QR_RS_LEN, QR_RS_EC> rs;
+    RsLds<unsigned char, QR_RS_LEN, QR_RS_EC, 8> rs;
 };
 
 // the versions 11 .. max_version (bit v) in reach of l2 = |AB|^2 + |AC|^2 and m = meA + meB + meC: n within 3 + n / 16 modules
@@ -594,98 +570,53 @@ __global__ __launch_bounds__(64) void qr_decode_versions_kernel(const u64* mask,
     const int pg = blockIdx.y, a = blockIdx.x, lane = threadIdx.x;
     const int nf = nfind[pg];
     if (nf > max_finders || a >= nf || nf > QR_MAX_FINDERS) return;
-    int* o = res + ((size_t)pg * max_finders + a) * RES_INTS;
-    if (o[13] == 1) return;   // stage 1 has A's symbol
+    int* o = res + ((size_t)pg * max_finders + a) * CODE_RES_INTS;
+    if (o[CODE_RES_STATE] == CODE_ROW) return;   // stage 1 has A's symbol
     const u64* mpage = mask + (size_t)pg * H * nw;
     const int4 f = lane < nf ? finders[(size_t)pg * max_finders + lane] : make_int4(0, 0, 0, 0);
     const int ida = __shfl(f.w, a);
     unsigned char* od = resdata + ((size_t)pg * max_finders + a) * QRV_MAX_DATA;
-    rs_load_tables(s.rs, QR_EXP, QR_LOG, lane);
+    rs_load_tables(s.rs, QR_EXP, QR_LOG, 8, lane);
     qr_pairs(f, nf, a, lane, [=](i64 l2, i64 m) { return reach_mask_versions(l2, m, max_version); },
              [&](const QrGrid& g, u64 reach) { return qr_try_versions(s, mpage, H, W, nw, g, reach, quiet, timing_max, ida, lane, o, od); });
 }
 
 // ---- 6: the output ----------------------------------------------------------------------------------------------------------------------------
 
-struct QrOutLds { int key[QR_MAX_CODES * 5], slot[QR_MAX_CODES], n; };
-
-// a page's valid results (one work-group): counted, gathered into tmp [max_codes][6] = y0, x0, y1, x1, root, slot, rank-sorted, the 12-int
-// rows written -> the number of rows, s.slot[rank] the finder slot of row rank.  An overflowing list has no rows: its count is all that
-// is reported.
-__device__ __forceinline__ int qr_output_rows(QrOutLds& s, const int* res, int nf, int max_finders, int max_codes, int* tmp, int* out) {
-    if (threadIdx.x == 0) s.n = 0;
-    __syncthreads();
-    const int lim = nf > max_finders ? 0 : nf;   // a page with too many finders is not read
-    for (int a = threadIdx.x; a < lim; a += 256) {
-        const int* r = res + a * RES_INTS;
-        if (r[13] != 1) continue;
-        const int idx = atomicAdd(&s.n, 1);
-        if (idx >= max_codes) continue;
-        int* o = tmp + idx * 6;
-        o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3]; o[4] = r[4]; o[5] = a;
-    }
-    __syncthreads();
-    const int n = s.n;
-    if (n > max_codes) return n;
-    int* slots = s.slot;
-    rank_sort<5>(s.key, tmp, 6, n, [=](int i, int rank, const int (&k)[5]) {
-        const int slot = clampi(tmp[i * 6 + 5], 0, max_finders - 1);
-        const int* r = res + slot * RES_INTS;
-        int* o = out + (size_t)rank * 12;
-        o[0] = k[1]; o[1] = k[0]; o[2] = k[3]; o[3] = k[2];
-        for (int j = 0; j < 8; ++j) o[4 + j] = r[5 + j];
-        slots[clampi(rank, 0, QR_MAX_CODES - 1)] = slot;
-    });
-    __syncthreads();
-    return n;
-}
-
-// the output kernel of either call: DataOut is int (stage 1's codewords alone, rows of QR_MAX_DATA) or unsigned char (rows of QRV_MAX_DATA,
-// a symbol's codewords from the stage that read it)
+// the output kernel of either call (code_output.h): DataOut is int (stage 1's codewords alone, rows of QR_MAX_DATA) or unsigned char (rows
+// of QRV_MAX_DATA, a symbol's codewords from the stage that read it)
 template <class DataOut, int ROW>
 __global__ __launch_bounds__(256) void qr_output_kernel(const int* res_all, const unsigned char* resdata1_all, const unsigned char* resdata2_all, const int* nfind,
                                                         int max_finders, int max_codes, int* tmp_all, int* counts, int* codes, DataOut* data, int* finder_counts) {
-    __shared__ QrOutLds s;
+    __shared__ CodeOutLds<QR_MAX_CODES> s;
     const int pg = blockIdx.x;
-    const int nf = nfind[pg];
-    const int* res = res_all + (size_t)pg * max_finders * RES_INTS;
-    const int n = qr_output_rows(s, res, nf, max_finders, max_codes, tmp_all + (size_t)pg * max_codes * 6, codes + (size_t)pg * max_codes * 12);
-    if (threadIdx.x == 0) {
-        counts[pg] = n;
-        if (finder_counts) finder_counts[pg] = nf;
-    }
+    const int* res = res_all + (size_t)pg * max_finders * CODE_RES_INTS;
+    const int n = code_output_rows(s, res, nfind[pg], max_finders, max_codes, tmp_all + (size_t)pg * max_codes * 6, codes + (size_t)pg * max_codes * 12,
+                                   counts + pg, finder_counts ? finder_counts + pg : nullptr);
     if (n > max_codes) return;
-    DataOut* odat = data + (size_t)pg * max_codes * ROW;
     const unsigned char* rd1 = resdata1_all + (size_t)pg * max_finders * QR_MAX_DATA;
     const unsigned char* rd2 = resdata2_all ? resdata2_all + (size_t)pg * max_finders * QRV_MAX_DATA : nullptr;
-    for (int idx = threadIdx.x; idx < n * ROW; idx += 256) {
-        const int rank = idx / ROW, j = idx - rank * ROW, slot = clampi(s.slot[rank & (QR_MAX_CODES - 1)], 0, max_finders - 1);
-        const int* r = res + slot * RES_INTS;
-        unsigned char v = 0;
-        if (j < r[8]) v = r[5] <= QR_VERSIONS || !rd2 ? (j < QR_MAX_DATA ? rd1[(size_t)slot * QR_MAX_DATA + j] : 0) : rd2[(size_t)slot * QRV_MAX_DATA + j];
-        odat[idx] = v;
-    }
+    code_output_data(s, n, max_finders, ROW, data + (size_t)pg * max_codes * ROW, [=](int slot, int j) -> DataOut {
+        const int* r = res + slot * CODE_RES_INTS;
+        if (j >= r[8]) return 0;
+        if (r[5] <= QR_VERSIONS || !rd2) return j < QR_MAX_DATA ? rd1[(size_t)slot * QR_MAX_DATA + j] : 0;
+        return rd2[(size_t)slot * QRV_MAX_DATA + j];
+    });
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------------------
 
 // the workspace's regions: one layout sizes it (the *_workspace_bytes) and carves it (qr_front_end); resdata2 is the all-versions call's
 struct QrWorkspace {
-    u64* mask; int* runoff; unsigned short *rxs, *rxe; int* parent; int4* box; int* area;
+    Components c;
     int* nfind; int4* finders; int* res; unsigned char *resdata, *resdata2; int* tmp;
 };
 QrWorkspace qrcodes_layout(Arena& a, int B, int H, int W, int max_finders, int max_codes, bool versions) {
-    const size_t runcap = run_cap(H, W), nw = (W + 63) / 64;
     QrWorkspace w;
-    w.mask = a.take<u64>((size_t)B * H * nw);
-    w.runoff = a.take<int>((size_t)B * (H + 1));   // run counts -> offsets
-    w.rxs = a.take<unsigned short>((size_t)B * runcap); w.rxe = a.take<unsigned short>((size_t)B * runcap);
-    w.parent = a.take<int>((size_t)B * runcap);
-    w.box = a.take<int4>((size_t)B * runcap);      // at a root: x0, x1, y0, y1 of its component
-    w.area = a.take<int>((size_t)B * runcap);      // at a root: its component's ink
+    w.c = components_layout(a, B, H, W, true);
     w.nfind = a.take<int>((size_t)B);
     w.finders = a.take<int4>((size_t)B * max_finders);
-    w.res = a.take<int>((size_t)B * max_finders * RES_INTS);
+    w.res = a.take<int>((size_t)B * max_finders * CODE_RES_INTS);
     w.resdata = a.take<unsigned char>((size_t)B * max_finders * QR_MAX_DATA);
     w.tmp = a.take<int>((size_t)B * max_codes * 6);
     w.resdata2 = versions ? a.take<unsigned char>((size_t)B * max_finders * QRV_MAX_DATA) : nullptr;
@@ -693,9 +624,7 @@ QrWorkspace qrcodes_layout(Arena& a, int B, int H, int W, int max_finders, int m
 }
 
 bool qrcodes_args_ok(int B, int H, int W, int max_finders, int max_codes) {
-    if (B <= 0 || H <= 0 || W <= 0 || H > 65535 || W > 65535 || max_codes < 1 || max_codes > QR_MAX_CODES || max_finders < 1 || max_finders > QR_MAX_FINDERS)
-        return false;
-    return (size_t)B * H < (1ull << 31) && run_cap(H, W) < (1ull << 31);
+    return page_args_ok(B, H, W) && max_codes >= 1 && max_codes <= QR_MAX_CODES && max_finders >= 1 && max_finders <= QR_MAX_FINDERS;
 }
 
 size_t qr_workspace_bytes(int B, int H, int W, int max_finders, int max_codes, bool versions) {
@@ -717,18 +646,12 @@ hipError_t qr_front_end(const QrCommon& p, const void* data, bool versions, void
     const size_t runcap = run_cap(H, W);
     hipError_t e;
     if ((e = hipMemsetAsync(w.nfind, 0, sizeof(int) * (size_t)B, st)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(w.res, 0, sizeof(int) * (size_t)B * p.max_finders * RES_INTS, st)) != hipSuccess) return e;
-    if ((e = ink_mask_resolve(p.rgb, p.mask_in, p.mask_out, w.mask, B, H, W, p.threshold, st, &mask)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.res, 0, sizeof(int) * (size_t)B * p.max_finders * CODE_RES_INTS, st)) != hipSuccess) return e;
+    if ((e = components_launch(w.c, p.rgb, p.mask_in, p.mask_out, B, H, W, p.threshold, st)) != hipSuccess) return e;
+    mask = w.c.mask;
     const int rows = B * H;
-    const dim3 grows = row_wave_grid(rows);
-    run_count_launch(mask, w.runoff, B, H, nw, st);
-    row_scan_launch(w.runoff, nullptr, B, H, st);
-    run_fill_launch(mask, w.runoff, w.rxs, w.rxe, w.parent, w.box, B, H, nw, runcap, st);
-    run_merge_launch(w.runoff, w.rxs, w.rxe, w.parent, B, H, runcap, st);
-    hipLaunchKernelGGL(qr_area_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.area, H, runcap, rows);
-    hipLaunchKernelGGL(qr_accum_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.box, w.area, H, runcap, rows);
-    hipLaunchKernelGGL(qr_finders_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.box, w.area, H, runcap, p.min_module, p.max_module,
-                       p.centre_tol, p.ring_tol, p.max_finders, w.nfind, w.finders, rows);
+    hipLaunchKernelGGL(qr_finders_kernel, row_wave_grid(rows), dim3(256), 0, st, w.c.runoff, w.c.rxs, w.c.rxe, w.c.parent, w.c.box, w.c.area, H, runcap,
+                       p.min_module, p.max_module, p.centre_tol, p.ring_tol, p.max_finders, w.nfind, w.finders, rows);
     hipLaunchKernelGGL(qr_decode_kernel, dim3(p.max_finders, B), dim3(64), 0, st, mask, w.finders, w.nfind, H, W, nw, p.max_finders, p.quiet, p.timing_max, w.res,
                        w.resdata);
     return hipSuccess;

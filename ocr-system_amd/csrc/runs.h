@@ -1,9 +1,9 @@
 #pragma once
 #include "common.h"
 
-// What the page-analysis passes share (DB post-process, de-skew, tables, selection marks, page orientation): the lock-free
-// union-find, the ink mask of a page and its bit transpose, the run list of a batch of row masks with its 8-connected merge, and a
-// rank sort of a few integer key columns in LDS.  Device helpers are defined here; the kernels live in runs.hip behind the host
+// What the page-analysis passes share (DB post-process, de-skew, tables, selection marks, matrix codes, page orientation): the lock-free
+// union-find, the ink mask of a page and its bit transpose, the run list of a batch of row masks with its 8-connected merge, the
+// components of all ink built from them (Components, at the end), and a rank sort of a few integer key columns in LDS.  Device helpers are defined here; the kernels live in runs.hip behind the host
 // launchers below (every kernel of the library sits in the anonymous namespace of its own file).
 
 // ---- min-label union-find (parents only ever decrease: the root of a set is its smallest index); on LDS tiles and on pages ----
@@ -50,6 +50,16 @@ __device__ __forceinline__ int run_join_root(int* P, const unsigned short* rxs, 
     if (xe > __atomic_load_n(b + 1, __ATOMIC_RELAXED)) atomicMax(b + 1, xe);
     if (row > __atomic_load_n(b + 3, __ATOMIC_RELAXED)) atomicMax(b + 3, row);
     return root;
+}
+
+// ---- the four diagonal extremes of one run (min x + y, max x - y, max x + y, min x - y) as packed words (key, y, x): min types hold y,
+// max types 65535 - y below the key, so that one atomic min / max keeps the tie rule (the smaller y) exact ----
+__device__ __forceinline__ void run_extremes(int xs, int xe, int y, unsigned long long (&e)[4]) {
+    typedef unsigned long long u64;
+    e[0] = ((u64)(unsigned)(xs + y) << 32) | ((u64)y << 16) | (u64)xs;
+    e[1] = ((u64)(unsigned)(xe - y + 65536) << 32) | ((u64)(65535 - y) << 16) | (u64)xe;
+    e[2] = ((u64)(unsigned)(xe + y) << 32) | ((u64)(65535 - y) << 16) | (u64)xe;
+    e[3] = ((u64)(unsigned)(xs - y + 65536) << 32) | ((u64)y << 16) | (u64)xs;
 }
 
 // ---- rank sort of n <= cap rows of NC integer key columns, by one 256-thread work-group: the keys (the first NC of every `stride`
@@ -102,3 +112,25 @@ void run_fill_launch(const unsigned long long* mask, const int* runoff, unsigned
 // union-find over run ids: a run joins every run of the row above that it touches (8-connectivity)
 void run_merge_launch(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* parent, int B, int H, size_t runcap,
                       hipStream_t st);
+
+// ---- the components of all ink of a batch of pages: what the matrix-code readers and the selection marks open with.  The regions come
+// first in a pass's workspace, in this order; a pass's own regions follow.  After components_launch every run's parent is its root (the
+// component's first run in raster order) and a root holds its component's box (x0, x1, y0, y1), its ink when there is an area region,
+// and its four packed diagonal extremes (run_extremes) when the caller has set ext to a region of [B][runcap][4] words. ----
+struct Components {
+    const unsigned long long* mask;   // the mask in use, set by components_launch: the caller's mask_in, its mask_out, or mask_buf
+    unsigned long long* mask_buf;     // [B][H][ceil(W / 64)]
+    int* runoff;                      // [B][H + 1]: run counts -> offsets
+    unsigned short *rxs, *rxe;        // [B][runcap]
+    int* parent;                      // [B][runcap]
+    int4* box;                        // [B][runcap]
+    int* area;                        // [B][runcap], or nullptr
+    unsigned long long* ext;          // the caller's, or nullptr (needs the area)
+};
+Components components_layout(Arena& a, int B, int H, int W, bool area);
+// sides 1 .. 65535 (run ends are 16-bit), B * H and the run capacity below 2^31
+bool page_args_ok(int B, int H, int W);
+// ink_mask_resolve, run_count, row_scan, run_fill, run_merge, then (with an area) every run's own area and extremes, then the
+// accumulation at the roots
+hipError_t components_launch(Components& c, const uint8_t* rgb, const unsigned long long* mask_in, unsigned long long* mask_out, int B, int H, int W,
+                             int threshold, hipStream_t st);

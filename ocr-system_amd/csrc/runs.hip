@@ -1,6 +1,7 @@
 // The kernels the page-analysis passes share (gfx950), each written once: the ink mask of a page and its bit transpose, and the run
-// list of a batch of row masks — count, scan, fill, 8-connected merge.  Their users are dbpost.hip (runs of the binarised
-// probability map), marks.hip (runs of all ink), tables.hip and orient.hip (mask and transpose).  Everything is integer.
+// list of a batch of row masks — count, scan, fill, 8-connected merge — and, behind components_launch, the components of all ink with
+// box, area and extremes at their roots.  Their users are dbpost.hip (runs of the binarised probability map), marks.hip, qrcodes.hip,
+// datamatrix.hip and aztec.hip (components of all ink), tables.hip and orient.hip (mask and transpose).  Everything is integer.
 #include "runs.h"
 
 namespace {
@@ -154,6 +155,52 @@ __global__ __launch_bounds__(256) void run_merge_kernel(const int* runoff, const
     }
 }
 
+// ---- components: a run's own length (and extremes) is the start of its component's ----
+template <bool EXT>
+__global__ __launch_bounds__(256) void run_area_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* area, u64* ext, int H,
+                                                       size_t runcap, int rows_total) {
+    int pg, row, lane;
+    if (!row_wave(H, rows_total, pg, row, lane)) return;
+    const int* ro = runoff + (size_t)pg * (H + 1);
+    const size_t rb = (size_t)pg * runcap;
+    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
+        const int xs = rxs[rb + id], xe = rxe[rb + id];
+        area[rb + id] = xe - xs + 1;
+        if (EXT) {
+            u64 e[4];
+            run_extremes(xs, xe, row, e);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ext[(rb + id) * 4 + j] = e[j];
+        }
+    }
+}
+
+// parent = root; the root's box grows to the component's (run_join_root), its area by every other run's length (AREA), its extremes to
+// the component's (EXT; as for the box, an atomic is issued only when the value read before it would change)
+template <bool AREA, bool EXT>
+__global__ __launch_bounds__(256) void run_accum_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* parent, int4* box, int* area,
+                                                        u64* ext, int H, size_t runcap, int rows_total) {
+    int pg, row, lane;
+    if (!row_wave(H, rows_total, pg, row, lane)) return;
+    const int* ro = runoff + (size_t)pg * (H + 1);
+    const size_t rb = (size_t)pg * runcap;
+    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
+        int xs, xe;
+        const int root = run_join_root(parent + rb, rxs + rb, rxe + rb, box + rb, id, row, xs, xe);
+        if (root < 0) continue;
+        if (AREA) atomicAdd(area + rb + root, xe - xs + 1);
+        if (EXT) {
+            u64 e[4];
+            run_extremes(xs, xe, row, e);
+            u64* x = ext + (rb + root) * 4;
+            if (e[0] < __atomic_load_n(x + 0, __ATOMIC_RELAXED)) atomicMin(x + 0, e[0]);
+            if (e[1] > __atomic_load_n(x + 1, __ATOMIC_RELAXED)) atomicMax(x + 1, e[1]);
+            if (e[2] > __atomic_load_n(x + 2, __ATOMIC_RELAXED)) atomicMax(x + 2, e[2]);
+            if (e[3] < __atomic_load_n(x + 3, __ATOMIC_RELAXED)) atomicMin(x + 3, e[3]);
+        }
+    }
+}
+
 }  // namespace
 
 hipError_t ink_mask_launch(const uint8_t* rgb, unsigned long long* mask, int B, int H, int W, int threshold, hipStream_t st) {
@@ -194,4 +241,40 @@ void run_fill_launch(const unsigned long long* mask, const int* runoff, unsigned
 void run_merge_launch(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, int* parent, int B, int H, size_t runcap,
                       hipStream_t st) {
     hipLaunchKernelGGL(run_merge_kernel, row_wave_grid(B * H), dim3(256), 0, st, runoff, rxs, rxe, parent, H, runcap, B * H);
+}
+
+Components components_layout(Arena& a, int B, int H, int W, bool area) {
+    const size_t runcap = run_cap(H, W), nw = (W + 63) / 64;
+    Components c{};
+    c.mask_buf = a.take<u64>((size_t)B * H * nw);
+    c.runoff = a.take<int>((size_t)B * (H + 1));
+    c.rxs = a.take<unsigned short>((size_t)B * runcap); c.rxe = a.take<unsigned short>((size_t)B * runcap);
+    c.parent = a.take<int>((size_t)B * runcap);
+    c.box = a.take<int4>((size_t)B * runcap);
+    c.area = area ? a.take<int>((size_t)B * runcap) : nullptr;
+    return c;
+}
+
+bool page_args_ok(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || H > 65535 || W > 65535) return false;
+    return (size_t)B * H < (1ull << 31) && run_cap(H, W) < (1ull << 31);
+}
+
+hipError_t components_launch(Components& c, const uint8_t* rgb, const unsigned long long* mask_in, unsigned long long* mask_out, int B, int H, int W,
+                             int threshold, hipStream_t st) {
+    if (c.ext && !c.area) return hipErrorInvalidValue;
+    const hipError_t e = ink_mask_resolve(rgb, mask_in, mask_out, c.mask_buf, B, H, W, threshold, st, &c.mask);
+    if (e != hipSuccess) return e;
+    const int nw = (W + 63) / 64, rows = B * H;
+    const size_t runcap = run_cap(H, W);
+    const dim3 grows = row_wave_grid(rows);
+    run_count_launch(c.mask, c.runoff, B, H, nw, st);
+    row_scan_launch(c.runoff, nullptr, B, H, st);
+    run_fill_launch(c.mask, c.runoff, c.rxs, c.rxe, c.parent, c.box, B, H, nw, runcap, st);
+    run_merge_launch(c.runoff, c.rxs, c.rxe, c.parent, B, H, runcap, st);
+    const auto area = c.ext ? run_area_kernel<true> : run_area_kernel<false>;
+    const auto accum = c.ext ? run_accum_kernel<true, true> : c.area ? run_accum_kernel<true, false> : run_accum_kernel<false, false>;
+    if (c.area) hipLaunchKernelGGL(area, grows, dim3(256), 0, st, c.runoff, c.rxs, c.rxe, c.area, c.ext, H, runcap, rows);
+    hipLaunchKernelGGL(accum, grows, dim3(256), 0, st, c.runoff, c.rxs, c.rxe, c.parent, c.box, c.area, c.ext, H, runcap, rows);
+    return hipSuccess;
 }

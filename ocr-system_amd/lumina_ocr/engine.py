@@ -671,6 +671,30 @@ class Engine:
             self._chk(self.lib.lumina_ocr_barcodes_kinds(*args, kinds if isinstance(kinds, int) else arch.barcode_kinds_mask(kinds)))
         return (codes, syms, counts, mask) if debug else (codes, syms, counts)
 
+    # -- the matrix codes: what qrcodes, qrcodes_versions, datamatrix, aztec and aztec_layers share ------------------------------------
+    def _matrix_codes(self, name, keys, defaults, data_cols, data_dtype, pages, params, mask_in, debug, extra=()):
+        """lumina_ocr_<name> on pages: the scalars are params' values for `keys` (the last one is max_codes), defaulting to `defaults`,
+        then `extra`; rows of 12 ints, data rows of data_cols elements of torch.<data_dtype>.
+        -> (codes, data, counts), with debug also the ink mask and the finder or candidate counts."""
+        torch = _torch()
+        n, h, w, c = pages.shape
+        assert c == 3 and pages.dtype == torch.uint8 and pages.is_contiguous()
+        unknown = set(params) - set(keys)
+        if unknown:
+            raise TypeError("%s: unknown parameters %s" % (name, sorted(unknown)))
+        q = [int(params[k]) if params.get(k) is not None else defaults[k] for k in keys]
+        max_codes = q[-1]
+        if mask_in is not None:
+            assert mask_in.dtype == torch.int64 and mask_in.is_contiguous() and tuple(mask_in.shape) == (n, h, (w + 63) // 64)
+        codes = torch.zeros((n, max(max_codes, 0), 12), dtype=torch.int32, device=pages.device)
+        data = torch.zeros((n, max(max_codes, 0), data_cols), dtype=getattr(torch, data_dtype), device=pages.device)
+        counts = torch.zeros((n,), dtype=torch.int32, device=pages.device)
+        mask = torch.zeros((n, h, (w + 63) // 64), dtype=torch.int64, device=pages.device) if debug else None
+        slots = torch.zeros((n,), dtype=torch.int32, device=pages.device) if debug else None
+        self._chk(getattr(self.lib, "lumina_ocr_" + name)(self._h, _ptr(pages), n, h, w, *q, *(int(v) for v in extra), _ptr(codes), _ptr(data),
+                                                          _ptr(counts), _ptr(slots), _ptr(mask_in), _ptr(mask), self._stream()))
+        return (codes, data, counts, mask, slots) if debug else (codes, data, counts)
+
     # -- QR codes (Model 2; qrcodes: versions 1-10, qrcodes_versions: 1-40; the host half is utils/qrcodes.py) --------------------------------------------------------
     _QR_KEYS = ("threshold", "min_module", "max_module", "quiet", "centre_tol", "ring_tol", "timing_max", "max_finders", "max_codes")
 
@@ -681,48 +705,14 @@ class Engine:
         whose count exceeds max_codes is not written).  params: any of arch.QR_PARAMS' keys, defaulting to them.  mask_in: the ink
         mask of the pages at this threshold, int64 [n,H,ceil(W/64)], when it is there already.  Asynchronous.  debug=True also
         returns the ink mask the pass worked on and the finder count of every page."""
-        torch = _torch()
-        n, h, w, c = pages.shape
-        assert c == 3 and pages.dtype == torch.uint8 and pages.is_contiguous()
-        unknown = set(params) - set(self._QR_KEYS)
-        if unknown:
-            raise TypeError("qrcodes: unknown parameters %s" % sorted(unknown))
-        q = [int(params[k]) if params.get(k) is not None else arch.QR_PARAMS[k] for k in self._QR_KEYS]
-        max_codes = q[-1]
-        if mask_in is not None:
-            assert mask_in.dtype == torch.int64 and mask_in.is_contiguous() and tuple(mask_in.shape) == (n, h, (w + 63) // 64)
-        codes = torch.zeros((n, max(max_codes, 0), 12), dtype=torch.int32, device=pages.device)
-        data = torch.zeros((n, max(max_codes, 0), 288), dtype=torch.int32, device=pages.device)
-        counts = torch.zeros((n,), dtype=torch.int32, device=pages.device)
-        mask = torch.zeros((n, h, (w + 63) // 64), dtype=torch.int64, device=pages.device) if debug else None
-        finders = torch.zeros((n,), dtype=torch.int32, device=pages.device) if debug else None
-        self._chk(self.lib.lumina_ocr_qrcodes(self._h, _ptr(pages), n, h, w, *q, _ptr(codes), _ptr(data), _ptr(counts), _ptr(finders), _ptr(mask_in),
-                                              _ptr(mask), self._stream()))
-        return (codes, data, counts, mask, finders) if debug else (codes, data, counts)
+        return self._matrix_codes("qrcodes", self._QR_KEYS, arch.QR_PARAMS, 288, "int32", pages, params, mask_in, debug)
 
     def qrcodes_versions(self, pages, max_version: int, mask_in=None, debug: bool = False, **params):
         """qrcodes for versions 1 .. max_version (10..40): uint8 [n,H,W,3] device -> (codes int32 [n,max_codes,12], data uint8
         [n,max_codes,2956], counts int32 [n]).  Versions 1-10 are read as qrcodes reads them, with the same rows; a corner finder that
         gave no such symbol is tried for versions 11 .. max_version (lumina_ocr_qrcodes_versions).  The data codewords are bytes here.
         params, mask_in and debug as in qrcodes."""
-        torch = _torch()
-        n, h, w, c = pages.shape
-        assert c == 3 and pages.dtype == torch.uint8 and pages.is_contiguous()
-        unknown = set(params) - set(self._QR_KEYS)
-        if unknown:
-            raise TypeError("qrcodes_versions: unknown parameters %s" % sorted(unknown))
-        q = [int(params[k]) if params.get(k) is not None else arch.QR_PARAMS[k] for k in self._QR_KEYS]
-        max_codes = q[-1]
-        if mask_in is not None:
-            assert mask_in.dtype == torch.int64 and mask_in.is_contiguous() and tuple(mask_in.shape) == (n, h, (w + 63) // 64)
-        codes = torch.zeros((n, max(max_codes, 0), 12), dtype=torch.int32, device=pages.device)
-        data = torch.zeros((n, max(max_codes, 0), 2956), dtype=torch.uint8, device=pages.device)
-        counts = torch.zeros((n,), dtype=torch.int32, device=pages.device)
-        mask = torch.zeros((n, h, (w + 63) // 64), dtype=torch.int64, device=pages.device) if debug else None
-        finders = torch.zeros((n,), dtype=torch.int32, device=pages.device) if debug else None
-        self._chk(self.lib.lumina_ocr_qrcodes_versions(self._h, _ptr(pages), n, h, w, *q, int(max_version), _ptr(codes), _ptr(data), _ptr(counts),
-                                                       _ptr(finders), _ptr(mask_in), _ptr(mask), self._stream()))
-        return (codes, data, counts, mask, finders) if debug else (codes, data, counts)
+        return self._matrix_codes("qrcodes_versions", self._QR_KEYS, arch.QR_PARAMS, 2956, "uint8", pages, params, mask_in, debug, (max_version,))
 
     # -- Data Matrix (ECC 200, 10 x 10 .. 52 x 52 and the rectangles; the host half is utils/datamatrix.py) ------------------------------
     _DM_KEYS = ("threshold", "min_module", "max_module", "quiet", "timing_max", "solid_max", "max_candidates", "max_codes")
@@ -734,24 +724,7 @@ class Engine:
         max_codes is not written).  params: any of arch.DM_PARAMS' keys, defaulting to them.  mask_in: the ink mask of the pages at
         this threshold, int64 [n,H,ceil(W/64)], when it is there already.  Asynchronous.  debug=True also returns the ink mask the
         pass worked on and the candidate count of every page."""
-        torch = _torch()
-        n, h, w, c = pages.shape
-        assert c == 3 and pages.dtype == torch.uint8 and pages.is_contiguous()
-        unknown = set(params) - set(self._DM_KEYS)
-        if unknown:
-            raise TypeError("datamatrix: unknown parameters %s" % sorted(unknown))
-        q = [int(params[k]) if params.get(k) is not None else arch.DM_PARAMS[k] for k in self._DM_KEYS]
-        max_codes = q[-1]
-        if mask_in is not None:
-            assert mask_in.dtype == torch.int64 and mask_in.is_contiguous() and tuple(mask_in.shape) == (n, h, (w + 63) // 64)
-        codes = torch.zeros((n, max(max_codes, 0), 12), dtype=torch.int32, device=pages.device)
-        data = torch.zeros((n, max(max_codes, 0), 208), dtype=torch.int32, device=pages.device)
-        counts = torch.zeros((n,), dtype=torch.int32, device=pages.device)
-        mask = torch.zeros((n, h, (w + 63) // 64), dtype=torch.int64, device=pages.device) if debug else None
-        cands = torch.zeros((n,), dtype=torch.int32, device=pages.device) if debug else None
-        self._chk(self.lib.lumina_ocr_datamatrix(self._h, _ptr(pages), n, h, w, *q, _ptr(codes), _ptr(data), _ptr(counts), _ptr(cands), _ptr(mask_in),
-                                                 _ptr(mask), self._stream()))
-        return (codes, data, counts, mask, cands) if debug else (codes, data, counts)
+        return self._matrix_codes("datamatrix", self._DM_KEYS, arch.DM_PARAMS, 208, "int32", pages, params, mask_in, debug)
 
     # -- Aztec (aztec: compact 1-4 layers, full-range 1-11 layers; aztec_layers: full-range up to 32; the host half is utils/aztec.py) ----------------------------------------------
     _AZTEC_KEYS = ("threshold", "min_module", "max_module", "quiet", "centre_tol", "ring_tol", "mark_max", "max_finders", "max_codes")
@@ -763,48 +736,15 @@ class Engine:
         numbers (a list whose count exceeds max_codes is not written).  params: any of arch.AZTEC_PARAMS' keys, defaulting to them.
         mask_in: the ink mask of the pages at this threshold, int64 [n,H,ceil(W/64)], when it is there already.  Asynchronous.
         debug=True also returns the ink mask the pass worked on and the finder count of every page."""
-        torch = _torch()
-        n, h, w, c = pages.shape
-        assert c == 3 and pages.dtype == torch.uint8 and pages.is_contiguous()
-        unknown = set(params) - set(self._AZTEC_KEYS)
-        if unknown:
-            raise TypeError("aztec: unknown parameters %s" % sorted(unknown))
-        q = [int(params[k]) if params.get(k) is not None else arch.AZTEC_PARAMS[k] for k in self._AZTEC_KEYS]
-        max_codes = q[-1]
-        if mask_in is not None:
-            assert mask_in.dtype == torch.int64 and mask_in.is_contiguous() and tuple(mask_in.shape) == (n, h, (w + 63) // 64)
-        codes = torch.zeros((n, max(max_codes, 0), 12), dtype=torch.int32, device=pages.device)
-        data = torch.zeros((n, max(max_codes, 0), 320), dtype=torch.int32, device=pages.device)
-        counts = torch.zeros((n,), dtype=torch.int32, device=pages.device)
-        mask = torch.zeros((n, h, (w + 63) // 64), dtype=torch.int64, device=pages.device) if debug else None
-        finders = torch.zeros((n,), dtype=torch.int32, device=pages.device) if debug else None
-        self._chk(self.lib.lumina_ocr_aztec(self._h, _ptr(pages), n, h, w, *q, _ptr(codes), _ptr(data), _ptr(counts), _ptr(finders), _ptr(mask_in),
-                                            _ptr(mask), self._stream()))
-        return (codes, data, counts, mask, finders) if debug else (codes, data, counts)
+        return self._matrix_codes("aztec", self._AZTEC_KEYS, arch.AZTEC_PARAMS, 320, "int32", pages, params, mask_in, debug)
 
     def aztec_layers(self, pages, max_layers: int, mask_in=None, debug: bool = False, **params):
         """aztec for full-range symbols of up to max_layers (11..32) layers: uint8 [n,H,W,3] device -> (codes int32 [n,max_codes,12], data
         uint16 [n,max_codes,1664], counts int32 [n]).  Every symbol aztec reads comes with the same row and codewords; a full-range finder
         of 12 .. max_layers layers that gave no such row goes through the second stage (lumina_ocr_aztec_layers).  params, mask_in and
         debug as in aztec."""
-        torch = _torch()
-        n, h, w, c = pages.shape
-        assert c == 3 and pages.dtype == torch.uint8 and pages.is_contiguous()
-        unknown = set(params) - set(self._AZTEC_KEYS)
-        if unknown:
-            raise TypeError("aztec_layers: unknown parameters %s" % sorted(unknown))
-        q = [int(params[k]) if params.get(k) is not None else arch.AZTEC_PARAMS[k] for k in self._AZTEC_KEYS]
-        max_codes = q[-1]
-        if mask_in is not None:
-            assert mask_in.dtype == torch.int64 and mask_in.is_contiguous() and tuple(mask_in.shape) == (n, h, (w + 63) // 64)
-        codes = torch.zeros((n, max(max_codes, 0), 12), dtype=torch.int32, device=pages.device)
-        data = torch.zeros((n, max(max_codes, 0), 1664), dtype=torch.int16, device=pages.device).view(torch.uint16)
-        counts = torch.zeros((n,), dtype=torch.int32, device=pages.device)
-        mask = torch.zeros((n, h, (w + 63) // 64), dtype=torch.int64, device=pages.device) if debug else None
-        finders = torch.zeros((n,), dtype=torch.int32, device=pages.device) if debug else None
-        self._chk(self.lib.lumina_ocr_aztec_layers(self._h, _ptr(pages), n, h, w, *q, int(max_layers), _ptr(codes), _ptr(data), _ptr(counts),
-                                                   _ptr(finders), _ptr(mask_in), _ptr(mask), self._stream()))
-        return (codes, data, counts, mask, finders) if debug else (codes, data, counts)
+        out = self._matrix_codes("aztec_layers", self._AZTEC_KEYS, arch.AZTEC_PARAMS, 1664, "int16", pages, params, mask_in, debug, (max_layers,))
+        return out[:1] + (out[1].view(_torch().uint16),) + out[2:]   # (allocated as int16: the words are unsigned)
 
     def rules_and_marks(self, pages, threshold=None, gap=None, min_len=None, max_thick=None, max_rules=None, min_side=None, max_side=None,
                         max_marks=None):

@@ -86,11 +86,16 @@ class _Pending:
     gathered: Optional[object] = None   # multi-GPU: handle of dist.PageGather.submit (the batch's results of ALL ranks)
     rules_host: Optional[list] = None   # tables: pinned copies of hrules, vrules, counts
     marks_host: Optional[list] = None   # marks: pinned copies of marks, counts (round_marks: and of round marks, round counts)
-    barcodes_host: Optional[list] = None   # barcodes: pinned copies of codes, symbol values, counts
-    qrcodes_host: Optional[list] = None    # qrcodes: pinned copies of codes, data codewords, counts
-    datamatrix_host: Optional[list] = None   # datamatrix: pinned copies of codes, data codewords, counts
-    aztec_host: Optional[list] = None        # aztec: pinned copies of codes, data codewords, counts
+    codes_host: dict = field(default_factory=dict)   # per code pass that ran (_CODE_PASSES): pinned copies of codes, symbol values or data codewords, counts
     words_host: Optional[list] = None   # word_boxes: pinned copies of word quads, spans, scores, counts
+
+
+# the code passes: the pipeline's switch (also the key of _Pending.codes_host), PageDetections' fields for the rows and their symbol
+# values or data codewords, and what the overflow warning calls them
+_CODE_PASSES = (("barcodes", ("barcodes", "barcode_syms"), "barcodes"),
+                ("qrcodes", ("qrcodes", "qr_data"), "QR codes"),
+                ("datamatrix", ("datamatrix", "dm_data"), "Data Matrix symbols"),
+                ("aztec", ("aztec", "az_data"), "Aztec symbols"))
 
 
 class OcrPipeline:
@@ -351,21 +356,16 @@ class OcrPipeline:
             pend.rules_host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in rules]
         if marks is not None:
             pend.marks_host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in marks]
-        if barcodes is not None:
-            pend.barcodes_host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in barcodes]
-        if qrcodes is not None:
-            pend.qrcodes_host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in qrcodes]
-        if datamatrix is not None:
-            pend.datamatrix_host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in datamatrix]
-        if aztec is not None:
-            pend.aztec_host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in aztec]
+        for kind, tensors in (("barcodes", barcodes), ("qrcodes", qrcodes), ("datamatrix", datamatrix), ("aztec", aztec)):
+            if tensors is not None:
+                pend.codes_host[kind] = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in tensors]
         if self.gather is not None:
             self.gather.begin(counts_h)          # capacity all-reduce runs beside the recogniser
         if n == 0:
             if self.gather is not None:          # every rank takes part in the collective, with or without lines
                 e = lambda *shape, dt=torch.int32: torch.empty(shape, dtype=dt, device=boxes.device)
                 pend.gathered = self.gather.submit(counts_h, e(0, 8), e(0, dt=torch.float32), e(0, 80), e(0), e(0, dt=torch.float32))
-            elif pend.rules_host is not None or pend.marks_host is not None or pend.barcodes_host is not None or pend.qrcodes_host is not None or pend.datamatrix_host is not None or pend.aztec_host is not None:
+            elif pend.rules_host is not None or pend.marks_host is not None or pend.codes_host:
                 pend.event = torch.cuda.Event()
                 pend.event.record(torch.cuda.current_stream(processed.device))
             return pend
@@ -405,15 +405,15 @@ class OcrPipeline:
         rules = self._page_rules(pend)
         marks = self._page_marks(pend)
         rounds = self._page_marks(pend, 2)
-        codes = self._page_barcodes(pend)
-        qrs = self._page_barcodes(pend, qr=True)
-        dms = self._page_barcodes(pend, dm=True)
-        azs = self._page_barcodes(pend, az=True)
+        codes = [{} for _ in range(b)]   # per page: PageDetections' fields of the four code passes
+        for kind, fields, _ in _CODE_PASSES:
+            for p, pair in enumerate(self._page_barcodes(pend, kind)):
+                codes[p].update(zip(fields, pair))
         if pend.n == 0:
             nw = self._empty_words() if self.word_boxes else {}
             return [PageDetections(np.zeros((0, 8), np.int32), [], np.zeros(0, np.float32), np.zeros(0, np.float32), w, h,
-                                   hrules=rules[p][0], vrules=rules[p][1], marks=marks[p], round_marks=rounds[p], barcodes=codes[p][0],
-                                   barcode_syms=codes[p][1], qrcodes=qrs[p][0], qr_data=qrs[p][1], datamatrix=dms[p][0], dm_data=dms[p][1], aztec=azs[p][0], az_data=azs[p][1], **nw) for p in range(b)], pend.processed
+                                   hrules=rules[p][0], vrules=rules[p][1], marks=marks[p], round_marks=rounds[p], **codes[p], **nw)
+                    for p in range(b)], pend.processed
         text_h, len_h, score_h, quads_h, det_h, *cls_h = (t.numpy() for t in pend.host)
         all_texts = self._decoder.decode(text_h, len_h)
         words_h = None
@@ -427,9 +427,7 @@ class OcrPipeline:
             out.append(PageDetections(quads_h[off:off + c], texts, score_h[off:off + c], det_h[off:off + c], w, h,
                                       text_h[off:off + c], len_h[off:off + c],
                                       *((cls_h[0][off:off + c], cls_h[1][off:off + c]) if cls_h else ()),
-                                      hrules=rules[p][0], vrules=rules[p][1], marks=marks[p], round_marks=rounds[p],
-                                      barcodes=codes[p][0], barcode_syms=codes[p][1], qrcodes=qrs[p][0], qr_data=qrs[p][1],
-                                      datamatrix=dms[p][0], dm_data=dms[p][1], aztec=azs[p][0], az_data=azs[p][1],
+                                      hrules=rules[p][0], vrules=rules[p][1], marks=marks[p], round_marks=rounds[p], **codes[p],
                                       **({} if words_h is None else dict(zip(self._WORD_FIELDS, (t[off:off + c] for t in words_h))))))
             off += c
         return out, pend.processed
@@ -488,20 +486,23 @@ class OcrPipeline:
             out.append(rows[p, :m].copy())
         return out
 
-    def _page_barcodes(self, pend: "_Pending", qr: bool = False, dm: bool = False, az: bool = False):
+    def _page_barcodes(self, pend: "_Pending", kind: str = "barcodes"):
         """-> per page (codes [m,8], symbol values [m,64]) from the pending batch's host copies, or (None, None) without barcodes.  A
-        page whose true count exceeds the capacity has no rows: it is treated as having no barcodes.  qr: the same of the QR pass's
-        copies, (codes [m,12], data codewords [m,288], or bytes [m,2956] above qr_max_version 10); dm: of the Data Matrix pass's, (codes [m,12], data codewords [m,208]); az: of the Aztec pass's, (codes [m,12], data codewords [m,320], or uint16 [m,1664] above aztec_max_layers 11)."""
-        host = pend.aztec_host if az else pend.datamatrix_host if dm else pend.qrcodes_host if qr else pend.barcodes_host
+        page whose true count exceeds the capacity has no rows: it is treated as having no barcodes.  kind: another row of _CODE_PASSES
+        for the same of that pass's copies, "qrcodes": (codes [m,12], data codewords [m,288], or bytes [m,2956] above qr_max_version 10);
+        "datamatrix": (codes [m,12], data codewords [m,208]); "aztec": (codes [m,12], data codewords [m,320], or uint16 [m,1664] above
+        aztec_max_layers 11)."""
+        host = pend.codes_host.get(kind)
         if host is None:
             return [(None, None)] * pend.b
+        noun = next(noun for k, _, noun in _CODE_PASSES if k == kind)
         rows, syms, cnt = (t.numpy() for t in host)
         cap = rows.shape[1]
         out = []
         for p in range(pend.b):
             m = int(cnt[p])
             if m > cap:
-                logger.warning("page %d of the batch has %d %s, more than max_codes = %d: none are reported for it", p, m, "Aztec symbols" if az else "Data Matrix symbols" if dm else "QR codes" if qr else "barcodes", cap)
+                logger.warning("page %d of the batch has %d %s, more than max_codes = %d: none are reported for it", p, m, noun, cap)
                 m = 0
             out.append((rows[p, :m].copy(), syms[p, :m].copy()))
         return out

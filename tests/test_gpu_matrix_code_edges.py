@@ -75,7 +75,7 @@ def test_aztec_blocks_beyond_the_correction_capacity(engine, symbol):
 
 @pytest.mark.parametrize("symbol", me.DM_RS_SYMBOLS, ids=me.dm_rs_id)
 def test_datamatrix_blocks_beyond_the_correction_capacity(engine, symbol):
-    """the same for rs_correct_block of rs_gf256.h on one- and two-block sizes; 52 x 52 with block 0 varied and block 1 at t, and
+    """the same for rs_correct_block of rs.h on one- and two-block sizes; 52 x 52 with block 0 varied and block 1 at t, and
     with block 0 at t and block 1 varied: there the decode returns after block 0's codewords have been written"""
     size, block, text = symbol
     pages, wrong, t = me.dm_rs_pages(*symbol)

@@ -136,9 +136,35 @@ def test_small_symbols_equal_the_ten_version_call(engine):
         assert np.array_equal(new[0][i, :len(rc)], rc) and np.array_equal(new[1][i, :len(rc), :qr.MAX_DATA], rd)
 
 
+def test_ragged_page_groups(engine):
+    """Four 250 x 310 pages in groups of 3 + 1: every per-group offset of the entry, the 2956-byte data stride among them.  The split
+    call equals the restatement, itself with its own mask handed back in, the call in one group, and every page alone — rows, data,
+    counts, mask and finder counts each time."""
+    pages = np.stack([C.blank(250, 310) for _ in range(4)])
+    want = [dict([C.put(pages[0], 20, 16, 2, 1, tag="P0 ")]), {},
+            dict([C.put(pages[2], 14, 12, 11, 1, tag="P2 "), C.put(pages[2], 230, 40, 1, 0, tag="P2b ")]),      # stage 2 beside stage 1
+            dict([C.put(pages[3], 18, 14, 12, 2, tag="P3 ")])]
+    dev = torch.from_numpy(pages).cuda()
+    call = lambda t, **kw: [x.cpu().numpy() for x in engine.qrcodes_versions(t, 40, debug=True, **kw)]
+    engine.set_option("post_group", 3)
+    try:
+        res = check(engine, pages)
+        split = call(dev)
+        again = call(dev, mask_in=torch.from_numpy(split[3]).cuda())
+    finally:
+        engine.set_option("post_group", 64)
+    assert [found(*r[:2]) for r in res] == want and len({t for f in want for t in f.values()}) == 4
+    assert [int(c) for c in split[2]] == [1, 0, 2, 1] and [int(f) for f in split[4]] == [3, 0, 6, 3]
+    whole = call(dev)
+    for other in (again, whole):
+        assert all(np.array_equal(a, b) for a, b in zip(split, other))
+    for i in range(4):
+        assert all(np.array_equal(a[i:i + 1], b) for a, b in zip(split, call(dev[i:i + 1]))), "page %d alone differs" % i
+
+
 def test_bad_arguments_return_a_status_and_launch_nothing(engine):
     pages = torch.from_numpy(C.blank(64, 200)[None]).cuda()
-    order = ("threshold", "min_module", "max_module", "quiet", "centre_tol", "ring_tol", "timing_max", "max_finders", "max_codes", "max_version")
+    order =("threshold", "min_module", "max_module", "quiet", "centre_tol", "ring_tol", "timing_max", "max_finders", "max_codes", "max_version")
     good = dict(P, max_codes=4, max_version=40)
     st = torch.cuda.current_stream().cuda_stream
     for bad in (dict(max_version=9), dict(max_version=41), dict(max_version=-1), dict(max_codes=0), dict(max_codes=65), dict(max_finders=65), dict(quiet=5),
