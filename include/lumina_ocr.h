@@ -498,6 +498,18 @@ int lumina_ocr_jpeg_decode_async(lumina_ocr_t* h, const uint8_t* const* files, c
                                  int* status_pinned, int passes, void* stream);
 /* synchronisation passes over the chunk decoders the last lumina_ocr_jpeg_decode call needed (diagnostic) */
 int lumina_ocr_jpeg_last_passes(const lumina_ocr_t* h);
+/* Progressive JPEG files (SOF2) as well.  The entries above keep their answers (-2 for a progressive file).
+ * lumina_ocr_jpeg_probe_progressive (host only): 0 for every file lumina_ocr_jpeg_probe takes, and for progressive Huffman files: 8 bit,
+ * grey or YCbCr, 4:4:4 / 4:2:2 / 4:2:0, any legal scan script of at most 32 scans (interleaved or single-component DC scans, any
+ * spectral bands and successive-approximation depth, DHT and DRI between scans).  info = {width, height, components, luma h, luma v,
+ * restart interval (of the first scan), 1 if progressive, number of scans}.  -2: arithmetic coding, 12 bit, 4 components, more than 32
+ * scans, a DQT after the first scan, a first scan over a coefficient that is complete already, or scans that stop short of all 64 coefficients of every component at full precision (libjpeg smooths such a file across
+ * blocks); -1: corrupt, an illegal progression included.
+ * lumina_ocr_jpeg_decode_progressive: the contract and the status codes of lumina_ocr_jpeg_decode; sequential and progressive files may
+ * be mixed in one batch, a sequential file takes the kernels and gives the bytes of lumina_ocr_jpeg_decode.  Synchronises `stream`. */
+int lumina_ocr_jpeg_probe_progressive(const uint8_t* file, size_t size, int info[8]);
+int lumina_ocr_jpeg_decode_progressive(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width,
+                                       uint8_t* out_dev, int* status, void* stream);
 
 /* PNG decode on the device — the pixel work of the reference's Image.open(...) + convert('RGB') for .png inputs and for the PNG pages
  * pdf2image returns (image_preprocessing.py:57-75).  The contract is the JPEG pair's: status 0 => byte-identical to Pillow's

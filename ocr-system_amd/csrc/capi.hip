@@ -505,6 +505,23 @@ int lumina_ocr_jpeg_decode_async(lumina_ocr_t* h, const uint8_t* const* files, c
 
 int lumina_ocr_jpeg_last_passes(const lumina_ocr_t* h) { return h ? h->jd_last_passes : 0; }
 
+int lumina_ocr_jpeg_probe_progressive(const uint8_t* file, size_t size, int info[8]) {
+    if (!file || !info) return -1;
+    JdProgInfo i{};
+    const int rc = jpegdec_probe_progressive(file, size, &i);
+    info[0] = i.width; info[1] = i.height; info[2] = i.ncomp; info[3] = i.hs; info[4] = i.vs; info[5] = i.restart; info[6] = i.progressive; info[7] = i.nscans;
+    return rc;
+}
+
+int lumina_ocr_jpeg_decode_progressive(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev,
+                                       int* status, void* stream) {
+    if (!h || !files || !sizes || !out_dev || !status || n <= 0 || height <= 0 || width <= 0) return locr_fail(h, "jpeg_decode_progressive", "bad arguments");
+    BIND(h);
+    API_TRY
+    return jpegdec_run_progressive(h, files, sizes, n, height, width, out_dev, status, (hipStream_t)stream);
+    API_CATCH(h)
+}
+
 int lumina_ocr_png_probe(const uint8_t* file, size_t size, int info[8]) {
     if (!file || !info) return -1;
     PdInfo i{};

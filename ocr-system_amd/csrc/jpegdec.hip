@@ -15,6 +15,8 @@
 //      are integrated per component (segmented by restart interval), then inverse DCT ("islow" integer), fancy chroma up-sampling
 //      and YCbCr -> RGB are embarrassingly parallel kernels.
 // Header parsing (a few hundred bytes of markers) is host code.
+// Progressive files (SOF2, jpegdec_run_progressive) reuse stages 1 and 3; their entropy stage is the jp_* kernels further down: every scan
+// is one un-stuffed stream, first scans decode in one round, refinement scans after them in file order.
 #include "jpegdec.h"
 
 #include <cstring>
@@ -483,6 +485,282 @@ __global__ void jd_status_kernel(const JdFile* files, const JdDyn* dyn, const in
     status[i] = rc;
 }
 
+// ------------------------------------------------------------------------------------------------ progressive files (SOF2)
+// A progressive file is a sequence of scans over one coefficient buffer.  Every scan is un-stuffed as a stream of its own by the three
+// kernels above (a JdFile per scan carries its byte range and the Huffman tables in force at its SOS), then decoded in rounds:
+//   round 0      every first scan (Ah = 0, DC or AC) of every file: they read no coefficient and write disjoint ones;
+//   round r >= 1 the r-th refinement scan of its components: it reads what the rounds before it wrote.
+// Within a round a restart segment (the whole scan where the file has none) is one serial stream: a thread for a first scan, a thread per
+// block for DC refinement, a wave64 for AC refinement — the bit cost of an AC refinement symbol depends on which coefficients of the block
+// are non-zero already, so no chunk can be decoded from a guessed state.
+constexpr int JP_MAX_SCANS = 32;   // scans per file (Pillow's script has 10, libjpeg's cjpeg -progressive 10, mozjpeg's up to 17): more is refused with -2
+struct JpScan {
+    int file, round, ncs, ss, se, ah, al, restart, bps, nmcu, wc, hc;
+    int comp[3], sblk[6], sci[6];   // frame component of scan component i; block-in-frame-MCU and scan component of block i of a scan MCU
+};
+
+// block index in the coefficient buffer (MCU-interleaved, padded to whole MCUs) of block i of MCU m of the scan: a single-component scan
+// walks that component's own raster of ceil(w_c / 8) x ceil(h_c / 8) blocks, not the padded grid
+__device__ __forceinline__ int jp_blk(const JdFile& F, const JpScan& P, int m, int i) {
+    if (P.ncs > 1) return m * F.bpm + P.sblk[i];
+    const int c = P.comp[0], hsc = c == 0 ? F.hs : 1, vsc = c == 0 ? F.vs : 1;
+    const int by = m / P.wc, bx = m - by * P.wc;
+    return ((by / vsc) * F.mcux + bx / hsc) * F.bpm + F.first_blk_of_comp[c] + (by % vsc) * hsc + bx % hsc;
+}
+__device__ __forceinline__ int jp_bits(JdRd& r, int nb) {   // 0 <= nb <= 16
+    if (nb == 0) return 0;
+    const int v = (int)jd_peek(r, nb);
+    jd_skip(r, nb);
+    return v;
+}
+// zig-zag index of the coefficient at natural position n (the inverse of JD_ZZ)
+__device__ constexpr unsigned char JP_IZZ[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30, 41, 43, 9,  11, 18, 24, 31, 40, 44, 53,
+                                                 10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
+// correction bits of the coefficients in `range` (a mask over zig-zag positions, ascending): one stream bit each -> the mask of those set
+__device__ __forceinline__ unsigned long long jp_corrections(JdRd& r, unsigned long long range) {
+    unsigned long long got = 0;
+    int n = __popcll(range);
+    while (n > 0) {   // up to 16 stream bits at a time, first bit first
+        const int c = n < 16 ? n : 16;
+        unsigned v = (unsigned)jp_bits(r, c) << (32 - c);
+        for (int i = 0; i < c; ++i, v <<= 1) {
+            const unsigned long long low = range & (0ull - range);
+            if (v & 0x80000000u) got |= low;
+            range ^= low;
+        }
+        n -= c;
+    }
+    return got;
+}
+
+// AC refinement: one wave64 per restart segment (per scan where the file has none).  The bits a symbol takes depend on which coefficients
+// of its block are non-zero already, so the stream itself is walked in order, by all lanes alike (wave-uniform, nothing diverges).  What the
+// lanes share out is the memory work around it, 64 blocks at a time: lane j loads block j and packs its non-zero history into one 64-bit
+// word over zig-zag positions; the walk reads block j's word by a cross-lane read and works on words alone — a zero run is the position of
+// the (r + 1)-th clear bit from k, the history coefficients on the way are the set bits below it and take one correction bit each in that
+// order — and leaves block j's outcome (corrected / new / negative, three words) with lane j; then every lane applies its block's words and
+// stores it.  Corrections go away from zero, and only where the bit is not yet set.
+__global__ __launch_bounds__(64) void jp_acref_kernel(const JdFile* files, JdDyn* fdyn, const JdFile* streams, const JpScan* scans, const JdDyn* sdyn,
+                                                      const unsigned char* cleanbuf, const unsigned* seg_start, short* coefbuf, int round) {
+    const int si = blockIdx.y;
+    const JpScan& P = scans[si];
+    if (P.round != round || P.ss == 0 || P.ah == 0) return;
+    const JdFile& S = streams[si];
+    const JdDyn& SD = sdyn[si];
+    const JdFile& F = files[P.file];
+    JdDyn& D = fdyn[P.file];
+    const int nsegs = S.seg_cap ? (int)S.seg_cap : 1, s = blockIdx.x, lane = threadIdx.x;
+    if (s >= nsegs) return;
+    __shared__ JdHuff T;
+    for (int i = lane; i < (int)(sizeof(JdHuff) / 4); i += 64) reinterpret_cast<unsigned*>(&T)[i] = reinterpret_cast<const unsigned*>(&S.ac[0])[i];
+    __syncthreads();
+    if (SD.nseg < 0 || SD.err) { D.err = 1; return; }
+    const unsigned* seg = seg_start + S.seg_off;
+    const unsigned total = SD.clean_len * 8u, pos0 = s ? seg[s - 1] * 8u : 0u, end = s < SD.nseg ? seg[s] * 8u : total;
+    if (pos0 >= end || end > total) { D.err = 1; return; }
+    const int per = P.restart > 0 ? P.restart : P.nmcu, m0 = s * per, m1 = min(m0 + per, P.nmcu);
+    uint4* coef4 = reinterpret_cast<uint4*>(coefbuf + (size_t)F.coef_off * 64);   // a block: 8 x 16 bytes
+    JdRd r; r.w = reinterpret_cast<const unsigned*>(cleanbuf + S.clean_off); r.have = 0; r.pos = pos0; r.acc = 0;
+    const int ss = P.ss, se = P.se, p1 = 1 << P.al;
+    const unsigned long long band = (se >= 63 ? ~0ull : (1ull << (se + 1)) - 1ull) & (~0ull << ss);
+    bool bad = m0 >= m1;
+    int eobrun = 0;
+    for (int mb = m0; mb < m1 && !bad; mb += 64) {
+        // ---- lane j: the history word of block mb + j ----
+        const int cnt = min(64, m1 - mb);
+        int B = -1;
+        unsigned long long nz = 0;
+        if (lane < cnt) {
+            B = jp_blk(F, P, mb + lane, 0);
+            if (B < 0 || B >= F.nblk) B = -1;
+        }
+        if (B >= 0) {
+            uint4 v[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v[q] = coef4[(size_t)B * 8 + q];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const unsigned w[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (w[e] & 0xFFFFu) nz |= 1ull << JP_IZZ[q * 8 + e * 2];
+                    if (w[e] >> 16) nz |= 1ull << JP_IZZ[q * 8 + e * 2 + 1];
+                }
+            }
+            nz &= band;
+        }
+        if (__any(lane < cnt && B < 0)) { bad = true; break; }
+        // ---- the walk: wave-uniform ----
+        // Every lane runs it with the same values: the reader's state comes from loads at addresses that do not depend on the lane, h is
+        // lane j's word read by all lanes, and `bad`, eobrun, k and the three outcome words follow from those alone.  So no branch below
+        // diverges, all 64 lanes are active at each __shfl, and `lane == j` is the only place where a lane keeps something of its own.
+        unsigned long long my_corr = 0, my_new = 0, my_neg = 0;
+        for (int j = 0; j < cnt && !bad; ++j) {
+            const unsigned long long h = ((unsigned long long)(unsigned)__shfl((int)(nz >> 32), j) << 32) | (unsigned)__shfl((int)(nz & 0xFFFFFFFFull), j);
+            unsigned long long corr = 0, nw = 0, neg = 0;
+            int k = ss;
+            if (eobrun == 0) {
+                while (k <= se) {
+                    const int rs = jd_sym(r, T);
+                    if (rs < 0) { bad = true; break; }
+                    int run = rs >> 4, val = 0;
+                    const int sz = rs & 15;
+                    if (sz) {
+                        if (sz != 1) { bad = true; break; }   // a new coefficient is +-1 at this depth
+                        val = jp_bits(r, 1) ? 1 : -1;
+                    } else if (run != 15) {
+                        eobrun = (1 << run) + jp_bits(r, run);
+                        break;   // the rest of the band takes its correction bits below
+                    }
+                    // the (run + 1)-th zero coefficient from k (past the band if there are fewer)
+                    unsigned long long z = ~h & band & (~0ull << k);
+                    for (int i = 0; i < run; ++i) z &= z - 1ull;
+                    const int kend = z ? __ffsll((long long)z) - 1 : se + 1;
+                    corr |= jp_corrections(r, h & (~0ull << k) & (kend > 63 ? ~0ull : (1ull << kend) - 1ull));
+                    k = kend;
+                    if (r.pos > end) { bad = true; break; }
+                    if (val) {
+                        if (k > se) { bad = true; break; }
+                        nw |= 1ull << k;
+                        if (val < 0) neg |= 1ull << k;
+                    }
+                    ++k;
+                }
+            }
+            if (!bad && eobrun > 0) {
+                if (k <= se) corr |= jp_corrections(r, h & (~0ull << k));
+                --eobrun;
+            }
+            if (r.pos > end) bad = true;
+            if (lane == j) { my_corr = corr; my_new = nw; my_neg = neg; }
+        }
+        // ---- lane j: apply and store (a page that went bad is not written out, so its blocks may stay half done) ----
+        if (B >= 0 && (my_corr | my_new)) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                uint4 v = coef4[(size_t)B * 8 + q];
+                unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const int zz = JP_IZZ[q * 8 + e];
+                    int c = (short)(e & 1 ? w[e >> 1] >> 16 : w[e >> 1] & 0xFFFFu);
+                    if (((my_corr >> zz) & 1ull) && (c & p1) == 0) c = c >= 0 ? c + p1 : c - p1;
+                    if ((my_new >> zz) & 1ull) c = ((my_neg >> zz) & 1ull) ? -p1 : p1;
+                    w[e >> 1] = e & 1 ? (w[e >> 1] & 0xFFFFu) | ((unsigned)(unsigned short)c << 16) : (w[e >> 1] & 0xFFFF0000u) | (unsigned short)c;
+                }
+                coef4[(size_t)B * 8 + q] = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+        }
+    }
+    // the segment's data ends with its blocks: fewer than 8 bits are left, all ones, and no end-of-band run is open
+    if (!bad) {
+        const unsigned rem = end - r.pos;
+        if (eobrun != 0 || rem >= 8u || (rem > 0u && jd_peek(r, (int)rem) != (1u << rem) - 1u)) bad = true;
+    }
+    if (bad && lane == 0) D.err = 1;
+}
+
+__global__ __launch_bounds__(64) void jp_entropy_kernel(const JdFile* files, JdDyn* fdyn, const JdFile* streams, const JpScan* scans, const JdDyn* sdyn,
+                                                        const unsigned char* cleanbuf, const unsigned* seg_start, short* coefbuf, int round) {
+    const int si = blockIdx.y;
+    const JpScan& P = scans[si];
+    if (P.round != round || P.ah != 0) return;   // (refinement: jp_dcref_kernel, jp_acref_kernel)
+    const JdFile& S = streams[si];
+    const JdDyn& SD = sdyn[si];
+    const JdFile& F = files[P.file];
+    JdDyn& D = fdyn[P.file];
+    // the scan's tables in LDS: every symbol is a dependent look-up (T[0 .. 2]: the DC tables of the scan's components, T[3]: its AC table)
+    __shared__ JdHuff T[4];
+    for (int i = threadIdx.x; i < (int)(sizeof(JdHuff) / 4) * 4; i += 64) {
+        const int t = i / (int)(sizeof(JdHuff) / 4), o = i - t * (int)(sizeof(JdHuff) / 4);
+        reinterpret_cast<unsigned*>(&T[t])[o] = reinterpret_cast<const unsigned*>(t < 3 ? &S.dc[t] : &S.ac[0])[o];
+    }
+    __syncthreads();
+    const int nsegs = S.seg_cap ? (int)S.seg_cap : 1, s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= nsegs) return;
+    if (SD.nseg < 0 || SD.err) { D.err = 1; return; }
+    const unsigned* seg = seg_start + S.seg_off;
+    const unsigned total = SD.clean_len * 8u, pos0 = s ? seg[s - 1] * 8u : 0u, end = s < SD.nseg ? seg[s] * 8u : total;
+    if (pos0 >= end || end > total) { D.err = 1; return; }
+    const int per = P.restart > 0 ? P.restart : P.nmcu, m0 = s * per, m1 = min(m0 + per, P.nmcu);
+    short* coef = coefbuf + (size_t)F.coef_off * 64;
+    JdRd r; r.w = reinterpret_cast<const unsigned*>(cleanbuf + S.clean_off); r.have = 0; r.pos = pos0; r.acc = 0;
+    bool bad = m0 >= m1;
+    int eobrun = 0;
+    if (P.ss == 0) {   // DC first: the baseline state machine without AC; the prediction restarts with the segment
+        int pred[3] = {0, 0, 0};
+        for (int m = m0; m < m1 && !bad; ++m)
+            for (int i = 0; i < P.bps && !bad; ++i) {
+                const int ci = P.sci[i];
+                const int sym = jd_sym(r, T[ci]);
+                if (sym < 0 || sym > 11) { bad = true; break; }
+                pred[ci] += sym ? jd_extend(jp_bits(r, sym), sym) : 0;
+                const int B = jp_blk(F, P, m, i);
+                if (r.pos > end || (unsigned)(pred[ci] + 32768) > 65535u || (unsigned)(pred[ci] * (1 << P.al) + 32768) > 65535u || B >= F.nblk) { bad = true; break; }
+                coef[(size_t)B * 64] = (short)(pred[ci] * (1 << P.al));
+            }
+    } else {   // AC first
+        for (int m = m0; m < m1 && !bad; ++m) {
+            if (eobrun > 0) { --eobrun; continue; }
+            const int B = jp_blk(F, P, m, 0);
+            if (B >= F.nblk) { bad = true; break; }
+            short* c = coef + (size_t)B * 64;
+            for (int k = P.ss; k <= P.se; ++k) {
+                const int rs = jd_sym(r, T[3]);
+                if (rs < 0) { bad = true; break; }
+                const int run = rs >> 4, sz = rs & 15;
+                if (sz) {
+                    k += run;
+                    const int v = jd_extend(jp_bits(r, sz), sz) * (1 << P.al);
+                    if (k > P.se || r.pos > end || (unsigned)(v + 32768) > 65535u) { bad = true; break; }
+                    c[JD_ZZ[k]] = (short)v;
+                } else if (run == 15) {
+                    k += 15;
+                    if (k > P.se || r.pos > end) { bad = true; break; }   // (libjpeg lets a zero run end past the band; no encoder writes one)
+                } else {   // EOBn: this block and 2^n + extra - 1 more end here
+                    eobrun = (1 << run) + jp_bits(r, run) - 1;
+                    if (r.pos > end) bad = true;
+                    break;
+                }
+            }
+        }
+    }
+    // the segment's data ends with its blocks: fewer than 8 bits are left, all ones, and no end-of-band run is open
+    if (!bad) {
+        const unsigned rem = end - r.pos;
+        if (eobrun != 0 || rem >= 8u || (rem > 0u && jd_peek(r, (int)rem) != (1u << rem) - 1u)) bad = true;
+    }
+    if (bad) D.err = 1;
+}
+
+// DC refinement: one raw bit per block, bit i of a segment belongs to its block i
+__global__ __launch_bounds__(256) void jp_dcref_kernel(const JdFile* files, JdDyn* fdyn, const JdFile* streams, const JpScan* scans, const JdDyn* sdyn,
+                                                       const unsigned char* cleanbuf, const unsigned* seg_start, short* coefbuf, int round) {
+    const int si = blockIdx.y;
+    const JpScan& P = scans[si];
+    if (P.round != round || P.ss != 0 || P.ah == 0) return;
+    const JdFile& S = streams[si];
+    const JdDyn& SD = sdyn[si];
+    const JdFile& F = files[P.file];
+    JdDyn& D = fdyn[P.file];
+    const int nb = P.nmcu * P.bps, j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= nb) return;
+    if (SD.nseg < 0 || SD.err) { D.err = 1; return; }
+    const int per = (P.restart > 0 ? P.restart : P.nmcu) * P.bps, s = j / per, bit = j - s * per;
+    const unsigned* seg = seg_start + S.seg_off;
+    const unsigned total = SD.clean_len * 8u, pos0 = s ? seg[s - 1] * 8u : 0u, end = s < SD.nseg ? seg[s] * 8u : total;
+    const unsigned char* clean = cleanbuf + S.clean_off;
+    const unsigned pos = pos0 + (unsigned)bit;
+    if (end > total || pos >= end) { D.err = 1; return; }
+    const int m = j / P.bps, B = jp_blk(F, P, m, j - m * P.bps);
+    if (B >= F.nblk) { D.err = 1; return; }
+    if ((clean[pos >> 3] >> (7 - (pos & 7))) & 1) coefbuf[((size_t)F.coef_off + B) * 64] |= (short)(1 << P.al);
+    if (bit == min(per, nb - s * per) - 1) {   // the segment's last block: only padding may follow
+        const unsigned rem = end - pos - 1u;
+        if (rem >= 8u || (rem > 0u && (clean[(pos + 1) >> 3] & ((1u << rem) - 1u)) != (1u << rem) - 1u)) D.err = 1;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host: headers
 struct HostHeader {
     int width = 0, height = 0, ncomp = 0, hs[3] = {1, 1, 1}, vs[3] = {1, 1, 1}, tq[3] = {0, 0, 0}, td[3] = {0, 0, 0}, ta[3] = {0, 0, 0}, restart = 0;
@@ -627,13 +905,156 @@ bool build_huff(const unsigned char bits[17], const unsigned char* vals, JdHuff*
     return true;
 }
 
+// ---- progressive files: every scan's parameters, the tables in force at its SOS and its entropy-coded bytes ----
+struct ProgScan { int ncs, comp[3], ss, se, ah, al, restart; size_t off, end; JdHuff dc[3], ac; };
+struct ProgHeader { HostHeader h; std::vector<ProgScan> scans; };
+
+// 0 = a progressive file of the subset; 1 = a sequential file (SOF0 / SOF1: parse_header judges it); -1 / -2 as parse_header.
+// The progression rules are libjpeg's (jdmaster / jdphuff start_pass): what it raises or warns on is corrupt here.  A file is taken only
+// if its scans bring all 64 coefficients of every component down to Al = 0: short of that libjpeg smooths across blocks.
+int parse_progressive(const uint8_t* f, size_t n, ProgHeader* ph) {
+    HostHeader& h = ph->h;
+    if (n < 4 || f[0] != 0xFF || f[1] != 0xD8) return -1;
+    size_t p = 2;
+    bool sof = false;
+    int adobe = -1;
+    int cbits[3][64];
+    for (auto& c : cbits) for (int& v : c) v = -1;
+    for (;;) {
+        if (p + 2 > n || f[p] != 0xFF) return -1;
+        while (p < n && f[p] == 0xFF) ++p;
+        if (p >= n) return -1;
+        const int m = f[p++];
+        if (m == 0xD9) break;
+        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
+        if (p + 2 > n) return -1;
+        const size_t len = ((size_t)f[p] << 8) | f[p + 1];
+        if (len < 2 || p + len > n) return -1;
+        const uint8_t* s = f + p + 2;
+        const size_t sl = len - 2;
+        if (m == 0xDB) {
+            if (!ph->scans.empty()) return -2;   // libjpeg latches a component's table at its first scan: a later DQT is not followed here
+            size_t i = 0;
+            while (i < sl) {
+                const int pq = s[i] >> 4, t = s[i] & 15;
+                ++i;
+                if (t > 3 || pq > 1 || i + (pq ? 128 : 64) > sl) return -1;
+                for (int k = 0; k < 64; ++k) { h.q[t][H_ZZ[k]] = pq ? (unsigned short)((s[i] << 8) | s[i + 1]) : s[i]; i += pq ? 2 : 1; }
+                h.have_q[t] = true;
+            }
+        } else if (m == 0xC4) {
+            size_t i = 0;
+            while (i < sl) {
+                const int tc = s[i] >> 4, t = s[i] & 15;
+                ++i;
+                if (tc > 1 || t > 3 || i + 16 > sl) return -1;
+                int cnt = 0;
+                h.bits[tc][t][0] = 0;
+                for (int k = 1; k <= 16; ++k) { h.bits[tc][t][k] = s[i + k - 1]; cnt += s[i + k - 1]; }
+                i += 16;
+                if (cnt > 256 || i + cnt > sl) return -1;
+                memset(h.vals[tc][t], 0, 256);
+                memcpy(h.vals[tc][t], s + i, (size_t)cnt);
+                if (!huff_counts_ok(h.bits[tc][t], h.vals[tc][t], tc == 0)) return -1;
+                i += cnt;
+                h.have_h[tc][t] = true;
+            }
+        } else if (m == 0xC0 || m == 0xC1) {
+            return sof ? -1 : 1;
+        } else if (m == 0xC2) {
+            if (sl < 6 || sof) return -1;
+            if (s[0] != 8) return -2;
+            h.height = (s[1] << 8) | s[2]; h.width = (s[3] << 8) | s[4]; h.ncomp = s[5];
+            if (h.height == 0 || h.width == 0 || (h.ncomp != 1 && h.ncomp != 3)) return -2;
+            if (sl != (size_t)(6 + 3 * h.ncomp)) return -1;
+            for (int c = 0; c < h.ncomp; ++c) {
+                if (s[6 + 3 * c] != c + 1) return -2;
+                h.hs[c] = s[7 + 3 * c] >> 4; h.vs[c] = s[7 + 3 * c] & 15; h.tq[c] = s[8 + 3 * c];
+                if (h.tq[c] > 3) return -1;
+            }
+            if (h.ncomp == 1) { h.hs[0] = h.vs[0] = 1; }
+            else {
+                if (h.hs[1] != 1 || h.vs[1] != 1 || h.hs[2] != 1 || h.vs[2] != 1) return -2;
+                if (!((h.hs[0] == 1 && h.vs[0] == 1) || (h.hs[0] == 2 && h.vs[0] == 1) || (h.hs[0] == 2 && h.vs[0] == 2))) return -2;
+            }
+            sof = true;
+        } else if (m >= 0xC3 && m <= 0xCF && m != 0xC8) {   // lossless, differential, arithmetic (DAC = 0xCC included)
+            return -2;
+        } else if (m == 0xDD) {
+            if (sl != 2) return -1;
+            h.restart = (s[0] << 8) | s[1];
+        } else if (m == 0xEE) {
+            if (sl >= 12 && memcmp(s, "Adobe", 5) == 0) adobe = s[11];
+        } else if (m == 0xDC) {   // DNL
+            return -2;
+        } else if (m == 0xDA) {
+            if (!sof || sl < 1) return -1;
+            ProgScan sc;
+            sc.ncs = s[0];
+            if (sc.ncs < 1 || sc.ncs > h.ncomp || sl != (size_t)(1 + 2 * sc.ncs + 3)) return -1;
+            if (ph->scans.size() >= (size_t)JP_MAX_SCANS) return -2;
+            if (ph->scans.empty())
+                for (int c = 0; c < h.ncomp; ++c)
+                    if (!h.have_q[h.tq[c]]) return -2;   // (a table that arrives after the first scan: left to libjpeg)
+            sc.ss = s[1 + 2 * sc.ncs]; sc.se = s[2 + 2 * sc.ncs]; sc.ah = s[3 + 2 * sc.ncs] >> 4; sc.al = s[3 + 2 * sc.ncs] & 15;
+            sc.restart = h.restart;
+            if (sc.ss > sc.se || sc.se > 63 || sc.ah > 13 || sc.al > 13) return -1;
+            if (sc.ss == 0 ? sc.se != 0 : sc.ncs != 1) return -1;   // a DC scan holds DC only, an AC scan one component
+            if (sc.ah != 0 && sc.al != sc.ah - 1) return -1;
+            memset(sc.dc, 0, sizeof(sc.dc)); memset(&sc.ac, 0, sizeof(sc.ac));
+            for (int i = 0; i < sc.ncs; ++i) {
+                const int c = s[1 + 2 * i] - 1, td = s[2 + 2 * i] >> 4, ta = s[2 + 2 * i] & 15;
+                if (c < 0 || c >= h.ncomp || td > 3 || ta > 3) return -1;
+                if (i > 0 && c <= sc.comp[i - 1]) return c == sc.comp[i - 1] ? -1 : -2;
+                sc.comp[i] = c;
+                if (sc.ss != 0 && cbits[c][0] < 0) return -1;   // AC before this component's DC
+                for (int k = sc.ss; k <= sc.se; ++k) {
+                    // a coefficient that is complete (Al = 0) sent again as a first scan: libjpeg takes it in silence and the later scan wins;
+                    // here all first scans run at once and must write disjoint coefficients, so such a file is left to libjpeg
+                    if (sc.ah == 0 && cbits[c][k] == 0) return -2;
+                    if (sc.ah != (cbits[c][k] < 0 ? 0 : cbits[c][k])) return -1;   // not the successor of this coefficient's last scan
+                    cbits[c][k] = sc.al;
+                }
+                if (sc.ss == 0 && sc.ah == 0 && (!h.have_h[0][td] || !build_huff(h.bits[0][td], h.vals[0][td], &sc.dc[i]))) return -1;
+                if (sc.ss != 0 && (!h.have_h[1][ta] || !build_huff(h.bits[1][ta], h.vals[1][ta], &sc.ac))) return -1;
+            }
+            // the entropy-coded bytes run to the next marker that is neither a stuffed zero nor RSTn
+            size_t q = p + len;
+            sc.off = q;
+            for (;;) {
+                const uint8_t* x = q < n ? static_cast<const uint8_t*>(memchr(f + q, 0xFF, n - q)) : nullptr;
+                if (x == nullptr) return -1;   // no EOI
+                q = (size_t)(x - f);
+                if (q + 1 >= n || f[q + 1] == 0xFF) return -1;
+                if (f[q + 1] != 0x00 && (f[q + 1] & 0xF8) != 0xD0) break;
+                q += 2;
+            }
+            sc.end = q;
+            if (sc.end - sc.off >= ((size_t)1 << 29)) return -2;
+            ph->scans.push_back(sc);
+            p = q;
+            continue;
+        }
+        p += len;
+    }
+    if (!sof || ph->scans.empty()) return -1;
+    if (h.ncomp == 3 && adobe >= 0 && adobe != 1) return -2;
+    for (int c = 0; c < h.ncomp; ++c)
+        for (int k = 0; k < 64; ++k)
+            if (cbits[c][k] != 0) return -2;   // a coefficient never sent, or short of full precision
+    return 0;
+}
+
 // the workspace's regions for a batch with these totals: one layout sizes it and carves it (jpegdec_run)
 struct JdWorkspace {
     JdFile* F; JdDyn* D; uint8_t *raw, *clean;   // scan bytes as uploaded / un-stuffed (+ 64: the bit reader's look-ahead)
     int *keep, *rst; unsigned* seg; JdChunks C; short* coef; uint8_t* plane; int *changed, *host_rc, *status;
+    JdFile* S; JpScan* P; JdDyn* SD;   // progressive batches: one stream per scan (at most JP_MAX_SCANS per file)
 };
-JdWorkspace jd_layout(Arena& a, int n, size_t raw_total, size_t ublk_total, size_t seg_total, size_t chunk_total, size_t blk_total, size_t plane_total) {
+JdWorkspace jd_layout(Arena& a, int n, size_t raw_total, size_t ublk_total, size_t seg_total, size_t chunk_total, size_t blk_total, size_t plane_total,
+                      size_t nstreams = 0) {
     JdWorkspace w;
+    w.S = a.take<JdFile>(nstreams); w.P = a.take<JpScan>(nstreams); w.SD = a.take<JdDyn>(nstreams);
     w.F = a.take<JdFile>(n); w.D = a.take<JdDyn>(n);
     w.raw = a.take<uint8_t>(raw_total); w.clean = a.take<uint8_t>(raw_total + 64);
     w.keep = a.take<int>(ublk_total + 8); w.rst = a.take<int>(ublk_total + 8);
@@ -795,5 +1216,162 @@ int jpegdec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* size
     LOCR_CHECK(hipGetLastError());
     for (int i = 0; i < n; ++i)
         if (F[(size_t)i].valid && (dyn[(size_t)i].err || dyn[(size_t)i].nseg < 0)) status[i] = -1;
+    return 0;
+}
+
+int jpegdec_probe_progressive(const uint8_t* file, size_t n, JdProgInfo* info) {
+    ProgHeader ph;
+    int rc = parse_progressive(file, n, &ph);
+    if (rc == 1) {
+        HostHeader h;
+        rc = parse_header(file, n, &h);
+        if (info) *info = JdProgInfo{h.width, h.height, h.ncomp, h.hs[0], h.vs[0], h.restart, 0, rc == 0 ? 1 : 0};
+        return rc;
+    }
+    const HostHeader& h = ph.h;
+    if (info) *info = JdProgInfo{h.width, h.height, h.ncomp, h.hs[0], h.vs[0], ph.scans.empty() ? h.restart : ph.scans[0].restart, 1, (int)ph.scans.size()};
+    return rc;
+}
+
+int jpegdec_run_progressive(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev, int* status,
+                            hipStream_t st) {
+    std::vector<ProgHeader> PH((size_t)n);
+    std::vector<int> prc((size_t)n);
+    bool any_seq = false;
+    for (int i = 0; i < n; ++i) { prc[(size_t)i] = parse_progressive(files[i], sizes[i], &PH[(size_t)i]); any_seq = any_seq || prc[(size_t)i] == 1; }
+    // sequential files take the existing kernels (the others are hidden from that call: an empty file is refused before it is read)
+    if (any_seq) {
+        static const uint8_t none = 0;
+        std::vector<const uint8_t*> bf((size_t)n);
+        std::vector<size_t> bs((size_t)n);
+        for (int i = 0; i < n; ++i) { const bool q = prc[(size_t)i] == 1; bf[(size_t)i] = q ? files[i] : &none; bs[(size_t)i] = q ? sizes[i] : 0; }
+        const int rc = jpegdec_run(eng, bf.data(), bs.data(), n, height, width, out_dev, status, st);
+        if (rc) return rc;
+    }
+    std::vector<JdFile> F((size_t)n), S;
+    std::vector<JpScan> P;
+    std::vector<JdDyn> D((size_t)n);
+    std::vector<const uint8_t*> src;
+    size_t raw_total = 0, ublk_total = 0, seg_total = 0, blk_total = 0, plane_total = 0;
+    unsigned max_ublk = 1;
+    int max_blk = 0, max_seg = 1, max_dcref = 0, rounds = 0, any = 0;
+    for (int i = 0; i < n; ++i) {
+        JdFile& f = F[(size_t)i];
+        memset(&f, 0, sizeof(f));
+        D[(size_t)i] = JdDyn{0u, 0, 0, 0};
+        if (prc[(size_t)i] == 1) continue;
+        const HostHeader& h = PH[(size_t)i].h;
+        int rc = prc[(size_t)i];
+        if (rc == 0 && (h.width != width || h.height != height)) rc = -4;
+        status[i] = rc;
+        if (rc) continue;
+        f.valid = 1; ++any;
+        f.width = h.width; f.height = h.height; f.ncomp = h.ncomp; f.hs = h.hs[0]; f.vs = h.vs[0];
+        f.mcux = (h.width + 8 * f.hs - 1) / (8 * f.hs); f.mcuy = (h.height + 8 * f.vs - 1) / (8 * f.vs);
+        f.bpm = f.hs * f.vs + (h.ncomp == 3 ? 2 : 0);
+        f.nblk = f.mcux * f.mcuy * f.bpm;
+        int b = 0;
+        for (int c = 0; c < h.ncomp; ++c) {
+            f.first_blk_of_comp[c] = b;
+            for (int k = 0; k < (c == 0 ? f.hs * f.vs : 1); ++k) f.comp_of_blk[b++] = c;
+            f.pw[c] = f.mcux * (c == 0 ? f.hs : 1) * 8; f.ph[c] = f.mcuy * (c == 0 ? f.vs : 1) * 8;
+            f.plane_off[c] = (unsigned)plane_total; plane_total += ((size_t)f.pw[c] * f.ph[c] + 255) & ~(size_t)255;
+            memcpy(f.q[c], h.q[h.tq[c]], sizeof(f.q[c]));
+        }
+        f.coef_off = (unsigned)blk_total; blk_total += (size_t)f.nblk;
+        if (f.nblk > max_blk) max_blk = f.nblk;
+        int nref[3] = {0, 0, 0};
+        for (const ProgScan& sc : PH[(size_t)i].scans) {
+            JdFile s;
+            memset(&s, 0, sizeof(s));
+            JpScan q;
+            memset(&q, 0, sizeof(q));
+            q.file = i; q.ncs = sc.ncs; q.ss = sc.ss; q.se = sc.se; q.ah = sc.ah; q.al = sc.al;
+            for (int k = 0; k < sc.ncs; ++k) {
+                const int c = sc.comp[k];
+                q.comp[k] = c;
+                s.dc[k] = sc.dc[k];
+                if (sc.ncs > 1)
+                    for (int j = 0; j < (c == 0 ? f.hs * f.vs : 1); ++j) { q.sblk[q.bps] = f.first_blk_of_comp[c] + j; q.sci[q.bps] = k; ++q.bps; }
+            }
+            s.ac[0] = sc.ac;
+            if (sc.ncs > 1) { q.nmcu = f.mcux * f.mcuy; q.wc = f.mcux; q.hc = f.mcuy; }
+            else {   // the component's own raster
+                const int c = sc.comp[0], wc = c == 0 ? h.width : (h.width + f.hs - 1) / f.hs, hc = c == 0 ? h.height : (h.height + f.vs - 1) / f.vs;
+                q.bps = 1; q.wc = (wc + 7) / 8; q.hc = (hc + 7) / 8; q.nmcu = q.wc * q.hc;
+            }
+            q.restart = sc.restart;
+            if (sc.ah != 0) {
+                int r = 0;
+                for (int k = 0; k < sc.ncs; ++k) r = nref[sc.comp[k]] > r ? nref[sc.comp[k]] : r;
+                q.round = r + 1;
+                for (int k = 0; k < sc.ncs; ++k) nref[sc.comp[k]] = q.round;
+                if (q.round > rounds) rounds = q.round;
+                if (sc.ss == 0 && q.nmcu * q.bps > max_dcref) max_dcref = q.nmcu * q.bps;
+            }
+            s.valid = 1;
+            s.raw_len = (unsigned)(sc.end - sc.off);
+            s.raw_off = (unsigned)raw_total; s.clean_off = s.raw_off;
+            raw_total += ((size_t)s.raw_len + 16 + 255) & ~(size_t)255;
+            s.nublk = (s.raw_len + JD_UB - 1) / JD_UB; s.ublk_off = (unsigned)ublk_total; ublk_total += s.nublk;
+            s.seg_cap = sc.restart ? (unsigned)((q.nmcu + sc.restart - 1) / sc.restart) : 0; s.seg_off = (unsigned)seg_total; seg_total += s.seg_cap + 1;
+            if (s.nublk > max_ublk) max_ublk = s.nublk;
+            if ((int)s.seg_cap > max_seg) max_seg = (int)s.seg_cap;
+            S.push_back(s); P.push_back(q); src.push_back(files[i] + sc.off);
+            if (raw_total >= (1ull << 31) || blk_total >= (1ull << 31)) return locr_fail(eng, "jpeg_decode_progressive", "batch too large (2 GiB of scan data / 2^31 blocks)");
+        }
+    }
+    if (!any) return 0;
+    const int ns = (int)S.size();
+    if (ns > 65535) return locr_fail(eng, "jpeg_decode_progressive", "batch too large (more than 65535 scans: the streams are a grid's second dimension)");
+    lumina_ocr::Staging& stage = eng->jd_stage[eng->jd_stage_next]; eng->jd_stage_next ^= 1;
+    if (stage.uploaded) LOCR_CHECK(hipEventSynchronize(stage.uploaded.get()));
+    else {
+        hipEvent_t ev = nullptr;
+        LOCR_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        stage.uploaded.reset(ev);
+    }
+    LOCR_CHECK(stage.buf.reserve(raw_total, stage.uploaded.get()));
+    uint8_t* raw = stage.buf.get();
+    Arena sizing;
+    jd_layout(sizing, n, raw_total, ublk_total, seg_total, 0, blk_total, plane_total, (size_t)ns);
+    if (eng_ws_reserve(eng, sizing.off)) return 1;
+    Arena a(eng->ws.get(), eng->ws.cap);
+    const JdWorkspace w = jd_layout(a, n, raw_total, ublk_total, seg_total, 0, blk_total, plane_total, (size_t)ns);
+    if (a.overflow) return locr_fail(eng, "jpeg_decode_progressive", "workspace layout exceeds the reservation");
+    for (int k = 0; k < ns; ++k) {
+        const JdFile& s = S[(size_t)k];
+        const size_t padded = ((size_t)s.raw_len + 16 + 255) & ~(size_t)255;
+        memcpy(raw + s.raw_off, src[(size_t)k], s.raw_len);
+        memset(raw + s.raw_off + s.raw_len, 0, padded - s.raw_len);
+    }
+    LOCR_CHECK(hipMemcpyAsync(w.raw, raw, raw_total, hipMemcpyHostToDevice, st));
+    LOCR_CHECK(hipEventRecord(stage.uploaded.get(), st));
+    LOCR_CHECK(hipMemcpyAsync(w.F, F.data(), sizeof(JdFile) * n, hipMemcpyHostToDevice, st));
+    LOCR_CHECK(hipMemcpyAsync(w.D, D.data(), sizeof(JdDyn) * n, hipMemcpyHostToDevice, st));
+    LOCR_CHECK(hipMemcpyAsync(w.S, S.data(), sizeof(JdFile) * ns, hipMemcpyHostToDevice, st));
+    LOCR_CHECK(hipMemcpyAsync(w.P, P.data(), sizeof(JpScan) * ns, hipMemcpyHostToDevice, st));
+    LOCR_CHECK(hipMemsetAsync(w.clean, 0, raw_total + 64, st));
+    LOCR_CHECK(hipMemsetAsync(w.seg, 0, sizeof(unsigned) * seg_total, st));
+    LOCR_CHECK(hipMemsetAsync(w.coef, 0, blk_total * 128, st));
+    // ---- un-stuff: once over all scans of all files ----
+    hipLaunchKernelGGL(jd_mark_kernel, dim3(max_ublk, ns), dim3(256), 0, st, w.S, w.raw, w.keep, w.rst);
+    hipLaunchKernelGGL(jd_scan_kernel, dim3(ns), dim3(256), 0, st, w.S, w.keep, w.rst, w.SD);
+    hipLaunchKernelGGL(jd_compact_kernel, dim3(max_ublk, ns), dim3(256), 0, st, w.S, w.raw, w.keep, w.rst, w.SD, w.clean, w.seg);
+    // ---- entropy decode: first scans, then the refinement rounds ----
+    hipLaunchKernelGGL(jp_entropy_kernel, dim3((max_seg + 63) / 64, ns), dim3(64), 0, st, w.F, w.D, w.S, w.P, w.SD, w.clean, w.seg, w.coef, 0);
+    for (int r = 1; r <= rounds; ++r) {
+        hipLaunchKernelGGL(jp_acref_kernel, dim3(max_seg, ns), dim3(64), 0, st, w.F, w.D, w.S, w.P, w.SD, w.clean, w.seg, w.coef, r);
+        if (max_dcref > 0)
+            hipLaunchKernelGGL(jp_dcref_kernel, dim3((max_dcref + 255) / 256, ns), dim3(256), 0, st, w.F, w.D, w.S, w.P, w.SD, w.clean, w.seg, w.coef, r);
+    }
+    // ---- pixels: unchanged ----
+    hipLaunchKernelGGL(jd_idct_kernel, dim3((max_blk + 31) / 32, n), dim3(256), 0, st, w.F, w.D, w.coef, w.plane);
+    hipLaunchKernelGGL(jd_color_kernel, dim3((width + 63) / 64, (height + 3) / 4, n), dim3(256), 0, st, w.F, w.D, w.plane, out_dev, height, width);
+    LOCR_CHECK(hipMemcpyAsync(D.data(), w.D, sizeof(JdDyn) * n, hipMemcpyDeviceToHost, st));
+    LOCR_CHECK(hipStreamSynchronize(st));
+    LOCR_CHECK(hipGetLastError());
+    for (int i = 0; i < n; ++i)
+        if (F[(size_t)i].valid && D[(size_t)i].err) status[i] = -1;
     return 0;
 }

@@ -76,6 +76,8 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_jpeg_last_passes": (i32, [vp]),
         "lumina_ocr_jpeg_decode_async": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp]),
         "lumina_ocr_jpeg_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+        "lumina_ocr_jpeg_probe_progressive": (i32, [vp, sz, vp]),
+        "lumina_ocr_jpeg_decode_progressive": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_jpeg_coefficients": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
         "lumina_ocr_png_probe": (i32, [vp, sz, vp]),
         "lumina_ocr_png_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
@@ -134,6 +136,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_load_cls_weights", "lumina_ocr_cls_forward", "lumina_ocr_rec_forward",
     "lumina_ocr_ctc_decode", "lumina_ocr_ctc_decode_words", "lumina_ocr_conv2d", "lumina_ocr_read_tap", "lumina_ocr_conv_timing", "lumina_ocr_conv_timing_detail",
     "lumina_ocr_resize_lanczos", "lumina_ocr_enhance", "lumina_ocr_jpeg_encode", "lumina_ocr_jpeg_coefficients", "lumina_ocr_jpeg_probe", "lumina_ocr_jpeg_decode", "lumina_ocr_jpeg_decode_async", "lumina_ocr_jpeg_last_passes",
+    "lumina_ocr_jpeg_probe_progressive", "lumina_ocr_jpeg_decode_progressive",
     "lumina_ocr_png_probe", "lumina_ocr_png_decode", "lumina_ocr_flate_image_decode", "lumina_ocr_ccitt_decode", "lumina_ocr_fax_decode", "lumina_ocr_strip_image_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
     "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks", "lumina_ocr_selection_marks_round",
@@ -239,6 +242,28 @@ class Engine:
         sizes = (ctypes.c_size_t * n)(*[len(f) for f in files])
         self._chk(self.lib.lumina_ocr_jpeg_decode_async(self._h, ptrs, sizes, n, int(height), int(width), _ptr(out), status.data_ptr(), int(passes), self._stream()))
         return out, status
+
+    @staticmethod
+    def jpeg_probe_progressive(data: bytes):
+        """Host only. jpeg_probe that also takes progressive files (SOF2) of the device subset -> (rc, dict(width, height, ncomp, h, v,
+        restart, progressive, scans)); rc as jpeg_probe (-2: arithmetic, 12 bit, CMYK, more than 32 scans, scans short of full precision)."""
+        lib = load_library()
+        info = (ctypes.c_int * 8)()
+        rc = lib.lumina_ocr_jpeg_probe_progressive(ctypes.c_char_p(data), len(data), info)
+        return rc, dict(width=info[0], height=info[1], ncomp=info[2], h=info[3], v=info[4], restart=info[5], progressive=bool(info[6]), scans=info[7])
+
+    def jpeg_decode_progressive(self, files, height: int, width: int, out=None):
+        """jpeg_decode for batches that may hold progressive files: the same result and status codes, status 0 => byte-identical to
+        Pillow's decode.  A sequential file takes jpeg_decode's kernels."""
+        torch = _torch()
+        n = len(files)
+        if out is None:
+            out = torch.empty((n, height, width, 3), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        ptrs = (ctypes.c_char_p * n)(*files)
+        sizes = (ctypes.c_size_t * n)(*[len(f) for f in files])
+        status = (ctypes.c_int * n)()
+        self._chk(self.lib.lumina_ocr_jpeg_decode_progressive(self._h, ptrs, sizes, n, int(height), int(width), _ptr(out), status, self._stream()))
+        return out, list(status)
 
     @staticmethod
     def png_probe(data: bytes):

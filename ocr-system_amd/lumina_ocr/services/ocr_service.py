@@ -116,6 +116,10 @@ class OCRService:
         # "simple" = the L > 128 threshold the reference falls back to without OpenCV (image_preprocessing.py:473-475)
         b = os.environ.get("PREPROCESSING_APPLY_BINARIZE", "false").lower()
         self.device_jpeg = os.environ.get("LUMINA_OCR_DEVICE_JPEG", "1").lower() not in ("0", "false", "no")   # baseline JPEG inputs are decoded on the device
+        # LUMINA_OCR_PROGRESSIVE_JPEG=1: progressive JPEG files (SOF2) of the device subset, and progressive /DCTDecode pages of
+        # LUMINA_OCR_PDF_SCANS, are decoded on the device as well (lumina_ocr_jpeg_decode_progressive).  Off by default: a progressive
+        # file is then decoded by Pillow, and exactly the calls made without the option are made.
+        self.progressive_jpeg = os.environ.get("LUMINA_OCR_PROGRESSIVE_JPEG", "0").lower() not in ("", "0", "false", "no")
         # LUMINA_OCR_DEVICE_PNG=1: non-interlaced PNG inputs of 8 bits or less and lazily opened PNG pages (pdf2image) are decoded on the
         # device.  Off by default: measured slower than Pillow for single pages and for 300 dpi batches
         self.device_png = os.environ.get("LUMINA_OCR_DEVICE_PNG", "0").lower() not in ("0", "false", "no")
@@ -479,12 +483,13 @@ class OCRService:
             if orientation not in range(0, 9):
                 return None
             from ..engine import Engine
-            rc, info = Engine.jpeg_probe(data)
+            rc, info = Engine.jpeg_probe_progressive(data) if self.progressive_jpeg else Engine.jpeg_probe(data)
             if rc != 0 or (info["width"], info["height"]) != image.size:
                 return None
             self._ensure_engine()
             with self._device_ctx():
-                out, status = self._engine.jpeg_decode([data], info["height"], info["width"])
+                decode = self._engine.jpeg_decode_progressive if self.progressive_jpeg else self._engine.jpeg_decode
+                out, status = decode([data], info["height"], info["width"])
                 if status != [0]:
                     return None
                 return self._engine.exif_transpose(out, orientation)     # auto_orient (image_preprocessing.py:213), on the device as well
@@ -727,7 +732,8 @@ class OCRService:
                 streams = [bytes(r.stream) for r in recs]
                 try:
                     if filt == "DCTDecode":
-                        out, status = eng.jpeg_decode(streams, h, w) if self.device_jpeg else (None, [-2] * len(idxs))
+                        decode = eng.jpeg_decode_progressive if self.progressive_jpeg else eng.jpeg_decode
+                        out, status = decode(streams, h, w) if self.device_jpeg else (None, [-2] * len(idxs))
                     elif filt in ("LZWDecode", "RunLengthDecode"):   # one-strip pages of the strip decoders
                         codec = 5 if filt == "LZWDecode" else 32773
                         params = [(codec, r.params["predictor"], r.params["components"], r.params["bits"], int(r.params["indexed"]),
@@ -987,7 +993,7 @@ class OCRService:
     # ---- status (:759-795) ----
     def get_status(self) -> Dict[str, Any]:
         st = {"client_initialized": self._pipeline is not None, "model_id": "dbnet-r18vd+crnn-mv3", "max_dimension": self.max_dimension,
-              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "aztec": self._use_aztec, "aztec_max_layers": self._aztec_max_layers_status(), "device_pdf": self.device_pdf, "device_tiff": self.device_tiff, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
+              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "aztec": self._use_aztec, "aztec_max_layers": self._aztec_max_layers_status(), "device_pdf": self.device_pdf, "progressive_jpeg": self.progressive_jpeg, "device_tiff": self.device_tiff, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
         if self._engine is not None:
             st["engine_version"] = self._engine.version()
             st["num_classes"] = self._engine.num_classes
