@@ -46,7 +46,8 @@ const char* lumina_ocr_version(void);
  * bit-identical either way): "fuse_head", "fuse_pool", "fuse_stem", "fuse_mb", "fpn_multi", "conv_ring", "ring_orient", "conv_big_min",
  * "blocked_layout" (experiment: fails loudly when a blocked tensor would reach a kernel other than the ring kernel);
  * "svtr_f16" (storage type of the next SVTR load), "conv2d_variant" (kernel choice of lumina_ocr_conv2d, parity tests);
- * "png_sub_batch_mb" (lumina_ocr_png_decode: MB of inflated scanlines per sub-batch, default 768 — bounds the workspace a PNG batch reserves) */
+ * "png_sub_batch_mb" (lumina_ocr_png_decode: MB of inflated scanlines per sub-batch, default 768 — bounds the workspace a PNG batch reserves);
+ * "jp2_sub_batch_mb" (lumina_ocr_jp2_decode: MB of coefficient planes per sub-batch, default 4096) */
 int lumina_ocr_set_option(lumina_ocr_t* h, const char* key, int value);
 
 /* weights: "LOCW" container (ocr-system_amd/lumina_ocr/arch.py write_blob), host memory.
@@ -526,6 +527,34 @@ int lumina_ocr_jpeg_decode_progressive(lumina_ocr_t* h, const uint8_t* const* fi
  * non-zero status is not written.  Synchronises `stream`. */
 int lumina_ocr_png_probe(const uint8_t* file, size_t size, int info[8]);
 int lumina_ocr_png_decode(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev,
+                          int* status, void* stream);
+
+/* JPEG 2000 decode on the device — the pixel work of the reference's Image.open(...) + convert('RGB') for .jp2 / .j2k inputs, and the
+ * /JPXDecode pages of scanned PDFs.  The contract is the JPEG pair's: status 0 => byte-identical to Pillow's (OpenJPEG's) decode; any
+ * other status => the file is left to Pillow.
+ * Read: a raw codestream or a JP2 / JPX-baseline file (ihdr, one colr of method 1 with sRGB or grey, the first jp2c; box length 0 and
+ * the 64-bit box length are honoured); one tile, origin 0, 1 or 3 components, 8 bit unsigned, no sub-sampling; the 5/3 reversible
+ * transform with 0-6 levels, lossless or cut short by up to 32 quality layers; the five progression orders; one precinct per
+ * resolution; code-blocks from 4 x 4 to 64 x 64; code-block style 0; with or without the reversible colour transform; COM, PLT and TLM
+ * are skipped.
+ * -2 (valid, outside the subset): the 9/7 irreversible transform, tiles, user precincts, a code-block side over 64, any code-block
+ * style bit, SOP / EPH, POC / RGN / PPM / PPT / PLM / CRG, a COC or QCC that differs from COD / QCD (or any of the four in a tile-part
+ * header), a non-zero origin, sub-sampling, 2 or 4+ components, another bit depth or signed samples, Rsiz other than 0, pclr / cmap /
+ * cdef / opct / bpcc boxes, colr of method 2 or sYCC, more than 32 layers or 6 levels, a side over 16384, more than 15 magnitude
+ * bit-planes in a sub-band.  -1: anything irregular — the decoder is strict where OpenJPEG is lenient (segments out of order or of the
+ * wrong length, a packet header past its tile-part, more coding passes or zero bit-planes than Mb allows, data left over after the last
+ * packet, a missing EOC, bytes after it).
+ * lumina_ocr_jp2_probe (host only, no handle): the boxes, the headers and the walk over every packet header; no pixel is decoded.
+ * info = {width, height, components, decomposition levels, layers, progression order (0 LRCP, 1 RLCP, 2 RPCL, 3 PCRL, 4 CPRL),
+ * code-block width, code-block height}, filled as far as the headers were read.  Returns 0, -1 or -2.
+ * lumina_ocr_jp2_reason: the reason behind the last non-zero lumina_ocr_jp2_probe result of the calling thread when `code` is that
+ * result (a static string, for logs); otherwise the general meaning of `code`.
+ * lumina_ocr_jp2_decode: files / sizes are HOST arrays of n file images, all height x width; out_dev uint8 [n][height][width][3] (a grey
+ * file: its value on all three channels); status HOST int [n]: 0 ok, -1, -2, -4 another size.  A page with a non-zero status is not
+ * written.  Synchronises `stream`. */
+int lumina_ocr_jp2_probe(const uint8_t* file, size_t size, int info[8]);
+const char* lumina_ocr_jp2_reason(int code);
+int lumina_ocr_jp2_decode(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev,
                           int* status, void* stream);
 
 /* Scanned PDF pages — the images of a PDF whose pages are one image each (utils/pdf_pages.py finds them), decoded at their own sample

@@ -19,6 +19,7 @@
 #include "jpeg.h"
 #include "jpegdec.h"
 #include "lzw.h"
+#include "jp2dec.h"
 #include "pngdec.h"
 #include "ccitt.h"
 #include "stem_conv.h"
@@ -172,6 +173,7 @@ int lumina_ocr_set_option(lumina_ocr_t* h, const char* key, int value) {
     else if (!strcmp(key, "tail_group")) h->tail_group = value > 0 ? value : 0;
     else if (!strcmp(key, "svtr_f16")) h->svtr_f16 = value < 0 ? -1 : (value != 0);
     else if (!strcmp(key, "png_sub_batch_mb")) h->pd_sub_batch_mb = value > 0 ? value : 1;
+    else if (!strcmp(key, "jp2_sub_batch_mb")) h->jp_sub_batch_mb = value > 0 ? value : 1;
     else if (!strcmp(key, "conv2d_variant")) h->conv2d_variant = value < 0 || value > 2 ? 0 : value;
     else return locr_fail(h, "set_option: unknown key", key);
     return 0;
@@ -537,6 +539,46 @@ int lumina_ocr_png_decode(lumina_ocr_t* h, const uint8_t* const* files, const si
     BIND(h);
     API_TRY
     return pngdec_run(h, files, sizes, n, height, width, out_dev, status, (hipStream_t)stream);
+    API_CATCH(h)
+}
+
+namespace {
+thread_local int jp2_last_code = 0;
+thread_local const char* jp2_last_reason = "";
+}  // namespace
+
+int lumina_ocr_jp2_probe(const uint8_t* file, size_t size, int info[8]) {
+    if (!file || !info) return -1;
+    Jp2Probe p{};
+    int rc = -1;
+    try {
+        rc = jp2dec_probe(file, size, &p);
+    } catch (const std::exception&) {   // (allocation failure: the file is left to the host decoder)
+        p.reason = "out of memory while reading the packet headers";
+        rc = -2;
+    }
+    for (int i = 0; i < 8; ++i) info[i] = p.info[i];
+    jp2_last_code = rc; jp2_last_reason = p.reason ? p.reason : "";
+    return rc;
+}
+
+const char* lumina_ocr_jp2_reason(int code) {
+    if (code != 0 && code == jp2_last_code && jp2_last_reason[0]) return jp2_last_reason;
+    switch (code) {
+        case 0: return "read";
+        case -1: return "corrupt or irregular JPEG 2000 file";
+        case -2: return "valid JPEG 2000 outside the device subset";
+        case -4: return "another size than the batch";
+    }
+    return "unknown status";
+}
+
+int lumina_ocr_jp2_decode(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev, int* status,
+                          void* stream) {
+    if (!h || !files || !sizes || !out_dev || !status || n <= 0 || height <= 0 || width <= 0) return locr_fail(h, "jp2_decode", "bad arguments");
+    BIND(h);
+    API_TRY
+    return jp2dec_run(h, files, sizes, n, height, width, out_dev, status, (hipStream_t)stream);
     API_CATCH(h)
 }
 

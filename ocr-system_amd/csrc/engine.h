@@ -163,6 +163,8 @@ struct lumina_ocr {
     int jd_stage_next = 0;
     Staging pd_stage;   // pinned staging of the PNG decoder's gathered IDAT payloads (pngdec.hip)
     int pd_sub_batch_mb = 768;   // PNG decoder: filtered-scanline MB per sub-batch (64 A4 RGB pages at 300 dpi are 1.7 GB); sizes its workspace
+    Staging jp_stage;   // pinned staging of the JPEG 2000 decoder's block records and coded bytes (jp2dec.hip)
+    int jp_sub_batch_mb = 4096;   // JPEG 2000 decoder: MB of coefficient planes per sub-batch (an A4 RGB page at 200 dpi takes 93 MB)
     float* dk_trig = nullptr; short* dk_wtab = nullptr;   // de-skew tables (deskew.h), uploaded at first use
 };
 

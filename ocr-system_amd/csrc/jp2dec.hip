@@ -1,0 +1,237 @@
+// JPEG 2000 decoder on the device (see jp2dec.h).  The host reads the boxes and headers and walks the packet headers (jp2_parse.h:
+// tier 2, kilobytes per page, no pixel).  The device does the rest:
+//   j2_tier1   one wave64 per code-block, every block of every page of the sub-batch in one launch: the MQ decoder and the three
+//              coding passes per bit-plane (jp2_t1.h).  The decision walk is serial and runs on one lane over row bit-maps in LDS
+//              (64-bit words, one per block row); the wave clears the state and writes the coefficients out.  10.5 KB of LDS per
+//              wave: 15 waves per CU.
+//   j2_dwt_h / j2_dwt_v   the inverse 5/3 lifting, level by level, horizontal then vertical, between two int32 planes
+//   j2_finish  inverse reversible colour transform, level shift, clamp -> RGB u8
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "engine.h"
+#include "jp2_parse.h"
+#include "jp2_t1.h"
+#include "jp2dec.h"
+
+namespace {
+
+struct J2Block {
+    unsigned long long data_off;   // its coded bytes (the segments of all layers, concatenated) in the sub-batch's byte buffer
+    unsigned data_len;
+    int plane;                     // index of its component plane in the sub-batch
+    int x, y;                      // rectangle in the plane
+    unsigned char w, h, orient, nbps;
+    int passes;
+};
+struct J2Page { int levels, comps, mct, out_index, plane0; };
+
+__global__ __launch_bounds__(64) void j2_tier1(const J2Block* __restrict__ blocks, const uint8_t* __restrict__ bytes, int* __restrict__ coef,
+                                               int height, int width) {
+    __shared__ Jp2T1State S;
+    const J2Block b = blocks[blockIdx.x];
+    const int lane = threadIdx.x;
+    unsigned* words = reinterpret_cast<unsigned*>(&S);
+    for (unsigned i = lane; i < sizeof(Jp2T1State) / 4; i += 64) words[i] = 0;
+    __syncthreads();
+    jp2_t1_tables(S, lane, 64);
+    __syncthreads();
+    if (lane == 0) jp2_t1_walk(S, bytes + b.data_off, b.data_len, b.w, b.h, b.orient, b.nbps, b.passes);
+    __syncthreads();
+    int* dst = coef + (size_t)b.plane * height * width;
+    const int n = (int)b.w * b.h;
+    for (int i = lane; i < n; i += 64) {
+        const int y = i / b.w, x = i - y * b.w;
+        dst[(size_t)(b.y + y) * width + b.x + x] = jp2_t1_value(S, y, x);
+    }
+}
+
+__device__ inline int j2_cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// one step of the inverse transform: the pages whose `levels` reach `step` rebuild their resolution `step` (rw x rh, top left of the plane)
+__global__ __launch_bounds__(256) void j2_dwt_h(const J2Page* __restrict__ pages, const int* __restrict__ src, int* __restrict__ dst, int height,
+                                                int width, int step) {
+    const J2Page pg = pages[blockIdx.z];
+    if (step > pg.levels || (int)blockIdx.y >= pg.comps) return;
+    const int sh = pg.levels - step, rw = j2_cdiv(width, 1 << sh), rh = j2_cdiv(height, 1 << sh), np = (rw + 1) / 2;
+    const size_t plane = (size_t)(pg.plane0 + blockIdx.y) * height * width;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < (long long)rh * np; i += (long long)gridDim.x * 256) {
+        const int y = (int)(i / np), k = (int)(i - (long long)y * np);
+        const int* line = src + plane + (size_t)y * width;
+        int* o = dst + plane + (size_t)y * width;
+        o[2 * k] = jp2_lift_even(line, 1, rw, k);
+        if (2 * k + 1 < rw) o[2 * k + 1] = jp2_lift_odd(line, 1, rw, k);
+    }
+}
+
+__global__ __launch_bounds__(256) void j2_dwt_v(const J2Page* __restrict__ pages, const int* __restrict__ src, int* __restrict__ dst, int height,
+                                                int width, int step) {
+    const J2Page pg = pages[blockIdx.z];
+    if (step > pg.levels || (int)blockIdx.y >= pg.comps) return;
+    const int sh = pg.levels - step, rw = j2_cdiv(width, 1 << sh), rh = j2_cdiv(height, 1 << sh), np = (rh + 1) / 2;
+    const size_t plane = (size_t)(pg.plane0 + blockIdx.y) * height * width;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < (long long)np * rw; i += (long long)gridDim.x * 256) {
+        const int k = (int)(i / rw), x = (int)(i - (long long)k * rw);
+        const int* line = src + plane + x;
+        int* o = dst + plane + x;
+        o[(size_t)(2 * k) * width] = jp2_lift_even(line, width, rh, k);
+        if (2 * k + 1 < rh) o[(size_t)(2 * k + 1) * width] = jp2_lift_odd(line, width, rh, k);
+    }
+}
+
+__device__ inline uint8_t j2_sample(int v) { v += 128; return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
+
+__global__ __launch_bounds__(256) void j2_finish(const J2Page* __restrict__ pages, const int* __restrict__ coef, uint8_t* __restrict__ out, int height, int width) {
+    const J2Page pg = pages[blockIdx.y];
+    const size_t npx = (size_t)height * width;
+    const int* p0 = coef + (size_t)pg.plane0 * npx;
+    uint8_t* o = out + (size_t)pg.out_index * npx * 3;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npx; i += (size_t)gridDim.x * 256) {
+        int r, g, b;
+        if (pg.comps == 1) {
+            r = g = b = p0[i];
+        } else if (pg.mct) {
+            const int y = p0[i], u = p0[npx + i], v = p0[2 * npx + i];
+            g = y - ((u + v) >> 2); r = v + g; b = u + g;
+        } else {
+            r = p0[i]; g = p0[npx + i]; b = p0[2 * npx + i];
+        }
+        o[3 * i] = j2_sample(r); o[3 * i + 1] = j2_sample(g); o[3 * i + 2] = j2_sample(b);
+    }
+}
+
+struct J2Workspace { J2Block* blocks; J2Page* pages; uint8_t* bytes; int *a, *b; };
+J2Workspace j2_layout(Arena& a, size_t nblocks, size_t nbytes, int pages, size_t planes, int height, int width) {
+    J2Workspace w;
+    w.blocks = a.take<J2Block>(nblocks); w.pages = a.take<J2Page>((size_t)pages); w.bytes = a.take<uint8_t>(nbytes);
+    w.a = a.take<int>(planes * height * width); w.b = a.take<int>(planes * height * width);
+    return w;
+}
+
+}  // namespace
+
+size_t jp2dec_workspace_bytes(size_t nblocks, size_t nbytes, int pages, size_t planes, int height, int width) {
+    Arena a;
+    j2_layout(a, nblocks, nbytes, pages, planes, height, width);
+    return a.off;
+}
+
+int jp2dec_probe(const uint8_t* file, size_t n, Jp2Probe* out) {
+    Jp2File f;
+    const int rc = jp2_parse(file, n, &f);
+    memcpy(out->info, f.info, sizeof(f.info));
+    out->reason = f.reason;
+    return rc;
+}
+
+int jp2dec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev, int* status,
+               hipStream_t st) {
+    lumina_ocr::Staging& stage = eng->jp_stage;
+    if (!stage.uploaded) {
+        hipEvent_t ev = nullptr;
+        LOCR_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        stage.uploaded.reset(ev);
+    }
+    const size_t npx = (size_t)height * width;
+    const size_t budget = (size_t)eng->jp_sub_batch_mb << 20;
+    constexpr size_t MAX_PAGES = 65535;   // a sub-batch's pages are a grid dimension of the transform and colour launches
+    int i0 = 0;
+    Jp2File held;          // the page that did not fit the last sub-batch: it opens the next one and is not parsed again
+    bool holding = false;
+    while (i0 < n) {
+        // a sub-batch: pages until their coefficient planes (two int32 copies) pass the budget, at least one page
+        std::vector<Jp2File> F;
+        std::vector<int> index;
+        size_t planes = 0, nblocks = 0, nbytes = 0;
+        int i1 = i0;
+        for (; i1 < n; ++i1) {
+            Jp2File f;
+            if (holding) {
+                f = std::move(held);
+                holding = false;
+            } else {
+                int rc = jp2_parse(files[i1], sizes[i1], &f);
+                if (rc == 0 && (f.width != width || f.height != height)) rc = -4;
+                status[i1] = rc;
+                if (rc) continue;
+            }
+            if (!index.empty() && ((planes + (size_t)f.comps) * npx * 8 > budget || index.size() == MAX_PAGES)) {
+                held = std::move(f);
+                holding = true;
+                break;
+            }
+            planes += (size_t)f.comps;
+            for (const Jp2Block& K : f.blocks)
+                if (K.passes) {
+                    ++nblocks;
+                    size_t len = 0;
+                    for (int s = K.seg_head; s >= 0; s = f.segs[(size_t)s].next) len += f.segs[(size_t)s].len;
+                    nbytes += len;
+                }
+            F.push_back(std::move(f));
+            index.push_back(i1);
+        }
+        const int np = (int)index.size();
+        if (np) {
+            // staging: [J2Block x nblocks][J2Page x np][bytes]
+            const size_t blocks_b = (sizeof(J2Block) * nblocks + 255) & ~(size_t)255, pages_b = (sizeof(J2Page) * np + 255) & ~(size_t)255;
+            LOCR_CHECK(hipEventSynchronize(stage.uploaded.get()));
+            LOCR_CHECK(stage.buf.reserve(blocks_b + pages_b + nbytes + 256, stage.uploaded.get()));
+            J2Block* hb = reinterpret_cast<J2Block*>(stage.buf.get());
+            J2Page* hp = reinterpret_cast<J2Page*>(stage.buf.get() + blocks_b);
+            uint8_t* hbytes = stage.buf.get() + blocks_b + pages_b;
+            size_t bi = 0, off = 0;
+            int plane0 = 0, max_levels = 0;
+            for (int k = 0; k < np; ++k) {
+                const Jp2File& f = F[(size_t)k];
+                hp[k] = J2Page{f.levels, f.comps, f.mct, index[(size_t)k], plane0};
+                max_levels = std::max(max_levels, f.levels);
+                for (const Jp2Block& K : f.blocks) {
+                    if (!K.passes) continue;
+                    J2Block& b = hb[bi++];
+                    b.data_off = off; b.plane = plane0 + K.comp; b.x = K.x; b.y = K.y;
+                    b.w = (unsigned char)K.w; b.h = (unsigned char)K.h; b.orient = (unsigned char)K.orient; b.nbps = (unsigned char)(K.mb - K.zbp);
+                    b.passes = K.passes;
+                    for (int s = K.seg_head; s >= 0; s = f.segs[(size_t)s].next) {
+                        memcpy(hbytes + off, files[index[(size_t)k]] + f.segs[(size_t)s].off, f.segs[(size_t)s].len);
+                        off += f.segs[(size_t)s].len;
+                    }
+                    b.data_len = (unsigned)(off - b.data_off);
+                }
+                plane0 += f.comps;
+            }
+            Arena sizing;
+            j2_layout(sizing, nblocks, nbytes + 256, np, planes, height, width);
+            if (eng_ws_reserve(eng, sizing.off)) return 1;
+            Arena a(eng->ws.get(), eng->ws.cap);
+            const J2Workspace w = j2_layout(a, nblocks, nbytes + 256, np, planes, height, width);
+            if (a.overflow) return locr_fail(eng, "jp2_decode", "workspace layout exceeds the reservation");
+            if (nblocks) LOCR_CHECK(hipMemcpyAsync(w.blocks, hb, sizeof(J2Block) * nblocks, hipMemcpyHostToDevice, st));
+            LOCR_CHECK(hipMemcpyAsync(w.pages, hp, sizeof(J2Page) * np, hipMemcpyHostToDevice, st));
+            if (nbytes) LOCR_CHECK(hipMemcpyAsync(w.bytes, hbytes, nbytes, hipMemcpyHostToDevice, st));
+            LOCR_CHECK(hipEventRecord(stage.uploaded.get(), st));
+            LOCR_CHECK(hipMemsetAsync(w.a, 0, planes * npx * sizeof(int), st));   // blocks no layer includes are zero
+            if (nblocks) hipLaunchKernelGGL(j2_tier1, dim3((unsigned)nblocks), dim3(64), 0, st, w.blocks, w.bytes, w.a, height, width);
+            for (int step = 1; step <= max_levels; ++step) {
+                size_t work = 0;   // the largest resolution any page rebuilds at this step
+                for (const Jp2File& f : F)
+                    if (step <= f.levels) {
+                        const int sh = f.levels - step;
+                        work = std::max(work, (size_t)((height + (1 << sh) - 1) >> sh) * (size_t)((width + (1 << sh) - 1) >> sh));
+                    }
+                const dim3 grid((unsigned)std::min<size_t>((work / 2 + 255) / 256 + 1, 2048), 3, (unsigned)np);
+                hipLaunchKernelGGL(j2_dwt_h, grid, dim3(256), 0, st, w.pages, w.a, w.b, height, width, step);
+                hipLaunchKernelGGL(j2_dwt_v, grid, dim3(256), 0, st, w.pages, w.b, w.a, height, width, step);
+            }
+            hipLaunchKernelGGL(j2_finish, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 2048), (unsigned)np), dim3(256), 0, st, w.pages, w.a, out_dev,
+                               height, width);
+            LOCR_CHECK(hipStreamSynchronize(st));
+            LOCR_CHECK(hipGetLastError());
+        }
+        i0 = i1;
+    }
+    return 0;
+}

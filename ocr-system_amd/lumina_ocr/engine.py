@@ -81,6 +81,9 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_jpeg_coefficients": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
         "lumina_ocr_png_probe": (i32, [vp, sz, vp]),
         "lumina_ocr_png_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+        "lumina_ocr_jp2_probe": (i32, [vp, sz, vp]),
+        "lumina_ocr_jp2_reason": (c.c_char_p, [i32]),
+        "lumina_ocr_jp2_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_flate_image_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
         "lumina_ocr_ccitt_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
         "lumina_ocr_fax_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
@@ -137,6 +140,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_ctc_decode", "lumina_ocr_ctc_decode_words", "lumina_ocr_conv2d", "lumina_ocr_read_tap", "lumina_ocr_conv_timing", "lumina_ocr_conv_timing_detail",
     "lumina_ocr_resize_lanczos", "lumina_ocr_enhance", "lumina_ocr_jpeg_encode", "lumina_ocr_jpeg_coefficients", "lumina_ocr_jpeg_probe", "lumina_ocr_jpeg_decode", "lumina_ocr_jpeg_decode_async", "lumina_ocr_jpeg_last_passes",
     "lumina_ocr_jpeg_probe_progressive", "lumina_ocr_jpeg_decode_progressive",
+    "lumina_ocr_jp2_probe", "lumina_ocr_jp2_reason", "lumina_ocr_jp2_decode",
     "lumina_ocr_png_probe", "lumina_ocr_png_decode", "lumina_ocr_flate_image_decode", "lumina_ocr_ccitt_decode", "lumina_ocr_fax_decode", "lumina_ocr_strip_image_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
     "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks", "lumina_ocr_selection_marks_round",
@@ -288,6 +292,35 @@ class Engine:
         sizes = (ctypes.c_size_t * n)(*[len(f) for f in files])
         status = (ctypes.c_int * n)()
         self._chk(self.lib.lumina_ocr_png_decode(self._h, ptrs, sizes, n, int(height), int(width), _ptr(out), status, self._stream()))
+        return out, list(status)
+
+    JP2_ORDERS = ("LRCP", "RLCP", "RPCL", "PCRL", "CPRL")
+
+    @staticmethod
+    def jp2_probe(data: bytes):
+        """Host only: the boxes, the headers and every packet header of a JPEG 2000 file (JP2 / JPX-baseline or a raw codestream); no
+        pixel is decoded. -> (rc, dict(width, height, components, levels, layers, progression, codeblock_width, codeblock_height,
+        reason)); rc 0: the device decodes this file, -2: valid outside the subset (9/7, tiles, precincts ...: decode with Pillow as the
+        reference does), -1: corrupt or irregular.  reason: why a non-zero rc was given, for logs."""
+        lib = load_library()
+        info = (ctypes.c_int * 8)()
+        rc = lib.lumina_ocr_jp2_probe(ctypes.c_char_p(data), len(data), info)
+        return rc, dict(width=info[0], height=info[1], components=info[2], levels=info[3], layers=info[4], progression=info[5],
+                        codeblock_width=info[6], codeblock_height=info[7], reason=lib.lumina_ocr_jp2_reason(rc).decode() if rc else "")
+
+    def jp2_decode(self, files, height: int, width: int, out=None):
+        """JPEG 2000 file images (a sequence of bytes objects, all height x width) -> (uint8 [n,H,W,3] device, status list): the pixels of
+        the reference's Image.open(...).convert('RGB') for .jp2 / .j2k inputs, byte-identical to Pillow.  status[i] != 0: page i was not
+        decoded (-1 corrupt, -2 outside the device subset, -4 another size) and is left to Pillow."""
+        torch = _torch()
+        n = len(files)
+        if out is None:
+            out = torch.empty((n, height, width, 3), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        files = [f if isinstance(f, bytes) else bytes(f) for f in files]
+        ptrs = (ctypes.c_char_p * n)(*files)
+        sizes = (ctypes.c_size_t * n)(*[len(f) for f in files])
+        status = (ctypes.c_int * n)()
+        self._chk(self.lib.lumina_ocr_jp2_decode(self._h, ptrs, sizes, n, int(height), int(width), _ptr(out), status, self._stream()))
         return out, list(status)
 
     def _stream_batch(self, streams, height: int, width: int, out):

@@ -43,6 +43,9 @@ logger = logging.getLogger(__name__)
 
 SUPPORTED_IMAGE_TYPES = ("png", "jpg", "jpeg", "webp", "bmp", "tiff")
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+JP2_SIGNATURE = b"\x00\x00\x00\x0cjP  \r\n\x87\n"   # the signature box of a JP2 / JPX file
+J2K_SIGNATURE = b"\xff\x4f\xff\x51"                 # SOC + SIZ: a raw JPEG 2000 codestream
+JP2_FILE_TYPES = ("jp2", "j2k", "jpx")                # process_document sends these to the image path with LUMINA_OCR_DEVICE_JP2=1
 
 
 @dataclass
@@ -131,6 +134,12 @@ class OCRService:
         # the device, process_tiff_sync reads every page of a multi-page TIFF, and process_document sends "tiff" and "tif" there.  Off by
         # default: a TIFF is then decoded by Pillow, first frame only, and every output is exactly the one without the option.
         self.device_tiff = os.environ.get("LUMINA_OCR_DEVICE_TIFF", "0").lower() not in ("", "0", "false", "no")
+        # LUMINA_OCR_DEVICE_JP2=1: JPEG 2000 inputs (JP2 / JPX-baseline files and raw codestreams, recognised by their magic) of the
+        # device subset (5/3 reversible, one tile ...: lumina_ocr_jp2_decode) are decoded on the device, lazily opened JPEG 2000 pages
+        # of a batch are grouped by size, process_document takes "jp2", "j2k" and "jpx", and with LUMINA_OCR_PDF_SCANS=1 the /JPXDecode
+        # pages of a scanned PDF are read as well.  Off by default: exactly the calls made without the option are made.
+        self.device_jp2 = os.environ.get("LUMINA_OCR_DEVICE_JP2", "0").lower() not in ("", "0", "false", "no")
+        self._jp2_reasons_logged: set = set()
         self.apply_binarize = "adaptive" if b in ("1", "true", "yes", "adaptive") else ("simple" if b == "simple" else None)
         self._device = int(os.environ.get("LUMINA_OCR_DEVICE", os.environ.get("LOCAL_RANK", 0)))
         self._det_weights = os.environ.get("LUMINA_OCR_DET_WEIGHTS", "")
@@ -551,8 +560,68 @@ class OCRService:
             return None
         return self._process_single_image_sync(image, page_number, decoded=decoded)
 
+    @staticmethod
+    def _is_jp2(head: bytes) -> bool:
+        return head[:12] == JP2_SIGNATURE or head[:4] == J2K_SIGNATURE
+
+    def _jp2_probe(self, data: bytes, size) -> Optional[Dict[str, Any]]:
+        """The probe's info when the device decodes this JPEG 2000 file and its size is `size`, else None, the reason logged once."""
+        from ..engine import Engine
+        rc, info = Engine.jp2_probe(data)
+        if rc == 0 and (info["width"], info["height"]) == tuple(size):
+            return info
+        reason = info["reason"] if rc else "size differs from the opened image's"
+        if reason not in self._jp2_reasons_logged:
+            self._jp2_reasons_logged.add(reason)
+            logger.info("JPEG 2000 input left to Pillow (status %d): %s", rc, reason)
+        return None
+
+    def _decode_jp2_on_device(self, data: bytes, image: Image.Image):
+        """A JPEG 2000 file of the device subset -> device tensor [1,H,W,3] (lumina_ocr_jp2_decode: byte-identical to Pillow), or None:
+        Pillow decodes.  `image` is the lazily opened file; one that carries EXIF or XMP is left to the host path and its auto_orient."""
+        try:
+            if image.format != "JPEG2000" or "exif" in image.info or "XML:com.adobe.xmp" in image.info or "xmp" in image.info:
+                return None
+            self._ensure_engine()   # (before the probe loads the engine library: see _decode_png_on_device)
+            info = self._jp2_probe(data, image.size)
+            if info is None:
+                return None
+            with self._device_ctx():
+                out, status = self._engine.jp2_decode([data], info["height"], info["width"])
+                return out if status == [0] else None
+        except Exception as e:       # any doubt: the reference's own path
+            logger.warning("device JPEG 2000 decode not used: %s", e)
+            return None
+
+    def _process_jp2_on_device(self, image_source: Union[str, Path, bytes], page_number: int) -> Optional[OCROutput]:
+        """A JPEG 2000 path / bytes (recognised by magic, never by extension) whose pixels the device decodes -> its result; None: today's path."""
+        try:
+            if isinstance(image_source, bytes):
+                data = image_source
+            else:
+                with open(image_source, "rb") as f:
+                    if not self._is_jp2(f.read(12)):
+                        return None
+                data = Path(image_source).read_bytes()
+        except OSError:
+            return None
+        if not self._is_jp2(data[:12]):
+            return None
+        try:
+            image = Image.open(io.BytesIO(data))
+        except Exception:
+            return None
+        decoded = self._decode_jp2_on_device(data, image)
+        if decoded is None:
+            return None
+        return self._process_single_image_sync(image, page_number, decoded=decoded)
+
     def process_image_sync(self, image_source: Union[str, Path, Image.Image, bytes], page_number: int = 1) -> OCROutput:
         data = None
+        if self.device_jp2 and isinstance(image_source, (bytes, str, Path)):
+            r = self._process_jp2_on_device(image_source, page_number)
+            if r is not None:
+                return r
         if self.device_tiff and isinstance(image_source, (bytes, str, Path)):
             r = self._process_tiff_on_device(image_source, page_number)
             if r is not None:
@@ -631,6 +700,39 @@ class OCRService:
             logger.warning("device PNG decode not used: %s", e)
             return {}
 
+    def _decode_jp2_pages(self, images: List[Image.Image]) -> Dict[int, Any]:
+        """Lazily opened JPEG 2000 pages -> {page index: device tensor [1,H,W,3]}, one jp2_decode per size group.  Pages the decoder
+        refuses, and everything else, are absent: they take the host path."""
+        try:
+            cand: Dict[Any, list] = {}
+            for i, im in enumerate(images):
+                if getattr(im, "format", None) != "JPEG2000" or getattr(im, "_im", 0) is not None:
+                    continue
+                if "exif" in im.info or "XML:com.adobe.xmp" in im.info or "xmp" in im.info:
+                    continue
+                fp = getattr(im, "fp", None)
+                try:
+                    data = fp.getvalue() if isinstance(fp, io.BytesIO) else Path(im.filename).read_bytes() if getattr(im, "filename", None) else None
+                except (OSError, ValueError):
+                    data = None
+                if data is None or not self._is_jp2(data[:12]):
+                    continue
+                self._ensure_engine()
+                if self._jp2_probe(data, im.size) is not None:
+                    cand.setdefault(im.size, []).append((i, data))
+            res: Dict[int, Any] = {}
+            if cand:
+                with self._device_ctx():
+                    for (w, h), items in cand.items():
+                        out, status = self._engine.jp2_decode([d for _, d in items], h, w)
+                        for k, (i, _) in enumerate(items):
+                            if status[k] == 0:
+                                res[i] = out[k:k + 1]
+            return res
+        except Exception as e:       # any doubt: the reference's own path for every page
+            logger.warning("device JPEG 2000 decode not used: %s", e)
+            return {}
+
     def process_pages_sync(self, images: List[Image.Image], first_page_number: int = 1) -> List[OCROutput]:
         """Same-size pages go through the engine as one batch; results are identical to the per-page path."""
         out: List[Optional[OCROutput]] = [None] * len(images)
@@ -638,6 +740,8 @@ class OCRService:
             groups: Dict[Any, List[int]] = {}
             prepared: List[Optional[Image.Image]] = [None] * len(images)
             on_device = self._decode_png_pages(images) if self.device_png else {}
+            if self.device_jp2:
+                on_device.update(self._decode_jp2_pages(images))
             for i, im in enumerate(images):
                 if i in on_device:   # decoded (and oriented) on the device: grouped by its oriented size, apart from host pages
                     groups.setdefault(("device", on_device[i].shape[2], on_device[i].shape[1]), []).append(i)
@@ -734,6 +838,8 @@ class OCRService:
                     if filt == "DCTDecode":
                         decode = eng.jpeg_decode_progressive if self.progressive_jpeg else eng.jpeg_decode
                         out, status = decode(streams, h, w) if self.device_jpeg else (None, [-2] * len(idxs))
+                    elif filt == "JPXDecode":   # (only with LUMINA_OCR_DEVICE_JP2: read_pages returns none otherwise)
+                        out, status = eng.jp2_decode(streams, h, w)
                     elif filt in ("LZWDecode", "RunLengthDecode"):   # one-strip pages of the strip decoders
                         codec = 5 if filt == "LZWDecode" else 32773
                         params = [(codec, r.params["predictor"], r.params["components"], r.params["bits"], int(r.params["indexed"]),
@@ -773,7 +879,7 @@ class OCRService:
         try:
             data = Path(pdf_path).read_bytes()
             try:
-                entries = pdf_pages.read_pages(data, strip_filters=self.device_tiff)
+                entries = pdf_pages.read_pages(data, strip_filters=self.device_tiff, **({"jpx": True} if self.device_jp2 else {}))
             except pdf_pages.PdfRefused as e:   # not a file the reader takes: the rasterise-and-batch path, whole
                 r = self.process_pdf_as_images_sync(pdf_path)
                 if not r.success and r.error and not r.pages:
@@ -984,7 +1090,7 @@ class OCRService:
                 return await asyncio.wait_for(asyncio.to_thread(self.process_tiff_sync, path), timeout=600.0)
             except asyncio.TimeoutError:
                 return DocumentOCRResult(success=False, error="Timed out after 600.0s")
-        if file_type in SUPPORTED_IMAGE_TYPES:
+        if file_type in SUPPORTED_IMAGE_TYPES or (self.device_jp2 and file_type in JP2_FILE_TYPES):
             r = await self.process_image(path)
             return DocumentOCRResult(pages=[r], total_pages=1, total_processing_time_ms=r.processing_time_ms, success=r.success,
                                      error=r.error, combined_markdown=r.markdown, combined_html=r.html, combined_layout_boxes=r.layout_boxes)
@@ -993,7 +1099,7 @@ class OCRService:
     # ---- status (:759-795) ----
     def get_status(self) -> Dict[str, Any]:
         st = {"client_initialized": self._pipeline is not None, "model_id": "dbnet-r18vd+crnn-mv3", "max_dimension": self.max_dimension,
-              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "aztec": self._use_aztec, "aztec_max_layers": self._aztec_max_layers_status(), "device_pdf": self.device_pdf, "progressive_jpeg": self.progressive_jpeg, "device_tiff": self.device_tiff, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
+              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "aztec": self._use_aztec, "aztec_max_layers": self._aztec_max_layers_status(), "device_pdf": self.device_pdf, "progressive_jpeg": self.progressive_jpeg, "device_tiff": self.device_tiff, "device_jp2": self.device_jp2, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
         if self._engine is not None:
             st["engine_version"] = self._engine.version()
             st["num_classes"] = self._engine.num_classes

@@ -20,7 +20,9 @@ Supported image: /BitsPerComponent 1 or 8 (2 and 4 for grey / indexed Flate imag
 N = 1 or 3 (READ AS ITS DEVICE ALTERNATE: the profile is not applied, as Pillow does not apply it to a JPEG or PNG file either), or
 Indexed over those with hival <= 255; one /Filter (a name or a one-element array) of DCTDecode, FlateDecode, CCITTFaxDecode (and, with
 strip_filters, LZWDecode and RunLengthDecode under the Flate rules); /Decode the default, or [1 0] on one-component Flate / CCITT
-images; no /ImageMask, /SMask or /Mask.
+images; no /ImageMask, /SMask or /Mask.  With jpx=True also /JPXDecode (JPEG 2000, for lumina_ocr_jp2_decode): /ColorSpace absent or
+DeviceGray / DeviceRGB matching the codestream's 1 or 3 components, /SMaskInData absent or 0, no /Decode, and the size in the codestream
+equal to the dictionary's.
 
 The reader ends on any input: every loop advances through the file or a decoded stream, /Prev chains, page-tree nodes and indirect
 references are followed through visited-sets, every offset and /Length is checked against the file size, and the number of objects, the
@@ -39,6 +41,7 @@ MAX_META_BYTES = 32 << 20    # inflated size of one metadata stream
 EDGE_TOLERANCE = 0.01        # each image edge within this fraction of the MediaBox side
 FILTERS = ("DCTDecode", "FlateDecode", "CCITTFaxDecode")
 STRIP_FILTERS = ("LZWDecode", "RunLengthDecode")   # taken only when read_pages is asked to (strip_filters=True)
+JPX_FILTER = "JPXDecode"                            # taken only when read_pages is asked to (jpx=True)
 
 _WS = b"\x00\t\n\x0c\r "
 _DELIM = b"()<>[]{}/%"
@@ -70,11 +73,11 @@ class Stream(dict):
 
 @dataclass
 class PageImage:
-    filter: str                     # "DCTDecode" | "FlateDecode" | "CCITTFaxDecode" | "LZWDecode" | "RunLengthDecode"
+    filter: str                     # "DCTDecode" | "FlateDecode" | "CCITTFaxDecode" | "LZWDecode" | "RunLengthDecode" | "JPXDecode"
     stream: memoryview              # the image's raw stream, a view into the file
     params: Dict[str, Any]          # FlateDecode, LZWDecode, RunLengthDecode: predictor, components, bits, indexed, invert, palette
     #                                 (768 bytes RGB or None); predictor is 1 | 2 for LZWDecode and 1 for RunLengthDecode
-    #                                 CCITTFaxDecode: K, EncodedByteAlign, BlackIs1, invert;  DCTDecode: components
+    #                                 CCITTFaxDecode: K, EncodedByteAlign, BlackIs1, invert;  DCTDecode, JPXDecode: components
     width: int
     height: int
     rotate: int                     # /Rotate, 0 / 90 / 180 / 270 (clockwise, when displayed)
@@ -684,7 +687,55 @@ def _colour_space(doc: _Document, cs):
     return _components(doc, cs), None
 
 
-def _page_image(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], strip_filters: bool = False) -> PageImage:
+def _jpx_size(raw) -> Tuple[int, int, int]:
+    """(width, height, components) from the SIZ segment of a JPEG 2000 stream (a raw codestream, or the first jp2c box of a JP2 / JPX
+    file); raises PdfRefused.  Nothing else is checked here: the decoder's own parser decides whether the stream is read."""
+    d = bytes(raw[:1 << 16]) if len(raw) > (1 << 16) else bytes(raw)
+    p = 0
+    if d[:12] == b"\x00\x00\x00\x0cjP  \r\n\x87\n":
+        p = 12
+        for _ in range(64):
+            if p + 8 > len(d):
+                raise PdfRefused("JPX stream without a codestream box in its first 64 KB")
+            ln, typ, hl = int.from_bytes(d[p:p + 4], "big"), d[p + 4:p + 8], 8
+            if ln == 1:
+                ln, hl = int.from_bytes(d[p + 8:p + 16], "big"), 16
+            if typ == b"jp2c":
+                p += hl
+                break
+            if ln < hl:
+                raise PdfRefused("JPX stream with a malformed box")
+            p += ln
+        else:
+            raise PdfRefused("JPX stream with too many boxes")
+    if d[p:p + 4] != b"\xff\x4f\xff\x51" or p + 42 > len(d):
+        raise PdfRefused("JPX stream without SOC and SIZ")
+    q = p + 4
+    x1, y1, x0, y0 = (int.from_bytes(d[q + o:q + o + 4], "big") for o in (4, 8, 12, 16))
+    comps = int.from_bytes(d[q + 36:q + 38], "big")
+    if x1 <= x0 or y1 <= y0:
+        raise PdfRefused("JPX stream with an empty image")
+    return x1 - x0, y1 - y0, comps
+
+
+def _jpx_page_image(doc: _Document, img: Stream, width: int, height: int, rotate: int, media_box) -> PageImage:
+    smask_in_data = doc.resolve(img.get("SMaskInData", 0))
+    if smask_in_data != 0:
+        raise PdfRefused("/SMaskInData %r" % (smask_in_data,))
+    if doc.resolve(img.get("Decode")) is not None:
+        raise PdfRefused("/Decode on a JPX image")
+    cs = doc.resolve(img.get("ColorSpace"))
+    if cs is not None and cs not in ("DeviceGray", "DeviceRGB"):
+        raise PdfRefused("JPX image with /ColorSpace %r" % (cs if isinstance(cs, str) else type(cs).__name__,))
+    w, h, comps = _jpx_size(img.raw)
+    if (w, h) != (width, height):
+        raise PdfRefused("JPX codestream is %d x %d, the image dictionary says %d x %d" % (w, h, width, height))
+    if comps not in (1, 3) or (cs is not None and comps != (1 if cs == "DeviceGray" else 3)):
+        raise PdfRefused("JPX codestream with %d components under /ColorSpace %r" % (comps, cs))
+    return PageImage(filter=JPX_FILTER, stream=img.raw, params={"components": comps}, width=w, height=h, rotate=rotate, media_box=media_box)
+
+
+def _page_image(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], strip_filters: bool = False, jpx: bool = False) -> PageImage:
     box = doc.resolve(attrs.get("MediaBox"))
     if not isinstance(box, list) or len(box) != 4:
         raise PdfRefused("no MediaBox")
@@ -735,6 +786,8 @@ def _page_image(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], str
     if not all(isinstance(v, int) and 0 < v <= 65535 for v in (width, height)):
         raise PdfRefused("malformed image size")
     filt, parms = doc.single_filter(img)
+    if jpx and filt == JPX_FILTER:
+        return _jpx_page_image(doc, img, width, height, rotate, (x0, y0, x1, y1))
     if filt not in FILTERS and not (strip_filters and filt in STRIP_FILTERS):
         raise PdfRefused("image filter %s" % filt)
     bits = doc.resolve(img.get("BitsPerComponent", 1 if filt == "CCITTFaxDecode" else None))
@@ -781,18 +834,20 @@ def _page_image(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], str
     return PageImage(filter=filt, stream=img.raw, params=params, width=width, height=height, rotate=rotate, media_box=(x0, y0, x1, y1))
 
 
-def read_pages(data, strip_filters: bool = False) -> List[Union[PageImage, PdfRefused]]:
+def read_pages(data, strip_filters: bool = False, jpx: bool = False) -> List[Union[PageImage, PdfRefused]]:
     """One entry per page of the PDF in `data` (bytes, or anything with the buffer protocol: the records' streams are views into it):
     the page's image record, or the PdfRefused that says why the page is not a scanned page.  Raises PdfRefused for the whole file.
     strip_filters: also take /LZWDecode (/EarlyChange 1 or absent, /Predictor 1 or 2) and /RunLengthDecode images, which
     lumina_ocr_strip_image_decode decodes as one-strip pages (the provider asks for them with LUMINA_OCR_DEVICE_TIFF=1); without it
-    they are refused as any other filter is."""
+    they are refused as any other filter is.
+    jpx: also take /JPXDecode images (JPEG 2000), which lumina_ocr_jp2_decode decodes (the provider asks for them with
+    LUMINA_OCR_DEVICE_JP2=1); without it they are refused as any other filter is."""
     try:
         doc = _Document(data)
         out: List[Union[PageImage, PdfRefused]] = []
         for page, attrs in doc.pages():
             try:
-                out.append(_page_image(doc, page, attrs, strip_filters))
+                out.append(_page_image(doc, page, attrs, strip_filters, jpx))
             except PdfRefused as e:
                 out.append(e)
         return out

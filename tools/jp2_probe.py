@@ -1,0 +1,100 @@
+"""Times the JPEG 2000 decode (lumina_ocr_jp2_decode): A4@200DPI text pages (1654 x 2339; --distinct different synth pages, repeated)
+written by Pillow (OpenJPEG) with the 5/3 reversible transform:
+  * `rgb_lossless`, `grey_lossless`      lossless files;
+  * `rgb_layers20`, `grey_layers20`      quality_layers=[20] (rate 20: blocks stop early);
+each as a batch of --pages pages in one call and as one page alone.  Wall-clock per call (the calls synchronise), median of --reps with
+min and max after one warm-up call.  Beside each, Pillow on one host thread over the distinct files, median of --host-reps, per page
+(host_batch_ms is that figure times the number of pages), and the host walk over the packet headers alone (tier 2: lumina_ocr_jp2_probe)
+per page.  The split of the device time between tier 1 and the DWT comes from a kernel trace of `--trace CASE` (one warm-up call and one
+timed call of that case, nothing else), in a run of its own.  Writes profiles/jp2_probe.json and prints it; needs an MI355X.  No
+threshold: the host decode is what each figure is compared with.
+
+    python tools/jp2_probe.py [--reps 20] [--pages 64] [--host-reps 3] [--cases ...] [--trace CASE]"""
+import argparse
+import io
+import json
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+for p in (ROOT, ROOT / "ocr-system_amd"):
+    sys.path.insert(0, str(p))
+
+W, H = 1654, 2339
+CASES = {"rgb_lossless": ("RGB", {}), "grey_lossless": ("L", {}), "rgb_layers20": ("RGB", {"quality_layers": [20]}),
+         "grey_layers20": ("L", {"quality_layers": [20]})}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--host-reps", type=int, default=3)
+    ap.add_argument("--pages", type=int, default=64)
+    ap.add_argument("--distinct", type=int, default=4)
+    ap.add_argument("--cases", default=",".join(CASES))
+    ap.add_argument("--trace", default="")
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "jp2_probe.json"))
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    from PIL import Image
+    from lumina_ocr import synth
+    from lumina_ocr.engine import Engine
+
+    eng = Engine(0)
+    src = [synth.synth_page(H, W, 100 + k, n_lines=40)[0] for k in range(args.distinct)]
+
+    def write(mode, opts):
+        files = []
+        for page in src:
+            op = io.BytesIO()
+            Image.fromarray(page if mode == "RGB" else np.ascontiguousarray(page[:, :, 1])).save(op, "JPEG2000", irreversible=False, **opts)
+            files.append(op.getvalue())
+        return files
+
+    def timed(fn, reps, sync=True):
+        times = []
+        for i in range(reps + 1):
+            t0 = time.perf_counter()
+            out = fn()
+            if sync:
+                torch.cuda.synchronize()
+            if i:
+                times.append((time.perf_counter() - t0) * 1e3)
+        return dict(median=round(float(np.median(times)), 2), min=round(min(times), 2), max=round(max(times), 2)), out
+
+    if args.trace:
+        files = write(*CASES[args.trace])
+        streams = [files[i % len(files)] for i in range(args.pages)]
+        out_buf = torch.empty((args.pages, H, W, 3), dtype=torch.uint8, device="cuda")
+        t, (_, status) = timed(lambda: eng.jp2_decode(streams, H, W, out=out_buf), 1)
+        print(json.dumps(dict(trace=args.trace, pages=args.pages, device_ms=t, status_ok=status.count(0))))
+        eng.close()
+        return
+
+    res = dict(pages=args.pages, height=H, width=W, distinct=args.distinct, reps=args.reps, host_reps=args.host_reps)
+    for name in args.cases.split(","):
+        files = write(*CASES[name])
+        t_host, ref = timed(lambda: [np.asarray(Image.open(io.BytesIO(s)).convert("RGB")) for s in files], args.host_reps, sync=False)
+        t_tier2, probes = timed(lambda: [Engine.jp2_probe(s) for s in files], args.host_reps, sync=False)
+        host_page = t_host["median"] / len(files)
+        entry = dict(file_kb=round(sum(len(s) for s in files) / len(files) / 1024, 1), probe_status=[rc for rc, _ in probes],
+                     host_ms_per_page=round(host_page, 2), host_ms_distinct=t_host, tier2_host_ms_per_page=round(t_tier2["median"] / len(files), 3))
+        for label, n in (("batch", args.pages), ("single", 1)):
+            streams = [files[i % len(files)] for i in range(n)]
+            out_buf = torch.empty((n, H, W, 3), dtype=torch.uint8, device="cuda")
+            t_dev, (out, status) = timed(lambda: eng.jp2_decode(streams, H, W, out=out_buf), args.reps)
+            equal = all(status[i] == 0 and np.array_equal(out[i].cpu().numpy(), ref[i]) for i in range(min(n, len(files))))
+            entry[label] = dict(pages=n, device_ms=t_dev, host_batch_ms=round(host_page * n, 1), status_ok=status.count(0), equal_to_host=bool(equal),
+                                device_pages_per_s=round(n / t_dev["median"] * 1e3, 1), host_pages_per_s=round(1e3 / host_page, 1))
+        res[name] = entry
+    text = json.dumps(res)
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text(text + "\n")
+    print(text)
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
