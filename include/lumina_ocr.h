@@ -556,6 +556,19 @@ int lumina_ocr_jp2_probe(const uint8_t* file, size_t size, int info[8]);
 const char* lumina_ocr_jp2_reason(int code);
 int lumina_ocr_jp2_decode(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev,
                           int* status, void* stream);
+/* 9/7 (irreversible, lossy) JPEG 2000 files as well.  The entries above keep their answers (-2 for a 9/7 file).
+ * lumina_ocr_jp2_probe_irreversible (host only): 0 for every file lumina_ocr_jp2_probe takes, and for files of the 9/7 irreversible
+ * transform inside the same subset with expounded step sizes (QCD style 2, one 16-bit step per sub-band), at most 15 magnitude
+ * bit-planes in a sub-band (OpenJPEG's own files of up to 5 levels, its default) and no line of one sample in a resolution above the
+ * lowest; with or without the irreversible colour transform.  -2 besides the list above: 9/7 with derived or no quantisation, 9/7
+ * with 16 bit-planes (OpenJPEG's 6-level files), a one-sample line, 5/3 with step sizes.  info and lumina_ocr_jp2_reason as above.
+ * lumina_ocr_jp2_decode_irreversible: the contract and the status codes of lumina_ocr_jp2_decode; 5/3 and 9/7 files may be mixed in
+ * one batch, a 5/3 file takes the kernels and gives the bytes of lumina_ocr_jp2_decode.  The float arithmetic of the 9/7 path
+ * (dequantisation, lifting, colour transform, rounding) is OpenJPEG's operation for operation in single precision, so status 0 =>
+ * byte-identical to Pillow here too.  Synchronises `stream`. */
+int lumina_ocr_jp2_probe_irreversible(const uint8_t* file, size_t size, int info[8]);
+int lumina_ocr_jp2_decode_irreversible(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width,
+                                       uint8_t* out_dev, int* status, void* stream);
 
 /* Scanned PDF pages — the images of a PDF whose pages are one image each (utils/pdf_pages.py finds them), decoded at their own sample
  * grid instead of the rasterisation pdf2image / poppler does for the reference (ocr_service.py:508-660).  /DCTDecode streams are JPEG

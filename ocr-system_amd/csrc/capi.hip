@@ -547,12 +547,13 @@ thread_local int jp2_last_code = 0;
 thread_local const char* jp2_last_reason = "";
 }  // namespace
 
-int lumina_ocr_jp2_probe(const uint8_t* file, size_t size, int info[8]) {
+namespace {
+int jp2_probe_any(const uint8_t* file, size_t size, int info[8], bool irreversible) {
     if (!file || !info) return -1;
     Jp2Probe p{};
     int rc = -1;
     try {
-        rc = jp2dec_probe(file, size, &p);
+        rc = jp2dec_probe(file, size, &p, irreversible);
     } catch (const std::exception&) {   // (allocation failure: the file is left to the host decoder)
         p.reason = "out of memory while reading the packet headers";
         rc = -2;
@@ -561,6 +562,10 @@ int lumina_ocr_jp2_probe(const uint8_t* file, size_t size, int info[8]) {
     jp2_last_code = rc; jp2_last_reason = p.reason ? p.reason : "";
     return rc;
 }
+}  // namespace
+
+int lumina_ocr_jp2_probe(const uint8_t* file, size_t size, int info[8]) { return jp2_probe_any(file, size, info, false); }
+int lumina_ocr_jp2_probe_irreversible(const uint8_t* file, size_t size, int info[8]) { return jp2_probe_any(file, size, info, true); }
 
 const char* lumina_ocr_jp2_reason(int code) {
     if (code != 0 && code == jp2_last_code && jp2_last_reason[0]) return jp2_last_reason;
@@ -579,6 +584,15 @@ int lumina_ocr_jp2_decode(lumina_ocr_t* h, const uint8_t* const* files, const si
     BIND(h);
     API_TRY
     return jp2dec_run(h, files, sizes, n, height, width, out_dev, status, (hipStream_t)stream);
+    API_CATCH(h)
+}
+
+int lumina_ocr_jp2_decode_irreversible(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev,
+                                       int* status, void* stream) {
+    if (!h || !files || !sizes || !out_dev || !status || n <= 0 || height <= 0 || width <= 0) return locr_fail(h, "jp2_decode_irreversible", "bad arguments");
+    BIND(h);
+    API_TRY
+    return jp2dec_run(h, files, sizes, n, height, width, out_dev, status, (hipStream_t)stream, true);
     API_CATCH(h)
 }
 

@@ -2,8 +2,11 @@
 // main header and the tile-part headers, then the walk over every packet in progression order (tier 2: inclusion and zero-bit-plane
 // tag trees, coding-pass counts, Lblock, segment lengths, the bit stuffing after 0xFF).  It emits one record per code-block; no pixel
 // is touched.  Status: 0 = the device subset, -2 = valid outside it, -1 = corrupt or irregular (the parser is strict: where OpenJPEG
-// is lenient the file is refused).  tests/jp2_reference.py restates every check in the same order.
+// is lenient the file is refused).  tests/jp2_reference.py restates every check in the same order.  With `irreversible`
+// the 9/7 transform is taken too (expounded step sizes: Jp2File::irreversible, Jp2Block::hs); tests/jp2_irreversible_reference.py
+// restates that form.
 #pragma once
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -25,11 +28,14 @@ struct Jp2Block {
     int mb, zbp, passes;        // Mb of the sub-band, zero bit-planes, coding passes in all layers
     int seg_head, seg_tail, nseg;
     int included, lblock;
+    float hs;                   // 9/7: half the step size of its sub-band (the magnitudes are in half units); 0 for 5/3
 };
 struct Jp2File {
     int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // width, height, components, levels, layers, progression order, code-block width, height
     int width = 0, height = 0, comps = 0, levels = 0, layers = 0, order = 0, cbw = 0, cbh = 0, mct = 0;
     int mb[3 * 32 + 1] = {};   // Mb per sub-band, in the QCD's order
+    int irreversible = 0;      // 1: the 9/7 transform; step[] then holds the step size per sub-band, in the QCD's order
+    float step[3 * 32 + 1] = {};
     const char* reason = "";
     std::vector<Jp2Block> blocks;
     std::vector<Jp2Seg> segs;
@@ -134,6 +140,8 @@ inline int find_codestream(const uint8_t* d, size_t n, Jp2File* f, size_t* s, si
     }
 }
 
+inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+
 inline const char* outside_marker(unsigned m) {
     switch (m) {
         case 0xFF5F: return "POC marker";
@@ -152,7 +160,7 @@ inline const char* outside_marker(unsigned m) {
     return nullptr;
 }
 
-inline int parse_headers(const uint8_t* d, size_t s, size_t e, bool boxed, const uint32_t box[4], Jp2File* f) {
+inline int parse_headers(const uint8_t* d, size_t s, size_t e, bool boxed, const uint32_t box[4], Jp2File* f, bool irreversible) {
     if (e - s < 4 || !(d[s] == 0xFF && d[s + 1] == 0x4F && d[s + 2] == 0xFF && d[s + 3] == 0x51)) JP2_BAD("no SOC + SIZ");
     size_t p = s + 4;
     if (p + 2 > e) JP2_BAD("SIZ cut short");
@@ -220,21 +228,39 @@ inline int parse_headers(const uint8_t* d, size_t s, size_t e, bool boxed, const
     f->info[3] = f->levels; f->info[4] = f->layers; f->info[5] = f->order; f->info[6] = f->cbw; f->info[7] = f->cbh;
     if (scod & 1) JP2_OUT("user precinct sizes");
     if (scod & 6) JP2_OUT("SOP or EPH markers");
-    if (xform == 0) JP2_OUT("the 9/7 irreversible transform");
+    if (xform == 0 && !irreversible) JP2_OUT("the 9/7 irreversible transform");
+    f->irreversible = xform == 0;
     if (style) JP2_OUT("code-block style bits");
     if (f->cbw > 64 || f->cbh > 64) JP2_OUT("code-block side over 64");
     if (f->layers > JP2_MAX_LAYERS) JP2_OUT("more than 32 layers");
     if (f->levels > JP2_MAX_LEVELS) JP2_OUT("more than 6 decomposition levels");
     if (mct && C != 3) JP2_BAD("component transform on a one-component image");
+    // (OpenJPEG leaves a 9/7 line of one sample unscaled and its encoder writes none: such a file cannot be pinned)
+    if (f->irreversible)
+        for (int r = 1; r <= f->levels; ++r)
+            if (cdiv((int)X, 1 << (f->levels - r)) == 1 || cdiv((int)Y, 1 << (f->levels - r)) == 1) JP2_OUT("the 9/7 transform over a line of one sample");
     const size_t nb = 3 * (size_t)levels + 1;
     const unsigned sq = d[qcd];
     if ((sq & 31) > 2) JP2_BAD("QCD style out of range");
-    if (sq & 31) JP2_OUT("quantised (scalar) step sizes with the reversible transform");
-    if (qcdn != 1 + nb) JP2_BAD("QCD of the wrong length");
     const int guard = (int)(sq >> 5);
+    if (!f->irreversible) {
+        if (sq & 31) JP2_OUT("quantised (scalar) step sizes with the reversible transform");
+        if (qcdn != 1 + nb) JP2_BAD("QCD of the wrong length");
+    } else {
+        if ((sq & 31) != 2) JP2_OUT("the 9/7 transform with derived or no quantisation");
+        if (qcdn != 1 + 2 * nb) JP2_BAD("QCD of the wrong length");
+    }
     for (size_t i = 0; i < nb; ++i) {
-        if (d[qcd + 1 + i] & 7) JP2_BAD("QCD exponent byte with mantissa bits");
-        const int mb = guard + (d[qcd + 1 + i] >> 3) - 1;
+        int expn;
+        if (!f->irreversible) {
+            if (d[qcd + 1 + i] & 7) JP2_BAD("QCD exponent byte with mantissa bits");
+            expn = d[qcd + 1 + i] >> 3;
+        } else {   // expounded: 5 bits of exponent, 11 of mantissa; the step is formed in double and rounded once, as OpenJPEG does
+            const unsigned v = (unsigned)be(d, qcd + 1 + 2 * i, 2);
+            expn = (int)(v >> 11);
+            f->step[i] = (float)((1.0 + (v & 0x7FF) / 2048.0) * std::ldexp(1.0, 8 - expn));
+        }
+        const int mb = guard + expn - 1;
         if (mb < 0) JP2_BAD("sub-band without magnitude bits");
         if (mb > JP2_MAX_MB) JP2_OUT("more magnitude bit-planes than the decoder takes");
         f->mb[i] = mb;
@@ -345,8 +371,6 @@ struct TagTree {
 
 struct Band { int first, nx, ny; TagTree incl, zbpt; };   // first: index of its first block in Jp2File::blocks
 
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-
 inline int npasses(Bits& bio) {
     if (!bio.bit()) return 1;
     if (!bio.bit()) return 2;
@@ -384,6 +408,7 @@ inline int geometry(Jp2File* f, std::vector<Band>& bands) {
                         K.w = w - bx * f->cbw < f->cbw ? w - bx * f->cbw : f->cbw;
                         K.h = h - by * f->cbh < f->cbh ? h - by * f->cbh : f->cbh;
                         K.mb = f->mb[r ? 3 * r - 3 + orient : 0]; K.zbp = 0; K.passes = 0;
+                        K.hs = f->irreversible ? 0.5f * f->step[r ? 3 * r - 3 + orient : 0] : 0.0f;
                         K.seg_head = K.seg_tail = -1; K.nseg = 0; K.included = 0; K.lblock = 3;
                         f->blocks.push_back(K);
                     }
@@ -465,15 +490,16 @@ inline int tier2(const uint8_t* d, Jp2File* f, std::vector<Band>& bands) {
 
 }  // namespace jp2p
 
-// The whole walk.  There is no headers-only form: a file counts as read only if every one of its packets parses.
-inline int jp2_parse(const uint8_t* file, size_t size, Jp2File* f) {
+// The whole walk.  There is no headers-only form: a file counts as read only if every one of its packets parses.  Without
+// `irreversible` a 9/7 file is -2, as it always was.
+inline int jp2_parse(const uint8_t* file, size_t size, Jp2File* f, bool irreversible = false) {
     size_t s = 0, e = 0;
     bool boxed = false;
     uint32_t box[4] = {0, 0, 0, 0};
     if (!file) { f->reason = "no file"; return -1; }
     int rc = jp2p::find_codestream(file, size, f, &s, &e, &boxed, box);
     if (rc) return rc;
-    rc = jp2p::parse_headers(file, s, e, boxed, box, f);
+    rc = jp2p::parse_headers(file, s, e, boxed, box, f, irreversible);
     if (rc) return rc;
     std::vector<jp2p::Band> bands;
     rc = jp2p::geometry(f, bands);

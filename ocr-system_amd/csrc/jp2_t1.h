@@ -1,4 +1,4 @@
-// JPEG 2000 tier 1 and the 5/3 lifting steps as plain functions: the decision walk of one code-block (MQ decoder + EBCOT context
+// JPEG 2000 tier 1, the 5/3 lifting steps and the 9/7 path (dequantisation, lifting, colour, rounding) as plain functions: the decision walk of one code-block (MQ decoder + EBCOT context
 // modelling) over a Jp2T1State, and the per-sample inverse lifting.  jp2dec.hip runs them on the device (the state in LDS, one wave
 // per block); tests/jp2_parse_main.cpp compiles the same text for the host, where the sanitizers can see it.
 #pragma once
@@ -230,4 +230,56 @@ JP2_HD inline int jp2_lift_odd(const T* line, long long stride, int n, int k) { 
     const int sn = (n + 1) / 2;
     const int a = jp2_lift_even(line, stride, n, k), b = jp2_lift_even(line, stride, n, k + 1 < sn ? k + 1 : k);
     return line[(sn + k) * stride] + ((a + b) >> 1);
+}
+
+// ---- the 9/7 irreversible path, in single precision in the order OpenJPEG evaluates it.  Every expression below is one rounding per
+// operation (the project compiles with -ffp-contract=off, and subnormals are kept), so host, device and any tiling give the same bits.
+
+// the coefficient of (y, x) after the walk, dequantised: the signed magnitude in half units times half the sub-band's step size
+JP2_HD inline float jp2_t1_value_f(const Jp2T1State& S, int y, int x, float hs) {
+    const int v = S.mag[y * 64 + x];
+    return (float)(((S.sgn[y + 1] >> x) & 1) ? -v : v) * hs;
+}
+
+// the scaling of a low-pass / high-pass sample as it is interleaved, and the four lifting steps: step s updates the samples of parity
+// s & 1 as x -= (left + right) * jp2_lift97_coef(s)
+#define JP2_K97_LOW 1.230174105f
+#define JP2_K97_HIGH 1.625732422f
+JP2_HD inline float jp2_lift97_coef(int s) { return s == 0 ? 0.443506852f : s == 1 ? 0.882911075f : s == 2 ? -0.052980118f : -1.586134342f; }
+
+// sample i of the interleaved line of n >= 2 samples, read from the sub-band order (low-pass first, sn = (n + 1) / 2 of them)
+JP2_HD inline float jp2_lift97_load(const float* line, long long stride, int n, int i) {
+    return (i & 1) ? line[((n + 1) / 2 + (i >> 1)) * stride] * JP2_K97_HIGH : line[(i >> 1) * stride] * JP2_K97_LOW;
+}
+
+// One lifting step at sample i of an interleaved line of n samples whose samples [lo, hi) are held at w[(i - lo) * stride].  A neighbour
+// outside the line is replaced by the other one (whole-sample mirror); a sample with a neighbour inside the line but outside the window
+// is left as it is: it belongs to the window's halo, which the four steps eat one sample a side each.  So a window that starts and
+// ends on even samples comes out right from lo + JP2_LIFT97_HALO to hi - JP2_LIFT97_HALO, and up to an end of the line it holds.
+constexpr int JP2_LIFT97_HALO = 4;
+JP2_HD inline void jp2_lift97_at(float* w, long long stride, int lo, int hi, int n, int i, float c) {
+    const int l = i > 0 ? i - 1 : i + 1, r = i + 1 < n ? i + 1 : i - 1;
+    if (l < lo || r < lo || l >= hi || r >= hi) return;
+    w[(i - lo) * stride] = w[(i - lo) * stride] - (w[(l - lo) * stride] + w[(r - lo) * stride]) * c;
+}
+
+// round to nearest even, level shift, clamp
+JP2_HD inline uint8_t jp2_sample97(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int i = __float2int_rn(v) + 128;
+#else
+    const int i = (int)__builtin_lrintf(v) + 128;
+#endif
+    return (uint8_t)(i < 0 ? 0 : i > 255 ? 255 : i);
+}
+
+// the inverse irreversible colour transform of one pixel, then jp2_sample97
+JP2_HD inline void jp2_finish97(float y, float u, float v, int mct, uint8_t rgb[3]) {
+    float r = y, g = u, b = v;
+    if (mct) {
+        r = y + v * 1.402f;
+        g = y - u * 0.34413f - v * 0.71414f;
+        b = y + u * 1.772f;
+    }
+    rgb[0] = jp2_sample97(r); rgb[1] = jp2_sample97(g); rgb[2] = jp2_sample97(b);
 }

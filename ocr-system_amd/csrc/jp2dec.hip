@@ -5,7 +5,11 @@
 //              (64-bit words, one per block row); the wave clears the state and writes the coefficients out.  10.5 KB of LDS per
 //              wave: 15 waves per CU.
 //   j2_dwt_h / j2_dwt_v   the inverse 5/3 lifting, level by level, horizontal then vertical, between two int32 planes
-//   j2_finish  inverse reversible colour transform, level shift, clamp -> RGB u8
+//   j2_dwt97_h / j2_dwt97_v   the inverse 9/7 lifting of the irreversible pages, beside them, over the same two planes read as float
+//   j2_finish  inverse colour transform (reversible or irreversible), level shift, clamp -> RGB u8
+// A 9/7 page (J2Page::kind 1) differs from a 5/3 page in the value tier 1 writes (the half-unit magnitude times half the step size,
+// as float), in its lifting kernels and in the branch of j2_finish; both kinds share a batch and the tier-1 launch.  All of the float
+// arithmetic is in jp2_t1.h, one rounding per operation in OpenJPEG's order, so the bytes are Pillow's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,8 +30,9 @@ struct J2Block {
     int x, y;                      // rectangle in the plane
     unsigned char w, h, orient, nbps;
     int passes;
+    float hs;                      // 9/7: half the step size of its sub-band; 0: the integer (5/3) path
 };
-struct J2Page { int levels, comps, mct, out_index, plane0; };
+struct J2Page { int levels, comps, mct, out_index, plane0, kind; };   // kind: 0 = 5/3 (int32 planes), 1 = 9/7 (float planes)
 
 __global__ __launch_bounds__(64) void j2_tier1(const J2Block* __restrict__ blocks, const uint8_t* __restrict__ bytes, int* __restrict__ coef,
                                                int height, int width) {
@@ -45,7 +50,7 @@ __global__ __launch_bounds__(64) void j2_tier1(const J2Block* __restrict__ block
     const int n = (int)b.w * b.h;
     for (int i = lane; i < n; i += 64) {
         const int y = i / b.w, x = i - y * b.w;
-        dst[(size_t)(b.y + y) * width + b.x + x] = jp2_t1_value(S, y, x);
+        dst[(size_t)(b.y + y) * width + b.x + x] = b.hs != 0.0f ? __float_as_int(jp2_t1_value_f(S, y, x, b.hs)) : jp2_t1_value(S, y, x);
     }
 }
 
@@ -55,7 +60,7 @@ __device__ inline int j2_cdiv(int a, int b) { return (a + b - 1) / b; }
 __global__ __launch_bounds__(256) void j2_dwt_h(const J2Page* __restrict__ pages, const int* __restrict__ src, int* __restrict__ dst, int height,
                                                 int width, int step) {
     const J2Page pg = pages[blockIdx.z];
-    if (step > pg.levels || (int)blockIdx.y >= pg.comps) return;
+    if (pg.kind != 0 || step > pg.levels || (int)blockIdx.y >= pg.comps) return;
     const int sh = pg.levels - step, rw = j2_cdiv(width, 1 << sh), rh = j2_cdiv(height, 1 << sh), np = (rw + 1) / 2;
     const size_t plane = (size_t)(pg.plane0 + blockIdx.y) * height * width;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < (long long)rh * np; i += (long long)gridDim.x * 256) {
@@ -70,7 +75,7 @@ __global__ __launch_bounds__(256) void j2_dwt_h(const J2Page* __restrict__ pages
 __global__ __launch_bounds__(256) void j2_dwt_v(const J2Page* __restrict__ pages, const int* __restrict__ src, int* __restrict__ dst, int height,
                                                 int width, int step) {
     const J2Page pg = pages[blockIdx.z];
-    if (step > pg.levels || (int)blockIdx.y >= pg.comps) return;
+    if (pg.kind != 0 || step > pg.levels || (int)blockIdx.y >= pg.comps) return;
     const int sh = pg.levels - step, rw = j2_cdiv(width, 1 << sh), rh = j2_cdiv(height, 1 << sh), np = (rh + 1) / 2;
     const size_t plane = (size_t)(pg.plane0 + blockIdx.y) * height * width;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < (long long)np * rw; i += (long long)gridDim.x * 256) {
@@ -82,6 +87,66 @@ __global__ __launch_bounds__(256) void j2_dwt_v(const J2Page* __restrict__ pages
     }
 }
 
+// ---- the 9/7 lifting.  An output sample depends on four input samples to either side through the four steps, so a work-group holds a
+// window of a line in LDS (jp2_lift97_at): the samples it owns and JP2_LIFT97_HALO more a side, interleaved and scaled as they are
+// loaded, then one step per barrier interval.  Windows start on even samples; the expression tree of a sample is fixed, so the tiling
+// does not show in the bits.
+constexpr int J2_HSEG = 256;    // samples of a row a work-group of j2_dwt97_h owns (a sample pair per thread and step; 3 % of halo)
+constexpr int J2_VSEG = 56;     // rows of a 64-column strip a work-group of j2_dwt97_v owns: 64 x 64 floats, 16 KB of LDS
+
+// blockIdx.x = window of the row * rows + row (rows: the most rows any page rebuilds at this step); y: component; z: page.
+// Lanes read the two halves of the row alternately (two runs of 32 floats per wave) and write the row out contiguously; the steps
+// touch every other float of the window, a 2-way bank conflict that four short passes over 1 KB do not repay removing.
+__global__ __launch_bounds__(128) void j2_dwt97_h(const J2Page* __restrict__ pages, const float* __restrict__ src, float* __restrict__ dst, int height,
+                                                  int width, int step, int rows) {
+    __shared__ float w[J2_HSEG + 2 * JP2_LIFT97_HALO];
+    const J2Page pg = pages[blockIdx.z];
+    if (pg.kind != 1 || step > pg.levels || (int)blockIdx.y >= pg.comps) return;
+    const int sh = pg.levels - step, rw = j2_cdiv(width, 1 << sh), rh = j2_cdiv(height, 1 << sh);
+    const int y = (int)(blockIdx.x % (unsigned)rows), seg0 = (int)(blockIdx.x / (unsigned)rows) * J2_HSEG;
+    if (y >= rh || seg0 >= rw) return;
+    const int lo = seg0 - JP2_LIFT97_HALO < 0 ? 0 : seg0 - JP2_LIFT97_HALO;
+    const int end = seg0 + J2_HSEG < rw ? seg0 + J2_HSEG : rw, hi = end + JP2_LIFT97_HALO < rw ? end + JP2_LIFT97_HALO : rw;
+    const size_t row = ((size_t)(pg.plane0 + blockIdx.y) * height + y) * width;
+    const int tid = threadIdx.x;
+    for (int i = lo + tid; i < hi; i += 128) w[i - lo] = jp2_lift97_load(src + row, 1, rw, i);
+    __syncthreads();
+    for (int s = 0; s < 4; ++s) {
+        const float c = jp2_lift97_coef(s);
+        for (int i = lo + (s & 1) + 2 * tid; i < hi; i += 256) jp2_lift97_at(w, 1, lo, hi, rw, i, c);
+        __syncthreads();
+    }
+    for (int i = seg0 + tid; i < end; i += 128) dst[row + i] = w[i - lo];
+}
+
+// blockIdx.x = window of the columns * strips + strip (strips: 64-column strips of the widest resolution any page rebuilds at this
+// step).  A wave is 64 neighbouring columns of one row: its loads and stores are 256 contiguous bytes and its LDS accesses one bank row.
+__global__ __launch_bounds__(256) void j2_dwt97_v(const J2Page* __restrict__ pages, const float* __restrict__ src, float* __restrict__ dst, int height,
+                                                  int width, int step, int strips) {
+    __shared__ float w[(J2_VSEG + 2 * JP2_LIFT97_HALO) * 64];
+    const J2Page pg = pages[blockIdx.z];
+    if (pg.kind != 1 || step > pg.levels || (int)blockIdx.y >= pg.comps) return;
+    const int sh = pg.levels - step, rw = j2_cdiv(width, 1 << sh), rh = j2_cdiv(height, 1 << sh);
+    const int x0 = (int)(blockIdx.x % (unsigned)strips) * 64, seg0 = (int)(blockIdx.x / (unsigned)strips) * J2_VSEG;
+    if (x0 >= rw || seg0 >= rh) return;
+    const int lo = seg0 - JP2_LIFT97_HALO < 0 ? 0 : seg0 - JP2_LIFT97_HALO;
+    const int end = seg0 + J2_VSEG < rh ? seg0 + J2_VSEG : rh, hi = end + JP2_LIFT97_HALO < rh ? end + JP2_LIFT97_HALO : rh;
+    const int cx = threadIdx.x & 63, q = threadIdx.x >> 6, x = x0 + cx;
+    const bool live = x < rw;
+    const size_t col = (size_t)(pg.plane0 + blockIdx.y) * height * width + (size_t)(live ? x : x0);
+    if (live)
+        for (int i = lo + q; i < hi; i += 4) w[(i - lo) * 64 + cx] = jp2_lift97_load(src + col, width, rh, i);
+    __syncthreads();
+    for (int s = 0; s < 4; ++s) {
+        const float c = jp2_lift97_coef(s);
+        if (live)
+            for (int i = lo + (s & 1) + 2 * q; i < hi; i += 8) jp2_lift97_at(w + cx, 64, lo, hi, rh, i, c);
+        __syncthreads();
+    }
+    if (live)
+        for (int i = seg0 + q; i < end; i += 4) dst[col + (size_t)i * width] = w[(i - lo) * 64 + cx];
+}
+
 __device__ inline uint8_t j2_sample(int v) { v += 128; return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
 
 __global__ __launch_bounds__(256) void j2_finish(const J2Page* __restrict__ pages, const int* __restrict__ coef, uint8_t* __restrict__ out, int height, int width) {
@@ -90,6 +155,14 @@ __global__ __launch_bounds__(256) void j2_finish(const J2Page* __restrict__ page
     const int* p0 = coef + (size_t)pg.plane0 * npx;
     uint8_t* o = out + (size_t)pg.out_index * npx * 3;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npx; i += (size_t)gridDim.x * 256) {
+        if (pg.kind == 1) {
+            const float* f0 = reinterpret_cast<const float*>(p0);
+            uint8_t rgb[3];
+            if (pg.comps == 1) rgb[0] = rgb[1] = rgb[2] = jp2_sample97(f0[i]);
+            else jp2_finish97(f0[i], f0[npx + i], f0[2 * npx + i], pg.mct, rgb);
+            o[3 * i] = rgb[0]; o[3 * i + 1] = rgb[1]; o[3 * i + 2] = rgb[2];
+            continue;
+        }
         int r, g, b;
         if (pg.comps == 1) {
             r = g = b = p0[i];
@@ -119,16 +192,16 @@ size_t jp2dec_workspace_bytes(size_t nblocks, size_t nbytes, int pages, size_t p
     return a.off;
 }
 
-int jp2dec_probe(const uint8_t* file, size_t n, Jp2Probe* out) {
+int jp2dec_probe(const uint8_t* file, size_t n, Jp2Probe* out, bool irreversible) {
     Jp2File f;
-    const int rc = jp2_parse(file, n, &f);
+    const int rc = jp2_parse(file, n, &f, irreversible);
     memcpy(out->info, f.info, sizeof(f.info));
     out->reason = f.reason;
     return rc;
 }
 
 int jp2dec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev, int* status,
-               hipStream_t st) {
+               hipStream_t st, bool irreversible) {
     lumina_ocr::Staging& stage = eng->jp_stage;
     if (!stage.uploaded) {
         hipEvent_t ev = nullptr;
@@ -153,7 +226,7 @@ int jp2dec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes
                 f = std::move(held);
                 holding = false;
             } else {
-                int rc = jp2_parse(files[i1], sizes[i1], &f);
+                int rc = jp2_parse(files[i1], sizes[i1], &f, irreversible);
                 if (rc == 0 && (f.width != width || f.height != height)) rc = -4;
                 status[i1] = rc;
                 if (rc) continue;
@@ -187,14 +260,14 @@ int jp2dec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes
             int plane0 = 0, max_levels = 0;
             for (int k = 0; k < np; ++k) {
                 const Jp2File& f = F[(size_t)k];
-                hp[k] = J2Page{f.levels, f.comps, f.mct, index[(size_t)k], plane0};
+                hp[k] = J2Page{f.levels, f.comps, f.mct, index[(size_t)k], plane0, f.irreversible};
                 max_levels = std::max(max_levels, f.levels);
                 for (const Jp2Block& K : f.blocks) {
                     if (!K.passes) continue;
                     J2Block& b = hb[bi++];
                     b.data_off = off; b.plane = plane0 + K.comp; b.x = K.x; b.y = K.y;
                     b.w = (unsigned char)K.w; b.h = (unsigned char)K.h; b.orient = (unsigned char)K.orient; b.nbps = (unsigned char)(K.mb - K.zbp);
-                    b.passes = K.passes;
+                    b.passes = K.passes; b.hs = K.hs;
                     for (int s = K.seg_head; s >= 0; s = f.segs[(size_t)s].next) {
                         memcpy(hbytes + off, files[index[(size_t)k]] + f.segs[(size_t)s].off, f.segs[(size_t)s].len);
                         off += f.segs[(size_t)s].len;
@@ -215,16 +288,29 @@ int jp2dec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes
             LOCR_CHECK(hipEventRecord(stage.uploaded.get(), st));
             LOCR_CHECK(hipMemsetAsync(w.a, 0, planes * npx * sizeof(int), st));   // blocks no layer includes are zero
             if (nblocks) hipLaunchKernelGGL(j2_tier1, dim3((unsigned)nblocks), dim3(64), 0, st, w.blocks, w.bytes, w.a, height, width);
+            float* const fa = reinterpret_cast<float*>(w.a);
+            float* const fb = reinterpret_cast<float*>(w.b);
             for (int step = 1; step <= max_levels; ++step) {
-                size_t work = 0;   // the largest resolution any page rebuilds at this step
+                size_t work = 0;         // the largest resolution any 5/3 page rebuilds at this step
+                int rw97 = 0, rh97 = 0;  // and the largest any 9/7 page does
                 for (const Jp2File& f : F)
                     if (step <= f.levels) {
-                        const int sh = f.levels - step;
-                        work = std::max(work, (size_t)((height + (1 << sh) - 1) >> sh) * (size_t)((width + (1 << sh) - 1) >> sh));
+                        const int sh = f.levels - step, rh = (height + (1 << sh) - 1) >> sh, rw = (width + (1 << sh) - 1) >> sh;
+                        if (f.irreversible) { rw97 = std::max(rw97, rw); rh97 = std::max(rh97, rh); }
+                        else work = std::max(work, (size_t)rh * (size_t)rw);
                     }
-                const dim3 grid((unsigned)std::min<size_t>((work / 2 + 255) / 256 + 1, 2048), 3, (unsigned)np);
-                hipLaunchKernelGGL(j2_dwt_h, grid, dim3(256), 0, st, w.pages, w.a, w.b, height, width, step);
-                hipLaunchKernelGGL(j2_dwt_v, grid, dim3(256), 0, st, w.pages, w.b, w.a, height, width, step);
+                if (work) {
+                    const dim3 grid((unsigned)std::min<size_t>((work / 2 + 255) / 256 + 1, 2048), 3, (unsigned)np);
+                    hipLaunchKernelGGL(j2_dwt_h, grid, dim3(256), 0, st, w.pages, w.a, w.b, height, width, step);
+                    hipLaunchKernelGGL(j2_dwt_v, grid, dim3(256), 0, st, w.pages, w.b, w.a, height, width, step);
+                }
+                if (rw97) {   // (sides <= 16384: at most 64 windows x 16384 rows and 256 strips x 293 windows)
+                    const int strips = (rw97 + 63) / 64;
+                    hipLaunchKernelGGL(j2_dwt97_h, dim3((unsigned)((rw97 + J2_HSEG - 1) / J2_HSEG * rh97), 3, (unsigned)np), dim3(128), 0, st, w.pages, fa, fb,
+                                       height, width, step, rh97);
+                    hipLaunchKernelGGL(j2_dwt97_v, dim3((unsigned)((rh97 + J2_VSEG - 1) / J2_VSEG * strips), 3, (unsigned)np), dim3(256), 0, st, w.pages, fb, fa,
+                                       height, width, step, strips);
+                }
             }
             hipLaunchKernelGGL(j2_finish, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 2048), (unsigned)np), dim3(256), 0, st, w.pages, w.a, out_dev,
                                height, width);

@@ -84,6 +84,8 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_jp2_probe": (i32, [vp, sz, vp]),
         "lumina_ocr_jp2_reason": (c.c_char_p, [i32]),
         "lumina_ocr_jp2_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+        "lumina_ocr_jp2_probe_irreversible": (i32, [vp, sz, vp]),
+        "lumina_ocr_jp2_decode_irreversible": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_flate_image_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
         "lumina_ocr_ccitt_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
         "lumina_ocr_fax_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
@@ -141,6 +143,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_resize_lanczos", "lumina_ocr_enhance", "lumina_ocr_jpeg_encode", "lumina_ocr_jpeg_coefficients", "lumina_ocr_jpeg_probe", "lumina_ocr_jpeg_decode", "lumina_ocr_jpeg_decode_async", "lumina_ocr_jpeg_last_passes",
     "lumina_ocr_jpeg_probe_progressive", "lumina_ocr_jpeg_decode_progressive",
     "lumina_ocr_jp2_probe", "lumina_ocr_jp2_reason", "lumina_ocr_jp2_decode",
+    "lumina_ocr_jp2_probe_irreversible", "lumina_ocr_jp2_decode_irreversible",
     "lumina_ocr_png_probe", "lumina_ocr_png_decode", "lumina_ocr_flate_image_decode", "lumina_ocr_ccitt_decode", "lumina_ocr_fax_decode", "lumina_ocr_strip_image_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
     "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks", "lumina_ocr_selection_marks_round",
@@ -302,9 +305,19 @@ class Engine:
         pixel is decoded. -> (rc, dict(width, height, components, levels, layers, progression, codeblock_width, codeblock_height,
         reason)); rc 0: the device decodes this file, -2: valid outside the subset (9/7, tiles, precincts ...: decode with Pillow as the
         reference does), -1: corrupt or irregular.  reason: why a non-zero rc was given, for logs."""
+        return Engine._jp2_probe(data, "lumina_ocr_jp2_probe")
+
+    @staticmethod
+    def jp2_probe_irreversible(data: bytes):
+        """Host only. jp2_probe that also takes files of the 9/7 irreversible transform (expounded step sizes, at most 15 magnitude
+        bit-planes a sub-band: OpenJPEG's files of up to 5 levels) -> (rc, dict) as jp2_probe."""
+        return Engine._jp2_probe(data, "lumina_ocr_jp2_probe_irreversible")
+
+    @staticmethod
+    def _jp2_probe(data: bytes, entry: str):
         lib = load_library()
         info = (ctypes.c_int * 8)()
-        rc = lib.lumina_ocr_jp2_probe(ctypes.c_char_p(data), len(data), info)
+        rc = getattr(lib, entry)(ctypes.c_char_p(data), len(data), info)
         return rc, dict(width=info[0], height=info[1], components=info[2], levels=info[3], layers=info[4], progression=info[5],
                         codeblock_width=info[6], codeblock_height=info[7], reason=lib.lumina_ocr_jp2_reason(rc).decode() if rc else "")
 
@@ -312,6 +325,14 @@ class Engine:
         """JPEG 2000 file images (a sequence of bytes objects, all height x width) -> (uint8 [n,H,W,3] device, status list): the pixels of
         the reference's Image.open(...).convert('RGB') for .jp2 / .j2k inputs, byte-identical to Pillow.  status[i] != 0: page i was not
         decoded (-1 corrupt, -2 outside the device subset, -4 another size) and is left to Pillow."""
+        return self._jp2_decode(self.lib.lumina_ocr_jp2_decode, files, height, width, out)
+
+    def jp2_decode_irreversible(self, files, height: int, width: int, out=None):
+        """jp2_decode for batches that may hold 9/7 (irreversible) files: the same result and status codes, status 0 => byte-identical
+        to Pillow; a 5/3 file gives the bytes of jp2_decode."""
+        return self._jp2_decode(self.lib.lumina_ocr_jp2_decode_irreversible, files, height, width, out)
+
+    def _jp2_decode(self, entry, files, height: int, width: int, out):
         torch = _torch()
         n = len(files)
         if out is None:
@@ -320,7 +341,7 @@ class Engine:
         ptrs = (ctypes.c_char_p * n)(*files)
         sizes = (ctypes.c_size_t * n)(*[len(f) for f in files])
         status = (ctypes.c_int * n)()
-        self._chk(self.lib.lumina_ocr_jp2_decode(self._h, ptrs, sizes, n, int(height), int(width), _ptr(out), status, self._stream()))
+        self._chk(entry(self._h, ptrs, sizes, n, int(height), int(width), _ptr(out), status, self._stream()))
         return out, list(status)
 
     def _stream_batch(self, streams, height: int, width: int, out):

@@ -139,6 +139,10 @@ class OCRService:
         # of a batch are grouped by size, process_document takes "jp2", "j2k" and "jpx", and with LUMINA_OCR_PDF_SCANS=1 the /JPXDecode
         # pages of a scanned PDF are read as well.  Off by default: exactly the calls made without the option are made.
         self.device_jp2 = os.environ.get("LUMINA_OCR_DEVICE_JP2", "0").lower() not in ("", "0", "false", "no")
+        # LUMINA_OCR_JP2_IRREVERSIBLE=1: with LUMINA_OCR_DEVICE_JP2, files of the 9/7 irreversible transform (what lossy JPEG 2000 is in
+        # practice) are decoded on the device as well (lumina_ocr_jp2_decode_irreversible), wherever a 5/3 file is.  Off by default, and
+        # ignored without LUMINA_OCR_DEVICE_JP2: exactly the calls made without the option are made.
+        self.jp2_irreversible = os.environ.get("LUMINA_OCR_JP2_IRREVERSIBLE", "0").lower() not in ("", "0", "false", "no")
         self._jp2_reasons_logged: set = set()
         self.apply_binarize = "adaptive" if b in ("1", "true", "yes", "adaptive") else ("simple" if b == "simple" else None)
         self._device = int(os.environ.get("LUMINA_OCR_DEVICE", os.environ.get("LOCAL_RANK", 0)))
@@ -567,7 +571,7 @@ class OCRService:
     def _jp2_probe(self, data: bytes, size) -> Optional[Dict[str, Any]]:
         """The probe's info when the device decodes this JPEG 2000 file and its size is `size`, else None, the reason logged once."""
         from ..engine import Engine
-        rc, info = Engine.jp2_probe(data)
+        rc, info = Engine.jp2_probe_irreversible(data) if self.jp2_irreversible else Engine.jp2_probe(data)
         if rc == 0 and (info["width"], info["height"]) == tuple(size):
             return info
         reason = info["reason"] if rc else "size differs from the opened image's"
@@ -575,6 +579,9 @@ class OCRService:
             self._jp2_reasons_logged.add(reason)
             logger.info("JPEG 2000 input left to Pillow (status %d): %s", rc, reason)
         return None
+
+    def _jp2_decoder(self):
+        return self._engine.jp2_decode_irreversible if self.jp2_irreversible else self._engine.jp2_decode
 
     def _decode_jp2_on_device(self, data: bytes, image: Image.Image):
         """A JPEG 2000 file of the device subset -> device tensor [1,H,W,3] (lumina_ocr_jp2_decode: byte-identical to Pillow), or None:
@@ -587,7 +594,7 @@ class OCRService:
             if info is None:
                 return None
             with self._device_ctx():
-                out, status = self._engine.jp2_decode([data], info["height"], info["width"])
+                out, status = self._jp2_decoder()([data], info["height"], info["width"])
                 return out if status == [0] else None
         except Exception as e:       # any doubt: the reference's own path
             logger.warning("device JPEG 2000 decode not used: %s", e)
@@ -724,7 +731,7 @@ class OCRService:
             if cand:
                 with self._device_ctx():
                     for (w, h), items in cand.items():
-                        out, status = self._engine.jp2_decode([d for _, d in items], h, w)
+                        out, status = self._jp2_decoder()([d for _, d in items], h, w)
                         for k, (i, _) in enumerate(items):
                             if status[k] == 0:
                                 res[i] = out[k:k + 1]
@@ -839,7 +846,7 @@ class OCRService:
                         decode = eng.jpeg_decode_progressive if self.progressive_jpeg else eng.jpeg_decode
                         out, status = decode(streams, h, w) if self.device_jpeg else (None, [-2] * len(idxs))
                     elif filt == "JPXDecode":   # (only with LUMINA_OCR_DEVICE_JP2: read_pages returns none otherwise)
-                        out, status = eng.jp2_decode(streams, h, w)
+                        out, status = self._jp2_decoder()(streams, h, w)
                     elif filt in ("LZWDecode", "RunLengthDecode"):   # one-strip pages of the strip decoders
                         codec = 5 if filt == "LZWDecode" else 32773
                         params = [(codec, r.params["predictor"], r.params["components"], r.params["bits"], int(r.params["indexed"]),
@@ -1099,7 +1106,7 @@ class OCRService:
     # ---- status (:759-795) ----
     def get_status(self) -> Dict[str, Any]:
         st = {"client_initialized": self._pipeline is not None, "model_id": "dbnet-r18vd+crnn-mv3", "max_dimension": self.max_dimension,
-              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "aztec": self._use_aztec, "aztec_max_layers": self._aztec_max_layers_status(), "device_pdf": self.device_pdf, "progressive_jpeg": self.progressive_jpeg, "device_tiff": self.device_tiff, "device_jp2": self.device_jp2, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
+              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "aztec": self._use_aztec, "aztec_max_layers": self._aztec_max_layers_status(), "device_pdf": self.device_pdf, "progressive_jpeg": self.progressive_jpeg, "device_tiff": self.device_tiff, "device_jp2": self.device_jp2, "jp2_irreversible": self.jp2_irreversible, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
         if self._engine is not None:
             st["engine_version"] = self._engine.version()
             st["num_classes"] = self._engine.num_classes

@@ -9,7 +9,13 @@ per page.  The split of the device time between tier 1 and the DWT comes from a 
 timed call of that case, nothing else), in a run of its own.  Writes profiles/jp2_probe.json and prints it; needs an MI355X.  No
 threshold: the host decode is what each figure is compared with.
 
-    python tools/jp2_probe.py [--reps 20] [--pages 64] [--host-reps 3] [--cases ...] [--trace CASE]"""
+--irreversible times lumina_ocr_jp2_decode_irreversible instead, on the 9/7 files an `irreversible=True` writer produces:
+  * `rgb97_default`, `grey97_default`    the writer's default rate;
+  * `rgb97_layers20`, `grey97_layers20`  quality_layers=[20];
+and, through the same entry in the same run, the 5/3 `rgb_layers20` / `grey_layers20` files to set them beside.  It writes
+profiles/jp2_irreversible_probe.json; `--trace CASE` splits tier 1, the 9/7 lifting (j2_dwt97_h / j2_dwt97_v) and the finish.
+
+    python tools/jp2_probe.py [--irreversible] [--reps 20] [--pages 64] [--host-reps 3] [--cases ...] [--trace CASE]"""
 import argparse
 import io
 import json
@@ -24,6 +30,10 @@ for p in (ROOT, ROOT / "ocr-system_amd"):
 W, H = 1654, 2339
 CASES = {"rgb_lossless": ("RGB", {}), "grey_lossless": ("L", {}), "rgb_layers20": ("RGB", {"quality_layers": [20]}),
          "grey_layers20": ("L", {"quality_layers": [20]})}
+CASES97 = {"rgb97_default": ("RGB", {"irreversible": True}), "grey97_default": ("L", {"irreversible": True}),
+           "rgb97_layers20": ("RGB", {"irreversible": True, "quality_layers": [20]}),
+           "grey97_layers20": ("L", {"irreversible": True, "quality_layers": [20]}),
+           "rgb_layers20": CASES["rgb_layers20"], "grey_layers20": CASES["grey_layers20"]}
 
 
 def main():
@@ -32,10 +42,14 @@ def main():
     ap.add_argument("--host-reps", type=int, default=3)
     ap.add_argument("--pages", type=int, default=64)
     ap.add_argument("--distinct", type=int, default=4)
-    ap.add_argument("--cases", default=",".join(CASES))
+    ap.add_argument("--irreversible", action="store_true")
+    ap.add_argument("--cases", default="")
     ap.add_argument("--trace", default="")
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "jp2_probe.json"))
+    ap.add_argument("--out", default="")
     args = ap.parse_args()
+    cases = CASES97 if args.irreversible else CASES
+    args.cases = args.cases or ",".join(cases)
+    args.out = args.out or str(ROOT / "profiles" / ("jp2_irreversible_probe.json" if args.irreversible else "jp2_probe.json"))
     import numpy as np
     import torch
     from PIL import Image
@@ -43,13 +57,15 @@ def main():
     from lumina_ocr.engine import Engine
 
     eng = Engine(0)
+    decode = eng.jp2_decode_irreversible if args.irreversible else eng.jp2_decode
+    probe = Engine.jp2_probe_irreversible if args.irreversible else Engine.jp2_probe
     src = [synth.synth_page(H, W, 100 + k, n_lines=40)[0] for k in range(args.distinct)]
 
     def write(mode, opts):
         files = []
         for page in src:
             op = io.BytesIO()
-            Image.fromarray(page if mode == "RGB" else np.ascontiguousarray(page[:, :, 1])).save(op, "JPEG2000", irreversible=False, **opts)
+            Image.fromarray(page if mode == "RGB" else np.ascontiguousarray(page[:, :, 1])).save(op, "JPEG2000", **dict(dict(irreversible=False), **opts))
             files.append(op.getvalue())
         return files
 
@@ -65,26 +81,26 @@ def main():
         return dict(median=round(float(np.median(times)), 2), min=round(min(times), 2), max=round(max(times), 2)), out
 
     if args.trace:
-        files = write(*CASES[args.trace])
+        files = write(*cases[args.trace])
         streams = [files[i % len(files)] for i in range(args.pages)]
         out_buf = torch.empty((args.pages, H, W, 3), dtype=torch.uint8, device="cuda")
-        t, (_, status) = timed(lambda: eng.jp2_decode(streams, H, W, out=out_buf), 1)
+        t, (_, status) = timed(lambda: decode(streams, H, W, out=out_buf), 1)
         print(json.dumps(dict(trace=args.trace, pages=args.pages, device_ms=t, status_ok=status.count(0))))
         eng.close()
         return
 
     res = dict(pages=args.pages, height=H, width=W, distinct=args.distinct, reps=args.reps, host_reps=args.host_reps)
     for name in args.cases.split(","):
-        files = write(*CASES[name])
+        files = write(*cases[name])
         t_host, ref = timed(lambda: [np.asarray(Image.open(io.BytesIO(s)).convert("RGB")) for s in files], args.host_reps, sync=False)
-        t_tier2, probes = timed(lambda: [Engine.jp2_probe(s) for s in files], args.host_reps, sync=False)
+        t_tier2, probes = timed(lambda: [probe(s) for s in files], args.host_reps, sync=False)
         host_page = t_host["median"] / len(files)
         entry = dict(file_kb=round(sum(len(s) for s in files) / len(files) / 1024, 1), probe_status=[rc for rc, _ in probes],
                      host_ms_per_page=round(host_page, 2), host_ms_distinct=t_host, tier2_host_ms_per_page=round(t_tier2["median"] / len(files), 3))
         for label, n in (("batch", args.pages), ("single", 1)):
             streams = [files[i % len(files)] for i in range(n)]
             out_buf = torch.empty((n, H, W, 3), dtype=torch.uint8, device="cuda")
-            t_dev, (out, status) = timed(lambda: eng.jp2_decode(streams, H, W, out=out_buf), args.reps)
+            t_dev, (out, status) = timed(lambda: decode(streams, H, W, out=out_buf), args.reps)
             equal = all(status[i] == 0 and np.array_equal(out[i].cpu().numpy(), ref[i]) for i in range(min(n, len(files))))
             entry[label] = dict(pages=n, device_ms=t_dev, host_batch_ms=round(host_page * n, 1), status_ok=status.count(0), equal_to_host=bool(equal),
                                 device_pages_per_s=round(n / t_dev["median"] * 1e3, 1), host_pages_per_s=round(1e3 / host_page, 1))
