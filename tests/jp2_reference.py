@@ -11,7 +11,8 @@ MAX_SIDE = 16384
 MAX_PIXELS = 1 << 26
 MAX_LAYERS = 32
 MAX_LEVELS = 6
-MAX_MB = 15          # magnitude bit-planes a block may have (8-bit samples through six 5/3 levels need 11 with two guard bits)
+MAX_MB = 15          # magnitude bit-planes a block may have (8-bit samples through six 5/3 levels need 11 with two guard bits;
+#                      tests/test_jp2_unusual.py::test_deep_cases_are_deep holds the files that reach 15, Pillow writes none)
 MAX_BLOCKS = 1 << 20
 
 

@@ -74,6 +74,27 @@ def test_intact_pixels(program, tmp_path, window):
         assert np.array_equal(rgb, exp), name
 
 
+@pytest.mark.parametrize("window", [6, 56])
+def test_unusual_corpus_pixels(program, tmp_path, window):
+    """tests/jp2_unusual_cases.py: the whole corpus has the restatement's statuses, and the host decode of every accepted 9/7 case is
+    Pillow's (the 5/3 ones: tests/test_jp2_parser_sanitized.py), before tests/test_gpu_jp2_unusual.py sends the files to the device"""
+    import jp2_unusual_cases as uc
+    cases = uc.accepted() + uc.refused()
+    got, names = run(program, tmp_path, [c.data for c in cases], pixels=window)
+    n97 = 0
+    for c, (status, info, kind), path in zip(cases, got, names):
+        st, _, inf = ir.probe(c.data)
+        assert (status, info) == (st, inf), c.name
+        assert st == (-2 if c.family == "refused" else 0), c.name
+        if st == 0:
+            assert kind == int(c.irreversible), c.name
+        if st == 0 and c.irreversible:
+            exp = jc.expected(c.data)
+            assert np.array_equal(np.fromfile(path + ".rgb", np.uint8).reshape(exp.shape), exp), c.name
+            n97 += 1
+    assert n97 >= 5
+
+
 def test_refused_and_reversible_statuses(program, tmp_path):
     cases = ic.refused()
     got, _ = run(program, tmp_path, [data for _, data, _ in cases])

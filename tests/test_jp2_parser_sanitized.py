@@ -88,6 +88,28 @@ def test_refused_statuses(program, tmp_path):
     assert [st for st, _ in got] == [-2] * len(cases)
 
 
+def test_unusual_corpus_statuses(program, tmp_path):
+    """every file of tests/jp2_unusual_cases.py, accepted and refused (a 9/7 one is refused here: this program has no such option)"""
+    import jp2_unusual_cases as uc
+    cases = uc.accepted() + uc.refused()
+    got, _ = run(program, tmp_path, [c.data for c in cases])
+    want = {c.name: jr.probe(c.data) for c in cases}
+    assert [(c.name, st, info) for c, (st, info) in zip(cases, got)] == [(c.name, want[c.name][0], want[c.name][2]) for c in cases]
+    assert [st for c, (st, _) in zip(cases, got) if not c.irreversible] == [0] * sum(not c.irreversible for c in uc.accepted()) + [-2] * 3
+
+
+def test_unusual_corpus_pixels(program, tmp_path):
+    """the host decode, by the functions the kernels run, of every accepted 5/3 case is Pillow's: each file goes through csrc/jp2_t1.h
+    under the sanitizers before tests/test_gpu_jp2_unusual.py sends it to the device (the 9/7 ones: test_jp2_irreversible_sanitized)"""
+    import jp2_unusual_cases as uc
+    cases = [c for c in uc.accepted() if not c.irreversible]
+    got, names = run(program, tmp_path, [c.data for c in cases], pixels=True)
+    for c, (status, info), path in zip(cases, got, names):
+        assert status == 0, c.name
+        exp = jc.expected(c.data)
+        assert np.array_equal(np.fromfile(path + ".rgb", np.uint8).reshape(exp.shape), exp), c.name
+
+
 def test_gpu_damage_sample_pixels(program, tmp_path):
     """the damaged files tests/test_gpu_jp2.py sends to the device, decoded on the host first by the functions the kernels run"""
     sample = jc.sweep_sample(200, seed=2000)
