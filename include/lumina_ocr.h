@@ -453,6 +453,41 @@ int lumina_ocr_page_turn(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int h
                          uint8_t* out_dev, void* stream);
 int lumina_ocr_page_vote(lumina_ocr_t* h, const int32_t* flip_dev, const int32_t* page_idx_dev, int n, int pages, int32_t* counts_dev, void* stream);
 
+/* ---- page composition (optional; DESIGN.md §3: "Layered PDF pages") ----
+ * A scanned PDF page painted from several images (strips, a stencil over a background, images with a soft or an explicit mask) is
+ * put together from its decoded layers.  lumina_ocr/utils/pdf_pages.py finds the layers and computes the integer canvas; the
+ * device sees integers only.
+ *
+ * lumina_ocr_page_compose: out_dev uint8 [n][height][width][3].  layers: HOST array of n_layers records, the layers of page 0 first,
+ * each page's in paint order (pages ascending; at most 64 layers a page; a page may have none).  A pixel starts at 255, 255, 255
+ * and is painted once per layer of its page, in that order, for each layer whose rectangle x0 <= x < x1, y0 <= y < y1 holds it
+ * (the rectangle may stick out of the canvas; it must meet it and |coordinate| <= 2^24):
+ *   sampling  the sample that holds the pixel centre (PDF's rule without /Interpolate):
+ *             u = floor((2 (x - x0) + 1) w / (2 (x1 - x0))), v likewise from y and h; for the mask the same with mw, mh over the
+ *             same rectangle.  (x1 - x0 == w is the identity u = x - x0.)
+ *   kind 0    opaque image:        c = src[v][u]
+ *   kind 1    stencil:             c = fill where (mask[v][u] < 128) != flip            (fill = r | g << 8 | b << 16)
+ *   kind 2    image with /SMask:   a = flip ? 255 - mask[v][u] : mask[v][u]; per channel c = div255(src * a + c * (255 - a)),
+ *             div255(t) = (t + 128 + ((t + 128) >> 8)) >> 8  (= t / 255 rounded to nearest)
+ *   kind 3    image with /Mask:    c = src[v][u] unless (mask[v][u] >= 128) != flip     (that sample is masked out)
+ * src and mask are device images as the decoders write them, uint8 [h][w][3] and [mh][mw][3]; a mask is read from channel 0.
+ * Pure integer arithmetic, every output byte written exactly once: defined byte for byte (tests/pdf_layers_reference.py).
+ * The table is checked on the host before anything is launched (sides 1..65535, kinds 0..3, non-empty rectangles that meet the
+ * canvas, a source for kinds 0 / 2 / 3 and a mask for kinds 1 / 2 / 3 with sides 1..65535, at most 64 layers a page): a table that
+ * fails returns 1 with the reason in lumina_ocr_last_error and launches nothing.  The table is copied to the device through the
+ * engine's own buffers: the caller may free it when the call returns.  Asynchronous; n == 0 is a no-op. */
+typedef struct {
+    int32_t page, kind;          /* page 0..n-1; kind 0..3 */
+    int32_t x0, y0, x1, y1;      /* canvas rectangle */
+    int32_t flip, fill;          /* polarity of the mask (0 | 1); fill colour of a stencil */
+    const uint8_t* src;          /* device, [h][w][3] (kinds 0, 2, 3) */
+    int32_t w, h;
+    const uint8_t* mask;         /* device, [mh][mw][3] (kinds 1, 2, 3) */
+    int32_t mw, mh;
+} lumina_ocr_compose_layer;
+int lumina_ocr_page_compose(lumina_ocr_t* h, const lumina_ocr_compose_layer* layers, int n_layers, int n, int height, int width,
+                            uint8_t* out_dev, void* stream);
+
 /* Second recogniser family (BASELINE configs[4]: "SVTR-base multilingual (Hindi dict), fp16 MFMA"): same slot and the same outputs as
  * lumina_ocr_load_rec_weights / lumina_ocr_rec_forward (the `rec` model of the engine call, ocr_service_paddleocr_backup.py:232-238,
  * :285), with an SVTR backbone (patch embedding, local / global mixing blocks, CTC head) instead of CRNN.  Blob: LOCW with the

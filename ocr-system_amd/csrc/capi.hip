@@ -14,6 +14,7 @@
 #include "aztec.h"
 #include "ops.h"
 #include "orient.h"
+#include "compose.h"
 #include "resize.h"
 #include "runs.h"
 #include "jpeg.h"
@@ -1035,6 +1036,16 @@ int lumina_ocr_page_vote(lumina_ocr_t* h, const int32_t* flip_dev, const int32_t
     if (!counts_dev || pages < 0 || n < 0 || (n > 0 && (!flip_dev || !page_idx_dev))) return locr_fail(h, "page_vote", "bad arguments");
     BIND(h);
     return hip_rc(h, "page_vote", page_vote_launch(flip_dev, page_idx_dev, n, pages, counts_dev, (hipStream_t)stream));
+}
+
+int lumina_ocr_page_compose(lumina_ocr_t* h, const lumina_ocr_compose_layer* layers, int n_layers, int n, int height, int width, uint8_t* out_dev,
+                            void* stream) {
+    if (!h) return 1;
+    if (n == 0) return 0;
+    BIND(h);
+    API_TRY
+    return page_compose_run(h, layers, n_layers, n, height, width, out_dev, (hipStream_t)stream);
+    API_CATCH(h)
 }
 
 int lumina_ocr_svtr_num_classes(const lumina_ocr_t* h) { return h ? h->svtr.num_classes : 0; }

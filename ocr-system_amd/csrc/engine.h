@@ -166,6 +166,8 @@ struct lumina_ocr {
     Staging jp_stage;   // pinned staging of the JPEG 2000 decoder's block records and coded bytes (jp2dec.hip)
     int jp_sub_batch_mb = 4096;   // JPEG 2000 decoder: MB of coefficient planes per sub-batch (an A4 RGB page at 200 dpi takes 93 MB)
     float* dk_trig = nullptr; short* dk_wtab = nullptr;   // de-skew tables (deskew.h), uploaded at first use
+    Staging pc_stage;               // pinned copy of the page-composition layer table (compose.hip) ...
+    Growable<DeviceMem> pc_table;   // ... and its device copy; `uploaded` is recorded after the kernel that reads it
 };
 
 int locr_fail(lumina_ocr* eng, const char* what, const char* detail);

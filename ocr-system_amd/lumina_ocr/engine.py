@@ -119,6 +119,7 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_page_quarter": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_page_turn": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp]),
         "lumina_ocr_page_vote": (i32, [vp, vp, vp, i32, i32, vp, vp]),
+        "lumina_ocr_page_compose": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     }
     missing = []
     for name, (res, args) in sig.items():
@@ -149,7 +150,15 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks", "lumina_ocr_selection_marks_round",
     "lumina_ocr_rules_and_marks_round", "lumina_ocr_barcodes", "lumina_ocr_barcodes_kinds", "lumina_ocr_qrcodes", "lumina_ocr_qrcodes_versions", "lumina_ocr_datamatrix", "lumina_ocr_aztec", "lumina_ocr_aztec_workspace_bytes", "lumina_ocr_aztec_layers", "lumina_ocr_aztec_layers_workspace_bytes",
     "lumina_ocr_page_quarter_workspace_bytes", "lumina_ocr_page_quarter", "lumina_ocr_page_turn", "lumina_ocr_page_vote",
+    "lumina_ocr_page_compose",
 ]
+
+
+class ComposeLayer(ctypes.Structure):
+    """lumina_ocr_compose_layer (include/lumina_ocr.h): one layer of a composed page"""
+    _fields_ = [("page", ctypes.c_int32), ("kind", ctypes.c_int32), ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("x1", ctypes.c_int32),
+                ("y1", ctypes.c_int32), ("flip", ctypes.c_int32), ("fill", ctypes.c_int32), ("src", ctypes.c_void_p), ("w", ctypes.c_int32),
+                ("h", ctypes.c_int32), ("mask", ctypes.c_void_p), ("mw", ctypes.c_int32), ("mh", ctypes.c_int32)]
 
 
 def _torch():
@@ -916,6 +925,33 @@ class Engine:
         m = index.shape[0]
         out = torch.empty((m, w, h, 3) if turn & 1 else (m, h, w, 3), dtype=torch.uint8, device=pages.device)
         self._chk(self.lib.lumina_ocr_page_turn(self._h, _ptr(pages), n, h, w, _ptr(index), m, int(turn), _ptr(out), self._stream()))
+        return out
+
+    def page_compose(self, canvas_hw, n: int, layers):
+        """Pages painted from decoded layers (lumina_ocr_page_compose): canvas_hw = (H, W) of every page, layers = [(page 0..n-1, kind 0..3,
+        (x0, y0, x1, y1), flip 0 | 1, fill (r, g, b), src, mask), ...] grouped by page in ascending order, each page's in paint order, at
+        most 64 a page; src / mask: uint8 [h,w,3] device tensors as the decoders write them (a mask is read from channel 0), None where the
+        kind has none (0 opaque image: src; 1 stencil: mask; 2 image with soft mask, 3 image with explicit mask: both).  A pixel starts
+        white and takes, per layer whose rectangle holds it, the sample that holds its centre -> uint8 [n,H,W,3].  The table is checked
+        before anything is launched (EngineError with the reason).  Asynchronous; the caller keeps src / mask alive until the stream is
+        past the call."""
+        torch = _torch()
+        h, w = int(canvas_hw[0]), int(canvas_hw[1])
+        dev = torch.device("cuda", self.device)
+        table = (ComposeLayer * max(1, len(layers)))()
+        for rec, (page, kind, rect, flip, fill, src, mask) in zip(table, layers):
+            for t in (src, mask):
+                if t is not None and not (t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3 and t.is_contiguous() and t.device == dev):
+                    raise ValueError("src and mask must be contiguous uint8 [h,w,3] on %s" % dev)
+            rec.page, rec.kind, rec.flip = int(page), int(kind), int(flip)
+            rec.x0, rec.y0, rec.x1, rec.y1 = (int(v) for v in rect)
+            rec.fill = int(fill[0]) | int(fill[1]) << 8 | int(fill[2]) << 16
+            rec.src, rec.h, rec.w = (None, 0, 0) if src is None else (src.data_ptr(), src.shape[0], src.shape[1])
+            rec.mask, rec.mh, rec.mw = (None, 0, 0) if mask is None else (mask.data_ptr(), mask.shape[0], mask.shape[1])
+        if not (0 < h <= 65535 and 0 < w <= 65535 and n >= 0):
+            raise ValueError("canvas sides must be 1..65535")
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+        self._chk(self.lib.lumina_ocr_page_compose(self._h, ctypes.addressof(table), len(layers), int(n), h, w, _ptr(out), self._stream()))
         return out
 
     def page_vote(self, flip, page_idx, pages: int):

@@ -130,6 +130,11 @@ class OCRService:
         # on the device from its embedded stream, at the image's own sample grid, instead of being rasterised by pdf2image / poppler; other
         # pages still go to pdf_to_images.  Off by default: process_pdf_sync is then the rasterise-and-batch path alone.
         self.device_pdf = os.environ.get("LUMINA_OCR_PDF_SCANS", "0").lower() not in ("", "0", "false", "no")
+        # LUMINA_OCR_PDF_LAYERS=1 (with LUMINA_OCR_PDF_SCANS=1; ignored without it): pages painted from several images (strips, a
+        # stencil over a background, images with /SMask or a /Mask stream) and pages with an invisible text layer are read as well:
+        # their layers join the decode groups and lumina_ocr_page_compose puts them together.  Off by default: exactly the calls made
+        # without the option are made.
+        self.pdf_layers = os.environ.get("LUMINA_OCR_PDF_LAYERS", "0").lower() not in ("", "0", "false", "no")
         # LUMINA_OCR_DEVICE_TIFF=1: stripped TIFF inputs (LZW, PackBits, Deflate, Group 4, Group 3, CCITT RLE, uncompressed; utils/tiff_pages.py) are decoded on
         # the device, process_tiff_sync reads every page of a multi-page TIFF, and process_document sends "tiff" and "tif" there.  Off by
         # default: a TIFF is then decoded by Pillow, first frame only, and every output is exactly the one without the option.
@@ -829,17 +834,27 @@ class OCRService:
     def _decode_pdf_pages(self, entries, reasons: Dict[int, str]) -> Dict[int, Any]:
         """The accepted pages of pdf_pages.read_pages -> {page index: device tensor [1,H,W,3], /Rotate applied}: grouped by filter and
         size, one decoder call per group.  A page a decoder refuses gets its reason in `reasons` (it goes to the rasteriser); a DCT page
-        the device JPEG decoder does not take is decoded by Pillow, as JPEG files are."""
-        groups: Dict[Any, List[int]] = {}
+        the device JPEG decoder does not take is decoded by Pillow, as JPEG files are.  The images and masks of a layered page
+        (pdf_pages.PageLayers, LUMINA_OCR_PDF_LAYERS=1) join the same groups; such pages are then put together per canvas size by
+        page_compose.  A layered page one of whose layers is not decoded gets that layer's reason and goes to the rasteriser whole."""
+        # what is decoded: (page index, None) for a one-image page, (page index, (layer, 0 image | 1 mask)) for a layer of a layered one
+        groups: Dict[Any, List[Any]] = {}
         for i, e in enumerate(entries):
             if isinstance(e, pdf_pages.PageImage):
-                groups.setdefault((e.filter, e.width, e.height), []).append(i)
+                groups.setdefault((e.filter, e.width, e.height), []).append(((i, None), e))
+            elif isinstance(e, pdf_pages.PageLayers):
+                for k, layer in enumerate(e.layers):
+                    for which, r in enumerate((layer.image, layer.mask)):
+                        if r is not None:
+                            groups.setdefault((r.filter, r.width, r.height), []).append(((i, (k, which)), r))
         res: Dict[int, Any] = {}
+        parts: Dict[Any, Any] = {}   # the decoded layers of layered pages
         self._ensure_engine()
         eng = self._engine
         with self._device_ctx():
-            for (filt, w, h), idxs in groups.items():
-                recs = [entries[i] for i in idxs]
+            for (filt, w, h), items in groups.items():
+                idxs = [key[0] for key, _ in items]
+                recs = [r for _, r in items]
                 streams = [bytes(r.stream) for r in recs]
                 try:
                     if filt == "DCTDecode":
@@ -861,9 +876,9 @@ class OCRService:
                         out, status = eng.fax_decode(streams, h, w, [q + (0,) for q in params])
                 except Exception as e:   # the engine's own failure: these pages go to the rasteriser
                     for i in idxs:
-                        reasons[i] = "%s decode failed: %s" % (filt, e)
+                        reasons.setdefault(i, "%s decode failed: %s" % (filt, e))
                     continue
-                for k, i in enumerate(idxs):
+                for k, (i, slot) in enumerate(key for key, _ in items):
                     page = None
                     if status[k] == 0:
                         page = out[k:k + 1]
@@ -873,12 +888,31 @@ class OCRService:
                             if im.size == (w, h):
                                 page = self._upload(self._stage_pages([im]))
                         except Exception as e:
-                            reasons[i] = "embedded JPEG not decodable: %s" % e
+                            reasons.setdefault(i, "embedded JPEG not decodable: %s" % e)
                             continue
                     if page is None:
-                        reasons[i] = "%s stream %s (status %d)" % (filt, "corrupt" if status[k] == -1 else "outside the device subset", status[k])
+                        reasons.setdefault(i, "%s stream %s (status %d)" % (filt, "corrupt" if status[k] == -1 else "outside the device subset", status[k]))
                         continue
-                    res[i] = eng.exif_transpose(page, self.ROTATE_TO_EXIF[recs[k].rotate])
+                    if slot is None:
+                        res[i] = eng.exif_transpose(page, self.ROTATE_TO_EXIF[recs[k].rotate])
+                    else:
+                        parts[(i, slot)] = page[0]
+            # layered pages: one page_compose per canvas size, then /Rotate; from here on they are ordinary pages
+            canvases: Dict[Any, List[int]] = {}
+            for i, e in enumerate(entries):
+                if isinstance(e, pdf_pages.PageLayers) and i not in reasons:
+                    canvases.setdefault((e.height, e.width), []).append(i)
+            for hw, idxs in canvases.items():
+                table = [(j, l.kind, l.rect, l.flip, l.fill, parts.get((i, (k, 0))), parts.get((i, (k, 1))))
+                         for j, i in enumerate(idxs) for k, l in enumerate(entries[i].layers)]
+                try:
+                    pages = eng.page_compose(hw, len(idxs), table)
+                except Exception as e:
+                    for i in idxs:
+                        reasons[i] = "page composition failed: %s" % e
+                    continue
+                for j, i in enumerate(idxs):
+                    res[i] = eng.exif_transpose(pages[j:j + 1], self.ROTATE_TO_EXIF[entries[i].rotate])
         return res
 
     def _process_pdf_scans_sync(self, pdf_path: Union[str, Path]) -> DocumentOCRResult:
@@ -886,7 +920,8 @@ class OCRService:
         try:
             data = Path(pdf_path).read_bytes()
             try:
-                entries = pdf_pages.read_pages(data, strip_filters=self.device_tiff, **({"jpx": True} if self.device_jp2 else {}))
+                entries = pdf_pages.read_pages(data, strip_filters=self.device_tiff, **({"jpx": True} if self.device_jp2 else {}),
+                                               **({"layers": True} if self.pdf_layers else {}))
             except pdf_pages.PdfRefused as e:   # not a file the reader takes: the rasterise-and-batch path, whole
                 r = self.process_pdf_as_images_sync(pdf_path)
                 if not r.success and r.error and not r.pages:
@@ -1106,7 +1141,7 @@ class OCRService:
     # ---- status (:759-795) ----
     def get_status(self) -> Dict[str, Any]:
         st = {"client_initialized": self._pipeline is not None, "model_id": "dbnet-r18vd+crnn-mv3", "max_dimension": self.max_dimension,
-              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "aztec": self._use_aztec, "aztec_max_layers": self._aztec_max_layers_status(), "device_pdf": self.device_pdf, "progressive_jpeg": self.progressive_jpeg, "device_tiff": self.device_tiff, "device_jp2": self.device_jp2, "jp2_irreversible": self.jp2_irreversible, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
+              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "aztec": self._use_aztec, "aztec_max_layers": self._aztec_max_layers_status(), "device_pdf": self.device_pdf, "pdf_layers": self.pdf_layers, "progressive_jpeg": self.progressive_jpeg, "device_tiff": self.device_tiff, "device_jp2": self.device_jp2, "jp2_irreversible": self.jp2_irreversible, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
         if self._engine is not None:
             st["engine_version"] = self._engine.version()
             st["num_classes"] = self._engine.num_classes

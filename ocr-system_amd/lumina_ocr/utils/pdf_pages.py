@@ -24,12 +24,39 @@ images; no /ImageMask, /SMask or /Mask.  With jpx=True also /JPXDecode (JPEG 200
 DeviceGray / DeviceRGB matching the codestream's 1 or 3 components, /SMaskInData absent or 0, no /Decode, and the size in the codestream
 equal to the dictionary's.
 
+Layered pages (read_pages(..., layers=True); the provider asks with LUMINA_OCR_PDF_LAYERS=1): scanner output painted from several
+images.  A page with one opaque image and no mask still yields the PageImage above, now also when it carries invisible text; any other
+accepted page yields a PageLayers record, whose layers lumina_ocr_page_compose puts together on an integer canvas.
+Content accepted: q, Q, cm and up to MAX_LAYERS = 64 Do of image XObjects; the fill colour by g, rg, or cs /DeviceGray | /DeviceRGB
+followed by sc / scn with 1 or 3 numbers in [0, 1] (8 bits a channel as floor(v * 255 + 0.5), black by default, saved by q / Q); gs
+when the ExtGState holds nothing beyond Type, SA, OP, op, OPM, CA / ca equal to 1, BM /Normal or /Compatible, SMask /None and AIS false;
+the marked-content operators BMC BDC EMC MP DP (skipped); text objects whose text rendering mode (Tr: graphics state, saved by q / Q,
+0 by default) is 3 at every showing operator (Tj TJ ' "), the other text operators being parsed and ignored.  Everything else is refused
+with the reasons of the one-image reader: paths, clipping, inline images, shading, form XObjects, k / K, visible text.
+Placement: every Do axis-aligned with positive scales; the hull of all layer rectangles covers the MediaBox within EDGE_TOLERANCE (a
+single layer need not).
+Layer kinds, kept in paint order: 0 an opaque image under the image rules above; 1 a stencil (/ImageMask true, 1 bit, Flate or CCITT,
+LZW / RunLength with strip_filters; /Decode absent, [0 1] or [1 0]) painted in the fill colour current at its Do; 2 an image with an
+/SMask (DeviceGray, 1 or 8 bits, Flate, CCITT, grey DCT, grey JPX with jpx; of any size of its own; /Decode default or [1 0]; no
+/Matte); 3 an image with a /Mask stream (a 1-bit /ImageMask image; a sample that reads 1 after /Decode is masked out).  Refused, each
+with its reason: a colour-key /Mask array, /SMaskInData other than 0, /SMask or /Mask on a stencil or on a mask, /SMask and /Mask on
+one image, /Matte.
+Canvas: with the MediaBox (X0, Y0, X1, Y1), layer i placed by cm (a, 0, 0, d, e, f) and showing an image of w x h samples (a stencil's
+own size counts, the size of an /SMask or /Mask does not): sx = max w / a, sy = max h / d, R(v) = floor(v + 0.5), W = R((X1 - X0) sx),
+H = R((Y1 - Y0) sy), and the layer's rectangle is x0 = R((e - X0) sx), x1 = R((e + a - X0) sx), y0 = R((Y1 - f - d) sy),
+y1 = R((Y1 - f) sy), all in double precision on the host.  W or H above 65535, or W H above MAX_CANVAS_PIXELS (2^26: A4 at 600 dpi is
+34.8 M), is refused; a rectangle may stick out of the canvas; one that is empty or misses the canvas is dropped.
+Not read (the page is refused and goes to the rasteriser): JBIG2 masks, rotated or flipped placements, clipped strips (re W n), white
+re f underlays, form XObjects, CMYK fill, /Matte, colour-key masks, blend modes and constant alpha.  /Interpolate true is sampled as
+false: every layer is shown by the sample that holds the pixel centre.
+
 The reader ends on any input: every loop advances through the file or a decoded stream, /Prev chains, page-tree nodes and indirect
-references are followed through visited-sets, every offset and /Length is checked against the file size, and the number of objects, the
-nesting depth and the number of pages are capped.
+references (ExtGState and mask references among them) are followed through visited-sets, every offset and /Length is checked against the
+file size, and the number of objects, the nesting depth, the number of pages and the number of layers of a page are capped.
 """
 from __future__ import annotations
 
+import math
 import zlib
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Tuple, Union
@@ -42,6 +69,9 @@ EDGE_TOLERANCE = 0.01        # each image edge within this fraction of the Media
 FILTERS = ("DCTDecode", "FlateDecode", "CCITTFaxDecode")
 STRIP_FILTERS = ("LZWDecode", "RunLengthDecode")   # taken only when read_pages is asked to (strip_filters=True)
 JPX_FILTER = "JPXDecode"                            # taken only when read_pages is asked to (jpx=True)
+MAX_LAYERS = 64                      # images painted on one page (read_pages with layers=True)
+MAX_CANVAS_PIXELS = 1 << 26          # canvas of a layered page: A4 at 600 dpi is 4960 x 7016 = 34.8 M samples
+MAX_COORD = 1 << 24                  # |coordinate| of a layer rectangle on the canvas grid
 
 _WS = b"\x00\t\n\x0c\r "
 _DELIM = b"()<>[]{}/%"
@@ -735,7 +765,8 @@ def _jpx_page_image(doc: _Document, img: Stream, width: int, height: int, rotate
     return PageImage(filter=JPX_FILTER, stream=img.raw, params={"components": comps}, width=w, height=h, rotate=rotate, media_box=media_box)
 
 
-def _page_image(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], strip_filters: bool = False, jpx: bool = False) -> PageImage:
+def _page_frame(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any]):
+    """-> ((x0, y0, x1, y1) of the MediaBox, /Rotate, the page's content bytes)"""
     box = doc.resolve(attrs.get("MediaBox"))
     if not isinstance(box, list) or len(box) != 4:
         raise PdfRefused("no MediaBox")
@@ -762,14 +793,10 @@ def _page_image(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], str
         if not isinstance(s, Stream):
             raise PdfRefused("no page content")
         chunks.append(doc._decode_meta(s))
-    name, m = _content_image(b"\n".join(chunks))
-    a, b, c, d, e, f = m
-    if not (a > 0 and d > 0) or abs(b) > 1e-4 * a or abs(c) > 1e-4 * d:
-        raise PdfRefused("image placement is not axis-aligned with positive scales")
-    if (abs(e - x0) > EDGE_TOLERANCE * bw or abs(e + a - x1) > EDGE_TOLERANCE * bw or abs(f - y0) > EDGE_TOLERANCE * bh
-            or abs(f + d - y1) > EDGE_TOLERANCE * bh):
-        raise PdfRefused("image does not cover the MediaBox")
-    # the image
+    return (x0, y0, x1, y1), rotate, b"\n".join(chunks)
+
+
+def _xobject_image(doc: _Document, attrs: Dict[str, Any], name: str) -> Stream:
     res = doc.resolve(attrs.get("Resources"))
     xobjs = doc.resolve(res.get("XObject")) if isinstance(res, dict) else None
     img = doc.resolve(xobjs.get(name)) if isinstance(xobjs, dict) else None
@@ -777,11 +804,31 @@ def _page_image(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], str
         raise PdfRefused("XObject %s not found" % name)
     if doc.resolve(img.get("Subtype")) != "Image":
         raise PdfRefused("XObject %s is not an image" % name)
+    return img
+
+
+def _page_image(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], strip_filters: bool = False, jpx: bool = False) -> PageImage:
+    (x0, y0, x1, y1), rotate, content = _page_frame(doc, page, attrs)
+    bw, bh = x1 - x0, y1 - y0
+    name, m = _content_image(content)
+    a, b, c, d, e, f = m
+    if not (a > 0 and d > 0) or abs(b) > 1e-4 * a or abs(c) > 1e-4 * d:
+        raise PdfRefused("image placement is not axis-aligned with positive scales")
+    if (abs(e - x0) > EDGE_TOLERANCE * bw or abs(e + a - x1) > EDGE_TOLERANCE * bw or abs(f - y0) > EDGE_TOLERANCE * bh
+            or abs(f + d - y1) > EDGE_TOLERANCE * bh):
+        raise PdfRefused("image does not cover the MediaBox")
+    img = _xobject_image(doc, attrs, name)
     if doc.resolve(img.get("ImageMask")) is True:
         raise PdfRefused("/ImageMask")
     for key in ("SMask", "Mask"):
         if doc.resolve(img.get(key)) is not None:
             raise PdfRefused("/" + key)
+    return _image_record(doc, img, rotate, (x0, y0, x1, y1), strip_filters, jpx)
+
+
+def _image_record(doc: _Document, img: Stream, rotate: int, media_box, strip_filters: bool, jpx: bool) -> PageImage:
+    """the record of one opaque image XObject (its mask keys are the caller's business)"""
+    x0, y0, x1, y1 = media_box
     width, height = doc.resolve(img.get("Width")), doc.resolve(img.get("Height"))
     if not all(isinstance(v, int) and 0 < v <= 65535 for v in (width, height)):
         raise PdfRefused("malformed image size")
@@ -834,20 +881,305 @@ def _page_image(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], str
     return PageImage(filter=filt, stream=img.raw, params=params, width=width, height=height, rotate=rotate, media_box=(x0, y0, x1, y1))
 
 
-def read_pages(data, strip_filters: bool = False, jpx: bool = False) -> List[Union[PageImage, PdfRefused]]:
+# ------------------------------------------------------------------------------------------------------------------ layered pages
+@dataclass
+class Layer:
+    kind: int                        # 0 opaque image | 1 stencil | 2 image with /SMask | 3 image with a /Mask stream
+    rect: Tuple[int, int, int, int]  # x0, y0, x1, y1 on the canvas grid, rows counted from the top; may stick out of the canvas
+    fill: Tuple[int, int, int]       # the fill colour at the Do, 8 bits a channel (what a stencil is painted in)
+    flip: int                        # the mask's /Decode is [1 0]: its samples are read inverted (masks are decoded with invert = 0)
+    image: Optional[PageImage]       # kinds 0, 2, 3
+    mask: Optional[PageImage]        # kinds 1, 2, 3: one grey component, read from channel 0 of the decoded image
+
+
+@dataclass
+class PageLayers:
+    width: int                       # the canvas: the MediaBox at the finest sample grid among the layers
+    height: int
+    layers: List[Layer]              # in paint order, at most MAX_LAYERS
+    rotate: int
+    media_box: Tuple[float, float, float, float] = field(default=(0.0, 0.0, 0.0, 0.0))
+
+
+_TEXT_SHOW_OPS = {"Tj", "TJ", "'", '"'}
+_TEXT_STATE_OPS = {"Tf": 2, "Td": 2, "TD": 2, "Tm": 6, "T*": 0, "Tc": 1, "Tw": 1, "Tz": 1, "TL": 1, "Ts": 1}   # operands; parsed and ignored
+_MARKED_OPS = {"BMC", "BDC", "EMC", "MP", "DP"}
+_GS_HARMLESS = ("Type", "SA", "OP", "op", "OPM")
+
+
+def _is_num(v) -> bool:
+    return isinstance(v, (int, float)) and not isinstance(v, bool)
+
+
+def _colour8(vals) -> Tuple[int, int, int]:
+    if len(vals) not in (1, 3) or not all(_is_num(v) and 0 <= v <= 1 for v in vals):
+        raise PdfRefused("malformed fill colour")
+    c = [int(float(v) * 255 + 0.5) for v in vals]
+    return (c[0], c[0], c[0]) if len(c) == 1 else (c[0], c[1], c[2])
+
+
+def _gs_harmless(doc: _Document, attrs: Dict[str, Any], name: str) -> None:
+    """refuses a `gs` whose ExtGState could change what an image paints"""
+    res = doc.resolve(attrs.get("Resources"))
+    table = doc.resolve(res.get("ExtGState")) if isinstance(res, dict) else None
+    gs = doc.resolve(table.get(name)) if isinstance(table, dict) else None
+    if not isinstance(gs, dict):
+        raise PdfRefused("ExtGState %s not found" % name)
+    for key, v in gs.items():
+        v = doc.resolve(v)
+        if key in _GS_HARMLESS:
+            continue
+        if key in ("CA", "ca"):
+            if not _is_num(v) or v != 1:
+                raise PdfRefused("ExtGState /%s %r (constant alpha)" % (key, v))
+        elif key == "BM":
+            if v not in ("Normal", "Compatible"):
+                raise PdfRefused("ExtGState /BM %s (blend mode)" % (v if isinstance(v, str) else "malformed"))
+        elif key == "SMask":
+            if v != "None":
+                raise PdfRefused("ExtGState /SMask")
+        elif key == "AIS":
+            if v is not False:
+                raise PdfRefused("ExtGState /AIS true")
+        else:
+            raise PdfRefused("ExtGState /%s" % key[:16])
+
+
+def _content_layers(doc: _Document, attrs: Dict[str, Any], content: bytes) -> List[Tuple[str, Tuple[float, ...], Tuple[int, int, int]]]:
+    """[(XObject name, CTM at its Do, fill colour at its Do)] in paint order, of a content stream that holds q / Q / cm / Do, fill
+    colours, harmless gs, marked content and invisible text (text rendering mode 3 at every showing operator)"""
+    p = _Parser(content)
+    state = ((1.0, 0.0, 0.0, 1.0, 0.0, 0.0), (0, 0, 0), 1, 0)   # CTM, fill colour, components of the fill colour space, Tr
+    stack: List[Any] = []
+    operands: List[Any] = []
+    found: List[Tuple[str, Tuple[float, ...], Tuple[int, int, int]]] = []
+    in_text = False
+    while True:
+        p.skip_ws()
+        if p.p >= p.end:
+            break
+        c = content[p.p]
+        if c in b"/[(<" or c in b"+-.0123456789":
+            operands.append(p.obj())
+            if len(operands) > 64:
+                raise PdfRefused("malformed content stream")
+            continue
+        op = p.token().decode("latin-1")
+        if not op:
+            raise PdfRefused("malformed content stream")
+        ctm, fill, fill_comps, tr = state
+        if op == "q":
+            stack.append(state)
+            if len(stack) > MAX_DEPTH:
+                raise PdfRefused("graphics state nested too deep")
+        elif op == "Q":
+            if not stack:
+                raise PdfRefused("unbalanced Q")
+            state = stack.pop()
+        elif op == "cm":
+            if len(operands) != 6 or not all(_is_num(v) for v in operands):
+                raise PdfRefused("malformed cm")
+            state = (_mul(tuple(float(v) for v in operands), ctm), fill, fill_comps, tr)
+        elif op == "Do":
+            if len(operands) != 1 or not isinstance(operands[0], Name):
+                raise PdfRefused("malformed Do")
+            if len(found) >= MAX_LAYERS:
+                raise PdfRefused("more than %d images on the page" % MAX_LAYERS)
+            found.append((str(operands[0]), ctm, fill))
+        elif op in ("g", "rg"):
+            if len(operands) != (1 if op == "g" else 3):
+                raise PdfRefused("malformed fill colour")
+            state = (ctm, _colour8(operands), len(operands), tr)
+        elif op == "cs":
+            if len(operands) != 1 or operands[0] not in ("DeviceGray", "DeviceRGB"):
+                raise PdfRefused("fill colour space %s" % (operands[0] if operands and isinstance(operands[0], Name) else "malformed"))
+            state = (ctm, (0, 0, 0), 1 if operands[0] == "DeviceGray" else 3, tr)
+        elif op in ("sc", "scn"):
+            if len(operands) != fill_comps:
+                raise PdfRefused("malformed fill colour")
+            state = (ctm, _colour8(operands), fill_comps, tr)
+        elif op == "gs":
+            if len(operands) != 1 or not isinstance(operands[0], Name):
+                raise PdfRefused("malformed gs")
+            _gs_harmless(doc, attrs, str(operands[0]))
+        elif op in _MARKED_OPS:
+            pass
+        elif op == "BT":
+            if in_text:
+                raise PdfRefused("malformed content stream")
+            in_text = True
+        elif op == "ET":
+            if not in_text:
+                raise PdfRefused("malformed content stream")
+            in_text = False
+        elif op == "Tr":
+            if len(operands) != 1 or not isinstance(operands[0], int) or isinstance(operands[0], bool):
+                raise PdfRefused("malformed Tr")
+            state = (ctm, fill, fill_comps, operands[0])
+        elif op in _TEXT_STATE_OPS:
+            if len(operands) != _TEXT_STATE_OPS[op]:
+                raise PdfRefused("malformed %s" % op)
+        elif op in _TEXT_SHOW_OPS:
+            if not in_text or tr != 3:
+                raise PdfRefused("text operators on the page (%s)" % op)
+        elif op in ("BI", "ID", "EI"):
+            raise PdfRefused("inline image")
+        elif op in _CLIP_OPS:
+            raise PdfRefused("clipping on the page (%s)" % op)
+        else:
+            raise PdfRefused("content operator %r" % op[:8])
+        operands = []
+    if not found:
+        raise PdfRefused("no image on the page")
+    return found
+
+
+def _mask_decode(doc: _Document, stm: Stream) -> int:
+    """-> 1 when the mask's /Decode is [1 0], 0 when it is absent or [0 1]"""
+    decode = doc.resolve(stm.get("Decode"))
+    if decode is None:
+        return 0
+    decode = [doc.resolve(v) for v in decode] if isinstance(decode, list) else None
+    if decode == [0, 1]:
+        return 0
+    if decode == [1, 0]:
+        return 1
+    raise PdfRefused("/Decode %r on a mask" % (decode,))
+
+
+def _without(stm: Stream, drop, **add) -> Stream:
+    s = Stream({k: v for k, v in stm.items() if k not in drop})
+    s.update(add)
+    s.raw = stm.raw
+    return s
+
+
+def _stencil_record(doc: _Document, stm: Stream, rotate: int, media_box, strip_filters: bool) -> Tuple[PageImage, int]:
+    """(record, flip) of an /ImageMask image: one bit a sample, Flate or CCITT (LZW / RunLength under strip_filters)"""
+    for key in ("SMask", "Mask"):
+        if doc.resolve(stm.get(key)) is not None:
+            raise PdfRefused("/%s on a stencil" % key)
+    bits = doc.resolve(stm.get("BitsPerComponent", 1))
+    if bits != 1:
+        raise PdfRefused("stencil with %r bits per component" % (bits,))
+    filt, _ = doc.single_filter(stm)
+    if filt not in ("FlateDecode", "CCITTFaxDecode") and not (strip_filters and filt in STRIP_FILTERS):
+        raise PdfRefused("stencil filter %s" % filt)
+    flip = _mask_decode(doc, stm)
+    rec = _image_record(doc, _without(stm, ("Decode", "ImageMask", "ColorSpace", "SMaskInData"), ColorSpace=Name("DeviceGray"), BitsPerComponent=1),
+                        rotate, media_box, strip_filters, False)
+    return rec, flip
+
+
+def _soft_mask_record(doc: _Document, stm, rotate: int, media_box, jpx: bool) -> Tuple[PageImage, int]:
+    """(record, flip) of an /SMask image: DeviceGray, 1 or 8 bits, Flate, CCITT, grey DCT (grey JPX with jpx), no /Matte"""
+    if not isinstance(stm, Stream) or doc.resolve(stm.get("Subtype")) != "Image":
+        raise PdfRefused("/SMask is not an image")
+    if doc.resolve(stm.get("Matte")) is not None:
+        raise PdfRefused("/Matte")
+    for key in ("SMask", "Mask"):
+        if doc.resolve(stm.get(key)) is not None:
+            raise PdfRefused("/%s on a mask" % key)
+    filt, _ = doc.single_filter(stm)
+    if filt not in ("FlateDecode", "CCITTFaxDecode", "DCTDecode") and not (jpx and filt == JPX_FILTER):
+        raise PdfRefused("/SMask filter %s" % filt)
+    cs = doc.resolve(stm.get("ColorSpace"))
+    if cs != "DeviceGray" and not (filt == JPX_FILTER and cs is None):
+        raise PdfRefused("/SMask colour space %s" % (cs if isinstance(cs, Name) else "is not a name"))
+    flip = _mask_decode(doc, stm)
+    rec = _image_record(doc, _without(stm, ("Decode",)), rotate, media_box, False, jpx)
+    bits = rec.params.get("bits", 1 if filt == "CCITTFaxDecode" else 8)
+    if rec.params.get("components", 1) != 1 or bits not in (1, 8):
+        raise PdfRefused("/SMask with %r components of %r bits" % (rec.params.get("components", 1), bits))
+    return rec, flip
+
+
+def _layer(doc: _Document, img: Stream, rect, fill, rotate: int, media_box, strip_filters: bool, jpx: bool) -> Layer:
+    if doc.resolve(img.get("ImageMask")) is True:
+        rec, flip = _stencil_record(doc, img, rotate, media_box, strip_filters)
+        return Layer(kind=1, rect=rect, fill=fill, flip=flip, image=None, mask=rec)
+    smask, mask = doc.resolve(img.get("SMask")), doc.resolve(img.get("Mask"))
+    sid = doc.resolve(img.get("SMaskInData", 0))
+    if sid != 0:
+        raise PdfRefused("/SMaskInData %r" % (sid,))
+    base = _image_record(doc, img, rotate, media_box, strip_filters, jpx)
+    if smask is not None and mask is not None:
+        raise PdfRefused("/SMask and /Mask on one image")
+    if smask is not None:
+        rec, flip = _soft_mask_record(doc, smask, rotate, media_box, jpx)
+        return Layer(kind=2, rect=rect, fill=fill, flip=flip, image=base, mask=rec)
+    if mask is not None:
+        if isinstance(mask, list):
+            raise PdfRefused("colour-key /Mask")
+        if not isinstance(mask, Stream) or doc.resolve(mask.get("Subtype")) != "Image" or doc.resolve(mask.get("ImageMask")) is not True:
+            raise PdfRefused("/Mask is not an /ImageMask image")
+        rec, flip = _stencil_record(doc, mask, rotate, media_box, strip_filters)
+        return Layer(kind=3, rect=rect, fill=fill, flip=flip, image=base, mask=rec)
+    return Layer(kind=0, rect=rect, fill=fill, flip=0, image=base, mask=None)
+
+
+def _round(v: float) -> int:
+    return int(math.floor(v + 0.5))
+
+
+def _page_layers(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], strip_filters: bool, jpx: bool) -> Union[PageImage, PageLayers]:
+    (X0, Y0, X1, Y1), rotate, content = _page_frame(doc, page, attrs)
+    bw, bh = X1 - X0, Y1 - Y0
+    placed = []
+    for name, m, fill in _content_layers(doc, attrs, content):
+        a, b, c, d, e, f = m
+        if not (a > 0 and d > 0) or abs(b) > 1e-4 * a or abs(c) > 1e-4 * d:
+            raise PdfRefused("image placement is not axis-aligned with positive scales")
+        placed.append((name, a, d, e, f, fill))
+    hx0, hx1 = min(q[3] for q in placed), max(q[3] + q[1] for q in placed)
+    hy0, hy1 = min(q[4] for q in placed), max(q[4] + q[2] for q in placed)
+    if abs(hx0 - X0) > EDGE_TOLERANCE * bw or abs(hx1 - X1) > EDGE_TOLERANCE * bw or abs(hy0 - Y0) > EDGE_TOLERANCE * bh or abs(hy1 - Y1) > EDGE_TOLERANCE * bh:
+        raise PdfRefused("image does not cover the MediaBox" if len(placed) == 1 else "the images do not cover the MediaBox")
+    box = (X0, Y0, X1, Y1)
+    layers = [_layer(doc, _xobject_image(doc, attrs, name), None, fill, rotate, box, strip_filters, jpx) for name, _, _, _, _, fill in placed]
+    if len(layers) == 1 and layers[0].kind == 0:
+        return layers[0].image   # one opaque image over the whole box: today's record
+    # the canvas: the MediaBox at the finest sample grid among the layers (a stencil's own size counts, a mask's does not)
+    sizes = [(l.image or l.mask).width for l in layers], [(l.image or l.mask).height for l in layers]
+    sx = max(w / q[1] for w, q in zip(sizes[0], placed))
+    sy = max(h / q[2] for h, q in zip(sizes[1], placed))
+    W, H = _round(bw * sx), _round(bh * sy)
+    if not (0 < W <= 65535 and 0 < H <= 65535):
+        raise PdfRefused("canvas of %d x %d samples" % (W, H))
+    if W * H > MAX_CANVAS_PIXELS:
+        raise PdfRefused("canvas of %d x %d samples is above the cap of %d" % (W, H, MAX_CANVAS_PIXELS))
+    kept = []
+    for l, (_, a, d, e, f, _) in zip(layers, placed):
+        x0, x1 = _round((e - X0) * sx), _round((e + a - X0) * sx)
+        y0, y1 = _round((Y1 - f - d) * sy), _round((Y1 - f) * sy)
+        if x0 >= x1 or y0 >= y1 or x0 >= W or x1 <= 0 or y0 >= H or y1 <= 0:
+            continue   # empty, or wholly outside the canvas: it paints nothing
+        if max(abs(x0), abs(x1), abs(y0), abs(y1)) > MAX_COORD:
+            raise PdfRefused("image placed far outside the page")
+        l.rect = (x0, y0, x1, y1)
+        kept.append(l)
+    if not kept:
+        raise PdfRefused("no image on the page")
+    return PageLayers(width=W, height=H, layers=kept, rotate=rotate, media_box=box)
+
+
+def read_pages(data, strip_filters: bool = False, jpx: bool = False, layers: bool = False) -> List[Union[PageImage, PageLayers, PdfRefused]]:
     """One entry per page of the PDF in `data` (bytes, or anything with the buffer protocol: the records' streams are views into it):
     the page's image record, or the PdfRefused that says why the page is not a scanned page.  Raises PdfRefused for the whole file.
     strip_filters: also take /LZWDecode (/EarlyChange 1 or absent, /Predictor 1 or 2) and /RunLengthDecode images, which
     lumina_ocr_strip_image_decode decodes as one-strip pages (the provider asks for them with LUMINA_OCR_DEVICE_TIFF=1); without it
     they are refused as any other filter is.
     jpx: also take /JPXDecode images (JPEG 2000), which lumina_ocr_jp2_decode decodes (the provider asks for them with
-    LUMINA_OCR_DEVICE_JP2=1); without it they are refused as any other filter is."""
+    LUMINA_OCR_DEVICE_JP2=1); without it they are refused as any other filter is.
+    layers: also take pages painted from up to MAX_LAYERS images (strips, stencils, images with /SMask or a /Mask stream) and pages
+    with invisible text, as the module docstring lists them: such a page yields a PageLayers record for lumina_ocr_page_compose (the
+    provider asks for them with LUMINA_OCR_PDF_LAYERS=1); without it every answer is the one given before the option existed."""
     try:
         doc = _Document(data)
         out: List[Union[PageImage, PdfRefused]] = []
         for page, attrs in doc.pages():
             try:
-                out.append(_page_image(doc, page, attrs, strip_filters, jpx))
+                out.append(_page_layers(doc, page, attrs, strip_filters, jpx) if layers else _page_image(doc, page, attrs, strip_filters, jpx))
             except PdfRefused as e:
                 out.append(e)
         return out
