@@ -640,6 +640,38 @@ int lumina_ocr_ccitt_decode(lumina_ocr_t* h, const uint8_t* const* streams, cons
 int lumina_ocr_fax_decode(lumina_ocr_t* h, const uint8_t* const* streams, const size_t* sizes, int n, int rows, int columns,
                           const int32_t* params, uint8_t* out_dev, int* status, void* stream);
 
+/* JBIG2 (ITU-T T.88) page and mask streams of scanned PDFs, generic-region subset: PDF's /JBIG2Decode in the embedded organisation
+ * (no file header; the segments of the optional /JBIG2Globals stream come first).  The contract follows lumina_ocr_fax_decode and
+ * lumina_ocr_jp2_probe.
+ * Read: page information (type 48), immediate generic regions (38, 39) coded arithmetically with templates 0-3, adaptive template
+ * pixels anywhere T.88 allows (y in -128..0, x in -128..127, before the current pixel) and typical prediction, or coded as MMR (T.6
+ * lines, 1 = black, EOFB optional); end of stripe (50: with a page height of 0xFFFFFFFF the height is the last stripe's y + 1), end of
+ * page (49) and end of file (51), which end the reading; profiles (52) and extensions (62) are skipped.  Regions are combined onto
+ * the page in segment order, each with its operator (OR, AND, XOR, XNOR, REPLACE), clipped to the page, over the default pixel.
+ * -2 (valid, outside the subset), each with its reason: symbol dictionaries (0), text regions (4, 6, 7), pattern dictionaries (16),
+ * halftone regions (20, 22, 23), intermediate generic regions (36), refinement regions (40, 42, 43), code tables (53), a data length
+ * of 0xFFFFFFFF, EXTTEMPLATE, a region or page wider than 8192, more than 256 regions, a page association other than 0 or 1, a
+ * second page information segment, a stream of 2^28 bytes or more.  -1: a header or length past the stream, a region before the page
+ * information, a region that does not meet the page, an operator other than the page's where the page forbids overriding, reserved
+ * flag bits, an adaptive pixel that is not before the current pixel, a type T.88 does not define, an unknown height without an end of
+ * stripe, no page information, an MMR region the fax decoder refuses (lumina_ocr_ccitt_decode's list).
+ * The segment syntax is written from recollection of T.88 and pinned to the project's own test encoder; no other JBIG2 coder was at
+ * hand (README).  The arithmetic coder is pinned to the standard's test sequence (H.2), the MMR path to libtiff.
+ * lumina_ocr_jbig2_probe (host only, no handle): the segments; no pixel is decoded (so an MMR region's -1 shows only in the decode).
+ * globals may be null.  info = {width, height, regions, arithmetic regions, MMR regions, highest template, TPGDON anywhere, striped},
+ * filled as far as the segments were read.  Returns 0, -1 or -2.
+ * lumina_ocr_jbig2_reason: the reason behind the last non-zero lumina_ocr_jbig2_probe result of the calling thread when `code` is
+ * that result (a static string, for logs); otherwise the general meaning of `code`.
+ * lumina_ocr_jbig2_decode: streams / sizes and globals / globals_sizes are HOST arrays of n entries (globals, or any entry of it, may
+ * be null), every page height x width; params int32 [n][1] = {invert}; out_dev uint8 [n][height][width][3] with bit 1 -> 0 (black)
+ * and bit 0 -> 255, PDF's rule for /JBIG2Decode, swapped by invert (/Decode [1 0]); status HOST int [n]: 0 ok, -1, -2, -4 another
+ * size.  A page with a non-zero status is not written.  n == 0 does nothing.  Synchronises `stream`. */
+int lumina_ocr_jbig2_probe(const uint8_t* stream, size_t size, const uint8_t* globals, size_t globals_size, int info[8]);
+const char* lumina_ocr_jbig2_reason(int code);
+int lumina_ocr_jbig2_decode(lumina_ocr_t* h, const uint8_t* const* streams, const size_t* sizes, const uint8_t* const* globals,
+                            const size_t* globals_sizes, int n, int height, int width, const int32_t* params, uint8_t* out_dev, int* status,
+                            void* stream);
+
 /* Strip-coded page images — the strips of a scanned TIFF page (utils/tiff_pages.py finds them) and PDF's /LZWDecode and
  * /RunLengthDecode image streams (one strip a page).  The batch contract is lumina_ocr_flate_image_decode's: HOST pointers, n pages of
  * one size, out_dev uint8 [n][height][width][3], a HOST status per page (0: exact pixels, the bytes of Pillow's

@@ -23,6 +23,8 @@
 #include "jp2dec.h"
 #include "pngdec.h"
 #include "ccitt.h"
+#include "jbig2.h"
+#include "jbig2_parse.h"
 #include "stem_conv.h"
 #include "tables.h"
 
@@ -632,6 +634,49 @@ int lumina_ocr_fax_decode(lumina_ocr_t* h, const uint8_t* const* streams, const 
     BIND(h);
     API_TRY
     return fax_run(h, streams, sizes, n, rows, columns, params, out_dev, status, (hipStream_t)stream);
+    API_CATCH(h)
+}
+
+namespace {
+thread_local int jb2_last_code = 0;
+thread_local const char* jb2_last_reason = "";
+}  // namespace
+
+int lumina_ocr_jbig2_probe(const uint8_t* stream, size_t size, const uint8_t* globals, size_t globals_size, int info[8]) {
+    if (!stream || !info) return -1;
+    Jb2Page p;
+    int rc = -1;
+    try {
+        rc = jbig2_probe(stream, size, globals, globals ? globals_size : 0, &p);
+    } catch (const std::exception&) {   // (allocation failure: the page is left to the host)
+        p.reason = "out of memory while reading the segments";
+        rc = -2;
+    }
+    for (int i = 0; i < 8; ++i) info[i] = p.info[i];
+    jb2_last_code = rc; jb2_last_reason = p.reason ? p.reason : "";
+    return rc;
+}
+
+const char* lumina_ocr_jbig2_reason(int code) {
+    if (code != 0 && code == jb2_last_code && jb2_last_reason[0]) return jb2_last_reason;
+    switch (code) {
+        case 0: return "read";
+        case -1: return "corrupt or irregular JBIG2 stream";
+        case -2: return "valid JBIG2 outside the device subset";
+        case -4: return "another size than the batch";
+    }
+    return "unknown status";
+}
+
+int lumina_ocr_jbig2_decode(lumina_ocr_t* h, const uint8_t* const* streams, const size_t* sizes, const uint8_t* const* globals,
+                            const size_t* globals_sizes, int n, int height, int width, const int32_t* params, uint8_t* out_dev, int* status,
+                            void* stream) {
+    if (h && n == 0) return 0;
+    if (!h || !streams || !sizes || !params || !out_dev || !status || n < 0 || height <= 0 || width <= 0 || (globals && !globals_sizes))
+        return locr_fail(h, "jbig2_decode", "bad arguments");
+    BIND(h);
+    API_TRY
+    return jbig2_run(h, streams, sizes, globals, globals_sizes, n, height, width, params, out_dev, status, (hipStream_t)stream);
     API_CATCH(h)
 }
 

@@ -89,6 +89,9 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_flate_image_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
         "lumina_ocr_ccitt_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
         "lumina_ocr_fax_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "lumina_ocr_jbig2_probe": (i32, [vp, sz, vp, sz, vp]),
+        "lumina_ocr_jbig2_reason": (c.c_char_p, [i32]),
+        "lumina_ocr_jbig2_decode": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
         "lumina_ocr_strip_image_decode": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
         "lumina_ocr_load_svtr_weights": (i32, [vp, vp, sz]),
         "lumina_ocr_svtr_forward": (i32, [vp, vp, vp, i32, vp, vp, vp]),
@@ -146,6 +149,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_jp2_probe", "lumina_ocr_jp2_reason", "lumina_ocr_jp2_decode",
     "lumina_ocr_jp2_probe_irreversible", "lumina_ocr_jp2_decode_irreversible",
     "lumina_ocr_png_probe", "lumina_ocr_png_decode", "lumina_ocr_flate_image_decode", "lumina_ocr_ccitt_decode", "lumina_ocr_fax_decode", "lumina_ocr_strip_image_decode",
+    "lumina_ocr_jbig2_probe", "lumina_ocr_jbig2_reason", "lumina_ocr_jbig2_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
     "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks", "lumina_ocr_selection_marks_round",
     "lumina_ocr_rules_and_marks_round", "lumina_ocr_barcodes", "lumina_ocr_barcodes_kinds", "lumina_ocr_qrcodes", "lumina_ocr_qrcodes_versions", "lumina_ocr_datamatrix", "lumina_ocr_aztec", "lumina_ocr_aztec_workspace_bytes", "lumina_ocr_aztec_layers", "lumina_ocr_aztec_layers_workspace_bytes",
@@ -396,6 +400,33 @@ class Engine:
         flat = (ctypes.c_int32 * (5 * n))(*[int(v) for p in params for v in p])
         assert len(flat) == 5 * n
         self._chk(self.lib.lumina_ocr_fax_decode(self._h, ptrs, sizes, n, int(rows), int(columns), flat, _ptr(out), status, self._stream()))
+        return out, list(status)
+
+    @staticmethod
+    def jbig2_probe(data: bytes, globals_data: bytes = None):
+        """Host only: the segments of one page's /JBIG2Decode stream behind those of its /JBIG2Globals stream (or None); no pixel is
+        decoded. -> (rc, dict(width, height, regions, arithmetic_regions, mmr_regions, highest_template, tpgdon, striped, reason)); rc 0:
+        the device decodes this page (generic regions), -2: valid JBIG2 outside the subset (symbol dictionaries, text, halftone and
+        refinement regions ...), -1: corrupt or irregular.  reason: why a non-zero rc was given, for logs."""
+        lib = load_library()
+        info = (ctypes.c_int * 8)()
+        data = data if isinstance(data, bytes) else bytes(data)
+        g = None if globals_data is None else (globals_data if isinstance(globals_data, bytes) else bytes(globals_data))
+        rc = lib.lumina_ocr_jbig2_probe(ctypes.c_char_p(data), len(data), ctypes.c_char_p(g), len(g) if g else 0, info)
+        return rc, dict(width=info[0], height=info[1], regions=info[2], arithmetic_regions=info[3], mmr_regions=info[4], highest_template=info[5],
+                        tpgdon=info[6], striped=info[7], reason=lib.lumina_ocr_jbig2_reason(rc).decode() if rc else "")
+
+    def jbig2_decode(self, streams, height: int, width: int, globals_list=None, invert=None, out=None):
+        """/JBIG2Decode page or mask streams (all height x width) -> (uint8 [n,H,W,3] device, status list).  globals_list: per stream its
+        /JBIG2Globals bytes or None; invert: per stream 0 | 1 (/Decode [1 0]; default 0: bit 1 is black).  status 0: exact pixels, -1
+        corrupt, -2 outside the generic-region subset, -4 another size; a page with a non-zero status is not written."""
+        n, out, streams, ptrs, sizes, status = self._stream_batch(streams, height, width, out)   # (n == 0: the call does nothing)
+        keep = [None] * n if globals_list is None else [None if g is None else (g if isinstance(g, bytes) else bytes(g)) for g in globals_list]
+        assert len(keep) == n
+        gptrs = (ctypes.c_char_p * n)(*keep)
+        gsizes = (ctypes.c_size_t * n)(*[len(g) if g else 0 for g in keep])
+        flat = (ctypes.c_int32 * n)(*[int(v) for v in (invert if invert is not None else [0] * n)])
+        self._chk(self.lib.lumina_ocr_jbig2_decode(self._h, ptrs, sizes, gptrs, gsizes, n, int(height), int(width), flat, _ptr(out), status, self._stream()))
         return out, list(status)
 
     def strip_image_decode(self, pages, height: int, width: int, rows_per_strip: int, params, palettes=None, out=None):

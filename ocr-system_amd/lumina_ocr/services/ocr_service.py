@@ -135,6 +135,11 @@ class OCRService:
         # their layers join the decode groups and lumina_ocr_page_compose puts them together.  Off by default: exactly the calls made
         # without the option are made.
         self.pdf_layers = os.environ.get("LUMINA_OCR_PDF_LAYERS", "0").lower() not in ("", "0", "false", "no")
+        # LUMINA_OCR_PDF_JBIG2=1 (with LUMINA_OCR_PDF_SCANS=1; ignored without it): /JBIG2Decode page images, and with
+        # LUMINA_OCR_PDF_LAYERS the JBIG2 stencils and masks of layered pages, are decoded on the device where they are made of generic
+        # regions (lumina_ocr_jbig2_decode); a symbol-coded or damaged stream goes where a refused page goes.  Off by default: exactly
+        # the calls made without the option are made.
+        self.pdf_jbig2 = os.environ.get("LUMINA_OCR_PDF_JBIG2", "0").lower() not in ("", "0", "false", "no")
         # LUMINA_OCR_DEVICE_TIFF=1: stripped TIFF inputs (LZW, PackBits, Deflate, Group 4, Group 3, CCITT RLE, uncompressed; utils/tiff_pages.py) are decoded on
         # the device, process_tiff_sync reads every page of a multi-page TIFF, and process_document sends "tiff" and "tif" there.  Off by
         # default: a TIFF is then decoded by Pillow, first frame only, and every output is exactly the one without the option.
@@ -862,6 +867,8 @@ class OCRService:
                         out, status = decode(streams, h, w) if self.device_jpeg else (None, [-2] * len(idxs))
                     elif filt == "JPXDecode":   # (only with LUMINA_OCR_DEVICE_JP2: read_pages returns none otherwise)
                         out, status = self._jp2_decoder()(streams, h, w)
+                    elif filt == "JBIG2Decode":   # (only with LUMINA_OCR_PDF_JBIG2: read_pages returns none otherwise)
+                        out, status = eng.jbig2_decode(streams, h, w, [r.params["globals"] for r in recs], [int(r.params["invert"]) for r in recs])
                     elif filt in ("LZWDecode", "RunLengthDecode"):   # one-strip pages of the strip decoders
                         codec = 5 if filt == "LZWDecode" else 32773
                         params = [(codec, r.params["predictor"], r.params["components"], r.params["bits"], int(r.params["indexed"]),
@@ -921,7 +928,7 @@ class OCRService:
             data = Path(pdf_path).read_bytes()
             try:
                 entries = pdf_pages.read_pages(data, strip_filters=self.device_tiff, **({"jpx": True} if self.device_jp2 else {}),
-                                               **({"layers": True} if self.pdf_layers else {}))
+                                               **({"layers": True} if self.pdf_layers else {}), **({"jbig2": True} if self.pdf_jbig2 else {}))
             except pdf_pages.PdfRefused as e:   # not a file the reader takes: the rasterise-and-batch path, whole
                 r = self.process_pdf_as_images_sync(pdf_path)
                 if not r.success and r.error and not r.pages:
@@ -1141,7 +1148,7 @@ class OCRService:
     # ---- status (:759-795) ----
     def get_status(self) -> Dict[str, Any]:
         st = {"client_initialized": self._pipeline is not None, "model_id": "dbnet-r18vd+crnn-mv3", "max_dimension": self.max_dimension,
-              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "aztec": self._use_aztec, "aztec_max_layers": self._aztec_max_layers_status(), "device_pdf": self.device_pdf, "pdf_layers": self.pdf_layers, "progressive_jpeg": self.progressive_jpeg, "device_tiff": self.device_tiff, "device_jp2": self.device_jp2, "jp2_irreversible": self.jp2_irreversible, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
+              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "aztec": self._use_aztec, "aztec_max_layers": self._aztec_max_layers_status(), "device_pdf": self.device_pdf, "pdf_layers": self.pdf_layers, "pdf_jbig2": self.pdf_jbig2, "progressive_jpeg": self.progressive_jpeg, "device_tiff": self.device_tiff, "device_jp2": self.device_jp2, "jp2_irreversible": self.jp2_irreversible, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
         if self._engine is not None:
             st["engine_version"] = self._engine.version()
             st["num_classes"] = self._engine.num_classes

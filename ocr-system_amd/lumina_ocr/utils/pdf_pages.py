@@ -46,7 +46,11 @@ own size counts, the size of an /SMask or /Mask does not): sx = max w / a, sy = 
 H = R((Y1 - Y0) sy), and the layer's rectangle is x0 = R((e - X0) sx), x1 = R((e + a - X0) sx), y0 = R((Y1 - f - d) sy),
 y1 = R((Y1 - f) sy), all in double precision on the host.  W or H above 65535, or W H above MAX_CANVAS_PIXELS (2^26: A4 at 600 dpi is
 34.8 M), is refused; a rectangle may stick out of the canvas; one that is empty or misses the canvas is dropped.
-Not read (the page is refused and goes to the rasteriser): JBIG2 masks, rotated or flipped placements, clipped strips (re W n), white
+JBIG2 (read_pages(..., jbig2=True); the provider asks with LUMINA_OCR_PDF_JBIG2=1): /JBIG2Decode images of one bit, DeviceGray or an
+/ImageMask, /Decode absent, [0 1] or [1 0], with /DecodeParms << /JBIG2Globals stream >> resolved and handed over as bytes: as the one
+image of a page and, with layers, as a stencil, a /Mask stream or a 1-bit /SMask.  Whether the stream is inside the decoder's subset
+(generic regions; symbol-coded text is not) is the decoder's own parser's business: lumina_ocr_jbig2_probe / _decode answer -2 there.
+Not read (the page is refused and goes to the rasteriser): JBIG2 without that option, rotated or flipped placements, clipped strips (re W n), white
 re f underlays, form XObjects, CMYK fill, /Matte, colour-key masks, blend modes and constant alpha.  /Interpolate true is sampled as
 false: every layer is shown by the sample that holds the pixel centre.
 
@@ -69,6 +73,7 @@ EDGE_TOLERANCE = 0.01        # each image edge within this fraction of the Media
 FILTERS = ("DCTDecode", "FlateDecode", "CCITTFaxDecode")
 STRIP_FILTERS = ("LZWDecode", "RunLengthDecode")   # taken only when read_pages is asked to (strip_filters=True)
 JPX_FILTER = "JPXDecode"                            # taken only when read_pages is asked to (jpx=True)
+JBIG2_FILTER = "JBIG2Decode"                        # taken only when read_pages is asked to (jbig2=True)
 MAX_LAYERS = 64                      # images painted on one page (read_pages with layers=True)
 MAX_CANVAS_PIXELS = 1 << 26          # canvas of a layered page: A4 at 600 dpi is 4960 x 7016 = 34.8 M samples
 MAX_COORD = 1 << 24                  # |coordinate| of a layer rectangle on the canvas grid
@@ -103,11 +108,12 @@ class Stream(dict):
 
 @dataclass
 class PageImage:
-    filter: str                     # "DCTDecode" | "FlateDecode" | "CCITTFaxDecode" | "LZWDecode" | "RunLengthDecode" | "JPXDecode"
+    filter: str                     # "DCTDecode" | "FlateDecode" | "CCITTFaxDecode" | "LZWDecode" | "RunLengthDecode" | "JPXDecode" | "JBIG2Decode"
     stream: memoryview              # the image's raw stream, a view into the file
     params: Dict[str, Any]          # FlateDecode, LZWDecode, RunLengthDecode: predictor, components, bits, indexed, invert, palette
     #                                 (768 bytes RGB or None); predictor is 1 | 2 for LZWDecode and 1 for RunLengthDecode
     #                                 CCITTFaxDecode: K, EncodedByteAlign, BlackIs1, invert;  DCTDecode, JPXDecode: components
+    #                                 JBIG2Decode: globals (the /JBIG2Globals stream's bytes or None), invert
     width: int
     height: int
     rotate: int                     # /Rotate, 0 / 90 / 180 / 270 (clockwise, when displayed)
@@ -765,6 +771,20 @@ def _jpx_page_image(doc: _Document, img: Stream, width: int, height: int, rotate
     return PageImage(filter=JPX_FILTER, stream=img.raw, params={"components": comps}, width=w, height=h, rotate=rotate, media_box=media_box)
 
 
+def _jbig2_page_image(doc: _Document, img: Stream, parms: Dict[str, Any], width: int, height: int, rotate: int, media_box) -> PageImage:
+    """the record of a /JBIG2Decode image: one bit of DeviceGray, /Decode absent, [0 1] or [1 0]; /JBIG2Globals (resolved by
+    single_filter through the visited-set of every reference) is a stream whose bytes go in front of the image's"""
+    bits = doc.resolve(img.get("BitsPerComponent", 1))
+    cs = doc.resolve(img.get("ColorSpace"))
+    if bits != 1 or cs != "DeviceGray":
+        raise PdfRefused("JBIG2 image that is not one bit of grey")
+    g = parms.get("JBIG2Globals")
+    if g is not None and not isinstance(g, Stream):
+        raise PdfRefused("/JBIG2Globals is not a stream")
+    return PageImage(filter=JBIG2_FILTER, stream=img.raw, params={"globals": None if g is None else doc._decode_meta(g), "invert": bool(_mask_decode(doc, img))},
+                     width=width, height=height, rotate=rotate, media_box=media_box)
+
+
 def _page_frame(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any]):
     """-> ((x0, y0, x1, y1) of the MediaBox, /Rotate, the page's content bytes)"""
     box = doc.resolve(attrs.get("MediaBox"))
@@ -807,7 +827,8 @@ def _xobject_image(doc: _Document, attrs: Dict[str, Any], name: str) -> Stream:
     return img
 
 
-def _page_image(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], strip_filters: bool = False, jpx: bool = False) -> PageImage:
+def _page_image(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], strip_filters: bool = False, jpx: bool = False,
+                jbig2: bool = False) -> PageImage:
     (x0, y0, x1, y1), rotate, content = _page_frame(doc, page, attrs)
     bw, bh = x1 - x0, y1 - y0
     name, m = _content_image(content)
@@ -819,14 +840,18 @@ def _page_image(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], str
         raise PdfRefused("image does not cover the MediaBox")
     img = _xobject_image(doc, attrs, name)
     if doc.resolve(img.get("ImageMask")) is True:
-        raise PdfRefused("/ImageMask")
+        # a JBIG2 stencil alone on the page: painted in the fill colour no operator of this subset can change (black) on the white page,
+        # which is the picture of the same samples as DeviceGray
+        if not (jbig2 and doc.single_filter(img)[0] == JBIG2_FILTER):
+            raise PdfRefused("/ImageMask")
+        img = _without(img, ("ImageMask", "ColorSpace", "SMaskInData"), ColorSpace=Name("DeviceGray"), BitsPerComponent=doc.resolve(img.get("BitsPerComponent", 1)))
     for key in ("SMask", "Mask"):
         if doc.resolve(img.get(key)) is not None:
             raise PdfRefused("/" + key)
-    return _image_record(doc, img, rotate, (x0, y0, x1, y1), strip_filters, jpx)
+    return _image_record(doc, img, rotate, (x0, y0, x1, y1), strip_filters, jpx, jbig2)
 
 
-def _image_record(doc: _Document, img: Stream, rotate: int, media_box, strip_filters: bool, jpx: bool) -> PageImage:
+def _image_record(doc: _Document, img: Stream, rotate: int, media_box, strip_filters: bool, jpx: bool, jbig2: bool = False) -> PageImage:
     """the record of one opaque image XObject (its mask keys are the caller's business)"""
     x0, y0, x1, y1 = media_box
     width, height = doc.resolve(img.get("Width")), doc.resolve(img.get("Height"))
@@ -835,6 +860,8 @@ def _image_record(doc: _Document, img: Stream, rotate: int, media_box, strip_fil
     filt, parms = doc.single_filter(img)
     if jpx and filt == JPX_FILTER:
         return _jpx_page_image(doc, img, width, height, rotate, (x0, y0, x1, y1))
+    if jbig2 and filt == JBIG2_FILTER:
+        return _jbig2_page_image(doc, img, parms, width, height, rotate, (x0, y0, x1, y1))
     if filt not in FILTERS and not (strip_filters and filt in STRIP_FILTERS):
         raise PdfRefused("image filter %s" % filt)
     bits = doc.resolve(img.get("BitsPerComponent", 1 if filt == "CCITTFaxDecode" else None))
@@ -1054,8 +1081,8 @@ def _without(stm: Stream, drop, **add) -> Stream:
     return s
 
 
-def _stencil_record(doc: _Document, stm: Stream, rotate: int, media_box, strip_filters: bool) -> Tuple[PageImage, int]:
-    """(record, flip) of an /ImageMask image: one bit a sample, Flate or CCITT (LZW / RunLength under strip_filters)"""
+def _stencil_record(doc: _Document, stm: Stream, rotate: int, media_box, strip_filters: bool, jbig2: bool = False) -> Tuple[PageImage, int]:
+    """(record, flip) of an /ImageMask image: one bit a sample, Flate or CCITT (LZW / RunLength under strip_filters, JBIG2 under jbig2)"""
     for key in ("SMask", "Mask"):
         if doc.resolve(stm.get(key)) is not None:
             raise PdfRefused("/%s on a stencil" % key)
@@ -1063,16 +1090,16 @@ def _stencil_record(doc: _Document, stm: Stream, rotate: int, media_box, strip_f
     if bits != 1:
         raise PdfRefused("stencil with %r bits per component" % (bits,))
     filt, _ = doc.single_filter(stm)
-    if filt not in ("FlateDecode", "CCITTFaxDecode") and not (strip_filters and filt in STRIP_FILTERS):
+    if filt not in ("FlateDecode", "CCITTFaxDecode") and not (strip_filters and filt in STRIP_FILTERS) and not (jbig2 and filt == JBIG2_FILTER):
         raise PdfRefused("stencil filter %s" % filt)
     flip = _mask_decode(doc, stm)
     rec = _image_record(doc, _without(stm, ("Decode", "ImageMask", "ColorSpace", "SMaskInData"), ColorSpace=Name("DeviceGray"), BitsPerComponent=1),
-                        rotate, media_box, strip_filters, False)
+                        rotate, media_box, strip_filters, False, jbig2)
     return rec, flip
 
 
-def _soft_mask_record(doc: _Document, stm, rotate: int, media_box, jpx: bool) -> Tuple[PageImage, int]:
-    """(record, flip) of an /SMask image: DeviceGray, 1 or 8 bits, Flate, CCITT, grey DCT (grey JPX with jpx), no /Matte"""
+def _soft_mask_record(doc: _Document, stm, rotate: int, media_box, jpx: bool, jbig2: bool = False) -> Tuple[PageImage, int]:
+    """(record, flip) of an /SMask image: DeviceGray, 1 or 8 bits, Flate, CCITT, grey DCT (grey JPX with jpx, JBIG2 with jbig2), no /Matte"""
     if not isinstance(stm, Stream) or doc.resolve(stm.get("Subtype")) != "Image":
         raise PdfRefused("/SMask is not an image")
     if doc.resolve(stm.get("Matte")) is not None:
@@ -1081,39 +1108,39 @@ def _soft_mask_record(doc: _Document, stm, rotate: int, media_box, jpx: bool) ->
         if doc.resolve(stm.get(key)) is not None:
             raise PdfRefused("/%s on a mask" % key)
     filt, _ = doc.single_filter(stm)
-    if filt not in ("FlateDecode", "CCITTFaxDecode", "DCTDecode") and not (jpx and filt == JPX_FILTER):
+    if filt not in ("FlateDecode", "CCITTFaxDecode", "DCTDecode") and not (jpx and filt == JPX_FILTER) and not (jbig2 and filt == JBIG2_FILTER):
         raise PdfRefused("/SMask filter %s" % filt)
     cs = doc.resolve(stm.get("ColorSpace"))
     if cs != "DeviceGray" and not (filt == JPX_FILTER and cs is None):
         raise PdfRefused("/SMask colour space %s" % (cs if isinstance(cs, Name) else "is not a name"))
     flip = _mask_decode(doc, stm)
-    rec = _image_record(doc, _without(stm, ("Decode",)), rotate, media_box, False, jpx)
-    bits = rec.params.get("bits", 1 if filt == "CCITTFaxDecode" else 8)
+    rec = _image_record(doc, _without(stm, ("Decode",)), rotate, media_box, False, jpx, jbig2)
+    bits = rec.params.get("bits", 1 if filt in ("CCITTFaxDecode", JBIG2_FILTER) else 8)
     if rec.params.get("components", 1) != 1 or bits not in (1, 8):
         raise PdfRefused("/SMask with %r components of %r bits" % (rec.params.get("components", 1), bits))
     return rec, flip
 
 
-def _layer(doc: _Document, img: Stream, rect, fill, rotate: int, media_box, strip_filters: bool, jpx: bool) -> Layer:
+def _layer(doc: _Document, img: Stream, rect, fill, rotate: int, media_box, strip_filters: bool, jpx: bool, jbig2: bool = False) -> Layer:
     if doc.resolve(img.get("ImageMask")) is True:
-        rec, flip = _stencil_record(doc, img, rotate, media_box, strip_filters)
+        rec, flip = _stencil_record(doc, img, rotate, media_box, strip_filters, jbig2)
         return Layer(kind=1, rect=rect, fill=fill, flip=flip, image=None, mask=rec)
     smask, mask = doc.resolve(img.get("SMask")), doc.resolve(img.get("Mask"))
     sid = doc.resolve(img.get("SMaskInData", 0))
     if sid != 0:
         raise PdfRefused("/SMaskInData %r" % (sid,))
-    base = _image_record(doc, img, rotate, media_box, strip_filters, jpx)
+    base = _image_record(doc, img, rotate, media_box, strip_filters, jpx, jbig2)
     if smask is not None and mask is not None:
         raise PdfRefused("/SMask and /Mask on one image")
     if smask is not None:
-        rec, flip = _soft_mask_record(doc, smask, rotate, media_box, jpx)
+        rec, flip = _soft_mask_record(doc, smask, rotate, media_box, jpx, jbig2)
         return Layer(kind=2, rect=rect, fill=fill, flip=flip, image=base, mask=rec)
     if mask is not None:
         if isinstance(mask, list):
             raise PdfRefused("colour-key /Mask")
         if not isinstance(mask, Stream) or doc.resolve(mask.get("Subtype")) != "Image" or doc.resolve(mask.get("ImageMask")) is not True:
             raise PdfRefused("/Mask is not an /ImageMask image")
-        rec, flip = _stencil_record(doc, mask, rotate, media_box, strip_filters)
+        rec, flip = _stencil_record(doc, mask, rotate, media_box, strip_filters, jbig2)
         return Layer(kind=3, rect=rect, fill=fill, flip=flip, image=base, mask=rec)
     return Layer(kind=0, rect=rect, fill=fill, flip=0, image=base, mask=None)
 
@@ -1122,7 +1149,8 @@ def _round(v: float) -> int:
     return int(math.floor(v + 0.5))
 
 
-def _page_layers(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], strip_filters: bool, jpx: bool) -> Union[PageImage, PageLayers]:
+def _page_layers(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], strip_filters: bool, jpx: bool,
+                 jbig2: bool = False) -> Union[PageImage, PageLayers]:
     (X0, Y0, X1, Y1), rotate, content = _page_frame(doc, page, attrs)
     bw, bh = X1 - X0, Y1 - Y0
     placed = []
@@ -1136,7 +1164,7 @@ def _page_layers(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], st
     if abs(hx0 - X0) > EDGE_TOLERANCE * bw or abs(hx1 - X1) > EDGE_TOLERANCE * bw or abs(hy0 - Y0) > EDGE_TOLERANCE * bh or abs(hy1 - Y1) > EDGE_TOLERANCE * bh:
         raise PdfRefused("image does not cover the MediaBox" if len(placed) == 1 else "the images do not cover the MediaBox")
     box = (X0, Y0, X1, Y1)
-    layers = [_layer(doc, _xobject_image(doc, attrs, name), None, fill, rotate, box, strip_filters, jpx) for name, _, _, _, _, fill in placed]
+    layers = [_layer(doc, _xobject_image(doc, attrs, name), None, fill, rotate, box, strip_filters, jpx, jbig2) for name, _, _, _, _, fill in placed]
     if len(layers) == 1 and layers[0].kind == 0:
         return layers[0].image   # one opaque image over the whole box: today's record
     # the canvas: the MediaBox at the finest sample grid among the layers (a stencil's own size counts, a mask's does not)
@@ -1163,7 +1191,8 @@ def _page_layers(doc: _Document, page: Dict[str, Any], attrs: Dict[str, Any], st
     return PageLayers(width=W, height=H, layers=kept, rotate=rotate, media_box=box)
 
 
-def read_pages(data, strip_filters: bool = False, jpx: bool = False, layers: bool = False) -> List[Union[PageImage, PageLayers, PdfRefused]]:
+def read_pages(data, strip_filters: bool = False, jpx: bool = False, layers: bool = False,
+               jbig2: bool = False) -> List[Union[PageImage, PageLayers, PdfRefused]]:
     """One entry per page of the PDF in `data` (bytes, or anything with the buffer protocol: the records' streams are views into it):
     the page's image record, or the PdfRefused that says why the page is not a scanned page.  Raises PdfRefused for the whole file.
     strip_filters: also take /LZWDecode (/EarlyChange 1 or absent, /Predictor 1 or 2) and /RunLengthDecode images, which
@@ -1173,13 +1202,17 @@ def read_pages(data, strip_filters: bool = False, jpx: bool = False, layers: boo
     LUMINA_OCR_DEVICE_JP2=1); without it they are refused as any other filter is.
     layers: also take pages painted from up to MAX_LAYERS images (strips, stencils, images with /SMask or a /Mask stream) and pages
     with invisible text, as the module docstring lists them: such a page yields a PageLayers record for lumina_ocr_page_compose (the
-    provider asks for them with LUMINA_OCR_PDF_LAYERS=1); without it every answer is the one given before the option existed."""
+    provider asks for them with LUMINA_OCR_PDF_LAYERS=1); without it every answer is the one given before the option existed.
+    jbig2: also take /JBIG2Decode images (one bit of DeviceGray or an /ImageMask, /Decode [0 1] or [1 0], /JBIG2Globals resolved), which
+    lumina_ocr_jbig2_decode decodes where they are made of generic regions: as the one image of a page and, with layers, as a stencil,
+    a /Mask stream or a 1-bit /SMask (the provider asks for them with LUMINA_OCR_PDF_JBIG2=1); without it every answer and reason is the
+    one given before the option existed."""
     try:
         doc = _Document(data)
         out: List[Union[PageImage, PdfRefused]] = []
         for page, attrs in doc.pages():
             try:
-                out.append(_page_layers(doc, page, attrs, strip_filters, jpx) if layers else _page_image(doc, page, attrs, strip_filters, jpx))
+                out.append(_page_layers(doc, page, attrs, strip_filters, jpx, jbig2) if layers else _page_image(doc, page, attrs, strip_filters, jpx, jbig2))
             except PdfRefused as e:
                 out.append(e)
         return out
