@@ -92,7 +92,7 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) void conv_ring_kernel(c
     };
 
     // multi-source input: source k supplies xs_nchunk[k] consecutive chunks, stored at 1 / 2^shift of the resolution, pixels xs_cstride[k] apart
-    const int nsrc = p.n_src > 1 ? p.n_src : 1;
+    const int nsrc = POOL ? 1 : (p.n_src > 1 ? p.n_src : 1);   // (conv_ring_supported admits the fused pool with one source only: its instantiation carries no multi-source code)
     // (selected with constant indices: indexing the kernel argument with a run-time `src` makes hipcc copy the struct to scratch,
     // and scratch loads queue with the LDS-DMA on the vector-memory counter)
     auto src_shift = [&](int src) { return src == 0 ? p.xs_shift[0] : (src == 1 ? p.xs_shift[1] : (src == 2 ? p.xs_shift[2] : p.xs_shift[3])); };
@@ -110,9 +110,30 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) void conv_ring_kernel(c
         const unsigned e = (unsigned)hy | ((unsigned)hx << 6) | ((unsigned)(i & 1) << 12) | ((unsigned)(i < R_A_ITEMS) << 13);
         if (it & 1) a_item[it >> 1] |= e << 16; else a_item[it >> 1] = e;
     }
+    // POOL (one source, lanes along the image rows): a tile whose halo lies inside the map — 89 % of an A4 page's — needs no bounds
+    // test per piece, and its pieces sit at offsets from the halo's first pixel that are the same for every tile: five registers
+    // kept across the loop, one add per piece and tile.  (The padding pieces of the last round re-read the halo's first piece:
+    // they land behind the halo tile, where no fragment read looks.)
+    int a_koff[POOL ? R_AIT : 1];
+    if constexpr (POOL) {
+#pragma unroll
+        for (int it = 0; it < R_AIT; ++it) {
+            const int i = tid + NTHR * it, pi = i >> 1, hy = pi / R_HW, hx = pi - hy * R_HW, cs = (i & 1) ^ ((hx >> 3) & 1);
+            a_koff[it] = i < R_A_ITEMS ? (hy * p.W + hx) * (p.x_blk ? 16 : p.Cin) + cs * 8 : 0;
+        }
+    }
     // ... and their global offsets for the tile / source being requested
     int a_goff[R_AIT];
     auto describe = [&](const RingTile& t, int src) {
+        if constexpr (POOL) {
+            const int hy0 = t.oyb - 1, hx0 = t.oxb - 1;
+            if (hy0 >= 0 && hx0 >= 0 && hy0 + R_TH + 2 <= LH && hx0 + R_HW <= LW && !(PROF && (p.dbg_skip & 8))) {   // uniform
+                const int tb = (hy0 * p.W + hx0) * (p.x_blk ? 16 : p.Cin);
+#pragma unroll
+                for (int it = 0; it < R_AIT; ++it) a_goff[it] = a_koff[it] + tb;
+                return;
+            }
+        }
         const int sh = nsrc > 1 ? src_shift(src) : 0, cin_s = nsrc > 1 ? src_cstride(src) : p.Cin, ws = p.W >> sh;
 #pragma unroll
         for (int j = 0; j < (R_AIT + 1) / 2; ++j) asm volatile("" : "+v"(a_item[j]));   // opaque: the unpacking below stays inside the tile loop
@@ -288,6 +309,17 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) void conv_ring_kernel(c
             for (int nt = 0; nt < R_NT; ++nt)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
+                    // (POOL: read with the fragments' type — in front of a float4 read of LDS hipcc waits for every LDS-DMA request in
+                    // flight, i.e. for chunk 0 of the next tile, before the epilogue's first instruction)
+                    if constexpr (POOL) {
+                        typedef float f32x4_t __attribute__((ext_vector_type(4)));
+                        const f32x4_t b4 = __builtin_bit_cast(f32x4_t, ring_frag(reinterpret_cast<const unsigned char*>(bsrc + nt * 32 + 8 * g)));
+                        typedef float f32x2_t __attribute__((ext_vector_type(2)));   // (two-element adds spelled out: v_pk_add_f32)
+                        const f32x2_t lo = f32x2_t{acc[mt][nt][4 * g + 0], acc[mt][nt][4 * g + 1]} + f32x2_t{b4[0], b4[1]};
+                        const f32x2_t hi = f32x2_t{acc[mt][nt][4 * g + 2], acc[mt][nt][4 * g + 3]} + f32x2_t{b4[2], b4[3]};
+                        acc[mt][nt][4 * g + 0] = lo[0]; acc[mt][nt][4 * g + 1] = lo[1]; acc[mt][nt][4 * g + 2] = hi[0]; acc[mt][nt][4 * g + 3] = hi[1];
+                        continue;
+                    }
                     const float4 b4 = *reinterpret_cast<const float4*>(bsrc + nt * 32 + 8 * g);
                     acc[mt][nt][4 * g + 0] += b4.x; acc[mt][nt][4 * g + 1] += b4.y; acc[mt][nt][4 * g + 2] += b4.z; acc[mt][nt][4 * g + 3] += b4.w;
                 }
@@ -310,7 +342,7 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) void conv_ring_kernel(c
                             v0 += __uint_as_float(rq[gq][0] << 16); v1 += __uint_as_float(rq[gq][0] & 0xFFFF0000u);
                             v2 += __uint_as_float(rq[gq][1] << 16); v3 += __uint_as_float(rq[gq][1] & 0xFFFF0000u);
                         }
-                        if (p.act == ACT_RELU) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
+                        if (!POOL && p.act == ACT_RELU) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
                         acc[mt][nt][4 * g + 0] = v0; acc[mt][nt][4 * g + 1] = v1; acc[mt][nt][4 * g + 2] = v2; acc[mt][nt][4 * g + 3] = v3;
                     }
                 }
@@ -326,45 +358,60 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) void conv_ring_kernel(c
                     const auto sx2 = __builtin_amdgcn_permlane32_swap(q0x, q1x, false, false);
                     const auto sy2 = __builtin_amdgcn_permlane32_swap(q0y, q1y, false, false);
                     pk[mt][nt][gp] = make_uint4(sx2[0], sy2[0], sx2[1], sy2[1]);
-                    if constexpr (POOL) {   // conv pixels outside the map are pool padding: ReLU output is >= 0, so 0 is neutral
-                        const int oy = cur.oyb + wave * R_MT + mt;
-                        const uint32_t keep = (oy >= 0 && oy < LH && ox >= 0 && ox < LW) ? 0xffffffffu : 0u;
-                        pk[mt][nt][gp].x &= keep; pk[mt][nt][gp].y &= keep; pk[mt][nt][gp].z &= keep; pk[mt][nt][gp].w &= keep;
-                    }
                 }
             __builtin_amdgcn_sched_barrier(0);
         }
         if constexpr (POOL) {
-            // 3x3/s2 max pool on the packed bf16 values.  After ReLU they are >= +0, where bf16 bit patterns order like signed
-            // 16-bit integers: v_pk_max_i16 is the float max.  Vertical: wave w owns conv rows 4w..4w+3 -> pooled row 2w is local
-            // (rows 0,1,2), pooled row 2w+1 needs row 0 of wave w+1, handed over through the ring slot that was just consumed
-            // (two barriers: its readers are done / the rows are there).  Horizontal: even lane r takes lanes r, r+1, r+2.
+            // 3x3/s2 max pool on the packed bf16 values, ReLU (the only activation conv_ring_supported admits here) ONCE, on the
+            // pooled values: relu(max) = max(relu).  Non-negative bf16 patterns order like signed 16-bit integers and every negative
+            // pattern (-0 included) is below every non-negative one, so v_pk_max_i16 over raw values finds the float max of a
+            // window that has any value >= +0, a negative pattern otherwise, and the final v_pk_max_i16(x, 0) makes that +0 as
+            // ReLU-then-pool did.  (A NaN cannot arise from u8 pages and finite weights; one with the sign bit clear would win its
+            // window like a large positive value, one with the sign bit set would read as negative and become +0.)
+            // Conv pixels outside the map are pool padding: zeroed, which cannot change relu(max) — only in tiles that reach
+            // past the map's border (one uniform test per tile).
+            // Vertical: wave w owns conv rows 4w..4w+3 -> pooled row 2w is local (rows 0,1,2), pooled row 2w+1 needs row 0 of wave
+            // w+1, handed over through the ring slot that was just consumed (two barriers: its readers are done / the rows are
+            // there).  Horizontal: pooled column q = lanes 2q, 2q+1, 2q+2 of a half-wave, fetched with two DPP wave shifts
+            // (register moves, no LDS instruction; lane 31 / 63 receive the other half's / no value: they hold no stored column).
+            if (cur.oyb < 0 || cur.oxb < 0 || cur.oyb + R_TH > LH || cur.oxb + R_TW > LW) {
+#pragma unroll
+                for (int mt = 0; mt < R_MT; ++mt) {
+                    const int oy = cur.oyb + wave * R_MT + mt;
+                    const uint32_t keep = (oy >= 0 && oy < LH && ox >= 0 && ox < LW) ? 0xffffffffu : 0u;
+#pragma unroll
+                    for (int nt = 0; nt < R_NT; ++nt)
+#pragma unroll
+                        for (int gp = 0; gp < 2; ++gp) { pk[mt][nt][gp].x &= keep; pk[mt][nt][gp].y &= keep; pk[mt][nt][gp].z &= keep; pk[mt][nt][gp].w &= keep; }
+                }
+            }
             typedef short s16x2_t __attribute__((ext_vector_type(2)));
             auto mx = [](uint32_t a, uint32_t b) {
                 const s16x2_t m = __builtin_elementwise_max(__builtin_bit_cast(s16x2_t, a), __builtin_bit_cast(s16x2_t, b));
                 return __builtin_bit_cast(uint32_t, m);
             };
             auto mx4 = [&](const uint4& a, const uint4& b) { return make_uint4(mx(a.x, b.x), mx(a.y, b.y), mx(a.z, b.z), mx(a.w, b.w)); };
-            auto hmax = [&](uint32_t v) {
-                const uint32_t v1 = (uint32_t)__builtin_amdgcn_ds_bpermute((lane + 1) * 4, (int)v);
-                const uint32_t v2 = (uint32_t)__builtin_amdgcn_ds_bpermute((lane + 2) * 4, (int)v);
-                return mx(mx(v, v1), v2);
+            auto shl1 = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, true); };   // wave_shl:1: lane i <- lane i + 1
+            auto hmax = [&](uint32_t v) {   // max(v[i], v[i+1], v[i+1], v[i+2]), then ReLU
+                const uint32_t m = mx(v, shl1(v));
+                return mx(mx(m, shl1(m)), 0u);
             };
+            // (the barriers are bare: __syncthreads() would also wait for the LDS-DMA of the next tile's first chunk, in flight here)
             unsigned char* exch = smem + free_slot;
-            __syncthreads();
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             if (wave > 0) {
 #pragma unroll
                 for (int nt = 0; nt < R_NT; ++nt)
 #pragma unroll
-                    for (int gp = 0; gp < 2; ++gp) *reinterpret_cast<uint4*>(exch + (wave - 1) * 4096 + ((nt * 2 + gp) * 64 + lane) * 16) = pk[0][nt][gp];
+                    for (int gp = 0; gp < 2; ++gp) *reinterpret_cast<bf16x8_t*>(exch + (wave - 1) * 4096 + ((nt * 2 + gp) * 64 + lane) * 16) = __builtin_bit_cast(bf16x8_t, pk[0][nt][gp]);
             }
-            __syncthreads();
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #pragma unroll
             for (int nt = 0; nt < R_NT; ++nt)
 #pragma unroll
                 for (int gp = 0; gp < 2; ++gp) {
                     uint4 nb = make_uint4(0, 0, 0, 0);
-                    if (wave < NWV - 1) nb = *reinterpret_cast<const uint4*>(exch + wave * 4096 + ((nt * 2 + gp) * 64 + lane) * 16);
+                    if (wave < NWV - 1) nb = __builtin_bit_cast(uint4, ring_frag(exch + wave * 4096 + ((nt * 2 + gp) * 64 + lane) * 16));
                     const uint4 top = mx4(mx4(pk[0][nt][gp], pk[1][nt][gp]), pk[2][nt][gp]);
                     const uint4 bot = mx4(mx4(pk[2][nt][gp], pk[3][nt][gp]), nb);
                     pk[0][nt][gp] = make_uint4(hmax(top.x), hmax(top.y), hmax(top.z), hmax(top.w));
@@ -456,7 +503,7 @@ bool conv_ring_supported(const ConvKernelCfg& cfg, const ConvParams& p) {
     if (off) return false;
     if (!(cfg.nw == 6 && cfg.ks == 3 && cfg.stride == 1 && cfg.bn == 64 && cfg.ck == 16)) return false;
     if ((p.out_mode != OUT_NORMAL && p.out_mode != OUT_POOL) || p.pix_limit != 0 || p.gate != nullptr || p.zeros == nullptr) return false;
-    if (p.out_mode == OUT_POOL && (p.act != ACT_RELU || p.res != nullptr)) return false;   // the pool compares bf16 bit patterns: values must be >= 0
+    if (p.out_mode == OUT_POOL && (p.act != ACT_RELU || p.res != nullptr)) return false;   // the pooled instantiation has ReLU built in (applied once, to the pooled bit patterns) and no residual path
     if (p.Cin < 32 || p.Cin % 16 != 0 || p.Cout % 64 != 0 || p.Cout * 4 > R_BIAS_BYTES || p.Ho != p.H || p.Wo != p.W) return false;
     if (p.n_src > 1) {   // chunks per source >= 2 (the peeled first chunk requests chunk 1 of the same source), whole low-resolution pixels
         if (p.n_src > 4 || p.x_blk || p.out_mode != OUT_NORMAL) return false;
@@ -532,21 +579,23 @@ hipError_t conv_ring_launch(ConvParams p, int orientation, hipStream_t stream) {
         else hipLaunchKernelGGL((conv_ring_kernel<0, false, false, 8>), dim3(8 * wgs), dim3(512), lds8, stream, p, (int)total, per_xcd, wgs, none8);
         return hipGetLastError();
     }
-    if (prof && !pool) {   // developer tool: where do the waves' cycles go (synchronises, prints one line per launch)
+    if (prof) {   // developer tool: where do the waves' cycles go (synchronises, prints one line per launch)
         static unsigned long long* dprof = nullptr;
         if (!dprof && hipMalloc(&dprof, 64) != hipSuccess) return hipErrorOutOfMemory;
         (void)hipMemsetAsync(dprof, 0, 64, stream);
-        const void* fnp = tr ? reinterpret_cast<const void*>(conv_ring_kernel<1, true>) : reinterpret_cast<const void*>(conv_ring_kernel<0, true>);
+        const void* fnp = pool ? reinterpret_cast<const void*>(conv_ring_kernel<0, true, true>)
+                               : (tr ? reinterpret_cast<const void*>(conv_ring_kernel<1, true>) : reinterpret_cast<const void*>(conv_ring_kernel<0, true>));
         hipError_t e = hipFuncSetAttribute(fnp, hipFuncAttributeMaxDynamicSharedMemorySize, R_LDS);
         if (e != hipSuccess) return e;
-        if (tr) hipLaunchKernelGGL((conv_ring_kernel<1, true>), dim3(8 * wg_per_xcd), dim3(256), R_LDS, stream, p, (int)total, per_xcd, wg_per_xcd, dprof);
+        if (pool) hipLaunchKernelGGL((conv_ring_kernel<0, true, true>), dim3(8 * wg_per_xcd), dim3(256), R_LDS, stream, p, (int)total, per_xcd, wg_per_xcd, dprof);
+        else if (tr) hipLaunchKernelGGL((conv_ring_kernel<1, true>), dim3(8 * wg_per_xcd), dim3(256), R_LDS, stream, p, (int)total, per_xcd, wg_per_xcd, dprof);
         else hipLaunchKernelGGL((conv_ring_kernel<0, true>), dim3(8 * wg_per_xcd), dim3(256), R_LDS, stream, p, (int)total, per_xcd, wg_per_xcd, dprof);
         unsigned long long hp[8] = {0};
         (void)hipStreamSynchronize(stream);
         (void)hipMemcpy(hp, dprof, 64, hipMemcpyDeviceToHost);
         const double w = hp[6] ? (double)hp[6] : 1.0, all = hp[5] ? (double)hp[5] : 1.0;
-        fprintf(stderr, "[ring prof] %dx%d cin %d cout %d tr %d tiles %lld waves %.0f cycles/wave %.0f clock %.2f GHz: dma-wait %.1f%% barrier %.1f%% issue+stores %.1f%% compute %.1f%% epilogue %.1f%%\n",
-                p.H, p.W, p.Cin, p.Cout, (int)tr, total, w, all / w, hp[7] ? 0.1 * all / (double)hp[7] : 0.0, 100.0 * hp[0] / all, 100.0 * hp[1] / all, 100.0 * hp[2] / all, 100.0 * hp[3] / all, 100.0 * hp[4] / all);
+        fprintf(stderr, "[ring prof] %dx%d cin %d cout %d tr %d pool %d tiles %lld waves %.0f cycles/wave %.0f clock %.2f GHz: dma-wait %.1f%% barrier %.1f%% issue+stores %.1f%% compute %.1f%% epilogue %.1f%%\n",
+                p.H, p.W, p.Cin, p.Cout, (int)tr, (int)pool, total, w, all / w, hp[7] ? 0.1 * all / (double)hp[7] : 0.0, 100.0 * hp[0] / all, 100.0 * hp[1] / all, 100.0 * hp[2] / all, 100.0 * hp[3] / all, 100.0 * hp[4] / all);
         return hipGetLastError();
     }
     const void* fn = pool ? reinterpret_cast<const void*>(conv_ring_kernel<0, false, true>)
