@@ -10,10 +10,12 @@
 //   2 run_merge     union-find (atomicMin) over run ids: a run joins the runs of the row above it touches (8-connectivity)
 //   3 rl_roots      parent = root = the component's first run (starts at its smallest linear pixel index: canonical); roots per row
 //   4 row_scan / rl_assign : roots in raster order -> component id k < max_boxes, top row
-//   5 rl_extent     atomicMax of the component's bottom row
-//   6 seg_scan / seg_init   per page: row-extreme segments; 7 rl_extremes: per-row min/max x (atomics, one pair per run)
-//   8 comp_box      one work-group per component: hull (monotone chains), rotating calipers over hull
-//                   edges (lanes = edges), fixed-point score (lanes = pixels), unclip, corner order
+//   5 rl_extent     atomicMax of the component's bottom row, by the runs that have no run below them
+//   6 seg_scan / seg_init   per page: row-extreme segments; 7 rl_extremes: per-row min/max x, reduced per component inside the wave
+//                   (atomics only in rows of more than 64 runs)
+//   8 live_list / comp_box   the live components (k < min(ncomp, max_boxes)) of the batch as one list, walked by a grid of what is
+//                   resident; a work-group per component: hull (monotone chains), rotating calipers over hull
+//                   edges (lanes = edges), fixed-point score (lanes = 8-pixel chunks of a row), unclip, corner order
 //   9 compact       valid boxes in component order -> boxes / scores / count
 // row_scan, run_fill and run_merge are the run-list kernels of runs.hip, shared with the selection marks.
 #include "dbpost.h"
@@ -95,14 +97,24 @@ __global__ __launch_bounds__(256) void rl_assign_kernel(const int* runoff, const
         k0 += __popcll(m);
     }
 }
-// 5: bottom row of every component
-__global__ __launch_bounds__(256) void rl_extent_kernel(const int* runoff, const int* parent, const int* cidr, int* ymax, int Hp, size_t runcap, int maxc,
-                                                        int rows_total) {
+// 5: bottom row of every component.  A run that touches a run of the row below (run_merge's rule, 8-connectivity) is not its
+// component's lowest: only the others report their row, so a component costs one atomic per bottom end, not one per run
+__global__ __launch_bounds__(256) void rl_extent_kernel(const int* runoff, const unsigned short* rxs, const unsigned short* rxe, const int* parent,
+                                                        const int* cidr, int* ymax, int Hp, size_t runcap, int maxc, int rows_total) {
     int pg, row, lane;
     if (!row_wave(Hp, rows_total, pg, row, lane)) return;
     const int* ro = runoff + (size_t)pg * (Hp + 1);
     const size_t rb = (size_t)pg * runcap;
-    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
+    const int r0 = ro[row], r1 = ro[row + 1];
+    if (r0 == r1) return;
+    const int b1 = row + 1 < Hp ? ro[row + 2] : r1;   // the row below holds runs [r1, b1)
+    for (int id = r0 + lane; id < r1; id += 64) {
+        if (r1 < b1) {
+            const int xs = rxs[rb + id], xe = rxe[rb + id];
+            int lo = r1, hi = b1;   // first run of the row below with xe' + 1 >= xs
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if ((int)rxe[rb + mid] + 1 < xs) lo = mid + 1; else hi = mid; }
+            if (lo < b1 && (int)rxs[rb + lo] <= xe + 1) continue;
+        }
         const int k = cidr[rb + parent[rb + id]];
         if (k >= 0) atomicMax(&ymax[(size_t)pg * maxc + k], row);
     }
@@ -137,12 +149,32 @@ __global__ __launch_bounds__(256) void rl_extremes_kernel(const int* runoff, con
     if (!row_wave(Hp, rows_total, pg, row, lane)) return;
     const int* ro = runoff + (size_t)pg * (Hp + 1);
     const size_t rb = (size_t)pg * runcap;
-    for (int id = ro[row] + lane; id < ro[row + 1]; id += 64) {
-        const int k = cidr[rb + parent[rb + id]];
-        if (k < 0) continue;
-        const size_t sg = (size_t)pg * seg_cap + segoff[(size_t)pg * (maxc + 1) + k] + (row - ymin[(size_t)pg * maxc + k]);
-        atomicMin(&rowmin[sg], (int)rxs[rb + id]);
-        atomicMax(&rowmax[sg], (int)rxe[rb + id]);
+    const int r0 = ro[row], r1 = ro[row + 1];
+    // the runs of a row are in raster order: among the (up to 64) runs the wave holds, a component's leftmost pixel is the start of
+    // its first run and its rightmost the end of its last.  A row of at most 64 runs is one batch and those two lanes store; a longer
+    // row may split a component over batches, and the same two lanes of every batch fall back to the atomics.
+    const bool single = r1 - r0 <= 64;
+    for (int i0 = r0; i0 < r1; i0 += 64) {   // (wave-uniform bounds: the ballots see every lane)
+        const int id = i0 + lane;
+        const int k = id < r1 ? cidr[rb + parent[rb + id]] : -1;
+        bool first = false, last = false;
+        unsigned long long todo = __ballot(k >= 0);
+        while (todo) {
+            const int kk = __shfl(k, __ffsll((long long)todo) - 1);
+            const unsigned long long m = __ballot(k == kk);
+            if (k == kk) { first = lane == __ffsll((long long)m) - 1; last = lane == 63 - __clzll((long long)m); }
+            todo &= ~m;
+        }
+        if (first || last) {
+            const size_t sg = (size_t)pg * seg_cap + segoff[(size_t)pg * (maxc + 1) + k] + (row - ymin[(size_t)pg * maxc + k]);
+            if (single) {
+                if (first) rowmin[sg] = (int)rxs[rb + id];
+                if (last) rowmax[sg] = (int)rxe[rb + id];
+            } else {
+                if (first) atomicMin(&rowmin[sg], (int)rxs[rb + id]);
+                if (last) atomicMax(&rowmax[sg], (int)rxe[rb + id]);
+            }
+        }
     }
 }
 
@@ -179,19 +211,18 @@ __device__ __forceinline__ long long shfl_xor_ll(long long v, int m) {
 
 constexpr int HULL_LDS = 4096;  // hull points kept in LDS (taller components fall back to the global scratch)
 
-__global__ __launch_bounds__(256) void comp_box_kernel(const bf16_t* prob, const int* ncomp, const int* ymin, const int* ymax, const int* segoff,
-                                                       const int* rowmin, const int* rowmax, int2* hullbuf, int* box_tmp, float* score_tmp,
-                                                       int* valid_tmp, int Hp, int Wp, int vh, int vw, int maxc, size_t seg_cap,
-                                                       float box_thresh, float unclip_ratio, int min_size) {
+// one live component (page pg, id k) by the whole work-group; every path out of it sets the component's valid flag
+__device__ __forceinline__ void comp_box_item(const int pg, const int k, const bf16_t* prob, const int* ymin, const int* ymax, const int* segoff,
+                                              const int* rowmin, const int* rowmax, int2* hullbuf, int* box_tmp, float* score_tmp,
+                                              int* valid_tmp, int Hp, int Wp, int vh, int vw, int maxc, size_t seg_cap,
+                                              float box_thresh, float unclip_ratio, int min_size) {
     __shared__ int2 s_hull[HULL_LDS];
     __shared__ int s_ext[HULL_LDS];  // row minima [0, HULL_LDS/2) and maxima [HULL_LDS/2, HULL_LDS) of the component
     __shared__ Cand s_cand[4];
     __shared__ unsigned long long s_sum[4], s_cnt[4];
     __shared__ int s_nl, s_nr, s_nh;
-    const int pg = blockIdx.x / maxc, k = blockIdx.x % maxc, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int* vflag = valid_tmp + (size_t)pg * maxc + k;
-    const int n = ncomp[pg] < maxc ? ncomp[pg] : maxc;
-    if (k >= n) { if (tid == 0) *vflag = 0; return; }
     const int y0 = ymin[(size_t)pg * maxc + k], y1 = ymax[(size_t)pg * maxc + k];
     const size_t seg = (size_t)pg * seg_cap + segoff[(size_t)pg * (maxc + 1) + k];
     const int* rmin = rowmin + seg;
@@ -294,29 +325,48 @@ __global__ __launch_bounds__(256) void comp_box_kernel(const bf16_t* prob, const
     int bx0 = (int)floor(fx0) - 1, bx1 = (int)ceil(fx1) + 1, by0 = (int)floor(fy0) - 1, by1 = (int)ceil(fy1) + 1;
     bx0 = bx0 < 0 ? 0 : bx0; by0 = by0 < 0 ? 0 : by0; bx1 = bx1 > vw - 1 ? vw - 1 : bx1; by1 = by1 > vh - 1 ? vh - 1 : by1;
     unsigned long long sum = 0, cnt = 0;
-    const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
+    const int bh = by1 - by0 + 1;
     const bf16_t* pp = prob + (size_t)pg * Hp * Wp;
-    // all 256 threads sweep the bounding span; 8 probability loads per thread are requested before the first inside-test
-    // (a load inside the divergent test costs one memory latency per pixel column)
-    const int npx = bw * bh;
-    for (int i0 = 0; i0 < npx; i0 += 256 * 8) {
-        float pv[8];
-        int px[8], py[8];
+    // all 256 threads sweep the bounding span in chunks of 8 pixels of a row, consecutive threads on consecutive chunks.  The two
+    // projections are affine in x: a chunk forms them once (the only 64-bit products) and steps them by (dx, -dy) per pixel.  Where
+    // every row of the map starts on a 16-byte boundary a chunk is one 16-byte load (the span's left edge moved down to a multiple
+    // of 8; pixels outside [bx0, bx1] are masked); two chunks per thread are requested before the first inside-test.
+    const bool vec = (Wp & 7) == 0 && (reinterpret_cast<uintptr_t>(prob) & 15) == 0;
+    const int xa = vec ? bx0 & ~7 : bx0;
+    if (bx1 < bx0 || bh <= 0) { if (tid == 0) *vflag = 0; return; }   // (no pixel: the count below would be 0)
+    const int nch = ((bx1 - xa) >> 3) + 1, ntot = nch * bh;
+    for (int i0 = 0; i0 < ntot; i0 += 256 * 2) {
+        uint4 raw[2];
+        int cx[2], cy[2];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
+        for (int u = 0; u < 2; ++u) {
             const int i = i0 + u * 256 + tid;
-            const int ic = i < npx ? i : 0;
-            const int ry = ic / bw;
-            py[u] = i < npx ? by0 + ry : -1;
-            px[u] = bx0 + (ic - ry * bw);
-            pv[u] = bf16_to_f32(pp[(size_t)(by0 + ry) * Wp + px[u]]);
+            const int ic = i < ntot ? i : 0;
+            const int ry = ic / nch;
+            cy[u] = i < ntot ? by0 + ry : -1;
+            cx[u] = xa + ((ic - ry * nch) << 3);
+            const bf16_t* src = pp + (size_t)(by0 + ry) * Wp + cx[u];
+            if (vec) raw[u] = *reinterpret_cast<const uint4*>(src);
+            else {
+                unsigned int h[8];
+#pragma unroll
+                for (int t = 0; t < 8; ++t) h[t] = cx[u] + t <= bx1 ? src[t] : 0u;
+                raw[u] = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+            }
         }
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const long long pd = (long long)px[u] * best.dx + (long long)py[u] * best.dy, pn = -(long long)px[u] * best.dy + (long long)py[u] * best.dx;
-            const bool in = py[u] >= 0 && pd >= best.mind && pd <= best.maxd && pn >= best.minn && pn <= best.maxn;
-            sum += in ? (unsigned long long)(pv[u] * 16777216.0f) : 0ull;
-            cnt += in ? 1ull : 0ull;
+        for (int u = 0; u < 2; ++u) {
+            long long pd = (long long)cx[u] * best.dx + (long long)cy[u] * best.dy, pn = -(long long)cx[u] * best.dy + (long long)cy[u] * best.dx;
+            const unsigned int w[4] = {raw[u].x, raw[u].y, raw[u].z, raw[u].w};
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                const int x = cx[u] + t;
+                const float pv = __uint_as_float((t & 1) ? (w[t >> 1] & 0xffff0000u) : (w[t >> 1] << 16));
+                const bool in = cy[u] >= 0 && x >= bx0 && x <= bx1 && pd >= best.mind && pd <= best.maxd && pn >= best.minn && pn <= best.maxn;
+                sum += in ? (unsigned long long)(pv * 16777216.0f) : 0ull;
+                cnt += in ? 1ull : 0ull;
+                pd += best.dx; pn -= best.dy;
+            }
         }
     }
 #pragma unroll
@@ -374,14 +424,45 @@ __global__ __launch_bounds__(256) void comp_box_kernel(const bf16_t* prob, const
     *vflag = 1;
 }
 
-// ---- 9 ----
-__global__ __launch_bounds__(64) void compact_kernel(const int* box_tmp, const float* score_tmp, const int* valid_tmp, int* boxes, float* scores,
-                                                     int* counts, int maxc) {
+// 8a: the live components of the batch as one list, page by page in component order: live[i] = pg * maxc + k for k < min(ncomp, maxc),
+// live[B * maxc] = their number.  One work-group per page; it sums the kept counts of the pages before its own.
+__global__ __launch_bounds__(256) void live_list_kernel(const int* ncomp, int* live, int B, int maxc) {
+    __shared__ int s_part[4];
+    const int pg = blockIdx.x, tid = threadIdx.x;
+    int before = 0;
+    for (int q = tid; q < pg; q += 256) before += ncomp[q] < maxc ? ncomp[q] : maxc;
+    before = wave_sum(before);
+    if ((tid & 63) == 0) s_part[tid >> 6] = before;
+    __syncthreads();
+    const int off = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+    const int n = ncomp[pg] < maxc ? ncomp[pg] : maxc;
+    for (int k = tid; k < n; k += 256) live[off + k] = pg * maxc + k;
+    if (pg == B - 1 && tid == 0) live[(size_t)B * maxc] = off + n;
+}
+// 8b: a grid of what is resident; work-group g takes the live components g, g + gridDim.x, ...
+__global__ __launch_bounds__(256) void comp_box_kernel(const bf16_t* prob, const int* live, int items_cap, const int* ymin, const int* ymax,
+                                                       const int* segoff, const int* rowmin, const int* rowmax, int2* hullbuf, int* box_tmp,
+                                                       float* score_tmp, int* valid_tmp, int Hp, int Wp, int vh, int vw, int maxc, size_t seg_cap,
+                                                       float box_thresh, float unclip_ratio, int min_size) {
+    int items = live[items_cap];
+    items = items < items_cap ? items : items_cap;
+    for (int it = blockIdx.x; it < items; it += gridDim.x) {
+        const int code = live[it];
+        comp_box_item(code / maxc, code % maxc, prob, ymin, ymax, segoff, rowmin, rowmax, hullbuf, box_tmp, score_tmp, valid_tmp, Hp, Wp, vh, vw, maxc,
+                      seg_cap, box_thresh, unclip_ratio, min_size);
+        __syncthreads();   // the item's LDS is free for the next one
+    }
+}
+
+// ---- 9: slots at and past min(ncomp, maxc) hold no component (and no flag: comp_box only visits the live ones) ----
+__global__ __launch_bounds__(64) void compact_kernel(const int* ncomp, const int* box_tmp, const float* score_tmp, const int* valid_tmp, int* boxes,
+                                                     float* scores, int* counts, int maxc) {
     const int pg = blockIdx.x, lane = threadIdx.x;
+    const int n = ncomp[pg] < maxc ? ncomp[pg] : maxc;
     int run = 0;
-    for (int k0 = 0; k0 < maxc; k0 += 64) {
+    for (int k0 = 0; k0 < n; k0 += 64) {
         const int k = k0 + lane;
-        const bool v = k < maxc && valid_tmp[(size_t)pg * maxc + k] != 0;
+        const bool v = k < n && valid_tmp[(size_t)pg * maxc + k] != 0;
         const unsigned long long m = __ballot(v);
         if (v) {
             const int pos = run + __popcll(m & ((1ull << lane) - 1ull));
@@ -427,13 +508,23 @@ __global__ __launch_bounds__(256) void crop_kernel(const uint8_t* pages, int H, 
     const float tlx = (float)p[0][0], tly = (float)p[0][1];
     const float ex = (float)(p[1][0] - p[0][0]), ey = (float)(p[1][1] - p[0][1]);
     const float fx = (float)(p[3][0] - p[0][0]), fy = (float)(p[3][1] - p[0][1]);
-    for (int t = tid; t < CH * CW; t += 256) {
-        const int i = t / CW, j = t - i * CW;
-        uint8_t r3[3] = {0, 0, 0};
-        if (j < wc) {
-            const int si = turn ? CH - 1 - i : i, sj = turn ? wc - 1 - j : j;
-            const float u = __fdiv_rn((float)sj + 0.5f, (float)wc), v = __fdiv_rn((float)si + 0.5f, (float)CH);
-            const float t1 = __fmul_rn(u, ex), t2 = __fmul_rn(v, fx), t3 = __fmul_rn(u, ey), t4 = __fmul_rn(v, fy);
+    // a thread owns 4 consecutive output columns of a row: 12 bytes, stored as three dwords (a crop row is CW * 3 bytes, a multiple
+    // of 4).  The row terms (v and its products) are formed once for the four; every pixel keeps its own operations and their order.
+    static_assert(CW % 4 == 0, "four columns per thread");
+    const bool dword_out = (reinterpret_cast<uintptr_t>(crops) & 3) == 0;
+    for (int t = tid; t < CH * (CW / 4); t += 256) {
+        const int i = t / (CW / 4), j0 = (t - i * (CW / 4)) * 4;
+        const int si = turn ? CH - 1 - i : i;
+        const float v = __fdiv_rn((float)si + 0.5f, (float)CH);
+        const float t2 = __fmul_rn(v, fx), t4 = __fmul_rn(v, fy);
+        uint32_t px[4] = {0, 0, 0, 0};   // r | g << 8 | b << 16 of the four pixels
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int j = j0 + q;
+            if (j >= wc) continue;
+            const int sj = turn ? wc - 1 - j : j;
+            const float u = __fdiv_rn((float)sj + 0.5f, (float)wc);
+            const float t1 = __fmul_rn(u, ex), t3 = __fmul_rn(u, ey);
             const float sx = __fadd_rn(__fadd_rn(tlx, t1), t2), sy = __fadd_rn(__fadd_rn(tly, t3), t4);
             const float x0f = floorf(sx), y0f = floorf(sy);
             const float ax = __fsub_rn(sx, x0f), ay = __fsub_rn(sy, y0f);
@@ -441,17 +532,37 @@ __global__ __launch_bounds__(256) void crop_kernel(const uint8_t* pages, int H, 
             x0 = x0 < 0 ? 0 : (x0 > W - 1 ? W - 1 : x0); x1 = x1 < 0 ? 0 : (x1 > W - 1 ? W - 1 : x1);
             y0 = y0 < 0 ? 0 : (y0 > H - 1 ? H - 1 : y0); y1 = y1 < 0 ? 0 : (y1 > H - 1 ? H - 1 : y1);
             const float bx = __fsub_rn(1.0f, ax), by = __fsub_rn(1.0f, ay);
+            // the two taps of a page row are 6 adjacent bytes unless the clamp folded them onto one pixel: fetched as 4 + 2
+            const uint8_t* r0 = page + ((size_t)y0 * W + x0) * 3;
+            const uint8_t* r1 = page + ((size_t)y1 * W + x0) * 3;
+            uint32_t a0, a1, b0, b1;   // bytes 0-3 (r g b r') and 4-5 (g' b') of the pair, per page row
+            if (x1 == x0 + 1) {
+                uint16_t h0, h1;
+                __builtin_memcpy(&a0, r0, 4); __builtin_memcpy(&h0, r0 + 4, 2); __builtin_memcpy(&b0, r1, 4); __builtin_memcpy(&h1, r1 + 4, 2);
+                a1 = h0; b1 = h1;
+            } else {   // x1 == x0
+                a0 = r0[0] | (r0[1] << 8) | (r0[2] << 16); b0 = r1[0] | (r1[1] << 8) | (r1[2] << 16);
+                a1 = a0 >> 8; a0 |= a0 << 24; b1 = b0 >> 8; b0 |= b0 << 24;
+            }
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float p00 = page[((size_t)y0 * W + x0) * 3 + c], p01 = page[((size_t)y0 * W + x1) * 3 + c];
-                const float p10 = page[((size_t)y1 * W + x0) * 3 + c], p11 = page[((size_t)y1 * W + x1) * 3 + c];
+                const float p00 = (float)((a0 >> (8 * c)) & 255u), p10 = (float)((b0 >> (8 * c)) & 255u);
+                const float p01 = (float)(c == 0 ? a0 >> 24 : (a1 >> (8 * (c - 1))) & 255u), p11 = (float)(c == 0 ? b0 >> 24 : (b1 >> (8 * (c - 1))) & 255u);
                 const float top = __fadd_rn(__fmul_rn(bx, p00), __fmul_rn(ax, p01)), bot = __fadd_rn(__fmul_rn(bx, p10), __fmul_rn(ax, p11));
                 float val = rintf(__fadd_rn(__fmul_rn(by, top), __fmul_rn(ay, bot)));
                 val = val < 0.f ? 0.f : (val > 255.f ? 255.f : val);
-                r3[c] = (uint8_t)val;
+                px[q] |= (uint32_t)val << (8 * c);
             }
         }
-        out[(size_t)t * 3 + 0] = r3[0]; out[(size_t)t * 3 + 1] = r3[1]; out[(size_t)t * 3 + 2] = r3[2];
+        uint8_t* o = out + (size_t)t * 12;
+        const uint32_t w0 = px[0] | (px[1] << 24), w1 = (px[1] >> 8) | (px[2] << 16), w2 = (px[2] >> 16) | (px[3] << 8);
+        if (dword_out) {
+            uint32_t* od = reinterpret_cast<uint32_t*>(o);
+            od[0] = w0; od[1] = w1; od[2] = w2;
+        } else {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) { o[b] = (uint8_t)(w0 >> (8 * b)); o[4 + b] = (uint8_t)(w1 >> (8 * b)); o[8 + b] = (uint8_t)(w2 >> (8 * b)); }
+        }
     }
 }
 
@@ -460,7 +571,7 @@ __global__ __launch_bounds__(256) void crop_kernel(const uint8_t* pages, int H, 
 // the workspace's regions: one layout sizes it (dbpost_workspace_bytes) and carves it (dbpost_launch)
 struct DbWorkspace {
     unsigned long long* mask; int *runoff, *rootoff, *nruns, *ncomp; unsigned short *rxs, *rxe;
-    int *parent, *cidr, *ymin, *ymax, *segoff, *rowmin, *rowmax; int2* hull; int* box_tmp; float* score_tmp; int* valid_tmp;
+    int *parent, *cidr, *ymin, *ymax, *segoff, *rowmin, *rowmax; int2* hull; int* box_tmp; float* score_tmp; int* valid_tmp; int* live;
 };
 static DbWorkspace dbpost_layout(Arena& a, int B, int Hp, int Wp, int maxc) {
     const size_t seg_cap = (size_t)maxc * Hp;  // worst case: every candidate spans the page height
@@ -476,6 +587,7 @@ static DbWorkspace dbpost_layout(Arena& a, int B, int Hp, int Wp, int maxc) {
     w.rowmin = a.take<int>((size_t)B * seg_cap); w.rowmax = a.take<int>((size_t)B * seg_cap);
     w.hull = a.take<int2>((size_t)B * seg_cap * 2);
     w.box_tmp = a.take<int>((size_t)B * maxc * 8); w.score_tmp = a.take<float>((size_t)B * maxc); w.valid_tmp = a.take<int>((size_t)B * maxc);
+    w.live = a.take<int>((size_t)B * maxc + 1);   // live components (page * maxc + id) + their number
     return w;
 }
 
@@ -487,12 +599,14 @@ size_t dbpost_workspace_bytes(int B, int Hp, int Wp, int maxc) {
 
 hipError_t dbpost_launch(const DbPostParams& p, void* workspace, size_t ws_bytes, hipStream_t st) {
     const int B = p.B, Hp = p.Hp, Wp = p.Wp, maxc = p.max_boxes;
-    if (B <= 0 || Hp <= 0 || Wp <= 0 || Wp > 65535 || maxc <= 0 || (size_t)B * Hp >= (1ull << 31) || run_cap(Hp, Wp) >= (1ull << 31)) return hipErrorInvalidValue;
+    if (B <= 0 || Hp <= 0 || Wp <= 0 || Wp > 65535 || maxc <= 0 || (size_t)B * Hp >= (1ull << 31) || (size_t)B * maxc >= (1ull << 31) || run_cap(Hp, Wp) >= (1ull << 31)) return hipErrorInvalidValue;
     const size_t seg_cap = (size_t)maxc * Hp, runcap = run_cap(Hp, Wp);
     const int nseg = (Wp + 63) / 64;
     Arena a(workspace, ws_bytes);
     const DbWorkspace w = dbpost_layout(a, B, Hp, Wp, maxc);
     if (a.overflow) return hipErrorOutOfMemory;
+    int dev = 0, cus = 0;
+    { hipError_t e = hipGetDevice(&dev); if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); if (e != hipSuccess) return e; }
 
     const int rows = B * Hp;
     const dim3 grows = row_wave_grid(rows);
@@ -503,13 +617,16 @@ hipError_t dbpost_launch(const DbPostParams& p, void* workspace, size_t ws_bytes
     hipLaunchKernelGGL(rl_roots_kernel, grows, dim3(256), 0, st, w.runoff, w.parent, w.rootoff, Hp, runcap, rows);
     row_scan_launch(w.rootoff, w.ncomp, B, Hp, st);
     hipLaunchKernelGGL(rl_assign_kernel, grows, dim3(256), 0, st, w.runoff, w.rootoff, w.parent, w.cidr, w.ymin, w.ymax, Hp, runcap, maxc, rows);
-    hipLaunchKernelGGL(rl_extent_kernel, grows, dim3(256), 0, st, w.runoff, w.parent, w.cidr, w.ymax, Hp, runcap, maxc, rows);
+    hipLaunchKernelGGL(rl_extent_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.cidr, w.ymax, Hp, runcap, maxc, rows);
     hipLaunchKernelGGL(seg_scan_kernel, dim3(B), dim3(64), 0, st, w.ncomp, w.ymin, w.ymax, w.segoff, maxc);
     hipLaunchKernelGGL(seg_init_kernel, dim3(64, B), dim3(256), 0, st, w.ncomp, w.segoff, w.rowmin, w.rowmax, maxc, seg_cap);
     hipLaunchKernelGGL(rl_extremes_kernel, grows, dim3(256), 0, st, w.runoff, w.rxs, w.rxe, w.parent, w.cidr, w.ymin, w.segoff, w.rowmin, w.rowmax, Hp, runcap, maxc, seg_cap, rows);
-    hipLaunchKernelGGL(comp_box_kernel, dim3(B * maxc), dim3(256), 0, st, p.prob, w.ncomp, w.ymin, w.ymax, w.segoff, w.rowmin, w.rowmax, w.hull, w.box_tmp,
+    hipLaunchKernelGGL(live_list_kernel, dim3(B), dim3(256), 0, st, w.ncomp, w.live, B, maxc);
+    // comp_box holds 48 KB of LDS: three work-groups are resident on a compute unit
+    const int resident = cus * 3 < B * maxc ? cus * 3 : B * maxc;
+    hipLaunchKernelGGL(comp_box_kernel, dim3(resident), dim3(256), 0, st, p.prob, w.live, B * maxc, w.ymin, w.ymax, w.segoff, w.rowmin, w.rowmax, w.hull, w.box_tmp,
                        w.score_tmp, w.valid_tmp, Hp, Wp, p.valid_h, p.valid_w, maxc, seg_cap, p.box_thresh, p.unclip_ratio, p.min_size);
-    hipLaunchKernelGGL(compact_kernel, dim3(B), dim3(64), 0, st, w.box_tmp, w.score_tmp, w.valid_tmp, p.boxes, p.scores, p.counts, maxc);
+    hipLaunchKernelGGL(compact_kernel, dim3(B), dim3(64), 0, st, w.ncomp, w.box_tmp, w.score_tmp, w.valid_tmp, p.boxes, p.scores, p.counts, maxc);
     return hipGetLastError();
 }
 
