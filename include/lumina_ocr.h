@@ -47,6 +47,8 @@ const char* lumina_ocr_version(void);
  * "blocked_layout" (experiment: fails loudly when a blocked tensor would reach a kernel other than the ring kernel);
  * "svtr_f16" (storage type of the next SVTR load), "conv2d_variant" (kernel choice of lumina_ocr_conv2d, parity tests);
  * "png_sub_batch_mb" (lumina_ocr_png_decode: MB of inflated scanlines per sub-batch, default 768 — bounds the workspace a PNG batch reserves);
+ * "webp_sub_batch_mb" (lumina_ocr_webp_decode: MB of pixel planes and code tables per sub-batch, default 2048 — bounds the workspace a WebP batch
+ * reserves);
  * "jp2_sub_batch_mb" (lumina_ocr_jp2_decode: MB of coefficient planes per sub-batch, default 4096) */
 int lumina_ocr_set_option(lumina_ocr_t* h, const char* key, int value);
 
@@ -563,6 +565,27 @@ int lumina_ocr_jpeg_decode_progressive(lumina_ocr_t* h, const uint8_t* const* fi
 int lumina_ocr_png_probe(const uint8_t* file, size_t size, int info[8]);
 int lumina_ocr_png_decode(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev,
                           int* status, void* stream);
+
+/* Lossless WebP decode on the device — the pixel work of the reference's Image.open(...) + convert('RGB') for .webp inputs
+ * (image_preprocessing.py:57-75).  The contract is the JPEG pair's: status 0 => byte-identical to Pillow's (libwebp's)
+ * Image.open(f).convert('RGB'); any other status => the file is left to Pillow (the device accepts a file only where every conformant
+ * decoder agrees: see the acceptance rule in DESIGN.md).
+ * lumina_ocr_webp_probe (host only, no handle): a walk over the RIFF chunks (no pixel data is read); info = {width, height, the VP8L
+ * alpha bit, 1 inside a VP8X container, 1 with an EXIF chunk, 1 with an XMP chunk, 0, 0}; returns 0 for a file the device decodes
+ * (RIFF / WEBP with one VP8L chunk, bare or inside VP8X; ICCP, EXIF, XMP and unknown chunks skipped), -2 valid WebP that is not read
+ * (lossy VP8, an ALPH chunk, animation, more than 2^26 pixels, a VP8L chunk of 256 MB or more): decode those with Pillow, as the reference
+ * does; -1 corrupt or irregular (signature byte other than 0x2F, version bits other than 0, a chunk or the RIFF size past the file, bytes
+ * after the RIFF payload, chunks after the image of a file without VP8X, a VP8X canvas that differs from the VP8L header).
+ * lumina_ocr_webp_reason: why the calling thread's last probe returned `code` (a static string; the generic meaning of the code otherwise).
+ * lumina_ocr_webp_decode: files / sizes are HOST arrays of n file images, all height x width; out_dev uint8 [n][height][width][3] (alpha
+ * dropped: the stored RGB, not pre-multiplied); status HOST int [n]: 0 ok; -1 corrupt (container, a prefix code that is over- or
+ * under-subscribed, a copy before the first or past the last pixel, a transform repeated, colour-cache bits outside 1..11, reading past
+ * the chunk); -2 outside the subset (as the probe; more than 4096 prefix-code groups); -4 another size.  A page with a non-zero status
+ * is not written.  Synchronises `stream`. */
+int lumina_ocr_webp_probe(const uint8_t* file, size_t size, int info[8]);
+const char* lumina_ocr_webp_reason(int code);
+int lumina_ocr_webp_decode(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev,
+                           int* status, void* stream);
 
 /* JPEG 2000 decode on the device — the pixel work of the reference's Image.open(...) + convert('RGB') for .jp2 / .j2k inputs, and the
  * /JPXDecode pages of scanned PDFs.  The contract is the JPEG pair's: status 0 => byte-identical to Pillow's (OpenJPEG's) decode; any

@@ -22,6 +22,8 @@
 #include "lzw.h"
 #include "jp2dec.h"
 #include "pngdec.h"
+#include "webpdec.h"
+#include "webp_parse.h"
 #include "ccitt.h"
 #include "jbig2.h"
 #include "jbig2_parse.h"
@@ -176,6 +178,7 @@ int lumina_ocr_set_option(lumina_ocr_t* h, const char* key, int value) {
     else if (!strcmp(key, "tail_group")) h->tail_group = value > 0 ? value : 0;
     else if (!strcmp(key, "svtr_f16")) h->svtr_f16 = value < 0 ? -1 : (value != 0);
     else if (!strcmp(key, "png_sub_batch_mb")) h->pd_sub_batch_mb = value > 0 ? value : 1;
+    else if (!strcmp(key, "webp_sub_batch_mb")) h->wp_sub_batch_mb = value > 0 ? value : 1;
     else if (!strcmp(key, "jp2_sub_batch_mb")) h->jp_sub_batch_mb = value > 0 ? value : 1;
     else if (!strcmp(key, "conv2d_variant")) h->conv2d_variant = value < 0 || value > 2 ? 0 : value;
     else return locr_fail(h, "set_option: unknown key", key);
@@ -542,6 +545,40 @@ int lumina_ocr_png_decode(lumina_ocr_t* h, const uint8_t* const* files, const si
     BIND(h);
     API_TRY
     return pngdec_run(h, files, sizes, n, height, width, out_dev, status, (hipStream_t)stream);
+    API_CATCH(h)
+}
+
+namespace {
+thread_local int webp_last_code = 0;
+thread_local const char* webp_last_reason = "";
+}  // namespace
+
+int lumina_ocr_webp_probe(const uint8_t* file, size_t size, int info[8]) {
+    if (!file || !info) return -1;
+    WpInfo i{};
+    const int rc = webp_probe(file, size, &i);
+    info[0] = i.width; info[1] = i.height; info[2] = i.alpha; info[3] = i.vp8x; info[4] = i.exif; info[5] = i.xmp; info[6] = 0; info[7] = 0;
+    webp_last_code = rc; webp_last_reason = i.reason ? i.reason : "";
+    return rc;
+}
+
+const char* lumina_ocr_webp_reason(int code) {
+    if (code != 0 && code == webp_last_code && webp_last_reason[0]) return webp_last_reason;
+    switch (code) {
+        case 0: return "read";
+        case -1: return "corrupt or irregular WebP file";
+        case -2: return "valid WebP that is not read";
+        case -4: return "another size than the batch";
+    }
+    return "unknown status";
+}
+
+int lumina_ocr_webp_decode(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev, int* status,
+                           void* stream) {
+    if (!h || !files || !sizes || !out_dev || !status || n <= 0 || height <= 0 || width <= 0) return locr_fail(h, "webp_decode", "bad arguments");
+    BIND(h);
+    API_TRY
+    return webpdec_run(h, files, sizes, n, height, width, out_dev, status, (hipStream_t)stream);
     API_CATCH(h)
 }
 

@@ -164,6 +164,8 @@ struct lumina_ocr {
     Staging pd_stage;   // pinned staging of the PNG decoder's gathered IDAT payloads (pngdec.hip)
     int pd_sub_batch_mb = 768;   // PNG decoder: filtered-scanline MB per sub-batch (64 A4 RGB pages at 300 dpi are 1.7 GB); sizes its workspace
     Staging jp_stage;   // pinned staging of the JPEG 2000 decoder's block records and coded bytes (jp2dec.hip)
+    Staging wp_stage;   // pinned staging of the WebP decoder's gathered VP8L payloads (webpdec.hip)
+    int wp_sub_batch_mb = 2048;   // WebP decoder: MB of planes and code tables per sub-batch (an A4 page at 200 dpi takes 69 MB, 37 of them tables)
     int jp_sub_batch_mb = 4096;   // JPEG 2000 decoder: MB of coefficient planes per sub-batch (an A4 RGB page at 200 dpi takes 93 MB)
     float* dk_trig = nullptr; short* dk_wtab = nullptr;   // de-skew tables (deskew.h), uploaded at first use
     Staging pc_stage;               // pinned copy of the page-composition layer table (compose.hip) ...

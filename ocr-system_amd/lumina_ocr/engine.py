@@ -81,6 +81,9 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_jpeg_coefficients": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
         "lumina_ocr_png_probe": (i32, [vp, sz, vp]),
         "lumina_ocr_png_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+        "lumina_ocr_webp_probe": (i32, [vp, sz, vp]),
+        "lumina_ocr_webp_reason": (c.c_char_p, [i32]),
+        "lumina_ocr_webp_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_jp2_probe": (i32, [vp, sz, vp]),
         "lumina_ocr_jp2_reason": (c.c_char_p, [i32]),
         "lumina_ocr_jp2_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
@@ -148,6 +151,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_jpeg_probe_progressive", "lumina_ocr_jpeg_decode_progressive",
     "lumina_ocr_jp2_probe", "lumina_ocr_jp2_reason", "lumina_ocr_jp2_decode",
     "lumina_ocr_jp2_probe_irreversible", "lumina_ocr_jp2_decode_irreversible",
+    "lumina_ocr_webp_probe", "lumina_ocr_webp_reason", "lumina_ocr_webp_decode",
     "lumina_ocr_png_probe", "lumina_ocr_png_decode", "lumina_ocr_flate_image_decode", "lumina_ocr_ccitt_decode", "lumina_ocr_fax_decode", "lumina_ocr_strip_image_decode",
     "lumina_ocr_jbig2_probe", "lumina_ocr_jbig2_reason", "lumina_ocr_jbig2_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
@@ -308,6 +312,32 @@ class Engine:
         sizes = (ctypes.c_size_t * n)(*[len(f) for f in files])
         status = (ctypes.c_int * n)()
         self._chk(self.lib.lumina_ocr_png_decode(self._h, ptrs, sizes, n, int(height), int(width), _ptr(out), status, self._stream()))
+        return out, list(status)
+
+    @staticmethod
+    def webp_probe(data: bytes):
+        """Host only, the RIFF chunk headers and the VP8L header. -> (rc, dict(width, height, alpha, vp8x, exif, xmp, reason)); rc 0: the
+        device decodes this file (lossless, one VP8L chunk, bare or inside VP8X), -2: valid WebP that is not read (lossy, ALPH, animated,
+        more than 2^26 pixels: decode with Pillow as the reference does), -1: corrupt or irregular.  exif / xmp: the file has such a chunk."""
+        lib = load_library()
+        info = (ctypes.c_int * 8)()
+        data = data if isinstance(data, bytes) else bytes(data)
+        rc = lib.lumina_ocr_webp_probe(ctypes.c_char_p(data), len(data), info)
+        return rc, dict(width=info[0], height=info[1], alpha=info[2], vp8x=info[3], exif=info[4], xmp=info[5],
+                        reason=lib.lumina_ocr_webp_reason(rc).decode() if rc else "")
+
+    def webp_decode(self, files, height: int, width: int, out=None):
+        """Lossless WebP file images (a sequence of bytes objects, all height x width) -> (uint8 [n,H,W,3] device, status list): the pixels
+        of the reference's Image.open(...).convert('RGB') for .webp inputs (image_preprocessing.py:57-75), byte-identical to Pillow.
+        status[i] != 0: page i was not decoded (-1 corrupt, -2 not read by the device, -4 another size) and is left to Pillow."""
+        torch = _torch()
+        n = len(files)
+        if out is None:
+            out = torch.empty((n, height, width, 3), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        ptrs = (ctypes.c_char_p * n)(*files)
+        sizes = (ctypes.c_size_t * n)(*[len(f) for f in files])
+        status = (ctypes.c_int * n)()
+        self._chk(self.lib.lumina_ocr_webp_decode(self._h, ptrs, sizes, n, int(height), int(width), _ptr(out), status, self._stream()))
         return out, list(status)
 
     JP2_ORDERS = ("LRCP", "RLCP", "RPCL", "PCRL", "CPRL")

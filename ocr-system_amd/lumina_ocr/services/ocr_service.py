@@ -126,6 +126,11 @@ class OCRService:
         # LUMINA_OCR_DEVICE_PNG=1: non-interlaced PNG inputs of 8 bits or less and lazily opened PNG pages (pdf2image) are decoded on the
         # device.  Off by default: measured slower than Pillow for single pages and for 300 dpi batches
         self.device_png = os.environ.get("LUMINA_OCR_DEVICE_PNG", "0").lower() not in ("0", "false", "no")
+        # LUMINA_OCR_DEVICE_WEBP=1: lossless WebP inputs (one VP8L chunk, bare or inside VP8X; recognised by magic) are decoded on the device
+        # (lumina_ocr_webp_decode); lossy and animated files, and files with an XMP chunk, still go to Pillow.  Off by default: exactly
+        # the calls made without the option are made (the measurements are in DESIGN.md §8.3)
+        self.device_webp = os.environ.get("LUMINA_OCR_DEVICE_WEBP", "0").lower() not in ("", "0", "false", "no")
+        self._webp_reasons_logged = set()
         # LUMINA_OCR_PDF_SCANS=1: a PDF page that is one image over the whole MediaBox (a scan: DCT, Flate or CCITT of any /K) is decoded
         # on the device from its embedded stream, at the image's own sample grid, instead of being rasterised by pdf2image / poppler; other
         # pages still go to pdf_to_images.  Off by default: process_pdf_sync is then the rasterise-and-batch path alone.
@@ -575,6 +580,61 @@ class OCRService:
         return self._process_single_image_sync(image, page_number, decoded=decoded)
 
     @staticmethod
+    def _is_webp(head: bytes) -> bool:
+        return head[:4] == b"RIFF" and head[8:12] == b"WEBP"
+
+    def _decode_webp_on_device(self, data: bytes, image: Image.Image):
+        """A lossless WebP file the device reads -> device tensor [1,H,W,3] with the EXIF orientation applied (lumina_ocr_webp_decode:
+        byte-identical to Pillow), or None: Pillow decodes.  `image` is the lazily opened file (nothing decoded yet): its info carries
+        the EXIF chunk, read here as _png_orientation reads a PNG's; a file with XMP is left to the host path and its auto_orient."""
+        try:
+            if image.format != "WEBP" or "xmp" in image.info or "XML:com.adobe.xmp" in image.info:
+                return None
+            orientation = image.getexif().get(0x0112, 1) if "exif" in image.info else 1
+            if orientation not in range(0, 9):
+                return None
+            self._ensure_engine()   # (before the probe loads the engine library: see _decode_png_on_device)
+            from ..engine import Engine
+            rc, info = Engine.webp_probe(data)
+            if rc != 0 or info["xmp"] or (info["width"], info["height"]) != image.size:
+                reason = info["reason"] if rc else "XMP chunk, or a size that differs from the opened image's"
+                if reason not in self._webp_reasons_logged:
+                    self._webp_reasons_logged.add(reason)
+                    logger.info("WebP input left to Pillow (status %d): %s", rc, reason)
+                return None
+            with self._device_ctx():
+                out, status = self._engine.webp_decode([data], info["height"], info["width"])
+                if status != [0]:
+                    return None
+                return self._engine.exif_transpose(out, orientation)     # auto_orient (image_preprocessing.py:213), on the device as well
+        except Exception as e:       # any doubt: the reference's own path
+            logger.warning("device WebP decode not used: %s", e)
+            return None
+
+    def _process_webp_on_device(self, image_source: Union[str, Path, bytes], page_number: int) -> Optional[OCROutput]:
+        """A WebP path / bytes (recognised by magic, never by extension) whose pixels the device decodes -> its result; None: today's path."""
+        try:
+            if isinstance(image_source, bytes):
+                data = image_source
+            else:
+                with open(image_source, "rb") as f:
+                    if not self._is_webp(f.read(12)):
+                        return None
+                data = Path(image_source).read_bytes()
+        except OSError:
+            return None
+        if not self._is_webp(data[:12]):
+            return None
+        try:
+            image = Image.open(io.BytesIO(data))
+        except Exception:
+            return None
+        decoded = self._decode_webp_on_device(data, image)
+        if decoded is None:
+            return None
+        return self._process_single_image_sync(image, page_number, decoded=decoded)
+
+    @staticmethod
     def _is_jp2(head: bytes) -> bool:
         return head[:12] == JP2_SIGNATURE or head[:4] == J2K_SIGNATURE
 
@@ -645,6 +705,10 @@ class OCRService:
                 return r
         if self.device_png and isinstance(image_source, (bytes, str, Path)):
             r = self._process_png_on_device(image_source, page_number)
+            if r is not None:
+                return r
+        if self.device_webp and isinstance(image_source, (bytes, str, Path)):
+            r = self._process_webp_on_device(image_source, page_number)
             if r is not None:
                 return r
         if isinstance(image_source, bytes):
