@@ -627,6 +627,26 @@ int lumina_ocr_jp2_decode(lumina_ocr_t* h, const uint8_t* const* files, const si
 int lumina_ocr_jp2_probe_irreversible(const uint8_t* file, size_t size, int info[8]);
 int lumina_ocr_jp2_decode_irreversible(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width,
                                        uint8_t* out_dev, int* status, void* stream);
+/* Tiled JPEG 2000 files as well: what scanners, Acrobat scan profiles and archive masters write.  `flags` names what is read beyond
+ * the first subset; the four entries above keep their answers (-2 for a tiled file, with their reasons).
+ * LUMINA_OCR_JP2_F_IRREVERSIBLE: 9/7 files, as the _irreversible entries take them.
+ * LUMINA_OCR_JP2_F_TILES: any XOsiz / YOsiz / XTOsiz / YTOsiz the standard allows (Xsiz, Ysiz up to 2^30); a grid of up to 4096
+ * tiles, their tile-parts in any order and interleaved, TPsot counting up within each tile, Psot = 0 on the last tile-part; user
+ * precinct sizes (COD with Scod & 1); all five progression orders over several precincts; code-blocks clipped to their precinct.
+ * height / width, and info[0] / info[1], are those of the image area (Xsiz - XOsiz by Ysiz - YOsiz), which keeps the limits above.
+ * Both inverse transforms run per tile-component, and a line whose first canvas coordinate is odd starts with a high-pass sample; the
+ * 9/7 refusal of a one-sample line holds per tile-component resolution.  status 0 => byte-identical to Pillow, as everywhere.
+ * Still -2: SOP / EPH, POC, coding parameters per tile (COD / COC / QCD / QCC / RGN in a tile-part header), PPM / PPT, sub-sampled
+ * components, more than 4096 tiles.  -1 besides the list above: origins that leave the first tile empty, a tile without a tile-part
+ * or with fewer than it announces, TPsot out of order within its tile, a tile index outside the grid, a precinct exponent of 0 above
+ * resolution 0, a tile whose packets end early or leave data over.  Other flag bits: -1 from the probe, an error from the decode.
+ * lumina_ocr_jp2_reason serves lumina_ocr_jp2_probe_ex too.  A one-tile file gives the bytes of the entries above.
+ * lumina_ocr_jp2_decode_ex synchronises `stream`. */
+#define LUMINA_OCR_JP2_F_IRREVERSIBLE 1u
+#define LUMINA_OCR_JP2_F_TILES 2u
+int lumina_ocr_jp2_probe_ex(const uint8_t* file, size_t size, unsigned flags, int info[8]);
+int lumina_ocr_jp2_decode_ex(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev,
+                             int* status, unsigned flags, void* stream);
 
 /* Scanned PDF pages — the images of a PDF whose pages are one image each (utils/pdf_pages.py finds them), decoded at their own sample
  * grid instead of the rasterisation pdf2image / poppler does for the reference (ocr_service.py:508-660).  /DCTDecode streams are JPEG

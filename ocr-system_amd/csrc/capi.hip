@@ -588,12 +588,12 @@ thread_local const char* jp2_last_reason = "";
 }  // namespace
 
 namespace {
-int jp2_probe_any(const uint8_t* file, size_t size, int info[8], bool irreversible) {
+int jp2_probe_any(const uint8_t* file, size_t size, int info[8], unsigned flags) {
     if (!file || !info) return -1;
     Jp2Probe p{};
     int rc = -1;
     try {
-        rc = jp2dec_probe(file, size, &p, irreversible);
+        rc = jp2dec_probe(file, size, &p, flags);
     } catch (const std::exception&) {   // (allocation failure: the file is left to the host decoder)
         p.reason = "out of memory while reading the packet headers";
         rc = -2;
@@ -604,8 +604,17 @@ int jp2_probe_any(const uint8_t* file, size_t size, int info[8], bool irreversib
 }
 }  // namespace
 
-int lumina_ocr_jp2_probe(const uint8_t* file, size_t size, int info[8]) { return jp2_probe_any(file, size, info, false); }
-int lumina_ocr_jp2_probe_irreversible(const uint8_t* file, size_t size, int info[8]) { return jp2_probe_any(file, size, info, true); }
+int lumina_ocr_jp2_probe(const uint8_t* file, size_t size, int info[8]) { return jp2_probe_any(file, size, info, 0); }
+int lumina_ocr_jp2_probe_irreversible(const uint8_t* file, size_t size, int info[8]) {
+    return jp2_probe_any(file, size, info, LUMINA_OCR_JP2_F_IRREVERSIBLE);
+}
+int lumina_ocr_jp2_probe_ex(const uint8_t* file, size_t size, unsigned flags, int info[8]) {
+    if (flags & ~(unsigned)(LUMINA_OCR_JP2_F_IRREVERSIBLE | LUMINA_OCR_JP2_F_TILES)) {
+        jp2_last_code = -1; jp2_last_reason = "unknown flag bits";
+        return -1;
+    }
+    return jp2_probe_any(file, size, info, flags);
+}
 
 const char* lumina_ocr_jp2_reason(int code) {
     if (code != 0 && code == jp2_last_code && jp2_last_reason[0]) return jp2_last_reason;
@@ -632,7 +641,18 @@ int lumina_ocr_jp2_decode_irreversible(lumina_ocr_t* h, const uint8_t* const* fi
     if (!h || !files || !sizes || !out_dev || !status || n <= 0 || height <= 0 || width <= 0) return locr_fail(h, "jp2_decode_irreversible", "bad arguments");
     BIND(h);
     API_TRY
-    return jp2dec_run(h, files, sizes, n, height, width, out_dev, status, (hipStream_t)stream, true);
+    return jp2dec_run(h, files, sizes, n, height, width, out_dev, status, (hipStream_t)stream, LUMINA_OCR_JP2_F_IRREVERSIBLE);
+    API_CATCH(h)
+}
+
+int lumina_ocr_jp2_decode_ex(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev,
+                             int* status, unsigned flags, void* stream) {
+    if (!h || !files || !sizes || !out_dev || !status || n <= 0 || height <= 0 || width <= 0 ||
+        (flags & ~(unsigned)(LUMINA_OCR_JP2_F_IRREVERSIBLE | LUMINA_OCR_JP2_F_TILES)))
+        return locr_fail(h, "jp2_decode_ex", "bad arguments");
+    BIND(h);
+    API_TRY
+    return jp2dec_run(h, files, sizes, n, height, width, out_dev, status, (hipStream_t)stream, flags);
     API_CATCH(h)
 }
 

@@ -215,22 +215,36 @@ JP2_HD inline int jp2_t1_value(const Jp2T1State& S, int y, int x) {
     return ((S.sgn[y + 1] >> x) & 1) ? -v : v;
 }
 
-// ---- inverse 5/3 lifting of one line of n samples, low-pass first (sn = (n + 1) / 2 of them), sample i of the line at line[i * stride].
-// Whole-sample symmetric extension: d[-1] = d[0], d[dn] = d[dn - 1], x[n] = x[n - 2].  A line of one sample is its low-pass sample.
+// ---- inverse 5/3 lifting of one line of n samples whose first canvas coordinate has parity cas, low-pass samples first (sn of them),
+// sample i of the line at line[i * stride].  Sample i of the rebuilt line sits on a low-pass position where i + cas is even, and is
+// the (i >> 1)-th of its kind either way.  Whole-sample symmetric extension by canvas parity: a neighbour outside the line is
+// replaced by the other one.  A line of one sample is its low-pass sample (cas 0) or half its high-pass sample, toward zero (cas 1).
 template <class T>
-JP2_HD inline int jp2_lift_even(const T* line, long long stride, int n, int k) {   // x[2k], 0 <= k < sn
-    const int sn = (n + 1) / 2, dn = n - sn;
-    const int s = line[k * stride];
-    if (dn == 0) return s;
-    const int dl = line[(sn + (k > 0 ? k - 1 : 0)) * stride], dr = line[(sn + (k < dn ? k : dn - 1)) * stride];
+JP2_HD inline int jp2_lift_low(const T* line, long long stride, int n, int cas, int i) {   // i + cas even
+    const int sn = (n + 1 - cas) >> 1;
+    const int s = line[(i >> 1) * stride];
+    if (n == sn) return s;
+    const int l = i > 0 ? i - 1 : i + 1, r = i + 1 < n ? i + 1 : i - 1;
+    const int dl = line[(sn + (l >> 1)) * stride], dr = line[(sn + (r >> 1)) * stride];
     return s - ((dl + dr + 2) >> 2);
 }
 template <class T>
-JP2_HD inline int jp2_lift_odd(const T* line, long long stride, int n, int k) {   // x[2k + 1], 0 <= k < dn
-    const int sn = (n + 1) / 2;
-    const int a = jp2_lift_even(line, stride, n, k), b = jp2_lift_even(line, stride, n, k + 1 < sn ? k + 1 : k);
-    return line[(sn + k) * stride] + ((a + b) >> 1);
+JP2_HD inline int jp2_lift_high(const T* line, long long stride, int n, int cas, int i) {   // i + cas odd
+    const int sn = (n + 1 - cas) >> 1;
+    const int d = line[(sn + (i >> 1)) * stride];
+    if (sn == 0) return d / 2;
+    const int l = i > 0 ? i - 1 : i + 1, r = i + 1 < n ? i + 1 : i - 1;
+    return d + ((jp2_lift_low(line, stride, n, cas, l) + jp2_lift_low(line, stride, n, cas, r)) >> 1);
 }
+template <class T>
+JP2_HD inline int jp2_lift_at(const T* line, long long stride, int n, int cas, int i) {
+    return ((i + cas) & 1) ? jp2_lift_high(line, stride, n, cas, i) : jp2_lift_low(line, stride, n, cas, i);
+}
+// the k-th low-pass position / the k-th high-pass position of the line
+template <class T>
+JP2_HD inline int jp2_lift_even(const T* line, long long stride, int n, int k, int cas = 0) { return jp2_lift_low(line, stride, n, cas, 2 * k + cas); }
+template <class T>
+JP2_HD inline int jp2_lift_odd(const T* line, long long stride, int n, int k, int cas = 0) { return jp2_lift_high(line, stride, n, cas, 2 * k + 1 - cas); }
 
 // ---- the 9/7 irreversible path, in single precision in the order OpenJPEG evaluates it.  Every expression below is one rounding per
 // operation (the project compiles with -ffp-contract=off, and subnormals are kept), so host, device and any tiling give the same bits.
@@ -241,16 +255,19 @@ JP2_HD inline float jp2_t1_value_f(const Jp2T1State& S, int y, int x, float hs) 
     return (float)(((S.sgn[y + 1] >> x) & 1) ? -v : v) * hs;
 }
 
-// the scaling of a low-pass / high-pass sample as it is interleaved, and the four lifting steps: step s updates the samples of parity
-// s & 1 as x -= (left + right) * jp2_lift97_coef(s)
+// the scaling of a low-pass / high-pass sample as it is interleaved, and the four lifting steps: step s updates the samples of canvas
+// parity s & 1 (0: the low-pass positions; jp2_lift97_first) as x -= (left + right) * jp2_lift97_coef(s)
 #define JP2_K97_LOW 1.230174105f
 #define JP2_K97_HIGH 1.625732422f
 JP2_HD inline float jp2_lift97_coef(int s) { return s == 0 ? 0.443506852f : s == 1 ? 0.882911075f : s == 2 ? -0.052980118f : -1.586134342f; }
 
-// sample i of the interleaved line of n >= 2 samples, read from the sub-band order (low-pass first, sn = (n + 1) / 2 of them)
-JP2_HD inline float jp2_lift97_load(const float* line, long long stride, int n, int i) {
-    return (i & 1) ? line[((n + 1) / 2 + (i >> 1)) * stride] * JP2_K97_HIGH : line[(i >> 1) * stride] * JP2_K97_LOW;
+// sample i of the interleaved line of n >= 2 samples whose first canvas coordinate has parity cas, read from the sub-band order
+// (low-pass first, sn = (n + 1 - cas) / 2 of them): low-pass where i + cas is even
+JP2_HD inline float jp2_lift97_load(const float* line, long long stride, int n, int i, int cas = 0) {
+    return ((i + cas) & 1) ? line[(((n + 1 - cas) >> 1) + (i >> 1)) * stride] * JP2_K97_HIGH : line[(i >> 1) * stride] * JP2_K97_LOW;
 }
+// the first sample at or after lo that step s updates: the steps go by canvas parity (s & 1: 0 low-pass positions, 1 high-pass ones)
+JP2_HD inline int jp2_lift97_first(int lo, int s, int cas) { return lo + ((lo + cas + s) & 1); }
 
 // One lifting step at sample i of an interleaved line of n samples whose samples [lo, hi) are held at w[(i - lo) * stride].  A neighbour
 // outside the line is replaced by the other one (whole-sample mirror); a sample with a neighbour inside the line but outside the window

@@ -4,12 +4,16 @@
 //              coding passes per bit-plane (jp2_t1.h).  The decision walk is serial and runs on one lane over row bit-maps in LDS
 //              (64-bit words, one per block row); the wave clears the state and writes the coefficients out.  10.5 KB of LDS per
 //              wave: 15 waves per CU.
-//   j2_dwt_h / j2_dwt_v   the inverse 5/3 lifting, level by level, horizontal then vertical, between two int32 planes
+//   j2_dwt_h / j2_dwt_v   the inverse 5/3 lifting, level by level, horizontal then vertical, between two int32 planes: one launch per
+//              level and direction over every tile-component of every page (J2Tile; a one-tile page is one tile-component a plane)
 //   j2_dwt97_h / j2_dwt97_v   the inverse 9/7 lifting of the irreversible pages, beside them, over the same two planes read as float
 //   j2_finish  inverse colour transform (reversible or irreversible), level shift, clamp -> RGB u8
 // A 9/7 page (J2Page::kind 1) differs from a 5/3 page in the value tier 1 writes (the half-unit magnitude times half the step size,
 // as float), in its lifting kernels and in the branch of j2_finish; both kinds share a batch and the tier-1 launch.  All of the float
 // arithmetic is in jp2_t1.h, one rounding per operation in OpenJPEG's order, so the bytes are Pillow's.
+// A component plane is [height][width] of the image area.  Each tile-component owns its rectangle of the plane and keeps its sub-bands
+// inside it as the transform reads them, low-pass part top left; tier 1 writes a block where the host's record says, so it does not
+// know tiles.  Sizes and the parity of a line's first sample come from the tile's corners on the canvas.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -54,97 +58,115 @@ __global__ __launch_bounds__(64) void j2_tier1(const J2Block* __restrict__ block
     }
 }
 
-__device__ inline int j2_cdiv(int a, int b) { return (a + b - 1) / b; }
+// A tile-component: its rectangle of its component plane (px, py, x1 - x0 wide, y1 - y0 high), its corners on the canvas, and what to
+// run on it.  Sizes on a resolution come from the canvas corners, ceil(x1 / 2^s) - ceil(x0 / 2^s), and so does the parity of a line's
+// first sample: a line that starts on an odd coordinate starts with a high-pass sample (jp2_t1.h).
+struct J2Tile { int plane, px, py, x0, y0, x1, y1, levels, kind; };
 
-// one step of the inverse transform: the pages whose `levels` reach `step` rebuild their resolution `step` (rw x rh, top left of the plane)
-__global__ __launch_bounds__(256) void j2_dwt_h(const J2Page* __restrict__ pages, const int* __restrict__ src, int* __restrict__ dst, int height,
-                                                int width, int step) {
-    const J2Page pg = pages[blockIdx.z];
-    if (pg.kind != 0 || step > pg.levels || (int)blockIdx.y >= pg.comps) return;
-    const int sh = pg.levels - step, rw = j2_cdiv(width, 1 << sh), rh = j2_cdiv(height, 1 << sh), np = (rw + 1) / 2;
-    const size_t plane = (size_t)(pg.plane0 + blockIdx.y) * height * width;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < (long long)rh * np; i += (long long)gridDim.x * 256) {
+__device__ inline int j2_cdivp(int a, int sh) { return (a + (1 << sh) - 1) >> sh; }
+
+// One step of the inverse transform: every tile-component whose `levels` reach `step` rebuilds its resolution `step` (top left of its
+// rectangle).  blockIdx.x = tile-component * per + share: `per` work-groups split a tile-component's samples between them.
+__global__ __launch_bounds__(256) void j2_dwt_h(const J2Tile* __restrict__ tiles, const int* __restrict__ src, int* __restrict__ dst, int height,
+                                                int width, int step, unsigned per) {
+    const J2Tile T = tiles[blockIdx.x / per];
+    if (T.kind != 0 || step > T.levels) return;
+    const int sh = T.levels - step, rx0 = j2_cdivp(T.x0, sh), rw = j2_cdivp(T.x1, sh) - rx0, rh = j2_cdivp(T.y1, sh) - j2_cdivp(T.y0, sh);
+    const int cas = rx0 & 1, np = (rw + 1) / 2;
+    const size_t base = ((size_t)T.plane * height + T.py) * width + T.px;
+    for (long long i = (long long)(blockIdx.x % per) * 256 + threadIdx.x; i < (long long)rh * np; i += (long long)per * 256) {
         const int y = (int)(i / np), k = (int)(i - (long long)y * np);
-        const int* line = src + plane + (size_t)y * width;
-        int* o = dst + plane + (size_t)y * width;
-        o[2 * k] = jp2_lift_even(line, 1, rw, k);
-        if (2 * k + 1 < rw) o[2 * k + 1] = jp2_lift_odd(line, 1, rw, k);
+        const int* line = src + base + (size_t)y * width;
+        int* o = dst + base + (size_t)y * width;
+        o[2 * k] = jp2_lift_at(line, 1, rw, cas, 2 * k);
+        if (2 * k + 1 < rw) o[2 * k + 1] = jp2_lift_at(line, 1, rw, cas, 2 * k + 1);
     }
 }
 
-__global__ __launch_bounds__(256) void j2_dwt_v(const J2Page* __restrict__ pages, const int* __restrict__ src, int* __restrict__ dst, int height,
-                                                int width, int step) {
-    const J2Page pg = pages[blockIdx.z];
-    if (pg.kind != 0 || step > pg.levels || (int)blockIdx.y >= pg.comps) return;
-    const int sh = pg.levels - step, rw = j2_cdiv(width, 1 << sh), rh = j2_cdiv(height, 1 << sh), np = (rh + 1) / 2;
-    const size_t plane = (size_t)(pg.plane0 + blockIdx.y) * height * width;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < (long long)np * rw; i += (long long)gridDim.x * 256) {
+__global__ __launch_bounds__(256) void j2_dwt_v(const J2Tile* __restrict__ tiles, const int* __restrict__ src, int* __restrict__ dst, int height,
+                                                int width, int step, unsigned per) {
+    const J2Tile T = tiles[blockIdx.x / per];
+    if (T.kind != 0 || step > T.levels) return;
+    const int sh = T.levels - step, ry0 = j2_cdivp(T.y0, sh), rw = j2_cdivp(T.x1, sh) - j2_cdivp(T.x0, sh), rh = j2_cdivp(T.y1, sh) - ry0;
+    const int cas = ry0 & 1, np = (rh + 1) / 2;
+    const size_t base = ((size_t)T.plane * height + T.py) * width + T.px;
+    for (long long i = (long long)(blockIdx.x % per) * 256 + threadIdx.x; i < (long long)np * rw; i += (long long)per * 256) {
         const int k = (int)(i / rw), x = (int)(i - (long long)k * rw);
-        const int* line = src + plane + x;
-        int* o = dst + plane + x;
-        o[(size_t)(2 * k) * width] = jp2_lift_even(line, width, rh, k);
-        if (2 * k + 1 < rh) o[(size_t)(2 * k + 1) * width] = jp2_lift_odd(line, width, rh, k);
+        const int* line = src + base + x;
+        int* o = dst + base + x;
+        o[(size_t)(2 * k) * width] = jp2_lift_at(line, width, rh, cas, 2 * k);
+        if (2 * k + 1 < rh) o[(size_t)(2 * k + 1) * width] = jp2_lift_at(line, width, rh, cas, 2 * k + 1);
     }
 }
 
 // ---- the 9/7 lifting.  An output sample depends on four input samples to either side through the four steps, so a work-group holds a
 // window of a line in LDS (jp2_lift97_at): the samples it owns and JP2_LIFT97_HALO more a side, interleaved and scaled as they are
-// loaded, then one step per barrier interval.  Windows start on even samples; the expression tree of a sample is fixed, so the tiling
-// does not show in the bits.
+// loaded, then one step per barrier interval.  The expression tree of a sample is fixed, so neither the windows nor the tiling of the
+// launch show in the bits.
 constexpr int J2_HSEG = 256;    // samples of a row a work-group of j2_dwt97_h owns (a sample pair per thread and step; 3 % of halo)
 constexpr int J2_VSEG = 56;     // rows of a 64-column strip a work-group of j2_dwt97_v owns: 64 x 64 floats, 16 KB of LDS
 
-// blockIdx.x = window of the row * rows + row (rows: the most rows any page rebuilds at this step); y: component; z: page.
-// Lanes read the two halves of the row alternately (two runs of 32 floats per wave) and write the row out contiguously; the steps
-// touch every other float of the window, a 2-way bank conflict that four short passes over 1 KB do not repay removing.
-__global__ __launch_bounds__(128) void j2_dwt97_h(const J2Page* __restrict__ pages, const float* __restrict__ src, float* __restrict__ dst, int height,
-                                                  int width, int step, int rows) {
+// blockIdx.x = tile-component * per + share; a tile-component's units are (window of the row, row), shared out between its `per`
+// work-groups.  Lanes read the two halves of the row alternately (two runs of 32 floats per wave) and write the row out contiguously;
+// the steps touch every other float of the window, a 2-way bank conflict that four short passes over 1 KB do not repay removing.
+__global__ __launch_bounds__(128) void j2_dwt97_h(const J2Tile* __restrict__ tiles, const float* __restrict__ src, float* __restrict__ dst, int height,
+                                                  int width, int step, unsigned per) {
     __shared__ float w[J2_HSEG + 2 * JP2_LIFT97_HALO];
-    const J2Page pg = pages[blockIdx.z];
-    if (pg.kind != 1 || step > pg.levels || (int)blockIdx.y >= pg.comps) return;
-    const int sh = pg.levels - step, rw = j2_cdiv(width, 1 << sh), rh = j2_cdiv(height, 1 << sh);
-    const int y = (int)(blockIdx.x % (unsigned)rows), seg0 = (int)(blockIdx.x / (unsigned)rows) * J2_HSEG;
-    if (y >= rh || seg0 >= rw) return;
-    const int lo = seg0 - JP2_LIFT97_HALO < 0 ? 0 : seg0 - JP2_LIFT97_HALO;
-    const int end = seg0 + J2_HSEG < rw ? seg0 + J2_HSEG : rw, hi = end + JP2_LIFT97_HALO < rw ? end + JP2_LIFT97_HALO : rw;
-    const size_t row = ((size_t)(pg.plane0 + blockIdx.y) * height + y) * width;
-    const int tid = threadIdx.x;
-    for (int i = lo + tid; i < hi; i += 128) w[i - lo] = jp2_lift97_load(src + row, 1, rw, i);
-    __syncthreads();
-    for (int s = 0; s < 4; ++s) {
-        const float c = jp2_lift97_coef(s);
-        for (int i = lo + (s & 1) + 2 * tid; i < hi; i += 256) jp2_lift97_at(w, 1, lo, hi, rw, i, c);
+    const J2Tile T = tiles[blockIdx.x / per];
+    if (T.kind != 1 || step > T.levels) return;
+    const int sh = T.levels - step, rx0 = j2_cdivp(T.x0, sh), rw = j2_cdivp(T.x1, sh) - rx0, rh = j2_cdivp(T.y1, sh) - j2_cdivp(T.y0, sh);
+    const int cas = rx0 & 1, tid = threadIdx.x;
+    const long long units = rh > 0 ? (long long)((rw + J2_HSEG - 1) / J2_HSEG) * rh : 0;
+    const size_t base = ((size_t)T.plane * height + T.py) * width + T.px;
+    for (long long u = blockIdx.x % per; u < units; u += per) {
+        const int y = (int)(u % rh), seg0 = (int)(u / rh) * J2_HSEG;
+        const int lo = seg0 - JP2_LIFT97_HALO < 0 ? 0 : seg0 - JP2_LIFT97_HALO;
+        const int end = seg0 + J2_HSEG < rw ? seg0 + J2_HSEG : rw, hi = end + JP2_LIFT97_HALO < rw ? end + JP2_LIFT97_HALO : rw;
+        const size_t row = base + (size_t)y * width;
+        for (int i = lo + tid; i < hi; i += 128) w[i - lo] = jp2_lift97_load(src + row, 1, rw, i, cas);
         __syncthreads();
+        for (int s = 0; s < 4; ++s) {
+            const float c = jp2_lift97_coef(s);
+            for (int i = jp2_lift97_first(lo, s, cas) + 2 * tid; i < hi; i += 256) jp2_lift97_at(w, 1, lo, hi, rw, i, c);
+            __syncthreads();
+        }
+        for (int i = seg0 + tid; i < end; i += 128) dst[row + i] = w[i - lo];
+        __syncthreads();   // the next unit loads over the window
     }
-    for (int i = seg0 + tid; i < end; i += 128) dst[row + i] = w[i - lo];
 }
 
-// blockIdx.x = window of the columns * strips + strip (strips: 64-column strips of the widest resolution any page rebuilds at this
-// step).  A wave is 64 neighbouring columns of one row: its loads and stores are 256 contiguous bytes and its LDS accesses one bank row.
-__global__ __launch_bounds__(256) void j2_dwt97_v(const J2Page* __restrict__ pages, const float* __restrict__ src, float* __restrict__ dst, int height,
-                                                  int width, int step, int strips) {
+// A tile-component's units are (window of the columns, 64-column strip).  A wave is 64 neighbouring columns of one row: its loads and
+// stores are 256 contiguous bytes and its LDS accesses one bank row.
+__global__ __launch_bounds__(256) void j2_dwt97_v(const J2Tile* __restrict__ tiles, const float* __restrict__ src, float* __restrict__ dst, int height,
+                                                  int width, int step, unsigned per) {
     __shared__ float w[(J2_VSEG + 2 * JP2_LIFT97_HALO) * 64];
-    const J2Page pg = pages[blockIdx.z];
-    if (pg.kind != 1 || step > pg.levels || (int)blockIdx.y >= pg.comps) return;
-    const int sh = pg.levels - step, rw = j2_cdiv(width, 1 << sh), rh = j2_cdiv(height, 1 << sh);
-    const int x0 = (int)(blockIdx.x % (unsigned)strips) * 64, seg0 = (int)(blockIdx.x / (unsigned)strips) * J2_VSEG;
-    if (x0 >= rw || seg0 >= rh) return;
-    const int lo = seg0 - JP2_LIFT97_HALO < 0 ? 0 : seg0 - JP2_LIFT97_HALO;
-    const int end = seg0 + J2_VSEG < rh ? seg0 + J2_VSEG : rh, hi = end + JP2_LIFT97_HALO < rh ? end + JP2_LIFT97_HALO : rh;
-    const int cx = threadIdx.x & 63, q = threadIdx.x >> 6, x = x0 + cx;
-    const bool live = x < rw;
-    const size_t col = (size_t)(pg.plane0 + blockIdx.y) * height * width + (size_t)(live ? x : x0);
-    if (live)
-        for (int i = lo + q; i < hi; i += 4) w[(i - lo) * 64 + cx] = jp2_lift97_load(src + col, width, rh, i);
-    __syncthreads();
-    for (int s = 0; s < 4; ++s) {
-        const float c = jp2_lift97_coef(s);
+    const J2Tile T = tiles[blockIdx.x / per];
+    if (T.kind != 1 || step > T.levels) return;
+    const int sh = T.levels - step, ry0 = j2_cdivp(T.y0, sh), rw = j2_cdivp(T.x1, sh) - j2_cdivp(T.x0, sh), rh = j2_cdivp(T.y1, sh) - ry0;
+    const int cas = ry0 & 1, strips = (rw + 63) / 64;
+    const long long units = (long long)strips * ((rh + J2_VSEG - 1) / J2_VSEG);
+    const int cx = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const size_t base = ((size_t)T.plane * height + T.py) * width + T.px;
+    for (long long u = blockIdx.x % per; u < units; u += per) {
+        const int x0 = (int)(u % strips) * 64, seg0 = (int)(u / strips) * J2_VSEG;
+        const int lo = seg0 - JP2_LIFT97_HALO < 0 ? 0 : seg0 - JP2_LIFT97_HALO;
+        const int end = seg0 + J2_VSEG < rh ? seg0 + J2_VSEG : rh, hi = end + JP2_LIFT97_HALO < rh ? end + JP2_LIFT97_HALO : rh;
+        const int x = x0 + cx;
+        const bool live = x < rw;
+        const size_t col = base + (size_t)(live ? x : x0);
         if (live)
-            for (int i = lo + (s & 1) + 2 * q; i < hi; i += 8) jp2_lift97_at(w + cx, 64, lo, hi, rh, i, c);
+            for (int i = lo + q; i < hi; i += 4) w[(i - lo) * 64 + cx] = jp2_lift97_load(src + col, width, rh, i, cas);
         __syncthreads();
+        for (int s = 0; s < 4; ++s) {
+            const float c = jp2_lift97_coef(s);
+            if (live)
+                for (int i = jp2_lift97_first(lo, s, cas) + 2 * q; i < hi; i += 8) jp2_lift97_at(w + cx, 64, lo, hi, rh, i, c);
+            __syncthreads();
+        }
+        if (live)
+            for (int i = seg0 + q; i < end; i += 4) dst[col + (size_t)i * width] = w[(i - lo) * 64 + cx];
+        __syncthreads();   // the next unit loads over the window
     }
-    if (live)
-        for (int i = seg0 + q; i < end; i += 4) dst[col + (size_t)i * width] = w[(i - lo) * 64 + cx];
 }
 
 __device__ inline uint8_t j2_sample(int v) { v += 128; return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
@@ -176,32 +198,34 @@ __global__ __launch_bounds__(256) void j2_finish(const J2Page* __restrict__ page
     }
 }
 
-struct J2Workspace { J2Block* blocks; J2Page* pages; uint8_t* bytes; int *a, *b; };
-J2Workspace j2_layout(Arena& a, size_t nblocks, size_t nbytes, int pages, size_t planes, int height, int width) {
+struct J2Workspace { J2Block* blocks; J2Page* pages; J2Tile* tiles; uint8_t* bytes; int *a, *b; };
+J2Workspace j2_layout(Arena& a, size_t nblocks, size_t nbytes, int pages, size_t planes, int height, int width, size_t ntiles) {
     J2Workspace w;
-    w.blocks = a.take<J2Block>(nblocks); w.pages = a.take<J2Page>((size_t)pages); w.bytes = a.take<uint8_t>(nbytes);
+    w.blocks = a.take<J2Block>(nblocks); w.pages = a.take<J2Page>((size_t)pages); w.tiles = a.take<J2Tile>(ntiles); w.bytes = a.take<uint8_t>(nbytes);
     w.a = a.take<int>(planes * height * width); w.b = a.take<int>(planes * height * width);
     return w;
 }
 
+inline int h_cdivp(int a, int sh) { return (a + (1 << sh) - 1) >> sh; }
+
 }  // namespace
 
-size_t jp2dec_workspace_bytes(size_t nblocks, size_t nbytes, int pages, size_t planes, int height, int width) {
+size_t jp2dec_workspace_bytes(size_t nblocks, size_t nbytes, int pages, size_t planes, int height, int width, size_t tile_components) {
     Arena a;
-    j2_layout(a, nblocks, nbytes, pages, planes, height, width);
+    j2_layout(a, nblocks, nbytes, pages, planes, height, width, tile_components);
     return a.off;
 }
 
-int jp2dec_probe(const uint8_t* file, size_t n, Jp2Probe* out, bool irreversible) {
+int jp2dec_probe(const uint8_t* file, size_t n, Jp2Probe* out, unsigned flags) {
     Jp2File f;
-    const int rc = jp2_parse(file, n, &f, irreversible);
+    const int rc = jp2_parse(file, n, &f, flags);
     memcpy(out->info, f.info, sizeof(f.info));
     out->reason = f.reason;
     return rc;
 }
 
 int jp2dec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev, int* status,
-               hipStream_t st, bool irreversible) {
+               hipStream_t st, unsigned flags) {
     lumina_ocr::Staging& stage = eng->jp_stage;
     if (!stage.uploaded) {
         hipEvent_t ev = nullptr;
@@ -210,7 +234,7 @@ int jp2dec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes
     }
     const size_t npx = (size_t)height * width;
     const size_t budget = (size_t)eng->jp_sub_batch_mb << 20;
-    constexpr size_t MAX_PAGES = 65535;   // a sub-batch's pages are a grid dimension of the transform and colour launches
+    constexpr size_t MAX_PAGES = 65535;   // a sub-batch's pages are a grid dimension of the colour launch
     int i0 = 0;
     Jp2File held;          // the page that did not fit the last sub-batch: it opens the next one and is not parsed again
     bool holding = false;
@@ -218,7 +242,7 @@ int jp2dec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes
         // a sub-batch: pages until their coefficient planes (two int32 copies) pass the budget, at least one page
         std::vector<Jp2File> F;
         std::vector<int> index;
-        size_t planes = 0, nblocks = 0, nbytes = 0;
+        size_t planes = 0, nblocks = 0, nbytes = 0, ntc = 0;
         int i1 = i0;
         for (; i1 < n; ++i1) {
             Jp2File f;
@@ -226,7 +250,7 @@ int jp2dec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes
                 f = std::move(held);
                 holding = false;
             } else {
-                int rc = jp2_parse(files[i1], sizes[i1], &f, irreversible);
+                int rc = jp2_parse(files[i1], sizes[i1], &f, flags);
                 if (rc == 0 && (f.width != width || f.height != height)) rc = -4;
                 status[i1] = rc;
                 if (rc) continue;
@@ -237,6 +261,7 @@ int jp2dec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes
                 break;
             }
             planes += (size_t)f.comps;
+            ntc += f.tiles.size() * (size_t)f.comps;
             for (const Jp2Block& K : f.blocks)
                 if (K.passes) {
                     ++nblocks;
@@ -249,19 +274,23 @@ int jp2dec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes
         }
         const int np = (int)index.size();
         if (np) {
-            // staging: [J2Block x nblocks][J2Page x np][bytes]
+            // staging: [J2Block x nblocks][J2Page x np][J2Tile x ntc][bytes]
             const size_t blocks_b = (sizeof(J2Block) * nblocks + 255) & ~(size_t)255, pages_b = (sizeof(J2Page) * np + 255) & ~(size_t)255;
+            const size_t tiles_b = (sizeof(J2Tile) * ntc + 255) & ~(size_t)255;
             LOCR_CHECK(hipEventSynchronize(stage.uploaded.get()));
-            LOCR_CHECK(stage.buf.reserve(blocks_b + pages_b + nbytes + 256, stage.uploaded.get()));
+            LOCR_CHECK(stage.buf.reserve(blocks_b + pages_b + tiles_b + nbytes + 256, stage.uploaded.get()));
             J2Block* hb = reinterpret_cast<J2Block*>(stage.buf.get());
             J2Page* hp = reinterpret_cast<J2Page*>(stage.buf.get() + blocks_b);
-            uint8_t* hbytes = stage.buf.get() + blocks_b + pages_b;
-            size_t bi = 0, off = 0;
+            J2Tile* ht = reinterpret_cast<J2Tile*>(stage.buf.get() + blocks_b + pages_b);
+            uint8_t* hbytes = stage.buf.get() + blocks_b + pages_b + tiles_b;
+            size_t bi = 0, ti = 0, off = 0;
             int plane0 = 0, max_levels = 0;
             for (int k = 0; k < np; ++k) {
                 const Jp2File& f = F[(size_t)k];
                 hp[k] = J2Page{f.levels, f.comps, f.mct, index[(size_t)k], plane0, f.irreversible};
                 max_levels = std::max(max_levels, f.levels);
+                for (int c = 0; c < f.comps; ++c)
+                    for (const Jp2Tile& T : f.tiles) ht[ti++] = J2Tile{plane0 + c, T.x0 - f.x0, T.y0 - f.y0, T.x0, T.y0, T.x1, T.y1, f.levels, f.irreversible};
                 for (const Jp2Block& K : f.blocks) {
                     if (!K.passes) continue;
                     J2Block& b = hb[bi++];
@@ -277,39 +306,48 @@ int jp2dec_run(lumina_ocr* eng, const uint8_t* const* files, const size_t* sizes
                 plane0 += f.comps;
             }
             Arena sizing;
-            j2_layout(sizing, nblocks, nbytes + 256, np, planes, height, width);
+            j2_layout(sizing, nblocks, nbytes + 256, np, planes, height, width, ntc);
             if (eng_ws_reserve(eng, sizing.off)) return 1;
             Arena a(eng->ws.get(), eng->ws.cap);
-            const J2Workspace w = j2_layout(a, nblocks, nbytes + 256, np, planes, height, width);
+            const J2Workspace w = j2_layout(a, nblocks, nbytes + 256, np, planes, height, width, ntc);
             if (a.overflow) return locr_fail(eng, "jp2_decode", "workspace layout exceeds the reservation");
             if (nblocks) LOCR_CHECK(hipMemcpyAsync(w.blocks, hb, sizeof(J2Block) * nblocks, hipMemcpyHostToDevice, st));
             LOCR_CHECK(hipMemcpyAsync(w.pages, hp, sizeof(J2Page) * np, hipMemcpyHostToDevice, st));
+            LOCR_CHECK(hipMemcpyAsync(w.tiles, ht, sizeof(J2Tile) * ntc, hipMemcpyHostToDevice, st));
             if (nbytes) LOCR_CHECK(hipMemcpyAsync(w.bytes, hbytes, nbytes, hipMemcpyHostToDevice, st));
             LOCR_CHECK(hipEventRecord(stage.uploaded.get(), st));
             LOCR_CHECK(hipMemsetAsync(w.a, 0, planes * npx * sizeof(int), st));   // blocks no layer includes are zero
             if (nblocks) hipLaunchKernelGGL(j2_tier1, dim3((unsigned)nblocks), dim3(64), 0, st, w.blocks, w.bytes, w.a, height, width);
             float* const fa = reinterpret_cast<float*>(w.a);
             float* const fb = reinterpret_cast<float*>(w.b);
+            // one launch per step and direction over all tile-components: blockIdx.x = tile-component * per + share, `per` from the
+            // largest tile-component of the step (a grid's x dimension holds 2^31 - 1 work-groups; the kernels stride over what is left)
+            const size_t most = (size_t)0x7FFFFFFF / ntc;
             for (int step = 1; step <= max_levels; ++step) {
-                size_t work = 0;         // the largest resolution any 5/3 page rebuilds at this step
-                int rw97 = 0, rh97 = 0;  // and the largest any 9/7 page does
+                size_t work = 0;               // the largest resolution any 5/3 tile-component rebuilds at this step
+                size_t units_h = 0, units_v = 0;   // the most windows any 9/7 tile-component has, along the rows and along the columns
                 for (const Jp2File& f : F)
                     if (step <= f.levels) {
-                        const int sh = f.levels - step, rh = (height + (1 << sh) - 1) >> sh, rw = (width + (1 << sh) - 1) >> sh;
-                        if (f.irreversible) { rw97 = std::max(rw97, rw); rh97 = std::max(rh97, rh); }
-                        else work = std::max(work, (size_t)rh * (size_t)rw);
+                        const int sh = f.levels - step;
+                        for (const Jp2Tile& T : f.tiles) {
+                            const size_t rw = (size_t)(h_cdivp(T.x1, sh) - h_cdivp(T.x0, sh)), rh = (size_t)(h_cdivp(T.y1, sh) - h_cdivp(T.y0, sh));
+                            if (f.irreversible) {
+                                units_h = std::max(units_h, (rw + J2_HSEG - 1) / J2_HSEG * rh);
+                                units_v = std::max(units_v, (rw + 63) / 64 * ((rh + J2_VSEG - 1) / J2_VSEG));
+                            } else {
+                                work = std::max(work, rh * rw);
+                            }
+                        }
                     }
                 if (work) {
-                    const dim3 grid((unsigned)std::min<size_t>((work / 2 + 255) / 256 + 1, 2048), 3, (unsigned)np);
-                    hipLaunchKernelGGL(j2_dwt_h, grid, dim3(256), 0, st, w.pages, w.a, w.b, height, width, step);
-                    hipLaunchKernelGGL(j2_dwt_v, grid, dim3(256), 0, st, w.pages, w.b, w.a, height, width, step);
+                    const unsigned per = (unsigned)std::min<size_t>(std::min<size_t>((work / 2 + 255) / 256 + 1, 2048), most);
+                    hipLaunchKernelGGL(j2_dwt_h, dim3((unsigned)(ntc * per)), dim3(256), 0, st, w.tiles, w.a, w.b, height, width, step, per);
+                    hipLaunchKernelGGL(j2_dwt_v, dim3((unsigned)(ntc * per)), dim3(256), 0, st, w.tiles, w.b, w.a, height, width, step, per);
                 }
-                if (rw97) {   // (sides <= 16384: at most 64 windows x 16384 rows and 256 strips x 293 windows)
-                    const int strips = (rw97 + 63) / 64;
-                    hipLaunchKernelGGL(j2_dwt97_h, dim3((unsigned)((rw97 + J2_HSEG - 1) / J2_HSEG * rh97), 3, (unsigned)np), dim3(128), 0, st, w.pages, fa, fb,
-                                       height, width, step, rh97);
-                    hipLaunchKernelGGL(j2_dwt97_v, dim3((unsigned)((rh97 + J2_VSEG - 1) / J2_VSEG * strips), 3, (unsigned)np), dim3(256), 0, st, w.pages, fb, fa,
-                                       height, width, step, strips);
+                if (units_h) {
+                    const unsigned per_h = (unsigned)std::min(units_h, most), per_v = (unsigned)std::min(units_v, most);
+                    hipLaunchKernelGGL(j2_dwt97_h, dim3((unsigned)(ntc * per_h)), dim3(128), 0, st, w.tiles, fa, fb, height, width, step, per_h);
+                    hipLaunchKernelGGL(j2_dwt97_v, dim3((unsigned)(ntc * per_v)), dim3(256), 0, st, w.tiles, fb, fa, height, width, step, per_v);
                 }
             }
             hipLaunchKernelGGL(j2_finish, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 2048), (unsigned)np), dim3(256), 0, st, w.pages, w.a, out_dev,

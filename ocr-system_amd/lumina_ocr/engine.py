@@ -89,6 +89,8 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_jp2_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_jp2_probe_irreversible": (i32, [vp, sz, vp]),
         "lumina_ocr_jp2_decode_irreversible": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+        "lumina_ocr_jp2_probe_ex": (i32, [vp, sz, c.c_uint, vp]),
+        "lumina_ocr_jp2_decode_ex": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, c.c_uint, vp]),
         "lumina_ocr_flate_image_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
         "lumina_ocr_ccitt_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
         "lumina_ocr_fax_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
@@ -150,7 +152,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_resize_lanczos", "lumina_ocr_enhance", "lumina_ocr_jpeg_encode", "lumina_ocr_jpeg_coefficients", "lumina_ocr_jpeg_probe", "lumina_ocr_jpeg_decode", "lumina_ocr_jpeg_decode_async", "lumina_ocr_jpeg_last_passes",
     "lumina_ocr_jpeg_probe_progressive", "lumina_ocr_jpeg_decode_progressive",
     "lumina_ocr_jp2_probe", "lumina_ocr_jp2_reason", "lumina_ocr_jp2_decode",
-    "lumina_ocr_jp2_probe_irreversible", "lumina_ocr_jp2_decode_irreversible",
+    "lumina_ocr_jp2_probe_irreversible", "lumina_ocr_jp2_decode_irreversible", "lumina_ocr_jp2_probe_ex", "lumina_ocr_jp2_decode_ex",
     "lumina_ocr_webp_probe", "lumina_ocr_webp_reason", "lumina_ocr_webp_decode",
     "lumina_ocr_png_probe", "lumina_ocr_png_decode", "lumina_ocr_flate_image_decode", "lumina_ocr_ccitt_decode", "lumina_ocr_fax_decode", "lumina_ocr_strip_image_decode",
     "lumina_ocr_jbig2_probe", "lumina_ocr_jbig2_reason", "lumina_ocr_jbig2_decode",
@@ -356,11 +358,21 @@ class Engine:
         bit-planes a sub-band: OpenJPEG's files of up to 5 levels) -> (rc, dict) as jp2_probe."""
         return Engine._jp2_probe(data, "lumina_ocr_jp2_probe_irreversible")
 
+    JP2_F_IRREVERSIBLE, JP2_F_TILES = 1, 2   # LUMINA_OCR_JP2_F_*
+
     @staticmethod
-    def _jp2_probe(data: bytes, entry: str):
+    def jp2_probe_ex(data: bytes, flags: int):
+        """Host only. jp2_probe with `flags` naming what is read beyond the first subset: JP2_F_IRREVERSIBLE (9/7 files) and
+        JP2_F_TILES (tiles, image and tile origins, user precincts) -> (rc, dict) as jp2_probe; with JP2_F_TILES width and height
+        are those of the image area."""
+        return Engine._jp2_probe(data, "lumina_ocr_jp2_probe_ex", int(flags))
+
+    @staticmethod
+    def _jp2_probe(data: bytes, entry: str, flags=None):
         lib = load_library()
         info = (ctypes.c_int * 8)()
-        rc = getattr(lib, entry)(ctypes.c_char_p(data), len(data), info)
+        args = (ctypes.c_char_p(data), len(data)) + (() if flags is None else (flags,)) + (info,)
+        rc = getattr(lib, entry)(*args)
         return rc, dict(width=info[0], height=info[1], components=info[2], levels=info[3], layers=info[4], progression=info[5],
                         codeblock_width=info[6], codeblock_height=info[7], reason=lib.lumina_ocr_jp2_reason(rc).decode() if rc else "")
 
@@ -375,7 +387,12 @@ class Engine:
         to Pillow; a 5/3 file gives the bytes of jp2_decode."""
         return self._jp2_decode(self.lib.lumina_ocr_jp2_decode_irreversible, files, height, width, out)
 
-    def _jp2_decode(self, entry, files, height: int, width: int, out):
+    def jp2_decode_ex(self, files, height: int, width: int, flags: int, out=None):
+        """jp2_decode with `flags` (JP2_F_IRREVERSIBLE | JP2_F_TILES): the same result and status codes, status 0 => byte-identical to
+        Pillow; height and width are those of the image area.  A file the other entries take gives their bytes."""
+        return self._jp2_decode(self.lib.lumina_ocr_jp2_decode_ex, files, height, width, out, int(flags))
+
+    def _jp2_decode(self, entry, files, height: int, width: int, out, flags=None):
         torch = _torch()
         n = len(files)
         if out is None:
@@ -384,7 +401,7 @@ class Engine:
         ptrs = (ctypes.c_char_p * n)(*files)
         sizes = (ctypes.c_size_t * n)(*[len(f) for f in files])
         status = (ctypes.c_int * n)()
-        self._chk(entry(self._h, ptrs, sizes, n, int(height), int(width), _ptr(out), status, self._stream()))
+        self._chk(entry(self._h, ptrs, sizes, n, int(height), int(width), _ptr(out), status, *(() if flags is None else (flags,)), self._stream()))
         return out, list(status)
 
     def _stream_batch(self, streams, height: int, width: int, out):

@@ -158,6 +158,11 @@ class OCRService:
         # practice) are decoded on the device as well (lumina_ocr_jp2_decode_irreversible), wherever a 5/3 file is.  Off by default, and
         # ignored without LUMINA_OCR_DEVICE_JP2: exactly the calls made without the option are made.
         self.jp2_irreversible = os.environ.get("LUMINA_OCR_JP2_IRREVERSIBLE", "0").lower() not in ("", "0", "false", "no")
+        # LUMINA_OCR_JP2_TILES=1: with LUMINA_OCR_DEVICE_JP2, tiled JPEG 2000 files (tiles, image and tile origins, user precincts: what
+        # scanners and Acrobat's scan profiles write) are decoded on the device as well (lumina_ocr_jp2_decode_ex), wherever a one-tile
+        # file is; it combines with LUMINA_OCR_JP2_IRREVERSIBLE.  Off by default, and ignored without LUMINA_OCR_DEVICE_JP2: exactly the
+        # calls made without the option are made.
+        self.jp2_tiles = os.environ.get("LUMINA_OCR_JP2_TILES", "0").lower() not in ("", "0", "false", "no")
         self._jp2_reasons_logged: set = set()
         self.apply_binarize = "adaptive" if b in ("1", "true", "yes", "adaptive") else ("simple" if b == "simple" else None)
         self._device = int(os.environ.get("LUMINA_OCR_DEVICE", os.environ.get("LOCAL_RANK", 0)))
@@ -641,7 +646,10 @@ class OCRService:
     def _jp2_probe(self, data: bytes, size) -> Optional[Dict[str, Any]]:
         """The probe's info when the device decodes this JPEG 2000 file and its size is `size`, else None, the reason logged once."""
         from ..engine import Engine
-        rc, info = Engine.jp2_probe_irreversible(data) if self.jp2_irreversible else Engine.jp2_probe(data)
+        if self.jp2_tiles:
+            rc, info = Engine.jp2_probe_ex(data, self._jp2_flags())
+        else:
+            rc, info = Engine.jp2_probe_irreversible(data) if self.jp2_irreversible else Engine.jp2_probe(data)
         if rc == 0 and (info["width"], info["height"]) == tuple(size):
             return info
         reason = info["reason"] if rc else "size differs from the opened image's"
@@ -650,7 +658,14 @@ class OCRService:
             logger.info("JPEG 2000 input left to Pillow (status %d): %s", rc, reason)
         return None
 
+    def _jp2_flags(self) -> int:
+        from ..engine import Engine
+        return Engine.JP2_F_TILES | (Engine.JP2_F_IRREVERSIBLE if self.jp2_irreversible else 0)
+
     def _jp2_decoder(self):
+        if self.jp2_tiles:
+            flags = self._jp2_flags()
+            return lambda files, height, width: self._engine.jp2_decode_ex(files, height, width, flags)
         return self._engine.jp2_decode_irreversible if self.jp2_irreversible else self._engine.jp2_decode
 
     def _decode_jp2_on_device(self, data: bytes, image: Image.Image):
@@ -1212,7 +1227,7 @@ class OCRService:
     # ---- status (:759-795) ----
     def get_status(self) -> Dict[str, Any]:
         st = {"client_initialized": self._pipeline is not None, "model_id": "dbnet-r18vd+crnn-mv3", "max_dimension": self.max_dimension,
-              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "aztec": self._use_aztec, "aztec_max_layers": self._aztec_max_layers_status(), "device_pdf": self.device_pdf, "pdf_layers": self.pdf_layers, "pdf_jbig2": self.pdf_jbig2, "progressive_jpeg": self.progressive_jpeg, "device_tiff": self.device_tiff, "device_jp2": self.device_jp2, "jp2_irreversible": self.jp2_irreversible, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
+              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "aztec": self._use_aztec, "aztec_max_layers": self._aztec_max_layers_status(), "device_pdf": self.device_pdf, "pdf_layers": self.pdf_layers, "pdf_jbig2": self.pdf_jbig2, "progressive_jpeg": self.progressive_jpeg, "device_tiff": self.device_tiff, "device_jp2": self.device_jp2, "jp2_irreversible": self.jp2_irreversible, "jp2_tiles": self.jp2_tiles, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
         if self._engine is not None:
             st["engine_version"] = self._engine.version()
             st["num_classes"] = self._engine.num_classes

@@ -15,7 +15,12 @@ threshold: the host decode is what each figure is compared with.
 and, through the same entry in the same run, the 5/3 `rgb_layers20` / `grey_layers20` files to set them beside.  It writes
 profiles/jp2_irreversible_probe.json; `--trace CASE` splits tier 1, the 9/7 lifting (j2_dwt97_h / j2_dwt97_v) and the finish.
 
-    python tools/jp2_probe.py [--irreversible] [--reps 20] [--pages 64] [--host-reps 3] [--cases ...] [--trace CASE]"""
+--tiles times lumina_ocr_jp2_decode_ex (both flags) on tiled files: `rgb_lossless` and `grey_layers20`, 5/3 and 9/7 (`rgb97_default`,
+`grey97_layers20`), each written with tile_size=(256, 256) (`..._t256`) and (1024, 1024) (`..._t1024`) and as a one-tile file
+(`..._one`), the yardstick: the three go through the same entry in the same run, their repetitions interleaved.  It writes
+profiles/jp2_tiles_probe.json; `--trace CASE` (for instance rgb_lossless_t256) splits tier 1, the transforms and the rest.
+
+    python tools/jp2_probe.py [--irreversible | --tiles] [--reps 20] [--pages 64] [--host-reps 3] [--cases ...] [--trace CASE]"""
 import argparse
 import io
 import json
@@ -34,6 +39,11 @@ CASES97 = {"rgb97_default": ("RGB", {"irreversible": True}), "grey97_default": (
            "rgb97_layers20": ("RGB", {"irreversible": True, "quality_layers": [20]}),
            "grey97_layers20": ("L", {"irreversible": True, "quality_layers": [20]}),
            "rgb_layers20": CASES["rgb_layers20"], "grey_layers20": CASES["grey_layers20"]}
+TILINGS = {"one": {}, "t256": {"tile_size": (256, 256)}, "t1024": {"tile_size": (1024, 1024)}}
+CASES_TILES = {f"{name}_{t}": (mode, dict(opts, **topts))
+               for name, (mode, opts) in (("rgb_lossless", CASES["rgb_lossless"]), ("grey_layers20", CASES["grey_layers20"]),
+                                          ("rgb97_default", CASES97["rgb97_default"]), ("grey97_layers20", CASES97["grey97_layers20"]))
+               for t, topts in TILINGS.items()}
 
 
 def main():
@@ -43,13 +53,14 @@ def main():
     ap.add_argument("--pages", type=int, default=64)
     ap.add_argument("--distinct", type=int, default=4)
     ap.add_argument("--irreversible", action="store_true")
+    ap.add_argument("--tiles", action="store_true")
     ap.add_argument("--cases", default="")
     ap.add_argument("--trace", default="")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
-    cases = CASES97 if args.irreversible else CASES
+    cases = CASES_TILES if args.tiles else CASES97 if args.irreversible else CASES
     args.cases = args.cases or ",".join(cases)
-    args.out = args.out or str(ROOT / "profiles" / ("jp2_irreversible_probe.json" if args.irreversible else "jp2_probe.json"))
+    args.out = args.out or str(ROOT / "profiles" / ("jp2_tiles_probe.json" if args.tiles else "jp2_irreversible_probe.json" if args.irreversible else "jp2_probe.json"))
     import numpy as np
     import torch
     from PIL import Image
@@ -59,6 +70,10 @@ def main():
     eng = Engine(0)
     decode = eng.jp2_decode_irreversible if args.irreversible else eng.jp2_decode
     probe = Engine.jp2_probe_irreversible if args.irreversible else Engine.jp2_probe
+    if args.tiles:
+        both = Engine.JP2_F_IRREVERSIBLE | Engine.JP2_F_TILES
+        decode = lambda files, h, w, out=None: eng.jp2_decode_ex(files, h, w, both, out=out)   # noqa: E731
+        probe = lambda data: Engine.jp2_probe_ex(data, both)                                    # noqa: E731
     src = [synth.synth_page(H, W, 100 + k, n_lines=40)[0] for k in range(args.distinct)]
 
     def write(mode, opts):
@@ -90,7 +105,38 @@ def main():
         return
 
     res = dict(pages=args.pages, height=H, width=W, distinct=args.distinct, reps=args.reps, host_reps=args.host_reps)
-    for name in args.cases.split(","):
+    if args.tiles:
+        # the tilings of one content side by side: a repetition is one call of each, in turn
+        names = args.cases.split(",")
+        for base in dict.fromkeys(n.rsplit("_", 1)[0] for n in names):
+            group = [n for n in names if n.rsplit("_", 1)[0] == base]
+            files = {n: write(*cases[n]) for n in group}
+            ref = {n: [np.asarray(Image.open(io.BytesIO(s)).convert("RGB")) for s in files[n]] for n in group}
+            for n in group:
+                t_tier2, probes = timed(lambda: [probe(s) for s in files[n]], args.host_reps, sync=False)
+                res[n] = dict(file_kb=round(sum(len(s) for s in files[n]) / len(files[n]) / 1024, 1), probe_status=[rc for rc, _ in probes],
+                              tier2_host_ms_per_page=round(t_tier2["median"] / len(files[n]), 3))
+            for label, npg in (("batch", args.pages), ("single", 1)):
+                out_buf = torch.empty((npg, H, W, 3), dtype=torch.uint8, device="cuda")
+                streams = {n: [files[n][i % len(files[n])] for i in range(npg)] for n in group}
+                times = {n: [] for n in group}
+                for i in range(args.reps + 1):
+                    for n in group:
+                        t0 = time.perf_counter()
+                        out, status = decode(streams[n], H, W, out=out_buf)
+                        torch.cuda.synchronize()
+                        if i:
+                            times[n].append((time.perf_counter() - t0) * 1e3)
+                        else:
+                            equal = all(status[k] == 0 and np.array_equal(out[k].cpu().numpy(), ref[n][k]) for k in range(min(npg, len(files[n]))))
+                            res[n][label] = dict(pages=npg, status_ok=status.count(0), equal_to_host=bool(equal))
+                for n in group:
+                    t = times[n]
+                    res[n][label]["device_ms"] = dict(median=round(float(np.median(t)), 2), min=round(min(t), 2), max=round(max(t), 2))
+                    res[n][label]["device_pages_per_s"] = round(npg / float(np.median(t)) * 1e3, 1)
+                    if base + "_one" in times:   # (the yardstick by name; absent when --cases leaves the one-tile file out)
+                        res[n][label]["vs_one_tile"] = round(float(np.median(t)) / float(np.median(times[base + "_one"])), 3)
+    for name in ([] if args.tiles else args.cases.split(",")):
         files = write(*cases[name])
         t_host, ref = timed(lambda: [np.asarray(Image.open(io.BytesIO(s)).convert("RGB")) for s in files], args.host_reps, sync=False)
         t_tier2, probes = timed(lambda: [probe(s) for s in files], args.host_reps, sync=False)
