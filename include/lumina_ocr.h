@@ -587,6 +587,28 @@ const char* lumina_ocr_webp_reason(int code);
 int lumina_ocr_webp_decode(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev,
                            int* status, void* stream);
 
+/* Lossy WebP (VP8 key frames) on the device, in one batch with lossless files.  The contract is the same: status 0 => byte-identical to
+ * Pillow's Image.open(f).convert('RGB'); any other status => the file is left to Pillow.  lumina_ocr_webp_probe / _decode above keep
+ * answering -2 for a lossy file.
+ * lumina_ocr_webp_probe_lossy (host only, no handle): as lumina_ocr_webp_probe, with the same info fields, and 0 also for a still lossy
+ * file: RIFF / WEBP with one `VP8 ` chunk, bare or inside VP8X, without ALPH; a key frame of profile 0..3 with show_frame 1 and start
+ * code 9d 01 2a, any size up to 16383 x 16383 and 2^26 pixels (the scale bits are ignored, as libwebp ignores them); segments, both loop
+ * filters, 1 / 2 / 4 / 8 token partitions.  info[6] = 1 for a lossy file, info[7] = its number of token partitions.  It reads the
+ * frame header (a few hundred boolean-coded flags), no macroblock.  -2: a lossy file with an ALPH chunk, animation, more than 2^26
+ * pixels, a chunk of 256 MB or more.  -1: the container cases; a VP8X canvas that differs from the frame header; both a VP8 and a VP8L
+ * chunk; an inter frame; a profile above 3; show_frame 0; a wrong start code; a first-partition length, a partition-size table or a
+ * partition past the chunk; an empty last partition; a frame header that reads past the first partition.
+ * lumina_ocr_webp_reason serves both probes.
+ * lumina_ocr_webp_decode_lossy: arguments and statuses as lumina_ocr_webp_decode; lossless files take its kernels and give its bytes.
+ * -1 from the decode also covers: a read of the first partition or of a token partition past its end (a decision of the boolean decoder
+ * that needs a byte the partition does not have: libwebp pads a truncated token partition with zeros, a strict reader need not), and a
+ * block beyond the coefficient bound inside which no inverse transform leaves 16 bits (libwebp's C and SIMD paths differ beyond it): the
+ * sum of the absolute values of a block's 16 dequantised coefficients above 19000, or of a macroblock's 16 Y2 values above 32764 (derived
+ * in csrc/vp8_dec.h).  Sub-batched by "webp_sub_batch_mb"; synchronises `stream`. */
+int lumina_ocr_webp_probe_lossy(const uint8_t* file, size_t size, int info[8]);
+int lumina_ocr_webp_decode_lossy(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width,
+                                 uint8_t* out_dev, int* status, void* stream);
+
 /* JPEG 2000 decode on the device — the pixel work of the reference's Image.open(...) + convert('RGB') for .jp2 / .j2k inputs, and the
  * /JPXDecode pages of scanned PDFs.  The contract is the JPEG pair's: status 0 => byte-identical to Pillow's (OpenJPEG's) decode; any
  * other status => the file is left to Pillow.

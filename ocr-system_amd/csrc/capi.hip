@@ -22,6 +22,7 @@
 #include "lzw.h"
 #include "jp2dec.h"
 #include "pngdec.h"
+#include "vp8dec.h"
 #include "webpdec.h"
 #include "webp_parse.h"
 #include "ccitt.h"
@@ -579,6 +580,23 @@ int lumina_ocr_webp_decode(lumina_ocr_t* h, const uint8_t* const* files, const s
     BIND(h);
     API_TRY
     return webpdec_run(h, files, sizes, n, height, width, out_dev, status, (hipStream_t)stream);
+    API_CATCH(h)
+}
+
+int lumina_ocr_webp_probe_lossy(const uint8_t* file, size_t size, int info[8]) {
+    if (!file || !info) return -1;
+    const char* reason = "";
+    const int rc = vp8dec_probe(file, size, info, &reason);
+    webp_last_code = rc; webp_last_reason = reason;
+    return rc;
+}
+
+int lumina_ocr_webp_decode_lossy(lumina_ocr_t* h, const uint8_t* const* files, const size_t* sizes, int n, int height, int width, uint8_t* out_dev,
+                                 int* status, void* stream) {
+    if (!h || !files || !sizes || !out_dev || !status || n <= 0 || height <= 0 || width <= 0) return locr_fail(h, "webp_decode_lossy", "bad arguments");
+    BIND(h);
+    API_TRY
+    return vp8dec_run(h, files, sizes, n, height, width, out_dev, status, (hipStream_t)stream);
     API_CATCH(h)
 }
 

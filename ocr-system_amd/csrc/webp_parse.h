@@ -16,9 +16,11 @@
 
 constexpr long long WP_MAX_PIXELS = 1ll << 26;   // 8192 x 8192; the longest lines (16384 x 1, 1 x 16384) are far inside
 constexpr size_t WP_MAX_CHUNK = (size_t)1 << 28;  // bit positions stay inside 32 bits
+constexpr char WP_REASON_LOSSY[] = "lossy WebP (VP8)";
 
 struct WpInfo {
     int width, height, alpha, vp8x, exif, xmp;
+    int lossy;              // status -2 for no other reason than the lossy format (a `VP8 ` chunk): vp8_parse.h takes such a file over
     size_t off, len;        // the VP8L payload in the file (status 0 only)
     const char* reason;     // "" for status 0
 };
@@ -67,7 +69,7 @@ inline int webp_probe(const uint8_t* f, size_t n, WpInfo* I) {
             if (memcmp(tag, "VP8L", 4) == 0) {
                 if (have) return fail(-1, "second VP8L chunk");
                 have = true; I->off = p + 8; I->len = size;
-            } else if (memcmp(tag, "VP8 ", 4) == 0) { if (!refused) refused = "lossy WebP (VP8)"; }
+            } else if (memcmp(tag, "VP8 ", 4) == 0) { if (!refused) refused = WP_REASON_LOSSY; }
             else if (memcmp(tag, "ALPH", 4) == 0) { if (!refused) refused = "lossy WebP with an ALPH chunk"; }
             else if (memcmp(tag, "ANIM", 4) == 0 || memcmp(tag, "ANMF", 4) == 0) { if (!refused) refused = "animated WebP"; }
             else if (memcmp(tag, "EXIF", 4) == 0) I->exif = 1;
@@ -79,11 +81,12 @@ inline int webp_probe(const uint8_t* f, size_t n, WpInfo* I) {
         have = true; I->off = off0; I->len = size0;
     } else if (memcmp(tag0, "VP8 ", 4) == 0) {
         if (nchunks != 1) return fail(-1, "chunks after the image of a file without VP8X");
-        return fail(-2, "lossy WebP (VP8)");
+        I->lossy = 1;
+        return fail(-2, WP_REASON_LOSSY);
     } else {
         return fail(-1, "first chunk is neither VP8X, VP8L nor VP8");
     }
-    if (refused) { I->off = I->len = 0; return fail(-2, refused); }
+    if (refused) { I->off = I->len = 0; I->lossy = refused == WP_REASON_LOSSY; return fail(-2, refused); }
     if (!have) return fail(-1, "no image chunk");
     const uint8_t* s = f + I->off;
     if (I->len < 5 || s[0] != 0x2F) { I->off = I->len = 0; return fail(-1, "VP8L signature byte is not 0x2F"); }

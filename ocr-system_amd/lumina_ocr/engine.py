@@ -84,6 +84,8 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_webp_probe": (i32, [vp, sz, vp]),
         "lumina_ocr_webp_reason": (c.c_char_p, [i32]),
         "lumina_ocr_webp_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+        "lumina_ocr_webp_probe_lossy": (i32, [vp, sz, vp]),
+        "lumina_ocr_webp_decode_lossy": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "lumina_ocr_jp2_probe": (i32, [vp, sz, vp]),
         "lumina_ocr_jp2_reason": (c.c_char_p, [i32]),
         "lumina_ocr_jp2_decode": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
@@ -153,7 +155,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_jpeg_probe_progressive", "lumina_ocr_jpeg_decode_progressive",
     "lumina_ocr_jp2_probe", "lumina_ocr_jp2_reason", "lumina_ocr_jp2_decode",
     "lumina_ocr_jp2_probe_irreversible", "lumina_ocr_jp2_decode_irreversible", "lumina_ocr_jp2_probe_ex", "lumina_ocr_jp2_decode_ex",
-    "lumina_ocr_webp_probe", "lumina_ocr_webp_reason", "lumina_ocr_webp_decode",
+    "lumina_ocr_webp_probe", "lumina_ocr_webp_reason", "lumina_ocr_webp_decode", "lumina_ocr_webp_probe_lossy", "lumina_ocr_webp_decode_lossy",
     "lumina_ocr_png_probe", "lumina_ocr_png_decode", "lumina_ocr_flate_image_decode", "lumina_ocr_ccitt_decode", "lumina_ocr_fax_decode", "lumina_ocr_strip_image_decode",
     "lumina_ocr_jbig2_probe", "lumina_ocr_jbig2_reason", "lumina_ocr_jbig2_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
@@ -340,6 +342,32 @@ class Engine:
         sizes = (ctypes.c_size_t * n)(*[len(f) for f in files])
         status = (ctypes.c_int * n)()
         self._chk(self.lib.lumina_ocr_webp_decode(self._h, ptrs, sizes, n, int(height), int(width), _ptr(out), status, self._stream()))
+        return out, list(status)
+
+    @staticmethod
+    def webp_probe_lossy(data: bytes):
+        """Host only, as webp_probe, and rc 0 also for a still lossy file (one `VP8 ` chunk without ALPH, a key frame): the chunk headers
+        and the boolean-coded frame header, no macroblock. -> (rc, dict(width, height, alpha, vp8x, exif, xmp, lossy, partitions,
+        reason)); -2: lossy with ALPH, animated, more than 2^26 pixels; -1: corrupt or irregular."""
+        lib = load_library()
+        info = (ctypes.c_int * 8)()
+        data = data if isinstance(data, bytes) else bytes(data)
+        rc = lib.lumina_ocr_webp_probe_lossy(ctypes.c_char_p(data), len(data), info)
+        return rc, dict(width=info[0], height=info[1], alpha=info[2], vp8x=info[3], exif=info[4], xmp=info[5], lossy=info[6],
+                        partitions=info[7], reason=lib.lumina_ocr_webp_reason(rc).decode() if rc else "")
+
+    def webp_decode_lossy(self, files, height: int, width: int, out=None):
+        """WebP file images, lossy (VP8 key frames) and lossless in one batch (a sequence of bytes objects, all height x width) ->
+        (uint8 [n,H,W,3] device, status list), byte-identical to Pillow's Image.open(...).convert('RGB').  The lossless files give
+        webp_decode's bytes.  status[i] != 0: page i was not decoded (-1 corrupt, -2 not read by the device, -4 another size)."""
+        torch = _torch()
+        n = len(files)
+        if out is None:
+            out = torch.empty((n, height, width, 3), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        ptrs = (ctypes.c_char_p * n)(*files)
+        sizes = (ctypes.c_size_t * n)(*[len(f) for f in files])
+        status = (ctypes.c_int * n)()
+        self._chk(self.lib.lumina_ocr_webp_decode_lossy(self._h, ptrs, sizes, n, int(height), int(width), _ptr(out), status, self._stream()))
         return out, list(status)
 
     JP2_ORDERS = ("LRCP", "RLCP", "RPCL", "PCRL", "CPRL")

@@ -131,6 +131,10 @@ class OCRService:
         # the calls made without the option are made (the measurements are in DESIGN.md §8.3)
         self.device_webp = os.environ.get("LUMINA_OCR_DEVICE_WEBP", "0").lower() not in ("", "0", "false", "no")
         self._webp_reasons_logged = set()
+        # LUMINA_OCR_WEBP_LOSSY=1 (takes effect only together with LUMINA_OCR_DEVICE_WEBP, ignored without it): lossy WebP files (one VP8
+        # key frame without ALPH) are decoded on the device as well; the provider then calls lumina_ocr_webp_probe_lossy /
+        # _decode_lossy for every WebP input, lossless ones included.  Off by default.
+        self.webp_lossy = os.environ.get("LUMINA_OCR_WEBP_LOSSY", "0").lower() not in ("", "0", "false", "no")
         # LUMINA_OCR_PDF_SCANS=1: a PDF page that is one image over the whole MediaBox (a scan: DCT, Flate or CCITT of any /K) is decoded
         # on the device from its embedded stream, at the image's own sample grid, instead of being rasterised by pdf2image / poppler; other
         # pages still go to pdf_to_images.  Off by default: process_pdf_sync is then the rasterise-and-batch path alone.
@@ -589,8 +593,8 @@ class OCRService:
         return head[:4] == b"RIFF" and head[8:12] == b"WEBP"
 
     def _decode_webp_on_device(self, data: bytes, image: Image.Image):
-        """A lossless WebP file the device reads -> device tensor [1,H,W,3] with the EXIF orientation applied (lumina_ocr_webp_decode:
-        byte-identical to Pillow), or None: Pillow decodes.  `image` is the lazily opened file (nothing decoded yet): its info carries
+        """A WebP file the device reads (lossless; lossy as well with webp_lossy) -> device tensor [1,H,W,3] with the EXIF orientation
+        applied (lumina_ocr_webp_decode / _decode_lossy: byte-identical to Pillow), or None: Pillow decodes.  `image` is the lazily opened file (nothing decoded yet): its info carries
         the EXIF chunk, read here as _png_orientation reads a PNG's; a file with XMP is left to the host path and its auto_orient."""
         try:
             if image.format != "WEBP" or "xmp" in image.info or "XML:com.adobe.xmp" in image.info:
@@ -600,7 +604,7 @@ class OCRService:
                 return None
             self._ensure_engine()   # (before the probe loads the engine library: see _decode_png_on_device)
             from ..engine import Engine
-            rc, info = Engine.webp_probe(data)
+            rc, info = Engine.webp_probe_lossy(data) if self.webp_lossy else Engine.webp_probe(data)
             if rc != 0 or info["xmp"] or (info["width"], info["height"]) != image.size:
                 reason = info["reason"] if rc else "XMP chunk, or a size that differs from the opened image's"
                 if reason not in self._webp_reasons_logged:
@@ -608,7 +612,8 @@ class OCRService:
                     logger.info("WebP input left to Pillow (status %d): %s", rc, reason)
                 return None
             with self._device_ctx():
-                out, status = self._engine.webp_decode([data], info["height"], info["width"])
+                decode = self._engine.webp_decode_lossy if self.webp_lossy else self._engine.webp_decode
+                out, status = decode([data], info["height"], info["width"])
                 if status != [0]:
                     return None
                 return self._engine.exif_transpose(out, orientation)     # auto_orient (image_preprocessing.py:213), on the device as well
