@@ -166,6 +166,10 @@ int lumina_ocr_set_option(lumina_ocr_t* h, const char* key, int value) {
     else if (!strcmp(key, "time_convs")) h->time_convs = value != 0;
     else if (!strcmp(key, "fuse_head")) h->fuse_head = value != 0;
     else if (!strcmp(key, "fuse_mb")) h->fuse_mb = value != 0;
+    else if (!strcmp(key, "fuse_xproj")) h->fuse_xproj = value != 0;
+    else if (!strcmp(key, "fuse_conv2_pool")) h->fuse_conv2_pool = value != 0;
+    else if (!strcmp(key, "lstm_waves")) h->lstm_waves = value == 3 ? 3 : 12;
+    else if (!strcmp(key, "seq_gemm_min")) h->seq_gemm_min = value >= 0 ? value : 128;
     else if (!strcmp(key, "fuse_pool")) h->fuse_pool = value != 0;
     else if (!strcmp(key, "fuse_stem")) h->fuse_stem = value != 0;
     else if (!strcmp(key, "fpn_multi")) h->fpn_multi = value != 0;

@@ -118,6 +118,7 @@ struct lumina_ocr {
     std::vector<RecBlock> rblocks;
     ConvLayer rconv2, xproj[2];
     bf16_t* whh[2] = {nullptr, nullptr};
+    bf16_t *xproj_spk[2] = {nullptr, nullptr}, *rconv2_spk = nullptr;  // the same weights in seq_gemm's tile order (bias: the layers' own)
     bf16_t* ctc_wpk = nullptr; float* ctc_bias = nullptr;
     SvtrModel svtr;
     // ---- orientation classifier (PP-OCR cls: MobileNetV3-small x0.35 on 48 x 192 crops, FC 200 -> 2) ----
@@ -148,6 +149,14 @@ struct lumina_ocr {
     bool fpn_multi = true;  // head.conv1 reads p5 / p4 / p3 / p2 at their own resolution (ring kernel): the FPN concat is never written
     bool fuse_stem = true;  // stem.conv1 + stem.conv2 in one kernel (the first 32-channel tensor stays in LDS)
     bool fuse_mb = true;    // recogniser blocks: expand + depthwise in one kernel (the expanded tensor stays in LDS)
+    bool fuse_xproj = true;       // LSTM x-projections on the A-stationary streaming GEMM (seq_gemm.h)
+    bool fuse_conv2_pool = true;  // rec.conv2 + rec.pool in one seq_gemm launch (the [N,2,160,288] tensor is never written)
+    int lstm_waves = 12;          // waves per work-group of the LSTM recurrence: 12, or 3 (the earlier kernel)
+    // seq_gemm only once a sub-batch gives at least this many of its 128-row work-groups (as conv_big_min): a work-group walks all
+    // column tiles one after the other, so row tiles are its only parallelism, and with few of them the tile-parallel kernels, which
+    // spread 5 to 12 times as many work-groups over the chip, are faster (measured, both x-projections: 29 to 39 us against 44 to 47 at 4 to 82
+    // work-groups, 62 against 49 us at 163)
+    int seq_gemm_min = 128;
     // per-kernel event timing (bench roofline): the launches of the last det forward
     bool time_convs = false;
     std::vector<LaunchRecord> launches;

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "ops.h"
+#include "seq_gemm.h"
 #include "stem_conv.h"
 
 int locr_fail(lumina_ocr* eng, const char* what, const char* detail) {
@@ -723,6 +724,13 @@ int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n) {
     if (load_mv3_blocks(eng, m, "rec", scale, sh, c0, &eng->rblocks)) return 1;
     const int cin = eng->rblocks.back().cout;
     if (!make_conv(eng, m, "rec.conv2", 1, 1, cin, 288, cp16(cin), 288, ACT_HSWISH, &eng->rconv2)) return 1;
+    eng->rconv2_spk = nullptr;
+    if (cin == 48) {   // the same weights once more, in seq_gemm's tile order (conv2 + pool in one launch)
+        std::vector<bf16_t> spk(seq_gemm_packed_elems(288, cin));
+        seq_gemm_pack_weights(reinterpret_cast<const bf16_t*>(m.find("rec.conv2.w")->second.data), 288, cin, spk.data());
+        eng->rconv2_spk = static_cast<bf16_t*>(eng_upload(eng, spk.data(), spk.size() * sizeof(bf16_t)));
+        if (!eng->rconv2_spk) return locr_fail(eng, "upload", "rec.conv2 (seq_gemm)");
+    }
     // LSTM: x-projection of both directions as one GEMM; recurrent weights [2][4H][H]
     const int Hh = 96;
     for (int l = 0; l < 2; ++l) {
@@ -742,6 +750,12 @@ int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n) {
         mm["x.b"] = HostBlobTensor{0, {8 * Hh}, bcat.data(), bcat.size()};
         if (!make_conv(eng, mm, "x", 1, 1, din, 8 * Hh, din, 8 * Hh, ACT_NONE, &eng->xproj[l])) return 1;
         eng->xproj[l].name = "lstm.l" + std::to_string(l) + ".xproj";
+        {   // and in seq_gemm's tile order
+            std::vector<bf16_t> spk(seq_gemm_packed_elems(8 * Hh, din));
+            seq_gemm_pack_weights(reinterpret_cast<const bf16_t*>(wcat.data()), 8 * Hh, din, spk.data());
+            eng->xproj_spk[l] = static_cast<bf16_t*>(eng_upload(eng, spk.data(), spk.size() * sizeof(bf16_t)));
+            if (!eng->xproj_spk[l]) return locr_fail(eng, "upload", "xproj (seq_gemm)");
+        }
         std::vector<uint8_t> hcat(hf->second.nbytes + hb->second.nbytes);
         memcpy(hcat.data(), hf->second.data, hf->second.nbytes); memcpy(hcat.data() + hf->second.nbytes, hb->second.data, hb->second.nbytes);
         eng->whh[l] = static_cast<bf16_t*>(eng_upload(eng, hcat.data(), hcat.size()));
@@ -808,19 +822,42 @@ static int rec_forward_sub(lumina_ocr* eng, const uint8_t* crops, const int* wid
     RUN(run_stem(eng, "rec.conv1", crops, widths, N, 32, 320, eng->rstem_wpk, eng->rstem_bias, ACT_HSWISH, STEM_SCALE_PM1, STEM_SHIFT_PM1, x, st));
     tap(eng, "rec.conv1", x);
     for (size_t bi = 0; bi < eng->rblocks.size(); ++bi) RUN(run_mv3_block(eng, eng->rblocks[bi], "rec.b" + std::to_string(bi), &x, st));
-    Tensor4 f = ws_tensor(eng, N, x.h, x.w, 288);
-    RUN(eng_run_conv(eng, eng->rconv2, x, &f, st, ConvCall().flat_gemm())); tap(eng, "rec.conv2", f);
+    // one seq_gemm launch (timed as `layer`) in place of a 1x1 conv [+ 2x2 pool]; the bias is the conv layer's own (64-column tiles)
+    auto seq_gemm = [&](const char* layer, const ConvLayer& L, const bf16_t* spk, const Tensor4& in, Tensor4& out, int epi) -> int {
+        SeqGemmParams sp{};
+        sp.x = in.p; sp.wpk = spk; sp.bias = L.bias; sp.y = out.p;
+        sp.M = N * T; sp.K = in.c; sp.Cout = out.c; sp.T = T; sp.epi = epi;
+        if (dry) return 0;
+        LaunchTimer tm(eng, st);
+        LAUNCH(layer, seq_gemm_launch(sp, st));
+        const double px = (double)N * in.h * in.w;
+        tm.done(layer, seq_gemm_kernel_name(sp), 2.0 * px * in.c * out.c, 2.0 * (px * in.c + (double)sp.M * out.c + (double)in.c * out.c));
+        return 0;
+    };
+    const bool seq_fills = (N * T + 127) / 128 >= eng->seq_gemm_min;   // enough row tiles for the A-stationary kernel (engine.h)
+    const bool pool_fused = seq_fills && eng->fuse_conv2_pool && eng->keep_taps != 1 && eng->rconv2_spk != nullptr && eng->rconv2.cfg.bn == 64 &&
+                            x.h == 2 && x.w == 2 * T && x.c == 48;
+    Tensor4 f{};
+    if (!pool_fused || dry) f = ws_tensor(eng, N, x.h, x.w, 288);   // (dry run sizes the arena for the unfused path too)
     Tensor4 seq = ws_tensor(eng, N, 1, T, 288);
-    LAUNCH("rec.pool", maxpool_launch(f.p, seq.p, N, f.h, f.w, 288, 2, 2, 0, 1, T, st));
+    if (pool_fused) {
+        RUN(seq_gemm("rec.conv2+pool", eng->rconv2, eng->rconv2_spk, x, seq, SEQ_POOL4));
+    } else {
+        RUN(eng_run_conv(eng, eng->rconv2, x, &f, st, ConvCall().flat_gemm())); tap(eng, "rec.conv2", f);
+        LAUNCH("rec.pool", maxpool_launch(f.p, seq.p, N, f.h, f.w, 288, 2, 2, 0, 1, T, st));
+    }
     tap(eng, "rec.feat", seq);
     for (int l = 0; l < 2; ++l) {
         Tensor4 xp = ws_tensor(eng, N, 1, T, 8 * 96);
-        RUN(eng_run_conv(eng, eng->xproj[l], seq, &xp, st, ConvCall().flat_gemm()));
+        if (seq_fills && eng->fuse_xproj && eng->xproj_spk[l] != nullptr && eng->xproj[l].cfg.bn == 64 && (seq.c == 288 || seq.c == 192))
+            RUN(seq_gemm(eng->xproj[l].name.c_str(), eng->xproj[l], eng->xproj_spk[l], seq, xp, SEQ_STORE));
+        else
+            RUN(eng_run_conv(eng, eng->xproj[l], seq, &xp, st, ConvCall().flat_gemm()));
         Tensor4 hs = ws_tensor(eng, N, 1, T, 2 * 96);
         {
             LaunchTimer tm(eng, st, !dry);
-            LAUNCH("lstm", lstm_recurrent_launch(xp.p, eng->whh[l], hs.p, N, T, st));
-            tm.done("lstm.l" + std::to_string(l), "lstm_kernel", 2.0 * N * T * 2 * 96 * 384, 2.0 * N * T * (768 + 192));
+            LAUNCH("lstm", lstm_recurrent_launch(xp.p, eng->whh[l], hs.p, N, T, st, eng->lstm_waves));
+            tm.done("lstm.l" + std::to_string(l), eng->lstm_waves == 3 ? "lstm3_kernel" : "lstm_kernel", 2.0 * N * T * 2 * 96 * 384, 2.0 * N * T * (768 + 192));
         }
         tap(eng, l == 0 ? "lstm.l0" : "lstm.l1", hs);
         seq = hs;

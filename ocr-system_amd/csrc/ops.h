@@ -18,8 +18,9 @@ hipError_t se_fc_launch(const float* pool, int strips, const bf16_t* w1, const f
 hipError_t se_scale_launch(const bf16_t* x, const bf16_t* gate, bf16_t* y, int N, int HW, int C, hipStream_t st);
 
 // LSTM recurrence for one layer, both directions. xproj: [N][T][2*4H] bf16 (fw gates then bw gates, bias included),
-// whh: [2][4H][H] bf16, out: [N][T][2H] bf16 (fw | bw). H == 96.
-hipError_t lstm_recurrent_launch(const bf16_t* xproj, const bf16_t* whh, bf16_t* out, int N, int T, hipStream_t st);
+// whh: [2][4H][H] bf16, out: [N][T][2H] bf16 (fw | bw). H == 96.  waves: 12 (a wave per 8 hidden units) or 3 (the earlier kernel, a wave
+// per 32 units); both give the same bits.
+hipError_t lstm_recurrent_launch(const bf16_t* xproj, const bf16_t* whh, bf16_t* out, int N, int T, hipStream_t st, int waves = 12);
 
 // CTC head: logits = seq[M][K] * W^T[K][C] + b, never materialised; per row -> argmax index + softmax max-prob.
 // wpk: weights packed [ntile of 64 classes][plane][64 rows][8] (pack_ctc_weights).

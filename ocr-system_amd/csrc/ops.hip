@@ -167,7 +167,7 @@ __global__ void se_scale_kernel(const bf16_t* x, const bf16_t* gate, bf16_t* y, 
 }
 
 // ------------------------------------------------------------------ LSTM recurrence on the matrix cores
-// One workgroup = 32 sequences x one direction, 3 waves; wave u owns hidden units [32u, 32u+32).  Per time step
+// The three-wave kernel (option lstm_waves = 3, kept for comparison).  One workgroup = 32 sequences x one direction, 3 waves; wave u owns hidden units [32u, 32u+32).  Per time step
 //   gates[4][32 units][32 seqs] = W_hh (A operand, resident in registers for all 80 steps) * h_{t-1} (B operand, LDS)
 // with the accumulators initialised from the stored x-projection.  The four gate tiles of a (unit, sequence) pair
 // land in the same lane / register slot, so the cell update is register-local; h_t goes to LDS (next step's operand)
@@ -177,7 +177,7 @@ constexpr int LH = 96, LSEQ = 32, LPITCH = 208;  // bytes per sequence row of th
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
 __device__ __forceinline__ float fast_tanh(float x) { return 2.f * fast_sigmoid(2.f * x) - 1.f; }
 
-__global__ __launch_bounds__(192) void lstm_kernel(const bf16_t* xproj, const bf16_t* whh, bf16_t* out, int N, int T) {
+__global__ __launch_bounds__(192) void lstm3_kernel(const bf16_t* xproj, const bf16_t* whh, bf16_t* out, int N, int T) {
     __shared__ __attribute__((aligned(16))) unsigned char hbuf[2][LSEQ * LPITCH];
     const int tid = threadIdx.x, lane = tid & 63, u = tid >> 6, r = lane & 31, h = lane >> 5;
     const int dir = blockIdx.x & 1, n0 = (blockIdx.x >> 1) * LSEQ;
@@ -246,6 +246,71 @@ __global__ __launch_bounds__(192) void lstm_kernel(const bf16_t* xproj, const bf
             *reinterpret_cast<uint2*>(&hbuf[cur ^ 1][r * LPITCH + (32 * u + 8 * q + 4 * h) * 2]) = o;
             if (valid) *reinterpret_cast<uint2*>(orow + 8 * q) = o;
         }
+        __syncthreads();
+        cur ^= 1;
+    }
+}
+
+// The same recurrence on twelve waves (the default).  Wave w owns hidden
+// units [8w, 8w+8) and runs ONE 32x32 tile per step whose A rows are ordered row = 8 * gate + unit_local: with the 32x32x16 output
+// layout (accumulator entry 4q + e is row 8q + 4h + e) a lane holds gates q = 0..3 of units 8w + 4h + e, e = 0..3, of its sequence, so
+// the cell update stays register-local on four (unit, sequence) pairs per lane instead of sixteen.  Six MFMAs per wave and step instead
+// of 24 (the same total), and the gate arithmetic (ten transcendentals per pair, the critical path) spreads over all four SIMDs with
+// three waves each.  Per element nothing changes: accumulator initialised from the bf16 x-projection, six k steps ascending, the same
+// gate expressions, c in fp32, h rounded to bf16.
+__global__ __launch_bounds__(768) void lstm_kernel(const bf16_t* xproj, const bf16_t* whh, bf16_t* out, int N, int T) {
+    __shared__ __attribute__((aligned(16))) unsigned char hbuf[2][LSEQ * LPITCH];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
+    const int dir = blockIdx.x & 1, n0 = (blockIdx.x >> 1) * LSEQ;
+    const int seq = n0 + r;
+    const bool valid = seq < N;
+    const int sq = valid ? seq : N - 1;  // clamp loads of the ragged last group
+    bf16x8_t afr[6];   // A row r of this wave's tile: w_hh row gate * 96 + 8w + (r & 7), gate = r >> 3
+#pragma unroll
+    for (int ks = 0; ks < 6; ++ks)
+        afr[ks] = *reinterpret_cast<const bf16x8_t*>(whh + ((size_t)dir * 4 * LH + (r >> 3) * LH + 8 * w + (r & 7)) * LH + ks * 16 + h * 8);
+    for (int i = tid; i < 2 * LSEQ * LPITCH / 16; i += 768) reinterpret_cast<uint4*>(&hbuf[0][0])[i] = make_uint4(0, 0, 0, 0);
+    float c[4] = {0.f, 0.f, 0.f, 0.f};
+    const size_t xrow = (size_t)sq * T;
+    const int xcol = dir * 4 * LH + 8 * w + 4 * h;
+    uint2 xq[4];
+    {
+        const int t = dir ? T - 1 : 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) xq[q] = *reinterpret_cast<const uint2*>(xproj + (xrow + t) * (8 * LH) + xcol + q * LH);
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int step = 0; step < T; ++step) {
+        const int t = dir ? (T - 1 - step) : step;
+        f32x16_t acc;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            acc[4 * q + 0] = __uint_as_float(xq[q].x << 16); acc[4 * q + 1] = __uint_as_float(xq[q].x & 0xFFFF0000u);
+            acc[4 * q + 2] = __uint_as_float(xq[q].y << 16); acc[4 * q + 3] = __uint_as_float(xq[q].y & 0xFFFF0000u);
+        }
+        if (step + 1 < T) {  // prefetch the next step's x-projection under this step's MFMAs
+            const int tn = dir ? (t - 1) : (t + 1);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) xq[q] = *reinterpret_cast<const uint2*>(xproj + (xrow + tn) * (8 * LH) + xcol + q * LH);
+        }
+#pragma unroll
+        for (int ks = 0; ks < 6; ++ks) {
+            const bf16x8_t bfr = *reinterpret_cast<const bf16x8_t*>(&hbuf[cur][r * LPITCH + (ks * 16 + h * 8) * 2]);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[ks], bfr, acc, 0, 0, 0);
+        }
+        float hn[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float ig = fast_sigmoid(acc[e]), fg = fast_sigmoid(acc[4 + e]), gg = fast_tanh(acc[8 + e]), og = fast_sigmoid(acc[12 + e]);
+            c[e] = fg * c[e] + ig * gg;
+            hn[e] = og * fast_tanh(c[e]);
+        }
+        uint2 o;
+        o.x = pack_bf16x2(hn[0], hn[1]);
+        o.y = pack_bf16x2(hn[2], hn[3]);
+        *reinterpret_cast<uint2*>(&hbuf[cur ^ 1][r * LPITCH + (8 * w + 4 * h) * 2]) = o;
+        if (valid) *reinterpret_cast<uint2*>(out + ((size_t)sq * T + t) * (2 * LH) + dir * LH + 8 * w + 4 * h) = o;
         __syncthreads();
         cur ^= 1;
     }
@@ -600,8 +665,11 @@ hipError_t se_scale_launch(const bf16_t* x, const bf16_t* gate, bf16_t* y, int N
     return hipGetLastError();
 }
 
-hipError_t lstm_recurrent_launch(const bf16_t* xproj, const bf16_t* whh, bf16_t* out, int N, int T, hipStream_t st) {
-    hipLaunchKernelGGL(lstm_kernel, dim3(((N + LSEQ - 1) / LSEQ) * 2), dim3(192), 0, st, xproj, whh, out, N, T);
+hipError_t lstm_recurrent_launch(const bf16_t* xproj, const bf16_t* whh, bf16_t* out, int N, int T, hipStream_t st, int waves) {
+    if (N < 1 || T < 1 || (waves != 3 && waves != 12)) return hipErrorInvalidValue;
+    const dim3 grid(((N + LSEQ - 1) / LSEQ) * 2);
+    if (waves == 3) hipLaunchKernelGGL(lstm3_kernel, grid, dim3(192), 0, st, xproj, whh, out, N, T);
+    else hipLaunchKernelGGL(lstm_kernel, grid, dim3(768), 0, st, xproj, whh, out, N, T);
     return hipGetLastError();
 }
 
