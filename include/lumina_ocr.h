@@ -365,13 +365,38 @@ int lumina_ocr_qrcodes_versions(lumina_ocr_t* h, const uint8_t* pages_dev, int n
  * = the true number (a list whose count exceeds max_codes is not written); candidate_counts_dev: optional, int32 [n] = the candidates
  * of each page (a page with more than max_candidates is not read: its count is 0).  mask_in_dev / mask_out_dev as in
  * lumina_ocr_barcodes.  1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= timing_max, solid_max <= 128, max_candidates 1..1024,
- * max_codes 1..64, sides 1..65535; defaults in lumina_ocr/arch.py DM_PARAMS.  Not read: 64 x 64 and larger, ECC 000-140,
+ * max_codes 1..64, sides 1..65535; defaults in lumina_ocr/arch.py DM_PARAMS.  Not read: 64 x 64 and larger (lumina_ocr_datamatrix_sizes below reads them), ECC 000-140,
  * light-on-dark and mirrored symbols, perspective, a symbol that other ink touches.  Integer arithmetic throughout: the result is
  * defined bit for bit (tests/dm_reference.py).  Asynchronous; n == 0 is a no-op; bad arguments return a status before anything is
  * written. */
 int lumina_ocr_datamatrix(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module, int max_module,
                           int quiet, int timing_max, int solid_max, int max_candidates, int max_codes, int32_t* codes_dev, int32_t* data_dev,
                           int32_t* counts_dev, int32_t* candidate_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream);
+
+/* lumina_ocr_datamatrix_sizes: lumina_ocr_datamatrix for every ECC 200 size, up to max_size (52 .. 144) modules a side.  STAGE 1 is
+ * lumina_ocr_datamatrix itself: the same candidates, rows and codewords, bit for bit, and max_size = 52 reads exactly what it reads.
+ * STAGE 2 (max_size >= 64) reads the squares of 64 x 64 .. 144 x 144 (4 x 4 or 6 x 6 regions, 2 .. 10 interleaved blocks) whose side is
+ * at most max_size.  It has a candidate list of its own, so that stage 1's count and its max_candidates cut-off do not move: the
+ * roots that pass the area test and whose box sides lie in 64 min_module .. 144 max_module, up to max_candidates of them (a page
+ * with more is not read by stage 2; stage 1's rows stand).  A root that gave a stage-1 row is skipped.  Tries, score (over all clock
+ * and solid rows and columns of the regions), quiet rings, placement and Reed-Solomon as in stage 1; the blocks are dealt by stream
+ * position: the codeword at position p of data + check belongs to block p mod blocks, which for 144 x 144 (1558 data codewords in ten
+ * blocks, eight of 156 + 62 and two of 155 + 62) makes the check codewords carry on from block 8.  The nine size rows and this
+ * interleave are written from recollection of the standard and pinned structurally and by this project's own encoder only.
+ * Both stages' rows are sorted together by the key of lumina_ocr_datamatrix; codes_dev as there; data_dev uint8 [n][max_codes][1560]
+ * = the corrected data codewords, zero behind ndata; candidate_counts_dev is stage 1's.  The other parameters, their ranges and
+ * mask_in_dev / mask_out_dev as in lumina_ocr_datamatrix.  Integer arithmetic throughout: the result is defined bit for bit
+ * (tests/dm_sizes_reference.py).  Asynchronous; n == 0 is a no-op; bad arguments (max_size outside 52..144 among them) return a
+ * status before anything is written.  lumina_ocr_datamatrix_sizes_workspace_bytes: the workspace of n pages (0 for bad arguments). */
+size_t lumina_ocr_datamatrix_sizes_workspace_bytes(int n, int height, int width, int max_candidates, int max_codes);
+/* Host only, no device needed: the placement table the second stage uses for the side x side symbol (64 .. 144), built by the
+ * library from the standard's walk: (row << 8 | col) of every codeword bit, the most significant bit of a codeword first, into
+ * out[capacity] -> the number of entries, 0 for another side or too small a capacity. */
+int lumina_ocr_datamatrix_placement(int side, uint16_t* out, int capacity);
+int lumina_ocr_datamatrix_sizes(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module,
+                                int max_module, int quiet, int timing_max, int solid_max, int max_candidates, int max_codes, int max_size,
+                                int32_t* codes_dev, uint8_t* data_dev, int32_t* counts_dev, int32_t* candidate_counts_dev,
+                                const uint64_t* mask_in_dev, uint64_t* mask_out_dev, void* stream);
 
 /* Aztec codes (ISO/IEC 24778, written from recollection of the public symbology): compact symbols of 1-4 layers and full-range
  * symbols of 1-11 layers (15 .. 61 modules: the symbols whose rows fit one 64-bit word) on the pages, located, sampled and

@@ -1064,6 +1064,32 @@ int lumina_ocr_datamatrix(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int 
         });
 }
 
+size_t lumina_ocr_datamatrix_sizes_workspace_bytes(int n, int height, int width, int max_candidates, int max_codes) {
+    return n > 0 ? datamatrix_sizes_workspace_bytes(n, height, width, max_candidates, max_codes) : 0;
+}
+
+int lumina_ocr_datamatrix_placement(int side, uint16_t* out, int capacity) { return datamatrix_placement(side, out, capacity); }
+
+int lumina_ocr_datamatrix_sizes(lumina_ocr_t* h, const uint8_t* pages_dev, int n, int height, int width, int threshold, int min_module, int max_module,
+                                int quiet, int timing_max, int solid_max, int max_candidates, int max_codes, int max_size, int32_t* codes_dev,
+                                uint8_t* data_dev, int32_t* counts_dev, int32_t* candidate_counts_dev, const uint64_t* mask_in_dev, uint64_t* mask_out_dev,
+                                void* stream) {
+    const char* bad = dm_params_ok(min_module, max_module, quiet, timing_max, solid_max, max_candidates, max_codes) && dm_max_size_ok(max_size)
+                          ? nullptr
+                          : "parameters must satisfy 1 <= min_module <= max_module <= 64, 0 <= quiet <= 4, 0 <= timing_max, solid_max <= 128, "
+                            "max_candidates 1..1024, max_codes 1..64, max_size 52..144";
+    return matrix_codes(
+        h, "datamatrix_sizes", bad, pages_dev, n, height, width, max_codes, DM_MAX_DATA_ALL, codes_dev, data_dev, counts_dev, candidate_counts_dev, mask_in_dev,
+        mask_out_dev, [&](int nb) { return datamatrix_sizes_workspace_bytes(nb, height, width, max_candidates, max_codes); },
+        [&](const CodeGroup<uint8_t>& g, void* ws, size_t cap) {
+            DmSizesParams p{};
+            g.bind(p); p.data_all = g.data; p.candidate_counts = g.slot_counts; p.H = height; p.W = width;
+            p.threshold = threshold; p.min_module = min_module; p.max_module = max_module; p.quiet = quiet; p.timing_max = timing_max; p.solid_max = solid_max;
+            p.max_candidates = max_candidates; p.max_codes = max_codes; p.max_size = max_size;
+            return datamatrix_sizes_launch(p, ws, cap, (hipStream_t)stream);
+        });
+}
+
 size_t lumina_ocr_aztec_workspace_bytes(int n, int height, int width, int max_finders, int max_codes) {
     return n > 0 ? aztec_workspace_bytes(n, height, width, max_finders, max_codes) : 0;
 }

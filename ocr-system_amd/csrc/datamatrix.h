@@ -28,6 +28,23 @@ constexpr int DM_MAX_MODULE = 64;
 constexpr int DM_MAX_QUIET = 4;
 constexpr int DM_MAX_TIMING = 128;
 
+// every ECC 200 size (definition restated in tests/dm_sizes_reference.py): stage 1 is the pass above, with the same rows and codewords;
+// a root with box sides in 64 min_module .. 144 max_module that gave no such row goes through stage 2, which reads the squares of
+// 64 x 64 .. max_size from a candidate list of its own (capacity max_candidates; a page with more is not read by stage 2).  `data` is
+// not used: the rows of both stages come as bytes in data_all.
+struct DmSizesParams : DmParams {
+    int max_size;               // DM_MIN_MAX_SIZE (stage 1 alone) .. DM_MAX_MAX_SIZE
+    unsigned char* data_all;    // device, [B][max_codes][DM_MAX_DATA_ALL]: the corrected data codewords, zero behind ndata
+};
+constexpr int DM_MAX_DATA_ALL = 1560;    // >= 1558, the data codewords of 144 x 144
+constexpr int DM_MIN_MAX_SIZE = 52, DM_MAX_MAX_SIZE = 144;
+
+bool dm_max_size_ok(int max_size);
+// host only: the placement table of the side x side symbol (64 .. 144) as the second stage uses it, (row << 8 | col) per codeword bit
+// -> the number of entries, 0 for another side or when cap is too small
+int datamatrix_placement(int side, unsigned short* out, int cap);
+size_t datamatrix_sizes_workspace_bytes(int B, int H, int W, int max_candidates, int max_codes);
+hipError_t datamatrix_sizes_launch(const DmSizesParams& p, void* workspace, size_t ws_bytes, hipStream_t st);
 bool dm_params_ok(int min_module, int max_module, int quiet, int timing_max, int solid_max, int max_candidates, int max_codes);
 size_t datamatrix_workspace_bytes(int B, int H, int W, int max_candidates, int max_codes);
 hipError_t datamatrix_launch(const DmParams& p, void* workspace, size_t ws_bytes, hipStream_t st);

@@ -528,7 +528,8 @@ QR_PARAMS = dict(threshold=BARCODE_PARAMS["threshold"], min_module=3, max_module
 # area filter lets every glyph of 24 px and more through, the benchmark's A4 text pages have 50 candidates on average and up to 98,
 # and a page above the capacity is not read at all; nothing in the pass needs a lane per candidate (the decode kernel's grid is
 # max_candidates waves a page, all but the candidates' exit after one load), so the capacity is max_candidates <= 1024 and 256 by
-# default.  max_codes <= 64.
+# default.  max_codes <= 64.  lumina_ocr_datamatrix_sizes takes the same parameters: its second stage (64 x 64 .. 144 x 144) has a candidate
+# list of its own with the same capacity, box sides in 64 min_module .. 144 max_module (tests/dm_sizes_reference.py).
 DM_PARAMS = dict(threshold=BARCODE_PARAMS["threshold"], min_module=3, max_module=24, quiet=1, timing_max=3, solid_max=3, max_candidates=256,
                  max_codes=16)
 

@@ -117,6 +117,9 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_qrcodes": (i32, [vp, vp, i32, i32, i32] + [i32] * 9 + [vp] * 7),
         "lumina_ocr_qrcodes_versions": (i32, [vp, vp, i32, i32, i32] + [i32] * 10 + [vp] * 7),
         "lumina_ocr_datamatrix": (i32, [vp, vp, i32, i32, i32] + [i32] * 8 + [vp] * 7),
+        "lumina_ocr_datamatrix_sizes": (i32, [vp, vp, i32, i32, i32] + [i32] * 9 + [vp] * 7),
+        "lumina_ocr_datamatrix_sizes_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+        "lumina_ocr_datamatrix_placement": (i32, [i32, vp, i32]),
         "lumina_ocr_aztec": (i32, [vp, vp, i32, i32, i32] + [i32] * 9 + [vp] * 7),
         "lumina_ocr_aztec_layers": (i32, [vp, vp, i32, i32, i32] + [i32] * 10 + [vp] * 7),
         "lumina_ocr_rules_and_marks": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
@@ -160,7 +163,7 @@ EXPORTED_SYMBOLS = [
     "lumina_ocr_jbig2_probe", "lumina_ocr_jbig2_reason", "lumina_ocr_jbig2_decode",
     "lumina_ocr_load_svtr_weights", "lumina_ocr_svtr_forward", "lumina_ocr_svtr_num_classes", "lumina_ocr_svtr_dtype", "lumina_ocr_binarize", "lumina_ocr_exif_transpose", "lumina_ocr_grayscale", "lumina_ocr_denoise", "lumina_ocr_deskew", "lumina_ocr_deskew_warp",
     "lumina_ocr_table_rules", "lumina_ocr_selection_marks", "lumina_ocr_rules_and_marks", "lumina_ocr_selection_marks_round",
-    "lumina_ocr_rules_and_marks_round", "lumina_ocr_barcodes", "lumina_ocr_barcodes_kinds", "lumina_ocr_qrcodes", "lumina_ocr_qrcodes_versions", "lumina_ocr_datamatrix", "lumina_ocr_aztec", "lumina_ocr_aztec_workspace_bytes", "lumina_ocr_aztec_layers", "lumina_ocr_aztec_layers_workspace_bytes",
+    "lumina_ocr_rules_and_marks_round", "lumina_ocr_barcodes", "lumina_ocr_barcodes_kinds", "lumina_ocr_qrcodes", "lumina_ocr_qrcodes_versions", "lumina_ocr_datamatrix", "lumina_ocr_datamatrix_sizes", "lumina_ocr_datamatrix_sizes_workspace_bytes", "lumina_ocr_datamatrix_placement", "lumina_ocr_aztec", "lumina_ocr_aztec_workspace_bytes", "lumina_ocr_aztec_layers", "lumina_ocr_aztec_layers_workspace_bytes",
     "lumina_ocr_page_quarter_workspace_bytes", "lumina_ocr_page_quarter", "lumina_ocr_page_turn", "lumina_ocr_page_vote",
     "lumina_ocr_page_compose",
 ]
@@ -865,7 +868,7 @@ class Engine:
             self._chk(self.lib.lumina_ocr_barcodes_kinds(*args, kinds if isinstance(kinds, int) else arch.barcode_kinds_mask(kinds)))
         return (codes, syms, counts, mask) if debug else (codes, syms, counts)
 
-    # -- the matrix codes: what qrcodes, qrcodes_versions, datamatrix, aztec and aztec_layers share ------------------------------------
+    # -- the matrix codes: what qrcodes, qrcodes_versions, datamatrix, datamatrix_sizes, aztec and aztec_layers share ------------------------------------
     def _matrix_codes(self, name, keys, defaults, data_cols, data_dtype, pages, params, mask_in, debug, extra=()):
         """lumina_ocr_<name> on pages: the scalars are params' values for `keys` (the last one is max_codes), defaulting to `defaults`,
         then `extra`; rows of 12 ints, data rows of data_cols elements of torch.<data_dtype>.
@@ -908,7 +911,7 @@ class Engine:
         params, mask_in and debug as in qrcodes."""
         return self._matrix_codes("qrcodes_versions", self._QR_KEYS, arch.QR_PARAMS, 2956, "uint8", pages, params, mask_in, debug, (max_version,))
 
-    # -- Data Matrix (ECC 200, 10 x 10 .. 52 x 52 and the rectangles; the host half is utils/datamatrix.py) ------------------------------
+    # -- Data Matrix (ECC 200; datamatrix: 10 x 10 .. 52 x 52 and the rectangles, datamatrix_sizes: up to 144 x 144; the host half is utils/datamatrix.py) ------------------------------
     _DM_KEYS = ("threshold", "min_module", "max_module", "quiet", "timing_max", "solid_max", "max_candidates", "max_codes")
 
     def datamatrix(self, pages, mask_in=None, debug: bool = False, **params):
@@ -919,6 +922,14 @@ class Engine:
         this threshold, int64 [n,H,ceil(W/64)], when it is there already.  Asynchronous.  debug=True also returns the ink mask the
         pass worked on and the candidate count of every page."""
         return self._matrix_codes("datamatrix", self._DM_KEYS, arch.DM_PARAMS, 208, "int32", pages, params, mask_in, debug)
+
+    def datamatrix_sizes(self, pages, max_size: int, mask_in=None, debug: bool = False, **params):
+        """datamatrix for every ECC 200 size up to max_size (52..144) modules a side: uint8 [n,H,W,3] device -> (codes int32
+        [n,max_codes,12], data uint8 [n,max_codes,1560], counts int32 [n]).  Every symbol datamatrix reads comes with the same row and
+        codewords; a component of 64 min_module .. 144 max_module a side that gave no such row goes through the second stage, which
+        reads the squares of 64 x 64 .. max_size (lumina_ocr_datamatrix_sizes).  The data codewords are bytes here.  params, mask_in and
+        debug as in datamatrix; the candidate count debug returns is the first stage's."""
+        return self._matrix_codes("datamatrix_sizes", self._DM_KEYS, arch.DM_PARAMS, 1560, "uint8", pages, params, mask_in, debug, (max_size,))
 
     # -- Aztec (aztec: compact 1-4 layers, full-range 1-11 layers; aztec_layers: full-range up to 32; the host half is utils/aztec.py) ----------------------------------------------
     _AZTEC_KEYS = ("threshold", "min_module", "max_module", "quiet", "centre_tol", "ring_tol", "mark_max", "max_finders", "max_codes")

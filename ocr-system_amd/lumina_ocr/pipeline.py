@@ -47,7 +47,8 @@ class PageDetections:
                                               # uint8 [m, 2956] with OcrPipeline(qr_max_version > 10)
     datamatrix: Optional[np.ndarray] = None   # int32 [m, 12] x0, y0, x1, y1, rows, cols, ndata, errors, rotation, timing mismatches, L misses, 0
                                               # of the page's Data Matrix symbols: OcrPipeline(datamatrix=True) only (empty on overflow)
-    dm_data: Optional[np.ndarray] = None      # int32 [m, 208] their corrected data codewords (utils/datamatrix.py turns them into text)
+    dm_data: Optional[np.ndarray] = None      # int32 [m, 208] their corrected data codewords (utils/datamatrix.py turns them into text);
+                                              # uint8 [m, 1560] with OcrPipeline(dm_max_size > 52)
     aztec: Optional[np.ndarray] = None        # int32 [m, 12] x0, y0, x1, y1, layers, compact, codeword width, ndata, errors, rotation, mode errors,
                                               # mismatches of the page's Aztec symbols: OcrPipeline(aztec=True) only (empty on overflow)
     az_data: Optional[np.ndarray] = None      # int32 [m, 320] their corrected data codewords (utils/aztec.py turns them into text);
@@ -106,7 +107,7 @@ class OcrPipeline:
                  round_mark_params: Optional[dict] = None, barcodes: bool = False, barcode_params: Optional[dict] = None,
                  qrcodes: bool = False, qr_params: Optional[dict] = None, qr_max_version: int = 10, barcode_kinds=arch.BARCODE_KINDS_DEFAULT,
                  datamatrix: bool = False, dm_params: Optional[dict] = None, aztec: bool = False, aztec_params: Optional[dict] = None,
-                 aztec_max_layers: int = 11):
+                 aztec_max_layers: int = 11, dm_max_size: int = 52):
         """recognizer: "crnn" (CRNN-MobileNetV3 + BiLSTM, engine.load_rec) or "svtr" (SVTR, engine.load_svtr).
         angle_cls: PaddleOCR's use_angle_cls — every line is classified 0 / 180 degrees (engine.load_cls) before recognition, and a line
         read as 180 with probability > cls_thresh is recognised turned; boxes and reading order are unchanged.  Per-line labels are
@@ -130,6 +131,8 @@ class OcrPipeline:
         datamatrix: the Data Matrix symbols (ECC 200, up to 52 x 52) of the processed pages (engine.datamatrix, parameters arch.DM_PARAMS
         or dm_params) come back as PageDetections.datamatrix / dm_data; the pass runs behind the QR pass and takes the ink mask the
         earlier passes made at its threshold; with a gather it is not run.
+        dm_max_size (52..144): above 52 the pass is engine.datamatrix_sizes, which reads the squares of 64 x 64 .. dm_max_size as well;
+        dm_data is then uint8 [m, 1560].
         aztec: the Aztec symbols (compact 1-4 layers, full-range 1-11 layers) of the processed pages (engine.aztec, parameters
         arch.AZTEC_PARAMS or aztec_params; an unknown key is a ValueError) come back as PageDetections.aztec / az_data; the pass runs behind
         the Data Matrix pass and takes the ink mask an earlier pass made at its threshold; with a gather it is not run.
@@ -175,6 +178,9 @@ class OcrPipeline:
             raise ValueError("qr_max_version must be 10..40, not %r" % (qr_max_version,))
         self.datamatrix = bool(datamatrix)
         self.dm_params = dict(arch.DM_PARAMS if dm_params is None else dm_params)
+        self.dm_max_size = int(dm_max_size)
+        if not 52 <= self.dm_max_size <= 144:
+            raise ValueError("dm_max_size must be 52..144, not %r" % (dm_max_size,))
         self.aztec = bool(aztec)
         self.aztec_params = dict(arch.AZTEC_PARAMS if aztec_params is None else aztec_params)
         if set(self.aztec_params) - set(arch.AZTEC_PARAMS):
@@ -230,7 +236,10 @@ class OcrPipeline:
         """Enqueue the Data Matrix pass -> (codes, data codewords, counts) device tensors; mask: the ink mask an earlier pass made at the
         threshold mask_at, or None."""
         dp = self.dm_params
-        return self.eng.datamatrix(processed, mask_in=mask if mask is not None and mask_at == dp["threshold"] else None, **dp)
+        mask_in = mask if mask is not None and mask_at == dp["threshold"] else None
+        if self.dm_max_size == 52:
+            return self.eng.datamatrix(processed, mask_in=mask_in, **dp)
+        return self.eng.datamatrix_sizes(processed, self.dm_max_size, mask_in=mask_in, **dp)
 
     def _submit_page_analysis(self, processed):
         """_submit_passes, then the Aztec pass behind them -> (rules, marks, codes, qr codes, data matrix symbols, aztec symbols), None
@@ -490,7 +499,7 @@ class OcrPipeline:
         """-> per page (codes [m,8], symbol values [m,64]) from the pending batch's host copies, or (None, None) without barcodes.  A
         page whose true count exceeds the capacity has no rows: it is treated as having no barcodes.  kind: another row of _CODE_PASSES
         for the same of that pass's copies, "qrcodes": (codes [m,12], data codewords [m,288], or bytes [m,2956] above qr_max_version 10);
-        "datamatrix": (codes [m,12], data codewords [m,208]); "aztec": (codes [m,12], data codewords [m,320], or uint16 [m,1664] above
+        "datamatrix": (codes [m,12], data codewords [m,208], or uint8 [m,1560] above dm_max_size 52); "aztec": (codes [m,12], data codewords [m,320], or uint16 [m,1664] above
         aztec_max_layers 11)."""
         host = pend.codes_host.get(kind)
         if host is None:

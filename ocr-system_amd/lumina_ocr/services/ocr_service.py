@@ -208,6 +208,10 @@ class OCRService:
         # "DataMatrix" with their decoded content and a `:barcode: <content>` line of the Markdown, behind the 1-D and QR codes of the page;
         # the text lines the detector found inside a symbol are dropped.  Off by default: every output is then the one without it.
         self._use_datamatrix = os.environ.get("LUMINA_OCR_DATAMATRIX", "0").lower() not in ("", "0", "false", "no")
+        # LUMINA_OCR_DATAMATRIX_MAX_SIZE=52..144 (with LUMINA_OCR_DATAMATRIX=1; alone it has no effect; default 52: the pass above and nothing
+        # else): the squares of 64 x 64 up to that many modules a side are read as well (lumina_ocr_datamatrix_sizes).  Checked when the
+        # engine starts: another value is an error result.
+        self._dm_max_size = os.environ.get("LUMINA_OCR_DATAMATRIX_MAX_SIZE", "") or "52"
         # LUMINA_OCR_AZTEC=1: Aztec symbols (compact 1-4 layers, full-range 1-11 layers) become `barcode` entries of kind "Aztec" with their
         # decoded content and a `:barcode: <content>` line of the Markdown, behind the 1-D, QR and Data Matrix codes of the page; the text
         # lines the detector found inside a symbol are dropped.  Off by default: every output is then the one without it.
@@ -259,6 +263,11 @@ class OCRService:
                 if not (self._qr_max_version.strip().isdigit() and 10 <= int(self._qr_max_version) <= 40):
                     raise RuntimeError("LUMINA_OCR_QR_MAX_VERSION: %r is not a version 10..40" % self._qr_max_version)
                 qr_max_version = int(self._qr_max_version)
+            dm_max_size = 52
+            if self._use_datamatrix:
+                if not (self._dm_max_size.strip().isdigit() and 52 <= int(self._dm_max_size) <= 144):
+                    raise RuntimeError("LUMINA_OCR_DATAMATRIX_MAX_SIZE: %r is not a number of modules 52..144" % self._dm_max_size)
+                dm_max_size = int(self._dm_max_size)
             aztec_max_layers = 11
             if self._use_aztec:
                 if not (self._aztec_max_layers.strip().isdigit() and 11 <= int(self._aztec_max_layers) <= 32):
@@ -305,7 +314,7 @@ class OCRService:
                                            angle_cls=self._use_angle_cls, tables=self._use_tables, marks=self._use_marks,
                                            page_orient=self._use_page_orient, word_boxes=self._use_word_boxes, round_marks=self._use_round_marks,
                                            barcodes=self._use_barcodes, qrcodes=self._use_qrcodes, qr_max_version=qr_max_version, datamatrix=self._use_datamatrix, aztec=self._use_aztec,
-                                           aztec_max_layers=aztec_max_layers, barcode_kinds=self._barcode_kinds if self._use_barcodes else arch.BARCODE_KINDS_DEFAULT)
+                                           aztec_max_layers=aztec_max_layers, dm_max_size=dm_max_size, barcode_kinds=self._barcode_kinds if self._use_barcodes else arch.BARCODE_KINDS_DEFAULT)
             except Exception:
                 eng.close()
                 raise
@@ -321,6 +330,13 @@ class OCRService:
             return None
         text = self._qr_max_version.strip()
         return int(text) if text.isdigit() and 10 <= int(text) <= 40 else self._qr_max_version
+
+    def _dm_max_size_status(self):
+        """The largest Data Matrix side the provider reads (None with Data Matrix off; the variable's text when it is no number 52..144)."""
+        if not self._use_datamatrix:
+            return None
+        text = self._dm_max_size.strip()
+        return int(text) if text.isdigit() and 52 <= int(text) <= 144 else self._dm_max_size
 
     def _aztec_max_layers_status(self):
         """The most layers of a full-range Aztec symbol the provider reads (None with Aztec off; the variable's text when it is no number 11..32)."""
@@ -1232,7 +1248,7 @@ class OCRService:
     # ---- status (:759-795) ----
     def get_status(self) -> Dict[str, Any]:
         st = {"client_initialized": self._pipeline is not None, "model_id": "dbnet-r18vd+crnn-mv3", "max_dimension": self.max_dimension,
-              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "aztec": self._use_aztec, "aztec_max_layers": self._aztec_max_layers_status(), "device_pdf": self.device_pdf, "pdf_layers": self.pdf_layers, "pdf_jbig2": self.pdf_jbig2, "progressive_jpeg": self.progressive_jpeg, "device_tiff": self.device_tiff, "device_jp2": self.device_jp2, "jp2_irreversible": self.jp2_irreversible, "jp2_tiles": self.jp2_tiles, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
+              "device": self._device, "weights": self._weights_kind, "recognizer": self._recognizer, "apply_deskew": self.apply_deskew, "apply_binarize": bool(self.apply_binarize), "word_boxes": self._use_word_boxes, "barcodes": self._use_barcodes, "barcode_kinds": self._barcode_kinds_names(), "qrcodes": self._use_qrcodes, "qr_max_version": self._qr_max_version_status(), "datamatrix": self._use_datamatrix, "datamatrix_max_size": self._dm_max_size_status(), "aztec": self._use_aztec, "aztec_max_layers": self._aztec_max_layers_status(), "device_pdf": self.device_pdf, "pdf_layers": self.pdf_layers, "pdf_jbig2": self.pdf_jbig2, "progressive_jpeg": self.progressive_jpeg, "device_tiff": self.device_tiff, "device_jp2": self.device_jp2, "jp2_irreversible": self.jp2_irreversible, "jp2_tiles": self.jp2_tiles, "engine": "Lumina MI355X det+rec (HIP, gfx950)"}
         if self._engine is not None:
             st["engine_version"] = self._engine.version()
             st["num_classes"] = self._engine.num_classes

@@ -912,7 +912,7 @@ def dm_data_codewords(data, size: int, scheme: str = "ascii") -> List[int]:
     an unlatch.  EDIFACT unlatches unless its triples end with the symbol; Base 256 writes its length, or 0 ("to the end of the
     symbol") when the field fills the symbol."""
     from .utils import datamatrix as dm
-    cap = dm.SIZES[size][2]
+    cap = dm.ALL_SIZES[size][2]
     if scheme not in DM_SCHEMES:
         raise ValueError("scheme must be one of %s" % (DM_SCHEMES,))
 
@@ -968,7 +968,7 @@ def dm_data_codewords(data, size: int, scheme: str = "ascii") -> List[int]:
     cw: List[int] = []
     part(data, scheme, cw)
     if len(cw) > cap:
-        raise ValueError("%d codewords do not fit %d x %d (%d)" % (len(cw), dm.SIZES[size][0], dm.SIZES[size][1], cap))
+        raise ValueError("%d codewords do not fit %d x %d (%d)" % (len(cw), dm.ALL_SIZES[size][0], dm.ALL_SIZES[size][1], cap))
     if len(cw) < cap:
         cw.append(dm.PAD)
     while len(cw) < cap:
@@ -990,19 +990,25 @@ def dm_rs_remainder(data: List[int], ec: int) -> List[int]:
 
 
 def dm_interleave(cw: List[int], size: int) -> List[int]:
-    """Data codewords -> all codewords of the symbol in placement order: the data, then the blocks' check codewords interleaved
-    (block b takes every nb-th data codeword from b on)."""
+    """Data codewords -> all codewords of the symbol in placement order: the data, then the blocks' check codewords, dealt by stream
+    position: the codeword at position p is block p mod nb's next one (block b takes every nb-th data codeword from b on; behind
+    144 x 144's 1558 data codewords the check codewords carry on from block 8)."""
     from .utils import datamatrix as dm
-    nb, ec = dm.SIZES[size][6], dm.SIZES[size][3] // dm.SIZES[size][6]
-    checks = [dm_rs_remainder(cw[b::nb], ec) for b in range(nb)]
-    return list(cw) + [checks[b][i] for i in range(ec) for b in range(nb)]
+    nd, ne, nb = dm.ALL_SIZES[size][2], dm.ALL_SIZES[size][3], dm.ALL_SIZES[size][6]
+    checks = [dm_rs_remainder(cw[b::nb], ne // nb) for b in range(nb)]
+    taken = [0] * nb
+    out = list(cw)
+    for p in range(nd, nd + ne):
+        out.append(checks[p % nb][taken[p % nb]])
+        taken[p % nb] += 1
+    return out
 
 
 def dm_matrix(codewords: List[int], size: int) -> np.ndarray:
     """All codewords of a symbol -> bool [rows, cols] (True = dark): function modules, the codewords through the placement and the
     fixed 2 x 2 corner."""
     from .utils import datamatrix as dm
-    m = np.zeros(dm.SIZES[size][:2], bool)
+    m = np.zeros(dm.ALL_SIZES[size][:2], bool)
     for (r, c), dark in dm.function_modules(size).items():
         m[r, c] = dark
     for i, (r, c) in enumerate(dm.placement_of(size)):
@@ -1017,11 +1023,11 @@ def dm_encode(data, size: int, scheme: str = "ascii") -> np.ndarray:
     return dm_matrix(dm_interleave(dm_data_codewords(data, size, scheme), size), size)
 
 
-def dm_smallest_size(data, scheme: str = "ascii", square: bool = True) -> int:
-    """The first square (or any) size of the table that holds data."""
+def dm_smallest_size(data, scheme: str = "ascii", square: bool = True, large: bool = False) -> int:
+    """The first square (or any) size of the table that holds data; large=True: of ALL_SIZES, up to 144 x 144."""
     from .utils import datamatrix as dm
-    for s in sorted(range(dm.NUM_SIZES), key=lambda s: dm.SIZES[s][2]):
-        if square and dm.SIZES[s][0] != dm.SIZES[s][1]:
+    for s in sorted(range(dm.NUM_SIZES_ALL if large else dm.NUM_SIZES), key=lambda s: dm.ALL_SIZES[s][2]):
+        if square and dm.ALL_SIZES[s][0] != dm.ALL_SIZES[s][1]:
             continue
         try:
             dm_data_codewords(data, s, scheme)

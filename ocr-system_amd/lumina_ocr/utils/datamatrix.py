@@ -1,11 +1,13 @@
-"""Data Matrix, host half (pure Python): the tables of the ECC 200 sizes whose rows fit one 64-bit word, the corrected data codewords
+"""Data Matrix, host half (pure Python): the tables of the ECC 200 sizes whose rows fit one 64-bit word (SIZES) and of the nine larger
+squares up to 144 x 144 (LARGE_SIZES; ALL_SIZES is both, and every size index below is one of ALL_SIZES), the corrected data codewords
 of a device row (lumina_ocr_datamatrix: x0, y0, x1, y1, rows, cols, ndata, errors, rotation, timing mismatches, L misses, 0 + the
 codewords) -> text, and the entries the provider reports.
 
 The tables are our reading of the public standard (ISO/IEC 16022), built from its rules: the L finder, the clock tracks and the
 alignment bars between data regions make the function masks; the diagonal walk with its four corner cases and the fixed 2 x 2
 corner gives the placement; the size table is typed and pinned by modules = 8 (data + check) + remainder (tests/test_dm_tables.py).
-csrc/dm_tables.h holds the same tables for the device (device_header() writes it; the test compares).
+csrc/dm_tables.h holds the same tables for the device (device_header() writes it; the test compares), csrc/dm_tables_large.h those
+of the larger squares without the placement, which the library builds itself (device_header_large()).
 
 Coordinates: a module is (row, col), row 0 the clock track opposite the L's foot, col 0 the L's upright; a row of modules is one
 64-bit word, bit col.  The DATA-REGION MATRIX is the symbol without its function modules, regions pushed together."""
@@ -24,6 +26,20 @@ MAX_DATA = 208                         # ints a device data row holds (>= 204, t
 MAX_CODEWORDS = 288
 MAX_BLOCK_LEN, MAX_EC = 242, 68        # 48 x 48: one block of 174 + 68
 
+# The nine larger squares (lumina_ocr_datamatrix_sizes reads them): 4 x 4 or 6 x 6 regions, two to ten interleaved blocks.  The rows are
+# written from recollection of the standard; what pins them is structural (data + check = mapping area / 8, tests/test_dm_sizes_tables.py)
+# and this project's own encoder.  The codeword at stream position p (data, then check) belongs to block p mod blocks: 144 x 144 has
+# 1558 data codewords in ten blocks, eight of 156 + 62 and two of 155 + 62, so its check codewords carry on from block 8.
+LARGE_SIZES = ((64, 64, 280, 112, 4, 4, 2), (72, 72, 368, 144, 4, 4, 4), (80, 80, 456, 192, 4, 4, 4), (88, 88, 576, 224, 4, 4, 4),
+               (96, 96, 696, 272, 4, 4, 4), (104, 104, 816, 336, 4, 4, 6), (120, 120, 1050, 408, 6, 6, 6), (132, 132, 1304, 496, 6, 6, 8),
+               (144, 144, 1558, 620, 6, 6, 10))
+ALL_SIZES = SIZES + LARGE_SIZES        # a size index of the functions below is an index into this
+NUM_SIZES_ALL = len(ALL_SIZES)
+MAX_DATA_ALL = 1560                    # bytes a device data row of lumina_ocr_datamatrix_sizes holds (>= 1558)
+MAX_CODEWORDS_ALL = 2178
+MAX_BLOCKS_ALL, MAX_BLOCK_LEN_ALL = 10, 243   # 120 x 120: six blocks of 175 + 68
+MIN_MAX_SIZE, MAX_MAX_SIZE = 52, 144   # lumina_ocr_datamatrix_sizes' max_size
+
 
 def size_index(rows: int, cols: int) -> int:
     """-> index into SIZES, or -1."""
@@ -33,21 +49,29 @@ def size_index(rows: int, cols: int) -> int:
     return -1
 
 
+def size_index_all(rows: int, cols: int) -> int:
+    """-> index into ALL_SIZES, or -1."""
+    for i, s in enumerate(ALL_SIZES):
+        if s[0] == rows and s[1] == cols:
+            return i
+    return -1
+
+
 def mapping_dims(size: int) -> Tuple[int, int]:
     """Rows and columns of the data-region matrix."""
-    r, c, _, _, nr, nc, _ = SIZES[size]
+    r, c, _, _, nr, nc, _ = ALL_SIZES[size]
     return r - 2 * nr, c - 2 * nc
 
 
 def remainder_modules(size: int) -> int:
     nrow, ncol = mapping_dims(size)
-    return nrow * ncol - 8 * (SIZES[size][2] + SIZES[size][3])
+    return nrow * ncol - 8 * (ALL_SIZES[size][2] + ALL_SIZES[size][3])
 
 
 def block_lengths(size: int) -> List[Tuple[int, int]]:
-    """-> [(data, check)] of every interleaved block."""
-    _, _, nd, ne, _, _, nb = SIZES[size]
-    return [(len(range(b, nd, nb)), ne // nb) for b in range(nb)]
+    """-> [(data, check)] of every interleaved block: block b takes the stream positions b, b + nb, ..., its last ne / nb are check."""
+    _, _, nd, ne, _, _, nb = ALL_SIZES[size]
+    return [(len(range(b, nd + ne, nb)) - ne // nb, ne // nb) for b in range(nb)]
 
 
 # ---- GF(256), polynomial 0x12D: EXP has 512 entries so that EXP[LOG[a] + LOG[b]] needs no reduction ----
@@ -85,7 +109,7 @@ def rs_generator(ec: int) -> List[int]:
 def function_modules(size: int) -> Dict[Tuple[int, int], bool]:
     """-> {(row, col): dark} of every function module: of each data region the solid left column and bottom row (the L and the inner
     solid bars), the clock row above it (dark on even columns) and the clock column to its right (dark on odd rows)."""
-    rows, cols, _, _, nr, nc, _ = SIZES[size]
+    rows, cols, _, _, nr, nc, _ = ALL_SIZES[size]
     rh, rw = rows // nr, cols // nc
     f: Dict[Tuple[int, int], bool] = {}
     for r in range(rows):
@@ -103,7 +127,7 @@ def function_modules(size: int) -> Dict[Tuple[int, int], bool]:
 def function_masks(size: int) -> Tuple[List[int], List[int], List[int]]:
     """-> (solid, clock, clock_dark): row words, bit col set where (row, col) is a module of the L or an inner solid bar / of a clock
     track or an inner clock bar / a dark one of those."""
-    rows, cols, _, _, nr, nc, _ = SIZES[size]
+    rows, cols, _, _, nr, nc, _ = ALL_SIZES[size]
     rh, rw = rows // nr, cols // nc
     solid, clock, dark = [0] * rows, [0] * rows, [0] * rows
     for (r, c), d in function_modules(size).items():
@@ -177,7 +201,7 @@ def mapping_placement(nrow: int, ncol: int) -> Tuple[List[List[Tuple[int, int]]]
 
 def to_symbol(size: int, r: int, c: int) -> Tuple[int, int]:
     """Data-region matrix (r, c) -> symbol (row, col): the function modules of every region are stepped over."""
-    rows, cols, _, _, nr, nc, _ = SIZES[size]
+    rows, cols, _, _, nr, nc, _ = ALL_SIZES[size]
     dh, dw = rows // nr - 2, cols // nc - 2
     return r + 1 + 2 * (r // dh), c + 1 + 2 * (c // dw)
 
@@ -200,8 +224,15 @@ def fixed_modules(size: int) -> List[Tuple[Tuple[int, int], bool]]:
 _PLACEMENT = tuple(tuple(placement(s)) for s in range(NUM_SIZES))
 
 
+_PLACEMENT_LARGE: Dict[int, Tuple[Tuple[int, int], ...]] = {}
+
+
 def placement_of(size: int) -> Tuple[Tuple[int, int], ...]:
-    return _PLACEMENT[size]
+    if size < NUM_SIZES:
+        return _PLACEMENT[size]
+    if size not in _PLACEMENT_LARGE:                       # (79 264 bits in all: built when first asked for)
+        _PLACEMENT_LARGE[size] = tuple(placement(size))
+    return _PLACEMENT_LARGE[size]
 
 
 def device_header() -> str:
@@ -224,6 +255,31 @@ def device_header() -> str:
             "__device__ const unsigned char DM_LOG[256] = {\n%s};\n"
             % (NUM_SIZES, len(place), rows(sizes, "%d", 16), rows(place, "0x%03x", 16), rows(off, "%d", 11), rows(list(GF_EXP), "%d", 32),
                rows(list(GF_LOG), "%d", 32)))
+
+
+def device_header_large() -> str:
+    """The text of csrc/dm_tables_large.h.  The placement table itself (79 264 entries) is not written out: datamatrix.hip builds it
+    on the host with the walk of mapping_placement and copies it to DML_PLACE once a device; lumina_ocr_datamatrix_placement returns
+    what it built and tests/test_dm_sizes_tables.py compares that with placement_of."""
+    rows = lambda v, f, per: ",\n".join("    " + ", ".join(f % x for x in v[i:i + per]) for i in range(0, len(v), per))
+    off = [0]
+    for s in LARGE_SIZES:
+        off.append(off[-1] + 8 * (s[2] + s[3]))
+    sizes = [x for s in LARGE_SIZES for x in s + (0,)]
+    return ("#pragma once\n// Written by lumina_ocr.utils.datamatrix.device_header_large(); tests/test_dm_sizes_tables.py compares.  Data Matrix ECC 200, the\n"
+            "// nine squares of 64 x 64 .. 144 x 144.  DML_SIZES: rows, cols, data codewords, check codewords, region rows, region cols,\n"
+            "// interleaved blocks, 0 of every size (DML_SIZES_HOST: the same for the host).  DML_PLACE: (row << 8 | col) of every codeword bit\n"
+            "// in placement order, the most significant bit of a codeword first, size s at DML_PLACE_OFF[s] .. DML_PLACE_OFF[s + 1]; global\n"
+            "// memory that datamatrix.hip fills once a device from the standard's walk (dml_placement there) and that no kernel writes.\n"
+            "constexpr int DML_NUM_SIZES = %d, DML_PLACE_N = %d;\n"
+            "#define DML_SIZE_ROWS \\\n%s\n"
+            "__device__ const unsigned short DML_SIZES[DML_NUM_SIZES * 8] = {DML_SIZE_ROWS};\n"
+            "static const unsigned short DML_SIZES_HOST[DML_NUM_SIZES * 8] = {DML_SIZE_ROWS};\n"
+            "#define DML_PLACE_OFFSETS %s\n"
+            "__device__ const int DML_PLACE_OFF[DML_NUM_SIZES + 1] = {DML_PLACE_OFFSETS};\n"
+            "static const int DML_PLACE_OFF_HOST[DML_NUM_SIZES + 1] = {DML_PLACE_OFFSETS};\n"
+            "__device__ unsigned short DML_PLACE[DML_PLACE_N];\n"
+            % (len(LARGE_SIZES), off[-1], rows(sizes, "%d", 8).replace(",\n", ", \\\n"), ", ".join("%d" % v for v in off)))
 
 
 # ---- codewords -> text ----
@@ -400,15 +456,15 @@ def confidence(size: int, errors: int) -> float:
 
 
 def read_datamatrix(codes, data) -> List[dict]:
-    """Device rows int32 [m,12] + data codewords [m,MAX_DATA] -> one dict a symbol, in the rows' order: kind "DataMatrix", content,
+    """Device rows int32 [m,12] + data codewords [m,MAX_DATA] (bytes [m,MAX_DATA_ALL] from lumina_ocr_datamatrix_sizes) -> one dict a symbol, in the rows' order: kind "DataMatrix", content,
     confidence, polygon (the hull's TL, TR, BR, BL as 8 floats), box, rows, cols, rotation, errors, `gs1`: True for a GS1 symbol, and
     `unsupported` with the reason where the content is out of scope (content is then "").  A row whose codewords are no valid
     encodation is left out."""
     out = []
     for c, d in zip(codes, data):
         x0, y0, x1, y1, rows, cols, ndata, errors, rotation = (int(v) for v in c[:9])
-        size = size_index(rows, cols)
-        if size < 0 or ndata != SIZES[size][2]:
+        size = size_index_all(rows, cols)
+        if size < 0 or ndata != ALL_SIZES[size][2]:
             continue
         cw = [int(v) for v in d[:ndata]]
         text, reason = codewords_text(cw)

@@ -4,7 +4,11 @@ own noise), in the same run on the same pages lumina_ocr_qrcodes (the yardstick:
 pipeline step with Data Matrix off and on (twice).  HIP events around each stage, median of --reps, with the spread (min, max) of the
 repeats.  One JSON line; needs an MI355X.
 
-    python tools/dm_probe.py [--reps 20]"""
+With --max-size N above 52 also lumina_ocr_datamatrix_sizes at that cap: on the pages above (no large symbol: what the second stage
+costs where it finds nothing) and on the same pages with one 64 x 64 and one 144 x 144 symbol at 3 px a module drawn on each of the
+first --code-pages, each time interleaved call by call with lumina_ocr_datamatrix on the same pages (the yardstick).
+
+    python tools/dm_probe.py [--reps 20] [--max-size 144]"""
 import argparse
 import json
 import sys
@@ -20,6 +24,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--pages", type=int, default=64)
     ap.add_argument("--code-pages", type=int, default=16)
+    ap.add_argument("--max-size", type=int, default=52, help="above 52: lumina_ocr_datamatrix_sizes as well (52..144)")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -69,6 +74,48 @@ def main():
                datamatrix_over_qrcodes=round(t_dm["median"] / t_qr["median"], 3),
                pipeline_delta_ms=round(min(t_on["median"], t_on2["median"]) - min(t_off["median"], t_off2["median"]), 2),
                off_spread_ms=round(abs(t_off["median"] - t_off2["median"]), 2))
+    if args.max_size > 52:
+        from lumina_ocr.utils import datamatrix as dm
+
+        def pair(fa, fb):
+            """fa and fb call by call, interleaved -> (times of fa, times of fb, the last outputs)"""
+            ta, tb, out = [], [], None
+            for i in range(args.reps + 3):
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                ev[0].record()
+                oa = fa()
+                ev[1].record()
+                ob = fb()
+                ev[2].record()
+                torch.cuda.synchronize()
+                if i >= 3:
+                    ta.append(ev[0].elapsed_time(ev[1]))
+                    tb.append(ev[1].elapsed_time(ev[2]))
+                out = (oa, ob)
+            st = lambda t: dict(median=round(float(np.median(t)), 3), min=round(min(t), 3), max=round(max(t), 3))
+            return st(ta), st(tb), out
+
+        ms = args.max_size
+        t_old, t_new, (o, nw) = pair(lambda: eng.datamatrix(pages), lambda: eng.datamatrix_sizes(pages, ms))
+        same = bool(torch.equal(o[0], nw[0]) and torch.equal(o[2], nw[2]))
+        big = pages.clone()
+        text64, text144 = "64 x 64 " * 30, "144 x 144 record " * 80
+        for i in range(n_code):
+            page = big[i].cpu().numpy()
+            y = h // 3 + 520                               # below the four symbols of synth_dm_page; the band is cleared first
+            page[y - 20:y + 144 * 3 + 20, 20:900] = 255
+            synth.draw_dm(page, 40, y, synth.dm_encode(text64, dm.size_index_all(64, 64)), 3)
+            synth.draw_dm(page, 400, y, synth.dm_encode(text144, dm.size_index_all(144, 144)), 3, i % 4)
+            big[i] = torch.from_numpy(page).cuda()
+        t_old_big, t_new_big, (o, nw) = pair(lambda: eng.datamatrix(big), lambda: eng.datamatrix_sizes(big, ms))
+        rows, data, cnt2 = (t.cpu().numpy() for t in nw)
+        large = [e["content"] for i in range(args.pages) for e in dm.read_datamatrix(rows[i, :cnt2[i]], data[i, :cnt2[i]]) if e["rows"] >= 64]
+        res.update(max_size=ms, plain_datamatrix_ms=t_old, plain_datamatrix_sizes_ms=t_new, plain_rows_equal=same,
+                   plain_sizes_over_datamatrix=round(t_new["median"] / t_old["median"], 3),
+                   large_drawn=2 * n_code, large_read=len(large), large_read_right=sum(t in (text64, text144) for t in large),
+                   large_datamatrix_ms=t_old_big, large_datamatrix_sizes_ms=t_new_big,
+                   large_sizes_over_datamatrix=round(t_new_big["median"] / t_old_big["median"], 3),
+                   large_codes_old=int(o[2].sum()), large_codes_new=int(cnt2.sum()))
     print(json.dumps(res))
     eng.close()
 
