@@ -53,10 +53,27 @@ const char* lumina_ocr_version(void);
 int lumina_ocr_set_option(lumina_ocr_t* h, const char* key, int value);
 
 /* weights: "LOCW" container (ocr-system_amd/lumina_ocr/arch.py write_blob), host memory.
- * Replaces PaddleOCRVL(...) model construction (ocr_service_paddleocr_backup.py:204-253). */
+ * Replaces PaddleOCRVL(...) model construction (ocr_service_paddleocr_backup.py:204-253).
+ *
+ * Every lumina_ocr_load_*_weights first parses the whole container and checks every tensor the model reads (csrc/blob_check.h: name,
+ * dtype, rank, every dimension, byte count = dims x element size) and only then touches the engine.  A REFUSED BLOB LEAVES THE
+ * PREVIOUSLY LOADED MODEL OF THAT KIND INTACT AND RUNNABLE, BIT FOR BIT; on an engine that had none, the model stays "not loaded".
+ * The call returns 1 and lumina_ocr_last_error() gives "load_<kind>_weights: <reason> (tensor <name>)".  Reasons:
+ *   container : bad magic | unsupported version | truncated | truncated data | unknown dtype | rank out of range (1 .. 4) |
+ *               implausible dimension (0, above 2^28, or a product above 2^34) | byte count does not match the dimensions |
+ *               duplicate tensor name | trailing bytes
+ *   model     : missing tensor | wrong dtype | wrong rank | wrong dimension | class count out of range (the CTC heads take 2 .. 65536
+ *               classes; weight and bias must agree) | svtr.config value not a small whole number | svtr.config out of range (...)
+ * Where several tensors are wrong, the one whose name sorts first is named.  Layout of every conv / linear weight: OHWI
+ * [out][kh][kw][in] bf16 (depthwise [c][k][k][1], squeeze-excite [mid][1][1][c]); biases and LayerNorm vectors f32.
+ * Choices: tensors the model does not read are ignored (a duplicate name is refused even then); bytes after the last tensor are
+ * refused; the blob may lie at any address (one that is no multiple of 16 is copied to aligned storage for the duration of the call)
+ * and is not referenced after the call returns.  If a device allocation or upload fails after the check has passed, the model of that
+ * kind is not loaded on return and its forward refuses with "not loaded". */
 int lumina_ocr_load_det_weights(lumina_ocr_t* h, const void* blob, size_t nbytes);
 int lumina_ocr_load_rec_weights(lumina_ocr_t* h, const void* blob, size_t nbytes);
 int lumina_ocr_num_classes(const lumina_ocr_t* h);
+int lumina_ocr_model_loaded(const lumina_ocr_t* h, int kind);   /* 1 if the model is loaded: kind 0 det, 1 rec (CRNN), 2 cls, 3 SVTR */
 
 /* image -> tensor: xn = bf16(u8 * scale[c] + shift[c]), zero outside (valid_h, valid_w).
  * layout_nchw = 1 writes [N,3,Hp,Wp], 0 writes [N,Hp,Wp,3]. */
@@ -91,7 +108,8 @@ int lumina_ocr_rec_crop_oriented(lumina_ocr_t* h, const uint8_t* pages_dev, int 
 
 /* Text-line orientation classifier (PP-OCR `cls`, ch_ppocr_mobile_v2.0_cls; PaddleOCR's use_angle_cls): MobileNetV3-small x0.35 on
  * 48 x 192 crops -> conv 1x1 (200) -> 2x2 max pool -> mean -> FC(2) -> soft-max.  Blob: LOCW with the cls.* tensors of
- * lumina_ocr/arch.py make_cls_weights; every shape is checked as lumina_ocr_load_rec_weights checks its own. */
+ * lumina_ocr/arch.py make_cls_weights; checked before anything is touched, as lumina_ocr_load_det_weights states for every model:
+ * a refused blob leaves the previously loaded classifier intact and runnable, bit for bit. */
 int lumina_ocr_load_cls_weights(lumina_ocr_t* h, const void* blob, size_t nbytes);
 
 /* Orientation-classifier crops (PP-OCR `cls` input): the sampling of lumina_ocr_rec_crop, 48 rows, into crops_dev
@@ -521,7 +539,10 @@ int lumina_ocr_page_compose(lumina_ocr_t* h, const lumina_ocr_compose_layer* lay
  * `svtr.*` tensors of lumina_ocr/arch.py make_svtr_weights; the optional f32 tensor `svtr.config` = [dim0, dim1, dim2, depth0,
  * depth1, depth2, heads0, heads1, heads2, local_blocks, out_channels, dtype] selects the variant (absent: SVTR-Tiny, bf16;
  * Base = 128/256/384, 3/6/9, 4/8/12, 8 local blocks) and the storage / MFMA type (0 bf16, 1 fp16: v_mfma_f32_32x32x16_f16,
- * activations and weights stored as IEEE half); option "svtr_f16" (0 / 1, -1 = as the blob says) overrides the type at load time. */
+ * activations and weights stored as IEEE half); option "svtr_f16" (0 / 1, -1 = as the blob says) overrides the type at load time.  Every svtr.config value must be a
+ * whole number 0 .. 65536 (checked before it is converted: NaN, infinities and fractions are refused); dims 64 / 128 / 256 / 384 with
+ * 32-wide heads and dims[0] <= 128, depths 1 .. 32, local_blocks <= depth0 + depth1, out_channels 192, dtype 0 / 1.  The tensor list
+ * is derived from these values; refusals as lumina_ocr_load_det_weights states. */
 int lumina_ocr_load_svtr_weights(lumina_ocr_t* h, const void* blob, size_t nbytes);
 int lumina_ocr_svtr_forward(lumina_ocr_t* h, const uint8_t* crops_dev, const int32_t* widths_dev, int n_crops, int32_t* idx_dev, float* prob_dev,
                             void* stream);

@@ -201,6 +201,10 @@ int lumina_ocr_load_rec_weights(lumina_ocr_t* h, const void* blob, size_t nbytes
     API_TRY return eng_load_rec(h, blob, nbytes); API_CATCH(h)
 }
 int lumina_ocr_num_classes(const lumina_ocr_t* h) { return h ? h->num_classes : 0; }
+int lumina_ocr_model_loaded(const lumina_ocr_t* h, int kind) {
+    if (!h) return 0;
+    return kind == 0 ? h->det_loaded : kind == 1 ? h->rec_loaded : kind == 2 ? h->cls_loaded : kind == 3 ? h->svtr.loaded : false;
+}
 
 int lumina_ocr_normalize(lumina_ocr_t* h, const uint8_t* img_dev, int n, int height, int width, int hp, int wp, const float scale[3],
                          const float shift[3], int layout_nchw, uint16_t* out_dev, void* stream) {

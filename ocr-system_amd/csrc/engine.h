@@ -6,6 +6,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "blob_check.h"
 #include "common.h"
 #include "conv_mfma.h"
 #include "mbconv.h"
@@ -102,8 +103,6 @@ template <class Mem> struct Growable {
 // one timed launch (option time_convs): HIP events around it on its stream, its algorithmic work, and what ran
 struct LaunchRecord { Event e0, e1; double flop, bytes; std::string layer, kernel; };
 
-struct HostBlobTensor { int dtype; std::vector<int> dims; const uint8_t* data; size_t nbytes; };
-
 struct lumina_ocr {
     int device = 0;
     std::string err;
@@ -182,7 +181,6 @@ struct lumina_ocr {
 };
 
 int locr_fail(lumina_ocr* eng, const char* what, const char* detail);
-bool parse_blob(lumina_ocr* eng, const void* blob, size_t n, std::map<std::string, HostBlobTensor>* out);
 
 int eng_load_det(lumina_ocr* eng, const void* blob, size_t n);
 int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n);

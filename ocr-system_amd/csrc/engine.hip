@@ -33,34 +33,16 @@ hipError_t locr_dyn_lds(const void* kernel, int bytes) {
 }
 
 // ------------------------------------------------------------------------------ blob
-bool parse_blob(lumina_ocr* eng, const void* blob, size_t n, std::map<std::string, HostBlobTensor>* out) {
-    const uint8_t* b = static_cast<const uint8_t*>(blob);
-    if (n < 12 || memcmp(b, "LOCW", 4) != 0) { locr_fail(eng, "parse_blob", "bad magic"); return false; }
-    uint32_t ver, cnt;
-    memcpy(&ver, b + 4, 4); memcpy(&cnt, b + 8, 4);
-    if (ver != 1) { locr_fail(eng, "parse_blob", "unsupported version"); return false; }
-    size_t off = 12;
-    for (uint32_t i = 0; i < cnt; ++i) {
-        if (off + 2 > n) { locr_fail(eng, "parse_blob", "truncated"); return false; }
-        uint16_t ln; memcpy(&ln, b + off, 2); off += 2;
-        if (off + ln + 2 > n) { locr_fail(eng, "parse_blob", "truncated"); return false; }
-        std::string name(reinterpret_cast<const char*>(b + off), ln); off += ln;
-        HostBlobTensor t;
-        t.dtype = b[off]; const int nd = b[off + 1]; off += 2;
-        if (t.dtype > 1 || nd < 1 || nd > 4) { locr_fail(eng, "parse_blob: unknown dtype / rank", name.c_str()); return false; }
-        if (off + 4 * (size_t)nd + 8 > n) { locr_fail(eng, "parse_blob", "truncated"); return false; }
-        uint64_t count = 1;
-        for (int d = 0; d < nd; ++d) {
-            uint32_t v; memcpy(&v, b + off, 4); off += 4;
-            if (v == 0 || v > (1u << 28) || count * v > (1ull << 34)) { locr_fail(eng, "parse_blob: implausible dimension", name.c_str()); return false; }
-            count *= v; t.dims.push_back((int)v);
-        }
-        uint64_t nb; memcpy(&nb, b + off, 8); off += 8;
-        off += (16 - off % 16) % 16;
-        if (off > n || nb > n - off) { locr_fail(eng, "parse_blob", "truncated data"); return false; }   // (off + nb could wrap)
-        if (nb != count * (t.dtype ? 2u : 4u)) { locr_fail(eng, "parse_blob: byte count does not match the dimensions", name.c_str()); return false; }
-        t.data = b + off; t.nbytes = (size_t)nb; off += nb;
-        (*out)[name] = t;
+// What every eng_load_* does first (blob_check.h): parse, then check every tensor the loader will read.  On a refusal the engine is
+// untouched: the error names the reason and the tensor, and the model loaded before stays as it was.  `storage` keeps the aligned copy
+// of a blob that came at an address the loaders cannot read arrays from in place.
+static bool checked_blob(lumina_ocr* eng, const char* what, BlobKind kind, const void* blob, size_t n, std::vector<uint64_t>* storage, BlobMap* m) {
+    BlobError e;
+    if (blob == nullptr) { locr_fail(eng, what, "null blob"); return false; }
+    blob = blob_realign(blob, n, storage);
+    if (!blob_parse(blob, n, m, &e) || !check_blob(kind, *m, &e)) {
+        locr_fail(eng, what, (e.reason + (e.tensor.empty() ? "" : " (tensor " + e.tensor + ")")).c_str());
+        return false;
     }
     return true;
 }
@@ -101,7 +83,7 @@ static const bf16_t* zero_block(lumina_ocr* eng) {
 }
 
 static inline int rup(int v, int m) { return (v + m - 1) / m * m; }
-constexpr int CLS_H = 48, CLS_W = 192, CLS_FEAT = 200;   // classifier crop, conv2 channels (arch.CLS_*)
+constexpr int CLS_H = 48, CLS_W = 192;   // classifier crop (arch.CLS_*; CLS_FEAT, conv2's channels: blob_check.h)
 
 // ------------------------------------------------------------------------------ layer construction
 static bool get_wb(lumina_ocr* eng, const std::map<std::string, HostBlobTensor>& m, const std::string& name,
@@ -246,9 +228,11 @@ static int compose_fpn_p2(lumina_ocr* eng, const std::map<std::string, HostBlobT
 }
 
 int eng_load_det(lumina_ocr* eng, const void* blob, size_t n) {
-    std::map<std::string, HostBlobTensor> m;
-    if (!parse_blob(eng, blob, n, &m)) return 1;
+    BlobMap m;
+    std::vector<uint64_t> aligned;
+    if (!checked_blob(eng, "load_det_weights", BLOB_DET, blob, n, &aligned, &m)) return 1;
     LOCR_CHECK(hipSetDevice(eng->device));
+    eng->det_loaded = false;   // from here on only an upload can fail; the detector then stays unloaded
     eng->det.clear();
     RUN(load_stem(eng, m, "stem.conv1", 32, &eng->stem_wpk, &eng->stem_bias));   // (Cin = 3: dedicated kernel)
     auto add = [&](const std::string& name, int ks, int stride, int cin, int cout, int act) -> bool {
@@ -630,14 +614,7 @@ int eng_det_forward(lumina_ocr* eng, const uint8_t* pages, int B, int H, int W, 
 }
 
 // ------------------------------------------------------------------------------ rec
-static inline int cp16(int c) { return rup(c, 16); }
-static int make_div(double v, int d = 8) {
-    int nv = (int)(v + d / 2.0) / d * d;
-    if (nv < d) nv = d;
-    if (nv < 0.9 * v) nv += d;
-    return nv;
-}
-
+// (cp16, make_div and the MobileNetV3 rows: blob_check.h, which lists the tensors from them)
 static bool make_dw(lumina_ocr* eng, const std::map<std::string, HostBlobTensor>& m, const std::string& name, int k, int c_r, int c_p, DwLayer* L) {
     const HostBlobTensor *w, *b;
     if (!get_wb(eng, m, name, &w, &b)) return false;
@@ -677,17 +654,13 @@ static bool make_se(lumina_ocr* eng, const std::map<std::string, HostBlobTensor>
 // `scale`, vertical strides sh[11], input channels cin
 static int load_mv3_blocks(lumina_ocr* eng, const std::map<std::string, HostBlobTensor>& m, const std::string& prefix, double scale, const int* sh,
                            int cin, std::vector<RecBlock>* blocks) {
-    struct Row { int k, exp, c; bool se; int act; };
-    static const Row rows[11] = {{3, 16, 16, true, ACT_RELU},    {3, 72, 24, false, ACT_RELU},   {3, 88, 24, false, ACT_RELU},
-                                 {5, 96, 40, true, ACT_HSWISH},  {5, 240, 40, true, ACT_HSWISH}, {5, 240, 40, true, ACT_HSWISH},
-                                 {5, 120, 48, true, ACT_HSWISH}, {5, 144, 48, true, ACT_HSWISH}, {5, 288, 96, true, ACT_HSWISH},
-                                 {5, 576, 96, true, ACT_HSWISH}, {5, 576, 96, true, ACT_HSWISH}};
+    const Mv3Row* rows = MV3_ROWS;   // (blob_check.h: the tensor list check_blob holds the blob to is written from the same rows)
     blocks->clear();
     blocks->resize(11);
     for (int i = 0; i < 11; ++i) {
         RecBlock& B = (*blocks)[i];
         B.k = rows[i].k; B.cin = cin; B.exp = make_div(rows[i].exp * scale); B.cout = make_div(rows[i].c * scale);
-        B.se = rows[i].se; B.se_mid = B.exp / 4; B.stride_h = sh[i]; B.act = rows[i].act;
+        B.se = rows[i].se; B.se_mid = B.exp / 4; B.stride_h = sh[i]; B.act = rows[i].hswish ? ACT_HSWISH : ACT_RELU;
         B.res = (B.stride_h == 1 && B.cin == B.cout);
         const std::string p = prefix + ".b" + std::to_string(i);
         if (!make_conv(eng, m, p + ".expand", 1, 1, B.cin, B.exp, cp16(B.cin), cp16(B.exp), B.act, &B.expand)) return 1;
@@ -714,14 +687,15 @@ static int load_mv3_blocks(lumina_ocr* eng, const std::map<std::string, HostBlob
 }
 
 int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n) {
-    std::map<std::string, HostBlobTensor> m;
-    if (!parse_blob(eng, blob, n, &m)) return 1;
+    BlobMap m;
+    std::vector<uint64_t> aligned;
+    if (!checked_blob(eng, "load_rec_weights", BLOB_REC, blob, n, &aligned, &m)) return 1;
     LOCR_CHECK(hipSetDevice(eng->device));
-    const double scale = 0.5;
+    eng->rec_loaded = false;   // from here on only an upload can fail; the recogniser then stays unloaded
+    const double scale = REC_SCALE;
     const int c0 = make_div(16 * scale);
     RUN(load_stem(eng, m, "rec.conv1", c0, &eng->rstem_wpk, &eng->rstem_bias));
-    static const int sh[11] = {1, 2, 1, 2, 1, 1, 1, 1, 2, 1, 1};
-    if (load_mv3_blocks(eng, m, "rec", scale, sh, c0, &eng->rblocks)) return 1;
+    if (load_mv3_blocks(eng, m, "rec", scale, REC_STRIDES, c0, &eng->rblocks)) return 1;
     const int cin = eng->rblocks.back().cout;
     if (!make_conv(eng, m, "rec.conv2", 1, 1, cin, 288, cp16(cin), 288, ACT_HSWISH, &eng->rconv2)) return 1;
     eng->rconv2_spk = nullptr;
@@ -732,7 +706,9 @@ int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n) {
         if (!eng->rconv2_spk) return locr_fail(eng, "upload", "rec.conv2 (seq_gemm)");
     }
     // LSTM: x-projection of both directions as one GEMM; recurrent weights [2][4H][H]
-    const int Hh = 96;
+    // (check_blob has proved all six tensors of a layer: w_ih bf16 [4H][din], w_hh bf16 [4H][H], b f32 [4H], so the concatenations
+    // below are exactly [8H][din], [8H] and [2][4H][H], which is what make_conv, seq_gemm_pack_weights and lstm_kernel read)
+    const int Hh = LSTM_HIDDEN;
     for (int l = 0; l < 2; ++l) {
         const int din = l == 0 ? 288 : 2 * Hh;
         const std::string pf = "lstm.l" + std::to_string(l) + ".fw", pb = "lstm.l" + std::to_string(l) + ".bw";
@@ -740,7 +716,9 @@ int eng_load_rec(lumina_ocr* eng, const void* blob, size_t n) {
         auto hf = m.find(pf + ".w_hh"), hb = m.find(pb + ".w_hh");
         if (wf == m.end() || wb == m.end() || bf == m.end() || bb == m.end() || hf == m.end() || hb == m.end())
             return locr_fail(eng, "lstm tensors missing", pf.c_str());
-        if (wf->second.dims[0] != 4 * Hh || wf->second.dims[1] != din || hf->second.dims[1] != Hh) return locr_fail(eng, "lstm shape", pf.c_str());
+        if (wf->second.nbytes != (size_t)4 * Hh * din * 2 || wb->second.nbytes != wf->second.nbytes || bf->second.nbytes != (size_t)4 * Hh * 4 ||
+            bb->second.nbytes != bf->second.nbytes || hf->second.nbytes != (size_t)4 * Hh * Hh * 2 || hb->second.nbytes != hf->second.nbytes)
+            return locr_fail(eng, "lstm shape", pf.c_str());   // (an assertion: check_blob has refused such a blob already)
         // synthesise a 1x1 conv blob entry [8H][1][1][din]
         std::vector<uint8_t> wcat(wf->second.nbytes + wb->second.nbytes), bcat(bf->second.nbytes + bb->second.nbytes);
         memcpy(wcat.data(), wf->second.data, wf->second.nbytes); memcpy(wcat.data() + wf->second.nbytes, wb->second.data, wb->second.nbytes);
@@ -886,15 +864,15 @@ int eng_rec_forward(lumina_ocr* eng, const uint8_t* crops, const int* widths, in
 // MobileNetV3-small x0.35 (arch.cls_block_table: the recogniser's blocks, vertical strides 2 on blocks 0, 1, 3, 8) on 48 x 192 crops:
 // 24 x 96 after the stem, 2 x 96 after block 10 -> conv2 (1x1, 200, hswish) -> 2x2 max pool -> 48 positions -> cls_head_kernel
 int eng_load_cls(lumina_ocr* eng, const void* blob, size_t n) {
-    std::map<std::string, HostBlobTensor> m;
-    if (!parse_blob(eng, blob, n, &m)) return 1;
+    BlobMap m;
+    std::vector<uint64_t> aligned;
+    if (!checked_blob(eng, "load_cls_weights", BLOB_CLS, blob, n, &aligned, &m)) return 1;
     LOCR_CHECK(hipSetDevice(eng->device));
-    eng->cls_loaded = false;
-    const double scale = 0.35;
+    eng->cls_loaded = false;   // from here on only an upload can fail; the classifier then stays unloaded
+    const double scale = CLS_SCALE;
     const int c0 = make_div(16 * scale);
     RUN(load_stem(eng, m, "cls.conv1", c0, &eng->cstem_wpk, &eng->cstem_bias));
-    static const int sh[11] = {2, 2, 1, 2, 1, 1, 1, 1, 2, 1, 1};
-    if (load_mv3_blocks(eng, m, "cls", scale, sh, c0, &eng->cblocks)) return 1;
+    if (load_mv3_blocks(eng, m, "cls", scale, CLS_STRIDES, c0, &eng->cblocks)) return 1;
     const int cin = eng->cblocks.back().cout;
     if (!make_conv(eng, m, "cls.conv2", 1, 1, cin, CLS_FEAT, cp16(cin), cp16(CLS_FEAT), ACT_HSWISH, &eng->cconv2)) return 1;
     {
@@ -983,19 +961,18 @@ static bool make_linear(lumina_ocr* eng, const std::map<std::string, HostBlobTen
 }
 
 int eng_load_svtr(lumina_ocr* eng, const void* blob, size_t n) {
-    std::map<std::string, HostBlobTensor> m;
-    if (!parse_blob(eng, blob, n, &m)) return 1;
+    BlobMap m;
+    std::vector<uint64_t> aligned;
+    if (!checked_blob(eng, "load_svtr_weights", BLOB_SVTR, blob, n, &aligned, &m)) return 1;
+    SvtrConfig cfg;
+    BlobError ce;
+    if (!blob_svtr_config(m, &cfg, &ce)) return locr_fail(eng, "load_svtr_weights", ce.reason.c_str());   // (check_blob has run it already)
     LOCR_CHECK(hipSetDevice(eng->device));
     SvtrModel& M = eng->svtr;
-    M = SvtrModel();
-    {   // variant + storage type
-        auto it = m.find("svtr.config");
-        if (it != m.end()) {
-            if (it->second.dtype != 0 || it->second.dims.size() != 1 || it->second.dims[0] != 12) return locr_fail(eng, "svtr.config", "expected 12 f32 values");
-            const float* c = reinterpret_cast<const float*>(it->second.data);
-            for (int i = 0; i < 3; ++i) { M.dims[i] = (int)c[i]; M.depths[i] = (int)c[3 + i]; M.heads[i] = (int)c[6 + i]; }
-            M.local_blocks = (int)c[9]; M.out_ch = (int)c[10]; M.dtype = (int)c[11] != 0;
-        }
+    M = SvtrModel();   // loaded = false: from here on only an upload can fail; the model then stays unloaded
+    {   // variant + storage type, validated by blob_svtr_config before any cast (the tests below are assertions now)
+        for (int i = 0; i < 3; ++i) { M.dims[i] = cfg.dims[i]; M.depths[i] = cfg.depths[i]; M.heads[i] = cfg.heads[i]; }
+        M.local_blocks = cfg.local_blocks; M.out_ch = cfg.out_ch; M.dtype = cfg.dtype;
         if (eng->svtr_f16 >= 0) M.dtype = eng->svtr_f16;
         for (int i = 0; i < 3; ++i) {
             const int d = M.dims[i];

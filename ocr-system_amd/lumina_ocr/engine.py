@@ -27,6 +27,9 @@ class EngineUnavailable(RuntimeError):
     pass
 
 
+_MODEL_KINDS = ("det", "rec", "cls", "svtr")   # lumina_ocr_model_loaded's kind
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -54,6 +57,7 @@ def load_library() -> ctypes.CDLL:
         "lumina_ocr_load_det_weights": (i32, [vp, vp, sz]),
         "lumina_ocr_load_rec_weights": (i32, [vp, vp, sz]),
         "lumina_ocr_num_classes": (i32, [vp]),
+        "lumina_ocr_model_loaded": (i32, [vp, i32]),
         "lumina_ocr_normalize": (i32, [vp, vp, i32, i32, i32, i32, i32, c.POINTER(f32), c.POINTER(f32), i32, vp, vp]),
         "lumina_ocr_det_forward": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp]),
         "lumina_ocr_det_postprocess": (i32, [vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, i32, i32, vp, vp, vp, vp]),
@@ -150,7 +154,7 @@ def load_library() -> ctypes.CDLL:
 
 EXPORTED_SYMBOLS = [
     "lumina_ocr_create", "lumina_ocr_destroy", "lumina_ocr_last_error", "lumina_ocr_version", "lumina_ocr_set_option",
-    "lumina_ocr_load_det_weights", "lumina_ocr_load_rec_weights", "lumina_ocr_num_classes", "lumina_ocr_normalize",
+    "lumina_ocr_load_det_weights", "lumina_ocr_load_rec_weights", "lumina_ocr_num_classes", "lumina_ocr_model_loaded", "lumina_ocr_normalize",
     "lumina_ocr_det_forward", "lumina_ocr_det_postprocess", "lumina_ocr_rec_crop", "lumina_ocr_rec_crop_oriented", "lumina_ocr_cls_crop",
     "lumina_ocr_load_cls_weights", "lumina_ocr_cls_forward", "lumina_ocr_rec_forward",
     "lumina_ocr_ctc_decode", "lumina_ocr_ctc_decode_words", "lumina_ocr_conv2d", "lumina_ocr_read_tap", "lumina_ocr_conv_timing", "lumina_ocr_conv_timing_detail",
@@ -553,36 +557,38 @@ class Engine:
         return self.lib.lumina_ocr_version().decode()
 
     # -- weights --------------------------------------------------------------------------
-    def load_det(self, weights):
+    def _load(self, kind: str, weights, _offset: int = 0):
+        """One LOCW blob (or a weight dict, written as one) into the model `kind`.  The engine checks every tensor before it touches the
+        model (csrc/blob_check.h): a refused blob raises EngineError naming the reason and the tensor and leaves the model loaded
+        before intact.  The Python-side flags follow the engine's, whatever the outcome.  _offset: bytes the blob is shifted from an
+        aligned address (tests)."""
         blob = weights if isinstance(weights, (bytes, bytearray)) else arch.write_blob(weights)
-        buf = ctypes.create_string_buffer(bytes(blob), len(blob))
-        self._chk(self.lib.lumina_ocr_load_det_weights(self._h, ctypes.cast(buf, ctypes.c_void_p), len(blob)))
-        self.det_loaded = True
+        buf = ctypes.create_string_buffer(len(blob) + _offset)
+        ctypes.memmove(ctypes.addressof(buf) + _offset, bytes(blob), len(blob))
+        setattr(self, kind + "_loaded", False)
+        try:
+            self._chk(getattr(self.lib, "lumina_ocr_load_%s_weights" % kind)(self._h, ctypes.c_void_p(ctypes.addressof(buf) + _offset), len(blob)))
+        finally:
+            setattr(self, kind + "_loaded", bool(self.lib.lumina_ocr_model_loaded(self._h, _MODEL_KINDS.index(kind))))
+            self.num_classes = self.lib.lumina_ocr_num_classes(self._h)
+            self.svtr_num_classes = self.lib.lumina_ocr_svtr_num_classes(self._h)
+            self.svtr_dtype = "f16" if self.lib.lumina_ocr_svtr_dtype(self._h) else "bf16"
 
-    def load_rec(self, weights):
-        blob = weights if isinstance(weights, (bytes, bytearray)) else arch.write_blob(weights)
-        buf = ctypes.create_string_buffer(bytes(blob), len(blob))
-        self._chk(self.lib.lumina_ocr_load_rec_weights(self._h, ctypes.cast(buf, ctypes.c_void_p), len(blob)))
-        self.num_classes = self.lib.lumina_ocr_num_classes(self._h)
-        self.rec_loaded = True
+    def load_det(self, weights, _offset: int = 0):
+        self._load("det", weights, _offset)
 
-    def load_cls(self, weights):
+    def load_rec(self, weights, _offset: int = 0):
+        self._load("rec", weights, _offset)
+
+    def load_cls(self, weights, _offset: int = 0):
         """Orientation-classifier weights (arch.make_cls_weights or a LOCW blob with the cls.* tensors)."""
-        blob = weights if isinstance(weights, (bytes, bytearray)) else arch.write_blob(weights)
-        buf = ctypes.create_string_buffer(bytes(blob), len(blob))
-        self._chk(self.lib.lumina_ocr_load_cls_weights(self._h, ctypes.cast(buf, ctypes.c_void_p), len(blob)))
-        self.cls_loaded = True
+        self._load("cls", weights, _offset)
 
-    def load_svtr(self, weights, f16=None):
+    def load_svtr(self, weights, f16=None, _offset: int = 0):
         """SVTR recogniser weights (arch.make_svtr_weights or a LOCW blob with the svtr.* tensors): Tiny or Base, bf16 or fp16 as the
         blob's svtr.config says; f16 = True / False overrides the storage / MFMA type."""
         self.set_option("svtr_f16", -1 if f16 is None else int(bool(f16)))
-        blob = weights if isinstance(weights, (bytes, bytearray)) else arch.write_blob(weights)
-        buf = ctypes.create_string_buffer(bytes(blob), len(blob))
-        self._chk(self.lib.lumina_ocr_load_svtr_weights(self._h, ctypes.cast(buf, ctypes.c_void_p), len(blob)))
-        self.svtr_loaded = True
-        self.svtr_num_classes = self.lib.lumina_ocr_svtr_num_classes(self._h)
-        self.svtr_dtype = "f16" if self.lib.lumina_ocr_svtr_dtype(self._h) else "bf16"
+        self._load("svtr", weights, _offset)
 
     # -- hot path -------------------------------------------------------------------------
     def normalize(self, img, hp: int, wp: int, scale, shift, nchw: bool = False):

@@ -104,17 +104,22 @@ def test_dispatch_matches_the_recording(engine, dense_det_weights, rec_weights):
 
 
 def test_malformed_stem_tensor_fails_with_a_message(engine, det_weights, rec_weights):
-    """One loader serves the three 3-channel stems with the classifier's checks: a weight of another rank and a bias of another length
-    are refused by name (the recogniser and the detector used to read past them)."""
+    """A stem weight of another rank and a stem bias of another length are refused with the reason and the tensor's name (the recogniser
+    and the detector used to read past them), by the check every loader runs before it touches the engine (csrc/blob_check.h): the
+    models loaded before stay loaded."""
     from lumina_ocr.engine import EngineError
     bad_rec = dict(rec_weights)
     bad_rec["rec.conv1.w"] = rec_weights["rec.conv1.w"].reshape(rec_weights["rec.conv1.w"].shape[0], 27)
-    with pytest.raises(EngineError, match="rec.conv1: shape"):
+    engine.load_rec(rec_weights)
+    with pytest.raises(EngineError, match=r"load_rec_weights: wrong rank \(tensor rec\.conv1\.w\)"):
         engine.load_rec(bad_rec)
+    assert engine.rec_loaded
     bad_det = dict(det_weights)
     bad_det["stem.conv1.b"] = det_weights["stem.conv1.b"][:16]
     try:
-        with pytest.raises(EngineError, match="stem.conv1: shape"):
+        engine.load_det(det_weights)
+        with pytest.raises(EngineError, match=r"load_det_weights: wrong dimension \(tensor stem\.conv1\.b\)"):
             engine.load_det(bad_det)
+        assert engine.det_loaded
     finally:
-        engine.load_det(det_weights)   # (the refused load had already dropped the detector's layers)
+        engine.load_det(det_weights)
